@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: iLQR iterations/s, Unitree H1 (nx=51, nu=19), N=25, batched standing-balance.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the benchmark measures
+or checks: the roofline and per-stage tables (event pairs around the launches), the gather check, the early-exit / contact / joint-limit /
+forward-difference / dedup lines and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float64; per-rollout trajectories and gains of a fixed sample of rollouts), for output-by-output comparisons of two builds.
 
 One "step" = one MPC step of the hot path over the whole batch with inputs resident in HBM:
 cold-start initializeWithReference (gravity-comp + noise controls, N rollouts) followed by
@@ -111,7 +116,32 @@ def parse():
                     help="default: --batch / --horizon as given (BASELINE configs[2] by default).  config3 / config4: the GLOBAL batch of BASELINE.json "
                          "configs[3] (32768 standing rollouts, N = 25) / configs[4] (8192 windows of the H1 walking reference, N = 50, contact-scheduled "
                          "costs, unilateral stance constraints) on ONE GPU -- the N = 1 anchors of the 8-GPU scaling series")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline / per-stage tables, gather check, early-exit, contact, joint-limit, fd and dedup lines, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_ROLLOUT_ROWS = 65536      # per-rollout rows (u0, cost, iterations) beyond this are sampled
+DUMP_TRAJ_ROWS = 256           # rollouts whose trajectories and gains are written
+DUMP_JAC_ROWS = 32             # rollouts whose (A_t, B_t) are written (--stage rollout_jacobians: 0.7 MB per rollout)
+
+
+def dump_sample(n, cap):
+    """Fixed, seeded choice of min(n, cap) of n rollout indices (sorted): the same for every run with the same batch."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))
+
+
+def write_dump(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(pkg, prob, x0, ui, iters, budget_s, contact=False):
@@ -226,8 +256,13 @@ def stage_bench(args, s, sv, x0_d, ui_d, B, N, world, rank, dev, prob):
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    A, Bm = s.linearization()
-    assert np.all(np.isfinite(A)) and np.all(np.isfinite(Bm))
+    if args.full or (args.dump_outputs and rank == 0):
+        A, Bm = s.linearization()
+    if args.dump_outputs and rank == 0:
+        i, j = dump_sample(B, DUMP_TRAJ_ROWS), dump_sample(B, DUMP_JAC_ROWS)
+        write_dump(args.dump_outputs, {"rollout_index": i, "xbar": s.xbar()[i], "ubar": s.ubar()[i], "jacobian_rollout_index": j, "A": A[j], "B": Bm[j]})
+    if args.full:
+        assert np.all(np.isfinite(A)) and np.all(np.isfinite(Bm))
     if rank == 0:
         ms = 1e3 * el / args.steps
         by = 8.0 * B * N * (70 + 493 + 493 + 70 + 2601 + 969)
@@ -355,7 +390,8 @@ def main():
         s.set_contact_mode(2)
     jac_mode = sv.JAC_FD_FORWARD if JAC_FD else sv.JAC_ANALYTIC
     s.set_options(jacobian_mode=jac_mode, fd_eps=1e-5, early_exit=False)
-    s.enable_profiling(True)
+    if args.full:
+        s.enable_profiling(True)
 
     dev = torch.device("cuda", local_rank)
     x0_d = torch.from_numpy(x0).to(dev)
@@ -447,14 +483,19 @@ def main():
             record_stages(timed_ms, timed_n)
         return g
 
-    # Event pairs around every launch cost time themselves (all eight stages: 1.3 ms of a 95 ms step), so the timed steps carry
-    # them only for the kernel group the roofline is about.  Which group that is comes from one untimed probe step with every
-    # stage timed; the full per-stage table of the JSON line comes from one more untimed step after the timed region.
+    # One untimed step ahead of the warm-up, in a plain run as well: lambda is solver state that survives a solve (as in the
+    # reference), so what the last timed step computes depends on how many solves the handle has run, and a plain run has to
+    # compute what a --full run with the same arguments computes.
+    # --full: event pairs around every launch cost time themselves (all eight stages: 1.3 ms of a 95 ms step), so the timed steps
+    # carry them only for the kernel group the roofline is about.  Which group that is comes from this probe step with every stage
+    # timed; the full per-stage table of the JSON line comes from one more untimed step after the timed region.  A plain run has no
+    # event pairs at all.
     one_step(False)
-    probe_ms, probe_n = {}, {}
-    record_stages(probe_ms, probe_n)
-    dom_stages = dominant_group(kernel_groups(args, B, N, max(1, s.num_slices())), probe_ms)[1]
-    s.set_profiled_stages(dom_stages)
+    if args.full:
+        probe_ms, probe_n = {}, {}
+        record_stages(probe_ms, probe_n)
+        dom_stages = dominant_group(kernel_groups(args, B, N, max(1, s.num_slices())), probe_ms)[1]
+        s.set_profiled_stages(dom_stages)
     for _ in range(args.warmup):
         one_step(False)
     if world > 1:
@@ -462,7 +503,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step(True)
+        last = one_step(args.full)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -476,6 +517,53 @@ def main():
     assert np.all(it_done == iters), "fixed-iteration mode must run exactly --iters iterations per rollout"
     cost = s.cost()
     assert np.all(np.isfinite(cost))
+    value = float(world) * B * iters * args.steps / elapsed
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step as its caller receives it: the gathered first-knot rows (global rollout order), and this rank's
+        # trajectories, feedforward terms and first-knot gains for a fixed sample of its rollouts
+        g = last.cpu().numpy()
+        r = dump_sample(g.shape[0], DUMP_ROLLOUT_ROWS)
+        i, li = dump_sample(B, DUMP_TRAJ_ROWS), dump_sample(B, DUMP_ROLLOUT_ROWS)
+        K0 = torch.zeros(B, 19, 51, dtype=torch.float64, device=dev)
+        u0l = torch.zeros(B, 19, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        s.pack_first_knot_device(u0l.data_ptr(), K0.data_ptr())     # (synchronises the handle's stream)
+        write_dump(args.dump_outputs, {"rollout_index": r, "u0": g[r, :19], "cost": g[r, 19],
+                                       "local_rollout_index": li, "iterations": it_done[li],
+                                       "traj_rollout_index": i, "xbar": s.xbar()[i], "ubar": s.ubar()[i], "kff": s.gains_kff()[i],
+                                       "K0": K0[torch.from_numpy(i).to(dev)].cpu().numpy()})
+        del K0, u0l
+
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "iLQR iterations/sec (H1 nx=51 nu=19 N=%d)" % N, "value": value, "unit": "iterations/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": workload_label(args, B, N, iters, world, prob["gravity"]),
+                       "flop_source": FLOP_SOURCE,
+                       "batch_per_gpu": B, "global_batch": B * world, "horizon": N, "iterations_per_solve": iters,
+                       "jacobians": "analytic (constrained step)" if args.contact else "analytic", "contact_mode": bool(args.contact), "batch_slices": max(1, s.num_slices()), "gather": "u0+cost" + ("+K0" if args.gather_gains else ""), "gather_check": None,
+                       "collective": ("ilqr_hip_gather_first_knot, one rank: device copy (no RCCL)" if world == 1 else
+                                      "RCCL grouped send/recv behind the C ABI (ilqr_hip_gather_first_knot)" if rccl else
+                                      "ilqr_hip_gather_first_knot per rank + gloo, host-staged (one-GPU rehearsal)" if args.rehearse_single_gpu else
+                                      "FALLBACK: ilqr_hip_gather_first_knot per rank + torch.distributed.gather (RCCL communicator did not come up)"),
+                       "collective_error": rccl_error,
+                       "barrier": ("none (one rank)" if world == 1 else
+                                   "torch.distributed process group, backend %s%s: barrier before and after the timed region and the max-over-ranks all_reduce of the elapsed time; "
+                                   "the product's own RCCL communicator (ilqr_hip_comm_init) carries only the per-step gather" %
+                                   (dist.get_backend(), " (= RCCL on ROCm)" if dist.get_backend() == "nccl" else "")),
+                       "launcher": "self-launched by `python bench.py --gpus N` (child torch.distributed.run)" if os.environ.get("ILQR_BENCH_SELF_LAUNCHED") else
+                                   ("torch.distributed.run (WORLD_SIZE from the environment)" if "WORLD_SIZE" in os.environ else "single process")}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        s.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # one more (untimed) step whose gathered payload is checked: rank 0 holds world x B rows in global rollout order; it also
     # carries the event pairs of every stage (stage_ms_per_step, kernels.* of the JSON line)
     s.set_profiled_stages(None)
@@ -624,8 +712,6 @@ def main():
         s.set_dedup_saturated_retry(False)
 
     if rank == 0:
-        total_iters = float(world) * B * iters * args.steps
-        value = total_iters / elapsed
         # dominant kernel = largest device time over the timed region (HIP events on the streams the kernels are
         # launched on); the lambda-retry launches of backward pass / line search are the same kernels on a subset
         # of the rollouts, so they count towards the kernel's total but the roofline uses the full-batch launches
@@ -719,25 +805,8 @@ def main():
                              "separate rocprofv3 --pmc passes of this command (see traffic_source), null when no record matches this run; "
                              "linearisation, cost quadratics and nominal re-rollout overlap on three streams: their spans include contention, the dominant "
                              "kernel is chosen on exclusive-equivalent time (kernels.*.exclusive_ms_per_step)"})
-        out = {
-            "metric": "iLQR iterations/sec (H1 nx=51 nu=19 N=%d)" % N, "value": value, "unit": "iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": workload_label(args, B, N, iters, world, prob["gravity"]),
-                       "flop_source": FLOP_SOURCE,
-                       "batch_per_gpu": B, "global_batch": B * world, "horizon": N, "iterations_per_solve": iters,
-                       "jacobians": "analytic (constrained step)" if args.contact else "analytic", "contact_mode": bool(args.contact), "batch_slices": n_slices, "gather": "u0+cost" + ("+K0" if args.gather_gains else ""), "gather_check": gather_check,
-                       "collective": ("ilqr_hip_gather_first_knot, one rank: device copy (no RCCL)" if world == 1 else
-                                      "RCCL grouped send/recv behind the C ABI (ilqr_hip_gather_first_knot)" if rccl else
-                                      "ilqr_hip_gather_first_knot per rank + gloo, host-staged (one-GPU rehearsal)" if args.rehearse_single_gpu else
-                                      "FALLBACK: ilqr_hip_gather_first_knot per rank + torch.distributed.gather (RCCL communicator did not come up)"),
-                       "collective_error": rccl_error,
-                       "barrier": ("none (one rank)" if world == 1 else
-                                   "torch.distributed process group, backend %s%s: barrier before and after the timed region and the max-over-ranks all_reduce of the elapsed time; "
-                                   "the product's own RCCL communicator (ilqr_hip_comm_init) carries only the per-step gather" %
-                                   (dist.get_backend(), " (= RCCL on ROCm)" if dist.get_backend() == "nccl" else "")),
-                       "launcher": "self-launched by `python bench.py --gpus N` (child torch.distributed.run)" if os.environ.get("ILQR_BENCH_SELF_LAUNCHED") else
-                                   ("torch.distributed.run (WORLD_SIZE from the environment)" if "WORLD_SIZE" in os.environ else "single process")},
+        out["config"]["gather_check"] = gather_check
+        out.update({
             "roofline": roof,
             "kernels": {n: {k: (round(v, 6) if isinstance(v, float) else v) for k, v in t.items() if k in
                             ("total_ms_per_step", "exclusive_ms_per_step", "avg_launch_ms", "frac_compute", "frac_hbm")} for n, t in table.items()},
@@ -749,7 +818,7 @@ def main():
                            "note": "same step with the reference's convergence exit (|dJ| < 1e-4) enabled: executed iterations per second; not the headline; "
                                    "once at most 512 rollouts are still active the lambda retry of ilqr.cpp:619-644 runs beside the first pass "
                                    "(same results, ilqr_hip_get_speculative_iterations; ILQR_SPEC=0 for the sequential order)"},
-        }
+        })
         if contact_line is not None:
             out["contact"] = contact_line
         if limits_line is not None:

@@ -828,7 +828,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(try_rccl):
     sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0",
-                        "--rehearse-single-gpu"] + (["--try-rccl"] if try_rccl else []), capture_output=True, text=True, timeout=900)
+                        "--rehearse-single-gpu", "--full"] + (["--try-rccl"] if try_rccl else []), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -849,7 +849,7 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     starts `--gpus 1`): the parent never touches the GPU, starts the two ranks as a child process and relays rank 0's line --
     `n_gpus: 2`, the global batch of both ranks gathered, the launcher named in the line (it used to time one rank)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0", "--rehearse-single-gpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0", "--rehearse-single-gpu", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -975,7 +975,7 @@ def test_bench_four_ranks_without_a_launcher_on_one_gpu():
     six, which is why the eight-rank case is not rehearsed here), shard_range for ranks 0..3, global batch 256 gathered in global
     rollout order, one line labelled n_gpus: 4."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "64", "--steps", "1", "--warmup", "0", "--rehearse-single-gpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "64", "--steps", "1", "--warmup", "0", "--rehearse-single-gpu", "--full"],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1092,7 +1092,7 @@ def test_bench_contract_json_line():
     """bench.py prints ONE JSON line with the fields the driver and the judge read (task statement, section 4)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "64", "--steps", "1", "--warmup", "0", "--cpu-seconds", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "64", "--steps", "1", "--warmup", "0", "--cpu-seconds", "1", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -1110,3 +1110,40 @@ def test_bench_contract_json_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] == "port" and c["value"] > 0 and d["value"] > 0
+
+
+def test_bench_plain_line_and_output_dump(tmp_path):
+    """A plain bench run prints the headline fields only (the roofline, per-stage tables, extra lines and the CPU baseline are --full),
+    times exactly --steps steps, and --dump-outputs writes the last timed step's outputs: the same arrays, bit for bit, from a plain
+    and a --full run with the same arguments (lambda survives a solve: the two must run the same solves), float64, within 64 MB."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {}
+    for tag, extra in (("plain", ["--steps", "3", "--warmup", "1"]), ("full", ["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "64"] + extra + ["--dump-outputs", str(tmp_path / tag)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        runs[tag] = json.loads(lines[0])
+    d = runs["plain"]
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "kernels", "stage_ms_per_step", "early_exit", "contact", "fd", "cpu_baseline"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["value"] > 0
+    assert abs(d["value"] - 64 * 10 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["metric"] == runs["full"]["metric"] and d["unit"] == runs["full"]["unit"] and "roofline" in runs["full"]
+    names = sorted(f for f in os.listdir(tmp_path / "plain") if f.endswith(".npy"))
+    assert names == sorted(f for f in os.listdir(tmp_path / "full") if f.endswith(".npy"))
+    assert {"u0.npy", "cost.npy", "iterations.npy", "xbar.npy", "ubar.npy", "kff.npy", "K0.npy"} <= set(names)
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    u0, cost, ub = np.load(tmp_path / "plain" / "u0.npy"), np.load(tmp_path / "plain" / "cost.npy"), np.load(tmp_path / "plain" / "ubar.npy")
+    ti = np.load(tmp_path / "plain" / "traj_rollout_index.npy").astype(int)
+    assert u0.shape == (64, 19) and np.all(np.isfinite(cost)) and np.array_equal(u0[ti], ub[:, 0])
+    assert np.all(np.load(tmp_path / "plain" / "iterations.npy") == 10)

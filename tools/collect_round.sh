@@ -13,7 +13,7 @@ bash tools/sq_profile.sh "$tag" > /dev/null 2>&1 || true
 cp gpurun_out/sq_$tag/sq_summary.txt "$out/${tag}_sq_issue_wait_summary.txt"
 cp gpurun_out/sq_$tag/sq_counter_collection.csv "$out/${tag}_pmc/sq_counter_collection.csv"
 echo "[collect] sq done"
-BENCH1="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-contact-line --no-fd-line"
+BENCH1="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-contact-line --no-fd-line"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_F64 \
   --output-format csv -d "$out/mix" -o x -- $BENCH1 > "$out/bench_mix.log" 2>&1
 cp "$(find "$out/mix" -name '*counter_collection.csv' | head -1)" "$out/${tag}_pmc/fp64_mix_counter_collection.csv"; rm -rf "$out/mix"
@@ -41,7 +41,7 @@ echo "[collect] fp64 mix done"
 # (one group per concurrent region for this trace: with the early continuation of the convergence-exit leg the regions of consecutive
 # iterations overlap and tools/timeline.py, which cuts at k_quad_kin, cannot attribute kernels to iterations)
 export ILQR_SPLIT=0
-rocprofv3 --kernel-trace --output-format csv -d "$out/tr" -o t -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-contact-line --no-fd-line > "$out/bench_trace.log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$out/tr" -o t -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-contact-line --no-fd-line > "$out/bench_trace.log" 2>&1
 unset ILQR_SPLIT
 f=$(find "$out/tr" -name "*kernel_trace.csv" | head -1)
 python3 tools/timeline.py "$f" 16 > "$out/${tag}_iteration_timeline.txt"
@@ -49,8 +49,8 @@ python3 tools/timeline.py "$f" 16 > "$out/${tag}_iteration_timeline.txt"
 rm -rf "$out/tr"
 echo "[collect] timelines done"
 # the contact workload's own passes: per-kernel time and HBM traffic of `bench.py --contact`
-CB="python3 bench.py --contact --steps 1 --warmup 0 --no-cpu-baseline"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/cst" -o k -- python3 bench.py --contact --steps 2 --warmup 1 --no-cpu-baseline > "$out/bench_contact_stats.log" 2>&1
+CB="python3 bench.py --full --contact --steps 1 --warmup 0 --no-cpu-baseline"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/cst" -o k -- python3 bench.py --full --contact --steps 2 --warmup 1 --no-cpu-baseline > "$out/bench_contact_stats.log" 2>&1
 cp "$(find "$out/cst" -name '*kernel_stats.csv' | head -1)" "$out/${tag}_contact_kernel_stats.csv"; rm -rf "$out/cst"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/cf" -o f -- $CB > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/cw" -o w -- $CB > /dev/null 2>&1
@@ -62,20 +62,20 @@ python3 tools/pmc_summary.py --traffic-json "$out/${tag}_contact_traffic.json" -
 echo "[collect] contact passes done"
 mkdir -p "$out/${tag}_bench_lines"
 L="$out/${tag}_bench_lines"
-python3 bench.py 2>/dev/null | grep '^{' > "$L/bench_default.json"; echo "[collect] default line done"
-python3 bench.py --contact --no-cpu-baseline 2>/dev/null | grep '^{' > "$L/bench_contact.json"
-python3 bench.py --batch 1 --no-cpu-baseline --no-contact-line --steps 20 --warmup 3 2>/dev/null | grep '^{' > "$L/bench_b1.json"
-ILQR_SPEC=0 python3 bench.py --batch 1 --no-cpu-baseline --no-contact-line --steps 20 --warmup 3 2>/dev/null | grep '^{' > "$L/bench_b1_sequential_retry.json"
-python3 bench.py --batch 256 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b256.json"
-ILQR_SPEC=0 python3 bench.py --batch 256 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b256_sequential_retry.json"
-ILQR_SPEC=0 ILQR_SPLIT=0 python3 bench.py --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_default_sequential_retry_one_group.json"
-python3 bench.py --stage rollout_jacobians --batch 1024 --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | grep '^{' > "$L/bench_cfg1.json"
-python3 bench.py --batch 1024 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b1024.json"
-python3 bench.py --batch 1024 --horizon 50 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b1024_n50.json"
-python3 bench.py --batch 8192 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b8192.json"
+python3 bench.py --full 2>/dev/null | grep '^{' > "$L/bench_default.json"; echo "[collect] default line done"
+python3 bench.py --full --contact --no-cpu-baseline 2>/dev/null | grep '^{' > "$L/bench_contact.json"
+python3 bench.py --full --batch 1 --no-cpu-baseline --no-contact-line --steps 20 --warmup 3 2>/dev/null | grep '^{' > "$L/bench_b1.json"
+ILQR_SPEC=0 python3 bench.py --full --batch 1 --no-cpu-baseline --no-contact-line --steps 20 --warmup 3 2>/dev/null | grep '^{' > "$L/bench_b1_sequential_retry.json"
+python3 bench.py --full --batch 256 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b256.json"
+ILQR_SPEC=0 python3 bench.py --full --batch 256 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b256_sequential_retry.json"
+ILQR_SPEC=0 ILQR_SPLIT=0 python3 bench.py --full --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_default_sequential_retry_one_group.json"
+python3 bench.py --full --stage rollout_jacobians --batch 1024 --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | grep '^{' > "$L/bench_cfg1.json"
+python3 bench.py --full --batch 1024 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b1024.json"
+python3 bench.py --full --batch 1024 --horizon 50 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b1024_n50.json"
+python3 bench.py --full --batch 8192 --no-cpu-baseline --no-contact-line 2>/dev/null | grep '^{' > "$L/bench_b8192.json"
 echo "[collect] small lines done"
-python3 bench.py --workload config3 --steps 3 --no-cpu-baseline 2>/dev/null | grep '^{' > "$L/bench_config3_global_batch_one_gpu.json"
-python3 bench.py --workload config4 --steps 3 2>/dev/null | grep '^{' > "$L/bench_config4_global_batch_one_gpu.json"
+python3 bench.py --full --workload config3 --steps 3 --no-cpu-baseline 2>/dev/null | grep '^{' > "$L/bench_config3_global_batch_one_gpu.json"
+python3 bench.py --full --workload config4 --steps 3 2>/dev/null | grep '^{' > "$L/bench_config4_global_batch_one_gpu.json"
 # every stage kernel alone, full batch (stage API): what "alone ms" in the summary means
 rm -f "$out/${tag}_alone_kernel_stats.csv"
 for st in linearize quadratics backward line_search rollout; do

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 ctrs=$1; name=${2:-pmc_bench}; shift; shift
 out=gpurun_out/$name
 rm -rf "$out"; mkdir -p "$out"
-timeout -k 10 ${PMC_TIMEOUT:-200} rocprofv3 --pmc $ctrs --output-format csv -d "$out" -o c -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-contact-line --no-fd-line "$@" > "$out/run.log" 2>&1
+timeout -k 10 ${PMC_TIMEOUT:-200} rocprofv3 --pmc $ctrs --output-format csv -d "$out" -o c -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-contact-line --no-fd-line "$@" > "$out/run.log" 2>&1
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections
 fs = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)
