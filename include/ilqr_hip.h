@@ -228,6 +228,25 @@ int ilqr_hip_set_joint_limits(ilqr_hip_ctx* ctx, int on);
    both Jacobian schemes (analytic: d qacc_i = -k rides the direction of the constrained hinge's own angle).  k < 0: ILQR_ERR_ARG. */
 int ilqr_hip_set_joint_limit_stiffness(ilqr_hip_ctx* ctx, double stiffness);
 int ilqr_hip_step_stance(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, double* x_next);
+/* Stance source of the dynamics (DESIGN 3.5 "Stance from the foot hulls").  The reference's plant and model are both mj_step
+   (src/common/robot_utils.cpp:106-117), which finds contacts from geometry on every step; its cost takes isStance from the schedule
+   (src/ilqr/ilqr.cpp:403-404,703).  ILQR_STANCE_SCHEDULE (default): the stance rows of contact modes 2-4 sit on the feet the contact
+   schedule marks.  ILQR_STANCE_GEOMETRY: at the start of every dynamics step foot f is in stance iff its ankle-link hull reaches the
+   floor, clearance_f(qpos_t) < 0 -- the rule of ilqr_hip_foot_clearance (get_contacts.py:96-147); release, friction and joint-limit rows
+   then act as before.  Every step decides for itself: rollout, the line-search candidates, the warm-start step, the plant step and each
+   forward-difference step (as mj_step does inside linearizeDynamicsFD, robot_utils.cpp:120-160); the analytic Jacobians hold the nominal
+   knot's decisions fixed.  The cost keeps reading the schedule.  Valid with contact modes 2, 3 and 4; mode 1 (a weld: a welded foot never
+   leaves) returns ILQR_ERR_UNSUPPORTED from whichever setter would create the combination, as does the scalar family (ILQR_DYN=s); mode 0
+   stores the source and ignores it (no stance rows). */
+enum ilqr_stance_source { ILQR_STANCE_SCHEDULE = 0, ILQR_STANCE_GEOMETRY = 1 };
+int ilqr_hip_set_stance_source(ilqr_hip_ctx* ctx, int source);
+/* Plant step with contacts from geometry (RobotUtils::rolloutOneStep, robot_utils.cpp:106-117): every item decides its stance from its
+   own x and steps with the handle's contact mode, whatever the handle's stance source; stance_out[count][2] (nullable) = the flags it
+   decided (left, right; before the unilateral release). */
+int ilqr_hip_step_geometry(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, double* x_next, int* stance_out);
+/* The stance flags the dynamics use for the steps t = 0..N-1 of the current nominal trajectories, stance[B][N][2] (left, right):
+   decided from xbar under ILQR_STANCE_GEOMETRY (get_contacts.py:96-147 applied to the nominal), the schedule's rows otherwise. */
+int ilqr_hip_get_stance(ilqr_hip_ctx* ctx, int* stance);
 
 /* per-stage device time of the last solve in milliseconds, keyed like the reference's profiler
    (src/ilqr/ilqr.cpp:537-639): 0 computeCost/rollout, 1 linearization, 2 costQuadratics, 3 backwardPass,

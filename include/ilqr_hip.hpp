@@ -94,6 +94,8 @@ class iLQR {
   void setContactSchedule(const std::vector<int>& stance /*[N+1][2]*/) { chk(ilqr_hip_set_contact_schedule(ctx_, stance.data(), 1)); }
   // contact row: ILQR_CONTACT_NONE (default) or ILQR_CONTACT_RIGID_STANCE on the scheduled feet
   void setContactMode(int mode, double softness = 0.0) { chk(ilqr_hip_set_contact_mode(ctx_, mode, softness)); }
+  // stance source of the dynamics: ILQR_STANCE_SCHEDULE (default) or ILQR_STANCE_GEOMETRY (contacts from the foot hulls, modes 2-4)
+  void setStanceSource(int source) { chk(ilqr_hip_set_stance_source(ctx_, source)); }
   // sliding friction coefficient of contact modes 3 / 4 (ilqr_hip.h: Coulomb limit on the stance feet; forward-difference Jacobians only)
   void setFriction(double mu) { chk(ilqr_hip_set_friction(ctx_, mu)); }
   void setJointLimits(bool on) { chk(ilqr_hip_set_joint_limits(ctx_, on ? 1 : 0)); }     // joint-limit rows of the plant (ilqr_hip.h)

@@ -9,6 +9,7 @@
 #include "h1_cost_dev.h"
 #define ABA_FENCE          // scheduling fences between the sweeps of the articulated-body algorithm (h1_aba_split.h)
 #include "h1_aba_split.h"
+#include "h1_foot_contact_dev.h"   // stance from the foot hulls (ProblemDev::stance_geom)
 #include "h1_linearize_dev.h"      // LinDumpG: what k_lin_tangent reads of the nominal knot
 #include "ilqr_kernels.h"
 
@@ -43,25 +44,27 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
 // The constraint-free path (contact mode 0, the headline) keeps its inlined step and is not touched by this.
 extern __shared__ double dyn_lds_c[];
 __device__ __attribute__((noinline)) void step_stance_shared(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
-                                                             double soft, int mode, int st_left, int st_right, double mu) {
+                                                             double soft, int mode, int st_left, int st_right, double mu, int geom) {
   const int lane = threadIdx.x;
   const bool side = (lane & 1) != 0;
   const h1s::LaneLds L{dyn_lds_c, 64, lane};
   const double grav[3] = {gx, gy, gz};
   h1s::HalfX h = *hp;
   const h1s::HalfU u = *up;
+  if (geom) h1s::geom_stance(side, h, st_left, st_right);      // (stance source GEOMETRY: the flags of x_t's own feet replace the schedule's)
   h1s::step_stance<false>(side, h, u, dt, grav, L, soft, mode, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu);
   *hp = h;
 }
 // the copy with kinetic friction on sliding feet (contact mode 4), see h1s::stance_correct<KIN>
 __device__ __attribute__((noinline)) void step_stance_shared_kin(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
-                                                                 double soft, int st_left, int st_right, double mu) {
+                                                                 double soft, int st_left, int st_right, double mu, int geom) {
   const int lane = threadIdx.x;
   const bool side = (lane & 1) != 0;
   const h1s::LaneLds L{dyn_lds_c, 64, lane};
   const double grav[3] = {gx, gy, gz};
   h1s::HalfX h = *hp;
   const h1s::HalfU u = *up;
+  if (geom) h1s::geom_stance(side, h, st_left, st_right);
   h1s::step_stance<true>(side, h, u, dt, grav, L, soft, 4, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu);
   *hp = h;
 }
@@ -86,8 +89,9 @@ __device__ __attribute__((noinline)) void lim_accelerations(const h1s::HalfX* hp
   *out = o;
 }
 template <bool KIN>
-DEVFN void step_lim(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz, double soft, int mode, int st_left, int st_right, double mu, double kr) {
+DEVFN void step_lim(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz, double soft, int mode, int st_left, int st_right, double mu, double kr, int geom) {
   const bool side = (threadIdx.x & 1) != 0;
+  if (geom) h1s::geom_stance(side, *hp, st_left, st_right);     // (decided once: both passes below run with these flags)
   LimAcc o;
   lim_accelerations<KIN>(hp, up, 0u, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, kr, &o);
   h1s::HalfX h = *hp;
@@ -100,12 +104,12 @@ DEVFN void step_lim(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, 
   *hp = h;
 }
 __device__ __attribute__((noinline)) void step_stance_shared_lim(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
-                                                                 double soft, int mode, int st_left, int st_right, double mu, double kr) {
-  step_lim<false>(hp, up, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, kr);
+                                                                 double soft, int mode, int st_left, int st_right, double mu, double kr, int geom) {
+  step_lim<false>(hp, up, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, kr, geom);
 }
 __device__ __attribute__((noinline)) void step_stance_shared_kin_lim(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
-                                                                     double soft, int st_left, int st_right, double mu, double kr) {
-  step_lim<true>(hp, up, dt, gx, gy, gz, soft, 4, st_left, st_right, mu, kr);
+                                                                     double soft, int st_left, int st_right, double mu, double kr, int geom) {
+  step_lim<true>(hp, up, dt, gx, gy, gz, soft, 4, st_left, st_right, mu, kr, geom);
 }
 // ---- joint-limit rows on the constraint-free plant (CONTACT == 5, round 6) ------------------------------------------------------
 // With no stance rows the first pass of the step with the rows IS the free step's recursion: it stays inlined, as in the constraint-free
@@ -196,8 +200,11 @@ DEVFN void pin_half_u(h1s::HalfU& u) {
 // 3 / 4: as 1 / 2 with joint-limit rows (DynParams::limits; 3 also serves the constraint-free plant with them: no stance rows in mode 0).
 // Mode 4 has kernels of its own: the private segment of a kernel is the largest frame it can reach, and the constrained kernels lose with
 // every kilobyte of it (1.4 -> 1.8 KB per lane: -0.7 % on the contact bench, -> 4 KB: -4 %, same machine code otherwise).
+// geom (ProblemDev::stance_geom, wave-uniform): the stance flags come from the feet of x_t (h1_foot_contact_dev.h) instead of `st`; the
+// constrained step functions decide, behind their call boundary, so the kernels' own code only gains an argument.  CONTACT 0 / 5 have no
+// stance rows and ignore it.
 template <int CONTACT>
-DEVFN void step_any(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L) {
+DEVFN void step_any(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L, int geom) {
   if constexpr (CONTACT == 5) {
     double dt = dyn.h; asm volatile("" : "+s"(dt));
     h1s::HalfU uo = u;
@@ -229,10 +236,10 @@ DEVFN void step_any(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynPara
     h1s::integrate_half(h, qh, qb, qa, dt);
     pin_half(h);
   }
-  else if constexpr (CONTACT == 4) step_stance_shared_kin_lim(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, st[0], st[1], dyn.mu, dyn.lim_k);
-  else if constexpr (CONTACT == 3) step_stance_shared_lim(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, dyn.contact, st[0], st[1], dyn.mu, dyn.lim_k);
-  else if constexpr (CONTACT == 2) step_stance_shared_kin(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, st[0], st[1], dyn.mu);
-  else if constexpr (CONTACT == 1) step_stance_shared(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, dyn.contact, st[0], st[1], dyn.mu);
+  else if constexpr (CONTACT == 4) step_stance_shared_kin_lim(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, st[0], st[1], dyn.mu, dyn.lim_k, geom);
+  else if constexpr (CONTACT == 3) step_stance_shared_lim(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, dyn.contact, st[0], st[1], dyn.mu, dyn.lim_k, geom);
+  else if constexpr (CONTACT == 2) step_stance_shared_kin(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, st[0], st[1], dyn.mu, geom);
+  else if constexpr (CONTACT == 1) step_stance_shared(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, dyn.contact, st[0], st[1], dyn.mu, geom);
   else {
     // (the step size behind an opaque barrier as well: with h a loop invariant the articulated quantities of the chains' leaf
     // bodies -- constants plus the armature term h * damping -- are hoisted out of the knot loop, spilled and reloaded per step)
@@ -453,7 +460,7 @@ __global__ void __launch_bounds__(64) k_line_search_s(DevState S, ProblemDev P, 
     LSS(2)
     int sd = side; asm volatile("" : "+v"(sd));          // (see k_rollout_s)
     const bool side_t = sd != 0;
-    step_any<CONTACT>(side_t, h, u, P.dyn, P.stance + b * P.stance_stride + 2 * t, L);
+    step_any<CONTACT>(side_t, h, u, P.dyn, P.stance + b * P.stance_stride + 2 * t, L, P.stance_geom);
     LSS(3)
     LSS(4)
   }
@@ -492,7 +499,7 @@ __global__ void __launch_bounds__(64) k_rollout_s(DevState S, ProblemDev P, int 
     // are hoisted out of the knot loop as loop invariants, spilled, and fetched back from scratch every step
     int sd = side; asm volatile("" : "+v"(sd));
     const bool side_t = sd != 0;
-    step_any<CONTACT>(side_t, h, u, P.dyn, P.stance + b * P.stance_stride + 2 * t, L);
+    step_any<CONTACT>(side_t, h, u, P.dyn, P.stance + b * P.stance_stride + 2 * t, L, P.stance_geom);
   }
   h1s::store_half(side, h, xb + (size_t)N * H1_NX);
 }
@@ -625,14 +632,33 @@ __global__ void __launch_bounds__(64) k_lin_primal_s(DevState S, ProblemDev P, i
     stage.flush(inv36 + 14, wh ? rec + 54 : -1L);
   }
 }
+// the stance flags the steps t = 0..N-1 of the nominal trajectories take under the stance source GEOMETRY: a lane pair per knot over xbar,
+// out[(b N + t) 2 + {0, 1}] (left, right).  The analytic linearisation runs on these (the nominal knot's decision held fixed, ProblemDev::
+// stance_dyn); list / count / mode select the rollouts as in k_lin_primal_s -- a concurrent linearisation of other rollouts is not touched.
+__global__ void __launch_bounds__(64) k_stance_geom_s(DevState S, int mode, const int* list, const int* count, int* out) {
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long knot = gid >> 1;
+  const bool side = (gid & 1) != 0;
+  const long total = (long)(list ? *count : S.B) * S.N;
+  if (knot >= total) return;      // (pairs leave together)
+  const int t = (int)(knot % S.N);
+  int b = (int)(knot / S.N);
+  if (list) b = list[b];
+  else if (!sel_s(S, b, mode)) return;
+  h1s::HalfX h; h1s::load_half(side, S.xbar + ((size_t)b * (S.N + 1) + t) * H1_NX, h);
+  int sl, sr;
+  h1s::geom_stance(side, h, sl, sr);
+  if (!side) { out[((size_t)b * S.N + t) * 2] = sl; out[((size_t)b * S.N + t) * 2 + 1] = sr; }
+}
 __global__ void __launch_bounds__(64) k_count_iter(DevState S, int mode) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < S.B && sel_s(S, b, mode)) S.iters[b] += 1;
 }
 
-// two lanes per item: plain batched step with explicit stance flags (stage API / plant of the closed loop)
+// two lanes per item: plain batched step with explicit stance flags (stage API / plant of the closed loop); geom: the flags come from
+// each item's own feet instead (ilqr_hip_step_geometry), and st_out[2 i], [2 i + 1] (if given) receive them
 template <int CK>     // CK: the CONTACT value of step_any (0: the constraint-free plant -- an instantiation that cannot reach the constrained step keeps its private segment small; 1..4)
-__global__ void __launch_bounds__(64) k_step_s(int count, const double* x, const double* u, DynParams dyn, double* xn, int st_l, int st_r) {
+__global__ void __launch_bounds__(64) k_step_s(int count, const double* x, const double* u, DynParams dyn, double* xn, int st_l, int st_r, int geom, int* st_out) {
   extern __shared__ double lds[];
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int i = gid >> 1;
@@ -641,8 +667,12 @@ __global__ void __launch_bounds__(64) k_step_s(int count, const double* x, const
   const h1s::LaneLds L{lds, 64, (int)threadIdx.x};
   h1s::HalfX h; h1s::load_half(side, x + (size_t)i * H1_NX, h);
   h1s::HalfU uu; load_half_u(side, u + (size_t)i * H1_NU, uu);
-  const int st[2] = {st_l, st_r};
-  step_any<CK>(side, h, uu, dyn, st, L);
+  int st[2] = {st_l, st_r};
+  if (st_out) {         // (the step decides again behind its call boundary, on the same state with the same machine code)
+    h1s::geom_stance(side, h, st[0], st[1]);
+    if (!side) { st_out[2 * (size_t)i] = st[0]; st_out[2 * (size_t)i + 1] = st[1]; }
+  }
+  step_any<CK>(side, h, uu, dyn, st, L, geom);
   h1s::store_half(side, h, xn + (size_t)i * H1_NX);
 }
 // last knot of the warm start: xbar[N] = f(xbar[N-1], ubar[N-1])  (ilqr.cpp:72-80)
@@ -657,7 +687,7 @@ __global__ void __launch_bounds__(64) k_last_step_s(DevState S, ProblemDev P) {
   const int N = S.N;
   h1s::HalfX h; h1s::load_half(side, S.xbar + ((size_t)b * (N + 1) + N - 1) * H1_NX, h);
   h1s::HalfU uu; load_half_u(side, S.ubar + ((size_t)b * N + N - 1) * H1_NU, uu);
-  step_any<CK>(side, h, uu, P.dyn, P.stance + b * P.stance_stride + 2 * (N - 1), L);
+  step_any<CK>(side, h, uu, P.dyn, P.stance + b * P.stance_stride + 2 * (N - 1), L, P.stance_geom);
   h1s::store_half(side, h, S.xbar + ((size_t)b * (N + 1) + N) * H1_NX);
 }
 // Reference-style forward differences (RobotUtils::linearizeDynamicsFD, robot_utils.cpp:120-160) on the two-lane step:
@@ -712,7 +742,7 @@ __global__ void __launch_bounds__(64) k_fd_steps_s(DevState S, ProblemDev P, int
   h1s::HalfX h; h1s::load_half(side, S.xbar + ((size_t)b * (S.N + 1) + t) * H1_NX, h);
   h1s::HalfU uu; load_half_u(side, S.ubar + ((size_t)b * S.N + t) * H1_NU, uu);
   perturb_half(side, h, uu, col, eps);
-  step_any<CK>(side, h, uu, P.dyn, P.stance + b * P.stance_stride + 2 * t, L);
+  step_any<CK>(side, h, uu, P.dyn, P.stance + b * P.stance_stride + 2 * t, L, P.stance_geom);      // (geometry: every perturbed step decides, as mj_step does in linearizeDynamicsFD)
   if (!act) return;
   if (col < H1_NX) store_half_col(side, h, S.A + (size_t)item * H1_NX * H1_NX, H1_NX, col);
   else if (col < H1_NX + H1_NU) store_half_col(side, h, S.Bm + (size_t)item * H1_NX * H1_NU, H1_NU, col - H1_NX);
@@ -814,16 +844,19 @@ void launch_lin_primal_s(const DevState& S, const ProblemDev& P, int mode, hipSt
   if (P.dyn.limits) hipLaunchKernelGGL(k_lin_primal_s<true>, dim3(waves), dim3(64), DYN_LDS_BYTES_S + (direct ? 0 : DUMP_STG_BYTES), st, S, P, mode, list, count, direct);
   else hipLaunchKernelGGL(k_lin_primal_s<false>, dim3(waves), dim3(64), DYN_LDS_BYTES_S + (direct ? 0 : DUMP_STG_BYTES), st, S, P, mode, list, count, direct);
 }
-void launch_step_s(int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r) {
+void launch_step_s(int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out) {
   const dim3 grid(cdiv_s((long)count * 2, 64));
   switch (step_kind(dyn)) {
-    case 5: hipLaunchKernelGGL(k_step_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r); break;
-    case 4: hipLaunchKernelGGL(k_step_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r); break;
-    case 3: hipLaunchKernelGGL(k_step_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r); break;
-    case 2: hipLaunchKernelGGL(k_step_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r); break;
-    case 1: hipLaunchKernelGGL(k_step_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r); break;
-    default: hipLaunchKernelGGL(k_step_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r);
+    case 5: hipLaunchKernelGGL(k_step_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
+    case 4: hipLaunchKernelGGL(k_step_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
+    case 3: hipLaunchKernelGGL(k_step_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
+    case 2: hipLaunchKernelGGL(k_step_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
+    case 1: hipLaunchKernelGGL(k_step_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
+    default: hipLaunchKernelGGL(k_step_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out);
   }
+}
+void launch_stance_geom_s(const DevState& S, int mode, const int* list, const int* count, int* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_stance_geom_s, dim3(cdiv_s((long)S.B * S.N * 2, 64)), dim3(64), 0, st, S, mode, list, count, out);
 }
 void launch_last_step_s(const DevState& S, const ProblemDev& P, hipStream_t st) {
   const dim3 grid(cdiv_s((long)S.B * 2, 64));

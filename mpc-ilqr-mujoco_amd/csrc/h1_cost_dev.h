@@ -26,6 +26,8 @@ namespace h1 {
 
 struct ProblemDev {
   int N;
+  int stance_geom;           // stance source of the DYNAMICS: 0 the schedule (`stance` below), 1 the feet of x_t (h1_foot_contact_dev.h; the cost
+                             // keeps reading `stance`).  Sits in what was padding: the layout of the rest (kernel arguments) does not move
   DynParams dyn;
   double Q[H1_NX], R[H1_NU], Qf[H1_NX];
   double w_com, w_com_vel, w_ee_pos, w_ee_vel, w_upright, w_balance, w_joint, w_ctrl;

@@ -63,6 +63,8 @@ struct ilqr_hip_ctx {
   // reference sets on the device
   double *d_xref = nullptr, *d_uref = nullptr, *d_comref = nullptr, *d_eeref = nullptr, *d_comvelref = nullptr;
   int* d_stance = nullptr;
+  int* d_stance_dyn = nullptr;            // [B][N][2] stance flags decided from the feet of xbar (stance source GEOMETRY: linearisation, ilqr_hip_get_stance)
+  int* d_stance_out = nullptr;            // [step_cap][2] flags decided by ilqr_hip_step_geometry
   int n_xref = 0, n_stance = 0, n_ee = 0;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
@@ -220,6 +222,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   // shared reference sets sized for per-rollout use
   A(dalloc(c, &c->d_xref, B * (N + 1) * n)); A(dalloc(c, &c->d_uref, B * N * m)); A(dalloc(c, &c->d_comref, B * (N + 1) * 3));
   A(dalloc(c, &c->d_eeref, B * (N + 1) * 6)); A(dalloc(c, &c->d_comvelref, B * (N + 1) * 3)); A(dalloc(c, &c->d_stance, B * (N + 1) * 2));
+  A(dalloc(c, &c->d_stance_dyn, B * N * 2));
   if (rc != ILQR_OK) { *out = c; return rc; }
   if (ilqr::backward_needs_lds_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; *out = c; return ILQR_ERR_HIP; }
   h1::ProblemDev& P = c->P;
@@ -253,7 +256,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an}; for (void* p : gp) if (p) hipFree(p); }
@@ -557,6 +560,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
                          hipEvent_t ev_lin = nullptr, hipEvent_t ev_adopt = nullptr) {
   // shadow target of the concurrent re-rollout: same rollouts as S.xbar, in the shadow buffer
   double* shadow = const_cast<double*>(shadow_base) + (S.xbar - c->S.xbar);
+  int* stance_dyn = c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N;     // (same rollouts as S)
   const double fold_h = ilqr::linearize_fold_h(P, c->jac_mode);
   { StageTimer T(c, 0, st); ilqr::launch_rollout(S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st); ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
   // With the convergence exit on, the launches of an iteration nobody needs are pure latency (17 launches that find nothing to
@@ -612,7 +616,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     }
     { StageTimer T(c, 2, G.q); ilqr::launch_cost_quadratics(S, P, knot_mode, G.q, iter_l, lxx_lower, wl); }
     HIPCHK(c, hipEventRecord(G.join, G.q));
-    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(S, P, knot_mode, c->jac_mode, c->fd_eps, G.m, 3, iter_l, pack, wl); }
+    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(S, P, knot_mode, c->jac_mode, c->fd_eps, G.m, 3, iter_l, pack, wl, stance_dyn); }
     if (concurrent_roll && G.lin && G.adopt) {
       HIPCHK(c, hipEventRecord(G.lin, G.m));
       HIPCHK(c, hipStreamWaitEvent(G.r, G.lin, 0)); HIPCHK(c, hipStreamWaitEvent(G.r, G.join, 0));
@@ -906,7 +910,7 @@ int ilqr_hip_set_trajectory(ilqr_hip_ctx* c, const double* xbar, const double* u
 #define STAGE_PRE if (!c) return ILQR_ERR_ARG; if (!c->initialized) return ILQR_ERR_STATE; enter(c); ENV_REFUSED(c)
 #define STAGE_POST HIPCHK(c, hipGetLastError()); HIPCHK(c, hipStreamSynchronize(c->stream)); return ILQR_OK
 int ilqr_hip_stage_rollout(ilqr_hip_ctx* c) { STAGE_PRE; ilqr::launch_rollout(c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream); STAGE_POST; }
-int ilqr_hip_stage_linearize(ilqr_hip_ctx* c) { STAGE_PRE; if (int rc = jacobians_available(c)) return rc; ilqr::launch_linearize(c->S, c->P, ilqr::MASK_ALL, c->jac_mode, c->fd_eps, c->stream); c->lin_fold_h = ilqr::linearize_fold_h(c->P, c->jac_mode); c->ab_packed = false; c->ab_pads_clean = false; STAGE_POST; }
+int ilqr_hip_stage_linearize(ilqr_hip_ctx* c) { STAGE_PRE; if (int rc = jacobians_available(c)) return rc; ilqr::launch_linearize(c->S, c->P, ilqr::MASK_ALL, c->jac_mode, c->fd_eps, c->stream, 3, -1, 0, nullptr, c->d_stance_dyn); c->lin_fold_h = ilqr::linearize_fold_h(c->P, c->jac_mode); c->ab_packed = false; c->ab_pads_clean = false; STAGE_POST; }
 int ilqr_hip_stage_cost_quadratics(ilqr_hip_ctx* c) { STAGE_PRE; if (!c->refs_set) return ILQR_ERR_STATE; ilqr::launch_cost_quadratics(c->S, c->P, ilqr::MASK_ALL, c->stream); c->lxx_layout = 0; STAGE_POST; }
 // layout conversions on demand (in place): what a consumer of the standard layout (getters, any kernel family but the operand-layout
 // one) or of the operand layout (stage API on riccati_pack.hip) calls first
@@ -1016,6 +1020,7 @@ int ilqr_hip_set_contact_mode(ilqr_hip_ctx* c, int mode, double softness) {
   if (!c || (mode != ILQR_CONTACT_NONE && mode != ILQR_CONTACT_RIGID_STANCE && mode != ILQR_CONTACT_UNILATERAL_STANCE && mode != ILQR_CONTACT_FRICTION_STANCE && mode != ILQR_CONTACT_KINETIC_FRICTION_STANCE)) return ILQR_ERR_ARG;
   enter(c);
   if (mode >= ILQR_CONTACT_FRICTION_STANCE && ilqr::variant_scalar_dyn()) { c->err = "contact modes 3 / 4 (Coulomb limit) exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+  if (mode == ILQR_CONTACT_RIGID_STANCE && c->P.stance_geom) { c->err = "contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4"; return ILQR_ERR_UNSUPPORTED; }
   c->P.dyn.contact = mode;
   if (softness > 0.0) c->P.dyn.soft = softness;
   return ILQR_OK;
@@ -1037,25 +1042,75 @@ int ilqr_hip_set_friction(ilqr_hip_ctx* c, double mu) {
   c->P.dyn.mu = mu;            // (a nominal rolled under another mu is recognised by same_dyn)
   return ILQR_OK;
 }
-int ilqr_hip_step_stance(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, double* x_next) {
-  if (!c || count <= 0 || !x || !u || !x_next) return ILQR_ERR_ARG;
-  enter(c);
+// the plant step of ilqr_hip_step_stance / ilqr_hip_step_geometry (geom: stance from each item's own feet, stance_out [count][2] nullable)
+static int plant_step(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, int geom, int* stance_out, double* x_next) {
   if ((size_t)count > c->step_cap) {   // scratch owned by the context, grown on demand (the closed loop steps the plant every MPC step)
     if (c->d_stepx) hipFree(c->d_stepx);
     if (c->d_stepu) hipFree(c->d_stepu);
     if (c->d_stepn) hipFree(c->d_stepn);
-    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->step_cap = 0;
+    if (c->d_stance_out) hipFree(c->d_stance_out);
+    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
     HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
     HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
     HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
     c->step_cap = (size_t)count;
   }
   HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  ilqr::launch_step(count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right);
+  ilqr::launch_step(count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right, geom, geom ? c->d_stance_out : nullptr);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (geom && stance_out) HIPCHK(c, hipMemcpyAsync(stance_out, c->d_stance_out, (size_t)count * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_step_stance(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, double* x_next) {
+  if (!c || count <= 0 || !x || !u || !x_next) return ILQR_ERR_ARG;
+  enter(c);
+  return plant_step(c, count, x, u, stance_left, stance_right, 0, nullptr, x_next);
+}
+// ---------------------------------------------------------------- stance from the foot hulls
+static const char* geometry_refusal(const ilqr_hip_ctx* c) {
+  if (ilqr::variant_scalar_dyn()) return "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s";
+  if (c->P.dyn.contact == ILQR_CONTACT_RIGID_STANCE) return "contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4";
+  return nullptr;
+}
+int ilqr_hip_set_stance_source(ilqr_hip_ctx* c, int source) {
+  if (!c || (source != ILQR_STANCE_SCHEDULE && source != ILQR_STANCE_GEOMETRY)) return ILQR_ERR_ARG;
+  enter(c);
+  if (source == ILQR_STANCE_GEOMETRY) {
+    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  }
+  if (c->P.stance_geom != source) c->xbar_rolled = false;      // (the nominal trajectory was rolled under the other source)
+  c->P.stance_geom = source;
+  return ILQR_OK;
+}
+int ilqr_hip_step_geometry(ilqr_hip_ctx* c, int count, const double* x, const double* u, double* x_next, int* stance_out) {
+  if (!c || count <= 0 || !x || !u || !x_next) return ILQR_ERR_ARG;
+  enter(c);
+  if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  return plant_step(c, count, x, u, 1, 1, 1, stance_out, x_next);
+}
+int ilqr_hip_get_stance(ilqr_hip_ctx* c, int* stance) {
+  if (!c || !stance) return ILQR_ERR_ARG;
+  enter(c);
+  const size_t B = c->B, N = c->N;
+  if (c->P.stance_geom) {
+    if (ilqr::variant_scalar_dyn()) { c->err = "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+    ilqr::launch_stance_geom_s(c->S, ilqr::MASK_ALL, nullptr, nullptr, c->d_stance_dyn, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(stance, c->d_stance_dyn, B * N * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ILQR_OK;
+  }
+  // the schedule's rows t = 0..N-1 (one shared set or one per rollout)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t per = (N + 1) * 2;
+  std::vector<int> sched(c->P.stance_stride ? B * per : per);
+  HIPCHK(c, hipMemcpy(sched.data(), c->d_stance, sched.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < B; ++b)
+    std::memcpy(stance + b * N * 2, sched.data() + (c->P.stance_stride ? b * per : 0), N * 2 * sizeof(int));
   return ILQR_OK;
 }
 int ilqr_hip_get_iterations_enqueued(const ilqr_hip_ctx* c) { return c ? c->iterations_enqueued : -1; }

@@ -68,11 +68,15 @@ struct DevState {
 };
 
 void launch_rollout(const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
-void launch_step(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l = 1, int stance_r = 1);
+// geom / st_out: stance from each item's own feet (ProblemDev::stance_geom) / the flags it decided, [count][2] (two-lane kernels only)
+void launch_step(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l = 1, int stance_r = 1, int geom = 0, int* st_out = nullptr);
 // pack != 0 (a solve whose backward pass is the operand-layout Riccati kernel): A_t, B_t in the layout of riccati_pack.h (the two-knot
 // analytic kernels write it themselves, any other producer is followed by the conversion kernel)
 struct WorkList;
-void launch_linearize(const DevState& S, const h1::ProblemDev& P, int mode, int jac_mode, double eps, hipStream_t st, int phases = 3, int iter = -1, int pack = 0, const WorkList* wl = nullptr);
+// stance_dyn: [S.B][N][2] scratch of the stance source GEOMETRY (ProblemDev::stance_geom) -- the analytic Jacobians hold the nominal knots'
+// decisions fixed, decided into it first
+void launch_linearize(const DevState& S, const h1::ProblemDev& P, int mode, int jac_mode, double eps, hipStream_t st, int phases = 3, int iter = -1, int pack = 0, const WorkList* wl = nullptr,
+                      int* stance_dyn = nullptr);
 // lower = 1: knots t < N get only the tiles I >= J of lxx (what k_backward_wave loads); 2: every knot in the operand layout of
 // riccati_pack.h (lx in row / column "aug"); the stage API always asks for the full matrix (0)
 void launch_cost_quadratics(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int lower = 0, const WorkList* wl = nullptr);
@@ -136,7 +140,9 @@ void launch_rollout_s(const DevState& S, const h1::ProblemDev& P, int mode, int 
 void launch_lin_primal_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr);
 void launch_line_search_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr, int max_rollouts = -1);
 int dyn_split_kernels_set_attr();
-void launch_step_s(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r);
+void launch_step_s(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out);
+// stance flags of the nominal knots t = 0..N-1 from the feet of xbar (out[B][N][2]); rollouts selected as by launch_lin_primal_s
+void launch_stance_geom_s(const DevState& S, int mode, const int* list, const int* count, int* out, hipStream_t st);
 void launch_last_step_s(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
 void launch_linearize_fd_s(const DevState& S, const h1::ProblemDev& P, int mode, double eps, hipStream_t st);
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);

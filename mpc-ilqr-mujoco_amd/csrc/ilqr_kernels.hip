@@ -1137,8 +1137,8 @@ void launch_rollout(const DevState& S, const ProblemDev& P, int mode, int do_rol
   if (!use_scalar_dyn()) { if (g_var.rollout_split || constrained(P.dyn)) launch_rollout_s(S, P, mode, do_roll, count_iter, cost_out, st); else launch_rollout_r(S, P, mode, do_roll, count_iter, cost_out, st); return; }
   LEGACY_LAUNCH(hipLaunchKernelGGL(k_rollout, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S, P, mode, do_roll, count_iter, cost_out));
 }
-void launch_step(int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r) {
-  if (!use_scalar_dyn()) { if (constrained(dyn)) launch_step_s(count, x, u, dyn, xn, st, stance_l, stance_r); else launch_step_r(count, x, u, dyn, xn, st); return; }
+void launch_step(int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out) {
+  if (!use_scalar_dyn()) { if (constrained(dyn) || st_out) launch_step_s(count, x, u, dyn, xn, st, stance_l, stance_r, geom, st_out); else launch_step_r(count, x, u, dyn, xn, st); return; }
   LEGACY_LAUNCH(hipLaunchKernelGGL(k_step, dim3(cdiv(count, 64)), dim3(64), 0, st, count, x, u, dyn, xn, stance_l, stance_r));
 }
 // phases: 1 = primal dump only, 2 = tangent sweeps / FD only, 3 = both
@@ -1151,8 +1151,16 @@ static void launch_lin_tangent_free(const DevState& S, const ProblemDev& P, int 
   else if (pack) hipLaunchKernelGGL((k_lin_tangent2<true, false>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count);
   else hipLaunchKernelGGL((k_lin_tangent2<false, false>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count);
 }
-void launch_linearize(const DevState& S, const ProblemDev& P, int mode, int jac_mode, double eps, hipStream_t st, int phases, int iter, int pack, const WorkList* wl) {
+void launch_linearize(const DevState& S, const ProblemDev& P0, int mode, int jac_mode, double eps, hipStream_t st, int phases, int iter, int pack, const WorkList* wl,
+                      int* stance_dyn) {
   const WorkList w = wl ? *wl : work_list(S, mode, iter);
+  ProblemDev P = P0;
+  if (jac_mode == 0 && !use_scalar_dyn() && P0.stance_geom && P0.dyn.contact && stance_dyn) {
+    // stance from the feet: the nominal knots decide once, the primal dump (joint-limit decision pass) and the tangent kernels read those
+    // decisions where they read the schedule otherwise -- held fixed, as every other decision of the analytic Jacobians
+    if (phases & 1) launch_stance_geom_s(S, mode, w.list, w.count, stance_dyn, st);
+    P.stance = stance_dyn; P.stance_stride = 2L * S.N;
+  }
   if (jac_mode == 0 && !use_scalar_dyn()) {
     // primal dump: on two lanes per knot beside the two-lane rollout kernels, one lane per knot with ILQR_ROLLOUT=r
     if (phases & 1) { if (g_var.rollout_split || constrained(P.dyn)) launch_lin_primal_s(S, P, mode, st, w.list, w.count); else launch_lin_primal_r(S, P, mode, st); }   // (contact mode: the dump is the free solve, see k_lin_tangent_c)

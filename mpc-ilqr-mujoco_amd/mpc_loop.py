@@ -58,8 +58,14 @@ class MPCLogs:
 class MPCRunner:
     """Batched closed loop: `solver` = BatchedILQR, `refs` = ReferenceData, `base_problem` = weights etc. (scenario.make_problem)."""
 
-    def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False):
+    def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule"):
+        if plant_contacts not in ("schedule", "geometry"):
+            raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         self.s, self.refs, self.base = solver, refs, base_problem
+        # "geometry": the plant finds its contacts from the foot hulls (BatchedILQR.step_geometry, the solver's contact mode), as mj_step
+        # does in the reference's plant (robot_utils.cpp:106-117); "schedule": the stance flags of the current schedule row
+        self.plant_contacts = plant_contacts
+        self.plant_stance = []
         self.prof = {}
         self.profile_stages = profile_stages
         if profile_stages:
@@ -119,7 +125,10 @@ class MPCRunner:
         xs, us = [x.copy()], []
         for _ in range(steps):
             u = self.step_once(x, u_init)
-            if getattr(self.s, "contact_mode", 0):    # contact row: the plant holds the feet in stance now
+            if self.plant_contacts == "geometry":
+                x, st = self.s.step_geometry(x, u)
+                self.plant_stance.append(st)
+            elif getattr(self.s, "contact_mode", 0):    # contact row: the plant holds the feet in stance now
                 st = np.asarray(self.last_stance0).reshape(-1)
                 x = self.s.step_stance(x, u, int(st[0]), int(st[1]))
             else:

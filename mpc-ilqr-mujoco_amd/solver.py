@@ -34,7 +34,7 @@ EXPORTS = [
     "ilqr_hip_set_trajectory", "ilqr_hip_stage_rollout", "ilqr_hip_stage_linearize", "ilqr_hip_stage_cost_quadratics",
     "ilqr_hip_stage_backward_pass", "ilqr_hip_stage_line_search", "ilqr_hip_stage_total_cost",
     "ilqr_hip_get_linearization", "ilqr_hip_set_linearization", "ilqr_hip_get_quadratics", "ilqr_hip_set_quadratics",
-    "ilqr_hip_get_value_function", "ilqr_hip_step", "ilqr_hip_step_stance", "ilqr_hip_set_contact_mode", "ilqr_hip_set_friction", "ilqr_hip_set_joint_limits", "ilqr_hip_set_joint_limit_stiffness", "ilqr_hip_enable_profiling", "ilqr_hip_get_stage_ms", "ilqr_hip_get_adopt_mismatches", "ilqr_hip_get_iterations_enqueued", "ilqr_hip_get_speculative_iterations", "ilqr_hip_get_split_iterations", "ilqr_hip_set_profiled_stages",
+    "ilqr_hip_get_value_function", "ilqr_hip_step", "ilqr_hip_step_stance", "ilqr_hip_set_stance_source", "ilqr_hip_step_geometry", "ilqr_hip_get_stance", "ilqr_hip_set_contact_mode", "ilqr_hip_set_friction", "ilqr_hip_set_joint_limits", "ilqr_hip_set_joint_limit_stiffness", "ilqr_hip_enable_profiling", "ilqr_hip_get_stage_ms", "ilqr_hip_get_adopt_mismatches", "ilqr_hip_get_iterations_enqueued", "ilqr_hip_get_speculative_iterations", "ilqr_hip_get_split_iterations", "ilqr_hip_set_profiled_stages",
     "ilqr_hip_payload_width", "ilqr_hip_comm_available", "ilqr_hip_comm_get_unique_id", "ilqr_hip_comm_init", "ilqr_hip_comm_destroy", "ilqr_hip_comm_world", "ilqr_hip_comm_rank",
     "ilqr_hip_gather_first_knot",
     "ilqr_hip_reference_kinematics", "ilqr_hip_reference_com_velocity", "ilqr_hip_foot_clearance", "ilqr_hip_gravity_compensation", "ilqr_hip_stream",
@@ -358,6 +358,29 @@ class BatchedILQR:
         xn = np.zeros_like(x)
         self._chk(self.L.ilqr_hip_step_stance(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(xn)))
         return xn
+
+    def set_stance_source(self, source):
+        """Stance source of the dynamics (include/ilqr_hip.h): "schedule" (default) or "geometry" -- every step takes the stance flags from
+        its own feet (a foot touches iff its ankle-link hull reaches the floor, foot_clearance < 0); the cost keeps the schedule."""
+        code = {"schedule": 0, "geometry": 1}.get(source)
+        if code is None:
+            raise ValueError("stance source must be 'schedule' or 'geometry'")
+        self._chk(self.L.ilqr_hip_set_stance_source(self.h, code))
+        self.stance_source = source
+
+    def step_geometry(self, x, u):
+        """Plant step with contacts from geometry: (x_next [count,51], stance [count,2]) -- the flags each item decided from its own x."""
+        x, u = _c64(x), _c64(u)
+        xn = np.zeros_like(x)
+        st = np.zeros((x.shape[0], 2), dtype=np.int32)
+        self._chk(self.L.ilqr_hip_step_geometry(self.h, int(x.shape[0]), _p(x), _p(u), _p(xn), st.ctypes.data_as(_ip)))
+        return xn, st
+
+    def stance(self):
+        """[B,N,2] stance flags the dynamics use for steps t = 0..N-1 of the current nominal trajectories."""
+        st = np.zeros((self.B, self.N, 2), dtype=np.int32)
+        self._chk(self.L.ilqr_hip_get_stance(self.h, st.ctypes.data_as(_ip)))
+        return st
 
     def set_contact_mode(self, mode, softness=0.0):
         """0: constraint-free step; 1: rigid stance constraints on the feet the contact schedule marks (SURVEY 8(f) f4);
