@@ -49,8 +49,12 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
 int ilqr_hip_destroy(ilqr_hip_ctx* ctx);
 /* The diagnostic environment switches (kernel families ILQR_BACKWARD / ILQR_LS / ILQR_ROLLOUT / ILQR_DYN / ILQR_LINT, launch orders
    ILQR_SLICES / ILQR_STAGGER / ILQR_OVERLAP_ROLLOUT / ILQR_REUSE_ROLLOUT / ILQR_EE_GATE / ILQR_SPLIT / ILQR_SPEC*) are read ONCE, by
-   ilqr_hip_create, and kept in the handle: no getenv on the call path.  This call re-reads them for one handle (tests, profiling
-   tools); ILQR_ENV_PER_CALL=1 at creation makes every call of the handle do so.  No reference counterpart. */
+   ilqr_hip_create, and kept in the handle: no getenv on the call path, and the handle's copy is the only one -- handles of different
+   kernel families may be driven from one host thread in any order.  This call re-reads them for one handle (tests, profiling tools);
+   ILQR_ENV_PER_CALL=1 at creation makes every call of the handle do so, and while such a re-read names a kernel family the library
+   does not hold, every call that launches a family-dependent kernel (initialize*, solve*, stage_rollout / linearize / backward_pass /
+   total_cost / line_search, step*, get_stance with the stance source GEOMETRY) returns ILQR_ERR_UNSUPPORTED; getters, setters and
+   the fixed conversion kernels never do.  No reference counterpart. */
 int ilqr_hip_reload_environment(ilqr_hip_ctx* ctx);
 /* Off by default (the solve then executes every pass the reference executes).  On: a lambda retry (ilqr.cpp:619-644) whose lambda is
    already saturated -- min(10 lambda, 1e-3) == lambda, the state a rollout reaches after a few failed searches -- is not executed:

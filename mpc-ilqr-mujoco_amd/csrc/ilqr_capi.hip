@@ -101,7 +101,7 @@ struct ilqr_hip_ctx {
   int lxx_layout = 0;
   bool ab_packed = false, ab_pads_clean = false;
   int dedup_retry = 0;          // ilqr_hip_set_dedup_saturated_retry
-  bool env_refused = false;     // ILQR_ENV_PER_CALL: the last re-read selected a family this library does not hold (enter)
+  bool env_refused = false;     // ILQR_ENV_PER_CALL: the last re-read selected a family this library does not hold (enter, enter_launching)
   double packed_h = 0.0;        // step size h of the packed image while ab_packed (k_unpack_ab rebuilds the position rows from it)
   Knobs knobs = read_knobs();   // (constructed in ilqr_hip_create)
   double lin_fold_h = 0.0;   // step size h while S.A / S.Bm hold the analytic Jacobians (folded backward kernel), else 0
@@ -163,18 +163,20 @@ struct StageTimer {
   ~StageTimer() { if (a && b) { hipEventRecord(b, st); c->spans.push_back({stage, a, b}); } }
 };
 
+// Prologue of every entry point that touches the device, called after its argument checks.  The kernel family is c->knobs.var and
+// nothing else: whatever depends on it takes an ilqr::Variants argument.  An entry point uses enter_launching iff it calls, directly or
+// through a static helper, a function that takes one; every other one uses enter and never refuses.
 static inline void enter(ilqr_hip_ctx* c) {
   hipSetDevice(c->device);
   if (c->knobs.per_call) {
-    // an unsupported selection keeps the previous one AND is recorded: the calls that launch kernels refuse (ENV_REFUSED) until the
+    // an unsupported selection keeps the previous one AND is recorded: the calls that launch family-dependent kernels refuse until the
     // environment selects a family this library holds again -- a test that switches families on a product handle must not pass vacuously
     const Knobs k = read_knobs();
     if (ilqr::variants_supported(k.var)) { c->knobs = k; c->env_refused = false; }
     else { c->env_refused = true; c->err = "ILQR_ENV_PER_CALL: the environment selects a kernel family this library does not hold (see ilqr_hip_create)"; }
   }
-  ilqr::set_variants(c->knobs.var);
 }
-#define ENV_REFUSED(c) do { if ((c)->env_refused) return ILQR_ERR_UNSUPPORTED; } while (0)
+static inline int enter_launching(ilqr_hip_ctx* c) { enter(c); return c->env_refused ? ILQR_ERR_UNSUPPORTED : ILQR_OK; }
 
 extern "C" {
 
@@ -375,8 +377,8 @@ int ilqr_hip_set_early_exit_gate(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_
 // and always in contact mode) or the one-lane ones.  Iteration 0 of a solve may re-roll a cold start BESIDE the linearisation only
 // if it is this very kernel under these very dynamics parameters (bit-identical result); compared field by field, not by memcmp
 // (padding bytes).
-static int rollout_kernel_identity(const h1::ProblemDev& P) {
-  return ilqr::variant_scalar_dyn() ? 2 : ((ilqr::variant_rollout_split() || h1::constrained(P.dyn)) ? 1 : 0);
+static int rollout_kernel_identity(const ilqr::Variants& V, const h1::ProblemDev& P) {
+  return V.scalar_dyn ? 2 : ((V.rollout_split || h1::constrained(P.dyn)) ? 1 : 0);
 }
 static bool same_dyn(const h1::DynParams& a, const h1::DynParams& b) {
   return a.h == b.h && a.g[0] == b.g[0] && a.g[1] == b.g[1] && a.g[2] == b.g[2] && a.contact == b.contact && a.soft == b.soft && a.mu == b.mu && a.limits == b.limits && a.lim_k == b.lim_k;
@@ -385,28 +387,28 @@ static int cold_start_device(ilqr_hip_ctx* c, const double* x0_dev, const double
   const size_t B = c->B, N = c->N;
   HIPCHK(c, hipMemcpyAsync(c->S.x0, x0_dev, B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->S.ubar, uinit_dev, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  ilqr::launch_rollout(c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream);  // N rollouts (ilqr.cpp:113-115)
+  ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream);  // N rollouts (ilqr.cpp:113-115)
   HIPCHK(c, hipGetLastError());
   c->initialized = true;
   c->xbar_rolled = true;
-  c->rolled_variant = rollout_kernel_identity(c->P); c->rolled_dyn = c->P.dyn;
+  c->rolled_variant = rollout_kernel_identity(c->knobs.var, c->P); c->rolled_dyn = c->P.dyn;
   return ILQR_OK;
 }
 int ilqr_hip_initialize_device(ilqr_hip_ctx* c, const double* x0_device, const double* u_init_device) {
   if (!c || !x0_device || !u_init_device) return ILQR_ERR_ARG;
-  enter(c);
+  TRY(enter_launching(c));
   return cold_start_device(c, x0_device, u_init_device);
 }
 int ilqr_hip_initialize(ilqr_hip_ctx* c, const double* x0, const double* u_init, const double* prev_xbar, const double* prev_ubar) {
   if (!c || !x0) return ILQR_ERR_ARG;
-  enter(c);
+  TRY(enter_launching(c));
   const size_t B = c->B, N = c->N;
   if (prev_xbar && prev_ubar) {
     HIPCHK(c, hipMemcpyAsync(c->S.x0, x0, B * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_prevx, prev_xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_prevu, prev_ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
     ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);
-    ilqr::launch_last_step(c->S, c->P, c->stream);
+    ilqr::launch_last_step(c->knobs.var, c->S, c->P, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->initialized = true;
@@ -432,13 +434,13 @@ int ilqr_hip_initialize(ilqr_hip_ctx* c, const double* x0, const double* u_init,
 int ilqr_hip_initialize_warm_resident(ilqr_hip_ctx* c, const double* x0) {
   if (!c || !x0) return ILQR_ERR_ARG;
   if (!c->initialized) return ILQR_ERR_STATE;
-  enter(c);
+  TRY(enter_launching(c));
   const size_t B = c->B, N = c->N;
   HIPCHK(c, hipMemcpyAsync(c->S.x0, x0, B * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);
-  ilqr::launch_last_step(c->S, c->P, c->stream);
+  ilqr::launch_last_step(c->knobs.var, c->S, c->P, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->xbar_rolled = false;
@@ -561,8 +563,9 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // shadow target of the concurrent re-rollout: same rollouts as S.xbar, in the shadow buffer
   double* shadow = const_cast<double*>(shadow_base) + (S.xbar - c->S.xbar);
   int* stance_dyn = c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N;     // (same rollouts as S)
-  const double fold_h = ilqr::linearize_fold_h(P, c->jac_mode);
-  { StageTimer T(c, 0, st); ilqr::launch_rollout(S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st); ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
+  const ilqr::Variants& V = c->knobs.var;      // (the per-call re-read happened in the caller's prologue: V cannot change under a solve)
+  const double fold_h = ilqr::linearize_fold_h(V, P, c->jac_mode);
+  { StageTimer T(c, 0, st); ilqr::launch_rollout(V, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st); ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
   // With the convergence exit on, the launches of an iteration nobody needs are pure latency (17 launches that find nothing to
   // do): the count of rollouts active after iteration i (DevState::order_n, maintained by k_control) follows iteration i to the
   // host, which enqueues iteration i only after it has seen the count left by iteration i - 2 -- one full iteration stays
@@ -573,8 +576,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   const bool xbar_rolled = c->first_aside;
   // the operand-layout Riccati kernel (analytic Jacobians, riccati_pack.hip) has its producers write A_t, B_t and lxx~_t in its own
   // layout; the generic one-wave kernel reads only the tiles I >= J of lxx_t (t < N): the cost quadratics then leave the others unwritten
-  const int pack = (fold_h != 0.0 && ilqr::variant_pack()) ? 1 : 0;
-  const int lxx_lower = pack ? 2 : (ilqr::variant_backward() == 2 ? 1 : 0);
+  const int pack = (fold_h != 0.0 && V.pack()) ? 1 : 0;
+  const int lxx_lower = pack ? 2 : (V.backward == 2 ? 1 : 0);
   // (iteration 0 rewrites A_t, B_t, lxx_t of every rollout: a solve leaves one layout behind; ilqr_hip_solve_async has prepared the padding)
   c->lxx_layout = lxx_lower;
   c->ab_packed = pack != 0;
@@ -611,12 +614,12 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     if (concurrent_roll) {
       HIPCHK(c, hipStreamWaitEvent(G.r, G.fork, 0));
       DevState Sr = Sm; Sr.xbar = shadow;
-      { StageTimer T(c, 0, G.r); ilqr::launch_rollout(Sr, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, G.r); }
+      { StageTimer T(c, 0, G.r); ilqr::launch_rollout(V, Sr, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, G.r); }
       HIPCHK(c, hipEventRecord(G.roll, G.r));
     }
     { StageTimer T(c, 2, G.q); ilqr::launch_cost_quadratics(S, P, knot_mode, G.q, iter_l, lxx_lower, wl); }
     HIPCHK(c, hipEventRecord(G.join, G.q));
-    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(S, P, knot_mode, c->jac_mode, c->fd_eps, G.m, 3, iter_l, pack, wl, stance_dyn); }
+    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(V, S, P, knot_mode, c->jac_mode, c->fd_eps, G.m, 3, iter_l, pack, wl, stance_dyn); }
     if (concurrent_roll && G.lin && G.adopt) {
       HIPCHK(c, hipEventRecord(G.lin, G.m));
       HIPCHK(c, hipStreamWaitEvent(G.r, G.lin, 0)); HIPCHK(c, hipStreamWaitEvent(G.r, G.join, 0));
@@ -626,8 +629,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     return ILQR_OK;
   };
   auto rolls_aside = [&](int iter) {
-    const bool first_aside = iter == 0 && xbar_rolled && !ilqr::variant_scalar_dyn();
-    return (iter > 0 || first_aside) && !c->knobs.reuse_rollout && c->knobs.overlap_rollout && (h1::constrained(P.dyn) || ilqr::variant_ls_split() == ilqr::variant_rollout_split());   // (contact mode: both on the two-lane kernels)
+    const bool first_aside = iter == 0 && xbar_rolled && !V.scalar_dyn;
+    return (iter > 0 || first_aside) && !c->knobs.reuse_rollout && c->knobs.overlap_rollout && (h1::constrained(P.dyn) || V.ls_split == V.rollout_split);   // (contact mode: both on the two-lane kernels)
   };
   // Early continuation: the rollouts whose first line search of iteration i accepted a step are done with iteration i; their share of
   // iteration i + 1's concurrent region (group A) starts right behind the first control pass, on streams of its own, while the
@@ -646,7 +649,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     }
     const bool concurrent_roll = rolls_aside(iter);
     if (!prev_split) {
-      if ((iter == 0 || !c->knobs.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
+      if ((iter == 0 || !c->knobs.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(V, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
       if (iter == 0 && wait_lead) HIPCHK(c, hipStreamWaitEvent(st, wait_lead, 0));
       TRY(region(G0, st, S, sel_mode, iter, nullptr, concurrent_roll));
     } else {
@@ -675,15 +678,15 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
       HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
       ilqr::launch_spec_lambda(S, Tw.lambda, st2);
-      { StageTimer T(c, 3, st); ilqr::launch_backward(S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward(Tw, ilqr::MASK_ACTIVE, st2, fold_h, iter); }
+      { StageTimer T(c, 3, st); ilqr::launch_backward(V, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
+      { StageTimer T(c, 6, st2); ilqr::launch_backward(V, Tw, ilqr::MASK_ACTIVE, st2, fold_h, iter); }
       TRY(wait_adoption(st)); TRY(wait_adoption(st2));
       if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-      { StageTimer T(c, 4, st); ilqr::launch_line_search(S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
-      { StageTimer T(c, 7, st2); ilqr::launch_line_search(Tw, P, ilqr::MASK_ACTIVE, st2, iter, ls_bound); }
+      { StageTimer T(c, 4, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
+      { StageTimer T(c, 7, st2); ilqr::launch_line_search(V, Tw, P, ilqr::MASK_ACTIVE, st2, iter, ls_bound); }
       HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
       HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
-      { StageTimer T(c, 5, st); ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(P)); }
+      { StageTimer T(c, 5, st); ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P)); }
       if (gate) {
         HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
@@ -691,7 +694,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       prev_split = false;
       continue;
     }
-    if (c->twin && c->knobs.spec && c->knobs.spec_dual && S.order && gate && pass_bound <= 4 * c->knobs.spec_max && ilqr::spec_dual_available(P)) {
+    if (c->twin && c->knobs.spec && c->knobs.spec_dual && S.order && gate && pass_bound <= 4 * c->knobs.spec_max && ilqr::spec_dual_available(V, P)) {
       // The host's count is one iteration old: between spec_max and 4 spec_max the pass may or may not have shrunk below the
       // threshold by now.  Both orders are enqueued and the device takes one (launch_spec_gate): the twin's launches and the
       // one-rollout-per-wave line search see a count of zero unless the list holds <= spec_max rollouts, the sequential first line
@@ -704,8 +707,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
       HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
       ilqr::launch_spec_lambda(S, Tw.lambda, st2);
-      { StageTimer T(c, 3, st); ilqr::launch_backward(S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(Tw, st2, fold_h, list, g); }
+      { StageTimer T(c, 3, st); ilqr::launch_backward(V, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
+      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(V, Tw, st2, fold_h, list, g); }
       TRY(wait_adoption(st)); TRY(wait_adoption(st2));
       { StageTimer T(c, 4, st);
         ilqr::launch_line_search_list(S, P, st, list, g, c->knobs.spec_max);
@@ -715,21 +718,21 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
       HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
       { StageTimer T(c, 5, st);
-        ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(P), g);
-        ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, ilqr::ls_costs_per_knot(P), g + 1); }
-      { StageTimer T(c, 6, st); ilqr::launch_backward(S, ilqr::MASK_RETRY, st, fold_h, iter); }
-      { StageTimer T(c, 7, st); ilqr::launch_line_search(S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
-      { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(P)); }
+        ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P), g);
+        ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, ilqr::ls_costs_per_knot(V, P), g + 1); }
+      { StageTimer T(c, 6, st); ilqr::launch_backward(V, S, ilqr::MASK_RETRY, st, fold_h, iter); }
+      { StageTimer T(c, 7, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
+      { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P)); }
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
       prev_split = false;
       continue;
     }
-    { StageTimer T(c, 3, st); ilqr::launch_backward(S, ilqr::MASK_ACTIVE, st, fold_h, iter); }                                  // :601
+    { StageTimer T(c, 3, st); ilqr::launch_backward(V, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }                                  // :601
     TRY(wait_adoption(st));
     if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-    { StageTimer T(c, 4, st); ilqr::launch_line_search(S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }                  // :616
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, ilqr::ls_costs_per_knot(P)); }          // :619-620,645-655
+    { StageTimer T(c, 4, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }                  // :616
+    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, ilqr::ls_costs_per_knot(V, P)); }          // :619-620,645-655
     const bool split_next = can_split && iter + 1 < c->max_iter && rolls_aside(iter + 1);
     if (split_next) {
       // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
@@ -738,9 +741,9 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       const ilqr::WorkList wa{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
       TRY(region(GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
     }
-    { StageTimer T(c, 6, st); ilqr::launch_backward(S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
-    { StageTimer T(c, 7, st); ilqr::launch_line_search(S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }                   // :638
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(P)); }                      // :640-646
+    { StageTimer T(c, 6, st); ilqr::launch_backward(V, S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
+    { StageTimer T(c, 7, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }                   // :638
+    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P)); }                      // :640-646
     if (gate) {
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
@@ -768,11 +771,12 @@ int ilqr_hip_num_slices(const ilqr_hip_ctx* c) { return c ? slices_wanted(c, c->
 // solution) is carried by the two-knot tangent kernel only (k_lin_tangent2c<., 1 / 2>): the one-knot and scalar cross-check families
 // refuse it.
 static int jacobians_available(ilqr_hip_ctx* c) {
-  if (c->P.dyn.limits && c->jac_mode == ILQR_JAC_ANALYTIC && (ilqr::variant_lin_one_knot() || ilqr::variant_scalar_dyn())) {
+  if (c->jac_mode != ILQR_JAC_ANALYTIC || !(c->knobs.var.lin_one_knot || c->knobs.var.scalar_dyn)) return ILQR_OK;
+  if (c->P.dyn.limits) {
     c->err = "joint-limit rows (ilqr_hip_set_joint_limits): analytic Jacobians are not available in this kernel family (ILQR_LIN / ILQR_DYN), select ILQR_JAC_FD_FORWARD with ilqr_hip_set_options";
     return ILQR_ERR_UNSUPPORTED;
   }
-  if (c->P.dyn.contact >= ILQR_CONTACT_FRICTION_STANCE && c->jac_mode == ILQR_JAC_ANALYTIC && (ilqr::variant_lin_one_knot() || ilqr::variant_scalar_dyn())) {
+  if (c->P.dyn.contact >= ILQR_CONTACT_FRICTION_STANCE) {
     c->err = "contact modes 3 / 4 (Coulomb limit): analytic Jacobians are not available in this kernel family (ILQR_LIN / ILQR_DYN), select ILQR_JAC_FD_FORWARD with ilqr_hip_set_options";
     return ILQR_ERR_UNSUPPORTED;
   }
@@ -781,19 +785,18 @@ static int jacobians_available(ilqr_hip_ctx* c) {
 int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   if (!c->initialized || !c->refs_set) { c->err = "solve before initialize/set_references"; return ILQR_ERR_STATE; }
-  enter(c);      // (first: the checks below read this handle's kernel family, not the last one entered on this thread)
-  ENV_REFUSED(c);
-  if (int rc = jacobians_available(c)) return rc;
+  TRY(enter_launching(c));
+  TRY(jacobians_available(c));
   hipStream_t st = c->stream;
-  const DevState& S = c->S; const h1::ProblemDev& P = c->P;
+  const DevState& S = c->S; const h1::ProblemDev& P = c->P; const ilqr::Variants& V = c->knobs.var;
   c->spans.clear(); c->pool_next = 0;
   HIPCHK(c, hipMemsetAsync(c->d_mismatch, 0, sizeof(unsigned long long), st));
   const int k = slices_wanted(c, c->B);
   c->n_slices = k;
   c->spec_iterations = 0; c->split_iterations = 0;
   if (c->knobs.spec && k <= 1 && !c->twin && (c->B <= c->knobs.spec_max || (c->early_exit && early_exit_gate(c)))) TRY(ensure_twin(c));
-  if (ilqr::linearize_fold_h(P, c->jac_mode) != 0.0 && ilqr::variant_pack() && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
-  c->first_aside = c->xbar_rolled && c->rolled_variant == rollout_kernel_identity(P) && same_dyn(c->rolled_dyn, P.dyn);
+  if (ilqr::linearize_fold_h(V, P, c->jac_mode) != 0.0 && V.pack() && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
+  c->first_aside = c->xbar_rolled && c->rolled_variant == rollout_kernel_identity(V, P) && same_dyn(c->rolled_dyn, P.dyn);
   c->xbar_rolled = false;                                   // after this solve xbar is an accepted line-search candidate
   if (k <= 1) {
     TRY(enqueue_solve(c, S, P, st, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_roll, c->d_shadowx, nullptr, nullptr, c->ev_lin, c->ev_adopt));
@@ -826,7 +829,7 @@ int ilqr_hip_synchronize(ilqr_hip_ctx* c) {
 }
 int ilqr_hip_solve(ilqr_hip_ctx* c, const double* x0, double* cost_out) {
   if (!c) return ILQR_ERR_ARG;
-  enter(c);
+  TRY(enter_launching(c));
   if (x0) {      // (a new x0: the nominal trajectory is rolled out from it before the linearisation, as the reference does)
     HIPCHK(c, hipMemcpyAsync(c->S.x0, x0, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->xbar_rolled = false;
@@ -907,11 +910,11 @@ int ilqr_hip_set_trajectory(ilqr_hip_ctx* c, const double* xbar, const double* u
   c->xbar_rolled = false;
   return ILQR_OK;
 }
-#define STAGE_PRE if (!c) return ILQR_ERR_ARG; if (!c->initialized) return ILQR_ERR_STATE; enter(c); ENV_REFUSED(c)
+#define STAGE_CHECK if (!c) return ILQR_ERR_ARG; if (!c->initialized) return ILQR_ERR_STATE
 #define STAGE_POST HIPCHK(c, hipGetLastError()); HIPCHK(c, hipStreamSynchronize(c->stream)); return ILQR_OK
-int ilqr_hip_stage_rollout(ilqr_hip_ctx* c) { STAGE_PRE; ilqr::launch_rollout(c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream); STAGE_POST; }
-int ilqr_hip_stage_linearize(ilqr_hip_ctx* c) { STAGE_PRE; if (int rc = jacobians_available(c)) return rc; ilqr::launch_linearize(c->S, c->P, ilqr::MASK_ALL, c->jac_mode, c->fd_eps, c->stream, 3, -1, 0, nullptr, c->d_stance_dyn); c->lin_fold_h = ilqr::linearize_fold_h(c->P, c->jac_mode); c->ab_packed = false; c->ab_pads_clean = false; STAGE_POST; }
-int ilqr_hip_stage_cost_quadratics(ilqr_hip_ctx* c) { STAGE_PRE; if (!c->refs_set) return ILQR_ERR_STATE; ilqr::launch_cost_quadratics(c->S, c->P, ilqr::MASK_ALL, c->stream); c->lxx_layout = 0; STAGE_POST; }
+int ilqr_hip_stage_rollout(ilqr_hip_ctx* c) { STAGE_CHECK; TRY(enter_launching(c)); ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream); STAGE_POST; }
+int ilqr_hip_stage_linearize(ilqr_hip_ctx* c) { STAGE_CHECK; TRY(enter_launching(c)); TRY(jacobians_available(c)); ilqr::launch_linearize(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, c->jac_mode, c->fd_eps, c->stream, 3, -1, 0, nullptr, c->d_stance_dyn); c->lin_fold_h = ilqr::linearize_fold_h(c->knobs.var, c->P, c->jac_mode); c->ab_packed = false; c->ab_pads_clean = false; STAGE_POST; }
+int ilqr_hip_stage_cost_quadratics(ilqr_hip_ctx* c) { STAGE_CHECK; enter(c); if (!c->refs_set) return ILQR_ERR_STATE; ilqr::launch_cost_quadratics(c->S, c->P, ilqr::MASK_ALL, c->stream); c->lxx_layout = 0; STAGE_POST; }
 // layout conversions on demand (in place): what a consumer of the standard layout (getters, any kernel family but the operand-layout
 // one) or of the operand layout (stage API on riccati_pack.hip) calls first
 static void want_standard_ab(ilqr_hip_ctx* c) { if (c->ab_packed) { ilqr::launch_unpack_ab(c->S, c->packed_h, c->stream); c->ab_packed = false; c->ab_pads_clean = false; } }
@@ -920,31 +923,32 @@ static void want_standard_lxx(ilqr_hip_ctx* c, bool whole) {
   if (c->lxx_layout == 1 && whole) { ilqr::launch_mirror_lxx(c->S, c->stream); c->lxx_layout = 0; }
 }
 int ilqr_hip_stage_backward_pass(ilqr_hip_ctx* c) {
-  STAGE_PRE;
-  if (c->lin_fold_h != 0.0 && ilqr::variant_pack()) {
+  STAGE_CHECK; TRY(enter_launching(c));
+  const ilqr::Variants& V = c->knobs.var;
+  if (c->lin_fold_h != 0.0 && V.pack()) {
     // analytic Jacobians and the operand-layout kernel (riccati_pack.hip): convert in place what is not yet in its layout
     if (!c->ab_packed) { ilqr::launch_pack_ab(c->S, c->stream); c->ab_packed = true; c->packed_h = c->lin_fold_h; c->ab_pads_clean = true; }
     if (c->lxx_layout != 2) { want_standard_lxx(c, true); ilqr::launch_pack_lxx(c->S, c->stream); c->lxx_layout = 2; }
   } else {
     // any other family reads the standard layout (the one-wave kernel: the tiles I >= J of lxx_t, t < N, suffice)
     want_standard_ab(c);
-    want_standard_lxx(c, ilqr::variant_backward() != 2);
+    want_standard_lxx(c, V.backward != 2);
   }
-  ilqr::launch_backward(c->S, ilqr::MASK_ALL, c->stream, c->lin_fold_h);
+  ilqr::launch_backward(V, c->S, ilqr::MASK_ALL, c->stream, c->lin_fold_h);
   STAGE_POST;
 }
 int ilqr_hip_stage_total_cost(ilqr_hip_ctx* c, double* cost) {
-  STAGE_PRE; if (!cost || !c->refs_set) return ILQR_ERR_ARG;
-  ilqr::launch_rollout(c->S, c->P, ilqr::MASK_ALL, 0, 0, c->d_cost_tmp, c->stream);
+  STAGE_CHECK; TRY(enter_launching(c)); if (!cost || !c->refs_set) return ILQR_ERR_ARG;
+  ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 0, 0, c->d_cost_tmp, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(cost, c->d_cost_tmp, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
 int ilqr_hip_stage_line_search(ilqr_hip_ctx* c, int* improved, double* new_cost, double* alpha) {
-  STAGE_PRE; if (!c->refs_set) return ILQR_ERR_STATE;
-  ilqr::launch_rollout(c->S, c->P, ilqr::MASK_ALL, 0, 0, c->S.Jbase, c->stream);   // baseline = computeTotalCost(xbar, ubar), ilqr.cpp:317
-  ilqr::launch_line_search(c->S, c->P, ilqr::MASK_ALL, c->stream);
+  STAGE_CHECK; TRY(enter_launching(c)); if (!c->refs_set) return ILQR_ERR_STATE;
+  ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 0, 0, c->S.Jbase, c->stream);   // baseline = computeTotalCost(xbar, ubar), ilqr.cpp:317
+  ilqr::launch_line_search(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, c->stream);
   ilqr::launch_control(c->S, 2, 0, c->tol, 0, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1019,7 +1023,7 @@ int ilqr_hip_step(ilqr_hip_ctx* c, int count, const double* x, const double* u, 
 int ilqr_hip_set_contact_mode(ilqr_hip_ctx* c, int mode, double softness) {
   if (!c || (mode != ILQR_CONTACT_NONE && mode != ILQR_CONTACT_RIGID_STANCE && mode != ILQR_CONTACT_UNILATERAL_STANCE && mode != ILQR_CONTACT_FRICTION_STANCE && mode != ILQR_CONTACT_KINETIC_FRICTION_STANCE)) return ILQR_ERR_ARG;
   enter(c);
-  if (mode >= ILQR_CONTACT_FRICTION_STANCE && ilqr::variant_scalar_dyn()) { c->err = "contact modes 3 / 4 (Coulomb limit) exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+  if (mode >= ILQR_CONTACT_FRICTION_STANCE && c->knobs.var.scalar_dyn) { c->err = "contact modes 3 / 4 (Coulomb limit) exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
   if (mode == ILQR_CONTACT_RIGID_STANCE && c->P.stance_geom) { c->err = "contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4"; return ILQR_ERR_UNSUPPORTED; }
   c->P.dyn.contact = mode;
   if (softness > 0.0) c->P.dyn.soft = softness;
@@ -1028,7 +1032,7 @@ int ilqr_hip_set_contact_mode(ilqr_hip_ctx* c, int mode, double softness) {
 int ilqr_hip_set_joint_limits(ilqr_hip_ctx* c, int on) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (on && ilqr::variant_scalar_dyn()) { c->err = "joint-limit rows exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+  if (on && c->knobs.var.scalar_dyn) { c->err = "joint-limit rows exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
   c->P.dyn.limits = on ? 1 : 0;     // (a nominal rolled under the other setting is recognised by same_dyn)
   return ILQR_OK;
 }
@@ -1058,7 +1062,7 @@ static int plant_step(ilqr_hip_ctx* c, int count, const double* x, const double*
   }
   HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  ilqr::launch_step(count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right, geom, geom ? c->d_stance_out : nullptr);
+  ilqr::launch_step(c->knobs.var, count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right, geom, geom ? c->d_stance_out : nullptr);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (geom && stance_out) HIPCHK(c, hipMemcpyAsync(stance_out, c->d_stance_out, (size_t)count * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1067,12 +1071,12 @@ static int plant_step(ilqr_hip_ctx* c, int count, const double* x, const double*
 }
 int ilqr_hip_step_stance(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, double* x_next) {
   if (!c || count <= 0 || !x || !u || !x_next) return ILQR_ERR_ARG;
-  enter(c);
+  TRY(enter_launching(c));
   return plant_step(c, count, x, u, stance_left, stance_right, 0, nullptr, x_next);
 }
 // ---------------------------------------------------------------- stance from the foot hulls
 static const char* geometry_refusal(const ilqr_hip_ctx* c) {
-  if (ilqr::variant_scalar_dyn()) return "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s";
+  if (c->knobs.var.scalar_dyn) return "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s";
   if (c->P.dyn.contact == ILQR_CONTACT_RIGID_STANCE) return "contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4";
   return nullptr;
 }
@@ -1088,16 +1092,16 @@ int ilqr_hip_set_stance_source(ilqr_hip_ctx* c, int source) {
 }
 int ilqr_hip_step_geometry(ilqr_hip_ctx* c, int count, const double* x, const double* u, double* x_next, int* stance_out) {
   if (!c || count <= 0 || !x || !u || !x_next) return ILQR_ERR_ARG;
-  enter(c);
+  TRY(enter_launching(c));
   if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   return plant_step(c, count, x, u, 1, 1, 1, stance_out, x_next);
 }
 int ilqr_hip_get_stance(ilqr_hip_ctx* c, int* stance) {
   if (!c || !stance) return ILQR_ERR_ARG;
-  enter(c);
   const size_t B = c->B, N = c->N;
-  if (c->P.stance_geom) {
-    if (ilqr::variant_scalar_dyn()) { c->err = "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+  if (c->P.stance_geom) {      // (the two-lane family's kernel decides: this branch launches by family, the schedule's does not)
+    TRY(enter_launching(c));
+    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
     ilqr::launch_stance_geom_s(c->S, ilqr::MASK_ALL, nullptr, nullptr, c->d_stance_dyn, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(stance, c->d_stance_dyn, B * N * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1105,6 +1109,7 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* c, int* stance) {
     return ILQR_OK;
   }
   // the schedule's rows t = 0..N-1 (one shared set or one per rollout)
+  enter(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t per = (N + 1) * 2;
   std::vector<int> sched(c->P.stance_stride ? B * per : per);

@@ -67,15 +67,25 @@ struct DevState {
   int* order_an;       // [max_iter + 2]
 };
 
-void launch_rollout(const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
+// kernel variants (ILQR_DYN / ILQR_ROLLOUT / ILQR_LS / ILQR_BACKWARD / ILQR_LINT): read from the environment ONCE per handle
+// (ilqr_hip_create; read_variants) and kept there; every launcher whose choice of kernel depends on the family takes the handle's copy
+// as its first argument.  backward: 0 four-wave MFMA, 1 LDS + VALU, 2 one wave per rollout; fold: see read_variants
+struct Variants {
+  int scalar_dyn, rollout_split, ls_split, backward, fold, lin_one_knot;
+  bool pack() const { return backward == 2 && fold == 2; }      // the operand-layout Riccati kernel (riccati_pack.hip) is in use
+};
+Variants read_variants();
+int variants_supported(const Variants& v);      // 0: the environment selects a cross-check family this build does not hold (-DILQR_LEGACY_KERNELS)
+
+void launch_rollout(const Variants& V, const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
 // geom / st_out: stance from each item's own feet (ProblemDev::stance_geom) / the flags it decided, [count][2] (two-lane kernels only)
-void launch_step(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l = 1, int stance_r = 1, int geom = 0, int* st_out = nullptr);
+void launch_step(const Variants& V, int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l = 1, int stance_r = 1, int geom = 0, int* st_out = nullptr);
 // pack != 0 (a solve whose backward pass is the operand-layout Riccati kernel): A_t, B_t in the layout of riccati_pack.h (the two-knot
 // analytic kernels write it themselves, any other producer is followed by the conversion kernel)
 struct WorkList;
 // stance_dyn: [S.B][N][2] scratch of the stance source GEOMETRY (ProblemDev::stance_geom) -- the analytic Jacobians hold the nominal knots'
 // decisions fixed, decided into it first
-void launch_linearize(const DevState& S, const h1::ProblemDev& P, int mode, int jac_mode, double eps, hipStream_t st, int phases = 3, int iter = -1, int pack = 0, const WorkList* wl = nullptr,
+void launch_linearize(const Variants& V, const DevState& S, const h1::ProblemDev& P, int mode, int jac_mode, double eps, hipStream_t st, int phases = 3, int iter = -1, int pack = 0, const WorkList* wl = nullptr,
                       int* stance_dyn = nullptr);
 // lower = 1: knots t < N get only the tiles I >= J of lxx (what k_backward_wave loads); 2: every knot in the operand layout of
 // riccati_pack.h (lx in row / column "aug"); the stage API always asks for the full matrix (0)
@@ -87,7 +97,7 @@ inline WorkList work_list(const DevState& S, int mode, int iter) {
   const int slot = 2 * iter + (mode == MASK_RETRY ? 1 : 0);
   return WorkList{S.order + (size_t)slot * S.B, S.order_n + slot};
 }
-void launch_backward(const DevState& S, int mode, hipStream_t st, double fold_h = 0.0, int iter = -1);
+void launch_backward(const Variants& V, const DevState& S, int mode, hipStream_t st, double fold_h = 0.0, int iter = -1);
 // speculative lambda retry (ilqr_kernels.hip k_control_spec): T = the twin view whose K, kff, Vx, Vxx, candidates and lambda are its own
 void launch_spec_lambda(const DevState& S, double* lambda2, hipStream_t st);
 void launch_control_spec(const DevState& S, const DevState& T, int iter, double tol, int early_exit, hipStream_t st, int sum_knots, const int* gate = nullptr);
@@ -95,35 +105,24 @@ void launch_control_spec(const DevState& S, const DevState& T, int iter, double 
 // the speculative launches), g[1] = 0 / 1 (gate of the sequential bookkeeping), g[2] = 0 / n (count of the sequential first line search), with
 // n = the length of list (iter, 0).  The launchers below take an explicit list / count (default kernel families only: spec_dual_available).
 void launch_spec_gate(const DevState& S, int iter, int max, int* g, hipStream_t st);
-bool spec_dual_available(const h1::ProblemDev& P);
-void launch_backward_list(const DevState& S, hipStream_t st, double fold_h, const int* list, const int* count);
+bool spec_dual_available(const Variants& V, const h1::ProblemDev& P);
+void launch_backward_list(const Variants& V, const DevState& S, hipStream_t st, double fold_h, const int* list, const int* count);
 void launch_line_search_list(const DevState& S, const h1::ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts);
-double linearize_fold_h(const h1::ProblemDev& P, int jac_mode);
+double linearize_fold_h(const Variants& V, const h1::ProblemDev& P, int jac_mode);
 // max_rollouts: upper bound of the rollouts this pass can select (the batch, or -- with the early-exit gate -- the count of
 // still-active rollouts the host saw two iterations ago): at most 1024 -> one rollout per wave in the two-lane line search
-void launch_line_search(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int max_rollouts = -1);
+void launch_line_search(const Variants& V, const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int max_rollouts = -1);
 void launch_control(const DevState& S, int phase, int iter, double tol, int early_exit, hipStream_t st, int sum_knots = 0, const int* gate = nullptr);
-bool ls_costs_per_knot(const h1::ProblemDev& P);
+bool ls_costs_per_knot(const Variants& V, const h1::ProblemDev& P);
 void launch_solve_begin(const DevState& S, hipStream_t st);
 void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, unsigned long long* mismatches, hipStream_t st);
 void launch_warm_shift(const DevState& S, const double* prev_x, const double* prev_u, hipStream_t st);
-void launch_last_step(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
+void launch_last_step(const Variants& V, const DevState& S, const h1::ProblemDev& P, hipStream_t st);
 void launch_compute_control(const DevState& S, const double* x_meas, double* u_out, hipStream_t st);
 void launch_pack_first_knot(const DevState& S, double* u0, double* K0, hipStream_t st);
 void launch_pack_payload(const DevState& S, int with_gains, double* out, hipStream_t st);
 void launch_mirror_lxx(const DevState& S, hipStream_t st);   // fill the strictly upper tiles of lxx_t, t < N, from the lower ones
 int backward_needs_lds_attr();
-// kernel variants (ILQR_DYN / ILQR_ROLLOUT / ILQR_LS / ILQR_BACKWARD / ILQR_LINT): read from the environment ONCE per handle
-// (ilqr_hip_create; read_variants) and installed for the calling host thread at the top of every C-ABI call (set_variants)
-struct Variants { int scalar_dyn, rollout_split, ls_split, backward, fold, lin_one_knot; };
-Variants read_variants();
-void set_variants(const Variants& v);
-int variants_supported(const Variants& v);      // 0: the environment selects a cross-check family this build does not hold (-DILQR_LEGACY_KERNELS)
-int variant_ls_split();
-int variant_rollout_split();
-int variant_backward();
-int variant_scalar_dyn();
-int variant_lin_one_knot();
 size_t backward_lds_bytes();
 size_t lin_dump_doubles();
 size_t quad_rec_doubles(size_t knots);
@@ -151,7 +150,6 @@ void launch_backward_wave(const DevState& S, int mode, hipStream_t st, double fo
 size_t backward_mfma_lds_bytes();
 // riccati_pack.hip: the one-wave kernel on the operand layout of riccati_pack.h and the conversions between that layout and the
 // standard one (in place, per knot region)
-int variant_pack();
 void launch_backward_pack(const DevState& S, int mode, hipStream_t st, double fold_h, const int* list, const int* count);
 void launch_pack_ab(const DevState& S, hipStream_t st, int mode = MASK_ALL, const int* list = nullptr, const int* count = nullptr);
 void launch_pack_zero_pads(const DevState& S, hipStream_t st);

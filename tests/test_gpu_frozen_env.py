@@ -109,18 +109,59 @@ def test_supported_switches_are_taken_at_creation_and_only_there():
 
 def test_per_call_handle_refuses_a_family_the_product_library_does_not_hold():
     """ILQR_ENV_PER_CALL=1 (the test suite's mode) on the PRODUCT library: switching to a cross-check family around a call no longer passes
-    vacuously on the default family -- the call that would launch kernels returns ILQR_ERR_UNSUPPORTED; back on a held family it runs."""
+    vacuously on the default family -- every call that would launch a family-dependent kernel returns ILQR_ERR_UNSUPPORTED, the getters
+    keep answering; back on a held family it runs."""
     from mpc_ilqr_mujoco_amd import solver as sv
     B = 2
     prob, x0, ui = _problem(B, 13)
     with env(ILQR_ENV_PER_CALL="1"):
         s = sv.BatchedILQR(B)
         c0, t0, K0 = _solve(s, prob, x0, ui, iters=2)
+        held = lambda: (s.xbar(), s.gains_K(), *s.trace(), *s.linearization())
+        before = held()
         with env(ILQR_BACKWARD="valu"):
             with pytest.raises(sv.ILQRError, match="kernel family"):
                 s.solve(x0)
             with pytest.raises(sv.ILQRError, match="kernel family"):
                 s.stage_backward_pass()
+            # every entry point that reaches a family-dependent launcher refuses, not only the solve ...
+            for call in (lambda: s.initialize(x0, ui), lambda: s.initialize_warm_resident(x0), lambda: s.step(x0, ui[:, 0]),
+                         s.stage_rollout, s.stage_linearize, s.stage_line_search):
+                with pytest.raises(sv.ILQRError, match="kernel family"):
+                    call()
+            # ... and the getters never do: they still return what the handle held before the block
+            for a, b in zip(before, held()):
+                assert np.array_equal(a, b)
         c1, t1, K1 = _solve(s, prob, x0, ui, iters=2)
         assert np.array_equal(c0, c1) and np.array_equal(K0, K1)
         s.close()
+
+
+def test_two_frozen_handles_of_different_families_interleave_on_one_thread():
+    """The kernel family belongs to the handle: two frozen handles on the TEST library, one of the default family and one on the
+    four-wave Riccati kernel with the one-lane line search and rollout, driven in turn from one host thread, each compute bit for bit
+    what the same handle computes when it is driven alone."""
+    from mpc_ilqr_mujoco_amd import solver as sv
+    B = 3
+    prob, x0, ui = _problem(B, 14)
+    other = dict(ILQR_BACKWARD="wg", ILQR_LS="r", ILQR_ROLLOUT="r")
+    with env(ILQR_ENV_PER_CALL=None, **{k: None for k in other}):
+        a = sv.BatchedILQR(B, lib_path=sv.LEGACY_LIB_PATH)
+    with env(ILQR_ENV_PER_CALL=None, **other):
+        b = sv.BatchedILQR(B, lib_path=sv.LEGACY_LIB_PATH)
+    alone = {s: _solve(s, prob, x0, ui) for s in (a, b)}
+
+    def prepare(s):
+        s.set_problem(prob); s.set_max_iterations(3); s.set_options(early_exit=False)
+        s.set_regularization(1e-6)
+
+    def check(s, cost):
+        c, t, K = alone[s]
+        assert np.array_equal(cost, c) and np.array_equal(s.trace()[0], t) and np.array_equal(s.gains_K(), K)
+
+    for first, second in ((a, b), (b, a)):
+        prepare(first); prepare(second)
+        first.initialize(x0, ui); second.initialize(x0, ui)
+        c_first = first.solve(x0); c_second = second.solve(x0)
+        check(first, c_first); check(second, c_second)
+    a.close(); b.close()
