@@ -252,6 +252,59 @@ int ilqr_hip_step_geometry(ilqr_hip_ctx* ctx, int count, const double* x, const 
    decided from xbar under ILQR_STANCE_GEOMETRY (get_contacts.py:96-147 applied to the nominal), the schedule's rows otherwise. */
 int ilqr_hip_get_stance(ilqr_hip_ctx* ctx, int* stance);
 
+/* ---- device-resident plant: the closed loop of runSimulation (main/humanoid_mpc.cpp:122-190) without a host round trip per MPC step.
+   The reference's loop reads the plant state (:131-132), calls MPC::stepOnce (:143), holds u_apply for physics_steps_per_mpc =
+   int(dt / physics_dt) plant steps (:128,167-170; physics_dt: config.yaml:19, main:99) and guards against non-finite states and controls
+   (:134-137,162-165).  Here the plant state lives in the handle, one per rollout, and ONE kernel per MPC step advances it under the policy
+   the handle has just solved -- the first knot (xbar_0, ubar_0, K_0) of "nominal trajectories + TV-LQR gains" (include/ilqr/ilqr.hpp:10-16).
+   The plant is the model's dynamics (contact mode, friction, joint-limit rows, gravity of the handle) at the step dt / substeps.  Per MPC
+   step:  set references / schedule -> ilqr_hip_initialize_warm_from_plant -> ilqr_hip_solve(ctx, NULL, cost) -> ilqr_hip_plant_advance;
+   the solve's own synchronisation is the only one.  Not provided: external wrenches, a contact model other than the solver's, solving
+   every m-th plant step only. */
+/* Upload the plant state x[B][51] (robot.getState's counterpart in reverse: RobotUtils::setState).  Every rollout becomes alive, a pending
+   kick is dropped, the history cursor returns to 0.  Synchronises the handle's stream. */
+int ilqr_hip_plant_reset(ilqr_hip_ctx* ctx, const double* x /*[B][51]*/);
+/* substeps >= 1: plant steps per MPC step, each of dt / substeps (main:128).  feedback_mode 0: the reference's loop, u = ubar_0 +
+   K_0 (x - xbar_0) evaluated once and held (main:167-170); 1: the same law re-evaluated on (xbar_0, ubar_0, K_0) before every substep --
+   the gains tracked at the physics rate.  contact_source: ILQR_STANCE_SCHEDULE -- the stance rows of contact modes 1-4 sit on the feet
+   that row 0 of the current contact schedule marks (per set); ILQR_STANCE_GEOMETRY -- every substep decides from the plant's own foot
+   hulls, as ilqr_hip_step_geometry does (refused with ILQR_ERR_UNSUPPORTED where ilqr_hip_set_stance_source refuses; contact mode 0 has no
+   stance rows and ignores it).  Defaults 1, 0, SCHEDULE.  Anything else: ILQR_ERR_ARG.  Launches nothing. */
+int ilqr_hip_plant_configure(ilqr_hip_ctx* ctx, int substeps, int feedback_mode, int contact_source);
+/* Arm a one-shot velocity kick dv[B][25] (order of qvel): the next advance adds it to the plant's qvel before it evaluates the control law,
+   then it is gone.  Synchronises the handle's stream (the caller's buffer is free on return).  No reference counterpart (xfrc_applied is
+   not modelled). */
+int ilqr_hip_plant_kick(ilqr_hip_ctx* ctx, const double* dv /*[B][25]*/);
+/* One MPC interval of the plant (main:162-170): kick, control law (src/ilqr/mpc.cpp:97-101; a u with a non-finite entry becomes zero,
+   main:162-165; the step clamps u to the control range, the reported u is unclamped), `substeps` plant steps, then x, u (as applied in the
+   last substep), the stance flags of the last substep and `alive` are written back, and a row of the history ring if there is one.
+   A rollout whose state is or becomes non-finite (main:134-137 breaks the loop) gets alive = 0 and is never advanced again: its state stays
+   as it was before that advance, its control reads zero; the other rollouts are not affected by it.  ENQUEUES on the handle's stream and
+   returns: no synchronisation.  The plant always runs on the two-lane step (the default family's), also on a handle of the test library
+   whose environment selects the scalar dynamics (ILQR_DYN=s), where ilqr_hip_step runs the scalar kernel.
+   ILQR_ERR_STATE before the first solve or before ilqr_hip_plant_reset; ILQR_ERR_UNSUPPORTED while an
+   ILQR_ENV_PER_CALL re-read names an absent kernel family (see ilqr_hip_reload_environment) or the GEOMETRY source meets contact mode 1. */
+int ilqr_hip_plant_advance(ilqr_hip_ctx* ctx);
+/* ilqr_hip_initialize_warm_resident with x0 taken from the plant state on the device (MPC::stepOnce, src/ilqr/mpc.cpp:58-60; shift of
+   ilqr.cpp:68-80): same kernels, same result bit for bit, nothing uploaded and NO synchronisation.  ILQR_ERR_STATE before a first
+   initialize or before ilqr_hip_plant_reset. */
+int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* ctx);
+/* History ring of `steps` rows (0: free it): every advance appends the state it started from (behind its kick -- the x the control law
+   saw) and the control it reported; the oldest row is overwritten once the ring is full.  Resets the cursor; synchronises. */
+int ilqr_hip_plant_set_history(ilqr_hip_ctx* ctx, int steps);
+/* x[rows][B][51], u[rows][B][19] (either may be NULL; sized for the ring's rows), oldest first; *steps_recorded = min(advances since the
+   last reset / set_history, rows).  ONE synchronisation for the whole run and at most two copies per array (a ring that has wrapped is two
+   contiguous runs) -- MPC::logCurrentStep's data, src/ilqr/mpc.cpp:181-262. */
+int ilqr_hip_plant_get_history(ilqr_hip_ctx* ctx, double* x, double* u, int* steps_recorded);
+/* robot.getState (main:131-132) and the companions of the last advance; each synchronises the handle's stream.  ILQR_ERR_STATE before
+   ilqr_hip_plant_reset. */
+int ilqr_hip_plant_get_state(ilqr_hip_ctx* ctx, double* x /*[B][51]*/);
+int ilqr_hip_plant_get_control(ilqr_hip_ctx* ctx, double* u /*[B][19]*/);
+int ilqr_hip_plant_get_stance(ilqr_hip_ctx* ctx, int* stance /*[B][2]*/);
+int ilqr_hip_plant_get_alive(ilqr_hip_ctx* ctx, int* alive /*[B]*/);
+/* The plant state as a device pointer [B][51], for a caller that chains its own kernels on ilqr_hip_stream; no synchronisation. */
+int ilqr_hip_plant_state_device(ilqr_hip_ctx* ctx, const double** x_device);
+
 /* per-stage device time of the last solve in milliseconds, keyed like the reference's profiler
    (src/ilqr/ilqr.cpp:537-639): 0 computeCost/rollout, 1 linearization, 2 costQuadratics, 3 backwardPass,
    4 lineSearch, 5 control, 6 backwardPass (lambda-retry launch), 7 lineSearch (lambda-retry launch);

@@ -149,6 +149,27 @@ class iLQR {
   int horizon() const { return N_; }
   int batch() const { return B_; }
 
+  // ---- device-resident plant (ilqr_hip.h ilqr_hip_plant_*): runSimulation's loop body, main/humanoid_mpc.cpp:122-190, kept on the device.
+  // Per MPC step: setWindow-style setters -> initializeWarmFromPlant() -> ilqr_hip_solve(handle(), nullptr, cost) -> plantAdvance().
+  void plantReset(const Vec& x /*[batch][51]*/) { checkState(x); chk(ilqr_hip_plant_reset(ctx_, x.data())); }          // robot.setState
+  void plantConfigure(int substeps, int feedback_mode = 0, int contact_source = ILQR_STANCE_SCHEDULE) { chk(ilqr_hip_plant_configure(ctx_, substeps, feedback_mode, contact_source)); }   // main:128
+  void plantKick(const Vec& dv /*[batch][25]*/) { if (dv.size() != (size_t)B_ * ILQR_NV) throw std::runtime_error("dv must hold batch * 25 doubles"); chk(ilqr_hip_plant_kick(ctx_, dv.data())); }
+  void plantAdvance() { chk(ilqr_hip_plant_advance(ctx_)); }                                                           // main:162-170; enqueues only
+  void initializeWarmFromPlant() { chk(ilqr_hip_initialize_warm_from_plant(ctx_)); }                                   // mpc.cpp:58-60; enqueues only
+  void plantSetHistory(int steps) { chk(ilqr_hip_plant_set_history(ctx_, steps)); hist_rows_ = steps; }
+  // rows recorded; x[rows][batch][51], u[rows][batch][19], oldest first
+  int plantHistory(Vec& x, Vec& u) {
+    x.assign((size_t)hist_rows_ * B_ * ILQR_NX, 0.0); u.assign((size_t)hist_rows_ * B_ * ILQR_NU, 0.0);
+    int rec = 0; chk(ilqr_hip_plant_get_history(ctx_, x.data(), u.data(), &rec));
+    x.resize((size_t)rec * B_ * ILQR_NX); u.resize((size_t)rec * B_ * ILQR_NU);
+    return rec;
+  }
+  Vec plantState() { Vec x((size_t)B_ * ILQR_NX); chk(ilqr_hip_plant_get_state(ctx_, x.data())); return x; }           // robot.getState, main:131-132
+  Vec plantControl() { Vec u((size_t)B_ * ILQR_NU); chk(ilqr_hip_plant_get_control(ctx_, u.data())); return u; }
+  std::vector<int> plantStance() { std::vector<int> s((size_t)B_ * 2); chk(ilqr_hip_plant_get_stance(ctx_, s.data())); return s; }
+  std::vector<int> plantAlive() { std::vector<int> a((size_t)B_); chk(ilqr_hip_plant_get_alive(ctx_, a.data())); return a; }   // main:134-137
+  const double* plantStateDevice() { const double* p = nullptr; chk(ilqr_hip_plant_state_device(ctx_, &p)); return p; }
+
  private:
   void chk(int rc) { if (rc != ILQR_OK) throw std::runtime_error(std::string("ilqr_hip: ") + ilqr_hip_last_error(ctx_)); }
   // x0 carries one state per rollout of the handle (the C ABI copies batch * 51 doubles)
@@ -164,6 +185,7 @@ class iLQR {
   }
   ilqr_hip_ctx* ctx_ = nullptr;
   int N_, B_;
+  int hist_rows_ = 0;
 };
 
 // MPC (include/ilqr/mpc.hpp:18-47, src/ilqr/mpc.cpp) for batch 1.  `window(t_idx, x_ref, u_ref, com_ref)` plays the role of

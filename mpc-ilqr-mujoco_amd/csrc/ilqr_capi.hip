@@ -131,6 +131,14 @@ struct ilqr_hip_ctx {
   hipStream_t a1 = nullptr;     // (its cost quadratics and re-rollout share streams 2 and 3 with the other group, see enqueue_solve)
   hipEvent_t evA_fork = nullptr, evA_join = nullptr, evA_roll = nullptr, evA_lin = nullptr, evA_adopt = nullptr;
   int split_iterations = 0;   // iterations of the last solve whose concurrent region ran in two groups
+  // device-resident plant (ilqr_hip_plant_*; plant_kernels.hip): every buffer is owned here and freed by ilqr_hip_destroy
+  ilqr::PlantDev plant{};
+  bool plant_set = false;     // ilqr_hip_plant_reset has given it a state
+  bool solved = false;        // a solve has been enqueued: the first knot of xbar / ubar / K is a policy
+  bool plant_kick = false;    // plant.dv holds a kick for the next advance
+  int plant_substeps = 1, plant_feedback = 0, plant_source = ILQR_STANCE_SCHEDULE;
+  int hist_cap = 0;           // rows of the history ring (0: none)
+  long hist_n = 0;            // advances recorded since the last reset / set_history
 };
 
 #define HIPCHK(ctx, call)                                                                   \
@@ -164,8 +172,11 @@ struct StageTimer {
 };
 
 // Prologue of every entry point that touches the device, called after its argument checks.  The kernel family is c->knobs.var and
-// nothing else: whatever depends on it takes an ilqr::Variants argument.  An entry point uses enter_launching iff it calls, directly or
-// through a static helper, a function that takes one; every other one uses enter and never refuses.
+// nothing else: whatever depends on it takes an ilqr::Variants argument.  An entry point uses enter_launching if it calls, directly or
+// through a static helper, a function that takes one; so does ilqr_hip_plant_advance, whose kernel exists in one family only (the
+// two-lane step, whatever the handle's family: on a scalar-dynamics handle of the test library the plant and ilqr_hip_step therefore run
+// different kernels) -- it steps the model, and a handle whose environment names an absent family has no model to speak of.  Every other
+// entry point uses enter and never refuses.
 static inline void enter(ilqr_hip_ctx* c) {
   hipSetDevice(c->device);
   if (c->knobs.per_call) {
@@ -225,8 +236,9 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   A(dalloc(c, &c->d_xref, B * (N + 1) * n)); A(dalloc(c, &c->d_uref, B * N * m)); A(dalloc(c, &c->d_comref, B * (N + 1) * 3));
   A(dalloc(c, &c->d_eeref, B * (N + 1) * 6)); A(dalloc(c, &c->d_comvelref, B * (N + 1) * 3)); A(dalloc(c, &c->d_stance, B * (N + 1) * 2));
   A(dalloc(c, &c->d_stance_dyn, B * N * 2));
+  A(dalloc(c, &c->plant.x, B * n)); A(dalloc(c, &c->plant.u, B * m)); A(dalloc(c, &c->plant.dv, B * ILQR_NV)); A(dalloc(c, &c->plant.stance, B * 2)); A(dalloc(c, &c->plant.alive, B));
   if (rc != ILQR_OK) { *out = c; return rc; }
-  if (ilqr::backward_needs_lds_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; *out = c; return ILQR_ERR_HIP; }
+  if (ilqr::backward_needs_lds_attr() != 0 || ilqr::plant_kernels_set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; *out = c; return ILQR_ERR_HIP; }
   h1::ProblemDev& P = c->P;
   P.N = horizon; P.dyn.h = dt; P.dyn.g[0] = 0; P.dyn.g[1] = 0; P.dyn.g[2] = -9.81; P.dyn.contact = 0; P.dyn.soft = 1e-5; P.dyn.mu = 1.0; P.dyn.limits = 0; P.dyn.lim_k = 0.0;
   for (int i = 0; i < ILQR_NX; ++i) { P.Q[i] = 1.0; P.Qf[i] = 1.0; }
@@ -262,6 +274,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an}; for (void* p : gp) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -818,6 +831,7 @@ int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
     }
   }
   HIPCHK(c, hipGetLastError());
+  c->solved = true;
   return ILQR_OK;
 }
 int ilqr_hip_synchronize(ilqr_hip_ctx* c) {
@@ -1116,6 +1130,116 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* c, int* stance) {
   HIPCHK(c, hipMemcpy(sched.data(), c->d_stance, sched.size() * sizeof(int), hipMemcpyDeviceToHost));
   for (size_t b = 0; b < B; ++b)
     std::memcpy(stance + b * N * 2, sched.data() + (c->P.stance_stride ? b * per : 0), N * 2 * sizeof(int));
+  return ILQR_OK;
+}
+// ---------------------------------------------------------------- device-resident plant (plant_kernels.hip)
+int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
+  if (!c || !x) return ILQR_ERR_ARG;
+  enter(c);
+  const size_t B = c->B;
+  const std::vector<int> ones(B, 1);
+  HIPCHK(c, hipMemcpyAsync(c->plant.x, x, B * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->plant.alive, ones.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->plant.u, 0, B * ILQR_NU * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->plant.stance, 0, B * 2 * sizeof(int), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's buffers are free on return)
+  c->plant_set = true; c->plant_kick = false; c->hist_n = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_configure(ilqr_hip_ctx* c, int substeps, int feedback_mode, int contact_source) {
+  if (!c || substeps < 1 || (feedback_mode != 0 && feedback_mode != 1) || (contact_source != ILQR_STANCE_SCHEDULE && contact_source != ILQR_STANCE_GEOMETRY)) return ILQR_ERR_ARG;
+  enter(c);
+  if (contact_source == ILQR_STANCE_GEOMETRY) {
+    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  }
+  c->plant_substeps = substeps; c->plant_feedback = feedback_mode; c->plant_source = contact_source;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_kick(ilqr_hip_ctx* c, const double* dv) {
+  if (!c || !dv) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipMemcpyAsync(c->plant.dv, dv, (size_t)c->B * ILQR_NV * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->plant_kick = true;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->solved || !c->plant_set) { c->err = "plant_advance before a solve / before ilqr_hip_plant_reset"; return ILQR_ERR_STATE; }
+  TRY(enter_launching(c));
+  const bool geom = c->plant_source == ILQR_STANCE_GEOMETRY;
+  if (geom) {      // (the contact mode or the family may have changed since plant_configure)
+    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  }
+  h1::DynParams dyn = c->P.dyn;      // the plant: the model's parameters at the physics step (main/humanoid_mpc.cpp:99,128)
+  dyn.h = c->P.dyn.h / c->plant_substeps;
+  const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
+  ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, (geom && dyn.contact != 0) ? 1 : 0, c->plant_substeps, c->plant_feedback, c->plant_kick ? 1 : 0, row, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->plant_kick = false;
+  if (row >= 0) c->hist_n += 1;
+  return ILQR_OK;      // asynchronous on the handle's stream
+}
+int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->initialized || !c->plant_set) return ILQR_ERR_STATE;
+  TRY(enter_launching(c));
+  const size_t B = c->B, N = c->N;
+  HIPCHK(c, hipMemcpyAsync(c->S.x0, c->plant.x, B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);      // (k_warm_shift reads x0 from S.x0: the plant's state by the copy above)
+  ilqr::launch_last_step(c->knobs.var, c->S, c->P, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->xbar_rolled = false;
+  return ILQR_OK;      // asynchronous on the handle's stream
+}
+int ilqr_hip_plant_set_history(ilqr_hip_ctx* c, int steps) {
+  if (!c || steps < 0) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (an advance in flight may still write the ring)
+  if (c->plant.hist_x) hipFree(c->plant.hist_x);
+  if (c->plant.hist_u) hipFree(c->plant.hist_u);
+  c->plant.hist_x = c->plant.hist_u = nullptr; c->hist_cap = 0; c->hist_n = 0;
+  if (steps > 0) {
+    HIPCHK(c, hipMalloc((void**)&c->plant.hist_x, (size_t)steps * c->B * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->plant.hist_u, (size_t)steps * c->B * ILQR_NU * sizeof(double)));
+    c->hist_cap = steps;
+  }
+  return ILQR_OK;
+}
+int ilqr_hip_plant_get_history(ilqr_hip_ctx* c, double* x, double* u, int* steps_recorded) {
+  if (!c || !steps_recorded) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const long cap = c->hist_cap, rec = c->hist_n < cap ? c->hist_n : cap;
+  *steps_recorded = (int)rec;
+  // oldest row first.  A ring that has not wrapped is one contiguous run; one that has is two: rows [first, cap) then [0, first)
+  const long first = c->hist_n > cap ? c->hist_n % cap : 0;
+  const long head = rec - first;      // rows of the first run
+  const size_t rx = (size_t)c->B * ILQR_NX, ru = (size_t)c->B * ILQR_NU;
+  if (x && head > 0) HIPCHK(c, hipMemcpy(x, c->plant.hist_x + first * rx, head * rx * sizeof(double), hipMemcpyDeviceToHost));
+  if (x && first > 0) HIPCHK(c, hipMemcpy(x + head * rx, c->plant.hist_x, first * rx * sizeof(double), hipMemcpyDeviceToHost));
+  if (u && head > 0) HIPCHK(c, hipMemcpy(u, c->plant.hist_u + first * ru, head * ru * sizeof(double), hipMemcpyDeviceToHost));
+  if (u && first > 0) HIPCHK(c, hipMemcpy(u + head * ru, c->plant.hist_u, first * ru * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+#define PLANT_GETTER(name, ptr, count, type)                                                                    \
+  int name(ilqr_hip_ctx* c, type* out) {                                                                        \
+    if (!c || !out) return ILQR_ERR_ARG;                                                                        \
+    if (!c->plant_set) return ILQR_ERR_STATE;                                                                   \
+    enter(c);                                                                                                   \
+    HIPCHK(c, hipStreamSynchronize(c->stream));                                                                 \
+    HIPCHK(c, hipMemcpy(out, c->plant.ptr, (size_t)(count) * sizeof(type), hipMemcpyDeviceToHost));             \
+    return ILQR_OK;                                                                                             \
+  }
+PLANT_GETTER(ilqr_hip_plant_get_state, x, (size_t)c->B * ILQR_NX, double)
+PLANT_GETTER(ilqr_hip_plant_get_control, u, (size_t)c->B * ILQR_NU, double)
+PLANT_GETTER(ilqr_hip_plant_get_stance, stance, (size_t)c->B * 2, int)
+PLANT_GETTER(ilqr_hip_plant_get_alive, alive, c->B, int)
+int ilqr_hip_plant_state_device(ilqr_hip_ctx* c, const double** x_device) {
+  if (!c || !x_device) return ILQR_ERR_ARG;
+  *x_device = c->plant.x;
   return ILQR_OK;
 }
 int ilqr_hip_get_iterations_enqueued(const ilqr_hip_ctx* c) { return c ? c->iterations_enqueued : -1; }

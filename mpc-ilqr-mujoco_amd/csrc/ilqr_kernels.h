@@ -144,6 +144,22 @@ void launch_step_s(int count, const double* x, const double* u, const h1::DynPar
 void launch_stance_geom_s(const DevState& S, int mode, const int* list, const int* count, int* out, hipStream_t st);
 void launch_last_step_s(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
 void launch_linearize_fd_s(const DevState& S, const h1::ProblemDev& P, int mode, double eps, hipStream_t st);
+// plant_kernels.hip: the closed-loop plant resident in the handle (include/ilqr_hip.h ilqr_hip_plant_*); all device pointers
+struct PlantDev {
+  double* x;        // [B][51] plant state
+  double* u;        // [B][19] control applied in the last substep of the last advance (zero for a rollout that is not alive)
+  double* dv;       // [B][25] pending velocity kick
+  int* stance;      // [B][2]  stance flags of the last substep
+  int* alive;       // [B]     0 once a rollout's state was or became non-finite
+  double* hist_x;   // [rows][B][51] history ring (null: none): the state each advance started from, behind its kick
+  double* hist_u;   // [rows][B][19]                            and the control it wrote to u
+};
+// one MPC interval of the plant under the policy of the last solve (first knot of S.xbar / S.ubar / S.K): `substeps` steps of dyn.h (the
+// caller passes the plant's parameters, h = dt / substeps); sched / sched_stride: row 0 of each set is the stance of this interval, geom:
+// from the feet instead; kick != 0: apply Pl.dv first; hist_row >= 0: fill that row of the ring
+void launch_plant_advance(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, long hist_row,
+                          hipStream_t st);
+int plant_kernels_set_attr();
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();
 void launch_backward_wave(const DevState& S, int mode, hipStream_t st, double fold_h, const int* list, const int* count);

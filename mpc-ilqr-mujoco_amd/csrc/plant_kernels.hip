@@ -1,0 +1,218 @@
+// The closed-loop plant kept on the device (include/ilqr_hip.h "device-resident plant"): ONE fused kernel per MPC step that does what the
+// reference's runSimulation does between two calls of MPC::stepOnce (main/humanoid_mpc.cpp:122-190) with the policy the handle has just solved:
+//   k_plant_advance  pending velocity kick -> u = ubar_0 + K_0 (x - xbar_0) (src/ilqr/mpc.cpp:97-101; a non-finite u becomes zero,
+//                    main:162-165) -> `substeps` plant steps of h = dt / substeps (main:128,168-170) -> x, u, stance, alive (main:134-137)
+//                    and the history ring
+// Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
+// A translation unit of its own: no kernel of the solve shares a compilation with it.
+#include <hip/hip_runtime.h>
+
+#include "h1_cost_dev.h"
+#define ABA_FENCE          // as dyn_split_kernels.hip: the step is compiled under the same switches there and here
+#include "h1_aba_split.h"
+#include "h1_foot_contact_dev.h"
+#include "ilqr_kernels.h"
+
+using namespace h1;
+
+namespace ilqr {
+
+#include "dyn_step_shared.h"
+
+// LDS of a workgroup, in doubles: the dynamics scratch of the step (LDS_SLOTS x 64, at the base: the non-inlined steps address it there),
+// then per rollout of the wave the state x (51), xbar_0 (51), ubar_0 (19), the control u (19) and -- feedback mode 1 -- K_0 (19 x 51).
+// RPW rollouts per wave: 32 (a lane pair each, as k_last_step_s) while K_0 is read once, from memory; 4 in feedback mode 1, where the
+// wave's K_0 stay in LDS across the substeps (4 x 7.6 KB; 32 of them are 248 KB and fit nowhere on the chip).
+#define PLANT_NX H1_NX
+#define PLANT_NU H1_NU
+template <int FB> struct PlantLayout {
+  static constexpr int RPW = FB ? 4 : 32;
+  static constexpr int XS = h1s::LDS_SLOTS * 64, XB = XS + RPW * PLANT_NX, UB = XB + RPW * PLANT_NX, US = UB + RPW * PLANT_NU, KS = US + RPW * PLANT_NU;
+  static constexpr int DOUBLES = KS + (FB ? RPW * PLANT_NU * PLANT_NX : 0);
+};
+
+DEVFN bool finite_half(const h1s::HalfX& h) {
+  bool f = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) f = f && isfinite(h.p[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) f = f && isfinite(h.quat[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) f = f && isfinite(h.vb[k]);
+  f = f && isfinite(h.q.th11) && isfinite(h.q.qd11);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) f = f && isfinite(h.q.thL[k]) && isfinite(h.q.qdL[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) f = f && isfinite(h.q.thA[k]) && isfinite(h.q.qdA[k]);
+  return f;
+}
+DEVFN bool finite_half_u(const h1s::HalfU& u) {
+  bool f = isfinite(u.u11);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) f = f && isfinite(u.uL[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) f = f && isfinite(u.uA[k]);
+  return f;
+}
+// this lane's hinges of a control vector (the torso's by the even lane)
+DEVFN void store_half_u(bool side, const h1s::HalfU& u, double* o) {
+  if (!side) o[10] = u.u11;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) o[h1s::jleg(side, k)] = u.uL[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[h1s::jarm(side, k)] = u.uA[k];
+}
+// qvel += dv (dv in the order of qvel: linear (world), angular (body), the 19 hinge rates)
+DEVFN void kick_half(bool side, h1s::HalfX& h, const double* dv) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) h.vb[k] += dv[k];
+  h.q.qd11 += dv[6 + 10];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) h.q.qdL[k] += dv[6 + h1s::jleg(side, k)];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h.q.qdA[k] += dv[6 + h1s::jarm(side, k)];
+}
+// LDS operations of a wave execute in order and the workgroup is one wave: only the compiler has to be kept from moving them
+DEVFN void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// u = ubar_0 + K_0 (x - xbar_0) for the wave's rollouts, x / xbar_0 / ubar_0 in LDS -> u in LDS.  The arithmetic of k_compute_control
+// (ilqr_kernels.hip): one accumulator per row, started at ubar_0, the 51 terms in index order.  The 64 lanes deal the RPW x 19 rows out;
+// nothing of the dynamics is live here (the state sits in LDS), so the step's register budget is its own.
+template <int FB>
+DEVFN void control_law(const DevState& S, double* lds, int b0) {
+  typedef PlantLayout<FB> Lay;
+  constexpr int n = PLANT_NX, m = PLANT_NU;
+  for (int it = threadIdx.x; it < Lay::RPW * m; it += 64) {
+    const int r = it / m, row = it - r * m;
+    const int b = b0 + r < S.B ? b0 + r : S.B - 1;
+    const double* Kr = FB ? lds + Lay::KS + (r * m + row) * n : S.K + ((size_t)b * S.N * m + row) * n;
+    const double* x = lds + Lay::XS + r * n;
+    const double* xb = lds + Lay::XB + r * n;
+    double s = lds[Lay::UB + r * m + row];
+    for (int j = 0; j < n; ++j) s += Kr[j] * (x[j] - xb[j]);
+    lds[Lay::US + r * m + row] = s;
+  }
+}
+
+// KIND: the CONTACT value of step_any (step_kind(dyn)); FB: feedback mode -- 0 the reference's loop, u held over the MPC interval; 1 the
+// control law re-evaluated on (xbar_0, ubar_0, K_0) before every substep.  dyn: the PLANT's parameters (h = dt / substeps).
+// sched / sched_stride: the contact schedule (row 0 of each set is the stance of this MPC step); geom: stance from the feet instead.
+// kick: a velocity kick Pl.dv is pending; hist_row >= 0: row of the history ring to fill.
+template <int KIND, int FB>
+__global__ void __launch_bounds__(64) k_plant_advance(DevState S, PlantDev Pl, DynParams dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, long hist_row) {
+  extern __shared__ double lds[];
+  typedef PlantLayout<FB> Lay;
+  constexpr int n = PLANT_NX, m = PLANT_NU, RPW = Lay::RPW;
+  const int tid = threadIdx.x;
+  const int pr = tid >> 1;
+  const bool side = (tid & 1) != 0;
+  const int b0 = blockIdx.x * RPW;
+  const bool owner = pr < RPW && b0 + pr < S.B;      // (lane pairs stay together: every flag below is the same on both lanes of a pair)
+  const int b = owner ? b0 + pr : S.B - 1;
+  const int N = S.N;
+  // ---- first knot of the policy -> LDS, consecutive lanes on consecutive doubles
+  for (int r = 0; r < RPW; ++r) {
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;
+    const double* xb = S.xbar + (size_t)br * (N + 1) * n;
+    const double* ub = S.ubar + (size_t)br * N * m;
+    if (tid < n) lds[Lay::XB + r * n + tid] = xb[tid];
+    if (tid < m) lds[Lay::UB + r * m + tid] = ub[tid];
+    if constexpr (FB != 0) {
+      const double* K0 = S.K + (size_t)br * N * m * n;
+      for (int e = tid; e < m * n; e += 64) lds[Lay::KS + r * m * n + e] = K0[e];
+    }
+  }
+  // ---- plant state, kick, the guards of main:134-137
+  h1s::HalfX h; h1s::load_half(side, Pl.x + (size_t)b * n, h);
+  const bool was_alive = owner && Pl.alive[b] != 0;
+  if (owner && hist_row >= 0 && !was_alive) h1s::store_half(side, h, Pl.hist_x + ((size_t)hist_row * S.B + b) * n);      // (a frozen rollout logs the state it stopped in)
+  if (kick && was_alive) kick_half(side, h, Pl.dv + (size_t)b * H1_NV);
+  bool fin = finite_half(h);
+  fin = h1s::xch_flag(fin) && fin;
+  bool run = was_alive && fin;
+  if (owner && hist_row >= 0 && was_alive) h1s::store_half(side, h, Pl.hist_x + ((size_t)hist_row * S.B + b) * n);       // x the control law sees (after the kick)
+  if (pr < RPW) h1s::store_half(side, h, lds + Lay::XS + pr * n);
+  int st[2] = {1, 1};
+  if (owner) { st[0] = sched[b * sched_stride]; st[1] = sched[b * sched_stride + 1]; }
+  h1s::HalfU u;
+  for (int k = 0; k < substeps; ++k) {
+    // The one piece that is not plain C++: an EMPTY asm statement (no instruction) that makes the lane index opaque per substep, as in
+    // k_rollout_s.  Without it the per-lane body constants `side ? right : left` are hoisted out of the substep loop and spilled: the free
+    // plant's frame grows from 228 to 728 B (120 -> 191 spilled registers), the joint-limit plant's from 1208 to 1720 B (158 -> 225).
+    int lane = tid; asm volatile("" : "+v"(lane));
+    const bool side_t = (lane & 1) != 0;
+    const int prt = lane >> 1;
+    if (FB != 0 || k == 0) {
+      wave_lds_fence();
+      control_law<FB>(S, lds, b0);
+      wave_lds_fence();
+    }
+    const int pc = prt < RPW ? prt : 0;
+    load_half_u(side_t, lds + Lay::US + pc * m, u);
+    bool ufin = finite_half_u(u);
+    ufin = h1s::xch_flag(ufin) && ufin;
+    if (!ufin) { u.u11 = 0.0; for (int q = 0; q < 5; ++q) u.uL[q] = 0.0; for (int q = 0; q < 4; ++q) u.uA[q] = 0.0; }      // main:162-165
+    wave_lds_fence();      // (the odd lane reads the shared coordinates its partner stored at the end of the previous substep)
+    if (run) {
+      const h1s::LaneLds L{lds, 64, lane};
+      h1s::load_half(side_t, lds + Lay::XS + prt * n, h);
+      if constexpr (KIND >= 1 && KIND <= 4) {
+        if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary, on the same state with the same machine code)
+      }
+      step_any<KIND>(side_t, h, u, dyn, st, L, geom);
+      wave_lds_fence();      // (the step's LDS scratch and the state rows are different words; the fence orders the row against the next control law)
+      h1s::store_half(side_t, h, lds + Lay::XS + prt * n);
+    }
+  }
+  // ---- write-back: a rollout whose state is or became non-finite keeps its state and stance, reports zero control and is never advanced again
+  fin = finite_half(h);
+  fin = h1s::xch_flag(fin) && fin;
+  run = run && fin;
+  if (!owner) return;
+  if (!run) { u.u11 = 0.0; for (int q = 0; q < 5; ++q) u.uL[q] = 0.0; for (int q = 0; q < 4; ++q) u.uA[q] = 0.0; }
+  store_half_u(side, u, Pl.u + (size_t)b * m);
+  if (hist_row >= 0) store_half_u(side, u, Pl.hist_u + ((size_t)hist_row * S.B + b) * m);
+  if (run) {
+    h1s::store_half(side, h, Pl.x + (size_t)b * n);
+    if (!side) { Pl.stance[2 * (size_t)b] = st[0]; Pl.stance[2 * (size_t)b + 1] = st[1]; }
+  }
+  if (!side) Pl.alive[b] = run ? 1 : 0;
+}
+
+template <int KIND, int FB> static int plant_attr() {
+  return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
+}
+int plant_kernels_set_attr() {
+  int rc = 0;
+  rc |= plant_attr<0, 0>(); rc |= plant_attr<1, 0>(); rc |= plant_attr<2, 0>(); rc |= plant_attr<3, 0>(); rc |= plant_attr<4, 0>(); rc |= plant_attr<5, 0>();
+  rc |= plant_attr<0, 1>(); rc |= plant_attr<1, 1>(); rc |= plant_attr<2, 1>(); rc |= plant_attr<3, 1>(); rc |= plant_attr<4, 1>(); rc |= plant_attr<5, 1>();
+  return rc;
+}
+template <int KIND, int FB>
+static void plant_launch(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, long hist_row, hipStream_t st) {
+  typedef PlantLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_advance<KIND, FB>), grid, dim3(64), Lay::DOUBLES * sizeof(double), st, S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row);
+}
+template <int FB>
+static void plant_launch_kind(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, long hist_row, hipStream_t st) {
+  switch (step_kind(dyn)) {
+    case 5: plant_launch<5, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
+    case 4: plant_launch<4, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
+    case 3: plant_launch<3, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
+    case 2: plant_launch<2, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
+    case 1: plant_launch<1, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
+    default: plant_launch<0, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+  }
+}
+void launch_plant_advance(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, long hist_row,
+                          hipStream_t st) {
+  if (feedback_mode) plant_launch_kind<1>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+  else plant_launch_kind<0>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+}
+
+}  // namespace ilqr

@@ -16,6 +16,15 @@ Mirrors (host side; the solve itself is the HIP library):
       MPC_iLQR_solve, MPC_computeControl (host clock, as the reference measures them) and, with `profile_stages=True`, the
       iLQR_* keys from the device events of the solve; `profiling_table()` formats them as `printProfilingResults` does.
 One log set per logged rollout (`log_rollouts`), the reference being single-trajectory.
+
+`MPCRunner(..., resident=True)` keeps the plant in the solver handle (include/ilqr_hip.h "device-resident plant"): after the cold start
+of the first step every step is  set_problem -> initialize_warm_from_plant -> solve(None) -> plant_advance,  with no upload of x, no
+download of u or x_next and no synchronisation but the solve's own.  `substeps` plant steps of dt / substeps per MPC step
+(physics_steps_per_mpc, main/humanoid_mpc.cpp:128,168-170) and `feedback_mode` 1 (u = ubar0 + K0 (x - xbar0) re-evaluated before every
+substep) exist on that path only.  States and controls come back from the history ring in one download when the run ends, and the CSV
+logs are written then, in the same formats (a logged run also fetches the first knot of the solution once per step: q_optimal.csv /
+u_optimal.csv hold it).  `run(..., kicks={step: dv})` adds dv [B,25] to the plant's qvel in that step, between the solve and the control
+law: the solver meets the push one step later, as a controller meets a push that arrives between measurement and actuation.
 """
 import os
 import time
@@ -58,9 +67,13 @@ class MPCLogs:
 class MPCRunner:
     """Batched closed loop: `solver` = BatchedILQR, `refs` = ReferenceData, `base_problem` = weights etc. (scenario.make_problem)."""
 
-    def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule"):
+    def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
+                 resident=False, substeps=1, feedback_mode=0):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
+        if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
+            raise ValueError("substeps / feedback_mode need the device-resident plant (resident=True)")
+        self.resident, self.substeps, self.feedback_mode = bool(resident), int(substeps), int(feedback_mode)
         self.s, self.refs, self.base = solver, refs, base_problem
         # "geometry": the plant finds its contacts from the foot hulls (BatchedILQR.step_geometry, the solver's contact mode), as mj_step
         # does in the reference's plant (robot_utils.cpp:106-117); "schedule": the stance flags of the current schedule row
@@ -88,7 +101,14 @@ class MPCRunner:
                 lines.append("%-20s%8d%12.2f%12.2f%12.2f%12.2f" % (key, len(t), sum(t), sum(t) / len(t), min(t), max(t)))
         return "\n".join(lines)
 
-    def step_once(self, x_measured, u_init=None):
+    def _add_stage_ms(self):
+        ms, _ = self.s.stage_ms()
+        for key, val in (("iLQR_forwardRollout", ms["iLQR_computeCost+forwardRollout"]), ("iLQR_linearization", ms["iLQR_linearization"]),
+                         ("iLQR_costQuadratics", ms["iLQR_costQuadratics"]), ("iLQR_backwardPass", ms["iLQR_backwardPass"] + ms["iLQR_backwardPass_retry"]),
+                         ("iLQR_lineSearch", ms["iLQR_lineSearch"] + ms["iLQR_lineSearch_retry"])):
+            self.prof.setdefault(key, []).append(float(val))
+
+    def step_once(self, x_measured, u_init=None, kick=None):
         t0 = time.perf_counter()
         prob = self.refs.problem_at(self.t_idx, self.s.N, self.base, follow_schedule=self.follow_schedule)   # extractReferenceWindow
         self.s.set_problem(prob)
@@ -102,11 +122,10 @@ class MPCRunner:
         self.last_cost = self.s.solve(x_measured)
         t3 = time.perf_counter(); self._add("MPC_iLQR_solve", t2, t3)
         if self.profile_stages:
-            ms, _ = self.s.stage_ms()
-            for key, val in (("iLQR_forwardRollout", ms["iLQR_computeCost+forwardRollout"]), ("iLQR_linearization", ms["iLQR_linearization"]),
-                             ("iLQR_costQuadratics", ms["iLQR_costQuadratics"]), ("iLQR_backwardPass", ms["iLQR_backwardPass"] + ms["iLQR_backwardPass_retry"]),
-                             ("iLQR_lineSearch", ms["iLQR_lineSearch"] + ms["iLQR_lineSearch_retry"])):
-                self.prof.setdefault(key, []).append(float(val))
+            self._add_stage_ms()
+        if kick is not None:                                  # a push between measurement and actuation (see run)
+            x_measured = np.array(x_measured, dtype=np.float64); x_measured[:, NQ:] += kick
+        self.last_x_applied = x_measured
         u = self.s.compute_control(x_measured)                # mpc.cpp:97-101
         t4 = time.perf_counter(); self._add("MPC_computeControl", t3, t4)
         self.has_prev = True
@@ -119,12 +138,20 @@ class MPCRunner:
         self._add("MPC_stepOnce", t0, time.perf_counter())
         return u
 
-    def run(self, x0, steps, u_init=None):
-        """`steps` closed-loop steps from x0 [B,51]; returns the visited states [steps+1,B,51] and controls [steps,B,19]."""
+    def run(self, x0, steps, u_init=None, kicks=None):
+        """`steps` closed-loop steps from x0 [B,51]; returns the visited states [steps+1,B,51] and controls [steps,B,19].
+        kicks: {step index: dv [B,25]} velocity kicks; the state recorded for such a step is the kicked one (what the control law saw)."""
+        kicks = {} if kicks is None else {int(k): np.asarray(v, dtype=np.float64) for k, v in kicks.items()}
+        if self.resident:
+            return self._run_resident(np.array(x0, dtype=np.float64), steps, u_init, kicks)
         x = np.array(x0, dtype=np.float64)
         xs, us = [x.copy()], []
-        for _ in range(steps):
-            u = self.step_once(x, u_init)
+        for k in range(steps):
+            if k in kicks:
+                u = self.step_once(x, u_init, kick=kicks[k])
+                x = self.last_x_applied; xs[-1] = x.copy()
+            else:
+                u = self.step_once(x, u_init)
             if self.plant_contacts == "geometry":
                 x, st = self.s.step_geometry(x, u)
                 self.plant_stance.append(st)
@@ -135,6 +162,51 @@ class MPCRunner:
                 x = self.s.step(x, u)
             xs.append(x.copy()); us.append(u.copy())
         return np.array(xs), np.array(us)
+
+    def _run_resident(self, x0, steps, u_init, kicks):
+        """The same loop with the plant in the handle: nothing of the state crosses the host between the cold start and the end of the run.
+        One difference from the host path besides the crossings: with a per-rollout contact schedule (`follow_schedule` windows stacked per
+        rollout) the resident plant steps every rollout with row 0 of ITS OWN set, as ilqr_hip_plant_configure documents; the host path
+        steps the whole batch with row 0 of set 0 (`last_stance0`).  With a shared schedule, which `problem_at` produces, the two agree."""
+        s = self.s
+        s.plant_configure(self.substeps, self.feedback_mode, self.plant_contacts)
+        s.plant_set_history(steps)
+        s.plant_reset(x0)                                    # the only upload of a state (besides the cold start's x0)
+        rows = []                                            # per step: (cost, ms, x_ref0, u_ref0, x_opt0, u_opt0)
+        for k in range(steps):
+            t0 = time.perf_counter()
+            prob = self.refs.problem_at(self.t_idx, s.N, self.base, follow_schedule=self.follow_schedule)
+            s.set_problem(prob)
+            t1 = time.perf_counter(); self._add("MPC_extractReference", t0, t1)
+            self.last_stance0 = prob["stance"][0, 0]
+            if self.has_prev:
+                s.initialize_warm_from_plant()               # ilqr.cpp:68-80, x0 from the plant on the device
+                t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
+                self.last_cost = s.solve(None)
+            else:                                            # the gravity-compensation guess is computed on the host from x0
+                s.initialize(x0, u_init)
+                t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
+                self.last_cost = s.solve(x0)
+            t3 = time.perf_counter(); self._add("MPC_iLQR_solve", t2, t3)
+            if self.profile_stages:
+                self._add_stage_ms()
+            if k in kicks:
+                s.plant_kick(kicks[k])
+            s.plant_advance()                                # mpc.cpp:97-101 + main:162-170, enqueued behind the solve
+            t4 = time.perf_counter(); self._add("MPC_plantAdvance", t3, t4)
+            self.has_prev = True
+            self.t_idx += 1
+            if self.logs:
+                xb, ub = s.xbar(), s.ubar()
+                rows.append((self.last_cost.copy(), 1e3 * (time.perf_counter() - t0), prob["x_ref"][0, 0].copy(), prob["u_ref"][0, 0].copy(), xb[:, 0].copy(), ub[:, 0].copy()))
+            self._add("MPC_stepOnce", t0, time.perf_counter())
+        hx, hu = s.plant_history()                           # ONE download for the whole run
+        xs = np.concatenate([hx, s.plant_state()[None]], axis=0)
+        t_first = self.t_idx - steps
+        for k, (cost, ms, xr0, ur0, xo0, uo0) in enumerate(rows):
+            for b, lg in self.logs.items():
+                lg.log(t_first + k + 1, cost[b], ms, hx[k, b], hu[k, b], xr0, ur0, xo0[b], uo0[b])
+        return xs, hu
 
     def close(self):
         for lg in self.logs.values():

@@ -38,6 +38,9 @@ EXPORTS = [
     "ilqr_hip_payload_width", "ilqr_hip_comm_available", "ilqr_hip_comm_get_unique_id", "ilqr_hip_comm_init", "ilqr_hip_comm_destroy", "ilqr_hip_comm_world", "ilqr_hip_comm_rank",
     "ilqr_hip_gather_first_knot",
     "ilqr_hip_reference_kinematics", "ilqr_hip_reference_com_velocity", "ilqr_hip_foot_clearance", "ilqr_hip_gravity_compensation", "ilqr_hip_stream",
+    "ilqr_hip_plant_reset", "ilqr_hip_plant_configure", "ilqr_hip_plant_kick", "ilqr_hip_plant_advance", "ilqr_hip_initialize_warm_from_plant",
+    "ilqr_hip_plant_set_history", "ilqr_hip_plant_get_history", "ilqr_hip_plant_get_state", "ilqr_hip_plant_get_control", "ilqr_hip_plant_get_stance",
+    "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
 ]
 
 
@@ -400,6 +403,68 @@ class BatchedILQR:
         """Restoring stiffness of the joint-limit rows (include/ilqr_hip.h): qacc_i = -v_i / h - k r_i on a constrained hinge; 0 = the pure stop,
         1 / (2 h)^2 = MuJoCo's default solref time constant."""
         self._chk(self.L.ilqr_hip_set_joint_limit_stiffness(self.h, C.c_double(float(k))))
+
+    # ---- device-resident plant (include/ilqr_hip.h "device-resident plant"): the closed loop without a host round trip per MPC step
+    def plant_reset(self, x):
+        """Upload the plant state [B,51]: every rollout alive, no pending kick, history cursor at 0."""
+        x = _c64(x)
+        if x.shape != (self.B, NX):
+            raise ValueError("plant state must be [B, 51]")
+        self._chk(self.L.ilqr_hip_plant_reset(self.h, _p(x)))
+
+    def plant_configure(self, substeps=1, feedback_mode=0, contact_source="schedule"):
+        """`substeps` plant steps of dt / substeps per MPC step; feedback_mode 0 holds u over the interval (the reference's loop), 1 re-evaluates
+        u = ubar0 + K0 (x - xbar0) before every substep; contact_source "schedule" (row 0 of the current schedule) or "geometry" (foot hulls)."""
+        code = {"schedule": 0, "geometry": 1}.get(contact_source)
+        if code is None:
+            raise ValueError("contact_source must be 'schedule' or 'geometry'")
+        self._chk(self.L.ilqr_hip_plant_configure(self.h, int(substeps), int(feedback_mode), code))
+
+    def plant_kick(self, dv):
+        """Arm a one-shot velocity kick [B,25] (order of qvel) for the next advance."""
+        dv = _c64(dv)
+        if dv.shape != (self.B, NV):
+            raise ValueError("kick must be [B, 25]")
+        self._chk(self.L.ilqr_hip_plant_kick(self.h, _p(dv)))
+
+    def plant_advance(self):
+        """Enqueue one MPC interval of the plant under the policy of the last solve; does not synchronise."""
+        self._chk(self.L.ilqr_hip_plant_advance(self.h))
+
+    def initialize_warm_from_plant(self):
+        """initialize_warm_resident with x0 taken from the plant state on the device; does not synchronise."""
+        self._chk(self.L.ilqr_hip_initialize_warm_from_plant(self.h))
+
+    def plant_set_history(self, steps):
+        """Allocate (steps > 0) or free (0) the history ring of the plant."""
+        self._chk(self.L.ilqr_hip_plant_set_history(self.h, int(steps)))
+        self._plant_hist_rows = int(steps)
+
+    def plant_history(self):
+        """(x [rows,B,51], u [rows,B,19]) of the recorded advances, oldest first: the state each advance started from and the control it applied."""
+        rows = getattr(self, "_plant_hist_rows", 0)
+        x, u = np.zeros((rows, self.B, NX)), np.zeros((rows, self.B, NU))
+        rec = C.c_int(0)
+        self._chk(self.L.ilqr_hip_plant_get_history(self.h, _p(x), _p(u), C.byref(rec)))
+        return x[:rec.value], u[:rec.value]
+
+    def plant_state(self):
+        return self._get("ilqr_hip_plant_get_state", (self.B, NX))
+
+    def plant_control(self):
+        return self._get("ilqr_hip_plant_get_control", (self.B, NU))
+
+    def plant_stance(self):
+        return self._get("ilqr_hip_plant_get_stance", (self.B, 2), np.int32)
+
+    def plant_alive(self):
+        return self._get("ilqr_hip_plant_get_alive", (self.B,), np.int32)
+
+    def plant_state_device(self):
+        """Device pointer of the plant state [B][51] (for kernels chained on `stream`)."""
+        p = C.c_void_p()
+        self._chk(self.L.ilqr_hip_plant_state_device(self.h, C.byref(p)))
+        return p.value
 
     def enable_profiling(self, on=True):
         self._chk(self.L.ilqr_hip_enable_profiling(self.h, int(bool(on))))
