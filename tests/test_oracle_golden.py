@@ -7,6 +7,7 @@ import pytest
 
 import oracle_lib as ol
 from conftest import load_package
+from cost_envelope_cases import golden_problem as _golden_problem, pen
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 sc = load_package().scenario
@@ -92,17 +93,6 @@ def test_state_conventions_against_reference_data_files():
         assert np.abs(r - qb / np.linalg.norm(qb)).max() < 1e-9
 
 
-def _golden_problem(c, **weights):
-    cfg = dict(sc.SHIPPED_CONFIG)
-    cfg.update(W_com_pos=0.0, W_com_vel=0.0, W_foot=0.0, W_foot_vel=0.0, W_upright=0.0, w_balance=0.0)
-    cfg.update(weights)
-    prob = sc.make_problem(ol.reference_kinematics, cfg=cfg)
-    # zero out tracking so only the task term remains
-    prob["Q"] = np.zeros(51); prob["Qf"] = np.zeros(51); prob["R"] = np.zeros(19)
-    prob["w_joint"] = 0.0; prob["w_ctrl"] = 0.0
-    return prob
-
-
 @pytest.mark.parametrize("mode", [0, 1])
 def test_cost_terms_vs_torch_autograd_golden(mode):
     c = np.load(os.path.join(G, "cost_golden.npz"))
@@ -163,10 +153,6 @@ def test_total_cost_and_reference_kinematics_vs_golden():
     Q, R, Qf = prob["Q"], prob["R"], prob["Qf"]
     wu, wb = prob["task_weights"][4], prob["task_weights"][5]
     jr, cr = c["jrange"], c["ctrlrange"]
-
-    def pen(val, rng_, w):
-        lo = rng_[:, 0] + 0.1 * (rng_[:, 1] - rng_[:, 0]); hi = rng_[:, 1] - 0.1 * (rng_[:, 1] - rng_[:, 0])
-        return w * (np.maximum(val - hi, 0) ** 2 + np.maximum(lo - val, 0) ** 2).sum()
 
     tot = 0.0
     for t in range(N + 1):
