@@ -105,6 +105,10 @@ int ilqr_hip_set_options(ilqr_hip_ctx* ctx, int jacobian_mode, double fd_eps, in
 int ilqr_hip_initialize(ilqr_hip_ctx* ctx, const double* x0, const double* u_init, const double* prev_xbar, const double* prev_ubar);
 /* warm start from the solver's own previous solution kept on the device (MPC::stepOnce, src/ilqr/mpc.cpp:58-60) */
 int ilqr_hip_initialize_warm_resident(ilqr_hip_ctx* ctx, const double* x0);
+/* The same after `shift` knots of the policy have been applied since the last solve (1 <= shift <= N - 1, else ILQR_ERR_ARG): see
+   ilqr_hip_initialize_warm_from_plant_shifted, whose x0 comes from the plant; this one uploads it and synchronises.  Generalises
+   ilqr.cpp:68-80 (the reference shifts by one knot, because it solves every step). */
+int ilqr_hip_initialize_warm_resident_shifted(ilqr_hip_ctx* ctx, const double* x0, int shift);
 /* device-resident variant of the cold start: x0_device[B][51], u_init_device[B][N][19] are HIP device pointers */
 int ilqr_hip_initialize_device(ilqr_hip_ctx* ctx, const double* x0_device, const double* u_init_device);
 
@@ -166,6 +170,10 @@ int ilqr_hip_gather_first_knot(ilqr_hip_ctx* ctx, int root, int with_gains, doub
 
 /* MPC::stepOnce control law u = ubar[0] + K[0](x_meas - xbar[0]) -- src/ilqr/mpc.cpp:97-101 */
 int ilqr_hip_compute_control(ilqr_hip_ctx* ctx, const double* x_measured /*[B][51]*/, double* u_apply /*[B][19]*/);
+/* The law of src/ilqr/mpc.cpp:97-101 on knot `knot` (0 .. N - 1, else ILQR_ERR_ARG) of the policy: u = ubar_knot + K_knot (x - xbar_knot),
+   for a caller that keeps the plant itself and solves every m-th interval (the reference solves every step and only ever uses knot 0).
+   knot = 0 equals ilqr_hip_compute_control bit for bit. */
+int ilqr_hip_compute_control_at(ilqr_hip_ctx* ctx, int knot, const double* x_measured /*[B][51]*/, double* u_apply /*[B][19]*/);
 
 /* ---- stage entry points (one reference function each; used by the parity tests and the bench breakdown) ---- */
 int ilqr_hip_set_trajectory(ilqr_hip_ctx* ctx, const double* xbar, const double* ubar);   /* overwrite nominal trajectory */
@@ -259,8 +267,9 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* ctx, int* stance);
    the handle has just solved -- the first knot (xbar_0, ubar_0, K_0) of "nominal trajectories + TV-LQR gains" (include/ilqr/ilqr.hpp:10-16).
    The plant is the model's dynamics (contact mode, friction, joint-limit rows, gravity of the handle) at the step dt / substeps.  Per MPC
    step:  set references / schedule -> ilqr_hip_initialize_warm_from_plant -> ilqr_hip_solve(ctx, NULL, cost) -> ilqr_hip_plant_advance;
-   the solve's own synchronisation is the only one.  Not provided: external wrenches, a contact model other than the solver's, solving
-   every m-th plant step only. */
+   the solve's own synchronisation is the only one.  Solving every m-th interval only: ilqr_hip_initialize_warm_from_plant_shifted(ctx, m)
+   -> ilqr_hip_solve -> ilqr_hip_plant_follow(ctx, 0, m), see there.  Not provided: external wrenches, a contact model other than the
+   solver's. */
 /* Upload the plant state x[B][51] (robot.getState's counterpart in reverse: RobotUtils::setState).  Every rollout becomes alive, a pending
    kick is dropped, the history cursor returns to 0.  Synchronises the handle's stream. */
 int ilqr_hip_plant_reset(ilqr_hip_ctx* ctx, const double* x /*[B][51]*/);
@@ -289,6 +298,23 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* ctx);
    ilqr.cpp:68-80): same kernels, same result bit for bit, nothing uploaded and NO synchronisation.  ILQR_ERR_STATE before a first
    initialize or before ilqr_hip_plant_reset. */
 int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* ctx);
+/* `count` consecutive MPC intervals of the plant in ONE kernel, under the knots first_knot .. first_knot + count - 1 of the policy of the
+   last solve: interval j applies u = ubar_k + K_k (x - xbar_k), k = first_knot + j -- the law of src/ilqr/mpc.cpp:97-101 and the loop body
+   of main/humanoid_mpc.cpp:162-170 with the knot index in the place of 0 -- and stands on row k of the contact schedule (or on the foot
+   hulls).  The reference itself solves before every interval and never reads more than knot 0 of its gains; this is the deployment in
+   which a solve takes longer than the control period.  Everything else is ilqr_hip_plant_advance, `count` times: a pending kick lands
+   before the first interval only, every interval fills one row of the history ring (the ring may wrap inside the call), a rollout whose
+   state is or becomes non-finite in interval j is frozen there exactly as separate advances would freeze it (its later rows log the frozen
+   state and zero control), and x, u, stance, alive are written back once, at the end.  (0, 1) is ilqr_hip_plant_advance.  ENQUEUES only.
+   ILQR_ERR_ARG unless first_knot >= 0, count >= 1, first_knot + count <= N; ILQR_ERR_STATE / ILQR_ERR_UNSUPPORTED as the advance. */
+int ilqr_hip_plant_follow(ilqr_hip_ctx* ctx, int first_knot, int count);
+/* ilqr_hip_initialize_warm_from_plant after `shift` followed intervals, 1 <= shift <= N - 1 (else ILQR_ERR_ARG): the shift of
+   ilqr.cpp:68-80 by `shift` knots instead of one -- xbar_0 = the plant state, xbar_t = previous xbar_{t + shift} for 1 <= t <= N - shift,
+   ubar_t = previous ubar_{min(t + shift, N - 1)} -- and ONE kernel that re-rolls xbar_{t + 1} = f(xbar_t, ubar_t), t = N - shift .. N - 1,
+   under row t of the schedule now set (the reference re-rolls its one last knot, ilqr.cpp:72-80, and solves every step).  shift = 1 gives
+   the result of ilqr_hip_initialize_warm_from_plant bit for bit.  On a handle of the test library whose environment selects the scalar
+   dynamics the tail still runs on the default family's step, as the plant does.  ENQUEUES only; ILQR_ERR_STATE as the one-knot call. */
+int ilqr_hip_initialize_warm_from_plant_shifted(ilqr_hip_ctx* ctx, int shift);
 /* History ring of `steps` rows (0: free it): every advance appends the state it started from (behind its kick -- the x the control law
    saw) and the control it reported; the oldest row is overwritten once the ring is full.  Resets the cursor; synchronises. */
 int ilqr_hip_plant_set_history(ilqr_hip_ctx* ctx, int steps);

@@ -156,6 +156,11 @@ class iLQR {
   void plantKick(const Vec& dv /*[batch][25]*/) { if (dv.size() != (size_t)B_ * ILQR_NV) throw std::runtime_error("dv must hold batch * 25 doubles"); chk(ilqr_hip_plant_kick(ctx_, dv.data())); }
   void plantAdvance() { chk(ilqr_hip_plant_advance(ctx_)); }                                                           // main:162-170; enqueues only
   void initializeWarmFromPlant() { chk(ilqr_hip_initialize_warm_from_plant(ctx_)); }                                   // mpc.cpp:58-60; enqueues only
+  // solving every m-th interval only: initializeWarmFromPlantShifted(m) -> ilqr_hip_solve(handle(), nullptr, cost) -> plantFollow(0, m)
+  void plantFollow(int first_knot, int count) { chk(ilqr_hip_plant_follow(ctx_, first_knot, count)); }                  // main:162-170 over `count` knots of the policy; enqueues only
+  void initializeWarmFromPlantShifted(int shift) { chk(ilqr_hip_initialize_warm_from_plant_shifted(ctx_, shift)); }    // ilqr.cpp:68-80 by `shift` knots; enqueues only
+  void initializeWarmResidentShifted(const Vec& x0 /*[batch][51]*/, int shift) { checkState(x0); chk(ilqr_hip_initialize_warm_resident_shifted(ctx_, x0.data(), shift)); }
+  Vec computeControlAt(int knot, const Vec& x /*[batch][51]*/) { checkState(x); Vec u((size_t)B_ * ILQR_NU); chk(ilqr_hip_compute_control_at(ctx_, knot, x.data(), u.data())); return u; }   // mpc.cpp:97-101 on knot `knot`
   void plantSetHistory(int steps) { chk(ilqr_hip_plant_set_history(ctx_, steps)); hist_rows_ = steps; }
   // rows recorded; x[rows][batch][51], u[rows][batch][19], oldest first
   int plantHistory(Vec& x, Vec& u) {

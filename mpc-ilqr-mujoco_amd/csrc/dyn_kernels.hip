@@ -94,6 +94,28 @@ __global__ void __launch_bounds__(64) k_last_step_r(DevState S, ProblemDev P) {
   for (int i = 0; i < H1_NX; ++i) S.xbar[((size_t)b * (N + 1) + N) * H1_NX + i] = xn[i];
 }
 
+// tail of the warm start shifted by sh knots (k_warm_shift_m): xbar[t + 1] = f(xbar[t], ubar[t]) for t = N - sh .. N - 1, the state in
+// registers over the sh steps; sh = 1 is k_last_step_r
+__global__ void __launch_bounds__(64) k_warm_tail_r(DevState S, ProblemDev P, int sh) {
+  extern __shared__ double lds[];
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S.B) return;
+  const h1r::LaneLds L{lds, 64, (int)threadIdx.x};
+  const int N = S.N;
+  double* xb = S.xbar + (size_t)b * (N + 1) * H1_NX;
+  const double* ub = S.ubar + (size_t)b * N * H1_NU;
+  double x[H1_NX], u[H1_NU];
+#pragma unroll
+  for (int i = 0; i < H1_NX; ++i) x[i] = xb[(N - sh) * H1_NX + i];
+  for (int t = N - sh; t < N; ++t) {
+#pragma unroll
+    for (int i = 0; i < H1_NU; ++i) u[i] = ub[t * H1_NU + i];
+    h1r::step(x, u, P.dyn.h, P.dyn.g, L, x);
+#pragma unroll
+    for (int i = 0; i < H1_NX; ++i) xb[(t + 1) * H1_NX + i] = x[i];
+  }
+}
+
 // thread per (rollout, alpha), the 8 alphas of a rollout in 8 adjacent lanes; candidates kept in HBM, k_control
 // copies the accepted one.  The feedback K (x - xbar) is evaluated cooperatively by the 8 lanes of a rollout:
 // lane a owns the columns j = a, a+8, ... of K_t (one fully used 64-byte line per row and load instruction, every
@@ -328,6 +350,7 @@ int dyn_kernels_set_attr() {
   int rc = 0;
   rc |= hipFuncSetAttribute((const void*)k_step_r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_last_step_r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES) != hipSuccess;
 #ifdef ILQR_LEGACY_KERNELS
   rc |= hipFuncSetAttribute((const void*)k_rollout_r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_line_search_r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_BYTES) != hipSuccess;
@@ -337,6 +360,9 @@ int dyn_kernels_set_attr() {
 }
 void launch_step_r(int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st) {
   hipLaunchKernelGGL(k_step_r, dim3(cdiv2(count, 64)), dim3(64), DYN_LDS_BYTES, st, count, x, u, dyn, xn);
+}
+void launch_warm_tail_r(const DevState& S, const ProblemDev& P, int shift, hipStream_t st) {
+  hipLaunchKernelGGL(k_warm_tail_r, dim3(cdiv2(S.B, 64)), dim3(64), DYN_LDS_BYTES, st, S, P, shift);
 }
 void launch_last_step_r(const DevState& S, const ProblemDev& P, hipStream_t st) {
   hipLaunchKernelGGL(k_last_step_r, dim3(cdiv2(S.B, 64)), dim3(64), DYN_LDS_BYTES, st, S, P);

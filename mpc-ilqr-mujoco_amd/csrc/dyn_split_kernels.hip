@@ -466,6 +466,28 @@ __global__ void __launch_bounds__(64) k_last_step_s(DevState S, ProblemDev P) {
   step_any<CK>(side, h, uu, P.dyn, P.stance + b * P.stance_stride + 2 * (N - 1), L, P.stance_geom);
   h1s::store_half(side, h, S.xbar + ((size_t)b * (N + 1) + N) * H1_NX);
 }
+// tail of the warm start shifted by sh knots (k_warm_shift_m): xbar[t + 1] = f(xbar[t], ubar[t]) for t = N - sh .. N - 1 under row t of the
+// schedule (or the feet of xbar[t]: stance source GEOMETRY, as k_last_step_s), the state in registers over the sh steps; sh = 1 is k_last_step_s
+template <int CK>
+__global__ void __launch_bounds__(64) k_warm_tail_s(DevState S, ProblemDev P, int sh) {
+  extern __shared__ double lds[];
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = gid >> 1;
+  const bool side = (gid & 1) != 0;
+  if (b >= S.B) return;
+  const h1s::LaneLds L{lds, 64, (int)threadIdx.x};
+  const int N = S.N;
+  double* xb = S.xbar + (size_t)b * (N + 1) * H1_NX;
+  const double* ub = S.ubar + (size_t)b * N * H1_NU;
+  h1s::HalfX h; h1s::load_half(side, xb + (size_t)(N - sh) * H1_NX, h);
+  for (int t = N - sh; t < N; ++t) {
+    int sd = side; asm volatile("" : "+v"(sd));      // (opaque per step, as in k_rollout_s: the per-lane body constants stay out of the loop's invariants)
+    const bool side_t = sd != 0;
+    h1s::HalfU uu; load_half_u(side_t, ub + t * H1_NU, uu);
+    step_any<CK>(side_t, h, uu, P.dyn, P.stance + b * P.stance_stride + 2 * t, L, P.stance_geom);
+    h1s::store_half(side_t, h, xb + (size_t)(t + 1) * H1_NX);
+  }
+}
 // Reference-style forward differences (RobotUtils::linearizeDynamicsFD, robot_utils.cpp:120-160) on the two-lane step:
 // a lane pair per (knot, column); columns 0..50 perturb x, 51..69 perturb u, column 70 is the unperturbed step (evaluated
 // once per knot, as the reference does).  The stepped states land in A / B / the knot's lin_dump record; k_fd_finish turns
@@ -573,6 +595,12 @@ int dyn_split_kernels_set_attr() {
   rc |= hipFuncSetAttribute((const void*)k_last_step_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_last_step_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_last_step_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
+  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
   rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
@@ -640,6 +668,17 @@ void launch_last_step_s(const DevState& S, const ProblemDev& P, hipStream_t st) 
     case 2: hipLaunchKernelGGL(k_last_step_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
     case 1: hipLaunchKernelGGL(k_last_step_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
     default: hipLaunchKernelGGL(k_last_step_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P);
+  }
+}
+void launch_warm_tail_s(const DevState& S, const ProblemDev& P, int shift, hipStream_t st) {
+  const dim3 grid(cdiv_s((long)S.B * 2, 64));
+  switch (step_kind(P.dyn)) {
+    case 5: hipLaunchKernelGGL(k_warm_tail_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
+    case 4: hipLaunchKernelGGL(k_warm_tail_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
+    case 3: hipLaunchKernelGGL(k_warm_tail_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
+    case 2: hipLaunchKernelGGL(k_warm_tail_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
+    case 1: hipLaunchKernelGGL(k_warm_tail_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
+    default: hipLaunchKernelGGL(k_warm_tail_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift);
   }
 }
 void launch_linearize_fd_s(const DevState& S, const ProblemDev& P, int mode, double eps, hipStream_t st) {

@@ -459,6 +459,26 @@ int ilqr_hip_initialize_warm_resident(ilqr_hip_ctx* c, const double* x0) {
   c->xbar_rolled = false;
   return ILQR_OK;
 }
+// the warm start shifted by `shift` knots on the resident solution (S.x0 already holds x0): copies, shift, tail re-roll -- enqueued
+static int warm_shifted(ilqr_hip_ctx* c, int shift) {
+  const size_t B = c->B, N = c->N;
+  HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  ilqr::launch_warm_shift_m(c->S, c->d_prevx, c->d_prevu, shift, c->stream);
+  ilqr::launch_warm_tail(c->S, c->P, shift, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->xbar_rolled = false;
+  return ILQR_OK;
+}
+int ilqr_hip_initialize_warm_resident_shifted(ilqr_hip_ctx* c, const double* x0, int shift) {
+  if (!c || !x0 || shift < 1 || shift > c->N - 1) return ILQR_ERR_ARG;
+  if (!c->initialized) return ILQR_ERR_STATE;
+  TRY(enter_launching(c));
+  HIPCHK(c, hipMemcpyAsync(c->S.x0, x0, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  TRY(warm_shifted(c, shift));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
 
 // ---------------------------------------------------------------- solve
 static void collect_profile(ilqr_hip_ctx* c) {
@@ -910,6 +930,16 @@ int ilqr_hip_compute_control(ilqr_hip_ctx* c, const double* x_measured, double* 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
+int ilqr_hip_compute_control_at(ilqr_hip_ctx* c, int knot, const double* x_measured, double* u_apply) {
+  if (!c || !x_measured || !u_apply || knot < 0 || knot >= c->N) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipMemcpyAsync(c->d_tmpx, x_measured, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  ilqr::launch_compute_control_at(c->S, knot, c->d_tmpx, c->d_u0, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(u_apply, c->d_u0, (size_t)c->B * ILQR_NU * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
 
 // ---------------------------------------------------------------- stage entry points
 int ilqr_hip_set_trajectory(ilqr_hip_ctx* c, const double* xbar, const double* ubar) {
@@ -1193,6 +1223,31 @@ int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* c) {
   HIPCHK(c, hipGetLastError());
   c->xbar_rolled = false;
   return ILQR_OK;      // asynchronous on the handle's stream
+}
+int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
+  if (!c || first_knot < 0 || count < 1 || count > c->N - first_knot) return ILQR_ERR_ARG;
+  if (!c->solved || !c->plant_set) { c->err = "plant_follow before a solve / before ilqr_hip_plant_reset"; return ILQR_ERR_STATE; }
+  TRY(enter_launching(c));
+  const bool geom = c->plant_source == ILQR_STANCE_GEOMETRY;
+  if (geom) {      // (as ilqr_hip_plant_advance)
+    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  }
+  h1::DynParams dyn = c->P.dyn;
+  dyn.h = c->P.dyn.h / c->plant_substeps;
+  const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
+  ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, (geom && dyn.contact != 0) ? 1 : 0, c->plant_substeps, c->plant_feedback, c->plant_kick ? 1 : 0, first_knot, count,
+                            row0, c->hist_cap, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->plant_kick = false;
+  if (c->hist_cap > 0) c->hist_n += count;
+  return ILQR_OK;      // asynchronous on the handle's stream
+}
+int ilqr_hip_initialize_warm_from_plant_shifted(ilqr_hip_ctx* c, int shift) {
+  if (!c || shift < 1 || shift > c->N - 1) return ILQR_ERR_ARG;
+  if (!c->initialized || !c->plant_set) return ILQR_ERR_STATE;
+  TRY(enter_launching(c));
+  HIPCHK(c, hipMemcpyAsync(c->S.x0, c->plant.x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  return warm_shifted(c, shift);      // asynchronous on the handle's stream
 }
 int ilqr_hip_plant_set_history(ilqr_hip_ctx* c, int steps) {
   if (!c || steps < 0) return ILQR_ERR_ARG;

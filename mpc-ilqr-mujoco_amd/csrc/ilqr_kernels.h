@@ -119,6 +119,13 @@ void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, uns
 void launch_warm_shift(const DevState& S, const double* prev_x, const double* prev_u, hipStream_t st);
 void launch_last_step(const Variants& V, const DevState& S, const h1::ProblemDev& P, hipStream_t st);
 void launch_compute_control(const DevState& S, const double* x_meas, double* u_out, hipStream_t st);
+// the warm start shifted by `shift` knots (1 <= shift <= N - 1): the copies, then ONE kernel that re-rolls xbar[N - shift + 1 .. N] with
+// the state in registers, in the family launch_last_step picks for the default kernels (unconstrained: _r; constrained: _s<KIND>)
+void launch_warm_shift_m(const DevState& S, const double* prev_x, const double* prev_u, int shift, hipStream_t st);
+void launch_warm_tail(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
+void launch_warm_tail_r(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
+void launch_warm_tail_s(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
+void launch_compute_control_at(const DevState& S, int knot, const double* x_meas, double* u_out, hipStream_t st);
 void launch_pack_first_knot(const DevState& S, double* u0, double* K0, hipStream_t st);
 void launch_pack_payload(const DevState& S, int with_gains, double* out, hipStream_t st);
 void launch_mirror_lxx(const DevState& S, hipStream_t st);   // fill the strictly upper tiles of lxx_t, t < N, from the lower ones
@@ -159,6 +166,10 @@ struct PlantDev {
 // from the feet instead; kick != 0: apply Pl.dv first; hist_row >= 0: fill that row of the ring
 void launch_plant_advance(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, long hist_row,
                           hipStream_t st);
+// `count` consecutive intervals in one launch under the policy knots first_knot .. first_knot + count - 1 (schedule rows likewise); the
+// kick before the first interval only; ring rows (hist_row0 + j) % hist_cap, hist_cap = 0: no ring
+void launch_plant_follow(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
+                         long hist_row0, long hist_cap, hipStream_t st);
 int plant_kernels_set_attr();
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

@@ -981,6 +981,21 @@ __global__ void k_warm_shift(DevState S, const double* prev_x, const double* pre
   for (int e = lane; e < (N - 1) * m; e += blockDim.x) ub[e] = pu[m + e];
   for (int e = lane; e < m; e += blockDim.x) ub[(N - 1) * m + e] = pu[(N - 1) * m + e];
 }
+// the same shift by `sh` knots, 1 <= sh <= N - 1 (a caller that follows the policy over sh intervals between two solves): xbar_0 = x0,
+// xbar_t = prev_xbar_{t + sh} for 1 <= t <= N - sh, ubar_t = prev_ubar_{min(t + sh, N - 1)}; the states xbar_{N - sh + 1 .. N} are
+// re-rolled by the caller (launch_warm_tail).  sh = 1 copies what k_warm_shift copies.
+__global__ void k_warm_shift_m(DevState S, const double* prev_x, const double* prev_u, int sh) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int N = S.N, n = H1_NX, m = H1_NU;
+  double* xb = S.xbar + (size_t)b * (N + 1) * n;
+  double* ub = S.ubar + (size_t)b * N * m;
+  const double* px = prev_x + (size_t)b * (N + 1) * n;
+  const double* pu = prev_u + (size_t)b * N * m;
+  for (int e = lane; e < n; e += blockDim.x) xb[e] = S.x0[(size_t)b * n + e];
+  for (int e = lane; e < (N - sh) * n; e += blockDim.x) xb[n + e] = px[(1 + sh) * n + e];
+  for (int e = lane; e < (N - sh) * m; e += blockDim.x) ub[e] = pu[sh * m + e];
+  for (int e = lane; e < sh * m; e += blockDim.x) ub[(N - sh) * m + e] = pu[(N - 1) * m + e % m];
+}
 // the nominal re-rollout of iterations >= 1 runs beside the linearisation into a shadow buffer (ilqr_capi.hip): adopt it
 __global__ void k_adopt_rollout(DevState S, const double* shadow, int mode, unsigned long long* mismatches) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -1026,6 +1041,17 @@ __global__ void k_compute_control(DevState S, const double* x_meas, double* u_ou
   const double* Kr = S.K + ((size_t)b * N * m + lane) * n;
   const double* xb = S.xbar + (size_t)b * (N + 1) * n;
   double s = S.ubar[(size_t)b * N * m + lane];
+  for (int j = 0; j < n; ++j) s += Kr[j] * (x_meas[(size_t)b * n + j] - xb[j]);
+  u_out[(size_t)b * m + lane] = s;
+}
+// the same law on knot `knot` of the policy: u = ubar[knot] + K[knot] (x_meas - xbar[knot]), the arithmetic of k_compute_control
+__global__ void k_compute_control_at(DevState S, int knot, const double* x_meas, double* u_out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int N = S.N, n = H1_NX, m = H1_NU;
+  if (lane >= m) return;
+  const double* Kr = S.K + (((size_t)b * N + knot) * m + lane) * n;
+  const double* xb = S.xbar + ((size_t)b * (N + 1) + knot) * n;
+  double s = S.ubar[((size_t)b * N + knot) * m + lane];
   for (int j = 0; j < n; ++j) s += Kr[j] * (x_meas[(size_t)b * n + j] - xb[j]);
   u_out[(size_t)b * m + lane] = s;
 }
@@ -1229,6 +1255,10 @@ void launch_solve_begin(const DevState& S, hipStream_t st) { hipLaunchKernelGGL(
 void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, unsigned long long* mismatches, hipStream_t st) { hipLaunchKernelGGL(k_adopt_rollout, dim3(S.B), dim3(64), 0, st, S, shadow, mode, mismatches); }
 void launch_warm_shift(const DevState& S, const double* px, const double* pu, hipStream_t st) { hipLaunchKernelGGL(k_warm_shift, dim3(S.B), dim3(64), 0, st, S, px, pu); }
 void launch_last_step(const Variants& V, const DevState& S, const ProblemDev& P, hipStream_t st) { if (!V.scalar_dyn) { if (constrained(P.dyn)) launch_last_step_s(S, P, st); else launch_last_step_r(S, P, st); return; } LEGACY_LAUNCH(hipLaunchKernelGGL(k_last_step, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S, P)); }
+void launch_warm_shift_m(const DevState& S, const double* px, const double* pu, int shift, hipStream_t st) { hipLaunchKernelGGL(k_warm_shift_m, dim3(S.B), dim3(64), 0, st, S, px, pu, shift); }
+// (the scalar cross-check family of the test library has no tail kernel: it re-rolls by the default family's, as the plant does)
+void launch_warm_tail(const DevState& S, const ProblemDev& P, int shift, hipStream_t st) { if (constrained(P.dyn)) launch_warm_tail_s(S, P, shift, st); else launch_warm_tail_r(S, P, shift, st); }
+void launch_compute_control_at(const DevState& S, int knot, const double* x_meas, double* u_out, hipStream_t st) { hipLaunchKernelGGL(k_compute_control_at, dim3(S.B), dim3(64), 0, st, S, knot, x_meas, u_out); }
 void launch_compute_control(const DevState& S, const double* x_meas, double* u_out, hipStream_t st) { hipLaunchKernelGGL(k_compute_control, dim3(S.B), dim3(64), 0, st, S, x_meas, u_out); }
 void launch_pack_first_knot(const DevState& S, double* u0, double* K0, hipStream_t st) { hipLaunchKernelGGL(k_pack_first_knot, dim3(S.B), dim3(64), 0, st, S, u0, K0); }
 void launch_pack_payload(const DevState& S, int with_gains, double* out, hipStream_t st) { hipLaunchKernelGGL(k_pack_payload, dim3(S.B), dim3(64), 0, st, S, with_gains, out); }

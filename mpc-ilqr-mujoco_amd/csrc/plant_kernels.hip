@@ -3,6 +3,9 @@
 //   k_plant_advance  pending velocity kick -> u = ubar_0 + K_0 (x - xbar_0) (src/ilqr/mpc.cpp:97-101; a non-finite u becomes zero,
 //                    main:162-165) -> `substeps` plant steps of h = dt / substeps (main:128,168-170) -> x, u, stance, alive (main:134-137)
 //                    and the history ring
+//   k_plant_follow   the same over `count` consecutive intervals under the policy knots k0 .. k0 + count - 1 of ONE solve (the caller
+//                    solves every count-th interval only; the reference itself solves every step): the state stays in LDS / registers
+//                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
 // A translation unit of its own: no kernel of the solve shares a compilation with it.
 #include <hip/hip_runtime.h>
@@ -79,17 +82,17 @@ DEVFN void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// u = ubar_0 + K_0 (x - xbar_0) for the wave's rollouts, x / xbar_0 / ubar_0 in LDS -> u in LDS.  The arithmetic of k_compute_control
+// u = ubar_k + K_k (x - xbar_k) for the wave's rollouts (k = knot; 0 in k_plant_advance), x / xbar_k / ubar_k in LDS -> u in LDS.  The arithmetic of k_compute_control
 // (ilqr_kernels.hip): one accumulator per row, started at ubar_0, the 51 terms in index order.  The 64 lanes deal the RPW x 19 rows out;
 // nothing of the dynamics is live here (the state sits in LDS), so the step's register budget is its own.
 template <int FB>
-DEVFN void control_law(const DevState& S, double* lds, int b0) {
+DEVFN void control_law(const DevState& S, double* lds, int b0, int knot = 0) {
   typedef PlantLayout<FB> Lay;
   constexpr int n = PLANT_NX, m = PLANT_NU;
   for (int it = threadIdx.x; it < Lay::RPW * m; it += 64) {
     const int r = it / m, row = it - r * m;
     const int b = b0 + r < S.B ? b0 + r : S.B - 1;
-    const double* Kr = FB ? lds + Lay::KS + (r * m + row) * n : S.K + ((size_t)b * S.N * m + row) * n;
+    const double* Kr = FB ? lds + Lay::KS + (r * m + row) * n : S.K + ((size_t)b * S.N * m + (size_t)knot * m + row) * n;
     const double* x = lds + Lay::XS + r * n;
     const double* xb = lds + Lay::XB + r * n;
     double s = lds[Lay::UB + r * m + row];
@@ -183,8 +186,121 @@ __global__ void __launch_bounds__(64) k_plant_advance(DevState S, PlantDev Pl, D
   if (!side) Pl.alive[b] = run ? 1 : 0;
 }
 
+// ---- k_plant_follow: `count` intervals in one launch.  Per interval j exactly what k_plant_advance does with knot k0 + j in the place of
+// knot 0, row k0 + j of the schedule and row (hist_row0 + j) % hist_cap of the ring; the kick before interval 0 only.  What an advance
+// leaves in memory for the next one stays on the chip: the state in the rollout's LDS row (the next interval loads it from there as an
+// advance loads Pl.x: the even lane's shared coordinates), alive in `run`, and -- for the one case in which an advance does NOT write its
+// state back, a rollout that is or becomes non-finite -- the state its interval started from in a keep row XK, from which the rollout is
+// restored and then frozen (interval 0: from Pl.x, which holds the state in front of the kick and is not written before the end).
+// FB = 0: xbar_k is dead once the interval's one control law has run, the keep row takes its place; FB = 1: a row of its own (4 x 408 B).
+template <int FB> struct FollowLayout : PlantLayout<FB> {
+  typedef PlantLayout<FB> Base;
+  static constexpr int XK = FB ? Base::DOUBLES : Base::XB;
+  static constexpr int DOUBLES = Base::DOUBLES + (FB ? Base::RPW * PLANT_NX : 0);
+};
+DEVFN void zero_half_u(h1s::HalfU& u) {
+  u.u11 = 0.0;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) u.uL[q] = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) u.uA[q] = 0.0;
+}
+template <int KIND, int FB>
+__global__ void __launch_bounds__(64) k_plant_follow(DevState S, PlantDev Pl, DynParams dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, int k0, int count,
+                                                     long hist_row0, long hist_cap) {
+  extern __shared__ double lds[];
+  typedef FollowLayout<FB> Lay;
+  constexpr int n = PLANT_NX, m = PLANT_NU, RPW = Lay::RPW;
+  const int tid = threadIdx.x;
+  const int pr = tid >> 1;
+  const bool side = (tid & 1) != 0;
+  const int b0 = blockIdx.x * RPW;
+  const bool owner = pr < RPW && b0 + pr < S.B;      // (lane pairs stay together: every flag below is the same on both lanes of a pair)
+  const int b = owner ? b0 + pr : S.B - 1;
+  const int N = S.N;
+  h1s::HalfX h; h1s::load_half(side, Pl.x + (size_t)b * n, h);
+  bool run = owner && Pl.alive[b] != 0;      // alive, as the advances would hand it from one to the next
+  bool moved = false;                        // an interval of this launch ran to its end: state and stance are written back
+  int st[2] = {1, 1}, st_done[2] = {1, 1};
+  h1s::HalfU u;
+  for (int j = 0; j < count; ++j) {
+    const int kt = k0 + j;
+    const long hist_row = hist_cap > 0 ? (hist_row0 + j) % hist_cap : -1L;
+    wave_lds_fence();      // (the previous interval is done with its policy rows and has stored its last state)
+    // ---- knot kt of the policy -> LDS, consecutive lanes on consecutive doubles
+    for (int r = 0; r < RPW; ++r) {
+      const int br = b0 + r < S.B ? b0 + r : S.B - 1;
+      const double* xb = S.xbar + ((size_t)br * (N + 1) + kt) * n;
+      const double* ub = S.ubar + ((size_t)br * N + kt) * m;
+      if (tid < n) lds[Lay::Base::XB + r * n + tid] = xb[tid];
+      if (tid < m) lds[Lay::UB + r * m + tid] = ub[tid];
+      if constexpr (FB != 0) {
+        const double* Kt = S.K + ((size_t)br * N + kt) * m * n;
+        for (int e = tid; e < m * n; e += 64) lds[Lay::KS + r * m * n + e] = Kt[e];
+      }
+    }
+    // ---- the state this interval starts from, kick, the guards of main:134-137
+    const bool was_alive = run;
+    if (j > 0 && was_alive) h1s::load_half(side, lds + Lay::XS + pr * n, h);
+    if (j == 0 && kick && was_alive) kick_half(side, h, Pl.dv + (size_t)b * H1_NV);
+    bool fin = finite_half(h);
+    fin = h1s::xch_flag(fin) && fin;
+    run = was_alive && fin;
+    if (owner && hist_row >= 0) h1s::store_half(side, h, Pl.hist_x + ((size_t)hist_row * S.B + b) * n);      // x the control law sees (after the kick); a frozen rollout logs the state it stopped in
+    if (pr < RPW) h1s::store_half(side, h, lds + Lay::XS + pr * n);
+    if (owner) { st[0] = sched[b * sched_stride + 2 * kt]; st[1] = sched[b * sched_stride + 2 * kt + 1]; }
+    for (int k = 0; k < substeps; ++k) {
+      // the lane index is opaque per substep, as in k_plant_advance (see there what it costs to lose it)
+      int lane = tid; asm volatile("" : "+v"(lane));
+      const bool side_t = (lane & 1) != 0;
+      const int prt = lane >> 1;
+      if (FB != 0 || k == 0) {
+        wave_lds_fence();
+        control_law<FB>(S, lds, b0, kt);
+        wave_lds_fence();
+      }
+      if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
+      const int pc = prt < RPW ? prt : 0;
+      load_half_u(side_t, lds + Lay::US + pc * m, u);
+      bool ufin = finite_half_u(u);
+      ufin = h1s::xch_flag(ufin) && ufin;
+      if (!ufin) zero_half_u(u);      // main:162-165
+      wave_lds_fence();      // (the odd lane reads the shared coordinates its partner stored at the end of the previous substep)
+      if (run) {
+        const h1s::LaneLds L{lds, 64, lane};
+        h1s::load_half(side_t, lds + Lay::XS + prt * n, h);
+        if constexpr (KIND >= 1 && KIND <= 4) {
+          if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
+        }
+        step_any<KIND>(side_t, h, u, dyn, st, L, geom);
+        wave_lds_fence();
+        h1s::store_half(side_t, h, lds + Lay::XS + prt * n);
+      }
+    }
+    // ---- end of the interval: a rollout whose state is or became non-finite keeps the state it had, reports zero control and never runs again
+    fin = finite_half(h);
+    fin = h1s::xch_flag(fin) && fin;
+    run = run && fin;
+    if (!run) zero_half_u(u);
+    if (owner && hist_row >= 0) store_half_u(side, u, Pl.hist_u + ((size_t)hist_row * S.B + b) * m);
+    if (run) { moved = true; st_done[0] = st[0]; st_done[1] = st[1]; }
+    else if (was_alive) {      // frozen in this interval: back to what the advance would have left in Pl.x
+      if (j == 0) h1s::load_half(side, Pl.x + (size_t)b * n, h);
+      else h1s::load_half(side, lds + Lay::XK + pr * n, h);
+    }
+  }
+  if (!owner) return;
+  store_half_u(side, u, Pl.u + (size_t)b * m);
+  if (moved) {
+    h1s::store_half(side, h, Pl.x + (size_t)b * n);
+    if (!side) { Pl.stance[2 * (size_t)b] = st_done[0]; Pl.stance[2 * (size_t)b + 1] = st_done[1]; }
+  }
+  if (!side) Pl.alive[b] = run ? 1 : 0;
+}
+
 template <int KIND, int FB> static int plant_attr() {
-  return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
+  return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess ||
+         hipFuncSetAttribute((const void*)k_plant_follow<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FollowLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
 }
 int plant_kernels_set_attr() {
   int rc = 0;
@@ -213,6 +329,31 @@ void launch_plant_advance(const DevState& S, const PlantDev& Pl, const DynParams
                           hipStream_t st) {
   if (feedback_mode) plant_launch_kind<1>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
   else plant_launch_kind<0>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+}
+
+struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
+template <int KIND, int FB>
+static void follow_launch(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow<KIND, FB>), grid, dim3(64), Lay::DOUBLES * sizeof(double), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap);
+}
+template <int FB>
+static void follow_launch_kind(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const FollowArgs& a, hipStream_t st) {
+  switch (step_kind(dyn)) {
+    case 5: follow_launch<5, FB>(S, Pl, dyn, a, st); break;
+    case 4: follow_launch<4, FB>(S, Pl, dyn, a, st); break;
+    case 3: follow_launch<3, FB>(S, Pl, dyn, a, st); break;
+    case 2: follow_launch<2, FB>(S, Pl, dyn, a, st); break;
+    case 1: follow_launch<1, FB>(S, Pl, dyn, a, st); break;
+    default: follow_launch<0, FB>(S, Pl, dyn, a, st);
+  }
+}
+void launch_plant_follow(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
+                         long hist_row0, long hist_cap, hipStream_t st) {
+  const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
+  if (feedback_mode) follow_launch_kind<1>(S, Pl, dyn, a, st);
+  else follow_launch_kind<0>(S, Pl, dyn, a, st);
 }
 
 }  // namespace ilqr

@@ -25,6 +25,13 @@ substep) exist on that path only.  States and controls come back from the histor
 logs are written then, in the same formats (a logged run also fetches the first knot of the solution once per step: q_optimal.csv /
 u_optimal.csv hold it).  `run(..., kicks={step: dv})` adds dv [B,25] to the plant's qvel in that step, between the solve and the control
 law: the solver meets the push one step later, as a controller meets a push that arrives between measurement and actuation.
+
+`MPCRunner(..., solve_every=m)`, m > 1, solves before every m-th plant interval only and follows the time-varying policy
+u = ubar_j + K_j (x - xbar_j), j = 0..m-1, in between (the reference solves every step and only ever uses knot 0).  Groups are counted from
+the start of each `run`; the warm start shifts by the number of intervals applied since the last solve.  Resident path, per group:
+set_problem -> initialize_warm_from_plant(shift=m) -> solve(None) -> plant_follow(0, m), t_idx += m; a kick is supported before the first
+interval of a group only.  Host path: compute_control(x, knot=j) and today's plant step per interval, the stance taken from row j of the
+group's window.  The logs keep one main row per plant interval, the solve cost and time repeated over the group.
 """
 import os
 import time
@@ -68,12 +75,15 @@ class MPCRunner:
     """Batched closed loop: `solver` = BatchedILQR, `refs` = ReferenceData, `base_problem` = weights etc. (scenario.make_problem)."""
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
-                 resident=False, substeps=1, feedback_mode=0):
+                 resident=False, substeps=1, feedback_mode=0, solve_every=1):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
             raise ValueError("substeps / feedback_mode need the device-resident plant (resident=True)")
+        if int(solve_every) < 1 or (int(solve_every) > 1 and int(solve_every) > solver.N - 1):
+            raise ValueError("solve_every must be in 1 .. N - 1")
         self.resident, self.substeps, self.feedback_mode = bool(resident), int(substeps), int(feedback_mode)
+        self.solve_every, self.since_solve = int(solve_every), 1      # since_solve: plant intervals applied since the last solve (the next warm start's shift)
         self.s, self.refs, self.base = solver, refs, base_problem
         # "geometry": the plant finds its contacts from the foot hulls (BatchedILQR.step_geometry, the solver's contact mode), as mj_step
         # does in the reference's plant (robot_utils.cpp:106-117); "schedule": the stance flags of the current schedule row
@@ -114,8 +124,10 @@ class MPCRunner:
         self.s.set_problem(prob)
         t1 = time.perf_counter(); self._add("MPC_extractReference", t0, t1)
         self.last_stance0 = prob["stance"][0, 0]
-        if self.has_prev:
+        if self.has_prev and self.since_solve == 1:
             self.s.initialize_warm_resident(x_measured)       # ilqr.cpp:68-80
+        elif self.has_prev:
+            self.s.initialize_warm_resident(x_measured, shift=self.since_solve)
         else:
             self.s.initialize(x_measured, u_init)            # cold start, ilqr.cpp:82-116
         t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
@@ -129,13 +141,34 @@ class MPCRunner:
         u = self.s.compute_control(x_measured)                # mpc.cpp:97-101
         t4 = time.perf_counter(); self._add("MPC_computeControl", t3, t4)
         self.has_prev = True
+        self.since_solve = 1
         self.t_idx += 1
         if self.logs:
             ms = 1e3 * (time.perf_counter() - t0)
             xb, ub = self.s.xbar(), self.s.ubar()
             for b, lg in self.logs.items():
                 lg.log(self.t_idx, self.last_cost[b], ms, x_measured[b], u[b], prob["x_ref"][0, 0], prob["u_ref"][0, 0], xb[b, 0], ub[b, 0])
+            self._group = (prob, ms, xb, ub)
+        elif self.solve_every > 1:
+            self._group = (prob, 0.0, None, None)
         self._add("MPC_stepOnce", t0, time.perf_counter())
+        return u
+
+    def follow_once(self, x_measured, kick=None):
+        """A plant interval WITHOUT a solve (solve_every > 1): the control of knot j = since_solve of the last solve's policy."""
+        t3 = time.perf_counter()
+        j = self.since_solve
+        prob, ms, xb, ub = self._group
+        self.last_stance0 = prob["stance"][0, j]
+        if kick is not None:
+            x_measured = np.array(x_measured, dtype=np.float64); x_measured[:, NQ:] += kick
+        self.last_x_applied = x_measured
+        u = self.s.compute_control(x_measured, knot=j)
+        self._add("MPC_computeControl", t3, time.perf_counter())
+        self.since_solve += 1
+        self.t_idx += 1
+        for b, lg in self.logs.items():
+            lg.log(self.t_idx, self.last_cost[b], ms, x_measured[b], u[b], prob["x_ref"][0, j], prob["u_ref"][0, j], xb[b, j], ub[b, j])
         return u
 
     def run(self, x0, steps, u_init=None, kicks=None):
@@ -147,11 +180,13 @@ class MPCRunner:
         x = np.array(x0, dtype=np.float64)
         xs, us = [x.copy()], []
         for k in range(steps):
-            if k in kicks:
-                u = self.step_once(x, u_init, kick=kicks[k])
-                x = self.last_x_applied; xs[-1] = x.copy()
+            kick = kicks.get(k)
+            if k % self.solve_every == 0:                # (groups count from the start of the run)
+                u = self.step_once(x, u_init, kick=kick)
             else:
-                u = self.step_once(x, u_init)
+                u = self.follow_once(x, kick=kick)
+            if kick is not None:
+                x = self.last_x_applied; xs[-1] = x.copy()
             if self.plant_contacts == "geometry":
                 x, st = self.s.step_geometry(x, u)
                 self.plant_stance.append(st)
@@ -168,19 +203,26 @@ class MPCRunner:
         One difference from the host path besides the crossings: with a per-rollout contact schedule (`follow_schedule` windows stacked per
         rollout) the resident plant steps every rollout with row 0 of ITS OWN set, as ilqr_hip_plant_configure documents; the host path
         steps the whole batch with row 0 of set 0 (`last_stance0`).  With a shared schedule, which `problem_at` produces, the two agree."""
-        s = self.s
+        s, m = self.s, self.solve_every
+        off = sorted(k for k in kicks if k % m != 0)
+        if off:
+            raise ValueError("resident plant: a kick is supported before the first interval of a group only (solve_every = %d, kicks at %s)" % (m, off))
         s.plant_configure(self.substeps, self.feedback_mode, self.plant_contacts)
         s.plant_set_history(steps)
         s.plant_reset(x0)                                    # the only upload of a state (besides the cold start's x0)
-        rows = []                                            # per step: (cost, ms, x_ref0, u_ref0, x_opt0, u_opt0)
-        for k in range(steps):
+        rows = []                                            # per plant interval: (cost, ms, x_ref_j, u_ref_j, x_opt_j, u_opt_j)
+        for k in range(0, steps, m):
+            cnt = min(m, steps - k)                          # plant intervals of this group
             t0 = time.perf_counter()
             prob = self.refs.problem_at(self.t_idx, s.N, self.base, follow_schedule=self.follow_schedule)
             s.set_problem(prob)
             t1 = time.perf_counter(); self._add("MPC_extractReference", t0, t1)
             self.last_stance0 = prob["stance"][0, 0]
             if self.has_prev:
-                s.initialize_warm_from_plant()               # ilqr.cpp:68-80, x0 from the plant on the device
+                if self.since_solve == 1:
+                    s.initialize_warm_from_plant()           # ilqr.cpp:68-80, x0 from the plant on the device
+                else:
+                    s.initialize_warm_from_plant(shift=self.since_solve)
                 t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
                 self.last_cost = s.solve(None)
             else:                                            # the gravity-compensation guess is computed on the host from x0
@@ -192,13 +234,19 @@ class MPCRunner:
                 self._add_stage_ms()
             if k in kicks:
                 s.plant_kick(kicks[k])
-            s.plant_advance()                                # mpc.cpp:97-101 + main:162-170, enqueued behind the solve
+            if m == 1:
+                s.plant_advance()                            # mpc.cpp:97-101 + main:162-170, enqueued behind the solve
+            else:
+                s.plant_follow(0, cnt)                       # the same over the knots 0 .. cnt - 1 of the policy, one kernel
             t4 = time.perf_counter(); self._add("MPC_plantAdvance", t3, t4)
             self.has_prev = True
-            self.t_idx += 1
+            self.since_solve = cnt
+            self.t_idx += cnt
             if self.logs:
                 xb, ub = s.xbar(), s.ubar()
-                rows.append((self.last_cost.copy(), 1e3 * (time.perf_counter() - t0), prob["x_ref"][0, 0].copy(), prob["u_ref"][0, 0].copy(), xb[:, 0].copy(), ub[:, 0].copy()))
+                ms = 1e3 * (time.perf_counter() - t0)
+                for j in range(cnt):
+                    rows.append((self.last_cost.copy(), ms, prob["x_ref"][0, j].copy(), prob["u_ref"][0, j].copy(), xb[:, j].copy(), ub[:, j].copy()))
             self._add("MPC_stepOnce", t0, time.perf_counter())
         hx, hu = s.plant_history()                           # ONE download for the whole run
         xs = np.concatenate([hx, s.plant_state()[None]], axis=0)

@@ -41,6 +41,7 @@ EXPORTS = [
     "ilqr_hip_plant_reset", "ilqr_hip_plant_configure", "ilqr_hip_plant_kick", "ilqr_hip_plant_advance", "ilqr_hip_initialize_warm_from_plant",
     "ilqr_hip_plant_set_history", "ilqr_hip_plant_get_history", "ilqr_hip_plant_get_state", "ilqr_hip_plant_get_control", "ilqr_hip_plant_get_stance",
     "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
+    "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
 ]
 
 
@@ -205,8 +206,21 @@ class BatchedILQR:
         ks = [_c64(x0), None if u_init is None else _c64(u_init), None if prev_xbar is None else _c64(prev_xbar), None if prev_ubar is None else _c64(prev_ubar)]
         self._chk(self.L.ilqr_hip_initialize(self.h, *[_p(k) for k in ks]))
 
-    def initialize_warm_resident(self, x0):
-        self._chk(self.L.ilqr_hip_initialize_warm_resident(self.h, _p(_c64(x0))))
+    def _check_shift(self, shift):
+        shift = int(shift)
+        if not 1 <= shift <= self.N - 1:
+            raise ValueError("shift must be in 1 .. N - 1")
+        return shift
+
+    def initialize_warm_resident(self, x0, shift=1):
+        """Warm start from the resident solution shifted by `shift` knots (the knots applied since the last solve; 1: the reference's)."""
+        shift, x0 = self._check_shift(shift), _c64(x0)
+        if x0.shape != (self.B, NX):
+            raise ValueError("x0 must be [B, 51]")
+        if shift == 1:
+            self._chk(self.L.ilqr_hip_initialize_warm_resident(self.h, _p(x0)))
+        else:
+            self._chk(self.L.ilqr_hip_initialize_warm_resident_shifted(self.h, _p(x0), shift))
 
     def initialize_device(self, x0_ptr, u_init_ptr):
         self._chk(self.L.ilqr_hip_initialize_device(self.h, C.c_void_p(x0_ptr), C.c_void_p(u_init_ptr)))
@@ -294,9 +308,18 @@ class BatchedILQR:
         """Enqueue the per-step gather of [u0 | cost | (K0)] rows to `root` (recv_ptr: device buffer there, None elsewhere)."""
         self._chk(self.L.ilqr_hip_gather_first_knot(self.h, int(root), int(bool(with_gains)), C.c_void_p(recv_ptr)))
 
-    def compute_control(self, x_measured):
+    def compute_control(self, x_measured, knot=0):
+        """u = ubar_knot + K_knot (x - xbar_knot) [B,19]; knot 0 is MPC::stepOnce's law, later knots serve a caller that solves every m-th interval."""
+        knot, x = int(knot), _c64(x_measured)
+        if not 0 <= knot < self.N:
+            raise ValueError("knot must be in 0 .. N - 1")
+        if x.shape != (self.B, NX):
+            raise ValueError("x_measured must be [B, 51]")
         u = np.zeros((self.B, NU))
-        self._chk(self.L.ilqr_hip_compute_control(self.h, _p(_c64(x_measured)), _p(u)))
+        if knot == 0:
+            self._chk(self.L.ilqr_hip_compute_control(self.h, _p(x), _p(u)))
+        else:
+            self._chk(self.L.ilqr_hip_compute_control_at(self.h, knot, _p(x), _p(u)))
         return u
 
     # ---- stage entry points
@@ -431,9 +454,21 @@ class BatchedILQR:
         """Enqueue one MPC interval of the plant under the policy of the last solve; does not synchronise."""
         self._chk(self.L.ilqr_hip_plant_advance(self.h))
 
-    def initialize_warm_from_plant(self):
-        """initialize_warm_resident with x0 taken from the plant state on the device; does not synchronise."""
-        self._chk(self.L.ilqr_hip_initialize_warm_from_plant(self.h))
+    def plant_follow(self, first_knot, count):
+        """Enqueue `count` MPC intervals of the plant in one kernel, under the knots first_knot .. first_knot + count - 1 of the policy of the
+        last solve (schedule rows likewise); plant_follow(0, 1) is plant_advance.  Does not synchronise."""
+        first_knot, count = int(first_knot), int(count)
+        if first_knot < 0 or count < 1 or first_knot + count > self.N:
+            raise ValueError("need first_knot >= 0, count >= 1, first_knot + count <= N")
+        self._chk(self.L.ilqr_hip_plant_follow(self.h, first_knot, count))
+
+    def initialize_warm_from_plant(self, shift=1):
+        """initialize_warm_resident(shift=shift) with x0 taken from the plant state on the device; does not synchronise."""
+        shift = self._check_shift(shift)
+        if shift == 1:
+            self._chk(self.L.ilqr_hip_initialize_warm_from_plant(self.h))
+        else:
+            self._chk(self.L.ilqr_hip_initialize_warm_from_plant_shifted(self.h, shift))
 
     def plant_set_history(self, steps):
         """Allocate (steps > 0) or free (0) the history ring of the plant."""
