@@ -78,6 +78,23 @@ int ilqr_hip_set_cost_weights(ilqr_hip_ctx* ctx, const double* Q_diag /*51*/, co
 int ilqr_hip_set_task_weights(ilqr_hip_ctx* ctx, double w_com, double w_com_vel, double w_ee_pos, double w_ee_vel, double w_upright, double w_balance);
 /* RobotUtils::setConstraintWeights -- src/common/robot_utils.cpp:674-680 */
 int ilqr_hip_set_constraint_weights(ilqr_hip_ctx* ctx, double w_joint_limits, double w_control_limits);
+/* Per-rollout weight sets (batched weight sweeps): one set of everything the three setters above carry -- Q, R, Qf, the six task weights in
+   the order of ilqr_hip_set_task_weights, and constraint = (w_joint_limits, w_control_limits) -- per rollout.  n_sets is 1 or the batch
+   (else ILQR_ERR_ARG), every pointer is required.  The sets go into a device table owned by the handle, one 144-double record (nine
+   128-byte lines) per set; while it is installed it takes precedence over the three shared setters, which keep storing their values and
+   launch nothing new, and the cost kernels run in their weight-set instantiations.  n_sets == 1 installs a one-record table that every
+   rollout reads.  Synchronises the handle's stream.  ILQR_ERR_UNSUPPORTED on a handle of the test library whose environment selects a
+   family that evaluates the cost inside its own rollout / line-search kernels (ILQR_DYN=s, ILQR_ROLLOUT=r, ILQR_LS=r); while a table is
+   installed and an ILQR_ENV_PER_CALL re-read selects such a family, the calls ilqr_hip_reload_environment lists as launching
+   family-dependent kernels return it too (ilqr_hip_stage_cost_quadratics is not one of them: its kernels are the same in every family,
+   and it keeps running under the table).  No reference counterpart:
+   RobotUtils::setCostWeights (robot_utils.cpp:253-279) holds one set. */
+int ilqr_hip_set_weight_sets(ilqr_hip_ctx* ctx, const double* Q /*[n_sets][51]*/, const double* R /*[n_sets][19]*/, const double* Qf /*[n_sets][51]*/,
+                             const double* task /*[n_sets][6]*/, const double* constraint /*[n_sets][2]*/, int n_sets);
+/* Back to the stored shared values (same kernels and kernel arguments as a handle that never had a table). */
+int ilqr_hip_clear_weight_sets(ilqr_hip_ctx* ctx);
+/* 0: no table installed (shared weights), else the n_sets of the installed table (1 or the batch); -1 for a null handle */
+int ilqr_hip_num_weight_sets(const ilqr_hip_ctx* ctx);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N

@@ -90,6 +90,13 @@ class iLQR {
   void setCostWeights(const Vec& Qdiag, const Vec& Rdiag, const Vec& Qfdiag) { chk(ilqr_hip_set_cost_weights(ctx_, Qdiag.data(), Rdiag.data(), Qfdiag.data())); }
   void setTaskWeights(double com, double com_vel, double ee_pos, double ee_vel, double upright, double balance) { chk(ilqr_hip_set_task_weights(ctx_, com, com_vel, ee_pos, ee_vel, upright, balance)); }
   void setConstraintWeights(double joint, double ctrl) { chk(ilqr_hip_set_constraint_weights(ctx_, joint, ctrl)); }
+  // per-rollout weight sets (ilqr_hip_set_weight_sets; no reference counterpart): row-major [n_sets][51 | 19 | 51 | 6 | 2], n_sets = 1 or the batch
+  void setWeightSets(const std::vector<double>& Q, const std::vector<double>& R, const std::vector<double>& Qf, const std::vector<double>& task, const std::vector<double>& constraint, int n_sets) {
+    if (n_sets <= 0 || Q.size() != (size_t)n_sets * ILQR_NX || R.size() != (size_t)n_sets * ILQR_NU || Qf.size() != (size_t)n_sets * ILQR_NX || task.size() != (size_t)n_sets * 6 || constraint.size() != (size_t)n_sets * 2)
+      chk(ILQR_ERR_ARG);
+    chk(ilqr_hip_set_weight_sets(ctx_, Q.data(), R.data(), Qf.data(), task.data(), constraint.data(), n_sets));
+  }
+  void clearWeightSets() { chk(ilqr_hip_clear_weight_sets(ctx_)); }
   void setGravity(double gx, double gy, double gz) { chk(ilqr_hip_set_gravity(ctx_, gx, gy, gz)); }
   void setContactSchedule(const std::vector<int>& stance /*[N+1][2]*/) { chk(ilqr_hip_set_contact_schedule(ctx_, stance.data(), 1)); }
   // contact row: ILQR_CONTACT_NONE (default) or ILQR_CONTACT_RIGID_STANCE on the scheduled feet

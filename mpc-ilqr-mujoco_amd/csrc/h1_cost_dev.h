@@ -38,28 +38,49 @@ struct ProblemDev {
   const int* stance;         long stance_stride;       // [(N+1)*2]
   const double* ee_ref;      long ee_ref_stride;       // [(N+1)*2*3]
   const double* com_vel_ref; long com_vel_ref_stride;  // [(N+1)*3]
+  // per-rollout weight sets (ilqr_hip_set_weight_sets): null = the shared Q ... w_ctrl above; else one WS_STRIDE record per set, stride 0
+  // when one set serves every rollout.  Appended: nothing above moves
+  const double* wsets;       long wsets_stride;
+};
+// Record of one weight set, in doubles: every weight the cost reads, padded to whole 128-byte lines (129 fields -> 9 lines)
+enum { WS_Q = 0, WS_QF = WS_Q + H1_NX, WS_R = WS_QF + H1_NX, WS_TASK = WS_R + H1_NU /* order of ilqr_hip_set_task_weights */, WS_W_JOINT = WS_TASK + 6, WS_W_CTRL = WS_W_JOINT + 1,
+       WS_FIELDS = WS_W_CTRL + 1, WS_STRIDE = (WS_FIELDS + 15) / 16 * 16 };
+// The one place a cost kernel takes a weight from: WS = false the shared values in the kernel argument, WS = true rollout b's record
+template <bool WS> struct CostWeights {
+  const double* w;           // rollout b's record (WS only); the shared values are read from the caller's own P
+  DEVFN CostWeights(const ProblemDev& P, int b) : w(WS ? P.wsets + (long)b * P.wsets_stride : nullptr) {}
+  DEVFN const double* Qd(const ProblemDev& P, bool term) const { if constexpr (WS) return w + (term ? WS_QF : WS_Q); else return term ? P.Qf : P.Q; }
+  DEVFN double R(const ProblemDev& P, int i) const { if constexpr (WS) return w[WS_R + i]; else return P.R[i]; }
+  DEVFN double w_com(const ProblemDev& P) const { if constexpr (WS) return w[WS_TASK + 0]; else return P.w_com; }
+  DEVFN double w_com_vel(const ProblemDev& P) const { if constexpr (WS) return w[WS_TASK + 1]; else return P.w_com_vel; }
+  DEVFN double w_ee_pos(const ProblemDev& P) const { if constexpr (WS) return w[WS_TASK + 2]; else return P.w_ee_pos; }
+  DEVFN double w_ee_vel(const ProblemDev& P) const { if constexpr (WS) return w[WS_TASK + 3]; else return P.w_ee_vel; }
+  DEVFN double w_upright(const ProblemDev& P) const { if constexpr (WS) return w[WS_TASK + 4]; else return P.w_upright; }
+  DEVFN double w_balance(const ProblemDev& P) const { if constexpr (WS) return w[WS_TASK + 5]; else return P.w_balance; }
+  DEVFN double w_joint(const ProblemDev& P) const { if constexpr (WS) return w[WS_W_JOINT]; else return P.w_joint; }
+  DEVFN double w_ctrl(const ProblemDev& P) const { if constexpr (WS) return w[WS_W_CTRL]; else return P.w_ctrl; }
 };
 
 DEVFN void limit_bounds(const double* range, double& lo, double& hi) {
   const double margin = 0.1 * (range[1] - range[0]);
   lo = range[0] + margin; hi = range[1] - margin;
 }
-DEVFN double joint_penalty(const ProblemDev& P, const double* x) {
+template <class W> DEVFN double joint_penalty(const ProblemDev& P, const W& Wt, const double* x) {
   double c = 0.0;
   for (int i = 0; i < H1_NJ; ++i) {
     double lo, hi; limit_bounds(H1_JRANGE[i], lo, hi);
     const double q = x[7 + i];
-    if (q > hi) { const double v = q - hi; c += P.w_joint * v * v; }
-    if (q < lo) { const double v = lo - q; c += P.w_joint * v * v; }
+    if (q > hi) { const double v = q - hi; c += Wt.w_joint(P) * v * v; }
+    if (q < lo) { const double v = lo - q; c += Wt.w_joint(P) * v * v; }
   }
   return c;
 }
-DEVFN double ctrl_penalty(const ProblemDev& P, const double* u) {
+template <class W> DEVFN double ctrl_penalty(const ProblemDev& P, const W& Wt, const double* u) {
   double c = 0.0;
   for (int i = 0; i < H1_NU; ++i) {
     double lo, hi; limit_bounds(H1_CTRLRANGE[i], lo, hi);
-    if (u[i] > hi) { const double v = u[i] - hi; c += P.w_ctrl * v * v; }
-    if (u[i] < lo) { const double v = lo - u[i]; c += P.w_ctrl * v * v; }
+    if (u[i] > hi) { const double v = u[i] - hi; c += Wt.w_ctrl(P) * v * v; }
+    if (u[i] < lo) { const double v = lo - u[i]; c += Wt.w_ctrl(P) * v * v; }
   }
   return c;
 }
@@ -73,38 +94,41 @@ DEVFN bool support_point(const ProblemDev& P, int b, int t, double* ps) {
   return false;
 }
 // one knot of computeTotalCost (ilqr.cpp:370-443 / 447-510) including its share of the penalties (512-515)
-template <class ComFn>
-DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u /*null at t==N*/, ComFn com_fn) {
+template <bool WS, class ComFn>
+DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, const double* u /*null at t==N*/, ComFn com_fn) {
+  const CostWeights<WS> Wt(P, b);
   const bool term = (t == P.N);
   const double* xr = P.x_ref + b * P.x_ref_stride + t * H1_NX;
-  const double* Qd = term ? P.Qf : P.Q;
+  const double* Qd = Wt.Qd(P, term);
   double a = 0.0;
   for (int i = 0; i < H1_NX; ++i) { const double e = x[i] - xr[i]; a += e * Qd[i] * e; }
   double c = 0.5 * a;
   if (!term) {
     const double* ur = P.u_ref + b * P.u_ref_stride + t * H1_NU;
     double s = 0.0;
-    for (int i = 0; i < H1_NU; ++i) { const double e = u[i] - ur[i]; s += e * P.R[i] * e; }
+    for (int i = 0; i < H1_NU; ++i) { const double e = u[i] - ur[i]; s += e * Wt.R(P, i) * e; }
     c += 0.5 * s;
   }
-  if (P.w_upright > 0.0) {
+  if (Wt.w_upright(P) > 0.0) {
     const double qw = x[3], qx = x[4], qy = x[5], qz = x[6];
     const double zx = 2.0 * (qx * qz + qw * qy), zy = 2.0 * (qy * qz - qw * qx), zz = 1.0 - 2.0 * (qx * qx + qy * qy);
-    c += 0.5 * P.w_upright * (zx * zx + zy * zy + (zz - 1.0) * (zz - 1.0));
+    c += 0.5 * Wt.w_upright(P) * (zx * zx + zy * zy + (zz - 1.0) * (zz - 1.0));
   }
-  if (P.w_balance > 0.0) {
+  if (Wt.w_balance(P) > 0.0) {
     double ps[2];
     if (support_point(P, b, t, ps)) {
       double com[3]; com_fn(x, com);
       const double om = sqrt(com[2] / 9.81);
       const double rx = com[0] + x[H1_NQ] * om - ps[0], ry = com[1] + x[H1_NQ + 1] * om - ps[1];
-      c += 0.5 * P.w_balance * (rx * rx + ry * ry);
+      c += 0.5 * Wt.w_balance(P) * (rx * rx + ry * ry);
     }
   }
-  c += joint_penalty(P, x);
-  if (!term) c += ctrl_penalty(P, u);
+  c += joint_penalty(P, Wt, x);
+  if (!term) c += ctrl_penalty(P, Wt, u);
   return c;
 }
+template <class ComFn>
+DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn) { return knot_cost_w<false>(P, b, t, x, u, com_fn); }
 struct ComLoop { DEVFN void operator()(const double* x, double* com) const { com_mj(x, com); } };
 __device__ inline double knot_cost(const ProblemDev& P, int b, int t, const double* x, const double* u) { return knot_cost_t(P, b, t, x, u, ComLoop()); }
 

@@ -66,6 +66,8 @@ struct ilqr_hip_ctx {
   int* d_stance_dyn = nullptr;            // [B][N][2] stance flags decided from the feet of xbar (stance source GEOMETRY: linearisation, ilqr_hip_get_stance)
   int* d_stance_out = nullptr;            // [step_cap][2] flags decided by ilqr_hip_step_geometry
   int n_xref = 0, n_stance = 0, n_ee = 0;
+  double* d_wsets = nullptr;              // [B][WS_STRIDE] weight-set table (ilqr_hip_set_weight_sets; allocated by its first call); installed while P.wsets points at it
+  int n_wsets = 0;                        // 0: shared weights, else the installed table's n_sets
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
@@ -187,7 +189,18 @@ static inline void enter(ilqr_hip_ctx* c) {
     else { c->env_refused = true; c->err = "ILQR_ENV_PER_CALL: the environment selects a kernel family this library does not hold (see ilqr_hip_create)"; }
   }
 }
-static inline int enter_launching(ilqr_hip_ctx* c) { enter(c); return c->env_refused ? ILQR_ERR_UNSUPPORTED : ILQR_OK; }
+// weight sets exist in the cost kernels of the default family; a family whose rollout / line-search kernels evaluate the cost themselves reads the shared values
+static const char* weight_sets_refusal(const ilqr_hip_ctx* c) {
+  const ilqr::Variants& V = c->knobs.var;
+  if (V.scalar_dyn || !V.rollout_split || !V.ls_split) return "weight sets exist in the default family's cost kernels only; unset ILQR_DYN=s / ILQR_ROLLOUT=r / ILQR_LS=r";
+  return nullptr;
+}
+static inline int enter_launching(ilqr_hip_ctx* c) {
+  enter(c);
+  if (c->env_refused) return ILQR_ERR_UNSUPPORTED;
+  if (c->P.wsets) if (const char* why = weight_sets_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  return ILQR_OK;
+}
 
 extern "C" {
 
@@ -247,6 +260,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   P.w_joint = 500.0; P.w_ctrl = 1000.0;  // RobotUtils ctor defaults, robot_utils.cpp:10
   P.x_ref = c->d_xref; P.u_ref = c->d_uref; P.com_ref = c->d_comref; P.stance = c->d_stance; P.ee_ref = c->d_eeref; P.com_vel_ref = c->d_comvelref;
   P.x_ref_stride = P.u_ref_stride = P.com_ref_stride = P.stance_stride = P.ee_ref_stride = P.com_vel_ref_stride = 0;
+  P.wsets = nullptr; P.wsets_stride = 0;
   // default: stance everywhere (RobotUtils::isStance default, robot_utils.cpp:494-504), lambda = 1e-6 (ilqr.cpp:16)
   std::vector<int> ones((N + 1) * 2, 1);
   hipMemcpyAsync(c->d_stance, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
@@ -270,7 +284,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an}; for (void* p : gp) if (p) hipFree(p); }
@@ -315,6 +329,31 @@ int ilqr_hip_set_constraint_weights(ilqr_hip_ctx* c, double wj, double wc) { if 
 int ilqr_hip_set_gravity(ilqr_hip_ctx* c, double gx, double gy, double gz) { if (!c) return ILQR_ERR_ARG; c->P.dyn.g[0] = gx; c->P.dyn.g[1] = gy; c->P.dyn.g[2] = gz; return ILQR_OK; }
 
 static int check_sets(const ilqr_hip_ctx* c, int n_sets) { return (n_sets == 1 || n_sets == c->B) ? ILQR_OK : ILQR_ERR_ARG; }
+
+int ilqr_hip_set_weight_sets(ilqr_hip_ctx* c, const double* Q, const double* R, const double* Qf, const double* task, const double* constraint, int n_sets) {
+  if (!c || !Q || !R || !Qf || !task || !constraint || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  if (const char* why = weight_sets_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  if (!c->d_wsets) TRY(dalloc(c, &c->d_wsets, (size_t)c->B * h1::WS_STRIDE));
+  std::vector<double> rec((size_t)n_sets * h1::WS_STRIDE, 0.0);
+  for (int s = 0; s < n_sets; ++s) {
+    double* r = rec.data() + (size_t)s * h1::WS_STRIDE;
+    std::memcpy(r + h1::WS_Q, Q + (size_t)s * ILQR_NX, sizeof(double) * ILQR_NX); std::memcpy(r + h1::WS_QF, Qf + (size_t)s * ILQR_NX, sizeof(double) * ILQR_NX);
+    std::memcpy(r + h1::WS_R, R + (size_t)s * ILQR_NU, sizeof(double) * ILQR_NU); std::memcpy(r + h1::WS_TASK, task + (size_t)s * 6, sizeof(double) * 6);
+    r[h1::WS_W_JOINT] = constraint[2 * s]; r[h1::WS_W_CTRL] = constraint[2 * s + 1];
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_wsets, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->P.wsets = c->d_wsets; c->P.wsets_stride = n_sets == 1 ? 0 : (long)h1::WS_STRIDE;
+  c->n_wsets = n_sets;
+  return ILQR_OK;
+}
+int ilqr_hip_clear_weight_sets(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  c->P.wsets = nullptr; c->P.wsets_stride = 0; c->n_wsets = 0;      // (the buffer stays with the handle for the next table)
+  return ILQR_OK;
+}
+int ilqr_hip_num_weight_sets(const ilqr_hip_ctx* c) { return c ? c->n_wsets : -1; }
 
 int ilqr_hip_set_contact_schedule(ilqr_hip_ctx* c, const int* stance, int n_sets) {
   if (!c || !stance || check_sets(c, n_sets)) return ILQR_ERR_ARG;
@@ -517,6 +556,7 @@ static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
   h1::ProblemDev T = P;
   T.x_ref += b0 * P.x_ref_stride; T.u_ref += b0 * P.u_ref_stride; T.com_ref += b0 * P.com_ref_stride;
   T.stance += b0 * P.stance_stride; T.ee_ref += b0 * P.ee_ref_stride; T.com_vel_ref += b0 * P.com_vel_ref_stride;
+  if (P.wsets) T.wsets += b0 * P.wsets_stride;
   return T;
 }
 static int ensure_slices(ilqr_hip_ctx* c, int k) {

@@ -180,6 +180,8 @@ template <int FIRST, int LEN, int FOOT, class Put> struct QChain {
 };
 
 // One lane per knot.  `rec`: the record buffer (quad_rec_doubles); knot0: index of the view's first knot in it (batch slices).
+// WS: the task weights come from the lane's own rollout's weight set (CostWeights, h1_cost_dev.h): the branches on them are per lane
+template <bool WS>
 __global__ void __launch_bounds__(64) k_quad_kin(DevState S, ProblemDev P, const int* list, const int* count, double* rec, long knot0) {
   const int N1 = S.N + 1;
   const unsigned g = blockIdx.x * 64u + threadIdx.x;                    // (32-bit on purpose: a 64-bit division is ~150 scalar instructions)
@@ -324,40 +326,41 @@ __global__ void __launch_bounds__(64) k_quad_kin(DevState S, ProblemDev P, const
     for (int k = 0; k < 3; ++k) { vec[c][k] = 0.0; gsum[c][k] = 0.0; } }
   const int* st = P.stance + b * P.stance_stride + 2 * t;
   const int st0 = st[0], st1 = st[1];
-  if (P.w_com > 0.0) {   // CoM position: w ||com - ref||^2
+  const CostWeights<WS> Wt(P, b);
+  if (Wt.w_com(P) > 0.0) {   // CoM position: w ||com - ref||^2
     const double* ref = P.com_ref + b * P.com_ref_stride + t * 3;
     double rb[3]; mv3(R0, beta[0], rb);
-    gscale[0] = 2.0 * P.w_com;
+    gscale[0] = 2.0 * Wt.w_com(P);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { const double e = mfr[0] * xg[k] + rb[k] - ref[k]; gsum[0][k] = gscale[0] * e; vec[0][k] = gscale[0] * e; }
   }
-  if (!term && P.w_com_vel > 0.0) {
+  if (!term && Wt.w_com_vel(P) > 0.0) {
     const double* ref = P.com_vel_ref + b * P.com_vel_ref_stride + t * 3;
     double v[3]; mv3(R0, gamma[0], v);
-    gscale[1] = 2.0 * P.w_com_vel;
+    gscale[1] = 2.0 * Wt.w_com_vel(P);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { const double e = v[k] - ref[k]; gsum[1][k] = gscale[1] * e; vec[1][k] = gscale[1] * e; }
   }
 #pragma unroll
   for (int ee = 0; ee < 2; ++ee) {
     const int set = 1 + ee, ste = ee == 0 ? st0 : st1;
-    if (P.w_ee_pos > 0.0 && ste != 1) {
+    if (Wt.w_ee_pos(P) > 0.0 && ste != 1) {
       const double* ref = P.ee_ref + b * P.ee_ref_stride + (t * 2 + ee) * 3;
       double rb[3]; mv3(R0, beta[set], rb);
-      gscale[2 + ee] = 2.0 * P.w_ee_pos;
+      gscale[2 + ee] = 2.0 * Wt.w_ee_pos(P);
 #pragma unroll
       for (int k = 0; k < 3; ++k) { const double e = mfr[set] * xg[k] + rb[k] - ref[k]; gsum[2 + ee][k] = gscale[2 + ee] * e; vec[2 + ee][k] = gscale[2 + ee] * e; }
     }
-    if (P.w_ee_vel > 0.0 && ste == 1) {
+    if (Wt.w_ee_vel(P) > 0.0 && ste == 1) {
       double e[3]; mv3(R0, gamma[set], e);   // zero target (ilqr.cpp:734)
-      gscale[2 + ee] = 2.0 * P.w_ee_vel;
+      gscale[2 + ee] = 2.0 * Wt.w_ee_vel(P);
 #pragma unroll
       for (int k = 0; k < 3; ++k) { gsum[2 + ee][k] = gscale[2 + ee] * e[k]; vec[2 + ee][k] = gscale[2 + ee] * e[k]; }
     }
   }
   double ps[2];
   double hasbal = 0.0, bal[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (P.w_balance > 0.0 && support_point(P, b, t, ps)) {
+  if (Wt.w_balance(P) > 0.0 && support_point(P, b, t, ps)) {
     double rb[3], vc[3]; mv3(R0, beta[0], rb); mv3(R0, gamma[0], vc);
     double com[3];
 #pragma unroll
@@ -370,7 +373,7 @@ __global__ void __launch_bounds__(64) k_quad_kin(DevState S, ProblemDev P, const
     hasbal = 1.0;
     const double mu[3] = {r0, r1, om1 * rv}, nu[3] = {om * r0, om * r1, 0.0};
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { vec[0][k] += P.w_balance * mu[k]; vec[1][k] += P.w_balance * nu[k]; }
+    for (int k = 0; k < 3; ++k) { vec[0][k] += Wt.w_balance(P) * mu[k]; vec[1][k] += Wt.w_balance(P) * nu[k]; }
   }
   put(QR_HASBAL, hasbal);
 #pragma unroll
@@ -644,6 +647,10 @@ DEVFN void quad_hessian_tiles(const double (&av)[4][2], const double (&bv)[4][4]
 // which that kernel loads whole, and every stage-API call keep the full matrix (ilqr_hip_get_quadratics mirrors the tiles back).
 // Workgroup numbering: workgroups are dealt to the 8 XCDs round-robin by index, and 16 consecutive knots share the 128-byte
 // lines of a record group; workgroup L therefore takes knot item (L % 8) * ceil(total / 8) + L / 8 -- consecutive items on one XCD.
+// WS: the weights are rollout b's weight set.  b is one value for the workgroup (blockIdx, or one list[bs] load) and is pinned to a scalar
+// register, so the record's address is wave-uniform: the weight reads stay scalar loads and the `w > 0.0` branches scalar branches.  The
+// table is indexed by the rollout b, never by its position bs in a compacted list.
+template <bool WS>
 __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S, ProblemDev P, int mode, const int* list, const int* count, int lower,
                                                                      const double* recg, long knot0) {
   const int lane = threadIdx.x, wv = lane >> 6;
@@ -655,6 +662,10 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   const int bs = (int)(item / (unsigned)N1), t = (int)(item - (unsigned)bs * (unsigned)N1);
   int b = bs;
   if (list) { b = list[bs]; mode = MASK_ALL; }     // compacted selection (DevState::order): no per-rollout flags to fetch
+  if constexpr (WS) b = __builtin_amdgcn_readfirstlane(b);
+  const CostWeights<WS> Wt(P, b);
+  // the set's four scalars this kernel uses, fetched ahead of its first store: behind a store they could not be scalar loads any more
+  const double w_upright_b = Wt.w_upright(P), w_balance_b = Wt.w_balance(P), w_joint_b = Wt.w_joint(P), w_ctrl_b = Wt.w_ctrl(P);
   const bool term = (t == N);
   const bool pk = lower == 2;            // operand layout (every knot, the terminal one included)
   __shared__ QuadLds L;
@@ -666,10 +677,14 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
 
   // ---- phase 0: the knot's record -> LDS.  The rollout's selection flags are requested together with the knot's data (indices
   // clamped instead of predicated) and tested before anything is written; so is everything phase 1 wants from HBM
-  const double* Qd = term ? P.Qf : P.Q;
+  // (the two reads that do not go through CostWeights for WS = false are this select and R[l1] of phase 2: the shared instantiation keeps
+  // the statements it had before the kernel became a template, so that its code object stays the one docs/KERNEL_RESOURCES_WEIGHT_SETS.md
+  // records; tools/kernel_resources.py tells whether folding them into the accessor would still change it)
+  const double* Qd;
+  if constexpr (WS) Qd = Wt.Qd(P, term); else Qd = term ? P.Qf : P.Q;
   const int* stq = P.stance + b * P.stance_stride + 2 * t;      // (wave-uniform: scalar loads)
   const int fvel[2] = {stq[0] == 1, stq[1] == 1};               // stance foot: the velocity functional; swing foot: the position one
-  double xv, xrv, qdv, uv = 0.0, urv = 0.0;
+  double xv, xrv, qdv, uv = 0.0, urv = 0.0, rwv = 0.0;
   unsigned colw[2], patw[3];
   {
     const int f1 = mode == MASK_ALL ? 1 : S.active[b], f2 = mode == MASK_RETRY ? S.need_retry[b] : 1;
@@ -682,7 +697,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
     const int a = lane < H1_NX ? lane : 0;
     xv = xg[a]; xrv = (P.x_ref + b * P.x_ref_stride + t * H1_NX)[a]; qdv = Qd[a];
     const int l1 = lane - 64, iu = (l1 >= 0 && l1 < H1_NU) ? l1 : 0, tu = term ? N - 1 : t;
-    if (wv == 1) { uv = S.ubar[((size_t)b * N + tu) * H1_NU + iu]; urv = (P.u_ref + b * P.u_ref_stride + tu * H1_NU)[iu]; }
+    if (wv == 1) { uv = S.ubar[((size_t)b * N + tu) * H1_NU + iu]; urv = (P.u_ref + b * P.u_ref_stride + tu * H1_NU)[iu]; if constexpr (WS) rwv = Wt.R(P, iu); }
     // the table words of phases 1a and 2b travel with the knot's data as well (each was a dependent round trip to the constant
     // segment in the middle of its phase: 8 k cycles for a phase of ~40 instructions)
     {
@@ -765,18 +780,18 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       double g = qdv * (xv - xrv);   // Q acts on the MuJoCo-ordered state
 #pragma unroll
       for (int i = 0; i < 4; ++i) { const double* gs = rec + QR_GSUM + 3 * i; g += jj[i][0] * gs[0] + jj[i][1] * gs[1] + jj[i][2] * gs[2]; }
-      if (P.w_upright > 0.0 && a >= 3 && a < 7) {
+      if (w_upright_b > 0.0 && a >= 3 && a < 7) {
         const double* uJ = rec + QR_UJ; const double* ur = rec + QR_UR;
-        g += P.w_upright * (uJ[a - 3] * ur[0] + uJ[4 + a - 3] * ur[1] + uJ[8 + a - 3] * ur[2]);
+        g += w_upright_b * (uJ[a - 3] * ur[0] + uJ[4 + a - 3] * ur[1] + uJ[8 + a - 3] * ur[2]);
       }
-      if (has_bal) g += P.w_balance * (jr0 * bal[0] + jr1 * bal[1]);
+      if (has_bal) g += w_balance_b * (jr0 * bal[0] + jr1 * bal[1]);
       double dgl = qdv;
       if (a >= 7 && a < H1_NQ) {
         double lo, hi; limit_bounds(H1_JRANGE[a - 7], lo, hi);
         const double q = xv;                           // (hinge slots are not permuted)
-        if (q > hi) g += 2.0 * P.w_joint * (q - hi);
-        if (q < lo) g += -2.0 * P.w_joint * (lo - q);
-        if (q > hi || q < lo) dgl += 2.0 * P.w_joint;
+        if (q > hi) g += 2.0 * w_joint_b * (q - hi);
+        if (q < lo) g += -2.0 * w_joint_b * (lo - q);
+        if (q > hi || q < lo) dgl += 2.0 * w_joint_b;
       }
       S.lx[((size_t)b * N1 + t) * H1_NX + a] = g;
       L.dg[a] = dgl;
@@ -814,11 +829,12 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
     }
     if (!term && l1 < H1_NU) {
       const double u = uv;
-      double g = P.R[l1] * (u - urv), h = P.R[l1];
+      auto Rl = [&]() { if constexpr (WS) return rwv; else return Wt.R(P, l1); };         // (the set's R[l1] came with the phase-0 loads)
+      double g = Rl() * (u - urv), h = Rl();
       double lo, hi; limit_bounds(H1_CTRLRANGE[l1], lo, hi);
-      if (u > hi) g += 2.0 * P.w_ctrl * (u - hi);
-      if (u < lo) g += -2.0 * P.w_ctrl * (lo - u);
-      if (u > hi || u < lo) h += 2.0 * P.w_ctrl;
+      if (u > hi) g += 2.0 * w_ctrl_b * (u - hi);
+      if (u < lo) g += -2.0 * w_ctrl_b * (lo - u);
+      if (u > hi || u < lo) h += 2.0 * w_ctrl_b;
       S.lu[((size_t)b * N + t) * H1_NU + l1] = g;
       S.luu[((size_t)b * N + t) * H1_NU + l1] = h;
     }
@@ -841,7 +857,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       const double* rowJ = L.J[3 * ks + (lk < 3 ? lk : 0)];
       const double* rowA = lk < 3 ? rowJ : (ks == 0 ? L.J[QJ_R0] : (ks == 1 ? L.J[QJ_R1] : (ks == 2 ? L.J[QJ_C + 2] : L.J[QJ_M])));
       const double* rowB = lk < 3 ? rowJ : (ks == 0 ? L.J[QJ_R0] : (ks == 1 ? L.J[QJ_R1] : (ks == 2 ? L.J[QJ_M] : L.J[QJ_C + 2])));
-      const double sA = lk < 3 ? rec[QR_GSCALE + ks] : P.w_balance;
+      const double sA = lk < 3 ? rec[QR_GSCALE + ks] : w_balance_b;
       const bool used = lk < 3 ? (sA != 0.0) : (has_bal != 0);
 #pragma unroll
       for (int T = 0; T < 4; ++T) {
@@ -960,7 +976,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
         double tv[3]; mv3(D2, cvel[c] ? rec + QR_GAMMA + 3 * st_ : rec + QR_BETA + 3 * st_, tv);
         h += dot3(rec + QR_VEC + 3 * c, tv);
       }
-      if (P.w_upright > 0.0) {
+      if (w_upright_b > 0.0) {
         const int i = ka, j = kb;
         const double* uJ = rec + QR_UJ; const double* ur = rec + QR_UR;
         double v = uJ[i] * uJ[j] + uJ[4 + i] * uJ[4 + j] + uJ[8 + i] * uJ[8 + j];
@@ -968,7 +984,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
         if (i == 2 && j == 3) v += 2.0 * ur[1];
         if (i == 0 && j == 1) v += -2.0 * ur[1];
         if ((i == 1 && j == 1) || (i == 2 && j == 2)) v += -4.0 * ur[2];
-        h += P.w_upright * v;
+        h += w_upright_b * v;
       }
       patch(Q0 + ka, Q0 + kb, h);
     }
@@ -988,10 +1004,13 @@ void launch_cost_quadratics(const DevState& S, const ProblemDev& P, int mode, hi
   const WorkList w = wl ? *wl : work_list(S, mode, iter);
   const long knots = (long)S.B * (S.N + 1);
   // the per-knot kinematics run for every rollout a masked (stage-API) launch might select; inside a solve for the compacted list
-  hipLaunchKernelGGL(k_quad_kin, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
+  // (a weight-set table, ProblemDev::wsets, selects the WS instantiations of both kernels)
+  if (P.wsets) hipLaunchKernelGGL(k_quad_kin<true>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
+  else hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
   // one workgroup per knot; the grid is padded to a multiple of 8 so that every XCD's share (L % 8) has ceil(total / 8) slots
   const long per = (knots + 7) / 8;
-  hipLaunchKernelGGL(k_cost_quadratics, dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  if (P.wsets) hipLaunchKernelGGL(k_cost_quadratics<true>, dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  else hipLaunchKernelGGL(k_cost_quadratics<false>, dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
 }
 
 }  // namespace ilqr

@@ -75,6 +75,24 @@ def make_problem(kin, N=25, cfg=SHIPPED_CONFIG, x_ref=None, stance=None, gravity
     )
 
 
+WEIGHT_KEYS = ("Q", "R", "Qf", "task_weights", "w_joint", "w_ctrl")
+
+
+def stack_weight_sets(problem, sets):
+    """Problem dict for a weight sweep: rollout b solves `problem` under the weights of sets[b], a dict that overrides any of Q, R, Qf,
+    task_weights, w_joint, w_ctrl (what it leaves out keeps the base value).  The six items come back stacked on a leading axis of
+    len(sets) -- Q [B,51], R [B,19], Qf [B,51], task_weights [B,6], w_joint [B], w_ctrl [B] -- which BatchedILQR.set_problem installs as
+    per-rollout weight sets; everything else is shared with `problem`."""
+    for b, ov in enumerate(sets):
+        bad = set(ov) - set(WEIGHT_KEYS)
+        if bad:
+            raise KeyError("set %d overrides %s: only %s vary per rollout" % (b, sorted(bad), ", ".join(WEIGHT_KEYS)))
+    out = dict(problem)
+    for k in WEIGHT_KEYS:
+        out[k] = np.stack([np.asarray(ov.get(k, problem[k]), dtype=np.float64) for ov in sets])
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

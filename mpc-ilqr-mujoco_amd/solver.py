@@ -24,6 +24,7 @@ JAC_ANALYTIC, JAC_FD_FORWARD = 0, 1
 EXPORTS = [
     "ilqr_hip_create", "ilqr_hip_destroy", "ilqr_hip_last_error", "ilqr_hip_batch", "ilqr_hip_horizon", "ilqr_hip_num_slices", "ilqr_hip_reload_environment", "ilqr_hip_set_dedup_saturated_retry",
     "ilqr_hip_set_cost_weights", "ilqr_hip_set_task_weights", "ilqr_hip_set_constraint_weights", "ilqr_hip_set_gravity",
+    "ilqr_hip_set_weight_sets", "ilqr_hip_clear_weight_sets", "ilqr_hip_num_weight_sets",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -124,6 +125,22 @@ def gravity_compensation(x, gravity):
     return u
 
 
+def weight_sets_of(prob, B):
+    """The per-rollout weight table a problem dict asks for, or None: a table is wanted when any of Q / R / Qf is 2-D or task_weights /
+    w_joint / w_ctrl has a leading axis of length B; the items that are still shared are broadcast to every set.
+    Returns (Q [B,51], R [B,19], Qf [B,51], task [B,6], constraint [B,2])."""
+    Q, R, Qf = (np.asarray(prob[k], dtype=np.float64) for k in ("Q", "R", "Qf"))
+    task = np.asarray(prob["task_weights"], dtype=np.float64)
+    wj, wc = np.asarray(prob["w_joint"], dtype=np.float64), np.asarray(prob["w_ctrl"], dtype=np.float64)
+    if not (Q.ndim == 2 or R.ndim == 2 or Qf.ndim == 2 or task.ndim == 2 or wj.ndim == 1 or wc.ndim == 1):
+        return None
+    for name, a, shape in (("Q", Q, (NX,)), ("R", R, (NU,)), ("Qf", Qf, (NX,)), ("task_weights", task, (6,)), ("w_joint", wj, ()), ("w_ctrl", wc, ())):
+        if a.shape != shape and a.shape != (B,) + shape:
+            raise ValueError("%s: shape %s is neither %s (shared) nor %s (one per rollout)" % (name, a.shape, shape, (B,) + shape))
+    bc = lambda a, shape: np.ascontiguousarray(np.broadcast_to(a, (B,) + shape))
+    return bc(Q, (NX,)), bc(R, (NU,)), bc(Qf, (NX,)), bc(task, (6,)), np.ascontiguousarray(np.stack([np.broadcast_to(wj, (B,)), np.broadcast_to(wc, (B,))], axis=1))
+
+
 class BatchedILQR:
     """iLQR for B independent rollouts on one GPU (reference include/ilqr/ilqr.hpp:17-45)."""
 
@@ -165,9 +182,16 @@ class BatchedILQR:
     # ---- problem data (RobotUtils setters)
     def set_problem(self, prob):
         L, h = self.L, self.h
-        self._chk(L.ilqr_hip_set_cost_weights(h, _p(_c64(prob["Q"])), _p(_c64(prob["R"])), _p(_c64(prob["Qf"]))))
-        self._chk(L.ilqr_hip_set_task_weights(h, *[C.c_double(float(v)) for v in prob["task_weights"]]))
-        self._chk(L.ilqr_hip_set_constraint_weights(h, C.c_double(prob["w_joint"]), C.c_double(prob["w_ctrl"])))
+        sets = weight_sets_of(prob, self.B)
+        if sets is not None:
+            # per-rollout weights: the table carries every weight (shared items broadcast); the shared setters keep what they hold
+            self.set_weight_sets(*sets)
+        else:
+            self._chk(L.ilqr_hip_set_cost_weights(h, _p(_c64(prob["Q"])), _p(_c64(prob["R"])), _p(_c64(prob["Qf"]))))
+            self._chk(L.ilqr_hip_set_task_weights(h, *[C.c_double(float(v)) for v in prob["task_weights"]]))
+            self._chk(L.ilqr_hip_set_constraint_weights(h, C.c_double(prob["w_joint"]), C.c_double(prob["w_ctrl"])))
+            if self.num_weight_sets():
+                self.clear_weight_sets()
         g = prob["gravity"]
         self.gravity = np.array(g, dtype=np.float64)
         self._chk(L.ilqr_hip_set_gravity(h, C.c_double(g[0]), C.c_double(g[1]), C.c_double(g[2])))
@@ -176,6 +200,24 @@ class BatchedILQR:
         ee, cv = _c64(prob["ee_ref"]), _c64(prob["com_vel_ref"])
         self._chk(L.ilqr_hip_set_ee_references(h, _p(ee), _p(cv), int(ee.shape[0])))
         self.set_references(prob["x_ref"], prob["u_ref"], prob["com_ref"])
+
+    def set_weight_sets(self, Q, R, Qf, task_weights, constraint_weights):
+        """One set of cost weights per rollout (ilqr_hip_set_weight_sets): Q [n,51], R [n,19], Qf [n,51], task_weights [n,6] in the order of
+        prob["task_weights"], constraint_weights [n,2] = (w_joint, w_ctrl); n = 1 or B.  Takes precedence over the shared weights until
+        clear_weight_sets()."""
+        Q, R, Qf, tw, cw = (np.atleast_2d(_c64(a)) for a in (Q, R, Qf, task_weights, constraint_weights))
+        n = Q.shape[0]
+        if Q.shape != (n, NX) or R.shape != (n, NU) or Qf.shape != (n, NX) or tw.shape != (n, 6) or cw.shape != (n, 2):
+            raise ValueError("weight sets: Q [n,51], R [n,19], Qf [n,51], task_weights [n,6], constraint_weights [n,2] with one n")
+        self._chk(self.L.ilqr_hip_set_weight_sets(self.h, _p(Q), _p(R), _p(Qf), _p(tw), _p(cw), int(n)))
+
+    def clear_weight_sets(self):
+        """Back to the shared weights the handle holds."""
+        self._chk(self.L.ilqr_hip_clear_weight_sets(self.h))
+
+    def num_weight_sets(self):
+        """0: shared weights; else the number of sets of the installed table (1 or B)."""
+        return int(self.L.ilqr_hip_num_weight_sets(self.h))
 
     def set_references(self, x_ref, u_ref, com_ref):
         x_ref, u_ref, com_ref = _c64(x_ref), _c64(u_ref), _c64(com_ref)
