@@ -48,7 +48,7 @@ typedef struct ilqr_hip_ctx ilqr_hip_ctx;
 int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt);
 int ilqr_hip_destroy(ilqr_hip_ctx* ctx);
 /* The diagnostic environment switches (kernel families ILQR_BACKWARD / ILQR_LS / ILQR_ROLLOUT / ILQR_DYN / ILQR_LINT, launch orders
-   ILQR_SLICES / ILQR_STAGGER / ILQR_OVERLAP_ROLLOUT / ILQR_REUSE_ROLLOUT / ILQR_EE_GATE / ILQR_SPLIT / ILQR_SPEC*) are read ONCE, by
+   ILQR_SLICES / ILQR_STAGGER / ILQR_OVERLAP_ROLLOUT / ILQR_REUSE_ROLLOUT / ILQR_EE_GATE / ILQR_SPLIT / ILQR_SPEC* / ILQR_RELIN) are read ONCE, by
    ilqr_hip_create, and kept in the handle: no getenv on the call path, and the handle's copy is the only one -- handles of different
    kernel families may be driven from one host thread in any order.  This call re-reads them for one handle (tests, profiling tools);
    ILQR_ENV_PER_CALL=1 at creation makes every call of the handle do so, and while such a re-read names a kernel family the library
@@ -380,6 +380,23 @@ int ilqr_hip_get_speculative_iterations(const ilqr_hip_ctx* ctx);
    Bit-identical results.  On by default when the convergence exit is enabled (where it pays; with a fixed iteration count nearly every
    rollout retries and the early group is small); environment ILQR_SPLIT=0 / 1 forces it off / on.  Returns the count, -1 for a null handle. */
 int ilqr_hip_get_split_iterations(const ilqr_hip_ctx* ctx);
+/* Linearisation cache.  A rollout whose two line searches of an iteration both fail (ilqr.cpp:640-655, the failing branch) keeps its
+   nominal trajectory bit for bit, and A_t, B_t, lx, lu, lxx, luu are functions of that trajectory and of the problem data alone -- not
+   of lambda: the next iteration's linearisation (:576) and cost quadratics (:588) would rewrite the values the buffers hold.  By default
+   they run, from iteration 1 on, only for the rollouts that accepted a candidate in the previous iteration (a list k_control builds on the
+   device); iteration 0 of every solve takes every rollout.  Every pass, decision, trace entry and lambda update stays where it is and
+   every observable of the solve is unchanged, bit for bit (GPU test).  on != 0 restores the full pass in every iteration (comparison,
+   profiling); environment ILQR_RELIN=1 / 0 overrides the handle's setting (read with the other switches, ilqr_hip_reload_environment).
+   The full pass is also what runs, whatever the setting, with forward-difference Jacobians, with batch slices and in the stage API.
+   bench.py's whole_iteration_frac* figures charge every iteration a full linearisation and cost-quadratics pass: with the cache they are
+   algorithmic-equivalent rates.  No reference counterpart: the reference recomputes. */
+int ilqr_hip_set_relinearize_unchanged(ilqr_hip_ctx* ctx, int on);
+/* Sum over the iterations of the last solve of the number of rollouts whose linearisation and cost quadratics ran: batch x iterations
+   with ilqr_hip_set_relinearize_unchanged set and a fixed iteration count (with the convergence exit: the rollouts still active, per
+   iteration), the executed count with the cache.  Synchronises the handle's stream.  0 before the first solve and after
+   ilqr_hip_set_max_iterations changed the count, -1 for a null handle or a failed read.  No reference counterpart: the reference
+   recomputes. */
+long long ilqr_hip_get_linearized_rollouts(ilqr_hip_ctx* ctx);
 
 /* ---- host-side model helpers (no GPU needed) ---- */
 /* reference construction as RobotUtils::loadReferences does it (src/common/robot_utils.cpp:369-403):

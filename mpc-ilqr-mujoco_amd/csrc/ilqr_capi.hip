@@ -27,6 +27,7 @@ using ilqr::DevState;
 struct Knobs {
   ilqr::Variants var;
   int dedup_retry;      // ILQR_DEDUP_RETRY (-1: the handle's own setting, ilqr_hip_set_dedup_saturated_retry)
+  int relin;            // ILQR_RELIN (-1: the handle's own setting, ilqr_hip_set_relinearize_unchanged)
   int slices, stagger, overlap_rollout, reuse_rollout, ee_gate /* -1: the handle's own setting */, split /* -1: on with the convergence exit */, spec, spec_dual, spec_max;
   bool per_call;
 };
@@ -40,6 +41,7 @@ static Knobs read_knobs() {
   k.slices = geti("ILQR_SLICES", SLICES_DEFAULT);
   k.stagger = geti("ILQR_STAGGER", 1);
   k.dedup_retry = geti("ILQR_DEDUP_RETRY", -1);
+  k.relin = geti("ILQR_RELIN", -1);
   k.overlap_rollout = geti("ILQR_OVERLAP_ROLLOUT", 1);
   { const char* e = getenv("ILQR_REUSE_ROLLOUT"); k.reuse_rollout = (e && e[0] == '1') ? 1 : 0; }
   k.ee_gate = geti("ILQR_EE_GATE", -1);
@@ -103,6 +105,11 @@ struct ilqr_hip_ctx {
   int lxx_layout = 0;
   bool ab_packed = false, ab_pads_clean = false;
   int dedup_retry = 0;          // ilqr_hip_set_dedup_saturated_retry
+  // linearisation cache (enqueue_solve): relin = ilqr_hip_set_relinearize_unchanged; what the last solve did, for
+  // ilqr_hip_get_linearized_rollouts: lin_iterations (0: no solve, or its lists are gone), lin_cached = iterations >= 1 ran from
+  // DevState::chg, lin_listed = the region of every iteration ran from list (it, 0) (convergence exit, whole batch), else from no list
+  int relin = 0, lin_iterations = 0;
+  bool lin_cached = false, lin_listed = false;
   bool env_refused = false;     // ILQR_ENV_PER_CALL: the last re-read selected a family this library does not hold (enter, enter_launching)
   double packed_h = 0.0;        // step size h of the packed image while ab_packed (k_unpack_ab rebuilds the position rows from it)
   Knobs knobs = read_knobs();   // (constructed in ilqr_hip_create)
@@ -238,6 +245,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   A(dalloc(c, &S.trace_cost, B * (c->max_iter + 1))); A(dalloc(c, &S.trace_alpha, B * c->max_iter)); A(dalloc(c, &S.trace_lambda, B * c->max_iter));
   A(dalloc(c, &S.order, B * 2 * (c->max_iter + 1))); A(dalloc(c, &S.order_n, 2 * (size_t)(c->max_iter + 1)));
   A(dalloc(c, &S.grp_a, B)); A(dalloc(c, &S.grp_r, B)); A(dalloc(c, &S.order_r, B)); A(dalloc(c, &S.order_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.order_an, (size_t)c->max_iter + 2));
+  A(dalloc(c, &S.chg, B * (c->max_iter + 1))); A(dalloc(c, &S.chg_n, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_r, B)); A(dalloc(c, &S.chg_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_an, (size_t)c->max_iter + 2));
   if (rc == ILQR_OK && (hipStreamCreate(&c->a1) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_roll, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_lin, hipEventDisableTiming) != hipSuccess ||
@@ -287,7 +295,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
                   c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
-  { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an}; for (void* p : gp) if (p) hipFree(p); }
+  { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
   { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
@@ -413,6 +421,9 @@ int ilqr_hip_set_max_iterations(ilqr_hip_ctx* c, int max_iter) {
     if (c->S.order_an) hipFree(c->S.order_an);
     c->S.order_rn = c->S.order_an = nullptr;
     TRY(dalloc(c, &c->S.order_rn, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.order_an, (size_t)max_iter + 2));
+    { void* cp[] = {c->S.chg, c->S.chg_n, c->S.chg_rn, c->S.chg_an}; for (void* p : cp) if (p) hipFree(p); }
+    c->S.chg = c->S.chg_n = c->S.chg_rn = c->S.chg_an = nullptr; c->lin_iterations = 0;
+    TRY(dalloc(c, &c->S.chg, (size_t)c->B * (max_iter + 1))); TRY(dalloc(c, &c->S.chg_n, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.chg_rn, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.chg_an, (size_t)max_iter + 2));
   }
   return ILQR_OK;
 }
@@ -550,6 +561,7 @@ static DevState slice_state(const DevState& S, size_t b0, int Bs) {
   T.trace_cost += b0 * (mi + 1); T.trace_alpha += b0 * mi; T.trace_lambda += b0 * mi;
   T.order = nullptr; T.order_n = nullptr;      // the compacted lists index the whole batch: not used by slices
   T.grp_a = T.grp_r = T.order_r = T.order_rn = T.order_an = nullptr;
+  T.chg = T.chg_n = T.chg_r = T.chg_rn = T.chg_an = nullptr;
   return T;
 }
 static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
@@ -674,6 +686,17 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // ilqr_hip_set_dedup_saturated_retry: bit 1 of k_control's early_exit argument (the sequential orders; the side-by-side order has
   // both passes in flight before either outcome is known)
   const int dedup_bit = (c->knobs.dedup_retry >= 0 ? c->knobs.dedup_retry : c->dedup_retry) ? 2 : 0;
+  // Linearisation cache: from iteration 1 on the per-knot kernels of the region (stance decisions, primal dump, tangent sweeps, kinematics
+  // record, cost quadratics) run from DevState::chg -- the active rollouts whose previous iteration accepted a candidate.  A rollout
+  // whose two line searches both failed enters the iteration with the nominal trajectory it had, bit for bit (k_control copies nothing),
+  // and S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu are functions of that trajectory and the problem data alone (not of lambda) that nothing
+  // between two regions writes: the backward kernels and the twin view read them, the control / adoption kernels never touch them,
+  // the in-place layout conversions belong to the getters and the stage API, outside a solve.  Iteration 0 takes every rollout.  Not for
+  // the forward-difference kernels (they select by S.active and use S.A / S.Bm as scratch) nor for batch slices (no lists);
+  // ilqr_hip_set_relinearize_unchanged / ILQR_RELIN=1: the full pass in every iteration.
+  const bool analytic_lists = c->jac_mode == ILQR_JAC_ANALYTIC && (!V.scalar_dyn || !P.dyn.contact);
+  const bool cache = !(c->knobs.relin >= 0 ? c->knobs.relin : c->relin) && S.order && S.chg && analytic_lists;
+  c->lin_cached = cache; c->lin_listed = sel_mode != ilqr::MASK_ALL && S.order != nullptr;
   struct Rg { hipStream_t m, q, r; hipEvent_t fork, join, roll, lin, adopt; };
   const Rg G0{st, st2, st3, ev_fork, ev_join, ev_roll, ev_lin, ev_adopt};
   // (group A's cost quadratics and re-rollout share the second and third stream with group R -- idle while the retry runs, and R's
@@ -724,10 +747,11 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     if (!prev_split) {
       if ((iter == 0 || !c->knobs.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(V, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
       if (iter == 0 && wait_lead) HIPCHK(c, hipStreamWaitEvent(st, wait_lead, 0));
-      TRY(region(G0, st, S, sel_mode, iter, nullptr, concurrent_roll));
+      const ilqr::WorkList wc{S.chg + (size_t)iter * S.B, S.chg_n + iter};
+      TRY(region(G0, st, S, sel_mode, iter, (cache && iter > 0) ? &wc : nullptr, concurrent_roll));
     } else {
-      DevState Sg = S; Sg.active = S.grp_r;
-      const ilqr::WorkList wr{S.order_r, S.order_rn + iter};
+      DevState Sg = S; Sg.active = S.grp_r;      // (the mask-selected kernels: every rollout of the group, changed or not)
+      const ilqr::WorkList wr = cache ? ilqr::WorkList{S.chg_r, S.chg_rn + iter} : ilqr::WorkList{S.order_r, S.order_rn + iter};
       TRY(region(G0, st, Sg, ilqr::MASK_ACTIVE, -1, &wr, true));
       ++c->split_iterations;
     }
@@ -811,7 +835,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
       HIPCHK(c, hipMemcpyAsync(S.order_an + iter + 1, S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToDevice, st));
       DevState Sg = S; Sg.active = S.grp_a;
-      const ilqr::WorkList wa{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
+      if (cache) HIPCHK(c, hipMemcpyAsync(S.chg_an + iter + 1, S.chg_n + iter + 1, sizeof(int), hipMemcpyDeviceToDevice, st));
+      const ilqr::WorkList wa = cache ? ilqr::WorkList{S.chg + (size_t)(iter + 1) * S.B, S.chg_an + iter + 1} : ilqr::WorkList{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
       TRY(region(GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
     }
     { StageTimer T(c, 6, st); ilqr::launch_backward(V, S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
@@ -826,7 +851,22 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   if (prev_split) {      // (the convergence exit ended the loop behind a group A that found nothing to do: its streams rejoin)
     HIPCHK(c, hipStreamWaitEvent(st, GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.lin, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.adopt, 0));
   }
+  c->lin_iterations = c->iterations_enqueued;
   return ILQR_OK;
+}
+int ilqr_hip_set_relinearize_unchanged(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->relin = on ? 1 : 0; return ILQR_OK; }
+long long ilqr_hip_get_linearized_rollouts(ilqr_hip_ctx* c) {
+  if (!c) return -1;
+  enter(c);
+  const int n = c->lin_iterations;
+  if (n <= 0) return 0;
+  if (!c->lin_cached && !c->lin_listed) return (long long)c->B * n;
+  std::vector<int> act(2 * (size_t)(c->max_iter + 1)), chg((size_t)c->max_iter + 2);
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "ilqr_hip_get_linearized_rollouts: reading the list counts failed"; return -1; }
+  long long total = 0;
+  for (int it = 0; it < n; ++it) total += (it > 0 && c->lin_cached) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
+  return total;
 }
 int ilqr_hip_get_split_iterations(const ilqr_hip_ctx* c) { return c ? c->split_iterations : -1; }
 int ilqr_hip_get_speculative_iterations(const ilqr_hip_ctx* c) { return c ? c->spec_iterations : -1; }

@@ -65,6 +65,17 @@ struct DevState {
   int* order_r;        // [B]
   int* order_rn;       // [max_iter + 2]
   int* order_an;       // [max_iter + 2]
+  // Linearisation cache (ilqr_capi.hip enqueue_solve): list it = the rollouts active in iteration it that ACCEPTED a candidate in iteration
+  // it - 1 (k_control / k_control_spec: acc >= 0, the condition under which xbar / ubar are overwritten), in the order of list (it, 0)
+  // restricted to them.  The other active rollouts enter iteration it with the nominal trajectory of iteration it - 1 bit for bit: A_t,
+  // B_t, lxx~_t, lx_t, lu_t, luu_t depend on that trajectory and the problem data only, so the per-knot kernels of the concurrent region
+  // run from this list.  Early continuation: group A = the first chg_an[it] entries (phase 0 fills the list first), group R = chg_r[0 ..
+  // chg_rn[it]) (phase 1).  Null: not in use.
+  int* chg;            // [max_iter + 1][B]
+  int* chg_n;          // [max_iter + 1]
+  int* chg_r;          // [B]
+  int* chg_rn;         // [max_iter + 2]
+  int* chg_an;         // [max_iter + 2]
 };
 
 // kernel variants (ILQR_DYN / ILQR_ROLLOUT / ILQR_LS / ILQR_BACKWARD / ILQR_LINT): read from the environment ONCE per handle

@@ -731,12 +731,12 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
   const int early_exit = ee_flags & 1, dedup = (ee_flags >> 1) & 1;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * CTRL_WAVES + wv;
-  __shared__ int s_accept[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[3];
+  __shared__ int s_accept[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[3], s_chg[CTRL_WAVES], s_cbase[2];
   const int N = S.N;
   bool run = b < S.B;
   if (run && phase == 0 && !S.active[b]) run = false;
   if (run && phase == 1 && !(S.active[b] && S.need_retry[b])) run = false;
-  if (lane == 0) { s_accept[wv] = -1; s_slot[wv] = -1; }
+  if (lane == 0) { s_accept[wv] = -1; s_slot[wv] = -1; s_chg[wv] = 0; }
   // sum_knots: the candidates' costs arrive as per-knot costs (k_traj_knot_cost); lane a adds candidate a's in knot order -- the
   // order of a sequential accumulation along the rollout, as k_traj_cost_sum does (one launch and one launch gap less per pass)
   double csum = 0.0;
@@ -801,6 +801,9 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
         if (phase == 0) { S.grp_a[b] = (!S.need_retry[b] && S.active[b]) ? 1 : 0; S.grp_r[b] = 0; }
         else S.grp_r[b] = S.active[b] ? 1 : 0;
       }
+      // linearisation cache (DevState::chg): the accepted candidate is about to replace xbar / ubar -- this rollout's Jacobians and cost
+      // quadratics are stale in iteration iter + 1; every other rollout keeps its nominal trajectory and with it both
+      if (S.chg && acc >= 0 && S.active[b]) s_chg[wv] = 1;
     }
   }
   __syncthreads();
@@ -813,7 +816,19 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
       s_base[threadIdx.x] = cnt ? atomicAdd(&S.order_n[slot], cnt) : 0;
       if (threadIdx.x == 0 && phase == 1 && S.order_r) s_base[2] = cnt ? atomicAdd(&S.order_rn[iter + 1], cnt) : 0;
     }
+    if (threadIdx.x == 64 && S.chg) {      // (the second wave: beside the two atomics above)
+      int cnt = 0;
+      for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_chg[w];
+      s_cbase[0] = cnt ? atomicAdd(&S.chg_n[iter + 1], cnt) : 0;
+      s_cbase[1] = (cnt && phase == 1) ? atomicAdd(&S.chg_rn[iter + 1], cnt) : 0;
+    }
     __syncthreads();
+    if (lane == 0 && s_chg[wv]) {
+      int pos = s_cbase[0], posr = s_cbase[1];
+      for (int w = 0; w < wv; ++w) { pos += s_chg[w]; posr += s_chg[w]; }
+      S.chg[(size_t)(iter + 1) * S.B + pos] = b;
+      if (phase == 1) S.chg_r[posr] = b;
+    }
     if (lane == 0 && s_slot[wv] >= 0) {
       const int kind = s_slot[wv];
       int pos = s_base[kind], posr = s_base[2];
@@ -849,10 +864,10 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control_spec(DevState S, De
   if (gate && *gate == 0) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * CTRL_WAVES + wv;
-  __shared__ int s_accept[CTRL_WAVES], s_retry[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[1];
+  __shared__ int s_accept[CTRL_WAVES], s_retry[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[1], s_chg[CTRL_WAVES], s_cbase[1];
   const int N = S.N;
   const bool run = b < S.B && S.active[b];
-  if (lane == 0) { s_accept[wv] = -1; s_retry[wv] = 0; s_slot[wv] = -1; }
+  if (lane == 0) { s_accept[wv] = -1; s_retry[wv] = 0; s_slot[wv] = -1; s_chg[wv] = 0; }
   // lanes 0..7: candidates of the first search, lanes 8..15: of the twin
   double csum = 0.0;
   if (run && lane < 16) {
@@ -904,6 +919,7 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control_spec(DevState S, De
       if (early_exit && iter > 1) S.active[b] = 0;
     }
     if (S.order && S.active[b]) s_slot[wv] = 0;
+    if (S.chg && acc >= 0 && S.active[b]) s_chg[wv] = 1;      // linearisation cache, as in k_control
   }
   __syncthreads();
   if (S.order) {
@@ -912,7 +928,17 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control_spec(DevState S, De
       for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_slot[w] == 0;
       s_base[0] = cnt ? atomicAdd(&S.order_n[2 * (iter + 1)], cnt) : 0;
     }
+    if (threadIdx.x == 64 && S.chg) {
+      int cnt = 0;
+      for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_chg[w];
+      s_cbase[0] = cnt ? atomicAdd(&S.chg_n[iter + 1], cnt) : 0;
+    }
     __syncthreads();
+    if (lane == 0 && s_chg[wv]) {
+      int pos = s_cbase[0];
+      for (int w = 0; w < wv; ++w) pos += s_chg[w];
+      S.chg[(size_t)(iter + 1) * S.B + pos] = b;
+    }
     if (lane == 0 && s_slot[wv] == 0) {
       int pos = s_base[0];
       for (int w = 0; w < wv; ++w) pos += s_slot[w] == 0;
@@ -962,6 +988,7 @@ __global__ void k_solve_begin(DevState S) {
     S.grp_a[b] = 0; S.grp_r[b] = 0;
     if (b == 0) for (int i = 0; i < S.max_iter + 2; ++i) { S.order_rn[i] = 0; S.order_an[i] = 0; }
   }
+  if (S.chg && b == 0) for (int i = 0; i < S.max_iter + 2; ++i) { if (i <= S.max_iter) S.chg_n[i] = 0; S.chg_rn[i] = 0; S.chg_an[i] = 0; }      // (iteration 0 linearises every rollout: no list survives a solve)
   const double J0 = S.Jbase[b];
   S.J[b] = J0;
   for (int i = 0; i <= S.max_iter; ++i) S.trace_cost[(size_t)b * (S.max_iter + 1) + i] = (i == 0) ? J0 : __builtin_nan("");

@@ -43,6 +43,7 @@ EXPORTS = [
     "ilqr_hip_plant_set_history", "ilqr_hip_plant_get_history", "ilqr_hip_plant_get_state", "ilqr_hip_plant_get_control", "ilqr_hip_plant_get_stance",
     "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
+    "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts",
 ]
 
 
@@ -159,6 +160,20 @@ class BatchedILQR:
     def set_dedup_saturated_retry(self, on=True):
         """Skip lambda retries whose lambda is already saturated (bit-identical repeats of the pass that has just failed); off by default."""
         self._chk(self.L.ilqr_hip_set_dedup_saturated_retry(self.h, int(bool(on))))
+
+    def set_relinearize_unchanged(self, on=True):
+        """Re-linearise every rollout in every iteration (comparison, profiling); off by default: an iteration linearises only the rollouts
+        whose nominal trajectory the previous one changed (ilqr_hip_set_relinearize_unchanged)."""
+        self._chk(self.L.ilqr_hip_set_relinearize_unchanged(self.h, int(bool(on))))
+
+    def linearized_rollouts(self):
+        """Rollouts whose linearisation and cost quadratics ran, summed over the iterations of the last solve."""
+        fn = self.L.ilqr_hip_get_linearized_rollouts
+        fn.restype = C.c_longlong
+        n = int(fn(self.h))
+        if n < 0:
+            raise ILQRError("ilqr_hip_get_linearized_rollouts: %s" % self.L.ilqr_hip_last_error(self.h).decode())
+        return n
 
     def reload_environment(self):
         """Re-read the diagnostic environment switches (read once, at creation) for this handle."""
