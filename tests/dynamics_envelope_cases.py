@@ -2,7 +2,8 @@
 seeded STATES and CONTROLS at which every branch and factor of the analytic linearisation (h1_linearize_dev.h lin_prologue /
 lin_column, h1_linearize_contact_dev.h) and of the step carries weight.  NumPy and the CPU oracle only; no GPU.
 
-Sixteen states per group, physical gravity, h = 0.02; hinges strictly inside their ranges (the joint-limit rows have goldens of their own).
+Sixteen states per group, physical gravity, h = 0.02; hinges strictly inside their ranges (the joint-limit rows have goldens of their own, and
+contact_envelope_cases.py takes them and contact modes 3 / 4 off the standing pose).
 
   * wide():     hinges at 2 % .. 98 % of their ranges, base rotation vectors in +-3 rad (state 0: an angle of pi - 1e-3), all 25
                 velocities in +-5, controls in +-0.9 ctrlrange.
@@ -154,14 +155,15 @@ def mid():
     return x, u
 
 
-def contact_kept(mode, x, u):
+def contact_kept(mode, x, u, o=None, rows=STANCE_ROWS):
     """kept [16,4] (bool; column p = STANCE_ROWS[p]): the oracle's contact-mode step is continuous at the state -- its result at the
     state and at the state with its velocities scaled by (1 +- 1e-7) differ by less than 1e-4 -- so no active-set decision of the
-    unilateral rule sits on a rounding tie that the device may settle the other way."""
-    o = oracle(mode=mode)
-    kept = np.zeros((len(x), 4), dtype=bool)
+    unilateral rule sits on a rounding tie that the device may settle the other way.  `o`: an oracle with further settings (friction,
+    joint-limit rows) in place of the plain one of `mode`; `rows`: the stance patterns, one column of `kept` each."""
+    o = o or oracle(mode=mode)
+    kept = np.zeros((len(x), len(rows)), dtype=bool)
     for i, (xi, ui) in enumerate(zip(x, u)):
-        for p, st in enumerate(STANCE_ROWS):
+        for p, st in enumerate(rows):
             f0 = o.step_stance(xi, ui, st)
             ok = True
             for sgn in (1.0, -1.0):
