@@ -564,51 +564,18 @@ __global__ void __launch_bounds__(256) k_fd_finish(DevState S, int mode, double 
 static inline int cdiv_s(long a, long b) { return (int)((a + b - 1) / b); }
 int dyn_split_kernels_set_attr() {
   int rc = 0;
-  const int lds = (int)DYN_LDS_BYTES_S;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<5, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_line_search_s<5, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_rollout_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_rollout_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_rollout_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_rollout_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_rollout_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_rollout_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_step_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_step_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_step_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_step_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_step_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_step_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_last_step_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_last_step_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_last_step_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_last_step_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_last_step_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_last_step_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_warm_tail_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_fd_steps_s<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_lin_primal_s<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DYN_LDS_BYTES_S + DUMP_STG_BYTES)) != hipSuccess;
-  rc |= hipFuncSetAttribute((const void*)k_lin_primal_s<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DYN_LDS_BYTES_S + DUMP_STG_BYTES)) != hipSuccess;
+  const auto attr = [&rc](const void* kernel, size_t lds) { rc |= hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess; };
+  for_each_step_kind([&](auto K) {
+    attr((const void*)k_line_search_s<K(), 4>, DYN_LDS_BYTES_S);
+    attr((const void*)k_line_search_s<K(), 1>, DYN_LDS_BYTES_S);
+    attr((const void*)k_rollout_s<K()>, DYN_LDS_BYTES_S);
+    attr((const void*)k_step_s<K()>, DYN_LDS_BYTES_S);
+    attr((const void*)k_last_step_s<K()>, DYN_LDS_BYTES_S);
+    attr((const void*)k_warm_tail_s<K()>, DYN_LDS_BYTES_S);
+    attr((const void*)k_fd_steps_s<K()>, DYN_LDS_BYTES_S);
+  });
+  attr((const void*)k_lin_primal_s<false>, DYN_LDS_BYTES_S + DUMP_STG_BYTES);
+  attr((const void*)k_lin_primal_s<true>, DYN_LDS_BYTES_S + DUMP_STG_BYTES);
   return rc;
 }
 #ifndef LS_RPW1_MAX_BATCH
@@ -619,24 +586,10 @@ void launch_line_search_s(const DevState& S, const ProblemDev& P, int mode, hipS
   // host knows an upper bound of the compacted list's length (the selected rollouts are its first entries: blocks past the
   // list's true count leave at once); the results do not depend on the choice
   const int nsel = (list && max_rollouts >= 0 && max_rollouts < S.B) ? max_rollouts : S.B;
-  const int ck = step_kind(P.dyn);      // the CONTACT value of step_any
-  if (nsel <= LS_RPW1_MAX_BATCH) {
-    const int blocks = nsel > 0 ? nsel : 1;
-    if (ck == 5) hipLaunchKernelGGL((k_line_search_s<5, 1>), dim3(blocks), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-    else if (ck == 4) hipLaunchKernelGGL((k_line_search_s<4, 1>), dim3(blocks), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-    else if (ck == 3) hipLaunchKernelGGL((k_line_search_s<3, 1>), dim3(blocks), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-    else if (ck == 2) hipLaunchKernelGGL((k_line_search_s<2, 1>), dim3(blocks), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-    else if (ck == 1) hipLaunchKernelGGL((k_line_search_s<1, 1>), dim3(blocks), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-    else hipLaunchKernelGGL((k_line_search_s<0, 1>), dim3(blocks), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-    return;
-  }
-  const dim3 grid(cdiv_s((long)S.B * 16, 64));
-  if (ck == 5) hipLaunchKernelGGL((k_line_search_s<5, 4>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-  else if (ck == 4) hipLaunchKernelGGL((k_line_search_s<4, 4>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-  else if (ck == 3) hipLaunchKernelGGL((k_line_search_s<3, 4>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-  else if (ck == 2) hipLaunchKernelGGL((k_line_search_s<2, 4>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-  else if (ck == 1) hipLaunchKernelGGL((k_line_search_s<1, 4>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
-  else hipLaunchKernelGGL((k_line_search_s<0, 4>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
+  with_step_kind(P.dyn, [&](auto K) {
+    if (nsel <= LS_RPW1_MAX_BATCH) hipLaunchKernelGGL((k_line_search_s<K(), 1>), dim3(nsel > 0 ? nsel : 1), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
+    else hipLaunchKernelGGL((k_line_search_s<K(), 4>), dim3(cdiv_s((long)S.B * 16, 64)), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
+  });
 }
 void launch_lin_primal_s(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, const int* list, const int* count) {
   // up to one wave per SIMD (32 knots per wave): the lanes store their blocks themselves, without the staging area (and its LDS: four waves per CU)
@@ -647,62 +600,28 @@ void launch_lin_primal_s(const DevState& S, const ProblemDev& P, int mode, hipSt
 }
 void launch_step_s(int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out) {
   const dim3 grid(cdiv_s((long)count * 2, 64));
-  switch (step_kind(dyn)) {
-    case 5: hipLaunchKernelGGL(k_step_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
-    case 4: hipLaunchKernelGGL(k_step_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
-    case 3: hipLaunchKernelGGL(k_step_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
-    case 2: hipLaunchKernelGGL(k_step_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
-    case 1: hipLaunchKernelGGL(k_step_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); break;
-    default: hipLaunchKernelGGL(k_step_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out);
-  }
+  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_s<K()>), grid, dim3(64), DYN_LDS_BYTES_S, st, count, x, u, dyn, xn, stance_l, stance_r, geom, st_out); });
 }
 void launch_stance_geom_s(const DevState& S, int mode, const int* list, const int* count, int* out, hipStream_t st) {
   hipLaunchKernelGGL(k_stance_geom_s, dim3(cdiv_s((long)S.B * S.N * 2, 64)), dim3(64), 0, st, S, mode, list, count, out);
 }
 void launch_last_step_s(const DevState& S, const ProblemDev& P, hipStream_t st) {
   const dim3 grid(cdiv_s((long)S.B * 2, 64));
-  switch (step_kind(P.dyn)) {
-    case 5: hipLaunchKernelGGL(k_last_step_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
-    case 4: hipLaunchKernelGGL(k_last_step_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
-    case 3: hipLaunchKernelGGL(k_last_step_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
-    case 2: hipLaunchKernelGGL(k_last_step_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
-    case 1: hipLaunchKernelGGL(k_last_step_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); break;
-    default: hipLaunchKernelGGL(k_last_step_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P);
-  }
+  with_step_kind(P.dyn, [&](auto K) { hipLaunchKernelGGL((k_last_step_s<K()>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P); });
 }
 void launch_warm_tail_s(const DevState& S, const ProblemDev& P, int shift, hipStream_t st) {
   const dim3 grid(cdiv_s((long)S.B * 2, 64));
-  switch (step_kind(P.dyn)) {
-    case 5: hipLaunchKernelGGL(k_warm_tail_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
-    case 4: hipLaunchKernelGGL(k_warm_tail_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
-    case 3: hipLaunchKernelGGL(k_warm_tail_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
-    case 2: hipLaunchKernelGGL(k_warm_tail_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
-    case 1: hipLaunchKernelGGL(k_warm_tail_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); break;
-    default: hipLaunchKernelGGL(k_warm_tail_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift);
-  }
+  with_step_kind(P.dyn, [&](auto K) { hipLaunchKernelGGL((k_warm_tail_s<K()>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, shift); });
 }
 void launch_linearize_fd_s(const DevState& S, const ProblemDev& P, int mode, double eps, hipStream_t st) {
   const int dd = (int)lin_dump_doubles();
   const dim3 grid(cdiv_s((long)S.B * S.N * FD_NCOL * 2, 64));
-  switch (step_kind(P.dyn)) {
-    case 5: hipLaunchKernelGGL(k_fd_steps_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd); break;
-    case 4: hipLaunchKernelGGL(k_fd_steps_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd); break;
-    case 3: hipLaunchKernelGGL(k_fd_steps_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd); break;
-    case 2: hipLaunchKernelGGL(k_fd_steps_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd); break;
-    case 1: hipLaunchKernelGGL(k_fd_steps_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd); break;
-    default: hipLaunchKernelGGL(k_fd_steps_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd);
-  }
+  with_step_kind(P.dyn, [&](auto K) { hipLaunchKernelGGL((k_fd_steps_s<K()>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, eps, dd); });
   hipLaunchKernelGGL(k_fd_finish, dim3(cdiv_s((long)S.B * S.N * H1_NX * (H1_NX + H1_NU), 256)), dim3(256), 0, st, S, mode, eps, dd);
 }
 void launch_rollout_s(const DevState& S, const ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st) {
   const dim3 grid(cdiv_s((long)S.B * 2, 64));
-  const int ck = step_kind(P.dyn);
-  if (do_roll && ck == 5) hipLaunchKernelGGL(k_rollout_s<5>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter);
-  else if (do_roll && ck == 4) hipLaunchKernelGGL(k_rollout_s<4>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter);
-  else if (do_roll && ck == 3) hipLaunchKernelGGL(k_rollout_s<3>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter);
-  else if (do_roll && ck == 2) hipLaunchKernelGGL(k_rollout_s<2>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter);
-  else if (do_roll && ck == 1) hipLaunchKernelGGL(k_rollout_s<1>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter);
-  else if (do_roll) hipLaunchKernelGGL(k_rollout_s<0>, grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter);
+  if (do_roll) with_step_kind(P.dyn, [&](auto K) { hipLaunchKernelGGL((k_rollout_s<K()>), grid, dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, count_iter); });
   else if (count_iter) hipLaunchKernelGGL(k_count_iter, dim3(cdiv_s(S.B, 64)), dim3(64), 0, st, S, mode);
   launch_nominal_costs(S, P, mode, cost_out, st);
 }

@@ -231,6 +231,22 @@ DEVFN void load_half_u(bool side, const double* u, h1s::HalfU& o) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) o.uA[k] = u[h1s::jarm(side, k)];
 }
-// CONTACT / CK of the kernels: 0 constraint-free; 1 / 2 stance rows (2: kinetic friction, mode 4); 3 / 4 the same with joint-limit rows;
-// 5 joint-limit rows on the constraint-free plant
-static inline int step_kind(const DynParams& d) { return !constrained(d) ? 0 : (d.contact == 0 ? 5 : (d.contact == 4 ? 2 : 1) + (d.limits ? 2 : 0)); }
+// CONTACT / CK / KIND of the kernels: the StepKind of the dynamics parameters (launch_plan.h, where the six values have their names)
+static inline int step_kind(const DynParams& d) { return step_kind_of(d.contact, d.limits); }
+// f(std::integral_constant<int, K>{}) for K = step_kind(d): the ONE place that turns the run-time kind into a template argument; a launcher
+// names its kernel as k<K()> inside a generic lambda
+template <class F> static inline void with_step_kind(const DynParams& d, F&& f) {
+  switch (step_kind(d)) {
+    case STEP_LIMITS: f(std::integral_constant<int, STEP_LIMITS>{}); break;
+    case STEP_KINETIC_LIMITS: f(std::integral_constant<int, STEP_KINETIC_LIMITS>{}); break;
+    case STEP_STANCE_LIMITS: f(std::integral_constant<int, STEP_STANCE_LIMITS>{}); break;
+    case STEP_KINETIC: f(std::integral_constant<int, STEP_KINETIC>{}); break;
+    case STEP_STANCE: f(std::integral_constant<int, STEP_STANCE>{}); break;
+    default: f(std::integral_constant<int, STEP_FREE>{});
+  }
+}
+// f with every kind: the attribute lists (a kernel of the family that is launched by kind is listed here once, for all six)
+template <class F> static inline void for_each_step_kind(F&& f) {
+  f(std::integral_constant<int, STEP_FREE>{}); f(std::integral_constant<int, STEP_STANCE>{}); f(std::integral_constant<int, STEP_KINETIC>{});
+  f(std::integral_constant<int, STEP_STANCE_LIMITS>{}); f(std::integral_constant<int, STEP_KINETIC_LIMITS>{}); f(std::integral_constant<int, STEP_LIMITS>{});
+}

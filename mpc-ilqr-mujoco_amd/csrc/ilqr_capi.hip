@@ -180,8 +180,16 @@ struct StageTimer {
   ~StageTimer() { if (a && b) { hipEventRecord(b, st); c->spans.push_back({stage, a, b}); } }
 };
 
+#ifdef ILQR_LEGACY_KERNELS
+static constexpr bool LEGACY_BUILD = true;
+#else
+static constexpr bool LEGACY_BUILD = false;
+#endif
+// Which kernel runs each stage of this handle and what that family can do (launch_plan.h): resolved from the handle's state whenever an
+// entry point needs it, behind its prologue -- never stored, so no setter has anything to invalidate.
+static ilqr::LaunchPlan plan_of(const ilqr_hip_ctx* c) { return ilqr::resolve_plan(c->knobs.var, c->P.dyn.contact, c->P.dyn.limits, c->jac_mode); }
 // Prologue of every entry point that touches the device, called after its argument checks.  The kernel family is c->knobs.var and
-// nothing else: whatever depends on it takes an ilqr::Variants argument.  An entry point uses enter_launching if it calls, directly or
+// nothing else: whatever depends on it takes an ilqr::LaunchPlan argument.  An entry point uses enter_launching if it calls, directly or
 // through a static helper, a function that takes one; so does ilqr_hip_plant_advance, whose kernel exists in one family only (the
 // two-lane step, whatever the handle's family: on a scalar-dynamics handle of the test library the plant and ilqr_hip_step therefore run
 // different kernels) -- it steps the model, and a handle whose environment names an absent family has no model to speak of.  Every other
@@ -192,14 +200,13 @@ static inline void enter(ilqr_hip_ctx* c) {
     // an unsupported selection keeps the previous one AND is recorded: the calls that launch family-dependent kernels refuse until the
     // environment selects a family this library holds again -- a test that switches families on a product handle must not pass vacuously
     const Knobs k = read_knobs();
-    if (ilqr::variants_supported(k.var)) { c->knobs = k; c->env_refused = false; }
+    if (ilqr::plan_supported(k.var, LEGACY_BUILD)) { c->knobs = k; c->env_refused = false; }
     else { c->env_refused = true; c->err = "ILQR_ENV_PER_CALL: the environment selects a kernel family this library does not hold (see ilqr_hip_create)"; }
   }
 }
 // weight sets exist in the cost kernels of the default family; a family whose rollout / line-search kernels evaluate the cost themselves reads the shared values
 static const char* weight_sets_refusal(const ilqr_hip_ctx* c) {
-  const ilqr::Variants& V = c->knobs.var;
-  if (V.scalar_dyn || !V.rollout_split || !V.ls_split) return "weight sets exist in the default family's cost kernels only; unset ILQR_DYN=s / ILQR_ROLLOUT=r / ILQR_LS=r";
+  if (!plan_of(c).weight_sets) return "weight sets exist in the default family's cost kernels only; unset ILQR_DYN=s / ILQR_ROLLOUT=r / ILQR_LS=r";
   return nullptr;
 }
 static inline int enter_launching(ilqr_hip_ctx* c) {
@@ -218,7 +225,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return ILQR_ERR_NO_DEVICE;
   ilqr_hip_ctx* c = new ilqr_hip_ctx();
   c->device = device; c->B = batch; c->N = horizon;
-  if (!ilqr::variants_supported(c->knobs.var)) {
+  if (!ilqr::plan_supported(c->knobs.var, LEGACY_BUILD)) {
     // (the handle is returned so that ilqr_hip_last_error can say why; the caller destroys it)
     c->err = "the environment selects a cross-check kernel family (ILQR_BACKWARD / ILQR_LS / ILQR_ROLLOUT / ILQR_DYN / ILQR_LINT) that this library does not hold: "
              "they are compiled into the test library only (make ../lib/libilqr_hip_legacy.so, -DILQR_LEGACY_KERNELS)";
@@ -436,13 +443,9 @@ int ilqr_hip_set_options(ilqr_hip_ctx* c, int jacobian_mode, double fd_eps, int 
 int ilqr_hip_set_early_exit_gate(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->ee_gate = on ? 1 : 0; return ILQR_OK; }
 
 // ---------------------------------------------------------------- initializeWithReference
-// Which kernel rolls a trajectory out under these switches: the scalar kernels (ILQR_DYN=s), the two-lane kernels (ILQR_ROLLOUT=s,
-// and always in contact mode) or the one-lane ones.  Iteration 0 of a solve may re-roll a cold start BESIDE the linearisation only
-// if it is this very kernel under these very dynamics parameters (bit-identical result); compared field by field, not by memcmp
-// (padding bytes).
-static int rollout_kernel_identity(const ilqr::Variants& V, const h1::ProblemDev& P) {
-  return V.scalar_dyn ? 2 : ((V.rollout_split || h1::constrained(P.dyn)) ? 1 : 0);
-}
+// Iteration 0 of a solve may re-roll a cold start BESIDE the linearisation only if it is the very kernel that rolled it out
+// (LaunchPlan::rollout, kept in rolled_variant) under these very dynamics parameters (bit-identical result); compared field by field,
+// not by memcmp (padding bytes).
 static bool same_dyn(const h1::DynParams& a, const h1::DynParams& b) {
   return a.h == b.h && a.g[0] == b.g[0] && a.g[1] == b.g[1] && a.g[2] == b.g[2] && a.contact == b.contact && a.soft == b.soft && a.mu == b.mu && a.limits == b.limits && a.lim_k == b.lim_k;
 }
@@ -450,11 +453,12 @@ static int cold_start_device(ilqr_hip_ctx* c, const double* x0_dev, const double
   const size_t B = c->B, N = c->N;
   HIPCHK(c, hipMemcpyAsync(c->S.x0, x0_dev, B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->S.ubar, uinit_dev, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream);  // N rollouts (ilqr.cpp:113-115)
+  const ilqr::LaunchPlan L = plan_of(c);
+  ilqr::launch_rollout(L, c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream);  // N rollouts (ilqr.cpp:113-115)
   HIPCHK(c, hipGetLastError());
   c->initialized = true;
   c->xbar_rolled = true;
-  c->rolled_variant = rollout_kernel_identity(c->knobs.var, c->P); c->rolled_dyn = c->P.dyn;
+  c->rolled_variant = L.rollout; c->rolled_dyn = c->P.dyn;
   return ILQR_OK;
 }
 int ilqr_hip_initialize_device(ilqr_hip_ctx* c, const double* x0_device, const double* u_init_device) {
@@ -471,7 +475,7 @@ int ilqr_hip_initialize(ilqr_hip_ctx* c, const double* x0, const double* u_init,
     HIPCHK(c, hipMemcpyAsync(c->d_prevx, prev_xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_prevu, prev_ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
     ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);
-    ilqr::launch_last_step(c->knobs.var, c->S, c->P, c->stream);
+    ilqr::launch_last_step(plan_of(c), c->S, c->P, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->initialized = true;
@@ -503,7 +507,7 @@ int ilqr_hip_initialize_warm_resident(ilqr_hip_ctx* c, const double* x0) {
   HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);
-  ilqr::launch_last_step(c->knobs.var, c->S, c->P, c->stream);
+  ilqr::launch_last_step(plan_of(c), c->S, c->P, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->xbar_rolled = false;
@@ -515,7 +519,7 @@ static int warm_shifted(ilqr_hip_ctx* c, int shift) {
   HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift_m(c->S, c->d_prevx, c->d_prevu, shift, c->stream);
-  ilqr::launch_warm_tail(c->S, c->P, shift, c->stream);
+  ilqr::launch_warm_tail(plan_of(c), c->S, c->P, shift, c->stream);
   HIPCHK(c, hipGetLastError());
   c->xbar_rolled = false;
   return ILQR_OK;
@@ -554,7 +558,7 @@ static DevState slice_state(const DevState& S, size_t b0, int Bs) {
   T.A += b0 * N * n * n; T.Bm += b0 * N * n * m;
   T.lx += b0 * (N + 1) * n; T.lu += b0 * N * m; T.lxx += b0 * (N + 1) * n * n; T.luu += b0 * N * m;
   T.K += b0 * N * m * n; T.kff += b0 * N * m; T.lin_dump += b0 * N * ilqr::lin_dump_doubles();
-  T.quad_knot0 = S.quad_knot0 + (long)(b0 * (N + 1));      // (the record buffer is indexed by knot, 16 to a line: not a pointer offset)
+  T.quad_knot0 = S.quad_knot0 + (long)(b0 * (N + 1));      // (the record buffer is indexed by knot, four to a line: not a pointer offset)
   T.Vx += b0 * n; T.Vxx += b0 * n * n;
   T.J += b0; T.Jbase += b0; T.ls_cost += b0; T.lambda += b0;
   T.active += b0; T.need_retry += b0; T.iters += b0; T.improved += b0; T.alpha_idx += b0;
@@ -648,9 +652,11 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // shadow target of the concurrent re-rollout: same rollouts as S.xbar, in the shadow buffer
   double* shadow = const_cast<double*>(shadow_base) + (S.xbar - c->S.xbar);
   int* stance_dyn = c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N;     // (same rollouts as S)
-  const ilqr::Variants& V = c->knobs.var;      // (the per-call re-read happened in the caller's prologue: V cannot change under a solve)
-  const double fold_h = ilqr::linearize_fold_h(V, P, c->jac_mode);
-  { StageTimer T(c, 0, st); ilqr::launch_rollout(V, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st); ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
+  const ilqr::LaunchPlan L = plan_of(c);      // (the per-call re-read happened in the caller's prologue: the plan cannot change under a solve)
+  // step size h while launch_linearize writes Jacobians whose hinge-position rows are exactly e_k + h * the hinge-velocity rows (the
+  // analytic tangent kernels, lin_column) and the backward kernel uses that (riccati_wave.hip fold_rows); else 0
+  const double fold_h = L.folds_h ? P.dyn.h : 0.0;
+  { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st); ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
   // With the convergence exit on, the launches of an iteration nobody needs are pure latency (17 launches that find nothing to
   // do): the count of rollouts active after iteration i (DevState::order_n, maintained by k_control) follows iteration i to the
   // host, which enqueues iteration i only after it has seen the count left by iteration i - 2 -- one full iteration stays
@@ -661,8 +667,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   const bool xbar_rolled = c->first_aside;
   // the operand-layout Riccati kernel (analytic Jacobians, riccati_pack.hip) has its producers write A_t, B_t and lxx~_t in its own
   // layout; the generic one-wave kernel reads only the tiles I >= J of lxx_t (t < N): the cost quadratics then leave the others unwritten
-  const int pack = (fold_h != 0.0 && V.pack()) ? 1 : 0;
-  const int lxx_lower = pack ? 2 : (V.backward == 2 ? 1 : 0);
+  const int pack = L.pack ? 1 : 0;
+  const int lxx_lower = L.lxx_layout;
   // (iteration 0 rewrites A_t, B_t, lxx_t of every rollout: a solve leaves one layout behind; ilqr_hip_solve_async has prepared the padding)
   c->lxx_layout = lxx_lower;
   c->ab_packed = pack != 0;
@@ -694,8 +700,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // the in-place layout conversions belong to the getters and the stage API, outside a solve.  Iteration 0 takes every rollout.  Not for
   // the forward-difference kernels (they select by S.active and use S.A / S.Bm as scratch) nor for batch slices (no lists);
   // ilqr_hip_set_relinearize_unchanged / ILQR_RELIN=1: the full pass in every iteration.
-  const bool analytic_lists = c->jac_mode == ILQR_JAC_ANALYTIC && (!V.scalar_dyn || !P.dyn.contact);
-  const bool cache = !(c->knobs.relin >= 0 ? c->knobs.relin : c->relin) && S.order && S.chg && analytic_lists;
+  const bool cache = !(c->knobs.relin >= 0 ? c->knobs.relin : c->relin) && S.order && S.chg && L.lin_lists;
   c->lin_cached = cache; c->lin_listed = sel_mode != ilqr::MASK_ALL && S.order != nullptr;
   struct Rg { hipStream_t m, q, r; hipEvent_t fork, join, roll, lin, adopt; };
   const Rg G0{st, st2, st3, ev_fork, ev_join, ev_roll, ev_lin, ev_adopt};
@@ -710,12 +715,12 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     if (concurrent_roll) {
       HIPCHK(c, hipStreamWaitEvent(G.r, G.fork, 0));
       DevState Sr = Sm; Sr.xbar = shadow;
-      { StageTimer T(c, 0, G.r); ilqr::launch_rollout(V, Sr, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, G.r); }
+      { StageTimer T(c, 0, G.r); ilqr::launch_rollout(L, Sr, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, G.r); }
       HIPCHK(c, hipEventRecord(G.roll, G.r));
     }
     { StageTimer T(c, 2, G.q); ilqr::launch_cost_quadratics(S, P, knot_mode, G.q, iter_l, lxx_lower, wl); }
     HIPCHK(c, hipEventRecord(G.join, G.q));
-    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(V, S, P, knot_mode, c->jac_mode, c->fd_eps, G.m, 3, iter_l, pack, wl, stance_dyn); }
+    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(L, S, P, knot_mode, c->fd_eps, G.m, 3, iter_l, pack, wl, stance_dyn); }
     if (concurrent_roll && G.lin && G.adopt) {
       HIPCHK(c, hipEventRecord(G.lin, G.m));
       HIPCHK(c, hipStreamWaitEvent(G.r, G.lin, 0)); HIPCHK(c, hipStreamWaitEvent(G.r, G.join, 0));
@@ -725,8 +730,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     return ILQR_OK;
   };
   auto rolls_aside = [&](int iter) {
-    const bool first_aside = iter == 0 && xbar_rolled && !V.scalar_dyn;
-    return (iter > 0 || first_aside) && !c->knobs.reuse_rollout && c->knobs.overlap_rollout && (h1::constrained(P.dyn) || V.ls_split == V.rollout_split);   // (contact mode: both on the two-lane kernels)
+    return (iter > 0 ? L.reroll_aside : (xbar_rolled && L.cold_start_aside)) && !c->knobs.reuse_rollout && c->knobs.overlap_rollout;
   };
   // Early continuation: the rollouts whose first line search of iteration i accepted a step are done with iteration i; their share of
   // iteration i + 1's concurrent region (group A) starts right behind the first control pass, on streams of its own, while the
@@ -745,7 +749,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     }
     const bool concurrent_roll = rolls_aside(iter);
     if (!prev_split) {
-      if ((iter == 0 || !c->knobs.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(V, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
+      if ((iter == 0 || !c->knobs.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
       if (iter == 0 && wait_lead) HIPCHK(c, hipStreamWaitEvent(st, wait_lead, 0));
       const ilqr::WorkList wc{S.chg + (size_t)iter * S.B, S.chg_n + iter};
       TRY(region(G0, st, S, sel_mode, iter, (cache && iter > 0) ? &wc : nullptr, concurrent_roll));
@@ -775,15 +779,15 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
       HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
       ilqr::launch_spec_lambda(S, Tw.lambda, st2);
-      { StageTimer T(c, 3, st); ilqr::launch_backward(V, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward(V, Tw, ilqr::MASK_ACTIVE, st2, fold_h, iter); }
+      { StageTimer T(c, 3, st); ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
+      { StageTimer T(c, 6, st2); ilqr::launch_backward(L, Tw, ilqr::MASK_ACTIVE, st2, fold_h, iter); }
       TRY(wait_adoption(st)); TRY(wait_adoption(st2));
       if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-      { StageTimer T(c, 4, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
-      { StageTimer T(c, 7, st2); ilqr::launch_line_search(V, Tw, P, ilqr::MASK_ACTIVE, st2, iter, ls_bound); }
+      { StageTimer T(c, 4, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
+      { StageTimer T(c, 7, st2); ilqr::launch_line_search(L, Tw, P, ilqr::MASK_ACTIVE, st2, iter, ls_bound); }
       HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
       HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
-      { StageTimer T(c, 5, st); ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P)); }
+      { StageTimer T(c, 5, st); ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }
       if (gate) {
         HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
@@ -791,7 +795,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       prev_split = false;
       continue;
     }
-    if (c->twin && c->knobs.spec && c->knobs.spec_dual && S.order && gate && pass_bound <= 4 * c->knobs.spec_max && ilqr::spec_dual_available(V, P)) {
+    if (c->twin && c->knobs.spec && c->knobs.spec_dual && S.order && gate && pass_bound <= 4 * c->knobs.spec_max && L.spec_dual) {
       // The host's count is one iteration old: between spec_max and 4 spec_max the pass may or may not have shrunk below the
       // threshold by now.  Both orders are enqueued and the device takes one (launch_spec_gate): the twin's launches and the
       // one-rollout-per-wave line search see a count of zero unless the list holds <= spec_max rollouts, the sequential first line
@@ -804,8 +808,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
       HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
       ilqr::launch_spec_lambda(S, Tw.lambda, st2);
-      { StageTimer T(c, 3, st); ilqr::launch_backward(V, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(V, Tw, st2, fold_h, list, g); }
+      { StageTimer T(c, 3, st); ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
+      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(L, Tw, st2, fold_h, list, g); }
       TRY(wait_adoption(st)); TRY(wait_adoption(st2));
       { StageTimer T(c, 4, st);
         ilqr::launch_line_search_list(S, P, st, list, g, c->knobs.spec_max);
@@ -815,21 +819,21 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
       HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
       { StageTimer T(c, 5, st);
-        ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P), g);
-        ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, ilqr::ls_costs_per_knot(V, P), g + 1); }
-      { StageTimer T(c, 6, st); ilqr::launch_backward(V, S, ilqr::MASK_RETRY, st, fold_h, iter); }
-      { StageTimer T(c, 7, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
-      { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P)); }
+        ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot, g);
+        ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot, g + 1); }
+      { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, fold_h, iter); }
+      { StageTimer T(c, 7, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
+      { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
       prev_split = false;
       continue;
     }
-    { StageTimer T(c, 3, st); ilqr::launch_backward(V, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }                                  // :601
+    { StageTimer T(c, 3, st); ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }                                  // :601
     TRY(wait_adoption(st));
     if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-    { StageTimer T(c, 4, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }                  // :616
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, ilqr::ls_costs_per_knot(V, P)); }          // :619-620,645-655
+    { StageTimer T(c, 4, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }                  // :616
+    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot); }          // :619-620,645-655
     const bool split_next = can_split && iter + 1 < c->max_iter && rolls_aside(iter + 1);
     if (split_next) {
       // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
@@ -839,9 +843,9 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       const ilqr::WorkList wa = cache ? ilqr::WorkList{S.chg + (size_t)(iter + 1) * S.B, S.chg_an + iter + 1} : ilqr::WorkList{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
       TRY(region(GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
     }
-    { StageTimer T(c, 6, st); ilqr::launch_backward(V, S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
-    { StageTimer T(c, 7, st); ilqr::launch_line_search(V, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }                   // :638
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, ilqr::ls_costs_per_knot(V, P)); }                      // :640-646
+    { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
+    { StageTimer T(c, 7, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }                   // :638
+    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }                      // :640-646
     if (gate) {
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
@@ -874,7 +878,7 @@ int ilqr_hip_set_dedup_saturated_retry(ilqr_hip_ctx* c, int on) { if (!c) return
 int ilqr_hip_reload_environment(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   const Knobs k = read_knobs();
-  if (!ilqr::variants_supported(k.var)) { c->err = "the environment selects a kernel family this library does not hold (see ilqr_hip_create)"; return ILQR_ERR_UNSUPPORTED; }
+  if (!ilqr::plan_supported(k.var, LEGACY_BUILD)) { c->err = "the environment selects a kernel family this library does not hold (see ilqr_hip_create)"; return ILQR_ERR_UNSUPPORTED; }
   const bool pc = c->knobs.per_call; c->knobs = k; c->knobs.per_call = k.per_call || pc;
   return ILQR_OK;
 }
@@ -884,7 +888,7 @@ int ilqr_hip_num_slices(const ilqr_hip_ctx* c) { return c ? slices_wanted(c, c->
 // solution) is carried by the two-knot tangent kernel only (k_lin_tangent2c<., 1 / 2>): the one-knot and scalar cross-check families
 // refuse it.
 static int jacobians_available(ilqr_hip_ctx* c) {
-  if (c->jac_mode != ILQR_JAC_ANALYTIC || !(c->knobs.var.lin_one_knot || c->knobs.var.scalar_dyn)) return ILQR_OK;
+  if (c->jac_mode != ILQR_JAC_ANALYTIC || plan_of(c).analytic_full) return ILQR_OK;
   if (c->P.dyn.limits) {
     c->err = "joint-limit rows (ilqr_hip_set_joint_limits): analytic Jacobians are not available in this kernel family (ILQR_LIN / ILQR_DYN), select ILQR_JAC_FD_FORWARD with ilqr_hip_set_options";
     return ILQR_ERR_UNSUPPORTED;
@@ -901,15 +905,15 @@ int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   TRY(enter_launching(c));
   TRY(jacobians_available(c));
   hipStream_t st = c->stream;
-  const DevState& S = c->S; const h1::ProblemDev& P = c->P; const ilqr::Variants& V = c->knobs.var;
+  const DevState& S = c->S; const h1::ProblemDev& P = c->P; const ilqr::LaunchPlan L = plan_of(c);
   c->spans.clear(); c->pool_next = 0;
   HIPCHK(c, hipMemsetAsync(c->d_mismatch, 0, sizeof(unsigned long long), st));
   const int k = slices_wanted(c, c->B);
   c->n_slices = k;
   c->spec_iterations = 0; c->split_iterations = 0;
   if (c->knobs.spec && k <= 1 && !c->twin && (c->B <= c->knobs.spec_max || (c->early_exit && early_exit_gate(c)))) TRY(ensure_twin(c));
-  if (ilqr::linearize_fold_h(V, P, c->jac_mode) != 0.0 && V.pack() && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
-  c->first_aside = c->xbar_rolled && c->rolled_variant == rollout_kernel_identity(V, P) && same_dyn(c->rolled_dyn, P.dyn);
+  if (L.pack && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
+  c->first_aside = c->xbar_rolled && c->rolled_variant == L.rollout && same_dyn(c->rolled_dyn, P.dyn);
   c->xbar_rolled = false;                                   // after this solve xbar is an accepted line-search candidate
   if (k <= 1) {
     TRY(enqueue_solve(c, S, P, st, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_roll, c->d_shadowx, nullptr, nullptr, c->ev_lin, c->ev_adopt));
@@ -1036,8 +1040,14 @@ int ilqr_hip_set_trajectory(ilqr_hip_ctx* c, const double* xbar, const double* u
 }
 #define STAGE_CHECK if (!c) return ILQR_ERR_ARG; if (!c->initialized) return ILQR_ERR_STATE
 #define STAGE_POST HIPCHK(c, hipGetLastError()); HIPCHK(c, hipStreamSynchronize(c->stream)); return ILQR_OK
-int ilqr_hip_stage_rollout(ilqr_hip_ctx* c) { STAGE_CHECK; TRY(enter_launching(c)); ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream); STAGE_POST; }
-int ilqr_hip_stage_linearize(ilqr_hip_ctx* c) { STAGE_CHECK; TRY(enter_launching(c)); TRY(jacobians_available(c)); ilqr::launch_linearize(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, c->jac_mode, c->fd_eps, c->stream, 3, -1, 0, nullptr, c->d_stance_dyn); c->lin_fold_h = ilqr::linearize_fold_h(c->knobs.var, c->P, c->jac_mode); c->ab_packed = false; c->ab_pads_clean = false; STAGE_POST; }
+int ilqr_hip_stage_rollout(ilqr_hip_ctx* c) { STAGE_CHECK; TRY(enter_launching(c)); ilqr::launch_rollout(plan_of(c), c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream); STAGE_POST; }
+int ilqr_hip_stage_linearize(ilqr_hip_ctx* c) {
+  STAGE_CHECK; TRY(enter_launching(c)); TRY(jacobians_available(c));
+  const ilqr::LaunchPlan L = plan_of(c);
+  ilqr::launch_linearize(L, c->S, c->P, ilqr::MASK_ALL, c->fd_eps, c->stream, 3, -1, 0, nullptr, c->d_stance_dyn);
+  c->lin_fold_h = L.folds_h ? c->P.dyn.h : 0.0; c->ab_packed = false; c->ab_pads_clean = false;
+  STAGE_POST;
+}
 int ilqr_hip_stage_cost_quadratics(ilqr_hip_ctx* c) { STAGE_CHECK; enter(c); if (!c->refs_set) return ILQR_ERR_STATE; ilqr::launch_cost_quadratics(c->S, c->P, ilqr::MASK_ALL, c->stream); c->lxx_layout = 0; STAGE_POST; }
 // layout conversions on demand (in place): what a consumer of the standard layout (getters, any kernel family but the operand-layout
 // one) or of the operand layout (stage API on riccati_pack.hip) calls first
@@ -1048,22 +1058,23 @@ static void want_standard_lxx(ilqr_hip_ctx* c, bool whole) {
 }
 int ilqr_hip_stage_backward_pass(ilqr_hip_ctx* c) {
   STAGE_CHECK; TRY(enter_launching(c));
-  const ilqr::Variants& V = c->knobs.var;
-  if (c->lin_fold_h != 0.0 && V.pack()) {
+  const ilqr::LaunchPlan L = plan_of(c);
+  const int layout = ilqr::lxx_layout_of(c->lin_fold_h != 0.0 ? L.backward_foldable : L.backward_plain);      // (of the kernel launch_backward picks)
+  if (layout == 2) {
     // analytic Jacobians and the operand-layout kernel (riccati_pack.hip): convert in place what is not yet in its layout
     if (!c->ab_packed) { ilqr::launch_pack_ab(c->S, c->stream); c->ab_packed = true; c->packed_h = c->lin_fold_h; c->ab_pads_clean = true; }
     if (c->lxx_layout != 2) { want_standard_lxx(c, true); ilqr::launch_pack_lxx(c->S, c->stream); c->lxx_layout = 2; }
   } else {
     // any other family reads the standard layout (the one-wave kernel: the tiles I >= J of lxx_t, t < N, suffice)
     want_standard_ab(c);
-    want_standard_lxx(c, V.backward != 2);
+    want_standard_lxx(c, layout == 0);
   }
-  ilqr::launch_backward(V, c->S, ilqr::MASK_ALL, c->stream, c->lin_fold_h);
+  ilqr::launch_backward(L, c->S, ilqr::MASK_ALL, c->stream, c->lin_fold_h);
   STAGE_POST;
 }
 int ilqr_hip_stage_total_cost(ilqr_hip_ctx* c, double* cost) {
   STAGE_CHECK; TRY(enter_launching(c)); if (!cost || !c->refs_set) return ILQR_ERR_ARG;
-  ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 0, 0, c->d_cost_tmp, c->stream);
+  ilqr::launch_rollout(plan_of(c), c->S, c->P, ilqr::MASK_ALL, 0, 0, c->d_cost_tmp, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(cost, c->d_cost_tmp, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1071,8 +1082,9 @@ int ilqr_hip_stage_total_cost(ilqr_hip_ctx* c, double* cost) {
 }
 int ilqr_hip_stage_line_search(ilqr_hip_ctx* c, int* improved, double* new_cost, double* alpha) {
   STAGE_CHECK; TRY(enter_launching(c)); if (!c->refs_set) return ILQR_ERR_STATE;
-  ilqr::launch_rollout(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, 0, 0, c->S.Jbase, c->stream);   // baseline = computeTotalCost(xbar, ubar), ilqr.cpp:317
-  ilqr::launch_line_search(c->knobs.var, c->S, c->P, ilqr::MASK_ALL, c->stream);
+  const ilqr::LaunchPlan L = plan_of(c);
+  ilqr::launch_rollout(L, c->S, c->P, ilqr::MASK_ALL, 0, 0, c->S.Jbase, c->stream);   // baseline = computeTotalCost(xbar, ubar), ilqr.cpp:317
+  ilqr::launch_line_search(L, c->S, c->P, ilqr::MASK_ALL, c->stream);
   ilqr::launch_control(c->S, 2, 0, c->tol, 0, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1147,7 +1159,7 @@ int ilqr_hip_step(ilqr_hip_ctx* c, int count, const double* x, const double* u, 
 int ilqr_hip_set_contact_mode(ilqr_hip_ctx* c, int mode, double softness) {
   if (!c || (mode != ILQR_CONTACT_NONE && mode != ILQR_CONTACT_RIGID_STANCE && mode != ILQR_CONTACT_UNILATERAL_STANCE && mode != ILQR_CONTACT_FRICTION_STANCE && mode != ILQR_CONTACT_KINETIC_FRICTION_STANCE)) return ILQR_ERR_ARG;
   enter(c);
-  if (mode >= ILQR_CONTACT_FRICTION_STANCE && c->knobs.var.scalar_dyn) { c->err = "contact modes 3 / 4 (Coulomb limit) exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+  if (mode >= ILQR_CONTACT_FRICTION_STANCE && !plan_of(c).cone_and_limits) { c->err = "contact modes 3 / 4 (Coulomb limit) exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
   if (mode == ILQR_CONTACT_RIGID_STANCE && c->P.stance_geom) { c->err = "contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4"; return ILQR_ERR_UNSUPPORTED; }
   c->P.dyn.contact = mode;
   if (softness > 0.0) c->P.dyn.soft = softness;
@@ -1156,7 +1168,7 @@ int ilqr_hip_set_contact_mode(ilqr_hip_ctx* c, int mode, double softness) {
 int ilqr_hip_set_joint_limits(ilqr_hip_ctx* c, int on) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (on && c->knobs.var.scalar_dyn) { c->err = "joint-limit rows exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
+  if (on && !plan_of(c).cone_and_limits) { c->err = "joint-limit rows exist on the two-lane kernels only; unset ILQR_DYN=s"; return ILQR_ERR_UNSUPPORTED; }
   c->P.dyn.limits = on ? 1 : 0;     // (a nominal rolled under the other setting is recognised by same_dyn)
   return ILQR_OK;
 }
@@ -1186,7 +1198,7 @@ static int plant_step(ilqr_hip_ctx* c, int count, const double* x, const double*
   }
   HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  ilqr::launch_step(c->knobs.var, count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right, geom, geom ? c->d_stance_out : nullptr);
+  ilqr::launch_step(plan_of(c), count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right, geom, geom ? c->d_stance_out : nullptr);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (geom && stance_out) HIPCHK(c, hipMemcpyAsync(stance_out, c->d_stance_out, (size_t)count * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1200,7 +1212,7 @@ int ilqr_hip_step_stance(ilqr_hip_ctx* c, int count, const double* x, const doub
 }
 // ---------------------------------------------------------------- stance from the foot hulls
 static const char* geometry_refusal(const ilqr_hip_ctx* c) {
-  if (c->knobs.var.scalar_dyn) return "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s";
+  if (!plan_of(c).stance_geometry) return "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s";
   if (c->P.dyn.contact == ILQR_CONTACT_RIGID_STANCE) return "contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4";
   return nullptr;
 }
@@ -1299,7 +1311,7 @@ int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);      // (k_warm_shift reads x0 from S.x0: the plant's state by the copy above)
-  ilqr::launch_last_step(c->knobs.var, c->S, c->P, c->stream);
+  ilqr::launch_last_step(plan_of(c), c->S, c->P, c->stream);
   HIPCHK(c, hipGetLastError());
   c->xbar_rolled = false;
   return ILQR_OK;      // asynchronous on the handle's stream

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <type_traits>
+
+#include "launch_plan.h"
 
 namespace h1 {
 struct ProblemDev;
@@ -78,29 +81,6 @@ struct DevState {
   int* chg_an;         // [max_iter + 2]
 };
 
-// kernel variants (ILQR_DYN / ILQR_ROLLOUT / ILQR_LS / ILQR_BACKWARD / ILQR_LINT): read from the environment ONCE per handle
-// (ilqr_hip_create; read_variants) and kept there; every launcher whose choice of kernel depends on the family takes the handle's copy
-// as its first argument.  backward: 0 four-wave MFMA, 1 LDS + VALU, 2 one wave per rollout; fold: see read_variants
-struct Variants {
-  int scalar_dyn, rollout_split, ls_split, backward, fold, lin_one_knot;
-  bool pack() const { return backward == 2 && fold == 2; }      // the operand-layout Riccati kernel (riccati_pack.hip) is in use
-};
-Variants read_variants();
-int variants_supported(const Variants& v);      // 0: the environment selects a cross-check family this build does not hold (-DILQR_LEGACY_KERNELS)
-
-void launch_rollout(const Variants& V, const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
-// geom / st_out: stance from each item's own feet (ProblemDev::stance_geom) / the flags it decided, [count][2] (two-lane kernels only)
-void launch_step(const Variants& V, int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l = 1, int stance_r = 1, int geom = 0, int* st_out = nullptr);
-// pack != 0 (a solve whose backward pass is the operand-layout Riccati kernel): A_t, B_t in the layout of riccati_pack.h (the two-knot
-// analytic kernels write it themselves, any other producer is followed by the conversion kernel)
-struct WorkList;
-// stance_dyn: [S.B][N][2] scratch of the stance source GEOMETRY (ProblemDev::stance_geom) -- the analytic Jacobians hold the nominal knots'
-// decisions fixed, decided into it first
-void launch_linearize(const Variants& V, const DevState& S, const h1::ProblemDev& P, int mode, int jac_mode, double eps, hipStream_t st, int phases = 3, int iter = -1, int pack = 0, const WorkList* wl = nullptr,
-                      int* stance_dyn = nullptr);
-// lower = 1: knots t < N get only the tiles I >= J of lxx (what k_backward_wave loads); 2: every knot in the operand layout of
-// riccati_pack.h (lx in row / column "aug"); the stage API always asks for the full matrix (0)
-void launch_cost_quadratics(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int lower = 0, const WorkList* wl = nullptr);
 // compacted list of the rollouts of a pass inside a solve (DevState::order), or nulls: MASK_ACTIVE at iteration iter -> list (iter, 0), MASK_RETRY -> (iter, 1)
 struct WorkList { const int* list; const int* count; };
 inline WorkList work_list(const DevState& S, int mode, int iter) {
@@ -108,61 +88,77 @@ inline WorkList work_list(const DevState& S, int mode, int iter) {
   const int slot = 2 * iter + (mode == MASK_RETRY ? 1 : 0);
   return WorkList{S.order + (size_t)slot * S.B, S.order_n + slot};
 }
-void launch_backward(const Variants& V, const DevState& S, int mode, hipStream_t st, double fold_h = 0.0, int iter = -1);
-// speculative lambda retry (ilqr_kernels.hip k_control_spec): T = the twin view whose K, kff, Vx, Vxx, candidates and lambda are its own
+
+// ---- ilqr_kernels.hip: the launchers that choose between kernel families.  L: the handle's LaunchPlan (launch_plan.h), resolved by the
+// caller from its switches (read_variants: the environment, once per handle), contact mode, joint-limit option and Jacobian mode.
+Variants read_variants();
+void launch_rollout(const LaunchPlan& L, const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
+// geom / st_out: stance from each item's own feet (ProblemDev::stance_geom) / the flags it decided, [count][2] (two-lane kernels only)
+void launch_step(const LaunchPlan& L, int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l = 1, int stance_r = 1, int geom = 0, int* st_out = nullptr);
+void launch_last_step(const LaunchPlan& L, const DevState& S, const h1::ProblemDev& P, hipStream_t st);
+// the warm start shifted by `shift` knots (1 <= shift <= N - 1): the copies (launch_warm_shift_m), then ONE kernel that re-rolls
+// xbar[N - shift + 1 .. N] with the state in registers
+void launch_warm_tail(const LaunchPlan& L, const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
+// phases: 1 = primal dump only, 2 = tangent sweeps / FD only, 3 = both.  pack != 0 (a solve under LaunchPlan::pack; the stage API asks
+// for the standard layout): A_t, B_t in the layout of riccati_pack.h (the two-knot analytic kernels write it themselves, any other producer
+// is followed by the conversion kernel).  stance_dyn: [S.B][N][2] scratch of the stance source GEOMETRY (LaunchPlan::lin_stance_prepass)
+void launch_linearize(const LaunchPlan& L, const DevState& S, const h1::ProblemDev& P, int mode, double eps, hipStream_t st, int phases = 3, int iter = -1, int pack = 0, const WorkList* wl = nullptr,
+                      int* stance_dyn = nullptr);
+// fold_h: the step size h if S.A / S.Bm hold foldable Jacobians (LaunchPlan::backward_foldable runs), else 0 (backward_plain)
+void launch_backward(const LaunchPlan& L, const DevState& S, int mode, hipStream_t st, double fold_h = 0.0, int iter = -1);
+void launch_backward_list(const LaunchPlan& L, const DevState& S, hipStream_t st, double fold_h, const int* list, const int* count);
+// max_rollouts: upper bound of the rollouts this pass can select (the batch, or -- with the early-exit gate -- the count of
+// still-active rollouts the host saw two iterations ago): at most 1024 -> one rollout per wave in the two-lane line search
+void launch_line_search(const LaunchPlan& L, const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int max_rollouts = -1);
+// ---- ilqr_kernels.hip: one kernel whatever the family
+void launch_line_search_list(const DevState& S, const h1::ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts);      // (LaunchPlan::spec_dual)
+void launch_control(const DevState& S, int phase, int iter, double tol, int early_exit, hipStream_t st, int sum_knots = 0, const int* gate = nullptr);
+// speculative lambda retry (k_control_spec): T = the twin view whose K, kff, Vx, Vxx, candidates and lambda are its own
 void launch_spec_lambda(const DevState& S, double* lambda2, hipStream_t st);
 void launch_control_spec(const DevState& S, const DevState& T, int iter, double tol, int early_exit, hipStream_t st, int sum_knots, const int* gate = nullptr);
 // Device-side choice between the two orders (the host's count of active rollouts is one iteration old): g[0] = n if n <= max else 0 (count of
 // the speculative launches), g[1] = 0 / 1 (gate of the sequential bookkeeping), g[2] = 0 / n (count of the sequential first line search), with
-// n = the length of list (iter, 0).  The launchers below take an explicit list / count (default kernel families only: spec_dual_available).
+// n = the length of list (iter, 0).  The list-driven launchers take an explicit list / count.
 void launch_spec_gate(const DevState& S, int iter, int max, int* g, hipStream_t st);
-bool spec_dual_available(const Variants& V, const h1::ProblemDev& P);
-void launch_backward_list(const Variants& V, const DevState& S, hipStream_t st, double fold_h, const int* list, const int* count);
-void launch_line_search_list(const DevState& S, const h1::ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts);
-double linearize_fold_h(const Variants& V, const h1::ProblemDev& P, int jac_mode);
-// max_rollouts: upper bound of the rollouts this pass can select (the batch, or -- with the early-exit gate -- the count of
-// still-active rollouts the host saw two iterations ago): at most 1024 -> one rollout per wave in the two-lane line search
-void launch_line_search(const Variants& V, const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int max_rollouts = -1);
-void launch_control(const DevState& S, int phase, int iter, double tol, int early_exit, hipStream_t st, int sum_knots = 0, const int* gate = nullptr);
-bool ls_costs_per_knot(const Variants& V, const h1::ProblemDev& P);
 void launch_solve_begin(const DevState& S, hipStream_t st);
 void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, unsigned long long* mismatches, hipStream_t st);
 void launch_warm_shift(const DevState& S, const double* prev_x, const double* prev_u, hipStream_t st);
-void launch_last_step(const Variants& V, const DevState& S, const h1::ProblemDev& P, hipStream_t st);
-void launch_compute_control(const DevState& S, const double* x_meas, double* u_out, hipStream_t st);
-// the warm start shifted by `shift` knots (1 <= shift <= N - 1): the copies, then ONE kernel that re-rolls xbar[N - shift + 1 .. N] with
-// the state in registers, in the family launch_last_step picks for the default kernels (unconstrained: _r; constrained: _s<KIND>)
 void launch_warm_shift_m(const DevState& S, const double* prev_x, const double* prev_u, int shift, hipStream_t st);
-void launch_warm_tail(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
-void launch_warm_tail_r(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
-void launch_warm_tail_s(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
+void launch_compute_control(const DevState& S, const double* x_meas, double* u_out, hipStream_t st);
 void launch_compute_control_at(const DevState& S, int knot, const double* x_meas, double* u_out, hipStream_t st);
 void launch_pack_first_knot(const DevState& S, double* u0, double* K0, hipStream_t st);
 void launch_pack_payload(const DevState& S, int with_gains, double* out, hipStream_t st);
 void launch_mirror_lxx(const DevState& S, hipStream_t st);   // fill the strictly upper tiles of lxx_t, t < N, from the lower ones
 int backward_needs_lds_attr();
-size_t backward_lds_bytes();
 size_t lin_dump_doubles();
+// ---- quad_kernels.hip
+// lower = 1: knots t < N get only the tiles I >= J of lxx (what k_backward_wave loads); 2: every knot in the operand layout of
+// riccati_pack.h (lx in row / column "aug"); the stage API always asks for the full matrix (0)
+void launch_cost_quadratics(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int lower = 0, const WorkList* wl = nullptr);
 size_t quad_rec_doubles(size_t knots);
+// ---- dyn_kernels.hip: one lane per rollout / candidate, and the cost kernels of the two-lane family
 void launch_rollout_r(const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
 void launch_step_r(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st);
 void launch_last_step_r(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
-void launch_cand_costs(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, bool with_sum = true, const int* gate = nullptr);
-void launch_nominal_costs(const DevState& S, const h1::ProblemDev& P, int mode, double* cost_out, hipStream_t st);
+void launch_warm_tail_r(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
 void launch_line_search_r(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st);
 void launch_lin_primal_r(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st);
+void launch_cand_costs(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, bool with_sum = true, const int* gate = nullptr);
+void launch_nominal_costs(const DevState& S, const h1::ProblemDev& P, int mode, double* cost_out, hipStream_t st);
 int dyn_kernels_set_attr();
-// dyn_split_kernels.hip: two lanes per rollout / candidate
+// ---- dyn_split_kernels.hip: two lanes per rollout / candidate, the StepKind instantiation picked from the dynamics parameters
 void launch_rollout_s(const DevState& S, const h1::ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st);
-void launch_lin_primal_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr);
-void launch_line_search_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr, int max_rollouts = -1);
-int dyn_split_kernels_set_attr();
 void launch_step_s(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out);
+void launch_last_step_s(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
+void launch_warm_tail_s(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
+void launch_line_search_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr, int max_rollouts = -1);
+void launch_lin_primal_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr);
 // stance flags of the nominal knots t = 0..N-1 from the feet of xbar (out[B][N][2]); rollouts selected as by launch_lin_primal_s
 void launch_stance_geom_s(const DevState& S, int mode, const int* list, const int* count, int* out, hipStream_t st);
-void launch_last_step_s(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
 void launch_linearize_fd_s(const DevState& S, const h1::ProblemDev& P, int mode, double eps, hipStream_t st);
-// plant_kernels.hip: the closed-loop plant resident in the handle (include/ilqr_hip.h ilqr_hip_plant_*); all device pointers
+int dyn_split_kernels_set_attr();
+// ---- plant_kernels.hip: the closed-loop plant resident in the handle (include/ilqr_hip.h ilqr_hip_plant_*); all device pointers.
+// Always the two-lane step, whatever the handle's family.
 struct PlantDev {
   double* x;        // [B][51] plant state
   double* u;        // [B][19] control applied in the last substep of the last advance (zero for a rollout that is not alive)
@@ -182,11 +178,11 @@ void launch_plant_advance(const DevState& S, const PlantDev& Pl, const h1::DynPa
 void launch_plant_follow(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
                          long hist_row0, long hist_cap, hipStream_t st);
 int plant_kernels_set_attr();
+// ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();
 void launch_backward_wave(const DevState& S, int mode, hipStream_t st, double fold_h, const int* list, const int* count);
-size_t backward_mfma_lds_bytes();
-// riccati_pack.hip: the one-wave kernel on the operand layout of riccati_pack.h and the conversions between that layout and the
+// ---- riccati_pack.hip: the one-wave kernel on the operand layout of riccati_pack.h and the conversions between that layout and the
 // standard one (in place, per knot region)
 void launch_backward_pack(const DevState& S, int mode, hipStream_t st, double fold_h, const int* list, const int* count);
 void launch_pack_ab(const DevState& S, hipStream_t st, int mode = MASK_ALL, const int* list = nullptr, const int* count = nullptr);

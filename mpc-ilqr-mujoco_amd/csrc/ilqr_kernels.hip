@@ -1127,9 +1127,9 @@ void launch_mirror_lxx(const DevState& S, hipStream_t st) { hipLaunchKernelGGL(k
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Kernel variants, selectable through the environment.  The switches are read ONCE when a handle is created (read_variants, called
-// from ilqr_hip_create) and kept in the handle; the launchers below that choose between families take the handle's copy as their
-// first argument -- no getenv on the call path and no state outside the handle: handles of different families may share a host thread,
-// and handles driven from different host threads (one thread and one handle per GPU, tests/cpp/cpp_multi_gpu_demo.cpp) share nothing.
+// from ilqr_hip_create) and kept in the handle -- no getenv on the call path and no state outside the handle: handles of different
+// families may share a host thread, and handles driven from different host threads (one thread and one handle per GPU,
+// tests/cpp/cpp_multi_gpu_demo.cpp) share nothing.
 //   ILQR_DYN=s        scratch-resident scalar ABA kernels for every dynamics stage (on-device cross-check; always in contact mode)
 //   ILQR_ROLLOUT=s|r  nominal rollout on two lanes (dyn_split_kernels.hip) or one lane per rollout
 //   ILQR_LS=s|r       line search on two lanes or one lane per candidate
@@ -1137,26 +1137,20 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 //                     the folded one-wave kernel on the standard layout (riccati_wave.hip) / never a folded variant / four-wave MFMA
 //                     (riccati_mfma.hip) / LDS + VALU cross-check
 //   ILQR_LINT=1       the one-knot two-wave tangent kernel (cross-check of k_lin_tangent2)
+// What the switches mean for a stage is decided in ONE place: resolve_plan (launch_plan.h) turns them, with the handle's contact mode,
+// joint-limit option and Jacobian mode, into a LaunchPlan -- the kernel of every stage, the step kind, the layouts a solve leaves behind,
+// and what the family can and cannot do (work lists, the re-rollout beside the linearisation, weight sets, stance from the feet, ...).
+// The launchers below switch on its fields; the C ABI resolves a plan per call and asks it instead of the switches.  The cross-check
+// families are compiled with -DILQR_LEGACY_KERNELS only (the test library lib/libilqr_hip_legacy.so); the product library holds the
+// default family alone and ilqr_hip_create refuses a handle whose environment selects anything else (plan_supported).
 #ifndef BACKWARD_DEFAULT
 #define BACKWARD_DEFAULT 2
 #endif
-// The cross-check families -- scalar scratch-resident dynamics (ILQR_DYN=s), one-lane rollout / line search / primal dump
-// (ILQR_ROLLOUT=r, ILQR_LS=r), the VALU and four-wave Riccati kernels (ILQR_BACKWARD=valu / wg), the folded Riccati kernel on the
-// standard layout (wave-fold), the one-knot tangent kernels (ILQR_LINT=1) -- are compiled with -DILQR_LEGACY_KERNELS only: the test
-// library lib/libilqr_hip_legacy.so.  The product library holds the default family alone; ilqr_hip_create refuses a handle whose
-// environment selects anything else (variants_supported).
 #ifdef ILQR_LEGACY_KERNELS
 #define LEGACY_LAUNCH(...) __VA_ARGS__
 #else
 #define LEGACY_LAUNCH(...) (void)0
 #endif
-int variants_supported(const Variants& v) {
-#ifdef ILQR_LEGACY_KERNELS
-  (void)v; return 1;
-#else
-  return (!v.scalar_dyn && v.rollout_split && v.ls_split && v.backward == 2 && v.fold != 1 && !v.lin_one_knot) ? 1 : 0;
-#endif
-}
 static int env_split(const char* var, int dflt) { const char* e = getenv(var); return !e ? dflt : (e[0] == 's' ? 1 : 0); }
 Variants read_variants() {
   Variants v;
@@ -1173,97 +1167,108 @@ Variants read_variants() {
   v.lin_one_knot = (e && e[0] == '1') ? 1 : 0;
   return v;
 }
-void launch_rollout(const Variants& V, const DevState& S, const ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st) {
-  // contact mode (f4) runs on the two-lane kernels (the one-lane register kernels are constraint-free only)
-  if (!V.scalar_dyn) { if (V.rollout_split || constrained(P.dyn)) launch_rollout_s(S, P, mode, do_roll, count_iter, cost_out, st); else launch_rollout_r(S, P, mode, do_roll, count_iter, cost_out, st); return; }
-  LEGACY_LAUNCH(hipLaunchKernelGGL(k_rollout, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S, P, mode, do_roll, count_iter, cost_out));
+void launch_rollout(const LaunchPlan& L, const DevState& S, const ProblemDev& P, int mode, int do_roll, int count_iter, double* cost_out, hipStream_t st) {
+  switch (L.rollout) {
+    case DYN_TWO_LANE: launch_rollout_s(S, P, mode, do_roll, count_iter, cost_out, st); break;
+    case DYN_ONE_LANE: launch_rollout_r(S, P, mode, do_roll, count_iter, cost_out, st); break;
+    case DYN_SCALAR: LEGACY_LAUNCH(hipLaunchKernelGGL(k_rollout, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S, P, mode, do_roll, count_iter, cost_out)); break;
+  }
 }
-void launch_step(const Variants& V, int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out) {
-  if (!V.scalar_dyn) { if (constrained(dyn) || st_out) launch_step_s(count, x, u, dyn, xn, st, stance_l, stance_r, geom, st_out); else launch_step_r(count, x, u, dyn, xn, st); return; }
-  LEGACY_LAUNCH(hipLaunchKernelGGL(k_step, dim3(cdiv(count, 64)), dim3(64), 0, st, count, x, u, dyn, xn, stance_l, stance_r));
+void launch_step(const LaunchPlan& L, int count, const double* x, const double* u, const DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out) {
+  if (L.step == DYN_SCALAR) LEGACY_LAUNCH(hipLaunchKernelGGL(k_step, dim3(cdiv(count, 64)), dim3(64), 0, st, count, x, u, dyn, xn, stance_l, stance_r));
+  else if (L.step == DYN_TWO_LANE || st_out) launch_step_s(count, x, u, dyn, xn, st, stance_l, stance_r, geom, st_out);
+  else launch_step_r(count, x, u, dyn, xn, st);
 }
-// phases: 1 = primal dump only, 2 = tangent sweeps / FD only, 3 = both
-// constraint-free tangent kernel: two knots per four-wave workgroup (default) or, ILQR_LINT=1, the one-knot two-wave kernel
-static void launch_lin_tangent_free(const Variants& V, const DevState& S, const ProblemDev& P, int mode, hipStream_t st, const WorkList& w, int pack) {
-  if (V.lin_one_knot) { LEGACY_LAUNCH(hipLaunchKernelGGL(k_lin_tangent, dim3(S.N, S.B), dim3(128), 0, st, S, P, mode, w.list, w.count)); if (pack) launch_pack_ab(S, st, mode, w.list, w.count); return; }
-  const long items = (long)S.B * S.N;
-  const dim3 grid2((unsigned)((items + 1) / 2));
-  if (P.dyn.limits) { if (pack) hipLaunchKernelGGL((k_lin_tangent2<true, true>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count); else hipLaunchKernelGGL((k_lin_tangent2<false, true>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count); }
-  else if (pack) hipLaunchKernelGGL((k_lin_tangent2<true, false>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count);
-  else hipLaunchKernelGGL((k_lin_tangent2<false, false>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count);
+void launch_last_step(const LaunchPlan& L, const DevState& S, const ProblemDev& P, hipStream_t st) {
+  switch (L.step) {
+    case DYN_TWO_LANE: launch_last_step_s(S, P, st); break;
+    case DYN_ONE_LANE: launch_last_step_r(S, P, st); break;
+    case DYN_SCALAR: LEGACY_LAUNCH(hipLaunchKernelGGL(k_last_step, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S, P)); break;
+  }
 }
-void launch_linearize(const Variants& V, const DevState& S, const ProblemDev& P0, int mode, int jac_mode, double eps, hipStream_t st, int phases, int iter, int pack, const WorkList* wl,
-                      int* stance_dyn) {
+// (the scalar cross-check family of the test library has no tail kernel: it re-rolls by the default family's, as the plant does)
+void launch_warm_tail(const LaunchPlan& L, const DevState& S, const ProblemDev& P, int shift, hipStream_t st) {
+  if (L.step_kind != STEP_FREE) launch_warm_tail_s(S, P, shift, st); else launch_warm_tail_r(S, P, shift, st);
+}
+// the tangent sweeps of the analytic modes: two knots per four-wave workgroup or, ILQR_LINT=1, the one-knot two-wave kernels (followed
+// by the conversion kernel where the operand layout is asked for)
+static void launch_lin_tangent(const LaunchPlan& L, const DevState& S, const ProblemDev& P, int mode, hipStream_t st, const WorkList& w, int pack) {
+  if (L.lin == LIN_ANALYTIC_ONE_KNOT) {
+    if (L.lin_contact_tangent) LEGACY_LAUNCH(hipLaunchKernelGGL(k_lin_tangent_c, dim3(S.N, S.B), dim3(128), 0, st, S, P, mode, w.list, w.count));
+    else LEGACY_LAUNCH(hipLaunchKernelGGL(k_lin_tangent, dim3(S.N, S.B), dim3(128), 0, st, S, P, mode, w.list, w.count));
+    if (pack) launch_pack_ab(S, st, mode, w.list, w.count);
+    return;
+  }
+  const dim3 grid2((unsigned)(((long)S.B * S.N + 1) / 2));
+  // (template values: operand layout, Coulomb-limit branch of the contact mode, joint-limit rows)
+#define LAUNCH_T2(PK, LM) hipLaunchKernelGGL((k_lin_tangent2<PK, LM>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count)
+#define LAUNCH_T2C(PK, FR, LM) hipLaunchKernelGGL((k_lin_tangent2c<PK, FR, LM>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count)
+#define LAUNCH_T2_L(PK) do { if (L.limits) LAUNCH_T2(PK, true); else LAUNCH_T2(PK, false); } while (0)
+#define LAUNCH_T2C_L(PK, FR) do { if (L.limits) LAUNCH_T2C(PK, FR, true); else LAUNCH_T2C(PK, FR, false); } while (0)
+#define LAUNCH_T2C_F(PK) do { if (L.lin_friction == 1) LAUNCH_T2C_L(PK, 1); else if (L.lin_friction == 2) LAUNCH_T2C_L(PK, 2); else LAUNCH_T2C_L(PK, 0); } while (0)
+  if (L.lin_contact_tangent) { if (pack) LAUNCH_T2C_F(true); else LAUNCH_T2C_F(false); }
+  else { if (pack) LAUNCH_T2_L(true); else LAUNCH_T2_L(false); }
+#undef LAUNCH_T2C_F
+#undef LAUNCH_T2C_L
+#undef LAUNCH_T2_L
+#undef LAUNCH_T2C
+#undef LAUNCH_T2
+}
+void launch_linearize(const LaunchPlan& L, const DevState& S, const ProblemDev& P0, int mode, double eps, hipStream_t st, int phases, int iter, int pack, const WorkList* wl, int* stance_dyn) {
   const WorkList w = wl ? *wl : work_list(S, mode, iter);
   ProblemDev P = P0;
-  if (jac_mode == 0 && !V.scalar_dyn && P0.stance_geom && P0.dyn.contact && stance_dyn) {
+  if (L.lin_stance_prepass && P0.stance_geom && stance_dyn) {
     // stance from the feet: the nominal knots decide once, the primal dump (joint-limit decision pass) and the tangent kernels read those
     // decisions where they read the schedule otherwise -- held fixed, as every other decision of the analytic Jacobians
     if (phases & 1) launch_stance_geom_s(S, mode, w.list, w.count, stance_dyn, st);
     P.stance = stance_dyn; P.stance_stride = 2L * S.N;
   }
-  if (jac_mode == 0 && !V.scalar_dyn) {
-    // primal dump: on two lanes per knot beside the two-lane rollout kernels, one lane per knot with ILQR_ROLLOUT=r
-    if (phases & 1) { if (V.rollout_split || constrained(P.dyn)) launch_lin_primal_s(S, P, mode, st, w.list, w.count); else launch_lin_primal_r(S, P, mode, st); }   // (contact mode: the dump is the free solve, see k_lin_tangent_c)
-    if ((phases & 2) && P.dyn.contact) {
-      const dim3 grid2((unsigned)(((long)S.B * S.N + 1) / 2));
-      if (V.lin_one_knot) { LEGACY_LAUNCH(hipLaunchKernelGGL(k_lin_tangent_c, dim3(S.N, S.B), dim3(128), 0, st, S, P, mode, w.list, w.count)); if (pack) launch_pack_ab(S, st, mode, w.list, w.count); }
-      else {
-        // (template values: operand layout, Coulomb-limit branch of the contact mode, joint-limit rows)
-#define LAUNCH_T2C(PK, FR, LM) hipLaunchKernelGGL((k_lin_tangent2c<PK, FR, LM>), grid2, dim3(256), 0, st, S, P, mode, w.list, w.count)
-#define LAUNCH_T2C_L(PK, FR) do { if (P.dyn.limits) LAUNCH_T2C(PK, FR, true); else LAUNCH_T2C(PK, FR, false); } while (0)
-#define LAUNCH_T2C_F(PK) do { if (P.dyn.contact == 3) LAUNCH_T2C_L(PK, 1); else if (P.dyn.contact == 4) LAUNCH_T2C_L(PK, 2); else LAUNCH_T2C_L(PK, 0); } while (0)
-        if (pack) LAUNCH_T2C_F(true); else LAUNCH_T2C_F(false);
-#undef LAUNCH_T2C_F
-#undef LAUNCH_T2C_L
-#undef LAUNCH_T2C
+  switch (L.lin) {
+    case LIN_ANALYTIC_TWO_KNOT: case LIN_ANALYTIC_ONE_KNOT:
+      // (contact mode: the dump is the free solve, see k_lin_tangent_c)
+      if (phases & 1) { if (L.primal_dump == DYN_TWO_LANE) launch_lin_primal_s(S, P, mode, st, w.list, w.count); else launch_lin_primal_r(S, P, mode, st); }
+      if (phases & 2) launch_lin_tangent(L, S, P, mode, st, w, pack);
+      break;
+    case LIN_FD_TWO_LANE:
+      if (phases & 2) launch_linearize_fd_s(S, P, mode, eps, st);
+      break;
+    case LIN_FD_SCALAR:
+      if (phases & 2) {
+        LEGACY_LAUNCH(hipLaunchKernelGGL(k_fd_base, dim3(cdiv((long)S.B * S.N, 64)), dim3(64), 0, st, S, P, mode));
+        LEGACY_LAUNCH(hipLaunchKernelGGL(k_linearize_fd, dim3(cdiv((long)S.B * S.N * (H1_NX + H1_NU), 256)), dim3(256), 0, st, S, P, mode, eps));
       }
-    }
-    else if (phases & 2) launch_lin_tangent_free(V, S, P, mode, st, w, pack);
-  } else if (jac_mode == 0 && !P.dyn.contact) {               // ILQR_DYN=s: the analytic kernels are constraint-free only
-    if (phases & 1) launch_lin_primal_r(S, P, mode, st);
-    if (phases & 2) launch_lin_tangent_free(V, S, P, mode, st, w, pack);
-  } else if ((phases & 2) && !V.scalar_dyn) {
-    launch_linearize_fd_s(S, P, mode, eps, st);       // forward differences on the two-lane step (any contact mode)
-  } else if (phases & 2) {
-    const long total = (long)S.B * S.N * (H1_NX + H1_NU);
-    LEGACY_LAUNCH(hipLaunchKernelGGL(k_fd_base, dim3(cdiv((long)S.B * S.N, 64)), dim3(64), 0, st, S, P, mode));
-    LEGACY_LAUNCH(hipLaunchKernelGGL(k_linearize_fd, dim3(cdiv(total, 256)), dim3(256), 0, st, S, P, mode, eps));
-    (void)total;
+      break;
   }
 }
 size_t lin_dump_doubles() { return LinDumpG_SIZE; }
-// Step size h if launch_linearize(jac_mode) writes Jacobians whose hinge-position rows are exactly e_k + h * the hinge-velocity
-// rows (the analytic tangent kernels, lin_column) and the backward kernel can use that (riccati_wave.hip fold_rows); else 0.
-double linearize_fold_h(const Variants& V, const ProblemDev& P, int jac_mode) {
-  const bool analytic = jac_mode == 0 && (!V.scalar_dyn || !P.dyn.contact);
-  return (analytic && V.fold && V.backward == 2) ? P.dyn.h : 0.0;
-}
-// ILQR_BACKWARD=valu selects the LDS + VALU kernel (kept as an on-device cross-check), =wg the four-wave MFMA
-// kernel (riccati_mfma.hip), =wave the one-wave-per-rollout MFMA kernel (riccati_wave.hip)
-void launch_backward(const Variants& V, const DevState& S, int mode, hipStream_t st, double fold_h, int iter) {
-  if (V.backward == 1) LEGACY_LAUNCH(hipLaunchKernelGGL(k_backward, dim3(S.B), dim3(256), backward_lds_bytes(), st, S, mode));
-  else if (V.backward == 2) {
-    const WorkList w = work_list(S, mode, iter);      // inside a solve (iter >= 0) the selected rollouts come from the compacted list of this pass
-    if (V.fold == 2 && fold_h != 0.0) launch_backward_pack(S, mode, st, fold_h, w.list, w.count);      // (S.A, S.Bm, S.lxx in the operand layout: the caller's business)
-    else launch_backward_wave(S, mode, st, V.fold == 1 ? fold_h : 0.0, w.list, w.count);
+// the backward pass of a selection given as mask (list / count null) or as compacted list; the one-wave kernels alone read the list
+static void backward_pass(const LaunchPlan& L, const DevState& S, int mode, hipStream_t st, double fold_h, const int* list, const int* count) {
+  switch (fold_h != 0.0 ? L.backward_foldable : L.backward_plain) {
+    case BWD_PACK: launch_backward_pack(S, mode, st, fold_h, list, count); break;      // (S.A, S.Bm, S.lxx in the operand layout: the caller's business)
+    case BWD_WAVE_FOLDED: launch_backward_wave(S, mode, st, fold_h, list, count); break;
+    case BWD_WAVE_GENERIC: launch_backward_wave(S, mode, st, 0.0, list, count); break;
+    case BWD_FOUR_WAVE: LEGACY_LAUNCH(launch_backward_mfma(S, mode, st)); break;
+    case BWD_VALU: LEGACY_LAUNCH(hipLaunchKernelGGL(k_backward, dim3(S.B), dim3(256), backward_lds_bytes(), st, S, mode)); break;
   }
-  else LEGACY_LAUNCH(launch_backward_mfma(S, mode, st));
 }
-void launch_line_search(const Variants& V, const DevState& S, const ProblemDev& P, int mode, hipStream_t st, int iter, int max_rollouts) {
-  if (!V.scalar_dyn) {
-    if (V.ls_split || constrained(P.dyn)) {
+void launch_backward(const LaunchPlan& L, const DevState& S, int mode, hipStream_t st, double fold_h, int iter) {
+  const WorkList w = work_list(S, mode, iter);      // inside a solve (iter >= 0) the selected rollouts come from the compacted list of this pass
+  backward_pass(L, S, mode, st, fold_h, w.list, w.count);
+}
+void launch_backward_list(const LaunchPlan& L, const DevState& S, hipStream_t st, double fold_h, const int* list, const int* count) { backward_pass(L, S, MASK_ACTIVE, st, fold_h, list, count); }
+void launch_line_search(const LaunchPlan& L, const DevState& S, const ProblemDev& P, int mode, hipStream_t st, int iter, int max_rollouts) {
+  switch (L.line_search) {
+    case DYN_TWO_LANE: {
       const WorkList w = work_list(S, mode, iter);      // as launch_backward
       launch_line_search_s(S, P, mode, st, w.list, w.count, w.list ? max_rollouts : -1);
-      launch_cand_costs(S, P, mode, st, iter < 0);      // (inside a solve k_control adds the knot costs up)
-    }   // candidates' costs: all knots in parallel
-    else launch_line_search_r(S, P, mode, st);                                                  // (the one-lane kernel sums its own)
-    return;
+      launch_cand_costs(S, P, mode, st, iter < 0);      // candidates' costs: all knots in parallel (inside a solve k_control adds the knot costs up: LaunchPlan::ls_costs_per_knot)
+      break;
+    }
+    case DYN_ONE_LANE: launch_line_search_r(S, P, mode, st); break;      // (the one-lane kernel sums its own)
+    case DYN_SCALAR: LEGACY_LAUNCH(hipLaunchKernelGGL(k_line_search, dim3(cdiv((long)S.B * 8, 64)), dim3(64), 0, st, S, P, mode)); break;
   }
-  LEGACY_LAUNCH(hipLaunchKernelGGL(k_line_search, dim3(cdiv((long)S.B * 8, 64)), dim3(64), 0, st, S, P, mode));
 }
-// inside a solve the two-lane line search leaves per-knot costs behind and k_control sums them itself (ls_costs_per_knot)
-bool ls_costs_per_knot(const Variants& V, const ProblemDev& P) { return !V.scalar_dyn && (V.ls_split || constrained(P.dyn)); }
+void launch_line_search_list(const DevState& S, const ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts) { launch_line_search_s(S, P, MASK_ACTIVE, st, list, count, max_rollouts); }
 void launch_control(const DevState& S, int phase, int iter, double tol, int early_exit, hipStream_t st, int sum_knots, const int* gate) {
   hipLaunchKernelGGL(k_control, dim3(cdiv(S.B, CTRL_WAVES)), dim3(64 * CTRL_WAVES), 0, st, S, phase, iter, tol, early_exit, sum_knots, gate);
 }
@@ -1272,19 +1277,10 @@ void launch_control_spec(const DevState& S, const DevState& T, int iter, double 
   hipLaunchKernelGGL(k_control_spec, dim3(cdiv(S.B, CTRL_WAVES)), dim3(64 * CTRL_WAVES), 0, st, S, T, iter, tol, early_exit, sum_knots, gate);
 }
 void launch_spec_gate(const DevState& S, int iter, int max, int* g, hipStream_t st) { hipLaunchKernelGGL(k_spec_gate, dim3(1), dim3(1), 0, st, (const int*)(S.order_n + 2 * iter), max, g); }
-bool spec_dual_available(const Variants& V, const ProblemDev& P) { return !V.scalar_dyn && V.backward == 2 && (V.ls_split || constrained(P.dyn)); }
-void launch_backward_list(const Variants& V, const DevState& S, hipStream_t st, double fold_h, const int* list, const int* count) {
-  if (V.fold == 2 && fold_h != 0.0) launch_backward_pack(S, MASK_ACTIVE, st, fold_h, list, count);
-  else launch_backward_wave(S, MASK_ACTIVE, st, V.fold == 1 ? fold_h : 0.0, list, count);
-}
-void launch_line_search_list(const DevState& S, const ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts) { launch_line_search_s(S, P, MASK_ACTIVE, st, list, count, max_rollouts); }
 void launch_solve_begin(const DevState& S, hipStream_t st) { hipLaunchKernelGGL(k_solve_begin, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S); }
 void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, unsigned long long* mismatches, hipStream_t st) { hipLaunchKernelGGL(k_adopt_rollout, dim3(S.B), dim3(64), 0, st, S, shadow, mode, mismatches); }
 void launch_warm_shift(const DevState& S, const double* px, const double* pu, hipStream_t st) { hipLaunchKernelGGL(k_warm_shift, dim3(S.B), dim3(64), 0, st, S, px, pu); }
-void launch_last_step(const Variants& V, const DevState& S, const ProblemDev& P, hipStream_t st) { if (!V.scalar_dyn) { if (constrained(P.dyn)) launch_last_step_s(S, P, st); else launch_last_step_r(S, P, st); return; } LEGACY_LAUNCH(hipLaunchKernelGGL(k_last_step, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S, P)); }
 void launch_warm_shift_m(const DevState& S, const double* px, const double* pu, int shift, hipStream_t st) { hipLaunchKernelGGL(k_warm_shift_m, dim3(S.B), dim3(64), 0, st, S, px, pu, shift); }
-// (the scalar cross-check family of the test library has no tail kernel: it re-rolls by the default family's, as the plant does)
-void launch_warm_tail(const DevState& S, const ProblemDev& P, int shift, hipStream_t st) { if (constrained(P.dyn)) launch_warm_tail_s(S, P, shift, st); else launch_warm_tail_r(S, P, shift, st); }
 void launch_compute_control_at(const DevState& S, int knot, const double* x_meas, double* u_out, hipStream_t st) { hipLaunchKernelGGL(k_compute_control_at, dim3(S.B), dim3(64), 0, st, S, knot, x_meas, u_out); }
 void launch_compute_control(const DevState& S, const double* x_meas, double* u_out, hipStream_t st) { hipLaunchKernelGGL(k_compute_control, dim3(S.B), dim3(64), 0, st, S, x_meas, u_out); }
 void launch_pack_first_knot(const DevState& S, double* u0, double* K0, hipStream_t st) { hipLaunchKernelGGL(k_pack_first_knot, dim3(S.B), dim3(64), 0, st, S, u0, K0); }

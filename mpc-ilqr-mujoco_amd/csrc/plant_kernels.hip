@@ -304,8 +304,7 @@ template <int KIND, int FB> static int plant_attr() {
 }
 int plant_kernels_set_attr() {
   int rc = 0;
-  rc |= plant_attr<0, 0>(); rc |= plant_attr<1, 0>(); rc |= plant_attr<2, 0>(); rc |= plant_attr<3, 0>(); rc |= plant_attr<4, 0>(); rc |= plant_attr<5, 0>();
-  rc |= plant_attr<0, 1>(); rc |= plant_attr<1, 1>(); rc |= plant_attr<2, 1>(); rc |= plant_attr<3, 1>(); rc |= plant_attr<4, 1>(); rc |= plant_attr<5, 1>();
+  for_each_step_kind([&](auto K) { rc |= plant_attr<K(), 0>(); rc |= plant_attr<K(), 1>(); });
   return rc;
 }
 template <int KIND, int FB>
@@ -314,21 +313,12 @@ static void plant_launch(const DevState& S, const PlantDev& Pl, const DynParams&
   const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
   hipLaunchKernelGGL((k_plant_advance<KIND, FB>), grid, dim3(64), Lay::DOUBLES * sizeof(double), st, S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row);
 }
-template <int FB>
-static void plant_launch_kind(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, long hist_row, hipStream_t st) {
-  switch (step_kind(dyn)) {
-    case 5: plant_launch<5, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
-    case 4: plant_launch<4, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
-    case 3: plant_launch<3, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
-    case 2: plant_launch<2, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
-    case 1: plant_launch<1, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st); break;
-    default: plant_launch<0, FB>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
-  }
-}
 void launch_plant_advance(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, long hist_row,
                           hipStream_t st) {
-  if (feedback_mode) plant_launch_kind<1>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
-  else plant_launch_kind<0>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+  with_step_kind(dyn, [&](auto K) {
+    if (feedback_mode) plant_launch<K(), 1>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+    else plant_launch<K(), 0>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
+  });
 }
 
 struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
@@ -338,22 +328,13 @@ static void follow_launch(const DevState& S, const PlantDev& Pl, const DynParams
   const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
   hipLaunchKernelGGL((k_plant_follow<KIND, FB>), grid, dim3(64), Lay::DOUBLES * sizeof(double), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap);
 }
-template <int FB>
-static void follow_launch_kind(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const FollowArgs& a, hipStream_t st) {
-  switch (step_kind(dyn)) {
-    case 5: follow_launch<5, FB>(S, Pl, dyn, a, st); break;
-    case 4: follow_launch<4, FB>(S, Pl, dyn, a, st); break;
-    case 3: follow_launch<3, FB>(S, Pl, dyn, a, st); break;
-    case 2: follow_launch<2, FB>(S, Pl, dyn, a, st); break;
-    case 1: follow_launch<1, FB>(S, Pl, dyn, a, st); break;
-    default: follow_launch<0, FB>(S, Pl, dyn, a, st);
-  }
-}
 void launch_plant_follow(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
                          long hist_row0, long hist_cap, hipStream_t st) {
   const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
-  if (feedback_mode) follow_launch_kind<1>(S, Pl, dyn, a, st);
-  else follow_launch_kind<0>(S, Pl, dyn, a, st);
+  with_step_kind(dyn, [&](auto K) {
+    if (feedback_mode) follow_launch<K(), 1>(S, Pl, dyn, a, st);
+    else follow_launch<K(), 0>(S, Pl, dyn, a, st);
+  });
 }
 
 }  // namespace ilqr

@@ -645,7 +645,7 @@ DEVFN void quad_hessian_tiles(const double (&av)[4][2], const double (&bv)[4][4]
 // computed and stored -- exactly the ones k_backward_wave loads (load_aug<true>, riccati_wave.hip); lxx is symmetric, the six
 // strictly upper 16 x 16 tiles (35 % of its entries, 0.85 GB per launch at B = 4096) were written for nobody.  The terminal knot,
 // which that kernel loads whole, and every stage-API call keep the full matrix (ilqr_hip_get_quadratics mirrors the tiles back).
-// Workgroup numbering: workgroups are dealt to the 8 XCDs round-robin by index, and 16 consecutive knots share the 128-byte
+// Workgroup numbering: workgroups are dealt to the 8 XCDs round-robin by index, and QREC_KNOTS = 4 consecutive knots share the 128-byte
 // lines of a record group; workgroup L therefore takes knot item (L % 8) * ceil(total / 8) + L / 8 -- consecutive items on one XCD.
 // WS: the weights are rollout b's weight set.  b is one value for the workgroup (blockIdx, or one list[bs] load) and is pinned to a scalar
 // register, so the record's address is wave-uniform: the weight reads stay scalar loads and the `w > 0.0` branches scalar branches.  The

@@ -33,7 +33,6 @@
 namespace ilqr {
 void launch_backward_mfma(const DevState&, int, hipStream_t) {}
 int backward_mfma_set_attr() { return 0; }
-size_t backward_mfma_lds_bytes() { return 0; }
 }  // namespace ilqr
 #else
 #include <hip/hip_runtime.h>
@@ -419,7 +418,6 @@ __global__ void __launch_bounds__(256, 2) k_backward_mfma(DevState S, int mode) 
   if (tid < n) S.Vx[(size_t)b * n + tid] = L.Vxx[51 * LDV + tid];
 }
 
-size_t backward_mfma_lds_bytes() { return sizeof(RiccatiLds); }
 int backward_mfma_set_attr() { return 0; }   // LDS is allocated statically
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st) {
   hipLaunchKernelGGL(k_backward_mfma, dim3(S.B), dim3(256), 0, st, S, mode);
