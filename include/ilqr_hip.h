@@ -347,6 +347,37 @@ int ilqr_hip_plant_get_stance(ilqr_hip_ctx* ctx, int* stance /*[B][2]*/);
 int ilqr_hip_plant_get_alive(ilqr_hip_ctx* ctx, int* alive /*[B]*/);
 /* The plant state as a device pointer [B][51], for a caller that chains its own kernels on ilqr_hip_stream; no synchronisation. */
 int ilqr_hip_plant_state_device(ilqr_hip_ctx* ctx, const double** x_device);
+/* ---- closed-loop score of the plant: which rollout's closed loop did best.  While a score is installed every ilqr_hip_plant_advance /
+   ilqr_hip_plant_follow is followed, on the same stream, by two small kernels that evaluate the terms of iLQR::computeTotalCost
+   (src/ilqr/ilqr.cpp:363-518) of every interval the call ran and add them to a record of ILQR_PLANT_SCORE_TERMS doubles per rollout:
+     0  sum of 1/2 sum_i Q_i (x_i - x_ref[k]_i)^2        1  sum of 1/2 sum_i R_i (u_i - u_ref[k]_i)^2
+     2  sum of the upright term (0 while w_upright == 0)
+     3  sum of the capture-point term: support point from row k of the contact SCHEDULE and of ee_ref, MuJoCo CoM (0 for a row without a
+        stance foot or while w_balance == 0)
+     4  sum of the joint-limit soft penalty (10 % margins)   5  sum of the control-limit soft penalty on the reported, unclamped u
+     6  minimum of x[2] (pelvis height) over the scored intervals, +inf before the first; a NaN height is ignored
+     7  number of intervals scored, as a double
+   -- the expressions of a non-terminal knot of the solver's cost, under ONE shared set of scoring weights that is independent of the
+   solver's weights (ilqr_hip_set_cost_weights ...) and of an installed weight-set table: in a weight sweep every rollout is measured with
+   the same ruler.  (x, u) of an interval are exactly the row the plant appends to the history ring (the state behind the kick, the control
+   reported; a frozen rollout scores the rows the ring logs for it, a non-finite row makes that rollout's sums non-finite and touches no
+   other rollout).  Reference row k: 0 of the window currently set for ilqr_hip_plant_advance, first_knot + j for interval j of
+   ilqr_hip_plant_follow; x_ref, u_ref, ee_ref and the schedule alike, each rollout its own set where the sets are per rollout.
+   The record is a pure function of ring rows, reference rows and scoring weights, and is accumulated without atomics in interval order:
+   ilqr_hip_plant_follow(0, m) and m calls (j, 1) give the same record bit for bit.
+   Ring requirement: the score kernels read the ring, so with a score installed a plant call whose intervals exceed the ring's rows (no
+   ring at all; count > rows) returns ILQR_ERR_STATE before anything is launched or counted.  The ring may be as small as the largest
+   call: a run of any length is scored without keeping or downloading its history.
+   set_score: installs the weights (Q_diag[51], R_diag[19]) and empties the record (calling it again empties it again); synchronises the
+   handle's stream.  ILQR_ERR_ARG for a null argument or a negative / non-finite weight.  ilqr_hip_plant_reset empties the record too.
+   clear_score: frees it; the plant calls then launch exactly what they launch without it.
+   get_score: score[B][8], synchronises the handle's stream; score_device: the record as a device pointer, no synchronisation.  Both
+   ILQR_ERR_STATE while no score is installed. */
+#define ILQR_PLANT_SCORE_TERMS 8
+int ilqr_hip_plant_set_score(ilqr_hip_ctx* ctx, const double* Q_diag /*[51]*/, const double* R_diag /*[19]*/, double w_upright, double w_balance, double w_joint_limits, double w_control_limits);
+int ilqr_hip_plant_clear_score(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_score(ilqr_hip_ctx* ctx, double* score /*[B][8]*/);
+int ilqr_hip_plant_score_device(ilqr_hip_ctx* ctx, const double** score_device);
 
 /* per-stage device time of the last solve in milliseconds, keyed like the reference's profiler
    (src/ilqr/ilqr.cpp:537-639): 0 computeCost/rollout, 1 linearization, 2 costQuadratics, 3 backwardPass,

@@ -181,6 +181,13 @@ class iLQR {
   std::vector<int> plantStance() { std::vector<int> s((size_t)B_ * 2); chk(ilqr_hip_plant_get_stance(ctx_, s.data())); return s; }
   std::vector<int> plantAlive() { std::vector<int> a((size_t)B_); chk(ilqr_hip_plant_get_alive(ctx_, a.data())); return a; }   // main:134-137
   const double* plantStateDevice() { const double* p = nullptr; chk(ilqr_hip_plant_state_device(ctx_, &p)); return p; }
+  // closed-loop score (ilqr_hip.h ilqr_hip_plant_set_score): the terms of computeTotalCost, ilqr.cpp:363-518, of the trajectory the plant drove
+  void plantSetScore(const Vec& Q /*[51]*/, const Vec& R /*[19]*/, double w_upright = 0.0, double w_balance = 0.0, double w_joint_limits = 0.0, double w_control_limits = 0.0) {
+    if (Q.size() != (size_t)ILQR_NX || R.size() != (size_t)ILQR_NU) throw std::runtime_error("score weights: Q holds 51 doubles, R 19");
+    chk(ilqr_hip_plant_set_score(ctx_, Q.data(), R.data(), w_upright, w_balance, w_joint_limits, w_control_limits));
+  }
+  void plantClearScore() { chk(ilqr_hip_plant_clear_score(ctx_)); }
+  Vec plantScore() { Vec s((size_t)B_ * ILQR_PLANT_SCORE_TERMS); chk(ilqr_hip_plant_get_score(ctx_, s.data())); return s; }      // [batch][8]
 
  private:
   void chk(int rc) { if (rc != ILQR_OK) throw std::runtime_error(std::string("ilqr_hip: ") + ilqr_hip_last_error(ctx_)); }

@@ -129,6 +129,41 @@ DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, con
 }
 template <class ComFn>
 DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn) { return knot_cost_w<false>(P, b, t, x, u, com_fn); }
+// The terms of knot_cost_w<false> at a NON-terminal knot, one by one, under the shared weights of P (a caller with weights of its own
+// passes a copy of P that holds them): out[0] state, [1] control, [2] upright, [3] balance, [4] joint-limit penalty, [5] control-limit
+// penalty -- the same expressions in the same order of operations, so that their sum is knot_cost_w's value up to its own additions
+// (csrc/plant_score_kernels.hip; include/ilqr_hip.h ILQR_PLANT_SCORE_TERMS)
+template <class ComFn>
+DEVFN void knot_cost_terms(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn, double* out) {
+  const CostWeights<false> Wt(P, b);
+  const double* xr = P.x_ref + b * P.x_ref_stride + t * H1_NX;
+  const double* Qd = Wt.Qd(P, false);
+  double a = 0.0;
+  for (int i = 0; i < H1_NX; ++i) { const double e = x[i] - xr[i]; a += e * Qd[i] * e; }
+  out[0] = 0.5 * a;
+  const double* ur = P.u_ref + b * P.u_ref_stride + t * H1_NU;
+  double s = 0.0;
+  for (int i = 0; i < H1_NU; ++i) { const double e = u[i] - ur[i]; s += e * Wt.R(P, i) * e; }
+  out[1] = 0.5 * s;
+  out[2] = 0.0;
+  if (Wt.w_upright(P) > 0.0) {
+    const double qw = x[3], qx = x[4], qy = x[5], qz = x[6];
+    const double zx = 2.0 * (qx * qz + qw * qy), zy = 2.0 * (qy * qz - qw * qx), zz = 1.0 - 2.0 * (qx * qx + qy * qy);
+    out[2] = 0.5 * Wt.w_upright(P) * (zx * zx + zy * zy + (zz - 1.0) * (zz - 1.0));
+  }
+  out[3] = 0.0;
+  if (Wt.w_balance(P) > 0.0) {
+    double ps[2];
+    if (support_point(P, b, t, ps)) {
+      double com[3]; com_fn(x, com);
+      const double om = sqrt(com[2] / 9.81);
+      const double rx = com[0] + x[H1_NQ] * om - ps[0], ry = com[1] + x[H1_NQ + 1] * om - ps[1];
+      out[3] = 0.5 * Wt.w_balance(P) * (rx * rx + ry * ry);
+    }
+  }
+  out[4] = joint_penalty(P, Wt, x);
+  out[5] = ctrl_penalty(P, Wt, u);
+}
 struct ComLoop { DEVFN void operator()(const double* x, double* com) const { com_mj(x, com); } };
 __device__ inline double knot_cost(const ProblemDev& P, int b, int t, const double* x, const double* u) { return knot_cost_t(P, b, t, x, u, ComLoop()); }
 

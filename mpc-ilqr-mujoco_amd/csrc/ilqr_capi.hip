@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -17,6 +18,7 @@
 #include "h1_cost_dev.h"
 #include "h1_host_model.h"
 #include "ilqr_kernels.h"
+#include "plant_score_kernels.h"
 
 using ilqr::DevState;
 
@@ -148,6 +150,11 @@ struct ilqr_hip_ctx {
   int plant_substeps = 1, plant_feedback = 0, plant_source = ILQR_STANCE_SCHEDULE;
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
+  // closed-loop score of the plant (ilqr_hip_plant_set_score; plant_score_kernels.hip): the record [B][8], the term rows of one plant call
+  // [N][B][8] and the scoring weights (Q, R, upright, balance, joint limits, control limits), all independent of P's and of the weight sets
+  double *d_score = nullptr, *d_score_terms = nullptr;
+  bool score_on = false;
+  double score_Q[ILQR_NX] = {0}, score_R[ILQR_NU] = {0}, score_w[4] = {0};
 };
 
 #define HIPCHK(ctx, call)                                                                   \
@@ -303,7 +310,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1255,6 +1262,22 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* c, int* stance) {
   return ILQR_OK;
 }
 // ---------------------------------------------------------------- device-resident plant (plant_kernels.hip)
+// the record of ilqr_hip_plant_set_score before the first scored interval: sums and count zero, minimum height +inf (empty while no score is installed)
+static std::vector<double> empty_score(const ilqr_hip_ctx* c) {
+  std::vector<double> r(c->score_on ? (size_t)c->B * ILQR_PLANT_SCORE_TERMS : 0, 0.0);
+  for (size_t i = 6; i < r.size(); i += ILQR_PLANT_SCORE_TERMS) r[i] = std::numeric_limits<double>::infinity();
+  return r;
+}
+// Scores the `count` ring rows the plant kernel just enqueued fills (from ring row row0 on, against the reference rows knot0 + j), directly
+// behind it on the handle's stream: the score kernels see the reference buffers that kernel saw.  Their problem descriptor is the handle's
+// with the scoring weights in the place of the shared ones and no weight-set table.
+static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
+  h1::ProblemDev Ps = c->P;
+  std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
+  Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
+  Ps.wsets = nullptr; Ps.wsets_stride = 0;
+  ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
+}
 int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   if (!c || !x) return ILQR_ERR_ARG;
   enter(c);
@@ -1264,6 +1287,8 @@ int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   HIPCHK(c, hipMemcpyAsync(c->plant.alive, ones.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->plant.u, 0, B * ILQR_NU * sizeof(double), c->stream));
   HIPCHK(c, hipMemsetAsync(c->plant.stance, 0, B * 2 * sizeof(int), c->stream));
+  const std::vector<double> empty = empty_score(c);      // (outlives the copy: the synchronisation below)
+  if (c->score_on) HIPCHK(c, hipMemcpyAsync(c->d_score, empty.data(), empty.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's buffers are free on return)
   c->plant_set = true; c->plant_kick = false; c->hist_n = 0;
   return ILQR_OK;
@@ -1293,10 +1318,12 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   if (geom) {      // (the contact mode or the family may have changed since plant_configure)
     if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
+  if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
   h1::DynParams dyn = c->P.dyn;      // the plant: the model's parameters at the physics step (main/humanoid_mpc.cpp:99,128)
   dyn.h = c->P.dyn.h / c->plant_substeps;
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, (geom && dyn.contact != 0) ? 1 : 0, c->plant_substeps, c->plant_feedback, c->plant_kick ? 1 : 0, row, c->stream);
+  if (c->score_on) enqueue_score(c, row, 0, 1);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
   if (row >= 0) c->hist_n += 1;
@@ -1324,11 +1351,16 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
   if (geom) {      // (as ilqr_hip_plant_advance)
     if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
+  if (c->score_on && count > c->hist_cap) {
+    c->err = "plant_follow with a score installed: " + std::to_string(count) + " intervals exceed the history ring's " + std::to_string(c->hist_cap) + " rows (the score kernels read the ring's rows)";
+    return ILQR_ERR_STATE;
+  }
   h1::DynParams dyn = c->P.dyn;
   dyn.h = c->P.dyn.h / c->plant_substeps;
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, (geom && dyn.contact != 0) ? 1 : 0, c->plant_substeps, c->plant_feedback, c->plant_kick ? 1 : 0, first_knot, count,
                             row0, c->hist_cap, c->stream);
+  if (c->score_on) enqueue_score(c, row0, first_knot, count);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
   if (c->hist_cap > 0) c->hist_n += count;
@@ -1387,6 +1419,48 @@ PLANT_GETTER(ilqr_hip_plant_get_alive, alive, c->B, int)
 int ilqr_hip_plant_state_device(ilqr_hip_ctx* c, const double** x_device) {
   if (!c || !x_device) return ILQR_ERR_ARG;
   *x_device = c->plant.x;
+  return ILQR_OK;
+}
+// ---- closed-loop score of the plant (plant_score_kernels.hip)
+int ilqr_hip_plant_set_score(ilqr_hip_ctx* c, const double* Q_diag, const double* R_diag, double w_upright, double w_balance, double w_joint_limits, double w_control_limits) {
+  if (!c || !Q_diag || !R_diag) return ILQR_ERR_ARG;
+  const double w[4] = {w_upright, w_balance, w_joint_limits, w_control_limits};
+  for (double v : w) if (!(v >= 0.0) || !std::isfinite(v)) return ILQR_ERR_ARG;
+  for (int i = 0; i < ILQR_NX; ++i) if (!(Q_diag[i] >= 0.0) || !std::isfinite(Q_diag[i])) return ILQR_ERR_ARG;
+  for (int i = 0; i < ILQR_NU; ++i) if (!(R_diag[i] >= 0.0) || !std::isfinite(R_diag[i])) return ILQR_ERR_ARG;
+  enter(c);
+  const size_t rec = (size_t)c->B * ILQR_PLANT_SCORE_TERMS;
+  if (!c->d_score) HIPCHK(c, hipMalloc((void**)&c->d_score, rec * sizeof(double)));
+  if (!c->d_score_terms) HIPCHK(c, hipMalloc((void**)&c->d_score_terms, (size_t)c->N * rec * sizeof(double)));
+  std::memcpy(c->score_Q, Q_diag, sizeof(c->score_Q)); std::memcpy(c->score_R, R_diag, sizeof(c->score_R)); std::memcpy(c->score_w, w, sizeof(c->score_w));
+  c->score_on = true;
+  const std::vector<double> empty = empty_score(c);
+  // (on the stream: behind the score kernels of a plant call still in flight, which then scored under the weights of their own call)
+  HIPCHK(c, hipMemcpyAsync(c->d_score, empty.data(), rec * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_clear_score(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (score kernels in flight still write the buffers)
+  if (c->d_score) hipFree(c->d_score);
+  if (c->d_score_terms) hipFree(c->d_score_terms);
+  c->d_score = c->d_score_terms = nullptr; c->score_on = false;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_get_score(ilqr_hip_ctx* c, double* score) {
+  if (!c || !score) return ILQR_ERR_ARG;
+  if (!c->score_on) return ILQR_ERR_STATE;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(score, c->d_score, (size_t)c->B * ILQR_PLANT_SCORE_TERMS * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_score_device(ilqr_hip_ctx* c, const double** score_device) {
+  if (!c || !score_device) return ILQR_ERR_ARG;
+  if (!c->score_on) return ILQR_ERR_STATE;
+  *score_device = c->d_score;
   return ILQR_OK;
 }
 int ilqr_hip_get_iterations_enqueued(const ilqr_hip_ctx* c) { return c ? c->iterations_enqueued : -1; }

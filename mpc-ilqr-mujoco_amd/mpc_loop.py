@@ -32,6 +32,12 @@ the start of each `run`; the warm start shifts by the number of intervals applie
 set_problem -> initialize_warm_from_plant(shift=m) -> solve(None) -> plant_follow(0, m), t_idx += m; a kick is supported before the first
 interval of a group only.  Host path: compute_control(x, knot=j) and today's plant step per interval, the stance taken from row j of the
 group's window.  The logs keep one main row per plant interval, the solve cost and time repeated over the group.
+
+`MPCRunner(..., resident=True, score={...})` installs the closed-loop score of the plant (BatchedILQR.plant_set_score; the dict holds its
+arguments) before the plant is reset: every plant call then adds the cost terms of its intervals, under the score's own weights, to a
+record per rollout on the device, and `runner.score()` returns it [B, 8] after `run`.  `history_rows=r` sizes the history ring to r rows
+instead of the whole run (r >= solve_every: a plant call must fit); `run` then returns the last min(r, steps) states and controls the ring
+still holds -- with a score, a run of any length is judged without keeping its history.
 """
 import os
 import time
@@ -75,13 +81,19 @@ class MPCRunner:
     """Batched closed loop: `solver` = BatchedILQR, `refs` = ReferenceData, `base_problem` = weights etc. (scenario.make_problem)."""
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
-                 resident=False, substeps=1, feedback_mode=0, solve_every=1):
+                 resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
             raise ValueError("substeps / feedback_mode need the device-resident plant (resident=True)")
         if int(solve_every) < 1 or (int(solve_every) > 1 and int(solve_every) > solver.N - 1):
             raise ValueError("solve_every must be in 1 .. N - 1")
+        if not resident and (score is not None or history_rows is not None):
+            raise ValueError("score / history_rows need the device-resident plant (resident=True)")
+        if history_rows is not None and int(history_rows) < int(solve_every):
+            raise ValueError("history_rows must be at least solve_every (the ring holds the intervals of one plant call)")
+        self.score_args = None if score is None else dict(score)
+        self.history_rows = None if history_rows is None else int(history_rows)
         self.resident, self.substeps, self.feedback_mode = bool(resident), int(substeps), int(feedback_mode)
         self.solve_every, self.since_solve = int(solve_every), 1      # since_solve: plant intervals applied since the last solve (the next warm start's shift)
         self.s, self.refs, self.base = solver, refs, base_problem
@@ -208,7 +220,9 @@ class MPCRunner:
         if off:
             raise ValueError("resident plant: a kick is supported before the first interval of a group only (solve_every = %d, kicks at %s)" % (m, off))
         s.plant_configure(self.substeps, self.feedback_mode, self.plant_contacts)
-        s.plant_set_history(steps)
+        s.plant_set_history(steps if self.history_rows is None else self.history_rows)
+        if self.score_args is not None:
+            s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)
         s.plant_reset(x0)                                    # the only upload of a state (besides the cold start's x0)
         rows = []                                            # per plant interval: (cost, ms, x_ref_j, u_ref_j, x_opt_j, u_opt_j)
         for k in range(0, steps, m):
@@ -251,10 +265,18 @@ class MPCRunner:
         hx, hu = s.plant_history()                           # ONE download for the whole run
         xs = np.concatenate([hx, s.plant_state()[None]], axis=0)
         t_first = self.t_idx - steps
+        gone = steps - len(hx)                               # intervals a ring of history_rows < steps has overwritten: not logged
         for k, (cost, ms, xr0, ur0, xo0, uo0) in enumerate(rows):
             for b, lg in self.logs.items():
-                lg.log(t_first + k + 1, cost[b], ms, hx[k, b], hu[k, b], xr0, ur0, xo0[b], uo0[b])
+                if k >= gone:
+                    lg.log(t_first + k + 1, cost[b], ms, hx[k - gone, b], hu[k - gone, b], xr0, ur0, xo0[b], uo0[b])
         return xs, hu
+
+    def score(self):
+        """The closed-loop score record [B, 8] of the last `run` (columns solver.PLANT_SCORE_TERMS); needs MPCRunner(..., score=...)."""
+        if self.score_args is None:
+            raise ValueError("no score was asked for (MPCRunner(..., resident=True, score={...}))")
+        return self.s.plant_score()
 
     def close(self):
         for lg in self.logs.values():

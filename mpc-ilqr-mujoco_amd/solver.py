@@ -44,7 +44,10 @@ EXPORTS = [
     "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
     "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts",
+    "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
 ]
+# slots of the closed-loop score record (include/ilqr_hip.h ILQR_PLANT_SCORE_TERMS)
+PLANT_SCORE_TERMS = ("state", "control", "upright", "balance", "joint_limits", "control_limits", "min_pelvis_height", "intervals")
 
 
 
@@ -557,6 +560,23 @@ class BatchedILQR:
         p = C.c_void_p()
         self._chk(self.L.ilqr_hip_plant_state_device(self.h, C.byref(p)))
         return p.value
+
+    def plant_set_score(self, Q, R, upright=0.0, balance=0.0, joint_limits=0.0, control_limits=0.0):
+        """Install the closed-loop score (ilqr_hip_plant_set_score): from now on every plant_advance / plant_follow adds the cost terms of its
+        intervals, under THESE weights (Q [51], R [19] diagonals and the four scalars; independent of the solver's), to a record per rollout.
+        Empties the record.  The history ring must hold at least the intervals of the largest plant call."""
+        Q, R = _c64(Q), _c64(R)
+        if Q.shape != (NX,) or R.shape != (NU,):
+            raise ValueError("score weights: Q [51], R [19]")
+        self._chk(self.L.ilqr_hip_plant_set_score(self.h, _p(Q), _p(R), *[C.c_double(float(v)) for v in (upright, balance, joint_limits, control_limits)]))
+
+    def plant_clear_score(self):
+        """Remove the score: the plant calls launch what they launch without it."""
+        self._chk(self.L.ilqr_hip_plant_clear_score(self.h))
+
+    def plant_score(self):
+        """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""
+        return self._get("ilqr_hip_plant_get_score", (self.B, len(PLANT_SCORE_TERMS)))
 
     def enable_profiling(self, on=True):
         self._chk(self.L.ilqr_hip_enable_profiling(self.h, int(bool(on))))
