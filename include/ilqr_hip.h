@@ -284,9 +284,12 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* ctx, int* stance);
    the handle has just solved -- the first knot (xbar_0, ubar_0, K_0) of "nominal trajectories + TV-LQR gains" (include/ilqr/ilqr.hpp:10-16).
    The plant is the model's dynamics (contact mode, friction, joint-limit rows, gravity of the handle) at the step dt / substeps.  Per MPC
    step:  set references / schedule -> ilqr_hip_initialize_warm_from_plant -> ilqr_hip_solve(ctx, NULL, cost) -> ilqr_hip_plant_advance;
-   the solve's own synchronisation is the only one.  Solving every m-th interval only: ilqr_hip_initialize_warm_from_plant_shifted(ctx, m)
-   -> ilqr_hip_solve -> ilqr_hip_plant_follow(ctx, 0, m), see there.  Not provided: external wrenches, a contact model other than the
-   solver's. */
+   the solve's own synchronisation is the only one, provided the references do not change: the three reference setters upload and
+   synchronise.  With a reference track on the device (ilqr_hip_set_reference_track, below) the order of MPC step k is
+   ilqr_hip_window_from_track(ctx, k, follow_schedule) -> ilqr_hip_initialize_warm_from_plant -> ilqr_hip_solve(ctx, NULL, cost) ->
+   ilqr_hip_plant_advance, and the solve's own synchronisation is the only one of the step for a moving reference too.  Solving every
+   m-th interval only: ilqr_hip_initialize_warm_from_plant_shifted(ctx, m) -> ilqr_hip_solve -> ilqr_hip_plant_follow(ctx, 0, m), see
+   there.  Not provided: external wrenches, a contact model other than the solver's. */
 /* Upload the plant state x[B][51] (robot.getState's counterpart in reverse: RobotUtils::setState).  Every rollout becomes alive, a pending
    kick is dropped, the history cursor returns to 0.  Synchronises the handle's stream. */
 int ilqr_hip_plant_reset(ilqr_hip_ctx* ctx, const double* x /*[B][51]*/);
@@ -378,6 +381,44 @@ int ilqr_hip_plant_set_score(ilqr_hip_ctx* ctx, const double* Q_diag /*[51]*/, c
 int ilqr_hip_plant_clear_score(ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_get_score(ilqr_hip_ctx* ctx, double* score /*[B][8]*/);
 int ilqr_hip_plant_score_device(ilqr_hip_ctx* ctx, const double** score_device);
+
+/* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
+   arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout
+   that is the largest host crossing of a resident step.  Here the full-length arrays are uploaded ONCE, one start row per rollout lives
+   on the device, and one kernel per step writes every window into the buffers the three reference setters fill.
+   set_reference_track: the arrays of RobotUtils::loadReferences / loadContactSchedule (src/common/robot_utils.cpp:281-492) --
+   x_ref_full_, u_ref_full_ (NULL: zeros), com_ref_full_, ee_ref_full_ (left, right ankle), com_vel_ref_full_ (NULL: zeros) with `rows`
+   rows each, contact_schedule_ with `contact_rows` rows, which may differ from `rows` (NULL: no table).  The handle owns a device copy:
+   one upload, one synchronisation of the handle's stream.  rows < 1, contact_rows < 0 or a null required pointer: ILQR_ERR_ARG.  A second
+   call replaces the track.  The start rows become one shared start of 0.
+   clear_reference_track: frees the track; the windows last written stay installed.
+   reference_track_rows: 0 without a track, else its rows; -1 for a null handle. */
+int ilqr_hip_set_reference_track(ilqr_hip_ctx* ctx, int rows, const double* x_ref /*[rows][51]*/, const double* u_ref /*[rows][19], NULL: zeros*/,
+                                 const double* com_ref /*[rows][3]*/, const double* ee_ref /*[rows][2][3]*/, const double* com_vel_ref /*[rows][3], NULL: zeros*/,
+                                 const int* contact /*[contact_rows][2], NULL: none*/, int contact_rows);
+int ilqr_hip_clear_reference_track(ilqr_hip_ctx* ctx);
+int ilqr_hip_reference_track_rows(const ilqr_hip_ctx* ctx);
+/* One start row per set, start[n_sets], n_sets 1 or the batch (else ILQR_ERR_ARG); every start >= 0 (else ILQR_ERR_ARG).  Kept on the
+   device; their maximum is kept on the host for the range check of the window call.  Synchronises the handle's stream.  ILQR_ERR_STATE
+   without a track. */
+int ilqr_hip_set_track_starts(ilqr_hip_ctx* ctx, const int* start, int n_sets);
+/* The windows of MPC step `step` >= 0 (else ILQR_ERR_ARG), for every set b with s = start[b] + step (one shared start: one window, read
+   by every rollout), t = 0 .. N:
+     x_ref, u_ref (t < N), com_ref     row min(s + t, rows - 1)     RobotUtils::getReferenceWindow's end clamp, robot_utils.cpp:422-443
+     ee_ref, com_vel_ref, stance       row r = (follow_schedule ? s : 0) + t: the horizon-local index the reference's solver uses
+                                       (ilqr.cpp:703,729-734,767-791), or the advancing one
+     stance flag                       contact[r][foot] == 1; 1 where r >= contact_rows or no table was given (isStance, :494-504)
+   getEEReference / getCoMVelReference have no clamp and throw past the end (:525-549): ILQR_ERR_ARG when the largest r of any set would
+   reach `rows`, checked on the host from the stored maximum start before anything is launched (the kernel clamps every row index it
+   forms as well).  ENQUEUES one kernel on the handle's stream: no upload, no synchronisation.  A pure copy: the windows are bit for bit
+   what the three reference setters would have uploaded, and afterwards the handle is in the state they leave (set strides, references
+   set); a later setter simply overwrites what this wrote.  ILQR_ERR_STATE without a track.  No reference counterpart for the batch:
+   the reference holds one trajectory. */
+int ilqr_hip_window_from_track(ilqr_hip_ctx* ctx, int step, int follow_schedule);
+/* The reference windows the solver currently reads, whoever wrote them (a setter or the track), expanded to one per rollout whatever the
+   set strides are; every pointer may be NULL.  Synchronises the handle's stream. */
+int ilqr_hip_get_reference_windows(ilqr_hip_ctx* ctx, double* x_ref /*[B][N+1][51]*/, double* u_ref /*[B][N][19]*/, double* com_ref /*[B][N+1][3]*/,
+                                   double* ee_ref /*[B][N+1][2][3]*/, double* com_vel_ref /*[B][N+1][3]*/, int* stance /*[B][N+1][2]*/);
 
 /* per-stage device time of the last solve in milliseconds, keyed like the reference's profiler
    (src/ilqr/ilqr.cpp:537-639): 0 computeCost/rollout, 1 linearization, 2 costQuadratics, 3 backwardPass,

@@ -188,6 +188,13 @@ class iLQR {
   }
   void plantClearScore() { chk(ilqr_hip_plant_clear_score(ctx_)); }
   Vec plantScore() { Vec s((size_t)B_ * ILQR_PLANT_SCORE_TERMS); chk(ilqr_hip_plant_get_score(ctx_, s.data())); return s; }      // [batch][8]
+  // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
+  void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492
+  void clearReferenceTrack() { chk(ilqr_hip_clear_reference_track(ctx_)); }
+  int referenceTrackRows() const { return ilqr_hip_reference_track_rows(ctx_); }
+  void setTrackStarts(const std::vector<int>& start /*1 or batch*/) { chk(ilqr_hip_set_track_starts(ctx_, start.data(), (int)start.size())); }
+  void windowFromTrack(int step, bool follow_schedule = false) { chk(ilqr_hip_window_from_track(ctx_, step, follow_schedule ? 1 : 0)); }   // mpc.cpp:163-166, robot_utils.cpp:422-443; enqueues only
+  void getReferenceWindows(double* x_ref, double* u_ref, double* com_ref, double* ee_ref, double* com_vel_ref, int* stance) { chk(ilqr_hip_get_reference_windows(ctx_, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, stance)); }
 
  private:
   void chk(int rc) { if (rc != ILQR_OK) throw std::runtime_error(std::string("ilqr_hip: ") + ilqr_hip_last_error(ctx_)); }

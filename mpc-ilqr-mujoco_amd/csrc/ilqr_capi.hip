@@ -19,6 +19,7 @@
 #include "h1_host_model.h"
 #include "ilqr_kernels.h"
 #include "plant_score_kernels.h"
+#include "reference_track_kernels.h"
 
 using ilqr::DevState;
 
@@ -155,6 +156,12 @@ struct ilqr_hip_ctx {
   double *d_score = nullptr, *d_score_terms = nullptr;
   bool score_on = false;
   double score_Q[ILQR_NX] = {0}, score_R[ILQR_NU] = {0}, score_w[4] = {0};
+  // reference track (ilqr_hip_set_reference_track; reference_track_kernels.hip): ONE allocation [rows][51 | 19 | 3 | 6 | 3] doubles array by
+  // array, then [contact_rows][2] ints; the start rows [B] on the device (allocated with the first track) and their maximum here, for the
+  // range check of ilqr_hip_window_from_track
+  double* d_track = nullptr;
+  int* d_track_start = nullptr;
+  int track_rows = 0, track_contact_rows = 0, track_sets = 1, track_max_start = 0;
 };
 
 #define HIPCHK(ctx, call)                                                                   \
@@ -310,7 +317,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -411,6 +418,104 @@ int ilqr_hip_set_references(ilqr_hip_ctx* c, const double* x_ref, const double* 
   c->P.u_ref_stride = n_sets == 1 ? 0 : (long)(N * ILQR_NU);
   c->P.com_ref_stride = n_sets == 1 ? 0 : (long)((N + 1) * 3);
   c->refs_set = true;
+  return ILQR_OK;
+}
+
+// ---- reference windows from a track on the device (reference_track_kernels.hip)
+static const size_t TRACK_ROW = ILQR_NX + ILQR_NU + 3 + 6 + 3;      // doubles per row of the track, all five arrays
+static ilqr::TrackDev track_view(const ilqr_hip_ctx* c) {
+  const size_t T = c->track_rows;
+  ilqr::TrackDev t;
+  t.x = c->d_track; t.u = t.x + T * ILQR_NX; t.com = t.u + T * ILQR_NU; t.ee = t.com + T * 3; t.com_vel = t.ee + T * 6;
+  t.contact = c->track_contact_rows ? (const int*)(t.com_vel + T * 3) : nullptr;
+  t.rows = c->track_rows; t.contact_rows = c->track_contact_rows;
+  return t;
+}
+int ilqr_hip_set_reference_track(ilqr_hip_ctx* c, int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref,
+                                 const int* contact, int contact_rows) {
+  if (!c || rows < 1 || !x_ref || !com_ref || !ee_ref || contact_rows < 0) return ILQR_ERR_ARG;
+  if (!contact) contact_rows = 0;
+  enter(c);
+  const size_t T = rows, nd = T * TRACK_ROW, bytes = nd * sizeof(double) + (size_t)contact_rows * 2 * sizeof(int);
+  std::vector<double> host((bytes + sizeof(double) - 1) / sizeof(double), 0.0);      // (u_ref / com_vel_ref NULL: their rows stay zero)
+  double* p = host.data();
+  std::memcpy(p, x_ref, T * ILQR_NX * sizeof(double)); p += T * ILQR_NX;
+  if (u_ref) std::memcpy(p, u_ref, T * ILQR_NU * sizeof(double));
+  p += T * ILQR_NU;
+  std::memcpy(p, com_ref, T * 3 * sizeof(double)); p += T * 3;
+  std::memcpy(p, ee_ref, T * 6 * sizeof(double)); p += T * 6;
+  if (com_vel_ref) std::memcpy(p, com_vel_ref, T * 3 * sizeof(double));
+  p += T * 3;
+  if (contact_rows) std::memcpy(p, contact, (size_t)contact_rows * 2 * sizeof(int));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a window kernel in flight still reads the track this call replaces)
+  if (c->d_track) { hipFree(c->d_track); c->d_track = nullptr; c->track_rows = c->track_contact_rows = 0; }
+  if (!c->d_track_start) HIPCHK(c, hipMalloc((void**)&c->d_track_start, (size_t)c->B * sizeof(int)));
+  HIPCHK(c, hipMalloc((void**)&c->d_track, host.size() * sizeof(double)));
+  HIPCHK(c, hipMemcpyAsync(c->d_track, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_track_start, 0, (size_t)c->B * sizeof(int), c->stream));      // one shared start of 0
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->track_rows = rows; c->track_contact_rows = contact_rows; c->track_sets = 1; c->track_max_start = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_clear_reference_track(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a window kernel in flight still reads it)
+  if (c->d_track) hipFree(c->d_track);
+  c->d_track = nullptr; c->track_rows = c->track_contact_rows = 0; c->track_sets = 1; c->track_max_start = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_reference_track_rows(const ilqr_hip_ctx* c) { return c ? c->track_rows : -1; }
+int ilqr_hip_set_track_starts(ilqr_hip_ctx* c, const int* start, int n_sets) {
+  if (!c || !start || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  int mx = 0;
+  for (int b = 0; b < n_sets; ++b) { if (start[b] < 0) return ILQR_ERR_ARG; mx = start[b] > mx ? start[b] : mx; }
+  if (!c->d_track) { c->err = "set_track_starts without a reference track (ilqr_hip_set_reference_track)"; return ILQR_ERR_STATE; }
+  enter(c);
+  HIPCHK(c, hipMemcpyAsync(c->d_track_start, start, (size_t)n_sets * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->track_sets = n_sets; c->track_max_start = mx;
+  return ILQR_OK;
+}
+int ilqr_hip_window_from_track(ilqr_hip_ctx* c, int step, int follow_schedule) {
+  if (!c || step < 0) return ILQR_ERR_ARG;
+  if (!c->d_track) { c->err = "window_from_track without a reference track (ilqr_hip_set_reference_track)"; return ILQR_ERR_STATE; }
+  // ee_ref / com_vel_ref have no end clamp (robot_utils.cpp:525-549 throws): the largest row any set would read, from the stored maximum start
+  const long r_last = (follow_schedule ? (long)c->track_max_start + step : 0L) + c->N;
+  if (r_last >= c->track_rows) {
+    c->err = "window_from_track: foot / CoM-velocity reference row " + std::to_string(r_last) + " is beyond the track's " + std::to_string(c->track_rows) + " rows";
+    return ILQR_ERR_ARG;
+  }
+  enter(c);
+  const int n_sets = c->track_sets, sched_sets = follow_schedule ? n_sets : 1;
+  const ilqr::WindowDev W{c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance};
+  ilqr::launch_window_from_track(track_view(c), W, c->d_track_start, n_sets, sched_sets, step, follow_schedule ? 1 : 0, c->N, c->stream);
+  HIPCHK(c, hipGetLastError());
+  const long n1 = c->N + 1, per = n_sets == 1 ? 0 : 1, sper = sched_sets == 1 ? 0 : 1;
+  c->P.x_ref_stride = per * n1 * ILQR_NX; c->P.u_ref_stride = per * (long)c->N * ILQR_NU; c->P.com_ref_stride = per * n1 * 3;
+  c->P.ee_ref_stride = sper * n1 * 6; c->P.com_vel_ref_stride = sper * n1 * 3; c->P.stance_stride = sper * n1 * 2;
+  c->refs_set = true;
+  c->xbar_rolled = false;      // (contact mode: the schedule is part of the dynamics)
+  return ILQR_OK;      // asynchronous on the handle's stream
+}
+int ilqr_hip_get_reference_windows(ilqr_hip_ctx* c, double* x_ref, double* u_ref, double* com_ref, double* ee_ref, double* com_vel_ref, int* stance) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t B = c->B, N = c->N;
+  // one array: `per` elements per set; the device holds B sets (stride != 0) or one, the caller gets B
+  auto fetch = [&](void* out, const void* dev, size_t per_bytes, long stride) -> hipError_t {
+    if (!out) return hipSuccess;
+    hipError_t e = hipMemcpy(out, dev, per_bytes * (stride ? B : 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !stride) for (size_t b = 1; b < B; ++b) std::memcpy((char*)out + b * per_bytes, out, per_bytes);
+    return e;
+  };
+  HIPCHK(c, fetch(x_ref, c->d_xref, (N + 1) * ILQR_NX * sizeof(double), c->P.x_ref_stride));
+  HIPCHK(c, fetch(u_ref, c->d_uref, N * ILQR_NU * sizeof(double), c->P.u_ref_stride));
+  HIPCHK(c, fetch(com_ref, c->d_comref, (N + 1) * 3 * sizeof(double), c->P.com_ref_stride));
+  HIPCHK(c, fetch(ee_ref, c->d_eeref, (N + 1) * 6 * sizeof(double), c->P.ee_ref_stride));
+  HIPCHK(c, fetch(com_vel_ref, c->d_comvelref, (N + 1) * 3 * sizeof(double), c->P.com_vel_ref_stride));
+  HIPCHK(c, fetch(stance, c->d_stance, (N + 1) * 2 * sizeof(int), c->P.stance_stride));
   return ILQR_OK;
 }
 

@@ -38,6 +38,14 @@ arguments) before the plant is reset: every plant call then adds the cost terms 
 record per rollout on the device, and `runner.score()` returns it [B, 8] after `run`.  `history_rows=r` sizes the history ring to r rows
 instead of the whole run (r >= solve_every: a plant call must fit); `run` then returns the last min(r, steps) states and controls the ring
 still holds -- with a score, a run of any length is judged without keeping its history.
+
+`MPCRunner(..., resident=True, device_refs=True, track_starts=None)` cuts the reference windows on the device too: the first `run` sets the
+weights and gravity of `base_problem` and uploads the whole of `refs` as a track (BatchedILQR.set_reference_track) with one start row per
+rollout (`track_starts` [B]; None or one entry: one shared start, 0 by default), and every group calls
+`window_from_track(t_idx, follow_schedule)` where the host path calls problem_at + set_problem -- one kernel, nothing uploaded, no
+synchronisation; rollout b then tracks the rows from track_starts[b] + t_idx on (ReferenceData.problem_at_starts is the same rule on the
+host).  MPC_extractReference times the enqueue only.  The logged reference rows come from the host's copy of the rule, for the logged
+rollouts alone, and `last_stance0` from the host's contact table (rollout 0).
 """
 import os
 import time
@@ -81,7 +89,8 @@ class MPCRunner:
     """Batched closed loop: `solver` = BatchedILQR, `refs` = ReferenceData, `base_problem` = weights etc. (scenario.make_problem)."""
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
-                 resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None):
+                 resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
+                 device_refs=False, track_starts=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -92,6 +101,12 @@ class MPCRunner:
             raise ValueError("score / history_rows need the device-resident plant (resident=True)")
         if history_rows is not None and int(history_rows) < int(solve_every):
             raise ValueError("history_rows must be at least solve_every (the ring holds the intervals of one plant call)")
+        if not resident and (device_refs or track_starts is not None):
+            raise ValueError("device_refs / track_starts need the device-resident plant (resident=True)")
+        if track_starts is not None and not device_refs:
+            raise ValueError("track_starts need device_refs=True (the host path cuts one shared window, problem_at)")
+        self.device_refs, self.track_ready = bool(device_refs), False
+        self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
         self.history_rows = None if history_rows is None else int(history_rows)
         self.resident, self.substeps, self.feedback_mode = bool(resident), int(substeps), int(feedback_mode)
@@ -224,14 +239,28 @@ class MPCRunner:
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)
         s.plant_reset(x0)                                    # the only upload of a state (besides the cold start's x0)
+        if self.device_refs and not self.track_ready:        # once: weights and gravity, the track, the start rows
+            s.set_problem_constants(self.base)
+            s.set_reference_track(self.refs)
+            s.set_track_starts(self.track_starts)
+            self.track_ready = True
+        start_of = lambda b: int(self.track_starts[b if len(self.track_starts) > 1 else 0])
         rows = []                                            # per plant interval: (cost, ms, x_ref_j, u_ref_j, x_opt_j, u_opt_j)
         for k in range(0, steps, m):
             cnt = min(m, steps - k)                          # plant intervals of this group
             t0 = time.perf_counter()
-            prob = self.refs.problem_at(self.t_idx, s.N, self.base, follow_schedule=self.follow_schedule)
-            s.set_problem(prob)
+            t_solve = self.t_idx
+            if self.device_refs:
+                s.window_from_track(t_solve, self.follow_schedule)       # enqueued: nothing uploaded, no synchronisation
+            else:
+                prob = self.refs.problem_at(t_solve, s.N, self.base, follow_schedule=self.follow_schedule)
+                s.set_problem(prob)
             t1 = time.perf_counter(); self._add("MPC_extractReference", t0, t1)
-            self.last_stance0 = prob["stance"][0, 0]
+            if self.device_refs:
+                r0 = start_of(0) + t_solve if self.follow_schedule else 0
+                self.last_stance0 = np.array([1 if self.refs.is_stance(e, r0) else 0 for e in range(2)], dtype=np.int32)
+            else:
+                self.last_stance0 = prob["stance"][0, 0]
             if self.has_prev:
                 if self.since_solve == 1:
                     s.initialize_warm_from_plant()           # ilqr.cpp:68-80, x0 from the plant on the device
@@ -259,8 +288,15 @@ class MPCRunner:
             if self.logs:
                 xb, ub = s.xbar(), s.ubar()
                 ms = 1e3 * (time.perf_counter() - t0)
+                if self.device_refs:                         # the host's copy of the rule, for the logged rollouts only
+                    logged = list(self.logs)
+                    lp = self.refs.problem_at_starts([start_of(b) for b in logged], t_solve, s.N, self.base, follow_schedule=self.follow_schedule)
                 for j in range(cnt):
-                    rows.append((self.last_cost.copy(), ms, prob["x_ref"][0, j].copy(), prob["u_ref"][0, j].copy(), xb[:, j].copy(), ub[:, j].copy()))
+                    if self.device_refs:
+                        xr, ur = ({b: lp[key][i, j].copy() for i, b in enumerate(logged)} for key in ("x_ref", "u_ref"))
+                    else:
+                        xr, ur = prob["x_ref"][0, j].copy(), prob["u_ref"][0, j].copy()
+                    rows.append((self.last_cost.copy(), ms, xr, ur, xb[:, j].copy(), ub[:, j].copy()))
             self._add("MPC_stepOnce", t0, time.perf_counter())
         hx, hu = s.plant_history()                           # ONE download for the whole run
         xs = np.concatenate([hx, s.plant_state()[None]], axis=0)
@@ -269,7 +305,8 @@ class MPCRunner:
         for k, (cost, ms, xr0, ur0, xo0, uo0) in enumerate(rows):
             for b, lg in self.logs.items():
                 if k >= gone:
-                    lg.log(t_first + k + 1, cost[b], ms, hx[k - gone, b], hu[k - gone, b], xr0, ur0, xo0[b], uo0[b])
+                    lg.log(t_first + k + 1, cost[b], ms, hx[k - gone, b], hu[k - gone, b], xr0[b] if isinstance(xr0, dict) else xr0, ur0[b] if isinstance(ur0, dict) else ur0,
+                           xo0[b], uo0[b])
         return xs, hu
 
     def score(self):

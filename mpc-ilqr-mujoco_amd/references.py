@@ -182,3 +182,30 @@ class ReferenceData:
                     stance=np.array([[1 if self.is_stance(e, s0 + t) else 0 for e in range(2)] for t in range(N + 1)], dtype=np.int32)[None],
                     ee_ref=self._rows(self.ee_ref, s0, N)[None].copy(), com_vel_ref=self._rows(self.com_vel_ref, s0, N)[None].copy())
         return prob
+
+    def problem_at_starts(self, starts, step, N, base_problem, follow_schedule=False):
+        """`problem_at(starts[b] + step, ...)` for every rollout b at once: the six reference items stacked on a leading axis of
+        len(starts) (one set when `starts` has one entry).  The host statement of the rule the device applies to a track
+        (BatchedILQR.window_from_track, include/ilqr_hip.h ilqr_hip_window_from_track): x_ref / u_ref / com_ref from the rows
+        min(s + t, T - 1), s = starts[b] + step; ee_ref / com_vel_ref / stance from the rows (s if follow_schedule else 0) + t.
+        IndexError where the C call returns ILQR_ERR_ARG: a negative start or step, a foot / CoM-velocity row beyond the loaded rows."""
+        st = np.atleast_1d(np.asarray(starts)).astype(np.int64)
+        if st.ndim != 1 or st.size == 0:
+            raise ValueError("starts must hold one entry, or one per rollout")
+        step = int(step)
+        if step < 0 or (st < 0).any():
+            raise IndexError("negative start row or step")
+        T = self.x_ref.shape[0]
+        t = np.arange(N + 1, dtype=np.int64)
+        s = st + step
+        idx = np.minimum(s[:, None] + t[None, :], T - 1)                       # getReferenceWindow's end clamp
+        r = (s if follow_schedule else np.zeros_like(s))[:, None] + t[None, :]   # horizon-local (Appendix D #3) or advancing
+        if int(r.max()) >= min(self.ee_ref.shape[0], self.com_vel_ref.shape[0]):
+            raise IndexError("reference index %d beyond the %d loaded rows" % (int(r.max()), min(self.ee_ref.shape[0], self.com_vel_ref.shape[0])))
+        stance = np.ones(r.shape + (2,), dtype=np.int32)                         # isStance: out of range -> stance
+        inside, cols = r < self.contact.shape[0], min(2, self.contact.shape[1])
+        stance[inside, :cols] = self.contact[r[inside], :cols] == 1
+        prob = dict(base_problem)
+        prob.update(N=N, x_ref=self.x_ref[idx], u_ref=self.u_ref[idx[:, :N]], com_ref=self.com_ref[idx], stance=stance,
+                    ee_ref=self.ee_ref[r], com_vel_ref=self.com_vel_ref[r])
+        return prob

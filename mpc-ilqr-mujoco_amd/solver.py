@@ -45,7 +45,11 @@ EXPORTS = [
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
     "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts",
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
+    "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
+    "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
 ]
+# the items of a problem dict that are reference windows (one set, or one per rollout)
+REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
 # slots of the closed-loop score record (include/ilqr_hip.h ILQR_PLANT_SCORE_TERMS)
 PLANT_SCORE_TERMS = ("state", "control", "upright", "balance", "joint_limits", "control_limits", "min_pelvis_height", "intervals")
 
@@ -200,6 +204,16 @@ class BatchedILQR:
     # ---- problem data (RobotUtils setters)
     def set_problem(self, prob):
         L, h = self.L, self.h
+        self.set_problem_constants(prob)
+        st = np.ascontiguousarray(prob["stance"], dtype=np.int32)
+        self._chk(L.ilqr_hip_set_contact_schedule(h, st.ctypes.data_as(_ip), int(st.shape[0])))
+        ee, cv = _c64(prob["ee_ref"]), _c64(prob["com_vel_ref"])
+        self._chk(L.ilqr_hip_set_ee_references(h, _p(ee), _p(cv), int(ee.shape[0])))
+        self.set_references(prob["x_ref"], prob["u_ref"], prob["com_ref"])
+
+    def set_problem_constants(self, prob):
+        """The items of a problem dict that are not reference windows: weights (or per-rollout weight sets) and gravity."""
+        L, h = self.L, self.h
         sets = weight_sets_of(prob, self.B)
         if sets is not None:
             # per-rollout weights: the table carries every weight (shared items broadcast); the shared setters keep what they hold
@@ -213,11 +227,6 @@ class BatchedILQR:
         g = prob["gravity"]
         self.gravity = np.array(g, dtype=np.float64)
         self._chk(L.ilqr_hip_set_gravity(h, C.c_double(g[0]), C.c_double(g[1]), C.c_double(g[2])))
-        st = np.ascontiguousarray(prob["stance"], dtype=np.int32)
-        self._chk(L.ilqr_hip_set_contact_schedule(h, st.ctypes.data_as(_ip), int(st.shape[0])))
-        ee, cv = _c64(prob["ee_ref"]), _c64(prob["com_vel_ref"])
-        self._chk(L.ilqr_hip_set_ee_references(h, _p(ee), _p(cv), int(ee.shape[0])))
-        self.set_references(prob["x_ref"], prob["u_ref"], prob["com_ref"])
 
     def set_weight_sets(self, Q, R, Qf, task_weights, constraint_weights):
         """One set of cost weights per rollout (ilqr_hip_set_weight_sets): Q [n,51], R [n,19], Qf [n,51], task_weights [n,6] in the order of
@@ -242,6 +251,48 @@ class BatchedILQR:
         if x_ref.shape[1:] != (self.N + 1, NX) or u_ref.shape[1:] != (self.N, NU) or com_ref.shape[1:] != (self.N + 1, 3):
             raise ILQRError("reference size mismatch")  # iLQR::solve returns false (ilqr.cpp:526-532)
         self._chk(self.L.ilqr_hip_set_references(self.h, _p(x_ref), _p(u_ref), _p(com_ref), int(x_ref.shape[0])))
+
+    # ---- reference windows from a track on the device (include/ilqr_hip.h "reference windows from a track")
+    def set_reference_track(self, refdata):
+        """Upload the full-length arrays of a references.ReferenceData (x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact) once; the start
+        rows become one shared start of 0.  A second call replaces the track."""
+        x, u, com, ee, cv = (_c64(a) for a in (refdata.x_ref, refdata.u_ref, refdata.com_ref, refdata.ee_ref, refdata.com_vel_ref))
+        T = x.shape[0]
+        if x.shape != (T, NX) or u.shape != (T, NU) or com.shape != (T, 3) or ee.shape != (T, 2, 3) or cv.shape != (T, 3):
+            raise ValueError("reference track: x_ref [T,51], u_ref [T,19], com_ref [T,3], ee_ref [T,2,3], com_vel_ref [T,3] with one T")
+        ct = np.ascontiguousarray(refdata.contact, dtype=np.int32)
+        if ct.shape[0] and ct.shape[1:] != (2,):
+            raise ValueError("reference track: contact [Tc,2]")
+        self._chk(self.L.ilqr_hip_set_reference_track(self.h, int(T), _p(x), _p(u), _p(com), _p(ee), _p(cv), ct.ctypes.data_as(_ip) if ct.shape[0] else None, int(ct.shape[0])))
+
+    def clear_reference_track(self):
+        """Free the track; the windows last written stay installed."""
+        self._chk(self.L.ilqr_hip_clear_reference_track(self.h))
+
+    def reference_track_rows(self):
+        """0 without a track, else its rows."""
+        return int(self.L.ilqr_hip_reference_track_rows(self.h))
+
+    def set_track_starts(self, starts):
+        """One start row of the track per rollout (B entries) or one shared start (one entry); every start >= 0."""
+        st = np.ascontiguousarray(np.atleast_1d(starts), dtype=np.int32)
+        if st.ndim != 1:
+            raise ValueError("starts must be one-dimensional (one entry, or one per rollout)")
+        self._chk(self.L.ilqr_hip_set_track_starts(self.h, st.ctypes.data_as(_ip), int(st.shape[0])))
+
+    def window_from_track(self, step, follow_schedule=False):
+        """Enqueue the kernel that writes the reference windows of MPC step `step` (rollout b: track rows from start[b] + step on, the rule
+        of ReferenceData.problem_at_starts) into the buffers the solver reads; uploads nothing and does not synchronise."""
+        self._chk(self.L.ilqr_hip_window_from_track(self.h, int(step), int(bool(follow_schedule))))
+
+    def reference_windows(self):
+        """The reference windows the solver currently reads, one per rollout whoever wrote them: a dict with the six keys REFERENCE_KEYS."""
+        B, n1 = self.B, self.N + 1
+        out = dict(x_ref=np.zeros((B, n1, NX)), u_ref=np.zeros((B, self.N, NU)), com_ref=np.zeros((B, n1, 3)), ee_ref=np.zeros((B, n1, 2, 3)),
+                   com_vel_ref=np.zeros((B, n1, 3)), stance=np.zeros((B, n1, 2), dtype=np.int32))
+        self._chk(self.L.ilqr_hip_get_reference_windows(self.h, _p(out["x_ref"]), _p(out["u_ref"]), _p(out["com_ref"]), _p(out["ee_ref"]), _p(out["com_vel_ref"]),
+                                                        out["stance"].ctypes.data_as(_ip)))
+        return out
 
     # ---- options (ilqr.hpp:22-24)
     def set_regularization(self, lam):

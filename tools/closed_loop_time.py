@@ -6,7 +6,15 @@ Ten fixed iterations per solve (no convergence exit), standing scenario.  --subs
 (the host path has neither: its figure stays the one-step, held-control loop).  --solve-every M goes to both runners: a solve before every
 M-th plant interval, the policy followed in between; the timed run is lengthened to the next multiple of M intervals (whole groups), and
 the figures stay milliseconds per PLANT interval.  --score installs the closed-loop score on the resident runner (the problem's own Q, R and
-unit weights on the four scalar terms; the two score kernels then run behind every plant call).  Prints one JSON line; not part of bench.py."""
+unit weights on the four scalar terms; the two score kernels then run behind every plant call).  Prints one JSON line; not part of bench.py.
+
+   python tools/closed_loop_time.py --device-refs [--per-rollout-starts] [--contact-mode 2] ...
+compares, instead, two ways of giving the RESIDENT runner a moving reference, alternating on one box: (a) the windows of every step cut
+on the host (ReferenceData.problem_at_starts) and uploaded through the three reference setters, (b) the windows cut on the device from a
+track uploaded once (MPCRunner(device_refs=True)).  The track is the 200 walking rows of tests/golden/refdata_golden.npz prepared as
+scenario.walking_batch prepares them, on the advancing schedule; one shared start of 0, or with --per-rollout-starts one start per
+rollout drawn so that start + steps + horizon < 200.  Also reports the time the host spends in MPC_extractReference per step on either
+path and the duration of the window kernel alone (events on the handle's stream around 50 launches) beside the bytes it writes."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py): behind the product library, torch finds "no HIP GPUs" when it is asked for the device name
@@ -26,12 +34,17 @@ def main():
     ap.add_argument("--steps", type=int, default=6); ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--substeps", type=int, default=1); ap.add_argument("--feedback-mode", type=int, default=0, choices=(0, 1))
     ap.add_argument("--solve-every", type=int, default=1); ap.add_argument("--score", action="store_true")
+    ap.add_argument("--device-refs", action="store_true"); ap.add_argument("--per-rollout-starts", action="store_true"); ap.add_argument("--contact-mode", type=int, default=2)
     a = ap.parse_args()
+    if a.per_rollout_starts and not a.device_refs:
+        ap.error("--per-rollout-starts needs --device-refs")
     pkg = load_package()
     from mpc_ilqr_mujoco_amd import mpc_loop as ml, references as rf, solver as sv
     sc = pkg.scenario
     B, N = a.batch, a.horizon
     a.steps = -(-a.steps // a.solve_every) * a.solve_every      # whole groups
+    if a.device_refs:
+        return device_refs_main(a, sc, ml, rf, sv)
     base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
     rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
     rows = a.steps + N + 10
@@ -56,6 +69,69 @@ def main():
                       "resident_substeps": a.substeps, "resident_feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "score": bool(a.score),
                       "ms_per_step_host_plant": float(np.median(ms[False])), "ms_per_step_resident_plant": float(np.median(ms[True])),
                       "samples_host": ms[False], "samples_resident": ms[True]}))
+
+
+class HostWindows:
+    """the parent's path for per-rollout windows: problem_at for MPCRunner, cut by problem_at_starts on the host"""
+
+    def __init__(self, rd, starts):
+        self.rd, self.starts = rd, starts
+
+    def problem_at(self, t0, N, base, follow_schedule=False):
+        return self.rd.problem_at_starts(self.starts, t0, N, base, follow_schedule=follow_schedule)
+
+
+def device_refs_main(a, sc, ml, rf, sv):
+    B, N = a.batch, a.horizon
+    r = np.load(os.path.join(ROOT, "tests", "golden", "refdata_golden.npz"))
+    q_mj = rf.pinocchio_to_mujoco(r["walking_pin_rows"])
+    rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
+    rd.set_states(np.concatenate([q_mj, rf.differentiate_positions(q_mj, float(r["dt"]))], axis=1)); rd.contact = rf.contact_schedule(q_mj, sv.foot_clearance)
+    T = rd.x_ref.shape[0]
+    total = 1 + a.steps                                   # the cold step and the timed ones run on one step counter
+    if total + N >= T:
+        raise SystemExit("steps + horizon must stay below the track's %d rows" % T)
+    rng = np.random.default_rng(0)
+    starts = rng.integers(0, T - N - total, size=B) if a.per_rollout_starts else np.zeros(1, dtype=np.int64)
+    base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -1.0))
+    x0 = rd.x_ref[np.broadcast_to(starts, (B,))].copy()      # scenario.walking_batch's initial states
+    x0[:, 7:26] += rng.uniform(-0.02, 0.02, (B, 19)); x0[:, 0:3] += rng.uniform(-0.01, 0.01, (B, 3)); x0[:, 26:] *= 0.5
+    ui = np.tile(sv.gravity_compensation(sc.standing_state(), base["gravity"]), (B, N, 1)) + rng.uniform(-0.5, 0.5, (B, N, 19))
+    ms, extract = {False: [], True: []}, {False: [], True: []}
+    kernel_us = []
+    for rnd in range(a.rounds + 1):                      # round 0 warms up (first launches, allocations)
+        for dev in (False, True):
+            s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False); s.set_contact_mode(a.contact_mode)
+            kw = dict(follow_schedule=True, resident=True, substeps=a.substeps, feedback_mode=a.feedback_mode, solve_every=a.solve_every)
+            run = ml.MPCRunner(s, rd, base, device_refs=True, track_starts=starts, **kw) if dev else ml.MPCRunner(s, HostWindows(rd, starts), base, **kw)
+            run.run(x0, 1, u_init=ui)                    # the cold start is not what is compared: every timed step is a warm one
+            s.synchronize()
+            run.prof.clear()
+            t0 = time.perf_counter()
+            run.run(x0, a.steps, u_init=ui)
+            dt = time.perf_counter() - t0
+            if rnd:
+                ms[dev].append(1e3 * dt / a.steps); extract[dev].append(float(np.median(run.prof["MPC_extractReference"])))
+            if dev and rnd == a.rounds:                  # the kernel alone, on the handle's stream
+                st = torch.cuda.ExternalStream(s.stream)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                for rep_ in range(3):
+                    e0.record(st)
+                    for _ in range(50):
+                        s.window_from_track(1, True)
+                    e1.record(st); e1.synchronize()
+                    kernel_us.append(1e3 * e0.elapsed_time(e1) / 50)
+            s.close()
+    n1, sets = N + 1, len(starts)
+    nbytes = sets * ((n1 * 51 + N * 19 + n1 * 3) * 8 + n1 * 9 * 8 + n1 * 2 * 4)
+    k_us = float(np.median(kernel_us))
+    print(json.dumps({"tool": "closed_loop_time", "mode": "device_refs", "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "iterations": a.iters, "steps": a.steps,
+                      "contact_mode": a.contact_mode, "substeps": a.substeps, "solve_every": a.solve_every, "per_rollout_starts": bool(a.per_rollout_starts), "track_rows": int(T),
+                      "ms_per_step_host_windows": float(np.median(ms[False])), "ms_per_step_device_windows": float(np.median(ms[True])),
+                      "samples_host_windows": ms[False], "samples_device_windows": ms[True],
+                      "extract_reference_ms_host_windows": float(np.median(extract[False])), "extract_reference_ms_device_windows": float(np.median(extract[True])),
+                      "window_bytes_per_step": int(nbytes), "window_kernel_us": k_us, "window_kernel_samples_us": kernel_us,
+                      "window_kernel_fraction_of_6TBps": float(nbytes / (k_us * 1e-6) / 6e12)}))
 
 
 if __name__ == "__main__":
