@@ -381,6 +381,35 @@ int ilqr_hip_plant_set_score(ilqr_hip_ctx* ctx, const double* Q_diag /*[51]*/, c
 int ilqr_hip_plant_clear_score(ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_get_score(ilqr_hip_ctx* ctx, double* score /*[B][8]*/);
 int ilqr_hip_plant_score_device(ilqr_hip_ctx* ctx, const double** score_device);
+/* ---- the plant's own model and one parameter set per rollout: closed loops in which the plant is NOT the solver's model.  By default the
+   plant steps with the handle's dynamics -- a loop in which the model is perfect; the reference's plant, mj_step, is not its solver's model
+   either (main/humanoid_mpc.cpp:99-118 builds the two separately).  Both calls below change what ilqr_hip_plant_advance / _follow step
+   with and nothing else: rollout, line search, Jacobians and warm-start tail keep the solver's model, and the solver's setters
+   (ilqr_hip_set_gravity, ilqr_hip_set_friction, ilqr_hip_set_contact_mode, ...) keep acting on the solve (and on a plant that follows it).
+   plant_set_model: the discrete part, shared by all rollouts.  contact_mode -1 (follow the solver's, the default) or 0..4
+   (ILQR_CONTACT_*); joint_limits -1 (follow), 0 or 1; anything else ILQR_ERR_ARG.  The plant kernels then run in the instantiation of
+   that pair; schedule row and stance source act as before, on the plant's mode.  The refusal of the stance source GEOMETRY (contact mode
+   1; scalar family) is evaluated against the plant's effective mode, here, in ilqr_hip_plant_configure and in the launching calls
+   (ILQR_ERR_UNSUPPORTED).  Launches nothing.
+   plant_set_params: the continuous part, ILQR_PLANT_PARAMS doubles per set --
+     0..2 gravity   3 friction coefficient mu (acts in plant contact modes 3 and 4)   4 contact softness (modes 1-4)
+     5 joint-limit stiffness (with the plant's joint-limit rows on)   6 torque gain
+   -- n_sets = 1 (one set that every rollout reads) or the batch (rollout b steps with set b), else ILQR_ERR_ARG; ILQR_ERR_ARG also for a
+   null pointer, a non-finite entry, mu < 0, softness <= 0, limit_stiffness < 0 or torque_gain < 0.  While a table is installed the set
+   replaces gravity, friction, softness and stiffness of the handle in the plant's step; the step size stays dt / substeps.  The torque
+   gain is an actuator mismatch: the step receives gain * u, with u the control law's output behind its non-finite guard (main:162-165),
+   and clamps to the control range as before; the REPORTED control (ilqr_hip_plant_get_control, the history ring, hence the score) stays
+   the law's output, unscaled, as it is unclamped.  The table is a device buffer of 64-byte records owned by the handle; the call uploads
+   it and synchronises the handle's stream.  It survives ilqr_hip_plant_reset and ilqr_hip_plant_configure.
+   plant_clear_params: frees it; the plant calls then launch exactly what they launch without it.
+   plant_num_param_sets: 0 without a table, else n_sets; -1 for a null handle.
+   plant_get_params: params[B][7], the values the plant would step rollout b with now -- without a table the handle's and gain 1. */
+#define ILQR_PLANT_PARAMS 7   /* gx, gy, gz, mu, softness, limit_stiffness, torque_gain */
+int ilqr_hip_plant_set_model(ilqr_hip_ctx* ctx, int contact_mode, int joint_limits);
+int ilqr_hip_plant_set_params(ilqr_hip_ctx* ctx, const double* params /*[n_sets][7]*/, int n_sets);
+int ilqr_hip_plant_clear_params(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_num_param_sets(const ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_params(ilqr_hip_ctx* ctx, double* params /*[B][7]*/);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

@@ -188,6 +188,14 @@ class iLQR {
   }
   void plantClearScore() { chk(ilqr_hip_plant_clear_score(ctx_)); }
   Vec plantScore() { Vec s((size_t)B_ * ILQR_PLANT_SCORE_TERMS); chk(ilqr_hip_plant_get_score(ctx_, s.data())); return s; }      // [batch][8]
+  // the plant's own model and parameter sets (ilqr_hip.h ilqr_hip_plant_set_model): a plant that is not the solver's model; -1 follows the solver
+  void plantSetModel(int contact_mode = -1, int joint_limits = -1) { chk(ilqr_hip_plant_set_model(ctx_, contact_mode, joint_limits)); }
+  void plantSetParams(const Vec& params /*[n_sets][7]: gx, gy, gz, mu, softness, limit_stiffness, torque_gain*/, int n_sets) {
+    if (n_sets < 1 || params.size() != (size_t)n_sets * ILQR_PLANT_PARAMS) throw std::runtime_error("params must hold n_sets * 7 doubles");
+    chk(ilqr_hip_plant_set_params(ctx_, params.data(), n_sets));
+  }
+  void plantClearParams() { chk(ilqr_hip_plant_clear_params(ctx_)); }
+  Vec plantParams() { Vec p((size_t)B_ * ILQR_PLANT_PARAMS); chk(ilqr_hip_plant_get_params(ctx_, p.data())); return p; }          // [batch][7], effective
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492
   void clearReferenceTrack() { chk(ilqr_hip_clear_reference_track(ctx_)); }

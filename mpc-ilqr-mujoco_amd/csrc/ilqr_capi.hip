@@ -149,6 +149,11 @@ struct ilqr_hip_ctx {
   bool solved = false;        // a solve has been enqueued: the first knot of xbar / ubar / K is a policy
   bool plant_kick = false;    // plant.dv holds a kick for the next advance
   int plant_substeps = 1, plant_feedback = 0, plant_source = ILQR_STANCE_SCHEDULE;
+  // the plant's own model (ilqr_hip_plant_set_model): -1 follows the solver's contact mode / joint-limit option, else the plant's
+  int plant_mode = -1, plant_limits = -1;
+  // plant parameter table (ilqr_hip_plant_set_params; plant_kernels.hip k_plant_follow_p): [n][8] doubles, n = 1 or B; null: none
+  double* d_pparams = nullptr;
+  int pparams_sets = 0;
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
   // closed-loop score of the plant (ilqr_hip_plant_set_score; plant_score_kernels.hip): the record [B][8], the term rows of one plant call
@@ -317,7 +322,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1383,6 +1388,35 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
   Ps.wsets = nullptr; Ps.wsets_stride = 0;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
 }
+// The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and
+// joint-limit option where ilqr_hip_plant_set_model has given it one.  (With a parameter table the kernels replace g, mu, soft and lim_k per rollout.)
+static h1::DynParams plant_dyn(const ilqr_hip_ctx* c) {
+  h1::DynParams dyn = c->P.dyn;
+  dyn.h = c->P.dyn.h / c->plant_substeps;
+  if (c->plant_mode >= 0) dyn.contact = c->plant_mode;
+  if (c->plant_limits >= 0) dyn.limits = c->plant_limits;
+  return dyn;
+}
+// geometry_refusal for the plant: against the contact mode the plant would step with
+static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode) {
+  if (!plan_of(c).stance_geometry) return "the stance source GEOMETRY exists on the two-lane kernels only; unset ILQR_DYN=s";
+  if ((plant_mode >= 0 ? plant_mode : c->P.dyn.contact) == ILQR_CONTACT_RIGID_STANCE) return "plant contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4";
+  return nullptr;
+}
+// The plant kernel of one call: without a table exactly the launch without the feature; with one, the followed kernel with the table's
+// records -- for an advance over the one interval (0, 1), which is an advance bit for bit.  row: the advance's ring row (-1: no ring) or the
+// follow's first ring row.
+static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
+  const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
+  if (c->d_pparams) {
+    const ilqr::PlantTable T{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1};
+    ilqr::launch_plant_follow_params(c->S, c->plant, dyn, T, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, c->hist_cap, c->stream);
+  } else if (follow) {
+    ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row, c->hist_cap, c->stream);
+  } else {
+    ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, row, c->stream);
+  }
+}
 int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   if (!c || !x) return ILQR_ERR_ARG;
   enter(c);
@@ -1402,7 +1436,7 @@ int ilqr_hip_plant_configure(ilqr_hip_ctx* c, int substeps, int feedback_mode, i
   if (!c || substeps < 1 || (feedback_mode != 0 && feedback_mode != 1) || (contact_source != ILQR_STANCE_SCHEDULE && contact_source != ILQR_STANCE_GEOMETRY)) return ILQR_ERR_ARG;
   enter(c);
   if (contact_source == ILQR_STANCE_GEOMETRY) {
-    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+    if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
   c->plant_substeps = substeps; c->plant_feedback = feedback_mode; c->plant_source = contact_source;
   return ILQR_OK;
@@ -1421,13 +1455,12 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   TRY(enter_launching(c));
   const bool geom = c->plant_source == ILQR_STANCE_GEOMETRY;
   if (geom) {      // (the contact mode or the family may have changed since plant_configure)
-    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+    if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
-  h1::DynParams dyn = c->P.dyn;      // the plant: the model's parameters at the physics step (main/humanoid_mpc.cpp:99,128)
-  dyn.h = c->P.dyn.h / c->plant_substeps;
+  const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
-  ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, (geom && dyn.contact != 0) ? 1 : 0, c->plant_substeps, c->plant_feedback, c->plant_kick ? 1 : 0, row, c->stream);
+  enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
   if (c->score_on) enqueue_score(c, row, 0, 1);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
@@ -1454,17 +1487,15 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
   TRY(enter_launching(c));
   const bool geom = c->plant_source == ILQR_STANCE_GEOMETRY;
   if (geom) {      // (as ilqr_hip_plant_advance)
-    if (const char* why = geometry_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+    if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
   if (c->score_on && count > c->hist_cap) {
     c->err = "plant_follow with a score installed: " + std::to_string(count) + " intervals exceed the history ring's " + std::to_string(c->hist_cap) + " rows (the score kernels read the ring's rows)";
     return ILQR_ERR_STATE;
   }
-  h1::DynParams dyn = c->P.dyn;
-  dyn.h = c->P.dyn.h / c->plant_substeps;
+  const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
-  ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, (geom && dyn.contact != 0) ? 1 : 0, c->plant_substeps, c->plant_feedback, c->plant_kick ? 1 : 0, first_knot, count,
-                            row0, c->hist_cap, c->stream);
+  enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
   if (c->score_on) enqueue_score(c, row0, first_knot, count);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
@@ -1524,6 +1555,64 @@ PLANT_GETTER(ilqr_hip_plant_get_alive, alive, c->B, int)
 int ilqr_hip_plant_state_device(ilqr_hip_ctx* c, const double** x_device) {
   if (!c || !x_device) return ILQR_ERR_ARG;
   *x_device = c->plant.x;
+  return ILQR_OK;
+}
+// ---- the plant's own model and its parameter sets (plant_kernels.hip k_plant_follow_p)
+int ilqr_hip_plant_set_model(ilqr_hip_ctx* c, int contact_mode, int joint_limits) {
+  if (!c || contact_mode < -1 || contact_mode > ILQR_CONTACT_KINETIC_FRICTION_STANCE || joint_limits < -1 || joint_limits > 1) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->plant_source == ILQR_STANCE_GEOMETRY) {
+    if (const char* why = plant_geometry_refusal(c, contact_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  }
+  c->plant_mode = contact_mode; c->plant_limits = joint_limits;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_set_params(ilqr_hip_ctx* c, const double* params, int n_sets) {
+  if (!c || !params || n_sets < 1 || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  constexpr int P = ILQR_PLANT_PARAMS, REC = ILQR_PLANT_PARAMS + 1;
+  for (size_t i = 0; i < (size_t)n_sets * P; ++i) if (!std::isfinite(params[i])) return ILQR_ERR_ARG;
+  for (int s = 0; s < n_sets; ++s) {
+    const double* r = params + (size_t)s * P;
+    if (r[3] < 0.0 || !(r[4] > 0.0) || r[5] < 0.0 || r[6] < 0.0) return ILQR_ERR_ARG;
+  }
+  enter(c);
+  std::vector<double> rec((size_t)n_sets * REC, 0.0);      // (64-byte records: the seven values and one double of padding)
+  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * REC, params + (size_t)s * P, P * sizeof(double));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (c->d_pparams && c->pparams_sets != n_sets) { hipFree(c->d_pparams); c->d_pparams = nullptr; c->pparams_sets = 0; }
+  if (!c->d_pparams) HIPCHK(c, hipMalloc((void**)&c->d_pparams, rec.size() * sizeof(double)));
+  c->pparams_sets = n_sets;
+  HIPCHK(c, hipMemcpyAsync(c->d_pparams, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_clear_params(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->d_pparams) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+    hipFree(c->d_pparams);
+  }
+  c->d_pparams = nullptr; c->pparams_sets = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_num_param_sets(const ilqr_hip_ctx* c) { return c ? c->pparams_sets : -1; }
+int ilqr_hip_plant_get_params(ilqr_hip_ctx* c, double* params) {
+  if (!c || !params) return ILQR_ERR_ARG;
+  enter(c);
+  constexpr int P = ILQR_PLANT_PARAMS, REC = ILQR_PLANT_PARAMS + 1;
+  if (!c->d_pparams) {
+    const h1::DynParams& d = c->P.dyn;
+    for (int b = 0; b < c->B; ++b) {
+      double* r = params + (size_t)b * P;
+      r[0] = d.g[0]; r[1] = d.g[1]; r[2] = d.g[2]; r[3] = d.mu; r[4] = d.soft; r[5] = d.lim_k; r[6] = 1.0;
+    }
+    return ILQR_OK;
+  }
+  std::vector<double> rec((size_t)c->pparams_sets * REC);
+  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pparams, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(params + (size_t)b * P, rec.data() + (size_t)(c->pparams_sets == 1 ? 0 : b) * REC, P * sizeof(double));
   return ILQR_OK;
 }
 // ---- closed-loop score of the plant (plant_score_kernels.hip)

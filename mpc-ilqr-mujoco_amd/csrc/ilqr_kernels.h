@@ -178,6 +178,16 @@ void launch_plant_advance(const DevState& S, const PlantDev& Pl, const h1::DynPa
 void launch_plant_follow(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
                          long hist_row0, long hist_cap, hipStream_t st);
 int plant_kernels_set_attr();
+// the same with a plant parameter table (ilqr_hip_plant_set_params): rollout b steps with record b * rec_stride of `records` -- g[3], mu,
+// soft, lim_k, torque gain, padding; 8 doubles -- in the place of those fields of dyn, and with gain * u.  rec_stride 8: one record per
+// rollout; 0: one record for all.  dyn still supplies h, the contact mode and the limits switch.  (first_knot, count) = (0, 1) is the
+// advance: with a table there is no kernel of its own for it.
+struct PlantTable {
+  const double* records;
+  int rec_stride;
+};
+void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const PlantTable& T, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode,
+                                int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

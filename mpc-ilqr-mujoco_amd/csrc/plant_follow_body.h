@@ -1,0 +1,117 @@
+// k_plant_follow of plant_kernels.hip, as source that file includes twice -- inside namespace ilqr, behind the helpers and layouts it uses:
+//   PLANT_TABLE 0  k_plant_follow: every rollout under the DynParams of the launch.  What the preprocessor leaves of this file is then the
+//                  text the kernel has always had: the fast path keeps its machine code.
+//   PLANT_TABLE 1  k_plant_follow_p: each rollout steps with its own record of a plant parameter table (ilqr_hip_plant_set_params) -- two
+//                  more kernel arguments, RPW more rows of LDS behind the layout, plant_step_table in the place of step_any.
+#ifndef PLANT_TABLE
+#error "define PLANT_TABLE (0 or 1) before including plant_follow_body.h"
+#endif
+#if PLANT_TABLE
+#define K_PLANT_FOLLOW k_plant_follow_p
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride
+#else
+#define K_PLANT_FOLLOW k_plant_follow
+#define PLANT_TABLE_PARAMS
+#endif
+template <int KIND, int FB>
+__global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, DynParams dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, int k0, int count,
+                                                     long hist_row0, long hist_cap PLANT_TABLE_PARAMS) {
+  extern __shared__ double lds[];
+  typedef FollowLayout<FB> Lay;
+  constexpr int n = PLANT_NX, m = PLANT_NU, RPW = Lay::RPW;
+  const int tid = threadIdx.x;
+  const int pr = tid >> 1;
+  const bool side = (tid & 1) != 0;
+  const int b0 = blockIdx.x * RPW;
+  const bool owner = pr < RPW && b0 + pr < S.B;      // (lane pairs stay together: every flag below is the same on both lanes of a pair)
+  const int b = owner ? b0 + pr : S.B - 1;
+  const int N = S.N;
+  h1s::HalfX h; h1s::load_half(side, Pl.x + (size_t)b * n, h);
+  bool run = owner && Pl.alive[b] != 0;      // alive, as the advances would hand it from one to the next
+  bool moved = false;                        // an interval of this launch ran to its end: state and stance are written back
+  int st[2] = {1, 1}, st_done[2] = {1, 1};
+  h1s::HalfU u;
+#if PLANT_TABLE
+  stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
+#endif
+  for (int j = 0; j < count; ++j) {
+    const int kt = k0 + j;
+    const long hist_row = hist_cap > 0 ? (hist_row0 + j) % hist_cap : -1L;
+    wave_lds_fence();      // (the previous interval is done with its policy rows and has stored its last state)
+    // ---- knot kt of the policy -> LDS, consecutive lanes on consecutive doubles
+    for (int r = 0; r < RPW; ++r) {
+      const int br = b0 + r < S.B ? b0 + r : S.B - 1;
+      const double* xb = S.xbar + ((size_t)br * (N + 1) + kt) * n;
+      const double* ub = S.ubar + ((size_t)br * N + kt) * m;
+      if (tid < n) lds[Lay::Base::XB + r * n + tid] = xb[tid];
+      if (tid < m) lds[Lay::UB + r * m + tid] = ub[tid];
+      if constexpr (FB != 0) {
+        const double* Kt = S.K + ((size_t)br * N + kt) * m * n;
+        for (int e = tid; e < m * n; e += 64) lds[Lay::KS + r * m * n + e] = Kt[e];
+      }
+    }
+    // ---- the state this interval starts from, kick, the guards of main:134-137
+    const bool was_alive = run;
+    if (j > 0 && was_alive) h1s::load_half(side, lds + Lay::XS + pr * n, h);
+    if (j == 0 && kick && was_alive) kick_half(side, h, Pl.dv + (size_t)b * H1_NV);
+    bool fin = finite_half(h);
+    fin = h1s::xch_flag(fin) && fin;
+    run = was_alive && fin;
+    if (owner && hist_row >= 0) h1s::store_half(side, h, Pl.hist_x + ((size_t)hist_row * S.B + b) * n);      // x the control law sees (after the kick); a frozen rollout logs the state it stopped in
+    if (pr < RPW) h1s::store_half(side, h, lds + Lay::XS + pr * n);
+    if (owner) { st[0] = sched[b * sched_stride + 2 * kt]; st[1] = sched[b * sched_stride + 2 * kt + 1]; }
+    for (int k = 0; k < substeps; ++k) {
+      // the lane index is opaque per substep, as in k_plant_advance (see there what it costs to lose it)
+      int lane = tid; asm volatile("" : "+v"(lane));
+      const bool side_t = (lane & 1) != 0;
+      const int prt = lane >> 1;
+      if (FB != 0 || k == 0) {
+        wave_lds_fence();
+        control_law<FB>(S, lds, b0, kt);
+        wave_lds_fence();
+      }
+      if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
+      const int pc = prt < RPW ? prt : 0;
+      load_half_u(side_t, lds + Lay::US + pc * m, u);
+      bool ufin = finite_half_u(u);
+      ufin = h1s::xch_flag(ufin) && ufin;
+      if (!ufin) zero_half_u(u);      // main:162-165
+      wave_lds_fence();      // (the odd lane reads the shared coordinates its partner stored at the end of the previous substep)
+      if (run) {
+        const h1s::LaneLds L{lds, 64, lane};
+        h1s::load_half(side_t, lds + Lay::XS + prt * n, h);
+        if constexpr (KIND >= 1 && KIND <= 4) {
+          if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
+        }
+#if PLANT_TABLE
+        plant_step_table<KIND>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC);
+#else
+        step_any<KIND>(side_t, h, u, dyn, st, L, geom);
+#endif
+        wave_lds_fence();
+        h1s::store_half(side_t, h, lds + Lay::XS + prt * n);
+      }
+    }
+    // ---- end of the interval: a rollout whose state is or became non-finite keeps the state it had, reports zero control and never runs again
+    fin = finite_half(h);
+    fin = h1s::xch_flag(fin) && fin;
+    run = run && fin;
+    if (!run) zero_half_u(u);
+    if (owner && hist_row >= 0) store_half_u(side, u, Pl.hist_u + ((size_t)hist_row * S.B + b) * m);
+    if (run) { moved = true; st_done[0] = st[0]; st_done[1] = st[1]; }
+    else if (was_alive) {      // frozen in this interval: back to what the advance would have left in Pl.x
+      if (j == 0) h1s::load_half(side, Pl.x + (size_t)b * n, h);
+      else h1s::load_half(side, lds + Lay::XK + pr * n, h);
+    }
+  }
+  if (!owner) return;
+  store_half_u(side, u, Pl.u + (size_t)b * m);
+  if (moved) {
+    h1s::store_half(side, h, Pl.x + (size_t)b * n);
+    if (!side) { Pl.stance[2 * (size_t)b] = st_done[0]; Pl.stance[2 * (size_t)b + 1] = st_done[1]; }
+  }
+  if (!side) Pl.alive[b] = run ? 1 : 0;
+}
+#undef K_PLANT_FOLLOW
+#undef PLANT_TABLE_PARAMS
+#undef PLANT_TABLE

@@ -7,7 +7,8 @@
 //                    solves every count-th interval only; the reference itself solves every step): the state stays in LDS / registers
 //                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
-// A translation unit of its own: no kernel of the solve shares a compilation with it.
+// A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
+// twice: without and with a plant parameter table (k_plant_follow_p).
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -205,106 +206,55 @@ DEVFN void zero_half_u(h1s::HalfU& u) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) u.uA[q] = 0.0;
 }
-template <int KIND, int FB>
-__global__ void __launch_bounds__(64) k_plant_follow(DevState S, PlantDev Pl, DynParams dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, int k0, int count,
-                                                     long hist_row0, long hist_cap) {
-  extern __shared__ double lds[];
-  typedef FollowLayout<FB> Lay;
-  constexpr int n = PLANT_NX, m = PLANT_NU, RPW = Lay::RPW;
-  const int tid = threadIdx.x;
-  const int pr = tid >> 1;
-  const bool side = (tid & 1) != 0;
-  const int b0 = blockIdx.x * RPW;
-  const bool owner = pr < RPW && b0 + pr < S.B;      // (lane pairs stay together: every flag below is the same on both lanes of a pair)
-  const int b = owner ? b0 + pr : S.B - 1;
-  const int N = S.N;
-  h1s::HalfX h; h1s::load_half(side, Pl.x + (size_t)b * n, h);
-  bool run = owner && Pl.alive[b] != 0;      // alive, as the advances would hand it from one to the next
-  bool moved = false;                        // an interval of this launch ran to its end: state and stance are written back
-  int st[2] = {1, 1}, st_done[2] = {1, 1};
-  h1s::HalfU u;
-  for (int j = 0; j < count; ++j) {
-    const int kt = k0 + j;
-    const long hist_row = hist_cap > 0 ? (hist_row0 + j) % hist_cap : -1L;
-    wave_lds_fence();      // (the previous interval is done with its policy rows and has stored its last state)
-    // ---- knot kt of the policy -> LDS, consecutive lanes on consecutive doubles
-    for (int r = 0; r < RPW; ++r) {
-      const int br = b0 + r < S.B ? b0 + r : S.B - 1;
-      const double* xb = S.xbar + ((size_t)br * (N + 1) + kt) * n;
-      const double* ub = S.ubar + ((size_t)br * N + kt) * m;
-      if (tid < n) lds[Lay::Base::XB + r * n + tid] = xb[tid];
-      if (tid < m) lds[Lay::UB + r * m + tid] = ub[tid];
-      if constexpr (FB != 0) {
-        const double* Kt = S.K + ((size_t)br * N + kt) * m * n;
-        for (int e = tid; e < m * n; e += 64) lds[Lay::KS + r * m * n + e] = Kt[e];
-      }
-    }
-    // ---- the state this interval starts from, kick, the guards of main:134-137
-    const bool was_alive = run;
-    if (j > 0 && was_alive) h1s::load_half(side, lds + Lay::XS + pr * n, h);
-    if (j == 0 && kick && was_alive) kick_half(side, h, Pl.dv + (size_t)b * H1_NV);
-    bool fin = finite_half(h);
-    fin = h1s::xch_flag(fin) && fin;
-    run = was_alive && fin;
-    if (owner && hist_row >= 0) h1s::store_half(side, h, Pl.hist_x + ((size_t)hist_row * S.B + b) * n);      // x the control law sees (after the kick); a frozen rollout logs the state it stopped in
-    if (pr < RPW) h1s::store_half(side, h, lds + Lay::XS + pr * n);
-    if (owner) { st[0] = sched[b * sched_stride + 2 * kt]; st[1] = sched[b * sched_stride + 2 * kt + 1]; }
-    for (int k = 0; k < substeps; ++k) {
-      // the lane index is opaque per substep, as in k_plant_advance (see there what it costs to lose it)
-      int lane = tid; asm volatile("" : "+v"(lane));
-      const bool side_t = (lane & 1) != 0;
-      const int prt = lane >> 1;
-      if (FB != 0 || k == 0) {
-        wave_lds_fence();
-        control_law<FB>(S, lds, b0, kt);
-        wave_lds_fence();
-      }
-      if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
-      const int pc = prt < RPW ? prt : 0;
-      load_half_u(side_t, lds + Lay::US + pc * m, u);
-      bool ufin = finite_half_u(u);
-      ufin = h1s::xch_flag(ufin) && ufin;
-      if (!ufin) zero_half_u(u);      // main:162-165
-      wave_lds_fence();      // (the odd lane reads the shared coordinates its partner stored at the end of the previous substep)
-      if (run) {
-        const h1s::LaneLds L{lds, 64, lane};
-        h1s::load_half(side_t, lds + Lay::XS + prt * n, h);
-        if constexpr (KIND >= 1 && KIND <= 4) {
-          if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
-        }
-        step_any<KIND>(side_t, h, u, dyn, st, L, geom);
-        wave_lds_fence();
-        h1s::store_half(side_t, h, lds + Lay::XS + prt * n);
-      }
-    }
-    // ---- end of the interval: a rollout whose state is or became non-finite keeps the state it had, reports zero control and never runs again
-    fin = finite_half(h);
-    fin = h1s::xch_flag(fin) && fin;
-    run = run && fin;
-    if (!run) zero_half_u(u);
-    if (owner && hist_row >= 0) store_half_u(side, u, Pl.hist_u + ((size_t)hist_row * S.B + b) * m);
-    if (run) { moved = true; st_done[0] = st[0]; st_done[1] = st[1]; }
-    else if (was_alive) {      // frozen in this interval: back to what the advance would have left in Pl.x
-      if (j == 0) h1s::load_half(side, Pl.x + (size_t)b * n, h);
-      else h1s::load_half(side, lds + Lay::XK + pr * n, h);
-    }
+#define PLANT_TABLE 0
+#include "plant_follow_body.h"
+
+// ---- plant parameter table (include/ilqr_hip.h ilqr_hip_plant_set_params): k_plant_follow_p.  One record of PLANT_REC doubles per rollout
+// -- g[3], mu, soft, lim_k, torque gain, one double of padding (64 B) -- or ONE record that every rollout reads (rec_stride = 0).  The wave
+// stages the records of its RPW rollouts in LDS once, behind the layout of the kernel: RPW x 8 consecutive doubles of the table,
+// consecutive lanes on consecutive doubles (2 KB at FB = 0, 256 B at FB = 1).  Each substep reads its seven values from there behind the
+// opaque lane index, right before the step: nothing of the record is live across the control law or from one substep to the next.
+// There is no k_plant_advance_p: with a table an advance is the followed kernel over one interval, which is an advance bit for bit
+// (GPU tests of plant_follow); a second family of twelve kernels would be a further 0.5 MB of code for a path that is not the fast one.
+#define PLANT_REC 8
+template <int RPW>
+DEVFN void stage_plant_records(const DevState& S, double* rows, int b0, const double* ptab, int rec_stride) {
+  for (int e = threadIdx.x; e < RPW * PLANT_REC; e += 64) {
+    const int r = e / PLANT_REC;
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;      // (a wave's unowned rows read the last rollout's record, as they read its policy)
+    rows[e] = ptab[(size_t)br * rec_stride + (e - r * PLANT_REC)];
   }
-  if (!owner) return;
-  store_half_u(side, u, Pl.u + (size_t)b * m);
-  if (moved) {
-    h1s::store_half(side, h, Pl.x + (size_t)b * n);
-    if (!side) { Pl.stance[2 * (size_t)b] = st_done[0]; Pl.stance[2 * (size_t)b + 1] = st_done[1]; }
-  }
-  if (!side) Pl.alive[b] = run ? 1 : 0;
 }
+// one plant step with the record `rec` in the place of g, mu, soft and lim_k of `dyn` (h stays the kernel argument: wave-uniform, as the
+// inlined steps need it behind their "+s" constraint) and gain * u in the place of u -- behind the non-finite guard, in front of the
+// step's clamp; the caller's u, which is what it reports, stays the law's output
+template <int KIND>
+DEVFN void plant_step_table(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L, int geom, const double* rec) {
+  DynParams dl = dyn;
+  dl.g[0] = rec[0]; dl.g[1] = rec[1]; dl.g[2] = rec[2]; dl.mu = rec[3]; dl.soft = rec[4]; dl.lim_k = rec[5];
+  const double gain = rec[6];
+  h1s::HalfU us;
+  us.u11 = gain * u.u11;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) us.uL[q] = gain * u.uL[q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) us.uA[q] = gain * u.uA[q];
+  step_any<KIND>(side, h, us, dl, st, L, geom);
+}
+#define PLANT_TABLE 1
+#include "plant_follow_body.h"
 
 template <int KIND, int FB> static int plant_attr() {
   return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess ||
          hipFuncSetAttribute((const void*)k_plant_follow<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FollowLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
 }
+template <int FB> static constexpr size_t follow_lds_p() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC) * sizeof(double); }
+template <int KIND, int FB> static int plant_attr_p() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_p<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_p<FB>()) != hipSuccess;
+}
 int plant_kernels_set_attr() {
   int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr<K(), 0>(); rc |= plant_attr<K(), 1>(); });
+  for_each_step_kind([&](auto K) { rc |= plant_attr<K(), 0>(); rc |= plant_attr<K(), 1>(); rc |= plant_attr_p<K(), 0>(); rc |= plant_attr_p<K(), 1>(); });
   return rc;
 }
 template <int KIND, int FB>
@@ -334,6 +284,22 @@ void launch_plant_follow(const DevState& S, const PlantDev& Pl, const DynParams&
   with_step_kind(dyn, [&](auto K) {
     if (feedback_mode) follow_launch<K(), 1>(S, Pl, dyn, a, st);
     else follow_launch<K(), 0>(S, Pl, dyn, a, st);
+  });
+}
+
+template <int KIND, int FB>
+static void follow_launch_p(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_p<KIND, FB>), grid, dim3(64), follow_lds_p<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride);
+}
+void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode,
+                                int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st) {
+  const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (feedback_mode) follow_launch_p<K(), 1>(S, Pl, dyn, T, a, st);
+    else follow_launch_p<K(), 0>(S, Pl, dyn, T, a, st);
   });
 }
 

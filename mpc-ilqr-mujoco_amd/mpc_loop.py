@@ -46,6 +46,12 @@ rollout (`track_starts` [B]; None or one entry: one shared start, 0 by default),
 synchronisation; rollout b then tracks the rows from track_starts[b] + t_idx on (ReferenceData.problem_at_starts is the same rule on the
 host).  MPC_extractReference times the enqueue only.  The logged reference rows come from the host's copy of the rule, for the logged
 rollouts alone, and `last_stance0` from the host's contact table (rollout 0).
+
+`MPCRunner(..., resident=True, plant_model=(contact_mode, joint_limits), plant_params=P)` runs closed loops in which the plant is not the
+solver's model: `plant_model` gives the plant its own contact mode and joint-limit option (either None: the solver's;
+BatchedILQR.plant_set_model), `plant_params` [1, 7] or [B, 7] (scenario.stack_plant_params) its own gravity, friction, softness,
+joint-limit stiffness and torque gain, one set for all rollouts or one per rollout (BatchedILQR.plant_set_params).  Both are installed
+before the plant is reset and stay on the handle after the run; the solve keeps the solver's model throughout.
 """
 import os
 import time
@@ -90,7 +96,7 @@ class MPCRunner:
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
-                 device_refs=False, track_starts=None):
+                 device_refs=False, track_starts=None, plant_params=None, plant_model=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -105,6 +111,15 @@ class MPCRunner:
             raise ValueError("device_refs / track_starts need the device-resident plant (resident=True)")
         if track_starts is not None and not device_refs:
             raise ValueError("track_starts need device_refs=True (the host path cuts one shared window, problem_at)")
+        if not resident and (plant_params is not None or plant_model is not None):
+            raise ValueError("plant_params / plant_model need the device-resident plant (resident=True)")
+        if plant_model is not None and len(tuple(plant_model)) != 2:
+            raise ValueError("plant_model must be (contact_mode, joint_limits), either None to follow the solver")
+        if plant_params is not None:
+            plant_params = np.atleast_2d(np.asarray(plant_params, dtype=np.float64))
+            if plant_params.ndim != 2 or plant_params.shape[1] != 7 or plant_params.shape[0] not in (1, solver.B):
+                raise ValueError("plant_params must be [1, 7] or [B, 7] (scenario.stack_plant_params)")
+        self.plant_params, self.plant_model = plant_params, None if plant_model is None else tuple(plant_model)
         self.device_refs, self.track_ready = bool(device_refs), False
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
@@ -234,7 +249,11 @@ class MPCRunner:
         off = sorted(k for k in kicks if k % m != 0)
         if off:
             raise ValueError("resident plant: a kick is supported before the first interval of a group only (solve_every = %d, kicks at %s)" % (m, off))
+        if self.plant_model is not None:
+            s.plant_set_model(*self.plant_model)             # (in front of plant_configure: the stance source is checked against the plant's mode)
         s.plant_configure(self.substeps, self.feedback_mode, self.plant_contacts)
+        if self.plant_params is not None:
+            s.plant_set_params(self.plant_params)
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)

@@ -93,6 +93,36 @@ def stack_weight_sets(problem, sets):
     return out
 
 
+# what a solver handle holds before any setter is called (ilqr_hip_create): gravity, friction coefficient, contact softness, joint-limit stiffness
+PLANT_PARAM_DEFAULTS = dict(gravity=(0.0, 0.0, -9.81), friction=1.0, softness=1e-5, limit_stiffness=0.0, torque_gain=1.0)
+
+
+def stack_plant_params(B, gravity=None, friction=None, softness=None, limit_stiffness=None, torque_gain=None):
+    """Plant parameter sets [B, 7] for BatchedILQR.plant_set_params / MPCRunner(plant_params=...): columns gravity x, y, z, friction
+    coefficient, contact softness, joint-limit stiffness, torque gain.  Each argument is one value for all rollouts (gravity: 3 values) or
+    one per rollout (gravity [B, 3], the others [B]); None is the handle's default (PLANT_PARAM_DEFAULTS).  Raises ValueError for a shape
+    that is neither, a non-finite entry, friction < 0, softness <= 0, limit_stiffness < 0 or torque_gain < 0."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    d = PLANT_PARAM_DEFAULTS
+    out = np.empty((B, 7))
+    g = np.asarray(d["gravity"] if gravity is None else gravity, dtype=np.float64)
+    if g.shape not in ((3,), (B, 3)):
+        raise ValueError("gravity must be [3] or [B, 3]")
+    out[:, 0:3] = g
+    for col, name, val in ((3, "friction", friction), (4, "softness", softness), (5, "limit_stiffness", limit_stiffness), (6, "torque_gain", torque_gain)):
+        v = np.asarray(d[name] if val is None else val, dtype=np.float64)
+        if v.shape not in ((), (B,)):
+            raise ValueError("%s must be a scalar or [B]" % name)
+        out[:, col] = v
+    if not np.isfinite(out).all():
+        raise ValueError("plant parameters must be finite")
+    if (out[:, 3] < 0).any() or (out[:, 4] <= 0).any() or (out[:, 5] < 0).any() or (out[:, 6] < 0).any():
+        raise ValueError("friction >= 0, softness > 0, limit_stiffness >= 0 and torque_gain >= 0 are required")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

@@ -47,11 +47,14 @@ EXPORTS = [
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
     "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
+    "ilqr_hip_plant_set_model", "ilqr_hip_plant_set_params", "ilqr_hip_plant_clear_params", "ilqr_hip_plant_num_param_sets", "ilqr_hip_plant_get_params",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
 # slots of the closed-loop score record (include/ilqr_hip.h ILQR_PLANT_SCORE_TERMS)
 PLANT_SCORE_TERMS = ("state", "control", "upright", "balance", "joint_limits", "control_limits", "min_pelvis_height", "intervals")
+# columns of a plant parameter set (include/ilqr_hip.h ILQR_PLANT_PARAMS)
+PLANT_PARAMS = ("gravity_x", "gravity_y", "gravity_z", "friction", "softness", "limit_stiffness", "torque_gain")
 
 
 
@@ -624,6 +627,36 @@ class BatchedILQR:
     def plant_clear_score(self):
         """Remove the score: the plant calls launch what they launch without it."""
         self._chk(self.L.ilqr_hip_plant_clear_score(self.h))
+
+    def plant_set_model(self, contact_mode=None, joint_limits=None):
+        """The plant's own contact mode (0..4) and joint-limit option (bool), each None to follow the solver's (the default): the plant kernels
+        step with that model, the solve keeps the solver's (ilqr_hip_plant_set_model).  Launches nothing."""
+        mode = -1 if contact_mode is None else int(contact_mode)
+        lim = -1 if joint_limits is None else int(bool(joint_limits))
+        if contact_mode is not None and not 0 <= mode <= 4:
+            raise ValueError("contact_mode must be None or 0..4")
+        self._chk(self.L.ilqr_hip_plant_set_model(self.h, mode, lim))
+
+    def plant_set_params(self, params):
+        """Install plant parameter sets [n_sets, 7] (columns PLANT_PARAMS; scenario.stack_plant_params builds them), n_sets 1 or B: rollout b's
+        plant steps with its own gravity, friction, softness, joint-limit stiffness and torque gain (ilqr_hip_plant_set_params)."""
+        params = _c64(params)
+        if params.ndim == 1:
+            params = params[None]
+        if params.ndim != 2 or params.shape[1] != len(PLANT_PARAMS) or params.shape[0] not in (1, self.B):
+            raise ValueError("plant parameters must be [1, 7] or [B, 7]")
+        self._chk(self.L.ilqr_hip_plant_set_params(self.h, _p(params), int(params.shape[0])))
+
+    def plant_clear_params(self):
+        """Remove the parameter sets: the plant steps every rollout with the handle's values again."""
+        self._chk(self.L.ilqr_hip_plant_clear_params(self.h))
+
+    def plant_num_param_sets(self):
+        return int(self.L.ilqr_hip_plant_num_param_sets(self.h))
+
+    def plant_params(self):
+        """[B, 7] (columns PLANT_PARAMS): the values the plant would step each rollout with now; without a table the handle's and gain 1."""
+        return self._get("ilqr_hip_plant_get_params", (self.B, len(PLANT_PARAMS)))
 
     def plant_score(self):
         """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""

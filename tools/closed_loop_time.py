@@ -14,7 +14,13 @@ on the host (ReferenceData.problem_at_starts) and uploaded through the three ref
 track uploaded once (MPCRunner(device_refs=True)).  The track is the 200 walking rows of tests/golden/refdata_golden.npz prepared as
 scenario.walking_batch prepares them, on the advancing schedule; one shared start of 0, or with --per-rollout-starts one start per
 rollout drawn so that start + steps + horizon < 200.  Also reports the time the host spends in MPC_extractReference per step on either
-path and the duration of the window kernel alone (events on the handle's stream around 50 launches) beside the bytes it writes."""
+path and the duration of the window kernel alone (events on the handle's stream around 50 launches) beside the bytes it writes.
+
+   python tools/closed_loop_time.py --plant-params {shared,per-rollout} [--solve-every M] ...
+compares, instead, the RESIDENT runner without a plant parameter table against the same runner with one installed
+(MPCRunner(plant_params=...): one set for all rollouts, or one per rollout with friction, softness, gravity and torque gain spread over the
+batch), alternating on one box, and times the plant kernel alone -- events on the handle's stream around 50 back-to-back plant_advance
+calls under one solve -- for the free plant and for plant contact mode 2 (ilqr_hip_plant_set_model), with and without the table."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py): behind the product library, torch finds "no HIP GPUs" when it is asked for the device name
@@ -34,6 +40,7 @@ def main():
     ap.add_argument("--steps", type=int, default=6); ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--substeps", type=int, default=1); ap.add_argument("--feedback-mode", type=int, default=0, choices=(0, 1))
     ap.add_argument("--solve-every", type=int, default=1); ap.add_argument("--score", action="store_true")
+    ap.add_argument("--plant-params", choices=("shared", "per-rollout"), default=None)
     ap.add_argument("--device-refs", action="store_true"); ap.add_argument("--per-rollout-starts", action="store_true"); ap.add_argument("--contact-mode", type=int, default=2)
     a = ap.parse_args()
     if a.per_rollout_starts and not a.device_refs:
@@ -45,6 +52,8 @@ def main():
     a.steps = -(-a.steps // a.solve_every) * a.solve_every      # whole groups
     if a.device_refs:
         return device_refs_main(a, sc, ml, rf, sv)
+    if a.plant_params:
+        return plant_params_main(a, sc, ml, rf, sv)
     base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
     rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
     rows = a.steps + N + 10
@@ -69,6 +78,61 @@ def main():
                       "resident_substeps": a.substeps, "resident_feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "score": bool(a.score),
                       "ms_per_step_host_plant": float(np.median(ms[False])), "ms_per_step_resident_plant": float(np.median(ms[True])),
                       "samples_host": ms[False], "samples_resident": ms[True]}))
+
+
+def plant_params_main(a, sc, ml, rf, sv):
+    B, N = a.batch, a.horizon
+    base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
+    rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
+    rows = a.steps + N + 10
+    rd.set_states(np.tile(sc.standing_state(), (rows, 1))); rd.contact = np.ones((rows, 2), dtype=np.int32)
+    x0, ui = sc.synthetic_batch(B, N, 0, sv.gravity_compensation(sc.standing_state(), base["gravity"]))
+    rng = np.random.default_rng(1)
+    if a.plant_params == "shared":
+        table = sc.stack_plant_params(1, friction=0.7, softness=2e-5, torque_gain=0.9)
+    else:
+        table = sc.stack_plant_params(B, gravity=np.array([0.0, 0.0, -9.81]) + rng.uniform(-0.3, 0.3, (B, 3)), friction=rng.uniform(0.3, 1.0, B),
+                                      softness=rng.uniform(1e-5, 1e-4, B), limit_stiffness=rng.uniform(0.0, 625.0, B), torque_gain=rng.uniform(0.8, 1.0, B))
+    ms = {False: [], True: []}
+    for rnd in range(a.rounds + 1):                      # round 0 warms up (first launches, allocations)
+        for tab in (False, True):
+            s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+            run = ml.MPCRunner(s, rd, base, resident=True, substeps=a.substeps, feedback_mode=a.feedback_mode, solve_every=a.solve_every, plant_params=table if tab else None)
+            run.run(x0, 1, u_init=ui)                    # the cold start is not what is compared: every timed step is a warm one
+            s.synchronize()
+            t0 = time.perf_counter()
+            run.run(x0, a.steps, u_init=ui)
+            dt = time.perf_counter() - t0
+            s.close()
+            if rnd:
+                ms[tab].append(1e3 * dt / a.steps)
+    # the plant kernel alone: 50 back-to-back advances under one solve, three repetitions from the same plant state
+    kernel_us, alive = {}, {}
+    for mode in (0, 2):
+        s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+        s.set_problem(base); s.initialize(x0, ui); s.solve(x0)
+        s.plant_set_model(mode, None); s.plant_configure(a.substeps, a.feedback_mode, "schedule")
+        st = torch.cuda.ExternalStream(s.stream)
+        for tab in (False, True):
+            if tab:
+                s.plant_set_params(table)
+            us = []
+            for rep_ in range(4):                        # (the first repetition warms up)
+                s.plant_reset(x0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(50):
+                    s.plant_advance()
+                e1.record(st); e1.synchronize()
+                us.append(1e3 * e0.elapsed_time(e1) / 50)
+            key = "mode%d_%s" % (mode, "table" if tab else "no_table")
+            kernel_us[key], alive[key] = us[1:], int(s.plant_alive().sum())
+        s.close()
+    print(json.dumps({"tool": "closed_loop_time", "mode": "plant_params", "plant_params": a.plant_params, "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N,
+                      "iterations": a.iters, "steps": a.steps, "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every,
+                      "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_table": float(np.median(ms[True])),
+                      "samples_no_table": ms[False], "samples_table": ms[True],
+                      "plant_kernel_us": {k: float(np.median(v)) for k, v in kernel_us.items()}, "plant_kernel_samples_us": kernel_us, "alive_after_50_advances": alive}))
 
 
 class HostWindows:
