@@ -289,7 +289,8 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* ctx, int* stance);
    ilqr_hip_window_from_track(ctx, k, follow_schedule) -> ilqr_hip_initialize_warm_from_plant -> ilqr_hip_solve(ctx, NULL, cost) ->
    ilqr_hip_plant_advance, and the solve's own synchronisation is the only one of the step for a moving reference too.  Solving every
    m-th interval only: ilqr_hip_initialize_warm_from_plant_shifted(ctx, m) -> ilqr_hip_solve -> ilqr_hip_plant_follow(ctx, 0, m), see
-   there.  Not provided: external wrenches, a contact model other than the solver's. */
+   there.  External wrenches on the pelvis: ilqr_hip_plant_set_wrench, below; a plant whose contact model or parameters are not the
+   solver's: ilqr_hip_plant_set_model / ilqr_hip_plant_set_params. */
 /* Upload the plant state x[B][51] (robot.getState's counterpart in reverse: RobotUtils::setState).  Every rollout becomes alive, a pending
    kick is dropped, the history cursor returns to 0.  Synchronises the handle's stream. */
 int ilqr_hip_plant_reset(ilqr_hip_ctx* ctx, const double* x /*[B][51]*/);
@@ -301,8 +302,8 @@ int ilqr_hip_plant_reset(ilqr_hip_ctx* ctx, const double* x /*[B][51]*/);
    stance rows and ignores it).  Defaults 1, 0, SCHEDULE.  Anything else: ILQR_ERR_ARG.  Launches nothing. */
 int ilqr_hip_plant_configure(ilqr_hip_ctx* ctx, int substeps, int feedback_mode, int contact_source);
 /* Arm a one-shot velocity kick dv[B][25] (order of qvel): the next advance adds it to the plant's qvel before it evaluates the control law,
-   then it is gone.  Synchronises the handle's stream (the caller's buffer is free on return).  No reference counterpart (xfrc_applied is
-   not modelled). */
+   then it is gone.  Synchronises the handle's stream (the caller's buffer is free on return).  No reference counterpart; a sustained
+   force is ilqr_hip_plant_set_wrench. */
 int ilqr_hip_plant_kick(ilqr_hip_ctx* ctx, const double* dv /*[B][25]*/);
 /* One MPC interval of the plant (main:162-170): kick, control law (src/ilqr/mpc.cpp:97-101; a u with a non-finite entry becomes zero,
    main:162-165; the step clamps u to the control range, the reported u is unclamped), `substeps` plant steps, then x, u (as applied in the
@@ -410,6 +411,44 @@ int ilqr_hip_plant_set_params(ilqr_hip_ctx* ctx, const double* params /*[n_sets]
 int ilqr_hip_plant_clear_params(ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_num_param_sets(const ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_get_params(ilqr_hip_ctx* ctx, double* params /*[B][7]*/);
+/* ---- sustained external wrench on the pelvis, one per rollout: the push of a robustness sweep.  The reference's plant, mj_step, applies
+   xfrc_applied in every substep; its main loop never sets it, so this is a capability of the plant and has no parity row.  Plant only:
+   rollout, line search, Jacobians and warm-start tail keep the solver's model -- the push is a disturbance the controller does not know.
+   One record of ILQR_PLANT_WRENCH doubles per set:
+     0..2  force F, world frame, N          3..5  torque T, world frame, N m
+     6..8  point of application r, pelvis frame, m: r = 0 is the origin of the pelvis frame, r = the pelvis inertial offset
+           (ilqr_hip_pelvis_inertial_offset) is MuJoCo's xfrc_applied
+     9, 10 first, end: the record acts in every substep of plant interval i with first <= i < end, intervals counted from 0 at
+           ilqr_hip_plant_reset (ilqr_hip_plant_intervals); integers stored as doubles, end may be +inf
+   Per substep, with R0 the pelvis rotation of the state the substep starts from, the generalized force on the free joint is
+   Wg = [F ; R0^T T + r x (R0^T F)], conjugate to qvel[0:6] (world linear, body angular).  In the articulated-body recursion it is one term
+   of the pelvis solve, IA0 a0 = f - p0, in every pass that solves the pelvis; stance rows and joint-limit rows act on that free solve as
+   they do without it, in all six step kinds.
+   plant_set_wrench: n_sets = 1 or the batch, else ILQR_ERR_ARG; ILQR_ERR_ARG also for a null pointer, a non-finite entry other than
+   end = +inf, a non-integral or negative first / end, or end < first (all checked before the handle is touched).  The table is a device
+   buffer of 128-byte records owned by the handle; the call uploads it and synchronises the handle's stream.  It survives
+   ilqr_hip_plant_reset and ilqr_hip_plant_configure.  While a table is installed ilqr_hip_plant_advance / _follow launch the wrench family
+   of the plant kernel (k_plant_follow_w; an advance is that kernel over one interval) and then the score kernels as before: ring, score,
+   alive, kick and the non-finite guards behave as without it, the reported control stays the law's output, a parameter table keeps
+   acting.  A wrench that makes a rollout's state non-finite freezes that rollout like any other cause.
+   plant_clear_wrench: frees it; the plant calls then launch exactly what they launch without it.
+   plant_num_wrench_sets: 0 without a table, else n_sets; -1 for a null handle.
+   plant_get_wrench: wrench[B][11], the record of each rollout (zeros without a table).
+   plant_intervals: plant intervals run since the last ilqr_hip_plant_reset -- ilqr_hip_plant_advance adds 1, ilqr_hip_plant_follow adds
+   count; a counter of its own on the host (the history cursor only counts while a ring exists, and ilqr_hip_plant_set_history does not
+   touch this one).  -1 for a null handle.
+   step_wrench: ilqr_hip_step_stance with one wrench (entries 0..8: F, T, r) per item, at the handle's dt, contact mode, friction,
+   softness and joint-limit options; always the two-lane step.  ILQR_ERR_ARG for a null pointer, count <= 0 or a non-finite entry;
+   ILQR_ERR_UNSUPPORTED as ilqr_hip_step_stance under an absent kernel family.
+   pelvis_inertial_offset: r[3] = the pelvis body's centre of mass in the pelvis frame (h1.xml inertial pos); host only, no GPU. */
+#define ILQR_PLANT_WRENCH 11   /* Fx, Fy, Fz, Tx, Ty, Tz, rx, ry, rz, first, end */
+int ilqr_hip_plant_set_wrench(ilqr_hip_ctx* ctx, const double* wrench /*[n_sets][11]*/, int n_sets);
+int ilqr_hip_plant_clear_wrench(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_num_wrench_sets(const ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_wrench(ilqr_hip_ctx* ctx, double* wrench /*[B][11]*/);
+long ilqr_hip_plant_intervals(const ilqr_hip_ctx* ctx);
+int ilqr_hip_step_wrench(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench /*[count][9]*/, double* x_next);
+void ilqr_hip_pelvis_inertial_offset(double r[3]);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

@@ -196,6 +196,20 @@ class iLQR {
   }
   void plantClearParams() { chk(ilqr_hip_plant_clear_params(ctx_)); }
   Vec plantParams() { Vec p((size_t)B_ * ILQR_PLANT_PARAMS); chk(ilqr_hip_plant_get_params(ctx_, p.data())); return p; }          // [batch][7], effective
+  // sustained external wrench on the pelvis per rollout (ilqr_hip.h ilqr_hip_plant_set_wrench): [n_sets][11] = F, T (world), r (pelvis frame), first, end
+  void plantSetWrench(const Vec& wrench, int n_sets) {
+    if (n_sets < 1 || wrench.size() != (size_t)n_sets * ILQR_PLANT_WRENCH) throw std::runtime_error("wrench must hold n_sets * 11 doubles");
+    chk(ilqr_hip_plant_set_wrench(ctx_, wrench.data(), n_sets));
+  }
+  void plantClearWrench() { chk(ilqr_hip_plant_clear_wrench(ctx_)); }
+  int plantNumWrenchSets() const { return ilqr_hip_plant_num_wrench_sets(ctx_); }
+  Vec plantWrench() { Vec w((size_t)B_ * ILQR_PLANT_WRENCH); chk(ilqr_hip_plant_get_wrench(ctx_, w.data())); return w; }          // [batch][11]
+  long plantIntervals() const { return ilqr_hip_plant_intervals(ctx_); }                                                              // since the last plantReset
+  Vec stepWrench(int count, const Vec& x, const Vec& u, int stance_left, int stance_right, const Vec& wrench /*[count][9]*/) {
+    if (count < 1 || x.size() != (size_t)count * ILQR_NX || u.size() != (size_t)count * ILQR_NU || wrench.size() != (size_t)count * 9) throw std::runtime_error("stepWrench: x [count][51], u [count][19], wrench [count][9]");
+    Vec xn((size_t)count * ILQR_NX); chk(ilqr_hip_step_wrench(ctx_, count, x.data(), u.data(), stance_left, stance_right, wrench.data(), xn.data())); return xn;
+  }
+  static std::array<double, 3> pelvisInertialOffset() { std::array<double, 3> r{}; ilqr_hip_pelvis_inertial_offset(r.data()); return r; }
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492
   void clearReferenceTrack() { chk(ilqr_hip_clear_reference_track(ctx_)); }

@@ -435,10 +435,26 @@ typedef Chain<12, 16, 4, 48> ArmChain;   // bodies 12..15 / 16..19, LDS slots 48
 // acceleration-prescribed joint, qacc = c, exactly: D = 2^1000, 1 / D = 2^-1000 and u / D = c to the last bit, the reduction of the
 // articulated inertia U U^T / D vanishes below rounding -- Featherstone's hybrid dynamics through the unmodified recursion, and every
 // later reader of U_i, 1 / D_i (the stance rows' unit-wrench responses, the linearisation's Minv columns) sees that hinge locked.
-template <bool PER = false>
+// WR: an external wrench on the pelvis (ilqr_hip_plant_set_wrench).  wr[9] = force F and torque T in the world frame, point of application r
+// in the pelvis frame; the pelvis solve IA0 a0 = -p0 becomes IA0 a0 = f - p0 with the spatial force f = (R0^T T + r x R0^T F, R0^T F).
+// Nothing else of the recursion changes: stance rows and limit rows act on this free solve as on the one without it.  Without WR the
+// function is, after the preprocessor and `if constexpr`, the text it was before the argument existed.
+template <bool WR>
+DEVFN void pelvis_rhs(const double* R0, const double* p0, const double* wr, double* rhs) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) rhs[k] = -p0[k];
+  if constexpr (WR) {
+    const double Fb[3] = {R0[0] * wr[0] + R0[3] * wr[1] + R0[6] * wr[2], R0[1] * wr[0] + R0[4] * wr[1] + R0[7] * wr[2], R0[2] * wr[0] + R0[5] * wr[1] + R0[8] * wr[2]};
+    const double Tb[3] = {R0[0] * wr[3] + R0[3] * wr[4] + R0[6] * wr[5], R0[1] * wr[3] + R0[4] * wr[4] + R0[7] * wr[5], R0[2] * wr[3] + R0[5] * wr[4] + R0[8] * wr[5]};
+    double rxF[3]; cross(wr + 6, Fb, rxF);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { rhs[k] += Tb[k] + rxF[k]; rhs[3 + k] += Fb[k]; }
+  }
+}
+template <bool PER = false, bool WR = false>
 DEVFN void forward_dynamics(bool side, const double* R0, const double* vb, const HalfState& q, const HalfTau& tau, double arm_eff,
                             const double* grav, const LaneLds& L, double* qbase, HalfAcc& qacc, Art* Y0_out = nullptr, double* a0_out = nullptr,
-                            const HalfTau* arm_add = nullptr) {
+                            const HalfTau* arm_add = nullptr, const double* wr = nullptr) {
   double v0[6] = {vb[3], vb[4], vb[5], 0, 0, 0};
   v0[3] = R0[0] * vb[0] + R0[3] * vb[1] + R0[6] * vb[2];
   v0[4] = R0[1] * vb[0] + R0[4] * vb[1] + R0[7] * vb[2];
@@ -484,6 +500,7 @@ DEVFN void forward_dynamics(bool side, const double* R0, const double* vb, const
 #endif
   // pelvis
   double rhs[6] = {-p0[0], -p0[1], -p0[2], -p0[3], -p0[4], -p0[5]}, a0[6];
+  if constexpr (WR) pelvis_rhs<true>(R0, p0, wr, rhs);
   solve6(Y0, rhs, a0);
   if (Y0_out) *Y0_out = Y0;
   if (a0_out) {
@@ -571,9 +588,10 @@ DEVFN void ldl6_solve(const Ldl6& F, const double* rhs, double* out) {
 // sink(body, v, a, sin, cos) for every body of this lane's side (pelvis and torso: both lanes report them), the explicit
 // inverse of the pelvis' articulated inertia and the pelvis' linear acceleration without the gravity term.  U, 1/D stay in
 // this lane's LDS slots (torso: slot block 0, leg hinge K: 8 + 8 K, arm hinge K: 48 + 8 K).
-template <class Sink, bool PER = false>
+template <class Sink, bool PER = false, bool WR = false>
 DEVFN void forward_dynamics_dump(bool side, const double* R0, const double* vb, const HalfState& q, const HalfTau& tau, double arm_eff, const double* grav,
-                                 const LaneLds& L, double* qbase, HalfAcc& qacc, Sink& sink, double* inv36, double* aL, const HalfTau* arm_add = nullptr) {
+                                 const LaneLds& L, double* qbase, HalfAcc& qacc, Sink& sink, double* inv36, double* aL, const HalfTau* arm_add = nullptr,
+                                 const double* wr = nullptr) {
   double v0[6] = {vb[3], vb[4], vb[5], 0, 0, 0};
   v0[3] = R0[0] * vb[0] + R0[3] * vb[1] + R0[6] * vb[2];
   v0[4] = R0[1] * vb[0] + R0[4] * vb[1] + R0[7] * vb[2];
@@ -614,6 +632,7 @@ DEVFN void forward_dynamics_dump(bool side, const double* R0, const double* vb, 
   __builtin_amdgcn_sched_barrier(0);
   // pelvis: one factorisation, the solve and (left lane's job to store) the explicit inverse column by column
   double rhs[6] = {-p0[0], -p0[1], -p0[2], -p0[3], -p0[4], -p0[5]}, a0[6];
+  if constexpr (WR) pelvis_rhs<true>(R0, p0, wr, rhs);
   Ldl6 F; ldl6_factor(Y0, F);
   ldl6_solve(F, rhs, a0);
 #pragma unroll
@@ -1034,7 +1053,8 @@ DEVFN void store_half(bool side, const HalfX& h, double* x) {
 DEVFN double clampu(double u, const double* range) { return u < range[0] ? range[0] : (u > range[1] ? range[1] : u); }
 
 // x <- f(x, u) in place: RobotUtils::rolloutOneStep (reference src/common/robot_utils.cpp:106-117), smooth regime
-DEVFN void step(bool side, HalfX& h, const HalfU& u, double dt, const double* grav, const LaneLds& L) {
+template <bool WR = false>
+DEVFN void step(bool side, HalfX& h, const HalfU& u, double dt, const double* grav, const LaneLds& L, const double* wr = nullptr) {
   const double qn = sqrt(h.quat[0] * h.quat[0] + h.quat[1] * h.quat[1] + h.quat[2] * h.quat[2] + h.quat[3] * h.quat[3]);
   const double qh[4] = {h.quat[0] / qn, h.quat[1] / qn, h.quat[2] / qn, h.quat[3] / qn};
   double R0[9]; quat_R(qh[0], qh[1], qh[2], qh[3], R0);
@@ -1053,7 +1073,8 @@ DEVFN void step(bool side, HalfX& h, const HalfU& u, double dt, const double* gr
     tau.tA[k] = uc - DAMPING * h.q.qdA[k];
   }
   double qb[6]; HalfAcc qa;
-  forward_dynamics(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa);
+  if constexpr (WR) forward_dynamics<false, true>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, nullptr, nullptr, nullptr, wr);
+  else forward_dynamics(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa);
   // semi-implicit Euler: v' = v + h qacc, q' = q (+) h v'
 #pragma unroll
   for (int k = 0; k < 6; ++k) h.vb[k] += dt * qb[k];
@@ -1144,11 +1165,11 @@ DEVFN void stance_prepare(bool side, const HalfX& h, const HalfU& u, double* qh,
     tau.tA[k] = uc - DAMPING * h.q.qdA[k];
   }
 }
-template <bool KIN, bool PER>
+template <bool KIN, bool PER, bool WR = false>
 DEVFN void stance_accelerations(bool side, const double* R0, const HalfX& h, const HalfTau& tau, double dt, const double* grav, const LaneLds& L, double soft, int mode,
-                                bool st_own, bool st_par, double mu, double* qb, HalfAcc& qa, const HalfTau* add = nullptr) {
+                                bool st_own, bool st_par, double mu, double* qb, HalfAcc& qa, const HalfTau* add = nullptr, const double* wr = nullptr) {
   Art Y0; double a0[6];
-  forward_dynamics<PER>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, &Y0, a0, add);
+  forward_dynamics<PER, WR>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, &Y0, a0, add, wr);
   if (st_own || st_par) stance_correct<KIN>(side, R0, h.vb, h.q, dt, soft, mode, st_own, st_par, grav, L, Y0, a0, qb, qa, mu);
 }
 DEVFN void integrate_half(HalfX& h, const double* qh, const double* qb, const HalfAcc& qa, double dt) {
@@ -1174,12 +1195,13 @@ DEVFN void integrate_half(HalfX& h, const double* qh, const double* qb, const Ha
   h.quat[0] = rw / rn; h.quat[1] = rx / rn; h.quat[2] = ry / rn; h.quat[3] = rz / rn;
 }
 // x <- f(x, u) with the stance constraints of the scheduled feet (contact mode 1 / 2 / 3 / 4)
-template <bool KIN = false>
-DEVFN void step_stance(bool side, HalfX& h, const HalfU& u, double dt, const double* grav, const LaneLds& L, double soft, int mode, bool st_own, bool st_par, double mu = 1.0) {
+template <bool KIN = false, bool WR = false>
+DEVFN void step_stance(bool side, HalfX& h, const HalfU& u, double dt, const double* grav, const LaneLds& L, double soft, int mode, bool st_own, bool st_par, double mu = 1.0,
+                       const double* wr = nullptr) {
   double qh[4], R0[9]; HalfTau tau;
   stance_prepare(side, h, u, qh, R0, tau);
   double qb[6]; HalfAcc qa;
-  stance_accelerations<KIN, false>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, qb, qa);
+  stance_accelerations<KIN, false, WR>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, qb, qa, nullptr, wr);
   integrate_half(h, qh, qb, qa, dt);
 }
 

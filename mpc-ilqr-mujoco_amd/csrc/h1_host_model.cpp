@@ -99,6 +99,11 @@ void foot_clearance(const double* q, double* clr) {
   }
 }
 
+// centre of mass of the pelvis body in the pelvis frame (h1.xml inertial pos; mjModel.body_ipos): the point at which xfrc_applied acts
+void pelvis_inertial_offset(double* r) {
+  for (int k = 0; k < 3; ++k) r[k] = H1_COM[0][k];
+}
+
 // qfrc_bias[6+j] at zero velocity = minus the generalized gravity force on hinge j
 void gravity_compensation(const double* x, const double* g, double* u) {
   double Rw[H1_NB][9], pw[H1_NB][3];

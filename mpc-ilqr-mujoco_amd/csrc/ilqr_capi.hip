@@ -154,6 +154,17 @@ struct ilqr_hip_ctx {
   // plant parameter table (ilqr_hip_plant_set_params; plant_kernels.hip k_plant_follow_p): [n][8] doubles, n = 1 or B; null: none
   double* d_pparams = nullptr;
   int pparams_sets = 0;
+  // wrench table (ilqr_hip_plant_set_wrench; plant_kernels.hip k_plant_follow_w): [n][16] doubles (128-byte records), n = 1 or B; null: none.
+  // d_self_params: the ONE parameter record the wrench kernels read while no parameter table is installed -- the handle's own values with
+  // gain 1, uploaded again whenever they differ from self_params
+  double* d_wrench = nullptr;
+  int wrench_sets = 0;
+  double* d_self_params = nullptr;
+  double self_params[ILQR_PLANT_PARAMS + 1] = {0};
+  double* d_stepw = nullptr;  // [step_w_cap][9] wrenches of ilqr_hip_step_wrench
+  size_t step_w_cap = 0;
+  bool wrench_attr_set = false;   // the wrench module's kernels have their LDS attributes on this handle's device
+  long plant_intervals = 0;   // plant intervals run since the last ilqr_hip_plant_reset (the history cursor only counts while a ring exists)
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
   // closed-loop score of the plant (ilqr_hip_plant_set_score; plant_score_kernels.hip): the record [B][8], the term rows of one plant call
@@ -232,6 +243,51 @@ static inline int enter_launching(ilqr_hip_ctx* c) {
   enter(c);
   if (c->env_refused) return ILQR_ERR_UNSUPPORTED;
   if (c->P.wsets) if (const char* why = weight_sets_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  return ILQR_OK;
+}
+
+// The wrench family of the plant kernels is a module of its own (csrc/Makefile ../lib/libilqr_hip_wrench.so; plant_kernels.hip says why),
+// opened on first use from the directory this library was loaded from, as RCCL is opened on first use: a process that never pushes its
+// plant never loads it.  A module that is missing or lacks an entry point is an error of the call that needs it (ILQR_ERR_UNSUPPORTED).
+namespace {
+struct WrenchModule {
+  void* lib = nullptr;
+  ilqr::wrench_set_attr_fn set_attr = nullptr;
+  ilqr::wrench_follow_fn follow = nullptr;
+  ilqr::wrench_step_fn step = nullptr;
+  std::string why;
+  bool ok() const { return lib && set_attr && follow && step; }
+};
+WrenchModule& wrench_module() {
+  static WrenchModule m;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    Dl_info info;
+    std::string dir = ".";
+    if (dladdr((const void*)&ilqr_hip_plant_intervals, &info) && info.dli_fname) {
+      const std::string self = info.dli_fname;
+      const size_t slash = self.rfind('/');
+      if (slash != std::string::npos) dir = self.substr(0, slash);
+    }
+    const std::string path = dir + "/libilqr_hip_wrench.so";
+    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!m.lib) { m.why = "the wrench kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.set_attr = (ilqr::wrench_set_attr_fn)dlsym(m.lib, "ilqr_wrench_module_set_attr");
+    m.follow = (ilqr::wrench_follow_fn)dlsym(m.lib, "ilqr_wrench_module_follow");
+    m.step = (ilqr::wrench_step_fn)dlsym(m.lib, "ilqr_wrench_module_step");
+    if (!m.ok()) m.why = "the wrench kernels' module lacks an entry point: " + path;
+  });
+  return m;
+}
+}  // namespace
+// the module, with its kernels' LDS attributes set on this handle's device (once per handle)
+static int need_wrench_module(ilqr_hip_ctx* c) {
+  WrenchModule& m = wrench_module();
+  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
+  if (!c->wrench_attr_set) {
+    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the wrench kernels"; return ILQR_ERR_HIP; }
+    c->wrench_attr_set = true;
+  }
   return ILQR_OK;
 }
 
@@ -322,7 +378,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1390,6 +1446,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and
 // joint-limit option where ilqr_hip_plant_set_model has given it one.  (With a parameter table the kernels replace g, mu, soft and lim_k per rollout.)
+constexpr int WRENCH_REC = 16;      // doubles of a wrench record on the device (128 B): the ILQR_PLANT_WRENCH values and padding
 static h1::DynParams plant_dyn(const ilqr_hip_ctx* c) {
   h1::DynParams dyn = c->P.dyn;
   dyn.h = c->P.dyn.h / c->plant_substeps;
@@ -1403,12 +1460,31 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
   if ((plant_mode >= 0 ? plant_mode : c->P.dyn.contact) == ILQR_CONTACT_RIGID_STANCE) return "plant contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4";
   return nullptr;
 }
+// The wrench family (k_plant_follow_w) always reads a parameter record: the parameter table's, or this ONE record of the handle's own values
+// with gain 1, uploaded again whenever the handle's values have changed.
+static int plant_self_params(ilqr_hip_ctx* c) {
+  if (!c->d_wrench || c->d_pparams) return ILQR_OK;
+  const h1::DynParams& d = c->P.dyn;
+  const double rec[ILQR_PLANT_PARAMS + 1] = {d.g[0], d.g[1], d.g[2], d.mu, d.soft, d.lim_k, 1.0, 0.0};
+  if (c->d_self_params && std::memcmp(rec, c->self_params, sizeof(rec)) == 0) return ILQR_OK;
+  if (!c->d_self_params) HIPCHK(c, hipMalloc((void**)&c->d_self_params, sizeof(rec)));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the record this one replaces)
+  HIPCHK(c, hipMemcpy(c->d_self_params, rec, sizeof(rec), hipMemcpyHostToDevice));
+  std::memcpy(c->self_params, rec, sizeof(rec));
+  return ILQR_OK;
+}
 // The plant kernel of one call: without a table exactly the launch without the feature; with one, the followed kernel with the table's
 // records -- for an advance over the one interval (0, 1), which is an advance bit for bit.  row: the advance's ring row (-1: no ring) or the
 // follow's first ring row.
+// With a wrench table: the wrench family of the module, under the parameter table or the handle's own record (plant_self_params).
 static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  if (c->d_pparams) {
+  if (c->d_wrench) {
+    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+    wrench_module().follow(&c->S, &c->plant, &dyn, &T, &W, &a, c->stream);      // (loaded by ilqr_hip_plant_set_wrench, which installed the table)
+  } else if (c->d_pparams) {
     const ilqr::PlantTable T{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1};
     ilqr::launch_plant_follow_params(c->S, c->plant, dyn, T, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, c->hist_cap, c->stream);
   } else if (follow) {
@@ -1429,7 +1505,7 @@ int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   const std::vector<double> empty = empty_score(c);      // (outlives the copy: the synchronisation below)
   if (c->score_on) HIPCHK(c, hipMemcpyAsync(c->d_score, empty.data(), empty.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's buffers are free on return)
-  c->plant_set = true; c->plant_kick = false; c->hist_n = 0;
+  c->plant_set = true; c->plant_kick = false; c->hist_n = 0; c->plant_intervals = 0;
   return ILQR_OK;
 }
 int ilqr_hip_plant_configure(ilqr_hip_ctx* c, int substeps, int feedback_mode, int contact_source) {
@@ -1458,12 +1534,14 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
     if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
+  TRY(plant_self_params(c));
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
   if (c->score_on) enqueue_score(c, row, 0, 1);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
+  c->plant_intervals += 1;
   if (row >= 0) c->hist_n += 1;
   return ILQR_OK;      // asynchronous on the handle's stream
 }
@@ -1493,12 +1571,14 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
     c->err = "plant_follow with a score installed: " + std::to_string(count) + " intervals exceed the history ring's " + std::to_string(c->hist_cap) + " rows (the score kernels read the ring's rows)";
     return ILQR_ERR_STATE;
   }
+  TRY(plant_self_params(c));
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
   if (c->score_on) enqueue_score(c, row0, first_knot, count);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
+  c->plant_intervals += count;
   if (c->hist_cap > 0) c->hist_n += count;
   return ILQR_OK;      // asynchronous on the handle's stream
 }
@@ -1614,6 +1694,93 @@ int ilqr_hip_plant_get_params(ilqr_hip_ctx* c, double* params) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int b = 0; b < c->B; ++b) std::memcpy(params + (size_t)b * P, rec.data() + (size_t)(c->pparams_sets == 1 ? 0 : b) * REC, P * sizeof(double));
   return ILQR_OK;
+}
+// ---- external wrench on the pelvis per rollout (plant_kernels.hip k_plant_follow_w, k_step_w)
+// the checks of a wrench record that need no handle: every entry finite but end = +inf, first / end non-negative integers, first <= end
+static bool wrench_values_ok(const double* r, int n) {
+  for (int i = 0; i < n; ++i) if (!std::isfinite(r[i]) && !(n == ILQR_PLANT_WRENCH && i == 10 && r[i] > 0.0 && std::isinf(r[i]))) return false;
+  if (n == ILQR_PLANT_WRENCH) {
+    if (r[9] < 0.0 || r[10] < 0.0 || r[9] != std::floor(r[9]) || (std::isfinite(r[10]) && r[10] != std::floor(r[10])) || r[10] < r[9]) return false;
+  }
+  return true;
+}
+int ilqr_hip_plant_set_wrench(ilqr_hip_ctx* c, const double* wrench, int n_sets) {
+  if (!wrench || n_sets < 1) return ILQR_ERR_ARG;
+  for (int s = 0; s < n_sets; ++s) if (!wrench_values_ok(wrench + (size_t)s * ILQR_PLANT_WRENCH, ILQR_PLANT_WRENCH)) return ILQR_ERR_ARG;
+  if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(need_wrench_module(c));
+  std::vector<double> rec((size_t)n_sets * WRENCH_REC, 0.0);      // (128-byte records: the eleven values and five doubles of padding)
+  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * WRENCH_REC, wrench + (size_t)s * ILQR_PLANT_WRENCH, ILQR_PLANT_WRENCH * sizeof(double));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (c->d_wrench && c->wrench_sets != n_sets) { hipFree(c->d_wrench); c->d_wrench = nullptr; c->wrench_sets = 0; }
+  if (!c->d_wrench) HIPCHK(c, hipMalloc((void**)&c->d_wrench, rec.size() * sizeof(double)));
+  c->wrench_sets = n_sets;
+  HIPCHK(c, hipMemcpyAsync(c->d_wrench, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_clear_wrench(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->d_wrench) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+    hipFree(c->d_wrench);
+  }
+  c->d_wrench = nullptr; c->wrench_sets = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_num_wrench_sets(const ilqr_hip_ctx* c) { return c ? c->wrench_sets : -1; }
+int ilqr_hip_plant_get_wrench(ilqr_hip_ctx* c, double* wrench) {
+  if (!c || !wrench) return ILQR_ERR_ARG;
+  enter(c);
+  constexpr int P = ILQR_PLANT_WRENCH;
+  if (!c->d_wrench) {      // (no table: no wrench, an empty window)
+    std::fill(wrench, wrench + (size_t)c->B * P, 0.0);
+    return ILQR_OK;
+  }
+  std::vector<double> rec((size_t)c->wrench_sets * WRENCH_REC);
+  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_wrench, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(wrench + (size_t)b * P, rec.data() + (size_t)(c->wrench_sets == 1 ? 0 : b) * WRENCH_REC, P * sizeof(double));
+  return ILQR_OK;
+}
+long ilqr_hip_plant_intervals(const ilqr_hip_ctx* c) { return c ? c->plant_intervals : -1L; }
+int ilqr_hip_step_wrench(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, double* x_next) {
+  if (count <= 0 || !x || !u || !wrench || !x_next) return ILQR_ERR_ARG;
+  for (int i = 0; i < count; ++i) if (!wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
+  if (!c) return ILQR_ERR_ARG;
+  TRY(enter_launching(c));
+  TRY(need_wrench_module(c));
+  if ((size_t)count > c->step_w_cap) {
+    if (c->d_stepw) hipFree(c->d_stepw);
+    c->d_stepw = nullptr; c->step_w_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->d_stepw, (size_t)count * 9 * sizeof(double)));
+    c->step_w_cap = (size_t)count;
+  }
+  if ((size_t)count > c->step_cap) {      // (the scratch of plant_step, grown the same way)
+    if (c->d_stepx) hipFree(c->d_stepx);
+    if (c->d_stepu) hipFree(c->d_stepu);
+    if (c->d_stepn) hipFree(c->d_stepn);
+    if (c->d_stance_out) hipFree(c->d_stance_out);
+    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
+    c->step_cap = (size_t)count;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, (size_t)count * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  wrench_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, c->d_stepw, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+void ilqr_hip_pelvis_inertial_offset(double r[3]) {
+  if (r) h1host::pelvis_inertial_offset(r);      // (host table: the model constants of this translation unit are device constants)
 }
 // ---- closed-loop score of the plant (plant_score_kernels.hip)
 int ilqr_hip_plant_set_score(ilqr_hip_ctx* c, const double* Q_diag, const double* R_diag, double w_upright, double w_balance, double w_joint_limits, double w_control_limits) {

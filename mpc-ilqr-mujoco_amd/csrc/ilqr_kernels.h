@@ -188,6 +188,25 @@ struct PlantTable {
 };
 void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const PlantTable& T, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode,
                                 int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st);
+// the same under an external wrench on the pelvis per rollout (ilqr_hip_plant_set_wrench): rollout b reads record b * rec_stride of
+// W.records -- F[3], T[3] (world), r[3] (pelvis frame), first, end, padding; 16 doubles -- and steps under it in the plant intervals
+// first <= W.interval0 + j < end.  rec_stride 16 or 0 as above.  T is always read: without a parameter table the caller passes ONE record
+// of the handle's own values with gain 1 (rec_stride 0).
+struct WrenchTable {
+  const double* records;
+  int rec_stride;
+  long interval0;      // plant intervals run since ilqr_hip_plant_reset when this launch starts
+};
+// The family lives in a module of its own, libilqr_hip_wrench.so (plant_kernels.hip compiled with -DPLANT_WRENCH_MODULE), which the C API
+// opens on first use; these are its three entry points, C linkage:
+//   int  ilqr_wrench_module_set_attr()                                  the LDS attributes of its kernels on the current device
+//   void ilqr_wrench_module_follow(S, Pl, dyn, T, W, args, stream)      the followed plant kernel under the two tables
+//   void ilqr_wrench_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9], stream)
+//                                                                       one two-lane step per item under its wrench (F, T, r): launch_step_s with explicit stance flags
+struct WrenchFollowArgs { const int* sched; long sched_stride; int geom, substeps, feedback_mode, kick, first_knot, count; long hist_row0, hist_cap; };
+typedef int (*wrench_set_attr_fn)();
+typedef void (*wrench_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const WrenchFollowArgs*, hipStream_t);
+typedef void (*wrench_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

@@ -3,10 +3,16 @@
 //                  text the kernel has always had: the fast path keeps its machine code.
 //   PLANT_TABLE 1  k_plant_follow_p: each rollout steps with its own record of a plant parameter table (ilqr_hip_plant_set_params) -- two
 //                  more kernel arguments, RPW more rows of LDS behind the layout, plant_step_table in the place of step_any.
+//   PLANT_TABLE 2  k_plant_follow_w: as 1 (it always reads a parameter record), and each rollout steps under the external wrench of its
+//                  record of a wrench table (ilqr_hip_plant_set_wrench) in the intervals of the record's window -- three more kernel
+//                  arguments, RPW + 1 more rows of LDS (the last one zero: the wrench outside the window), the wrench-carrying steps.
 #ifndef PLANT_TABLE
-#error "define PLANT_TABLE (0 or 1) before including plant_follow_body.h"
+#error "define PLANT_TABLE (0, 1 or 2) before including plant_follow_body.h"
 #endif
-#if PLANT_TABLE
+#if PLANT_TABLE == 2
+#define K_PLANT_FOLLOW k_plant_follow_w
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0
+#elif PLANT_TABLE
 #define K_PLANT_FOLLOW k_plant_follow_p
 #define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride
 #else
@@ -33,6 +39,10 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
   h1s::HalfU u;
 #if PLANT_TABLE
   stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
+#endif
+#if PLANT_TABLE == 2
+  constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // wrench rows behind the parameter rows, then the zero row
+  stage_wrench_records<RPW>(S, lds + WR0, b0, wtab, wr_stride);
 #endif
   for (int j = 0; j < count; ++j) {
     const int kt = k0 + j;
@@ -83,7 +93,13 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
         if constexpr (KIND >= 1 && KIND <= 4) {
           if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
         }
-#if PLANT_TABLE
+#if PLANT_TABLE == 2
+        // interval interval0 + j, counted from ilqr_hip_plant_reset; the window's bounds are integers stored as doubles (end may be +inf)
+        const double* wrow = lds + WR0 + pc * WRENCH_REC;
+        const double iv = (double)(interval0 + j);
+        const int wro = (wrow[9] <= iv && iv < wrow[10]) ? WR0 + pc * WRENCH_REC : WR0 + RPW * WRENCH_REC;
+        plant_step_table<KIND, true>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC, wro);
+#elif PLANT_TABLE
         plant_step_table<KIND>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC);
 #else
         step_any<KIND>(side_t, h, u, dyn, st, L, geom);

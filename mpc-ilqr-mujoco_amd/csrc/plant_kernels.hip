@@ -8,7 +8,7 @@
 //                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
 // A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
-// twice: without and with a plant parameter table (k_plant_follow_p).
+// three times: without a table, with a plant parameter table (k_plant_follow_p), and with a parameter and a wrench table (k_plant_follow_w).
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -21,6 +21,14 @@ using namespace h1;
 
 namespace ilqr {
 
+// This file is compiled twice (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
+// libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
+// which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
+// library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
+// have used up.  One module serves both libraries: the plant runs on the two-lane step whatever the handle's family.
+#ifdef PLANT_WRENCH_MODULE
+#define DYN_STEP_WRENCH      // the wrench-carrying copies of the non-inlined steps: compiled in the module alone
+#endif
 #include "dyn_step_shared.h"
 
 // LDS of a workgroup, in doubles: the dynamics scratch of the step (LDS_SLOTS x 64, at the base: the non-inlined steps address it there),
@@ -102,6 +110,7 @@ DEVFN void control_law(const DevState& S, double* lds, int b0, int knot = 0) {
   }
 }
 
+#ifndef PLANT_WRENCH_MODULE
 // KIND: the CONTACT value of step_any (step_kind(dyn)); FB: feedback mode -- 0 the reference's loop, u held over the MPC interval; 1 the
 // control law re-evaluated on (xbar_0, ubar_0, K_0) before every substep.  dyn: the PLANT's parameters (h = dt / substeps).
 // sched / sched_stride: the contact schedule (row 0 of each set is the stance of this MPC step); geom: stance from the feet instead.
@@ -187,6 +196,7 @@ __global__ void __launch_bounds__(64) k_plant_advance(DevState S, PlantDev Pl, D
   if (!side) Pl.alive[b] = run ? 1 : 0;
 }
 
+#endif
 // ---- k_plant_follow: `count` intervals in one launch.  Per interval j exactly what k_plant_advance does with knot k0 + j in the place of
 // knot 0, row k0 + j of the schedule and row (hist_row0 + j) % hist_cap of the ring; the kick before interval 0 only.  What an advance
 // leaves in memory for the next one stays on the chip: the state in the rollout's LDS row (the next interval loads it from there as an
@@ -206,8 +216,10 @@ DEVFN void zero_half_u(h1s::HalfU& u) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) u.uA[q] = 0.0;
 }
+#ifndef PLANT_WRENCH_MODULE
 #define PLANT_TABLE 0
 #include "plant_follow_body.h"
+#endif
 
 // ---- plant parameter table (include/ilqr_hip.h ilqr_hip_plant_set_params): k_plant_follow_p.  One record of PLANT_REC doubles per rollout
 // -- g[3], mu, soft, lim_k, torque gain, one double of padding (64 B) -- or ONE record that every rollout reads (rec_stride = 0).  The wave
@@ -228,8 +240,9 @@ DEVFN void stage_plant_records(const DevState& S, double* rows, int b0, const do
 // one plant step with the record `rec` in the place of g, mu, soft and lim_k of `dyn` (h stays the kernel argument: wave-uniform, as the
 // inlined steps need it behind their "+s" constraint) and gain * u in the place of u -- behind the non-finite guard, in front of the
 // step's clamp; the caller's u, which is what it reports, stays the law's output
-template <int KIND>
-DEVFN void plant_step_table(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L, int geom, const double* rec) {
+// WR: under the external wrench at LDS offset wro (step_any_w)
+template <int KIND, bool WR = false>
+DEVFN void plant_step_table(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L, int geom, const double* rec, int wro = 0) {
   DynParams dl = dyn;
   dl.g[0] = rec[0]; dl.g[1] = rec[1]; dl.g[2] = rec[2]; dl.mu = rec[3]; dl.soft = rec[4]; dl.lim_k = rec[5];
   const double gain = rec[6];
@@ -239,11 +252,66 @@ DEVFN void plant_step_table(bool side, h1s::HalfX& h, const h1s::HalfU& u, const
   for (int q = 0; q < 5; ++q) us.uL[q] = gain * u.uL[q];
 #pragma unroll
   for (int q = 0; q < 4; ++q) us.uA[q] = gain * u.uA[q];
+#ifdef PLANT_WRENCH_MODULE
+  if constexpr (WR) step_any_w<KIND>(side, h, us, dl, st, L, geom, wro);
+  else
+#endif
   step_any<KIND>(side, h, us, dl, st, L, geom);
 }
+#ifndef PLANT_WRENCH_MODULE
 #define PLANT_TABLE 1
 #include "plant_follow_body.h"
+#endif
 
+#ifdef PLANT_WRENCH_MODULE
+// ---- wrench table (include/ilqr_hip.h ilqr_hip_plant_set_wrench): k_plant_follow_w.  One record of WRENCH_REC doubles (128 B) per rollout
+// -- force F[3] and torque T[3] in the world frame, point of application r[3] in the pelvis frame, the window [first, end) in plant
+// intervals, five doubles of padding -- or ONE record that every rollout reads (wr_stride = 0).  Staged in LDS once per launch behind the
+// parameter rows, consecutive lanes on consecutive doubles (4 KB at FB = 0, 512 B at FB = 1), followed by one row of zeros: the wrench of
+// an interval outside the window.  A substep hands the step the offset of one of the two rows, so the window costs no second code path
+// and a wrench of zero is the arithmetic of a table whose window is shut.  The kernel always reads a parameter record: without a
+// parameter table the caller passes one record of the handle's own values with gain 1.
+#define WRENCH_REC 16
+template <int RPW>
+DEVFN void stage_wrench_records(const DevState& S, double* rows, int b0, const double* wtab, int wr_stride) {
+  for (int e = threadIdx.x; e < (RPW + 1) * WRENCH_REC; e += 64) {
+    const int r = e / WRENCH_REC;
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;
+    rows[e] = r < RPW ? wtab[(size_t)br * wr_stride + (e - r * WRENCH_REC)] : 0.0;
+  }
+}
+#define PLANT_TABLE 2
+#include "plant_follow_body.h"
+
+// ---- one step under a wrench per item (ilqr_hip_step_wrench): k_step_s of dyn_split_kernels.hip with the wrench-carrying step; the 32
+// items of a workgroup stage their nine values behind the dynamics scratch
+#define STEP_W_LDS_BYTES ((h1s::LDS_SLOTS * 64 + 32 * 9) * sizeof(double))
+template <int CK>
+__global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const double* u, DynParams dyn, double* xn, int st_l, int st_r, const double* wrench) {
+  extern __shared__ double lds[];
+  constexpr int WR0 = h1s::LDS_SLOTS * 64;
+  const int i0 = blockIdx.x * 32;
+  for (int e = threadIdx.x; e < 32 * 9; e += 64) {
+    const int r = e / 9;
+    const int ir = i0 + r < count ? i0 + r : count - 1;
+    lds[WR0 + e] = wrench[(size_t)ir * 9 + (e - r * 9)];
+  }
+  wave_lds_fence();
+  const int i = i0 + ((int)threadIdx.x >> 1);
+  const bool side = (threadIdx.x & 1) != 0;
+  if (i >= count) return;
+  const h1s::LaneLds L{lds, 64, (int)threadIdx.x};
+  h1s::HalfX h; h1s::load_half(side, x + (size_t)i * H1_NX, h);
+  h1s::HalfU uu; load_half_u(side, u + (size_t)i * H1_NU, uu);
+  int st[2] = {st_l, st_r};
+  step_any_w<CK>(side, h, uu, dyn, st, L, 0, WR0 + ((int)threadIdx.x >> 1) * 9);
+  h1s::store_half(side, h, xn + (size_t)i * H1_NX);
+}
+
+#endif
+
+struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
+#ifndef PLANT_WRENCH_MODULE
 template <int KIND, int FB> static int plant_attr() {
   return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess ||
          hipFuncSetAttribute((const void*)k_plant_follow<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FollowLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
@@ -271,7 +339,6 @@ void launch_plant_advance(const DevState& S, const PlantDev& Pl, const DynParams
   });
 }
 
-struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
 template <int KIND, int FB>
 static void follow_launch(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const FollowArgs& a, hipStream_t st) {
   typedef FollowLayout<FB> Lay;
@@ -302,5 +369,50 @@ void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const Dyn
     else follow_launch_p<K(), 0>(S, Pl, dyn, T, a, st);
   });
 }
+#else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
+template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
+template <int KIND, int FB> static int plant_attr_w() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_w<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_w<FB>()) != hipSuccess;
+}
+template <int KIND> static int step_attr_w() {
+  return hipFuncSetAttribute((const void*)k_step_w<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_W_LDS_BYTES) != hipSuccess;
+}
+static int wrench_kernels_set_attr() {
+  int rc = 0;
+  for_each_step_kind([&](auto K) { rc |= plant_attr_w<K(), 0>(); rc |= plant_attr_w<K(), 1>(); rc |= step_attr_w<K()>(); });
+  return rc;
+}
+template <int KIND, int FB>
+static void follow_launch_w(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_w<KIND, FB>), grid, dim3(64), follow_lds_w<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0);
+}
+static void launch_plant_follow_wrench(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const int* sched, long sched_stride, int geom, int substeps,
+                                int feedback_mode, int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st) {
+  const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (feedback_mode) follow_launch_w<K(), 1>(S, Pl, dyn, T, W, a, st);
+    else follow_launch_w<K(), 0>(S, Pl, dyn, T, W, a, st);
+  });
+}
+static void launch_step_wrench(int count, const double* x, const double* u, const DynParams& dyn, double* xn, int stance_l, int stance_r, const double* wrench, hipStream_t st) {
+  const dim3 grid((unsigned)((count + 31) / 32));
+  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_w<K()>), grid, dim3(64), STEP_W_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench); });
+}
+#endif
 
 }  // namespace ilqr
+
+#ifdef PLANT_WRENCH_MODULE
+extern "C" {
+int ilqr_wrench_module_set_attr() { return ilqr::wrench_kernels_set_attr(); }
+void ilqr_wrench_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
+  ilqr::launch_plant_follow_wrench(*S, *Pl, *dyn, *T, *W, a->sched, a->sched_stride, a->geom, a->substeps, a->feedback_mode, a->kick, a->first_knot, a->count, a->hist_row0, a->hist_cap, st);
+}
+void ilqr_wrench_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, hipStream_t st) {
+  ilqr::launch_step_wrench(count, x, u, *dyn, xn, stance_l, stance_r, wrench, st);
+}
+}
+#endif

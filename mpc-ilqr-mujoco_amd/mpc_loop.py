@@ -52,6 +52,10 @@ solver's model: `plant_model` gives the plant its own contact mode and joint-lim
 BatchedILQR.plant_set_model), `plant_params` [1, 7] or [B, 7] (scenario.stack_plant_params) its own gravity, friction, softness,
 joint-limit stiffness and torque gain, one set for all rollouts or one per rollout (BatchedILQR.plant_set_params).  Both are installed
 before the plant is reset and stay on the handle after the run; the solve keeps the solver's model throughout.
+
+`MPCRunner(..., resident=True, plant_wrench=W)` pushes the plant: W [1, 11] or [B, 11] (scenario.stack_plant_wrench) is a sustained external
+wrench on the pelvis per rollout -- force, torque, point of application and the window of plant intervals it acts in, counted from the
+reset of the run (BatchedILQR.plant_set_wrench).  Installed behind the parameter sets, in front of the reset; the solve does not know of it.
 """
 import os
 import time
@@ -96,7 +100,7 @@ class MPCRunner:
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
-                 device_refs=False, track_starts=None, plant_params=None, plant_model=None):
+                 device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -120,6 +124,13 @@ class MPCRunner:
             if plant_params.ndim != 2 or plant_params.shape[1] != 7 or plant_params.shape[0] not in (1, solver.B):
                 raise ValueError("plant_params must be [1, 7] or [B, 7] (scenario.stack_plant_params)")
         self.plant_params, self.plant_model = plant_params, None if plant_model is None else tuple(plant_model)
+        if not resident and plant_wrench is not None:
+            raise ValueError("plant_wrench needs the device-resident plant (resident=True)")
+        if plant_wrench is not None:
+            plant_wrench = np.atleast_2d(np.asarray(plant_wrench, dtype=np.float64))
+            if plant_wrench.ndim != 2 or plant_wrench.shape[1] != 11 or plant_wrench.shape[0] not in (1, solver.B):
+                raise ValueError("plant_wrench must be [1, 11] or [B, 11] (scenario.stack_plant_wrench)")
+        self.plant_wrench = plant_wrench
         self.device_refs, self.track_ready = bool(device_refs), False
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
@@ -254,6 +265,8 @@ class MPCRunner:
         s.plant_configure(self.substeps, self.feedback_mode, self.plant_contacts)
         if self.plant_params is not None:
             s.plant_set_params(self.plant_params)
+        if self.plant_wrench is not None:
+            s.plant_set_wrench(self.plant_wrench)
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)

@@ -123,6 +123,36 @@ def stack_plant_params(B, gravity=None, friction=None, softness=None, limit_stif
     return out
 
 
+def stack_plant_wrench(B, force=None, torque=None, point=None, first=0, end=np.inf):
+    """External wrenches on the pelvis [B, 11] for BatchedILQR.plant_set_wrench / MPCRunner(plant_wrench=...): columns force x, y, z (world
+    frame, N), torque x, y, z (world frame, N m), point of application x, y, z (pelvis frame, m; solver.pelvis_inertial_offset() is
+    MuJoCo's xfrc_applied), first and end of the window of plant intervals the wrench acts in (first <= i < end, counted from plant_reset).
+    Each vector is [3] for all rollouts or [B, 3], None is zero; first / end are a scalar or [B], end may be inf.  Raises ValueError for a
+    shape that is neither, a non-finite entry other than end = inf, a negative or non-integral first / end, or end < first."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    out = np.empty((B, 11))
+    for col, name, val in ((0, "force", force), (3, "torque", torque), (6, "point", point)):
+        v = np.zeros(3) if val is None else np.asarray(val, dtype=np.float64)
+        if v.shape not in ((3,), (B, 3)):
+            raise ValueError("%s must be [3] or [B, 3]" % name)
+        out[:, col:col + 3] = v
+    for col, name, val in ((9, "first", first), (10, "end", end)):
+        v = np.asarray(val, dtype=np.float64)
+        if v.shape not in ((), (B,)):
+            raise ValueError("%s must be a scalar or [B]" % name)
+        out[:, col] = v
+    if not np.isfinite(out[:, :10]).all() or np.isnan(out[:, 10]).any() or (out[:, 10] == -np.inf).any():
+        raise ValueError("plant wrenches must be finite (end may be inf)")
+    fin_end = np.where(np.isfinite(out[:, 10]), out[:, 10], 0.0)
+    if (out[:, 9] < 0).any() or (out[:, 10] < 0).any() or (out[:, 9] != np.floor(out[:, 9])).any() or (fin_end != np.floor(fin_end)).any():
+        raise ValueError("first and end must be non-negative integers")
+    if (out[:, 10] < out[:, 9]).any():
+        raise ValueError("end >= first is required")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

@@ -48,6 +48,8 @@ EXPORTS = [
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
     "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
     "ilqr_hip_plant_set_model", "ilqr_hip_plant_set_params", "ilqr_hip_plant_clear_params", "ilqr_hip_plant_num_param_sets", "ilqr_hip_plant_get_params",
+    "ilqr_hip_plant_set_wrench", "ilqr_hip_plant_clear_wrench", "ilqr_hip_plant_num_wrench_sets", "ilqr_hip_plant_get_wrench", "ilqr_hip_plant_intervals",
+    "ilqr_hip_step_wrench", "ilqr_hip_pelvis_inertial_offset",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
@@ -55,6 +57,8 @@ REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref"
 PLANT_SCORE_TERMS = ("state", "control", "upright", "balance", "joint_limits", "control_limits", "min_pelvis_height", "intervals")
 # columns of a plant parameter set (include/ilqr_hip.h ILQR_PLANT_PARAMS)
 PLANT_PARAMS = ("gravity_x", "gravity_y", "gravity_z", "friction", "softness", "limit_stiffness", "torque_gain")
+# columns of a plant wrench record (include/ilqr_hip.h ILQR_PLANT_WRENCH)
+PLANT_WRENCH = ("force_x", "force_y", "force_z", "torque_x", "torque_y", "torque_z", "point_x", "point_y", "point_z", "first", "end")
 
 
 
@@ -123,6 +127,15 @@ def foot_clearance(qpos):
     if rc:
         raise ILQRError(STATUS.get(rc, str(rc)))
     return clr
+
+
+def pelvis_inertial_offset():
+    """Centre of mass of the pelvis body in the pelvis frame [3]: a wrench applied at this point is MuJoCo's xfrc_applied (host only)."""
+    r = np.zeros(3)
+    fn = load_library().ilqr_hip_pelvis_inertial_offset
+    fn.restype = None
+    fn(_p(r))
+    return r
 
 
 def gravity_compensation(x, gravity):
@@ -499,6 +512,16 @@ class BatchedILQR:
         self._chk(self.L.ilqr_hip_step_stance(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(xn)))
         return xn
 
+    def step_wrench(self, x, u, stance_left, stance_right, wrench):
+        """step_stance with one external wrench on the pelvis per item: wrench [count, 9] = force, torque (world frame) and point of
+        application (pelvis frame); always the two-lane step (ilqr_hip_step_wrench)."""
+        x, u, wrench = _c64(x), _c64(u), _c64(wrench)
+        if wrench.shape != (x.shape[0], 9):
+            raise ValueError("wrench must be [count, 9]")
+        xn = np.zeros_like(x)
+        self._chk(self.L.ilqr_hip_step_wrench(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(xn)))
+        return xn
+
     def set_stance_source(self, source):
         """Stance source of the dynamics (include/ilqr_hip.h): "schedule" (default) or "geometry" -- every step takes the stance flags from
         its own feet (a foot touches iff its ankle-link hull reaches the floor, foot_clearance < 0); the cost keeps the schedule."""
@@ -657,6 +680,34 @@ class BatchedILQR:
     def plant_params(self):
         """[B, 7] (columns PLANT_PARAMS): the values the plant would step each rollout with now; without a table the handle's and gain 1."""
         return self._get("ilqr_hip_plant_get_params", (self.B, len(PLANT_PARAMS)))
+
+    def plant_set_wrench(self, wrench):
+        """Install external wrenches on the pelvis [n_sets, 11] (columns PLANT_WRENCH; scenario.stack_plant_wrench builds them), n_sets 1 or B:
+        rollout b's plant steps under force, torque and point of application of its record in the plant intervals first <= i < end, counted
+        from plant_reset (ilqr_hip_plant_set_wrench).  The solve does not know of it."""
+        wrench = _c64(wrench)
+        if wrench.ndim == 1:
+            wrench = wrench[None]
+        if wrench.ndim != 2 or wrench.shape[1] != len(PLANT_WRENCH) or wrench.shape[0] not in (1, self.B):
+            raise ValueError("plant wrenches must be [1, 11] or [B, 11]")
+        self._chk(self.L.ilqr_hip_plant_set_wrench(self.h, _p(wrench), int(wrench.shape[0])))
+
+    def plant_clear_wrench(self):
+        """Remove the wrenches: the plant calls launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_clear_wrench(self.h))
+
+    def plant_num_wrench_sets(self):
+        return int(self.L.ilqr_hip_plant_num_wrench_sets(self.h))
+
+    def plant_wrench(self):
+        """[B, 11] (columns PLANT_WRENCH): the record of each rollout; zeros without a table."""
+        return self._get("ilqr_hip_plant_get_wrench", (self.B, len(PLANT_WRENCH)))
+
+    def plant_intervals(self):
+        """Plant intervals run since the last plant_reset (plant_advance adds 1, plant_follow its count)."""
+        fn = self.L.ilqr_hip_plant_intervals
+        fn.restype = C.c_long
+        return int(fn(self.h))
 
     def plant_score(self):
         """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""
