@@ -290,7 +290,8 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* ctx, int* stance);
    ilqr_hip_plant_advance, and the solve's own synchronisation is the only one of the step for a moving reference too.  Solving every
    m-th interval only: ilqr_hip_initialize_warm_from_plant_shifted(ctx, m) -> ilqr_hip_solve -> ilqr_hip_plant_follow(ctx, 0, m), see
    there.  External wrenches on the pelvis: ilqr_hip_plant_set_wrench, below; a plant whose contact model or parameters are not the
-   solver's: ilqr_hip_plant_set_model / ilqr_hip_plant_set_params. */
+   solver's: ilqr_hip_plant_set_model / ilqr_hip_plant_set_params; a plant that carries a load the solver does not know of:
+   ilqr_hip_plant_set_payload. */
 /* Upload the plant state x[B][51] (robot.getState's counterpart in reverse: RobotUtils::setState).  Every rollout becomes alive, a pending
    kick is dropped, the history cursor returns to 0.  Synchronises the handle's stream. */
 int ilqr_hip_plant_reset(ilqr_hip_ctx* ctx, const double* x /*[B][51]*/);
@@ -449,6 +450,37 @@ int ilqr_hip_plant_get_wrench(ilqr_hip_ctx* ctx, double* wrench /*[B][11]*/);
 long ilqr_hip_plant_intervals(const ilqr_hip_ctx* ctx);
 int ilqr_hip_step_wrench(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench /*[count][9]*/, double* x_next);
 void ilqr_hip_pelvis_inertial_offset(double r[3]);
+/* ---- rigid payload fixed to the pelvis, one per rollout: a plant whose mass distribution is not the solver's -- the robot carries a load
+   it did not plan for.  Plant only: rollout, line search, Jacobians, warm-start tail, ilqr_hip_gravity_compensation and the score's
+   capture-point centre of mass keep the solver's model.  No reference counterpart (its plant and its solver share one model file).
+   One record of ILQR_PLANT_PAYLOAD doubles per set:
+     0     mass m, kg                        1..3  centre of mass c, pelvis frame, m (a backpack at torso height: c ~ (-0.1, 0, 0.3))
+     4..9  Ixx, Iyy, Izz, Ixy, Ixz, Iyz of the rotational inertia Ic about the payload's own centre of mass, pelvis axes, kg m^2
+   The pelvis is the root of the articulated-body recursion, so the payload's spatial inertia about the pelvis origin,
+   dI = [[Ic + m (|c|^2 E - c c^T), m [c]x], [-m [c]x, m E]] (angular, then linear), joins the pelvis' own in every substep: in its
+   articulated inertia and in its velocity-product force.  Gravity needs no term (the recursion works in the frame that accelerates with
+   -g); stance rows, joint-limit rows and the wrench's pelvis solve all read the loaded pelvis, in all six step kinds.  Permanent from set
+   to clear: no window.
+   plant_set_payload: n_sets = 1 or the batch, else ILQR_ERR_ARG; ILQR_ERR_ARG also for a null pointer, a non-finite entry, m < 0 or an Ic
+   that is not positive semidefinite (its seven principal minors >= 0 up to rounding), all checked before the handle is touched.  The table
+   is a device buffer of 128-byte records owned by the handle; the call uploads it and synchronises the handle's stream.  It survives
+   ilqr_hip_plant_reset and ilqr_hip_plant_configure.  While it is installed ilqr_hip_plant_advance / _follow launch the payload family of
+   the plant kernel (k_plant_follow_m of the module libilqr_hip_payload.so, opened from the library's directory on first use -- missing:
+   ILQR_ERR_UNSUPPORTED with the path in ilqr_hip_last_error; an advance is that kernel over one interval) and then the score kernels as
+   before.  The family carries parameter record, wrench and payload together: ring, score, alive, kick, the non-finite guards, the reported
+   control, a parameter table and a wrench table with its window behave as without the payload.
+   plant_clear_payload: frees it; the plant calls then launch exactly what they launch without it.
+   plant_num_payload_sets: 0 without a table, else n_sets; -1 for a null handle.
+   plant_get_payload: payload[B][10], the record of each rollout (zeros without a table).
+   step_payload: ilqr_hip_step_wrench with one payload record per item as well; wrench may be NULL (none).  ILQR_ERR_ARG for a null
+   x / u / payload / x_next, count <= 0 or a record that plant_set_payload would refuse; ILQR_ERR_UNSUPPORTED as ilqr_hip_step_wrench. */
+#define ILQR_PLANT_PAYLOAD 10   /* m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz */
+int ilqr_hip_plant_set_payload(ilqr_hip_ctx* ctx, const double* payload /*[n_sets][10]*/, int n_sets);
+int ilqr_hip_plant_clear_payload(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_num_payload_sets(const ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_payload(ilqr_hip_ctx* ctx, double* payload /*[B][10]*/);
+int ilqr_hip_step_payload(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench /*[count][9], NULL: none*/,
+                          const double* payload /*[count][10]*/, double* x_next);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

@@ -209,6 +209,19 @@ class iLQR {
     if (count < 1 || x.size() != (size_t)count * ILQR_NX || u.size() != (size_t)count * ILQR_NU || wrench.size() != (size_t)count * 9) throw std::runtime_error("stepWrench: x [count][51], u [count][19], wrench [count][9]");
     Vec xn((size_t)count * ILQR_NX); chk(ilqr_hip_step_wrench(ctx_, count, x.data(), u.data(), stance_left, stance_right, wrench.data(), xn.data())); return xn;
   }
+  // rigid payload on the pelvis per rollout (ilqr_hip.h ilqr_hip_plant_set_payload): [n_sets][10] = m, c (pelvis frame), Ixx, Iyy, Izz, Ixy, Ixz, Iyz about c
+  void plantSetPayload(const Vec& payload, int n_sets) {
+    if (n_sets < 1 || payload.size() != (size_t)n_sets * ILQR_PLANT_PAYLOAD) throw std::runtime_error("payload must hold n_sets * 10 doubles");
+    chk(ilqr_hip_plant_set_payload(ctx_, payload.data(), n_sets));
+  }
+  void plantClearPayload() { chk(ilqr_hip_plant_clear_payload(ctx_)); }
+  int plantNumPayloadSets() const { return ilqr_hip_plant_num_payload_sets(ctx_); }
+  Vec plantPayload() { Vec p((size_t)B_ * ILQR_PLANT_PAYLOAD); chk(ilqr_hip_plant_get_payload(ctx_, p.data())); return p; }      // [batch][10]
+  Vec stepPayload(int count, const Vec& x, const Vec& u, int stance_left, int stance_right, const Vec& wrench /*[count][9] or empty: none*/, const Vec& payload /*[count][10]*/) {
+    if (count < 1 || x.size() != (size_t)count * ILQR_NX || u.size() != (size_t)count * ILQR_NU || (!wrench.empty() && wrench.size() != (size_t)count * 9) || payload.size() != (size_t)count * ILQR_PLANT_PAYLOAD)
+      throw std::runtime_error("stepPayload: x [count][51], u [count][19], wrench [count][9] or empty, payload [count][10]");
+    Vec xn((size_t)count * ILQR_NX); chk(ilqr_hip_step_payload(ctx_, count, x.data(), u.data(), stance_left, stance_right, wrench.empty() ? nullptr : wrench.data(), payload.data(), xn.data())); return xn;
+  }
   static std::array<double, 3> pelvisInertialOffset() { std::array<double, 3> r{}; ilqr_hip_pelvis_inertial_offset(r.data()); return r; }
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492

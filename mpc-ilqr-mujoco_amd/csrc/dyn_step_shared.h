@@ -228,7 +228,14 @@ DEVFN void step_any(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynPara
 // behind the kernel's layout and crosses every call boundary as the offset `wro` of its row from the base of the workgroup's LDS, in
 // doubles: the non-inlined steps read it there, next to the dynamics scratch they already address from that base.  Each copy is its
 // original with h1s::...<WR = true> in the place of the piece it calls; the originals above keep their text.
+// Under DYN_STEP_PAYLOAD as well (the payload module of plant_kernels.hip) the same copies carry the payload of ilqr_hip_plant_set_payload too:
+// the row at `wro` is then the widened disturbance row (wrench 0..8, payload from h1s::PAYLOAD_AT), and DYN_WR picks the instantiation.
 #ifdef DYN_STEP_WRENCH
+#ifdef DYN_STEP_PAYLOAD
+#define DYN_WR true, true
+#else
+#define DYN_WR true
+#endif
 __device__ __attribute__((noinline)) void step_stance_shared_w(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
                                                                double soft, int mode, int st_left, int st_right, double mu, int geom, int wro) {
   const int lane = threadIdx.x;
@@ -238,7 +245,7 @@ __device__ __attribute__((noinline)) void step_stance_shared_w(h1s::HalfX* hp, c
   h1s::HalfX h = *hp;
   const h1s::HalfU u = *up;
   if (geom) h1s::geom_stance(side, h, st_left, st_right);
-  h1s::step_stance<false, true>(side, h, u, dt, grav, L, soft, mode, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu, dyn_lds_c + wro);
+  h1s::step_stance<false, DYN_WR>(side, h, u, dt, grav, L, soft, mode, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu, dyn_lds_c + wro);
   *hp = h;
 }
 __device__ __attribute__((noinline)) void step_stance_shared_kin_w(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
@@ -250,7 +257,7 @@ __device__ __attribute__((noinline)) void step_stance_shared_kin_w(h1s::HalfX* h
   h1s::HalfX h = *hp;
   const h1s::HalfU u = *up;
   if (geom) h1s::geom_stance(side, h, st_left, st_right);
-  h1s::step_stance<true, true>(side, h, u, dt, grav, L, soft, 4, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu, dyn_lds_c + wro);
+  h1s::step_stance<true, DYN_WR>(side, h, u, dt, grav, L, soft, 4, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu, dyn_lds_c + wro);
   *hp = h;
 }
 template <bool KIN>
@@ -267,7 +274,7 @@ __device__ __attribute__((noinline)) void lim_accelerations_w(const h1s::HalfX* 
   h1s::apply_lock_mask(side, mask, h.q, dt, kr, tau, add);
   const bool st_own = mode != 0 && (side ? st_right : st_left) == 1, st_par = mode != 0 && (side ? st_left : st_right) == 1;
   LimAcc o;
-  h1s::stance_accelerations<KIN, true, true>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, o.qb, o.qa, &add, dyn_lds_c + wro);      // (both passes carry the wrench)
+  h1s::stance_accelerations<KIN, true, DYN_WR>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, o.qb, o.qa, &add, dyn_lds_c + wro);      // (both passes carry the wrench)
   *out = o;
 }
 template <bool KIN>
@@ -311,7 +318,7 @@ __device__ __attribute__((noinline)) void lim_second_pass_lds_w(double dt, doubl
   h1s::stance_prepare(side, h, u, qh, R0, tau);
   h1s::apply_lock_mask(side, mask, h.q, dt, kr, tau, add);
   double qb[6]; h1s::HalfAcc qa;
-  h1s::forward_dynamics<true, true>(side, R0, h.vb, h.q, tau, h1s::ARMATURE + dt * h1s::DAMPING, grav, L, qb, qa, nullptr, nullptr, &add, dyn_lds_c + wro);
+  h1s::forward_dynamics<true, DYN_WR>(side, R0, h.vb, h.q, tau, h1s::ARMATURE + dt * h1s::DAMPING, grav, L, qb, qa, nullptr, nullptr, &add, dyn_lds_c + wro);
 #pragma unroll
   for (int k = 0; k < 6; ++k) L[k] = qb[k];
   L[6] = qa.q11;
@@ -330,7 +337,7 @@ DEVFN void step_any_w(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynPa
     double qh[4], R0[9]; h1s::HalfTau tau;
     h1s::stance_prepare(side, h, uo, qh, R0, tau);
     double qb[6]; h1s::HalfAcc qa;
-    h1s::forward_dynamics<false, true>(side, R0, h.vb, h.q, tau, h1s::ARMATURE + dt * h1s::DAMPING, dyn.g, L, qb, qa, nullptr, nullptr, nullptr, L.base + wro);
+    h1s::forward_dynamics<false, DYN_WR>(side, R0, h.vb, h.q, tau, h1s::ARMATURE + dt * h1s::DAMPING, dyn.g, L, qb, qa, nullptr, nullptr, nullptr, L.base + wro);
     const unsigned mask = h1s::limit_lock_mask(side, h.q, qa, dt, dyn.lim_k);
     const bool any = mask != 0u;
     if (h1s::xch_flag(any) || any) {
@@ -361,7 +368,7 @@ DEVFN void step_any_w(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynPa
     double dt = dyn.h; asm volatile("" : "+s"(dt));
     h1s::HalfU uo = u;
     pin_half(h); pin_half_u(uo);
-    h1s::step<true>(side, h, uo, dt, dyn.g, L, L.base + wro);
+    h1s::step<DYN_WR>(side, h, uo, dt, dyn.g, L, L.base + wro);
     pin_half(h);
   }
 }

@@ -451,7 +451,34 @@ DEVFN void pelvis_rhs(const double* R0, const double* p0, const double* wr, doub
     for (int k = 0; k < 3; ++k) { rhs[k] += Tb[k] + rxF[k]; rhs[3 + k] += Fb[k]; }
   }
 }
-template <bool PER = false, bool WR = false>
+// PL: a rigid payload fixed to the pelvis (ilqr_hip_plant_set_payload), behind the wrench in the same row: pl = wr + PAYLOAD_AT holds the mass m,
+// the centre of mass c (pelvis frame) and Ixx, Iyy, Izz, Ixy, Ixz, Iyz of the rotational inertia Ic about c (pelvis axes).  Its spatial inertia
+// about the pelvis origin, dI = [[Ic + m (|c|^2 E - c c^T), m [c]x], [-m [c]x, m E]], joins the pelvis' own: Y0 += dI and, in the velocity-product
+// force, Iv += dI v0.  Gravity needs no term (the recursion works in the frame that accelerates with -g), and everything that reads Y0 afterwards
+// -- the pelvis solve, the stance rows' unit-wrench responses, the second pass of the joint limits -- sees the loaded pelvis.  PL implies WR.
+// The widened disturbance row that carries both across every call boundary, its whole layout: wrench F, T, r at 0..8, the wrench's window
+// first, end at DIST_FIRST, DIST_END (read by the kernel that picks the row, not by the step), the payload's PAYLOAD_VALS values from
+// PAYLOAD_AT, padding up to DIST_REC doubles.
+constexpr int DIST_WRENCH_VALS = 9, DIST_FIRST = 9, DIST_END = 10, PAYLOAD_AT = 11, PAYLOAD_VALS = 10, DIST_REC = 24;
+DEVFN void payload_add(const double* pl, const double* v, Art& Y, double* Iv) {
+  const double m = pl[0], cx = pl[1], cy = pl[2], cz = pl[3], cc = cx * cx + cy * cy + cz * cz;
+  Art D;
+  D.A[0] = pl[4] + m * (cc - cx * cx); D.A[1] = pl[7] - m * cx * cy; D.A[2] = pl[8] - m * cx * cz;
+  D.A[3] = pl[5] + m * (cc - cy * cy); D.A[4] = pl[9] - m * cy * cz; D.A[5] = pl[6] + m * (cc - cz * cz);
+  D.B[0] = 0.0; D.B[1] = -m * cz; D.B[2] = m * cy; D.B[3] = m * cz; D.B[4] = 0.0; D.B[5] = -m * cx; D.B[6] = -m * cy; D.B[7] = m * cx; D.B[8] = 0.0;
+  D.C[0] = m; D.C[1] = 0.0; D.C[2] = 0.0; D.C[3] = m; D.C[4] = 0.0; D.C[5] = m;
+  art_add(Y, D);
+  // dI v as inertia_mul has it: f_lin = m (v_lin + w x c), f_ang = Ic w + c x f_lin
+  const double c[3] = {cx, cy, cz};
+  double wc[3]; cross(v, c, wc);
+  const double fl[3] = {m * (v[3] + wc[0]), m * (v[4] + wc[1]), m * (v[5] + wc[2])};
+  double cf[3]; cross(c, fl, cf);
+  Iv[0] += pl[4] * v[0] + pl[7] * v[1] + pl[8] * v[2] + cf[0];
+  Iv[1] += pl[7] * v[0] + pl[5] * v[1] + pl[9] * v[2] + cf[1];
+  Iv[2] += pl[8] * v[0] + pl[9] * v[1] + pl[6] * v[2] + cf[2];
+  Iv[3] += fl[0]; Iv[4] += fl[1]; Iv[5] += fl[2];
+}
+template <bool PER = false, bool WR = false, bool PL = false>
 DEVFN void forward_dynamics(bool side, const double* R0, const double* vb, const HalfState& q, const HalfTau& tau, double arm_eff,
                             const double* grav, const LaneLds& L, double* qbase, HalfAcc& qacc, Art* Y0_out = nullptr, double* a0_out = nullptr,
                             const HalfTau* arm_add = nullptr, const double* wr = nullptr) {
@@ -491,7 +518,9 @@ DEVFN void forward_dynamics(bool side, const double* R0, const double* vb, const
 #pragma unroll
     for (int k = 0; k < 6; ++k) p0[k] += pl[k];
     Art Yb; body_inertia<0, 0>(side, Yb); art_add(Y0, Yb);
-    double Iv[6], pv[6]; inertia_mul<0, 0>(side, v0, Iv); crf(v0, Iv, pv);
+    double Iv[6], pv[6]; inertia_mul<0, 0>(side, v0, Iv);
+    if constexpr (PL) payload_add(wr + PAYLOAD_AT, v0, Y0, Iv);
+    crf(v0, Iv, pv);
 #pragma unroll
     for (int k = 0; k < 6; ++k) p0[k] += pv[k];
   }
@@ -588,7 +617,7 @@ DEVFN void ldl6_solve(const Ldl6& F, const double* rhs, double* out) {
 // sink(body, v, a, sin, cos) for every body of this lane's side (pelvis and torso: both lanes report them), the explicit
 // inverse of the pelvis' articulated inertia and the pelvis' linear acceleration without the gravity term.  U, 1/D stay in
 // this lane's LDS slots (torso: slot block 0, leg hinge K: 8 + 8 K, arm hinge K: 48 + 8 K).
-template <class Sink, bool PER = false, bool WR = false>
+template <class Sink, bool PER = false, bool WR = false, bool PL = false>
 DEVFN void forward_dynamics_dump(bool side, const double* R0, const double* vb, const HalfState& q, const HalfTau& tau, double arm_eff, const double* grav,
                                  const LaneLds& L, double* qbase, HalfAcc& qacc, Sink& sink, double* inv36, double* aL, const HalfTau* arm_add = nullptr,
                                  const double* wr = nullptr) {
@@ -625,7 +654,9 @@ DEVFN void forward_dynamics_dump(bool side, const double* R0, const double* vb, 
 #pragma unroll
     for (int k = 0; k < 6; ++k) p0[k] += pl[k];
     Art Yb; body_inertia<0, 0>(side, Yb); art_add(Y0, Yb);
-    double Iv[6], pv[6]; inertia_mul<0, 0>(side, v0, Iv); crf(v0, Iv, pv);
+    double Iv[6], pv[6]; inertia_mul<0, 0>(side, v0, Iv);
+    if constexpr (PL) payload_add(wr + PAYLOAD_AT, v0, Y0, Iv);
+    crf(v0, Iv, pv);
 #pragma unroll
     for (int k = 0; k < 6; ++k) p0[k] += pv[k];
   }
@@ -1053,7 +1084,7 @@ DEVFN void store_half(bool side, const HalfX& h, double* x) {
 DEVFN double clampu(double u, const double* range) { return u < range[0] ? range[0] : (u > range[1] ? range[1] : u); }
 
 // x <- f(x, u) in place: RobotUtils::rolloutOneStep (reference src/common/robot_utils.cpp:106-117), smooth regime
-template <bool WR = false>
+template <bool WR = false, bool PL = false>
 DEVFN void step(bool side, HalfX& h, const HalfU& u, double dt, const double* grav, const LaneLds& L, const double* wr = nullptr) {
   const double qn = sqrt(h.quat[0] * h.quat[0] + h.quat[1] * h.quat[1] + h.quat[2] * h.quat[2] + h.quat[3] * h.quat[3]);
   const double qh[4] = {h.quat[0] / qn, h.quat[1] / qn, h.quat[2] / qn, h.quat[3] / qn};
@@ -1073,7 +1104,7 @@ DEVFN void step(bool side, HalfX& h, const HalfU& u, double dt, const double* gr
     tau.tA[k] = uc - DAMPING * h.q.qdA[k];
   }
   double qb[6]; HalfAcc qa;
-  if constexpr (WR) forward_dynamics<false, true>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, nullptr, nullptr, nullptr, wr);
+  if constexpr (WR) forward_dynamics<false, true, PL>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, nullptr, nullptr, nullptr, wr);
   else forward_dynamics(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa);
   // semi-implicit Euler: v' = v + h qacc, q' = q (+) h v'
 #pragma unroll
@@ -1165,11 +1196,11 @@ DEVFN void stance_prepare(bool side, const HalfX& h, const HalfU& u, double* qh,
     tau.tA[k] = uc - DAMPING * h.q.qdA[k];
   }
 }
-template <bool KIN, bool PER, bool WR = false>
+template <bool KIN, bool PER, bool WR = false, bool PL = false>
 DEVFN void stance_accelerations(bool side, const double* R0, const HalfX& h, const HalfTau& tau, double dt, const double* grav, const LaneLds& L, double soft, int mode,
                                 bool st_own, bool st_par, double mu, double* qb, HalfAcc& qa, const HalfTau* add = nullptr, const double* wr = nullptr) {
   Art Y0; double a0[6];
-  forward_dynamics<PER, WR>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, &Y0, a0, add, wr);
+  forward_dynamics<PER, WR, PL>(side, R0, h.vb, h.q, tau, ARMATURE + dt * DAMPING, grav, L, qb, qa, &Y0, a0, add, wr);
   if (st_own || st_par) stance_correct<KIN>(side, R0, h.vb, h.q, dt, soft, mode, st_own, st_par, grav, L, Y0, a0, qb, qa, mu);
 }
 DEVFN void integrate_half(HalfX& h, const double* qh, const double* qb, const HalfAcc& qa, double dt) {
@@ -1195,13 +1226,13 @@ DEVFN void integrate_half(HalfX& h, const double* qh, const double* qb, const Ha
   h.quat[0] = rw / rn; h.quat[1] = rx / rn; h.quat[2] = ry / rn; h.quat[3] = rz / rn;
 }
 // x <- f(x, u) with the stance constraints of the scheduled feet (contact mode 1 / 2 / 3 / 4)
-template <bool KIN = false, bool WR = false>
+template <bool KIN = false, bool WR = false, bool PL = false>
 DEVFN void step_stance(bool side, HalfX& h, const HalfU& u, double dt, const double* grav, const LaneLds& L, double soft, int mode, bool st_own, bool st_par, double mu = 1.0,
                        const double* wr = nullptr) {
   double qh[4], R0[9]; HalfTau tau;
   stance_prepare(side, h, u, qh, R0, tau);
   double qb[6]; HalfAcc qa;
-  stance_accelerations<KIN, false, WR>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, qb, qa, nullptr, wr);
+  stance_accelerations<KIN, false, WR, PL>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, qb, qa, nullptr, wr);
   integrate_half(h, qh, qb, qa, dt);
 }
 

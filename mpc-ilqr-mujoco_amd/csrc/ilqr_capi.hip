@@ -164,6 +164,13 @@ struct ilqr_hip_ctx {
   double* d_stepw = nullptr;  // [step_w_cap][9] wrenches of ilqr_hip_step_wrench
   size_t step_w_cap = 0;
   bool wrench_attr_set = false;   // the wrench module's kernels have their LDS attributes on this handle's device
+  // payload table (ilqr_hip_plant_set_payload; plant_kernels.hip k_plant_follow_m): [n][16] doubles (128-byte records), n = 1 or B; null: none.
+  // While it is installed the plant calls launch the payload family, which reads d_self_params / d_wrench as the wrench family does.
+  double* d_ppayload = nullptr;
+  int payload_sets = 0;
+  double* d_stepm = nullptr;  // [step_m_cap][10] payloads of ilqr_hip_step_payload (its wrenches go through d_stepw)
+  size_t step_m_cap = 0;
+  bool payload_attr_set = false;  // the payload module's kernels have their LDS attributes on this handle's device
   long plant_intervals = 0;   // plant intervals run since the last ilqr_hip_plant_reset (the history cursor only counts while a ring exists)
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
@@ -291,6 +298,49 @@ static int need_wrench_module(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 
+// The payload family (csrc/Makefile ../lib/libilqr_hip_payload.so) is a module of its own in the same way, opened on the first
+// ilqr_hip_plant_set_payload / ilqr_hip_step_payload.
+namespace {
+struct PayloadModule {
+  void* lib = nullptr;
+  ilqr::payload_set_attr_fn set_attr = nullptr;
+  ilqr::payload_follow_fn follow = nullptr;
+  ilqr::payload_step_fn step = nullptr;
+  std::string why;
+  bool ok() const { return lib && set_attr && follow && step; }
+};
+PayloadModule& payload_module() {
+  static PayloadModule m;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    Dl_info info;
+    std::string dir = ".";
+    if (dladdr((const void*)&ilqr_hip_plant_num_payload_sets, &info) && info.dli_fname) {
+      const std::string self = info.dli_fname;
+      const size_t slash = self.rfind('/');
+      if (slash != std::string::npos) dir = self.substr(0, slash);
+    }
+    const std::string path = dir + "/libilqr_hip_payload.so";
+    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!m.lib) { m.why = "the payload kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.set_attr = (ilqr::payload_set_attr_fn)dlsym(m.lib, "ilqr_payload_module_set_attr");
+    m.follow = (ilqr::payload_follow_fn)dlsym(m.lib, "ilqr_payload_module_follow");
+    m.step = (ilqr::payload_step_fn)dlsym(m.lib, "ilqr_payload_module_step");
+    if (!m.ok()) m.why = "the payload kernels' module lacks an entry point: " + path;
+  });
+  return m;
+}
+}  // namespace
+static int need_payload_module(ilqr_hip_ctx* c) {
+  PayloadModule& m = payload_module();
+  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
+  if (!c->payload_attr_set) {
+    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the payload kernels"; return ILQR_ERR_HIP; }
+    c->payload_attr_set = true;
+  }
+  return ILQR_OK;
+}
+
 extern "C" {
 
 int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt) {
@@ -378,7 +428,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1447,6 +1497,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and
 // joint-limit option where ilqr_hip_plant_set_model has given it one.  (With a parameter table the kernels replace g, mu, soft and lim_k per rollout.)
 constexpr int WRENCH_REC = 16;      // doubles of a wrench record on the device (128 B): the ILQR_PLANT_WRENCH values and padding
+constexpr int PAYLOAD_REC = 16;     // doubles of a payload record on the device (128 B): the ILQR_PLANT_PAYLOAD values and padding
 static h1::DynParams plant_dyn(const ilqr_hip_ctx* c) {
   h1::DynParams dyn = c->P.dyn;
   dyn.h = c->P.dyn.h / c->plant_substeps;
@@ -1463,7 +1514,7 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
 // The wrench family (k_plant_follow_w) always reads a parameter record: the parameter table's, or this ONE record of the handle's own values
 // with gain 1, uploaded again whenever the handle's values have changed.
 static int plant_self_params(ilqr_hip_ctx* c) {
-  if (!c->d_wrench || c->d_pparams) return ILQR_OK;
+  if ((!c->d_wrench && !c->d_ppayload) || c->d_pparams) return ILQR_OK;
   const h1::DynParams& d = c->P.dyn;
   const double rec[ILQR_PLANT_PARAMS + 1] = {d.g[0], d.g[1], d.g[2], d.mu, d.soft, d.lim_k, 1.0, 0.0};
   if (c->d_self_params && std::memcmp(rec, c->self_params, sizeof(rec)) == 0) return ILQR_OK;
@@ -1479,7 +1530,13 @@ static int plant_self_params(ilqr_hip_ctx* c) {
 // With a wrench table: the wrench family of the module, under the parameter table or the handle's own record (plant_self_params).
 static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  if (c->d_wrench) {
+  if (c->d_ppayload) {      // the payload family: parameter record, wrench (none: a null table) and payload together
+    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
+    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+    payload_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, &a, c->stream);      // (the callers have checked the module: need_payload_module)
+  } else if (c->d_wrench) {
     const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
     const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
     const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
@@ -1535,6 +1592,7 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
   TRY(plant_self_params(c));
+  if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
@@ -1572,6 +1630,7 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
     return ILQR_ERR_STATE;
   }
   TRY(plant_self_params(c));
+  if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
@@ -1774,6 +1833,104 @@ int ilqr_hip_step_wrench(ilqr_hip_ctx* c, int count, const double* x, const doub
   HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, (size_t)count * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   wrench_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, c->d_stepw, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+// ---- rigid payload on the pelvis per rollout (plant_kernels.hip k_plant_follow_m, k_step_m)
+// the checks of a payload record that need no handle: every entry finite, m >= 0, Ic positive semidefinite -- its seven principal minors
+// non-negative up to rounding (relative to the products they are differences of)
+static bool payload_values_ok(const double* r) {
+  for (int i = 0; i < ILQR_PLANT_PAYLOAD; ++i) if (!std::isfinite(r[i])) return false;
+  if (r[0] < 0.0) return false;
+  const double xx = r[4], yy = r[5], zz = r[6], xy = r[7], xz = r[8], yz = r[9];
+  const double eps = 1e-12;
+  if (xx < 0.0 || yy < 0.0 || zz < 0.0) return false;
+  if (xx * yy - xy * xy < -eps * (xx * yy + xy * xy) || xx * zz - xz * xz < -eps * (xx * zz + xz * xz) || yy * zz - yz * yz < -eps * (yy * zz + yz * yz)) return false;
+  const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+  const double mag = std::fabs(xx * yy * zz) + std::fabs(xx * yz * yz) + std::fabs(xy * xy * zz) + 2.0 * std::fabs(xy * yz * xz) + std::fabs(yy * xz * xz);
+  return det >= -eps * mag;
+}
+int ilqr_hip_plant_set_payload(ilqr_hip_ctx* c, const double* payload, int n_sets) {
+  if (!payload || n_sets < 1) return ILQR_ERR_ARG;
+  for (int s = 0; s < n_sets; ++s) if (!payload_values_ok(payload + (size_t)s * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
+  if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(need_payload_module(c));
+  std::vector<double> rec((size_t)n_sets * PAYLOAD_REC, 0.0);      // (128-byte records: the ten values and six doubles of padding)
+  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * PAYLOAD_REC, payload + (size_t)s * ILQR_PLANT_PAYLOAD, ILQR_PLANT_PAYLOAD * sizeof(double));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (c->d_ppayload && c->payload_sets != n_sets) { hipFree(c->d_ppayload); c->d_ppayload = nullptr; c->payload_sets = 0; }
+  if (!c->d_ppayload) HIPCHK(c, hipMalloc((void**)&c->d_ppayload, rec.size() * sizeof(double)));
+  c->payload_sets = n_sets;
+  HIPCHK(c, hipMemcpyAsync(c->d_ppayload, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_clear_payload(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->d_ppayload) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+    hipFree(c->d_ppayload);
+  }
+  c->d_ppayload = nullptr; c->payload_sets = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_num_payload_sets(const ilqr_hip_ctx* c) { return c ? c->payload_sets : -1; }
+int ilqr_hip_plant_get_payload(ilqr_hip_ctx* c, double* payload) {
+  if (!c || !payload) return ILQR_ERR_ARG;
+  enter(c);
+  constexpr int P = ILQR_PLANT_PAYLOAD;
+  if (!c->d_ppayload) {      // (no table: nothing carried)
+    std::fill(payload, payload + (size_t)c->B * P, 0.0);
+    return ILQR_OK;
+  }
+  std::vector<double> rec((size_t)c->payload_sets * PAYLOAD_REC);
+  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_ppayload, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(payload + (size_t)b * P, rec.data() + (size_t)(c->payload_sets == 1 ? 0 : b) * PAYLOAD_REC, P * sizeof(double));
+  return ILQR_OK;
+}
+int ilqr_hip_step_payload(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, const double* payload, double* x_next) {
+  if (count <= 0 || !x || !u || !payload || !x_next) return ILQR_ERR_ARG;
+  for (int i = 0; i < count; ++i) {
+    if (wrench && !wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
+    if (!payload_values_ok(payload + (size_t)i * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
+  }
+  if (!c) return ILQR_ERR_ARG;
+  TRY(enter_launching(c));
+  TRY(need_payload_module(c));
+  if (wrench && (size_t)count > c->step_w_cap) {
+    if (c->d_stepw) hipFree(c->d_stepw);
+    c->d_stepw = nullptr; c->step_w_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->d_stepw, (size_t)count * 9 * sizeof(double)));
+    c->step_w_cap = (size_t)count;
+  }
+  if ((size_t)count > c->step_m_cap) {
+    if (c->d_stepm) hipFree(c->d_stepm);
+    c->d_stepm = nullptr; c->step_m_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->d_stepm, (size_t)count * ILQR_PLANT_PAYLOAD * sizeof(double)));
+    c->step_m_cap = (size_t)count;
+  }
+  if ((size_t)count > c->step_cap) {      // (the scratch of plant_step, grown the same way)
+    if (c->d_stepx) hipFree(c->d_stepx);
+    if (c->d_stepu) hipFree(c->d_stepu);
+    if (c->d_stepn) hipFree(c->d_stepn);
+    if (c->d_stance_out) hipFree(c->d_stance_out);
+    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
+    c->step_cap = (size_t)count;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (wrench) HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, (size_t)count * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepm, payload, (size_t)count * ILQR_PLANT_PAYLOAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  payload_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, wrench ? c->d_stepw : nullptr, c->d_stepm, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

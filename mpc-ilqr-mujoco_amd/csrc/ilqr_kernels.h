@@ -207,6 +207,20 @@ struct WrenchFollowArgs { const int* sched; long sched_stride; int geom, substep
 typedef int (*wrench_set_attr_fn)();
 typedef void (*wrench_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const WrenchFollowArgs*, hipStream_t);
 typedef void (*wrench_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, hipStream_t);
+// the same with a rigid payload on the pelvis per rollout as well (ilqr_hip_plant_set_payload): rollout b reads record b * rec_stride of
+// M.records -- mass, centre of mass c[3] (pelvis frame), Ixx, Iyy, Izz, Ixy, Ixz, Iyz about c, padding; 16 doubles -- in every substep.
+// rec_stride 16 or 0 as above.  T and W as in the wrench family, except that W.records may be null: no wrench.
+struct PayloadTable {
+  const double* records;
+  int rec_stride;
+};
+// The family lives in a module of its own as well, libilqr_hip_payload.so (plant_kernels.hip compiled with -DPLANT_PAYLOAD_MODULE):
+//   int  ilqr_payload_module_set_attr()
+//   void ilqr_payload_module_follow(S, Pl, dyn, T, W, M, args, stream)
+//   void ilqr_payload_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9] or null, payload[count][10], stream)
+typedef int (*payload_set_attr_fn)();
+typedef void (*payload_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const WrenchFollowArgs*, hipStream_t);
+typedef void (*payload_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

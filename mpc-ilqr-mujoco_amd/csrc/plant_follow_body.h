@@ -1,4 +1,4 @@
-// k_plant_follow of plant_kernels.hip, as source that file includes twice -- inside namespace ilqr, behind the helpers and layouts it uses:
+// k_plant_follow of plant_kernels.hip, as source that file includes once per family -- inside namespace ilqr, behind the helpers and layouts it uses:
 //   PLANT_TABLE 0  k_plant_follow: every rollout under the DynParams of the launch.  What the preprocessor leaves of this file is then the
 //                  text the kernel has always had: the fast path keeps its machine code.
 //   PLANT_TABLE 1  k_plant_follow_p: each rollout steps with its own record of a plant parameter table (ilqr_hip_plant_set_params) -- two
@@ -6,10 +6,17 @@
 //   PLANT_TABLE 2  k_plant_follow_w: as 1 (it always reads a parameter record), and each rollout steps under the external wrench of its
 //                  record of a wrench table (ilqr_hip_plant_set_wrench) in the intervals of the record's window -- three more kernel
 //                  arguments, RPW + 1 more rows of LDS (the last one zero: the wrench outside the window), the wrench-carrying steps.
+//   PLANT_TABLE 3  k_plant_follow_m: as 2, and each rollout's pelvis carries the payload of its record of a payload table
+//                  (ilqr_hip_plant_set_payload) in every substep -- two more kernel arguments; the rollout has two widened disturbance rows in
+//                  LDS, wrench and payload / zero wrench and payload, and a substep hands the step the offset of one of them.  wtab may be
+//                  null: no wrench.
 #ifndef PLANT_TABLE
-#error "define PLANT_TABLE (0, 1 or 2) before including plant_follow_body.h"
+#error "define PLANT_TABLE (0, 1, 2 or 3) before including plant_follow_body.h"
 #endif
-#if PLANT_TABLE == 2
+#if PLANT_TABLE == 3
+#define K_PLANT_FOLLOW k_plant_follow_m
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride
+#elif PLANT_TABLE == 2
 #define K_PLANT_FOLLOW k_plant_follow_w
 #define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0
 #elif PLANT_TABLE
@@ -40,7 +47,10 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #if PLANT_TABLE
   stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
 #endif
-#if PLANT_TABLE == 2
+#if PLANT_TABLE == 3
+  constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // disturbance rows behind the parameter rows: RPW with the wrench, RPW with a zero wrench
+  stage_disturbance_records<RPW>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
+#elif PLANT_TABLE == 2
   constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // wrench rows behind the parameter rows, then the zero row
   stage_wrench_records<RPW>(S, lds + WR0, b0, wtab, wr_stride);
 #endif
@@ -93,7 +103,13 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
         if constexpr (KIND >= 1 && KIND <= 4) {
           if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
         }
-#if PLANT_TABLE == 2
+#if PLANT_TABLE == 3
+        // the wrench's window as in k_plant_follow_w; the payload has none: both rows of the rollout carry it
+        const double* wrow = lds + WR0 + pc * h1s::DIST_REC;
+        const double iv = (double)(interval0 + j);
+        const int wro = (wrow[h1s::DIST_FIRST] <= iv && iv < wrow[h1s::DIST_END]) ? WR0 + pc * h1s::DIST_REC : WR0 + (RPW + pc) * h1s::DIST_REC;
+        plant_step_table<KIND, true>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC, wro);
+#elif PLANT_TABLE == 2
         // interval interval0 + j, counted from ilqr_hip_plant_reset; the window's bounds are integers stored as doubles (end may be +inf)
         const double* wrow = lds + WR0 + pc * WRENCH_REC;
         const double iv = (double)(interval0 + j);

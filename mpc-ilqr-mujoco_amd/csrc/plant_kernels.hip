@@ -8,7 +8,8 @@
 //                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
 // A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
-// three times: without a table, with a plant parameter table (k_plant_follow_p), and with a parameter and a wrench table (k_plant_follow_w).
+// four times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w), and
+// with parameter, wrench and payload tables (k_plant_follow_m).
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -21,13 +22,22 @@ using namespace h1;
 
 namespace ilqr {
 
-// This file is compiled twice (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
+// This file is compiled three times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
 // libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
 // which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
 // library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
 // have used up.  One module serves both libraries: the plant runs on the two-lane step whatever the handle's family.
+// A third compilation, -DPLANT_PAYLOAD_MODULE into libilqr_hip_payload.so, is the payload family alone (k_plant_follow_m, k_step_m and the
+// same copies of the non-inlined steps instantiated with the payload as well), opened on first use in the same way and for the same reason.
 #ifdef PLANT_WRENCH_MODULE
 #define DYN_STEP_WRENCH      // the wrench-carrying copies of the non-inlined steps: compiled in the module alone
+#endif
+#ifdef PLANT_PAYLOAD_MODULE
+#define DYN_STEP_WRENCH
+#define DYN_STEP_PAYLOAD     // ... carrying the payload too
+#endif
+#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE)
+#define PLANT_MODULE         // a module: none of the library's own kernels and launchers
 #endif
 #include "dyn_step_shared.h"
 
@@ -110,7 +120,7 @@ DEVFN void control_law(const DevState& S, double* lds, int b0, int knot = 0) {
   }
 }
 
-#ifndef PLANT_WRENCH_MODULE
+#ifndef PLANT_MODULE
 // KIND: the CONTACT value of step_any (step_kind(dyn)); FB: feedback mode -- 0 the reference's loop, u held over the MPC interval; 1 the
 // control law re-evaluated on (xbar_0, ubar_0, K_0) before every substep.  dyn: the PLANT's parameters (h = dt / substeps).
 // sched / sched_stride: the contact schedule (row 0 of each set is the stance of this MPC step); geom: stance from the feet instead.
@@ -216,7 +226,7 @@ DEVFN void zero_half_u(h1s::HalfU& u) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) u.uA[q] = 0.0;
 }
-#ifndef PLANT_WRENCH_MODULE
+#ifndef PLANT_MODULE
 #define PLANT_TABLE 0
 #include "plant_follow_body.h"
 #endif
@@ -252,13 +262,13 @@ DEVFN void plant_step_table(bool side, h1s::HalfX& h, const h1s::HalfU& u, const
   for (int q = 0; q < 5; ++q) us.uL[q] = gain * u.uL[q];
 #pragma unroll
   for (int q = 0; q < 4; ++q) us.uA[q] = gain * u.uA[q];
-#ifdef PLANT_WRENCH_MODULE
+#ifdef PLANT_MODULE
   if constexpr (WR) step_any_w<KIND>(side, h, us, dl, st, L, geom, wro);
   else
 #endif
   step_any<KIND>(side, h, us, dl, st, L, geom);
 }
-#ifndef PLANT_WRENCH_MODULE
+#ifndef PLANT_MODULE
 #define PLANT_TABLE 1
 #include "plant_follow_body.h"
 #endif
@@ -310,8 +320,61 @@ __global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const
 
 #endif
 
+#ifdef PLANT_PAYLOAD_MODULE
+// ---- payload table (include/ilqr_hip.h ilqr_hip_plant_set_payload): k_plant_follow_m.  A rollout has two disturbance rows of h1s::DIST_REC doubles
+// in LDS behind the parameter rows, staged once per launch, consecutive lanes on consecutive doubles (12 KB at FB = 0, 1.5 KB at FB = 1):
+//   row r        the wrench record (F, T, r, first, end; zeros without a wrench table, wtab null), the payload record, padding
+//   row RPW + r  zeros, the same payload record, padding: the row of an interval outside the wrench's window
+// (the layout of a row: h1_aba_split.h, at PAYLOAD_AT)
+// A substep hands the step the offset of one of the two, as k_plant_follow_w does with its zero row; the payload is in both, so it acts in
+// every substep.  Records of the tables: wrench 16 doubles (WRENCH_REC of the wrench module), payload PAYLOAD_REC = 16 doubles (ten values
+// and padding, 128 B); a stride of 0 is ONE record that every rollout reads.
+template <int RPW>
+DEVFN void stage_disturbance_records(const DevState& S, double* rows, int b0, const double* wtab, int wr_stride, const double* mtab, int m_stride) {
+  for (int e = threadIdx.x; e < 2 * RPW * h1s::DIST_REC; e += 64) {
+    const int r2 = e / h1s::DIST_REC, k = e - r2 * h1s::DIST_REC;
+    const int r = r2 < RPW ? r2 : r2 - RPW;
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;      // (a wave's unowned rows read the last rollout's records)
+    double v = 0.0;
+    if (k < h1s::PAYLOAD_AT) { if (r2 < RPW && wtab) v = wtab[(size_t)br * wr_stride + k]; }
+    else if (k < h1s::PAYLOAD_AT + h1s::PAYLOAD_VALS) v = mtab[(size_t)br * m_stride + (k - h1s::PAYLOAD_AT)];
+    rows[e] = v;
+  }
+}
+#define PLANT_TABLE 3
+#include "plant_follow_body.h"
+
+// ---- one step under a wrench and a payload per item (ilqr_hip_step_payload): k_step_w with the widened row; wrench null: none
+#define STEP_M_LDS_BYTES ((h1s::LDS_SLOTS * 64 + 32 * h1s::DIST_REC) * sizeof(double))
+template <int CK>
+__global__ void __launch_bounds__(64) k_step_m(int count, const double* x, const double* u, DynParams dyn, double* xn, int st_l, int st_r, const double* wrench, const double* payload) {
+  extern __shared__ double lds[];
+  constexpr int WR0 = h1s::LDS_SLOTS * 64;
+  const int i0 = blockIdx.x * 32;
+  for (int e = threadIdx.x; e < 32 * h1s::DIST_REC; e += 64) {
+    const int r = e / h1s::DIST_REC, k = e - r * h1s::DIST_REC;
+    const int ir = i0 + r < count ? i0 + r : count - 1;
+    double v = 0.0;
+    if (k < h1s::DIST_WRENCH_VALS) { if (wrench) v = wrench[(size_t)ir * h1s::DIST_WRENCH_VALS + k]; }
+    else if (k >= h1s::PAYLOAD_AT && k < h1s::PAYLOAD_AT + h1s::PAYLOAD_VALS) v = payload[(size_t)ir * h1s::PAYLOAD_VALS + (k - h1s::PAYLOAD_AT)];
+    lds[WR0 + e] = v;
+  }
+  wave_lds_fence();
+  const int i = i0 + ((int)threadIdx.x >> 1);
+  const bool side = (threadIdx.x & 1) != 0;
+  if (i >= count) return;
+  const h1s::LaneLds L{lds, 64, (int)threadIdx.x};
+  h1s::HalfX h; h1s::load_half(side, x + (size_t)i * H1_NX, h);
+  h1s::HalfU uu; load_half_u(side, u + (size_t)i * H1_NU, uu);
+  int st[2] = {st_l, st_r};
+  step_any_w<CK>(side, h, uu, dyn, st, L, 0, WR0 + ((int)threadIdx.x >> 1) * h1s::DIST_REC);
+  h1s::store_half(side, h, xn + (size_t)i * H1_NX);
+}
+
+#endif
+
 struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
-#ifndef PLANT_WRENCH_MODULE
+#ifndef PLANT_MODULE
 template <int KIND, int FB> static int plant_attr() {
   return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess ||
          hipFuncSetAttribute((const void*)k_plant_follow<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FollowLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
@@ -369,6 +432,37 @@ void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const Dyn
     else follow_launch_p<K(), 0>(S, Pl, dyn, T, a, st);
   });
 }
+#elif defined(PLANT_PAYLOAD_MODULE)      // attributes and launchers of the payload family, exported from its module with C linkage (ilqr_kernels.h)
+template <int FB> static constexpr size_t follow_lds_m() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC) * sizeof(double); }
+template <int KIND, int FB> static int plant_attr_m() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_m<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_m<FB>()) != hipSuccess;
+}
+template <int KIND> static int step_attr_m() {
+  return hipFuncSetAttribute((const void*)k_step_m<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_M_LDS_BYTES) != hipSuccess;
+}
+static int payload_kernels_set_attr() {
+  int rc = 0;
+  for_each_step_kind([&](auto K) { rc |= plant_attr_m<K(), 0>(); rc |= plant_attr_m<K(), 1>(); rc |= step_attr_m<K()>(); });
+  return rc;
+}
+template <int KIND, int FB>
+static void follow_launch_m(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_m<KIND, FB>), grid, dim3(64), follow_lds_m<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride);
+}
+static void launch_plant_follow_payload(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const WrenchFollowArgs& w, hipStream_t st) {
+  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (w.feedback_mode) follow_launch_m<K(), 1>(S, Pl, dyn, T, W, M, a, st);
+    else follow_launch_m<K(), 0>(S, Pl, dyn, T, W, M, a, st);
+  });
+}
+static void launch_step_payload(int count, const double* x, const double* u, const DynParams& dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload, hipStream_t st) {
+  const dim3 grid((unsigned)((count + 31) / 32));
+  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_m<K()>), grid, dim3(64), STEP_M_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench, payload); });
+}
 #else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
 template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
 template <int KIND, int FB> static int plant_attr_w() {
@@ -413,6 +507,19 @@ void ilqr_wrench_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl
 }
 void ilqr_wrench_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, hipStream_t st) {
   ilqr::launch_step_wrench(count, x, u, *dyn, xn, stance_l, stance_r, wrench, st);
+}
+}
+#endif
+
+#ifdef PLANT_PAYLOAD_MODULE
+extern "C" {
+int ilqr_payload_module_set_attr() { return ilqr::payload_kernels_set_attr(); }
+void ilqr_payload_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
+                                const ilqr::WrenchFollowArgs* a, hipStream_t st) {
+  ilqr::launch_plant_follow_payload(*S, *Pl, *dyn, *T, *W, *M, *a, st);
+}
+void ilqr_payload_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload, hipStream_t st) {
+  ilqr::launch_step_payload(count, x, u, *dyn, xn, stance_l, stance_r, wrench, payload, st);
 }
 }
 #endif

@@ -56,6 +56,10 @@ before the plant is reset and stay on the handle after the run; the solve keeps 
 `MPCRunner(..., resident=True, plant_wrench=W)` pushes the plant: W [1, 11] or [B, 11] (scenario.stack_plant_wrench) is a sustained external
 wrench on the pelvis per rollout -- force, torque, point of application and the window of plant intervals it acts in, counted from the
 reset of the run (BatchedILQR.plant_set_wrench).  Installed behind the parameter sets, in front of the reset; the solve does not know of it.
+
+`MPCRunner(..., resident=True, plant_payload=P)` loads the plant: P [1, 10] or [B, 10] (scenario.stack_plant_payload) is a rigid payload fixed
+to the pelvis per rollout -- mass, centre of mass and rotational inertia, carried over the whole run (BatchedILQR.plant_set_payload).  Installed
+beside the wrench, in front of the reset; the solve keeps the unloaded model.
 """
 import os
 import time
@@ -100,7 +104,7 @@ class MPCRunner:
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
-                 device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None):
+                 device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -131,6 +135,13 @@ class MPCRunner:
             if plant_wrench.ndim != 2 or plant_wrench.shape[1] != 11 or plant_wrench.shape[0] not in (1, solver.B):
                 raise ValueError("plant_wrench must be [1, 11] or [B, 11] (scenario.stack_plant_wrench)")
         self.plant_wrench = plant_wrench
+        if not resident and plant_payload is not None:
+            raise ValueError("plant_payload needs the device-resident plant (resident=True)")
+        if plant_payload is not None:
+            plant_payload = np.atleast_2d(np.asarray(plant_payload, dtype=np.float64))
+            if plant_payload.ndim != 2 or plant_payload.shape[1] != 10 or plant_payload.shape[0] not in (1, solver.B):
+                raise ValueError("plant_payload must be [1, 10] or [B, 10] (scenario.stack_plant_payload)")
+        self.plant_payload = plant_payload
         self.device_refs, self.track_ready = bool(device_refs), False
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
@@ -267,6 +278,8 @@ class MPCRunner:
             s.plant_set_params(self.plant_params)
         if self.plant_wrench is not None:
             s.plant_set_wrench(self.plant_wrench)
+        if self.plant_payload is not None:
+            s.plant_set_payload(self.plant_payload)
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)

@@ -153,6 +153,40 @@ def stack_plant_wrench(B, force=None, torque=None, point=None, first=0, end=np.i
     return out
 
 
+def stack_plant_payload(B, mass, com=None, inertia=None):
+    """Rigid payloads on the pelvis [B, 10] for BatchedILQR.plant_set_payload / MPCRunner(plant_payload=...): columns mass (kg), centre of
+    mass x, y, z (pelvis frame, m), Ixx, Iyy, Izz, Ixy, Ixz, Iyz of the rotational inertia about the payload's own centre of mass (pelvis
+    axes, kg m^2).  mass is a scalar or [B]; com [3] or [B, 3], None the pelvis origin; inertia [6] or [B, 6], None a point mass.  Raises
+    ValueError for a shape that is neither, a non-finite entry, a negative mass or an inertia that is not positive semidefinite -- what
+    ilqr_hip_plant_set_payload refuses."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    out = np.empty((B, 10))
+    m = np.asarray(mass, dtype=np.float64)
+    if m.shape not in ((), (B,)):
+        raise ValueError("mass must be a scalar or [B]")
+    out[:, 0] = m
+    for col, n, name, val in ((1, 3, "com", com), (4, 6, "inertia", inertia)):
+        v = np.zeros(n) if val is None else np.asarray(val, dtype=np.float64)
+        if v.shape not in ((n,), (B, n)):
+            raise ValueError("%s must be [%d] or [B, %d]" % (name, n, n))
+        out[:, col:col + n] = v
+    if not np.isfinite(out).all():
+        raise ValueError("plant payloads must be finite")
+    if (out[:, 0] < 0).any():
+        raise ValueError("mass >= 0 is required")
+    xx, yy, zz, xy, xz, yz = (out[:, 4 + k] for k in range(6))
+    eps = 1e-12
+    det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz)
+    mag = np.abs(xx * yy * zz) + np.abs(xx * yz * yz) + np.abs(xy * xy * zz) + 2.0 * np.abs(xy * yz * xz) + np.abs(yy * xz * xz)
+    bad = (xx < 0) | (yy < 0) | (zz < 0) | (xx * yy - xy * xy < -eps * (xx * yy + xy * xy)) | (xx * zz - xz * xz < -eps * (xx * zz + xz * xz)) \
+        | (yy * zz - yz * yz < -eps * (yy * zz + yz * yz)) | (det < -eps * mag)
+    if bad.any():
+        raise ValueError("the rotational inertia must be positive semidefinite")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

@@ -50,6 +50,7 @@ EXPORTS = [
     "ilqr_hip_plant_set_model", "ilqr_hip_plant_set_params", "ilqr_hip_plant_clear_params", "ilqr_hip_plant_num_param_sets", "ilqr_hip_plant_get_params",
     "ilqr_hip_plant_set_wrench", "ilqr_hip_plant_clear_wrench", "ilqr_hip_plant_num_wrench_sets", "ilqr_hip_plant_get_wrench", "ilqr_hip_plant_intervals",
     "ilqr_hip_step_wrench", "ilqr_hip_pelvis_inertial_offset",
+    "ilqr_hip_plant_set_payload", "ilqr_hip_plant_clear_payload", "ilqr_hip_plant_num_payload_sets", "ilqr_hip_plant_get_payload", "ilqr_hip_step_payload",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
@@ -59,6 +60,8 @@ PLANT_SCORE_TERMS = ("state", "control", "upright", "balance", "joint_limits", "
 PLANT_PARAMS = ("gravity_x", "gravity_y", "gravity_z", "friction", "softness", "limit_stiffness", "torque_gain")
 # columns of a plant wrench record (include/ilqr_hip.h ILQR_PLANT_WRENCH)
 PLANT_WRENCH = ("force_x", "force_y", "force_z", "torque_x", "torque_y", "torque_z", "point_x", "point_y", "point_z", "first", "end")
+# columns of a plant payload record (include/ilqr_hip.h ILQR_PLANT_PAYLOAD)
+PLANT_PAYLOAD = ("mass", "com_x", "com_y", "com_z", "Ixx", "Iyy", "Izz", "Ixy", "Ixz", "Iyz")
 
 
 
@@ -522,6 +525,20 @@ class BatchedILQR:
         self._chk(self.L.ilqr_hip_step_wrench(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(xn)))
         return xn
 
+    def step_payload(self, x, u, stance_left, stance_right, payload, wrench=None):
+        """step_wrench with one rigid payload on the pelvis per item as well: payload [count, 10] (columns PLANT_PAYLOAD), wrench [count, 9]
+        or None for none; always the two-lane step (ilqr_hip_step_payload)."""
+        x, u, payload = _c64(x), _c64(u), _c64(payload)
+        if payload.shape != (x.shape[0], len(PLANT_PAYLOAD)):
+            raise ValueError("payload must be [count, 10]")
+        if wrench is not None:
+            wrench = _c64(wrench)
+            if wrench.shape != (x.shape[0], 9):
+                raise ValueError("wrench must be [count, 9]")
+        xn = np.zeros_like(x)
+        self._chk(self.L.ilqr_hip_step_payload(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), None if wrench is None else _p(wrench), _p(payload), _p(xn)))
+        return xn
+
     def set_stance_source(self, source):
         """Stance source of the dynamics (include/ilqr_hip.h): "schedule" (default) or "geometry" -- every step takes the stance flags from
         its own feet (a foot touches iff its ankle-link hull reaches the floor, foot_clearance < 0); the cost keeps the schedule."""
@@ -708,6 +725,28 @@ class BatchedILQR:
         fn = self.L.ilqr_hip_plant_intervals
         fn.restype = C.c_long
         return int(fn(self.h))
+
+    def plant_set_payload(self, payload):
+        """Install rigid payloads on the pelvis [n_sets, 10] (columns PLANT_PAYLOAD; scenario.stack_plant_payload builds them), n_sets 1 or B:
+        rollout b's plant carries mass, centre of mass and rotational inertia of its record in every substep until plant_clear_payload
+        (ilqr_hip_plant_set_payload).  The solve does not know of it."""
+        payload = _c64(payload)
+        if payload.ndim == 1:
+            payload = payload[None]
+        if payload.ndim != 2 or payload.shape[1] != len(PLANT_PAYLOAD) or payload.shape[0] not in (1, self.B):
+            raise ValueError("plant payloads must be [1, 10] or [B, 10]")
+        self._chk(self.L.ilqr_hip_plant_set_payload(self.h, _p(payload), int(payload.shape[0])))
+
+    def plant_clear_payload(self):
+        """Remove the payloads: the plant calls launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_clear_payload(self.h))
+
+    def plant_num_payload_sets(self):
+        return int(self.L.ilqr_hip_plant_num_payload_sets(self.h))
+
+    def plant_get_payload(self):
+        """[B, 10] (columns PLANT_PAYLOAD): the record of each rollout; zeros without a table."""
+        return self._get("ilqr_hip_plant_get_payload", (self.B, len(PLANT_PAYLOAD)))
 
     def plant_score(self):
         """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""

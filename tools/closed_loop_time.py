@@ -25,7 +25,12 @@ calls under one solve -- for the free plant and for plant contact mode 2 (ilqr_h
    python tools/closed_loop_time.py --wrench [--contact-mode 2] [--solve-every M] ...
 compares, instead, the RESIDENT runner without a wrench table against the same runner with one installed (MPCRunner(plant_wrench=...): a
 lateral push of 20 to 60 N per rollout, at the pelvis inertial offset, over the whole run), alternating on one box, the plant in the
-given contact mode."""
+given contact mode.
+
+   python tools/closed_loop_time.py --payload [--contact-mode 2] [--solve-every M] ...
+compares, instead, the RESIDENT runner without a payload table against the same runner with one installed (MPCRunner(plant_payload=...): a
+rigid payload of 0 to 20 kg per rollout at the fixed offset (-0.1, 0, 0.3) in the pelvis frame, a backpack at torso height, over the whole
+run), alternating on one box, the plant in the given contact mode."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py): behind the product library, torch finds "no HIP GPUs" when it is asked for the device name
@@ -47,6 +52,7 @@ def main():
     ap.add_argument("--solve-every", type=int, default=1); ap.add_argument("--score", action="store_true")
     ap.add_argument("--plant-params", choices=("shared", "per-rollout"), default=None)
     ap.add_argument("--wrench", action="store_true")
+    ap.add_argument("--payload", action="store_true")
     ap.add_argument("--device-refs", action="store_true"); ap.add_argument("--per-rollout-starts", action="store_true"); ap.add_argument("--contact-mode", type=int, default=2)
     a = ap.parse_args()
     if a.per_rollout_starts and not a.device_refs:
@@ -62,6 +68,8 @@ def main():
         return plant_params_main(a, sc, ml, rf, sv)
     if a.wrench:
         return wrench_main(a, sc, ml, rf, sv)
+    if a.payload:
+        return payload_main(a, sc, ml, rf, sv)
     base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
     rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
     rows = a.steps + N + 10
@@ -171,6 +179,36 @@ def wrench_main(a, sc, ml, rf, sv):
                       "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
                       "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_wrench": float(np.median(ms[True])),
                       "samples_no_wrench": ms[False], "samples_wrench": ms[True], "alive_no_wrench": alive[False], "alive_wrench": alive[True]}))
+
+
+def payload_main(a, sc, ml, rf, sv):
+    B, N = a.batch, a.horizon
+    base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
+    rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
+    rows = a.steps + N + 10
+    rd.set_states(np.tile(sc.standing_state(), (rows, 1))); rd.contact = np.ones((rows, 2), dtype=np.int32)
+    x0, ui = sc.synthetic_batch(B, N, 0, sv.gravity_compensation(sc.standing_state(), base["gravity"]))
+    mass = np.random.default_rng(1).uniform(0.0, 20.0, B)
+    table = sc.stack_plant_payload(B, mass, com=(-0.1, 0.0, 0.3), inertia=np.outer(mass / 20.0, (0.4, 0.3, 0.3, 0.0, 0.0, 0.0)))
+    ms, alive = {False: [], True: []}, {}
+    for rnd in range(a.rounds + 1):                      # round 0 warms up (first launches, allocations)
+        for tab in (False, True):
+            s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+            s.set_contact_mode(a.contact_mode)
+            run = ml.MPCRunner(s, rd, base, resident=True, substeps=a.substeps, feedback_mode=a.feedback_mode, solve_every=a.solve_every, plant_payload=table if tab else None)
+            run.run(x0, 1, u_init=ui)                    # the cold start is not what is compared: every timed step is a warm one
+            s.synchronize()
+            t0 = time.perf_counter()
+            run.run(x0, a.steps, u_init=ui)
+            dt = time.perf_counter() - t0
+            alive[tab] = int(s.plant_alive().sum())
+            s.close()
+            if rnd:
+                ms[tab].append(1e3 * dt / a.steps)
+    print(json.dumps({"tool": "closed_loop_time", "mode": "payload", "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "iterations": a.iters, "steps": a.steps,
+                      "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
+                      "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_payload": float(np.median(ms[True])),
+                      "samples_no_payload": ms[False], "samples_payload": ms[True], "alive_no_payload": alive[False], "alive_payload": alive[True]}))
 
 
 class HostWindows:
