@@ -481,6 +481,48 @@ int ilqr_hip_plant_num_payload_sets(const ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_get_payload(ilqr_hip_ctx* ctx, double* payload /*[B][10]*/);
 int ilqr_hip_step_payload(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench /*[count][9], NULL: none*/,
                           const double* payload /*[count][10]*/, double* x_next);
+/* ---- noisy and biased state observation, one model per rollout: a controller that is told a MEASUREMENT of the plant's state, as
+   MPC::stepOnce(x_measured, ...) is on a robot -- encoder noise, IMU orientation and rate noise, a drifting pelvis position.  Two places
+   read the plant's state for the controller, the warm starts (x0 of the solve) and the plant kernels' control law; under a table both
+   read the same measurement x [+] delta.  The physics, the ring, alive and the score stay on the true state; a pending kick is applied
+   to the true state in front of the law, as before.
+   One record of ILQR_PLANT_OBSERVATION doubles per set: bias[50], then sigma[50], in the tangent order of the Jacobians --
+     dp[3] pelvis position (world)   dphi[3] orientation, a rotation vector in the body frame   dq[19] joint positions
+     dv[3] linear velocity (world)   domega[3] angular velocity (body)                          dqdot[19] joint velocities
+   The error of rollout b in plant interval i (counted as ilqr_hip_plant_intervals counts, from the last ilqr_hip_plant_reset) is
+   e = bias + sigma o z, z[50] standard normals, laid out as a state-shaped row delta[51]: delta.p = e.dp, delta.quat = (cos(t/2),
+   sin(t/2)/t e.dphi) with t = |e.dphi| (exactly (1, 0, 0, 0) for t == 0), the 44 remaining entries e itself.  The measured state
+   x [+] delta is p + delta.p, quat (x) delta.quat (Hamilton product, wxyz, not renormalised), every other entry added.
+   The normals come from Philox4x32-10, a counter-based generator, so they depend on (seed, rollout stream, interval) alone -- not on
+   launch shape, batch split or call grouping: key (seed & 0xffffffff, seed >> 32), counter (s & 0xffffffff, s >> 32, i & 0xffffffff, k)
+   with s = stream0 + b and the block k = 0..24; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85.  With the
+   output words w0..w3: u1 = (((w0 << 32 | w1) >> 11) + 0.5) 2^-53, u2 likewise from w2, w3, r = sqrt(-2 log u1), z[2k] = r cos(2 pi u2),
+   z[2k + 1] = r sin(2 pi u2), 2 pi the double constant, multiplied once.  Draws are made whatever sigma is: a rollout's stream never
+   depends on its record.  stream0 is the first GLOBAL rollout index of a shard, so a sharded batch draws what the global batch draws.
+   delta(i) is drawn once per plant interval and held over it: the warm start taken while ilqr_hip_plant_intervals == i, the control law
+   of interval i (in every substep at feedback mode 1), and inside ilqr_hip_plant_follow(k0, m) interval i + j with knot k0 + j.
+   plant_set_observation: n_sets = 1 (one record that every rollout reads; the streams still differ) or the batch, else ILQR_ERR_ARG;
+   ILQR_ERR_ARG also for a null pointer, a non-finite entry or a negative sigma, all checked before the handle is touched.  The table and a
+   buffer of N x B x 51 error rows are owned by the handle; the call uploads and synchronises the handle's stream.  It survives
+   ilqr_hip_plant_reset and ilqr_hip_plant_configure.  While it is installed ilqr_hip_plant_advance / _follow launch the draw of the call's
+   intervals and the observation family of the plant kernel (k_observation_draw, k_plant_follow_o of the module libilqr_hip_observe.so,
+   opened from the library's directory on first use -- missing: ILQR_ERR_UNSUPPORTED with the path in ilqr_hip_last_error; an advance is
+   that kernel over one interval), which carries parameter record, wrench and payload as the payload family does, each table present or
+   not; ilqr_hip_initialize_warm_from_plant[_shifted] write x0 with a one-row draw and k_observe_apply in the place of the device copy.
+   plant_clear_observation: frees the table; the plant calls and warm starts then launch exactly what they launch without it.
+   plant_num_observation_sets: 0 without a table, else n_sets; -1 for a null handle.
+   plant_get_observation: obs[B][100], the record of each rollout (zeros without a table); seed / stream0 (each may be NULL; 0 without).
+   plant_observation_errors: delta[count][B][51] of the intervals interval0 .. interval0 + count - 1, a pure function of table, seed,
+   stream0 and interval; 1 <= count <= N and interval0 >= 0, else ILQR_ERR_ARG; ILQR_ERR_STATE without a table.
+   plant_get_observed: x_obs[B][51] = plant state [+] delta(ilqr_hip_plant_intervals), what a warm start would hand the solve now; the
+   plant state itself without a table. */
+#define ILQR_PLANT_OBSERVATION 100   /* bias[50], sigma[50] */
+int ilqr_hip_plant_set_observation(ilqr_hip_ctx* ctx, const double* obs /*[n_sets][100]*/, int n_sets, unsigned long long seed, unsigned long long stream0);
+int ilqr_hip_plant_clear_observation(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_num_observation_sets(const ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_observation(ilqr_hip_ctx* ctx, double* obs /*[B][100]*/, unsigned long long* seed, unsigned long long* stream0);
+int ilqr_hip_plant_observation_errors(ilqr_hip_ctx* ctx, long interval0, int count, double* delta /*[count][B][51]*/);
+int ilqr_hip_plant_get_observed(ilqr_hip_ctx* ctx, double* x_obs /*[B][51]*/);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

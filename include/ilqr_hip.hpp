@@ -222,6 +222,21 @@ class iLQR {
       throw std::runtime_error("stepPayload: x [count][51], u [count][19], wrench [count][9] or empty, payload [count][10]");
     Vec xn((size_t)count * ILQR_NX); chk(ilqr_hip_step_payload(ctx_, count, x.data(), u.data(), stance_left, stance_right, wrench.empty() ? nullptr : wrench.data(), payload.data(), xn.data())); return xn;
   }
+  // noisy and biased state observation per rollout (ilqr_hip.h ilqr_hip_plant_set_observation): [n_sets][100] = bias[50], sigma[50] in tangent order
+  void plantSetObservation(const Vec& obs, int n_sets, unsigned long long seed, unsigned long long stream0 = 0) {
+    if (n_sets < 1 || obs.size() != (size_t)n_sets * ILQR_PLANT_OBSERVATION) throw std::runtime_error("observation records must hold n_sets * 100 doubles");
+    chk(ilqr_hip_plant_set_observation(ctx_, obs.data(), n_sets, seed, stream0));
+  }
+  void plantClearObservation() { chk(ilqr_hip_plant_clear_observation(ctx_)); }
+  int plantNumObservationSets() const { return ilqr_hip_plant_num_observation_sets(ctx_); }
+  Vec plantObservation(unsigned long long* seed = nullptr, unsigned long long* stream0 = nullptr) {      // [batch][100]
+    Vec o((size_t)B_ * ILQR_PLANT_OBSERVATION); chk(ilqr_hip_plant_get_observation(ctx_, o.data(), seed, stream0)); return o;
+  }
+  Vec plantObservationErrors(long interval0, int count) {      // [count][batch][51]
+    if (count < 1) throw std::runtime_error("plantObservationErrors: count >= 1");
+    Vec d((size_t)count * B_ * ILQR_NX); chk(ilqr_hip_plant_observation_errors(ctx_, interval0, count, d.data())); return d;
+  }
+  Vec plantObserved() { Vec x((size_t)B_ * ILQR_NX); chk(ilqr_hip_plant_get_observed(ctx_, x.data())); return x; }      // [batch][51]
   static std::array<double, 3> pelvisInertialOffset() { std::array<double, 3> r{}; ilqr_hip_pelvis_inertial_offset(r.data()); return r; }
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492

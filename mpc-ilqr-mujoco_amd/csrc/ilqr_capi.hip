@@ -171,6 +171,15 @@ struct ilqr_hip_ctx {
   double* d_stepm = nullptr;  // [step_m_cap][10] payloads of ilqr_hip_step_payload (its wrenches go through d_stepw)
   size_t step_m_cap = 0;
   bool payload_attr_set = false;  // the payload module's kernels have their LDS attributes on this handle's device
+  // observation table (ilqr_hip_plant_set_observation; plant_kernels.hip k_plant_follow_o): [n][100] doubles, n = 1 or B; null: none.  While it
+  // is installed the plant calls launch the observation family behind a draw of the call's error rows into d_obs_delta [N][B][51] (a follow
+  // never exceeds N intervals), and the warm starts hand the solve Pl.x [+] delta of the current interval.
+  double* d_pobs = nullptr;
+  int obs_sets = 0;
+  unsigned long long obs_seed = 0, obs_stream0 = 0;
+  double* d_obs_delta = nullptr;
+  double* d_obs_x = nullptr;      // [B][51] the measured state of ilqr_hip_plant_get_observed
+  bool observe_attr_set = false;  // the observation module's kernels have their LDS attributes on this handle's device
   long plant_intervals = 0;   // plant intervals run since the last ilqr_hip_plant_reset (the history cursor only counts while a ring exists)
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
@@ -341,6 +350,51 @@ static int need_payload_module(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 
+// The observation family (csrc/Makefile ../lib/libilqr_hip_observe.so) is a module of its own in the same way, opened on the first
+// ilqr_hip_plant_set_observation.
+namespace {
+struct ObserveModule {
+  void* lib = nullptr;
+  ilqr::observe_set_attr_fn set_attr = nullptr;
+  ilqr::observe_follow_fn follow = nullptr;
+  ilqr::observe_draw_fn draw = nullptr;
+  ilqr::observe_apply_fn apply = nullptr;
+  std::string why;
+  bool ok() const { return lib && set_attr && follow && draw && apply; }
+};
+ObserveModule& observe_module() {
+  static ObserveModule m;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    Dl_info info;
+    std::string dir = ".";
+    if (dladdr((const void*)&ilqr_hip_plant_num_observation_sets, &info) && info.dli_fname) {
+      const std::string self = info.dli_fname;
+      const size_t slash = self.rfind('/');
+      if (slash != std::string::npos) dir = self.substr(0, slash);
+    }
+    const std::string path = dir + "/libilqr_hip_observe.so";
+    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!m.lib) { m.why = "the observation kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.set_attr = (ilqr::observe_set_attr_fn)dlsym(m.lib, "ilqr_observe_module_set_attr");
+    m.follow = (ilqr::observe_follow_fn)dlsym(m.lib, "ilqr_observe_module_follow");
+    m.draw = (ilqr::observe_draw_fn)dlsym(m.lib, "ilqr_observe_module_draw");
+    m.apply = (ilqr::observe_apply_fn)dlsym(m.lib, "ilqr_observe_module_apply");
+    if (!m.ok()) m.why = "the observation kernels' module lacks an entry point: " + path;
+  });
+  return m;
+}
+}  // namespace
+static int need_observe_module(ilqr_hip_ctx* c) {
+  ObserveModule& m = observe_module();
+  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
+  if (!c->observe_attr_set) {
+    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the observation kernels"; return ILQR_ERR_HIP; }
+    c->observe_attr_set = true;
+  }
+  return ILQR_OK;
+}
+
 extern "C" {
 
 int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt) {
@@ -428,7 +482,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm, c->d_pobs, c->d_obs_delta, c->d_obs_x}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1514,7 +1568,7 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
 // The wrench family (k_plant_follow_w) always reads a parameter record: the parameter table's, or this ONE record of the handle's own values
 // with gain 1, uploaded again whenever the handle's values have changed.
 static int plant_self_params(ilqr_hip_ctx* c) {
-  if ((!c->d_wrench && !c->d_ppayload) || c->d_pparams) return ILQR_OK;
+  if ((!c->d_wrench && !c->d_ppayload && !c->d_pobs) || c->d_pparams) return ILQR_OK;
   const h1::DynParams& d = c->P.dyn;
   const double rec[ILQR_PLANT_PARAMS + 1] = {d.g[0], d.g[1], d.g[2], d.mu, d.soft, d.lim_k, 1.0, 0.0};
   if (c->d_self_params && std::memcmp(rec, c->self_params, sizeof(rec)) == 0) return ILQR_OK;
@@ -1528,9 +1582,34 @@ static int plant_self_params(ilqr_hip_ctx* c) {
 // records -- for an advance over the one interval (0, 1), which is an advance bit for bit.  row: the advance's ring row (-1: no ring) or the
 // follow's first ring row.
 // With a wrench table: the wrench family of the module, under the parameter table or the handle's own record (plant_self_params).
+static ilqr::ObservationTable observation_table(const ilqr_hip_ctx* c) {
+  return ilqr::ObservationTable{c->d_pobs, c->obs_sets == 1 ? 0 : ILQR_PLANT_OBSERVATION, c->obs_seed, c->obs_stream0};
+}
+// What a warm start hands the solve as x0: the plant's state, or -- under an observation table -- its measurement in the current interval,
+// Pl.x [+] delta(plant_intervals): a one-row draw and the apply in the place of the device copy.
+static int enqueue_measured_x0(ilqr_hip_ctx* c, double* out) {
+  if (!c->d_pobs) {
+    HIPCHK(c, hipMemcpyAsync(out, c->plant.x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return ILQR_OK;
+  }
+  TRY(need_observe_module(c));
+  const ilqr::ObservationTable O = observation_table(c);
+  observe_module().draw(c->B, &O, c->plant_intervals, 1, c->d_obs_delta, c->stream);
+  observe_module().apply(c->B, c->plant.x, c->d_obs_delta, out, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return ILQR_OK;
+}
 static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  if (c->d_ppayload) {      // the payload family: parameter record, wrench (none: a null table) and payload together
+  if (c->d_pobs) {      // the observation family: the payload family's superset (either table may be null) behind the draw of the call's error rows
+    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
+    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+    const ilqr::ObservationTable O = observation_table(c);
+    observe_module().draw(c->B, &O, c->plant_intervals, count, c->d_obs_delta, c->stream);      // (the callers have checked the module: need_observe_module)
+    observe_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, c->d_obs_delta, &a, c->stream);
+  } else if (c->d_ppayload) {      // the payload family: parameter record, wrench (none: a null table) and payload together
     const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
     const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
     const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
@@ -1592,7 +1671,8 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
   TRY(plant_self_params(c));
-  if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  if (c->d_pobs) TRY(need_observe_module(c));
+  else if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
@@ -1608,7 +1688,7 @@ int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* c) {
   if (!c->initialized || !c->plant_set) return ILQR_ERR_STATE;
   TRY(enter_launching(c));
   const size_t B = c->B, N = c->N;
-  HIPCHK(c, hipMemcpyAsync(c->S.x0, c->plant.x, B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  TRY(enqueue_measured_x0(c, c->S.x0));
   HIPCHK(c, hipMemcpyAsync(c->d_prevx, c->S.xbar, B * (N + 1) * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);      // (k_warm_shift reads x0 from S.x0: the plant's state by the copy above)
@@ -1630,7 +1710,8 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
     return ILQR_ERR_STATE;
   }
   TRY(plant_self_params(c));
-  if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  if (c->d_pobs) TRY(need_observe_module(c));
+  else if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
@@ -1645,7 +1726,7 @@ int ilqr_hip_initialize_warm_from_plant_shifted(ilqr_hip_ctx* c, int shift) {
   if (!c || shift < 1 || shift > c->N - 1) return ILQR_ERR_ARG;
   if (!c->initialized || !c->plant_set) return ILQR_ERR_STATE;
   TRY(enter_launching(c));
-  HIPCHK(c, hipMemcpyAsync(c->S.x0, c->plant.x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  TRY(enqueue_measured_x0(c, c->S.x0));
   return warm_shifted(c, shift);      // asynchronous on the handle's stream
 }
 int ilqr_hip_plant_set_history(ilqr_hip_ctx* c, int steps) {
@@ -1933,6 +2014,76 @@ int ilqr_hip_step_payload(ilqr_hip_ctx* c, int count, const double* x, const dou
   payload_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, wrench ? c->d_stepw : nullptr, c->d_stepm, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+// ---- noisy and biased state observation per rollout (plant_kernels.hip k_observation_draw, k_observe_apply, k_plant_follow_o)
+int ilqr_hip_plant_set_observation(ilqr_hip_ctx* c, const double* obs, int n_sets, unsigned long long seed, unsigned long long stream0) {
+  if (!obs || n_sets < 1) return ILQR_ERR_ARG;
+  constexpr int R = ILQR_PLANT_OBSERVATION;
+  for (size_t i = 0; i < (size_t)n_sets * R; ++i) {
+    if (!std::isfinite(obs[i])) return ILQR_ERR_ARG;
+    if (i % R >= R / 2 && obs[i] < 0.0) return ILQR_ERR_ARG;      // (sigma)
+  }
+  if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(need_observe_module(c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (c->d_pobs && c->obs_sets != n_sets) { hipFree(c->d_pobs); c->d_pobs = nullptr; c->obs_sets = 0; }
+  if (!c->d_obs_delta) HIPCHK(c, hipMalloc((void**)&c->d_obs_delta, (size_t)c->N * c->B * ILQR_NX * sizeof(double)));
+  if (!c->d_obs_x) HIPCHK(c, hipMalloc((void**)&c->d_obs_x, (size_t)c->B * ILQR_NX * sizeof(double)));
+  if (!c->d_pobs) HIPCHK(c, hipMalloc((void**)&c->d_pobs, (size_t)n_sets * R * sizeof(double)));
+  c->obs_sets = n_sets; c->obs_seed = seed; c->obs_stream0 = stream0;
+  HIPCHK(c, hipMemcpyAsync(c->d_pobs, obs, (size_t)n_sets * R * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_clear_observation(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->d_pobs) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+    hipFree(c->d_pobs);
+  }
+  c->d_pobs = nullptr; c->obs_sets = 0; c->obs_seed = 0; c->obs_stream0 = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_plant_num_observation_sets(const ilqr_hip_ctx* c) { return c ? c->obs_sets : -1; }
+int ilqr_hip_plant_get_observation(ilqr_hip_ctx* c, double* obs, unsigned long long* seed, unsigned long long* stream0) {
+  if (!c || !obs) return ILQR_ERR_ARG;
+  enter(c);
+  constexpr int R = ILQR_PLANT_OBSERVATION;
+  if (seed) *seed = c->obs_seed;
+  if (stream0) *stream0 = c->obs_stream0;
+  if (!c->d_pobs) {      // (no table: the controller sees the truth)
+    std::fill(obs, obs + (size_t)c->B * R, 0.0);
+    return ILQR_OK;
+  }
+  std::vector<double> rec((size_t)c->obs_sets * R);
+  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pobs, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(obs + (size_t)b * R, rec.data() + (size_t)(c->obs_sets == 1 ? 0 : b) * R, R * sizeof(double));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_observation_errors(ilqr_hip_ctx* c, long interval0, int count, double* delta) {
+  if (!c || !delta || interval0 < 0 || count < 1 || count > c->N) return ILQR_ERR_ARG;
+  if (!c->d_pobs) { c->err = "plant_observation_errors without an observation table (ilqr_hip_plant_set_observation)"; return ILQR_ERR_STATE; }
+  TRY(enter_launching(c));
+  TRY(need_observe_module(c));
+  const ilqr::ObservationTable O = observation_table(c);
+  observe_module().draw(c->B, &O, interval0, count, c->d_obs_delta, c->stream);      // (the buffer of the plant calls: they draw again in front of every use)
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(delta, c->d_obs_delta, (size_t)count * c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_get_observed(ilqr_hip_ctx* c, double* x_obs) {
+  if (!c || !x_obs) return ILQR_ERR_ARG;
+  if (!c->plant_set) return ILQR_ERR_STATE;
+  if (!c->d_pobs) return ilqr_hip_plant_get_state(c, x_obs);
+  TRY(enter_launching(c));
+  TRY(enqueue_measured_x0(c, c->d_obs_x));
+  HIPCHK(c, hipMemcpyAsync(x_obs, c->d_obs_x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }

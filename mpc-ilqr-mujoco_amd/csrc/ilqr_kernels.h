@@ -221,6 +221,24 @@ struct PayloadTable {
 typedef int (*payload_set_attr_fn)();
 typedef void (*payload_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const WrenchFollowArgs*, hipStream_t);
 typedef void (*payload_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, hipStream_t);
+// the same under an observation table (ilqr_hip_plant_set_observation): the control law reads x [+] delta, delta the error rows
+// [count][B][51] of the call's intervals as ilqr_observe_module_draw wrote them.  rollout b reads record b * rec_stride of O.records --
+// bias[50], sigma[50] in tangent order; 100 doubles -- rec_stride 100 or 0 as above; its stream of the generator is stream0 + b.
+// T as in the wrench family; W.records and M.records may each be null: no wrench, no payload.
+struct ObservationTable {
+  const double* records;
+  int rec_stride;
+  unsigned long long seed, stream0;
+};
+// The family lives in a module of its own as well, libilqr_hip_observe.so (plant_kernels.hip compiled with -DPLANT_OBSERVE_MODULE):
+//   int  ilqr_observe_module_set_attr()
+//   void ilqr_observe_module_follow(S, Pl, dyn, T, W, M, delta, args, stream)
+//   void ilqr_observe_module_draw(B, O, interval0, count, delta[count][B][51], stream)     the errors of intervals interval0 .. + count - 1
+//   void ilqr_observe_module_apply(B, x[B][51], delta[B][51], out[B][51], stream)          out = x [+] delta
+typedef int (*observe_set_attr_fn)();
+typedef void (*observe_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const WrenchFollowArgs*, hipStream_t);
+typedef void (*observe_draw_fn)(int, const ObservationTable*, long, int, double*, hipStream_t);
+typedef void (*observe_apply_fn)(int, const double*, const double*, double*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

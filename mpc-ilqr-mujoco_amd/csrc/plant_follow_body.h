@@ -10,10 +10,17 @@
 //                  (ilqr_hip_plant_set_payload) in every substep -- two more kernel arguments; the rollout has two widened disturbance rows in
 //                  LDS, wrench and payload / zero wrench and payload, and a substep hands the step the offset of one of them.  wtab may be
 //                  null: no wrench.
+//   PLANT_TABLE 4  k_plant_follow_o: as 3 with either of wtab / mtab null or both (both null: the step of family 1), and the control law sees
+//                  a MEASUREMENT of the state (ilqr_hip_plant_set_observation): one more kernel argument, the error rows dobs[count][B][51]
+//                  of the call's intervals, and RPW more rows of LDS, XO = XS [+] delta_j, written in front of every control law.  Ring,
+//                  alive, the guards and the step stay on the true state XS.
 #ifndef PLANT_TABLE
-#error "define PLANT_TABLE (0, 1, 2 or 3) before including plant_follow_body.h"
+#error "define PLANT_TABLE (0, 1, 2, 3 or 4) before including plant_follow_body.h"
 #endif
-#if PLANT_TABLE == 3
+#if PLANT_TABLE == 4
+#define K_PLANT_FOLLOW k_plant_follow_o
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs
+#elif PLANT_TABLE == 3
 #define K_PLANT_FOLLOW k_plant_follow_m
 #define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride
 #elif PLANT_TABLE == 2
@@ -47,7 +54,12 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #if PLANT_TABLE
   stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
 #endif
-#if PLANT_TABLE == 3
+#if PLANT_TABLE == 4
+  constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // disturbance rows as in family 3 (a null payload table stages zeros), then the observed rows
+  constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
+  stage_disturbance_records<RPW, true>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
+  const bool disturbed = wtab != nullptr || mtab != nullptr;      // (wave-uniform: kernel arguments)
+#elif PLANT_TABLE == 3
   constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // disturbance rows behind the parameter rows: RPW with the wrench, RPW with a zero wrench
   stage_disturbance_records<RPW>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
 #elif PLANT_TABLE == 2
@@ -87,7 +99,14 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
       const int prt = lane >> 1;
       if (FB != 0 || k == 0) {
         wave_lds_fence();
+#if PLANT_TABLE == 4
+        // what the controller is told of the state: the interval's error on the rows as they stand (FB = 1: the substep's), the law on XO
+        observe_rows<RPW>(S, lds + Lay::XS, dobs + (size_t)j * S.B * n, b0, lds + XO0);
+        wave_lds_fence();
+        control_law<FB, XO0>(S, lds, b0, kt);
+#else
         control_law<FB>(S, lds, b0, kt);
+#endif
         wave_lds_fence();
       }
       if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
@@ -103,7 +122,18 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
         if constexpr (KIND >= 1 && KIND <= 4) {
           if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
         }
-#if PLANT_TABLE == 3
+#if PLANT_TABLE == 4
+        // without a wrench and a payload table the step of k_plant_follow_p (under the handle's own record: the plant without a table, bit
+        // for bit); with either the step of k_plant_follow_m
+        if (disturbed) {
+          const double* wrow = lds + WR0 + pc * h1s::DIST_REC;
+          const double iv = (double)(interval0 + j);
+          const int wro = (wrow[h1s::DIST_FIRST] <= iv && iv < wrow[h1s::DIST_END]) ? WR0 + pc * h1s::DIST_REC : WR0 + (RPW + pc) * h1s::DIST_REC;
+          plant_step_table<KIND, true>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC, wro);
+        } else {
+          plant_step_table<KIND>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC);
+        }
+#elif PLANT_TABLE == 3
         // the wrench's window as in k_plant_follow_w; the payload has none: both rows of the rollout carry it
         const double* wrow = lds + WR0 + pc * h1s::DIST_REC;
         const double iv = (double)(interval0 + j);

@@ -8,8 +8,8 @@
 //                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
 // A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
-// four times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w), and
-// with parameter, wrench and payload tables (k_plant_follow_m).
+// five times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w),
+// with parameter, wrench and payload tables (k_plant_follow_m), and with those three under an observation table (k_plant_follow_o).
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -22,7 +22,7 @@ using namespace h1;
 
 namespace ilqr {
 
-// This file is compiled three times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
+// This file is compiled four times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
 // libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
 // which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
 // library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
@@ -32,11 +32,13 @@ namespace ilqr {
 #ifdef PLANT_WRENCH_MODULE
 #define DYN_STEP_WRENCH      // the wrench-carrying copies of the non-inlined steps: compiled in the module alone
 #endif
-#ifdef PLANT_PAYLOAD_MODULE
+// A fourth compilation, -DPLANT_OBSERVE_MODULE into libilqr_hip_observe.so, is the observation family alone (k_plant_follow_o, the superset of
+// the payload family whose control law reads a measured state, k_observation_draw and k_observe_apply), opened in the same way.
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE)
 #define DYN_STEP_WRENCH
 #define DYN_STEP_PAYLOAD     // ... carrying the payload too
 #endif
-#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE)
+#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE)
 #define PLANT_MODULE         // a module: none of the library's own kernels and launchers
 #endif
 #include "dyn_step_shared.h"
@@ -104,7 +106,8 @@ DEVFN void wave_lds_fence() {
 // u = ubar_k + K_k (x - xbar_k) for the wave's rollouts (k = knot; 0 in k_plant_advance), x / xbar_k / ubar_k in LDS -> u in LDS.  The arithmetic of k_compute_control
 // (ilqr_kernels.hip): one accumulator per row, started at ubar_0, the 51 terms in index order.  The 64 lanes deal the RPW x 19 rows out;
 // nothing of the dynamics is live here (the state sits in LDS), so the step's register budget is its own.
-template <int FB>
+// XOFF >= 0: the law reads its state from the rows at that LDS offset instead of XS (k_plant_follow_o: the observed rows).
+template <int FB, int XOFF = -1>
 DEVFN void control_law(const DevState& S, double* lds, int b0, int knot = 0) {
   typedef PlantLayout<FB> Lay;
   constexpr int n = PLANT_NX, m = PLANT_NU;
@@ -112,7 +115,7 @@ DEVFN void control_law(const DevState& S, double* lds, int b0, int knot = 0) {
     const int r = it / m, row = it - r * m;
     const int b = b0 + r < S.B ? b0 + r : S.B - 1;
     const double* Kr = FB ? lds + Lay::KS + (r * m + row) * n : S.K + ((size_t)b * S.N * m + (size_t)knot * m + row) * n;
-    const double* x = lds + Lay::XS + r * n;
+    const double* x = lds + (XOFF >= 0 ? XOFF : Lay::XS) + r * n;
     const double* xb = lds + Lay::XB + r * n;
     double s = lds[Lay::UB + r * m + row];
     for (int j = 0; j < n; ++j) s += Kr[j] * (x[j] - xb[j]);
@@ -320,7 +323,7 @@ __global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const
 
 #endif
 
-#ifdef PLANT_PAYLOAD_MODULE
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE)
 // ---- payload table (include/ilqr_hip.h ilqr_hip_plant_set_payload): k_plant_follow_m.  A rollout has two disturbance rows of h1s::DIST_REC doubles
 // in LDS behind the parameter rows, staged once per launch, consecutive lanes on consecutive doubles (12 KB at FB = 0, 1.5 KB at FB = 1):
 //   row r        the wrench record (F, T, r, first, end; zeros without a wrench table, wtab null), the payload record, padding
@@ -329,7 +332,8 @@ __global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const
 // A substep hands the step the offset of one of the two, as k_plant_follow_w does with its zero row; the payload is in both, so it acts in
 // every substep.  Records of the tables: wrench 16 doubles (WRENCH_REC of the wrench module), payload PAYLOAD_REC = 16 doubles (ten values
 // and padding, 128 B); a stride of 0 is ONE record that every rollout reads.
-template <int RPW>
+// MNULL: mtab may be null as well (k_plant_follow_o): no payload, zeros
+template <int RPW, bool MNULL = false>
 DEVFN void stage_disturbance_records(const DevState& S, double* rows, int b0, const double* wtab, int wr_stride, const double* mtab, int m_stride) {
   for (int e = threadIdx.x; e < 2 * RPW * h1s::DIST_REC; e += 64) {
     const int r2 = e / h1s::DIST_REC, k = e - r2 * h1s::DIST_REC;
@@ -337,10 +341,12 @@ DEVFN void stage_disturbance_records(const DevState& S, double* rows, int b0, co
     const int br = b0 + r < S.B ? b0 + r : S.B - 1;      // (a wave's unowned rows read the last rollout's records)
     double v = 0.0;
     if (k < h1s::PAYLOAD_AT) { if (r2 < RPW && wtab) v = wtab[(size_t)br * wr_stride + k]; }
-    else if (k < h1s::PAYLOAD_AT + h1s::PAYLOAD_VALS) v = mtab[(size_t)br * m_stride + (k - h1s::PAYLOAD_AT)];
+    else if (k < h1s::PAYLOAD_AT + h1s::PAYLOAD_VALS) { if (!MNULL || mtab) v = mtab[(size_t)br * m_stride + (k - h1s::PAYLOAD_AT)]; }
     rows[e] = v;
   }
 }
+#endif
+#ifdef PLANT_PAYLOAD_MODULE
 #define PLANT_TABLE 3
 #include "plant_follow_body.h"
 
@@ -371,6 +377,112 @@ __global__ void __launch_bounds__(64) k_step_m(int count, const double* x, const
   h1s::store_half(side, h, xn + (size_t)i * H1_NX);
 }
 
+#endif
+
+#ifdef PLANT_OBSERVE_MODULE
+// ---- observation table (include/ilqr_hip.h ilqr_hip_plant_set_observation): what the controller is told of the state.  One record of
+// OBS_REC = 100 doubles per rollout -- bias[50], sigma[50] in the tangent order of the Jacobians (dp, dphi, dq, dv, domega, dqdot) -- or ONE
+// record that every rollout reads (stride 0).  The error of rollout b in plant interval i is e = bias + sigma o z(seed, stream0 + b, i),
+// laid out as a state-shaped row delta[51] (the rotation vector as a unit quaternion); the measured state is x [+] delta.
+//   k_observation_draw  delta[count][B][51] of the intervals interval0 .. interval0 + count - 1: a pure function of its arguments
+//   k_observe_apply     out = x [+] delta for B rows (the warm starts' x0, ilqr_hip_plant_get_observed)
+//   k_plant_follow_o    plant_follow_body.h a fifth time: the control law on XO = XS [+] delta_j
+// observe_entry is the ONE statement of [+]: entry e of the measured row.  Both users compile it in this translation unit under
+// -ffp-contract=on, where the front end alone decides what is fused, so the solve's x0 and the law's x agree to the bit.
+#define OBS_NT 50
+#define OBS_REC 100
+DEVFN double observe_entry(const double* x, const double* d, int e) {
+  if (e < 3 || e > 6) return x[e] + d[e];
+  const double aw = x[3], ax = x[4], ay = x[5], az = x[6], bw = d[3], bx = d[4], by = d[5], bz = d[6];      // Hamilton product, wxyz, not renormalised
+  if (e == 3) return aw * bw - ax * bx - ay * by - az * bz;
+  if (e == 4) return aw * bx + ax * bw + ay * bz - az * by;
+  if (e == 5) return aw * by - ax * bz + ay * bw + az * bx;
+  return aw * bz + ax * by - ay * bx + az * bw;
+}
+// the wave's RPW rows: xs in LDS, the error rows of the interval in memory (rows without a rollout read the last rollout's, as they read its policy)
+template <int RPW>
+DEVFN void observe_rows(const DevState& S, const double* xs, const double* drow, int b0, double* xo) {
+  constexpr int n = PLANT_NX;
+  for (int it = threadIdx.x; it < RPW * n; it += 64) {
+    const int r = it / n, e = it - r * n;
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;
+    xo[it] = observe_entry(xs + r * n, drow + (size_t)br * n, e);
+  }
+}
+#define PLANT_TABLE 4
+#include "plant_follow_body.h"
+
+// Philox4x32-10 (Salmon et al., SC'11), the counter-based generator: ten rounds of two 32 x 32 -> 64 bit products, the key bumped by the
+// Weyl constants between rounds.  Integer arithmetic only: every implementation gives the same words.
+DEVFN void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// One lane per (rollout, Philox block): 25 blocks -- counter (stream lo, stream hi, interval lo, block), key (seed lo, seed hi) -- make a
+// rollout's 50 normals by Box-Muller, the fp64 log and sincos being the cost.  OBS_RPB rollouts per workgroup of 256 lanes (250 busy); the
+// tangent errors and then the state-shaped rows are assembled in LDS and leave in one coalesced run of OBS_RPB x 51 consecutive doubles:
+// the rows of one interval are contiguous over the rollouts.  grid (ceil(B / OBS_RPB), count).  Draws are made whatever sigma is.
+#define OBS_RPB 10
+__global__ void __launch_bounds__(256) k_observation_draw(int B, const double* records, int rec_stride, unsigned long long seed, unsigned long long stream0, long interval0, double* out) {
+  __shared__ double er[OBS_RPB * OBS_NT];
+  __shared__ double dr[OBS_RPB * PLANT_NX];
+  const int tid = threadIdx.x;
+  const int b0 = blockIdx.x * OBS_RPB;
+  const int rows = B - b0 < OBS_RPB ? B - b0 : OBS_RPB;
+  const unsigned long long iv = (unsigned long long)(interval0 + (long)blockIdx.y);
+  const int r = tid / 25, k = tid - r * 25;
+  if (r < rows) {
+    const unsigned long long s = stream0 + (unsigned long long)(b0 + r);
+    unsigned w[4];
+    philox4x32_10((unsigned)s, (unsigned)(s >> 32), (unsigned)iv, (unsigned)k, (unsigned)seed, (unsigned)(seed >> 32), w);
+    const double u1 = ((double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) + 0.5) * 0x1p-53;
+    const double u2 = ((double)((((unsigned long long)w[2] << 32) | w[3]) >> 11) + 0.5) * 0x1p-53;
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586 * u2;
+    double sn, cs;
+    sincos(ang, &sn, &cs);
+    const double* rec = records + (size_t)(b0 + r) * rec_stride;
+    // (the product rounded on its own, then the sum: no fused multiply-add between a record and its draw)
+    const double z0 = rad * cs, z1 = rad * sn;
+    const double s0 = rec[OBS_NT + 2 * k] * z0, s1 = rec[OBS_NT + 2 * k + 1] * z1;
+    er[r * OBS_NT + 2 * k] = rec[2 * k] + s0;
+    er[r * OBS_NT + 2 * k + 1] = rec[2 * k + 1] + s1;
+  }
+  __syncthreads();
+  for (int it = tid; it < rows * PLANT_NX; it += 256) {
+    const int rr = it / PLANT_NX, e = it - rr * PLANT_NX;
+    const double* ev = er + rr * OBS_NT;
+    double v;
+    if (e < 3) v = ev[e];
+    else if (e > 6) v = ev[e - 1];
+    else {
+      const double xx = ev[3] * ev[3], yy = ev[4] * ev[4], zz = ev[5] * ev[5];
+      const double sum = xx + yy;
+      const double th = sqrt(sum + zz);
+      if (th == 0.0) v = e == 3 ? 1.0 : 0.0;
+      else if (e == 3) v = cos(0.5 * th);
+      else { const double f = sin(0.5 * th) / th; v = f * ev[e - 1]; }
+    }
+    dr[it] = v;
+  }
+  __syncthreads();
+  double* o = out + ((size_t)blockIdx.y * B + b0) * PLANT_NX;
+  for (int it = tid; it < rows * PLANT_NX; it += 256) o[it] = dr[it];
+}
+// out[b] = x[b] [+] delta[b], one lane per entry
+__global__ void __launch_bounds__(256) k_observe_apply(int B, const double* x, const double* delta, double* out) {
+  const long it = (long)blockIdx.x * 256 + threadIdx.x;
+  if (it >= (long)B * PLANT_NX) return;
+  const int b = (int)(it / PLANT_NX), e = (int)(it - (long)b * PLANT_NX);
+  out[it] = observe_entry(x + (size_t)b * PLANT_NX, delta + (size_t)b * PLANT_NX, e);
+}
 #endif
 
 struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
@@ -463,6 +575,42 @@ static void launch_step_payload(int count, const double* x, const double* u, con
   const dim3 grid((unsigned)((count + 31) / 32));
   with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_m<K()>), grid, dim3(64), STEP_M_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench, payload); });
 }
+#elif defined(PLANT_OBSERVE_MODULE)      // attributes and launchers of the observation family, exported from its module with C linkage (ilqr_kernels.h)
+template <int FB> static constexpr size_t follow_lds_o() {
+  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX) * sizeof(double);
+}
+static_assert(follow_lds_o<0>() <= 160 * 1024 && follow_lds_o<1>() <= 160 * 1024, "k_plant_follow_o: the workgroup's LDS");
+template <int KIND, int FB> static int plant_attr_o() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_o<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_o<FB>()) != hipSuccess;
+}
+static int observe_kernels_set_attr() {
+  int rc = 0;
+  for_each_step_kind([&](auto K) { rc |= plant_attr_o<K(), 0>(); rc |= plant_attr_o<K(), 1>(); });
+  return rc;
+}
+template <int KIND, int FB>
+static void follow_launch_o(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_o<KIND, FB>), grid, dim3(64), follow_lds_o<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs);
+}
+static void launch_plant_follow_observe(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const WrenchFollowArgs& w,
+                                        hipStream_t st) {
+  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (w.feedback_mode) follow_launch_o<K(), 1>(S, Pl, dyn, T, W, M, dobs, a, st);
+    else follow_launch_o<K(), 0>(S, Pl, dyn, T, W, M, dobs, a, st);
+  });
+}
+static void launch_observation_draw(int B, const ObservationTable& O, long interval0, int count, double* out, hipStream_t st) {
+  const dim3 grid((unsigned)((B + OBS_RPB - 1) / OBS_RPB), (unsigned)count);
+  hipLaunchKernelGGL(k_observation_draw, grid, dim3(256), 0, st, B, O.records, O.rec_stride, O.seed, O.stream0, interval0, out);
+}
+static void launch_observe_apply(int B, const double* x, const double* delta, double* out, hipStream_t st) {
+  const dim3 grid((unsigned)(((long)B * PLANT_NX + 255) / 256));
+  hipLaunchKernelGGL(k_observe_apply, grid, dim3(256), 0, st, B, x, delta, out);
+}
 #else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
 template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
 template <int KIND, int FB> static int plant_attr_w() {
@@ -521,5 +669,17 @@ void ilqr_payload_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* P
 void ilqr_payload_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload, hipStream_t st) {
   ilqr::launch_step_payload(count, x, u, *dyn, xn, stance_l, stance_r, wrench, payload, st);
 }
+}
+#endif
+
+#ifdef PLANT_OBSERVE_MODULE
+extern "C" {
+int ilqr_observe_module_set_attr() { return ilqr::observe_kernels_set_attr(); }
+void ilqr_observe_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
+                                const double* delta, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
+  ilqr::launch_plant_follow_observe(*S, *Pl, *dyn, *T, *W, *M, delta, *a, st);
+}
+void ilqr_observe_module_draw(int B, const ilqr::ObservationTable* O, long interval0, int count, double* delta, hipStream_t st) { ilqr::launch_observation_draw(B, *O, interval0, count, delta, st); }
+void ilqr_observe_module_apply(int B, const double* x, const double* delta, double* out, hipStream_t st) { ilqr::launch_observe_apply(B, x, delta, out, st); }
 }
 #endif

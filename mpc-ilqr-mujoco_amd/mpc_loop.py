@@ -60,6 +60,11 @@ reset of the run (BatchedILQR.plant_set_wrench).  Installed behind the parameter
 `MPCRunner(..., resident=True, plant_payload=P)` loads the plant: P [1, 10] or [B, 10] (scenario.stack_plant_payload) is a rigid payload fixed
 to the pelvis per rollout -- mass, centre of mass and rotational inertia, carried over the whole run (BatchedILQR.plant_set_payload).  Installed
 beside the wrench, in front of the reset; the solve keeps the unloaded model.
+
+`MPCRunner(..., resident=True, plant_observation=O, observation_seed=S, observation_stream0=0)` blurs what the controller is told: O [1, 100]
+or [B, 100] (scenario.stack_plant_observation) is a bias and a noise level per tangent coordinate and rollout; the warm starts and the
+plant's control law read the plant state with that error, drawn once per plant interval on the device (BatchedILQR.plant_set_observation).
+The cold first step initialises from plant_get_observed(); physics, ring and score stay on the true state.
 """
 import os
 import time
@@ -104,7 +109,8 @@ class MPCRunner:
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
-                 device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None):
+                 device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None,
+                 plant_observation=None, observation_seed=0, observation_stream0=0):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -142,6 +148,13 @@ class MPCRunner:
             if plant_payload.ndim != 2 or plant_payload.shape[1] != 10 or plant_payload.shape[0] not in (1, solver.B):
                 raise ValueError("plant_payload must be [1, 10] or [B, 10] (scenario.stack_plant_payload)")
         self.plant_payload = plant_payload
+        if not resident and plant_observation is not None:
+            raise ValueError("plant_observation needs the device-resident plant (resident=True)")
+        if plant_observation is not None:
+            plant_observation = np.atleast_2d(np.asarray(plant_observation, dtype=np.float64))
+            if plant_observation.ndim != 2 or plant_observation.shape[1] != 100 or plant_observation.shape[0] not in (1, solver.B):
+                raise ValueError("plant_observation must be [1, 100] or [B, 100] (scenario.stack_plant_observation)")
+        self.plant_observation, self.observation_seed, self.observation_stream0 = plant_observation, int(observation_seed), int(observation_stream0)
         self.device_refs, self.track_ready = bool(device_refs), False
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
@@ -280,6 +293,8 @@ class MPCRunner:
             s.plant_set_wrench(self.plant_wrench)
         if self.plant_payload is not None:
             s.plant_set_payload(self.plant_payload)
+        if self.plant_observation is not None:
+            s.plant_set_observation(self.plant_observation, seed=self.observation_seed, stream0=self.observation_stream0)
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)
@@ -314,9 +329,10 @@ class MPCRunner:
                 t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
                 self.last_cost = s.solve(None)
             else:                                            # the gravity-compensation guess is computed on the host from x0
-                s.initialize(x0, u_init)
+                xm = x0 if self.plant_observation is None else s.plant_get_observed()      # (the measurement of interval 0: the plant was reset to x0)
+                s.initialize(xm, u_init)
                 t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
-                self.last_cost = s.solve(x0)
+                self.last_cost = s.solve(xm)
             t3 = time.perf_counter(); self._add("MPC_iLQR_solve", t2, t3)
             if self.profile_stages:
                 self._add_stage_ms()

@@ -187,6 +187,39 @@ def stack_plant_payload(B, mass, com=None, inertia=None):
     return out
 
 
+# groups of an observation record in tangent order: argument stem, first coordinate, width (solver.PLANT_OBSERVATION_GROUPS)
+_OBSERVATION_GROUPS = (("position", 0, 3), ("orientation", 3, 3), ("joints", 6, 19), ("linear_velocity", 25, 3), ("angular_velocity", 28, 3), ("joint_velocities", 31, 19))
+
+
+def stack_plant_observation(B, **groups):
+    """Observation models [B, 100] for BatchedILQR.plant_set_observation / MPCRunner(plant_observation=...): bias[50] then sigma[50] in the
+    tangent order of the Jacobians.  Keywords, each `<group>_bias` or `<group>_noise` with group one of position (m, world), orientation
+    (rotation vector, body frame, rad), joints (rad), linear_velocity (m/s, world), angular_velocity (rad/s, body), joint_velocities
+    (rad/s); a value is a scalar, a vector of the group's width (3 or 19), [B] (one scalar per rollout) or [B, width]; what is not given is
+    zero.  Raises ValueError for an unknown keyword, a shape that is none of these, a non-finite entry or a negative noise level -- what
+    ilqr_hip_plant_set_observation refuses."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    out = np.zeros((B, 100))
+    known = {g + suffix: (first + half, width) for g, first, width in _OBSERVATION_GROUPS for suffix, half in (("_bias", 0), ("_noise", 50))}
+    for name, val in groups.items():
+        if name not in known:
+            raise ValueError("unknown observation group %r (known: %s)" % (name, ", ".join(sorted(known))))
+        first, width = known[name]
+        v = np.asarray(val, dtype=np.float64)
+        if v.shape == (B,) and B != width:      # (B == width: a vector is read per coordinate; [B, 1] says per rollout)
+            v = v[:, None]
+        if v.shape not in ((), (width,), (1, width), (B, 1), (B, width)):
+            raise ValueError("%s must be a scalar, [%d], [B] or [B, %d]" % (name, width, width))
+        out[:, first:first + width] = v
+    if not np.isfinite(out).all():
+        raise ValueError("plant observation records must be finite")
+    if (out[:, 50:] < 0).any():
+        raise ValueError("noise levels >= 0 are required")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

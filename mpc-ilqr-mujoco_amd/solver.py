@@ -51,6 +51,8 @@ EXPORTS = [
     "ilqr_hip_plant_set_wrench", "ilqr_hip_plant_clear_wrench", "ilqr_hip_plant_num_wrench_sets", "ilqr_hip_plant_get_wrench", "ilqr_hip_plant_intervals",
     "ilqr_hip_step_wrench", "ilqr_hip_pelvis_inertial_offset",
     "ilqr_hip_plant_set_payload", "ilqr_hip_plant_clear_payload", "ilqr_hip_plant_num_payload_sets", "ilqr_hip_plant_get_payload", "ilqr_hip_step_payload",
+    "ilqr_hip_plant_set_observation", "ilqr_hip_plant_clear_observation", "ilqr_hip_plant_num_observation_sets", "ilqr_hip_plant_get_observation",
+    "ilqr_hip_plant_observation_errors", "ilqr_hip_plant_get_observed",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
@@ -62,6 +64,10 @@ PLANT_PARAMS = ("gravity_x", "gravity_y", "gravity_z", "friction", "softness", "
 PLANT_WRENCH = ("force_x", "force_y", "force_z", "torque_x", "torque_y", "torque_z", "point_x", "point_y", "point_z", "first", "end")
 # columns of a plant payload record (include/ilqr_hip.h ILQR_PLANT_PAYLOAD)
 PLANT_PAYLOAD = ("mass", "com_x", "com_y", "com_z", "Ixx", "Iyy", "Izz", "Ixy", "Ixz", "Iyz")
+# groups of a plant observation record (include/ilqr_hip.h ILQR_PLANT_OBSERVATION): name, first tangent coordinate, width; the record is
+# bias[50] then sigma[50] in this order
+PLANT_OBSERVATION_GROUPS = (("position", 0, 3), ("orientation", 3, 3), ("joints", 6, 19), ("linear_velocity", 25, 3), ("angular_velocity", 28, 3), ("joint_velocities", 31, 19))
+PLANT_OBSERVATION = 100
 
 
 
@@ -747,6 +753,50 @@ class BatchedILQR:
     def plant_get_payload(self):
         """[B, 10] (columns PLANT_PAYLOAD): the record of each rollout; zeros without a table."""
         return self._get("ilqr_hip_plant_get_payload", (self.B, len(PLANT_PAYLOAD)))
+
+    def plant_set_observation(self, observation, seed=0, stream0=0):
+        """Install observation models [n_sets, 100] (bias[50], sigma[50] in tangent order; scenario.stack_plant_observation builds them),
+        n_sets 1 or B: the warm starts and the plant's control law read rollout b's state with the error of its record, drawn once per plant
+        interval from the counter-based generator under `seed`, rollout stream stream0 + b (ilqr_hip_plant_set_observation).  The plant's
+        physics, the ring and the score stay on the true state."""
+        observation = _c64(observation)
+        if observation.ndim == 1:
+            observation = observation[None]
+        if observation.ndim != 2 or observation.shape[1] != PLANT_OBSERVATION or observation.shape[0] not in (1, self.B):
+            raise ValueError("plant observation records must be [1, 100] or [B, 100]")
+        seed, stream0 = int(seed), int(stream0)
+        if not (0 <= seed < 1 << 64 and 0 <= stream0 < 1 << 64):
+            raise ValueError("seed and stream0 must fit 64 unsigned bits")
+        self._chk(self.L.ilqr_hip_plant_set_observation(self.h, _p(observation), int(observation.shape[0]), C.c_ulonglong(seed), C.c_ulonglong(stream0)))
+
+    def plant_clear_observation(self):
+        """Remove the observation models: the plant calls and warm starts launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_clear_observation(self.h))
+
+    def plant_num_observation_sets(self):
+        return int(self.L.ilqr_hip_plant_num_observation_sets(self.h))
+
+    def plant_get_observation(self):
+        """(records [B, 100], seed, stream0): the record of each rollout; zeros and 0, 0 without a table."""
+        out = np.zeros((self.B, PLANT_OBSERVATION))
+        seed, stream0 = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._chk(self.L.ilqr_hip_plant_get_observation(self.h, _p(out), C.byref(seed), C.byref(stream0)))
+        return out, int(seed.value), int(stream0.value)
+
+    def plant_observation_errors(self, interval0, count):
+        """delta [count, B, 51]: the state-shaped observation errors of the plant intervals interval0 .. interval0 + count - 1, a pure
+        function of table, seed, stream0 and interval (ilqr_hip_plant_observation_errors); 1 <= count <= N."""
+        interval0, count = int(interval0), int(count)
+        if interval0 < 0 or count < 1 or count > self.N:
+            raise ValueError("plant_observation_errors: interval0 >= 0 and 1 <= count <= N")
+        out = np.zeros((count, self.B, NX))
+        self._chk(self.L.ilqr_hip_plant_observation_errors(self.h, C.c_long(interval0), count, _p(out)))
+        return out
+
+    def plant_get_observed(self):
+        """[B, 51]: the plant state as the controller is told it now, x [+] delta(plant_intervals) -- what a warm start would hand the solve;
+        the plant state itself without a table."""
+        return self._get("ilqr_hip_plant_get_observed", (self.B, NX))
 
     def plant_score(self):
         """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""

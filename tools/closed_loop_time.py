@@ -30,7 +30,12 @@ given contact mode.
    python tools/closed_loop_time.py --payload [--contact-mode 2] [--solve-every M] ...
 compares, instead, the RESIDENT runner without a payload table against the same runner with one installed (MPCRunner(plant_payload=...): a
 rigid payload of 0 to 20 kg per rollout at the fixed offset (-0.1, 0, 0.3) in the pelvis frame, a backpack at torso height, over the whole
-run), alternating on one box, the plant in the given contact mode."""
+run), alternating on one box, the plant in the given contact mode.
+
+   python tools/closed_loop_time.py --observation [--contact-mode 0] [--solve-every M] ...
+compares, instead, the RESIDENT runner without an observation table against the same runner with one installed
+(MPCRunner(plant_observation=...): per rollout a pelvis position bias of up to 1 cm, 2 mrad of joint encoder noise and 0.05 rad/s of gyro
+noise), alternating on one box, the plant in the given contact mode."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py): behind the product library, torch finds "no HIP GPUs" when it is asked for the device name
@@ -53,6 +58,7 @@ def main():
     ap.add_argument("--plant-params", choices=("shared", "per-rollout"), default=None)
     ap.add_argument("--wrench", action="store_true")
     ap.add_argument("--payload", action="store_true")
+    ap.add_argument("--observation", action="store_true")
     ap.add_argument("--device-refs", action="store_true"); ap.add_argument("--per-rollout-starts", action="store_true"); ap.add_argument("--contact-mode", type=int, default=2)
     a = ap.parse_args()
     if a.per_rollout_starts and not a.device_refs:
@@ -70,6 +76,8 @@ def main():
         return wrench_main(a, sc, ml, rf, sv)
     if a.payload:
         return payload_main(a, sc, ml, rf, sv)
+    if a.observation:
+        return observation_main(a, sc, ml, rf, sv)
     base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
     rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
     rows = a.steps + N + 10
@@ -209,6 +217,59 @@ def payload_main(a, sc, ml, rf, sv):
                       "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
                       "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_payload": float(np.median(ms[True])),
                       "samples_no_payload": ms[False], "samples_payload": ms[True], "alive_no_payload": alive[False], "alive_payload": alive[True]}))
+
+
+def observation_main(a, sc, ml, rf, sv):
+    B, N = a.batch, a.horizon
+    base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
+    rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
+    rows = a.steps + N + 10
+    rd.set_states(np.tile(sc.standing_state(), (rows, 1))); rd.contact = np.ones((rows, 2), dtype=np.int32)
+    x0, ui = sc.synthetic_batch(B, N, 0, sv.gravity_compensation(sc.standing_state(), base["gravity"]))
+    table = sc.stack_plant_observation(B, position_bias=np.random.default_rng(1).uniform(-0.01, 0.01, (B, 3)), joints_noise=0.002, angular_velocity_noise=0.05)
+    ms, alive = {False: [], True: []}, {}
+    for rnd in range(a.rounds + 1):                      # round 0 warms up (first launches, allocations)
+        for tab in (False, True):
+            s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+            s.set_contact_mode(a.contact_mode)
+            run = ml.MPCRunner(s, rd, base, resident=True, substeps=a.substeps, feedback_mode=a.feedback_mode, solve_every=a.solve_every, plant_observation=table if tab else None,
+                               observation_seed=2024)
+            run.run(x0, 1, u_init=ui)                    # the cold start is not what is compared: every timed step is a warm one
+            s.synchronize()
+            t0 = time.perf_counter()
+            run.run(x0, a.steps, u_init=ui)
+            dt = time.perf_counter() - t0
+            alive[tab] = int(s.plant_alive().sum())
+            s.close()
+            if rnd:
+                ms[tab].append(1e3 * dt / a.steps)
+    # the plant call alone (with a table: the draw and the plant kernel): 50 back-to-back advances under one solve, three repetitions from the same plant state
+    kernel_us, alive_k = {}, {}
+    for mode in (0, 2):
+        s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+        s.set_problem(base); s.initialize(x0, ui); s.solve(x0)
+        s.plant_set_model(mode, None); s.plant_configure(a.substeps, a.feedback_mode, "schedule")
+        st = torch.cuda.ExternalStream(s.stream)
+        for tab in (False, True):
+            if tab:
+                s.plant_set_observation(table, seed=2024)
+            us = []
+            for rep_ in range(4):                        # (the first repetition warms up)
+                s.plant_reset(x0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(50):
+                    s.plant_advance()
+                e1.record(st); e1.synchronize()
+                us.append(1e3 * e0.elapsed_time(e1) / 50)
+            key = "mode%d_%s" % (mode, "table" if tab else "no_table")
+            kernel_us[key], alive_k[key] = us[1:], int(s.plant_alive().sum())
+        s.close()
+    print(json.dumps({"tool": "closed_loop_time", "mode": "observation", "plant_call_us": {k: float(np.median(v)) for k, v in kernel_us.items()}, "plant_call_samples_us": kernel_us,
+                      "alive_after_50_advances": alive_k, "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "iterations": a.iters, "steps": a.steps,
+                      "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
+                      "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_observation": float(np.median(ms[True])),
+                      "samples_no_observation": ms[False], "samples_observation": ms[True], "alive_no_observation": alive[False], "alive_observation": alive[True]}))
 
 
 class HostWindows:
