@@ -523,6 +523,58 @@ int ilqr_hip_plant_num_observation_sets(const ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_get_observation(ilqr_hip_ctx* ctx, double* obs /*[B][100]*/, unsigned long long* seed, unsigned long long* stream0);
 int ilqr_hip_plant_observation_errors(ilqr_hip_ctx* ctx, long interval0, int count, double* delta /*[count][B][51]*/);
 int ilqr_hip_plant_get_observed(ilqr_hip_ctx* ctx, double* x_obs /*[B][51]*/);
+/* ---- actuator delay, lag and torque noise, one model per rollout: between the control law and the joints.  In the reference's loop
+   (main/humanoid_mpc.cpp:122-190) the torque the law computes acts in the same substep, exactly; on a robot the solve takes time, the motor
+   drivers have a bandwidth and the delivered torque ripples.  One record of ILQR_PLANT_ACTUATOR doubles per set:
+     delay      an integer stored as a double, in plant SUBSTEPS, 0 <= delay <= ILQR_PLANT_ACTUATOR_MAX_DELAY
+     tau[19]    time constant of a first-order lag per joint, seconds, >= 0; 0: no lag
+     sigma[19]  torque noise per joint, N m, >= 0
+   With n the plant substeps run since the actuator's state was last primed and h = dt / substeps:
+     c_n     the COMMAND: the control law's output for substep n behind the non-finite guard (main:162-165: a command with a non-finite
+             entry is zero) -- constant over an interval at feedback mode 0, new in every substep at mode 1.  It stays what the plant
+             REPORTS: ilqr_hip_plant_get_control, the ring, hence the score.
+     a_n   = c_{n - delay}: a delay line of MAX_DELAY + 1 slots of 19 doubles per rollout, slot n % 9 written, slot (n - delay) % 9 read.
+     y_n   = y_{n-1} + beta o (a_n - y_{n-1}), beta_i = -expm1(-h / tau_i), the exact discretisation of tau y' = a - y (as MuJoCo's
+             `filterexact` activation dynamics is documented; the reference's h1.xml motors have none, so this is an option, no parity
+             claim).  The host computes beta in double when the table is installed and whenever ilqr_hip_plant_configure changes
+             `substeps`; the kernel reads it, and the product beta_i (a_i - y_i) is rounded on its own (no fused multiply-add).  For
+             tau_i == 0, y_i = a_i by SELECTION, not by arithmetic; its beta is never computed (the getter returns 1).
+     t_n   = y_n + sigma o z(i): z(i) 19 standard normals drawn once per plant INTERVAL i (ilqr_hip_plant_intervals) and held over it, as
+             the observation error is; sigma_i z_i is rounded on its own; sigma_i == 0 adds nothing, again by selection.
+     t_n goes where the control goes without a table: through the torque gain of the parameter record and then the step's clamp.
+   So a record of zeros is no table, bit for bit.
+   Priming: ilqr_hip_plant_reset, ilqr_hip_plant_configure and ilqr_hip_plant_set_actuator set n = 0; the first substep after that writes
+   c_0 into every slot and into y -- the joint was already holding that torque, a standing rollout does not drop for `delay` substeps.
+   The delay line and y persist across the plant calls.  A rollout that is frozen (non-finite) is handled as without a table.
+   The normals come from the generator of the observation model above, Philox4x32-10 with key (seed lo, seed hi) and counter
+   (s lo, s hi, i lo, k), s = stream0 + b, under a seed and stream0 of this call's own, in the blocks k = 32..41: block 32 + q gives the
+   normals of joints 2q and 2q + 1 as the observation's block gives z[2k], z[2k + 1]; the second normal of block 41 is discarded.  (The
+   observation uses k = 0..24: equal seeds do not correlate the two.)  Draws are made whatever sigma is.
+   plant_set_actuator: n_sets = 1 (one record that every rollout reads; the streams still differ) or the batch, else ILQR_ERR_ARG;
+   ILQR_ERR_ARG also for a null pointer, a non-finite entry, a negative tau or sigma, or a delay that is not an integer in 0..8, all checked
+   before the handle is touched.  The table, the derived beta rows, the actuator's state and a buffer of N x B x 19 normals are owned by the
+   handle; the call uploads and synchronises the handle's stream.  The table survives ilqr_hip_plant_reset and ilqr_hip_plant_configure.
+   While it is installed ilqr_hip_plant_advance / _follow launch the draw of the call's intervals and the actuator family of the plant
+   kernel (k_actuator_draw, k_plant_follow_a of the module libilqr_hip_actuator.so, opened from the library's directory on first use --
+   missing: ILQR_ERR_UNSUPPORTED with the path in ilqr_hip_last_error, never a fall-back; an advance is that kernel over one interval),
+   which carries parameter record, wrench, payload and observation as the observation family does, each table present or not.
+   plant_clear_actuator: frees the table; the plant calls then launch exactly what they launch without it.
+   plant_num_actuator_sets: 0 without a table, else n_sets; -1 for a null handle.
+   plant_get_actuator: act[B][39], the record of each rollout (zeros without a table); seed / stream0 (each may be NULL; 0 without).
+   plant_get_actuator_blend: beta[B][19] as the kernel reads it, to the bit; ILQR_ERR_STATE without a table.
+   plant_actuator_draws: z[count][B][19] of the intervals interval0 .. interval0 + count - 1, a pure function of seed, stream0 and
+   interval; 1 <= count <= N and interval0 >= 0, else ILQR_ERR_ARG; ILQR_ERR_STATE without a table.
+   plant_get_applied: tau[B][19] = t_n of the last substep run under the table, in front of the torque gain and the clamp (zeros before
+   the first); without a table the reported control. */
+#define ILQR_PLANT_ACTUATOR 39            /* delay, tau[19], sigma[19] */
+#define ILQR_PLANT_ACTUATOR_MAX_DELAY 8
+int ilqr_hip_plant_set_actuator(ilqr_hip_ctx* ctx, const double* act /*[n_sets][39]*/, int n_sets, unsigned long long seed, unsigned long long stream0);
+int ilqr_hip_plant_clear_actuator(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_num_actuator_sets(const ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_actuator(ilqr_hip_ctx* ctx, double* act /*[B][39]*/, unsigned long long* seed, unsigned long long* stream0);
+int ilqr_hip_plant_get_actuator_blend(ilqr_hip_ctx* ctx, double* beta /*[B][19]*/);
+int ilqr_hip_plant_actuator_draws(ilqr_hip_ctx* ctx, long interval0, int count, double* z /*[count][B][19]*/);
+int ilqr_hip_plant_get_applied(ilqr_hip_ctx* ctx, double* tau /*[B][19]*/);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

@@ -237,6 +237,22 @@ class iLQR {
     Vec d((size_t)count * B_ * ILQR_NX); chk(ilqr_hip_plant_observation_errors(ctx_, interval0, count, d.data())); return d;
   }
   Vec plantObserved() { Vec x((size_t)B_ * ILQR_NX); chk(ilqr_hip_plant_get_observed(ctx_, x.data())); return x; }      // [batch][51]
+  // actuator delay, lag and torque noise per rollout (ilqr_hip.h ilqr_hip_plant_set_actuator): [n_sets][39] = delay (plant substeps), tau[19], sigma[19]
+  void plantSetActuator(const Vec& act, int n_sets, unsigned long long seed, unsigned long long stream0 = 0) {
+    if (n_sets < 1 || act.size() != (size_t)n_sets * ILQR_PLANT_ACTUATOR) throw std::runtime_error("actuator records must hold n_sets * 39 doubles");
+    chk(ilqr_hip_plant_set_actuator(ctx_, act.data(), n_sets, seed, stream0));
+  }
+  void plantClearActuator() { chk(ilqr_hip_plant_clear_actuator(ctx_)); }
+  int plantNumActuatorSets() const { return ilqr_hip_plant_num_actuator_sets(ctx_); }
+  Vec plantActuator(unsigned long long* seed = nullptr, unsigned long long* stream0 = nullptr) {      // [batch][39]
+    Vec a((size_t)B_ * ILQR_PLANT_ACTUATOR); chk(ilqr_hip_plant_get_actuator(ctx_, a.data(), seed, stream0)); return a;
+  }
+  Vec plantActuatorBlend() { Vec b((size_t)B_ * ILQR_NU); chk(ilqr_hip_plant_get_actuator_blend(ctx_, b.data())); return b; }      // [batch][19]
+  Vec plantActuatorDraws(long interval0, int count) {      // [count][batch][19]
+    if (count < 1) throw std::runtime_error("plantActuatorDraws: count >= 1");
+    Vec z((size_t)count * B_ * ILQR_NU); chk(ilqr_hip_plant_actuator_draws(ctx_, interval0, count, z.data())); return z;
+  }
+  Vec plantApplied() { Vec t((size_t)B_ * ILQR_NU); chk(ilqr_hip_plant_get_applied(ctx_, t.data())); return t; }      // [batch][19]
   static std::array<double, 3> pelvisInertialOffset() { std::array<double, 3> r{}; ilqr_hip_pelvis_inertial_offset(r.data()); return r; }
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492

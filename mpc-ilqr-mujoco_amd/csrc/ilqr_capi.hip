@@ -180,6 +180,22 @@ struct ilqr_hip_ctx {
   double* d_obs_delta = nullptr;
   double* d_obs_x = nullptr;      // [B][51] the measured state of ilqr_hip_plant_get_observed
   bool observe_attr_set = false;  // the observation module's kernels have their LDS attributes on this handle's device
+  // actuator table (ilqr_hip_plant_set_actuator; plant_kernels.hip k_plant_follow_a): [n][39] doubles, n = 1 or B; null: none.  While it is
+  // installed the plant calls launch the actuator family behind a draw of the call's normals into d_act_z [N][B][19].  act_rec is the host's
+  // copy, from which d_act_beta [n][19] is derived again when plant_configure changes the substeps.  The actuator's state -- delay line
+  // [B][9][19], lag output [B][19] -- and the applied torque of the last substep [B][19] persist across the calls; act_substeps counts the
+  // substeps run since the state was primed (0: the next substep primes it).
+  double* d_pact = nullptr;
+  int act_sets = 0;
+  unsigned long long act_seed = 0, act_stream0 = 0;
+  std::vector<double> act_rec, act_beta;
+  double* d_act_beta = nullptr;
+  double* d_act_z = nullptr;
+  double* d_act_fifo = nullptr;
+  double* d_act_y = nullptr;
+  double* d_act_applied = nullptr;
+  long act_substeps = 0;
+  bool actuator_attr_set = false;  // the actuator module's kernels have their LDS attributes on this handle's device
   long plant_intervals = 0;   // plant intervals run since the last ilqr_hip_plant_reset (the history cursor only counts while a ring exists)
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
@@ -395,6 +411,49 @@ static int need_observe_module(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 
+// The actuator family (csrc/Makefile ../lib/libilqr_hip_actuator.so) is a module of its own in the same way, opened on the first
+// ilqr_hip_plant_set_actuator.
+namespace {
+struct ActuatorModule {
+  void* lib = nullptr;
+  ilqr::actuator_set_attr_fn set_attr = nullptr;
+  ilqr::actuator_follow_fn follow = nullptr;
+  ilqr::actuator_draw_fn draw = nullptr;
+  std::string why;
+  bool ok() const { return lib && set_attr && follow && draw; }
+};
+ActuatorModule& actuator_module() {
+  static ActuatorModule m;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    Dl_info info;
+    std::string dir = ".";
+    if (dladdr((const void*)&ilqr_hip_plant_num_actuator_sets, &info) && info.dli_fname) {
+      const std::string self = info.dli_fname;
+      const size_t slash = self.rfind('/');
+      if (slash != std::string::npos) dir = self.substr(0, slash);
+    }
+    const std::string path = dir + "/libilqr_hip_actuator.so";
+    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!m.lib) { m.why = "the actuator kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.set_attr = (ilqr::actuator_set_attr_fn)dlsym(m.lib, "ilqr_actuator_module_set_attr");
+    m.follow = (ilqr::actuator_follow_fn)dlsym(m.lib, "ilqr_actuator_module_follow");
+    m.draw = (ilqr::actuator_draw_fn)dlsym(m.lib, "ilqr_actuator_module_draw");
+    if (!m.ok()) m.why = "the actuator kernels' module lacks an entry point: " + path;
+  });
+  return m;
+}
+}  // namespace
+static int need_actuator_module(ilqr_hip_ctx* c) {
+  ActuatorModule& m = actuator_module();
+  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
+  if (!c->actuator_attr_set) {
+    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the actuator kernels"; return ILQR_ERR_HIP; }
+    c->actuator_attr_set = true;
+  }
+  return ILQR_OK;
+}
+
 extern "C" {
 
 int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt) {
@@ -482,7 +541,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm, c->d_pobs, c->d_obs_delta, c->d_obs_x}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm, c->d_pobs, c->d_obs_delta, c->d_obs_x, c->d_pact, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1568,7 +1627,7 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
 // The wrench family (k_plant_follow_w) always reads a parameter record: the parameter table's, or this ONE record of the handle's own values
 // with gain 1, uploaded again whenever the handle's values have changed.
 static int plant_self_params(ilqr_hip_ctx* c) {
-  if ((!c->d_wrench && !c->d_ppayload && !c->d_pobs) || c->d_pparams) return ILQR_OK;
+  if ((!c->d_wrench && !c->d_ppayload && !c->d_pobs && !c->d_pact) || c->d_pparams) return ILQR_OK;
   const h1::DynParams& d = c->P.dyn;
   const double rec[ILQR_PLANT_PARAMS + 1] = {d.g[0], d.g[1], d.g[2], d.mu, d.soft, d.lim_k, 1.0, 0.0};
   if (c->d_self_params && std::memcmp(rec, c->self_params, sizeof(rec)) == 0) return ILQR_OK;
@@ -1599,9 +1658,37 @@ static int enqueue_measured_x0(ilqr_hip_ctx* c, double* out) {
   HIPCHK(c, hipGetLastError());
   return ILQR_OK;
 }
+// beta = -expm1(-h / tau), h = dt / substeps, of every record of the actuator table, in double on the host -> d_act_beta.  tau == 0 (no lag: the
+// kernel selects y = a) is never computed; its beta reads 1.
+static int upload_actuator_blend(ilqr_hip_ctx* c) {
+  const double h = c->P.dyn.h / c->plant_substeps;      // (the plant's step: plant_dyn)
+  c->act_beta.assign((size_t)c->act_sets * ILQR_NU, 1.0);
+  for (int s = 0; s < c->act_sets; ++s)
+    for (int i = 0; i < ILQR_NU; ++i) {
+      const double tau = c->act_rec[(size_t)s * ILQR_PLANT_ACTUATOR + 1 + i];
+      if (tau != 0.0) c->act_beta[(size_t)s * ILQR_NU + i] = -std::expm1(-h / tau);
+    }
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the rows this one replaces)
+  HIPCHK(c, hipMemcpy(c->d_act_beta, c->act_beta.data(), c->act_beta.size() * sizeof(double), hipMemcpyHostToDevice));
+  return ILQR_OK;
+}
 static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  if (c->d_pobs) {      // the observation family: the payload family's superset (either table may be null) behind the draw of the call's error rows
+  if (c->d_pact) {      // the actuator family: the observation family's superset (each of its tables may be null) behind the draw(s) of the call's intervals
+    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
+    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+    if (c->d_pobs) {      // (the callers have checked both modules: need_observe_module, need_actuator_module)
+      const ilqr::ObservationTable O = observation_table(c);
+      observe_module().draw(c->B, &O, c->plant_intervals, count, c->d_obs_delta, c->stream);
+    }
+    actuator_module().draw(c->B, c->act_seed, c->act_stream0, c->plant_intervals, count, c->d_act_z, c->stream);
+    const bool one = c->act_sets == 1;
+    const ilqr::ActuatorTable A{c->d_pact, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
+    actuator_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, c->d_pobs ? c->d_obs_delta : nullptr, &A, &a, c->stream);
+    c->act_substeps += (long)count * c->plant_substeps;
+  } else if (c->d_pobs) {      // the observation family: the payload family's superset (either table may be null) behind the draw of the call's error rows
     const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
     const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
     const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
@@ -1642,6 +1729,7 @@ int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   if (c->score_on) HIPCHK(c, hipMemcpyAsync(c->d_score, empty.data(), empty.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's buffers are free on return)
   c->plant_set = true; c->plant_kick = false; c->hist_n = 0; c->plant_intervals = 0;
+  c->act_substeps = 0;      // (the actuator's state is primed again by the next substep)
   return ILQR_OK;
 }
 int ilqr_hip_plant_configure(ilqr_hip_ctx* c, int substeps, int feedback_mode, int contact_source) {
@@ -1650,7 +1738,10 @@ int ilqr_hip_plant_configure(ilqr_hip_ctx* c, int substeps, int feedback_mode, i
   if (contact_source == ILQR_STANCE_GEOMETRY) {
     if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
+  const bool new_h = substeps != c->plant_substeps;
   c->plant_substeps = substeps; c->plant_feedback = feedback_mode; c->plant_source = contact_source;
+  c->act_substeps = 0;      // (the actuator's state is primed again by the next substep)
+  if (c->d_pact && new_h) TRY(upload_actuator_blend(c));      // (beta depends on h = dt / substeps)
   return ILQR_OK;
 }
 int ilqr_hip_plant_kick(ilqr_hip_ctx* c, const double* dv) {
@@ -1671,8 +1762,9 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
   TRY(plant_self_params(c));
+  if (c->d_pact) TRY(need_actuator_module(c));
   if (c->d_pobs) TRY(need_observe_module(c));
-  else if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  else if (c->d_ppayload && !c->d_pact) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
@@ -1710,8 +1802,9 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
     return ILQR_ERR_STATE;
   }
   TRY(plant_self_params(c));
+  if (c->d_pact) TRY(need_actuator_module(c));
   if (c->d_pobs) TRY(need_observe_module(c));
-  else if (c->d_ppayload) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  else if (c->d_ppayload && !c->d_pact) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
@@ -2084,6 +2177,90 @@ int ilqr_hip_plant_get_observed(ilqr_hip_ctx* c, double* x_obs) {
   TRY(enter_launching(c));
   TRY(enqueue_measured_x0(c, c->d_obs_x));
   HIPCHK(c, hipMemcpyAsync(x_obs, c->d_obs_x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+// ---- actuator delay, lag and torque noise per rollout (plant_kernels.hip k_actuator_draw, k_plant_follow_a)
+int ilqr_hip_plant_set_actuator(ilqr_hip_ctx* c, const double* act, int n_sets, unsigned long long seed, unsigned long long stream0) {
+  if (!act || n_sets < 1) return ILQR_ERR_ARG;
+  constexpr int R = ILQR_PLANT_ACTUATOR;
+  for (size_t i = 0; i < (size_t)n_sets * R; ++i) {
+    if (!std::isfinite(act[i]) || act[i] < 0.0) return ILQR_ERR_ARG;      // (delay, tau and sigma are all non-negative)
+    if (i % R == 0 && (act[i] > ILQR_PLANT_ACTUATOR_MAX_DELAY || act[i] != std::floor(act[i]))) return ILQR_ERR_ARG;
+  }
+  if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(need_actuator_module(c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (c->d_pact && c->act_sets != n_sets) { hipFree(c->d_pact); hipFree(c->d_act_beta); c->d_pact = c->d_act_beta = nullptr; c->act_sets = 0; }
+  const size_t bu = (size_t)c->B * ILQR_NU;
+  if (!c->d_act_z) HIPCHK(c, hipMalloc((void**)&c->d_act_z, (size_t)c->N * bu * sizeof(double)));
+  if (!c->d_act_fifo) HIPCHK(c, hipMalloc((void**)&c->d_act_fifo, (size_t)(ILQR_PLANT_ACTUATOR_MAX_DELAY + 1) * bu * sizeof(double)));
+  if (!c->d_act_y) HIPCHK(c, hipMalloc((void**)&c->d_act_y, bu * sizeof(double)));
+  if (!c->d_act_applied) { HIPCHK(c, hipMalloc((void**)&c->d_act_applied, bu * sizeof(double))); HIPCHK(c, hipMemsetAsync(c->d_act_applied, 0, bu * sizeof(double), c->stream)); }
+  if (!c->d_act_beta) HIPCHK(c, hipMalloc((void**)&c->d_act_beta, (size_t)n_sets * ILQR_NU * sizeof(double)));
+  if (!c->d_pact) HIPCHK(c, hipMalloc((void**)&c->d_pact, (size_t)n_sets * R * sizeof(double)));
+  c->act_sets = n_sets; c->act_seed = seed; c->act_stream0 = stream0;
+  c->act_rec.assign(act, act + (size_t)n_sets * R);
+  c->act_substeps = 0;      // (the actuator's state is primed again by the next substep)
+  HIPCHK(c, hipMemcpyAsync(c->d_pact, act, (size_t)n_sets * R * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return upload_actuator_blend(c);      // (synchronises the stream)
+}
+int ilqr_hip_plant_clear_actuator(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->d_pact) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+    hipFree(c->d_pact); hipFree(c->d_act_beta);
+  }
+  c->d_pact = c->d_act_beta = nullptr; c->act_sets = 0; c->act_seed = 0; c->act_stream0 = 0; c->act_substeps = 0;
+  c->act_rec.clear(); c->act_beta.clear();
+  return ILQR_OK;
+}
+int ilqr_hip_plant_num_actuator_sets(const ilqr_hip_ctx* c) { return c ? c->act_sets : -1; }
+int ilqr_hip_plant_get_actuator(ilqr_hip_ctx* c, double* act, unsigned long long* seed, unsigned long long* stream0) {
+  if (!c || !act) return ILQR_ERR_ARG;
+  enter(c);
+  constexpr int R = ILQR_PLANT_ACTUATOR;
+  if (seed) *seed = c->act_seed;
+  if (stream0) *stream0 = c->act_stream0;
+  if (!c->d_pact) {      // (no table: the command is the torque)
+    std::fill(act, act + (size_t)c->B * R, 0.0);
+    return ILQR_OK;
+  }
+  std::vector<double> rec((size_t)c->act_sets * R);
+  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pact, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(act + (size_t)b * R, rec.data() + (size_t)(c->act_sets == 1 ? 0 : b) * R, R * sizeof(double));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_get_actuator_blend(ilqr_hip_ctx* c, double* beta) {
+  if (!c || !beta) return ILQR_ERR_ARG;
+  enter(c);
+  if (!c->d_pact) { c->err = "plant_get_actuator_blend without an actuator table (ilqr_hip_plant_set_actuator)"; return ILQR_ERR_STATE; }
+  std::vector<double> rows((size_t)c->act_sets * ILQR_NU);      // (from the device: the rows the kernel reads)
+  HIPCHK(c, hipMemcpyAsync(rows.data(), c->d_act_beta, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(beta + (size_t)b * ILQR_NU, rows.data() + (size_t)(c->act_sets == 1 ? 0 : b) * ILQR_NU, ILQR_NU * sizeof(double));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_actuator_draws(ilqr_hip_ctx* c, long interval0, int count, double* z) {
+  if (!c || !z || interval0 < 0 || count < 1 || count > c->N) return ILQR_ERR_ARG;
+  if (!c->d_pact) { c->err = "plant_actuator_draws without an actuator table (ilqr_hip_plant_set_actuator)"; return ILQR_ERR_STATE; }
+  TRY(enter_launching(c));
+  TRY(need_actuator_module(c));
+  actuator_module().draw(c->B, c->act_seed, c->act_stream0, interval0, count, c->d_act_z, c->stream);      // (the buffer of the plant calls: they draw again in front of every use)
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(z, c->d_act_z, (size_t)count * c->B * ILQR_NU * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_get_applied(ilqr_hip_ctx* c, double* tau) {
+  if (!c || !tau) return ILQR_ERR_ARG;
+  if (!c->plant_set) return ILQR_ERR_STATE;
+  if (!c->d_pact) return ilqr_hip_plant_get_control(c, tau);
+  enter(c);
+  HIPCHK(c, hipMemcpyAsync(tau, c->d_act_applied, (size_t)c->B * ILQR_NU * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }

@@ -239,6 +239,33 @@ typedef int (*observe_set_attr_fn)();
 typedef void (*observe_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const WrenchFollowArgs*, hipStream_t);
 typedef void (*observe_draw_fn)(int, const ObservationTable*, long, int, double*, hipStream_t);
 typedef void (*observe_apply_fn)(int, const double*, const double*, double*, hipStream_t);
+// the same with an actuator between the control law and the joints (ilqr_hip_plant_set_actuator): per substep the law's output -- the
+// COMMAND, which stays what the plant reports -- goes through a delay line, a first-order lag and additive noise, and the step takes the
+// result.  rollout b reads record b * rec_stride of A.records -- delay, tau[19], sigma[19]; 39 doubles -- and row b * blend_stride of
+// A.blend, beta[19] = -expm1(-h / tau) as the host computed it (rec_stride 39 / blend_stride 19, or both 0: one record for all).
+// A.z: the normals [count][B][19] of the call's intervals as ilqr_actuator_module_draw wrote them.  The actuator's state is the handle's
+// and persists across launches: fifo [B][9][19], y [B][19]; applied [B][19] takes the torque of the launch's last substep.  substep0:
+// substeps run since the state was primed; 0 primes it (every slot and y take the first command).
+// T as in the wrench family; W.records, M.records and the observation rows delta may each be null.
+struct ActuatorTable {
+  const double* records;
+  int rec_stride;
+  const double* blend;
+  int blend_stride;
+  const double* z;
+  double* fifo;
+  double* y;
+  double* applied;
+  long substep0;
+};
+// The family lives in a module of its own as well, libilqr_hip_actuator.so (plant_kernels.hip compiled with -DPLANT_ACTUATOR_MODULE):
+//   int  ilqr_actuator_module_set_attr()
+//   void ilqr_actuator_module_follow(S, Pl, dyn, T, W, M, delta or null, A, args, stream)
+//   void ilqr_actuator_module_draw(B, seed, stream0, interval0, count, z[count][B][19], stream)     the normals of intervals interval0 .. + count - 1
+typedef int (*actuator_set_attr_fn)();
+typedef void (*actuator_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
+                                   const WrenchFollowArgs*, hipStream_t);
+typedef void (*actuator_draw_fn)(int, unsigned long long, unsigned long long, long, int, double*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

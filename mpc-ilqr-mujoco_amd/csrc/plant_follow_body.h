@@ -14,10 +14,19 @@
 //                  a MEASUREMENT of the state (ilqr_hip_plant_set_observation): one more kernel argument, the error rows dobs[count][B][51]
 //                  of the call's intervals, and RPW more rows of LDS, XO = XS [+] delta_j, written in front of every control law.  Ring,
 //                  alive, the guards and the step stay on the true state XS.
+//   PLANT_TABLE 5  k_plant_follow_a: as 4 with dobs null as well (then the law reads XS itself), and an ACTUATOR between the law and the joints
+//                  (ilqr_hip_plant_set_actuator): nine more kernel arguments and RPW more rows of LDS, UA -- in every substep the actuator stage
+//                  turns the command rows US into the applied rows UA (delay line and lag state in memory, actuator_stage), and the step
+//                  loads UA.  What the interval reports stays the command: it is loaded again from US at the interval's end, so no second
+//                  control vector is live across the step.
 #ifndef PLANT_TABLE
-#error "define PLANT_TABLE (0, 1, 2, 3 or 4) before including plant_follow_body.h"
+#error "define PLANT_TABLE (0, 1, 2, 3, 4 or 5) before including plant_follow_body.h"
 #endif
-#if PLANT_TABLE == 4
+#if PLANT_TABLE == 5
+#define K_PLANT_FOLLOW k_plant_follow_a
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs, \
+                           const double* atab, int a_stride, const double* abeta, int ab_stride, const double* az, double* afifo, double* ay, double* aapplied, long substep0
+#elif PLANT_TABLE == 4
 #define K_PLANT_FOLLOW k_plant_follow_o
 #define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs
 #elif PLANT_TABLE == 3
@@ -54,7 +63,13 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #if PLANT_TABLE
   stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
 #endif
-#if PLANT_TABLE == 4
+#if PLANT_TABLE == 5
+  constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // the rows of family 4, then the applied rows
+  constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
+  constexpr int UA0 = XO0 + RPW * n;
+  stage_disturbance_records<RPW, true>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
+  const bool disturbed = wtab != nullptr || mtab != nullptr;      // (wave-uniform: kernel arguments)
+#elif PLANT_TABLE == 4
   constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // disturbance rows as in family 3 (a null payload table stages zeros), then the observed rows
   constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
   stage_disturbance_records<RPW, true>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
@@ -99,7 +114,15 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
       const int prt = lane >> 1;
       if (FB != 0 || k == 0) {
         wave_lds_fence();
-#if PLANT_TABLE == 4
+#if PLANT_TABLE == 5
+        if (dobs) {      // (wave-uniform: a kernel argument) as family 4; without observation rows the law on XS itself, as families 0 to 3
+          observe_rows<RPW>(S, lds + Lay::XS, dobs + (size_t)j * S.B * n, b0, lds + XO0);
+          wave_lds_fence();
+          control_law<FB, XO0>(S, lds, b0, kt);
+        } else {
+          control_law<FB>(S, lds, b0, kt);
+        }
+#elif PLANT_TABLE == 4
         // what the controller is told of the state: the interval's error on the rows as they stand (FB = 1: the substep's), the law on XO
         observe_rows<RPW>(S, lds + Lay::XS, dobs + (size_t)j * S.B * n, b0, lds + XO0);
         wave_lds_fence();
@@ -109,12 +132,24 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #endif
         wave_lds_fence();
       }
+#if PLANT_TABLE == 5
+      // the actuator, in every substep (FB = 0: the command rows are the interval's, the delay line and the lag still move): US -> UA.  Its
+      // lanes are dealt out over the RPW x 19 entries as the law's; the guard of main:162-165 acts in it, in front of the delay line
+      wave_lds_fence();      // (the previous substep's readers of UA are done)
+      actuator_stage<FB>(S, lds, b0, UA0, atab, a_stride, abeta, ab_stride, az + (size_t)j * S.B * m, afifo, ay, aapplied, substep0 + (long)j * substeps + k,
+                         j == count - 1 && k == substeps - 1);
+      wave_lds_fence();
+#endif
       if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
       const int pc = prt < RPW ? prt : 0;
+#if PLANT_TABLE == 5
+      load_half_u(side_t, lds + UA0 + pc * m, u);      // the APPLIED torque (guarded in the stage); the command is loaded again at the interval's end
+#else
       load_half_u(side_t, lds + Lay::US + pc * m, u);
       bool ufin = finite_half_u(u);
       ufin = h1s::xch_flag(ufin) && ufin;
       if (!ufin) zero_half_u(u);      // main:162-165
+#endif
       wave_lds_fence();      // (the odd lane reads the shared coordinates its partner stored at the end of the previous substep)
       if (run) {
         const h1s::LaneLds L{lds, 64, lane};
@@ -122,7 +157,7 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
         if constexpr (KIND >= 1 && KIND <= 4) {
           if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
         }
-#if PLANT_TABLE == 4
+#if PLANT_TABLE >= 4
         // without a wrench and a payload table the step of k_plant_follow_p (under the handle's own record: the plant without a table, bit
         // for bit); with either the step of k_plant_follow_m
         if (disturbed) {
@@ -158,6 +193,14 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
     fin = finite_half(h);
     fin = h1s::xch_flag(fin) && fin;
     run = run && fin;
+#if PLANT_TABLE == 5
+    {      // what the interval reports is the COMMAND of its last substep, behind the guard: the rows US still hold it
+      load_half_u(side, lds + Lay::US + (pr < RPW ? pr : 0) * m, u);
+      bool ufin = finite_half_u(u);
+      ufin = h1s::xch_flag(ufin) && ufin;
+      if (!ufin) zero_half_u(u);
+    }
+#endif
     if (!run) zero_half_u(u);
     if (owner && hist_row >= 0) store_half_u(side, u, Pl.hist_u + ((size_t)hist_row * S.B + b) * m);
     if (run) { moved = true; st_done[0] = st[0]; st_done[1] = st[1]; }

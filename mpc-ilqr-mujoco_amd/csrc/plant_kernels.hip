@@ -8,8 +8,9 @@
 //                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
 // A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
-// five times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w),
-// with parameter, wrench and payload tables (k_plant_follow_m), and with those three under an observation table (k_plant_follow_o).
+// six times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w),
+// with parameter, wrench and payload tables (k_plant_follow_m), with those three under an observation table (k_plant_follow_o), and with
+// those four under an actuator table (k_plant_follow_a).
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -22,7 +23,7 @@ using namespace h1;
 
 namespace ilqr {
 
-// This file is compiled four times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
+// This file is compiled five times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
 // libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
 // which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
 // library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
@@ -34,11 +35,13 @@ namespace ilqr {
 #endif
 // A fourth compilation, -DPLANT_OBSERVE_MODULE into libilqr_hip_observe.so, is the observation family alone (k_plant_follow_o, the superset of
 // the payload family whose control law reads a measured state, k_observation_draw and k_observe_apply), opened in the same way.
-#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE)
+// A fifth compilation, -DPLANT_ACTUATOR_MODULE into libilqr_hip_actuator.so, is the actuator family alone (k_plant_follow_a, the superset of
+// the observation family whose step takes a delayed, lagged and noisy torque, and k_actuator_draw), opened in the same way.
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
 #define DYN_STEP_WRENCH
 #define DYN_STEP_PAYLOAD     // ... carrying the payload too
 #endif
-#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE)
+#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
 #define PLANT_MODULE         // a module: none of the library's own kernels and launchers
 #endif
 #include "dyn_step_shared.h"
@@ -323,7 +326,7 @@ __global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const
 
 #endif
 
-#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE)
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
 // ---- payload table (include/ilqr_hip.h ilqr_hip_plant_set_payload): k_plant_follow_m.  A rollout has two disturbance rows of h1s::DIST_REC doubles
 // in LDS behind the parameter rows, staged once per launch, consecutive lanes on consecutive doubles (12 KB at FB = 0, 1.5 KB at FB = 1):
 //   row r        the wrench record (F, T, r, first, end; zeros without a wrench table, wtab null), the payload record, padding
@@ -379,7 +382,7 @@ __global__ void __launch_bounds__(64) k_step_m(int count, const double* x, const
 
 #endif
 
-#ifdef PLANT_OBSERVE_MODULE
+#if defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
 // ---- observation table (include/ilqr_hip.h ilqr_hip_plant_set_observation): what the controller is told of the state.  One record of
 // OBS_REC = 100 doubles per rollout -- bias[50], sigma[50] in the tangent order of the Jacobians (dp, dphi, dq, dv, domega, dqdot) -- or ONE
 // record that every rollout reads (stride 0).  The error of rollout b in plant interval i is e = bias + sigma o z(seed, stream0 + b, i),
@@ -409,8 +412,10 @@ DEVFN void observe_rows(const DevState& S, const double* xs, const double* drow,
     xo[it] = observe_entry(xs + r * n, drow + (size_t)br * n, e);
   }
 }
+#ifdef PLANT_OBSERVE_MODULE
 #define PLANT_TABLE 4
 #include "plant_follow_body.h"
+#endif
 
 // Philox4x32-10 (Salmon et al., SC'11), the counter-based generator: ten rounds of two 32 x 32 -> 64 bit products, the key bumped by the
 // Weyl constants between rounds.  Integer arithmetic only: every implementation gives the same words.
@@ -425,6 +430,8 @@ DEVFN void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, uns
   }
   w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
+#endif
+#ifdef PLANT_OBSERVE_MODULE
 // One lane per (rollout, Philox block): 25 blocks -- counter (stream lo, stream hi, interval lo, block), key (seed lo, seed hi) -- make a
 // rollout's 50 normals by Box-Muller, the fp64 log and sincos being the cost.  OBS_RPB rollouts per workgroup of 256 lanes (250 busy); the
 // tangent errors and then the state-shaped rows are assembled in LDS and leave in one coalesced run of OBS_RPB x 51 consecutive doubles:
@@ -482,6 +489,103 @@ __global__ void __launch_bounds__(256) k_observe_apply(int B, const double* x, c
   if (it >= (long)B * PLANT_NX) return;
   const int b = (int)(it / PLANT_NX), e = (int)(it - (long)b * PLANT_NX);
   out[it] = observe_entry(x + (size_t)b * PLANT_NX, delta + (size_t)b * PLANT_NX, e);
+}
+#endif
+
+#ifdef PLANT_ACTUATOR_MODULE
+// ---- actuator table (include/ilqr_hip.h ilqr_hip_plant_set_actuator): what the joints get of the law's command.  One record of ACT_REC = 39
+// doubles per rollout -- delay (plant substeps, an integer 0..8), tau[19] (s), sigma[19] (N m) -- or ONE record that every rollout reads
+// (stride 0), and beside it the rows beta[19] = -expm1(-h / tau) that the host derived from it.  In substep n (counted from the priming)
+// the command c_n -- the law's row US behind the guard of main:162-165 -- becomes
+//   a_n = c_{n - delay}                                      a delay line of ACT_SLOTS = 9 slots per rollout: slot n % 9 written, (n - delay) % 9 read
+//   y_n = y_{n-1} + beta o (a_n - y_{n-1})                   the product rounded on its own; tau_i == 0: y_i = a_i by selection
+//   t_n = y_n + sigma o z                                    z the interval's normals; the product rounded on its own; sigma_i == 0: t_i = y_i by selection
+// and t_n is the row UA the step loads.  n == 0 primes: every slot and y take c_0.
+//   k_actuator_draw    z[count][B][19] of the intervals interval0 .. interval0 + count - 1: a pure function of its arguments
+//   k_plant_follow_a   plant_follow_body.h a sixth time
+#define ACT_REC 39
+#define ACT_SLOTS 9
+// One entry (rollout row r, joint i) per lane and turn, dealt out as control_law deals its rows; an entry belongs to the same lane in every
+// substep of a launch, so the lane that wrote a slot of the delay line or y is the one that reads it: program order is all the ordering
+// it needs (between launches: the stream).  The rows a wave does not own have no state in memory: they pass the command through.
+template <int FB>
+DEVFN void actuator_stage(const DevState& S, double* lds, int b0, int ua0, const double* atab, int a_stride, const double* abeta, int ab_stride, const double* zrow, double* fifo, double* yst,
+                          double* applied, long nsub, bool last) {
+  typedef PlantLayout<FB> Lay;
+  constexpr int m = PLANT_NU;
+  const int slot_w = (int)(nsub % ACT_SLOTS);
+  for (int it = threadIdx.x; it < Lay::RPW * m; it += 64) {
+    const int r = it / m, i = it - r * m;
+    const double* us = lds + Lay::US + r * m;
+    bool fin = true;
+    for (int q = 0; q < m; ++q) fin = fin && isfinite(us[q]);
+    const double c = fin ? us[i] : 0.0;      // main:162-165: a command with a non-finite entry is zero, all of it
+    double t = c;
+    if (b0 + r < S.B) {
+      const size_t b = (size_t)(b0 + r);
+      const double* rec = atab + b * a_stride;
+      const int delay = (int)rec[0];
+      const double tau = rec[1 + i], sigma = rec[1 + m + i];
+      double* f = fifo + b * (ACT_SLOTS * m) + i;
+      double* yp = yst + b * m + i;
+      double y;
+      if (nsub == 0) {      // (wave-uniform) priming: the joint was already holding this torque
+        for (int s = 0; s < ACT_SLOTS; ++s) f[s * m] = c;
+        y = c;
+      } else {
+        f[slot_w * m] = c;
+        const double a = delay == 0 ? c : f[(int)((nsub - delay + ACT_SLOTS) % ACT_SLOTS) * m];
+        if (tau == 0.0) y = a;
+        else {
+          const double yo = *yp;
+          const double d = abeta[b * ab_stride + i] * (a - yo);
+          y = yo + d;
+        }
+      }
+      *yp = y;
+      const double s = sigma * zrow[b * m + i];
+      t = sigma == 0.0 ? y : y + s;
+      if (last) applied[b * m + i] = t;
+    }
+    lds[ua0 + it] = t;
+  }
+}
+#define PLANT_TABLE 5
+#include "plant_follow_body.h"
+
+// One lane per (rollout, Philox block): the blocks ACT_BLK0 .. ACT_BLK0 + 9 of the rollout's stream -- behind the observation's 0..24, so equal
+// seeds do not correlate the two -- make 20 normals by the observation's Box-Muller, of which the first 19 are the joints'.  ACT_RPB rollouts
+// per workgroup of 256 lanes (250 busy); the rows are assembled in LDS and leave in one coalesced run of ACT_RPB x 19 consecutive doubles.
+// grid (ceil(B / ACT_RPB), count).
+#define ACT_RPB 25
+#define ACT_BLK 10
+#define ACT_BLK0 32
+__global__ void __launch_bounds__(256) k_actuator_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, double* out) {
+  __shared__ double zr[ACT_RPB * 2 * ACT_BLK];
+  const int tid = threadIdx.x;
+  const int b0 = blockIdx.x * ACT_RPB;
+  const int rows = B - b0 < ACT_RPB ? B - b0 : ACT_RPB;
+  const unsigned long long iv = (unsigned long long)(interval0 + (long)blockIdx.y);
+  const int r = tid / ACT_BLK, q = tid - r * ACT_BLK;
+  if (r < rows) {
+    const unsigned long long s = stream0 + (unsigned long long)(b0 + r);
+    unsigned w[4];
+    philox4x32_10((unsigned)s, (unsigned)(s >> 32), (unsigned)iv, (unsigned)(ACT_BLK0 + q), (unsigned)seed, (unsigned)(seed >> 32), w);
+    const double u1 = ((double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) + 0.5) * 0x1p-53;
+    const double u2 = ((double)((((unsigned long long)w[2] << 32) | w[3]) >> 11) + 0.5) * 0x1p-53;
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586 * u2;
+    double sn, cs;
+    sincos(ang, &sn, &cs);
+    zr[r * 2 * ACT_BLK + 2 * q] = rad * cs;
+    zr[r * 2 * ACT_BLK + 2 * q + 1] = rad * sn;
+  }
+  __syncthreads();
+  double* o = out + ((size_t)blockIdx.y * B + b0) * PLANT_NU;
+  for (int it = tid; it < rows * PLANT_NU; it += 256) {
+    const int rr = it / PLANT_NU, i = it - rr * PLANT_NU;
+    o[it] = zr[rr * 2 * ACT_BLK + i];
+  }
 }
 #endif
 
@@ -611,6 +715,40 @@ static void launch_observe_apply(int B, const double* x, const double* delta, do
   const dim3 grid((unsigned)(((long)B * PLANT_NX + 255) / 256));
   hipLaunchKernelGGL(k_observe_apply, grid, dim3(256), 0, st, B, x, delta, out);
 }
+#elif defined(PLANT_ACTUATOR_MODULE)      // attributes and launchers of the actuator family, exported from its module with C linkage (ilqr_kernels.h)
+template <int FB> static constexpr size_t follow_lds_a() {
+  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX + FollowLayout<FB>::RPW * PLANT_NU) * sizeof(double);
+}
+static_assert(follow_lds_a<0>() <= 160 * 1024 && follow_lds_a<1>() <= 160 * 1024, "k_plant_follow_a: the workgroup's LDS");
+template <int KIND, int FB> static int plant_attr_a() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_a<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_a<FB>()) != hipSuccess;
+}
+static int actuator_kernels_set_attr() {
+  int rc = 0;
+  for_each_step_kind([&](auto K) { rc |= plant_attr_a<K(), 0>(); rc |= plant_attr_a<K(), 1>(); });
+  return rc;
+}
+template <int KIND, int FB>
+static void follow_launch_a(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const ActuatorTable& A,
+                            const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_a<KIND, FB>), grid, dim3(64), follow_lds_a<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs, A.records, A.rec_stride, A.blend, A.blend_stride, A.z, A.fifo, A.y, A.applied,
+                     A.substep0);
+}
+static void launch_plant_follow_actuator(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs,
+                                         const ActuatorTable& A, const WrenchFollowArgs& w, hipStream_t st) {
+  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (w.feedback_mode) follow_launch_a<K(), 1>(S, Pl, dyn, T, W, M, dobs, A, a, st);
+    else follow_launch_a<K(), 0>(S, Pl, dyn, T, W, M, dobs, A, a, st);
+  });
+}
+static void launch_actuator_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, int count, double* out, hipStream_t st) {
+  const dim3 grid((unsigned)((B + ACT_RPB - 1) / ACT_RPB), (unsigned)count);
+  hipLaunchKernelGGL(k_actuator_draw, grid, dim3(256), 0, st, B, seed, stream0, interval0, out);
+}
 #else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
 template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
 template <int KIND, int FB> static int plant_attr_w() {
@@ -681,5 +819,18 @@ void ilqr_observe_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* P
 }
 void ilqr_observe_module_draw(int B, const ilqr::ObservationTable* O, long interval0, int count, double* delta, hipStream_t st) { ilqr::launch_observation_draw(B, *O, interval0, count, delta, st); }
 void ilqr_observe_module_apply(int B, const double* x, const double* delta, double* out, hipStream_t st) { ilqr::launch_observe_apply(B, x, delta, out, st); }
+}
+#endif
+
+#ifdef PLANT_ACTUATOR_MODULE
+extern "C" {
+int ilqr_actuator_module_set_attr() { return ilqr::actuator_kernels_set_attr(); }
+void ilqr_actuator_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
+                                 const double* delta, const ilqr::ActuatorTable* A, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
+  ilqr::launch_plant_follow_actuator(*S, *Pl, *dyn, *T, *W, *M, delta, *A, *a, st);
+}
+void ilqr_actuator_module_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, int count, double* z, hipStream_t st) {
+  ilqr::launch_actuator_draw(B, seed, stream0, interval0, count, z, st);
+}
 }
 #endif

@@ -220,6 +220,35 @@ def stack_plant_observation(B, **groups):
     return out
 
 
+def stack_plant_actuator(B, delay=0, tau=0.0, sigma=0.0):
+    """Actuator models [B, 39] for BatchedILQR.plant_set_actuator / MPCRunner(plant_actuator=...): delay, tau[19], sigma[19].  delay (plant
+    substeps, an integer 0..8) is a scalar or [B]; tau (s, the time constant of a first-order lag, 0: none) and sigma (N m, torque noise) are
+    each a scalar, a vector per joint [19], [B] (one scalar per rollout) or [B, 19].  Raises ValueError for a shape that is none of these, a
+    non-finite entry, a negative tau or sigma or a delay that is not an integer in 0..8 -- what ilqr_hip_plant_set_actuator refuses."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    out = np.zeros((B, 39))
+    d = np.asarray(delay, dtype=np.float64)
+    if d.shape not in ((), (1,), (B,)):
+        raise ValueError("delay must be a scalar or [B]")
+    out[:, 0] = d
+    for name, val, first in (("tau", tau, 1), ("sigma", sigma, 20)):
+        v = np.asarray(val, dtype=np.float64)
+        if v.shape == (B,) and B != 19:      # (B == 19: a vector is read per joint; [B, 1] says per rollout)
+            v = v[:, None]
+        if v.shape not in ((), (19,), (1, 19), (B, 1), (B, 19)):
+            raise ValueError("%s must be a scalar, [19], [B] or [B, 19]" % name)
+        out[:, first:first + 19] = v
+    if not np.isfinite(out).all():
+        raise ValueError("plant actuator records must be finite")
+    if (out[:, 1:] < 0).any():
+        raise ValueError("tau >= 0 and sigma >= 0 are required")
+    if (out[:, 0] < 0).any() or (out[:, 0] > 8).any() or (out[:, 0] != np.floor(out[:, 0])).any():
+        raise ValueError("delay must be an integer in 0..8 (plant substeps)")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

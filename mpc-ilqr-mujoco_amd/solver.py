@@ -53,6 +53,8 @@ EXPORTS = [
     "ilqr_hip_plant_set_payload", "ilqr_hip_plant_clear_payload", "ilqr_hip_plant_num_payload_sets", "ilqr_hip_plant_get_payload", "ilqr_hip_step_payload",
     "ilqr_hip_plant_set_observation", "ilqr_hip_plant_clear_observation", "ilqr_hip_plant_num_observation_sets", "ilqr_hip_plant_get_observation",
     "ilqr_hip_plant_observation_errors", "ilqr_hip_plant_get_observed",
+    "ilqr_hip_plant_set_actuator", "ilqr_hip_plant_clear_actuator", "ilqr_hip_plant_num_actuator_sets", "ilqr_hip_plant_get_actuator",
+    "ilqr_hip_plant_get_actuator_blend", "ilqr_hip_plant_actuator_draws", "ilqr_hip_plant_get_applied",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
@@ -68,6 +70,9 @@ PLANT_PAYLOAD = ("mass", "com_x", "com_y", "com_z", "Ixx", "Iyy", "Izz", "Ixy", 
 # bias[50] then sigma[50] in this order
 PLANT_OBSERVATION_GROUPS = (("position", 0, 3), ("orientation", 3, 3), ("joints", 6, 19), ("linear_velocity", 25, 3), ("angular_velocity", 28, 3), ("joint_velocities", 31, 19))
 PLANT_OBSERVATION = 100
+# a plant actuator record (include/ilqr_hip.h ILQR_PLANT_ACTUATOR): delay (plant substeps, an integer 0..PLANT_ACTUATOR_MAX_DELAY), tau[19], sigma[19]
+PLANT_ACTUATOR = 39
+PLANT_ACTUATOR_MAX_DELAY = 8
 
 
 
@@ -797,6 +802,54 @@ class BatchedILQR:
         """[B, 51]: the plant state as the controller is told it now, x [+] delta(plant_intervals) -- what a warm start would hand the solve;
         the plant state itself without a table."""
         return self._get("ilqr_hip_plant_get_observed", (self.B, NX))
+
+    def plant_set_actuator(self, actuator, seed=0, stream0=0):
+        """Install actuator models [n_sets, 39] (delay in plant substeps, tau[19] s, sigma[19] N m; scenario.stack_plant_actuator builds
+        them), n_sets 1 or B: the torque the plant's joints get is the law's command behind a delay line, a first-order lag and noise drawn
+        once per plant interval under `seed`, rollout stream stream0 + b (ilqr_hip_plant_set_actuator).  What the plant reports -- control,
+        ring, score -- stays the command."""
+        actuator = _c64(actuator)
+        if actuator.ndim == 1:
+            actuator = actuator[None]
+        if actuator.ndim != 2 or actuator.shape[1] != PLANT_ACTUATOR or actuator.shape[0] not in (1, self.B):
+            raise ValueError("plant actuator records must be [1, 39] or [B, 39]")
+        seed, stream0 = int(seed), int(stream0)
+        if not (0 <= seed < 1 << 64 and 0 <= stream0 < 1 << 64):
+            raise ValueError("seed and stream0 must fit 64 unsigned bits")
+        self._chk(self.L.ilqr_hip_plant_set_actuator(self.h, _p(actuator), int(actuator.shape[0]), C.c_ulonglong(seed), C.c_ulonglong(stream0)))
+
+    def plant_clear_actuator(self):
+        """Remove the actuator models: the plant calls launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_clear_actuator(self.h))
+
+    def plant_num_actuator_sets(self):
+        return int(self.L.ilqr_hip_plant_num_actuator_sets(self.h))
+
+    def plant_get_actuator(self):
+        """(records [B, 39], seed, stream0): the record of each rollout; zeros and 0, 0 without a table."""
+        out = np.zeros((self.B, PLANT_ACTUATOR))
+        seed, stream0 = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._chk(self.L.ilqr_hip_plant_get_actuator(self.h, _p(out), C.byref(seed), C.byref(stream0)))
+        return out, int(seed.value), int(stream0.value)
+
+    def plant_actuator_blend(self):
+        """beta [B, 19] = -expm1(-h / tau) as the plant kernel reads it, to the bit (1 where tau == 0: never used, the kernel selects)."""
+        return self._get("ilqr_hip_plant_get_actuator_blend", (self.B, NU))
+
+    def plant_actuator_draws(self, interval0, count):
+        """z [count, B, 19]: the standard normals of the torque noise in the plant intervals interval0 .. interval0 + count - 1, a pure
+        function of seed, stream0 and interval (ilqr_hip_plant_actuator_draws); 1 <= count <= N."""
+        interval0, count = int(interval0), int(count)
+        if interval0 < 0 or count < 1 or count > self.N:
+            raise ValueError("plant_actuator_draws: interval0 >= 0 and 1 <= count <= N")
+        out = np.zeros((count, self.B, NU))
+        self._chk(self.L.ilqr_hip_plant_actuator_draws(self.h, C.c_long(interval0), count, _p(out)))
+        return out
+
+    def plant_get_applied(self):
+        """[B, 19]: the torque of the last substep run under the actuator table, in front of the torque gain and the clamp; the reported
+        control without a table."""
+        return self._get("ilqr_hip_plant_get_applied", (self.B, NU))
 
     def plant_score(self):
         """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""
