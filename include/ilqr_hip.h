@@ -575,6 +575,38 @@ int ilqr_hip_plant_get_actuator(ilqr_hip_ctx* ctx, double* act /*[B][39]*/, unsi
 int ilqr_hip_plant_get_actuator_blend(ilqr_hip_ctx* ctx, double* beta /*[B][19]*/);
 int ilqr_hip_plant_actuator_draws(ilqr_hip_ctx* ctx, long interval0, int count, double* z /*[count][B][19]*/);
 int ilqr_hip_plant_get_applied(ilqr_hip_ctx* ctx, double* tau /*[B][19]*/);
+/* ---- joint gain, torque range, damping and armature, one set per rollout: a joint that is not the model's.  The model's joints have
+   armature 0.1, damping 1 and the torque ranges of h1.xml, and the parameter record has ONE torque gain for all 19 motors; rotor inertia
+   behind the gearbox and joint friction are the worst-known numbers of a real robot, and a weak, saturating or dead motor is a fault of
+   ONE joint.  One record of ILQR_PLANT_JOINTS doubles per set, the joints in the order of u:
+     gain[19]     g_i, per-joint torque gain, >= 0
+     scale[19]    s_i, scale on the model's torque range [lo_i, hi_i], >= 0; 0: a dead motor
+     damping[19]  d_i, N m s / rad, >= 0
+     armature[19] a_i, kg m^2, >= 0
+   In every plant substep of length h_s, with G the scalar gain of the parameter record (1 without one):
+     tau_i = clamp(G g_i u_i, s_i lo_i, s_i hi_i) - d_i v_i
+     (M + diag(a) + h_s diag(d)) qacc = tau - bias + J^T lambda + E^T nu      (MuJoCo's Euler step with implicit joint damping)
+   g_i acts in front of the clamp, s_i on the clamp.  Everything else of the step is unchanged in all six step kinds: stance rows, unilateral
+   and Coulomb decisions, the joint-limit rows' lock decision and second pass (a stopped hinge keeps its prescribed acceleration: nothing of
+   the record reaches it), wrench and payload.  The nominal record g = s = d = 1, a = 0.1 is the model: a table whose every record is
+   nominal is no table, bit for bit (the plant calls launch what they launch without it).  The plant keeps REPORTING the commanded torque
+   (ilqr_hip_plant_get_control, the ring, the score, ilqr_hip_plant_get_applied behind the actuator): the record acts inside the step,
+   behind all of them, and the solver does not know of it.
+   plant_set_joints: n_sets = 1 (one record that every rollout reads) or the batch, else ILQR_ERR_ARG; ILQR_ERR_ARG also for a non-finite or
+   negative entry, checked before the handle is touched.  joints NULL with n_sets 0 clears the table: the plant calls then launch exactly
+   what they launch without it.  The table is owned by the handle; the call uploads and synchronises the handle's stream.  It survives
+   ilqr_hip_plant_reset and ilqr_hip_plant_configure.  While it is installed ilqr_hip_plant_advance / _follow launch the joints family of
+   the plant kernel (k_plant_follow_j of the module libilqr_hip_joints.so, opened from the library's directory on first use -- missing:
+   ILQR_ERR_UNSUPPORTED with the path in ilqr_hip_last_error, never a fall-back; an advance is that kernel over one interval), which
+   carries parameter record, wrench, payload, observation and actuator as the actuator family does, each table present or not.
+   plant_get_joints: joints[B][76], the record of each rollout (the nominal record without a table).
+   step_joints: x_next[i] = f(x[i], u[i]) under joints[i], and under wrench[i] (F, T, r) and payload[i] where given, with the handle's
+   dynamics parameters and step size, as ilqr_hip_step_payload. */
+#define ILQR_PLANT_JOINTS 76   /* gain[19], scale[19], damping[19], armature[19] */
+int ilqr_hip_plant_set_joints(ilqr_hip_ctx* ctx, const double* joints /*[n_sets][76]; NULL with n_sets 0: clear*/, int n_sets);
+int ilqr_hip_plant_get_joints(ilqr_hip_ctx* ctx, double* joints /*[B][76]*/);
+int ilqr_hip_step_joints(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench /*[count][9], NULL: none*/,
+                         const double* payload /*[count][10], NULL: none*/, const double* joints /*[count][76]*/, double* x_next);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

@@ -253,6 +253,17 @@ class iLQR {
     Vec z((size_t)count * B_ * ILQR_NU); chk(ilqr_hip_plant_actuator_draws(ctx_, interval0, count, z.data())); return z;
   }
   Vec plantApplied() { Vec t((size_t)B_ * ILQR_NU); chk(ilqr_hip_plant_get_applied(ctx_, t.data())); return t; }      // [batch][19]
+  // joint gain, torque range, damping, armature per rollout (ilqr_hip.h ilqr_hip_plant_set_joints): [n_sets][76] = gain[19], scale[19], damping[19], armature[19]
+  void plantSetJoints(const Vec& joints, int n_sets) {
+    if (n_sets < 1 || joints.size() != (size_t)n_sets * ILQR_PLANT_JOINTS) throw std::runtime_error("joint records must hold n_sets * 76 doubles");
+    chk(ilqr_hip_plant_set_joints(ctx_, joints.data(), n_sets));
+  }
+  void plantClearJoints() { chk(ilqr_hip_plant_set_joints(ctx_, nullptr, 0)); }
+  Vec plantJoints() { Vec j((size_t)B_ * ILQR_PLANT_JOINTS); chk(ilqr_hip_plant_get_joints(ctx_, j.data())); return j; }      // [batch][76]
+  Vec stepJoints(int count, const Vec& x, const Vec& u, int stance_left, int stance_right, const Vec& joints, const double* wrench = nullptr, const double* payload = nullptr) {
+    if (count < 1 || x.size() != (size_t)count * ILQR_NX || u.size() != (size_t)count * ILQR_NU || joints.size() != (size_t)count * ILQR_PLANT_JOINTS) throw std::runtime_error("stepJoints: sizes");
+    Vec xn((size_t)count * ILQR_NX); chk(ilqr_hip_step_joints(ctx_, count, x.data(), u.data(), stance_left, stance_right, wrench, payload, joints.data(), xn.data())); return xn;
+  }
   static std::array<double, 3> pelvisInertialOffset() { std::array<double, 3> r{}; ilqr_hip_pelvis_inertial_offset(r.data()); return r; }
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492

@@ -374,6 +374,146 @@ DEVFN void step_any_w(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynPa
 }
 #endif
 
+// ---- the same steps under a joint record per rollout (DYN_STEP_JOINTS: the joints module of plant_kernels.hip alone defines it, with
+// DYN_STEP_WRENCH and DYN_STEP_PAYLOAD; k_plant_follow_j and k_step_j are the only kernels that reach these copies).  Each is its `_w` copy
+// with the record's torques and per-hinge armature in the place of the model's (h1_aba_split.h stance_prepare_j): every kind runs the PER
+// recursion, and a stopped hinge takes LOCK_ARM by selection (apply_lock_mask_j).  The record -- h1s::JOINT_REC doubles -- lives in LDS behind
+// the disturbance rows and crosses every call boundary as the offset `jro` of its row, as the disturbance row does as `wro`.  The copies
+// above keep their text.
+#ifdef DYN_STEP_JOINTS
+template <bool KIN>
+DEVFN void step_stance_j(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz, double soft, int mode, int st_left, int st_right, double mu, int geom, int wro, int jro) {
+  const int lane = threadIdx.x;
+  const bool side = (lane & 1) != 0;
+  const h1s::LaneLds L{dyn_lds_c, 64, lane};
+  const double grav[3] = {gx, gy, gz};
+  h1s::HalfX h = *hp;
+  const h1s::HalfU u = *up;
+  if (geom) h1s::geom_stance(side, h, st_left, st_right);
+  double qh[4], R0[9]; h1s::HalfTau tau, add;
+  h1s::stance_prepare_j(side, h, u, dt, dyn_lds_c + jro, qh, R0, tau, add);
+  double qb[6]; h1s::HalfAcc qa;
+  h1s::stance_accelerations<KIN, true, DYN_WR>(side, R0, h, tau, dt, grav, L, soft, mode, (side ? st_right : st_left) == 1, (side ? st_left : st_right) == 1, mu, qb, qa, &add, dyn_lds_c + wro);
+  h1s::integrate_half(h, qh, qb, qa, dt);
+  *hp = h;
+}
+__device__ __attribute__((noinline)) void step_stance_shared_j(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
+                                                               double soft, int mode, int st_left, int st_right, double mu, int geom, int wro, int jro) {
+  step_stance_j<false>(hp, up, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, geom, wro, jro);
+}
+__device__ __attribute__((noinline)) void step_stance_shared_kin_j(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
+                                                                   double soft, int st_left, int st_right, double mu, int geom, int wro, int jro) {
+  step_stance_j<true>(hp, up, dt, gx, gy, gz, soft, 4, st_left, st_right, mu, geom, wro, jro);
+}
+template <bool KIN>
+__device__ __attribute__((noinline)) void lim_accelerations_j(const h1s::HalfX* hp, const h1s::HalfU* up, unsigned mask, double dt, double gx, double gy, double gz,
+                                                              double soft, int mode, int st_left, int st_right, double mu, double kr, int wro, int jro, LimAcc* out) {
+  const int lane = threadIdx.x;
+  const bool side = (lane & 1) != 0;
+  const h1s::LaneLds L{dyn_lds_c, 64, lane};
+  const double grav[3] = {gx, gy, gz};
+  const h1s::HalfX h = *hp;
+  const h1s::HalfU u = *up;
+  double qh[4], R0[9]; h1s::HalfTau tau, add;
+  h1s::stance_prepare_j(side, h, u, dt, dyn_lds_c + jro, qh, R0, tau, add);
+  h1s::apply_lock_mask_j(side, mask, h.q, dt, kr, tau, add);
+  const bool st_own = mode != 0 && (side ? st_right : st_left) == 1, st_par = mode != 0 && (side ? st_left : st_right) == 1;
+  LimAcc o;
+  h1s::stance_accelerations<KIN, true, DYN_WR>(side, R0, h, tau, dt, grav, L, soft, mode, st_own, st_par, mu, o.qb, o.qa, &add, dyn_lds_c + wro);
+  *out = o;
+}
+template <bool KIN>
+DEVFN void step_lim_j(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz, double soft, int mode, int st_left, int st_right, double mu, double kr, int geom, int wro, int jro) {
+  const bool side = (threadIdx.x & 1) != 0;
+  if (geom) h1s::geom_stance(side, *hp, st_left, st_right);
+  LimAcc o;
+  lim_accelerations_j<KIN>(hp, up, 0u, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, kr, wro, jro, &o);
+  h1s::HalfX h = *hp;
+  const unsigned mask = h1s::limit_lock_mask(side, h.q, o.qa, dt, kr);
+  const bool any = mask != 0u;
+  if (h1s::xch_flag(any) || any) lim_accelerations_j<KIN>(hp, up, mask, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, kr, wro, jro, &o);
+  const double qn = sqrt(h.quat[0] * h.quat[0] + h.quat[1] * h.quat[1] + h.quat[2] * h.quat[2] + h.quat[3] * h.quat[3]);
+  const double qh[4] = {h.quat[0] / qn, h.quat[1] / qn, h.quat[2] / qn, h.quat[3] / qn};
+  h1s::integrate_half(h, qh, o.qb, o.qa, dt);
+  *hp = h;
+}
+__device__ __attribute__((noinline)) void step_stance_shared_lim_j(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
+                                                                   double soft, int mode, int st_left, int st_right, double mu, double kr, int geom, int wro, int jro) {
+  step_lim_j<false>(hp, up, dt, gx, gy, gz, soft, mode, st_left, st_right, mu, kr, geom, wro, jro);
+}
+__device__ __attribute__((noinline)) void step_stance_shared_kin_lim_j(h1s::HalfX* hp, const h1s::HalfU* up, double dt, double gx, double gy, double gz,
+                                                                       double soft, int st_left, int st_right, double mu, double kr, int geom, int wro, int jro) {
+  step_lim_j<true>(hp, up, dt, gx, gy, gz, soft, 4, st_left, st_right, mu, kr, geom, wro, jro);
+}
+// lim_second_pass_lds_w under the joint record (L[0..43] as there)
+__device__ __attribute__((noinline)) void lim_second_pass_lds_j(double dt, double gx, double gy, double gz, double kr, int wro, int jro) {
+  const int lane = threadIdx.x;
+  const bool side = (lane & 1) != 0;
+  const h1s::LaneLds L{dyn_lds_c, 64, lane};
+  const double grav[3] = {gx, gy, gz};
+  h1s::HalfX h; h1s::HalfU u;
+  lds_get_state(L, h);
+  u.u11 = L[33];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) u.uL[k] = L[34 + k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) u.uA[k] = L[39 + k];
+  const unsigned mask = (unsigned)__double_as_longlong(L[43]);
+  double qh[4], R0[9]; h1s::HalfTau tau, add;
+  h1s::stance_prepare_j(side, h, u, dt, dyn_lds_c + jro, qh, R0, tau, add);
+  h1s::apply_lock_mask_j(side, mask, h.q, dt, kr, tau, add);
+  double qb[6]; h1s::HalfAcc qa;
+  h1s::forward_dynamics<true, DYN_WR>(side, R0, h.vb, h.q, tau, h1s::ARMATURE + dt * h1s::DAMPING, grav, L, qb, qa, nullptr, nullptr, &add, dyn_lds_c + wro);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) L[k] = qb[k];
+  L[6] = qa.q11;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) L[7 + k] = qa.qL[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) L[12 + k] = qa.qA[k];
+}
+// step_any_w under the joint record at LDS offset jro (the comments of step_any hold for every branch)
+template <int CONTACT>
+DEVFN void step_any_j(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L, int geom, int wro, int jro) {
+  if constexpr (CONTACT == 5 || CONTACT == 0) {
+    double dt = dyn.h; asm volatile("" : "+s"(dt));
+    h1s::HalfU uo = u;
+    pin_half(h); pin_half_u(uo);
+    double qh[4], R0[9]; h1s::HalfTau tau, add;
+    h1s::stance_prepare_j(side, h, uo, dt, L.base + jro, qh, R0, tau, add);
+    double qb[6]; h1s::HalfAcc qa;
+    h1s::forward_dynamics<true, DYN_WR>(side, R0, h.vb, h.q, tau, h1s::ARMATURE + dt * h1s::DAMPING, dyn.g, L, qb, qa, nullptr, nullptr, &add, L.base + wro);
+    if constexpr (CONTACT == 5) {
+      const unsigned mask = h1s::limit_lock_mask(side, h.q, qa, dt, dyn.lim_k);
+      const bool any = mask != 0u;
+      if (h1s::xch_flag(any) || any) {
+        lds_put_state(L, h);
+        L[33] = uo.u11;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) L[34 + k] = uo.uL[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) L[39 + k] = uo.uA[k];
+        L[43] = __longlong_as_double((long long)mask);
+        lim_second_pass_lds_j(dt, dyn.g[0], dyn.g[1], dyn.g[2], dyn.lim_k, wro, jro);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) qb[k] = L[k];
+        qa.q11 = L[6];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) qa.qL[k] = L[7 + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) qa.qA[k] = L[12 + k];
+      }
+    }
+    h1s::integrate_half(h, qh, qb, qa, dt);
+    pin_half(h);
+  }
+  else if constexpr (CONTACT == 4) step_stance_shared_kin_lim_j(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, st[0], st[1], dyn.mu, dyn.lim_k, geom, wro, jro);
+  else if constexpr (CONTACT == 3) step_stance_shared_lim_j(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, dyn.contact, st[0], st[1], dyn.mu, dyn.lim_k, geom, wro, jro);
+  else if constexpr (CONTACT == 2) step_stance_shared_kin_j(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, st[0], st[1], dyn.mu, geom, wro, jro);
+  else step_stance_shared_j(&h, &u, dyn.h, dyn.g[0], dyn.g[1], dyn.g[2], dyn.soft, dyn.contact, st[0], st[1], dyn.mu, geom, wro, jro);
+}
+#endif
+
 #define DYN_LDS_BYTES_S (h1s::LDS_SLOTS * 64 * sizeof(double))
 DEVFN void load_half_u(bool side, const double* u, h1s::HalfU& o) {
   o.u11 = u[10];

@@ -1236,6 +1236,49 @@ DEVFN void step_stance(bool side, HalfX& h, const HalfU& u, double dt, const dou
   integrate_half(h, qh, qb, qa, dt);
 }
 
+// ---- a joint record in the place of the model's joint constants (ilqr_hip_plant_set_joints): jr[JOINT_REC] = gain g[19], range scale s[19],
+// damping d[19], armature a[19] in the order of u, padding.  Hinge i gets tau_i = clamp(g_i u_i, s_i lo_i, s_i hi_i) - d_i v_i and the effective
+// armature a_i + h d_i: the recursion runs with PER and the add (a_i - ARMATURE) + h (d_i - DAMPING) on top of the common ARMATURE + h DAMPING,
+// which is 0.0 for the nominal record g = s = d = 1, a = ARMATURE (and d_i v_i, fused or not, rounds to v_i there: the nominal record is the
+// model's step bit for bit).  The record is read where it is used, hinge by hinge; only the ten adds of the lane stay live across the recursion,
+// as the joint-limit rows' adds do.
+constexpr int JOINT_GAIN = 0, JOINT_SCALE = 19, JOINT_DAMP = 38, JOINT_ARM = 57, JOINT_VALS = 76, JOINT_REC = 80;
+DEVFN void joint_torque(const double* jr, int i, double rlo, double rhi, double u, double qd, double dt, double& tq, double& ad) {
+  const double s = jr[JOINT_SCALE + i], d = jr[JOINT_DAMP + i];
+  const double lo = s * rlo, hi = s * rhi, gu = jr[JOINT_GAIN + i] * u;
+  const double uc = gu < lo ? lo : (gu > hi ? hi : gu);
+  tq = uc - d * qd;
+  ad = (jr[JOINT_ARM + i] - ARMATURE) + dt * (d - DAMPING);
+}
+// stance_prepare under a joint record: the torques, and the per-hinge armature on top of ARMATURE + dt * DAMPING
+DEVFN void stance_prepare_j(bool side, const HalfX& h, const HalfU& u, double dt, const double* jr, double* qh, double* R0, HalfTau& tau, HalfTau& add) {
+  const double qn = sqrt(h.quat[0] * h.quat[0] + h.quat[1] * h.quat[1] + h.quat[2] * h.quat[2] + h.quat[3] * h.quat[3]);
+  qh[0] = h.quat[0] / qn; qh[1] = h.quat[1] / qn; qh[2] = h.quat[2] / qn; qh[3] = h.quat[3] / qn;
+  quat_R(qh[0], qh[1], qh[2], qh[3], R0);
+  joint_torque(jr, 10, C_CTRLRANGE[10][0], C_CTRLRANGE[10][1], u.u11, h.q.qd11, dt, tau.t11, add.t11);
+#pragma unroll
+  for (int k = 0; k < 5; ++k)
+    joint_torque(jr, jleg(side, k), side ? C_CTRLRANGE[5 + k][0] : C_CTRLRANGE[k][0], side ? C_CTRLRANGE[5 + k][1] : C_CTRLRANGE[k][1], u.uL[k], h.q.qdL[k], dt, tau.tL[k], add.tL[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    joint_torque(jr, jarm(side, k), side ? C_CTRLRANGE[15 + k][0] : C_CTRLRANGE[11 + k][0], side ? C_CTRLRANGE[15 + k][1] : C_CTRLRANGE[11 + k][1], u.uA[k], h.q.qdA[k], dt, tau.tA[k], add.tA[k]);
+}
+// apply_lock_mask beside a joint record: a stopped hinge takes LOCK_ARM and its prescribed torque by selection (nothing of the record reaches
+// it), every other hinge keeps the record's add
+DEVFN void apply_lock_mask_j(bool side, unsigned mask, const HalfState& q, double dt, double kr, HalfTau& tau, HalfTau& add) {
+  auto ap = [&](int bit, double lo, double hi, double th, double qd, double& tq, double& ad) {
+    const bool lk = ((mask >> bit) & 1u) != 0u;
+    const double r = th > hi ? th - hi : th - lo;
+    ad = lk ? LOCK_ARM : ad;
+    tq = lk ? (-qd / dt - kr * r) * LOCK_ARM : tq;
+  };
+  ap(0, C_JRANGE[10][0], C_JRANGE[10][1], q.th11, q.qd11, tau.t11, add.t11);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) ap(1 + k, side ? C_JRANGE[5 + k][0] : C_JRANGE[k][0], side ? C_JRANGE[5 + k][1] : C_JRANGE[k][1], q.thL[k], q.qdL[k], tau.tL[k], add.tL[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ap(6 + k, side ? C_JRANGE[15 + k][0] : C_JRANGE[11 + k][0], side ? C_JRANGE[15 + k][1] : C_JRANGE[11 + k][1], q.thA[k], q.qdA[k], tau.tA[k], add.tA[k]);
+}
+
 // ---- whole-body CoM with MuJoCo masses (RobotUtils::computeCoM, reference src/common/robot_utils.cpp:810-833):
 // each lane sums the bodies of its side, pelvis and torso are counted by the even lane, then the pair adds up
 template <int IL, int IR, int LEN, int K> DEVFN void com_chain(bool side, const double* Rp, const double* pp, const double* th, double* acc) {

@@ -196,6 +196,14 @@ struct ilqr_hip_ctx {
   double* d_act_applied = nullptr;
   long act_substeps = 0;
   bool actuator_attr_set = false;  // the actuator module's kernels have their LDS attributes on this handle's device
+  // joint table (ilqr_hip_plant_set_joints; plant_kernels.hip k_plant_follow_j): [n][80] doubles, n = 1 or B; null: none.  While it is installed
+  // and not all nominal (joints_nominal: such a table is no table, decided here on the host) the plant calls launch the joints family.
+  double* d_pjoints = nullptr;
+  int joints_sets = 0;
+  bool joints_nominal = false;
+  double* d_stepj = nullptr;  // [step_j_cap][76] records of ilqr_hip_step_joints (wrenches and payloads go through d_stepw, d_stepm)
+  size_t step_j_cap = 0;
+  bool joints_attr_set = false;    // the joints module's kernels have their LDS attributes on this handle's device
   long plant_intervals = 0;   // plant intervals run since the last ilqr_hip_plant_reset (the history cursor only counts while a ring exists)
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
@@ -454,6 +462,49 @@ static int need_actuator_module(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 
+// The joints family (csrc/Makefile ../lib/libilqr_hip_joints.so) is a module of its own in the same way, opened on the first
+// ilqr_hip_plant_set_joints / ilqr_hip_step_joints.
+namespace {
+struct JointsModule {
+  void* lib = nullptr;
+  ilqr::joints_set_attr_fn set_attr = nullptr;
+  ilqr::joints_follow_fn follow = nullptr;
+  ilqr::joints_step_fn step = nullptr;
+  std::string why;
+  bool ok() const { return lib && set_attr && follow && step; }
+};
+JointsModule& joints_module() {
+  static JointsModule m;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    Dl_info info;
+    std::string dir = ".";
+    if (dladdr((const void*)&ilqr_hip_plant_get_joints, &info) && info.dli_fname) {
+      const std::string self = info.dli_fname;
+      const size_t slash = self.rfind('/');
+      if (slash != std::string::npos) dir = self.substr(0, slash);
+    }
+    const std::string path = dir + "/libilqr_hip_joints.so";
+    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!m.lib) { m.why = "the joints kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.set_attr = (ilqr::joints_set_attr_fn)dlsym(m.lib, "ilqr_joints_module_set_attr");
+    m.follow = (ilqr::joints_follow_fn)dlsym(m.lib, "ilqr_joints_module_follow");
+    m.step = (ilqr::joints_step_fn)dlsym(m.lib, "ilqr_joints_module_step");
+    if (!m.ok()) m.why = "the joints kernels' module lacks an entry point: " + path;
+  });
+  return m;
+}
+}  // namespace
+static int need_joints_module(ilqr_hip_ctx* c) {
+  JointsModule& m = joints_module();
+  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
+  if (!c->joints_attr_set) {
+    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the joints kernels"; return ILQR_ERR_HIP; }
+    c->joints_attr_set = true;
+  }
+  return ILQR_OK;
+}
+
 extern "C" {
 
 int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt) {
@@ -541,7 +592,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm, c->d_pobs, c->d_obs_delta, c->d_obs_x, c->d_pact, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm, c->d_pobs, c->d_obs_delta, c->d_obs_x, c->d_pact, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->d_pjoints, c->d_stepj}; for (void* p : pl) if (p) hipFree(p); }
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1611,6 +1662,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
 // joint-limit option where ilqr_hip_plant_set_model has given it one.  (With a parameter table the kernels replace g, mu, soft and lim_k per rollout.)
 constexpr int WRENCH_REC = 16;      // doubles of a wrench record on the device (128 B): the ILQR_PLANT_WRENCH values and padding
 constexpr int PAYLOAD_REC = 16;     // doubles of a payload record on the device (128 B): the ILQR_PLANT_PAYLOAD values and padding
+constexpr int JOINT_REC = 80;       // doubles of a joint record on the device (640 B): the ILQR_PLANT_JOINTS values and padding
 static h1::DynParams plant_dyn(const ilqr_hip_ctx* c) {
   h1::DynParams dyn = c->P.dyn;
   dyn.h = c->P.dyn.h / c->plant_substeps;
@@ -1627,7 +1679,7 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
 // The wrench family (k_plant_follow_w) always reads a parameter record: the parameter table's, or this ONE record of the handle's own values
 // with gain 1, uploaded again whenever the handle's values have changed.
 static int plant_self_params(ilqr_hip_ctx* c) {
-  if ((!c->d_wrench && !c->d_ppayload && !c->d_pobs && !c->d_pact) || c->d_pparams) return ILQR_OK;
+  if ((!c->d_wrench && !c->d_ppayload && !c->d_pobs && !c->d_pact && !c->d_pjoints) || c->d_pparams) return ILQR_OK;
   const h1::DynParams& d = c->P.dyn;
   const double rec[ILQR_PLANT_PARAMS + 1] = {d.g[0], d.g[1], d.g[2], d.mu, d.soft, d.lim_k, 1.0, 0.0};
   if (c->d_self_params && std::memcmp(rec, c->self_params, sizeof(rec)) == 0) return ILQR_OK;
@@ -1674,7 +1726,22 @@ static int upload_actuator_blend(ilqr_hip_ctx* c) {
 }
 static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  if (c->d_pact) {      // the actuator family: the observation family's superset (each of its tables may be null) behind the draw(s) of the call's intervals
+  if (c->d_pjoints && !c->joints_nominal) {      // the joints family: the actuator family's superset (each of its tables may be null)
+    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
+    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+    if (c->d_pobs) {      // (the callers have checked every module this branch calls: plant_need_modules)
+      const ilqr::ObservationTable O = observation_table(c);
+      observe_module().draw(c->B, &O, c->plant_intervals, count, c->d_obs_delta, c->stream);
+    }
+    if (c->d_pact) actuator_module().draw(c->B, c->act_seed, c->act_stream0, c->plant_intervals, count, c->d_act_z, c->stream);
+    const bool one = c->act_sets == 1;
+    const ilqr::ActuatorTable A{c->d_pact, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
+    const ilqr::JointTable J{c->d_pjoints, c->joints_sets == 1 ? 0 : JOINT_REC};
+    joints_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, c->d_pobs ? c->d_obs_delta : nullptr, &A, &J, &a, c->stream);
+    if (c->d_pact) c->act_substeps += (long)count * c->plant_substeps;
+  } else if (c->d_pact) {      // the actuator family: the observation family's superset (each of its tables may be null) behind the draw(s) of the call's intervals
     const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
     const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
     const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
@@ -1762,9 +1829,10 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
   TRY(plant_self_params(c));
+  if (c->d_pjoints && !c->joints_nominal) TRY(need_joints_module(c));
   if (c->d_pact) TRY(need_actuator_module(c));
   if (c->d_pobs) TRY(need_observe_module(c));
-  else if (c->d_ppayload && !c->d_pact) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  else if (c->d_ppayload && !c->d_pact && !(c->d_pjoints && !c->joints_nominal)) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
@@ -1802,9 +1870,10 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
     return ILQR_ERR_STATE;
   }
   TRY(plant_self_params(c));
+  if (c->d_pjoints && !c->joints_nominal) TRY(need_joints_module(c));
   if (c->d_pact) TRY(need_actuator_module(c));
   if (c->d_pobs) TRY(need_observe_module(c));
-  else if (c->d_ppayload && !c->d_pact) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  else if (c->d_ppayload && !c->d_pact && !(c->d_pjoints && !c->joints_nominal)) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
@@ -2261,6 +2330,102 @@ int ilqr_hip_plant_get_applied(ilqr_hip_ctx* c, double* tau) {
   if (!c->d_pact) return ilqr_hip_plant_get_control(c, tau);
   enter(c);
   HIPCHK(c, hipMemcpyAsync(tau, c->d_act_applied, (size_t)c->B * ILQR_NU * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+// ---- joint gain, torque range, damping and armature per rollout (plant_kernels.hip k_plant_follow_j, k_step_j)
+static bool joint_values_ok(const double* j, size_t n) {
+  for (size_t i = 0; i < n; ++i) if (!std::isfinite(j[i]) || j[i] < 0.0) return false;
+  return true;
+}
+int ilqr_hip_plant_set_joints(ilqr_hip_ctx* c, const double* joints, int n_sets) {
+  if (!c) return ILQR_ERR_ARG;
+  constexpr int P = ILQR_PLANT_JOINTS;
+  if (!joints || n_sets == 0) {      // clears
+    if (joints || n_sets != 0) return ILQR_ERR_ARG;
+    enter(c);
+    if (c->d_pjoints) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+      hipFree(c->d_pjoints);
+    }
+    c->d_pjoints = nullptr; c->joints_sets = 0; c->joints_nominal = false;
+    return ILQR_OK;
+  }
+  if (n_sets < 1 || !joint_values_ok(joints, (size_t)n_sets * P) || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(need_joints_module(c));
+  std::vector<double> rec((size_t)n_sets * JOINT_REC, 0.0);      // (640-byte records: the 76 values and four doubles of padding)
+  bool nominal = true;
+  for (int s = 0; s < n_sets; ++s) {
+    const double* r = joints + (size_t)s * P;
+    std::memcpy(rec.data() + (size_t)s * JOINT_REC, r, P * sizeof(double));
+    for (int i = 0; i < ILQR_NU; ++i) nominal = nominal && r[i] == 1.0 && r[ILQR_NU + i] == 1.0 && r[2 * ILQR_NU + i] == 1.0 && r[3 * ILQR_NU + i] == 0.1;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (c->d_pjoints && c->joints_sets != n_sets) { hipFree(c->d_pjoints); c->d_pjoints = nullptr; c->joints_sets = 0; }
+  if (!c->d_pjoints) HIPCHK(c, hipMalloc((void**)&c->d_pjoints, rec.size() * sizeof(double)));
+  c->joints_sets = n_sets; c->joints_nominal = nominal;
+  HIPCHK(c, hipMemcpyAsync(c->d_pjoints, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_plant_get_joints(ilqr_hip_ctx* c, double* joints) {
+  if (!c || !joints) return ILQR_ERR_ARG;
+  enter(c);
+  constexpr int P = ILQR_PLANT_JOINTS;
+  if (!c->d_pjoints) {      // (no table: the model's joints)
+    for (size_t i = 0; i < (size_t)c->B * P; ++i) joints[i] = i % P < 3 * ILQR_NU ? 1.0 : 0.1;
+    return ILQR_OK;
+  }
+  std::vector<double> rec((size_t)c->joints_sets * JOINT_REC);
+  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pjoints, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(joints + (size_t)b * P, rec.data() + (size_t)(c->joints_sets == 1 ? 0 : b) * JOINT_REC, P * sizeof(double));
+  return ILQR_OK;
+}
+// grows a scratch buffer of the single-step calls to `count` rows of `width` doubles
+static int grow_step_buffer(ilqr_hip_ctx* c, double** p, size_t* cap, size_t count, size_t width) {
+  if (count <= *cap) return ILQR_OK;
+  if (*p) hipFree(*p);
+  *p = nullptr; *cap = 0;
+  HIPCHK(c, hipMalloc((void**)p, count * width * sizeof(double)));
+  *cap = count;
+  return ILQR_OK;
+}
+int ilqr_hip_step_joints(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, const double* payload, const double* joints,
+                         double* x_next) {
+  if (count <= 0 || !x || !u || !joints || !x_next) return ILQR_ERR_ARG;
+  for (int i = 0; i < count; ++i) {
+    if (wrench && !wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
+    if (payload && !payload_values_ok(payload + (size_t)i * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
+  }
+  if (!joint_values_ok(joints, (size_t)count * ILQR_PLANT_JOINTS) || !c) return ILQR_ERR_ARG;
+  TRY(enter_launching(c));
+  TRY(need_joints_module(c));
+  const size_t n = (size_t)count;
+  if (wrench) TRY(grow_step_buffer(c, &c->d_stepw, &c->step_w_cap, n, 9));
+  if (payload) TRY(grow_step_buffer(c, &c->d_stepm, &c->step_m_cap, n, ILQR_PLANT_PAYLOAD));
+  TRY(grow_step_buffer(c, &c->d_stepj, &c->step_j_cap, n, ILQR_PLANT_JOINTS));
+  if (n > c->step_cap) {      // (the scratch of plant_step, grown the same way)
+    if (c->d_stepx) hipFree(c->d_stepx);
+    if (c->d_stepu) hipFree(c->d_stepu);
+    if (c->d_stepn) hipFree(c->d_stepn);
+    if (c->d_stance_out) hipFree(c->d_stance_out);
+    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->d_stepx, n * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stepu, n * ILQR_NU * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stepn, n * ILQR_NX * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, n * 2 * sizeof(int)));
+    c->step_cap = n;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, n * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, n * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (wrench) HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, n * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (payload) HIPCHK(c, hipMemcpyAsync(c->d_stepm, payload, n * ILQR_PLANT_PAYLOAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepj, joints, n * ILQR_PLANT_JOINTS * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  joints_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, wrench ? c->d_stepw : nullptr, payload ? c->d_stepm : nullptr, c->d_stepj, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, n * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }

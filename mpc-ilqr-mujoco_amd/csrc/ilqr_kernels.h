@@ -266,6 +266,21 @@ typedef int (*actuator_set_attr_fn)();
 typedef void (*actuator_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
                                    const WrenchFollowArgs*, hipStream_t);
 typedef void (*actuator_draw_fn)(int, unsigned long long, unsigned long long, long, int, double*, hipStream_t);
+// the same with the joints of each rollout read from a record (ilqr_hip_plant_set_joints): rollout b reads record b * rec_stride of J.records
+// -- gain[19], range scale[19], damping[19], armature[19], four doubles of padding; 80 doubles -- (rec_stride 80, or 0: one record for all).
+// T as in the wrench family; W.records, M.records, the observation rows delta and A.records may each be null.
+struct JointTable {
+  const double* records;
+  int rec_stride;
+};
+// The family lives in a module of its own as well, libilqr_hip_joints.so (plant_kernels.hip compiled with -DPLANT_JOINTS_MODULE):
+//   int  ilqr_joints_module_set_attr()
+//   void ilqr_joints_module_follow(S, Pl, dyn, T, W, M, delta or null, A, J, args, stream)
+//   void ilqr_joints_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9] or null, payload[count][10] or null, joints[count][76], stream)
+typedef int (*joints_set_attr_fn)();
+typedef void (*joints_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
+                                 const JointTable*, const WrenchFollowArgs*, hipStream_t);
+typedef void (*joints_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, const double*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

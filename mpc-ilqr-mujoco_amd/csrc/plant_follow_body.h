@@ -19,10 +19,20 @@
 //                  turns the command rows US into the applied rows UA (delay line and lag state in memory, actuator_stage), and the step
 //                  loads UA.  What the interval reports stays the command: it is loaded again from US at the interval's end, so no second
 //                  control vector is live across the step.
+//   PLANT_TABLE 6  k_plant_follow_j: as 5 with atab null as well (then the step loads the command rows US behind the guard, as family 4), and
+//                  each rollout steps with the joints of its record of a joint table (ilqr_hip_plant_set_joints): two more kernel arguments
+//                  and RPW more rows of LDS, JR -- ONE record of h1s::JOINT_REC doubles per rollout, staged once per launch -- whose offset
+//                  the step gets beside the disturbance row's (step_any_j).  Without a wrench and a payload table the disturbance rows
+//                  hold zeros: the step is the one of family 3 under no wrench and no payload.
 #ifndef PLANT_TABLE
-#error "define PLANT_TABLE (0, 1, 2, 3, 4 or 5) before including plant_follow_body.h"
+#error "define PLANT_TABLE (0, 1, 2, 3, 4, 5 or 6) before including plant_follow_body.h"
 #endif
-#if PLANT_TABLE == 5
+#if PLANT_TABLE == 6
+#define K_PLANT_FOLLOW k_plant_follow_j
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs, \
+                           const double* atab, int a_stride, const double* abeta, int ab_stride, const double* az, double* afifo, double* ay, double* aapplied, long substep0, \
+                           const double* jtab, int j_stride
+#elif PLANT_TABLE == 5
 #define K_PLANT_FOLLOW k_plant_follow_a
 #define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs, \
                            const double* atab, int a_stride, const double* abeta, int ab_stride, const double* az, double* afifo, double* ay, double* aapplied, long substep0
@@ -63,7 +73,14 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #if PLANT_TABLE
   stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
 #endif
-#if PLANT_TABLE == 5
+#if PLANT_TABLE == 6
+  constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // the rows of family 5, then the joint records
+  constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
+  constexpr int UA0 = XO0 + RPW * n;
+  constexpr int JR0 = UA0 + RPW * m;
+  stage_disturbance_records<RPW, true>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
+  stage_joint_records<RPW>(S, lds + JR0, b0, jtab, j_stride);
+#elif PLANT_TABLE == 5
   constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // the rows of family 4, then the applied rows
   constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
   constexpr int UA0 = XO0 + RPW * n;
@@ -114,7 +131,7 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
       const int prt = lane >> 1;
       if (FB != 0 || k == 0) {
         wave_lds_fence();
-#if PLANT_TABLE == 5
+#if PLANT_TABLE >= 5
         if (dobs) {      // (wave-uniform: a kernel argument) as family 4; without observation rows the law on XS itself, as families 0 to 3
           observe_rows<RPW>(S, lds + Lay::XS, dobs + (size_t)j * S.B * n, b0, lds + XO0);
           wave_lds_fence();
@@ -132,7 +149,14 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #endif
         wave_lds_fence();
       }
-#if PLANT_TABLE == 5
+#if PLANT_TABLE == 6
+      if (atab) {      // (wave-uniform: a kernel argument) the actuator as in family 5
+        wave_lds_fence();
+        actuator_stage<FB>(S, lds, b0, UA0, atab, a_stride, abeta, ab_stride, az + (size_t)j * S.B * m, afifo, ay, aapplied, substep0 + (long)j * substeps + k,
+                           j == count - 1 && k == substeps - 1);
+        wave_lds_fence();
+      }
+#elif PLANT_TABLE == 5
       // the actuator, in every substep (FB = 0: the command rows are the interval's, the delay line and the lag still move): US -> UA.  Its
       // lanes are dealt out over the RPW x 19 entries as the law's; the guard of main:162-165 acts in it, in front of the delay line
       wave_lds_fence();      // (the previous substep's readers of UA are done)
@@ -142,7 +166,14 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #endif
       if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
       const int pc = prt < RPW ? prt : 0;
-#if PLANT_TABLE == 5
+#if PLANT_TABLE == 6
+      load_half_u(side_t, lds + (atab ? UA0 : Lay::US) + pc * m, u);      // the applied torque, or without an actuator the command, behind the guard
+      if (!atab) {
+        bool ufin = finite_half_u(u);
+        ufin = h1s::xch_flag(ufin) && ufin;
+        if (!ufin) zero_half_u(u);      // main:162-165
+      }
+#elif PLANT_TABLE == 5
       load_half_u(side_t, lds + UA0 + pc * m, u);      // the APPLIED torque (guarded in the stage); the command is loaded again at the interval's end
 #else
       load_half_u(side_t, lds + Lay::US + pc * m, u);
@@ -157,7 +188,13 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
         if constexpr (KIND >= 1 && KIND <= 4) {
           if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
         }
-#if PLANT_TABLE >= 4
+#if PLANT_TABLE == 6
+        // the disturbance row as in family 3 (zeros without the tables), the joint record of the rollout beside it
+        const double* wrow = lds + WR0 + pc * h1s::DIST_REC;
+        const double iv = (double)(interval0 + j);
+        const int wro = (wrow[h1s::DIST_FIRST] <= iv && iv < wrow[h1s::DIST_END]) ? WR0 + pc * h1s::DIST_REC : WR0 + (RPW + pc) * h1s::DIST_REC;
+        plant_step_table_j<KIND>(side_t, h, u, dyn, st, L, geom, lds + Lay::DOUBLES + pc * PLANT_REC, wro, JR0 + pc * h1s::JOINT_REC);
+#elif PLANT_TABLE >= 4
         // without a wrench and a payload table the step of k_plant_follow_p (under the handle's own record: the plant without a table, bit
         // for bit); with either the step of k_plant_follow_m
         if (disturbed) {
@@ -193,7 +230,7 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
     fin = finite_half(h);
     fin = h1s::xch_flag(fin) && fin;
     run = run && fin;
-#if PLANT_TABLE == 5
+#if PLANT_TABLE >= 5
     {      // what the interval reports is the COMMAND of its last substep, behind the guard: the rows US still hold it
       load_half_u(side, lds + Lay::US + (pr < RPW ? pr : 0) * m, u);
       bool ufin = finite_half_u(u);

@@ -8,9 +8,9 @@
 //                    between the intervals, only the rows of the history ring are written on the way
 // Two lanes per rollout as in dyn_split_kernels.hip (the step itself is that file's step_any, dyn_step_shared.h), one wave per workgroup.
 // A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
-// six times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w),
+// seven times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w),
 // with parameter, wrench and payload tables (k_plant_follow_m), with those three under an observation table (k_plant_follow_o), and with
-// those four under an actuator table (k_plant_follow_a).
+// those four under an actuator table (k_plant_follow_a), and with those five under a joint table (k_plant_follow_j).
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -23,7 +23,7 @@ using namespace h1;
 
 namespace ilqr {
 
-// This file is compiled five times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
+// This file is compiled seven times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
 // libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
 // which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
 // library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
@@ -37,11 +37,16 @@ namespace ilqr {
 // the payload family whose control law reads a measured state, k_observation_draw and k_observe_apply), opened in the same way.
 // A fifth compilation, -DPLANT_ACTUATOR_MODULE into libilqr_hip_actuator.so, is the actuator family alone (k_plant_follow_a, the superset of
 // the observation family whose step takes a delayed, lagged and noisy torque, and k_actuator_draw), opened in the same way.
-#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
+// A sixth compilation, -DPLANT_JOINTS_MODULE into libilqr_hip_joints.so, is the joints family alone (k_plant_follow_j, the superset of the
+// actuator family whose step reads gain, torque range, damping and armature of every joint from a record, and k_step_j), opened in the same way.
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
 #define DYN_STEP_WRENCH
 #define DYN_STEP_PAYLOAD     // ... carrying the payload too
 #endif
-#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
+#ifdef PLANT_JOINTS_MODULE
+#define DYN_STEP_JOINTS      // ... and the copies that read a joint record as well
+#endif
+#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
 #define PLANT_MODULE         // a module: none of the library's own kernels and launchers
 #endif
 #include "dyn_step_shared.h"
@@ -326,7 +331,7 @@ __global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const
 
 #endif
 
-#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
 // ---- payload table (include/ilqr_hip.h ilqr_hip_plant_set_payload): k_plant_follow_m.  A rollout has two disturbance rows of h1s::DIST_REC doubles
 // in LDS behind the parameter rows, staged once per launch, consecutive lanes on consecutive doubles (12 KB at FB = 0, 1.5 KB at FB = 1):
 //   row r        the wrench record (F, T, r, first, end; zeros without a wrench table, wtab null), the payload record, padding
@@ -382,7 +387,7 @@ __global__ void __launch_bounds__(64) k_step_m(int count, const double* x, const
 
 #endif
 
-#if defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE)
+#if defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
 // ---- observation table (include/ilqr_hip.h ilqr_hip_plant_set_observation): what the controller is told of the state.  One record of
 // OBS_REC = 100 doubles per rollout -- bias[50], sigma[50] in the tangent order of the Jacobians (dp, dphi, dq, dv, domega, dqdot) -- or ONE
 // record that every rollout reads (stride 0).  The error of rollout b in plant interval i is e = bias + sigma o z(seed, stream0 + b, i),
@@ -492,7 +497,7 @@ __global__ void __launch_bounds__(256) k_observe_apply(int B, const double* x, c
 }
 #endif
 
-#ifdef PLANT_ACTUATOR_MODULE
+#if defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
 // ---- actuator table (include/ilqr_hip.h ilqr_hip_plant_set_actuator): what the joints get of the law's command.  One record of ACT_REC = 39
 // doubles per rollout -- delay (plant substeps, an integer 0..8), tau[19] (s), sigma[19] (N m) -- or ONE record that every rollout reads
 // (stride 0), and beside it the rows beta[19] = -expm1(-h / tau) that the host derived from it.  In substep n (counted from the priming)
@@ -550,6 +555,73 @@ DEVFN void actuator_stage(const DevState& S, double* lds, int b0, int ua0, const
     lds[ua0 + it] = t;
   }
 }
+#endif
+#ifdef PLANT_JOINTS_MODULE
+// ---- joint table (include/ilqr_hip.h ilqr_hip_plant_set_joints): k_plant_follow_j.  One record of h1s::JOINT_REC = 80 doubles (640 B) per rollout --
+// gain[19], range scale[19], damping[19], armature[19] in the order of u, four doubles of padding -- or ONE record that every rollout reads
+// (j_stride = 0).  Staged in LDS once per launch behind the rows of the actuator family, consecutive lanes on consecutive doubles (20 KB at
+// FB = 0, 2.5 KB at FB = 1): ONE copy per rollout, which both disturbance rows of the rollout share.  A substep hands the step the offset of
+// the record; the step reads each value where it uses it (h1_aba_split.h stance_prepare_j).
+template <int RPW>
+DEVFN void stage_joint_records(const DevState& S, double* rows, int b0, const double* jtab, int j_stride) {
+  for (int e = threadIdx.x; e < RPW * h1s::JOINT_REC; e += 64) {
+    const int r = e / h1s::JOINT_REC;
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;      // (a wave's unowned rows read the last rollout's record)
+    rows[e] = jtab[(size_t)br * j_stride + (e - r * h1s::JOINT_REC)];
+  }
+}
+// plant_step_table<KIND, true> with the joint record at LDS offset jro: the scalar gain of the parameter record in front, as there
+template <int KIND>
+DEVFN void plant_step_table_j(bool side, h1s::HalfX& h, const h1s::HalfU& u, const DynParams& dyn, const int* st, const h1s::LaneLds& L, int geom, const double* rec, int wro, int jro) {
+  DynParams dl = dyn;
+  dl.g[0] = rec[0]; dl.g[1] = rec[1]; dl.g[2] = rec[2]; dl.mu = rec[3]; dl.soft = rec[4]; dl.lim_k = rec[5];
+  const double gain = rec[6];
+  h1s::HalfU us;
+  us.u11 = gain * u.u11;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) us.uL[q] = gain * u.uL[q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) us.uA[q] = gain * u.uA[q];
+  step_any_j<KIND>(side, h, us, dl, st, L, geom, wro, jro);
+}
+#define PLANT_TABLE 6
+#include "plant_follow_body.h"
+
+// ---- one step under a joint record per item, with an optional wrench and payload (ilqr_hip_step_joints): k_step_m with the record behind the
+// widened rows; wrench / payload null: none
+#define STEP_J_LDS_BYTES ((h1s::LDS_SLOTS * 64 + 32 * h1s::DIST_REC + 32 * h1s::JOINT_REC) * sizeof(double))
+template <int CK>
+__global__ void __launch_bounds__(64) k_step_j(int count, const double* x, const double* u, DynParams dyn, double* xn, int st_l, int st_r, const double* wrench, const double* payload,
+                                               const double* joints) {
+  extern __shared__ double lds[];
+  constexpr int WR0 = h1s::LDS_SLOTS * 64, JR0 = WR0 + 32 * h1s::DIST_REC;
+  const int i0 = blockIdx.x * 32;
+  for (int e = threadIdx.x; e < 32 * h1s::DIST_REC; e += 64) {
+    const int r = e / h1s::DIST_REC, k = e - r * h1s::DIST_REC;
+    const int ir = i0 + r < count ? i0 + r : count - 1;
+    double v = 0.0;
+    if (k < h1s::DIST_WRENCH_VALS) { if (wrench) v = wrench[(size_t)ir * h1s::DIST_WRENCH_VALS + k]; }
+    else if (k >= h1s::PAYLOAD_AT && k < h1s::PAYLOAD_AT + h1s::PAYLOAD_VALS) { if (payload) v = payload[(size_t)ir * h1s::PAYLOAD_VALS + (k - h1s::PAYLOAD_AT)]; }
+    lds[WR0 + e] = v;
+  }
+  for (int e = threadIdx.x; e < 32 * h1s::JOINT_REC; e += 64) {
+    const int r = e / h1s::JOINT_REC, k = e - r * h1s::JOINT_REC;
+    const int ir = i0 + r < count ? i0 + r : count - 1;
+    lds[JR0 + e] = k < h1s::JOINT_VALS ? joints[(size_t)ir * h1s::JOINT_VALS + k] : 0.0;
+  }
+  wave_lds_fence();
+  const int i = i0 + ((int)threadIdx.x >> 1);
+  const bool side = (threadIdx.x & 1) != 0;
+  if (i >= count) return;
+  const h1s::LaneLds L{lds, 64, (int)threadIdx.x};
+  h1s::HalfX h; h1s::load_half(side, x + (size_t)i * H1_NX, h);
+  h1s::HalfU uu; load_half_u(side, u + (size_t)i * H1_NU, uu);
+  int st[2] = {st_l, st_r};
+  step_any_j<CK>(side, h, uu, dyn, st, L, 0, WR0 + ((int)threadIdx.x >> 1) * h1s::DIST_REC, JR0 + ((int)threadIdx.x >> 1) * h1s::JOINT_REC);
+  h1s::store_half(side, h, xn + (size_t)i * H1_NX);
+}
+#endif
+#ifdef PLANT_ACTUATOR_MODULE
 #define PLANT_TABLE 5
 #include "plant_follow_body.h"
 
@@ -749,6 +821,45 @@ static void launch_actuator_draw(int B, unsigned long long seed, unsigned long l
   const dim3 grid((unsigned)((B + ACT_RPB - 1) / ACT_RPB), (unsigned)count);
   hipLaunchKernelGGL(k_actuator_draw, grid, dim3(256), 0, st, B, seed, stream0, interval0, out);
 }
+#elif defined(PLANT_JOINTS_MODULE)      // attributes and launchers of the joints family, exported from its module with C linkage (ilqr_kernels.h)
+template <int FB> static constexpr size_t follow_lds_j() {
+  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX + FollowLayout<FB>::RPW * PLANT_NU +
+          FollowLayout<FB>::RPW * h1s::JOINT_REC) * sizeof(double);
+}
+static_assert(follow_lds_j<0>() <= 160 * 1024 && follow_lds_j<1>() <= 160 * 1024, "k_plant_follow_j: the workgroup's LDS");
+template <int KIND, int FB> static int plant_attr_j() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_j<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_j<FB>()) != hipSuccess;
+}
+template <int KIND> static int step_attr_j() {
+  return hipFuncSetAttribute((const void*)k_step_j<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_J_LDS_BYTES) != hipSuccess;
+}
+static int joints_kernels_set_attr() {
+  int rc = 0;
+  for_each_step_kind([&](auto K) { rc |= plant_attr_j<K(), 0>(); rc |= plant_attr_j<K(), 1>(); rc |= step_attr_j<K()>(); });
+  return rc;
+}
+template <int KIND, int FB>
+static void follow_launch_j(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const ActuatorTable& A,
+                            const JointTable& J, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_j<KIND, FB>), grid, dim3(64), follow_lds_j<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs, A.records, A.rec_stride, A.blend, A.blend_stride, A.z, A.fifo, A.y, A.applied,
+                     A.substep0, J.records, J.rec_stride);
+}
+static void launch_plant_follow_joints(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs,
+                                       const ActuatorTable& A, const JointTable& J, const WrenchFollowArgs& w, hipStream_t st) {
+  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (w.feedback_mode) follow_launch_j<K(), 1>(S, Pl, dyn, T, W, M, dobs, A, J, a, st);
+    else follow_launch_j<K(), 0>(S, Pl, dyn, T, W, M, dobs, A, J, a, st);
+  });
+}
+static void launch_step_joints(int count, const double* x, const double* u, const DynParams& dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload,
+                               const double* joints, hipStream_t st) {
+  const dim3 grid((unsigned)((count + 31) / 32));
+  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_j<K()>), grid, dim3(64), STEP_J_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench, payload, joints); });
+}
 #else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
 template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
 template <int KIND, int FB> static int plant_attr_w() {
@@ -831,6 +942,20 @@ void ilqr_actuator_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* 
 }
 void ilqr_actuator_module_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, int count, double* z, hipStream_t st) {
   ilqr::launch_actuator_draw(B, seed, stream0, interval0, count, z, st);
+}
+}
+#endif
+
+#ifdef PLANT_JOINTS_MODULE
+extern "C" {
+int ilqr_joints_module_set_attr() { return ilqr::joints_kernels_set_attr(); }
+void ilqr_joints_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
+                               const double* delta, const ilqr::ActuatorTable* A, const ilqr::JointTable* J, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
+  ilqr::launch_plant_follow_joints(*S, *Pl, *dyn, *T, *W, *M, delta, *A, *J, *a, st);
+}
+void ilqr_joints_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload,
+                             const double* joints, hipStream_t st) {
+  ilqr::launch_step_joints(count, x, u, *dyn, xn, stance_l, stance_r, wrench, payload, joints, st);
 }
 }
 #endif

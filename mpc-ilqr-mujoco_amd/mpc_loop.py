@@ -69,6 +69,10 @@ The cold first step initialises from plant_get_observed(); physics, ring and sco
 `MPCRunner(..., resident=True, plant_actuator=A, actuator_seed=S, actuator_stream0=0)` puts an actuator between the control law and the
 joints: A [1, 39] or [B, 39] (scenario.stack_plant_actuator) is a delay in plant substeps, a lag time constant and a torque noise level per
 joint and rollout (BatchedILQR.plant_set_actuator).  The log and the score keep the commanded torque; the solve knows of none of it.
+
+`MPCRunner(..., resident=True, plant_joints=J)` gives every rollout's plant joints of its own: J [1, 76] or [B, 76]
+(scenario.stack_plant_joints) is a torque gain, a scale on the torque range, a damping and an armature per joint and rollout
+(BatchedILQR.plant_set_joints), installed in front of the reset.  The log and the score keep the commanded torque; the solve keeps the model's joints.
 """
 import os
 import time
@@ -114,7 +118,7 @@ class MPCRunner:
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
                  device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None,
-                 plant_observation=None, observation_seed=0, observation_stream0=0, plant_actuator=None, actuator_seed=0, actuator_stream0=0):
+                 plant_observation=None, observation_seed=0, observation_stream0=0, plant_actuator=None, actuator_seed=0, actuator_stream0=0, plant_joints=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -166,6 +170,13 @@ class MPCRunner:
             if plant_actuator.ndim != 2 or plant_actuator.shape[1] != 39 or plant_actuator.shape[0] not in (1, solver.B):
                 raise ValueError("plant_actuator must be [1, 39] or [B, 39] (scenario.stack_plant_actuator)")
         self.plant_actuator, self.actuator_seed, self.actuator_stream0 = plant_actuator, int(actuator_seed), int(actuator_stream0)
+        if not resident and plant_joints is not None:
+            raise ValueError("plant_joints needs the device-resident plant (resident=True)")
+        if plant_joints is not None:
+            plant_joints = np.atleast_2d(np.asarray(plant_joints, dtype=np.float64))
+            if plant_joints.ndim != 2 or plant_joints.shape[1] != 76 or plant_joints.shape[0] not in (1, solver.B):
+                raise ValueError("plant_joints must be [1, 76] or [B, 76] (scenario.stack_plant_joints)")
+        self.plant_joints = plant_joints
         self.device_refs, self.track_ready = bool(device_refs), False
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
@@ -308,6 +319,8 @@ class MPCRunner:
             s.plant_set_observation(self.plant_observation, seed=self.observation_seed, stream0=self.observation_stream0)
         if self.plant_actuator is not None:
             s.plant_set_actuator(self.plant_actuator, seed=self.actuator_seed, stream0=self.actuator_stream0)
+        if self.plant_joints is not None:
+            s.plant_set_joints(self.plant_joints)
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)

@@ -249,6 +249,44 @@ def stack_plant_actuator(B, delay=0, tau=0.0, sigma=0.0):
     return out
 
 
+# fields of a joint record in record order with their nominal values (solver.PLANT_JOINT_FIELDS)
+_JOINT_FIELDS = (("gain", 1.0), ("range_scale", 1.0), ("damping", 1.0), ("armature", 0.1))
+
+
+def stack_plant_joints(records, B):
+    """Joint records [B, 76] for BatchedILQR.plant_set_joints / MPCRunner(plant_joints=...): gain[19], range_scale[19], damping[19],
+    armature[19] in the order of u.  records is one dict (every rollout) or a sequence of B dicts; a dict holds any of "gain", "range_scale",
+    "damping", "armature", each a scalar (every joint) or a vector per joint [19]; what it leaves out is nominal (1, 1, 1, 0.1), so {} is the
+    model's joints.  Raises ValueError for another key, a shape that is neither, a sequence that is not B long, a non-finite or a negative
+    entry -- what ilqr_hip_plant_set_joints refuses."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    if isinstance(records, dict):
+        records = [records] * B
+    records = list(records)
+    if len(records) != B:
+        raise ValueError("records must be one dict or B of them")
+    out = np.empty((B, 76))
+    names = [f for f, _ in _JOINT_FIELDS]
+    for b, rec in enumerate(records):
+        if not isinstance(rec, dict):
+            raise ValueError("a joint record is a dict")
+        extra = set(rec) - set(names)
+        if extra:
+            raise ValueError("unknown joint field(s) %s: a record has %s" % (sorted(extra), names))
+        for k, (name, nominal) in enumerate(_JOINT_FIELDS):
+            v = np.asarray(rec.get(name, nominal), dtype=np.float64)
+            if v.shape not in ((), (19,)):
+                raise ValueError("%s must be a scalar or [19]" % name)
+            out[b, 19 * k:19 * (k + 1)] = v
+    if not np.isfinite(out).all():
+        raise ValueError("plant joint records must be finite")
+    if (out < 0).any():
+        raise ValueError("gain, range_scale, damping and armature must be >= 0")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

@@ -55,6 +55,7 @@ EXPORTS = [
     "ilqr_hip_plant_observation_errors", "ilqr_hip_plant_get_observed",
     "ilqr_hip_plant_set_actuator", "ilqr_hip_plant_clear_actuator", "ilqr_hip_plant_num_actuator_sets", "ilqr_hip_plant_get_actuator",
     "ilqr_hip_plant_get_actuator_blend", "ilqr_hip_plant_actuator_draws", "ilqr_hip_plant_get_applied",
+    "ilqr_hip_plant_set_joints", "ilqr_hip_plant_get_joints", "ilqr_hip_step_joints",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
@@ -73,6 +74,9 @@ PLANT_OBSERVATION = 100
 # a plant actuator record (include/ilqr_hip.h ILQR_PLANT_ACTUATOR): delay (plant substeps, an integer 0..PLANT_ACTUATOR_MAX_DELAY), tau[19], sigma[19]
 PLANT_ACTUATOR = 39
 PLANT_ACTUATOR_MAX_DELAY = 8
+# fields of a plant joint record (include/ilqr_hip.h ILQR_PLANT_JOINTS), 19 values each in the order of u, with their nominal values
+PLANT_JOINT_FIELDS = (("gain", 1.0), ("range_scale", 1.0), ("damping", 1.0), ("armature", 0.1))
+PLANT_JOINTS = 76
 
 
 
@@ -550,6 +554,25 @@ class BatchedILQR:
         self._chk(self.L.ilqr_hip_step_payload(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), None if wrench is None else _p(wrench), _p(payload), _p(xn)))
         return xn
 
+    def step_joints(self, x, u, stance_left, stance_right, joints, wrench=None, payload=None):
+        """step_payload with one joint record per item: joints [count, 76] (gain, range scale, damping, armature of the 19 joints;
+        scenario.stack_plant_joints builds them), wrench [count, 9] and payload [count, 10] each or None for none; always the two-lane step
+        (ilqr_hip_step_joints)."""
+        x, u, joints = _c64(x), _c64(u), _c64(joints)
+        if joints.shape != (x.shape[0], PLANT_JOINTS):
+            raise ValueError("joints must be [count, 76]")
+        if wrench is not None:
+            wrench = _c64(wrench)
+            if wrench.shape != (x.shape[0], 9):
+                raise ValueError("wrench must be [count, 9]")
+        if payload is not None:
+            payload = _c64(payload)
+            if payload.shape != (x.shape[0], len(PLANT_PAYLOAD)):
+                raise ValueError("payload must be [count, 10]")
+        xn = np.zeros_like(x)
+        self._chk(self.L.ilqr_hip_step_joints(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(payload), _p(joints), _p(xn)))
+        return xn
+
     def set_stance_source(self, source):
         """Stance source of the dynamics (include/ilqr_hip.h): "schedule" (default) or "geometry" -- every step takes the stance flags from
         its own feet (a foot touches iff its ankle-link hull reaches the floor, foot_clearance < 0); the cost keeps the schedule."""
@@ -747,6 +770,27 @@ class BatchedILQR:
         if payload.ndim != 2 or payload.shape[1] != len(PLANT_PAYLOAD) or payload.shape[0] not in (1, self.B):
             raise ValueError("plant payloads must be [1, 10] or [B, 10]")
         self._chk(self.L.ilqr_hip_plant_set_payload(self.h, _p(payload), int(payload.shape[0])))
+
+    def plant_set_joints(self, joints):
+        """Install joint records [n_sets, 76] (gain, range scale, damping, armature of the 19 joints; scenario.stack_plant_joints builds them),
+        n_sets 1 or B: rollout b's plant steps with the joints of its record until plant_clear_joints (ilqr_hip_plant_set_joints).  None
+        clears.  The solve does not know of it; the plant keeps reporting the commanded torque."""
+        if joints is None:
+            return self.plant_clear_joints()
+        joints = _c64(joints)
+        if joints.ndim == 1:
+            joints = joints[None]
+        if joints.ndim != 2 or joints.shape[1] != PLANT_JOINTS or joints.shape[0] not in (1, self.B):
+            raise ValueError("plant joints must be [1, 76] or [B, 76]")
+        self._chk(self.L.ilqr_hip_plant_set_joints(self.h, _p(joints), int(joints.shape[0])))
+
+    def plant_clear_joints(self):
+        """Remove the joint records: the plant calls launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_set_joints(self.h, None, 0))
+
+    def plant_get_joints(self):
+        """[B, 76]: the record of each rollout; the nominal record without a table."""
+        return self._get("ilqr_hip_plant_get_joints", (self.B, PLANT_JOINTS))
 
     def plant_clear_payload(self):
         """Remove the payloads: the plant calls launch what they launch without them."""

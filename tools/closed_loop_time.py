@@ -40,7 +40,13 @@ noise), alternating on one box, the plant in the given contact mode.
    python tools/closed_loop_time.py --actuator [--contact-mode 0] [--solve-every M] ...
 compares, instead, the RESIDENT runner without an actuator table against the same runner with one installed (MPCRunner(plant_actuator=...):
 per rollout a delay of 0 to 2 plant substeps, a lag of 5 to 20 ms and 0.5 N m of torque noise per joint), alternating on one box, the plant
-in the given contact mode; then the plant call alone, events around 50 back-to-back advances."""
+in the given contact mode; then the plant call alone, events around 50 back-to-back advances.
+
+   python tools/closed_loop_time.py --joints [--contact-mode 0] [--solve-every M] ...
+compares, instead, the RESIDENT runner without a joint table against the same runner with one installed (MPCRunner(plant_joints=...): per
+rollout and joint a gain of 0.8 to 1, a range scale of 0.7 to 1, a damping of 0.5 to 2 and an armature of 0.05 to 0.2), alternating on one
+box, the plant in the given contact mode; then the plant call alone, events around 50 back-to-back advances: without a table, under the
+actuator table of --actuator alone (the family the joints family widens) and under the joint table alone."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py): behind the product library, torch finds "no HIP GPUs" when it is asked for the device name
@@ -65,6 +71,7 @@ def main():
     ap.add_argument("--payload", action="store_true")
     ap.add_argument("--observation", action="store_true")
     ap.add_argument("--actuator", action="store_true")
+    ap.add_argument("--joints", action="store_true")
     ap.add_argument("--device-refs", action="store_true"); ap.add_argument("--per-rollout-starts", action="store_true"); ap.add_argument("--contact-mode", type=int, default=2)
     a = ap.parse_args()
     if a.per_rollout_starts and not a.device_refs:
@@ -86,6 +93,8 @@ def main():
         return observation_main(a, sc, ml, rf, sv)
     if a.actuator:
         return actuator_main(a, sc, ml, rf, sv)
+    if a.joints:
+        return joints_main(a, sc, ml, rf, sv)
     base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
     rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
     rows = a.steps + N + 10
@@ -332,6 +341,64 @@ def actuator_main(a, sc, ml, rf, sv):
                       "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
                       "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_actuator": float(np.median(ms[True])),
                       "samples_no_actuator": ms[False], "samples_actuator": ms[True], "alive_no_actuator": alive[False], "alive_actuator": alive[True]}))
+
+
+def joints_main(a, sc, ml, rf, sv):
+    B, N = a.batch, a.horizon
+    base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
+    rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
+    rows = a.steps + N + 10
+    rd.set_states(np.tile(sc.standing_state(), (rows, 1))); rd.contact = np.ones((rows, 2), dtype=np.int32)
+    x0, ui = sc.synthetic_batch(B, N, 0, sv.gravity_compensation(sc.standing_state(), base["gravity"]))
+    rng = np.random.default_rng(1)
+    table = sc.stack_plant_joints([dict(gain=rng.uniform(0.8, 1.0, 19), range_scale=rng.uniform(0.7, 1.0, 19), damping=rng.uniform(0.5, 2.0, 19), armature=rng.uniform(0.05, 0.2, 19))
+                                   for _ in range(B)], B)
+    act = sc.stack_plant_actuator(B, delay=rng.integers(0, 3, B), tau=rng.uniform(0.005, 0.02, (B, 19)), sigma=0.5)
+    ms, alive = {False: [], True: []}, {}
+    for rnd in range(a.rounds + 1):                      # round 0 warms up (first launches, allocations)
+        for tab in (False, True):
+            s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+            s.set_contact_mode(a.contact_mode)
+            run = ml.MPCRunner(s, rd, base, resident=True, substeps=a.substeps, feedback_mode=a.feedback_mode, solve_every=a.solve_every, plant_joints=table if tab else None)
+            run.run(x0, 1, u_init=ui)                    # the cold start is not what is compared: every timed step is a warm one
+            s.synchronize()
+            t0 = time.perf_counter()
+            run.run(x0, a.steps, u_init=ui)
+            dt = time.perf_counter() - t0
+            alive[tab] = int(s.plant_alive().sum())
+            s.close()
+            if rnd:
+                ms[tab].append(1e3 * dt / a.steps)
+    # the plant call alone: 50 back-to-back advances under one solve, three repetitions from the same plant state
+    kernel_us, alive_k = {}, {}
+    for mode in (0, 2):
+        s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+        s.set_problem(base); s.initialize(x0, ui); s.solve(x0)
+        s.plant_set_model(mode, None); s.plant_configure(a.substeps, a.feedback_mode, "schedule")
+        st = torch.cuda.ExternalStream(s.stream)
+        for tab in ("no_table", "actuator_table", "joint_table"):
+            s.plant_clear_actuator(); s.plant_clear_joints()
+            if tab == "actuator_table":
+                s.plant_set_actuator(act, seed=2024)
+            if tab == "joint_table":
+                s.plant_set_joints(table)
+            us = []
+            for rep_ in range(4):                        # (the first repetition warms up)
+                s.plant_reset(x0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(50):
+                    s.plant_advance()
+                e1.record(st); e1.synchronize()
+                us.append(1e3 * e0.elapsed_time(e1) / 50)
+            key = "mode%d_%s" % (mode, tab)
+            kernel_us[key], alive_k[key] = us[1:], int(s.plant_alive().sum())
+        s.close()
+    print(json.dumps({"tool": "closed_loop_time", "mode": "joints", "plant_call_us": {k: float(np.median(v)) for k, v in kernel_us.items()}, "plant_call_samples_us": kernel_us,
+                      "alive_after_50_advances": alive_k, "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "iterations": a.iters, "steps": a.steps,
+                      "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
+                      "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_joints": float(np.median(ms[True])),
+                      "samples_no_joints": ms[False], "samples_joints": ms[True], "alive_no_joints": alive[False], "alive_joints": alive[True]}))
 
 
 class HostWindows:
