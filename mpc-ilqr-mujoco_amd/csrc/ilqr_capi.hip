@@ -18,6 +18,7 @@
 #include "h1_cost_dev.h"
 #include "h1_host_model.h"
 #include "ilqr_kernels.h"
+#include "plant_plan.h"
 #include "plant_score_kernels.h"
 #include "reference_track_kernels.h"
 
@@ -151,42 +152,33 @@ struct ilqr_hip_ctx {
   int plant_substeps = 1, plant_feedback = 0, plant_source = ILQR_STANCE_SCHEDULE;
   // the plant's own model (ilqr_hip_plant_set_model): -1 follows the solver's contact mode / joint-limit option, else the plant's
   int plant_mode = -1, plant_limits = -1;
-  // plant parameter table (ilqr_hip_plant_set_params; plant_kernels.hip k_plant_follow_p): [n][8] doubles, n = 1 or B; null: none
-  double* d_pparams = nullptr;
-  int pparams_sets = 0;
-  // wrench table (ilqr_hip_plant_set_wrench; plant_kernels.hip k_plant_follow_w): [n][16] doubles (128-byte records), n = 1 or B; null: none.
-  // d_self_params: the ONE parameter record the wrench kernels read while no parameter table is installed -- the handle's own values with
+  // Per-rollout tables of the plant, one TableBuf each: [sets][record] doubles on the device, sets = 1 or B; d null: none installed
+  // (table_install / table_clear / table_read).  While any is installed the plant calls launch the family resolve_plant_plan names.
+  //   pparams (ilqr_hip_plant_set_params; k_plant_follow_p): records of 8 doubles
+  //   wrench  (ilqr_hip_plant_set_wrench; k_plant_follow_w): records of WRENCH_REC doubles
+  //   payload (ilqr_hip_plant_set_payload; k_plant_follow_m): records of PAYLOAD_REC doubles
+  //   obs     (ilqr_hip_plant_set_observation; k_plant_follow_o): records of 100 doubles
+  //   act     (ilqr_hip_plant_set_actuator; k_plant_follow_a): records of 39 doubles
+  //   joints  (ilqr_hip_plant_set_joints; k_plant_follow_j): records of JOINT_REC doubles
+  struct TableBuf { double* d = nullptr; int sets = 0; };
+  TableBuf pparams, wrench, payload, obs, act, joints;
+  // d_self_params: the ONE parameter record the module families read while no parameter table is installed -- the handle's own values with
   // gain 1, uploaded again whenever they differ from self_params
-  double* d_wrench = nullptr;
-  int wrench_sets = 0;
   double* d_self_params = nullptr;
   double self_params[ILQR_PLANT_PARAMS + 1] = {0};
-  double* d_stepw = nullptr;  // [step_w_cap][9] wrenches of ilqr_hip_step_wrench
-  size_t step_w_cap = 0;
-  bool wrench_attr_set = false;   // the wrench module's kernels have their LDS attributes on this handle's device
-  // payload table (ilqr_hip_plant_set_payload; plant_kernels.hip k_plant_follow_m): [n][16] doubles (128-byte records), n = 1 or B; null: none.
-  // While it is installed the plant calls launch the payload family, which reads d_self_params / d_wrench as the wrench family does.
-  double* d_ppayload = nullptr;
-  int payload_sets = 0;
-  double* d_stepm = nullptr;  // [step_m_cap][10] payloads of ilqr_hip_step_payload (its wrenches go through d_stepw)
-  size_t step_m_cap = 0;
-  bool payload_attr_set = false;  // the payload module's kernels have their LDS attributes on this handle's device
-  // observation table (ilqr_hip_plant_set_observation; plant_kernels.hip k_plant_follow_o): [n][100] doubles, n = 1 or B; null: none.  While it
-  // is installed the plant calls launch the observation family behind a draw of the call's error rows into d_obs_delta [N][B][51] (a follow
-  // never exceeds N intervals), and the warm starts hand the solve Pl.x [+] delta of the current interval.
-  double* d_pobs = nullptr;
-  int obs_sets = 0;
+  unsigned module_attr_set = 0;   // bit ilqr::PlantModule: that module's kernels have their LDS attributes on this handle's device
+  // scratch of the single-step calls beside d_stepx / d_stepu / d_stepn: [cap][9] wrenches, [cap][10] payloads, [cap][76] joint records
+  double *d_stepw = nullptr, *d_stepm = nullptr, *d_stepj = nullptr;
+  size_t step_w_cap = 0, step_m_cap = 0, step_j_cap = 0;
+  // Observation: the plant calls run behind a draw of the call's error rows into d_obs_delta [N][B][51] (a follow never exceeds N intervals),
+  // and the warm starts hand the solve Pl.x [+] delta of the current interval.
   unsigned long long obs_seed = 0, obs_stream0 = 0;
   double* d_obs_delta = nullptr;
   double* d_obs_x = nullptr;      // [B][51] the measured state of ilqr_hip_plant_get_observed
-  bool observe_attr_set = false;  // the observation module's kernels have their LDS attributes on this handle's device
-  // actuator table (ilqr_hip_plant_set_actuator; plant_kernels.hip k_plant_follow_a): [n][39] doubles, n = 1 or B; null: none.  While it is
-  // installed the plant calls launch the actuator family behind a draw of the call's normals into d_act_z [N][B][19].  act_rec is the host's
-  // copy, from which d_act_beta [n][19] is derived again when plant_configure changes the substeps.  The actuator's state -- delay line
-  // [B][9][19], lag output [B][19] -- and the applied torque of the last substep [B][19] persist across the calls; act_substeps counts the
-  // substeps run since the state was primed (0: the next substep primes it).
-  double* d_pact = nullptr;
-  int act_sets = 0;
+  // Actuator: the plant calls run behind a draw of the call's normals into d_act_z [N][B][19].  act_rec is the host's copy of the table, from
+  // which d_act_beta [sets][19] is derived again when plant_configure changes the substeps.  The actuator's state -- delay line [B][9][19], lag
+  // output [B][19] -- and the applied torque of the last substep [B][19] persist across the calls; act_substeps counts the substeps run since
+  // the state was primed (0: the next substep primes it).
   unsigned long long act_seed = 0, act_stream0 = 0;
   std::vector<double> act_rec, act_beta;
   double* d_act_beta = nullptr;
@@ -195,15 +187,8 @@ struct ilqr_hip_ctx {
   double* d_act_y = nullptr;
   double* d_act_applied = nullptr;
   long act_substeps = 0;
-  bool actuator_attr_set = false;  // the actuator module's kernels have their LDS attributes on this handle's device
-  // joint table (ilqr_hip_plant_set_joints; plant_kernels.hip k_plant_follow_j): [n][80] doubles, n = 1 or B; null: none.  While it is installed
-  // and not all nominal (joints_nominal: such a table is no table, decided here on the host) the plant calls launch the joints family.
-  double* d_pjoints = nullptr;
-  int joints_sets = 0;
+  // Joints: a table whose every record is the model's own joints is no table (joints_nominal, decided on the host when it is installed)
   bool joints_nominal = false;
-  double* d_stepj = nullptr;  // [step_j_cap][76] records of ilqr_hip_step_joints (wrenches and payloads go through d_stepw, d_stepm)
-  size_t step_j_cap = 0;
-  bool joints_attr_set = false;    // the joints module's kernels have their LDS attributes on this handle's device
   long plant_intervals = 0;   // plant intervals run since the last ilqr_hip_plant_reset (the history cursor only counts while a ring exists)
   int hist_cap = 0;           // rows of the history ring (0: none)
   long hist_n = 0;            // advances recorded since the last reset / set_history
@@ -286,22 +271,33 @@ static inline int enter_launching(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 
-// The wrench family of the plant kernels is a module of its own (csrc/Makefile ../lib/libilqr_hip_wrench.so; plant_kernels.hip says why),
-// opened on first use from the directory this library was loaded from, as RCCL is opened on first use: a process that never pushes its
-// plant never loads it.  A module that is missing or lacks an entry point is an error of the call that needs it (ILQR_ERR_UNSUPPORTED).
+// The wrench, payload, observation, actuator and joints families of the plant kernels are modules of their own (csrc/Makefile PLANT_MODULE;
+// plant_kernels.hip says why), each opened on first use from the directory this library was loaded from, as RCCL is opened on first use: a
+// process that never uses a family never loads it.  A module that is missing or lacks an entry point is an error of the call that needs it
+// (ILQR_ERR_UNSUPPORTED).
 namespace {
-struct WrenchModule {
-  void* lib = nullptr;
-  ilqr::wrench_set_attr_fn set_attr = nullptr;
-  ilqr::wrench_follow_fn follow = nullptr;
-  ilqr::wrench_step_fn step = nullptr;
-  std::string why;
-  bool ok() const { return lib && set_attr && follow && step; }
+enum ModuleFn { FN_SET_ATTR = 0, FN_FOLLOW, FN_STEP, FN_DRAW = FN_STEP, FN_APPLY, MODULE_FNS };
+// stem: of the file (libilqr_hip_<stem>.so) and of the symbols (ilqr_<stem>_module_<entry>); name: in the messages; entry: by ModuleFn
+struct ModuleDesc { const char *stem, *name; const char* entry[MODULE_FNS]; };
+const ModuleDesc MODULE_DESC[ilqr::PLANT_MODULES] = {
+  {"wrench", "wrench", {"set_attr", "follow", "step", nullptr}},
+  {"payload", "payload", {"set_attr", "follow", "step", nullptr}},
+  {"observe", "observation", {"set_attr", "follow", "draw", "apply"}},
+  {"actuator", "actuator", {"set_attr", "follow", "draw", nullptr}},
+  {"joints", "joints", {"set_attr", "follow", "step", nullptr}},
 };
-WrenchModule& wrench_module() {
-  static WrenchModule m;
-  static std::once_flag once;
-  std::call_once(once, [] {
+struct PlantModuleLib {
+  void* fn[MODULE_FNS] = {nullptr};
+  bool ok = false;
+  std::string why;
+};
+// opened and resolved once per process and module
+PlantModuleLib& plant_module(int which) {
+  static PlantModuleLib mods[ilqr::PLANT_MODULES];
+  static std::once_flag once[ilqr::PLANT_MODULES];
+  std::call_once(once[which], [which] {
+    PlantModuleLib& m = mods[which];
+    const ModuleDesc& d = MODULE_DESC[which];
     Dl_info info;
     std::string dir = ".";
     if (dladdr((const void*)&ilqr_hip_plant_intervals, &info) && info.dli_fname) {
@@ -309,198 +305,28 @@ WrenchModule& wrench_module() {
       const size_t slash = self.rfind('/');
       if (slash != std::string::npos) dir = self.substr(0, slash);
     }
-    const std::string path = dir + "/libilqr_hip_wrench.so";
-    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!m.lib) { m.why = "the wrench kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
-    m.set_attr = (ilqr::wrench_set_attr_fn)dlsym(m.lib, "ilqr_wrench_module_set_attr");
-    m.follow = (ilqr::wrench_follow_fn)dlsym(m.lib, "ilqr_wrench_module_follow");
-    m.step = (ilqr::wrench_step_fn)dlsym(m.lib, "ilqr_wrench_module_step");
-    if (!m.ok()) m.why = "the wrench kernels' module lacks an entry point: " + path;
+    const std::string path = dir + "/libilqr_hip_" + d.stem + ".so";
+    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!lib) { m.why = std::string("the ") + d.name + " kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.ok = true;
+    for (int i = 0; i < MODULE_FNS && d.entry[i]; ++i) {
+      m.fn[i] = dlsym(lib, (std::string("ilqr_") + d.stem + "_module_" + d.entry[i]).c_str());
+      m.ok = m.ok && m.fn[i];
+    }
+    if (!m.ok) m.why = std::string("the ") + d.name + " kernels' module lacks an entry point: " + path;
   });
-  return m;
+  return mods[which];
 }
+// entry point `slot` of a module that need_module has checked, as its typedef of ilqr_kernels.h
+template <class Fn> Fn module_fn(int which, ModuleFn slot) { return (Fn)plant_module(which).fn[slot]; }
 }  // namespace
 // the module, with its kernels' LDS attributes set on this handle's device (once per handle)
-static int need_wrench_module(ilqr_hip_ctx* c) {
-  WrenchModule& m = wrench_module();
-  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
-  if (!c->wrench_attr_set) {
-    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the wrench kernels"; return ILQR_ERR_HIP; }
-    c->wrench_attr_set = true;
-  }
-  return ILQR_OK;
-}
-
-// The payload family (csrc/Makefile ../lib/libilqr_hip_payload.so) is a module of its own in the same way, opened on the first
-// ilqr_hip_plant_set_payload / ilqr_hip_step_payload.
-namespace {
-struct PayloadModule {
-  void* lib = nullptr;
-  ilqr::payload_set_attr_fn set_attr = nullptr;
-  ilqr::payload_follow_fn follow = nullptr;
-  ilqr::payload_step_fn step = nullptr;
-  std::string why;
-  bool ok() const { return lib && set_attr && follow && step; }
-};
-PayloadModule& payload_module() {
-  static PayloadModule m;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    Dl_info info;
-    std::string dir = ".";
-    if (dladdr((const void*)&ilqr_hip_plant_num_payload_sets, &info) && info.dli_fname) {
-      const std::string self = info.dli_fname;
-      const size_t slash = self.rfind('/');
-      if (slash != std::string::npos) dir = self.substr(0, slash);
-    }
-    const std::string path = dir + "/libilqr_hip_payload.so";
-    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!m.lib) { m.why = "the payload kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
-    m.set_attr = (ilqr::payload_set_attr_fn)dlsym(m.lib, "ilqr_payload_module_set_attr");
-    m.follow = (ilqr::payload_follow_fn)dlsym(m.lib, "ilqr_payload_module_follow");
-    m.step = (ilqr::payload_step_fn)dlsym(m.lib, "ilqr_payload_module_step");
-    if (!m.ok()) m.why = "the payload kernels' module lacks an entry point: " + path;
-  });
-  return m;
-}
-}  // namespace
-static int need_payload_module(ilqr_hip_ctx* c) {
-  PayloadModule& m = payload_module();
-  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
-  if (!c->payload_attr_set) {
-    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the payload kernels"; return ILQR_ERR_HIP; }
-    c->payload_attr_set = true;
-  }
-  return ILQR_OK;
-}
-
-// The observation family (csrc/Makefile ../lib/libilqr_hip_observe.so) is a module of its own in the same way, opened on the first
-// ilqr_hip_plant_set_observation.
-namespace {
-struct ObserveModule {
-  void* lib = nullptr;
-  ilqr::observe_set_attr_fn set_attr = nullptr;
-  ilqr::observe_follow_fn follow = nullptr;
-  ilqr::observe_draw_fn draw = nullptr;
-  ilqr::observe_apply_fn apply = nullptr;
-  std::string why;
-  bool ok() const { return lib && set_attr && follow && draw && apply; }
-};
-ObserveModule& observe_module() {
-  static ObserveModule m;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    Dl_info info;
-    std::string dir = ".";
-    if (dladdr((const void*)&ilqr_hip_plant_num_observation_sets, &info) && info.dli_fname) {
-      const std::string self = info.dli_fname;
-      const size_t slash = self.rfind('/');
-      if (slash != std::string::npos) dir = self.substr(0, slash);
-    }
-    const std::string path = dir + "/libilqr_hip_observe.so";
-    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!m.lib) { m.why = "the observation kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
-    m.set_attr = (ilqr::observe_set_attr_fn)dlsym(m.lib, "ilqr_observe_module_set_attr");
-    m.follow = (ilqr::observe_follow_fn)dlsym(m.lib, "ilqr_observe_module_follow");
-    m.draw = (ilqr::observe_draw_fn)dlsym(m.lib, "ilqr_observe_module_draw");
-    m.apply = (ilqr::observe_apply_fn)dlsym(m.lib, "ilqr_observe_module_apply");
-    if (!m.ok()) m.why = "the observation kernels' module lacks an entry point: " + path;
-  });
-  return m;
-}
-}  // namespace
-static int need_observe_module(ilqr_hip_ctx* c) {
-  ObserveModule& m = observe_module();
-  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
-  if (!c->observe_attr_set) {
-    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the observation kernels"; return ILQR_ERR_HIP; }
-    c->observe_attr_set = true;
-  }
-  return ILQR_OK;
-}
-
-// The actuator family (csrc/Makefile ../lib/libilqr_hip_actuator.so) is a module of its own in the same way, opened on the first
-// ilqr_hip_plant_set_actuator.
-namespace {
-struct ActuatorModule {
-  void* lib = nullptr;
-  ilqr::actuator_set_attr_fn set_attr = nullptr;
-  ilqr::actuator_follow_fn follow = nullptr;
-  ilqr::actuator_draw_fn draw = nullptr;
-  std::string why;
-  bool ok() const { return lib && set_attr && follow && draw; }
-};
-ActuatorModule& actuator_module() {
-  static ActuatorModule m;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    Dl_info info;
-    std::string dir = ".";
-    if (dladdr((const void*)&ilqr_hip_plant_num_actuator_sets, &info) && info.dli_fname) {
-      const std::string self = info.dli_fname;
-      const size_t slash = self.rfind('/');
-      if (slash != std::string::npos) dir = self.substr(0, slash);
-    }
-    const std::string path = dir + "/libilqr_hip_actuator.so";
-    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!m.lib) { m.why = "the actuator kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
-    m.set_attr = (ilqr::actuator_set_attr_fn)dlsym(m.lib, "ilqr_actuator_module_set_attr");
-    m.follow = (ilqr::actuator_follow_fn)dlsym(m.lib, "ilqr_actuator_module_follow");
-    m.draw = (ilqr::actuator_draw_fn)dlsym(m.lib, "ilqr_actuator_module_draw");
-    if (!m.ok()) m.why = "the actuator kernels' module lacks an entry point: " + path;
-  });
-  return m;
-}
-}  // namespace
-static int need_actuator_module(ilqr_hip_ctx* c) {
-  ActuatorModule& m = actuator_module();
-  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
-  if (!c->actuator_attr_set) {
-    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the actuator kernels"; return ILQR_ERR_HIP; }
-    c->actuator_attr_set = true;
-  }
-  return ILQR_OK;
-}
-
-// The joints family (csrc/Makefile ../lib/libilqr_hip_joints.so) is a module of its own in the same way, opened on the first
-// ilqr_hip_plant_set_joints / ilqr_hip_step_joints.
-namespace {
-struct JointsModule {
-  void* lib = nullptr;
-  ilqr::joints_set_attr_fn set_attr = nullptr;
-  ilqr::joints_follow_fn follow = nullptr;
-  ilqr::joints_step_fn step = nullptr;
-  std::string why;
-  bool ok() const { return lib && set_attr && follow && step; }
-};
-JointsModule& joints_module() {
-  static JointsModule m;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    Dl_info info;
-    std::string dir = ".";
-    if (dladdr((const void*)&ilqr_hip_plant_get_joints, &info) && info.dli_fname) {
-      const std::string self = info.dli_fname;
-      const size_t slash = self.rfind('/');
-      if (slash != std::string::npos) dir = self.substr(0, slash);
-    }
-    const std::string path = dir + "/libilqr_hip_joints.so";
-    m.lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!m.lib) { m.why = "the joints kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
-    m.set_attr = (ilqr::joints_set_attr_fn)dlsym(m.lib, "ilqr_joints_module_set_attr");
-    m.follow = (ilqr::joints_follow_fn)dlsym(m.lib, "ilqr_joints_module_follow");
-    m.step = (ilqr::joints_step_fn)dlsym(m.lib, "ilqr_joints_module_step");
-    if (!m.ok()) m.why = "the joints kernels' module lacks an entry point: " + path;
-  });
-  return m;
-}
-}  // namespace
-static int need_joints_module(ilqr_hip_ctx* c) {
-  JointsModule& m = joints_module();
-  if (!m.ok()) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
-  if (!c->joints_attr_set) {
-    if (m.set_attr() != 0) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the joints kernels"; return ILQR_ERR_HIP; }
-    c->joints_attr_set = true;
+static int need_module(ilqr_hip_ctx* c, int which) {
+  const PlantModuleLib& m = plant_module(which);
+  if (!m.ok) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
+  if (!((c->module_attr_set >> which) & 1u)) {
+    if (module_fn<ilqr::wrench_set_attr_fn>(which, FN_SET_ATTR)() != 0) { c->err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the ") + MODULE_DESC[which].name + " kernels"; return ILQR_ERR_HIP; }
+    c->module_attr_set |= 1u << which;
   }
   return ILQR_OK;
 }
@@ -592,7 +418,8 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_pparams, c->d_wrench, c->d_self_params, c->d_stepw, c->d_ppayload, c->d_stepm, c->d_pobs, c->d_obs_delta, c->d_obs_x, c->d_pact, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->d_pjoints, c->d_stepj}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
+  for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints}) if (t->d) hipFree(t->d);
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1569,20 +1396,34 @@ int ilqr_hip_set_friction(ilqr_hip_ctx* c, double mu) {
   c->P.dyn.mu = mu;            // (a nominal rolled under another mu is recognised by same_dyn)
   return ILQR_OK;
 }
+// grows a scratch buffer of the single-step calls to `count` rows of `width` doubles
+static int grow_step_buffer(ilqr_hip_ctx* c, double** p, size_t* cap, size_t count, size_t width) {
+  if (count <= *cap) return ILQR_OK;
+  if (*p) hipFree(*p);
+  *p = nullptr; *cap = 0;
+  HIPCHK(c, hipMalloc((void**)p, count * width * sizeof(double)));
+  *cap = count;
+  return ILQR_OK;
+}
+// the scratch every single-step call uses -- states, controls, next states and the stance flags out -- owned by the context and grown on
+// demand (the closed loop steps the plant every MPC step)
+static int grow_step_scratch(ilqr_hip_ctx* c, int count) {
+  if ((size_t)count <= c->step_cap) return ILQR_OK;
+  if (c->d_stepx) hipFree(c->d_stepx);
+  if (c->d_stepu) hipFree(c->d_stepu);
+  if (c->d_stepn) hipFree(c->d_stepn);
+  if (c->d_stance_out) hipFree(c->d_stance_out);
+  c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
+  HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
+  HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
+  HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
+  HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
+  c->step_cap = (size_t)count;
+  return ILQR_OK;
+}
 // the plant step of ilqr_hip_step_stance / ilqr_hip_step_geometry (geom: stance from each item's own feet, stance_out [count][2] nullable)
 static int plant_step(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, int geom, int* stance_out, double* x_next) {
-  if ((size_t)count > c->step_cap) {   // scratch owned by the context, grown on demand (the closed loop steps the plant every MPC step)
-    if (c->d_stepx) hipFree(c->d_stepx);
-    if (c->d_stepu) hipFree(c->d_stepu);
-    if (c->d_stepn) hipFree(c->d_stepn);
-    if (c->d_stance_out) hipFree(c->d_stance_out);
-    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
-    c->step_cap = (size_t)count;
-  }
+  TRY(grow_step_scratch(c, count));
   HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
   ilqr::launch_step(plan_of(c), count, c->d_stepx, c->d_stepu, c->P.dyn, c->d_stepn, c->stream, stance_left, stance_right, geom, geom ? c->d_stance_out : nullptr);
@@ -1676,10 +1517,13 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
   if ((plant_mode >= 0 ? plant_mode : c->P.dyn.contact) == ILQR_CONTACT_RIGID_STANCE) return "plant contact mode 1 (bilateral weld) with the stance source GEOMETRY: a welded foot never leaves the floor; use mode 2, 3 or 4";
   return nullptr;
 }
-// The wrench family (k_plant_follow_w) always reads a parameter record: the parameter table's, or this ONE record of the handle's own values
-// with gain 1, uploaded again whenever the handle's values have changed.
+// What a plant call launches (plant_plan.h): resolved from the installed tables behind the call's prologue, never stored.
+static ilqr::PlantPlan plant_plan_of(const ilqr_hip_ctx* c, bool follow) {
+  return ilqr::resolve_plant_plan({c->pparams.d != nullptr, c->wrench.d != nullptr, c->payload.d != nullptr, c->obs.d != nullptr, c->act.d != nullptr, c->joints.d != nullptr, c->joints_nominal}, follow);
+}
+// The module families always read a parameter record: the parameter table's, or (PlantPlan::self_params) this ONE record of the handle's own
+// values with gain 1, uploaded again whenever the handle's values have changed.
 static int plant_self_params(ilqr_hip_ctx* c) {
-  if ((!c->d_wrench && !c->d_ppayload && !c->d_pobs && !c->d_pact && !c->d_pjoints) || c->d_pparams) return ILQR_OK;
   const h1::DynParams& d = c->P.dyn;
   const double rec[ILQR_PLANT_PARAMS + 1] = {d.g[0], d.g[1], d.g[2], d.mu, d.soft, d.lim_k, 1.0, 0.0};
   if (c->d_self_params && std::memcmp(rec, c->self_params, sizeof(rec)) == 0) return ILQR_OK;
@@ -1689,24 +1533,26 @@ static int plant_self_params(ilqr_hip_ctx* c) {
   std::memcpy(c->self_params, rec, sizeof(rec));
   return ILQR_OK;
 }
-// The plant kernel of one call: without a table exactly the launch without the feature; with one, the followed kernel with the table's
-// records -- for an advance over the one interval (0, 1), which is an advance bit for bit.  row: the advance's ring row (-1: no ring) or the
-// follow's first ring row.
-// With a wrench table: the wrench family of the module, under the parameter table or the handle's own record (plant_self_params).
 static ilqr::ObservationTable observation_table(const ilqr_hip_ctx* c) {
-  return ilqr::ObservationTable{c->d_pobs, c->obs_sets == 1 ? 0 : ILQR_PLANT_OBSERVATION, c->obs_seed, c->obs_stream0};
+  return ilqr::ObservationTable{c->obs.d, c->obs.sets == 1 ? 0 : ILQR_PLANT_OBSERVATION, c->obs_seed, c->obs_stream0};
+}
+static void enqueue_observation_draw(ilqr_hip_ctx* c, long interval0, int count) {
+  const ilqr::ObservationTable O = observation_table(c);
+  module_fn<ilqr::observe_draw_fn>(ilqr::MOD_OBSERVE, FN_DRAW)(c->B, &O, interval0, count, c->d_obs_delta, c->stream);
+}
+static void enqueue_actuator_draw(ilqr_hip_ctx* c, long interval0, int count) {
+  module_fn<ilqr::actuator_draw_fn>(ilqr::MOD_ACTUATOR, FN_DRAW)(c->B, c->act_seed, c->act_stream0, interval0, count, c->d_act_z, c->stream);
 }
 // What a warm start hands the solve as x0: the plant's state, or -- under an observation table -- its measurement in the current interval,
 // Pl.x [+] delta(plant_intervals): a one-row draw and the apply in the place of the device copy.
 static int enqueue_measured_x0(ilqr_hip_ctx* c, double* out) {
-  if (!c->d_pobs) {
+  if (!c->obs.d) {
     HIPCHK(c, hipMemcpyAsync(out, c->plant.x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return ILQR_OK;
   }
-  TRY(need_observe_module(c));
-  const ilqr::ObservationTable O = observation_table(c);
-  observe_module().draw(c->B, &O, c->plant_intervals, 1, c->d_obs_delta, c->stream);
-  observe_module().apply(c->B, c->plant.x, c->d_obs_delta, out, c->stream);
+  TRY(need_module(c, ilqr::MOD_OBSERVE));
+  enqueue_observation_draw(c, c->plant_intervals, 1);
+  module_fn<ilqr::observe_apply_fn>(ilqr::MOD_OBSERVE, FN_APPLY)(c->B, c->plant.x, c->d_obs_delta, out, c->stream);
   HIPCHK(c, hipGetLastError());
   return ILQR_OK;
 }
@@ -1714,8 +1560,8 @@ static int enqueue_measured_x0(ilqr_hip_ctx* c, double* out) {
 // kernel selects y = a) is never computed; its beta reads 1.
 static int upload_actuator_blend(ilqr_hip_ctx* c) {
   const double h = c->P.dyn.h / c->plant_substeps;      // (the plant's step: plant_dyn)
-  c->act_beta.assign((size_t)c->act_sets * ILQR_NU, 1.0);
-  for (int s = 0; s < c->act_sets; ++s)
+  c->act_beta.assign((size_t)c->act.sets * ILQR_NU, 1.0);
+  for (int s = 0; s < c->act.sets; ++s)
     for (int i = 0; i < ILQR_NU; ++i) {
       const double tau = c->act_rec[(size_t)s * ILQR_PLANT_ACTUATOR + 1 + i];
       if (tau != 0.0) c->act_beta[(size_t)s * ILQR_NU + i] = -std::expm1(-h / tau);
@@ -1724,64 +1570,40 @@ static int upload_actuator_blend(ilqr_hip_ctx* c) {
   HIPCHK(c, hipMemcpy(c->d_act_beta, c->act_beta.data(), c->act_beta.size() * sizeof(double), hipMemcpyHostToDevice));
   return ILQR_OK;
 }
-static void enqueue_plant(ilqr_hip_ctx* c, const h1::DynParams& dyn, int geom, int first_knot, int count, bool follow, long row) {
+// The plant kernel of one call: without a table exactly the launch without the feature; with one, the followed kernel of the plan's family
+// with the tables' records -- for an advance over the one interval (0, 1), which is an advance bit for bit -- behind the draws the plan names.
+// Each family takes the tables of the ones before it, any of which may be null but the parameter record: the parameter table's or the
+// handle's own (plant_self_params).  row: the advance's ring row (-1: no ring) or the follow's first ring row.  The caller has loaded
+// plan.modules.
+static void enqueue_plant(ilqr_hip_ctx* c, const ilqr::PlantPlan& plan, const h1::DynParams& dyn, int geom, int first_knot, int count, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  if (c->d_pjoints && !c->joints_nominal) {      // the joints family: the actuator family's superset (each of its tables may be null)
-    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
-    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
-    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
-    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
-    if (c->d_pobs) {      // (the callers have checked every module this branch calls: plant_need_modules)
-      const ilqr::ObservationTable O = observation_table(c);
-      observe_module().draw(c->B, &O, c->plant_intervals, count, c->d_obs_delta, c->stream);
-    }
-    if (c->d_pact) actuator_module().draw(c->B, c->act_seed, c->act_stream0, c->plant_intervals, count, c->d_act_z, c->stream);
-    const bool one = c->act_sets == 1;
-    const ilqr::ActuatorTable A{c->d_pact, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
-    const ilqr::JointTable J{c->d_pjoints, c->joints_sets == 1 ? 0 : JOINT_REC};
-    joints_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, c->d_pobs ? c->d_obs_delta : nullptr, &A, &J, &a, c->stream);
-    if (c->d_pact) c->act_substeps += (long)count * c->plant_substeps;
-  } else if (c->d_pact) {      // the actuator family: the observation family's superset (each of its tables may be null) behind the draw(s) of the call's intervals
-    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
-    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
-    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
-    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
-    if (c->d_pobs) {      // (the callers have checked both modules: need_observe_module, need_actuator_module)
-      const ilqr::ObservationTable O = observation_table(c);
-      observe_module().draw(c->B, &O, c->plant_intervals, count, c->d_obs_delta, c->stream);
-    }
-    actuator_module().draw(c->B, c->act_seed, c->act_stream0, c->plant_intervals, count, c->d_act_z, c->stream);
-    const bool one = c->act_sets == 1;
-    const ilqr::ActuatorTable A{c->d_pact, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
-    actuator_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, c->d_pobs ? c->d_obs_delta : nullptr, &A, &a, c->stream);
-    c->act_substeps += (long)count * c->plant_substeps;
-  } else if (c->d_pobs) {      // the observation family: the payload family's superset (either table may be null) behind the draw of the call's error rows
-    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
-    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
-    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
-    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
-    const ilqr::ObservationTable O = observation_table(c);
-    observe_module().draw(c->B, &O, c->plant_intervals, count, c->d_obs_delta, c->stream);      // (the callers have checked the module: need_observe_module)
-    observe_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, c->d_obs_delta, &a, c->stream);
-  } else if (c->d_ppayload) {      // the payload family: parameter record, wrench (none: a null table) and payload together
-    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
-    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
-    const ilqr::PayloadTable M{c->d_ppayload, c->payload_sets == 1 ? 0 : PAYLOAD_REC};
-    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
-    payload_module().follow(&c->S, &c->plant, &dyn, &T, &W, &M, &a, c->stream);      // (the callers have checked the module: need_payload_module)
-  } else if (c->d_wrench) {
-    const ilqr::PlantTable T = c->d_pparams ? ilqr::PlantTable{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
-    const ilqr::WrenchTable W{c->d_wrench, c->wrench_sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
-    const ilqr::WrenchFollowArgs a{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
-    wrench_module().follow(&c->S, &c->plant, &dyn, &T, &W, &a, c->stream);      // (loaded by ilqr_hip_plant_set_wrench, which installed the table)
-  } else if (c->d_pparams) {
-    const ilqr::PlantTable T{c->d_pparams, c->pparams_sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1};
-    ilqr::launch_plant_follow_params(c->S, c->plant, dyn, T, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, c->hist_cap, c->stream);
-  } else if (follow) {
-    ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row, c->hist_cap, c->stream);
-  } else {
-    ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, row, c->stream);
+  const ilqr::PlantTable T = c->pparams.d ? ilqr::PlantTable{c->pparams.d, c->pparams.sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+  const auto W = ilqr::WrenchTable{c->wrench.d, c->wrench.sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+  const auto M = ilqr::PayloadTable{c->payload.d, c->payload.sets == 1 ? 0 : PAYLOAD_REC};
+  const bool one = c->act.sets == 1;
+  const auto A = ilqr::ActuatorTable{c->act.d, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
+  const auto J = ilqr::JointTable{c->joints.d, c->joints.sets == 1 ? 0 : JOINT_REC};
+  const auto a = ilqr::WrenchFollowArgs{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+  const double* delta = plan.draw_observation ? c->d_obs_delta : nullptr;
+  if (plan.draw_observation) enqueue_observation_draw(c, c->plant_intervals, count);
+  if (plan.draw_actuator) enqueue_actuator_draw(c, c->plant_intervals, count);
+  switch (plan.family) {
+    case ilqr::PLANT_JOINTS: module_fn<ilqr::joints_follow_fn>(ilqr::MOD_JOINTS, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &J, &a, c->stream); break;
+    case ilqr::PLANT_ACTUATOR: module_fn<ilqr::actuator_follow_fn>(ilqr::MOD_ACTUATOR, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &a, c->stream); break;
+    case ilqr::PLANT_OBSERVE: module_fn<ilqr::observe_follow_fn>(ilqr::MOD_OBSERVE, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &a, c->stream); break;
+    case ilqr::PLANT_PAYLOAD: module_fn<ilqr::payload_follow_fn>(ilqr::MOD_PAYLOAD, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, &a, c->stream); break;
+    case ilqr::PLANT_WRENCH: module_fn<ilqr::wrench_follow_fn>(ilqr::MOD_WRENCH, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &a, c->stream); break;
+    case ilqr::PLANT_PARAMS: ilqr::launch_plant_follow_params(c->S, c->plant, dyn, T, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, a.hist_row0, c->hist_cap, c->stream); break;
+    case ilqr::PLANT_FOLLOW: ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row, c->hist_cap, c->stream); break;
+    case ilqr::PLANT_ADVANCE: ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, row, c->stream); break;
   }
+  if (plan.draw_actuator) c->act_substeps += (long)count * c->plant_substeps;
+}
+// what ilqr_hip_plant_advance and ilqr_hip_plant_follow do in front of enqueue_plant: the handle's own parameter record and every module of the plan
+static int prepare_plant(ilqr_hip_ctx* c, const ilqr::PlantPlan& plan) {
+  if (plan.self_params) TRY(plant_self_params(c));
+  for (int m = 0; m < ilqr::PLANT_MODULES; ++m) if ((plan.modules >> m) & 1u) TRY(need_module(c, m));
+  return ILQR_OK;
 }
 int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   if (!c || !x) return ILQR_ERR_ARG;
@@ -1808,7 +1630,7 @@ int ilqr_hip_plant_configure(ilqr_hip_ctx* c, int substeps, int feedback_mode, i
   const bool new_h = substeps != c->plant_substeps;
   c->plant_substeps = substeps; c->plant_feedback = feedback_mode; c->plant_source = contact_source;
   c->act_substeps = 0;      // (the actuator's state is primed again by the next substep)
-  if (c->d_pact && new_h) TRY(upload_actuator_blend(c));      // (beta depends on h = dt / substeps)
+  if (c->act.d && new_h) TRY(upload_actuator_blend(c));      // (beta depends on h = dt / substeps)
   return ILQR_OK;
 }
 int ilqr_hip_plant_kick(ilqr_hip_ctx* c, const double* dv) {
@@ -1828,14 +1650,11 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
     if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
   if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
-  TRY(plant_self_params(c));
-  if (c->d_pjoints && !c->joints_nominal) TRY(need_joints_module(c));
-  if (c->d_pact) TRY(need_actuator_module(c));
-  if (c->d_pobs) TRY(need_observe_module(c));
-  else if (c->d_ppayload && !c->d_pact && !(c->d_pjoints && !c->joints_nominal)) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  const ilqr::PlantPlan plan = plant_plan_of(c, false);
+  TRY(prepare_plant(c, plan));
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
-  enqueue_plant(c, dyn, geom ? 1 : 0, 0, 1, false, row);
+  enqueue_plant(c, plan, dyn, geom ? 1 : 0, 0, 1, row);
   if (c->score_on) enqueue_score(c, row, 0, 1);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
@@ -1869,14 +1688,11 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
     c->err = "plant_follow with a score installed: " + std::to_string(count) + " intervals exceed the history ring's " + std::to_string(c->hist_cap) + " rows (the score kernels read the ring's rows)";
     return ILQR_ERR_STATE;
   }
-  TRY(plant_self_params(c));
-  if (c->d_pjoints && !c->joints_nominal) TRY(need_joints_module(c));
-  if (c->d_pact) TRY(need_actuator_module(c));
-  if (c->d_pobs) TRY(need_observe_module(c));
-  else if (c->d_ppayload && !c->d_pact && !(c->d_pjoints && !c->joints_nominal)) TRY(need_payload_module(c));      // (enqueue_plant calls into the module: an error here, never a null call)
+  const ilqr::PlantPlan plan = plant_plan_of(c, true);
+  TRY(prepare_plant(c, plan));
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
-  enqueue_plant(c, dyn, geom ? 1 : 0, first_knot, count, true, row0);
+  enqueue_plant(c, plan, dyn, geom ? 1 : 0, first_knot, count, row0);
   if (c->score_on) enqueue_score(c, row0, first_knot, count);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
@@ -1949,41 +1765,64 @@ int ilqr_hip_plant_set_model(ilqr_hip_ctx* c, int contact_mode, int joint_limits
   c->plant_mode = contact_mode; c->plant_limits = joint_limits;
   return ILQR_OK;
 }
+// ---- what the entry points of the six tables share (ilqr_hip_ctx::TableBuf); their argument checks, their no-table values and whatever else is
+// specific to a table stay with them
+using TableBuf = ilqr_hip_ctx::TableBuf;
+// installs n_sets records of `values` doubles, padded with zeros to `rec` doubles on the device
+static int table_install(ilqr_hip_ctx* c, TableBuf* t, const double* v, int n_sets, int values, int rec) {
+  std::vector<double> padded;
+  if (rec != values) {
+    padded.assign((size_t)n_sets * rec, 0.0);
+    for (int s = 0; s < n_sets; ++s) std::memcpy(padded.data() + (size_t)s * rec, v + (size_t)s * values, values * sizeof(double));
+    v = padded.data();
+  }
+  const size_t bytes = (size_t)n_sets * rec * sizeof(double);
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
+  if (t->d && t->sets != n_sets) { hipFree(t->d); t->d = nullptr; t->sets = 0; }
+  if (!t->d) HIPCHK(c, hipMalloc((void**)&t->d, bytes));
+  t->sets = n_sets;
+  HIPCHK(c, hipMemcpyAsync(t->d, v, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+static int table_clear(ilqr_hip_ctx* c, TableBuf* t) {
+  if (t->d) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
+    hipFree(t->d);
+  }
+  t->d = nullptr; t->sets = 0;
+  return ILQR_OK;
+}
+// the installed table as [B][values]: one record for all is repeated
+static int table_read(ilqr_hip_ctx* c, const TableBuf& t, double* out, int values, int rec) {
+  std::vector<double> r((size_t)t.sets * rec);
+  HIPCHK(c, hipMemcpyAsync(r.data(), t.d, r.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->B; ++b) std::memcpy(out + (size_t)b * values, r.data() + (size_t)(t.sets == 1 ? 0 : b) * rec, values * sizeof(double));
+  return ILQR_OK;
+}
 int ilqr_hip_plant_set_params(ilqr_hip_ctx* c, const double* params, int n_sets) {
   if (!c || !params || n_sets < 1 || check_sets(c, n_sets)) return ILQR_ERR_ARG;
-  constexpr int P = ILQR_PLANT_PARAMS, REC = ILQR_PLANT_PARAMS + 1;
+  constexpr int P = ILQR_PLANT_PARAMS;
   for (size_t i = 0; i < (size_t)n_sets * P; ++i) if (!std::isfinite(params[i])) return ILQR_ERR_ARG;
   for (int s = 0; s < n_sets; ++s) {
     const double* r = params + (size_t)s * P;
     if (r[3] < 0.0 || !(r[4] > 0.0) || r[5] < 0.0 || r[6] < 0.0) return ILQR_ERR_ARG;
   }
   enter(c);
-  std::vector<double> rec((size_t)n_sets * REC, 0.0);      // (64-byte records: the seven values and one double of padding)
-  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * REC, params + (size_t)s * P, P * sizeof(double));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
-  if (c->d_pparams && c->pparams_sets != n_sets) { hipFree(c->d_pparams); c->d_pparams = nullptr; c->pparams_sets = 0; }
-  if (!c->d_pparams) HIPCHK(c, hipMalloc((void**)&c->d_pparams, rec.size() * sizeof(double)));
-  c->pparams_sets = n_sets;
-  HIPCHK(c, hipMemcpyAsync(c->d_pparams, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
+  return table_install(c, &c->pparams, params, n_sets, P, P + 1);      // (64-byte records: the seven values and one double of padding)
 }
 int ilqr_hip_plant_clear_params(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (c->d_pparams) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
-    hipFree(c->d_pparams);
-  }
-  c->d_pparams = nullptr; c->pparams_sets = 0;
-  return ILQR_OK;
+  return table_clear(c, &c->pparams);
 }
-int ilqr_hip_plant_num_param_sets(const ilqr_hip_ctx* c) { return c ? c->pparams_sets : -1; }
+int ilqr_hip_plant_num_param_sets(const ilqr_hip_ctx* c) { return c ? c->pparams.sets : -1; }
 int ilqr_hip_plant_get_params(ilqr_hip_ctx* c, double* params) {
   if (!c || !params) return ILQR_ERR_ARG;
   enter(c);
-  constexpr int P = ILQR_PLANT_PARAMS, REC = ILQR_PLANT_PARAMS + 1;
-  if (!c->d_pparams) {
+  constexpr int P = ILQR_PLANT_PARAMS;
+  if (!c->pparams.d) {
     const h1::DynParams& d = c->P.dyn;
     for (int b = 0; b < c->B; ++b) {
       double* r = params + (size_t)b * P;
@@ -1991,11 +1830,7 @@ int ilqr_hip_plant_get_params(ilqr_hip_ctx* c, double* params) {
     }
     return ILQR_OK;
   }
-  std::vector<double> rec((size_t)c->pparams_sets * REC);
-  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pparams, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(params + (size_t)b * P, rec.data() + (size_t)(c->pparams_sets == 1 ? 0 : b) * REC, P * sizeof(double));
-  return ILQR_OK;
+  return table_read(c, c->pparams, params, P, P + 1);
 }
 // ---- external wrench on the pelvis per rollout (plant_kernels.hip k_plant_follow_w, k_step_w)
 // the checks of a wrench record that need no handle: every entry finite but end = +inf, first / end non-negative integers, first <= end
@@ -2011,76 +1846,25 @@ int ilqr_hip_plant_set_wrench(ilqr_hip_ctx* c, const double* wrench, int n_sets)
   for (int s = 0; s < n_sets; ++s) if (!wrench_values_ok(wrench + (size_t)s * ILQR_PLANT_WRENCH, ILQR_PLANT_WRENCH)) return ILQR_ERR_ARG;
   if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   enter(c);
-  TRY(need_wrench_module(c));
-  std::vector<double> rec((size_t)n_sets * WRENCH_REC, 0.0);      // (128-byte records: the eleven values and five doubles of padding)
-  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * WRENCH_REC, wrench + (size_t)s * ILQR_PLANT_WRENCH, ILQR_PLANT_WRENCH * sizeof(double));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
-  if (c->d_wrench && c->wrench_sets != n_sets) { hipFree(c->d_wrench); c->d_wrench = nullptr; c->wrench_sets = 0; }
-  if (!c->d_wrench) HIPCHK(c, hipMalloc((void**)&c->d_wrench, rec.size() * sizeof(double)));
-  c->wrench_sets = n_sets;
-  HIPCHK(c, hipMemcpyAsync(c->d_wrench, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
+  TRY(need_module(c, ilqr::MOD_WRENCH));
+  return table_install(c, &c->wrench, wrench, n_sets, ILQR_PLANT_WRENCH, WRENCH_REC);      // (128-byte records: the eleven values and five doubles of padding)
 }
 int ilqr_hip_plant_clear_wrench(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (c->d_wrench) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
-    hipFree(c->d_wrench);
-  }
-  c->d_wrench = nullptr; c->wrench_sets = 0;
-  return ILQR_OK;
+  return table_clear(c, &c->wrench);
 }
-int ilqr_hip_plant_num_wrench_sets(const ilqr_hip_ctx* c) { return c ? c->wrench_sets : -1; }
+int ilqr_hip_plant_num_wrench_sets(const ilqr_hip_ctx* c) { return c ? c->wrench.sets : -1; }
 int ilqr_hip_plant_get_wrench(ilqr_hip_ctx* c, double* wrench) {
   if (!c || !wrench) return ILQR_ERR_ARG;
   enter(c);
-  constexpr int P = ILQR_PLANT_WRENCH;
-  if (!c->d_wrench) {      // (no table: no wrench, an empty window)
-    std::fill(wrench, wrench + (size_t)c->B * P, 0.0);
+  if (!c->wrench.d) {      // (no table: no wrench, an empty window)
+    std::fill(wrench, wrench + (size_t)c->B * ILQR_PLANT_WRENCH, 0.0);
     return ILQR_OK;
   }
-  std::vector<double> rec((size_t)c->wrench_sets * WRENCH_REC);
-  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_wrench, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(wrench + (size_t)b * P, rec.data() + (size_t)(c->wrench_sets == 1 ? 0 : b) * WRENCH_REC, P * sizeof(double));
-  return ILQR_OK;
+  return table_read(c, c->wrench, wrench, ILQR_PLANT_WRENCH, WRENCH_REC);
 }
 long ilqr_hip_plant_intervals(const ilqr_hip_ctx* c) { return c ? c->plant_intervals : -1L; }
-int ilqr_hip_step_wrench(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, double* x_next) {
-  if (count <= 0 || !x || !u || !wrench || !x_next) return ILQR_ERR_ARG;
-  for (int i = 0; i < count; ++i) if (!wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
-  if (!c) return ILQR_ERR_ARG;
-  TRY(enter_launching(c));
-  TRY(need_wrench_module(c));
-  if ((size_t)count > c->step_w_cap) {
-    if (c->d_stepw) hipFree(c->d_stepw);
-    c->d_stepw = nullptr; c->step_w_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepw, (size_t)count * 9 * sizeof(double)));
-    c->step_w_cap = (size_t)count;
-  }
-  if ((size_t)count > c->step_cap) {      // (the scratch of plant_step, grown the same way)
-    if (c->d_stepx) hipFree(c->d_stepx);
-    if (c->d_stepu) hipFree(c->d_stepu);
-    if (c->d_stepn) hipFree(c->d_stepn);
-    if (c->d_stance_out) hipFree(c->d_stance_out);
-    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
-    c->step_cap = (size_t)count;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, (size_t)count * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  wrench_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, c->d_stepw, c->stream);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
-}
 // ---- rigid payload on the pelvis per rollout (plant_kernels.hip k_plant_follow_m, k_step_m)
 // the checks of a payload record that need no handle: every entry finite, m >= 0, Ic positive semidefinite -- its seven principal minors
 // non-negative up to rounding (relative to the products they are differences of)
@@ -2100,84 +1884,23 @@ int ilqr_hip_plant_set_payload(ilqr_hip_ctx* c, const double* payload, int n_set
   for (int s = 0; s < n_sets; ++s) if (!payload_values_ok(payload + (size_t)s * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
   if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   enter(c);
-  TRY(need_payload_module(c));
-  std::vector<double> rec((size_t)n_sets * PAYLOAD_REC, 0.0);      // (128-byte records: the ten values and six doubles of padding)
-  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * PAYLOAD_REC, payload + (size_t)s * ILQR_PLANT_PAYLOAD, ILQR_PLANT_PAYLOAD * sizeof(double));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
-  if (c->d_ppayload && c->payload_sets != n_sets) { hipFree(c->d_ppayload); c->d_ppayload = nullptr; c->payload_sets = 0; }
-  if (!c->d_ppayload) HIPCHK(c, hipMalloc((void**)&c->d_ppayload, rec.size() * sizeof(double)));
-  c->payload_sets = n_sets;
-  HIPCHK(c, hipMemcpyAsync(c->d_ppayload, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
+  TRY(need_module(c, ilqr::MOD_PAYLOAD));
+  return table_install(c, &c->payload, payload, n_sets, ILQR_PLANT_PAYLOAD, PAYLOAD_REC);      // (128-byte records: the ten values and six doubles of padding)
 }
 int ilqr_hip_plant_clear_payload(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (c->d_ppayload) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
-    hipFree(c->d_ppayload);
-  }
-  c->d_ppayload = nullptr; c->payload_sets = 0;
-  return ILQR_OK;
+  return table_clear(c, &c->payload);
 }
-int ilqr_hip_plant_num_payload_sets(const ilqr_hip_ctx* c) { return c ? c->payload_sets : -1; }
+int ilqr_hip_plant_num_payload_sets(const ilqr_hip_ctx* c) { return c ? c->payload.sets : -1; }
 int ilqr_hip_plant_get_payload(ilqr_hip_ctx* c, double* payload) {
   if (!c || !payload) return ILQR_ERR_ARG;
   enter(c);
-  constexpr int P = ILQR_PLANT_PAYLOAD;
-  if (!c->d_ppayload) {      // (no table: nothing carried)
-    std::fill(payload, payload + (size_t)c->B * P, 0.0);
+  if (!c->payload.d) {      // (no table: nothing carried)
+    std::fill(payload, payload + (size_t)c->B * ILQR_PLANT_PAYLOAD, 0.0);
     return ILQR_OK;
   }
-  std::vector<double> rec((size_t)c->payload_sets * PAYLOAD_REC);
-  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_ppayload, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(payload + (size_t)b * P, rec.data() + (size_t)(c->payload_sets == 1 ? 0 : b) * PAYLOAD_REC, P * sizeof(double));
-  return ILQR_OK;
-}
-int ilqr_hip_step_payload(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, const double* payload, double* x_next) {
-  if (count <= 0 || !x || !u || !payload || !x_next) return ILQR_ERR_ARG;
-  for (int i = 0; i < count; ++i) {
-    if (wrench && !wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
-    if (!payload_values_ok(payload + (size_t)i * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
-  }
-  if (!c) return ILQR_ERR_ARG;
-  TRY(enter_launching(c));
-  TRY(need_payload_module(c));
-  if (wrench && (size_t)count > c->step_w_cap) {
-    if (c->d_stepw) hipFree(c->d_stepw);
-    c->d_stepw = nullptr; c->step_w_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepw, (size_t)count * 9 * sizeof(double)));
-    c->step_w_cap = (size_t)count;
-  }
-  if ((size_t)count > c->step_m_cap) {
-    if (c->d_stepm) hipFree(c->d_stepm);
-    c->d_stepm = nullptr; c->step_m_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepm, (size_t)count * ILQR_PLANT_PAYLOAD * sizeof(double)));
-    c->step_m_cap = (size_t)count;
-  }
-  if ((size_t)count > c->step_cap) {      // (the scratch of plant_step, grown the same way)
-    if (c->d_stepx) hipFree(c->d_stepx);
-    if (c->d_stepu) hipFree(c->d_stepu);
-    if (c->d_stepn) hipFree(c->d_stepn);
-    if (c->d_stance_out) hipFree(c->d_stance_out);
-    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepx, (size_t)count * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepu, (size_t)count * ILQR_NU * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepn, (size_t)count * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, (size_t)count * 2 * sizeof(int)));
-    c->step_cap = (size_t)count;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, (size_t)count * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (wrench) HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, (size_t)count * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stepm, payload, (size_t)count * ILQR_PLANT_PAYLOAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  payload_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, wrench ? c->d_stepw : nullptr, c->d_stepm, c->stream);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, (size_t)count * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
+  return table_read(c, c->payload, payload, ILQR_PLANT_PAYLOAD, PAYLOAD_REC);
 }
 // ---- noisy and biased state observation per rollout (plant_kernels.hip k_observation_draw, k_observe_apply, k_plant_follow_o)
 int ilqr_hip_plant_set_observation(ilqr_hip_ctx* c, const double* obs, int n_sets, unsigned long long seed, unsigned long long stream0) {
@@ -2189,51 +1912,39 @@ int ilqr_hip_plant_set_observation(ilqr_hip_ctx* c, const double* obs, int n_set
   }
   if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   enter(c);
-  TRY(need_observe_module(c));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
-  if (c->d_pobs && c->obs_sets != n_sets) { hipFree(c->d_pobs); c->d_pobs = nullptr; c->obs_sets = 0; }
+  TRY(need_module(c, ilqr::MOD_OBSERVE));
   if (!c->d_obs_delta) HIPCHK(c, hipMalloc((void**)&c->d_obs_delta, (size_t)c->N * c->B * ILQR_NX * sizeof(double)));
   if (!c->d_obs_x) HIPCHK(c, hipMalloc((void**)&c->d_obs_x, (size_t)c->B * ILQR_NX * sizeof(double)));
-  if (!c->d_pobs) HIPCHK(c, hipMalloc((void**)&c->d_pobs, (size_t)n_sets * R * sizeof(double)));
-  c->obs_sets = n_sets; c->obs_seed = seed; c->obs_stream0 = stream0;
-  HIPCHK(c, hipMemcpyAsync(c->d_pobs, obs, (size_t)n_sets * R * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(table_install(c, &c->obs, obs, n_sets, R, R));
+  c->obs_seed = seed; c->obs_stream0 = stream0;
   return ILQR_OK;
 }
 int ilqr_hip_plant_clear_observation(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (c->d_pobs) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
-    hipFree(c->d_pobs);
-  }
-  c->d_pobs = nullptr; c->obs_sets = 0; c->obs_seed = 0; c->obs_stream0 = 0;
+  TRY(table_clear(c, &c->obs));
+  c->obs_seed = 0; c->obs_stream0 = 0;
   return ILQR_OK;
 }
-int ilqr_hip_plant_num_observation_sets(const ilqr_hip_ctx* c) { return c ? c->obs_sets : -1; }
+int ilqr_hip_plant_num_observation_sets(const ilqr_hip_ctx* c) { return c ? c->obs.sets : -1; }
 int ilqr_hip_plant_get_observation(ilqr_hip_ctx* c, double* obs, unsigned long long* seed, unsigned long long* stream0) {
   if (!c || !obs) return ILQR_ERR_ARG;
   enter(c);
   constexpr int R = ILQR_PLANT_OBSERVATION;
   if (seed) *seed = c->obs_seed;
   if (stream0) *stream0 = c->obs_stream0;
-  if (!c->d_pobs) {      // (no table: the controller sees the truth)
+  if (!c->obs.d) {      // (no table: the controller sees the truth)
     std::fill(obs, obs + (size_t)c->B * R, 0.0);
     return ILQR_OK;
   }
-  std::vector<double> rec((size_t)c->obs_sets * R);
-  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pobs, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(obs + (size_t)b * R, rec.data() + (size_t)(c->obs_sets == 1 ? 0 : b) * R, R * sizeof(double));
-  return ILQR_OK;
+  return table_read(c, c->obs, obs, R, R);
 }
 int ilqr_hip_plant_observation_errors(ilqr_hip_ctx* c, long interval0, int count, double* delta) {
   if (!c || !delta || interval0 < 0 || count < 1 || count > c->N) return ILQR_ERR_ARG;
-  if (!c->d_pobs) { c->err = "plant_observation_errors without an observation table (ilqr_hip_plant_set_observation)"; return ILQR_ERR_STATE; }
+  if (!c->obs.d) { c->err = "plant_observation_errors without an observation table (ilqr_hip_plant_set_observation)"; return ILQR_ERR_STATE; }
   TRY(enter_launching(c));
-  TRY(need_observe_module(c));
-  const ilqr::ObservationTable O = observation_table(c);
-  observe_module().draw(c->B, &O, interval0, count, c->d_obs_delta, c->stream);      // (the buffer of the plant calls: they draw again in front of every use)
+  TRY(need_module(c, ilqr::MOD_OBSERVE));
+  enqueue_observation_draw(c, interval0, count);      // (the buffer of the plant calls: they draw again in front of every use)
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(delta, c->d_obs_delta, (size_t)count * c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2242,7 +1953,7 @@ int ilqr_hip_plant_observation_errors(ilqr_hip_ctx* c, long interval0, int count
 int ilqr_hip_plant_get_observed(ilqr_hip_ctx* c, double* x_obs) {
   if (!c || !x_obs) return ILQR_ERR_ARG;
   if (!c->plant_set) return ILQR_ERR_STATE;
-  if (!c->d_pobs) return ilqr_hip_plant_get_state(c, x_obs);
+  if (!c->obs.d) return ilqr_hip_plant_get_state(c, x_obs);
   TRY(enter_launching(c));
   TRY(enqueue_measured_x0(c, c->d_obs_x));
   HIPCHK(c, hipMemcpyAsync(x_obs, c->d_obs_x, (size_t)c->B * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2259,66 +1970,56 @@ int ilqr_hip_plant_set_actuator(ilqr_hip_ctx* c, const double* act, int n_sets, 
   }
   if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   enter(c);
-  TRY(need_actuator_module(c));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
-  if (c->d_pact && c->act_sets != n_sets) { hipFree(c->d_pact); hipFree(c->d_act_beta); c->d_pact = c->d_act_beta = nullptr; c->act_sets = 0; }
+  TRY(need_module(c, ilqr::MOD_ACTUATOR));
+  const bool resized = c->act.d && c->act.sets != n_sets;
+  TRY(table_install(c, &c->act, act, n_sets, R, R));
+  if (resized) { hipFree(c->d_act_beta); c->d_act_beta = nullptr; }      // (the blend rows follow the table's size; nothing is in flight behind table_install)
   const size_t bu = (size_t)c->B * ILQR_NU;
   if (!c->d_act_z) HIPCHK(c, hipMalloc((void**)&c->d_act_z, (size_t)c->N * bu * sizeof(double)));
   if (!c->d_act_fifo) HIPCHK(c, hipMalloc((void**)&c->d_act_fifo, (size_t)(ILQR_PLANT_ACTUATOR_MAX_DELAY + 1) * bu * sizeof(double)));
   if (!c->d_act_y) HIPCHK(c, hipMalloc((void**)&c->d_act_y, bu * sizeof(double)));
   if (!c->d_act_applied) { HIPCHK(c, hipMalloc((void**)&c->d_act_applied, bu * sizeof(double))); HIPCHK(c, hipMemsetAsync(c->d_act_applied, 0, bu * sizeof(double), c->stream)); }
   if (!c->d_act_beta) HIPCHK(c, hipMalloc((void**)&c->d_act_beta, (size_t)n_sets * ILQR_NU * sizeof(double)));
-  if (!c->d_pact) HIPCHK(c, hipMalloc((void**)&c->d_pact, (size_t)n_sets * R * sizeof(double)));
-  c->act_sets = n_sets; c->act_seed = seed; c->act_stream0 = stream0;
+  c->act_seed = seed; c->act_stream0 = stream0;
   c->act_rec.assign(act, act + (size_t)n_sets * R);
   c->act_substeps = 0;      // (the actuator's state is primed again by the next substep)
-  HIPCHK(c, hipMemcpyAsync(c->d_pact, act, (size_t)n_sets * R * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return upload_actuator_blend(c);      // (synchronises the stream)
 }
 int ilqr_hip_plant_clear_actuator(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  if (c->d_pact) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
-    hipFree(c->d_pact); hipFree(c->d_act_beta);
-  }
-  c->d_pact = c->d_act_beta = nullptr; c->act_sets = 0; c->act_seed = 0; c->act_stream0 = 0; c->act_substeps = 0;
+  const bool installed = c->act.d != nullptr;
+  TRY(table_clear(c, &c->act));
+  if (installed) hipFree(c->d_act_beta);
+  c->d_act_beta = nullptr; c->act_seed = 0; c->act_stream0 = 0; c->act_substeps = 0;
   c->act_rec.clear(); c->act_beta.clear();
   return ILQR_OK;
 }
-int ilqr_hip_plant_num_actuator_sets(const ilqr_hip_ctx* c) { return c ? c->act_sets : -1; }
+int ilqr_hip_plant_num_actuator_sets(const ilqr_hip_ctx* c) { return c ? c->act.sets : -1; }
 int ilqr_hip_plant_get_actuator(ilqr_hip_ctx* c, double* act, unsigned long long* seed, unsigned long long* stream0) {
   if (!c || !act) return ILQR_ERR_ARG;
   enter(c);
   constexpr int R = ILQR_PLANT_ACTUATOR;
   if (seed) *seed = c->act_seed;
   if (stream0) *stream0 = c->act_stream0;
-  if (!c->d_pact) {      // (no table: the command is the torque)
+  if (!c->act.d) {      // (no table: the command is the torque)
     std::fill(act, act + (size_t)c->B * R, 0.0);
     return ILQR_OK;
   }
-  std::vector<double> rec((size_t)c->act_sets * R);
-  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pact, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(act + (size_t)b * R, rec.data() + (size_t)(c->act_sets == 1 ? 0 : b) * R, R * sizeof(double));
-  return ILQR_OK;
+  return table_read(c, c->act, act, R, R);
 }
 int ilqr_hip_plant_get_actuator_blend(ilqr_hip_ctx* c, double* beta) {
   if (!c || !beta) return ILQR_ERR_ARG;
   enter(c);
-  if (!c->d_pact) { c->err = "plant_get_actuator_blend without an actuator table (ilqr_hip_plant_set_actuator)"; return ILQR_ERR_STATE; }
-  std::vector<double> rows((size_t)c->act_sets * ILQR_NU);      // (from the device: the rows the kernel reads)
-  HIPCHK(c, hipMemcpyAsync(rows.data(), c->d_act_beta, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(beta + (size_t)b * ILQR_NU, rows.data() + (size_t)(c->act_sets == 1 ? 0 : b) * ILQR_NU, ILQR_NU * sizeof(double));
-  return ILQR_OK;
+  if (!c->act.d) { c->err = "plant_get_actuator_blend without an actuator table (ilqr_hip_plant_set_actuator)"; return ILQR_ERR_STATE; }
+  return table_read(c, TableBuf{c->d_act_beta, c->act.sets}, beta, ILQR_NU, ILQR_NU);      // (from the device: the rows the kernel reads)
 }
 int ilqr_hip_plant_actuator_draws(ilqr_hip_ctx* c, long interval0, int count, double* z) {
   if (!c || !z || interval0 < 0 || count < 1 || count > c->N) return ILQR_ERR_ARG;
-  if (!c->d_pact) { c->err = "plant_actuator_draws without an actuator table (ilqr_hip_plant_set_actuator)"; return ILQR_ERR_STATE; }
+  if (!c->act.d) { c->err = "plant_actuator_draws without an actuator table (ilqr_hip_plant_set_actuator)"; return ILQR_ERR_STATE; }
   TRY(enter_launching(c));
-  TRY(need_actuator_module(c));
-  actuator_module().draw(c->B, c->act_seed, c->act_stream0, interval0, count, c->d_act_z, c->stream);      // (the buffer of the plant calls: they draw again in front of every use)
+  TRY(need_module(c, ilqr::MOD_ACTUATOR));
+  enqueue_actuator_draw(c, interval0, count);      // (the buffer of the plant calls: they draw again in front of every use)
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(z, c->d_act_z, (size_t)count * c->B * ILQR_NU * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2327,7 +2028,7 @@ int ilqr_hip_plant_actuator_draws(ilqr_hip_ctx* c, long interval0, int count, do
 int ilqr_hip_plant_get_applied(ilqr_hip_ctx* c, double* tau) {
   if (!c || !tau) return ILQR_ERR_ARG;
   if (!c->plant_set) return ILQR_ERR_STATE;
-  if (!c->d_pact) return ilqr_hip_plant_get_control(c, tau);
+  if (!c->act.d) return ilqr_hip_plant_get_control(c, tau);
   enter(c);
   HIPCHK(c, hipMemcpyAsync(tau, c->d_act_applied, (size_t)c->B * ILQR_NU * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2344,53 +2045,72 @@ int ilqr_hip_plant_set_joints(ilqr_hip_ctx* c, const double* joints, int n_sets)
   if (!joints || n_sets == 0) {      // clears
     if (joints || n_sets != 0) return ILQR_ERR_ARG;
     enter(c);
-    if (c->d_pjoints) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read it)
-      hipFree(c->d_pjoints);
-    }
-    c->d_pjoints = nullptr; c->joints_sets = 0; c->joints_nominal = false;
+    TRY(table_clear(c, &c->joints));
+    c->joints_nominal = false;
     return ILQR_OK;
   }
   if (n_sets < 1 || !joint_values_ok(joints, (size_t)n_sets * P) || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   enter(c);
-  TRY(need_joints_module(c));
-  std::vector<double> rec((size_t)n_sets * JOINT_REC, 0.0);      // (640-byte records: the 76 values and four doubles of padding)
+  TRY(need_module(c, ilqr::MOD_JOINTS));
   bool nominal = true;
   for (int s = 0; s < n_sets; ++s) {
     const double* r = joints + (size_t)s * P;
-    std::memcpy(rec.data() + (size_t)s * JOINT_REC, r, P * sizeof(double));
     for (int i = 0; i < ILQR_NU; ++i) nominal = nominal && r[i] == 1.0 && r[ILQR_NU + i] == 1.0 && r[2 * ILQR_NU + i] == 1.0 && r[3 * ILQR_NU + i] == 0.1;
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
-  if (c->d_pjoints && c->joints_sets != n_sets) { hipFree(c->d_pjoints); c->d_pjoints = nullptr; c->joints_sets = 0; }
-  if (!c->d_pjoints) HIPCHK(c, hipMalloc((void**)&c->d_pjoints, rec.size() * sizeof(double)));
-  c->joints_sets = n_sets; c->joints_nominal = nominal;
-  HIPCHK(c, hipMemcpyAsync(c->d_pjoints, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(table_install(c, &c->joints, joints, n_sets, P, JOINT_REC));      // (640-byte records: the 76 values and four doubles of padding)
+  c->joints_nominal = nominal;
   return ILQR_OK;
 }
 int ilqr_hip_plant_get_joints(ilqr_hip_ctx* c, double* joints) {
   if (!c || !joints) return ILQR_ERR_ARG;
   enter(c);
   constexpr int P = ILQR_PLANT_JOINTS;
-  if (!c->d_pjoints) {      // (no table: the model's joints)
+  if (!c->joints.d) {      // (no table: the model's joints)
     for (size_t i = 0; i < (size_t)c->B * P; ++i) joints[i] = i % P < 3 * ILQR_NU ? 1.0 : 0.1;
     return ILQR_OK;
   }
-  std::vector<double> rec((size_t)c->joints_sets * JOINT_REC);
-  HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_pjoints, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return table_read(c, c->joints, joints, P, JOINT_REC);
+}
+// ---- single steps under a wrench, a payload and a joint record per item: ONE body behind the argument checks of the three entry points.
+// `which` is the entry point's own module, whose step kernel runs (k_step_w / k_step_m / k_step_j); it takes the arrays of the modules before
+// it, of which `wrench` and `payload` may be null where the entry point allows it.
+static int step_in_module(ilqr_hip_ctx* c, ilqr::PlantModule which, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, const double* payload,
+                          const double* joints, double* x_next) {
+  TRY(enter_launching(c));
+  TRY(need_module(c, which));
+  const size_t n = (size_t)count;
+  if (wrench) TRY(grow_step_buffer(c, &c->d_stepw, &c->step_w_cap, n, 9));
+  if (payload) TRY(grow_step_buffer(c, &c->d_stepm, &c->step_m_cap, n, ILQR_PLANT_PAYLOAD));
+  if (joints) TRY(grow_step_buffer(c, &c->d_stepj, &c->step_j_cap, n, ILQR_PLANT_JOINTS));
+  TRY(grow_step_scratch(c, count));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, n * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, n * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (wrench) HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, n * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (payload) HIPCHK(c, hipMemcpyAsync(c->d_stepm, payload, n * ILQR_PLANT_PAYLOAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (joints) HIPCHK(c, hipMemcpyAsync(c->d_stepj, joints, n * ILQR_PLANT_JOINTS * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  const double *w = wrench ? c->d_stepw : nullptr, *m = payload ? c->d_stepm : nullptr;
+  if (which == ilqr::MOD_WRENCH) module_fn<ilqr::wrench_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, c->stream);
+  else if (which == ilqr::MOD_PAYLOAD) module_fn<ilqr::payload_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, m, c->stream);
+  else module_fn<ilqr::joints_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, m, c->d_stepj, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, n * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int b = 0; b < c->B; ++b) std::memcpy(joints + (size_t)b * P, rec.data() + (size_t)(c->joints_sets == 1 ? 0 : b) * JOINT_REC, P * sizeof(double));
   return ILQR_OK;
 }
-// grows a scratch buffer of the single-step calls to `count` rows of `width` doubles
-static int grow_step_buffer(ilqr_hip_ctx* c, double** p, size_t* cap, size_t count, size_t width) {
-  if (count <= *cap) return ILQR_OK;
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIPCHK(c, hipMalloc((void**)p, count * width * sizeof(double)));
-  *cap = count;
-  return ILQR_OK;
+int ilqr_hip_step_wrench(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, double* x_next) {
+  if (count <= 0 || !x || !u || !wrench || !x_next) return ILQR_ERR_ARG;
+  for (int i = 0; i < count; ++i) if (!wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
+  if (!c) return ILQR_ERR_ARG;
+  return step_in_module(c, ilqr::MOD_WRENCH, count, x, u, stance_left, stance_right, wrench, nullptr, nullptr, x_next);
+}
+int ilqr_hip_step_payload(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, const double* payload, double* x_next) {
+  if (count <= 0 || !x || !u || !payload || !x_next) return ILQR_ERR_ARG;
+  for (int i = 0; i < count; ++i) {
+    if (wrench && !wrench_values_ok(wrench + (size_t)i * 9, 9)) return ILQR_ERR_ARG;
+    if (!payload_values_ok(payload + (size_t)i * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
+  }
+  if (!c) return ILQR_ERR_ARG;
+  return step_in_module(c, ilqr::MOD_PAYLOAD, count, x, u, stance_left, stance_right, wrench, payload, nullptr, x_next);
 }
 int ilqr_hip_step_joints(ilqr_hip_ctx* c, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench, const double* payload, const double* joints,
                          double* x_next) {
@@ -2400,34 +2120,7 @@ int ilqr_hip_step_joints(ilqr_hip_ctx* c, int count, const double* x, const doub
     if (payload && !payload_values_ok(payload + (size_t)i * ILQR_PLANT_PAYLOAD)) return ILQR_ERR_ARG;
   }
   if (!joint_values_ok(joints, (size_t)count * ILQR_PLANT_JOINTS) || !c) return ILQR_ERR_ARG;
-  TRY(enter_launching(c));
-  TRY(need_joints_module(c));
-  const size_t n = (size_t)count;
-  if (wrench) TRY(grow_step_buffer(c, &c->d_stepw, &c->step_w_cap, n, 9));
-  if (payload) TRY(grow_step_buffer(c, &c->d_stepm, &c->step_m_cap, n, ILQR_PLANT_PAYLOAD));
-  TRY(grow_step_buffer(c, &c->d_stepj, &c->step_j_cap, n, ILQR_PLANT_JOINTS));
-  if (n > c->step_cap) {      // (the scratch of plant_step, grown the same way)
-    if (c->d_stepx) hipFree(c->d_stepx);
-    if (c->d_stepu) hipFree(c->d_stepu);
-    if (c->d_stepn) hipFree(c->d_stepn);
-    if (c->d_stance_out) hipFree(c->d_stance_out);
-    c->d_stepx = c->d_stepu = c->d_stepn = nullptr; c->d_stance_out = nullptr; c->step_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_stepx, n * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepu, n * ILQR_NU * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stepn, n * ILQR_NX * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_stance_out, n * 2 * sizeof(int)));
-    c->step_cap = n;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, n * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, n * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (wrench) HIPCHK(c, hipMemcpyAsync(c->d_stepw, wrench, n * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (payload) HIPCHK(c, hipMemcpyAsync(c->d_stepm, payload, n * ILQR_PLANT_PAYLOAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stepj, joints, n * ILQR_PLANT_JOINTS * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  joints_module().step(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, wrench ? c->d_stepw : nullptr, payload ? c->d_stepm : nullptr, c->d_stepj, c->stream);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, n * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
+  return step_in_module(c, ilqr::MOD_JOINTS, count, x, u, stance_left, stance_right, wrench, payload, joints, x_next);
 }
 void ilqr_hip_pelvis_inertial_offset(double r[3]) {
   if (r) h1host::pelvis_inertial_offset(r);      // (host table: the model constants of this translation unit are device constants)

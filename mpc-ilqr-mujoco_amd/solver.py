@@ -112,6 +112,26 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(_dp)
 
 
+def _table(a, B, width, what):
+    """a per-rollout table as [n_sets, width] doubles, n_sets 1 or B (one record may come one-dimensional); `what` names it in the error"""
+    a = _c64(a)
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2 or a.shape[1] != width or a.shape[0] not in (1, B):
+        raise ValueError("plant %s must be [1, %d] or [B, %d]" % (what, width, width))
+    return a
+
+
+def _rows(a, count, width, what):
+    """an optional per-item array of the single-step calls as [count, width] doubles; None stays None"""
+    if a is None:
+        return None
+    a = _c64(a)
+    if a.shape != (count, width):
+        raise ValueError("%s must be [count, %d]" % (what, width))
+    return a
+
+
 def reference_kinematics(x):
     """(com[3], ee[2,3]) as RobotUtils::loadReferences computes them (robot_utils.cpp:369-403)."""
     L = load_library()
@@ -533,9 +553,8 @@ class BatchedILQR:
     def step_wrench(self, x, u, stance_left, stance_right, wrench):
         """step_stance with one external wrench on the pelvis per item: wrench [count, 9] = force, torque (world frame) and point of
         application (pelvis frame); always the two-lane step (ilqr_hip_step_wrench)."""
-        x, u, wrench = _c64(x), _c64(u), _c64(wrench)
-        if wrench.shape != (x.shape[0], 9):
-            raise ValueError("wrench must be [count, 9]")
+        x, u = _c64(x), _c64(u)
+        wrench = _rows(_c64(wrench), x.shape[0], 9, "wrench")
         xn = np.zeros_like(x)
         self._chk(self.L.ilqr_hip_step_wrench(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(xn)))
         return xn
@@ -543,32 +562,21 @@ class BatchedILQR:
     def step_payload(self, x, u, stance_left, stance_right, payload, wrench=None):
         """step_wrench with one rigid payload on the pelvis per item as well: payload [count, 10] (columns PLANT_PAYLOAD), wrench [count, 9]
         or None for none; always the two-lane step (ilqr_hip_step_payload)."""
-        x, u, payload = _c64(x), _c64(u), _c64(payload)
-        if payload.shape != (x.shape[0], len(PLANT_PAYLOAD)):
-            raise ValueError("payload must be [count, 10]")
-        if wrench is not None:
-            wrench = _c64(wrench)
-            if wrench.shape != (x.shape[0], 9):
-                raise ValueError("wrench must be [count, 9]")
+        x, u = _c64(x), _c64(u)
+        payload = _rows(_c64(payload), x.shape[0], len(PLANT_PAYLOAD), "payload")
+        wrench = _rows(wrench, x.shape[0], 9, "wrench")
         xn = np.zeros_like(x)
-        self._chk(self.L.ilqr_hip_step_payload(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), None if wrench is None else _p(wrench), _p(payload), _p(xn)))
+        self._chk(self.L.ilqr_hip_step_payload(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(payload), _p(xn)))
         return xn
 
     def step_joints(self, x, u, stance_left, stance_right, joints, wrench=None, payload=None):
         """step_payload with one joint record per item: joints [count, 76] (gain, range scale, damping, armature of the 19 joints;
         scenario.stack_plant_joints builds them), wrench [count, 9] and payload [count, 10] each or None for none; always the two-lane step
         (ilqr_hip_step_joints)."""
-        x, u, joints = _c64(x), _c64(u), _c64(joints)
-        if joints.shape != (x.shape[0], PLANT_JOINTS):
-            raise ValueError("joints must be [count, 76]")
-        if wrench is not None:
-            wrench = _c64(wrench)
-            if wrench.shape != (x.shape[0], 9):
-                raise ValueError("wrench must be [count, 9]")
-        if payload is not None:
-            payload = _c64(payload)
-            if payload.shape != (x.shape[0], len(PLANT_PAYLOAD)):
-                raise ValueError("payload must be [count, 10]")
+        x, u = _c64(x), _c64(u)
+        joints = _rows(_c64(joints), x.shape[0], PLANT_JOINTS, "joints")
+        wrench = _rows(wrench, x.shape[0], 9, "wrench")
+        payload = _rows(payload, x.shape[0], len(PLANT_PAYLOAD), "payload")
         xn = np.zeros_like(x)
         self._chk(self.L.ilqr_hip_step_joints(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(payload), _p(joints), _p(xn)))
         return xn
@@ -714,11 +722,7 @@ class BatchedILQR:
     def plant_set_params(self, params):
         """Install plant parameter sets [n_sets, 7] (columns PLANT_PARAMS; scenario.stack_plant_params builds them), n_sets 1 or B: rollout b's
         plant steps with its own gravity, friction, softness, joint-limit stiffness and torque gain (ilqr_hip_plant_set_params)."""
-        params = _c64(params)
-        if params.ndim == 1:
-            params = params[None]
-        if params.ndim != 2 or params.shape[1] != len(PLANT_PARAMS) or params.shape[0] not in (1, self.B):
-            raise ValueError("plant parameters must be [1, 7] or [B, 7]")
+        params = _table(params, self.B, len(PLANT_PARAMS), "parameters")
         self._chk(self.L.ilqr_hip_plant_set_params(self.h, _p(params), int(params.shape[0])))
 
     def plant_clear_params(self):
@@ -736,11 +740,7 @@ class BatchedILQR:
         """Install external wrenches on the pelvis [n_sets, 11] (columns PLANT_WRENCH; scenario.stack_plant_wrench builds them), n_sets 1 or B:
         rollout b's plant steps under force, torque and point of application of its record in the plant intervals first <= i < end, counted
         from plant_reset (ilqr_hip_plant_set_wrench).  The solve does not know of it."""
-        wrench = _c64(wrench)
-        if wrench.ndim == 1:
-            wrench = wrench[None]
-        if wrench.ndim != 2 or wrench.shape[1] != len(PLANT_WRENCH) or wrench.shape[0] not in (1, self.B):
-            raise ValueError("plant wrenches must be [1, 11] or [B, 11]")
+        wrench = _table(wrench, self.B, len(PLANT_WRENCH), "wrenches")
         self._chk(self.L.ilqr_hip_plant_set_wrench(self.h, _p(wrench), int(wrench.shape[0])))
 
     def plant_clear_wrench(self):
@@ -764,33 +764,8 @@ class BatchedILQR:
         """Install rigid payloads on the pelvis [n_sets, 10] (columns PLANT_PAYLOAD; scenario.stack_plant_payload builds them), n_sets 1 or B:
         rollout b's plant carries mass, centre of mass and rotational inertia of its record in every substep until plant_clear_payload
         (ilqr_hip_plant_set_payload).  The solve does not know of it."""
-        payload = _c64(payload)
-        if payload.ndim == 1:
-            payload = payload[None]
-        if payload.ndim != 2 or payload.shape[1] != len(PLANT_PAYLOAD) or payload.shape[0] not in (1, self.B):
-            raise ValueError("plant payloads must be [1, 10] or [B, 10]")
+        payload = _table(payload, self.B, len(PLANT_PAYLOAD), "payloads")
         self._chk(self.L.ilqr_hip_plant_set_payload(self.h, _p(payload), int(payload.shape[0])))
-
-    def plant_set_joints(self, joints):
-        """Install joint records [n_sets, 76] (gain, range scale, damping, armature of the 19 joints; scenario.stack_plant_joints builds them),
-        n_sets 1 or B: rollout b's plant steps with the joints of its record until plant_clear_joints (ilqr_hip_plant_set_joints).  None
-        clears.  The solve does not know of it; the plant keeps reporting the commanded torque."""
-        if joints is None:
-            return self.plant_clear_joints()
-        joints = _c64(joints)
-        if joints.ndim == 1:
-            joints = joints[None]
-        if joints.ndim != 2 or joints.shape[1] != PLANT_JOINTS or joints.shape[0] not in (1, self.B):
-            raise ValueError("plant joints must be [1, 76] or [B, 76]")
-        self._chk(self.L.ilqr_hip_plant_set_joints(self.h, _p(joints), int(joints.shape[0])))
-
-    def plant_clear_joints(self):
-        """Remove the joint records: the plant calls launch what they launch without them."""
-        self._chk(self.L.ilqr_hip_plant_set_joints(self.h, None, 0))
-
-    def plant_get_joints(self):
-        """[B, 76]: the record of each rollout; the nominal record without a table."""
-        return self._get("ilqr_hip_plant_get_joints", (self.B, PLANT_JOINTS))
 
     def plant_clear_payload(self):
         """Remove the payloads: the plant calls launch what they launch without them."""
@@ -803,16 +778,29 @@ class BatchedILQR:
         """[B, 10] (columns PLANT_PAYLOAD): the record of each rollout; zeros without a table."""
         return self._get("ilqr_hip_plant_get_payload", (self.B, len(PLANT_PAYLOAD)))
 
+    def plant_set_joints(self, joints):
+        """Install joint records [n_sets, 76] (gain, range scale, damping, armature of the 19 joints; scenario.stack_plant_joints builds them),
+        n_sets 1 or B: rollout b's plant steps with the joints of its record until plant_clear_joints (ilqr_hip_plant_set_joints).  None
+        clears.  The solve does not know of it; the plant keeps reporting the commanded torque."""
+        if joints is None:
+            return self.plant_clear_joints()
+        joints = _table(joints, self.B, PLANT_JOINTS, "joints")
+        self._chk(self.L.ilqr_hip_plant_set_joints(self.h, _p(joints), int(joints.shape[0])))
+
+    def plant_clear_joints(self):
+        """Remove the joint records: the plant calls launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_set_joints(self.h, None, 0))
+
+    def plant_get_joints(self):
+        """[B, 76]: the record of each rollout; the nominal record without a table."""
+        return self._get("ilqr_hip_plant_get_joints", (self.B, PLANT_JOINTS))
+
     def plant_set_observation(self, observation, seed=0, stream0=0):
         """Install observation models [n_sets, 100] (bias[50], sigma[50] in tangent order; scenario.stack_plant_observation builds them),
         n_sets 1 or B: the warm starts and the plant's control law read rollout b's state with the error of its record, drawn once per plant
         interval from the counter-based generator under `seed`, rollout stream stream0 + b (ilqr_hip_plant_set_observation).  The plant's
         physics, the ring and the score stay on the true state."""
-        observation = _c64(observation)
-        if observation.ndim == 1:
-            observation = observation[None]
-        if observation.ndim != 2 or observation.shape[1] != PLANT_OBSERVATION or observation.shape[0] not in (1, self.B):
-            raise ValueError("plant observation records must be [1, 100] or [B, 100]")
+        observation = _table(observation, self.B, PLANT_OBSERVATION, "observation records")
         seed, stream0 = int(seed), int(stream0)
         if not (0 <= seed < 1 << 64 and 0 <= stream0 < 1 << 64):
             raise ValueError("seed and stream0 must fit 64 unsigned bits")
@@ -852,11 +840,7 @@ class BatchedILQR:
         them), n_sets 1 or B: the torque the plant's joints get is the law's command behind a delay line, a first-order lag and noise drawn
         once per plant interval under `seed`, rollout stream stream0 + b (ilqr_hip_plant_set_actuator).  What the plant reports -- control,
         ring, score -- stays the command."""
-        actuator = _c64(actuator)
-        if actuator.ndim == 1:
-            actuator = actuator[None]
-        if actuator.ndim != 2 or actuator.shape[1] != PLANT_ACTUATOR or actuator.shape[0] not in (1, self.B):
-            raise ValueError("plant actuator records must be [1, 39] or [B, 39]")
+        actuator = _table(actuator, self.B, PLANT_ACTUATOR, "actuator records")
         seed, stream0 = int(seed), int(stream0)
         if not (0 <= seed < 1 << 64 and 0 <= stream0 < 1 << 64):
             raise ValueError("seed and stream0 must fit 64 unsigned bits")

@@ -11,6 +11,7 @@ A mutant of the chain has to move the applied torque by 1e3 x the GPU test's tor
 import ctypes as C
 import os
 import re
+import subprocess
 import warnings
 
 import numpy as np
@@ -225,8 +226,10 @@ def test_header_and_wrappers_declare_the_feature():
     assert all(name in integ for name in NAMES)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "ilqr_hip_plant_set_actuator" in design and "k_plant_follow_a" in design and "k_actuator_draw" in design
-    mk = open(os.path.join(ROOT, "mpc-ilqr-mujoco_amd", "csrc", "Makefile")).read()
-    assert "libilqr_hip_actuator.so" in mk and "-DPLANT_ACTUATOR_MODULE" in mk
+    # a dry run (nothing is compiled): what builds the module compiles plant_kernels.hip with the module's macro
+    mk = subprocess.run(["make", "-n", "-B", "../lib/libilqr_hip_actuator.so"], cwd=os.path.join(ROOT, "mpc-ilqr-mujoco_amd", "csrc"), capture_output=True, text=True)
+    assert mk.returncode == 0, mk.stderr
+    assert any("plant_kernels.hip" in line and "-DPLANT_ACTUATOR_MODULE" in line for line in mk.stdout.splitlines()), mk.stdout
     s = sv.BatchedILQR.__new__(sv.BatchedILQR)      # no handle: the shape checks fail before the library is reached
     s.B, s.N, s.h = 3, 25, None
     for bad in (np.ones(38), np.ones((2, 39)), np.ones((3, 40)), np.ones((1, 3, 39))):

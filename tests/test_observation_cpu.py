@@ -9,6 +9,7 @@ sin at r <= 8.7)."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -175,8 +176,10 @@ def test_header_and_wrappers_declare_the_feature():
     assert all(name in integ for name in NAMES)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "ilqr_hip_plant_set_observation" in design and "k_plant_follow_o" in design and "k_observation_draw" in design
-    mk = open(os.path.join(ROOT, "mpc-ilqr-mujoco_amd", "csrc", "Makefile")).read()
-    assert "libilqr_hip_observe.so" in mk and "-DPLANT_OBSERVE_MODULE" in mk
+    # a dry run (nothing is compiled): what builds the module compiles plant_kernels.hip with the module's macro
+    mk = subprocess.run(["make", "-n", "-B", "../lib/libilqr_hip_observe.so"], cwd=os.path.join(ROOT, "mpc-ilqr-mujoco_amd", "csrc"), capture_output=True, text=True)
+    assert mk.returncode == 0, mk.stderr
+    assert any("plant_kernels.hip" in line and "-DPLANT_OBSERVE_MODULE" in line for line in mk.stdout.splitlines()), mk.stdout
     s = sv.BatchedILQR.__new__(sv.BatchedILQR)      # no handle: the shape checks fail before the library is reached
     s.B, s.N, s.h = 3, 25, None
     for bad in (np.ones(99), np.ones((2, 100)), np.ones((3, 101)), np.ones((1, 3, 100))):

@@ -1,0 +1,88 @@
+"""csrc/plant_plan.h: resolve_plant_plan over every combination of the six plant tables, an all-nominal joint table and advance / follow --
+256 combinations, printed by tests/cpp/plant_plan_dump.cpp (host-only C++17, no HIP) -- against the rules restated here from the
+comments of enqueue_plant (ilqr_capi.hip) and the texts of the table setters in include/ilqr_hip.h.  No GPU."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mpc-ilqr-mujoco_amd", "csrc")
+ADVANCE, FOLLOW, PARAMS, WRENCH, PAYLOAD, OBSERVE, ACTUATOR, JOINTS = range(8)      # PlantFamily
+MOD_WRENCH, MOD_PAYLOAD, MOD_OBSERVE, MOD_ACTUATOR, MOD_JOINTS = (1 << i for i in range(5))      # bits of PlantPlan::modules
+KEYS = ("params", "wrench", "payload", "observation", "actuator", "joints", "joints_nominal", "follow")
+
+
+@pytest.fixture(scope="module")
+def rows(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("plant_plan") / "plant_plan_dump")
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "plant_plan_dump.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = [{k: int(v) for k, v in (tok.split("=") for tok in line.split())} for line in r.stdout.splitlines()]
+    assert len(out) == 256
+    assert len({tuple(d[k] for k in KEYS) for d in out}) == 256        # every combination once
+    return out
+
+
+def expected(d):
+    """the plan of one combination, rule by rule"""
+    e = {}
+    # "While it is installed ilqr_hip_plant_advance / _follow launch the X family", each family carrying the tables of the ones before it,
+    # "each table present or not": the last table installed in the order params, wrench, payload, observation, actuator, joints decides.  A
+    # joint table whose every record is the model's own joints is no table.
+    joints = d["joints"] and not d["joints_nominal"]
+    if joints:
+        fam = JOINTS
+    elif d["actuator"]:
+        fam = ACTUATOR
+    elif d["observation"]:
+        fam = OBSERVE
+    elif d["payload"]:
+        fam = PAYLOAD
+    elif d["wrench"]:
+        fam = WRENCH
+    elif d["params"]:
+        fam = PARAMS
+    else:
+        fam = FOLLOW if d["follow"] else ADVANCE        # "without a table exactly the launch without the feature"
+    e["p.family"] = fam
+    # the draws run in front of a family that reads their rows: the observation family and the ones above it / the actuator family and
+    # the joints family -- and only for a table that is installed (the rows of an absent table are a null pointer to the kernel)
+    e["p.draw_observation"] = int(bool(d["observation"]) and fam >= OBSERVE)
+    e["p.draw_actuator"] = int(bool(d["actuator"]) and fam >= ACTUATOR)
+    # the family's own module and the module of each draw: what the call calls into
+    mods = {WRENCH: MOD_WRENCH, PAYLOAD: MOD_PAYLOAD, OBSERVE: MOD_OBSERVE, ACTUATOR: MOD_ACTUATOR, JOINTS: MOD_JOINTS}.get(fam, 0)
+    if e["p.draw_observation"]:
+        mods |= MOD_OBSERVE
+    if e["p.draw_actuator"]:
+        mods |= MOD_ACTUATOR
+    e["p.modules"] = mods
+    # the module families read "the parameter table or the handle's own record": uploaded whenever a table of theirs is installed -- an
+    # all-nominal joint table too -- and no parameter table is
+    e["p.self_params"] = int(any(d[k] for k in ("wrench", "payload", "observation", "actuator", "joints")) and not d["params"])
+    return e
+
+
+def test_plan_equals_the_rules_of_the_tables_in_all_256_combinations(rows):
+    fields = set(expected(rows[0]))
+    assert fields == {k for k in rows[0] if k.startswith("p.")}      # every field of the dump is compared
+    bad = [(k, d[k], e[k], d) for d in rows for e in [expected(d)] for k in fields if d[k] != e[k]]
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_a_nominal_joint_table_alone_is_no_table(rows):
+    hit = [d for d in rows if d["joints"] and d["joints_nominal"] and not any(d[k] for k in KEYS[:5])]
+    assert len(hit) == 2
+    for d in hit:
+        assert d["p.family"] == (FOLLOW if d["follow"] else ADVANCE) and d["p.modules"] == 0
+        assert not d["p.draw_observation"] and not d["p.draw_actuator"]
+
+
+def test_every_module_family_names_its_module(rows):
+    for d in rows:
+        if d["p.family"] >= WRENCH:
+            assert d["p.modules"] & (1 << (d["p.family"] - WRENCH)), d      # never a call through a module nobody loaded
+        else:
+            assert d["p.modules"] == 0, d
