@@ -607,6 +607,43 @@ int ilqr_hip_plant_set_joints(ilqr_hip_ctx* ctx, const double* joints /*[n_sets]
 int ilqr_hip_plant_get_joints(ilqr_hip_ctx* ctx, double* joints /*[B][76]*/);
 int ilqr_hip_step_joints(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, int stance_left, int stance_right, const double* wrench /*[count][9], NULL: none*/,
                          const double* payload /*[count][10], NULL: none*/, const double* joints /*[count][76]*/, double* x_next);
+/* ---- a floor of its own height under each foot, one record per rollout: a ground that is not the solver's.  With the stance source
+   GEOMETRY the plant's feet land and lift against z = 0, exactly where the solver's model expects them to; an unexpected ground height -- a
+   touchdown a few centimetres early or late, a kerb, a floor that gives way -- is the standard disturbance of a walking controller.  One
+   record of ILQR_PLANT_TERRAIN doubles per set:
+     z_left, z_right   floor height under the left / right foot, m; finite
+     edge_x            m; the height holds for a foot only while the world x of its ankle-link origin is >= edge_x; finite, or -inf: everywhere
+     first, end        the record acts in the plant intervals first <= i < end, counted as ilqr_hip_plant_intervals counts them and checked
+                       as the wrench's window is (non-negative integers, first <= end, end may be +inf)
+   The rule, per plant substep, on the state the substep starts from: foot f is in stance iff clearance_f(qpos) < floor_f, where
+   floor_f = z_f while the window is open and ankle_x_f >= edge_x, else 0, and clearance_f is what ilqr_hip_foot_clearance returns.  The
+   contact step itself is unchanged: the stance rows weld a touching foot where it is, at whatever height, and release, the Coulomb limit,
+   kinetic friction and joint-limit rows act on these flags as on any flags.  What changes is the flags the plant reports
+   (ilqr_hip_plant_get_stance, the ring's states follow from them); the score's capture-point term keeps reading the schedule and the solver
+   knows nothing of the record.  A record with z = 0, or whose window is shut, is the solver's ground.
+   plant_set_terrain: n_sets = 1 (one record that every rollout reads) or the batch, else ILQR_ERR_ARG; ILQR_ERR_ARG also for a value outside
+   the ranges above, checked before the handle is touched.  The table is owned by the handle; the call uploads and synchronises the handle's
+   stream.  It survives ilqr_hip_plant_reset and ilqr_hip_plant_configure; plant_clear_terrain removes it.  While it is installed
+   ilqr_hip_plant_advance / _follow launch the terrain family of the plant kernel (k_plant_follow_t of the module libilqr_hip_terrain.so,
+   opened from the library's directory on first use -- missing: ILQR_ERR_UNSUPPORTED with the path in ilqr_hip_last_error, never a fall-back;
+   an advance is that kernel over one interval), which carries parameter record, wrench, payload, observation, actuator and joints as the
+   joints family does, each table present or not.  A floor nobody consults is refused, not ignored: while the table is installed a plant call
+   whose contact source is ILQR_STANCE_SCHEDULE, or whose effective contact mode (ilqr_hip_plant_set_model, else the solver's) is 0 or 1,
+   returns ILQR_ERR_UNSUPPORTED before anything is launched.
+   plant_get_terrain: terrain[B][5], the record of each rollout (without a table: heights 0, edge -inf, the empty window [0, 0)).
+   step_terrain: x_next[i] = f(x[i], u[i]) under the flags the rule gives x[i] on the floor terrain[i] = z_left, z_right, edge_x (no window:
+   always open), decided on the device, with the handle's dynamics parameters and step size; the flags in stance_out[i].  Contact mode 0 or
+   1: ILQR_ERR_UNSUPPORTED.  Always the two-lane step.
+   terrain_stance: the rule itself on the host, no GPU and no handle: stance[2] of qpos[26] under terrain[5] in plant interval `interval`,
+   and the floor each foot was held against in floor[2] where it is not NULL. */
+#define ILQR_PLANT_TERRAIN 5   /* z_left, z_right, edge_x, first, end */
+int ilqr_hip_plant_set_terrain(ilqr_hip_ctx* ctx, const double* terrain /*[n_sets][5]*/, int n_sets);
+int ilqr_hip_plant_clear_terrain(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_num_terrain_sets(const ilqr_hip_ctx* ctx);   /* 0: no table */
+int ilqr_hip_plant_get_terrain(ilqr_hip_ctx* ctx, double* terrain /*[B][5]*/);
+int ilqr_hip_step_terrain(ilqr_hip_ctx* ctx, int count, const double* x, const double* u, const double* terrain /*[count][3]: z_left, z_right, edge_x*/, double* x_next,
+                          int* stance_out /*[count][2]*/);
+int ilqr_hip_terrain_stance(const double* qpos /*26*/, const double* terrain /*5*/, long interval, int* stance /*2*/, double* floor /*2, NULL: not wanted*/);
 
 /* ---- reference windows from a track on the device.  The reference cuts the window of every MPC step out of RobotUtils' full-length
    arrays on the host (MPC::extractReferenceWindow, src/ilqr/mpc.cpp:163-166) and hands it to the solver; with one window per rollout

@@ -264,6 +264,20 @@ class iLQR {
     if (count < 1 || x.size() != (size_t)count * ILQR_NX || u.size() != (size_t)count * ILQR_NU || joints.size() != (size_t)count * ILQR_PLANT_JOINTS) throw std::runtime_error("stepJoints: sizes");
     Vec xn((size_t)count * ILQR_NX); chk(ilqr_hip_step_joints(ctx_, count, x.data(), u.data(), stance_left, stance_right, wrench, payload, joints.data(), xn.data())); return xn;
   }
+  // a floor of its own height under each foot per rollout (ilqr_hip.h ilqr_hip_plant_set_terrain): [n_sets][5] = z_left, z_right, edge_x, first, end
+  void plantSetTerrain(const Vec& terrain, int n_sets) {
+    if (n_sets < 1 || terrain.size() != (size_t)n_sets * ILQR_PLANT_TERRAIN) throw std::runtime_error("terrain records must hold n_sets * 5 doubles");
+    chk(ilqr_hip_plant_set_terrain(ctx_, terrain.data(), n_sets));
+  }
+  void plantClearTerrain() { chk(ilqr_hip_plant_clear_terrain(ctx_)); }
+  int plantNumTerrainSets() const { return ilqr_hip_plant_num_terrain_sets(ctx_); }
+  Vec plantTerrain() { Vec t((size_t)B_ * ILQR_PLANT_TERRAIN); chk(ilqr_hip_plant_get_terrain(ctx_, t.data())); return t; }      // [batch][5]
+  // x_next [count][51]; the flags each item stepped with in stance_out [count][2].  terrain [count][3] = z_left, z_right, edge_x
+  Vec stepTerrain(int count, const Vec& x, const Vec& u, const Vec& terrain, std::vector<int>& stance_out) {
+    if (count < 1 || x.size() != (size_t)count * ILQR_NX || u.size() != (size_t)count * ILQR_NU || terrain.size() != (size_t)count * 3) throw std::runtime_error("stepTerrain: sizes");
+    Vec xn((size_t)count * ILQR_NX); stance_out.assign((size_t)count * 2, 0);
+    chk(ilqr_hip_step_terrain(ctx_, count, x.data(), u.data(), terrain.data(), xn.data(), stance_out.data())); return xn;
+  }
   static std::array<double, 3> pelvisInertialOffset() { std::array<double, 3> r{}; ilqr_hip_pelvis_inertial_offset(r.data()); return r; }
   // reference windows from a track on the device (ilqr_hip.h ilqr_hip_set_reference_track): per step windowFromTrack(k) -> initializeWarmFromPlant() -> solve -> plantAdvance()
   void setReferenceTrack(int rows, const double* x_ref, const double* u_ref, const double* com_ref, const double* ee_ref, const double* com_vel_ref, const int* contact, int contact_rows) { chk(ilqr_hip_set_reference_track(ctx_, rows, x_ref, u_ref, com_ref, ee_ref, com_vel_ref, contact, contact_rows)); }   // robot_utils.cpp:281-492

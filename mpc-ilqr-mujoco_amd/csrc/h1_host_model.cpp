@@ -99,6 +99,26 @@ void foot_clearance(const double* q, double* clr) {
   }
 }
 
+// The stance flags of a plant on a floor of its own height (ilqr_hip_plant_set_terrain), stated on the host: foot f touches iff
+// clearance_f(q) < floor_f, where floor_f is the record's z_f while the record's window [first, end) holds plant interval `interval` and the
+// world x of the foot's ankle-link origin is >= edge_x, and 0 otherwise.  terrain = z_left, z_right, edge_x, first, end; floor may be null.
+void terrain_stance(const double* q, const double* terrain, long interval, int* stance, double* floor) {
+  double x[H1_NX] = {0};
+  for (int i = 0; i < H1_NQ; ++i) x[i] = q[i];
+  double Rw[H1_NB][9], pw[H1_NB][3];
+  forward_kinematics(x, Rw, pw);
+  double clr[2];
+  foot_clearance(q, clr);
+  const double iv = (double)interval;
+  const bool open = terrain[3] <= iv && iv < terrain[4];
+  const int body[2] = {H1_EE_LEFT, H1_EE_RIGHT};
+  for (int f = 0; f < 2; ++f) {
+    const double fl = (open && pw[body[f]][0] >= terrain[2]) ? terrain[f] : 0.0;
+    stance[f] = clr[f] < fl ? 1 : 0;
+    if (floor) floor[f] = fl;
+  }
+}
+
 // centre of mass of the pelvis body in the pelvis frame (h1.xml inertial pos; mjModel.body_ipos): the point at which xfrc_applied acts
 void pelvis_inertial_offset(double* r) {
   for (int k = 0; k < 3; ++k) r[k] = H1_COM[0][k];

@@ -160,16 +160,18 @@ struct ilqr_hip_ctx {
   //   obs     (ilqr_hip_plant_set_observation; k_plant_follow_o): records of 100 doubles
   //   act     (ilqr_hip_plant_set_actuator; k_plant_follow_a): records of 39 doubles
   //   joints  (ilqr_hip_plant_set_joints; k_plant_follow_j): records of JOINT_REC doubles
+  //   terrain (ilqr_hip_plant_set_terrain; k_plant_follow_t): records of TERRAIN_REC doubles
   struct TableBuf { double* d = nullptr; int sets = 0; };
-  TableBuf pparams, wrench, payload, obs, act, joints;
+  TableBuf pparams, wrench, payload, obs, act, joints, terrain;
   // d_self_params: the ONE parameter record the module families read while no parameter table is installed -- the handle's own values with
   // gain 1, uploaded again whenever they differ from self_params
   double* d_self_params = nullptr;
   double self_params[ILQR_PLANT_PARAMS + 1] = {0};
   unsigned module_attr_set = 0;   // bit ilqr::PlantModule: that module's kernels have their LDS attributes on this handle's device
-  // scratch of the single-step calls beside d_stepx / d_stepu / d_stepn: [cap][9] wrenches, [cap][10] payloads, [cap][76] joint records
-  double *d_stepw = nullptr, *d_stepm = nullptr, *d_stepj = nullptr;
-  size_t step_w_cap = 0, step_m_cap = 0, step_j_cap = 0;
+  // scratch of the single-step calls beside d_stepx / d_stepu / d_stepn: [cap][9] wrenches, [cap][10] payloads, [cap][76] joint records,
+  // 4 doubles per item of floors: [count][3] doubles, then the flags that come back, [count][2] ints
+  double *d_stepw = nullptr, *d_stepm = nullptr, *d_stepj = nullptr, *d_stept = nullptr;
+  size_t step_w_cap = 0, step_m_cap = 0, step_j_cap = 0, step_t_cap = 0;
   // Observation: the plant calls run behind a draw of the call's error rows into d_obs_delta [N][B][51] (a follow never exceeds N intervals),
   // and the warm starts hand the solve Pl.x [+] delta of the current interval.
   unsigned long long obs_seed = 0, obs_stream0 = 0;
@@ -271,7 +273,7 @@ static inline int enter_launching(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 
-// The wrench, payload, observation, actuator and joints families of the plant kernels are modules of their own (csrc/Makefile PLANT_MODULE;
+// The wrench, payload, observation, actuator, joints and terrain families of the plant kernels are modules of their own (csrc/Makefile PLANT_MODULE;
 // plant_kernels.hip says why), each opened on first use from the directory this library was loaded from, as RCCL is opened on first use: a
 // process that never uses a family never loads it.  A module that is missing or lacks an entry point is an error of the call that needs it
 // (ILQR_ERR_UNSUPPORTED).
@@ -285,6 +287,7 @@ const ModuleDesc MODULE_DESC[ilqr::PLANT_MODULES] = {
   {"observe", "observation", {"set_attr", "follow", "draw", "apply"}},
   {"actuator", "actuator", {"set_attr", "follow", "draw", nullptr}},
   {"joints", "joints", {"set_attr", "follow", "step", nullptr}},
+  {"terrain", "terrain", {"set_attr", "follow", "step", nullptr}},
 };
 struct PlantModuleLib {
   void* fn[MODULE_FNS] = {nullptr};
@@ -418,8 +421,8 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
-  for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints}) if (t->d) hipFree(t->d);
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
+  for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints, &c->terrain}) if (t->d) hipFree(t->d);
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -1504,6 +1507,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
 constexpr int WRENCH_REC = 16;      // doubles of a wrench record on the device (128 B): the ILQR_PLANT_WRENCH values and padding
 constexpr int PAYLOAD_REC = 16;     // doubles of a payload record on the device (128 B): the ILQR_PLANT_PAYLOAD values and padding
 constexpr int JOINT_REC = 80;       // doubles of a joint record on the device (640 B): the ILQR_PLANT_JOINTS values and padding
+constexpr int TERRAIN_REC = 8;      // doubles of a terrain record on the device (64 B): the ILQR_PLANT_TERRAIN values and padding
 static h1::DynParams plant_dyn(const ilqr_hip_ctx* c) {
   h1::DynParams dyn = c->P.dyn;
   dyn.h = c->P.dyn.h / c->plant_substeps;
@@ -1519,7 +1523,7 @@ static const char* plant_geometry_refusal(const ilqr_hip_ctx* c, int plant_mode)
 }
 // What a plant call launches (plant_plan.h): resolved from the installed tables behind the call's prologue, never stored.
 static ilqr::PlantPlan plant_plan_of(const ilqr_hip_ctx* c, bool follow) {
-  return ilqr::resolve_plant_plan({c->pparams.d != nullptr, c->wrench.d != nullptr, c->payload.d != nullptr, c->obs.d != nullptr, c->act.d != nullptr, c->joints.d != nullptr, c->joints_nominal}, follow);
+  return ilqr::resolve_plant_plan({c->pparams.d != nullptr, c->wrench.d != nullptr, c->payload.d != nullptr, c->obs.d != nullptr, c->act.d != nullptr, c->joints.d != nullptr, c->joints_nominal, c->terrain.d != nullptr}, follow);
 }
 // The module families always read a parameter record: the parameter table's, or (PlantPlan::self_params) this ONE record of the handle's own
 // values with gain 1, uploaded again whenever the handle's values have changed.
@@ -1588,6 +1592,12 @@ static void enqueue_plant(ilqr_hip_ctx* c, const ilqr::PlantPlan& plan, const h1
   if (plan.draw_observation) enqueue_observation_draw(c, c->plant_intervals, count);
   if (plan.draw_actuator) enqueue_actuator_draw(c, c->plant_intervals, count);
   switch (plan.family) {
+    case ilqr::PLANT_TERRAIN: {      // (an all-nominal joint table is no table to this family either)
+      const auto Jt = c->joints_nominal ? ilqr::JointTable{nullptr, 0} : J;
+      const auto R = ilqr::TerrainTable{c->terrain.d, c->terrain.sets == 1 ? 0 : TERRAIN_REC};
+      module_fn<ilqr::terrain_follow_fn>(ilqr::MOD_TERRAIN, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &Jt, &R, &a, c->stream);
+      break;
+    }
     case ilqr::PLANT_JOINTS: module_fn<ilqr::joints_follow_fn>(ilqr::MOD_JOINTS, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &J, &a, c->stream); break;
     case ilqr::PLANT_ACTUATOR: module_fn<ilqr::actuator_follow_fn>(ilqr::MOD_ACTUATOR, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &a, c->stream); break;
     case ilqr::PLANT_OBSERVE: module_fn<ilqr::observe_follow_fn>(ilqr::MOD_OBSERVE, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &a, c->stream); break;
@@ -1599,8 +1609,16 @@ static void enqueue_plant(ilqr_hip_ctx* c, const ilqr::PlantPlan& plan, const h1
   }
   if (plan.draw_actuator) c->act_substeps += (long)count * c->plant_substeps;
 }
+// a terrain table is a floor somebody has to consult: the plant decides its own contacts (source GEOMETRY) in a mode with unilateral rows
+static const char* terrain_refusal(const ilqr_hip_ctx* c) {
+  if (c->plant_source != ILQR_STANCE_GEOMETRY) return "a terrain table is installed and the plant's contact source is SCHEDULE: nothing would consult the floor; ilqr_hip_plant_configure(..., ILQR_STANCE_GEOMETRY) or ilqr_hip_plant_clear_terrain";
+  const int mode = c->plant_mode >= 0 ? c->plant_mode : c->P.dyn.contact;
+  if (mode == ILQR_CONTACT_NONE || mode == ILQR_CONTACT_RIGID_STANCE) return "a terrain table is installed and the plant's contact mode is 0 or 1: no foot lands or lifts by its height; use mode 2, 3 or 4 or ilqr_hip_plant_clear_terrain";
+  return nullptr;
+}
 // what ilqr_hip_plant_advance and ilqr_hip_plant_follow do in front of enqueue_plant: the handle's own parameter record and every module of the plan
 static int prepare_plant(ilqr_hip_ctx* c, const ilqr::PlantPlan& plan) {
+  if (plan.family == ilqr::PLANT_TERRAIN) if (const char* why = terrain_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   if (plan.self_params) TRY(plant_self_params(c));
   for (int m = 0; m < ilqr::PLANT_MODULES; ++m) if ((plan.modules >> m) & 1u) TRY(need_module(c, m));
   return ILQR_OK;
@@ -1765,7 +1783,7 @@ int ilqr_hip_plant_set_model(ilqr_hip_ctx* c, int contact_mode, int joint_limits
   c->plant_mode = contact_mode; c->plant_limits = joint_limits;
   return ILQR_OK;
 }
-// ---- what the entry points of the six tables share (ilqr_hip_ctx::TableBuf); their argument checks, their no-table values and whatever else is
+// ---- what the entry points of the seven tables share (ilqr_hip_ctx::TableBuf); their argument checks, their no-table values and whatever else is
 // specific to a table stay with them
 using TableBuf = ilqr_hip_ctx::TableBuf;
 // installs n_sets records of `values` doubles, padded with zeros to `rec` doubles on the device
@@ -2070,6 +2088,70 @@ int ilqr_hip_plant_get_joints(ilqr_hip_ctx* c, double* joints) {
     return ILQR_OK;
   }
   return table_read(c, c->joints, joints, P, JOINT_REC);
+}
+// ---- a floor of its own height under each foot per rollout (plant_kernels.hip k_plant_follow_t, k_step_t; the rule: h1_host_model.cpp terrain_stance)
+// the checks that need no handle: z_left, z_right finite, edge_x finite or -inf, and with n == ILQR_PLANT_TERRAIN the wrench's window
+static bool terrain_values_ok(const double* r, int n) {
+  if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !(std::isfinite(r[2]) || (r[2] < 0.0 && std::isinf(r[2])))) return false;
+  if (n == ILQR_PLANT_TERRAIN) {
+    double w[ILQR_PLANT_WRENCH] = {0};
+    w[9] = r[3]; w[10] = r[4];
+    return wrench_values_ok(w, ILQR_PLANT_WRENCH);
+  }
+  return true;
+}
+int ilqr_hip_plant_set_terrain(ilqr_hip_ctx* c, const double* terrain, int n_sets) {
+  if (!terrain || n_sets < 1) return ILQR_ERR_ARG;
+  for (int s = 0; s < n_sets; ++s) if (!terrain_values_ok(terrain + (size_t)s * ILQR_PLANT_TERRAIN, ILQR_PLANT_TERRAIN)) return ILQR_ERR_ARG;
+  if (!c || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(need_module(c, ilqr::MOD_TERRAIN));
+  return table_install(c, &c->terrain, terrain, n_sets, ILQR_PLANT_TERRAIN, TERRAIN_REC);      // (64-byte records: the five values and three doubles of padding)
+}
+int ilqr_hip_plant_clear_terrain(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  return table_clear(c, &c->terrain);
+}
+int ilqr_hip_plant_num_terrain_sets(const ilqr_hip_ctx* c) { return c ? c->terrain.sets : -1; }
+int ilqr_hip_plant_get_terrain(ilqr_hip_ctx* c, double* terrain) {
+  if (!c || !terrain) return ILQR_ERR_ARG;
+  enter(c);
+  if (!c->terrain.d) {      // (no table: the solver's ground, a window that is shut)
+    for (size_t i = 0; i < (size_t)c->B * ILQR_PLANT_TERRAIN; ++i) terrain[i] = i % ILQR_PLANT_TERRAIN == 2 ? -HUGE_VAL : 0.0;
+    return ILQR_OK;
+  }
+  return table_read(c, c->terrain, terrain, ILQR_PLANT_TERRAIN, TERRAIN_REC);
+}
+int ilqr_hip_step_terrain(ilqr_hip_ctx* c, int count, const double* x, const double* u, const double* terrain, double* x_next, int* stance_out) {
+  if (count <= 0 || !x || !u || !terrain || !x_next || !stance_out) return ILQR_ERR_ARG;
+  for (int i = 0; i < count; ++i) if (!terrain_values_ok(terrain + (size_t)i * 3, 3)) return ILQR_ERR_ARG;
+  if (!c) return ILQR_ERR_ARG;
+  if (c->P.dyn.contact == ILQR_CONTACT_NONE || c->P.dyn.contact == ILQR_CONTACT_RIGID_STANCE) {
+    c->err = "step_terrain in contact mode 0 or 1: no foot lands or lifts by the floor's height; use mode 2, 3 or 4";
+    return ILQR_ERR_UNSUPPORTED;
+  }
+  TRY(enter_launching(c));
+  TRY(need_module(c, ilqr::MOD_TERRAIN));
+  const size_t n = (size_t)count;
+  TRY(grow_step_buffer(c, &c->d_stept, &c->step_t_cap, n, 4));
+  TRY(grow_step_scratch(c, count));
+  int* d_flags = (int*)(c->d_stept + n * 3);      // (behind the floors: 2 ints per item)
+  HIPCHK(c, hipMemcpyAsync(c->d_stepx, x, n * ILQR_NX * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stepu, u, n * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stept, terrain, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  module_fn<ilqr::terrain_step_fn>(ilqr::MOD_TERRAIN, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, c->d_stept, d_flags, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, n * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(stance_out, d_flags, n * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_terrain_stance(const double* qpos, const double* terrain, long interval, int* stance, double* floor) {
+  if (!qpos || !terrain || !stance || interval < 0 || !terrain_values_ok(terrain, ILQR_PLANT_TERRAIN)) return ILQR_ERR_ARG;
+  for (int i = 0; i < ILQR_NQ; ++i) if (!std::isfinite(qpos[i])) return ILQR_ERR_ARG;
+  h1host::terrain_stance(qpos, terrain, interval, stance, floor);
+  return ILQR_OK;
 }
 // ---- single steps under a wrench, a payload and a joint record per item: ONE body behind the argument checks of the three entry points.
 // `which` is the entry point's own module, whose step kernel runs (k_step_w / k_step_m / k_step_j); it takes the arrays of the modules before

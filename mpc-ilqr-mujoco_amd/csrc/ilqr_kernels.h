@@ -281,6 +281,22 @@ typedef int (*joints_set_attr_fn)();
 typedef void (*joints_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
                                  const JointTable*, const WrenchFollowArgs*, hipStream_t);
 typedef void (*joints_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, const double*, hipStream_t);
+// the same on a floor of each rollout's own height (ilqr_hip_plant_set_terrain): rollout b reads record b * rec_stride of R.records -- z_left,
+// z_right, edge_x, first, end, three doubles of padding; 8 doubles -- (rec_stride 8, or 0: one record for all) and decides its stance flags
+// per substep against that floor.  T as in the wrench family; W.records, M.records, the observation rows delta, A.records and J.records may
+// each be null.  The window is counted from W.interval0, which is set whether or not there is a wrench table.
+struct TerrainTable {
+  const double* records;
+  int rec_stride;
+};
+// The family lives in a module of its own as well, libilqr_hip_terrain.so (plant_kernels.hip compiled with -DPLANT_TERRAIN_MODULE):
+//   int  ilqr_terrain_module_set_attr()
+//   void ilqr_terrain_module_follow(S, Pl, dyn, T, W, M, delta or null, A, J, R, args, stream)
+//   void ilqr_terrain_module_step(count, x, u, dyn, xn, terrain[count][3] (z_left, z_right, edge_x), stance_out[count][2], stream)
+typedef int (*terrain_set_attr_fn)();
+typedef void (*terrain_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
+                                  const JointTable*, const TerrainTable*, const WrenchFollowArgs*, hipStream_t);
+typedef void (*terrain_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, const double*, int*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

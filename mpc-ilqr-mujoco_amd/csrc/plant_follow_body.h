@@ -24,10 +24,21 @@
 //                  and RPW more rows of LDS, JR -- ONE record of h1s::JOINT_REC doubles per rollout, staged once per launch -- whose offset
 //                  the step gets beside the disturbance row's (step_any_j).  Without a wrench and a payload table the disturbance rows
 //                  hold zeros: the step is the one of family 3 under no wrench and no payload.
+//   PLANT_TABLE 7  k_plant_follow_t: as 6 with jtab null as well (then the step of family 5: under the disturbance rows if either table is there,
+//                  else the step of family 1), and the FLOOR under each foot of a rollout has the height of its record of a terrain table
+//                  (ilqr_hip_plant_set_terrain): two more kernel arguments and RPW more rows of LDS, TR -- one record of TERRAIN_REC doubles per
+//                  rollout, staged once per launch.  Per substep the kernel decides the stance flags itself (terrain_stance: foot_contact at
+//                  pz - floor) where the other families decide the reported ones, and hands them to the step with geom = 0: the non-inlined
+//                  steps are the ones of the families below and decide nothing.
 #ifndef PLANT_TABLE
-#error "define PLANT_TABLE (0, 1, 2, 3, 4, 5 or 6) before including plant_follow_body.h"
+#error "define PLANT_TABLE (0, 1, 2, 3, 4, 5, 6 or 7) before including plant_follow_body.h"
 #endif
-#if PLANT_TABLE == 6
+#if PLANT_TABLE == 7
+#define K_PLANT_FOLLOW k_plant_follow_t
+#define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs, \
+                           const double* atab, int a_stride, const double* abeta, int ab_stride, const double* az, double* afifo, double* ay, double* aapplied, long substep0, \
+                           const double* jtab, int j_stride, const double* ttab, int t_stride
+#elif PLANT_TABLE == 6
 #define K_PLANT_FOLLOW k_plant_follow_j
 #define PLANT_TABLE_PARAMS , const double* ptab, int rec_stride, const double* wtab, int wr_stride, long interval0, const double* mtab, int m_stride, const double* dobs, \
                            const double* atab, int a_stride, const double* abeta, int ab_stride, const double* az, double* afifo, double* ay, double* aapplied, long substep0, \
@@ -73,7 +84,17 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #if PLANT_TABLE
   stage_plant_records<RPW>(S, lds + Lay::DOUBLES, b0, ptab, rec_stride);      // (once for all intervals; the fence at the head of interval 0 orders it)
 #endif
-#if PLANT_TABLE == 6
+#if PLANT_TABLE == 7
+  constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // the rows of family 6, then the terrain records
+  constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
+  constexpr int UA0 = XO0 + RPW * n;
+  constexpr int JR0 = UA0 + RPW * m;
+  constexpr int TR0 = JR0 + RPW * h1s::JOINT_REC;
+  stage_disturbance_records<RPW, true>(S, lds + WR0, b0, wtab, wr_stride, mtab, m_stride);
+  if (jtab) stage_joint_records<RPW>(S, lds + JR0, b0, jtab, j_stride);      // (wave-uniform: a kernel argument)
+  stage_terrain_records<RPW>(S, lds + TR0, b0, ttab, t_stride);
+  const bool disturbed = wtab != nullptr || mtab != nullptr;
+#elif PLANT_TABLE == 6
   constexpr int WR0 = Lay::DOUBLES + RPW * PLANT_REC;      // the rows of family 5, then the joint records
   constexpr int XO0 = WR0 + 2 * RPW * h1s::DIST_REC;
   constexpr int UA0 = XO0 + RPW * n;
@@ -149,7 +170,7 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #endif
         wave_lds_fence();
       }
-#if PLANT_TABLE == 6
+#if PLANT_TABLE >= 6
       if (atab) {      // (wave-uniform: a kernel argument) the actuator as in family 5
         wave_lds_fence();
         actuator_stage<FB>(S, lds, b0, UA0, atab, a_stride, abeta, ab_stride, az + (size_t)j * S.B * m, afifo, ay, aapplied, substep0 + (long)j * substeps + k,
@@ -166,7 +187,7 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
 #endif
       if (k == 0 && prt < RPW) h1s::store_half(side_t, h, lds + Lay::XK + prt * n);      // keep row (FB = 0: over xbar_k, behind its last reader)
       const int pc = prt < RPW ? prt : 0;
-#if PLANT_TABLE == 6
+#if PLANT_TABLE >= 6
       load_half_u(side_t, lds + (atab ? UA0 : Lay::US) + pc * m, u);      // the applied torque, or without an actuator the command, behind the guard
       if (!atab) {
         bool ufin = finite_half_u(u);
@@ -185,10 +206,26 @@ __global__ void __launch_bounds__(64) K_PLANT_FOLLOW(DevState S, PlantDev Pl, Dy
       if (run) {
         const h1s::LaneLds L{lds, 64, lane};
         h1s::load_half(side_t, lds + Lay::XS + prt * n, h);
+#if PLANT_TABLE == 7
+        // the flags of this substep, decided HERE on the state it starts from: each foot against the floor of the rollout's record in this
+        // interval.  The record is read from LDS behind the opaque lane index; only the two flags leave the decision.
+        if constexpr (KIND >= 1 && KIND <= 4) {
+          if (geom) terrain_stance(side_t, h, lds + TR0 + pc * TERRAIN_REC, (double)(interval0 + j), st[0], st[1]);
+        }
+#else
         if constexpr (KIND >= 1 && KIND <= 4) {
           if (geom) h1s::geom_stance(side_t, h, st[0], st[1]);      // (reported; the step decides again behind its call boundary)
         }
-#if PLANT_TABLE == 6
+#endif
+#if PLANT_TABLE == 7
+        // the step of the families below under the flags decided above (geom = 0): with a joint record family 6's, else family 5's
+        const double* wrow = lds + WR0 + pc * h1s::DIST_REC;
+        const double iv = (double)(interval0 + j);
+        const int wro = (wrow[h1s::DIST_FIRST] <= iv && iv < wrow[h1s::DIST_END]) ? WR0 + pc * h1s::DIST_REC : WR0 + (RPW + pc) * h1s::DIST_REC;
+        if (jtab) plant_step_table_j<KIND>(side_t, h, u, dyn, st, L, 0, lds + Lay::DOUBLES + pc * PLANT_REC, wro, JR0 + pc * h1s::JOINT_REC);
+        else if (disturbed) plant_step_table<KIND, true>(side_t, h, u, dyn, st, L, 0, lds + Lay::DOUBLES + pc * PLANT_REC, wro);
+        else plant_step_table<KIND>(side_t, h, u, dyn, st, L, 0, lds + Lay::DOUBLES + pc * PLANT_REC);
+#elif PLANT_TABLE == 6
         // the disturbance row as in family 3 (zeros without the tables), the joint record of the rollout beside it
         const double* wrow = lds + WR0 + pc * h1s::DIST_REC;
         const double iv = (double)(interval0 + j);

@@ -10,7 +10,8 @@
 // A translation unit of its own: no kernel of the solve shares a compilation with it.  k_plant_follow is plant_follow_body.h, included
 // seven times: without a table, with a plant parameter table (k_plant_follow_p), with a parameter and a wrench table (k_plant_follow_w),
 // with parameter, wrench and payload tables (k_plant_follow_m), with those three under an observation table (k_plant_follow_o), and with
-// those four under an actuator table (k_plant_follow_a), and with those five under a joint table (k_plant_follow_j).
+// those four under an actuator table (k_plant_follow_a), and with those five under a joint table (k_plant_follow_j); an eighth time, with
+// those six under a terrain table (k_plant_follow_t), by the terrain module.
 #include <hip/hip_runtime.h>
 
 #include "h1_cost_dev.h"
@@ -23,7 +24,7 @@ using namespace h1;
 
 namespace ilqr {
 
-// This file is compiled seven times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
+// This file is compiled eight times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
 // libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
 // which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
 // library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
@@ -39,14 +40,19 @@ namespace ilqr {
 // the observation family whose step takes a delayed, lagged and noisy torque, and k_actuator_draw), opened in the same way.
 // A sixth compilation, -DPLANT_JOINTS_MODULE into libilqr_hip_joints.so, is the joints family alone (k_plant_follow_j, the superset of the
 // actuator family whose step reads gain, torque range, damping and armature of every joint from a record, and k_step_j), opened in the same way.
-#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
+// A seventh compilation, -DPLANT_TERRAIN_MODULE into libilqr_hip_terrain.so, is the terrain family alone (k_plant_follow_t, the superset of the
+// joints family that decides each rollout's stance flags against a floor of the rollout's own height, and k_step_t), opened in the same way.
+#ifdef PLANT_TERRAIN_MODULE
+#define PLANT_LOWER_FAMILIES      // a family above the joints': everything the families below it are made of, none of their kernels
+#endif
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 #define DYN_STEP_WRENCH
 #define DYN_STEP_PAYLOAD     // ... carrying the payload too
 #endif
-#ifdef PLANT_JOINTS_MODULE
+#if defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 #define DYN_STEP_JOINTS      // ... and the copies that read a joint record as well
 #endif
-#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
+#if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 #define PLANT_MODULE         // a module: none of the library's own kernels and launchers
 #endif
 #include "dyn_step_shared.h"
@@ -331,7 +337,7 @@ __global__ void __launch_bounds__(64) k_step_w(int count, const double* x, const
 
 #endif
 
-#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
+#if defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 // ---- payload table (include/ilqr_hip.h ilqr_hip_plant_set_payload): k_plant_follow_m.  A rollout has two disturbance rows of h1s::DIST_REC doubles
 // in LDS behind the parameter rows, staged once per launch, consecutive lanes on consecutive doubles (12 KB at FB = 0, 1.5 KB at FB = 1):
 //   row r        the wrench record (F, T, r, first, end; zeros without a wrench table, wtab null), the payload record, padding
@@ -387,7 +393,7 @@ __global__ void __launch_bounds__(64) k_step_m(int count, const double* x, const
 
 #endif
 
-#if defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
+#if defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 // ---- observation table (include/ilqr_hip.h ilqr_hip_plant_set_observation): what the controller is told of the state.  One record of
 // OBS_REC = 100 doubles per rollout -- bias[50], sigma[50] in the tangent order of the Jacobians (dp, dphi, dq, dv, domega, dqdot) -- or ONE
 // record that every rollout reads (stride 0).  The error of rollout b in plant interval i is e = bias + sigma o z(seed, stream0 + b, i),
@@ -497,7 +503,7 @@ __global__ void __launch_bounds__(256) k_observe_apply(int B, const double* x, c
 }
 #endif
 
-#if defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE)
+#if defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 // ---- actuator table (include/ilqr_hip.h ilqr_hip_plant_set_actuator): what the joints get of the law's command.  One record of ACT_REC = 39
 // doubles per rollout -- delay (plant substeps, an integer 0..8), tau[19] (s), sigma[19] (N m) -- or ONE record that every rollout reads
 // (stride 0), and beside it the rows beta[19] = -expm1(-h / tau) that the host derived from it.  In substep n (counted from the priming)
@@ -556,7 +562,7 @@ DEVFN void actuator_stage(const DevState& S, double* lds, int b0, int ua0, const
   }
 }
 #endif
-#ifdef PLANT_JOINTS_MODULE
+#if defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 // ---- joint table (include/ilqr_hip.h ilqr_hip_plant_set_joints): k_plant_follow_j.  One record of h1s::JOINT_REC = 80 doubles (640 B) per rollout --
 // gain[19], range scale[19], damping[19], armature[19] in the order of u, four doubles of padding -- or ONE record that every rollout reads
 // (j_stride = 0).  Staged in LDS once per launch behind the rows of the actuator family, consecutive lanes on consecutive doubles (20 KB at
@@ -584,6 +590,8 @@ DEVFN void plant_step_table_j(bool side, h1s::HalfX& h, const h1s::HalfU& u, con
   for (int q = 0; q < 4; ++q) us.uA[q] = gain * u.uA[q];
   step_any_j<KIND>(side, h, us, dl, st, L, geom, wro, jro);
 }
+#endif
+#ifdef PLANT_JOINTS_MODULE
 #define PLANT_TABLE 6
 #include "plant_follow_body.h"
 
@@ -658,6 +666,77 @@ __global__ void __launch_bounds__(256) k_actuator_draw(int B, unsigned long long
     const int rr = it / PLANT_NU, i = it - rr * PLANT_NU;
     o[it] = zr[rr * 2 * ACT_BLK + i];
   }
+}
+#endif
+
+#ifdef PLANT_TERRAIN_MODULE
+// ---- terrain table (include/ilqr_hip.h ilqr_hip_plant_set_terrain): k_plant_follow_t.  One record of TERRAIN_REC = 8 doubles (64 B) per rollout --
+// z_left, z_right (the floor's height under each foot), edge_x (the height holds for a foot whose ankle-link origin has world x >= edge_x;
+// -inf: everywhere), the window [first, end) in plant intervals, three doubles of padding -- or ONE record that every rollout reads (t_stride = 0).
+// Staged in LDS once per launch behind the joint rows, consecutive lanes on consecutive doubles (2 KB at FB = 0, 256 B at FB = 1).
+#define TERRAIN_REC 8
+template <int RPW>
+DEVFN void stage_terrain_records(const DevState& S, double* rows, int b0, const double* ttab, int t_stride) {
+  for (int e = threadIdx.x; e < RPW * TERRAIN_REC; e += 64) {
+    const int r = e / TERRAIN_REC;
+    const int br = b0 + r < S.B ? b0 + r : S.B - 1;      // (a wave's unowned rows read the last rollout's record, as stage_plant_records)
+    rows[e] = ttab[(size_t)br * t_stride + (e - r * TERRAIN_REC)];
+  }
+}
+// Stance flags (left, right) of a substep from the pair's own state and the record `rec` in plant interval iv: foot f touches iff
+// clearance_f < floor_f, floor_f = z_f while the window is open and the foot's ankle-link origin is at x >= edge_x, else 0.  Each lane asks
+// h1s::foot_contact for its own foot at the base height pz - floor_own -- the link heights are sums that start from pz, so lowering the base
+// by the floor's height is the test against that floor, and with floor = 0 the subtraction is exact: the decision of h1s::geom_stance -- and
+// the pair swaps the answers as geom_stance does (both lanes of the pair must be active).  The ankle's x comes from the chain the height
+// comes from: h1s::leg_row2 with row 0 of the pelvis rotation and p_x in the place of row 2 and p_z.
+DEVFN void terrain_stance(bool side, const h1s::HalfX& hx, const double* rec, double iv, int& st_left, int& st_right) {
+  const double qw = hx.quat[0], qx = hx.quat[1], qy = hx.quat[2], qz = hx.quat[3];
+  const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+  const double w = qw / qn, x = qx / qn, y = qy / qn, z = qz / qn;
+  double r[3] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)};      // row 0 of the pelvis rotation (h1host quat_R)
+  double ax = hx.p[0];
+  h1s::leg_row2<0>(side, r, ax, hx.q.thL[0]);
+  h1s::leg_row2<1>(side, r, ax, hx.q.thL[1]);
+  h1s::leg_row2<2>(side, r, ax, hx.q.thL[2]);
+  h1s::leg_row2<3>(side, r, ax, hx.q.thL[3]);
+  h1s::leg_row2<4>(side, r, ax, hx.q.thL[4]);
+  const bool open = rec[3] <= iv && iv < rec[4];
+  const double zf = side ? rec[1] : rec[0];
+  const double floor_own = (open && ax >= rec[2]) ? zf : 0.0;
+  const bool own = h1s::foot_contact(side, hx.p[2] - floor_own, qw, qx, qy, qz, hx.q.thL[0], hx.q.thL[1], hx.q.thL[2], hx.q.thL[3], hx.q.thL[4]) != 0;
+  const bool par = h1s::xch_flag(own);
+  st_left = (side ? par : own) ? 1 : 0;
+  st_right = (side ? own : par) ? 1 : 0;
+}
+#define PLANT_TABLE 7
+#include "plant_follow_body.h"
+
+// ---- one step on a floor per item (ilqr_hip_step_terrain): k_step_s of dyn_split_kernels.hip behind the decision of terrain_stance -- the 32
+// items of a workgroup stage a record each behind the dynamics scratch, z_left, z_right, edge_x of the item under a window that is always
+// open -- and the flags it stepped with in stance_out[count][2].  CK 0 / 5 (no stance rows) decide nothing; the C API refuses them.
+#define STEP_T_LDS_BYTES ((h1s::LDS_SLOTS * 64 + 32 * TERRAIN_REC) * sizeof(double))
+template <int CK>
+__global__ void __launch_bounds__(64) k_step_t(int count, const double* x, const double* u, DynParams dyn, double* xn, const double* terrain, int* stance_out) {
+  extern __shared__ double lds[];
+  constexpr int TR0 = h1s::LDS_SLOTS * 64;
+  const int i0 = blockIdx.x * 32;
+  for (int e = threadIdx.x; e < 32 * TERRAIN_REC; e += 64) {
+    const int r = e / TERRAIN_REC, k = e - r * TERRAIN_REC;
+    const int ir = i0 + r < count ? i0 + r : count - 1;
+    lds[TR0 + e] = k < 3 ? terrain[(size_t)ir * 3 + k] : k == 4 ? __builtin_inf() : 0.0;
+  }
+  wave_lds_fence();
+  const int i = i0 + ((int)threadIdx.x >> 1);
+  const bool side = (threadIdx.x & 1) != 0;
+  if (i >= count) return;
+  const h1s::LaneLds L{lds, 64, (int)threadIdx.x};
+  h1s::HalfX h; h1s::load_half(side, x + (size_t)i * H1_NX, h);
+  h1s::HalfU uu; load_half_u(side, u + (size_t)i * H1_NU, uu);
+  int st[2] = {1, 1};
+  if constexpr (CK >= 1 && CK <= 4) terrain_stance(side, h, lds + TR0 + ((int)threadIdx.x >> 1) * TERRAIN_REC, 0.0, st[0], st[1]);
+  step_any<CK>(side, h, uu, dyn, st, L, 0);
+  h1s::store_half(side, h, xn + (size_t)i * H1_NX);
+  if (!side) { stance_out[2 * (size_t)i] = st[0]; stance_out[2 * (size_t)i + 1] = st[1]; }
 }
 #endif
 
@@ -860,6 +939,44 @@ static void launch_step_joints(int count, const double* x, const double* u, cons
   const dim3 grid((unsigned)((count + 31) / 32));
   with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_j<K()>), grid, dim3(64), STEP_J_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench, payload, joints); });
 }
+#elif defined(PLANT_TERRAIN_MODULE)      // attributes and launchers of the terrain family, exported from its module with C linkage (ilqr_kernels.h)
+template <int FB> static constexpr size_t follow_lds_t() {
+  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX + FollowLayout<FB>::RPW * PLANT_NU +
+          FollowLayout<FB>::RPW * h1s::JOINT_REC + FollowLayout<FB>::RPW * TERRAIN_REC) * sizeof(double);
+}
+static_assert(follow_lds_t<0>() <= 160 * 1024 && follow_lds_t<1>() <= 160 * 1024, "k_plant_follow_t: the workgroup's LDS");
+template <int KIND, int FB> static int plant_attr_t() {
+  return hipFuncSetAttribute((const void*)k_plant_follow_t<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_t<FB>()) != hipSuccess;
+}
+template <int KIND> static int step_attr_t() {
+  return hipFuncSetAttribute((const void*)k_step_t<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_T_LDS_BYTES) != hipSuccess;
+}
+static int terrain_kernels_set_attr() {
+  int rc = 0;
+  for_each_step_kind([&](auto K) { rc |= plant_attr_t<K(), 0>(); rc |= plant_attr_t<K(), 1>(); rc |= step_attr_t<K()>(); });
+  return rc;
+}
+template <int KIND, int FB>
+static void follow_launch_t(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const ActuatorTable& A,
+                            const JointTable& J, const TerrainTable& R, const FollowArgs& a, hipStream_t st) {
+  typedef FollowLayout<FB> Lay;
+  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
+  hipLaunchKernelGGL((k_plant_follow_t<KIND, FB>), grid, dim3(64), follow_lds_t<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
+                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs, A.records, A.rec_stride, A.blend, A.blend_stride, A.z, A.fifo, A.y, A.applied,
+                     A.substep0, J.records, J.rec_stride, R.records, R.rec_stride);
+}
+static void launch_plant_follow_terrain(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs,
+                                        const ActuatorTable& A, const JointTable& J, const TerrainTable& R, const WrenchFollowArgs& w, hipStream_t st) {
+  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
+  with_step_kind(dyn, [&](auto K) {
+    if (w.feedback_mode) follow_launch_t<K(), 1>(S, Pl, dyn, T, W, M, dobs, A, J, R, a, st);
+    else follow_launch_t<K(), 0>(S, Pl, dyn, T, W, M, dobs, A, J, R, a, st);
+  });
+}
+static void launch_step_terrain(int count, const double* x, const double* u, const DynParams& dyn, double* xn, const double* terrain, int* stance_out, hipStream_t st) {
+  const dim3 grid((unsigned)((count + 31) / 32));
+  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_t<K()>), grid, dim3(64), STEP_T_LDS_BYTES, st, count, x, u, dyn, xn, terrain, stance_out); });
+}
 #else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
 template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
 template <int KIND, int FB> static int plant_attr_w() {
@@ -956,6 +1073,19 @@ void ilqr_joints_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl
 void ilqr_joints_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload,
                              const double* joints, hipStream_t st) {
   ilqr::launch_step_joints(count, x, u, *dyn, xn, stance_l, stance_r, wrench, payload, joints, st);
+}
+}
+#endif
+
+#ifdef PLANT_TERRAIN_MODULE
+extern "C" {
+int ilqr_terrain_module_set_attr() { return ilqr::terrain_kernels_set_attr(); }
+void ilqr_terrain_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
+                                const double* delta, const ilqr::ActuatorTable* A, const ilqr::JointTable* J, const ilqr::TerrainTable* R, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
+  ilqr::launch_plant_follow_terrain(*S, *Pl, *dyn, *T, *W, *M, delta, *A, *J, *R, *a, st);
+}
+void ilqr_terrain_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, const double* terrain, int* stance_out, hipStream_t st) {
+  ilqr::launch_step_terrain(count, x, u, *dyn, xn, terrain, stance_out, st);
 }
 }
 #endif

@@ -7,7 +7,7 @@
 namespace ilqr {
 
 // Each family from PARAMS on is the superset of the one before it (every table below its own may be absent), so the family is decided by
-// the highest table installed.  WRENCH .. JOINTS live in modules of their own (csrc/Makefile), ADVANCE .. PARAMS in the library.
+// the highest table installed.  WRENCH .. TERRAIN live in modules of their own (csrc/Makefile), ADVANCE .. PARAMS in the library.
 enum PlantFamily {
   PLANT_ADVANCE = 0,        // k_plant_advance: no table, one interval
   PLANT_FOLLOW,             // k_plant_follow: no table, several intervals
@@ -16,13 +16,15 @@ enum PlantFamily {
   PLANT_PAYLOAD,            // k_plant_follow_m
   PLANT_OBSERVE,            // k_plant_follow_o behind the draw of the call's error rows
   PLANT_ACTUATOR,           // k_plant_follow_a behind the draw of the call's normals
-  PLANT_JOINTS              // k_plant_follow_j
+  PLANT_JOINTS,             // k_plant_follow_j
+  PLANT_TERRAIN             // k_plant_follow_t
 };
 // the modules, in the order of their families; a bit of PlantPlan::modules each
-enum PlantModule { MOD_WRENCH = 0, MOD_PAYLOAD, MOD_OBSERVE, MOD_ACTUATOR, MOD_JOINTS, PLANT_MODULES };
+enum PlantModule { MOD_WRENCH = 0, MOD_PAYLOAD, MOD_OBSERVE, MOD_ACTUATOR, MOD_JOINTS, MOD_TERRAIN, PLANT_MODULES };
 
 // which tables are installed; joints_nominal: the joint table holds the model's own joints in every record -- such a table is no table
-struct PlantTables { bool params, wrench, payload, observation, actuator, joints, joints_nominal; };
+// (terrain is the last member: an initialiser that names the seven above leaves it false)
+struct PlantTables { bool params, wrench, payload, observation, actuator, joints, joints_nominal, terrain; };
 struct PlantPlan {
   PlantFamily family;
   unsigned modules;         // bit PlantModule of every module the call calls into
@@ -33,7 +35,7 @@ struct PlantPlan {
 
 inline PlantPlan resolve_plant_plan(const PlantTables& t, bool follow) {
   PlantPlan p{};
-  p.family = (t.joints && !t.joints_nominal) ? PLANT_JOINTS : t.actuator ? PLANT_ACTUATOR : t.observation ? PLANT_OBSERVE : t.payload ? PLANT_PAYLOAD
+  p.family = t.terrain ? PLANT_TERRAIN : (t.joints && !t.joints_nominal) ? PLANT_JOINTS : t.actuator ? PLANT_ACTUATOR : t.observation ? PLANT_OBSERVE : t.payload ? PLANT_PAYLOAD
            : t.wrench ? PLANT_WRENCH : t.params ? PLANT_PARAMS : follow ? PLANT_FOLLOW : PLANT_ADVANCE;
   p.draw_observation = t.observation && p.family >= PLANT_OBSERVE;
   p.draw_actuator = t.actuator && p.family >= PLANT_ACTUATOR;
@@ -41,7 +43,7 @@ inline PlantPlan resolve_plant_plan(const PlantTables& t, bool follow) {
   if (p.draw_observation) p.modules |= 1u << MOD_OBSERVE;
   if (p.draw_actuator) p.modules |= 1u << MOD_ACTUATOR;
   // (an all-nominal joint table counts here: the record is uploaded although no family reads it)
-  p.self_params = (t.wrench || t.payload || t.observation || t.actuator || t.joints) && !t.params;
+  p.self_params = (t.wrench || t.payload || t.observation || t.actuator || t.joints || t.terrain) && !t.params;
   return p;
 }
 

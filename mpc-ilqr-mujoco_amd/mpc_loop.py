@@ -73,6 +73,11 @@ joint and rollout (BatchedILQR.plant_set_actuator).  The log and the score keep 
 `MPCRunner(..., resident=True, plant_joints=J)` gives every rollout's plant joints of its own: J [1, 76] or [B, 76]
 (scenario.stack_plant_joints) is a torque gain, a scale on the torque range, a damping and an armature per joint and rollout
 (BatchedILQR.plant_set_joints), installed in front of the reset.  The log and the score keep the commanded torque; the solve keeps the model's joints.
+
+`MPCRunner(..., resident=True, plant_contacts="geometry", plant_terrain=T)` puts a floor of its own height under each rollout's feet: T [1, 5]
+or [B, 5] (scenario.stack_plant_terrain) is a height under the left and the right foot, an edge in x behind which the height holds and the
+window of plant intervals it holds in, counted from the reset of the run (BatchedILQR.plant_set_terrain), installed behind the joints, in
+front of the reset.  The plant's feet land and lift against that floor; the solve and the score's schedule know nothing of it.
 """
 import os
 import time
@@ -118,7 +123,8 @@ class MPCRunner:
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
                  device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None,
-                 plant_observation=None, observation_seed=0, observation_stream0=0, plant_actuator=None, actuator_seed=0, actuator_stream0=0, plant_joints=None):
+                 plant_observation=None, observation_seed=0, observation_stream0=0, plant_actuator=None, actuator_seed=0, actuator_stream0=0, plant_joints=None,
+                 plant_terrain=None):
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -177,6 +183,15 @@ class MPCRunner:
             if plant_joints.ndim != 2 or plant_joints.shape[1] != 76 or plant_joints.shape[0] not in (1, solver.B):
                 raise ValueError("plant_joints must be [1, 76] or [B, 76] (scenario.stack_plant_joints)")
         self.plant_joints = plant_joints
+        if not resident and plant_terrain is not None:
+            raise ValueError("plant_terrain needs the device-resident plant (resident=True)")
+        if plant_terrain is not None:
+            if plant_contacts != "geometry":
+                raise ValueError("plant_terrain needs plant_contacts='geometry': with the schedule as the contact source nothing consults the floor")
+            plant_terrain = np.atleast_2d(np.asarray(plant_terrain, dtype=np.float64))
+            if plant_terrain.ndim != 2 or plant_terrain.shape[1] != 5 or plant_terrain.shape[0] not in (1, solver.B):
+                raise ValueError("plant_terrain must be [1, 5] or [B, 5] (scenario.stack_plant_terrain)")
+        self.plant_terrain = plant_terrain
         self.device_refs, self.track_ready = bool(device_refs), False
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
@@ -321,6 +336,8 @@ class MPCRunner:
             s.plant_set_actuator(self.plant_actuator, seed=self.actuator_seed, stream0=self.actuator_stream0)
         if self.plant_joints is not None:
             s.plant_set_joints(self.plant_joints)
+        if self.plant_terrain is not None:
+            s.plant_set_terrain(self.plant_terrain)
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)

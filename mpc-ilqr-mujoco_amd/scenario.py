@@ -287,6 +287,52 @@ def stack_plant_joints(records, B):
     return out
 
 
+# fields of a terrain record in record order with their flat defaults (solver.PLANT_TERRAIN): the solver's ground, everywhere, always
+_TERRAIN_FIELDS = (("z_left", 0.0), ("z_right", 0.0), ("edge_x", -np.inf), ("first", 0.0), ("end", np.inf))
+
+
+def stack_plant_terrain(records, B):
+    """Floors [B, 5] for BatchedILQR.plant_set_terrain / MPCRunner(plant_terrain=...): z_left, z_right (floor height under the left / right
+    foot, m), edge_x (the height holds for a foot whose ankle is at world x >= edge_x, m; -inf: everywhere), first and end of the window of
+    plant intervals the record acts in (first <= i < end, counted from plant_reset).  records is one dict (every rollout) or a sequence of B
+    dicts; a dict holds any of these five scalars, what it leaves out is flat (0, 0, -inf, 0, inf), so {} is the solver's ground.  Raises
+    ValueError for another key, a value that is no scalar, a sequence that is not B long, a non-finite height, an edge that is neither finite
+    nor -inf, a negative or non-integral first / end (end may be inf) or end < first -- what ilqr_hip_plant_set_terrain refuses."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    if isinstance(records, dict):
+        records = [records] * B
+    records = list(records)
+    if len(records) != B:
+        raise ValueError("records must be one dict or B of them")
+    out = np.empty((B, 5))
+    names = [f for f, _ in _TERRAIN_FIELDS]
+    for b, rec in enumerate(records):
+        if not isinstance(rec, dict):
+            raise ValueError("a terrain record is a dict")
+        extra = set(rec) - set(names)
+        if extra:
+            raise ValueError("unknown terrain field(s) %s: a record has %s" % (sorted(extra), names))
+        for k, (name, flat) in enumerate(_TERRAIN_FIELDS):
+            v = np.asarray(rec.get(name, flat), dtype=np.float64)
+            if v.shape != ():
+                raise ValueError("%s must be a scalar" % name)
+            out[b, k] = v
+    if not np.isfinite(out[:, :2]).all():
+        raise ValueError("floor heights must be finite")
+    if np.isnan(out[:, 2]).any() or (out[:, 2] == np.inf).any():
+        raise ValueError("edge_x must be finite or -inf")
+    if not np.isfinite(out[:, 3]).all() or np.isnan(out[:, 4]).any() or (out[:, 4] == -np.inf).any():
+        raise ValueError("first must be finite, end finite or inf")
+    fin_end = np.where(np.isfinite(out[:, 4]), out[:, 4], 0.0)
+    if (out[:, 3] < 0).any() or (out[:, 4] < 0).any() or (out[:, 3] != np.floor(out[:, 3])).any() or (fin_end != np.floor(fin_end)).any():
+        raise ValueError("first and end must be non-negative integers")
+    if (out[:, 4] < out[:, 3]).any():
+        raise ValueError("end >= first is required")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

@@ -56,6 +56,8 @@ EXPORTS = [
     "ilqr_hip_plant_set_actuator", "ilqr_hip_plant_clear_actuator", "ilqr_hip_plant_num_actuator_sets", "ilqr_hip_plant_get_actuator",
     "ilqr_hip_plant_get_actuator_blend", "ilqr_hip_plant_actuator_draws", "ilqr_hip_plant_get_applied",
     "ilqr_hip_plant_set_joints", "ilqr_hip_plant_get_joints", "ilqr_hip_step_joints",
+    "ilqr_hip_plant_set_terrain", "ilqr_hip_plant_clear_terrain", "ilqr_hip_plant_num_terrain_sets", "ilqr_hip_plant_get_terrain", "ilqr_hip_step_terrain",
+    "ilqr_hip_terrain_stance",
 ]
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
@@ -77,6 +79,8 @@ PLANT_ACTUATOR_MAX_DELAY = 8
 # fields of a plant joint record (include/ilqr_hip.h ILQR_PLANT_JOINTS), 19 values each in the order of u, with their nominal values
 PLANT_JOINT_FIELDS = (("gain", 1.0), ("range_scale", 1.0), ("damping", 1.0), ("armature", 0.1))
 PLANT_JOINTS = 76
+# columns of a plant terrain record (include/ilqr_hip.h ILQR_PLANT_TERRAIN)
+PLANT_TERRAIN = ("z_left", "z_right", "edge_x", "first", "end")
 
 
 
@@ -152,6 +156,21 @@ def reference_com_velocity(x):
     if rc:
         raise ILQRError(STATUS.get(rc, str(rc)))
     return cv
+
+
+def terrain_stance(qpos, terrain, interval=0):
+    """(stance[2], floor[2]) of qpos[26] on the floor of the record terrain[5] (columns PLANT_TERRAIN) in plant interval `interval`: foot f
+    touches iff foot_clearance(qpos)[f] < floor[f], floor[f] = z_f while the window holds the interval and the foot's ankle-link origin is at
+    world x >= edge_x, else 0 (ilqr_hip_terrain_stance: the rule of the plant under plant_set_terrain, on the host)."""
+    L = load_library()
+    q, t = _c64(qpos), _c64(terrain)
+    if q.shape != (26,) or t.shape != (len(PLANT_TERRAIN),):
+        raise ValueError("qpos must have 26 entries (MuJoCo order), terrain 5")
+    st, fl = np.zeros(2, dtype=np.int32), np.zeros(2)
+    rc = L.ilqr_hip_terrain_stance(_p(q), _p(t), C.c_long(int(interval)), st.ctypes.data_as(C.POINTER(C.c_int)), _p(fl))
+    if rc:
+        raise ILQRError(STATUS.get(rc, str(rc)))
+    return st, fl
 
 
 def foot_clearance(qpos):
@@ -581,6 +600,15 @@ class BatchedILQR:
         self._chk(self.L.ilqr_hip_step_joints(self.h, int(x.shape[0]), _p(x), _p(u), int(stance_left), int(stance_right), _p(wrench), _p(payload), _p(joints), _p(xn)))
         return xn
 
+    def step_terrain(self, x, u, terrain):
+        """(x_next, stance [count, 2]): one step per item under the flags its own feet give on the floor terrain[i] = z_left, z_right, edge_x
+        (terrain_stance with the window open), decided on the device; contact modes 2-4, always the two-lane step (ilqr_hip_step_terrain)."""
+        x, u = _c64(x), _c64(u)
+        terrain = _rows(_c64(terrain), x.shape[0], 3, "terrain")
+        xn, st = np.zeros_like(x), np.zeros((x.shape[0], 2), dtype=np.int32)
+        self._chk(self.L.ilqr_hip_step_terrain(self.h, int(x.shape[0]), _p(x), _p(u), _p(terrain), _p(xn), st.ctypes.data_as(C.POINTER(C.c_int))))
+        return xn, st
+
     def set_stance_source(self, source):
         """Stance source of the dynamics (include/ilqr_hip.h): "schedule" (default) or "geometry" -- every step takes the stance flags from
         its own feet (a foot touches iff its ankle-link hull reaches the floor, foot_clearance < 0); the cost keeps the schedule."""
@@ -794,6 +822,27 @@ class BatchedILQR:
     def plant_get_joints(self):
         """[B, 76]: the record of each rollout; the nominal record without a table."""
         return self._get("ilqr_hip_plant_get_joints", (self.B, PLANT_JOINTS))
+
+    def plant_set_terrain(self, terrain):
+        """Install floors [n_sets, 5] (columns PLANT_TERRAIN; scenario.stack_plant_terrain builds them), n_sets 1 or B: in the plant intervals
+        first <= i < end rollout b's feet land and lift against a floor of height z_left / z_right where their ankle is at x >= edge_x, and
+        against z = 0 elsewhere (ilqr_hip_plant_set_terrain).  None clears.  Needs the stance source "geometry" and a plant contact mode
+        2-4: a plant call under another configuration raises.  The solve does not know of it."""
+        if terrain is None:
+            return self.plant_clear_terrain()
+        terrain = _table(terrain, self.B, len(PLANT_TERRAIN), "terrain records")
+        self._chk(self.L.ilqr_hip_plant_set_terrain(self.h, _p(terrain), int(terrain.shape[0])))
+
+    def plant_clear_terrain(self):
+        """Remove the floors: the plant calls launch what they launch without them."""
+        self._chk(self.L.ilqr_hip_plant_clear_terrain(self.h))
+
+    def plant_num_terrain_sets(self):
+        return int(self.L.ilqr_hip_plant_num_terrain_sets(self.h))
+
+    def plant_get_terrain(self):
+        """[B, 5] (columns PLANT_TERRAIN): the record of each rollout; without a table heights 0, edge -inf and an empty window."""
+        return self._get("ilqr_hip_plant_get_terrain", (self.B, len(PLANT_TERRAIN)))
 
     def plant_set_observation(self, observation, seed=0, stream0=0):
         """Install observation models [n_sets, 100] (bias[50], sigma[50] in tangent order; scenario.stack_plant_observation builds them),

@@ -46,7 +46,14 @@ in the given contact mode; then the plant call alone, events around 50 back-to-b
 compares, instead, the RESIDENT runner without a joint table against the same runner with one installed (MPCRunner(plant_joints=...): per
 rollout and joint a gain of 0.8 to 1, a range scale of 0.7 to 1, a damping of 0.5 to 2 and an armature of 0.05 to 0.2), alternating on one
 box, the plant in the given contact mode; then the plant call alone, events around 50 back-to-back advances: without a table, under the
-actuator table of --actuator alone (the family the joints family widens) and under the joint table alone."""
+actuator table of --actuator alone (the family the joints family widens) and under the joint table alone.
+
+   python tools/closed_loop_time.py --terrain [--contact-mode 2] ...
+times the plant call alone, events around 50 back-to-back advances, three repetitions from the same plant state, the plant in the given
+contact mode (2, 3 or 4): without a table and under the joint table of --joints with the schedule as the contact source, the same two with
+the plant's own feet as the source, and under a terrain table alone (MPCRunner's plant_terrain: per rollout a floor of -2 to 2 cm under
+each foot from interval 1 on) -- which needs that source.  A library without the terrain entry points (ILQR_HIP_LIB naming an older build)
+times the first four: run the tool under both libraries in turn to compare the families on one box."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py): behind the product library, torch finds "no HIP GPUs" when it is asked for the device name
@@ -72,6 +79,7 @@ def main():
     ap.add_argument("--observation", action="store_true")
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--joints", action="store_true")
+    ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--device-refs", action="store_true"); ap.add_argument("--per-rollout-starts", action="store_true"); ap.add_argument("--contact-mode", type=int, default=2)
     a = ap.parse_args()
     if a.per_rollout_starts and not a.device_refs:
@@ -95,6 +103,8 @@ def main():
         return actuator_main(a, sc, ml, rf, sv)
     if a.joints:
         return joints_main(a, sc, ml, rf, sv)
+    if a.terrain:
+        return terrain_main(a, sc, ml, rf, sv)
     base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
     rd = rf.ReferenceData(sv.reference_kinematics, sv.reference_com_velocity)
     rows = a.steps + N + 10
@@ -399,6 +409,50 @@ def joints_main(a, sc, ml, rf, sv):
                       "substeps": a.substeps, "feedback_mode": a.feedback_mode, "solve_every": a.solve_every, "contact_mode": a.contact_mode,
                       "ms_per_step_resident_plant": float(np.median(ms[False])), "ms_per_step_resident_plant_with_joints": float(np.median(ms[True])),
                       "samples_no_joints": ms[False], "samples_joints": ms[True], "alive_no_joints": alive[False], "alive_joints": alive[True]}))
+
+
+def terrain_main(a, sc, ml, rf, sv):
+    B, N = a.batch, a.horizon
+    if a.contact_mode not in (2, 3, 4):
+        raise SystemExit("--terrain needs --contact-mode 2, 3 or 4")
+    base = sc.make_problem(sv.reference_kinematics, N=N, gravity=(0.0, 0.0, -9.81))
+    x0, ui = sc.synthetic_batch(B, N, 0, sv.gravity_compensation(sc.standing_state(), base["gravity"]))
+    rng = np.random.default_rng(1)
+    joints = sc.stack_plant_joints([dict(gain=rng.uniform(0.8, 1.0, 19), range_scale=rng.uniform(0.7, 1.0, 19), damping=rng.uniform(0.5, 2.0, 19), armature=rng.uniform(0.05, 0.2, 19))
+                                    for _ in range(B)], B)
+    floors = rng.uniform(-0.02, 0.02, (B, 2))
+    terrain = sc.stack_plant_terrain([dict(z_left=floors[b, 0], z_right=floors[b, 1], first=1) for b in range(B)], B)
+    has_terrain = hasattr(sv.load_library(), "ilqr_hip_plant_set_terrain")
+    kernel_us, alive_k = {}, {}
+    s = sv.BatchedILQR(B, N=N, dt=base["dt"]); s.set_max_iterations(a.iters); s.set_options(early_exit=False)
+    s.set_problem(base); s.initialize(x0, ui); s.solve(x0)
+    s.plant_set_model(a.contact_mode, None)
+    st = torch.cuda.ExternalStream(s.stream)
+    cases = [("no_table", "schedule"), ("joint_table", "schedule"), ("no_table", "geometry"), ("joint_table", "geometry")] + ([("terrain_table", "geometry")] if has_terrain else [])
+    for tab, source in cases:
+        s.plant_clear_joints()
+        if has_terrain:
+            s.plant_clear_terrain()
+        s.plant_configure(a.substeps, a.feedback_mode, source)
+        if tab == "joint_table":
+            s.plant_set_joints(joints)
+        if tab == "terrain_table":
+            s.plant_set_terrain(terrain)
+        us = []
+        for rep_ in range(4):                        # (the first repetition warms up)
+            s.plant_reset(x0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(50):
+                s.plant_advance()
+            e1.record(st); e1.synchronize()
+            us.append(1e3 * e0.elapsed_time(e1) / 50)
+        key = "mode%d_%s_%s" % (a.contact_mode, tab, source)
+        kernel_us[key], alive_k[key] = us[1:], int(s.plant_alive().sum())
+    s.close()
+    print(json.dumps({"tool": "closed_loop_time", "mode": "terrain", "library": sv.LIB_PATH, "plant_call_us": {k: float(np.median(v)) for k, v in kernel_us.items()},
+                      "plant_call_samples_us": kernel_us, "alive_after_50_advances": alive_k, "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N,
+                      "iterations": a.iters, "substeps": a.substeps, "feedback_mode": a.feedback_mode, "contact_mode": a.contact_mode}))
 
 
 class HostWindows:
