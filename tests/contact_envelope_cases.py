@@ -2,7 +2,7 @@
 (test_contact_envelope_cpu.py, test_gpu_contact_envelope.py), beside dynamics_envelope_cases.py, whose states, schedule and step-continuity
 rule they reuse.  NumPy and the CPU oracle only; no GPU.
 
-Sixteen states per group, physical gravity, h = 0.02, N = 4 under SCHEDULE: knot p steps under STANCE_ROWS[p] (both feet, left only, right
+Sixteen states per group, physical gravity, h = 0.02 unless `h` is given, N = 4 under SCHEDULE: knot p steps under STANCE_ROWS[p] (both feet, left only, right
 only, none) and every knot of rollout i carries state i.  Contact mode 0 has no stance rows: one case per state there, not four.
 
   * sliding group:  mid() (rotation +-0.5 rad, hinges +-0.4 about standing, velocities +-3) at the friction coefficients MUS, and for
@@ -35,6 +35,9 @@ STEP_TOL, JAC_TOL = 1e-9, 1e-8  # the bounds of the existing tests of the stance
 SLIDING_VARIANTS = (("mid", 0.3), ("mid", 0.7), ("nonunit", 0.3), ("clamped", 0.3))
 # step_kind (dyn_step_shared.h) -> (contact mode, joint-limit rows): the instantiations of the rollout / line-search kernels
 STEP_KINDS = {1: (2, False), 2: (4, False), 3: (2, True), 4: (4, True), 5: (0, True)}
+# (kind, h) of test_gpu_timestep.py: sliding in modes 3 / 4 (mid, mu 0.3) and the joint-limit rows (mode 2, k 625) at the steps of
+# dc.TIMESTEPS at which the reference keeps at least the share of cases it keeps at 0.02 (test_timestep_cpu.py measures it)
+TIMESTEP_CASES = tuple((kind, h) for kind in ("sliding3", "sliding4", "limits2") for h in dc.TIMESTEPS)      # all of them: 64 of 64 pairs kept
 
 
 def rows(mode):
@@ -51,9 +54,9 @@ def configure(o, mu=None, limits=False, k=0.0):
     return o
 
 
-def oracle(mode, mu=None, limits=False, k=0.0, **opts):
+def oracle(mode, mu=None, limits=False, k=0.0, h=H, **opts):
     """the oracle of a mode: N = 4 under SCHEDULE, or (mode 0) N = 1"""
-    o = dc.oracle(N=4, mode=mode, stance=dc.SCHEDULE, **opts) if mode else dc.oracle(N=1, **opts)
+    o = dc.oracle(N=4, mode=mode, stance=dc.SCHEDULE, h=h, **opts) if mode else dc.oracle(N=1, h=h, **opts)
     return configure(o, mu, limits, k)
 
 
@@ -167,10 +170,10 @@ def violation(x):
     return np.where(th > jr[:, 1], th - jr[:, 1], np.where(th < jr[:, 0], th - jr[:, 0], 0.0))
 
 
-def stopped_hinges(x, xn, k):
+def stopped_hinges(x, xn, k, h=H):
     """[n,P,19] bool: hinge j of state i is stopped in the step x[i] -> xn[i,p] when its new velocity is the row's, v+ = -h k r, to 1e-10"""
     r = violation(x)[:, None, :]
-    return np.abs(xn[..., NQ + 6:] + H * k * r) < 1e-10
+    return np.abs(xn[..., NQ + 6:] + h * k * r) < 1e-10
 
 
 def _freeze(*arrays):
@@ -180,38 +183,38 @@ def _freeze(*arrays):
 
 
 @functools.lru_cache(maxsize=None)
-def mode2_steps(variant="mid"):
-    """the oracle's mode-2 step of the sliding states, [16,4,51]: what a step without the cone is; computed once, read-only"""
+def mode2_steps(variant="mid", h=H):
+    """the oracle's mode-2 step of the sliding states, [16,4,51]: what a step without the cone is; computed once per time step, read-only"""
     x, u, _ = sliding_states(variant)
-    return _freeze(steps(oracle(2), x, u, 2))[0]
+    return _freeze(steps(oracle(2, h=h), x, u, 2))[0]
 
 
 @functools.lru_cache(maxsize=None)
-def sliding_cases(mode, mu, variant="mid"):
+def sliding_cases(mode, mu, variant="mid", h=H):
     """dict of a sliding parametrisation: x, u, beyond, kept [16,4], A, B (AD), step [16,4,51], slides [16,4] (the oracle's mode-3 step
-    differs from its mode-2 step by more than 1e-6), drift.  Computed once and shared: read-only"""
+    differs from its mode-2 step by more than 1e-6), drift.  Computed once per time step and shared: read-only"""
     x, u, beyond = sliding_states(variant)
-    o = oracle(mode, mu)
+    o = oracle(mode, mu, h=h)
     A, B = jacobians(o, x, u)
     kept, drift = kept_cases(o, x, u, mode, A)
     xn = steps(o, x, u, mode)
-    x3 = xn if mode == 3 else steps(oracle(3, mu), x, u, 3)
-    slides = np.abs(x3 - mode2_steps(variant)).max(axis=2) > 1e-6
+    x3 = xn if mode == 3 else steps(oracle(3, mu, h=h), x, u, 3)
+    slides = np.abs(x3 - mode2_steps(variant, h)).max(axis=2) > 1e-6
     _freeze(x, u, beyond, kept, A, B, xn, slides)
     return dict(x=x, u=u, beyond=beyond, kept=kept, A=A, B=B, step=xn, slides=slides, drift=drift)
 
 
 @functools.lru_cache(maxsize=None)
-def limit_cases(mode, k):
+def limit_cases(mode, k, h=H):
     """dict of a joint-limit parametrisation: x, u, kept [16,P], A, B (AD), step [16,P,51], stopped [16,P,19], drift, cls, end; P = 4, or 1
-    in mode 0.  Computed once and shared: read-only"""
+    in mode 0.  Computed once per time step and shared: read-only"""
     x, u = limit_states()
     cls, end = limit_pattern()
-    o = oracle(mode, MU_LIMITS if mode >= 3 else None, True, k)
+    o = oracle(mode, MU_LIMITS if mode >= 3 else None, True, k, h=h)
     A, B = jacobians(o, x, u)
     kept, drift = kept_cases(o, x, u, mode, A)
     xn = steps(o, x, u, mode)
-    stopped = stopped_hinges(x, xn, k)
+    stopped = stopped_hinges(x, xn, k, h)
     _freeze(x, u, kept, A, B, xn, stopped, cls, end)
     return dict(x=x, u=u, kept=kept, A=A, B=B, step=xn, stopped=stopped, drift=drift, cls=cls, end=end)
 

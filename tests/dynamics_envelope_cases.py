@@ -2,7 +2,8 @@
 seeded STATES and CONTROLS at which every branch and factor of the analytic linearisation (h1_linearize_dev.h lin_prologue /
 lin_column, h1_linearize_contact_dev.h) and of the step carries weight.  NumPy and the CPU oracle only; no GPU.
 
-Sixteen states per group, physical gravity, h = 0.02; hinges strictly inside their ranges (the joint-limit rows have goldens of their own, and
+Sixteen states per group, physical gravity, h = 0.02 unless `h` is given (TIMESTEPS: the other steps the kernels are held to the oracle
+at; the builders set prob["dt"] = h, and a handle must be constructed with dt = prob["dt"]); hinges strictly inside their ranges (the joint-limit rows have goldens of their own, and
 contact_envelope_cases.py takes them and contact modes 3 / 4 off the standing pose).
 
   * wide():     hinges at 2 % .. 98 % of their ranges, base rotation vectors in +-3 rad (state 0: an angle of pi - 1e-3), all 25
@@ -28,6 +29,7 @@ sc = load_package().scenario
 NX, NU, NQ, NV = 51, 19, 26, 25
 NS = 16                                     # states per group
 H = 0.02
+TIMESTEPS = (0.005, 0.01, 0.04)               # the other time steps of test_timestep_cpu.py / test_gpu_timestep.py
 GRAVITY = (0.0, 0.0, -9.81)
 SEED = 20
 STANCE_ROWS = np.array([[1, 1], [1, 0], [0, 1], [0, 0]], dtype=np.int32)
@@ -35,16 +37,21 @@ SCHEDULE = np.vstack([STANCE_ROWS, STANCE_ROWS[:1]])       # N = 4: knot p steps
 SPIN_THRESHOLD = 1e-6
 # s = |h w'|^2 of spin() state i: eight below the threshold (one within a factor 2), eight above (one within a factor 2, two above 1e-2)
 SPIN_S = np.array([1e-14, 1e-11, 1e-9, 3e-8, 1e-7, 3e-7, 6e-7, 9.5e-7, 1.05e-6, 1.6e-6, 4e-6, 3e-5, 1e-3, 6e-3, 2e-2, 6e-2])
+POS = np.r_[0:3, 7:26]; VEL = np.r_[26:29, 32:51]          # position rows of A and the velocity rows they are e_p + h x of
+E_POS = np.zeros((22, NX)); E_POS[np.arange(22), POS] = 1.0
 QUAT_SCALE = np.array([0.5, 1.6, 0.7, 1.3, 0.9, 1.1, 0.6, 1.45, 0.8, 1.2, 0.55, 1.55, 0.95, 1.05, 0.65, 1.35])
 
 
-def problem(N=2, stance=None, gravity=GRAVITY):
-    """shipped problem under physical gravity; `stance` [N+1,2] (default: both feet at every knot)"""
-    return sc.make_problem(ol.reference_kinematics, N=N, gravity=gravity, stance=stance)
+def problem(N=2, stance=None, gravity=GRAVITY, h=H):
+    """shipped problem under physical gravity with prob["dt"] = h; `stance` [N+1,2] (default: both feet at every knot)"""
+    prob = sc.make_problem(ol.reference_kinematics, N=N, gravity=gravity, stance=stance)
+    assert prob["dt"] == H
+    prob["dt"] = float(h)
+    return prob
 
 
-def oracle(N=2, mode=0, stance=None, gravity=GRAVITY, **opts):
-    prob = problem(N, stance, gravity)
+def oracle(N=2, mode=0, stance=None, gravity=GRAVITY, h=H, **opts):
+    prob = problem(N, stance, gravity, h)
     o = ol.Oracle(N, prob["dt"]); o.set_problem(prob); o.set_contact_mode(mode)
     if opts:
         o.set_options(**opts)
@@ -112,23 +119,23 @@ def pulled_inside(u):
     return np.clip(u, -0.9 * sc.CTRLRANGE, 0.9 * sc.CTRLRANGE)
 
 
-def spin_s(x, u, o=None):
-    """s = |h w'|^2 of every state: w' the post-step base angular velocity of the oracle's constraint-free step"""
-    o = o or oracle()
-    return np.array([(H * H) * (o.step(xi, ui)[NQ + 3:NQ + 6] ** 2).sum() for xi, ui in zip(x, u)])
+def spin_s(x, u, o=None, h=H):
+    """s = |h w'|^2 of every state: w' the post-step base angular velocity of the oracle's constraint-free step (`o`: an oracle AT `h`)"""
+    o = o or oracle(h=h)
+    return np.array([(h * h) * (o.step(xi, ui)[NQ + 3:NQ + 6] ** 2).sum() for xi, ui in zip(x, u)])
 
 
-def spin():
+def spin(h=H):
     """(x, u): wide() with w chosen so that w' = sqrt(SPIN_S[i]) / h along a seeded direction (fixed point of w <- w - (w'(w) - target):
-    d w' / d w = I + O(h))"""
+    d w' / d w = I + O(h): it contracts by 0.03 per pass at h = 0.02 and by 0.74 at h = 0.04, hence the cap of 600 passes)"""
     x, u = wide()
     x = x.copy()
-    o = oracle()
+    o = oracle(h=h)
     rng = np.random.default_rng(SEED + 1)
     d = rng.standard_normal((NS, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
     for i in range(NS):
-        target = d[i] * np.sqrt(SPIN_S[i]) / H
-        for _ in range(60):
+        target = d[i] * np.sqrt(SPIN_S[i]) / h
+        for _ in range(600):
             r = o.step(x[i], u[i])[NQ + 3:NQ + 6] - target
             if np.abs(r).max() < 1e-13 * max(1.0, np.abs(target).max()):
                 break
@@ -155,12 +162,12 @@ def mid():
     return x, u
 
 
-def contact_kept(mode, x, u, o=None, rows=STANCE_ROWS):
+def contact_kept(mode, x, u, o=None, rows=STANCE_ROWS, h=H):
     """kept [16,4] (bool; column p = STANCE_ROWS[p]): the oracle's contact-mode step is continuous at the state -- its result at the
     state and at the state with its velocities scaled by (1 +- 1e-7) differ by less than 1e-4 -- so no active-set decision of the
     unilateral rule sits on a rounding tie that the device may settle the other way.  `o`: an oracle with further settings (friction,
     joint-limit rows) in place of the plain one of `mode`; `rows`: the stance patterns, one column of `kept` each."""
-    o = o or oracle(mode=mode)
+    o = o or oracle(mode=mode, h=h)
     kept = np.zeros((len(x), len(rows)), dtype=bool)
     for i, (xi, ui) in enumerate(zip(x, u)):
         for p, st in enumerate(rows):
@@ -181,18 +188,18 @@ def stage_trajectory(x, u, N=2):
 FREE_GROUPS = ("wide", "nonunit", "negq", "clamped", "spin")
 
 
-def group(name):
-    """(x, u) of a free-flight group"""
-    return dict(wide=wide, nonunit=nonunit, negq=negq, clamped=lambda: clamped()[:2], spin=spin)[name]()
+def group(name, h=H):
+    """(x, u) of a free-flight group (only spin depends on the time step)"""
+    return dict(wide=wide, nonunit=nonunit, negq=negq, clamped=lambda: clamped()[:2], spin=lambda: spin(h))[name]()
 
 
-def oracle_jacobians(x, u, mode=0, jac_mode=0, fd_eps=1e-5, gravity=GRAVITY):
+def oracle_jacobians(x, u, mode=0, jac_mode=0, fd_eps=1e-5, gravity=GRAVITY, h=H):
     """AD (jac_mode 0) or forward-difference Jacobians of the oracle's step at every state: (A [n,51,51], B [n,51,19]); in a contact mode
     (A [n,4,51,51], B [n,4,51,19]), knot p under STANCE_ROWS[p]"""
     if mode == 0:
-        o = oracle(N=1, gravity=gravity, jac_mode=jac_mode, fd_eps=fd_eps)
+        o = oracle(N=1, gravity=gravity, h=h, jac_mode=jac_mode, fd_eps=fd_eps)
     else:
-        o = oracle(N=4, mode=mode, stance=SCHEDULE, gravity=gravity, jac_mode=jac_mode, fd_eps=fd_eps)
+        o = oracle(N=4, mode=mode, stance=SCHEDULE, gravity=gravity, h=h, jac_mode=jac_mode, fd_eps=fd_eps)
     As, Bs = [], []
     for xi, ui in zip(x, u):
         X, U = stage_trajectory(xi[None], ui[None], o.N)
@@ -203,25 +210,25 @@ def oracle_jacobians(x, u, mode=0, jac_mode=0, fd_eps=1e-5, gravity=GRAVITY):
 
 
 @functools.lru_cache(maxsize=None)
-def group_ad(name):
-    """the oracle's AD Jacobians of a free-flight group, computed once and shared: treat as read-only"""
-    A, B = oracle_jacobians(*group(name))
+def group_ad(name, h=H):
+    """the oracle's AD Jacobians of a free-flight group, computed once per time step and shared: treat as read-only"""
+    A, B = oracle_jacobians(*group(name, h), h=h)
     A.setflags(write=False); B.setflags(write=False)
     return A, B
 
 
 @functools.lru_cache(maxsize=None)
-def mid_cases(mode, variant="mid"):
+def mid_cases(mode, variant="mid", h=H):
     """(x, u, kept [16,4], A [16,4,51,51], B [16,4,51,19], beyond [16,19]) of the contact modes: variant "mid", or its "nonunit" /
-    "clamped" transformation; computed once and shared: treat as read-only"""
+    "clamped" transformation; computed once per time step and shared: treat as read-only"""
     x, u = mid()
     beyond = np.zeros((NS, NU), dtype=bool)
     if variant == "nonunit":
         x, u = nonunit((x, u))
     elif variant == "clamped":
         x, u, beyond = clamped((x, u))
-    kept = contact_kept(mode, x, u)
-    A, B = oracle_jacobians(x, u, mode=mode)
+    kept = contact_kept(mode, x, u, h=h)
+    A, B = oracle_jacobians(x, u, mode=mode, h=h)
     for a in (x, u, kept, A, B, beyond):
         a.setflags(write=False)
     return x, u, kept, A, B, beyond

@@ -2,7 +2,7 @@
 (test_solve_envelope_cpu.py, test_gpu_solve_envelope.py).  NumPy and the CPU oracle only; no GPU.
 
   * tame(N=5):           the sixteen dynamics_envelope_cases.mid() states with their velocities scaled by 0.3, controls
-                         grav_comp(x_i) + U(-2, 2) per knot clipped to 0.9 ctrlrange, physical gravity, h = 0.02; the trajectory is the
+                         grav_comp(x_i) + U(-2, 2) per knot clipped to 0.9 ctrlrange, physical gravity, h = 0.02 unless `h` is given; the trajectory is the
                          oracle's ROLLOUT of those controls, so every knot is another linearisation point.  On these lxx is indefinite,
                          and some rollouts reach the `indefinite even after the +1e-4 bump' branch of the Riccati pass at some knot.
   * tame_contact(mode):  the same states and controls (first four knots), contact mode 1 or 2 under dynamics_envelope_cases.SCHEDULE.
@@ -41,6 +41,10 @@ MAX_DROPPED = 2
 BUMPED_EIG = -5e-5                           # bumped_luu(): the smallest eigenvalue of Quu it leaves, half-way into (-1e-4, 0)
 RICCATI_MUTANTS = ("no_quat_rows", "no_lambda", "no_bump")
 LS_MUTANTS = ("drop_K_col50", "drop_quat_dx", "alpha_shift")
+# the steps of dc.TIMESTEPS at which the line search is tested: at 0.04 fifteen of the 48 free-flight cases are undecided (test_timestep_cpu.py)
+LS_TIMESTEPS = dc.TIMESTEPS[:2]
+LS_WIDE_SCALE = 1                            # the scale of the four-rollouts-per-wave case at LS_TIMESTEPS[0]: five alpha slots are accepted there (three at scale 4)
+SOLVE_B, SOLVE_N, SOLVE_SEED, SOLVE_ITERATIONS = 4, 8, 31, 5       # standing_solve(): one full solve per time step
 
 
 def rel(a, b):
@@ -57,11 +61,11 @@ def oracle_of(prob, mode=0, **opts):
 
 
 @functools.lru_cache(maxsize=None)
-def tame(N=5, mode=0):
-    """(prob, X [16,N+1,51], U [16,N,19]); read-only.  mode != 0: N = 4 under dc.SCHEDULE"""
+def tame(N=5, mode=0, h=dc.H):
+    """(prob, X [16,N+1,51], U [16,N,19]); read-only.  mode != 0: N = 4 under dc.SCHEDULE.  prob["dt"] = h: the rollout steps by it"""
     x = dc.mid()[0].copy()
     x[:, NQ:] *= 0.3
-    prob = dc.problem(N, dc.SCHEDULE if mode else None)
+    prob = dc.problem(N, dc.SCHEDULE if mode else None, h=h)
     o = oracle_of(prob, mode)
     noise = np.random.default_rng(SEED).uniform(-2.0, 2.0, (NS, 5, NU))
     lim = 0.9 * dc.sc.CTRLRANGE
@@ -75,22 +79,22 @@ def tame(N=5, mode=0):
     return prob, X, U
 
 
-def tame_contact(mode):
-    return tame(4, mode)
+def tame_contact(mode, h=dc.H):
+    return tame(4, mode, h)
 
 
-def trajectories(name):
+def trajectories(name, h=dc.H):
     """name: "tame", "contact1", "contact2" -> (prob, mode, X, U)"""
     mode = 0 if name == "tame" else int(name[-1])
-    prob, X, U = tame(5, 0) if mode == 0 else tame_contact(mode)
+    prob, X, U = tame(5, 0, h) if mode == 0 else tame_contact(mode, h)
     return prob, mode, X, U
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_inputs(name):
+def oracle_inputs(name, h=dc.H):
     """the oracle's own Jacobians (forward-mode AD) and cost quadratics along the trajectories: dict of arrays over the sixteen rollouts;
     read-only.  (The GPU test hands the DEVICE's to the references; these serve the CPU test.)"""
-    prob, mode, X, U = trajectories(name)
+    prob, mode, X, U = trajectories(name, h)
     o = oracle_of(prob, mode)
     out = {k: [] for k in ("A", "B", "lx", "lu", "lxx", "luu")}
     for i in range(NS):
@@ -105,6 +109,32 @@ def oracle_inputs(name):
 
 def scaled(lx, lu, s):
     return lx * float(s), lu * float(s)
+
+
+def standing_solve(h=dc.H):
+    """(prob, x0 [4,51], u_init [4,8,19]): the shipped problem (its own gravity) with prob["dt"] = h over N = 8, and the seeded perturbed
+    standing batch about the oracle's gravity compensation"""
+    prob = dc.sc.make_problem(ol.reference_kinematics, N=SOLVE_N)
+    prob["dt"] = float(h)
+    o = ol.Oracle(SOLVE_N, h); o.set_problem(prob)
+    x0, ui = dc.sc.synthetic_batch(SOLVE_B, SOLVE_N, SOLVE_SEED, o.grav_comp(dc.sc.standing_state()))
+    return prob, x0, ui
+
+
+def standing_solve_ref(prob, x0, ui):
+    """the oracle's cold solve of one rollout (five iterations at the most, default options) and its warm-started second solve from the
+    same x0 (the first solution shifted by one knot): two dicts with it, cost [6], alpha [5], lam [5], K, xbar, ubar, final cost"""
+    o = ol.Oracle(prob["N"], prob["dt"]); o.set_problem(prob); o.set_options(max_iter=SOLVE_ITERATIONS)
+    out = []
+    for warm in (False, True):
+        if warm:
+            o.initialize(x0, None, out[0]["xbar"], out[0]["ubar"])
+        else:
+            o.initialize(x0, ui)
+        _, c = o.solve(x0)
+        it, cost, alpha, lam = o.trace()
+        out.append(dict(it=it, cost=cost, alpha=alpha, lam=lam, K=o.get("K"), xbar=o.get("xbar"), ubar=o.get("ubar"), final=c))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

@@ -40,13 +40,14 @@ def _stage_jacobians(s, x, u):
     return s.linearization()
 
 
-def _check_structure(A, Bm, worst, tag):
+def _check_structure(A, Bm, worst, tag, h=H):
     """what the folded Riccati kernels rely on, exactly: base-linear-velocity columns [h I; 0; I; 0]; position rows e_p + h x velocity row"""
-    assert np.array_equal(A[..., 26:29], np.broadcast_to(C_LIN, A[..., 26:29].shape)), tag
-    e = np.abs(A[..., POS, :] - (E_POS + H * A[..., VEL, :])).max()
+    c_lin = C_LIN.copy(); c_lin[0:3] = h * np.eye(3)
+    assert np.array_equal(A[..., 26:29], np.broadcast_to(c_lin, A[..., 26:29].shape)), tag
+    e = np.abs(A[..., POS, :] - (E_POS + h * A[..., VEL, :])).max()
     worst["position rows (absolute)"] = max(worst.get("position rows (absolute)", 0.0), e)
     assert e <= 2.3e-16, (tag, e)
-    assert np.array_equal(Bm[..., POS, :], H * Bm[..., VEL, :]), tag
+    assert np.array_equal(Bm[..., POS, :], h * Bm[..., VEL, :]), tag
 
 
 @pytest.mark.parametrize("name", dc.FREE_GROUPS)
