@@ -732,6 +732,27 @@ int ilqr_hip_set_relinearize_unchanged(ilqr_hip_ctx* ctx, int on);
    ilqr_hip_set_max_iterations changed the count, -1 for a null handle or a failed read.  No reference counterpart: the reference
    recomputes. */
 long long ilqr_hip_get_linearized_rollouts(ilqr_hip_ctx* ctx);
+/* First-pass skip.  The same rollout -- both line searches of iteration i failed -- also enters iteration i + 1 with the lambda of the
+   retry of i (the reference `continue`s with the raised lambda, ilqr.cpp:619-646) and with a baseline cost that is the cost of the same
+   trajectory: the first backward pass (:601), line search (:616) and candidate costs of i + 1 would recompute, from identical inputs, the
+   gains, value function, candidates and candidate costs that its last executed pass left in the buffers, and fail again.  By default, in
+   the sequential order of a solve (the order of large batches with a fixed iteration count), the first pass of iterations >= 1 runs only
+   for the rollouts that accepted a candidate in the previous iteration -- the list of the linearisation cache; the line search takes the
+   one-rollout-per-wave kernel once that list holds at most 1024 rollouts (decided on the device; environment ILQR_LS_LIST_MAX moves the
+   threshold).  The bookkeeping (:619-620) still runs for every active rollout, from the costs that pass left.
+   Invariant: every decision, trace entry, lambda update and every observable of the solve is unchanged, bit for bit (GPU test); nothing
+   the bookkeeping reads is written by a skipped launch.  on != 0, or environment ILQR_REPASS=1, restores the full first pass in every
+   iteration (comparison, profiling: the per-launch figures of bench.py --full then are full-batch figures again).  The full pass is also
+   what runs, whatever the setting, in the side-by-side orders (ilqr_hip_get_speculative_iterations), with the early-continuation groups
+   (ilqr_hip_get_split_iterations), with forward-difference Jacobians and with batch slices.  Independent of
+   ilqr_hip_set_relinearize_unchanged and ilqr_hip_set_dedup_saturated_retry; with the latter on as well, a rollout stuck at the lambda
+   cap costs neither pass.  No reference counterpart: the reference recomputes. */
+int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* ctx, int on);
+/* Sum over the iterations of the last solve of the number of rollouts whose first pass ran: the batch for iteration 0, the rollouts
+   active in the iteration where the full pass ran (the batch without the convergence exit), the list's length where it was skipped.
+   Synchronises the handle's stream.  0 before the first solve and after ilqr_hip_set_max_iterations changed the count, -1 for a null
+   handle or a failed read. */
+long long ilqr_hip_get_first_pass_rollouts(ilqr_hip_ctx* ctx);
 
 /* ---- host-side model helpers (no GPU needed) ---- */
 /* reference construction as RobotUtils::loadReferences does it (src/common/robot_utils.cpp:369-403):

@@ -581,13 +581,14 @@ int dyn_split_kernels_set_attr() {
 #ifndef LS_RPW1_MAX_BATCH
 #define LS_RPW1_MAX_BATCH 1024      // one wave per SIMD on the 1024 SIMDs of an MI355X
 #endif
-void launch_line_search_s(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, const int* list, const int* count, int max_rollouts) {
+void launch_line_search_s(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, const int* list, const int* count, int max_rollouts, int rpw) {
   // a rollout per wave (see the kernel) for small batches -- and for the tail of an early-exit solve of a large one, where the
   // host knows an upper bound of the compacted list's length (the selected rollouts are its first entries: blocks past the
   // list's true count leave at once); the results do not depend on the choice
+  // (rpw != 0: the caller has chosen -- launch_line_search_gated, where the device decides which of two enqueued launches sees the list)
   const int nsel = (list && max_rollouts >= 0 && max_rollouts < S.B) ? max_rollouts : S.B;
   with_step_kind(P.dyn, [&](auto K) {
-    if (nsel <= LS_RPW1_MAX_BATCH) hipLaunchKernelGGL((k_line_search_s<K(), 1>), dim3(nsel > 0 ? nsel : 1), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
+    if (rpw ? rpw == 1 : nsel <= LS_RPW1_MAX_BATCH) hipLaunchKernelGGL((k_line_search_s<K(), 1>), dim3(nsel > 0 ? nsel : 1), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
     else hipLaunchKernelGGL((k_line_search_s<K(), 4>), dim3(cdiv_s((long)S.B * 16, 64)), dim3(64), DYN_LDS_BYTES_S, st, S, P, mode, list, count);
   });
 }

@@ -32,6 +32,8 @@ struct Knobs {
   ilqr::Variants var;
   int dedup_retry;      // ILQR_DEDUP_RETRY (-1: the handle's own setting, ilqr_hip_set_dedup_saturated_retry)
   int relin;            // ILQR_RELIN (-1: the handle's own setting, ilqr_hip_set_relinearize_unchanged)
+  int repass;           // ILQR_REPASS=1: the full first pass in every iteration (as ilqr_hip_set_repeat_first_pass; either one is enough)
+  int ls_list_max;      // ILQR_LS_LIST_MAX: a first-pass list of at most this many rollouts takes the one-rollout-per-wave line search (1024: one wave per SIMD)
   int slices, stagger, overlap_rollout, reuse_rollout, ee_gate /* -1: the handle's own setting */, split /* -1: on with the convergence exit */, spec, spec_dual, spec_max;
   bool per_call;
 };
@@ -46,6 +48,8 @@ static Knobs read_knobs() {
   k.stagger = geti("ILQR_STAGGER", 1);
   k.dedup_retry = geti("ILQR_DEDUP_RETRY", -1);
   k.relin = geti("ILQR_RELIN", -1);
+  k.repass = geti("ILQR_REPASS", 0);
+  k.ls_list_max = geti("ILQR_LS_LIST_MAX", 1024);
   k.overlap_rollout = geti("ILQR_OVERLAP_ROLLOUT", 1);
   { const char* e = getenv("ILQR_REUSE_ROLLOUT"); k.reuse_rollout = (e && e[0] == '1') ? 1 : 0; }
   k.ee_gate = geti("ILQR_EE_GATE", -1);
@@ -114,6 +118,11 @@ struct ilqr_hip_ctx {
   // DevState::chg, lin_listed = the region of every iteration ran from list (it, 0) (convergence exit, whole batch), else from no list
   int relin = 0, lin_iterations = 0;
   bool lin_cached = false, lin_listed = false;
+  // first-pass skip (enqueue_solve): repass = ilqr_hip_set_repeat_first_pass; fp_listed[it] = the first pass of iteration it of the last solve
+  // ran from DevState::chg (ilqr_hip_get_first_pass_rollouts); d_fp_gate [2]: device-side choice of the line-search kernel (launch_line_search_gated)
+  int repass = 0;
+  std::vector<char> fp_listed;
+  int* d_fp_gate = nullptr;
   bool env_refused = false;     // ILQR_ENV_PER_CALL: the last re-read selected a family this library does not hold (enter, enter_launching)
   double packed_h = 0.0;        // step size h of the packed image while ab_packed (k_unpack_ab rebuilds the position rows from it)
   Knobs knobs = read_knobs();   // (constructed in ilqr_hip_create)
@@ -371,6 +380,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   A(dalloc(c, &S.order, B * 2 * (c->max_iter + 1))); A(dalloc(c, &S.order_n, 2 * (size_t)(c->max_iter + 1)));
   A(dalloc(c, &S.grp_a, B)); A(dalloc(c, &S.grp_r, B)); A(dalloc(c, &S.order_r, B)); A(dalloc(c, &S.order_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.order_an, (size_t)c->max_iter + 2));
   A(dalloc(c, &S.chg, B * (c->max_iter + 1))); A(dalloc(c, &S.chg_n, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_r, B)); A(dalloc(c, &S.chg_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_an, (size_t)c->max_iter + 2));
+  A(dalloc(c, &S.chg_f, B)); A(dalloc(c, &c->d_fp_gate, 2));
   if (rc == ILQR_OK && (hipStreamCreate(&c->a1) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_roll, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_lin, hipEventDisableTiming) != hipSuccess ||
@@ -420,7 +430,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
                   c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
-  { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an}; for (void* p : gp) if (p) hipFree(p); }
+  { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate}; for (void* p : gp) if (p) hipFree(p); }
   { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
   for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints, &c->terrain}) if (t->d) hipFree(t->d);
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
@@ -782,7 +792,7 @@ static DevState slice_state(const DevState& S, size_t b0, int Bs) {
   T.trace_cost += b0 * (mi + 1); T.trace_alpha += b0 * mi; T.trace_lambda += b0 * mi;
   T.order = nullptr; T.order_n = nullptr;      // the compacted lists index the whole batch: not used by slices
   T.grp_a = T.grp_r = T.order_r = T.order_rn = T.order_an = nullptr;
-  T.chg = T.chg_n = T.chg_r = T.chg_rn = T.chg_an = nullptr;
+  T.chg = T.chg_n = T.chg_r = T.chg_rn = T.chg_an = nullptr; T.chg_f = nullptr;
   return T;
 }
 static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
@@ -958,7 +968,20 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // (analytic Jacobians only: the forward-difference launchers select by S.active, not by the group's list, and use S.A / S.Bm as
   // scratch that k_fd_finish rewrites in place -- group A's pass would rewrite the Jacobians the retry's backward pass is reading)
   const bool can_split = split_enabled(c) && S.order && S.grp_a && ev_lin && ev_adopt && c->a1 != nullptr && c->jac_mode == ILQR_JAC_ANALYTIC;
+  // First-pass skip: a rollout whose two line searches of iteration i both failed enters iteration i + 1 with its nominal trajectory, its
+  // Jacobians and quadratics (above) AND its lambda unchanged -- the reference `continue`s with the raised lambda, so the first pass of i + 1
+  // runs at the lambda of the retry of i (ilqr.cpp:619-646) -- and S.Jbase is the cost of a bit-identical re-roll.  Its first backward pass,
+  // line search and candidate costs would rewrite S.K, S.kff, S.Vx, S.Vxx, S.xcand, S.ucand, S.cand_knot with what its last executed pass
+  // (that retry; with the dedup option the first pass that saturated) left there, and fail again.  In the sequential order below the first
+  // pass of iterations >= 1 therefore runs from the list of the rollouts that accepted a candidate, DevState::chg -- the cache's list --,
+  // the candidates' knot costs from the same set as flags (DevState::chg_f).  k_control phase 0 still runs for every active rollout: for a
+  // skipped one it reads the costs that pass left and decides acc = -1 again from them and S.Jbase -- nothing a skipped launch writes.
+  // Not inside the side-by-side orders or the early-continuation split (they keep the full pass: a full pass is always valid), nor
+  // without lists (batch slices, forward differences).  ilqr_hip_set_repeat_first_pass / ILQR_REPASS=1: the full first pass everywhere.
+  const bool skip_first = !(c->knobs.repass || c->repass) && S.order && S.chg && S.chg_f && L.lin_lists && L.spec_dual && !can_split;
+  c->fp_listed.assign((size_t)c->max_iter, 0);
   bool prev_split = false;      // group A of the iteration at hand is already enqueued
+  bool prev_seq = false;        // the previous iteration ran in the sequential order (k_control has written chg_f for this one)
   for (int iter = 0; iter < c->max_iter; ++iter) {
     if (gate && iter >= 2) {
       HIPCHK(c, hipEventSynchronize(c->ev_active[iter - 2]));
@@ -1009,7 +1032,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
         HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
       }
-      prev_split = false;
+      prev_split = false; prev_seq = false;
       continue;
     }
     if (c->twin && c->knobs.spec && c->knobs.spec_dual && S.order && gate && pass_bound <= 4 * c->knobs.spec_max && L.spec_dual) {
@@ -1043,13 +1066,23 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
-      prev_split = false;
+      prev_split = false; prev_seq = false;
       continue;
     }
-    { StageTimer T(c, 3, st); ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }                                  // :601
+    const bool first_listed = skip_first && iter > 0 && prev_seq;
+    c->fp_listed[iter] = first_listed;
+    const ilqr::WorkList wf{S.chg + (size_t)iter * S.B, S.chg_n + iter};
+    { StageTimer T(c, 3, st);                                                                                              // :601
+      if (first_listed) ilqr::launch_backward_list(L, S, st, fold_h, wf.list, wf.count);
+      else ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
     TRY(wait_adoption(st));
     if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-    { StageTimer T(c, 4, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }                  // :616
+    { StageTimer T(c, 4, st);                                                                                              // :616
+      if (first_listed) {
+        DevState Sf = S; Sf.active = S.chg_f;      // (the candidates' knot costs select by mask: the list as flags; every other rollout's cand_knot stays)
+        ilqr::launch_line_search_gated(S, P, st, wf.list, wf.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate);
+        ilqr::launch_cand_costs(Sf, P, ilqr::MASK_ACTIVE, st, false);
+      } else ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
     { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot); }          // :619-620,645-655
     const bool split_next = can_split && iter + 1 < c->max_iter && rolls_aside(iter + 1);
     if (split_next) {
@@ -1067,7 +1100,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
     }
-    prev_split = split_next;
+    prev_split = split_next; prev_seq = true;
   }
   if (prev_split) {      // (the convergence exit ended the loop behind a group A that found nothing to do: its streams rejoin)
     HIPCHK(c, hipStreamWaitEvent(st, GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.lin, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.adopt, 0));
@@ -1087,6 +1120,19 @@ long long ilqr_hip_get_linearized_rollouts(ilqr_hip_ctx* c) {
       hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "ilqr_hip_get_linearized_rollouts: reading the list counts failed"; return -1; }
   long long total = 0;
   for (int it = 0; it < n; ++it) total += (it > 0 && c->lin_cached) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
+  return total;
+}
+int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->repass = on ? 1 : 0; return ILQR_OK; }
+long long ilqr_hip_get_first_pass_rollouts(ilqr_hip_ctx* c) {
+  if (!c) return -1;
+  enter(c);
+  const int n = c->lin_iterations;
+  if (n <= 0) return 0;
+  std::vector<int> act(2 * (size_t)(c->max_iter + 1)), chg((size_t)c->max_iter + 2);
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "ilqr_hip_get_first_pass_rollouts: reading the list counts failed"; return -1; }
+  long long total = 0;
+  for (int it = 0; it < n; ++it) total += ((size_t)it < c->fp_listed.size() && c->fp_listed[it]) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
   return total;
 }
 int ilqr_hip_get_split_iterations(const ilqr_hip_ctx* c) { return c ? c->split_iterations : -1; }

@@ -79,6 +79,9 @@ struct DevState {
   int* chg_r;          // [B]
   int* chg_rn;         // [max_iter + 2]
   int* chg_an;         // [max_iter + 2]
+  // First-pass skip (ilqr_capi.hip enqueue_solve): chg_f[b] = 1 while rollout b is on list it of the iteration to come (k_control writes it
+  // beside the list), for the kernels that select by mask (the candidates' knot costs).  Null: not in use.
+  int* chg_f;          // [B]
 };
 
 // compacted list of the rollouts of a pass inside a solve (DevState::order), or nulls: MASK_ACTIVE at iteration iter -> list (iter, 0), MASK_RETRY -> (iter, 1)
@@ -112,6 +115,11 @@ void launch_backward_list(const LaunchPlan& L, const DevState& S, hipStream_t st
 void launch_line_search(const LaunchPlan& L, const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, int iter = -1, int max_rollouts = -1);
 // ---- ilqr_kernels.hip: one kernel whatever the family
 void launch_line_search_list(const DevState& S, const h1::ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts);      // (LaunchPlan::spec_dual)
+// The line search of a list whose length only the device knows: one rollout per wave if it holds <= threshold rollouts, else four per wave
+// (same results either way).  Both launches are enqueued behind k_list_gate, which hands the list's count to one of them and zero to the other
+// (g[0] / g[1]); max_rollouts (< 0: the batch) bounds the length from the host -- a bound <= threshold needs neither gate nor second launch,
+// threshold <= 0 means four per wave always.  An empty list costs the launches.
+void launch_line_search_gated(const DevState& S, const h1::ProblemDev& P, hipStream_t st, const int* list, const int* count, int threshold, int max_rollouts, int* g);
 void launch_control(const DevState& S, int phase, int iter, double tol, int early_exit, hipStream_t st, int sum_knots = 0, const int* gate = nullptr);
 // speculative lambda retry (k_control_spec): T = the twin view whose K, kff, Vx, Vxx, candidates and lambda are its own
 void launch_spec_lambda(const DevState& S, double* lambda2, hipStream_t st);
@@ -151,7 +159,8 @@ void launch_rollout_s(const DevState& S, const h1::ProblemDev& P, int mode, int 
 void launch_step_s(int count, const double* x, const double* u, const h1::DynParams& dyn, double* xn, hipStream_t st, int stance_l, int stance_r, int geom, int* st_out);
 void launch_last_step_s(const DevState& S, const h1::ProblemDev& P, hipStream_t st);
 void launch_warm_tail_s(const DevState& S, const h1::ProblemDev& P, int shift, hipStream_t st);
-void launch_line_search_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr, int max_rollouts = -1);
+// rpw: 0 = rollouts per wave chosen from max_rollouts, 1 / 4 = as given (1: a grid of max_rollouts waves)
+void launch_line_search_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr, int max_rollouts = -1, int rpw = 0);
 void launch_lin_primal_s(const DevState& S, const h1::ProblemDev& P, int mode, hipStream_t st, const int* list = nullptr, const int* count = nullptr);
 // stance flags of the nominal knots t = 0..N-1 from the feet of xbar (out[B][N][2]); rollouts selected as by launch_lin_primal_s
 void launch_stance_geom_s(const DevState& S, int mode, const int* list, const int* count, int* out, hipStream_t st);

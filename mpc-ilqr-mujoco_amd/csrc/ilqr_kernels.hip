@@ -804,6 +804,9 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
       // linearisation cache (DevState::chg): the accepted candidate is about to replace xbar / ubar -- this rollout's Jacobians and cost
       // quadratics are stale in iteration iter + 1; every other rollout keeps its nominal trajectory and with it both
       if (S.chg && acc >= 0 && S.active[b]) s_chg[wv] = 1;
+      // first-pass skip (DevState::chg_f): the same set as a flag -- every other rollout enters iteration iter + 1 with the lambda, gains,
+      // value function, candidates and candidate costs of its last executed pass, which its first pass would only reproduce
+      if (S.chg_f) S.chg_f[b] = (acc >= 0 && S.active[b]) ? 1 : 0;
     }
   }
   __syncthreads();
@@ -856,6 +859,7 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
 // outcomes on the table: first search accepted -> the twin is dropped; else the twin IS the retry the reference would have run
 // (its gains, value function, candidates and costs replace the first pass's, accepted or not).  Same results, one pass of latency.
 __global__ void k_spec_gate(const int* n_ptr, int max, int* g) { const int n = *n_ptr; g[0] = n <= max ? n : 0; g[1] = n <= max ? 0 : 1; g[2] = n <= max ? 0 : n; }
+__global__ void k_list_gate(const int* n_ptr, int max, int* g) { const int n = *n_ptr; g[0] = n <= max ? n : 0; g[1] = n <= max ? 0 : n; }
 __global__ void k_spec_lambda(DevState S, double* lambda2) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < S.B) lambda2[b] = fmin(S.lambda[b] * 10.0, 1e-3);
@@ -1269,6 +1273,14 @@ void launch_line_search(const LaunchPlan& L, const DevState& S, const ProblemDev
   }
 }
 void launch_line_search_list(const DevState& S, const ProblemDev& P, hipStream_t st, const int* list, const int* count, int max_rollouts) { launch_line_search_s(S, P, MASK_ACTIVE, st, list, count, max_rollouts); }
+void launch_line_search_gated(const DevState& S, const ProblemDev& P, hipStream_t st, const int* list, const int* count, int threshold, int max_rollouts, int* g) {
+  const int bound = (max_rollouts >= 0 && max_rollouts < S.B) ? max_rollouts : S.B;
+  if (bound <= threshold) { launch_line_search_s(S, P, MASK_ACTIVE, st, list, count, bound, 1); return; }
+  if (threshold <= 0) { launch_line_search_s(S, P, MASK_ACTIVE, st, list, count, -1, 4); return; }
+  hipLaunchKernelGGL(k_list_gate, dim3(1), dim3(1), 0, st, count, threshold, g);
+  launch_line_search_s(S, P, MASK_ACTIVE, st, list, g, threshold, 1);
+  launch_line_search_s(S, P, MASK_ACTIVE, st, list, g + 1, -1, 4);
+}
 void launch_control(const DevState& S, int phase, int iter, double tol, int early_exit, hipStream_t st, int sum_knots, const int* gate) {
   hipLaunchKernelGGL(k_control, dim3(cdiv(S.B, CTRL_WAVES)), dim3(64 * CTRL_WAVES), 0, st, S, phase, iter, tol, early_exit, sum_knots, gate);
 }

@@ -43,7 +43,7 @@ EXPORTS = [
     "ilqr_hip_plant_set_history", "ilqr_hip_plant_get_history", "ilqr_hip_plant_get_state", "ilqr_hip_plant_get_control", "ilqr_hip_plant_get_stance",
     "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
-    "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts",
+    "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts", "ilqr_hip_set_repeat_first_pass", "ilqr_hip_get_first_pass_rollouts",
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
     "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
@@ -253,6 +253,21 @@ class BatchedILQR:
         n = int(fn(self.h))
         if n < 0:
             raise ILQRError("ilqr_hip_get_linearized_rollouts: %s" % self.L.ilqr_hip_last_error(self.h).decode())
+        return n
+
+    def set_repeat_first_pass(self, on=True):
+        """Run the first backward pass, line search and candidate costs of every iteration for every active rollout (comparison, profiling);
+        off by default: from iteration 1 on they run only for the rollouts that accepted a candidate in the previous iteration
+        (ilqr_hip_set_repeat_first_pass)."""
+        self._chk(self.L.ilqr_hip_set_repeat_first_pass(self.h, int(bool(on))))
+
+    def first_pass_rollouts(self):
+        """Rollouts whose first pass ran, summed over the iterations of the last solve."""
+        fn = self.L.ilqr_hip_get_first_pass_rollouts
+        fn.restype = C.c_longlong
+        n = int(fn(self.h))
+        if n < 0:
+            raise ILQRError("ilqr_hip_get_first_pass_rollouts: %s" % self.L.ilqr_hip_last_error(self.h).decode())
         return n
 
     def reload_environment(self):
