@@ -56,13 +56,25 @@ int ilqr_hip_destroy(ilqr_hip_ctx* ctx);
    total_cost / line_search, step*, get_stance with the stance source GEOMETRY) returns ILQR_ERR_UNSUPPORTED; getters, setters and
    the fixed conversion kernels never do.  No reference counterpart. */
 int ilqr_hip_reload_environment(ilqr_hip_ctx* ctx);
-/* Off by default (the solve then executes every pass the reference executes).  On: a lambda retry (ilqr.cpp:619-644) whose lambda is
-   already saturated -- min(10 lambda, 1e-3) == lambda, the state a rollout reaches after a few failed searches -- is not executed:
+/* On by default (the solve executes every pass the reference executes on new inputs).  A lambda retry (ilqr.cpp:619-644) whose lambda is
+   already saturated -- min(10 lambda, 1e-3) == lambda, the state a rollout reaches after three failed searches -- is not executed:
    it would repeat the backward pass and the line search that have just failed on identical inputs, bit for bit, and fail again.  Its
    bookkeeping (trace entry, iteration count, convergence-exit rule of ilqr.cpp:640-655) is played at once.  Every observable of the solve
-   is unchanged (GPU test); bench.py reports the resulting rate as its own object, never as the headline.  No reference counterpart:
-   the reference recomputes. */
+   is unchanged (GPU tests).  lambda outlives a solve, so a rollout may enter a later solve at the cap: the pass its skipped retry repeats
+   is then the first pass of the same iteration, and iteration 0 of every solve runs that pass for every rollout, on whatever trajectory
+   the warm start or ilqr_hip_initialize* left.  on = 0, or environment ILQR_DEDUP_RETRY=0, restores the full retry (comparison,
+   profiling; ILQR_DEDUP_RETRY=1 / 0 overrides this call, unset or -1 leaves it in charge).  In the side-by-side order
+   (ilqr_hip_get_speculative_iterations) both passes are in flight before either outcome is known: nothing is skipped there, whatever
+   the setting.  bench.py's dedup_saturated_retry object therefore repeats its headline.  No reference counterpart: the reference
+   recomputes. */
 int ilqr_hip_set_dedup_saturated_retry(ilqr_hip_ctx* ctx, int on);
+/* Sum over the iterations of the last solve of the number of rollouts whose lambda retry (backward pass and line search) ran: the length
+   of the iteration's retry list in the sequential order -- the rollouts whose first search failed, less the saturated repeats above --,
+   the rollouts active in the iteration where both passes ran side by side, batch x iterations with batch slices (no lists).  In the
+   sequential order, without the early-continuation groups, the retry's line search takes the one-rollout-per-wave kernel once its list
+   holds at most 1024 rollouts (decided on the device; environment ILQR_LS_LIST_MAX, as for the first pass).  Synchronises the handle's stream.  0 before the first solve and
+   after ilqr_hip_set_max_iterations changed the count, -1 for a null handle or a failed read. */
+long long ilqr_hip_get_retry_pass_rollouts(ilqr_hip_ctx* ctx);
 const char* ilqr_hip_last_error(const ilqr_hip_ctx* ctx);
 int ilqr_hip_batch(const ilqr_hip_ctx* ctx);
 int ilqr_hip_horizon(const ilqr_hip_ctx* ctx);
@@ -745,8 +757,8 @@ long long ilqr_hip_get_linearized_rollouts(ilqr_hip_ctx* ctx);
    iteration (comparison, profiling: the per-launch figures of bench.py --full then are full-batch figures again).  The full pass is also
    what runs, whatever the setting, in the side-by-side orders (ilqr_hip_get_speculative_iterations), with the early-continuation groups
    (ilqr_hip_get_split_iterations), with forward-difference Jacobians and with batch slices.  Independent of
-   ilqr_hip_set_relinearize_unchanged and ilqr_hip_set_dedup_saturated_retry; with the latter on as well, a rollout stuck at the lambda
-   cap costs neither pass.  No reference counterpart: the reference recomputes. */
+   ilqr_hip_set_relinearize_unchanged and ilqr_hip_set_dedup_saturated_retry; with the latter on (the default), a rollout stuck at the
+   lambda cap costs neither pass.  No reference counterpart: the reference recomputes. */
 int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* ctx, int on);
 /* Sum over the iterations of the last solve of the number of rollouts whose first pass ran: the batch for iteration 0, the rollouts
    active in the iteration where the full pass ran (the batch without the convergence exit), the list's length where it was skipped.

@@ -112,16 +112,20 @@ struct ilqr_hip_ctx {
   // standard layout over them).  The stage API and the getters convert on demand (in place, per knot region).
   int lxx_layout = 0;
   bool ab_packed = false, ab_pads_clean = false;
-  int dedup_retry = 0;          // ilqr_hip_set_dedup_saturated_retry
+  int dedup_retry = 1;          // ilqr_hip_set_dedup_saturated_retry: on unless the caller or ILQR_DEDUP_RETRY=0 asks for the full retry
   // linearisation cache (enqueue_solve): relin = ilqr_hip_set_relinearize_unchanged; what the last solve did, for
   // ilqr_hip_get_linearized_rollouts: lin_iterations (0: no solve, or its lists are gone), lin_cached = iterations >= 1 ran from
   // DevState::chg, lin_listed = the region of every iteration ran from list (it, 0) (convergence exit, whole batch), else from no list
   int relin = 0, lin_iterations = 0;
   bool lin_cached = false, lin_listed = false;
   // first-pass skip (enqueue_solve): repass = ilqr_hip_set_repeat_first_pass; fp_listed[it] = the first pass of iteration it of the last solve
-  // ran from DevState::chg (ilqr_hip_get_first_pass_rollouts); d_fp_gate [2]: device-side choice of the line-search kernel (launch_line_search_gated)
+  // ran from DevState::chg (ilqr_hip_get_first_pass_rollouts); d_fp_gate [4]: device-side choice of the line-search kernel
+  // (launch_line_search_gated) -- words 0, 1 for the first pass, words 2, 3 for the lambda retry
+  // retry_order[it]: what the retry of iteration it of the last solve ran for (ilqr_hip_get_retry_pass_rollouts) -- RETRY_LIST the retry
+  // list (it, 1), RETRY_TWIN every active rollout (side by side), RETRY_DUAL whichever of the two the device chose
   int repass = 0;
-  std::vector<char> fp_listed;
+  std::vector<char> fp_listed, retry_order;
+  enum { RETRY_LIST = 0, RETRY_TWIN = 1, RETRY_DUAL = 2 };
   int* d_fp_gate = nullptr;
   bool env_refused = false;     // ILQR_ENV_PER_CALL: the last re-read selected a family this library does not hold (enter, enter_launching)
   double packed_h = 0.0;        // step size h of the packed image while ab_packed (k_unpack_ab rebuilds the position rows from it)
@@ -380,7 +384,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   A(dalloc(c, &S.order, B * 2 * (c->max_iter + 1))); A(dalloc(c, &S.order_n, 2 * (size_t)(c->max_iter + 1)));
   A(dalloc(c, &S.grp_a, B)); A(dalloc(c, &S.grp_r, B)); A(dalloc(c, &S.order_r, B)); A(dalloc(c, &S.order_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.order_an, (size_t)c->max_iter + 2));
   A(dalloc(c, &S.chg, B * (c->max_iter + 1))); A(dalloc(c, &S.chg_n, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_r, B)); A(dalloc(c, &S.chg_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_an, (size_t)c->max_iter + 2));
-  A(dalloc(c, &S.chg_f, B)); A(dalloc(c, &c->d_fp_gate, 2));
+  A(dalloc(c, &S.chg_f, B)); A(dalloc(c, &c->d_fp_gate, 4));
   if (rc == ILQR_OK && (hipStreamCreate(&c->a1) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_roll, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_lin, hipEventDisableTiming) != hipSuccess ||
@@ -916,8 +920,10 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   //   caller-supplied trajectory is rolled out BEFORE the linearisation, as the reference does)
   // Sm: the view the mask-selected kernels (rollout, trajectory cost, adoption) get -- S, or S with a group's flags as `active`;
   // wl: the group's compacted list for the per-knot kernels (null: the iteration's own list / mask, as knot_mode and iter_l say).
-  // ilqr_hip_set_dedup_saturated_retry: bit 1 of k_control's early_exit argument (the sequential orders; the side-by-side order has
-  // both passes in flight before either outcome is known)
+  // ilqr_hip_set_dedup_saturated_retry (on by default): bit 1 of k_control's early_exit argument (the sequential orders; the side-by-side
+  // order has both passes in flight before either outcome is known).  A retry at the lambda cap repeats its rollout's last executed pass
+  // -- the first pass of the same iteration, or, where that one was skipped, the pass it repeats in turn; iteration 0 of every solve runs
+  // the full first pass, so the chain never leaves the solve
   const int dedup_bit = (c->knobs.dedup_retry >= 0 ? c->knobs.dedup_retry : c->dedup_retry) ? 2 : 0;
   // Linearisation cache: from iteration 1 on the per-knot kernels of the region (stance decisions, primal dump, tangent sweeps, kinematics
   // record, cost quadratics) run from DevState::chg -- the active rollouts whose previous iteration accepted a candidate.  A rollout
@@ -980,6 +986,12 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // without lists (batch slices, forward differences).  ilqr_hip_set_repeat_first_pass / ILQR_REPASS=1: the full first pass everywhere.
   const bool skip_first = !(c->knobs.repass || c->repass) && S.order && S.chg && S.chg_f && L.lin_lists && L.spec_dual && !can_split;
   c->fp_listed.assign((size_t)c->max_iter, 0);
+  c->retry_order.assign((size_t)c->max_iter, ilqr_hip_ctx::RETRY_LIST);
+  // The retry's line search in the sequential order: from its list (iter, 1), a few hundred rollouts in the early iterations and, with the
+  // saturated retries gone, in the late ones -- one rollout per wave where the list holds at most ILQR_LS_LIST_MAX, decided on the device
+  // as for the first pass's list; the candidates' knot costs stay selected by need_retry.  Not with the early-continuation split: there the
+  // retry runs beside group A's region, and a wave per rollout takes SIMDs from it (the early_exit object of bench.py lost 2 %)
+  const bool retry_gated = S.order && L.line_search == ilqr::DYN_TWO_LANE && !can_split;
   bool prev_split = false;      // group A of the iteration at hand is already enqueued
   bool prev_seq = false;        // the previous iteration ran in the sequential order (k_control has written chg_f for this one)
   for (int iter = 0; iter < c->max_iter; ++iter) {
@@ -1032,6 +1044,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
         HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
       }
+      c->retry_order[iter] = ilqr_hip_ctx::RETRY_TWIN;
       prev_split = false; prev_seq = false;
       continue;
     }
@@ -1066,6 +1079,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
+      c->retry_order[iter] = ilqr_hip_ctx::RETRY_DUAL;
       prev_split = false; prev_seq = false;
       continue;
     }
@@ -1094,7 +1108,12 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       TRY(region(GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
     }
     { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
-    { StageTimer T(c, 7, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }                   // :638
+    { StageTimer T(c, 7, st);                                                                                              // :638
+      if (retry_gated) {
+        const ilqr::WorkList wr = ilqr::work_list(S, ilqr::MASK_RETRY, iter);
+        ilqr::launch_line_search_gated(S, P, st, wr.list, wr.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate + 2);
+        ilqr::launch_cand_costs(S, P, ilqr::MASK_RETRY, st, false);
+      } else ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
     { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }                      // :640-646
     if (gate) {
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1133,6 +1152,25 @@ long long ilqr_hip_get_first_pass_rollouts(ilqr_hip_ctx* c) {
       hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "ilqr_hip_get_first_pass_rollouts: reading the list counts failed"; return -1; }
   long long total = 0;
   for (int it = 0; it < n; ++it) total += ((size_t)it < c->fp_listed.size() && c->fp_listed[it]) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
+  return total;
+}
+long long ilqr_hip_get_retry_pass_rollouts(ilqr_hip_ctx* c) {
+  if (!c) return -1;
+  enter(c);
+  const int n = c->lin_iterations;
+  if (n <= 0) return 0;
+  if (c->n_slices > 1 || !c->S.order) return (long long)c->B * n;      // (batch slices keep no lists: the retry launches cover the slice)
+  std::vector<int> act(2 * (size_t)(c->max_iter + 1));
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+    c->err = "ilqr_hip_get_retry_pass_rollouts: reading the list counts failed"; return -1;
+  }
+  long long total = 0;
+  for (int it = 0; it < n; ++it) {
+    const int kind = (size_t)it < c->retry_order.size() ? c->retry_order[it] : ilqr_hip_ctx::RETRY_LIST;
+    // side by side the twin pass runs for every active rollout; where both orders were enqueued the device took the twin for a list of at most spec_max
+    const bool twin = kind == ilqr_hip_ctx::RETRY_TWIN || (kind == ilqr_hip_ctx::RETRY_DUAL && act[2 * it] <= c->knobs.spec_max);
+    total += twin ? act[2 * it] : act[2 * it + 1];
+  }
   return total;
 }
 int ilqr_hip_get_split_iterations(const ilqr_hip_ctx* c) { return c ? c->split_iterations : -1; }

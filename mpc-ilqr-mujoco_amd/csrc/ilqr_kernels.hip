@@ -724,7 +724,7 @@ __device__ __forceinline__ void wave_copy(double* dst, const double* src, int le
 #define CTRL_WAVES 16
 __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int phase, int iter, double tol, int ee_flags, int sum_knots, const int* gate) {
   if (gate && *gate == 0) return;      // (device-side choice between two enqueued launch orders: launch_spec_gate)
-  // bit 0: the reference's convergence exit; bit 1 (phase 0 only, ilqr_hip_set_dedup_saturated_retry): a lambda retry whose lambda is
+  // bit 0: the reference's convergence exit; bit 1 (phase 0 only, ilqr_hip_set_dedup_saturated_retry, on by default): a lambda retry whose lambda is
   // already saturated -- min(10 lambda, 1e-3) == lambda -- would repeat the pass that has just failed bit for bit (same Jacobians,
   // quadratics and lambda give the same gains, the same eight candidates and the same costs): its bookkeeping (ilqr.cpp:640-655, the
   // failing branch) is played now and the rollout does not join the retry pass

@@ -44,6 +44,7 @@ EXPORTS = [
     "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
     "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts", "ilqr_hip_set_repeat_first_pass", "ilqr_hip_get_first_pass_rollouts",
+    "ilqr_hip_get_retry_pass_rollouts",
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
     "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
@@ -238,8 +239,18 @@ class BatchedILQR:
             raise ILQRError("ilqr_hip_create failed: %s %s" % (STATUS.get(rc, rc), msg))
 
     def set_dedup_saturated_retry(self, on=True):
-        """Skip lambda retries whose lambda is already saturated (bit-identical repeats of the pass that has just failed); off by default."""
+        """Skip lambda retries whose lambda is already saturated (bit-identical repeats of the pass that has just failed); on by default,
+        False restores the full retry (as ILQR_DEDUP_RETRY=0)."""
         self._chk(self.L.ilqr_hip_set_dedup_saturated_retry(self.h, int(bool(on))))
+
+    def retry_pass_rollouts(self):
+        """Rollouts whose lambda retry ran, summed over the iterations of the last solve (ilqr_hip_get_retry_pass_rollouts)."""
+        fn = self.L.ilqr_hip_get_retry_pass_rollouts
+        fn.restype = C.c_longlong
+        n = int(fn(self.h))
+        if n < 0:
+            raise ILQRError("ilqr_hip_get_retry_pass_rollouts: %s" % self.L.ilqr_hip_last_error(self.h).decode())
+        return n
 
     def set_relinearize_unchanged(self, on=True):
         """Re-linearise every rollout in every iteration (comparison, profiling); off by default: an iteration linearises only the rollouts
