@@ -107,6 +107,53 @@ int ilqr_hip_set_weight_sets(ilqr_hip_ctx* ctx, const double* Q /*[n_sets][51]*/
 int ilqr_hip_clear_weight_sets(ilqr_hip_ctx* ctx);
 /* 0: no table installed (shared weights), else the n_sets of the installed table (1 or the batch); -1 for a null handle */
 int ilqr_hip_num_weight_sets(const ilqr_hip_ctx* ctx);
+/* Augmented-Lagrangian joint and torque limits: an outer loop of up to `rounds` rounds around the solve that ENFORCES the two range tables
+   the plain penalties (ilqr_hip_set_constraint_weights) only discourage.  No reference counterpart: RobotUtils::setConstraintWeights
+   (robot_utils.cpp:674-680) is all the reference has.
+   Constraints, per rollout, all of the form c <= 0: hinge j (state slot 7 + j) at the knots t = 0..N, q - hi_j and lo_j - q; actuator i at
+   t = 0..N-1, u - hi_i and lo_i - u; lo = range[0] + margin (range[1] - range[0]), hi = range[1] - margin (...) from the model's joint /
+   control ranges.  margin = 0.1 gives the penalties' bounds, margin = 0 the hard range.  With multiplier mu >= 0 and penalty rho > 0 the
+   knot cost gets phi = (max(0, mu + rho c)^2 - mu^2) / (2 rho) per constraint IN PLACE of the plain penalties (w_joint_limits /
+   w_control_limits are not read while this is installed); one rho per rollout and family, rho_joint and rho_ctrl.  After each inner solve,
+   on the accepted nominal trajectory: mu <- max(0, mu + rho c); viol_joint = the largest max(0, c) over hinges, sides and knots t >= 1
+   (x_0 is given: knot 0 carries the cost term, its multipliers stay zero and it is left out), viol_ctrl likewise over t = 0..N-1; the
+   rollout is done when viol_joint <= tol_joint and viol_ctrl <= tol_ctrl, otherwise rho <- min(rho growth, rho_max_factor rho_0) for both
+   families.  A done rollout's multipliers and penalties are frozen for the rest of the call.  Every rule is per rollout.
+   With this installed ilqr_hip_solve / ilqr_hip_solve_async run up to `rounds` rounds; each is the solve described there (max_iter, tol,
+   lambda persisting from round to round as from solve to solve), a later round starting from its predecessor's nominal trajectory.  With
+   the convergence exit (ilqr_hip_set_options early_exit = 1) a done rollout enters the later rounds inactive and, with the early-exit gate
+   on, the host stops enqueuing rounds once every rollout is done (one read between two rounds; gate off: all rounds are enqueued, the
+   results are the same).  With early_exit = 0 every round runs max_iter iterations on every rollout.  ilqr_hip_get_trace,
+   ilqr_hip_get_iterations and ilqr_hip_get_cost then describe, per rollout, the last round that ran for it -- the cost is the augmented
+   cost under the multipliers that round ran with --; ilqr_hip_get_linearized_rollouts, _first_pass_rollouts and _retry_pass_rollouts the
+   last round enqueued.  The cold initialisers zero the multipliers and reset rho; the warm ones (ilqr_hip_initialize with a previous
+   solution, ilqr_hip_initialize_warm_resident[_shifted], ilqr_hip_initialize_warm_from_plant[_shifted]) shift the multipliers by the
+   knots the trajectory is shifted by, zero the tail and reset rho.  The stage calls (ilqr_hip_stage_cost_quadratics, _total_cost,
+   _line_search, _rollout) use the installed multipliers and penalties.
+   rounds >= 1, rho_joint0 > 0, rho_ctrl0 > 0, growth >= 1, rho_max_factor >= 1, 0 <= margin < 0.5, tolerances >= 0, else ILQR_ERR_ARG.
+   Allocates the multiplier store on first use ([B] records of 16 + 80 (N + 1) doubles: h1_cost_dev.h), zeroes it, sets rho = rho_0.
+   ILQR_ERR_UNSUPPORTED: in the families of the test library that evaluate the cost inside their own rollout / line-search kernels (the rule
+   and the ILQR_ENV_PER_CALL behaviour of ilqr_hip_set_weight_sets), and together with an installed weight-set table -- this call while a
+   table is installed, ilqr_hip_set_weight_sets while this is.  Synchronises the handle's stream. */
+int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* ctx, int rounds, double rho_joint0, double rho_ctrl0, double growth, double rho_max_factor, double margin,
+                                      double tol_joint, double tol_ctrl);
+/* Back to the plain penalties (same kernels and kernel arguments as a handle that never had it). */
+int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* ctx);
+/* 0: not installed, else the `rounds` it was installed with; -1 for a null handle */
+int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* ctx);
+/* The multipliers, (lower, upper) per coordinate; either pointer may be NULL.  ILQR_ERR_STATE while nothing is installed (all six calls below). */
+int ilqr_hip_get_al_multipliers(ilqr_hip_ctx* ctx, double* joint /*[B][N+1][19][2]*/, double* ctrl /*[B][N][19][2]*/);
+/* Any pointer may be NULL (that part stays).  Multipliers >= 0, penalties > 0, else ILQR_ERR_ARG; the hinges' knot-0 entries are stored as zero. */
+int ilqr_hip_set_al_multipliers(ilqr_hip_ctx* ctx, const double* joint /*[B][N+1][19][2]*/, const double* ctrl /*[B][N][19][2]*/, const double* rho /*[B][2] joint, ctrl*/);
+int ilqr_hip_get_al_penalties(ilqr_hip_ctx* ctx, double* rho /*[B][2] joint, ctrl*/);
+/* violations of the nominal trajectory at the last update and the done flags; either pointer may be NULL */
+int ilqr_hip_get_al_violation(ilqr_hip_ctx* ctx, double* viol /*[B][2] joint, ctrl*/, int* done /*[B]*/);
+/* Per round of the last solve and rollout: joint violation, control violation, rho_joint and rho_ctrl the round ran with, inner iterations
+   executed.  NaN where the round did not run for the rollout (done before it, convergence exit) or was not run at all. */
+int ilqr_hip_get_al_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][5]*/);
+/* Stage call: the update that follows an inner solve, alone, on the resident nominal trajectory (ilqr_hip_set_trajectory) and the installed
+   multipliers; writes row `round` (0 <= round < rounds) of the trace.  Synchronises. */
+int ilqr_hip_al_update(ilqr_hip_ctx* ctx, int round);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N

@@ -97,6 +97,13 @@ class iLQR {
     chk(ilqr_hip_set_weight_sets(ctx_, Q.data(), R.data(), Qf.data(), task.data(), constraint.data(), n_sets));
   }
   void clearWeightSets() { chk(ilqr_hip_clear_weight_sets(ctx_)); }
+  // augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian; no reference counterpart): solve() then runs up to `rounds`
+  // rounds of inner solve + multiplier update; replaces the plain penalties of setConstraintWeights until clearAugmentedLagrangian()
+  void setAugmentedLagrangian(int rounds, double rho_joint0, double rho_ctrl0, double growth, double rho_max_factor, double margin, double tol_joint, double tol_ctrl) {
+    chk(ilqr_hip_set_augmented_lagrangian(ctx_, rounds, rho_joint0, rho_ctrl0, growth, rho_max_factor, margin, tol_joint, tol_ctrl));
+  }
+  void clearAugmentedLagrangian() { chk(ilqr_hip_clear_augmented_lagrangian(ctx_)); }
+  int augmentedLagrangianRounds() const { return ilqr_hip_augmented_lagrangian_rounds(ctx_); }
   void setGravity(double gx, double gy, double gz) { chk(ilqr_hip_set_gravity(ctx_, gx, gy, gz)); }
   void setContactSchedule(const std::vector<int>& stance /*[N+1][2]*/) { chk(ilqr_hip_set_contact_schedule(ctx_, stance.data(), 1)); }
   // contact row: ILQR_CONTACT_NONE (default) or ILQR_CONTACT_RIGID_STANCE on the scheduled feet

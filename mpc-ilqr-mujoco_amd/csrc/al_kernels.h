@@ -1,0 +1,132 @@
+// Augmented-Lagrangian outer loop of the batched solve (ilqr_hip_set_augmented_lagrangian; no reference counterpart): the kernels that run
+// between two inner solves.  The cost side -- the AL instantiations of k_traj_knot_cost and k_cost_quadratics -- is in dyn_kernels.hip,
+// quad_kernels.hip and h1_cost_dev.h, which also states the layout of the multiplier store.
+//   k_al_update        multiplier update, violations, done flag, penalty growth, trace row and the count of rollouts left, one pass over
+//                      the nominal trajectory, one wave per rollout
+//   k_al_shift         warm-start shift of the multipliers by the knots the trajectory is shifted by (zero tail; shift > N: all zero), penalties reset
+//   k_solve_begin_al   k_solve_begin with active = !done: the prologue of the rounds >= 2 of a solve with the convergence exit
+// Every rule is per rollout: nothing here reads another rollout's data, and the one shared word (AlDev::left) is a count.
+// Compiled as the tail of ilqr_kernels.hip, beside k_solve_begin and k_warm_shift (a code object of their own for three small kernels cost
+// each library ~25 KB of headers and metadata).
+#pragma once
+#include "h1_cost_dev.h"
+#include "ilqr_kernels.h"
+
+namespace ilqr {
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { const double o = __shfl_xor(v, m); v = o > v ? o : v; }
+  return v;
+}
+
+// Constraint e of a knot's record, e in [0, 38): side = e / 19 (0 lower, 1 upper bound), coordinate e % 19.  The multiplier sits at
+// base + e for both families (AL_JHI = AL_JLO + 19, AL_UHI = AL_ULO + 19).
+__global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round, int masked) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int N = S.N;
+  double* rec = A.store + (long)b * A.stride;
+  const double rho_j = rec[AL_RHO_JOINT], rho_c = rec[AL_RHO_CTRL];
+  const int was_done = A.done[b];
+  const int iters = S.iters[b];
+  const double* xb = S.xbar + (size_t)b * (N + 1) * H1_NX;
+  const double* ub = S.ubar + (size_t)b * N * H1_NU;
+  double vj = 0.0, vc = 0.0;
+  // hinges, knots 1..N (x_0 is given: its multipliers stay zero and it is left out of the violation)
+  for (int e = lane; e < N * 2 * H1_NJ; e += 64) {
+    const int t = 1 + e / (2 * H1_NJ), r = e % (2 * H1_NJ), side = r / H1_NJ, j = r % H1_NJ;
+    double lo, hi; al_bounds(H1_JRANGE[j], A.margin, lo, hi);
+    const double q = xb[t * H1_NX + 7 + j];
+    const double c = side ? q - hi : lo - q;
+    vj = c > vj ? c : vj;
+    if (!was_done) {
+      double* mu = rec + AL_HDR + (long)t * AL_KNOT + AL_JLO + r;
+      const double s = *mu + rho_j * c;
+      *mu = s > 0.0 ? s : 0.0;
+    }
+  }
+  // actuators, knots 0..N-1
+  for (int e = lane; e < N * 2 * H1_NU; e += 64) {
+    const int t = e / (2 * H1_NU), r = e % (2 * H1_NU), side = r / H1_NU, i = r % H1_NU;
+    double lo, hi; al_bounds(H1_CTRLRANGE[i], A.margin, lo, hi);
+    const double u = ub[t * H1_NU + i];
+    const double c = side ? u - hi : lo - u;
+    vc = c > vc ? c : vc;
+    if (!was_done) {
+      double* mu = rec + AL_HDR + (long)t * AL_KNOT + AL_ULO + r;
+      const double s = *mu + rho_c * c;
+      *mu = s > 0.0 ? s : 0.0;
+    }
+  }
+  vj = wave_max(vj); vc = wave_max(vc);
+  if (lane != 0) return;
+  A.viol[2 * b] = vj; A.viol[2 * b + 1] = vc;
+  if (was_done && masked) return;          // (the round did not run for this rollout: its trace row stays NaN)
+  double* tr = A.trace + ((size_t)round * S.B + b) * 5;
+  tr[0] = vj; tr[1] = vc; tr[2] = rho_j; tr[3] = rho_c; tr[4] = (double)iters;
+  if (was_done) return;
+  if (vj <= A.tol_joint && vc <= A.tol_ctrl) { A.done[b] = 1; return; }
+  const double gj = rho_j * A.growth, gc = rho_c * A.growth;
+  rec[AL_RHO_JOINT] = gj < A.rho_joint_max ? gj : A.rho_joint_max;
+  rec[AL_RHO_CTRL] = gc < A.rho_ctrl_max ? gc : A.rho_ctrl_max;
+  atomicAdd(A.left + round, 1);
+}
+
+// Each lane owns one column of the knot records and walks the knots upwards: it reads knot t + shift after it has written every knot < t, so
+// the shift is in place without a barrier.
+__global__ void __launch_bounds__(128) k_al_shift(AlDev A, int N, int shift, double rho_joint, double rho_ctrl) {
+  const int b = blockIdx.x, e = threadIdx.x;
+  double* rec = A.store + (long)b * A.stride;
+  if (e == 0) { rec[AL_RHO_JOINT] = rho_joint; rec[AL_RHO_CTRL] = rho_ctrl; A.done[b] = 0; A.viol[2 * b] = 0.0; A.viol[2 * b + 1] = 0.0; }
+  if (e >= AL_KNOT) return;
+  const bool joint = e < AL_ULO;
+  double* k = rec + AL_HDR;
+  for (int t = 0; t <= N; ++t) {
+    const long ts = (long)t + shift;
+    const bool keep = joint ? (t >= 1 && ts <= N) : (ts <= N - 1);
+    const double v = k[(ts <= N ? ts : (long)N) * AL_KNOT + e];      // (index clamped into the record, masked below)
+    k[(long)t * AL_KNOT + e] = keep ? v : 0.0;
+  }
+}
+
+// One wave: the rollouts not yet done enter list (0, 0) in order.  A done rollout is inactive and keeps what its last round left in the
+// per-rollout observables (cost, iteration count, traces): the existing getters describe the last round that ran for it.
+__global__ void __launch_bounds__(64) k_solve_begin_al(DevState S, const int* done) {
+  const int lane = threadIdx.x;
+  int n = 0;
+  for (int b0 = 0; b0 < S.B; b0 += 64) {
+    const int b = b0 + lane;
+    const bool in = b < S.B;
+    const bool act = in && done[b] == 0;
+    const unsigned long long m = __ballot(act);
+    if (in) {
+      S.active[b] = act ? 1 : 0; S.need_retry[b] = 0;
+      if (S.grp_a) { S.grp_a[b] = 0; S.grp_r[b] = 0; }
+    }
+    if (act) {
+      if (S.order) S.order[n + __popcll(m & ((1ull << lane) - 1ull))] = b;
+      S.iters[b] = 0;
+      const double J0 = S.Jbase[b];
+      S.J[b] = J0;
+      for (int i = 0; i <= S.max_iter; ++i) S.trace_cost[(size_t)b * (S.max_iter + 1) + i] = (i == 0) ? J0 : __builtin_nan("");
+      for (int i = 0; i < S.max_iter; ++i) { S.trace_alpha[(size_t)b * S.max_iter + i] = __builtin_nan(""); S.trace_lambda[(size_t)b * S.max_iter + i] = __builtin_nan(""); }
+    }
+    n += __popcll(m);
+  }
+  if (lane == 0) {
+    if (S.order) { S.order_n[0] = n; for (int i = 1; i < 2 * (S.max_iter + 1); ++i) S.order_n[i] = 0; }
+    if (S.grp_a) for (int i = 0; i < S.max_iter + 2; ++i) { S.order_rn[i] = 0; S.order_an[i] = 0; }
+    if (S.chg) for (int i = 0; i < S.max_iter + 2; ++i) { if (i <= S.max_iter) S.chg_n[i] = 0; S.chg_rn[i] = 0; S.chg_an[i] = 0; }
+  }
+}
+
+void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st) {
+  hipLaunchKernelGGL(k_al_update, dim3(S.B), dim3(64), 0, st, S, A, round, masked);
+}
+void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st) {
+  hipLaunchKernelGGL(k_al_shift, dim3(B), dim3(128), 0, st, A, N, shift, rho_joint, rho_ctrl);
+}
+void launch_solve_begin_al(const DevState& S, const int* done, hipStream_t st) { hipLaunchKernelGGL(k_solve_begin_al, dim3(1), dim3(64), 0, st, S, done); }
+
+}  // namespace ilqr

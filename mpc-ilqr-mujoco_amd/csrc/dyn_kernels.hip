@@ -229,7 +229,8 @@ __global__ void __launch_bounds__(64) k_line_search_r(DevState S, ProblemDev P, 
 // gate (optional): the launch does nothing when *gate == 0 (device-side choice between two enqueued launch orders, ilqr_capi.hip)
 // WS: each lane takes the weights of its own rollout's weight set (b comes from the clamped index idc: a lane past the end forms the
 // address of the last rollout's record, never one outside the table)
-template <bool WS>
+// AL: the augmented-Lagrangian terms of the lane's own rollout and knot (ProblemDev::al) in place of the plain penalties
+template <bool WS, bool AL>
 __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate) {
   if (gate && *gate == 0) return;
   __shared__ double xs[32 * CK_LD];     // half a wave's rows at a time: 13 KB, so that the registers (two waves per SIMD), not the LDS, set the occupancy
@@ -272,7 +273,7 @@ __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P,
   const double* ug = usrc + (cand * N + (t < N ? t : N - 1)) * H1_NU;
 #pragma unroll
   for (int i = 0; i < H1_NU; ++i) u[i] = ug[i];
-  const double c = knot_cost_w<WS>(P, b, t, x, t < N ? u : (const double*)nullptr, ComReg());
+  const double c = knot_cost_w<WS, AL>(P, b, t, x, t < N ? u : (const double*)nullptr, ComReg());
   if (act) S.cand_knot[((cand << oshift) * (N + 1)) + t] = c;
 }
 __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int cshift, int oshift, double* cost_out) {
@@ -286,15 +287,17 @@ __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int 
 }
 void launch_cand_costs(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, bool with_sum, const int* gate) {
   const long total = (long)S.B * 8 * (S.N + 1);
-  if (P.wsets) hipLaunchKernelGGL(k_traj_knot_cost<true>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  else hipLaunchKernelGGL(k_traj_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  else hipLaunchKernelGGL((k_traj_knot_cost<false, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   if (with_sum) hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)(((long)S.B * 8 + 63) / 64)), dim3(64), 0, st, S, mode, 3, 0, S.cand_cost);
 }
 // computeTotalCost of the nominal trajectories (S.xbar, S.ubar) into cost_out[B], same kernels, same summation order
 void launch_nominal_costs(const DevState& S, const ProblemDev& P, int mode, double* cost_out, hipStream_t st) {
   const long total = (long)S.B * (S.N + 1);
-  if (P.wsets) hipLaunchKernelGGL(k_traj_knot_cost<true>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  else hipLaunchKernelGGL(k_traj_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  else hipLaunchKernelGGL((k_traj_knot_cost<false, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)((S.B + 63) / 64)), dim3(64), 0, st, S, mode, 0, 3, cost_out);
 }
 

@@ -41,7 +41,63 @@ struct ProblemDev {
   // per-rollout weight sets (ilqr_hip_set_weight_sets): null = the shared Q ... w_ctrl above; else one WS_STRIDE record per set, stride 0
   // when one set serves every rollout.  Appended: nothing above moves
   const double* wsets;       long wsets_stride;
+  // augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian): null = the plain penalties w_joint / w_ctrl; else the
+  // multiplier store, one record of al_stride doubles per rollout (layout below), and the margin fraction of the bounds.  Appended: nothing above moves
+  const double* al;          long al_stride;
+  double al_margin;
 };
+// The multiplier store, in doubles.  Rollout b's record: one 128-byte line of scalars (AL_RHO_JOINT, AL_RHO_CTRL, the rest padding), then one
+// record of AL_KNOT = 80 doubles (five whole lines) per knot t = 0..N: the hinges' multipliers of the lower bounds, of the upper bounds, two
+// doubles of padding, then the same for the actuators (zeros at t = N).  Knot-major, because k_cost_quadratics reads one knot per workgroup
+// with lane = coordinate (two 152-byte runs per wave) and k_traj_knot_cost one knot per lane, each lane using every byte of its knot's five
+// lines; the eight candidates of a rollout read the same lines.
+enum { AL_RHO_JOINT = 0, AL_RHO_CTRL = 1, AL_HDR = 16, AL_JLO = 0, AL_JHI = H1_NJ, AL_ULO = 40, AL_UHI = 40 + H1_NU, AL_KNOT = 80 };
+static_assert(H1_NJ == 19 && H1_NU == 19 && AL_JHI + H1_NJ <= AL_ULO && AL_UHI + H1_NU <= AL_KNOT && AL_KNOT % 16 == 0 && AL_HDR % 16 == 0, "multiplier record: whole 128-byte lines");
+inline long al_record_doubles(int N) { return AL_HDR + (long)AL_KNOT * (N + 1); }
+// Bounds lo = r0 + m (r1 - r0), hi = r1 - m (r1 - r0), each operation rounded once (no contraction): every kernel and the host restatement
+// of the tests then hold the same two doubles
+DEVFN void al_bounds(const double* range, double m, double& lo, double& hi) {
+#pragma clang fp contract(off)
+  const double d = range[1] - range[0];
+  const double mg = m * d;
+  lo = range[0] + mg; hi = range[1] - mg;
+}
+// One constraint c <= 0 with multiplier mu >= 0 and penalty rho > 0: phi = (max(0, mu + rho c)^2 - mu^2) / (2 rho); its gradient with
+// respect to c is max(0, mu + rho c), its second derivative rho where that is positive (exact: c is linear in the coordinate)
+// (al_phi2 is 2 rho phi: a family's terms share rho, so their sum is divided once -- an fp64 division is ~30 instructions, and a knot has 76 terms)
+DEVFN double al_phi2(double c, double mu, double rho) {
+  const double s = mu + rho * c;
+  const double sp = s > 0.0 ? s : 0.0;
+  return sp * sp - mu * mu;
+}
+// the two families' terms of knot t of rollout b (x: the knot's state, u: its control), in the order of joint_penalty / ctrl_penalty
+DEVFN double al_joint_term(const ProblemDev& P, int b, int t, const double* x) {
+  const double* r = P.al + (long)b * P.al_stride;
+  const double rho = r[AL_RHO_JOINT];
+  const double* k = r + AL_HDR + (long)t * AL_KNOT;
+  double c = 0.0;
+#pragma unroll
+  for (int i = 0; i < H1_NJ; ++i) {
+    double lo, hi; al_bounds(H1_JRANGE[i], P.al_margin, lo, hi);
+    const double q = x[7 + i];
+    c += al_phi2(q - hi, k[AL_JHI + i], rho);
+    c += al_phi2(lo - q, k[AL_JLO + i], rho);
+  }
+  return c / (2.0 * rho);
+}
+DEVFN double al_ctrl_term(const ProblemDev& P, int b, int t, const double* u) {
+  const double* r = P.al + (long)b * P.al_stride;
+  const double rho = r[AL_RHO_CTRL];
+  const double* k = r + AL_HDR + (long)t * AL_KNOT;
+  double c = 0.0;
+#pragma unroll
+  for (int i = 0; i < H1_NU; ++i) {
+    double lo, hi; al_bounds(H1_CTRLRANGE[i], P.al_margin, lo, hi);
+    c += al_phi2(u[i] - hi, k[AL_UHI + i], rho);
+    c += al_phi2(lo - u[i], k[AL_ULO + i], rho);
+  }
+  return c / (2.0 * rho);
+}
 // Record of one weight set, in doubles: every weight the cost reads, padded to whole 128-byte lines (129 fields -> 9 lines)
 enum { WS_Q = 0, WS_QF = WS_Q + H1_NX, WS_R = WS_QF + H1_NX, WS_TASK = WS_R + H1_NU /* order of ilqr_hip_set_task_weights */, WS_W_JOINT = WS_TASK + 6, WS_W_CTRL = WS_W_JOINT + 1,
        WS_FIELDS = WS_W_CTRL + 1, WS_STRIDE = (WS_FIELDS + 15) / 16 * 16 };
@@ -94,7 +150,8 @@ DEVFN bool support_point(const ProblemDev& P, int b, int t, double* ps) {
   return false;
 }
 // one knot of computeTotalCost (ilqr.cpp:370-443 / 447-510) including its share of the penalties (512-515)
-template <bool WS, class ComFn>
+// AL: the augmented-Lagrangian terms of the installed multipliers in place of the two plain penalties
+template <bool WS, bool AL = false, class ComFn>
 DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, const double* u /*null at t==N*/, ComFn com_fn) {
   const CostWeights<WS> Wt(P, b);
   const bool term = (t == P.N);
@@ -123,12 +180,17 @@ DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, con
       c += 0.5 * Wt.w_balance(P) * (rx * rx + ry * ry);
     }
   }
-  c += joint_penalty(P, Wt, x);
-  if (!term) c += ctrl_penalty(P, Wt, u);
+  if constexpr (AL) {
+    c += al_joint_term(P, b, t, x);
+    if (!term) c += al_ctrl_term(P, b, t, u);
+  } else {
+    c += joint_penalty(P, Wt, x);
+    if (!term) c += ctrl_penalty(P, Wt, u);
+  }
   return c;
 }
 template <class ComFn>
-DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn) { return knot_cost_w<false>(P, b, t, x, u, com_fn); }
+DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn) { return knot_cost_w<false, false>(P, b, t, x, u, com_fn); }
 // The terms of knot_cost_w<false> at a NON-terminal knot, one by one, under the shared weights of P (a caller with weights of its own
 // passes a copy of P that holds them): out[0] state, [1] control, [2] upright, [3] balance, [4] joint-limit penalty, [5] control-limit
 // penalty -- the same expressions in the same order of operations, so that their sum is knot_cost_w's value up to its own additions

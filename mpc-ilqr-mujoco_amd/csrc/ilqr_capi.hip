@@ -78,6 +78,15 @@ struct ilqr_hip_ctx {
   int n_xref = 0, n_stance = 0, n_ee = 0;
   double* d_wsets = nullptr;              // [B][WS_STRIDE] weight-set table (ilqr_hip_set_weight_sets; allocated by its first call); installed while P.wsets points at it
   int n_wsets = 0;                        // 0: shared weights, else the installed table's n_sets
+  // Augmented Lagrangian (ilqr_hip_set_augmented_lagrangian): installed while P.al points at d_al.  d_al [B][al_record_doubles(N)] the multiplier
+  // store (h1_cost_dev.h), d_al_viol [B][2], d_al_done [B], d_al_trace [al_trace_cap][B][5], d_al_left [al_trace_cap] rollouts not done after each
+  // round and its pinned copy h_al_left (the host's read between two rounds, as the early-exit gate reads its counts); all kept by the handle
+  // once allocated.  al_round: the round enqueue_solve is enqueuing; al_rounds_run: rounds the last solve enqueued
+  int al_rounds = 0, al_trace_cap = 0, al_round = 0, al_rounds_run = 0;
+  double al_rho0[2] = {0, 0}, al_growth = 1.0, al_max_factor = 1.0, al_tol[2] = {0, 0};
+  double *d_al = nullptr, *d_al_viol = nullptr, *d_al_trace = nullptr;
+  int *d_al_done = nullptr, *d_al_left = nullptr, *h_al_left = nullptr;
+  hipEvent_t ev_al = nullptr;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
@@ -229,6 +238,13 @@ struct ilqr_hip_ctx {
     }                                                                                       \
   } while (0)
 
+// the same check with the message built out of line (HIPCHK expands to ~200 bytes of string handling per use)
+__attribute__((noinline, cold)) static int hip_failed(ilqr_hip_ctx* c, const char* what, hipError_t e) {
+  c->err = std::string(what) + ": " + hipGetErrorString(e);
+  return ILQR_ERR_HIP;
+}
+#define HIPCHK_S(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed((ctx), #call, e_); } while (0)
+
 template <class T> static int dalloc(ilqr_hip_ctx* c, T** p, size_t count) {
   HIPCHK(c, hipMalloc((void**)p, count * sizeof(T)));
   HIPCHK(c, hipMemsetAsync(*p, 0, count * sizeof(T), c->stream));
@@ -279,11 +295,30 @@ static const char* weight_sets_refusal(const ilqr_hip_ctx* c) {
   if (!plan_of(c).weight_sets) return "weight sets exist in the default family's cost kernels only; unset ILQR_DYN=s / ILQR_ROLLOUT=r / ILQR_LS=r";
   return nullptr;
 }
+// the augmented-Lagrangian terms live in the same two cost kernels: the same rule
+static const char* al_refusal(const ilqr_hip_ctx* c) {
+  if (!plan_of(c).weight_sets) return "the augmented-Lagrangian terms exist in the default family's cost kernels only; unset ILQR_DYN=s / ILQR_ROLLOUT=r / ILQR_LS=r";
+  return nullptr;
+}
 static inline int enter_launching(ilqr_hip_ctx* c) {
   enter(c);
   if (c->env_refused) return ILQR_ERR_UNSUPPORTED;
   if (c->P.wsets) if (const char* why = weight_sets_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  if (c->P.al) if (const char* why = al_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   return ILQR_OK;
+}
+static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
+  ilqr::AlDev A{};
+  A.store = c->d_al; A.stride = h1::al_record_doubles(c->N);
+  A.margin = c->P.al_margin; A.growth = c->al_growth; A.tol_joint = c->al_tol[0]; A.tol_ctrl = c->al_tol[1];
+  A.rho_joint_max = c->al_rho0[0] * c->al_max_factor; A.rho_ctrl_max = c->al_rho0[1] * c->al_max_factor;
+  A.viol = c->d_al_viol; A.done = c->d_al_done; A.trace = c->d_al_trace; A.left = c->d_al_left;
+  return A;
+}
+// the multipliers follow the trajectory: shifted by the knots it is shifted by (shift > N: a cold start, all zero), penalties back to their
+// initial values -- enqueued on the handle's stream by every initialiser while AL is installed
+static void al_follow_initialize(ilqr_hip_ctx* c, int shift) {
+  if (c->P.al) ilqr::launch_al_shift(al_view(c), c->B, c->N, shift, c->al_rho0[0], c->al_rho0[1], c->stream);
 }
 
 // The wrench, payload, observation, actuator, joints and terrain families of the plant kernels are modules of their own (csrc/Makefile PLANT_MODULE;
@@ -408,6 +443,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   P.x_ref = c->d_xref; P.u_ref = c->d_uref; P.com_ref = c->d_comref; P.stance = c->d_stance; P.ee_ref = c->d_eeref; P.com_vel_ref = c->d_comvelref;
   P.x_ref_stride = P.u_ref_stride = P.com_ref_stride = P.stance_stride = P.ee_ref_stride = P.com_vel_ref_stride = 0;
   P.wsets = nullptr; P.wsets_stride = 0;
+  P.al = nullptr; P.al_stride = 0; P.al_margin = 0.0;
   // default: stance everywhere (RobotUtils::isStance default, robot_utils.cpp:494-504), lambda = 1e-6 (ilqr.cpp:16)
   std::vector<int> ones((N + 1) * 2, 1);
   hipMemcpyAsync(c->d_stance, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
@@ -431,8 +467,10 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left};
   for (void* p : ptrs) if (p) hipFree(p);
+  if (c->h_al_left) (void)hipHostFree(c->h_al_left);
+  if (c->ev_al) hipEventDestroy(c->ev_al);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate}; for (void* p : gp) if (p) hipFree(p); }
   { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
@@ -482,6 +520,7 @@ int ilqr_hip_set_weight_sets(ilqr_hip_ctx* c, const double* Q, const double* R, 
   if (!c || !Q || !R || !Qf || !task || !constraint || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   enter(c);
   if (const char* why = weight_sets_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  if (c->P.al) { c->err = "weight sets together with the augmented Lagrangian are not supported: ilqr_hip_clear_augmented_lagrangian first"; return ILQR_ERR_UNSUPPORTED; }
   if (!c->d_wsets) TRY(dalloc(c, &c->d_wsets, (size_t)c->B * h1::WS_STRIDE));
   std::vector<double> rec((size_t)n_sets * h1::WS_STRIDE, 0.0);
   for (int s = 0; s < n_sets; ++s) {
@@ -502,6 +541,121 @@ int ilqr_hip_clear_weight_sets(ilqr_hip_ctx* c) {
   return ILQR_OK;
 }
 int ilqr_hip_num_weight_sets(const ilqr_hip_ctx* c) { return c ? c->n_wsets : -1; }
+
+// ---------------------------------------------------------------- augmented-Lagrangian joint and torque limits
+int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_joint0, double rho_ctrl0, double growth, double rho_max_factor, double margin,
+                                      double tol_joint, double tol_ctrl) {
+  if (!c || rounds < 1 || !(rho_joint0 > 0.0) || !(rho_ctrl0 > 0.0) || !(growth >= 1.0) || !(rho_max_factor >= 1.0) || !(margin >= 0.0) || !(margin < 0.5) ||
+      !(tol_joint >= 0.0) || !(tol_ctrl >= 0.0) || !std::isfinite(rho_joint0) || !std::isfinite(rho_ctrl0) || !std::isfinite(growth) || !std::isfinite(rho_max_factor)) return ILQR_ERR_ARG;
+  enter(c);
+  if (const char* why = al_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  if (c->P.wsets) { c->err = "the augmented Lagrangian together with weight sets is not supported: ilqr_hip_clear_weight_sets first"; return ILQR_ERR_UNSUPPORTED; }
+  const size_t B = c->B;
+  if (!c->d_al) { TRY(dalloc(c, &c->d_al, B * (size_t)h1::al_record_doubles(c->N))); TRY(dalloc(c, &c->d_al_viol, B * 2)); TRY(dalloc(c, &c->d_al_done, B)); }
+  if (!c->ev_al) HIPCHK_S(c, hipEventCreateWithFlags(&c->ev_al, hipEventDisableTiming));
+  if (rounds > c->al_trace_cap) {
+    HIPCHK_S(c, hipStreamSynchronize(c->stream));
+    if (c->d_al_trace) (void)hipFree(c->d_al_trace);
+    if (c->d_al_left) (void)hipFree(c->d_al_left);
+    if (c->h_al_left) (void)hipHostFree(c->h_al_left);
+    c->d_al_trace = nullptr; c->d_al_left = nullptr; c->h_al_left = nullptr; c->al_trace_cap = 0;
+    TRY(dalloc(c, &c->d_al_trace, (size_t)rounds * B * 5)); TRY(dalloc(c, &c->d_al_left, (size_t)rounds));
+    HIPCHK_S(c, hipHostMalloc((void**)&c->h_al_left, sizeof(int) * (size_t)rounds, hipHostMallocDefault));
+    c->al_trace_cap = rounds;
+  }
+  c->al_rounds = rounds; c->al_rho0[0] = rho_joint0; c->al_rho0[1] = rho_ctrl0; c->al_growth = growth; c->al_max_factor = rho_max_factor;
+  c->al_tol[0] = tol_joint; c->al_tol[1] = tol_ctrl; c->al_rounds_run = 0;
+  c->P.al = c->d_al; c->P.al_stride = h1::al_record_doubles(c->N); c->P.al_margin = margin;
+  HIPCHK_S(c, hipMemsetAsync(c->d_al_trace, 0xFF, (size_t)rounds * B * 5 * sizeof(double), c->stream));      // (all bits set: NaN)
+  al_follow_initialize(c, c->N + 1);
+  HIPCHK_S(c, hipGetLastError());
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al_rounds = 0; c->al_rounds_run = 0;      // (the buffers stay with the handle for the next call)
+  return ILQR_OK;
+}
+int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al_rounds : 0) : -1; }
+// host image of the store <-> the interface's [B][N+1][19][2] / [B][N][19][2] (lo, hi) arrays
+static int al_read_store(ilqr_hip_ctx* c, std::vector<double>& st) {
+  st.resize((size_t)c->B * h1::al_record_doubles(c->N));
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(st.data(), c->d_al, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+// one pass over the store's image: to_store = false reads it into the interface's arrays, true writes them into it (any pointer may be null;
+// knot 0 of the hinges is stored as zero: x_0 is given, its multipliers stay zero)
+__attribute__((noinline, minsize)) static void al_convert(const ilqr_hip_ctx* c, double* st, double* joint, double* ctrl, double* rho, bool to_store) {
+  const size_t N = c->N, rec = h1::al_record_doubles(c->N);
+  auto mv = [&](double& s, double& o, bool zero) { if (to_store) s = zero ? 0.0 : o; else o = s; };
+  for (size_t b = 0; b < (size_t)c->B; ++b) {
+    double* r = st + b * rec;
+    if (rho) { mv(r[h1::AL_RHO_JOINT], rho[2 * b], false); mv(r[h1::AL_RHO_CTRL], rho[2 * b + 1], false); }
+    for (size_t t = 0; t <= N; ++t) {
+      double* k = r + h1::AL_HDR + t * h1::AL_KNOT;
+      for (int i = 0; i < 19; ++i) {
+        if (joint) { double* o = joint + ((b * (N + 1) + t) * 19 + i) * 2; mv(k[h1::AL_JLO + i], o[0], t == 0); mv(k[h1::AL_JHI + i], o[1], t == 0); }
+        if (ctrl && t < N) { double* o = ctrl + ((b * N + t) * 19 + i) * 2; mv(k[h1::AL_ULO + i], o[0], false); mv(k[h1::AL_UHI + i], o[1], false); }
+      }
+    }
+  }
+}
+static int al_get(ilqr_hip_ctx* c, double* joint, double* ctrl, double* rho) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  enter(c);
+  std::vector<double> st; TRY(al_read_store(c, st));
+  al_convert(c, st.data(), joint, ctrl, rho, false);
+  return ILQR_OK;
+}
+int ilqr_hip_get_al_multipliers(ilqr_hip_ctx* c, double* joint, double* ctrl) { return al_get(c, joint, ctrl, nullptr); }
+int ilqr_hip_get_al_penalties(ilqr_hip_ctx* c, double* rho) { return rho ? al_get(c, nullptr, nullptr, rho) : ILQR_ERR_ARG; }
+__attribute__((noinline, minsize)) static bool al_values_ok(const double* v, size_t n, bool positive) {
+  if (v) for (size_t e = 0; e < n; ++e) if (!std::isfinite(v[e]) || v[e] < 0.0 || (positive && v[e] == 0.0)) return false;
+  return true;
+}
+int ilqr_hip_set_al_multipliers(ilqr_hip_ctx* c, const double* joint, const double* ctrl, const double* rho) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  const size_t B = c->B, N = c->N;
+  if (!al_values_ok(joint, B * (N + 1) * 38, false) || !al_values_ok(ctrl, B * N * 38, false) || !al_values_ok(rho, B * 2, true)) return ILQR_ERR_ARG;
+  enter(c);
+  std::vector<double> st; TRY(al_read_store(c, st));
+  al_convert(c, st.data(), const_cast<double*>(joint), const_cast<double*>(ctrl), const_cast<double*>(rho), true);
+  HIPCHK_S(c, hipMemcpy(c->d_al, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
+  return ILQR_OK;
+}
+int ilqr_hip_get_al_violation(ilqr_hip_ctx* c, double* viol, int* done) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  enter(c);
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  if (viol) HIPCHK_S(c, hipMemcpy(viol, c->d_al_viol, (size_t)c->B * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (done) HIPCHK_S(c, hipMemcpy(done, c->d_al_done, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+int ilqr_hip_get_al_trace(ilqr_hip_ctx* c, double* out) {
+  if (!c || !out) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  enter(c);
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(out, c->d_al_trace, (size_t)c->al_rounds * c->B * 5 * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+int ilqr_hip_al_update(ilqr_hip_ctx* c, int round) {
+  if (!c || round < 0) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  if (round >= c->al_rounds) return ILQR_ERR_ARG;
+  if (!c->initialized) return ILQR_ERR_STATE;
+  enter(c);
+  HIPCHK_S(c, hipMemsetAsync(c->d_al_left + round, 0, sizeof(int), c->stream));
+  ilqr::launch_al_update(c->S, al_view(c), round, c->early_exit, c->stream);
+  HIPCHK_S(c, hipGetLastError());
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
 
 int ilqr_hip_set_contact_schedule(ilqr_hip_ctx* c, const int* stance, int n_sets) {
   if (!c || !stance || check_sets(c, n_sets)) return ILQR_ERR_ARG;
@@ -685,6 +839,7 @@ static int cold_start_device(ilqr_hip_ctx* c, const double* x0_dev, const double
   HIPCHK(c, hipMemcpyAsync(c->S.x0, x0_dev, B * ILQR_NX * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->S.ubar, uinit_dev, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   const ilqr::LaunchPlan L = plan_of(c);
+  al_follow_initialize(c, c->N + 1);      // (ahead of the rollout: its cost is the augmented one)
   ilqr::launch_rollout(L, c->S, c->P, ilqr::MASK_ALL, 1, 0, c->S.Jbase, c->stream);  // N rollouts (ilqr.cpp:113-115)
   HIPCHK(c, hipGetLastError());
   c->initialized = true;
@@ -707,6 +862,7 @@ int ilqr_hip_initialize(ilqr_hip_ctx* c, const double* x0, const double* u_init,
     HIPCHK(c, hipMemcpyAsync(c->d_prevu, prev_ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyHostToDevice, c->stream));
     ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);
     ilqr::launch_last_step(plan_of(c), c->S, c->P, c->stream);
+    al_follow_initialize(c, 1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->initialized = true;
@@ -739,6 +895,7 @@ int ilqr_hip_initialize_warm_resident(ilqr_hip_ctx* c, const double* x0) {
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);
   ilqr::launch_last_step(plan_of(c), c->S, c->P, c->stream);
+  al_follow_initialize(c, 1);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->xbar_rolled = false;
@@ -751,6 +908,7 @@ static int warm_shifted(ilqr_hip_ctx* c, int shift) {
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift_m(c->S, c->d_prevx, c->d_prevu, shift, c->stream);
   ilqr::launch_warm_tail(plan_of(c), c->S, c->P, shift, c->stream);
+  al_follow_initialize(c, shift);
   HIPCHK(c, hipGetLastError());
   c->xbar_rolled = false;
   return ILQR_OK;
@@ -804,6 +962,7 @@ static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
   T.x_ref += b0 * P.x_ref_stride; T.u_ref += b0 * P.u_ref_stride; T.com_ref += b0 * P.com_ref_stride;
   T.stance += b0 * P.stance_stride; T.ee_ref += b0 * P.ee_ref_stride; T.com_vel_ref += b0 * P.com_vel_ref_stride;
   if (P.wsets) T.wsets += b0 * P.wsets_stride;
+  if (P.al) T.al += b0 * P.al_stride;
   return T;
 }
 static int ensure_slices(ilqr_hip_ctx* c, int k) {
@@ -887,7 +1046,10 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   // step size h while launch_linearize writes Jacobians whose hinge-position rows are exactly e_k + h * the hinge-velocity rows (the
   // analytic tangent kernels, lin_column) and the backward kernel uses that (riccati_wave.hip fold_rows); else 0
   const double fold_h = L.folds_h ? P.dyn.h : 0.0;
-  { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st); ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
+  { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st);
+    // (rounds >= 2 of an augmented-Lagrangian solve with the convergence exit: the rollouts that are done enter inactive)
+    if (P.al && c->al_round > 0 && c->early_exit) ilqr::launch_solve_begin_al(S, c->d_al_done + (S.active - c->S.active), st);
+    else ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
   // With the convergence exit on, the launches of an iteration nobody needs are pure latency (17 launches that find nothing to
   // do): the count of rollouts active after iteration i (DevState::order_n, maintained by k_control) follows iteration i to the
   // host, which enqueues iteration i only after it has seen the count left by iteration i - 2 -- one full iteration stays
@@ -1200,6 +1362,63 @@ static int jacobians_available(ilqr_hip_ctx* c) {
   }
   return ILQR_OK;
 }
+// one inner solve of the whole batch on the handle's stream: one launch sequence, or one per batch slice behind ev_begin
+__attribute__((noinline)) static int enqueue_batch(ilqr_hip_ctx* c, int k) {
+  hipStream_t st = c->stream;
+  const DevState& S = c->S; const h1::ProblemDev& P = c->P;
+  if (k <= 1) {
+    TRY(enqueue_solve(c, S, P, st, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_roll, c->d_shadowx, nullptr, nullptr, c->ev_lin, c->ev_adopt));
+  } else {
+    TRY(ensure_slices(c, k));
+    HIPCHK_S(c, hipEventRecord(c->ev_begin, st));
+    const int per = (c->B + k - 1) / k;
+    const bool stagger = c->knobs.stagger != 0;
+    for (int i = 0; i < k; ++i) {
+      const int b0 = i * per, Bs = (b0 + per <= c->B) ? per : (c->B - b0);
+      if (Bs <= 0) continue;
+      auto& sl = c->slices[i];
+      HIPCHK_S(c, hipStreamWaitEvent(sl.st, c->ev_begin, 0));
+      const DevState Ss = slice_state(S, (size_t)b0, Bs);
+      const h1::ProblemDev Ps = slice_problem(P, b0);
+      TRY(enqueue_solve(c, Ss, Ps, sl.st, sl.st2, sl.st3, sl.fork, sl.join, sl.roll, c->d_shadowx, (stagger && i > 0) ? c->slices[i - 1].lead : nullptr, sl.lead));
+      HIPCHK_S(c, hipEventRecord(sl.done, sl.st));
+      HIPCHK_S(c, hipStreamWaitEvent(st, sl.done, 0));
+    }
+  }
+  return ILQR_OK;
+}
+// Augmented Lagrangian: up to al_rounds rounds, each the inner solve as it stands followed by the update kernel on the handle's stream.
+// A round after the first starts from the nominal trajectory its predecessor left -- iteration 0 of that round rolled it out from x0 with
+// LaunchPlan::rollout, or the line search produced it: the nominal of an iteration >= 1, so its iteration 0 re-rolls it aside under the rule
+// of those iterations (first_aside).  The baseline cost, every Jacobian and every quadratic are recomputed by iteration 0 under the new
+// multipliers, and no list survives k_solve_begin: the linearisation cache and the two skips see nothing of the round before.
+__attribute__((noinline)) static int enqueue_al_rounds(ilqr_hip_ctx* c, int k) {
+  hipStream_t st = c->stream;
+  const int rounds = c->al_rounds;
+  const bool al_stop = c->early_exit && early_exit_gate(c);      // the host reads the count of rollouts left between two rounds
+  HIPCHK_S(c, hipMemsetAsync(c->d_al_done, 0, (size_t)c->B * sizeof(int), st));
+  HIPCHK_S(c, hipMemsetAsync(c->d_al_left, 0, (size_t)rounds * sizeof(int), st));
+  HIPCHK_S(c, hipMemsetAsync(c->d_al_trace, 0xFF, (size_t)rounds * c->B * 5 * sizeof(double), st));      // (all bits set: NaN)
+  c->al_rounds_run = 0;
+  int rc = ILQR_OK;
+  for (int round = 0; round < rounds && rc == ILQR_OK; ++round) {
+    c->al_round = round;
+    if (round > 0) { c->first_aside = true; c->spec_iterations = 0; c->split_iterations = 0; }
+    rc = enqueue_batch(c, k);
+    if (rc != ILQR_OK) break;
+    ilqr::launch_al_update(c->S, al_view(c), round, c->early_exit, st);
+    c->al_rounds_run = round + 1;
+    if (al_stop && round + 1 < rounds) {
+      hipError_t e = hipMemcpyAsync(&c->h_al_left[round], c->d_al_left + round, sizeof(int), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(c->ev_al, st);
+      if (e == hipSuccess) e = hipEventSynchronize(c->ev_al);
+      if (e != hipSuccess) rc = hip_failed(c, "reading the count of rollouts left between two rounds", e);
+      else if (c->h_al_left[round] == 0) break;      // every rollout is done
+    }
+  }
+  c->al_round = 0;
+  return rc;
+}
 int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   if (!c->initialized || !c->refs_set) { c->err = "solve before initialize/set_references"; return ILQR_ERR_STATE; }
@@ -1216,25 +1435,8 @@ int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   if (L.pack && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
   c->first_aside = c->xbar_rolled && c->rolled_variant == L.rollout && same_dyn(c->rolled_dyn, P.dyn);
   c->xbar_rolled = false;                                   // after this solve xbar is an accepted line-search candidate
-  if (k <= 1) {
-    TRY(enqueue_solve(c, S, P, st, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_roll, c->d_shadowx, nullptr, nullptr, c->ev_lin, c->ev_adopt));
-  } else {
-    TRY(ensure_slices(c, k));
-    HIPCHK(c, hipEventRecord(c->ev_begin, st));
-    const int per = (c->B + k - 1) / k;
-    const bool stagger = c->knobs.stagger != 0;
-    for (int i = 0; i < k; ++i) {
-      const int b0 = i * per, Bs = (b0 + per <= c->B) ? per : (c->B - b0);
-      if (Bs <= 0) continue;
-      auto& sl = c->slices[i];
-      HIPCHK(c, hipStreamWaitEvent(sl.st, c->ev_begin, 0));
-      const DevState Ss = slice_state(S, (size_t)b0, Bs);
-      const h1::ProblemDev Ps = slice_problem(P, b0);
-      TRY(enqueue_solve(c, Ss, Ps, sl.st, sl.st2, sl.st3, sl.fork, sl.join, sl.roll, c->d_shadowx, (stagger && i > 0) ? c->slices[i - 1].lead : nullptr, sl.lead));
-      HIPCHK(c, hipEventRecord(sl.done, sl.st));
-      HIPCHK(c, hipStreamWaitEvent(st, sl.done, 0));
-    }
-  }
+  if (P.al) TRY(enqueue_al_rounds(c, k));
+  else TRY(enqueue_batch(c, k));
   HIPCHK(c, hipGetLastError());
   c->solved = true;
   return ILQR_OK;
@@ -1583,7 +1785,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
   h1::ProblemDev Ps = c->P;
   std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
   Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
-  Ps.wsets = nullptr; Ps.wsets_stride = 0;
+  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and
@@ -1774,6 +1976,7 @@ int ilqr_hip_initialize_warm_from_plant(ilqr_hip_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->d_prevu, c->S.ubar, B * N * ILQR_NU * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   ilqr::launch_warm_shift(c->S, c->d_prevx, c->d_prevu, c->stream);      // (k_warm_shift reads x0 from S.x0: the plant's state by the copy above)
   ilqr::launch_last_step(plan_of(c), c->S, c->P, c->stream);
+  al_follow_initialize(c, 1);
   HIPCHK(c, hipGetLastError());
   c->xbar_rolled = false;
   return ILQR_OK;      // asynchronous on the handle's stream

@@ -129,6 +129,21 @@ void launch_control_spec(const DevState& S, const DevState& T, int iter, double 
 // n = the length of list (iter, 0).  The list-driven launchers take an explicit list / count.
 void launch_spec_gate(const DevState& S, int iter, int max, int* g, hipStream_t st);
 void launch_solve_begin(const DevState& S, hipStream_t st);
+// ---- al_kernels.h (the tail of ilqr_kernels.hip): the augmented-Lagrangian outer loop (ilqr_hip_set_augmented_lagrangian).  All pointers are device pointers of the whole batch.
+struct AlDev {
+  double* store; long stride;      // the multiplier store (h1_cost_dev.h: ProblemDev::al points at the same records)
+  double margin, growth, tol_joint, tol_ctrl, rho_joint_max, rho_ctrl_max;
+  double* viol;                    // [B][2] joint, control violation of the nominal trajectory at the last update
+  int* done;                       // [B]
+  double* trace;                   // [rounds][B][5]
+  int* left;                       // [rounds] rollouts not done after each round (zeroed ahead of the round's update)
+};
+// masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row
+void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st);
+// shift > N: every multiplier becomes zero (cold start); the penalties are reset to the given values, done flags and violations cleared
+void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st);
+// launch_solve_begin with active = !done (done: of S's rollouts)
+void launch_solve_begin_al(const DevState& S, const int* done, hipStream_t st);
 void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, unsigned long long* mismatches, hipStream_t st);
 void launch_warm_shift(const DevState& S, const double* prev_x, const double* prev_u, hipStream_t st);
 void launch_warm_shift_m(const DevState& S, const double* prev_x, const double* prev_u, int shift, hipStream_t st);

@@ -1309,3 +1309,5 @@ int backward_needs_lds_attr() {
 }
 
 }  // namespace ilqr
+
+#include "al_kernels.h"      // the augmented-Lagrangian outer loop: k_al_update, k_al_shift, k_solve_begin_al

@@ -25,6 +25,9 @@ EXPORTS = [
     "ilqr_hip_create", "ilqr_hip_destroy", "ilqr_hip_last_error", "ilqr_hip_batch", "ilqr_hip_horizon", "ilqr_hip_num_slices", "ilqr_hip_reload_environment", "ilqr_hip_set_dedup_saturated_retry",
     "ilqr_hip_set_cost_weights", "ilqr_hip_set_task_weights", "ilqr_hip_set_constraint_weights", "ilqr_hip_set_gravity",
     "ilqr_hip_set_weight_sets", "ilqr_hip_clear_weight_sets", "ilqr_hip_num_weight_sets",
+    "ilqr_hip_set_augmented_lagrangian", "ilqr_hip_clear_augmented_lagrangian", "ilqr_hip_augmented_lagrangian_rounds",
+    "ilqr_hip_get_al_multipliers", "ilqr_hip_set_al_multipliers", "ilqr_hip_get_al_penalties", "ilqr_hip_get_al_violation", "ilqr_hip_get_al_trace",
+    "ilqr_hip_al_update",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -344,6 +347,51 @@ class BatchedILQR:
     def num_weight_sets(self):
         """0: shared weights; else the number of sets of the installed table (1 or B)."""
         return int(self.L.ilqr_hip_num_weight_sets(self.h))
+
+    # ---- augmented-Lagrangian joint and torque limits (include/ilqr_hip.h ilqr_hip_set_augmented_lagrangian)
+    def set_augmented_lagrangian(self, rounds, rho_joint0, rho_ctrl0, growth=10.0, rho_max_factor=1e4, margin=0.0, tol_joint=1e-3, tol_ctrl=1e-2):
+        """Enforce the joint and torque ranges (shrunk by `margin` of their width on each side) by up to `rounds` rounds of solve + multiplier
+        update in every solve(); replaces the plain penalties w_joint / w_ctrl until clear_augmented_lagrangian()."""
+        self._chk(self.L.ilqr_hip_set_augmented_lagrangian(self.h, int(rounds), *[C.c_double(float(v)) for v in (rho_joint0, rho_ctrl0, growth, rho_max_factor, margin, tol_joint, tol_ctrl)]))
+
+    def clear_augmented_lagrangian(self):
+        """Back to the plain penalties the handle holds."""
+        self._chk(self.L.ilqr_hip_clear_augmented_lagrangian(self.h))
+
+    def augmented_lagrangian_rounds(self):
+        """0: not installed; else the rounds it was installed with."""
+        return int(self.L.ilqr_hip_augmented_lagrangian_rounds(self.h))
+
+    def al_multipliers(self):
+        """(joint [B,N+1,19,2], ctrl [B,N,19,2]): the multipliers of the (lower, upper) bounds."""
+        joint, ctrl = np.zeros((self.B, self.N + 1, NU, 2)), np.zeros((self.B, self.N, NU, 2))
+        self._chk(self.L.ilqr_hip_get_al_multipliers(self.h, _p(joint), _p(ctrl)))
+        return joint, ctrl
+
+    def set_al_multipliers(self, joint=None, ctrl=None, rho=None):
+        """Install multipliers (shapes of al_multipliers) and / or the penalties rho [B,2] = (joint, ctrl); None leaves that part as it is."""
+        joint, ctrl, rho = (None if a is None else _c64(a) for a in (joint, ctrl, rho))
+        if (joint is not None and joint.shape != (self.B, self.N + 1, NU, 2)) or (ctrl is not None and ctrl.shape != (self.B, self.N, NU, 2)) or (rho is not None and rho.shape != (self.B, 2)):
+            raise ValueError("multipliers: joint [B,N+1,19,2], ctrl [B,N,19,2], rho [B,2]")
+        self._chk(self.L.ilqr_hip_set_al_multipliers(self.h, _p(joint), _p(ctrl), _p(rho)))
+
+    def al_penalties(self):
+        """rho [B,2] = (joint, ctrl) as the store holds them."""
+        return self._get("ilqr_hip_get_al_penalties", (self.B, 2))
+
+    def al_violation(self):
+        """(viol [B,2] = (joint, ctrl), done [B]) of the last update."""
+        viol, done = np.zeros((self.B, 2)), np.zeros(self.B, dtype=np.int32)
+        self._chk(self.L.ilqr_hip_get_al_violation(self.h, _p(viol), done.ctypes.data_as(_ip)))
+        return viol, done
+
+    def al_trace(self):
+        """[rounds, B, 5]: joint violation, control violation, rho_joint, rho_ctrl, inner iterations of every round of the last solve (NaN: not run)."""
+        return self._get("ilqr_hip_get_al_trace", (self.augmented_lagrangian_rounds(), self.B, 5))
+
+    def al_update(self, round=0):
+        """Stage call: the multiplier update on the resident nominal trajectory, into row `round` of the trace."""
+        self._chk(self.L.ilqr_hip_al_update(self.h, int(round)))
 
     def set_references(self, x_ref, u_ref, com_ref):
         x_ref, u_ref, com_ref = _c64(x_ref), _c64(u_ref), _c64(com_ref)

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""Cost of the augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian) against the plain penalties on ONE handle,
+on one GPU, the two alternating:
+   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10]
+  * ms per call of the two cost stages (stage_cost_quadratics: k_quad_kin + k_cost_quadratics; stage_total_cost: k_traj_knot_cost +
+    k_traj_cost_sum) and, per launch inside a solve, of the cost quadratics (ilqr_hip_get_stage_ms, stage 2);
+  * ms per call of the update kernel alone (ilqr_hip_al_update: k_al_update, one memset, one synchronisation);
+  * one solve under the plain penalties and one three-round AL solve, fixed iteration count (what bench.py times), cold start each.
+Each stage sample is the wall time of `calls` back-to-back calls (every call synchronises the handle's stream) divided by `calls`;
+medians over the rounds are reported and no threshold is applied.  Prints one JSON line; not part of bench.py."""
+import argparse, importlib.util, json, os, sys, time
+import numpy as np
+import torch      # first HIP runtime of the process (as tests/conftest.py)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def load_package():
+    name, path = "mpc_ilqr_mujoco_amd", os.path.join(ROOT, "mpc-ilqr-mujoco_amd", "__init__.py")
+    spec = importlib.util.spec_from_file_location(name, path, submodule_search_locations=[os.path.dirname(path)])
+    mod = importlib.util.module_from_spec(spec); sys.modules[name] = mod; spec.loader.exec_module(mod)
+    return mod
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096); ap.add_argument("--horizon", type=int, default=25)
+    ap.add_argument("--calls", type=int, default=20); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", type=int, default=10)
+    a = ap.parse_args()
+    pkg = load_package()
+    from mpc_ilqr_mujoco_amd import solver as sv
+    sc = pkg.scenario
+    B, N = a.batch, a.horizon
+    prob = sc.make_problem(sv.reference_kinematics, N=N)
+    x0, ui = sc.synthetic_batch(B, N, 0, sv.gravity_compensation(sc.standing_state(), prob["gravity"]))
+    s = sv.BatchedILQR(B, N=N, dt=prob["dt"]); s.set_problem(prob)
+    s.set_options(early_exit=False); s.set_max_iterations(a.iters)
+    al = dict(rounds=3, rho_joint0=2 * prob["w_joint"], rho_ctrl0=2 * prob["w_ctrl"], growth=10.0, rho_max_factor=1e4, margin=0.1, tol_joint=0.0, tol_ctrl=0.0)
+    modes = ("plain", "al")
+    ms = {m: {"quadratics": [], "total_cost": [], "solve": [], "quadratics_per_launch_in_solve": []} for m in modes}
+    ms["al"]["update"] = []
+
+    def timed(fn, calls):
+        fn()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        return 1e3 * (time.perf_counter() - t0) / calls
+
+    for rnd in range(a.rounds + 1):                      # round 0 warms up
+        for m in modes:
+            if m == "al":
+                s.set_augmented_lagrangian(**al)
+            else:
+                s.clear_augmented_lagrangian()
+            s.initialize(x0, ui)
+            s.enable_profiling(True)
+            t0 = time.perf_counter(); s.solve(None); dt = 1e3 * (time.perf_counter() - t0)
+            st, launches = s.stage_ms()
+            s.enable_profiling(False)
+            row = {"solve": dt, "quadratics_per_launch_in_solve": float(st["iLQR_costQuadratics"] / max(1.0, launches["iLQR_costQuadratics"])),
+                   "quadratics": timed(s.stage_cost_quadratics, a.calls), "total_cost": timed(s.stage_total_cost, a.calls)}
+            if m == "al":
+                row["update"] = timed(lambda: s.al_update(0), a.calls)
+            if rnd:
+                for k, v in row.items():
+                    ms[m][k].append(v)
+    s.close()
+    print(json.dumps({"tool": "al_time", "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "calls": a.calls, "rounds": a.rounds, "iters": a.iters,
+                      "al": al, "ms_median": {m: {k: float(np.median(v)) for k, v in d.items()} for m, d in ms.items()}, "samples": ms}))
+
+
+if __name__ == "__main__":
+    main()
