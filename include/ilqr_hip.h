@@ -154,6 +154,34 @@ int ilqr_hip_get_al_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][5]*/);
 /* Stage call: the update that follows an inner solve, alone, on the resident nominal trajectory (ilqr_hip_set_trajectory) and the installed
    multipliers; writes row `round` (0 <= round < rounds) of the trace.  Synchronises. */
 int ilqr_hip_al_update(ilqr_hip_ctx* ctx, int round);
+/* One table of bounds per rollout for the augmented-Lagrangian limits.  A record is ILQR_AL_BOUNDS = 76 doubles: joint_lo[19], joint_hi[19]
+   (hinges in the order of the state slots 7..25), ctrl_lo[19], ctrl_hi[19] (actuators in the order of u).  n_sets is 1 (one record that every
+   rollout reads) or the batch (rollout b reads record b).  While a table is installed every constraint of ilqr_hip_set_augmented_lagrangian
+   takes its lo / hi from rollout b's record: the model's ranges and the margin fraction are not read, and the margin of the installation is
+   NOT applied to the table -- the table holds the final bounds.  Everything else of the description above stays as it is: the term phi,
+   the update, the violations with the hinges' knot 0 left out, the done rule, rho growth, the rounds, the warm-start shift, the getters.
+   A lower bound may be -inf and an upper bound +inf: that side is switched off -- its c is -inf, its term the constant -mu^2 / (2 rho), its
+   gradient and curvature 0, its multiplier driven to 0 by the update, its violation 0.
+   The table acts on the COST only: the solver's dynamics step keeps clamping u to the model's control range, so a torque bound wider than
+   the model's is not a wider actuator; the plant, the score and the plain penalties are untouched.
+   ILQR_ERR_STATE while no augmented Lagrangian is installed (all four handle calls).  ILQR_ERR_ARG: a null pointer, n_sets not 1 or the
+   batch, a NaN, lo > hi, lo == +inf, hi == -inf; everything is checked before the handle is touched, a refused call leaves a previously
+   installed table as it was.  lo == hi is allowed (a dead motor: ctrl_lo = ctrl_hi = 0).  Uploads and synchronises the handle's stream.
+   The table survives the cold and warm initialisers, ilqr_hip_set_al_multipliers and a repeated ilqr_hip_set_augmented_lagrangian on a
+   handle that has it installed (whose margin is then unused); ilqr_hip_clear_augmented_lagrangian drops it.  The refusals of
+   ilqr_hip_set_augmented_lagrangian (cross-check families, weight sets) stay as they are. */
+#define ILQR_AL_BOUNDS 76
+int ilqr_hip_set_al_bounds(ilqr_hip_ctx* ctx, const double* bounds /*[n_sets][76]*/, int n_sets);
+/* Back to the model's ranges at the installed margin (same kernels and kernel arguments as a handle that never had a table). */
+int ilqr_hip_clear_al_bounds(ilqr_hip_ctx* ctx);
+/* 0: no table installed, else the n_sets of the installed table (1 or the batch); -1 for a null handle */
+int ilqr_hip_num_al_bound_sets(const ilqr_hip_ctx* ctx);
+/* The record each rollout is solved with: a one-record table expanded; without a table the model's bounds at the installed margin. */
+int ilqr_hip_get_al_bounds(ilqr_hip_ctx* ctx, double* bounds /*[B][76]*/);
+/* The bounds ilqr_hip_set_augmented_lagrangian(margin) enforces without a table, as one record: lo = range[0] + margin (range[1] - range[0]),
+   hi = range[1] - margin (...), the doubles the kernels form.  margin = 0: the model's joint and control ranges.  Host only: no GPU, no
+   handle.  0 <= margin < 0.5 and a non-null pointer, else ILQR_ERR_ARG. */
+int ilqr_hip_al_default_bounds(double margin, double* bounds /*[76]*/);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N

@@ -104,6 +104,20 @@ class iLQR {
   }
   void clearAugmentedLagrangian() { chk(ilqr_hip_clear_augmented_lagrangian(ctx_)); }
   int augmentedLagrangianRounds() const { return ilqr_hip_augmented_lagrangian_rounds(ctx_); }
+  // one table of bounds per rollout for those limits (ilqr_hip_set_al_bounds): row-major [n_sets][ILQR_AL_BOUNDS] = joint_lo[19], joint_hi[19],
+  // ctrl_lo[19], ctrl_hi[19], n_sets = 1 or the batch; the table holds the final bounds (the installed margin is not applied), -inf / +inf
+  // switch a side off; getAlBounds: the record each rollout is solved with, [batch][ILQR_AL_BOUNDS]
+  void setAlBounds(const std::vector<double>& bounds, int n_sets) {
+    if (n_sets <= 0 || bounds.size() != (size_t)n_sets * ILQR_AL_BOUNDS) chk(ILQR_ERR_ARG);
+    chk(ilqr_hip_set_al_bounds(ctx_, bounds.data(), n_sets));
+  }
+  void clearAlBounds() { chk(ilqr_hip_clear_al_bounds(ctx_)); }
+  int numAlBoundSets() const { return ilqr_hip_num_al_bound_sets(ctx_); }
+  std::vector<double> getAlBounds() {
+    std::vector<double> out((size_t)ilqr_hip_batch(ctx_) * ILQR_AL_BOUNDS);
+    chk(ilqr_hip_get_al_bounds(ctx_, out.data()));
+    return out;
+  }
   void setGravity(double gx, double gy, double gz) { chk(ilqr_hip_set_gravity(ctx_, gx, gy, gz)); }
   void setContactSchedule(const std::vector<int>& stance /*[N+1][2]*/) { chk(ilqr_hip_set_contact_schedule(ctx_, stance.data(), 1)); }
   // contact row: ILQR_CONTACT_NONE (default) or ILQR_CONTACT_RIGID_STANCE on the scheduled feet

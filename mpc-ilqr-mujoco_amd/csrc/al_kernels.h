@@ -2,7 +2,8 @@
 // between two inner solves.  The cost side -- the AL instantiations of k_traj_knot_cost and k_cost_quadratics -- is in dyn_kernels.hip,
 // quad_kernels.hip and h1_cost_dev.h, which also states the layout of the multiplier store.
 //   k_al_update        multiplier update, violations, done flag, penalty growth, trace row and the count of rollouts left, one pass over
-//                      the nominal trajectory, one wave per rollout
+//                      the nominal trajectory, one wave per rollout; <true>: the bounds are rollout b's record of the bounds table
+//                      (ilqr_hip_set_al_bounds), <false> the model's ranges at the installed margin
 //   k_al_shift         warm-start shift of the multipliers by the knots the trajectory is shifted by (zero tail; shift > N: all zero), penalties reset
 //   k_solve_begin_al   k_solve_begin with active = !done: the prologue of the rounds >= 2 of a solve with the convergence exit
 // Every rule is per rollout: nothing here reads another rollout's data, and the one shared word (AlDev::left) is a count.
@@ -22,9 +23,11 @@ __device__ __forceinline__ double wave_max(double v) {
 
 // Constraint e of a knot's record, e in [0, 38): side = e / 19 (0 lower, 1 upper bound), coordinate e % 19.  The multiplier sits at
 // base + e for both families (AL_JHI = AL_JLO + 19, AL_UHI = AL_ULO + 19).
+template <bool TABLE>
 __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round, int masked) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x, lane = threadIdx.x;
+  const double* bd = A.bounds + (long)b * A.bounds_stride;      // (TABLE only: an infinite side gives c = -inf, mu = 0 and no violation)
   const int N = S.N;
   double* rec = A.store + (long)b * A.stride;
   const double rho_j = rec[AL_RHO_JOINT], rho_c = rec[AL_RHO_CTRL];
@@ -36,7 +39,8 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
   // hinges, knots 1..N (x_0 is given: its multipliers stay zero and it is left out of the violation)
   for (int e = lane; e < N * 2 * H1_NJ; e += 64) {
     const int t = 1 + e / (2 * H1_NJ), r = e % (2 * H1_NJ), side = r / H1_NJ, j = r % H1_NJ;
-    double lo, hi; al_bounds(H1_JRANGE[j], A.margin, lo, hi);
+    double lo, hi;
+    if constexpr (TABLE) { lo = bd[ALB_JLO + j]; hi = bd[ALB_JHI + j]; } else al_bounds(H1_JRANGE[j], A.margin, lo, hi);
     const double q = xb[t * H1_NX + 7 + j];
     const double c = side ? q - hi : lo - q;
     vj = c > vj ? c : vj;
@@ -49,7 +53,8 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
   // actuators, knots 0..N-1
   for (int e = lane; e < N * 2 * H1_NU; e += 64) {
     const int t = e / (2 * H1_NU), r = e % (2 * H1_NU), side = r / H1_NU, i = r % H1_NU;
-    double lo, hi; al_bounds(H1_CTRLRANGE[i], A.margin, lo, hi);
+    double lo, hi;
+    if constexpr (TABLE) { lo = bd[ALB_ULO + i]; hi = bd[ALB_UHI + i]; } else al_bounds(H1_CTRLRANGE[i], A.margin, lo, hi);
     const double u = ub[t * H1_NU + i];
     const double c = side ? u - hi : lo - u;
     vc = c > vc ? c : vc;
@@ -122,7 +127,8 @@ __global__ void __launch_bounds__(64) k_solve_begin_al(DevState S, const int* do
 }
 
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st) {
-  hipLaunchKernelGGL(k_al_update, dim3(S.B), dim3(64), 0, st, S, A, round, masked);
+  if (A.bounds) hipLaunchKernelGGL(k_al_update<true>, dim3(S.B), dim3(64), 0, st, S, A, round, masked);
+  else hipLaunchKernelGGL(k_al_update<false>, dim3(S.B), dim3(64), 0, st, S, A, round, masked);
 }
 void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st) {
   hipLaunchKernelGGL(k_al_shift, dim3(B), dim3(128), 0, st, A, N, shift, rho_joint, rho_ctrl);

@@ -229,8 +229,10 @@ __global__ void __launch_bounds__(64) k_line_search_r(DevState S, ProblemDev P, 
 // gate (optional): the launch does nothing when *gate == 0 (device-side choice between two enqueued launch orders, ilqr_capi.hip)
 // WS: each lane takes the weights of its own rollout's weight set (b comes from the clamped index idc: a lane past the end forms the
 // address of the last rollout's record, never one outside the table)
-// AL: the augmented-Lagrangian terms of the lane's own rollout and knot (ProblemDev::al) in place of the plain penalties
-template <bool WS, bool AL>
+// AL (h1_cost_dev.h AL_OFF / AL_MODEL / AL_TABLE): the augmented-Lagrangian terms of the lane's own rollout and knot (ProblemDev::al) in place
+// of the plain penalties; AL_TABLE with the bounds of the lane's own rollout (ProblemDev::alb: the knots and the eight candidates of a
+// rollout read the same five lines)
+template <bool WS, int AL>
 __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate) {
   if (gate && *gate == 0) return;
   __shared__ double xs[32 * CK_LD];     // half a wave's rows at a time: 13 KB, so that the registers (two waves per SIMD), not the LDS, set the occupancy
@@ -287,17 +289,19 @@ __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int 
 }
 void launch_cand_costs(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, bool with_sum, const int* gate) {
   const long total = (long)S.B * 8 * (S.N + 1);
-  if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  else hipLaunchKernelGGL((k_traj_knot_cost<false, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   if (with_sum) hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)(((long)S.B * 8 + 63) / 64)), dim3(64), 0, st, S, mode, 3, 0, S.cand_cost);
 }
 // computeTotalCost of the nominal trajectories (S.xbar, S.ubar) into cost_out[B], same kernels, same summation order
 void launch_nominal_costs(const DevState& S, const ProblemDev& P, int mode, double* cost_out, hipStream_t st) {
   const long total = (long)S.B * (S.N + 1);
-  if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  else hipLaunchKernelGGL((k_traj_knot_cost<false, false>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)((S.B + 63) / 64)), dim3(64), 0, st, S, mode, 0, 3, cost_out);
 }
 

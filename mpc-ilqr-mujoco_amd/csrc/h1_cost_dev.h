@@ -45,6 +45,9 @@ struct ProblemDev {
   // multiplier store, one record of al_stride doubles per rollout (layout below), and the margin fraction of the bounds.  Appended: nothing above moves
   const double* al;          long al_stride;
   double al_margin;
+  // per-rollout bounds of those limits (ilqr_hip_set_al_bounds): null = the model's ranges shrunk by al_margin; else one ALB_STRIDE record per
+  // set (layout below), stride 0 when one record serves every rollout, and al_margin is not read.  Appended: nothing above moves
+  const double* alb;         long alb_stride;
 };
 // The multiplier store, in doubles.  Rollout b's record: one 128-byte line of scalars (AL_RHO_JOINT, AL_RHO_CTRL, the rest padding), then one
 // record of AL_KNOT = 80 doubles (five whole lines) per knot t = 0..N: the hinges' multipliers of the lower bounds, of the upper bounds, two
@@ -54,6 +57,15 @@ struct ProblemDev {
 enum { AL_RHO_JOINT = 0, AL_RHO_CTRL = 1, AL_HDR = 16, AL_JLO = 0, AL_JHI = H1_NJ, AL_ULO = 40, AL_UHI = 40 + H1_NU, AL_KNOT = 80 };
 static_assert(H1_NJ == 19 && H1_NU == 19 && AL_JHI + H1_NJ <= AL_ULO && AL_UHI + H1_NU <= AL_KNOT && AL_KNOT % 16 == 0 && AL_HDR % 16 == 0, "multiplier record: whole 128-byte lines");
 inline long al_record_doubles(int N) { return AL_HDR + (long)AL_KNOT * (N + 1); }
+// The bounds table, in doubles.  One record per set: the hinges' lower bounds, their upper bounds, the actuators' lower bounds, their upper
+// bounds (the order of ilqr_hip_set_al_bounds), padded to five whole 128-byte lines.  Indexed by the rollout b, never by a position in a
+// compacted list.  A lower bound may be -inf, an upper bound +inf: the kernels form q - hi, lo - q and mu + rho c only (rho is finite and
+// positive), so c = -inf, max(0, mu + rho c) = 0 and no 0 * inf or inf - inf arises.
+enum { ALB_JLO = 0, ALB_JHI = H1_NJ, ALB_ULO = 2 * H1_NJ, ALB_UHI = 2 * H1_NJ + H1_NU, ALB_FIELDS = 2 * H1_NJ + 2 * H1_NU, ALB_STRIDE = (ALB_FIELDS + 15) / 16 * 16 };
+static_assert(ALB_FIELDS == 76 && ALB_STRIDE == 80, "bounds record: 76 doubles in five 128-byte lines");
+// Where the limit terms take their bounds from: AL_MODEL the model's ranges at ProblemDev::al_margin, AL_TABLE rollout b's record of
+// ProblemDev::alb.  (AL_OFF: the plain penalties.)  A template axis, so that the paths without a table keep their machine code.
+enum { AL_OFF = 0, AL_MODEL = 1, AL_TABLE = 2 };
 // Bounds lo = r0 + m (r1 - r0), hi = r1 - m (r1 - r0), each operation rounded once (no contraction): every kernel and the host restatement
 // of the tests then hold the same two doubles
 DEVFN void al_bounds(const double* range, double m, double& lo, double& hi) {
@@ -71,28 +83,34 @@ DEVFN double al_phi2(double c, double mu, double rho) {
   return sp * sp - mu * mu;
 }
 // the two families' terms of knot t of rollout b (x: the knot's state, u: its control), in the order of joint_penalty / ctrl_penalty
+template <int AL>
 DEVFN double al_joint_term(const ProblemDev& P, int b, int t, const double* x) {
   const double* r = P.al + (long)b * P.al_stride;
+  const double* bd = P.alb + (long)b * P.alb_stride;      // (AL_TABLE only)
   const double rho = r[AL_RHO_JOINT];
   const double* k = r + AL_HDR + (long)t * AL_KNOT;
   double c = 0.0;
 #pragma unroll
   for (int i = 0; i < H1_NJ; ++i) {
-    double lo, hi; al_bounds(H1_JRANGE[i], P.al_margin, lo, hi);
+    double lo, hi;
+    if constexpr (AL == AL_TABLE) { lo = bd[ALB_JLO + i]; hi = bd[ALB_JHI + i]; } else al_bounds(H1_JRANGE[i], P.al_margin, lo, hi);
     const double q = x[7 + i];
     c += al_phi2(q - hi, k[AL_JHI + i], rho);
     c += al_phi2(lo - q, k[AL_JLO + i], rho);
   }
   return c / (2.0 * rho);
 }
+template <int AL>
 DEVFN double al_ctrl_term(const ProblemDev& P, int b, int t, const double* u) {
   const double* r = P.al + (long)b * P.al_stride;
+  const double* bd = P.alb + (long)b * P.alb_stride;      // (AL_TABLE only)
   const double rho = r[AL_RHO_CTRL];
   const double* k = r + AL_HDR + (long)t * AL_KNOT;
   double c = 0.0;
 #pragma unroll
   for (int i = 0; i < H1_NU; ++i) {
-    double lo, hi; al_bounds(H1_CTRLRANGE[i], P.al_margin, lo, hi);
+    double lo, hi;
+    if constexpr (AL == AL_TABLE) { lo = bd[ALB_ULO + i]; hi = bd[ALB_UHI + i]; } else al_bounds(H1_CTRLRANGE[i], P.al_margin, lo, hi);
     c += al_phi2(u[i] - hi, k[AL_UHI + i], rho);
     c += al_phi2(lo - u[i], k[AL_ULO + i], rho);
   }
@@ -150,8 +168,8 @@ DEVFN bool support_point(const ProblemDev& P, int b, int t, double* ps) {
   return false;
 }
 // one knot of computeTotalCost (ilqr.cpp:370-443 / 447-510) including its share of the penalties (512-515)
-// AL: the augmented-Lagrangian terms of the installed multipliers in place of the two plain penalties
-template <bool WS, bool AL = false, class ComFn>
+// AL: AL_MODEL / AL_TABLE the augmented-Lagrangian terms of the installed multipliers in place of the two plain penalties
+template <bool WS, int AL = AL_OFF, class ComFn>
 DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, const double* u /*null at t==N*/, ComFn com_fn) {
   const CostWeights<WS> Wt(P, b);
   const bool term = (t == P.N);
@@ -180,9 +198,9 @@ DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, con
       c += 0.5 * Wt.w_balance(P) * (rx * rx + ry * ry);
     }
   }
-  if constexpr (AL) {
-    c += al_joint_term(P, b, t, x);
-    if (!term) c += al_ctrl_term(P, b, t, u);
+  if constexpr (AL != AL_OFF) {
+    c += al_joint_term<AL>(P, b, t, x);
+    if (!term) c += al_ctrl_term<AL>(P, b, t, u);
   } else {
     c += joint_penalty(P, Wt, x);
     if (!term) c += ctrl_penalty(P, Wt, u);
@@ -190,7 +208,7 @@ DEVFN double knot_cost_w(const ProblemDev& P, int b, int t, const double* x, con
   return c;
 }
 template <class ComFn>
-DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn) { return knot_cost_w<false, false>(P, b, t, x, u, com_fn); }
+DEVFN double knot_cost_t(const ProblemDev& P, int b, int t, const double* x, const double* u, ComFn com_fn) { return knot_cost_w<false, AL_OFF>(P, b, t, x, u, com_fn); }
 // The terms of knot_cost_w<false> at a NON-terminal knot, one by one, under the shared weights of P (a caller with weights of its own
 // passes a copy of P that holds them): out[0] state, [1] control, [2] upright, [3] balance, [4] joint-limit penalty, [5] control-limit
 // penalty -- the same expressions in the same order of operations, so that their sum is knot_cost_w's value up to its own additions

@@ -124,6 +124,18 @@ void pelvis_inertial_offset(double* r) {
   for (int k = 0; k < 3; ++k) r[k] = H1_COM[0][k];
 }
 
+// The bounds of the augmented-Lagrangian limits at a margin: al_bounds of h1_cost_dev.h on the host, the same four operations each rounded
+// once (no contraction), so that the doubles are the ones the kernels form from the same tables
+__attribute__((optimize("-ffp-contract=off"))) void al_default_bounds(double margin, double* bounds) {
+  for (int f = 0; f < 2; ++f)
+    for (int i = 0; i < H1_NJ; ++i) {
+      const double* range = f ? H1_CTRLRANGE[i] : H1_JRANGE[i];
+      const double d = range[1] - range[0];
+      const double mg = margin * d;
+      bounds[2 * H1_NJ * f + i] = range[0] + mg; bounds[2 * H1_NJ * f + H1_NJ + i] = range[1] - mg;
+    }
+}
+
 // qfrc_bias[6+j] at zero velocity = minus the generalized gravity force on hinge j
 void gravity_compensation(const double* x, const double* g, double* u) {
   double Rw[H1_NB][9], pw[H1_NB][3];

@@ -8,4 +8,5 @@ void foot_clearance(const double* q, double* clr);
 void terrain_stance(const double* q, const double* terrain, long interval, int* stance, double* floor);
 void gravity_compensation(const double* x, const double* g, double* u);
 void pelvis_inertial_offset(double* r);
+void al_default_bounds(double margin, double* bounds /*76: joint lo, joint hi, ctrl lo, ctrl hi*/);
 }  // namespace h1host

@@ -87,6 +87,11 @@ struct ilqr_hip_ctx {
   double *d_al = nullptr, *d_al_viol = nullptr, *d_al_trace = nullptr;
   int *d_al_done = nullptr, *d_al_left = nullptr, *h_al_left = nullptr;
   hipEvent_t ev_al = nullptr;
+  // bounds table of the augmented Lagrangian (ilqr_hip_set_al_bounds): installed while P.alb points at d_alb [B][ALB_STRIDE] (allocated by the
+  // first call, kept by the handle); h_alb the installed records as the caller gave them, [n_alb][76]
+  double* d_alb = nullptr;
+  int n_alb = 0;                          // 0: the model's ranges at the installed margin, else the installed table's n_sets
+  std::vector<double> h_alb;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
@@ -229,21 +234,15 @@ struct ilqr_hip_ctx {
   int track_rows = 0, track_contact_rows = 0, track_sets = 1, track_max_start = 0;
 };
 
-#define HIPCHK(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                       \
-      return ILQR_ERR_HIP;                                                                  \
-    }                                                                                       \
-  } while (0)
-
-// the same check with the message built out of line (HIPCHK expands to ~200 bytes of string handling per use)
+// A failed HIP call: "<the call>: <HIP's message>" into the handle, ILQR_ERR_HIP to the caller.  The message is built out of line: built
+// in place it was ~200 bytes of string handling per use, 250 uses, and the product library has to stay under 0.8 x the test library
+// (test_product_library_holds_the_default_kernel_family_only)
 __attribute__((noinline, cold)) static int hip_failed(ilqr_hip_ctx* c, const char* what, hipError_t e) {
   c->err = std::string(what) + ": " + hipGetErrorString(e);
   return ILQR_ERR_HIP;
 }
-#define HIPCHK_S(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed((ctx), #call, e_); } while (0)
+#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed((ctx), #call, e_); } while (0)
+#define HIPCHK_S(ctx, call) HIPCHK(ctx, call)
 
 template <class T> static int dalloc(ilqr_hip_ctx* c, T** p, size_t count) {
   HIPCHK(c, hipMalloc((void**)p, count * sizeof(T)));
@@ -313,6 +312,7 @@ static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   A.margin = c->P.al_margin; A.growth = c->al_growth; A.tol_joint = c->al_tol[0]; A.tol_ctrl = c->al_tol[1];
   A.rho_joint_max = c->al_rho0[0] * c->al_max_factor; A.rho_ctrl_max = c->al_rho0[1] * c->al_max_factor;
   A.viol = c->d_al_viol; A.done = c->d_al_done; A.trace = c->d_al_trace; A.left = c->d_al_left;
+  A.bounds = c->P.alb; A.bounds_stride = c->P.alb_stride;
   return A;
 }
 // the multipliers follow the trajectory: shifted by the knots it is shifted by (shift > N: a cold start, all zero), penalties back to their
@@ -443,7 +443,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   P.x_ref = c->d_xref; P.u_ref = c->d_uref; P.com_ref = c->d_comref; P.stance = c->d_stance; P.ee_ref = c->d_eeref; P.com_vel_ref = c->d_comvelref;
   P.x_ref_stride = P.u_ref_stride = P.com_ref_stride = P.stance_stride = P.ee_ref_stride = P.com_vel_ref_stride = 0;
   P.wsets = nullptr; P.wsets_stride = 0;
-  P.al = nullptr; P.al_stride = 0; P.al_margin = 0.0;
+  P.al = nullptr; P.al_stride = 0; P.al_margin = 0.0; P.alb = nullptr; P.alb_stride = 0;
   // default: stance everywhere (RobotUtils::isStance default, robot_utils.cpp:494-504), lambda = 1e-6 (ilqr.cpp:16)
   std::vector<int> ones((N + 1) * 2, 1);
   hipMemcpyAsync(c->d_stance, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
@@ -467,7 +467,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_alb, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->h_al_left) (void)hipHostFree(c->h_al_left);
   if (c->ev_al) hipEventDestroy(c->ev_al);
@@ -575,9 +575,58 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
 int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al_rounds = 0; c->al_rounds_run = 0;      // (the buffers stay with the handle for the next call)
+  c->P.alb = nullptr; c->P.alb_stride = 0; c->n_alb = 0;      // (the bounds table goes with it: a fresh installation starts on the model's ranges)
   return ILQR_OK;
 }
 int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al_rounds : 0) : -1; }
+// ---- the bounds table: one record of ILQR_AL_BOUNDS doubles per set, joint lo, joint hi, ctrl lo, ctrl hi
+int ilqr_hip_al_default_bounds(double margin, double* bounds) {
+  if (!bounds || !(margin >= 0.0) || !(margin < 0.5)) return ILQR_ERR_ARG;
+  h1host::al_default_bounds(margin, bounds);
+  return ILQR_OK;
+}
+// every pair: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
+__attribute__((noinline, minsize)) static bool al_bounds_ok(const double* v, int n_sets) {
+  for (int s = 0; s < n_sets; ++s)
+    for (int f = 0; f < 2; ++f)
+      for (int i = 0; i < 19; ++i) {
+        const double lo = v[(size_t)s * ILQR_AL_BOUNDS + 38 * f + i], hi = v[(size_t)s * ILQR_AL_BOUNDS + 38 * f + 19 + i];
+        if (!(lo <= hi) || lo == HUGE_VAL || hi == -HUGE_VAL) return false;      // (a NaN fails lo <= hi)
+      }
+  return true;
+}
+int ilqr_hip_set_al_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  if (!bounds || check_sets(c, n_sets) || !al_bounds_ok(bounds, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  if (!c->d_alb) TRY(dalloc(c, &c->d_alb, (size_t)c->B * h1::ALB_STRIDE));
+  static_assert(h1::ALB_FIELDS == ILQR_AL_BOUNDS && h1::ALB_JHI == 19 && h1::ALB_ULO == 38 && h1::ALB_UHI == 57, "the interface's record is the device record without its padding");
+  std::vector<double> rec((size_t)n_sets * h1::ALB_STRIDE, 0.0);
+  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * h1::ALB_STRIDE, bounds + (size_t)s * ILQR_AL_BOUNDS, sizeof(double) * ILQR_AL_BOUNDS);
+  HIPCHK(c, hipMemcpyAsync(c->d_alb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->h_alb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_BOUNDS);
+  c->P.alb = c->d_alb; c->P.alb_stride = n_sets == 1 ? 0 : (long)h1::ALB_STRIDE;
+  c->n_alb = n_sets;
+  return ILQR_OK;
+}
+int ilqr_hip_clear_al_bounds(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  c->P.alb = nullptr; c->P.alb_stride = 0; c->n_alb = 0;      // (the buffer stays with the handle for the next table)
+  return ILQR_OK;
+}
+int ilqr_hip_num_al_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alb : -1; }
+int ilqr_hip_get_al_bounds(ilqr_hip_ctx* c, double* bounds) {
+  if (!c || !bounds) return ILQR_ERR_ARG;
+  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  double def[ILQR_AL_BOUNDS];
+  if (!c->n_alb) h1host::al_default_bounds(c->P.al_margin, def);
+  for (int b = 0; b < c->B; ++b)
+    std::memcpy(bounds + (size_t)b * ILQR_AL_BOUNDS, c->n_alb ? c->h_alb.data() + (size_t)(c->n_alb == 1 ? 0 : b) * ILQR_AL_BOUNDS : def, sizeof(double) * ILQR_AL_BOUNDS);
+  return ILQR_OK;
+}
 // host image of the store <-> the interface's [B][N+1][19][2] / [B][N][19][2] (lo, hi) arrays
 static int al_read_store(ilqr_hip_ctx* c, std::vector<double>& st) {
   st.resize((size_t)c->B * h1::al_record_doubles(c->N));
@@ -963,6 +1012,7 @@ static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
   T.stance += b0 * P.stance_stride; T.ee_ref += b0 * P.ee_ref_stride; T.com_vel_ref += b0 * P.com_vel_ref_stride;
   if (P.wsets) T.wsets += b0 * P.wsets_stride;
   if (P.al) T.al += b0 * P.al_stride;
+  if (P.alb) T.alb += b0 * P.alb_stride;
   return T;
 }
 static int ensure_slices(ilqr_hip_ctx* c, int k) {
@@ -1785,7 +1835,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
   h1::ProblemDev Ps = c->P;
   std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
   Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
-  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0;
+  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and

@@ -137,6 +137,7 @@ struct AlDev {
   int* done;                       // [B]
   double* trace;                   // [rounds][B][5]
   int* left;                       // [rounds] rollouts not done after each round (zeroed ahead of the round's update)
+  const double* bounds; long bounds_stride;      // the bounds table (ProblemDev::alb, the same records; stride 0: one record for all); null: the model's ranges at `margin`
 };
 // masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st);

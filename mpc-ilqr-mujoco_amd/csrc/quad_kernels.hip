@@ -652,8 +652,11 @@ DEVFN void quad_hessian_tiles(const double (&av)[4][2], const double (&bv)[4][4]
 // table is indexed by the rollout b, never by its position bs in a compacted list.
 // AL: the hinge lanes (7..25 of wave 0) and the actuator lanes (0..18 of wave 1) add the augmented-Lagrangian terms of their two bounds
 // (h1_cost_dev.h al_phi2) in place of the plain penalty.  Their two multipliers come with the phase-0 requests, the rollout's two penalties
-// as scalar loads ahead of the first store (b is pinned to a scalar register as for WS).
-template <bool WS, bool AL>
+// as scalar loads ahead of the first store (b is pinned to a scalar register as for WS).  AL is h1_cost_dev.h's AL_OFF / AL_MODEL / AL_TABLE;
+// AL_TABLE: the same lanes request their own lo and hi from rollout b's bounds record (ProblemDev::alb) beside their two multipliers --
+// two more per-lane loads in the phase-0 batch, nothing on the path between phase 0 and the lanes' use in phases 1b / 2.  Indexed by b,
+// never by bs, as the weight sets are.
+template <bool WS, int AL>
 __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S, ProblemDev P, int mode, const int* list, const int* count, int lower,
                                                                      const double* recg, long knot0) {
   const int lane = threadIdx.x, wv = lane >> 6;
@@ -665,14 +668,14 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   const int bs = (int)(item / (unsigned)N1), t = (int)(item - (unsigned)bs * (unsigned)N1);
   int b = bs;
   if (list) { b = list[bs]; mode = MASK_ALL; }     // compacted selection (DevState::order): no per-rollout flags to fetch
-  if constexpr (WS || AL) b = __builtin_amdgcn_readfirstlane(b);
+  if constexpr (WS || AL != AL_OFF) b = __builtin_amdgcn_readfirstlane(b);
   const CostWeights<WS> Wt(P, b);
   // the set's four scalars this kernel uses, fetched ahead of its first store: behind a store they could not be scalar loads any more
   const double w_upright_b = Wt.w_upright(P), w_balance_b = Wt.w_balance(P), w_joint_b = Wt.w_joint(P), w_ctrl_b = Wt.w_ctrl(P);
   const bool term = (t == N);
   const bool pk = lower == 2;            // operand layout (every knot, the terminal one included)
-  double al_rho_j = 0.0, al_rho_c = 0.0, al_mu_lo = 0.0, al_mu_hi = 0.0;
-  if constexpr (AL) { const double* ar = P.al + (long)b * P.al_stride; al_rho_j = ar[AL_RHO_JOINT]; al_rho_c = ar[AL_RHO_CTRL]; }
+  double al_rho_j = 0.0, al_rho_c = 0.0, al_mu_lo = 0.0, al_mu_hi = 0.0, al_lo = 0.0, al_hi = 0.0;
+  if constexpr (AL != AL_OFF) { const double* ar = P.al + (long)b * P.al_stride; al_rho_j = ar[AL_RHO_JOINT]; al_rho_c = ar[AL_RHO_CTRL]; }
   __shared__ QuadLds L;
 #ifdef QUAD_STAMP
   long long qlast = clock64();
@@ -703,11 +706,16 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
     xv = xg[a]; xrv = (P.x_ref + b * P.x_ref_stride + t * H1_NX)[a]; qdv = Qd[a];
     const int l1 = lane - 64, iu = (l1 >= 0 && l1 < H1_NU) ? l1 : 0, tu = term ? N - 1 : t;
     if (wv == 1) { uv = S.ubar[((size_t)b * N + tu) * H1_NU + iu]; urv = (P.u_ref + b * P.u_ref_stride + tu * H1_NU)[iu]; if constexpr (WS) rwv = Wt.R(P, iu); }
-    if constexpr (AL) {
+    if constexpr (AL != AL_OFF) {
       // wave 0: hinge lane - 7 of knot t; wave 1: actuator lane - 64 of knot tu (indices clamped into the knot's record, masked by the users)
       const double* ak = P.al + (long)b * P.al_stride + AL_HDR + (long)(wv == 0 ? t : tu) * AL_KNOT;
       const int ai = wv == 0 ? AL_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : AL_ULO + iu;
       al_mu_lo = ak[ai]; al_mu_hi = ak[ai + H1_NJ];
+      if constexpr (AL == AL_TABLE) {
+        const double* ab = P.alb + (long)b * P.alb_stride;      // (the same clamped coordinate; ALB_JHI = ALB_JLO + 19, ALB_UHI = ALB_ULO + 19)
+        const int bi = wv == 0 ? ALB_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : ALB_ULO + iu;
+        al_lo = ab[bi]; al_hi = ab[bi + H1_NJ];
+      }
     }
     // the table words of phases 1a and 2b travel with the knot's data as well (each was a dependent round trip to the constant
     // segment in the middle of its phase: 8 k cycles for a phase of ~40 instructions)
@@ -797,9 +805,10 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       }
       if (has_bal) g += w_balance_b * (jr0 * bal[0] + jr1 * bal[1]);
       double dgl = qdv;
-      if constexpr (AL) {
+      if constexpr (AL != AL_OFF) {
         if (a >= 7 && a < H1_NQ) {
-          double lo, hi; al_bounds(H1_JRANGE[a - 7], P.al_margin, lo, hi);
+          double lo, hi;
+          if constexpr (AL == AL_TABLE) { lo = al_lo; hi = al_hi; } else al_bounds(H1_JRANGE[a - 7], P.al_margin, lo, hi);
           const double q = xv;                           // (hinge slots are not permuted)
           const double sh = al_mu_hi + al_rho_j * (q - hi), sl = al_mu_lo + al_rho_j * (lo - q);
           if (sh > 0.0) { g += sh; dgl += al_rho_j; }
@@ -851,8 +860,9 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       const double u = uv;
       auto Rl = [&]() { if constexpr (WS) return rwv; else return Wt.R(P, l1); };         // (the set's R[l1] came with the phase-0 loads)
       double g = Rl() * (u - urv), h = Rl();
-      if constexpr (AL) {
-        double lo, hi; al_bounds(H1_CTRLRANGE[l1], P.al_margin, lo, hi);
+      if constexpr (AL != AL_OFF) {
+        double lo, hi;
+        if constexpr (AL == AL_TABLE) { lo = al_lo; hi = al_hi; } else al_bounds(H1_CTRLRANGE[l1], P.al_margin, lo, hi);
         const double sh = al_mu_hi + al_rho_c * (u - hi), sl = al_mu_lo + al_rho_c * (lo - u);
         if (sh > 0.0) { g += sh; h += al_rho_c; }
         if (sl > 0.0) { g -= sl; h += al_rho_c; }
@@ -1036,9 +1046,10 @@ void launch_cost_quadratics(const DevState& S, const ProblemDev& P, int mode, hi
   else hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
   // one workgroup per knot; the grid is padded to a multiple of 8 so that every XCD's share (L % 8) has ceil(total / 8) slots
   const long per = (knots + 7) / 8;
-  if (P.al) hipLaunchKernelGGL((k_cost_quadratics<false, true>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else if (P.wsets) hipLaunchKernelGGL((k_cost_quadratics<true, false>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else hipLaunchKernelGGL((k_cost_quadratics<false, false>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  if (P.al && P.alb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_TABLE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  else if (P.al) hipLaunchKernelGGL((k_cost_quadratics<false, AL_MODEL>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  else if (P.wsets) hipLaunchKernelGGL((k_cost_quadratics<true, AL_OFF>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  else hipLaunchKernelGGL((k_cost_quadratics<false, AL_OFF>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
 }
 
 }  // namespace ilqr

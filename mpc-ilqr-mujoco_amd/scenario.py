@@ -287,6 +287,85 @@ def stack_plant_joints(records, B):
     return out
 
 
+_AL_BOUND_FIELDS = ("joint_lo", "joint_hi", "ctrl_lo", "ctrl_hi")
+
+
+def _check_al_bounds(out):
+    """what ilqr_hip_set_al_bounds refuses"""
+    lo, hi = out.reshape(-1, 2, 2, 19)[:, :, 0], out.reshape(-1, 2, 2, 19)[:, :, 1]
+    if np.isnan(out).any() or (lo > hi).any() or (lo == np.inf).any() or (hi == -np.inf).any():
+        raise ValueError("bounds: no NaN, lo <= hi, lo < +inf, hi > -inf")
+    return out
+
+
+def stack_al_bounds(records, B, margin=0.0):
+    """Bounds table [n, 76] for BatchedILQR.set_al_bounds: joint_lo[19], joint_hi[19] (hinges in the order of the state slots 7..25),
+    ctrl_lo[19], ctrl_hi[19] (order of u).  records is one dict (n = 1: every rollout reads it) or a sequence of B dicts (n = B).  Every key
+    is optional: "joint_lo", "joint_hi", "ctrl_lo", "ctrl_hi", each a [19] array or a dict {index: value} that overrides single
+    coordinates, and "torque_scale", a scalar or [19], which scales both ends of the model's control bound at `margin` as the `scale` of
+    plant_joints scales the plant's clamp (0: a dead motor, lo = hi = 0); "ctrl_lo" / "ctrl_hi" are applied after it.  A key left out gives
+    the default bound at `margin` (solver.al_default_bounds).  -inf / +inf switch a side off.  Raises ValueError for another key, a wrong
+    shape or index, a sequence that is not B long, or a record ilqr_hip_set_al_bounds refuses (a NaN, lo > hi, lo = +inf, hi = -inf)."""
+    from . import solver
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    if isinstance(records, dict):
+        records = [records]
+    else:
+        records = list(records)
+        if len(records) != B:
+            raise ValueError("records must be one dict or B of them")
+    default = solver.al_default_bounds(margin)
+    out = np.tile(default, (len(records), 1))
+    for b, rec in enumerate(records):
+        if not isinstance(rec, dict):
+            raise ValueError("a bounds record is a dict")
+        extra = set(rec) - set(_AL_BOUND_FIELDS) - {"torque_scale"}
+        if extra:
+            raise ValueError("unknown bounds field(s) %s: a record has %s and torque_scale" % (sorted(extra), list(_AL_BOUND_FIELDS)))
+        if "torque_scale" in rec:
+            sc_ = np.asarray(rec["torque_scale"], dtype=np.float64)
+            if sc_.shape not in ((), (19,)) or not np.isfinite(sc_).all() or (sc_ < 0).any():
+                raise ValueError("torque_scale must be a finite scalar or [19], >= 0")
+            out[b, 38:57] = sc_ * default[38:57]; out[b, 57:76] = sc_ * default[57:76]
+        for k, name in enumerate(_AL_BOUND_FIELDS):
+            v = rec.get(name)
+            if v is None:
+                continue
+            if isinstance(v, dict):
+                for i, val in v.items():
+                    if not (isinstance(i, (int, np.integer)) and 0 <= i < 19):
+                        raise ValueError("%s: index %r is not in 0..18" % (name, i))
+                    out[b, 19 * k + int(i)] = float(val)
+            else:
+                v = np.asarray(v, dtype=np.float64)
+                if v.shape != (19,):
+                    raise ValueError("%s must be [19] or {index: value}" % name)
+                out[b, 19 * k:19 * (k + 1)] = v
+    return _check_al_bounds(out)
+
+
+def al_bounds_from_plant_joints(joints, margin=0.0):
+    """The bounds table [n, 76] in which the solver knows each rollout's torque range of stack_plant_joints' records `joints` [n, 76]:
+    ctrl_lo, ctrl_hi = range_scale_i * the default control bound of actuator i at `margin` (range_scale = 0, a dead motor: lo = hi = 0);
+    the joint bounds are the default.  The per-joint `gain` of the records is NOT folded in: the plant multiplies the commanded torque by it
+    ahead of its clamp, so the command that saturates is hi / gain, which this table does not express; neither are damping and armature."""
+    from . import solver
+    j = np.asarray(joints, dtype=np.float64)
+    if j.ndim == 1:
+        j = j[None]
+    if j.ndim != 2 or j.shape[1] != 76:
+        raise ValueError("joints must be [n, 76] (stack_plant_joints)")
+    scale = j[:, 19:38]
+    if not np.isfinite(scale).all() or (scale < 0).any():
+        raise ValueError("range_scale must be finite and >= 0")
+    default = solver.al_default_bounds(margin)
+    out = np.tile(default, (j.shape[0], 1))
+    out[:, 38:57] = scale * default[38:57]; out[:, 57:76] = scale * default[57:76]
+    return _check_al_bounds(out)
+
+
 # fields of a terrain record in record order with their flat defaults (solver.PLANT_TERRAIN): the solver's ground, everywhere, always
 _TERRAIN_FIELDS = (("z_left", 0.0), ("z_right", 0.0), ("edge_x", -np.inf), ("first", 0.0), ("end", np.inf))
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "ilqr_hip_set_augmented_lagrangian", "ilqr_hip_clear_augmented_lagrangian", "ilqr_hip_augmented_lagrangian_rounds",
     "ilqr_hip_get_al_multipliers", "ilqr_hip_set_al_multipliers", "ilqr_hip_get_al_penalties", "ilqr_hip_get_al_violation", "ilqr_hip_get_al_trace",
     "ilqr_hip_al_update",
+    "ilqr_hip_set_al_bounds", "ilqr_hip_clear_al_bounds", "ilqr_hip_num_al_bound_sets", "ilqr_hip_get_al_bounds", "ilqr_hip_al_default_bounds",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -83,6 +84,8 @@ PLANT_ACTUATOR_MAX_DELAY = 8
 # fields of a plant joint record (include/ilqr_hip.h ILQR_PLANT_JOINTS), 19 values each in the order of u, with their nominal values
 PLANT_JOINT_FIELDS = (("gain", 1.0), ("range_scale", 1.0), ("damping", 1.0), ("armature", 0.1))
 PLANT_JOINTS = 76
+# one record of the bounds table of the augmented-Lagrangian limits (ILQR_AL_BOUNDS): joint_lo[19], joint_hi[19], ctrl_lo[19], ctrl_hi[19]
+AL_BOUNDS = 76
 # columns of a plant terrain record (include/ilqr_hip.h ILQR_PLANT_TERRAIN)
 PLANT_TERRAIN = ("z_left", "z_right", "edge_x", "first", "end")
 
@@ -208,6 +211,16 @@ def gravity_compensation(x, gravity):
     if rc:
         raise ILQRError(STATUS.get(rc, str(rc)))
     return u
+
+
+def al_default_bounds(margin=0.0):
+    """The bounds set_augmented_lagrangian(margin=...) enforces without a table, as one record [AL_BOUNDS] = joint_lo[19], joint_hi[19],
+    ctrl_lo[19], ctrl_hi[19]; margin = 0: the model's joint and control ranges (ilqr_hip_al_default_bounds; host only)."""
+    out = np.zeros(AL_BOUNDS)
+    rc = load_library().ilqr_hip_al_default_bounds(C.c_double(float(margin)), _p(out))
+    if rc:
+        raise ILQRError(STATUS.get(rc, str(rc)))
+    return out
 
 
 def weight_sets_of(prob, B):
@@ -392,6 +405,30 @@ class BatchedILQR:
     def al_update(self, round=0):
         """Stage call: the multiplier update on the resident nominal trajectory, into row `round` of the trace."""
         self._chk(self.L.ilqr_hip_al_update(self.h, int(round)))
+
+    def set_al_bounds(self, bounds):
+        """One table of bounds per rollout for the augmented-Lagrangian limits: [AL_BOUNDS] / [1, AL_BOUNDS] (every rollout) or
+        [B, AL_BOUNDS] (rollout b reads row b); columns joint_lo[19], joint_hi[19], ctrl_lo[19], ctrl_hi[19] (al_default_bounds,
+        scenario.stack_al_bounds).  The table holds the final bounds: the installed margin is not applied to it.  -inf / +inf switch a side
+        off.  Acts on the cost only; stays until clear_al_bounds() or clear_augmented_lagrangian()."""
+        b = _c64(bounds)
+        if b.ndim == 1:
+            b = b[None]
+        if b.ndim != 2 or b.shape[1] != AL_BOUNDS:
+            raise ValueError("bounds must be [%d], [1, %d] or [B, %d]" % (AL_BOUNDS, AL_BOUNDS, AL_BOUNDS))
+        self._chk(self.L.ilqr_hip_set_al_bounds(self.h, _p(b), int(b.shape[0])))
+
+    def clear_al_bounds(self):
+        """Back to the model's ranges at the installed margin."""
+        self._chk(self.L.ilqr_hip_clear_al_bounds(self.h))
+
+    def num_al_bound_sets(self):
+        """0: no table; else the number of records of the installed table (1 or B)."""
+        return int(self.L.ilqr_hip_num_al_bound_sets(self.h))
+
+    def al_bounds(self):
+        """[B, AL_BOUNDS]: the record each rollout is solved with (without a table: the model's bounds at the installed margin)."""
+        return self._get("ilqr_hip_get_al_bounds", (self.B, AL_BOUNDS))
 
     def set_references(self, x_ref, u_ref, com_ref):
         x_ref, u_ref, com_ref = _c64(x_ref), _c64(u_ref), _c64(com_ref)

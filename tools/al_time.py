@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Cost of the augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian) against the plain penalties on ONE handle,
 on one GPU, the two alternating:
-   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10]
+   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds]
   * ms per call of the two cost stages (stage_cost_quadratics: k_quad_kin + k_cost_quadratics; stage_total_cost: k_traj_knot_cost +
     k_traj_cost_sum) and, per launch inside a solve, of the cost quadratics (ilqr_hip_get_stage_ms, stage 2);
   * ms per call of the update kernel alone (ilqr_hip_al_update: k_al_update, one memset, one synchronisation);
   * one solve under the plain penalties and one three-round AL solve, fixed iteration count (what bench.py times), cold start each.
 Each stage sample is the wall time of `calls` back-to-back calls (every call synchronises the handle's stream) divided by `calls`;
-medians over the rounds are reported and no threshold is applied.  Prints one JSON line; not part of bench.py."""
+medians over the rounds are reported and no threshold is applied.  Prints one JSON line; not part of bench.py.
+--bounds adds two modes to the alternation on the same handle: AL under a one-record table of bounds (ilqr_hip_set_al_bounds, n_sets = 1)
+and under a per-rollout table (n_sets = batch).  Both tables hold the bounds the installation has without a table, so the three AL modes
+do the same arithmetic on the same values and differ in where the bounds come from."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py)
@@ -25,6 +28,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096); ap.add_argument("--horizon", type=int, default=25)
     ap.add_argument("--calls", type=int, default=20); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--bounds", action="store_true", help="also time AL under a one-record and under a per-rollout table of bounds")
     a = ap.parse_args()
     pkg = load_package()
     from mpc_ilqr_mujoco_amd import solver as sv
@@ -35,9 +39,11 @@ def main():
     s = sv.BatchedILQR(B, N=N, dt=prob["dt"]); s.set_problem(prob)
     s.set_options(early_exit=False); s.set_max_iterations(a.iters)
     al = dict(rounds=3, rho_joint0=2 * prob["w_joint"], rho_ctrl0=2 * prob["w_ctrl"], growth=10.0, rho_max_factor=1e4, margin=0.1, tol_joint=0.0, tol_ctrl=0.0)
-    modes = ("plain", "al")
+    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ())
     ms = {m: {"quadratics": [], "total_cost": [], "solve": [], "quadratics_per_launch_in_solve": []} for m in modes}
-    ms["al"]["update"] = []
+    for m in modes[1:]:
+        ms[m]["update"] = []
+    record = sv.al_default_bounds(al["margin"])
 
     def timed(fn, calls):
         fn()
@@ -48,10 +54,15 @@ def main():
 
     for rnd in range(a.rounds + 1):                      # round 0 warms up
         for m in modes:
-            if m == "al":
-                s.set_augmented_lagrangian(**al)
-            else:
+            if m == "plain":
                 s.clear_augmented_lagrangian()
+            else:
+                s.set_augmented_lagrangian(**al)
+                if m == "al":
+                    s.clear_al_bounds()
+                else:
+                    s.set_al_bounds(record if m == "al_bounds_1" else np.tile(record, (B, 1)))
+                assert s.num_al_bound_sets() == {"al": 0, "al_bounds_1": 1, "al_bounds_B": B}[m]
             s.initialize(x0, ui)
             s.enable_profiling(True)
             t0 = time.perf_counter(); s.solve(None); dt = 1e3 * (time.perf_counter() - t0)
@@ -59,7 +70,7 @@ def main():
             s.enable_profiling(False)
             row = {"solve": dt, "quadratics_per_launch_in_solve": float(st["iLQR_costQuadratics"] / max(1.0, launches["iLQR_costQuadratics"])),
                    "quadratics": timed(s.stage_cost_quadratics, a.calls), "total_cost": timed(s.stage_total_cost, a.calls)}
-            if m == "al":
+            if m != "plain":
                 row["update"] = timed(lambda: s.al_update(0), a.calls)
             if rnd:
                 for k, v in row.items():
