@@ -796,6 +796,40 @@ int ilqr_hip_get_iterations_enqueued(const ilqr_hip_ctx* ctx);
    old) is between 512 and 2048 both orders are enqueued and the device takes one by the length of the work list (ILQR_SPEC_DUAL=0: host
    count alone).  Environment ILQR_SPEC=0 keeps the sequential order.  Returns the count, -1 for a null handle. */
 int ilqr_hip_get_speculative_iterations(const ilqr_hip_ctx* ctx);
+/* Listed side-by-side order (on by default): in a fixed-iteration solve of a batch above ILQR_SPEC_MAX the late iterations' lists are short
+   and the chip is nearly empty, yet each iteration is a chain of two latency-bound passes.  From iteration 3 max_iterations / 5 on (environment
+   ILQR_SPEC_LIST_FROM moves the start, at least 1) the device then takes, per iteration and by the lengths of its lists, the order that runs
+   them side by side: the first pass of the rollouts that accepted a candidate
+   in the previous iteration (list chg), their lambda retry speculatively into the twin buffers, and -- on the solve's own buffers -- the retry
+   of the rollouts whose two searches of the previous iteration both failed below the lambda cap (list kr: their first pass is skipped and
+   fails by construction, so the retry is known before the iteration starts).  Taken while 2 chg_n + kr_n <= ILQR_SPEC_LIST_MAX (environment,
+   default 1024 one-wave-per-SIMD slots); both orders are enqueued and the one not taken sees empty lists.  Every observable of the solve is
+   that of the sequential order (GPU tests).  Not counted by ilqr_hip_get_speculative_iterations.  Off with on = 0, ILQR_SPEC_LISTS=0 or
+   ILQR_SPEC=0 (the parent's launch order exactly), and wherever the lists do not exist: convergence exit, batch slices, forward-difference
+   Jacobians, the early-continuation split, ILQR_REPASS=1, ILQR_RELIN=1, ILQR_DEDUP_RETRY=0 and their setters.  The twin buffers (0.33 MB per
+   rollout) are allocated by the first solve that can take the order; a failed allocation keeps the sequential order.
+   ilqr_hip_get_first_pass_rollouts / _retry_pass_rollouts keep counting the rollouts whose pass ran: chg_n for the first pass and
+   chg_n + kr_n for the retry side of an iteration taken in this order. */
+int ilqr_hip_set_listed_spec(ilqr_hip_ctx* ctx, int on);
+/* Iterations of the last solve in which the device took the listed side-by-side order (read from the per-iteration gate words).
+   Synchronises the handle's stream.  -1 for a null handle or a failed read. */
+int ilqr_hip_get_listed_spec_iterations(ilqr_hip_ctx* ctx);
+/* One code per enqueued iteration of the last solve into out[0 .. max_iterations): returns the count, -1 for a null argument or a failed
+   read.  Synchronises the handle's stream. */
+enum {
+  ILQR_ORDER_SEQUENTIAL = 0,      /* first pass, bookkeeping, lambda retry, bookkeeping */
+  ILQR_ORDER_TWIN = 1,            /* both passes side by side for every active rollout (ilqr_hip_get_speculative_iterations) */
+  ILQR_ORDER_DUAL_SEQUENTIAL = 2, /* both of the above enqueued, the device took the sequential one */
+  ILQR_ORDER_DUAL_TWIN = 3,       /* ... the side-by-side one */
+  ILQR_ORDER_LISTED_SPEC = 4      /* listed side by side (above); an iteration that enqueued the pair and took the sequential order reports 0 */
+};
+int ilqr_hip_get_iteration_orders(ilqr_hip_ctx* ctx, int* out);
+/* The two lists iteration `iter` (0 <= iter < max_iterations) of the last solve started from, as the device left them (diagnostics, tests):
+   counts[0] rollouts into chg (batch entries; may be NULL) -- those that accepted a candidate in iteration iter - 1 --, counts[1] into kr
+   (likewise) -- those whose two searches of iter - 1 failed below the lambda cap.  Disjoint; an active rollout on neither is stuck at the
+   cap and runs no pass.  Iteration 0 runs every rollout: both counts 0.  The order within a list is not defined.  Synchronises the handle's
+   stream.  ILQR_ERR_STATE when the last solve kept no lists (none yet, batch slices, forward differences, ILQR_RELIN=1). */
+int ilqr_hip_get_iteration_lists(ilqr_hip_ctx* ctx, int iter, int* chg, int* kr, int* counts);
 /* Iterations of the last solve whose concurrent region (linearisation, cost quadratics, nominal re-rollout: ilqr.cpp:551-588) ran in
    two groups: the rollouts whose first line search of the previous iteration accepted a step start right behind that iteration's first
    bookkeeping pass, beside the lambda retry (:619-644) of the others, which follow behind the second; both meet at the backward pass.

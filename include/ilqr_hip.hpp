@@ -19,6 +19,7 @@
 #include <ostream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ilqr_hip.h"
@@ -139,6 +140,23 @@ class iLQR {
   void setOptions(int jacobian_mode, double fd_eps = 1e-5, bool early_exit = true) { chk(ilqr_hip_set_options(ctx_, jacobian_mode, fd_eps, early_exit ? 1 : 0)); }
   // off: solveAsync enqueues every iteration at once and never blocks the host (see ilqr_hip_solve_async in ilqr_hip.h)
   void setEarlyExitGate(bool on) { chk(ilqr_hip_set_early_exit_gate(ctx_, on ? 1 : 0)); }
+  // listed side-by-side order of the late iterations of a fixed-iteration solve (on by default; same results, see ilqr_hip_set_listed_spec)
+  void setListedSpec(bool on) { chk(ilqr_hip_set_listed_spec(ctx_, on ? 1 : 0)); }
+  int listedSpecIterations() { return ilqr_hip_get_listed_spec_iterations(ctx_); }
+  // one ILQR_ORDER_* code per enqueued iteration of the last solve
+  std::vector<int> iterationOrders(int max_iterations) {
+    std::vector<int> o((size_t)(max_iterations > 0 ? max_iterations : 1));
+    const int n = ilqr_hip_get_iteration_orders(ctx_, o.data());
+    o.resize((size_t)(n > 0 ? n : 0));
+    return o;
+  }
+  // the lists (chg, kr) iteration `iter` of the last solve started from
+  std::pair<std::vector<int>, std::vector<int>> iterationLists(int iter) {
+    std::vector<int> chg((size_t)B_), kr((size_t)B_); int cnt[2] = {0, 0};
+    chk(ilqr_hip_get_iteration_lists(ctx_, iter, chg.data(), kr.data(), cnt));
+    chg.resize((size_t)cnt[0]); kr.resize((size_t)cnt[1]);
+    return {chg, kr};
+  }
   void enableProfiling(bool on) { chk(ilqr_hip_enable_profiling(ctx_, on ? 1 : 0)); }
   // device time per stage of the last solve, keyed like the reference's profiler (ilqr.cpp:537-639)
   std::map<std::string, double> stageMs() {

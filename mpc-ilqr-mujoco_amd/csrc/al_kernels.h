@@ -122,6 +122,7 @@ __global__ void __launch_bounds__(64) k_solve_begin_al(DevState S, const int* do
   if (lane == 0) {
     if (S.order) { S.order_n[0] = n; for (int i = 1; i < 2 * (S.max_iter + 1); ++i) S.order_n[i] = 0; }
     if (S.grp_a) for (int i = 0; i < S.max_iter + 2; ++i) { S.order_rn[i] = 0; S.order_an[i] = 0; }
+    if (S.kr) for (int i = 0; i <= S.max_iter; ++i) S.kr_n[i] = 0;
     if (S.chg) for (int i = 0; i < S.max_iter + 2; ++i) { if (i <= S.max_iter) S.chg_n[i] = 0; S.chg_rn[i] = 0; S.chg_an[i] = 0; }
   }
 }

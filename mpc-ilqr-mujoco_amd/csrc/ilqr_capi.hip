@@ -35,8 +35,17 @@ struct Knobs {
   int repass;           // ILQR_REPASS=1: the full first pass in every iteration (as ilqr_hip_set_repeat_first_pass; either one is enough)
   int ls_list_max;      // ILQR_LS_LIST_MAX: a first-pass list of at most this many rollouts takes the one-rollout-per-wave line search (1024: one wave per SIMD)
   int slices, stagger, overlap_rollout, reuse_rollout, ee_gate /* -1: the handle's own setting */, split /* -1: on with the convergence exit */, spec, spec_dual, spec_max;
+  int spec_lists;       // ILQR_SPEC_LISTS=0: never the listed side-by-side order (as ilqr_hip_set_listed_spec(ctx, 0); either one is enough)
+  int spec_list_max;    // ILQR_SPEC_LIST_MAX: the order is taken while 2 chg_n + kr_n is at most this many one-wave-per-SIMD slots
+  int spec_list_from;   // ILQR_SPEC_LIST_FROM: first iteration that enqueues the pair of orders (0: iteration 3 max_iter / 5, a fixed rule -- the empty launches of the order not taken cost time where the lists are long)
   bool per_call;
 };
+#ifndef SPEC_LIST_MAX_DEFAULT
+#define SPEC_LIST_MAX_DEFAULT 1024
+#endif
+#ifndef SPEC_LIST_FROM_DEFAULT
+#define SPEC_LIST_FROM_DEFAULT 0
+#endif
 static Knobs read_knobs() {
   Knobs k;
   auto geti = [](const char* n, int d) { const char* e = getenv(n); return e ? atoi(e) : d; };
@@ -57,6 +66,9 @@ static Knobs read_knobs() {
   k.spec = geti("ILQR_SPEC", 1);
   k.spec_dual = geti("ILQR_SPEC_DUAL", 1);
   k.spec_max = geti("ILQR_SPEC_MAX", 512);
+  k.spec_lists = geti("ILQR_SPEC_LISTS", 1);
+  k.spec_list_max = geti("ILQR_SPEC_LIST_MAX", SPEC_LIST_MAX_DEFAULT);
+  k.spec_list_from = geti("ILQR_SPEC_LIST_FROM", SPEC_LIST_FROM_DEFAULT);
   k.per_call = geti("ILQR_ENV_PER_CALL", 0) != 0;
   return k;
 }
@@ -167,6 +179,11 @@ struct ilqr_hip_ctx {
   hipEvent_t ev_spec_fork = nullptr, ev_spec_join = nullptr;
   int spec_iterations = 0;    // iterations of the last solve that enqueued both passes side by side
   int* d_spec_gate = nullptr; // [4] device-side choice of the order (launch_spec_gate)
+  // listed side-by-side order (ilqr_kernels.hip k_control_listed): listed_spec = ilqr_hip_set_listed_spec; d_lgate [max_iter][8] the gate words of
+  // every iteration (launch_listed_prologue; word 4 = taken), read back by the getters; listed_dual[it] = iteration it of the last solve enqueued the pair
+  int listed_spec = 1;
+  int* d_lgate = nullptr;
+  std::vector<char> listed_dual;
   // early continuation (enqueue_solve): streams / events of the group that starts the next iteration behind the first control pass
   hipStream_t a1 = nullptr;     // (its cost quadratics and re-rollout share streams 2 and 3 with the other group, see enqueue_solve)
   hipEvent_t evA_fork = nullptr, evA_join = nullptr, evA_roll = nullptr, evA_lin = nullptr, evA_adopt = nullptr;
@@ -420,6 +437,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   A(dalloc(c, &S.grp_a, B)); A(dalloc(c, &S.grp_r, B)); A(dalloc(c, &S.order_r, B)); A(dalloc(c, &S.order_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.order_an, (size_t)c->max_iter + 2));
   A(dalloc(c, &S.chg, B * (c->max_iter + 1))); A(dalloc(c, &S.chg_n, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_r, B)); A(dalloc(c, &S.chg_rn, (size_t)c->max_iter + 2)); A(dalloc(c, &S.chg_an, (size_t)c->max_iter + 2));
   A(dalloc(c, &S.chg_f, B)); A(dalloc(c, &c->d_fp_gate, 4));
+  A(dalloc(c, &S.kr, B * (c->max_iter + 1))); A(dalloc(c, &S.kr_n, (size_t)c->max_iter + 1)); A(dalloc(c, &S.ls_list, B)); A(dalloc(c, &S.ls_kind, B)); A(dalloc(c, &c->d_lgate, 8 * (size_t)c->max_iter));
   if (rc == ILQR_OK && (hipStreamCreate(&c->a1) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_roll, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_lin, hipEventDisableTiming) != hipSuccess ||
@@ -472,7 +490,7 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   if (c->h_al_left) (void)hipHostFree(c->h_al_left);
   if (c->ev_al) hipEventDestroy(c->ev_al);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
-  { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate}; for (void* p : gp) if (p) hipFree(p); }
+  { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate, S.kr, S.kr_n, S.ls_list, S.ls_kind, c->d_lgate}; for (void* p : gp) if (p) hipFree(p); }
   { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
   for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints, &c->terrain}) if (t->d) hipFree(t->d);
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
@@ -865,6 +883,9 @@ int ilqr_hip_set_max_iterations(ilqr_hip_ctx* c, int max_iter) {
     { void* cp[] = {c->S.chg, c->S.chg_n, c->S.chg_rn, c->S.chg_an}; for (void* p : cp) if (p) hipFree(p); }
     c->S.chg = c->S.chg_n = c->S.chg_rn = c->S.chg_an = nullptr; c->lin_iterations = 0;
     TRY(dalloc(c, &c->S.chg, (size_t)c->B * (max_iter + 1))); TRY(dalloc(c, &c->S.chg_n, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.chg_rn, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.chg_an, (size_t)max_iter + 2));
+    { void* kp[] = {c->S.kr, c->S.kr_n, c->d_lgate}; for (void* p : kp) if (p) hipFree(p); }
+    c->S.kr = c->S.kr_n = c->d_lgate = nullptr; c->listed_dual.clear();
+    TRY(dalloc(c, &c->S.kr, (size_t)c->B * (max_iter + 1))); TRY(dalloc(c, &c->S.kr_n, (size_t)max_iter + 1)); TRY(dalloc(c, &c->d_lgate, 8 * (size_t)max_iter));
   }
   return ILQR_OK;
 }
@@ -1004,6 +1025,7 @@ static DevState slice_state(const DevState& S, size_t b0, int Bs) {
   T.order = nullptr; T.order_n = nullptr;      // the compacted lists index the whole batch: not used by slices
   T.grp_a = T.grp_r = T.order_r = T.order_rn = T.order_an = nullptr;
   T.chg = T.chg_n = T.chg_r = T.chg_rn = T.chg_an = nullptr; T.chg_f = nullptr;
+  T.kr = T.kr_n = T.ls_list = T.ls_kind = nullptr;
   return T;
 }
 static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
@@ -1047,6 +1069,15 @@ static int ensure_gate(ilqr_hip_ctx* c) {
 // (headline -3 %, contact +3 % / -3.5 % at B = 4096 / 1024).  ILQR_SPLIT=0 / 1 forces it off / on.
 static int split_enabled(const ilqr_hip_ctx* c) { return c->knobs.split >= 0 ? c->knobs.split : c->early_exit; }
 static int alloc_twin(ilqr_hip_ctx* c);
+// Listed side-by-side order (enqueue_solve): what a handle's settings must allow before a fixed-iteration solve enqueues it -- the lists it rests on
+// (linearisation cache, first-pass skip, saturated-retry skip: not with ILQR_RELIN=1, ILQR_REPASS=1, ILQR_DEDUP_RETRY=0 or their setters), analytic
+// Jacobians, the whole batch on one stream set, no early-continuation split, no convergence exit (that path has the orders above)
+static bool listed_spec_wanted(const ilqr_hip_ctx* c, const ilqr::LaunchPlan& L, int slices) {
+  const int dedup = c->knobs.dedup_retry >= 0 ? c->knobs.dedup_retry : c->dedup_retry, relin = c->knobs.relin >= 0 ? c->knobs.relin : c->relin;
+  return c->knobs.spec && c->knobs.spec_lists && c->listed_spec && c->knobs.spec_list_max > 0 && !c->early_exit && slices <= 1 && c->max_iter > 1 &&
+         c->jac_mode == ILQR_JAC_ANALYTIC && L.lin_lists && L.spec_dual && dedup && !relin && !(c->knobs.repass || c->repass) && !split_enabled(c) &&
+         c->B > c->knobs.spec_max && c->S.kr && c->S.kr_n && c->S.ls_list && c->S.ls_kind && c->d_lgate;
+}
 // (the side-by-side order is an optimisation: a handle that cannot get the memory keeps the sequential order instead of failing the solve)
 // Memory: the twin is indexed by rollout like everything else, so it is a full-batch copy of K, k, Vx, Vxx, the eight candidates and
 // their knot costs -- 0.33 MB per rollout at N = 25 (1.3 GB at B = 4096, 10.7 GB at B = 32 768), allocated by the first solve that can
@@ -1206,6 +1237,14 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   const bool retry_gated = S.order && L.line_search == ilqr::DYN_TWO_LANE && !can_split;
   bool prev_split = false;      // group A of the iteration at hand is already enqueued
   bool prev_seq = false;        // the previous iteration ran in the sequential order (k_control has written chg_f for this one)
+  // Listed side-by-side order: from iteration listed_from on, the pair (listed side by side, sequential from the lists) is enqueued and
+  // the device takes one by the lists' lengths (launch_listed_prologue).  k_control and k_control_listed both leave order, chg, chg_f and kr
+  // behind, so either order may follow either.
+  const bool listed = listed_spec_wanted(c, L, c->n_slices) && c->twin && skip_first && cache && dedup_bit && !gate;
+  c->listed_dual.assign((size_t)c->max_iter, 0);
+  // (the pair costs ~60 us of empty launches per iteration where the lists stay long -- the early iterations of any solve, every iteration of
+  // a batch that keeps accepting: measured, DESIGN 9 -- so it starts with the last two fifths of the iterations unless ILQR_SPEC_LIST_FROM says otherwise)
+  const int listed_from = c->knobs.spec_list_from >= 1 ? c->knobs.spec_list_from : (3 * c->max_iter / 5 > 1 ? 3 * c->max_iter / 5 : 1);
   for (int iter = 0; iter < c->max_iter; ++iter) {
     if (gate && iter >= 2) {
       HIPCHK(c, hipEventSynchronize(c->ev_active[iter - 2]));
@@ -1297,7 +1336,31 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     }
     const bool first_listed = skip_first && iter > 0 && prev_seq;
     c->fp_listed[iter] = first_listed;
-    const ilqr::WorkList wf{S.chg + (size_t)iter * S.B, S.chg_n + iter};
+    ilqr::WorkList wf{S.chg + (size_t)iter * S.B, S.chg_n + iter};
+    const bool pair = listed && first_listed && iter >= listed_from;
+    const int* gseq = nullptr;      // gate of the sequential order's bookkeeping where the pair is enqueued
+    if (pair) {
+      int* g = c->d_lgate + 8 * (size_t)iter;
+      const DevState Tw = twin_view(c, S);
+      const int slots = c->knobs.spec_list_max < S.B ? c->knobs.spec_list_max : S.B;      // (either list holds at most this many rollouts where the order is taken)
+      DevState Su = S; Su.active = S.ls_kind;       // the candidates' knot costs select by mask: chg and kr as flags on S, chg on the twin
+      DevState Tf = Tw; Tf.active = S.chg_f;
+      c->listed_dual[iter] = 1;
+      ilqr::launch_listed_prologue(S, Tw.lambda, iter, c->knobs.spec_list_max, g, st);
+      HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
+      HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
+      { StageTimer T(c, 3, st); ilqr::launch_backward_list(L, S, st, fold_h, S.ls_list, g + 3); }
+      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(L, Tw, st2, fold_h, wf.list, g); }
+      TRY(wait_adoption(st)); TRY(wait_adoption(st2));
+      { StageTimer T(c, 4, st); ilqr::launch_line_search_s(S, P, ilqr::MASK_ACTIVE, st, S.ls_list, g + 3, slots, 1); ilqr::launch_cand_costs(Su, P, ilqr::MASK_ACTIVE, st, false, g + 4); }
+      { StageTimer T(c, 7, st2); ilqr::launch_line_search_s(Tw, P, ilqr::MASK_ACTIVE, st2, wf.list, g, slots, 1); ilqr::launch_cand_costs(Tf, P, ilqr::MASK_ACTIVE, st2, false, g + 4); }
+      HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
+      HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
+      { StageTimer T(c, 5, st); ilqr::launch_control_listed(S, Tw, iter, st, L.ls_costs_per_knot, g); }
+      // the sequential order behind it sees an empty first-pass list and closed gates where the device took the order above (its retry
+      // list stays empty: nobody ran phase 0)
+      wf.count = g + 2; gseq = g + 1;
+    }
     { StageTimer T(c, 3, st);                                                                                              // :601
       if (first_listed) ilqr::launch_backward_list(L, S, st, fold_h, wf.list, wf.count);
       else ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
@@ -1307,9 +1370,9 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       if (first_listed) {
         DevState Sf = S; Sf.active = S.chg_f;      // (the candidates' knot costs select by mask: the list as flags; every other rollout's cand_knot stays)
         ilqr::launch_line_search_gated(S, P, st, wf.list, wf.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate);
-        ilqr::launch_cand_costs(Sf, P, ilqr::MASK_ACTIVE, st, false);
+        ilqr::launch_cand_costs(Sf, P, ilqr::MASK_ACTIVE, st, false, gseq);
       } else ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot); }          // :619-620,645-655
+    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot, gseq); }          // :619-620,645-655
     const bool split_next = can_split && iter + 1 < c->max_iter && rolls_aside(iter + 1);
     if (split_next) {
       // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
@@ -1324,9 +1387,9 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
       if (retry_gated) {
         const ilqr::WorkList wr = ilqr::work_list(S, ilqr::MASK_RETRY, iter);
         ilqr::launch_line_search_gated(S, P, st, wr.list, wr.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate + 2);
-        ilqr::launch_cand_costs(S, P, ilqr::MASK_RETRY, st, false);
+        ilqr::launch_cand_costs(S, P, ilqr::MASK_RETRY, st, false, gseq);
       } else ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }                      // :640-646
+    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot, gseq); }                      // :640-646
     if (gate) {
       HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
@@ -1366,18 +1429,71 @@ long long ilqr_hip_get_first_pass_rollouts(ilqr_hip_ctx* c) {
   for (int it = 0; it < n; ++it) total += ((size_t)it < c->fp_listed.size() && c->fp_listed[it]) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
   return total;
 }
+// took[it] = 1 where iteration it of the last solve enqueued the listed pair and the device took the side-by-side order (word 4 of its gate)
+static int read_listed_taken(ilqr_hip_ctx* c, std::vector<int>& took) {
+  took.assign((size_t)c->max_iter, 0);
+  if (!c->d_lgate || c->listed_dual.empty()) return ILQR_OK;
+  std::vector<int> g(8 * (size_t)c->max_iter);
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(g.data(), c->d_lgate, g.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ILQR_ERR_HIP;
+  for (int it = 0; it < c->max_iter && (size_t)it < c->listed_dual.size(); ++it) took[it] = (c->listed_dual[it] && g[8 * (size_t)it + 4]) ? 1 : 0;
+  return ILQR_OK;
+}
+int ilqr_hip_set_listed_spec(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->listed_spec = on ? 1 : 0; return ILQR_OK; }
+int ilqr_hip_get_listed_spec_iterations(ilqr_hip_ctx* c) {
+  if (!c) return -1;
+  enter(c);
+  std::vector<int> took;
+  if (read_listed_taken(c, took) != ILQR_OK) { c->err = "ilqr_hip_get_listed_spec_iterations: reading the gate words failed"; return -1; }
+  int total = 0;
+  for (int it = 0; it < c->lin_iterations && it < c->max_iter; ++it) total += took[it];
+  return total;
+}
+int ilqr_hip_get_iteration_lists(ilqr_hip_ctx* c, int iter, int* chg, int* kr, int* counts) {
+  if (!c || !counts || iter < 0 || iter >= c->max_iter) return ILQR_ERR_ARG;
+  enter(c);
+  if (c->lin_iterations <= 0 || !c->S.chg || !c->S.kr || !c->lin_cached) { c->err = "ilqr_hip_get_iteration_lists: the last solve kept no lists"; return ILQR_ERR_STATE; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(&counts[0], c->S.chg_n + iter, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&counts[1], c->S.kr_n + iter, sizeof(int), hipMemcpyDeviceToHost));
+  if (iter == 0) counts[0] = counts[1] = 0;      // (iteration 0 runs every rollout and reads neither list)
+  if (chg && counts[0] > 0) HIPCHK(c, hipMemcpy(chg, c->S.chg + (size_t)iter * c->B, sizeof(int) * (size_t)counts[0], hipMemcpyDeviceToHost));
+  if (kr && counts[1] > 0) HIPCHK(c, hipMemcpy(kr, c->S.kr + (size_t)iter * c->B, sizeof(int) * (size_t)counts[1], hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+int ilqr_hip_get_iteration_orders(ilqr_hip_ctx* c, int* out) {
+  if (!c || !out) return -1;
+  enter(c);
+  const int n = c->lin_iterations;
+  if (n <= 0) return 0;
+  std::vector<int> took, act(2 * (size_t)(c->max_iter + 1));
+  if (read_listed_taken(c, took) != ILQR_OK || (c->S.order_n && hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
+    c->err = "ilqr_hip_get_iteration_orders: reading the gate words failed"; return -1;
+  }
+  for (int it = 0; it < n; ++it) {
+    const int kind = (size_t)it < c->retry_order.size() ? c->retry_order[it] : ilqr_hip_ctx::RETRY_LIST;
+    if (took[it]) out[it] = ILQR_ORDER_LISTED_SPEC;
+    else if (kind == ilqr_hip_ctx::RETRY_TWIN) out[it] = ILQR_ORDER_TWIN;
+    else if (kind == ilqr_hip_ctx::RETRY_DUAL) out[it] = act[2 * it] <= c->knobs.spec_max ? ILQR_ORDER_DUAL_TWIN : ILQR_ORDER_DUAL_SEQUENTIAL;
+    else out[it] = ILQR_ORDER_SEQUENTIAL;
+  }
+  return n;
+}
 long long ilqr_hip_get_retry_pass_rollouts(ilqr_hip_ctx* c) {
   if (!c) return -1;
   enter(c);
   const int n = c->lin_iterations;
   if (n <= 0) return 0;
   if (c->n_slices > 1 || !c->S.order) return (long long)c->B * n;      // (batch slices keep no lists: the retry launches cover the slice)
-  std::vector<int> act(2 * (size_t)(c->max_iter + 1));
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+  std::vector<int> act(2 * (size_t)(c->max_iter + 1)), took, chg((size_t)c->max_iter + 1), kr((size_t)c->max_iter + 1);
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      read_listed_taken(c, took) != ILQR_OK || hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      (c->S.kr_n && hipMemcpy(kr.data(), c->S.kr_n, kr.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
     c->err = "ilqr_hip_get_retry_pass_rollouts: reading the list counts failed"; return -1;
   }
   long long total = 0;
   for (int it = 0; it < n; ++it) {
+    // listed side by side: the twin ran for the changed rollouts, the known retries on the solve's own buffers
+    if (took[it]) { total += chg[it] + kr[it]; continue; }
     const int kind = (size_t)it < c->retry_order.size() ? c->retry_order[it] : ilqr_hip_ctx::RETRY_LIST;
     // side by side the twin pass runs for every active rollout; where both orders were enqueued the device took the twin for a list of at most spec_max
     const bool twin = kind == ilqr_hip_ctx::RETRY_TWIN || (kind == ilqr_hip_ctx::RETRY_DUAL && act[2 * it] <= c->knobs.spec_max);
@@ -1481,7 +1597,7 @@ int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   const int k = slices_wanted(c, c->B);
   c->n_slices = k;
   c->spec_iterations = 0; c->split_iterations = 0;
-  if (c->knobs.spec && k <= 1 && !c->twin && (c->B <= c->knobs.spec_max || (c->early_exit && early_exit_gate(c)))) TRY(ensure_twin(c));
+  if (c->knobs.spec && k <= 1 && !c->twin && (c->B <= c->knobs.spec_max || (c->early_exit && early_exit_gate(c)) || listed_spec_wanted(c, L, k))) TRY(ensure_twin(c));
   if (L.pack && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
   c->first_aside = c->xbar_rolled && c->rolled_variant == L.rollout && same_dyn(c->rolled_dyn, P.dyn);
   c->xbar_rolled = false;                                   // after this solve xbar is an accepted line-search candidate

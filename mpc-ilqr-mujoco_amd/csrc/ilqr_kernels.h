@@ -82,6 +82,15 @@ struct DevState {
   // First-pass skip (ilqr_capi.hip enqueue_solve): chg_f[b] = 1 while rollout b is on list it of the iteration to come (k_control writes it
   // beside the list), for the kernels that select by mask (the candidates' knot costs).  Null: not in use.
   int* chg_f;          // [B]
+  // Listed side-by-side order (ilqr_capi.hip enqueue_solve): kr list it = the rollouts active in iteration it whose two line searches of
+  // iteration it - 1 both failed and whose lambda is below its cap (min(10 lambda, 1e-3) != lambda): their first pass of it is skipped and
+  // fails by construction, their retry is known before the iteration starts.  Written by the control kernel that closes iteration it - 1,
+  // compacted like chg; disjoint from chg by construction (chg: accepted, kr: failed).  ls_list: chg ++ kr of the iteration at hand, ls_kind[b]:
+  // 0 = neither (stuck at the cap: no pass), 1 = on chg, 2 = on kr -- both written by k_listed_prologue.  Null: not in use.
+  int* kr;             // [max_iter + 1][B]
+  int* kr_n;           // [max_iter + 1]
+  int* ls_list;        // [B]
+  int* ls_kind;        // [B]
 };
 
 // compacted list of the rollouts of a pass inside a solve (DevState::order), or nulls: MASK_ACTIVE at iteration iter -> list (iter, 0), MASK_RETRY -> (iter, 1)
@@ -128,6 +137,13 @@ void launch_control_spec(const DevState& S, const DevState& T, int iter, double 
 // the speculative launches), g[1] = 0 / 1 (gate of the sequential bookkeeping), g[2] = 0 / n (count of the sequential first line search), with
 // n = the length of list (iter, 0).  The list-driven launchers take an explicit list / count.
 void launch_spec_gate(const DevState& S, int iter, int max, int* g, hipStream_t st);
+// Listed side-by-side order.  launch_listed_prologue decides on the device: taken while 2 chg_n[iter] + kr_n[iter] <= max (max <= 0: never) --
+// g[0] = chg_n / 0 (the twin's launches), g[1] = 0 / 1 (gate of the sequential order's bookkeeping and candidate costs), g[2] = 0 / chg_n (count
+// of the sequential first pass), g[3] = chg_n + kr_n / 0 (the launches on S), g[4] = 1 / 0 (gate of the order's own kernels; read back by the
+// getters): taken / not taken -- and, where taken, writes lambda of the known retries and of the twin, S.ls_list and S.ls_kind.
+// launch_control_listed (gate g + 4): ilqr.cpp:619-655 for every active rollout by its kind.
+void launch_listed_prologue(const DevState& S, double* lambda2, int iter, int max, int* g, hipStream_t st);
+void launch_control_listed(const DevState& S, const DevState& T, int iter, hipStream_t st, int sum_knots, const int* g);
 void launch_solve_begin(const DevState& S, hipStream_t st);
 // ---- al_kernels.h (the tail of ilqr_kernels.hip): the augmented-Lagrangian outer loop (ilqr_hip_set_augmented_lagrangian).  All pointers are device pointers of the whole batch.
 struct AlDev {

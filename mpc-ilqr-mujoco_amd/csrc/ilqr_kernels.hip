@@ -731,12 +731,12 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
   const int early_exit = ee_flags & 1, dedup = (ee_flags >> 1) & 1;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * CTRL_WAVES + wv;
-  __shared__ int s_accept[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[3], s_chg[CTRL_WAVES], s_cbase[2];
+  __shared__ int s_accept[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[3], s_chg[CTRL_WAVES], s_cbase[2], s_kr[CTRL_WAVES], s_kbase[1];
   const int N = S.N;
   bool run = b < S.B;
   if (run && phase == 0 && !S.active[b]) run = false;
   if (run && phase == 1 && !(S.active[b] && S.need_retry[b])) run = false;
-  if (lane == 0) { s_accept[wv] = -1; s_slot[wv] = -1; s_chg[wv] = 0; }
+  if (lane == 0) { s_accept[wv] = -1; s_slot[wv] = -1; s_chg[wv] = 0; s_kr[wv] = 0; }
   // sum_knots: the candidates' costs arrive as per-knot costs (k_traj_knot_cost); lane a adds candidate a's in knot order -- the
   // order of a sequential accumulation along the rollout, as k_traj_cost_sum does (one launch and one launch gap less per pass)
   double csum = 0.0;
@@ -789,6 +789,8 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
         S.trace_alpha[(size_t)b * S.max_iter + tr] = 0.0;
         S.trace_lambda[(size_t)b * S.max_iter + tr] = lam_used;
         if (early_exit && iter > 1) S.active[b] = 0;
+        // known retries (DevState::kr): the iteration is over and both searches have failed -- below the cap the retry of iteration iter + 1 is known now
+        if (S.kr && S.active[b] && fmin(lam_used * 10.0, 1e-3) != lam_used) s_kr[wv] = 1;
       }
       // compacted work lists (DevState::order): this rollout goes into the retry pass of this iteration (kind 1) or, its
       // iteration being over, among the rollouts still active in the next one (kind 0)
@@ -825,7 +827,17 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control(DevState S, int pha
       s_cbase[0] = cnt ? atomicAdd(&S.chg_n[iter + 1], cnt) : 0;
       s_cbase[1] = (cnt && phase == 1) ? atomicAdd(&S.chg_rn[iter + 1], cnt) : 0;
     }
+    if (threadIdx.x == 128 && S.kr) {     // (the third wave)
+      int cnt = 0;
+      for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_kr[w];
+      s_kbase[0] = cnt ? atomicAdd(&S.kr_n[iter + 1], cnt) : 0;
+    }
     __syncthreads();
+    if (lane == 0 && s_kr[wv]) {
+      int pos = s_kbase[0];
+      for (int w = 0; w < wv; ++w) pos += s_kr[w];
+      S.kr[(size_t)(iter + 1) * S.B + pos] = b;
+    }
     if (lane == 0 && s_chg[wv]) {
       int pos = s_cbase[0], posr = s_cbase[1];
       for (int w = 0; w < wv; ++w) { pos += s_chg[w]; posr += s_chg[w]; }
@@ -979,6 +991,161 @@ __global__ void __launch_bounds__(64 * CTRL_WAVES) k_control_spec(DevState S, De
   }
 }
 
+// ---- listed side-by-side order (late iterations of a fixed-iteration solve: the lists are short, the chip nearly empty) -----------------
+// An iteration >= 1 whose predecessor has left chg, chg_f and kr.  Three kinds of active rollout:
+//   1, on chg (accepted a candidate in iteration iter - 1): both passes side by side as above -- the first on S, the retry on the twin T;
+//   2, on kr (both searches of iter - 1 failed, lambda below its cap): the first pass is skipped and fails by construction (k_control phase 0
+//      would read the costs its last pass left and decide acc = -1 from them), so the retry at min(10 lambda, 1e-3) is the only pass: it reads
+//      the cached Jacobians and quadratics, the unchanged nominal trajectory and Jbase, and runs on S itself beside the others' first pass;
+//   0, stuck at the cap: the skipped first pass fails and its saturated retry would repeat it -- the failing branch, no pass (as k_control).
+// k_listed_prologue takes the decision between the two enqueued orders (below), raises lambda for kind 2 (S) and kind 1 (T), concatenates the two lists for the launches on S and writes the kinds, which
+// also serve as the selection flags of the candidates' knot costs on S (chg_f selects on T); k_control_listed then plays ilqr.cpp:619-655.
+// (the gate is the prologue's first thread: every thread takes the decision from the two counts itself, one launch less per iteration)
+__global__ void k_listed_prologue(DevState S, double* lambda2, const int* chg, const int* kr, const int* chg_n, const int* kr_n, int max, int* g) {
+  const int nc = *chg_n, nu = nc + *kr_n;
+  const bool take = max > 0 && nc + nu <= max;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b == 0) { g[0] = take ? nc : 0; g[1] = take ? 0 : 1; g[2] = take ? 0 : nc; g[3] = take ? nu : 0; g[4] = take ? 1 : 0; }
+  if (!take || b >= S.B) return;
+  if (b < nc) S.ls_list[b] = chg[b];
+  else if (b < nu) S.ls_list[b] = kr[b - nc];
+  int kind = 0;
+  if (S.active[b]) {
+    const double lam = S.lambda[b], raised = fmin(lam * 10.0, 1e-3);
+    if (S.chg_f[b]) { kind = 1; lambda2[b] = raised; }
+    else if (raised != lam) { kind = 2; S.lambda[b] = raised; }      // (ilqr.cpp:634 of the known retry)
+  }
+  S.ls_kind[b] = kind;
+}
+__global__ void __launch_bounds__(64 * CTRL_WAVES) k_control_listed(DevState S, DevState T, int iter, int sum_knots, const int* gate) {
+  if (*gate == 0) return;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x * CTRL_WAVES + wv;
+  __shared__ int s_accept[CTRL_WAVES], s_retry[CTRL_WAVES], s_slot[CTRL_WAVES], s_base[1], s_chg[CTRL_WAVES], s_cbase[1], s_kr[CTRL_WAVES], s_kbase[1];
+  const int N = S.N;
+  const bool run = b < S.B && S.active[b];
+  const int kind = run ? S.ls_kind[b] : 0;
+  if (lane == 0) { s_accept[wv] = -1; s_retry[wv] = 0; s_slot[wv] = -1; s_chg[wv] = 0; s_kr[wv] = 0; }
+  // lanes 0..7: candidates of the pass on S, lanes 8..15 (kind 1): of the twin
+  double csum = 0.0;
+  if (kind != 0 && (lane < 8 || (kind == 1 && lane < 16))) {
+    const DevState& D = lane < 8 ? S : T;
+    const int a = lane & 7;
+    if (sum_knots) {
+      const double* ck = D.cand_knot + ((size_t)b * 8 + a) * (N + 1);
+      for (int t = 0; t <= N; ++t) csum += ck[t];
+    } else csum = D.cand_cost[(size_t)b * 8 + a];
+  }
+  double cc[16];
+#pragma unroll
+  for (int a = 0; a < 16; ++a) {
+    const int lo = __shfl(__double2loint(csum), a), hi = __shfl(__double2hiint(csum), a);
+    cc[a] = __hiloint2double(hi, lo);
+  }
+  if (run && lane == 0) {
+    S.iters[b] += 1;
+    const double base = S.Jbase[b];
+    int acc1 = -1, acc2 = -1;
+    if (kind != 0) {
+#pragma unroll
+      for (int a = 7; a >= 0; --a) { if (cc[a] < base - 1e-6) acc1 = a; if (kind == 1 && cc[8 + a] < base - 1e-6) acc2 = a; }
+    }
+    const double lam0 = S.lambda[b];      // (kind 2: already raised by the prologue)
+    // kind 1 at the cap: the twin repeats the failed first pass -- the failing branch is taken from S, the twin is not read (as k_control's dedup)
+    const bool retry = kind == 1 && acc1 < 0 && fmin(lam0 * 10.0, 1e-3) != lam0;
+    const double lam_used = retry ? fmin(lam0 * 10.0, 1e-3) : lam0;
+    const int acc = retry ? acc2 : acc1;
+    s_accept[wv] = acc; s_retry[wv] = retry ? 1 : 0;
+    S.improved[b] = acc >= 0;
+    S.alpha_idx[b] = acc;
+    S.need_retry[b] = 0;
+    if (kind != 0) {
+#pragma unroll
+      for (int a = 0; a < 8; ++a) S.cand_cost[(size_t)b * 8 + a] = retry ? cc[8 + a] : cc[a];
+    }
+    const int tr = iter;
+    if (acc >= 0) {
+      const double Jn = retry ? cc[8 + acc] : cc[acc];
+      S.J[b] = Jn;
+      S.Jbase[b] = Jn;
+      S.lambda[b] = fmax(lam_used / 2.0, 1e-6);
+      S.trace_cost[(size_t)b * (S.max_iter + 1) + tr + 1] = Jn;
+      S.trace_alpha[(size_t)b * S.max_iter + tr] = ALPHAS[acc];
+      S.trace_lambda[(size_t)b * S.max_iter + tr] = lam_used;
+      s_chg[wv] = 1;
+    } else {
+      S.lambda[b] = lam_used;
+      S.trace_cost[(size_t)b * (S.max_iter + 1) + tr + 1] = S.J[b];
+      S.trace_alpha[(size_t)b * S.max_iter + tr] = 0.0;
+      S.trace_lambda[(size_t)b * S.max_iter + tr] = lam_used;
+      if (fmin(lam_used * 10.0, 1e-3) != lam_used) s_kr[wv] = 1;
+    }
+    s_slot[wv] = 0;      // (no convergence exit in this order: every rollout stays active)
+    S.chg_f[b] = acc >= 0 ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int cnt = 0;
+    for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_slot[w] == 0;
+    s_base[0] = cnt ? atomicAdd(&S.order_n[2 * (iter + 1)], cnt) : 0;
+  }
+  if (threadIdx.x == 64) {
+    int cnt = 0;
+    for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_chg[w];
+    s_cbase[0] = cnt ? atomicAdd(&S.chg_n[iter + 1], cnt) : 0;
+  }
+  if (threadIdx.x == 128) {
+    int cnt = 0;
+    for (int w = 0; w < CTRL_WAVES; ++w) cnt += s_kr[w];
+    s_kbase[0] = cnt ? atomicAdd(&S.kr_n[iter + 1], cnt) : 0;
+  }
+  __syncthreads();
+  if (lane == 0 && s_chg[wv]) {
+    int pos = s_cbase[0];
+    for (int w = 0; w < wv; ++w) pos += s_chg[w];
+    S.chg[(size_t)(iter + 1) * S.B + pos] = b;
+  }
+  if (lane == 0 && s_kr[wv]) {
+    int pos = s_kbase[0];
+    for (int w = 0; w < wv; ++w) pos += s_kr[w];
+    S.kr[(size_t)(iter + 1) * S.B + pos] = b;
+  }
+  if (lane == 0 && s_slot[wv] == 0) {
+    int pos = s_base[0];
+    for (int w = 0; w < wv; ++w) pos += s_slot[w] == 0;
+    S.order[(size_t)(2 * (iter + 1)) * S.B + pos] = b;
+  }
+  // the copies, by the whole workgroup as in k_control_spec.  A kind-1 rollout whose first search failed keeps the twin's pass as its last
+  // executed one: gains, value function and the candidates' knot costs (a later skipped first pass sums them again).  Its candidates
+  // themselves are not copied unless accepted: xcand / ucand are read by the control kernel behind the pass that wrote them and only on acceptance.
+  for (int w = 0; w < CTRL_WAVES; ++w) {
+    const int acc = s_accept[w];
+    const bool retry = s_retry[w] != 0;
+    if (acc < 0 && !retry) continue;
+    const size_t bb = (size_t)blockIdx.x * CTRL_WAVES + w;
+    auto block_copy = [&](double* dst, const double* src, int len) {
+      for (int base = 0; base < len; base += 64 * CTRL_WAVES * 4) {
+        double v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int e = base + 64 * CTRL_WAVES * j + (int)threadIdx.x; v[j] = src[e < len ? e : 0]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int e = base + 64 * CTRL_WAVES * j + (int)threadIdx.x; if (e < len) dst[e] = v[j]; }
+      }
+    };
+    if (retry) {
+      block_copy(S.K + bb * N * H1_NU * H1_NX, T.K + bb * N * H1_NU * H1_NX, N * H1_NU * H1_NX);
+      block_copy(S.kff + bb * N * H1_NU, T.kff + bb * N * H1_NU, N * H1_NU);
+      block_copy(S.Vx + bb * H1_NX, T.Vx + bb * H1_NX, H1_NX);
+      block_copy(S.Vxx + bb * H1_NX * H1_NX, T.Vxx + bb * H1_NX * H1_NX, H1_NX * H1_NX);
+      block_copy(S.cand_knot + bb * 8 * (N + 1), T.cand_knot + bb * 8 * (N + 1), 8 * (N + 1));
+    }
+    if (acc < 0) continue;
+    const DevState& D = retry ? T : S;
+    block_copy(S.xbar + bb * (N + 1) * H1_NX, D.xcand + (bb * 8 + acc) * (N + 1) * H1_NX, (N + 1) * H1_NX);
+    block_copy(S.ubar + bb * N * H1_NU, D.ucand + (bb * 8 + acc) * N * H1_NU, N * H1_NU);
+  }
+}
+
 // solve prologue: J = initial cost, trace[0], counters
 __global__ void k_solve_begin(DevState S) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -992,6 +1159,7 @@ __global__ void k_solve_begin(DevState S) {
     S.grp_a[b] = 0; S.grp_r[b] = 0;
     if (b == 0) for (int i = 0; i < S.max_iter + 2; ++i) { S.order_rn[i] = 0; S.order_an[i] = 0; }
   }
+  if (S.kr && b == 0) for (int i = 0; i <= S.max_iter; ++i) S.kr_n[i] = 0;
   if (S.chg && b == 0) for (int i = 0; i < S.max_iter + 2; ++i) { if (i <= S.max_iter) S.chg_n[i] = 0; S.chg_rn[i] = 0; S.chg_an[i] = 0; }      // (iteration 0 linearises every rollout: no list survives a solve)
   const double J0 = S.Jbase[b];
   S.J[b] = J0;
@@ -1289,6 +1457,13 @@ void launch_control_spec(const DevState& S, const DevState& T, int iter, double 
   hipLaunchKernelGGL(k_control_spec, dim3(cdiv(S.B, CTRL_WAVES)), dim3(64 * CTRL_WAVES), 0, st, S, T, iter, tol, early_exit, sum_knots, gate);
 }
 void launch_spec_gate(const DevState& S, int iter, int max, int* g, hipStream_t st) { hipLaunchKernelGGL(k_spec_gate, dim3(1), dim3(1), 0, st, (const int*)(S.order_n + 2 * iter), max, g); }
+void launch_listed_prologue(const DevState& S, double* lambda2, int iter, int max, int* g, hipStream_t st) {
+  hipLaunchKernelGGL(k_listed_prologue, dim3(cdiv(S.B, 256)), dim3(256), 0, st, S, lambda2, (const int*)(S.chg + (size_t)iter * S.B), (const int*)(S.kr + (size_t)iter * S.B),
+                     (const int*)(S.chg_n + iter), (const int*)(S.kr_n + iter), max, g);
+}
+void launch_control_listed(const DevState& S, const DevState& T, int iter, hipStream_t st, int sum_knots, const int* g) {
+  hipLaunchKernelGGL(k_control_listed, dim3(cdiv(S.B, CTRL_WAVES)), dim3(64 * CTRL_WAVES), 0, st, S, T, iter, sum_knots, g + 4);
+}
 void launch_solve_begin(const DevState& S, hipStream_t st) { hipLaunchKernelGGL(k_solve_begin, dim3(cdiv(S.B, 64)), dim3(64), 0, st, S); }
 void launch_adopt_rollout(const DevState& S, const double* shadow, int mode, unsigned long long* mismatches, hipStream_t st) { hipLaunchKernelGGL(k_adopt_rollout, dim3(S.B), dim3(64), 0, st, S, shadow, mode, mismatches); }
 void launch_warm_shift(const DevState& S, const double* px, const double* pu, hipStream_t st) { hipLaunchKernelGGL(k_warm_shift, dim3(S.B), dim3(64), 0, st, S, px, pu); }

@@ -49,6 +49,7 @@ EXPORTS = [
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
     "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts", "ilqr_hip_set_repeat_first_pass", "ilqr_hip_get_first_pass_rollouts",
     "ilqr_hip_get_retry_pass_rollouts",
+    "ilqr_hip_set_listed_spec", "ilqr_hip_get_listed_spec_iterations", "ilqr_hip_get_iteration_orders", "ilqr_hip_get_iteration_lists",
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
     "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
@@ -1067,6 +1068,35 @@ class BatchedILQR:
     def speculative_iterations(self):
         """Iterations of the last solve whose lambda retry ran beside the first pass (small passes; ILQR_SPEC=0 disables)."""
         return int(self.L.ilqr_hip_get_speculative_iterations(self.h))
+
+    ORDER_NAMES = ("sequential", "twin", "dual-sequential", "dual-twin", "listed-spec")
+
+    def set_listed_spec(self, on=True):
+        """Let late iterations of a fixed-iteration solve run their two lambda passes side by side from their lists (on by default;
+        ilqr_hip_set_listed_spec; ILQR_SPEC_LISTS=0 or ILQR_SPEC=0 switch it off as well)."""
+        self._chk(self.L.ilqr_hip_set_listed_spec(self.h, int(bool(on))))
+
+    def listed_spec_iterations(self):
+        """Iterations of the last solve in which the device took the listed side-by-side order (ilqr_hip_get_listed_spec_iterations)."""
+        n = int(self.L.ilqr_hip_get_listed_spec_iterations(self.h))
+        if n < 0:
+            raise ILQRError("ilqr_hip_get_listed_spec_iterations: %s" % self.L.ilqr_hip_last_error(self.h).decode())
+        return n
+
+    def iteration_orders(self):
+        """One code per enqueued iteration of the last solve (ilqr_hip_get_iteration_orders; index into ORDER_NAMES)."""
+        out = np.zeros(max(self.max_iter, 1), dtype=np.int32)
+        n = int(self.L.ilqr_hip_get_iteration_orders(self.h, out.ctypes.data_as(C.c_void_p)))
+        if n < 0:
+            raise ILQRError("ilqr_hip_get_iteration_orders: %s" % self.L.ilqr_hip_last_error(self.h).decode())
+        return [int(v) for v in out[:n]]
+
+    def iteration_lists(self, it):
+        """(chg, kr) of iteration `it` of the last solve as sorted int arrays (ilqr_hip_get_iteration_lists)."""
+        chg, kr = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self.L.ilqr_hip_get_iteration_lists(self.h, int(it), chg.ctypes.data_as(C.c_void_p), kr.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+        return np.sort(chg[:cnt[0]]), np.sort(kr[:cnt[1]])
 
     def split_iterations(self):
         """Iterations of the last solve whose concurrent region ran in two groups (early continuation; ILQR_SPLIT=0 disables)."""

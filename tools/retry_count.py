@@ -19,9 +19,17 @@ for step in range(2):      # (bench.py solves on one handle again and again: lam
     s.solve(x0)
     tc, ta, tl = s.trace()
     print("solve %d: %d rollouts enter at the lambda cap; retry passes executed %d, first passes %d of %d" % (step + 1, (lam == 1e-3).sum(), s.retry_pass_rollouts(), s.first_pass_rollouts(), B * ta.shape[1]))
+    # the launch order the device took per iteration, and the lists the iteration started from (listed side-by-side order: chg = accepted in
+    # the previous iteration -- first pass on the solve's buffers, retry speculated into the twin --, kr = known retries)
+    orders = s.iteration_orders()
+    print("         listed side by side in %d iterations: %s" % (s.listed_spec_iterations(), " ".join(sv.BatchedILQR.ORDER_NAMES[o] for o in orders)))
     for i in range(ta.shape[1]):
         used = tl[:, i]
         retried = (ta[:, i] == 0.0) | (used != lam)
         saturated = (ta[:, i] == 0.0) & (lam == 1e-3)
-        print("iteration %d: first search failed for %4d rollouts (both passes failed: %4d), %4d of them at the lambda cap: retry list %4d" % (i, retried.sum(), (ta[:, i] == 0.0).sum(), saturated.sum(), (retried & ~saturated).sum()))
+        chg, kr = s.iteration_lists(i)
+        side = i < len(orders) and orders[i] == 4
+        print("iteration %d: first search failed for %4d rollouts (both passes failed: %4d), %4d of them at the lambda cap: retry list %4d; chg %4d kr %4d%s"
+              % (i, retried.sum(), (ta[:, i] == 0.0).sum(), saturated.sum(), (retried & ~saturated).sum(), len(chg), len(kr),
+                 "  SIDE BY SIDE: %d retries speculated, %d slots" % (len(chg), 2 * len(chg) + len(kr)) if side else ""))
         lam = np.where(ta[:, i] > 0.0, np.maximum(used / 2.0, 1e-6), used)

@@ -51,4 +51,9 @@ if len(sys.argv) > 3 and sys.argv[3] == "all":
             nm = r["Kernel_Name"].replace("void ", "").replace("ilqr::", "").split("(")[0].split("<")[0]
             if nm in ("k_lin_primal_r", "k_lin_primal_s", "k_lin_tangent", "k_lin_tangent2", "k_lin_tangent2c", "k_quad_kin", "k_cost_quadratics", "k_backward_wave", "k_backward_pack", "k_line_search_s", "k_rollout_s"):
                 parts.append("%s %.0f" % (nm[2:14], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
-        print("%4d %9.1f  %s" % (k, (b - a) / 1e3, "  ".join(parts)))
+        # side by side (k_control_spec, k_control_listed): two Riccati passes in flight at once
+        bw = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in seg if "k_backward_pack" in r["Kernel_Name"] or "k_backward_wave" in r["Kernel_Name"]]
+        side = any(p[0] < q[1] and q[0] < p[1] for i, p in enumerate(bw) for q in bw[i + 1:])
+        listed = any("k_control_listed" in r["Kernel_Name"] for r in seg)
+        print("%4d %9.1f  %-12s %s" % (k, (b - a) / 1e3, ("side-by-side" if side else "sequential") + ("*" if listed and not side else ""), "  ".join(parts)))
+    print("(side-by-side: two Riccati passes overlap in time; *: the listed pair was enqueued and the device took the sequential order)")
