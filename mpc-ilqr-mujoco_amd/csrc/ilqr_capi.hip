@@ -19,6 +19,7 @@
 #include "h1_host_model.h"
 #include "ilqr_kernels.h"
 #include "plant_plan.h"
+#include "solve_order.h"
 #include "plant_score_kernels.h"
 #include "reference_track_kernels.h"
 
@@ -78,7 +79,7 @@ struct ilqr_hip_ctx {
   hipStream_t stream2 = nullptr;          // cost quadratics run here, concurrently with the linearisation
   hipStream_t stream3 = nullptr;          // nominal re-rollout of iterations >= 1, concurrently with both
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_roll = nullptr;
-  hipEvent_t ev_lin = nullptr, ev_adopt = nullptr;   // adoption of the re-rolled trajectory beside the backward pass (enqueue_solve)
+  hipEvent_t ev_lin = nullptr, ev_adopt = nullptr;   // adoption of the re-rolled trajectory beside the backward pass (enqueue_region, wait_adoption)
   double* d_shadowx = nullptr;            // [B][N+1][51] target of the concurrent re-rollout
   DevState S{};
   h1::ProblemDev P{};
@@ -108,12 +109,12 @@ struct ilqr_hip_ctx {
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
   size_t step_cap = 0;
-  unsigned long long* d_mismatch = nullptr;
+  unsigned long long* d_mismatch = nullptr;   // elements in which a concurrent re-rollout differed from the trajectory it replaced
   // multi-GPU: RCCL communicator of this handle's rank and the packed first-knot payload it sends
   ncclComm_t comm = nullptr;
   int world = 1, rank = 0;
   double* d_payload = nullptr;
-  size_t payload_cap = 0;   // elements in which a concurrent re-rollout differed from the trajectory it replaced
+  size_t payload_cap = 0;
   int max_iter = 10;
   double tol = 1e-4;
   int jac_mode = ILQR_JAC_ANALYTIC;
@@ -127,7 +128,7 @@ struct ilqr_hip_ctx {
   std::vector<hipEvent_t> ev_active;
   int iterations_enqueued = 0;
   // S.xbar is a rollout of (S.x0, S.ubar) by `rolled_variant` under `rolled_dyn` (the cold start): iteration 0 of the next solve
-  // may then re-roll it beside the linearisation like every later iteration (enqueue_solve); cleared by anything that changes
+  // may then re-roll it beside the linearisation like every later iteration (solve_order.h rolls_aside); cleared by anything that changes
   // the trajectory or x0 without a rollout
   bool xbar_rolled = false, first_aside = false;
   int rolled_variant = -1;
@@ -139,20 +140,21 @@ struct ilqr_hip_ctx {
   int lxx_layout = 0;
   bool ab_packed = false, ab_pads_clean = false;
   int dedup_retry = 1;          // ilqr_hip_set_dedup_saturated_retry: on unless the caller or ILQR_DEDUP_RETRY=0 asks for the full retry
-  // linearisation cache (enqueue_solve): relin = ilqr_hip_set_relinearize_unchanged; what the last solve did, for
+  // linearisation cache (solve_order.h SolveOrder::cache): relin = ilqr_hip_set_relinearize_unchanged; what the last solve did, for
   // ilqr_hip_get_linearized_rollouts: lin_iterations (0: no solve, or its lists are gone), lin_cached = iterations >= 1 ran from
   // DevState::chg, lin_listed = the region of every iteration ran from list (it, 0) (convergence exit, whole batch), else from no list
   int relin = 0, lin_iterations = 0;
   bool lin_cached = false, lin_listed = false;
-  // first-pass skip (enqueue_solve): repass = ilqr_hip_set_repeat_first_pass; fp_listed[it] = the first pass of iteration it of the last solve
-  // ran from DevState::chg (ilqr_hip_get_first_pass_rollouts); d_fp_gate [4]: device-side choice of the line-search kernel
-  // (launch_line_search_gated) -- words 0, 1 for the first pass, words 2, 3 for the lambda retry
-  // retry_order[it]: what the retry of iteration it of the last solve ran for (ilqr_hip_get_retry_pass_rollouts) -- RETRY_LIST the retry
-  // list (it, 1), RETRY_TWIN every active rollout (side by side), RETRY_DUAL whichever of the two the device chose
+  // first-pass skip (solve_order.h SolveOrder::skip_first): repass = ilqr_hip_set_repeat_first_pass; d_fp_gate [4]: device-side choice of the
+  // line-search kernel (launch_line_search_gated) -- words 0, 1 for the first pass, words 2, 3 for the lambda retry
   int repass = 0;
-  std::vector<char> fp_listed, retry_order;
-  enum { RETRY_LIST = 0, RETRY_TWIN = 1, RETRY_DUAL = 2 };
   int* d_fp_gate = nullptr;
+  // record[it]: the order iteration it of the last solve was enqueued in (enqueue_solve; sized once per solve), for the getters
+  // (read_iteration_counts).  first_listed: its first pass ran from DevState::chg (ilqr_hip_get_first_pass_rollouts); kind: what its retry ran
+  // for (ilqr_hip_get_retry_pass_rollouts) -- ORDER_SEQUENTIAL the retry list (it, 1), ORDER_TWIN every active rollout (side by side),
+  // ORDER_DUAL whichever of the two the device chose; pair: it enqueued the listed pair (word 4 of its gate words says whether the device
+  // took the side-by-side order)
+  std::vector<ilqr::IterationRecord> record;
   bool env_refused = false;     // ILQR_ENV_PER_CALL: the last re-read selected a family this library does not hold (enter, enter_launching)
   double packed_h = 0.0;        // step size h of the packed image while ab_packed (k_unpack_ab rebuilds the position rows from it)
   Knobs knobs = read_knobs();   // (constructed in ilqr_hip_create)
@@ -180,12 +182,11 @@ struct ilqr_hip_ctx {
   int spec_iterations = 0;    // iterations of the last solve that enqueued both passes side by side
   int* d_spec_gate = nullptr; // [4] device-side choice of the order (launch_spec_gate)
   // listed side-by-side order (ilqr_kernels.hip k_control_listed): listed_spec = ilqr_hip_set_listed_spec; d_lgate [max_iter][8] the gate words of
-  // every iteration (launch_listed_prologue; word 4 = taken), read back by the getters; listed_dual[it] = iteration it of the last solve enqueued the pair
+  // every iteration (launch_listed_prologue; word 4 = taken), read back by the getters
   int listed_spec = 1;
   int* d_lgate = nullptr;
-  std::vector<char> listed_dual;
-  // early continuation (enqueue_solve): streams / events of the group that starts the next iteration behind the first control pass
-  hipStream_t a1 = nullptr;     // (its cost quadratics and re-rollout share streams 2 and 3 with the other group, see enqueue_solve)
+  // early continuation (solve_order.h SolveOrder::can_split): streams / events of the group that starts the next iteration behind the first control pass
+  hipStream_t a1 = nullptr;     // (its cost quadratics and re-rollout share streams 2 and 3 with the other group, see group_a_lanes)
   hipEvent_t evA_fork = nullptr, evA_join = nullptr, evA_roll = nullptr, evA_lin = nullptr, evA_adopt = nullptr;
   int split_iterations = 0;   // iterations of the last solve whose concurrent region ran in two groups
   // device-resident plant (ilqr_hip_plant_*; plant_kernels.hip): every buffer is owned here and freed by ilqr_hip_destroy
@@ -884,7 +885,7 @@ int ilqr_hip_set_max_iterations(ilqr_hip_ctx* c, int max_iter) {
     c->S.chg = c->S.chg_n = c->S.chg_rn = c->S.chg_an = nullptr; c->lin_iterations = 0;
     TRY(dalloc(c, &c->S.chg, (size_t)c->B * (max_iter + 1))); TRY(dalloc(c, &c->S.chg_n, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.chg_rn, (size_t)max_iter + 2)); TRY(dalloc(c, &c->S.chg_an, (size_t)max_iter + 2));
     { void* kp[] = {c->S.kr, c->S.kr_n, c->d_lgate}; for (void* p : kp) if (p) hipFree(p); }
-    c->S.kr = c->S.kr_n = c->d_lgate = nullptr; c->listed_dual.clear();
+    c->S.kr = c->S.kr_n = c->d_lgate = nullptr; c->record.clear();
     TRY(dalloc(c, &c->S.kr, (size_t)c->B * (max_iter + 1))); TRY(dalloc(c, &c->S.kr_n, (size_t)max_iter + 1)); TRY(dalloc(c, &c->d_lgate, 8 * (size_t)max_iter));
   }
   return ILQR_OK;
@@ -1049,10 +1050,9 @@ static int ensure_slices(ilqr_hip_ctx* c, int k) {
   }
   return ILQR_OK;
 }
-// the launch sequence of iLQR::solve (ilqr.cpp:521-660) for one slice on its streams; `wait_lead` (optional) delays the
-// first throughput-bound stage until the previous slice has finished its first backward pass, `lead` is recorded there
-// the handle's own setting (ilqr_hip_set_early_exit_gate); the environment, when set, overrides it (diagnostics, tests)
-static int early_exit_gate(const ilqr_hip_ctx* c) { return c->knobs.ee_gate >= 0 ? c->knobs.ee_gate : c->ee_gate; }
+// a switch that the handle has a setting of its own for (`own`: its setter's value): the environment, when set, overrides it (diagnostics, tests)
+static int effective(int knob, int own) { return knob >= 0 ? knob : own; }
+static int early_exit_gate(const ilqr_hip_ctx* c) { return effective(c->knobs.ee_gate, c->ee_gate); }      // ilqr_hip_set_early_exit_gate
 static int ensure_gate(ilqr_hip_ctx* c) {
   if ((int)c->ev_active.size() >= c->max_iter + 2 && c->h_active) return ILQR_OK;
   if (c->h_active) { (void)hipHostFree(c->h_active); c->h_active = nullptr; }
@@ -1060,24 +1060,32 @@ static int ensure_gate(ilqr_hip_ctx* c) {
   while ((int)c->ev_active.size() < c->max_iter + 2) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_active.push_back(e); }
   return ILQR_OK;
 }
-// Speculative lambda retry: while at most SPEC_MAX rollouts are in a pass (the whole batch, or -- convergence exit with the gate --
-// the count the host has seen), two Riccati passes / line searches of that many one-wave rollouts fit on the chip's 1024 SIMDs side by
-// side.  ILQR_SPEC=0 switches it off (sequential retry as for large passes), ILQR_SPEC_MAX moves the threshold (diagnostics, tests).
-// early continuation (enqueue_solve): by default with the convergence exit only -- measured on one MI355X, executed iterations/s with / without:
-// constraint-free B = 4096 +1.5 %, contact B = 4096 +9 %, contact B = 1024 +5 %, configs[4] +4 %; with a fixed iteration count most rollouts
-// retry in most iterations, the early group is small, and its kernels only take SIMDs from the one-wave-per-SIMD kernels of the retry
-// (headline -3 %, contact +3 % / -3.5 % at B = 4096 / 1024).  ILQR_SPLIT=0 / 1 forces it off / on.
-static int split_enabled(const ilqr_hip_ctx* c) { return c->knobs.split >= 0 ? c->knobs.split : c->early_exit; }
-static int alloc_twin(ilqr_hip_ctx* c);
-// Listed side-by-side order (enqueue_solve): what a handle's settings must allow before a fixed-iteration solve enqueues it -- the lists it rests on
-// (linearisation cache, first-pass skip, saturated-retry skip: not with ILQR_RELIN=1, ILQR_REPASS=1, ILQR_DEDUP_RETRY=0 or their setters), analytic
-// Jacobians, the whole batch on one stream set, no early-continuation split, no convergence exit (that path has the orders above)
-static bool listed_spec_wanted(const ilqr_hip_ctx* c, const ilqr::LaunchPlan& L, int slices) {
-  const int dedup = c->knobs.dedup_retry >= 0 ? c->knobs.dedup_retry : c->dedup_retry, relin = c->knobs.relin >= 0 ? c->knobs.relin : c->relin;
-  return c->knobs.spec && c->knobs.spec_lists && c->listed_spec && c->knobs.spec_list_max > 0 && !c->early_exit && slices <= 1 && c->max_iter > 1 &&
-         c->jac_mode == ILQR_JAC_ANALYTIC && L.lin_lists && L.spec_dual && dedup && !relin && !(c->knobs.repass || c->repass) && !split_enabled(c) &&
-         c->B > c->knobs.spec_max && c->S.kr && c->S.kr_n && c->S.ls_list && c->S.ls_kind && c->d_lgate;
+// The streams and events one launch sequence is enqueued on -- m: the sequence itself and the linearisation, q: cost quadratics (and the
+// twin's passes of a side-by-side order), r: the nominal re-rollout and its adoption (lin / adopt: null where the adoption waits on m
+// instead).  Values built from the fields of their owners (the handle, a slice): nothing changes hands.
+struct Lanes { hipStream_t m, q, r; hipEvent_t fork, join, roll, lin, adopt; };
+static Lanes main_lanes(const ilqr_hip_ctx* c) { return Lanes{c->stream, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_roll, c->ev_lin, c->ev_adopt}; }
+static Lanes slice_lanes(const ilqr_hip_ctx::Slice& sl) { return Lanes{sl.st, sl.st2, sl.st3, sl.fork, sl.join, sl.roll, nullptr, nullptr}; }
+// (group A's cost quadratics and re-rollout share the second and third stream with group R -- idle while the retry runs, and R's
+// work comes behind A's anyway --, only its linearisation has a stream of its own: the runtime maps streams onto four hardware
+// queues by default, and streams that share a queue serialise)
+static Lanes group_a_lanes(const ilqr_hip_ctx* c, const Lanes& G) { return Lanes{c->a1, G.q, G.r, c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}; }
+// what solve_order.h decides from, for the view S of the batch enqueued on G: the effective switches, the sizes and which buffers exist
+static ilqr::SolveSettings solve_settings(const ilqr_hip_ctx* c, const DevState& S, const Lanes& G) {
+  const Knobs& k = c->knobs;
+  ilqr::SolveSettings s{};
+  s.early_exit = c->early_exit != 0; s.early_exit_gate = early_exit_gate(c) != 0; s.split = effective(k.split, c->early_exit) != 0;
+  s.spec = k.spec != 0; s.spec_dual = k.spec_dual != 0; s.spec_max = k.spec_max;
+  s.spec_lists = k.spec_lists != 0; s.listed_spec = c->listed_spec != 0; s.spec_list_max = k.spec_list_max; s.spec_list_from = k.spec_list_from;
+  s.dedup = effective(k.dedup_retry, c->dedup_retry) != 0; s.relin = effective(k.relin, c->relin) != 0; s.repass = k.repass || c->repass;
+  s.overlap_rollout = k.overlap_rollout != 0; s.reuse_rollout = k.reuse_rollout != 0;
+  s.max_iter = c->max_iter; s.B = S.B; s.slices = c->n_slices; s.analytic_jacobians = c->jac_mode == ILQR_JAC_ANALYTIC; s.first_aside = c->first_aside;
+  s.lists = S.order != nullptr; s.chg = S.chg != nullptr; s.chg_f = S.chg_f != nullptr; s.kr = S.kr && S.kr_n;
+  s.ls_list = S.ls_list != nullptr; s.ls_kind = S.ls_kind != nullptr; s.lgate = c->d_lgate != nullptr;
+  s.grp_a = S.grp_a != nullptr; s.stream_a = c->a1 != nullptr; s.adopt_events = G.lin && G.adopt; s.twin = c->twin;
+  return s;
 }
+static int alloc_twin(ilqr_hip_ctx* c);
 // (the side-by-side order is an optimisation: a handle that cannot get the memory keeps the sequential order instead of failing the solve)
 // Memory: the twin is indexed by rollout like everything else, so it is a full-batch copy of K, k, Vx, Vxx, the eight candidates and
 // their knot costs -- 0.33 MB per rollout at N = 25 (1.3 GB at B = 4096, 10.7 GB at B = 32 768), allocated by the first solve that can
@@ -1117,344 +1125,318 @@ static DevState twin_view(const ilqr_hip_ctx* c, const DevState& S) {
   T.cand_knot = W.cand_knot + (S.cand_knot - F.cand_knot); T.lambda = W.lambda + (S.lambda - F.lambda);
   return T;
 }
-static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDev& P, hipStream_t st, hipStream_t st2, hipStream_t st3,
-                         hipEvent_t ev_fork, hipEvent_t ev_join, hipEvent_t ev_roll, const double* shadow_base, hipEvent_t wait_lead, hipEvent_t lead,
-                         hipEvent_t ev_lin = nullptr, hipEvent_t ev_adopt = nullptr) {
-  // shadow target of the concurrent re-rollout: same rollouts as S.xbar, in the shadow buffer
-  double* shadow = const_cast<double*>(shadow_base) + (S.xbar - c->S.xbar);
-  int* stance_dyn = c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N;     // (same rollouts as S)
-  const ilqr::LaunchPlan L = plan_of(c);      // (the per-call re-read happened in the caller's prologue: the plan cannot change under a solve)
+// What the functions that enqueue one solve share: the handle, the view of the batch and its problem data, the plan and the order resolved
+// for them, the lanes, and the iteration at hand.
+struct SolveCtx {
+  ilqr_hip_ctx* c;
+  const DevState& S;
+  const h1::ProblemDev& P;
+  ilqr::LaunchPlan L;       // (the per-call re-read happened in the caller's prologue: the plan cannot change under a solve)
+  ilqr::SolveOrder O;
+  Lanes G, GA;              // the solve's own lanes (group R's where an iteration runs in two groups) and group A's
+  hipEvent_t lead;
+  double* shadow;           // target of the concurrent re-rollout: same rollouts as S.xbar, in the shadow buffer
+  int* stance_dyn;          // (same rollouts as S)
   // step size h while launch_linearize writes Jacobians whose hinge-position rows are exactly e_k + h * the hinge-velocity rows (the
   // analytic tangent kernels, lin_column) and the backward kernel uses that (riccati_wave.hip fold_rows); else 0
-  const double fold_h = L.folds_h ? P.dyn.h : 0.0;
+  double fold_h;
+  DevState Tw;              // the twin view of S (S itself while the handle has no twin: no order reads it then)
+  // ---- the iteration at hand
+  int iter;
+  int ls_bound;             // with the gate the host has seen how many rollouts were still active at the start of iteration iter - 1: an upper
+                            // bound for this iteration's passes -- the active set only shrinks; else -1
+  bool adopt_aside;         // the re-rolled trajectory is adopted on G.r, beside the backward pass
+  bool prev_split;          // group A of the iteration at hand is already enqueued
+};
+// One group's share of the concurrent region of an iteration -- linearisation (:576) on G.m, cost quadratics (:588) on G.q, the
+// nominal re-rollout (:551,563) into the shadow buffer and its adoption on G.r (solve_order.h rolls_aside) -- behind an event recorded on
+// fork_src.
+// Sm: the view the mask-selected kernels (rollout, trajectory cost, adoption) get -- S, or S with a group's flags as `active`;
+// wl: the group's compacted list for the per-knot kernels (null: the iteration's own list / mask, as knot_mode and iter_l say).
+static int enqueue_region(const SolveCtx& X, const Lanes& G, hipStream_t fork_src, const DevState& Sm, int knot_mode, int iter_l, const ilqr::WorkList* wl, bool concurrent_roll) {
+  ilqr_hip_ctx* c = X.c;
+  HIPCHK(c, hipEventRecord(G.fork, fork_src));
+  if (G.m != fork_src) HIPCHK(c, hipStreamWaitEvent(G.m, G.fork, 0));
+  HIPCHK(c, hipStreamWaitEvent(G.q, G.fork, 0));
+  if (concurrent_roll) {
+    HIPCHK(c, hipStreamWaitEvent(G.r, G.fork, 0));
+    DevState Sr = Sm; Sr.xbar = X.shadow;
+    { StageTimer T(c, 0, G.r); ilqr::launch_rollout(X.L, Sr, X.P, ilqr::MASK_ACTIVE, 1, 0, X.S.Jbase, G.r); }
+    HIPCHK(c, hipEventRecord(G.roll, G.r));
+  }
+  { StageTimer T(c, 2, G.q); ilqr::launch_cost_quadratics(X.S, X.P, knot_mode, G.q, iter_l, X.L.lxx_layout, wl); }
+  HIPCHK(c, hipEventRecord(G.join, G.q));
+  { StageTimer T(c, 1, G.m); ilqr::launch_linearize(X.L, X.S, X.P, knot_mode, c->fd_eps, G.m, 3, iter_l, X.L.pack ? 1 : 0, wl, X.stance_dyn); }
+  if (concurrent_roll && G.lin && G.adopt) {
+    HIPCHK(c, hipEventRecord(G.lin, G.m));
+    HIPCHK(c, hipStreamWaitEvent(G.r, G.lin, 0)); HIPCHK(c, hipStreamWaitEvent(G.r, G.join, 0));
+    ilqr::launch_adopt_rollout(Sm, X.shadow, ilqr::MASK_ACTIVE, c->d_mismatch, G.r);
+    HIPCHK(c, hipEventRecord(G.adopt, G.r));
+  }
+  return ILQR_OK;
+}
+// t goes on only behind the adoption of the re-rolled trajectory (the line search reads it; the backward pass does not)
+static int wait_adoption(const SolveCtx& X, hipStream_t t) {
+  if (X.adopt_aside) HIPCHK(X.c, hipStreamWaitEvent(t, X.G.adopt, 0));
+  if (X.prev_split) HIPCHK(X.c, hipStreamWaitEvent(t, X.GA.adopt, 0));
+  return ILQR_OK;
+}
+// a side-by-side pass: the second stream starts behind what G.m holds so far, and G.m goes on behind what the second stream was given
+static int fork_second(const SolveCtx& X) {
+  HIPCHK(X.c, hipEventRecord(X.c->ev_spec_fork, X.G.m));
+  HIPCHK(X.c, hipStreamWaitEvent(X.G.q, X.c->ev_spec_fork, 0));
+  return ILQR_OK;
+}
+static int join_second(const SolveCtx& X) {
+  HIPCHK(X.c, hipEventRecord(X.c->ev_spec_join, X.G.q));
+  HIPCHK(X.c, hipStreamWaitEvent(X.G.m, X.c->ev_spec_join, 0));
+  return ILQR_OK;
+}
+// with the gate: the count of rollouts still active behind this iteration travels to the host (SolveOrder::gate)
+static int publish_active(const SolveCtx& X) {
+  if (!X.O.gate) return ILQR_OK;
+  HIPCHK(X.c, hipMemcpyAsync(&X.c->h_active[X.iter + 1], X.S.order_n + 2 * (X.iter + 1), sizeof(int), hipMemcpyDeviceToHost, X.G.m));
+  HIPCHK(X.c, hipEventRecord(X.c->ev_active[X.iter], X.G.m));
+  return ILQR_OK;
+}
+// ORDER_TWIN: both passes of ilqr.cpp:601-646 side by side (k_control_spec), the twin on the second stream
+static int enqueue_twin_iteration(const SolveCtx& X) {
+  ilqr_hip_ctx* c = X.c; const DevState& S = X.S; const DevState& Tw = X.Tw;
+  const hipStream_t st = X.G.m, st2 = X.G.q;
+  ++c->spec_iterations;
+  TRY(fork_second(X));
+  ilqr::launch_spec_lambda(S, Tw.lambda, st2);
+  { StageTimer T(c, 3, st); ilqr::launch_backward(X.L, S, ilqr::MASK_ACTIVE, st, X.fold_h, X.iter); }
+  { StageTimer T(c, 6, st2); ilqr::launch_backward(X.L, Tw, ilqr::MASK_ACTIVE, st2, X.fold_h, X.iter); }
+  TRY(wait_adoption(X, st)); TRY(wait_adoption(X, st2));
+  if (X.iter == 0 && X.lead) HIPCHK(c, hipEventRecord(X.lead, st));
+  { StageTimer T(c, 4, st); ilqr::launch_line_search(X.L, S, X.P, ilqr::MASK_ACTIVE, st, X.iter, X.ls_bound); }
+  { StageTimer T(c, 7, st2); ilqr::launch_line_search(X.L, Tw, X.P, ilqr::MASK_ACTIVE, st2, X.iter, X.ls_bound); }
+  TRY(join_second(X));
+  { StageTimer T(c, 5, st); ilqr::launch_control_spec(S, Tw, X.iter, c->tol, c->early_exit, st, X.L.ls_costs_per_knot); }
+  return publish_active(X);
+}
+// ORDER_DUAL: both orders are enqueued and the device takes one (SolveOrder::dual_order)
+static int enqueue_dual_iteration(const SolveCtx& X) {
+  ilqr_hip_ctx* c = X.c; const DevState& S = X.S; const DevState& Tw = X.Tw;
+  const hipStream_t st = X.G.m, st2 = X.G.q;
+  const int iter = X.iter, spec_max = X.O.spec_max;
+  const int* list = S.order + (size_t)(2 * iter) * S.B;
+  int* g = c->d_spec_gate;
+  ++c->spec_iterations;
+  ilqr::launch_spec_gate(S, iter, spec_max, g, st);
+  TRY(fork_second(X));
+  ilqr::launch_spec_lambda(S, Tw.lambda, st2);
+  { StageTimer T(c, 3, st); ilqr::launch_backward(X.L, S, ilqr::MASK_ACTIVE, st, X.fold_h, iter); }
+  { StageTimer T(c, 6, st2); ilqr::launch_backward_list(X.L, Tw, st2, X.fold_h, list, g); }
+  TRY(wait_adoption(X, st)); TRY(wait_adoption(X, st2));
+  { StageTimer T(c, 4, st);
+    ilqr::launch_line_search_list(S, X.P, st, list, g, spec_max);
+    ilqr::launch_line_search_list(S, X.P, st, list, g + 2, X.ls_bound);
+    ilqr::launch_cand_costs(S, X.P, ilqr::MASK_ACTIVE, st, false); }
+  { StageTimer T(c, 7, st2); ilqr::launch_line_search_list(Tw, X.P, st2, list, g, spec_max); ilqr::launch_cand_costs(Tw, X.P, ilqr::MASK_ACTIVE, st2, false, g); }
+  TRY(join_second(X));
+  { StageTimer T(c, 5, st);
+    ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, X.L.ls_costs_per_knot, g);
+    ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | X.O.dedup_bit, st, X.L.ls_costs_per_knot, g + 1); }
+  { StageTimer T(c, 6, st); ilqr::launch_backward(X.L, S, ilqr::MASK_RETRY, st, X.fold_h, iter); }
+  { StageTimer T(c, 7, st); ilqr::launch_line_search(X.L, S, X.P, ilqr::MASK_RETRY, st, iter, X.ls_bound); }
+  { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, X.L.ls_costs_per_knot); }
+  return publish_active(X);
+}
+// The listed side-by-side order in front of the sequential one (SolveOrder::listed): the twin runs the first pass of the changed rollouts
+// (wf, the iteration's chg list), the solve's own buffers the known retries.  The sequential order behind it sees an empty first-pass list
+// (wf->count) and closed gates (*gseq: the gate of its bookkeeping) where the device took this order -- its retry list stays empty: nobody
+// ran phase 0.
+static int enqueue_listed_pair(const SolveCtx& X, ilqr::WorkList* wf, const int** gseq) {
+  ilqr_hip_ctx* c = X.c; const DevState& S = X.S; const DevState& Tw = X.Tw;
+  const hipStream_t st = X.G.m, st2 = X.G.q;
+  int* g = c->d_lgate + 8 * (size_t)X.iter;
+  const int slots = c->knobs.spec_list_max < S.B ? c->knobs.spec_list_max : S.B;      // (either list holds at most this many rollouts where the order is taken)
+  DevState Su = S; Su.active = S.ls_kind;       // the candidates' knot costs select by mask: chg and kr as flags on S, chg on the twin
+  DevState Tf = Tw; Tf.active = S.chg_f;
+  ilqr::launch_listed_prologue(S, Tw.lambda, X.iter, c->knobs.spec_list_max, g, st);
+  TRY(fork_second(X));
+  { StageTimer T(c, 3, st); ilqr::launch_backward_list(X.L, S, st, X.fold_h, S.ls_list, g + 3); }
+  { StageTimer T(c, 6, st2); ilqr::launch_backward_list(X.L, Tw, st2, X.fold_h, wf->list, g); }
+  TRY(wait_adoption(X, st)); TRY(wait_adoption(X, st2));
+  { StageTimer T(c, 4, st); ilqr::launch_line_search_s(S, X.P, ilqr::MASK_ACTIVE, st, S.ls_list, g + 3, slots, 1); ilqr::launch_cand_costs(Su, X.P, ilqr::MASK_ACTIVE, st, false, g + 4); }
+  { StageTimer T(c, 7, st2); ilqr::launch_line_search_s(Tw, X.P, ilqr::MASK_ACTIVE, st2, wf->list, g, slots, 1); ilqr::launch_cand_costs(Tf, X.P, ilqr::MASK_ACTIVE, st2, false, g + 4); }
+  TRY(join_second(X));
+  { StageTimer T(c, 5, st); ilqr::launch_control_listed(S, Tw, X.iter, st, X.L.ls_costs_per_knot, g); }
+  wf->count = g + 2; *gseq = g + 1;
+  return ILQR_OK;
+}
+// ORDER_SEQUENTIAL: first pass (:601-620), lambda retry (:637-646); with or without lists, behind the listed pair where ord.pair.
+// *split_next: group A of the next iteration has been enqueued behind the first control pass (SolveOrder::can_split)
+static int enqueue_sequential_iteration(const SolveCtx& X, const ilqr::IterationOrder& ord, bool* split_next) {
+  ilqr_hip_ctx* c = X.c; const DevState& S = X.S; const h1::ProblemDev& P = X.P; const ilqr::LaunchPlan& L = X.L;
+  const hipStream_t st = X.G.m;
+  const int iter = X.iter, ls_bound = X.ls_bound;
+  ilqr::WorkList wf{S.chg + (size_t)iter * S.B, S.chg_n + iter};
+  const int* gseq = nullptr;
+  if (ord.pair) TRY(enqueue_listed_pair(X, &wf, &gseq));
+  { StageTimer T(c, 3, st);                                                                                              // :601
+    if (ord.first_listed) ilqr::launch_backward_list(L, S, st, X.fold_h, wf.list, wf.count);
+    else ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, X.fold_h, iter); }
+  TRY(wait_adoption(X, st));
+  if (iter == 0 && X.lead) HIPCHK(c, hipEventRecord(X.lead, st));
+  { StageTimer T(c, 4, st);                                                                                              // :616
+    if (ord.first_listed) {
+      DevState Sf = S; Sf.active = S.chg_f;      // (the candidates' knot costs select by mask: the list as flags; every other rollout's cand_knot stays)
+      ilqr::launch_line_search_gated(S, P, st, wf.list, wf.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate);
+      ilqr::launch_cand_costs(Sf, P, ilqr::MASK_ACTIVE, st, false, gseq);
+    } else ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
+  { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | X.O.dedup_bit, st, L.ls_costs_per_knot, gseq); }      // :619-620,645-655
+  *split_next = X.O.can_split && iter + 1 < c->max_iter && ilqr::rolls_aside(X.O, L, iter + 1);
+  if (*split_next) {
+    // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
+    HIPCHK(c, hipMemcpyAsync(S.order_an + iter + 1, S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToDevice, st));
+    DevState Sg = S; Sg.active = S.grp_a;
+    if (X.O.cache) HIPCHK(c, hipMemcpyAsync(S.chg_an + iter + 1, S.chg_n + iter + 1, sizeof(int), hipMemcpyDeviceToDevice, st));
+    const ilqr::WorkList wa = X.O.cache ? ilqr::WorkList{S.chg + (size_t)(iter + 1) * S.B, S.chg_an + iter + 1} : ilqr::WorkList{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
+    TRY(enqueue_region(X, X.GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
+  }
+  { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, X.fold_h, iter); }                                // :637
+  { StageTimer T(c, 7, st);                                                                                              // :638
+    if (X.O.retry_gated) {
+      const ilqr::WorkList wr = ilqr::work_list(S, ilqr::MASK_RETRY, iter);
+      ilqr::launch_line_search_gated(S, P, st, wr.list, wr.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate + 2);
+      ilqr::launch_cand_costs(S, P, ilqr::MASK_RETRY, st, false, gseq);
+    } else ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
+  { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot, gseq); }                    // :640-646
+  return publish_active(X);
+}
+// the launch sequence of iLQR::solve (ilqr.cpp:521-660) for one slice on its streams; `wait_lead` (optional) delays the
+// first throughput-bound stage until the previous slice has finished its first backward pass, `lead` is recorded there.
+// Which order each iteration takes is decided in solve_order.h; every order has a function of its own above.
+static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDev& P, const Lanes& G, hipEvent_t wait_lead, hipEvent_t lead) {
+  const hipStream_t st = G.m;
+  const ilqr::LaunchPlan L = plan_of(c);
+  const ilqr::SolveOrder O = ilqr::resolve_solve_order(solve_settings(c, S, G), L);
+  SolveCtx X{c, S, P, L, O, G, group_a_lanes(c, G), lead,
+             c->d_shadowx + (S.xbar - c->S.xbar), c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N,
+             L.folds_h ? P.dyn.h : 0.0, c->twin ? twin_view(c, S) : S, 0, -1, false, false};
   { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st);
     // (rounds >= 2 of an augmented-Lagrangian solve with the convergence exit: the rollouts that are done enter inactive)
     if (P.al && c->al_round > 0 && c->early_exit) ilqr::launch_solve_begin_al(S, c->d_al_done + (S.active - c->S.active), st);
     else ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
-  // With the convergence exit on, the launches of an iteration nobody needs are pure latency (17 launches that find nothing to
-  // do): the count of rollouts active after iteration i (DevState::order_n, maintained by k_control) follows iteration i to the
-  // host, which enqueues iteration i only after it has seen the count left by iteration i - 2 -- one full iteration stays
-  // queued on the device meanwhile, so the device never waits for the host.  (ILQR_EE_GATE=0: always enqueue max_iter.)
-  // without the convergence exit every rollout stays active: the per-knot kernels then skip the selection altogether
-  const int sel_mode = c->early_exit ? ilqr::MASK_ACTIVE : ilqr::MASK_ALL;
-  const bool gate = c->early_exit && S.order && early_exit_gate(c);
-  const bool xbar_rolled = c->first_aside;
   // the operand-layout Riccati kernel (analytic Jacobians, riccati_pack.hip) has its producers write A_t, B_t and lxx~_t in its own
   // layout; the generic one-wave kernel reads only the tiles I >= J of lxx_t (t < N): the cost quadratics then leave the others unwritten
-  const int pack = L.pack ? 1 : 0;
-  const int lxx_lower = L.lxx_layout;
   // (iteration 0 rewrites A_t, B_t, lxx_t of every rollout: a solve leaves one layout behind; ilqr_hip_solve_async has prepared the padding)
-  c->lxx_layout = lxx_lower;
-  c->ab_packed = pack != 0;
-  c->lin_fold_h = fold_h;        // what S.A / S.Bm hold after this solve; assigned with the layout flags (an early return above leaves all of them alone)
-  if (pack) c->packed_h = fold_h;
-  if (!pack) c->ab_pads_clean = false;
-  if (gate) TRY(ensure_gate(c));
+  c->lxx_layout = L.lxx_layout;
+  c->ab_packed = L.pack;
+  c->lin_fold_h = X.fold_h;      // what S.A / S.Bm hold after this solve; assigned with the layout flags (an early return above leaves all of them alone)
+  if (L.pack) c->packed_h = X.fold_h;
+  if (!L.pack) c->ab_pads_clean = false;
+  if (O.gate) TRY(ensure_gate(c));
   c->iterations_enqueued = c->max_iter;
-  // One group's share of the concurrent region of an iteration -- linearisation (:576) on G.m, cost quadratics (:588) on G.q, the
-  // nominal re-rollout (:551,563) into the shadow buffer and its adoption on G.r -- behind an event recorded on fork_src.
-  //   From the second iteration on the nominal trajectory already is a rollout from x0 (the accepted line-search candidate, or the
-  //   unchanged previous nominal), so the re-rollout reproduces it bit for bit (ilqr_hip_get_adopt_mismatches): it runs beside the
-  //   linearisation and is adopted (with its cost, the line-search baseline) once the linearisation and the cost quadratics have
-  //   read the old copy; the backward pass reads neither, only the line search waits for the adoption.  ILQR_OVERLAP_ROLLOUT=0
-  //   restores the sequential order; ILQR_REUSE_ROLLOUT=1 skips the re-rollout (not the default: SURVEY 8(d) counts it).
-  //   (only while the line search and the rollout run the same step implementation; iteration 0 as well when the nominal trajectory
-  //   is itself a rollout by this very kernel -- the cold start, initializeWithReference ilqr.cpp:113-115; a warm-shifted or
-  //   caller-supplied trajectory is rolled out BEFORE the linearisation, as the reference does)
-  // Sm: the view the mask-selected kernels (rollout, trajectory cost, adoption) get -- S, or S with a group's flags as `active`;
-  // wl: the group's compacted list for the per-knot kernels (null: the iteration's own list / mask, as knot_mode and iter_l say).
-  // ilqr_hip_set_dedup_saturated_retry (on by default): bit 1 of k_control's early_exit argument (the sequential orders; the side-by-side
-  // order has both passes in flight before either outcome is known).  A retry at the lambda cap repeats its rollout's last executed pass
-  // -- the first pass of the same iteration, or, where that one was skipped, the pass it repeats in turn; iteration 0 of every solve runs
-  // the full first pass, so the chain never leaves the solve
-  const int dedup_bit = (c->knobs.dedup_retry >= 0 ? c->knobs.dedup_retry : c->dedup_retry) ? 2 : 0;
-  // Linearisation cache: from iteration 1 on the per-knot kernels of the region (stance decisions, primal dump, tangent sweeps, kinematics
-  // record, cost quadratics) run from DevState::chg -- the active rollouts whose previous iteration accepted a candidate.  A rollout
-  // whose two line searches both failed enters the iteration with the nominal trajectory it had, bit for bit (k_control copies nothing),
-  // and S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu are functions of that trajectory and the problem data alone (not of lambda) that nothing
-  // between two regions writes: the backward kernels and the twin view read them, the control / adoption kernels never touch them,
-  // the in-place layout conversions belong to the getters and the stage API, outside a solve.  Iteration 0 takes every rollout.  Not for
-  // the forward-difference kernels (they select by S.active and use S.A / S.Bm as scratch) nor for batch slices (no lists);
-  // ilqr_hip_set_relinearize_unchanged / ILQR_RELIN=1: the full pass in every iteration.
-  const bool cache = !(c->knobs.relin >= 0 ? c->knobs.relin : c->relin) && S.order && S.chg && L.lin_lists;
-  c->lin_cached = cache; c->lin_listed = sel_mode != ilqr::MASK_ALL && S.order != nullptr;
-  struct Rg { hipStream_t m, q, r; hipEvent_t fork, join, roll, lin, adopt; };
-  const Rg G0{st, st2, st3, ev_fork, ev_join, ev_roll, ev_lin, ev_adopt};
-  // (group A's cost quadratics and re-rollout share the second and third stream with group R -- idle while the retry runs, and R's
-  // work comes behind A's anyway --, only its linearisation has a stream of its own: the runtime maps streams onto four hardware
-  // queues by default, and streams that share a queue serialise)
-  const Rg GA{c->a1, st2, st3, c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt};
-  auto region = [&](const Rg& G, hipStream_t fork_src, const DevState& Sm, int knot_mode, int iter_l, const ilqr::WorkList* wl, bool concurrent_roll) -> int {
-    HIPCHK(c, hipEventRecord(G.fork, fork_src));
-    if (G.m != fork_src) HIPCHK(c, hipStreamWaitEvent(G.m, G.fork, 0));
-    HIPCHK(c, hipStreamWaitEvent(G.q, G.fork, 0));
-    if (concurrent_roll) {
-      HIPCHK(c, hipStreamWaitEvent(G.r, G.fork, 0));
-      DevState Sr = Sm; Sr.xbar = shadow;
-      { StageTimer T(c, 0, G.r); ilqr::launch_rollout(L, Sr, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, G.r); }
-      HIPCHK(c, hipEventRecord(G.roll, G.r));
-    }
-    { StageTimer T(c, 2, G.q); ilqr::launch_cost_quadratics(S, P, knot_mode, G.q, iter_l, lxx_lower, wl); }
-    HIPCHK(c, hipEventRecord(G.join, G.q));
-    { StageTimer T(c, 1, G.m); ilqr::launch_linearize(L, S, P, knot_mode, c->fd_eps, G.m, 3, iter_l, pack, wl, stance_dyn); }
-    if (concurrent_roll && G.lin && G.adopt) {
-      HIPCHK(c, hipEventRecord(G.lin, G.m));
-      HIPCHK(c, hipStreamWaitEvent(G.r, G.lin, 0)); HIPCHK(c, hipStreamWaitEvent(G.r, G.join, 0));
-      ilqr::launch_adopt_rollout(Sm, shadow, ilqr::MASK_ACTIVE, c->d_mismatch, G.r);
-      HIPCHK(c, hipEventRecord(G.adopt, G.r));
-    }
-    return ILQR_OK;
-  };
-  auto rolls_aside = [&](int iter) {
-    return (iter > 0 ? L.reroll_aside : (xbar_rolled && L.cold_start_aside)) && !c->knobs.reuse_rollout && c->knobs.overlap_rollout;
-  };
-  // Early continuation: the rollouts whose first line search of iteration i accepted a step are done with iteration i; their share of
-  // iteration i + 1's concurrent region (group A) starts right behind the first control pass, on streams of its own, while the
-  // others take their lambda retry (:619-644); those follow as group R behind the second control pass, and both groups meet again at
-  // the backward pass.  The retry of an early iteration keeps a fraction of the chip busy for two latency-bound passes: the time it
-  // left idle is what this recovers.  Same kernels on the same data in the same per-rollout order: results are bit-identical
-  // (GPU test).  On by default with the convergence exit (split_enabled above); ILQR_SPLIT=0 / 1 forces one / two groups.
-  // (analytic Jacobians only: the forward-difference launchers select by S.active, not by the group's list, and use S.A / S.Bm as
-  // scratch that k_fd_finish rewrites in place -- group A's pass would rewrite the Jacobians the retry's backward pass is reading)
-  const bool can_split = split_enabled(c) && S.order && S.grp_a && ev_lin && ev_adopt && c->a1 != nullptr && c->jac_mode == ILQR_JAC_ANALYTIC;
-  // First-pass skip: a rollout whose two line searches of iteration i both failed enters iteration i + 1 with its nominal trajectory, its
-  // Jacobians and quadratics (above) AND its lambda unchanged -- the reference `continue`s with the raised lambda, so the first pass of i + 1
-  // runs at the lambda of the retry of i (ilqr.cpp:619-646) -- and S.Jbase is the cost of a bit-identical re-roll.  Its first backward pass,
-  // line search and candidate costs would rewrite S.K, S.kff, S.Vx, S.Vxx, S.xcand, S.ucand, S.cand_knot with what its last executed pass
-  // (that retry; with the dedup option the first pass that saturated) left there, and fail again.  In the sequential order below the first
-  // pass of iterations >= 1 therefore runs from the list of the rollouts that accepted a candidate, DevState::chg -- the cache's list --,
-  // the candidates' knot costs from the same set as flags (DevState::chg_f).  k_control phase 0 still runs for every active rollout: for a
-  // skipped one it reads the costs that pass left and decides acc = -1 again from them and S.Jbase -- nothing a skipped launch writes.
-  // Not inside the side-by-side orders or the early-continuation split (they keep the full pass: a full pass is always valid), nor
-  // without lists (batch slices, forward differences).  ilqr_hip_set_repeat_first_pass / ILQR_REPASS=1: the full first pass everywhere.
-  const bool skip_first = !(c->knobs.repass || c->repass) && S.order && S.chg && S.chg_f && L.lin_lists && L.spec_dual && !can_split;
-  c->fp_listed.assign((size_t)c->max_iter, 0);
-  c->retry_order.assign((size_t)c->max_iter, ilqr_hip_ctx::RETRY_LIST);
-  // The retry's line search in the sequential order: from its list (iter, 1), a few hundred rollouts in the early iterations and, with the
-  // saturated retries gone, in the late ones -- one rollout per wave where the list holds at most ILQR_LS_LIST_MAX, decided on the device
-  // as for the first pass's list; the candidates' knot costs stay selected by need_retry.  Not with the early-continuation split: there the
-  // retry runs beside group A's region, and a wave per rollout takes SIMDs from it (the early_exit object of bench.py lost 2 %)
-  const bool retry_gated = S.order && L.line_search == ilqr::DYN_TWO_LANE && !can_split;
-  bool prev_split = false;      // group A of the iteration at hand is already enqueued
+  c->lin_cached = O.cache; c->lin_listed = O.lin_listed;
+  c->record.assign((size_t)c->max_iter, ilqr::IterationRecord{ilqr::ORDER_SEQUENTIAL, false, false});
+  const int sel_mode = O.sel_active ? ilqr::MASK_ACTIVE : ilqr::MASK_ALL;
   bool prev_seq = false;        // the previous iteration ran in the sequential order (k_control has written chg_f for this one)
-  // Listed side-by-side order: from iteration listed_from on, the pair (listed side by side, sequential from the lists) is enqueued and
-  // the device takes one by the lists' lengths (launch_listed_prologue).  k_control and k_control_listed both leave order, chg, chg_f and kr
-  // behind, so either order may follow either.
-  const bool listed = listed_spec_wanted(c, L, c->n_slices) && c->twin && skip_first && cache && dedup_bit && !gate;
-  c->listed_dual.assign((size_t)c->max_iter, 0);
-  // (the pair costs ~60 us of empty launches per iteration where the lists stay long -- the early iterations of any solve, every iteration of
-  // a batch that keeps accepting: measured, DESIGN 9 -- so it starts with the last two fifths of the iterations unless ILQR_SPEC_LIST_FROM says otherwise)
-  const int listed_from = c->knobs.spec_list_from >= 1 ? c->knobs.spec_list_from : (3 * c->max_iter / 5 > 1 ? 3 * c->max_iter / 5 : 1);
   for (int iter = 0; iter < c->max_iter; ++iter) {
-    if (gate && iter >= 2) {
+    if (O.gate && iter >= 2) {
       HIPCHK(c, hipEventSynchronize(c->ev_active[iter - 2]));
       if (c->h_active[iter - 1] == 0) { c->iterations_enqueued = iter; break; }     // nobody was active in iteration iter - 1
     }
-    const bool concurrent_roll = rolls_aside(iter);
-    if (!prev_split) {
-      if ((iter == 0 || !c->knobs.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
+    X.iter = iter;
+    X.ls_bound = (O.gate && iter >= 2) ? c->h_active[iter - 1] : -1;
+    const bool concurrent_roll = ilqr::rolls_aside(O, L, iter);
+    if (!X.prev_split) {
+      if ((iter == 0 || !O.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
       if (iter == 0 && wait_lead) HIPCHK(c, hipStreamWaitEvent(st, wait_lead, 0));
       const ilqr::WorkList wc{S.chg + (size_t)iter * S.B, S.chg_n + iter};
-      TRY(region(G0, st, S, sel_mode, iter, (cache && iter > 0) ? &wc : nullptr, concurrent_roll));
+      TRY(enqueue_region(X, G, st, S, sel_mode, iter, (O.cache && iter > 0) ? &wc : nullptr, concurrent_roll));
     } else {
       DevState Sg = S; Sg.active = S.grp_r;      // (the mask-selected kernels: every rollout of the group, changed or not)
-      const ilqr::WorkList wr = cache ? ilqr::WorkList{S.chg_r, S.chg_rn + iter} : ilqr::WorkList{S.order_r, S.order_rn + iter};
-      TRY(region(G0, st, Sg, ilqr::MASK_ACTIVE, -1, &wr, true));
+      const ilqr::WorkList wr = O.cache ? ilqr::WorkList{S.chg_r, S.chg_rn + iter} : ilqr::WorkList{S.order_r, S.order_rn + iter};
+      TRY(enqueue_region(X, G, st, Sg, ilqr::MASK_ACTIVE, -1, &wr, true));
       ++c->split_iterations;
     }
-    const bool adopt_aside = concurrent_roll && ev_lin && ev_adopt;
-    HIPCHK(c, hipStreamWaitEvent(st, ev_join, 0));
-    if (prev_split) { HIPCHK(c, hipStreamWaitEvent(st, GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.lin, 0)); }
-    if (concurrent_roll && !adopt_aside) { HIPCHK(c, hipStreamWaitEvent(st, ev_roll, 0)); ilqr::launch_adopt_rollout(S, shadow, ilqr::MASK_ACTIVE, c->d_mismatch, st); }
-    auto wait_adoption = [&](hipStream_t t) -> int {
-      if (adopt_aside) HIPCHK(c, hipStreamWaitEvent(t, ev_adopt, 0));
-      if (prev_split) HIPCHK(c, hipStreamWaitEvent(t, GA.adopt, 0));
-      return ILQR_OK;
-    };
-    // (with the gate the host has seen how many rollouts were still active at the start of iteration iter - 1: an upper bound
-    // for this iteration's passes -- the active set only shrinks)
-    const int ls_bound = (gate && iter >= 2) ? c->h_active[iter - 1] : -1;
-    const int pass_bound = ls_bound >= 0 ? ls_bound : S.B;
-    if (c->twin && c->knobs.spec && S.order && pass_bound <= c->knobs.spec_max) {
-      // both passes of ilqr.cpp:601-646 side by side (k_control_spec): the twin on the second stream
-      const DevState Tw = twin_view(c, S);
-      ++c->spec_iterations;
-      HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
-      HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
-      ilqr::launch_spec_lambda(S, Tw.lambda, st2);
-      { StageTimer T(c, 3, st); ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward(L, Tw, ilqr::MASK_ACTIVE, st2, fold_h, iter); }
-      TRY(wait_adoption(st)); TRY(wait_adoption(st2));
-      if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-      { StageTimer T(c, 4, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
-      { StageTimer T(c, 7, st2); ilqr::launch_line_search(L, Tw, P, ilqr::MASK_ACTIVE, st2, iter, ls_bound); }
-      HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
-      HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
-      { StageTimer T(c, 5, st); ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }
-      if (gate) {
-        HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
-      }
-      c->retry_order[iter] = ilqr_hip_ctx::RETRY_TWIN;
-      prev_split = false; prev_seq = false;
-      continue;
+    X.adopt_aside = concurrent_roll && G.lin && G.adopt;
+    HIPCHK(c, hipStreamWaitEvent(st, G.join, 0));
+    if (X.prev_split) { HIPCHK(c, hipStreamWaitEvent(st, X.GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, X.GA.lin, 0)); }
+    if (concurrent_roll && !X.adopt_aside) { HIPCHK(c, hipStreamWaitEvent(st, G.roll, 0)); ilqr::launch_adopt_rollout(S, X.shadow, ilqr::MASK_ACTIVE, c->d_mismatch, st); }
+    const ilqr::IterationOrder ord = ilqr::iteration_order(O, iter, X.ls_bound >= 0 ? X.ls_bound : S.B, prev_seq);
+    bool split_next = false;
+    switch (ord.kind) {
+      case ilqr::ORDER_TWIN: TRY(enqueue_twin_iteration(X)); break;
+      case ilqr::ORDER_DUAL: TRY(enqueue_dual_iteration(X)); break;
+      case ilqr::ORDER_SEQUENTIAL: TRY(enqueue_sequential_iteration(X, ord, &split_next)); break;
     }
-    if (c->twin && c->knobs.spec && c->knobs.spec_dual && S.order && gate && pass_bound <= 4 * c->knobs.spec_max && L.spec_dual) {
-      // The host's count is one iteration old: between spec_max and 4 spec_max the pass may or may not have shrunk below the
-      // threshold by now.  Both orders are enqueued and the device takes one (launch_spec_gate): the twin's launches and the
-      // one-rollout-per-wave line search see a count of zero unless the list holds <= spec_max rollouts, the sequential first line
-      // search and bookkeeping see zero if it does; the lambda-retry launches find an empty retry list behind k_control_spec.
-      const DevState Tw = twin_view(c, S);
-      const int* list = S.order + (size_t)(2 * iter) * S.B;
-      int* g = c->d_spec_gate;
-      ++c->spec_iterations;
-      ilqr::launch_spec_gate(S, iter, c->knobs.spec_max, g, st);
-      HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
-      HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
-      ilqr::launch_spec_lambda(S, Tw.lambda, st2);
-      { StageTimer T(c, 3, st); ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(L, Tw, st2, fold_h, list, g); }
-      TRY(wait_adoption(st)); TRY(wait_adoption(st2));
-      { StageTimer T(c, 4, st);
-        ilqr::launch_line_search_list(S, P, st, list, g, c->knobs.spec_max);
-        ilqr::launch_line_search_list(S, P, st, list, g + 2, ls_bound);
-        ilqr::launch_cand_costs(S, P, ilqr::MASK_ACTIVE, st, false); }
-      { StageTimer T(c, 7, st2); ilqr::launch_line_search_list(Tw, P, st2, list, g, c->knobs.spec_max); ilqr::launch_cand_costs(Tw, P, ilqr::MASK_ACTIVE, st2, false, g); }
-      HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
-      HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
-      { StageTimer T(c, 5, st);
-        ilqr::launch_control_spec(S, Tw, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot, g);
-        ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot, g + 1); }
-      { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, fold_h, iter); }
-      { StageTimer T(c, 7, st); ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
-      { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot); }
-      HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
-      c->retry_order[iter] = ilqr_hip_ctx::RETRY_DUAL;
-      prev_split = false; prev_seq = false;
-      continue;
-    }
-    const bool first_listed = skip_first && iter > 0 && prev_seq;
-    c->fp_listed[iter] = first_listed;
-    ilqr::WorkList wf{S.chg + (size_t)iter * S.B, S.chg_n + iter};
-    const bool pair = listed && first_listed && iter >= listed_from;
-    const int* gseq = nullptr;      // gate of the sequential order's bookkeeping where the pair is enqueued
-    if (pair) {
-      int* g = c->d_lgate + 8 * (size_t)iter;
-      const DevState Tw = twin_view(c, S);
-      const int slots = c->knobs.spec_list_max < S.B ? c->knobs.spec_list_max : S.B;      // (either list holds at most this many rollouts where the order is taken)
-      DevState Su = S; Su.active = S.ls_kind;       // the candidates' knot costs select by mask: chg and kr as flags on S, chg on the twin
-      DevState Tf = Tw; Tf.active = S.chg_f;
-      c->listed_dual[iter] = 1;
-      ilqr::launch_listed_prologue(S, Tw.lambda, iter, c->knobs.spec_list_max, g, st);
-      HIPCHK(c, hipEventRecord(c->ev_spec_fork, st));
-      HIPCHK(c, hipStreamWaitEvent(st2, c->ev_spec_fork, 0));
-      { StageTimer T(c, 3, st); ilqr::launch_backward_list(L, S, st, fold_h, S.ls_list, g + 3); }
-      { StageTimer T(c, 6, st2); ilqr::launch_backward_list(L, Tw, st2, fold_h, wf.list, g); }
-      TRY(wait_adoption(st)); TRY(wait_adoption(st2));
-      { StageTimer T(c, 4, st); ilqr::launch_line_search_s(S, P, ilqr::MASK_ACTIVE, st, S.ls_list, g + 3, slots, 1); ilqr::launch_cand_costs(Su, P, ilqr::MASK_ACTIVE, st, false, g + 4); }
-      { StageTimer T(c, 7, st2); ilqr::launch_line_search_s(Tw, P, ilqr::MASK_ACTIVE, st2, wf.list, g, slots, 1); ilqr::launch_cand_costs(Tf, P, ilqr::MASK_ACTIVE, st2, false, g + 4); }
-      HIPCHK(c, hipEventRecord(c->ev_spec_join, st2));
-      HIPCHK(c, hipStreamWaitEvent(st, c->ev_spec_join, 0));
-      { StageTimer T(c, 5, st); ilqr::launch_control_listed(S, Tw, iter, st, L.ls_costs_per_knot, g); }
-      // the sequential order behind it sees an empty first-pass list and closed gates where the device took the order above (its retry
-      // list stays empty: nobody ran phase 0)
-      wf.count = g + 2; gseq = g + 1;
-    }
-    { StageTimer T(c, 3, st);                                                                                              // :601
-      if (first_listed) ilqr::launch_backward_list(L, S, st, fold_h, wf.list, wf.count);
-      else ilqr::launch_backward(L, S, ilqr::MASK_ACTIVE, st, fold_h, iter); }
-    TRY(wait_adoption(st));
-    if (iter == 0 && lead) HIPCHK(c, hipEventRecord(lead, st));
-    { StageTimer T(c, 4, st);                                                                                              // :616
-      if (first_listed) {
-        DevState Sf = S; Sf.active = S.chg_f;      // (the candidates' knot costs select by mask: the list as flags; every other rollout's cand_knot stays)
-        ilqr::launch_line_search_gated(S, P, st, wf.list, wf.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate);
-        ilqr::launch_cand_costs(Sf, P, ilqr::MASK_ACTIVE, st, false, gseq);
-      } else ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | dedup_bit, st, L.ls_costs_per_knot, gseq); }          // :619-620,645-655
-    const bool split_next = can_split && iter + 1 < c->max_iter && rolls_aside(iter + 1);
-    if (split_next) {
-      // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
-      HIPCHK(c, hipMemcpyAsync(S.order_an + iter + 1, S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToDevice, st));
-      DevState Sg = S; Sg.active = S.grp_a;
-      if (cache) HIPCHK(c, hipMemcpyAsync(S.chg_an + iter + 1, S.chg_n + iter + 1, sizeof(int), hipMemcpyDeviceToDevice, st));
-      const ilqr::WorkList wa = cache ? ilqr::WorkList{S.chg + (size_t)(iter + 1) * S.B, S.chg_an + iter + 1} : ilqr::WorkList{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
-      TRY(region(GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
-    }
-    { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, fold_h, iter); }                                  // :637
-    { StageTimer T(c, 7, st);                                                                                              // :638
-      if (retry_gated) {
-        const ilqr::WorkList wr = ilqr::work_list(S, ilqr::MASK_RETRY, iter);
-        ilqr::launch_line_search_gated(S, P, st, wr.list, wr.count, c->knobs.ls_list_max, ls_bound, c->d_fp_gate + 2);
-        ilqr::launch_cand_costs(S, P, ilqr::MASK_RETRY, st, false, gseq);
-      } else ilqr::launch_line_search(L, S, P, ilqr::MASK_RETRY, st, iter, ls_bound); }
-    { StageTimer T(c, 5, st); ilqr::launch_control(S, 1, iter, c->tol, c->early_exit, st, L.ls_costs_per_knot, gseq); }                      // :640-646
-    if (gate) {
-      HIPCHK(c, hipMemcpyAsync(&c->h_active[iter + 1], S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipEventRecord(c->ev_active[iter], st));
-    }
-    prev_split = split_next; prev_seq = true;
+    c->record[iter] = ord;
+    X.prev_split = split_next; prev_seq = ord.kind == ilqr::ORDER_SEQUENTIAL;
   }
-  if (prev_split) {      // (the convergence exit ended the loop behind a group A that found nothing to do: its streams rejoin)
-    HIPCHK(c, hipStreamWaitEvent(st, GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.lin, 0)); HIPCHK(c, hipStreamWaitEvent(st, GA.adopt, 0));
+  if (X.prev_split) {      // (the convergence exit ended the loop behind a group A that found nothing to do: its streams rejoin)
+    HIPCHK(c, hipStreamWaitEvent(st, X.GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, X.GA.lin, 0)); HIPCHK(c, hipStreamWaitEvent(st, X.GA.adopt, 0));
   }
   c->lin_iterations = c->iterations_enqueued;
   return ILQR_OK;
 }
 int ilqr_hip_set_relinearize_unchanged(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->relin = on ? 1 : 0; return ILQR_OK; }
+int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->repass = on ? 1 : 0; return ILQR_OK; }
+int ilqr_hip_set_listed_spec(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->listed_spec = on ? 1 : 0; return ILQR_OK; }
+// What the lists of the last solve held, iteration by iteration, read ONCE behind the handle's stream for the getters below: act[2 it] /
+// act[2 it + 1] the rollouts active at the start of iteration it / in its lambda retry (DevState::order_n), chg[it] and kr[it] the lengths of
+// its chg and kr lists, took[it] = 1 where it enqueued the listed pair and the device took the side-by-side order (word 4 of its gate
+// words).  A buffer the handle does not hold reads as zeros.  On failure "<who>: reading <what> failed" is the handle's error.
+struct IterationCounts { std::vector<int> act, chg, kr, took; };
+static int read_iteration_counts(ilqr_hip_ctx* c, const char* who, const char* what, IterationCounts* n) {
+  const size_t mi = (size_t)c->max_iter;
+  n->act.assign(2 * (mi + 1), 0); n->chg.assign(mi + 1, 0); n->kr.assign(mi + 1, 0); n->took.assign(mi, 0);
+  std::vector<int> g(c->d_lgate ? 8 * mi : 0);
+  auto fetch = [](std::vector<int>& v, const int* dev) { return !dev || v.empty() || hipMemcpy(v.data(), dev, v.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; };
+  if (hipStreamSynchronize(c->stream) != hipSuccess || !fetch(n->act, c->S.order_n) || !fetch(n->chg, c->S.chg_n) || !fetch(n->kr, c->S.kr_n) || !fetch(g, c->d_lgate)) {
+    c->err = std::string(who) + ": reading " + what + " failed";
+    return ILQR_ERR_HIP;
+  }
+  for (size_t it = 0; it < mi && it < c->record.size() && !g.empty(); ++it) n->took[it] = (c->record[it].pair && g[8 * it + 4]) ? 1 : 0;
+  return ILQR_OK;
+}
+// the order iteration it of the last solve was enqueued in
+static ilqr::IterationRecord recorded(const ilqr_hip_ctx* c, int it) {
+  return (size_t)it < c->record.size() ? c->record[it] : ilqr::IterationRecord{ilqr::ORDER_SEQUENTIAL, false, false};
+}
 long long ilqr_hip_get_linearized_rollouts(ilqr_hip_ctx* c) {
   if (!c) return -1;
   enter(c);
   const int n = c->lin_iterations;
   if (n <= 0) return 0;
   if (!c->lin_cached && !c->lin_listed) return (long long)c->B * n;
-  std::vector<int> act(2 * (size_t)(c->max_iter + 1)), chg((size_t)c->max_iter + 2);
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "ilqr_hip_get_linearized_rollouts: reading the list counts failed"; return -1; }
+  IterationCounts k;
+  if (read_iteration_counts(c, "ilqr_hip_get_linearized_rollouts", "the list counts", &k) != ILQR_OK) return -1;
   long long total = 0;
-  for (int it = 0; it < n; ++it) total += (it > 0 && c->lin_cached) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
+  for (int it = 0; it < n; ++it) total += (it > 0 && c->lin_cached) ? k.chg[it] : (c->lin_listed ? k.act[2 * it] : c->B);
   return total;
 }
-int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->repass = on ? 1 : 0; return ILQR_OK; }
 long long ilqr_hip_get_first_pass_rollouts(ilqr_hip_ctx* c) {
   if (!c) return -1;
   enter(c);
   const int n = c->lin_iterations;
   if (n <= 0) return 0;
-  std::vector<int> act(2 * (size_t)(c->max_iter + 1)), chg((size_t)c->max_iter + 2);
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "ilqr_hip_get_first_pass_rollouts: reading the list counts failed"; return -1; }
+  IterationCounts k;
+  if (read_iteration_counts(c, "ilqr_hip_get_first_pass_rollouts", "the list counts", &k) != ILQR_OK) return -1;
   long long total = 0;
-  for (int it = 0; it < n; ++it) total += ((size_t)it < c->fp_listed.size() && c->fp_listed[it]) ? chg[it] : (c->lin_listed ? act[2 * it] : c->B);
+  for (int it = 0; it < n; ++it) total += recorded(c, it).first_listed ? k.chg[it] : (c->lin_listed ? k.act[2 * it] : c->B);
   return total;
 }
-// took[it] = 1 where iteration it of the last solve enqueued the listed pair and the device took the side-by-side order (word 4 of its gate)
-static int read_listed_taken(ilqr_hip_ctx* c, std::vector<int>& took) {
-  took.assign((size_t)c->max_iter, 0);
-  if (!c->d_lgate || c->listed_dual.empty()) return ILQR_OK;
-  std::vector<int> g(8 * (size_t)c->max_iter);
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(g.data(), c->d_lgate, g.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ILQR_ERR_HIP;
-  for (int it = 0; it < c->max_iter && (size_t)it < c->listed_dual.size(); ++it) took[it] = (c->listed_dual[it] && g[8 * (size_t)it + 4]) ? 1 : 0;
-  return ILQR_OK;
-}
-int ilqr_hip_set_listed_spec(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->listed_spec = on ? 1 : 0; return ILQR_OK; }
 int ilqr_hip_get_listed_spec_iterations(ilqr_hip_ctx* c) {
   if (!c) return -1;
   enter(c);
-  std::vector<int> took;
-  if (read_listed_taken(c, took) != ILQR_OK) { c->err = "ilqr_hip_get_listed_spec_iterations: reading the gate words failed"; return -1; }
+  IterationCounts k;
+  if (read_iteration_counts(c, "ilqr_hip_get_listed_spec_iterations", "the gate words", &k) != ILQR_OK) return -1;
   int total = 0;
-  for (int it = 0; it < c->lin_iterations && it < c->max_iter; ++it) total += took[it];
+  for (int it = 0; it < c->lin_iterations && it < c->max_iter; ++it) total += k.took[it];
   return total;
 }
 int ilqr_hip_get_iteration_lists(ilqr_hip_ctx* c, int iter, int* chg, int* kr, int* counts) {
   if (!c || !counts || iter < 0 || iter >= c->max_iter) return ILQR_ERR_ARG;
   enter(c);
   if (c->lin_iterations <= 0 || !c->S.chg || !c->S.kr || !c->lin_cached) { c->err = "ilqr_hip_get_iteration_lists: the last solve kept no lists"; return ILQR_ERR_STATE; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(&counts[0], c->S.chg_n + iter, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(&counts[1], c->S.kr_n + iter, sizeof(int), hipMemcpyDeviceToHost));
+  IterationCounts k;
+  TRY(read_iteration_counts(c, "ilqr_hip_get_iteration_lists", "the list counts", &k));
+  counts[0] = k.chg[iter]; counts[1] = k.kr[iter];
   if (iter == 0) counts[0] = counts[1] = 0;      // (iteration 0 runs every rollout and reads neither list)
   if (chg && counts[0] > 0) HIPCHK(c, hipMemcpy(chg, c->S.chg + (size_t)iter * c->B, sizeof(int) * (size_t)counts[0], hipMemcpyDeviceToHost));
   if (kr && counts[1] > 0) HIPCHK(c, hipMemcpy(kr, c->S.kr + (size_t)iter * c->B, sizeof(int) * (size_t)counts[1], hipMemcpyDeviceToHost));
@@ -1465,15 +1447,13 @@ int ilqr_hip_get_iteration_orders(ilqr_hip_ctx* c, int* out) {
   enter(c);
   const int n = c->lin_iterations;
   if (n <= 0) return 0;
-  std::vector<int> took, act(2 * (size_t)(c->max_iter + 1));
-  if (read_listed_taken(c, took) != ILQR_OK || (c->S.order_n && hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
-    c->err = "ilqr_hip_get_iteration_orders: reading the gate words failed"; return -1;
-  }
+  IterationCounts k;
+  if (read_iteration_counts(c, "ilqr_hip_get_iteration_orders", "the gate words", &k) != ILQR_OK) return -1;
   for (int it = 0; it < n; ++it) {
-    const int kind = (size_t)it < c->retry_order.size() ? c->retry_order[it] : ilqr_hip_ctx::RETRY_LIST;
-    if (took[it]) out[it] = ILQR_ORDER_LISTED_SPEC;
-    else if (kind == ilqr_hip_ctx::RETRY_TWIN) out[it] = ILQR_ORDER_TWIN;
-    else if (kind == ilqr_hip_ctx::RETRY_DUAL) out[it] = act[2 * it] <= c->knobs.spec_max ? ILQR_ORDER_DUAL_TWIN : ILQR_ORDER_DUAL_SEQUENTIAL;
+    const ilqr::OrderKind kind = recorded(c, it).kind;
+    if (k.took[it]) out[it] = ILQR_ORDER_LISTED_SPEC;
+    else if (kind == ilqr::ORDER_TWIN) out[it] = ILQR_ORDER_TWIN;
+    else if (kind == ilqr::ORDER_DUAL) out[it] = k.act[2 * it] <= c->knobs.spec_max ? ILQR_ORDER_DUAL_TWIN : ILQR_ORDER_DUAL_SEQUENTIAL;
     else out[it] = ILQR_ORDER_SEQUENTIAL;
   }
   return n;
@@ -1484,20 +1464,16 @@ long long ilqr_hip_get_retry_pass_rollouts(ilqr_hip_ctx* c) {
   const int n = c->lin_iterations;
   if (n <= 0) return 0;
   if (c->n_slices > 1 || !c->S.order) return (long long)c->B * n;      // (batch slices keep no lists: the retry launches cover the slice)
-  std::vector<int> act(2 * (size_t)(c->max_iter + 1)), took, chg((size_t)c->max_iter + 1), kr((size_t)c->max_iter + 1);
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(act.data(), c->S.order_n, act.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      read_listed_taken(c, took) != ILQR_OK || hipMemcpy(chg.data(), c->S.chg_n, chg.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      (c->S.kr_n && hipMemcpy(kr.data(), c->S.kr_n, kr.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
-    c->err = "ilqr_hip_get_retry_pass_rollouts: reading the list counts failed"; return -1;
-  }
+  IterationCounts k;
+  if (read_iteration_counts(c, "ilqr_hip_get_retry_pass_rollouts", "the list counts", &k) != ILQR_OK) return -1;
   long long total = 0;
   for (int it = 0; it < n; ++it) {
     // listed side by side: the twin ran for the changed rollouts, the known retries on the solve's own buffers
-    if (took[it]) { total += chg[it] + kr[it]; continue; }
-    const int kind = (size_t)it < c->retry_order.size() ? c->retry_order[it] : ilqr_hip_ctx::RETRY_LIST;
+    if (k.took[it]) { total += k.chg[it] + k.kr[it]; continue; }
+    const ilqr::OrderKind kind = recorded(c, it).kind;
     // side by side the twin pass runs for every active rollout; where both orders were enqueued the device took the twin for a list of at most spec_max
-    const bool twin = kind == ilqr_hip_ctx::RETRY_TWIN || (kind == ilqr_hip_ctx::RETRY_DUAL && act[2 * it] <= c->knobs.spec_max);
-    total += twin ? act[2 * it] : act[2 * it + 1];
+    const bool twin = kind == ilqr::ORDER_TWIN || (kind == ilqr::ORDER_DUAL && k.act[2 * it] <= c->knobs.spec_max);
+    total += twin ? k.act[2 * it] : k.act[2 * it + 1];
   }
   return total;
 }
@@ -1533,7 +1509,7 @@ __attribute__((noinline)) static int enqueue_batch(ilqr_hip_ctx* c, int k) {
   hipStream_t st = c->stream;
   const DevState& S = c->S; const h1::ProblemDev& P = c->P;
   if (k <= 1) {
-    TRY(enqueue_solve(c, S, P, st, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_roll, c->d_shadowx, nullptr, nullptr, c->ev_lin, c->ev_adopt));
+    TRY(enqueue_solve(c, S, P, main_lanes(c), nullptr, nullptr));
   } else {
     TRY(ensure_slices(c, k));
     HIPCHK_S(c, hipEventRecord(c->ev_begin, st));
@@ -1546,7 +1522,7 @@ __attribute__((noinline)) static int enqueue_batch(ilqr_hip_ctx* c, int k) {
       HIPCHK_S(c, hipStreamWaitEvent(sl.st, c->ev_begin, 0));
       const DevState Ss = slice_state(S, (size_t)b0, Bs);
       const h1::ProblemDev Ps = slice_problem(P, b0);
-      TRY(enqueue_solve(c, Ss, Ps, sl.st, sl.st2, sl.st3, sl.fork, sl.join, sl.roll, c->d_shadowx, (stagger && i > 0) ? c->slices[i - 1].lead : nullptr, sl.lead));
+      TRY(enqueue_solve(c, Ss, Ps, slice_lanes(sl), (stagger && i > 0) ? c->slices[i - 1].lead : nullptr, sl.lead));
       HIPCHK_S(c, hipEventRecord(sl.done, sl.st));
       HIPCHK_S(c, hipStreamWaitEvent(st, sl.done, 0));
     }
@@ -1597,7 +1573,7 @@ int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   const int k = slices_wanted(c, c->B);
   c->n_slices = k;
   c->spec_iterations = 0; c->split_iterations = 0;
-  if (c->knobs.spec && k <= 1 && !c->twin && (c->B <= c->knobs.spec_max || (c->early_exit && early_exit_gate(c)) || listed_spec_wanted(c, L, k))) TRY(ensure_twin(c));
+  if (!c->twin && ilqr::resolve_solve_order(solve_settings(c, S, main_lanes(c)), L).twin_wanted) TRY(ensure_twin(c));
   if (L.pack && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
   c->first_aside = c->xbar_rolled && c->rolled_variant == L.rollout && same_dyn(c->rolled_dyn, P.dyn);
   c->xbar_rolled = false;                                   // after this solve xbar is an accepted line-search candidate

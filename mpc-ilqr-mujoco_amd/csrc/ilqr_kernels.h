@@ -58,7 +58,7 @@ struct DevState {
   // round-robin by index: with a scattered selection one engine needs an extra 0.5 ms round of the one-wave-per-SIMD kernel).
   int* order;          // [2 (max_iter + 1)][B]
   int* order_n;        // [2 (max_iter + 1)]
-  // Early continuation (ilqr_capi.hip enqueue_solve): the rollouts whose FIRST line search of iteration it - 1 accepted a step start
+  // Early continuation (solve_order.h SolveOrder::can_split; ilqr_capi.hip enqueue_sequential_iteration): the rollouts whose FIRST line search of iteration it - 1 accepted a step start
   // the linearisation / cost quadratics / re-rollout of iteration it while the others still take their lambda retry.  Group A =
   // the first order_an[it] entries of list (it, 0) (k_control phase 0 fills that list first; the count is snapshot after it), group R =
   // order_r[0 .. order_rn[it]) (filled by phase 1); grp_a / grp_r: the same two sets as per-rollout flags for the kernels that select
@@ -68,7 +68,7 @@ struct DevState {
   int* order_r;        // [B]
   int* order_rn;       // [max_iter + 2]
   int* order_an;       // [max_iter + 2]
-  // Linearisation cache (ilqr_capi.hip enqueue_solve): list it = the rollouts active in iteration it that ACCEPTED a candidate in iteration
+  // Linearisation cache (solve_order.h SolveOrder::cache): list it = the rollouts active in iteration it that ACCEPTED a candidate in iteration
   // it - 1 (k_control / k_control_spec: acc >= 0, the condition under which xbar / ubar are overwritten), in the order of list (it, 0)
   // restricted to them.  The other active rollouts enter iteration it with the nominal trajectory of iteration it - 1 bit for bit: A_t,
   // B_t, lxx~_t, lx_t, lu_t, luu_t depend on that trajectory and the problem data only, so the per-knot kernels of the concurrent region
@@ -79,10 +79,10 @@ struct DevState {
   int* chg_r;          // [B]
   int* chg_rn;         // [max_iter + 2]
   int* chg_an;         // [max_iter + 2]
-  // First-pass skip (ilqr_capi.hip enqueue_solve): chg_f[b] = 1 while rollout b is on list it of the iteration to come (k_control writes it
+  // First-pass skip (solve_order.h SolveOrder::skip_first): chg_f[b] = 1 while rollout b is on list it of the iteration to come (k_control writes it
   // beside the list), for the kernels that select by mask (the candidates' knot costs).  Null: not in use.
   int* chg_f;          // [B]
-  // Listed side-by-side order (ilqr_capi.hip enqueue_solve): kr list it = the rollouts active in iteration it whose two line searches of
+  // Listed side-by-side order (solve_order.h SolveOrder::listed; ilqr_capi.hip enqueue_listed_pair): kr list it = the rollouts active in iteration it whose two line searches of
   // iteration it - 1 both failed and whose lambda is below its cap (min(10 lambda, 1e-3) != lambda): their first pass of it is skipped and
   // fails by construction, their retry is known before the iteration starts.  Written by the control kernel that closes iteration it - 1,
   // compacted like chg; disjoint from chg by construction (chg: accepted, kr: failed).  ls_list: chg ++ kr of the iteration at hand, ls_kind[b]:

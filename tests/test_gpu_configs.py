@@ -279,7 +279,7 @@ def test_position_rows_of_the_jacobians_have_no_slot_in_the_operand_layout_and_a
 
 def test_early_exit_gate_stops_launching_and_changes_nothing():
     """With the convergence exit on, the host follows the device-side count of active rollouts and stops enqueuing iterations
-    once the batch is done (ilqr_capi.hip enqueue_solve); the compacted work lists (DevState::order) feed the Riccati and
+    once the batch is done (solve_order.h SolveOrder::gate; ilqr_capi.hip enqueue_solve, publish_active); the compacted work lists (DevState::order) feed the Riccati and
     line-search launches.  Same traces, iteration counts, gains and trajectories with the gate off, and against the oracle."""
     B = 6
     prob, x0, ui = standing(B, seed=41)

@@ -167,9 +167,9 @@ def test_stance_constrained_step_matches_oracle_on_the_kept_cases(mode):
 
 def test_operand_layout_jacobians_inside_a_solve_match_the_stage_api_and_oracle_ad():
     """B = 5, N = 5: 25 knots, so the two-knot kernel has an odd item count and a pair that crosses from one rollout into the next.
-    One iteration, no convergence exit: ilqr_capi.hip enqueue_solve linearises once, in iteration 0, the nominal trajectory -- the cold
-    start's rollout of u_init from x0, which the solve re-rolls to the same bits -- and starts no later iteration's linearisation
-    (split_next needs iter + 1 < max_iter); the line search then replaces xbar / ubar by the accepted candidate.  So the Jacobians a
+    One iteration, no convergence exit: ilqr_capi.hip enqueue_solve linearises once, in iteration 0 (enqueue_region), the nominal trajectory
+    -- the cold start's rollout of u_init from x0, which the solve re-rolls to the same bits (solve_order.h rolls_aside) -- and starts no later
+    iteration's linearisation (enqueue_sequential_iteration: split_next needs iter + 1 < max_iter); the line search then replaces xbar / ubar by the accepted candidate.  So the Jacobians a
     solve leaves behind (operand layout, converted back by the getter) belong to the trajectory read BEFORE the solve."""
     B = N = 5
     rng = np.random.default_rng(dc.SEED + 3)
