@@ -182,6 +182,53 @@ int ilqr_hip_get_al_bounds(ilqr_hip_ctx* ctx, double* bounds /*[B][76]*/);
    hi = range[1] - margin (...), the doubles the kernels form.  margin = 0: the model's joint and control ranges.  Host only: no GPU, no
    handle.  0 <= margin < 0.5 and a non-null pointer, else ILQR_ERR_ARG. */
 int ilqr_hip_al_default_bounds(double margin, double* bounds /*[76]*/);
+/* Augmented-Lagrangian bounds on the other 28 non-quaternion state coordinates, the "box coordinates" k = 0..27: pelvis position in the
+   world (k = 0..2, state slots 0..2), pelvis linear velocity in the world (k = 3..5) and angular velocity in the body (k = 6..8), the 19
+   joint velocities in the order of u (k = 9..27); k >= 3 is state slot 23 + k (ilqr_hip_al_state_slot).  A record is ILQR_AL_STATE_BOUNDS =
+   56 doubles, lo[28] then hi[28]; n_sets is 1 (every rollout reads the one record) or the batch (rollout b reads record b).  The model has no
+   ranges for these coordinates: there is no default table, and without a table nothing here is constrained.
+   A third family beside the hinges and the actuators of ilqr_hip_set_augmented_lagrangian, rule for rule: the constraints x_slot - hi and
+   lo - x_slot at the knots t = 0..N with the term phi per constraint; knot 0 carries the cost term, keeps zero multipliers and is left out of
+   the violation (x_0 is given); one penalty rho_state per rollout, starting at rho_state0 and capped at rho_max_factor rho_state0 (the factor
+   of the installation); after each inner solve mu <- max(0, mu + rho_state c) and viol_state = the largest max(0, c) over coordinates, sides
+   and knots 1..N.  With a table installed a rollout is done only when viol_joint <= tol_joint, viol_ctrl <= tol_ctrl AND viol_state <=
+   tol_state; otherwise all three penalties grow.  A done rollout is frozen; the convergence exit, the early-exit gate and the rounds work off
+   that one done flag as described above.  ilqr_hip_al_update updates this family too.  The getters above keep their shapes and meaning.
+   A lower bound may be -inf and an upper bound +inf: that side is switched off as in ilqr_hip_set_al_bounds (c = -inf, term -mu^2 / (2 rho),
+   zero gradient and curvature, multiplier driven to 0, violation 0).  The table acts on the COST only: dynamics, plant and score are untouched.
+   It works with or without a joint / torque bounds table.
+   ILQR_ERR_STATE while no augmented Lagrangian is installed (every handle call below).  ILQR_ERR_ARG: a null pointer, n_sets not 1 or the
+   batch, a NaN, lo > hi, lo == +inf, hi == -inf, rho_state0 <= 0 or not finite, tol_state < 0; everything is checked before the handle is
+   touched, a refused call leaves a previously installed table as it was.  Allocates the second multiplier store on first use ([B] records of
+   16 + 64 (N + 1) doubles: h1_cost_dev.h).  Installing where no table was installed zeroes the state multipliers; replacing a table keeps
+   them; rho_state = rho_state0 either way.  Uploads and synchronises the handle's stream.
+   The table survives the cold and warm initialisers, ilqr_hip_set_al_multipliers and a repeated ilqr_hip_set_augmented_lagrangian;
+   ilqr_hip_clear_augmented_lagrangian drops it.  The cold initialisers zero the state multipliers and reset rho_state; the warm ones shift
+   the state multipliers by the knots the trajectory is shifted by (zero tail, knot 0 zero) and reset rho_state.  The refusals of
+   ilqr_hip_set_augmented_lagrangian (cross-check families, weight sets) stay as they are. */
+#define ILQR_AL_STATE_COORDS 28
+#define ILQR_AL_STATE_BOUNDS 56
+int ilqr_hip_set_al_state_bounds(ilqr_hip_ctx* ctx, const double* bounds /*[n_sets][56]*/, int n_sets, double rho_state0, double tol_state);
+/* No state family any more (same kernels and kernel arguments as a handle that never had a table). */
+int ilqr_hip_clear_al_state_bounds(ilqr_hip_ctx* ctx);
+/* 0: no table installed, else the n_sets of the installed table (1 or the batch); -1 for a null handle */
+int ilqr_hip_num_al_state_bound_sets(const ilqr_hip_ctx* ctx);
+/* The record each rollout is solved with: a one-record table expanded; without a table lo = -inf, hi = +inf in every row. */
+int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* ctx, double* bounds /*[B][56]*/);
+/* The state multipliers, (lower, upper) per box coordinate; zeros without a table. */
+int ilqr_hip_get_al_state_multipliers(ilqr_hip_ctx* ctx, double* mu /*[B][N+1][28][2]*/);
+/* Either pointer may be NULL (that part stays).  Multipliers >= 0, penalties > 0, else ILQR_ERR_ARG; knot-0 entries are stored as zero.
+   ILQR_ERR_STATE without a table. */
+int ilqr_hip_set_al_state_multipliers(ilqr_hip_ctx* ctx, const double* mu /*[B][N+1][28][2]*/, const double* rho /*[B]*/);
+/* rho_state as the store holds it; zeros without a table */
+int ilqr_hip_get_al_state_penalties(ilqr_hip_ctx* ctx, double* rho /*[B]*/);
+/* viol_state of the nominal trajectory at the last update; zeros without a table (the done flags: ilqr_hip_get_al_violation) */
+int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* ctx, double* viol /*[B]*/);
+/* Per round of the last solve and rollout: viol_state and the rho_state the round ran with.  NaN where ilqr_hip_get_al_trace has NaN, and
+   everywhere without a table. */
+int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][2]*/);
+/* The state slot of box coordinate k; -1 outside 0..27.  Host only: no GPU, no handle. */
+int ilqr_hip_al_state_slot(int k);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N

@@ -119,6 +119,30 @@ class iLQR {
     chk(ilqr_hip_get_al_bounds(ctx_, out.data()));
     return out;
   }
+  // bounds on pelvis position, pelvis velocity and joint velocities as a third family of those limits (ilqr_hip_set_al_state_bounds): row-major
+  // [n_sets][ILQR_AL_STATE_BOUNDS] = lo[28], hi[28], n_sets = 1 or the batch, -inf / +inf switch a side off; getAlStateBounds: the record each
+  // rollout is solved with; getAlStateMultipliers [batch][N+1][28][2] (lower, upper); getAlStateViolation [batch]
+  void setAlStateBounds(const std::vector<double>& bounds, int n_sets, double rho_state0, double tol_state) {
+    if (n_sets <= 0 || bounds.size() != (size_t)n_sets * ILQR_AL_STATE_BOUNDS) chk(ILQR_ERR_ARG);
+    chk(ilqr_hip_set_al_state_bounds(ctx_, bounds.data(), n_sets, rho_state0, tol_state));
+  }
+  void clearAlStateBounds() { chk(ilqr_hip_clear_al_state_bounds(ctx_)); }
+  int numAlStateBoundSets() const { return ilqr_hip_num_al_state_bound_sets(ctx_); }
+  std::vector<double> getAlStateBounds() {
+    std::vector<double> out((size_t)ilqr_hip_batch(ctx_) * ILQR_AL_STATE_BOUNDS);
+    chk(ilqr_hip_get_al_state_bounds(ctx_, out.data()));
+    return out;
+  }
+  std::vector<double> getAlStateMultipliers() {
+    std::vector<double> out((size_t)ilqr_hip_batch(ctx_) * (ilqr_hip_horizon(ctx_) + 1) * ILQR_AL_STATE_BOUNDS);
+    chk(ilqr_hip_get_al_state_multipliers(ctx_, out.data()));
+    return out;
+  }
+  std::vector<double> getAlStateViolation() {
+    std::vector<double> out((size_t)ilqr_hip_batch(ctx_));
+    chk(ilqr_hip_get_al_state_violation(ctx_, out.data()));
+    return out;
+  }
   void setGravity(double gx, double gy, double gz) { chk(ilqr_hip_set_gravity(ctx_, gx, gy, gz)); }
   void setContactSchedule(const std::vector<int>& stance /*[N+1][2]*/) { chk(ilqr_hip_set_contact_schedule(ctx_, stance.data(), 1)); }
   // contact row: ILQR_CONTACT_NONE (default) or ILQR_CONTACT_RIGID_STANCE on the scheduled feet

@@ -3,8 +3,11 @@
 // quad_kernels.hip and h1_cost_dev.h, which also states the layout of the multiplier store.
 //   k_al_update        multiplier update, violations, done flag, penalty growth, trace row and the count of rollouts left, one pass over
 //                      the nominal trajectory, one wave per rollout; <true>: the bounds are rollout b's record of the bounds table
-//                      (ilqr_hip_set_al_bounds), <false> the model's ranges at the installed margin
+//                      (ilqr_hip_set_al_bounds), <false> the model's ranges at the installed margin; <., true>: and the state family
+//                      (ilqr_hip_set_al_state_bounds: the second store, AlDev::sstore) -- a third loop, a third maximum, the done rule over
+//                      all three families, the growth of rho_state and the state trace row
 //   k_al_shift         warm-start shift of the multipliers by the knots the trajectory is shifted by (zero tail; shift > N: all zero), penalties reset
+//   k_al_state_shift   the same for the state family's store: every column shifts as a hinge column does (knot 0 stays zero)
 //   k_solve_begin_al   k_solve_begin with active = !done: the prologue of the rounds >= 2 of a solve with the convergence exit
 // Every rule is per rollout: nothing here reads another rollout's data, and the one shared word (AlDev::left) is a count.
 // Compiled as the tail of ilqr_kernels.hip, beside k_solve_begin and k_warm_shift (a code object of their own for three small kernels cost
@@ -23,7 +26,7 @@ __device__ __forceinline__ double wave_max(double v) {
 
 // Constraint e of a knot's record, e in [0, 38): side = e / 19 (0 lower, 1 upper bound), coordinate e % 19.  The multiplier sits at
 // base + e for both families (AL_JHI = AL_JLO + 19, AL_UHI = AL_ULO + 19).
-template <bool TABLE>
+template <bool TABLE, bool STATE>
 __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round, int masked) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -64,17 +67,40 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
       *mu = s > 0.0 ? s : 0.0;
     }
   }
+  // box coordinates (STATE), knots 1..N as the hinges: entry r of a knot's record is side r / 28 of coordinate r % 28 (ALS_HI = ALS_LO + 28)
+  double vs = 0.0, rho_s = 0.0;
+  double* srec = nullptr;
+  if constexpr (STATE) {
+    srec = A.sstore + (long)b * A.sstride;
+    rho_s = srec[ALS_RHO];
+    const double* sb = A.sbounds + (long)b * A.sbounds_stride;
+    for (int e = lane; e < N * 2 * ALS_COORDS; e += 64) {
+      const int t = 1 + e / (2 * ALS_COORDS), r = e % (2 * ALS_COORDS), side = r / ALS_COORDS, k = r % ALS_COORDS;
+      const double v = xb[t * H1_NX + als_slot(k)];
+      const double c = side ? v - sb[ALSB_HI + k] : sb[ALSB_LO + k] - v;
+      vs = c > vs ? c : vs;
+      if (!was_done) {
+        double* mu = srec + ALS_HDR + (long)t * ALS_KNOT + ALS_LO + r;
+        const double s = *mu + rho_s * c;
+        *mu = s > 0.0 ? s : 0.0;
+      }
+    }
+  }
   vj = wave_max(vj); vc = wave_max(vc);
+  if constexpr (STATE) vs = wave_max(vs);
   if (lane != 0) return;
   A.viol[2 * b] = vj; A.viol[2 * b + 1] = vc;
+  if constexpr (STATE) A.sviol[b] = vs;
   if (was_done && masked) return;          // (the round did not run for this rollout: its trace row stays NaN)
   double* tr = A.trace + ((size_t)round * S.B + b) * 5;
   tr[0] = vj; tr[1] = vc; tr[2] = rho_j; tr[3] = rho_c; tr[4] = (double)iters;
+  if constexpr (STATE) { double* ts = A.strace + ((size_t)round * S.B + b) * 2; ts[0] = vs; ts[1] = rho_s; }
   if (was_done) return;
-  if (vj <= A.tol_joint && vc <= A.tol_ctrl) { A.done[b] = 1; return; }
+  if (vj <= A.tol_joint && vc <= A.tol_ctrl && (!STATE || vs <= A.tol_state)) { A.done[b] = 1; return; }
   const double gj = rho_j * A.growth, gc = rho_c * A.growth;
   rec[AL_RHO_JOINT] = gj < A.rho_joint_max ? gj : A.rho_joint_max;
   rec[AL_RHO_CTRL] = gc < A.rho_ctrl_max ? gc : A.rho_ctrl_max;
+  if constexpr (STATE) { const double gs = rho_s * A.growth; srec[ALS_RHO] = gs < A.rho_state_max ? gs : A.rho_state_max; }
   atomicAdd(A.left + round, 1);
 }
 
@@ -92,6 +118,21 @@ __global__ void __launch_bounds__(128) k_al_shift(AlDev A, int N, int shift, dou
     const bool keep = joint ? (t >= 1 && ts <= N) : (ts <= N - 1);
     const double v = k[(ts <= N ? ts : (long)N) * AL_KNOT + e];      // (index clamped into the record, masked below)
     k[(long)t * AL_KNOT + e] = keep ? v : 0.0;
+  }
+}
+
+// The state family's store under the same walk: every column is a box coordinate's bound at the knots 0..N, kept for 1 <= t and t + shift <= N.
+__global__ void __launch_bounds__(64) k_al_state_shift(AlDev A, int N, int shift) {
+  const int b = blockIdx.x, e = threadIdx.x;
+  double* rec = A.sstore + (long)b * A.sstride;
+  if (e == 0) { rec[ALS_RHO] = A.rho_state0; A.sviol[b] = 0.0; }
+  if (e >= 2 * ALS_COORDS) return;
+  double* k = rec + ALS_HDR + ALS_LO;
+  for (int t = 0; t <= N; ++t) {
+    const long ts = (long)t + shift;
+    const bool keep = t >= 1 && ts <= N;
+    const double v = k[(ts <= N ? ts : (long)N) * ALS_KNOT + e];      // (index clamped into the record, masked below)
+    k[(long)t * ALS_KNOT + e] = keep ? v : 0.0;
   }
 }
 
@@ -128,11 +169,13 @@ __global__ void __launch_bounds__(64) k_solve_begin_al(DevState S, const int* do
 }
 
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st) {
-  if (A.bounds) hipLaunchKernelGGL(k_al_update<true>, dim3(S.B), dim3(64), 0, st, S, A, round, masked);
-  else hipLaunchKernelGGL(k_al_update<false>, dim3(S.B), dim3(64), 0, st, S, A, round, masked);
+  if (A.sbounds && A.bounds) hipLaunchKernelGGL((k_al_update<true, true>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);      // (a state table brings a bounds record with it)
+  else if (A.bounds) hipLaunchKernelGGL((k_al_update<true, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);
+  else hipLaunchKernelGGL((k_al_update<false, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);
 }
 void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st) {
   hipLaunchKernelGGL(k_al_shift, dim3(B), dim3(128), 0, st, A, N, shift, rho_joint, rho_ctrl);
+  if (A.sbounds) hipLaunchKernelGGL(k_al_state_shift, dim3(B), dim3(64), 0, st, A, N, shift);
 }
 void launch_solve_begin_al(const DevState& S, const int* done, hipStream_t st) { hipLaunchKernelGGL(k_solve_begin_al, dim3(1), dim3(64), 0, st, S, done); }
 

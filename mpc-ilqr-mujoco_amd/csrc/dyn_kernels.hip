@@ -231,7 +231,9 @@ __global__ void __launch_bounds__(64) k_line_search_r(DevState S, ProblemDev P, 
 // address of the last rollout's record, never one outside the table)
 // AL (h1_cost_dev.h AL_OFF / AL_MODEL / AL_TABLE): the augmented-Lagrangian terms of the lane's own rollout and knot (ProblemDev::al) in place
 // of the plain penalties; AL_TABLE with the bounds of the lane's own rollout (ProblemDev::alb: the knots and the eight candidates of a
-// rollout read the same five lines)
+// rollout read the same five lines).  The state family (ilqr_hip_set_al_state_bounds) is not an instantiation of this kernel: with its 56 terms
+// inlined the kernel needs 268 + 12 registers and drops to one wave per SIMD (docs/KERNEL_RESOURCES_AL_STATE.md); k_al_state_knot_cost below adds
+// them to the knot costs this kernel has written.
 template <bool WS, int AL>
 __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate) {
   if (gate && *gate == 0) return;
@@ -278,6 +280,22 @@ __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P,
   const double c = knot_cost_w<WS, AL>(P, b, t, x, t < N ? u : (const double*)nullptr, ComReg());
   if (act) S.cand_knot[((cand << oshift) * (N + 1)) + t] = c;
 }
+// The state family's terms of the same knots, added to the knot costs k_traj_knot_cost has written (the same stream: behind it, ahead of
+// k_traj_cost_sum): one lane per (candidate, knot) under the same numbering, selection and gate.  al_state_term is the last term of the knot
+// cost either way -- c + term, one rounding -- so the sum is the one an instantiation of k_traj_knot_cost would have stored.  The lane reads its
+// 28 coordinates from the row itself (224 of its 408 bytes) and the four lines of multipliers and the four of bounds of its rollout and knot.
+__global__ void __launch_bounds__(64) k_al_state_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, int cshift, int oshift, const int* gate) {
+  if (gate && *gate == 0) return;
+  const int N = S.N;
+  const long total = ((long)S.B << cshift) * (N + 1);
+  const long idx = (long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= total) return;
+  const int t = (int)(idx % (N + 1));
+  const long cand = idx / (N + 1);
+  const int b = (int)(cand >> cshift);
+  if (!sel(S, b, mode)) return;
+  S.cand_knot[((cand << oshift) * (N + 1)) + t] += al_state_term(P, b, t, xsrc + idx * H1_NX);
+}
 __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int cshift, int oshift, double* cost_out) {
   const int cand = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = cand >> cshift;
@@ -293,6 +311,7 @@ void launch_cand_costs(const DevState& S, const ProblemDev& P, int mode, hipStre
   else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, 3, 0, gate);
   if (with_sum) hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)(((long)S.B * 8 + 63) / 64)), dim3(64), 0, st, S, mode, 3, 0, S.cand_cost);
 }
 // computeTotalCost of the nominal trajectories (S.xbar, S.ubar) into cost_out[B], same kernels, same summation order
@@ -302,6 +321,7 @@ void launch_nominal_costs(const DevState& S, const ProblemDev& P, int mode, doub
   else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, 0, 3, (const int*)nullptr);
   hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)((S.B + 63) / 64)), dim3(64), 0, st, S, mode, 0, 3, cost_out);
 }
 

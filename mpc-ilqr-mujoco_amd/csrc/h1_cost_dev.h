@@ -48,6 +48,11 @@ struct ProblemDev {
   // per-rollout bounds of those limits (ilqr_hip_set_al_bounds): null = the model's ranges shrunk by al_margin; else one ALB_STRIDE record per
   // set (layout below), stride 0 when one record serves every rollout, and al_margin is not read.  Appended: nothing above moves
   const double* alb;         long alb_stride;
+  // augmented-Lagrangian bounds on the other 28 non-quaternion state coordinates (ilqr_hip_set_al_state_bounds): alsb null = none; else als
+  // the second multiplier store, one record of als_stride doubles per rollout, and alsb one ALSB_STRIDE record of bounds per set, stride 0
+  // when one record serves every rollout (layouts below).  Read while `al` is installed only.  Appended: nothing above moves
+  const double* als;         long als_stride;
+  const double* alsb;        long alsb_stride;
 };
 // The multiplier store, in doubles.  Rollout b's record: one 128-byte line of scalars (AL_RHO_JOINT, AL_RHO_CTRL, the rest padding), then one
 // record of AL_KNOT = 80 doubles (five whole lines) per knot t = 0..N: the hinges' multipliers of the lower bounds, of the upper bounds, two
@@ -63,9 +68,25 @@ inline long al_record_doubles(int N) { return AL_HDR + (long)AL_KNOT * (N + 1); 
 // positive), so c = -inf, max(0, mu + rho c) = 0 and no 0 * inf or inf - inf arises.
 enum { ALB_JLO = 0, ALB_JHI = H1_NJ, ALB_ULO = 2 * H1_NJ, ALB_UHI = 2 * H1_NJ + H1_NU, ALB_FIELDS = 2 * H1_NJ + 2 * H1_NU, ALB_STRIDE = (ALB_FIELDS + 15) / 16 * 16 };
 static_assert(ALB_FIELDS == 76 && ALB_STRIDE == 80, "bounds record: 76 doubles in five 128-byte lines");
+// The state family: box coordinate k in [0, 28) is state slot k (pelvis position) for k < 3, else slot 23 + k (pelvis linear and angular
+// velocity 26..31, joint velocities 32..50).  Its multiplier store, in doubles: rollout b's record is one 128-byte line of scalars (ALS_RHO,
+// the rest padding), then one record of ALS_KNOT = 64 doubles (four whole lines) per knot t = 0..N: the multipliers of the 28 lower bounds, of
+// the 28 upper bounds, eight doubles of padding.  Knot-major as the store above, for the same two readers.  Its bounds table: one record per
+// set, lo[28] then hi[28] (the order of ilqr_hip_set_al_state_bounds) padded to four lines, indexed by the rollout b; -inf / +inf as above.
+enum { ALS_COORDS = 28, ALS_RHO = 0, ALS_HDR = 16, ALS_LO = 0, ALS_HI = ALS_COORDS, ALS_KNOT = 64 };
+enum { ALSB_LO = 0, ALSB_HI = ALS_COORDS, ALSB_FIELDS = 2 * ALS_COORDS, ALSB_STRIDE = (ALSB_FIELDS + 15) / 16 * 16 };
+static_assert(ALS_HI + ALS_COORDS <= ALS_KNOT && ALS_KNOT % 16 == 0 && ALS_HDR % 16 == 0 && ALSB_STRIDE == 64, "state records: whole 128-byte lines");
+static_assert(H1_NX == 51 && H1_NQ == 26, "box coordinates: slots 0..2 and 26..50");
+inline long als_record_doubles(int N) { return ALS_HDR + (long)ALS_KNOT * (N + 1); }
+constexpr int als_slot(int k) { return k < 3 ? k : 23 + k; }
 // Where the limit terms take their bounds from: AL_MODEL the model's ranges at ProblemDev::al_margin, AL_TABLE rollout b's record of
 // ProblemDev::alb.  (AL_OFF: the plain penalties.)  A template axis, so that the paths without a table keep their machine code.
-enum { AL_OFF = 0, AL_MODEL = 1, AL_TABLE = 2 };
+// AL_TABLE_STATE: AL_TABLE with the state family (ProblemDev::als, alsb) on top.  There is no AL_MODEL_STATE: while a state table is
+// installed without a joint / torque table, ProblemDev::alb points at one record of the model's bounds at the installed margin, the same
+// doubles al_bounds forms (ilqr_capi.hip al_point_bounds) -- a second state instantiation of k_cost_quadratics costs the library 29 KB.
+enum { AL_OFF = 0, AL_MODEL = 1, AL_TABLE = 2, AL_TABLE_STATE = 3 };
+constexpr bool al_table(int AL) { return AL == AL_TABLE || AL == AL_TABLE_STATE; }
+constexpr bool al_state(int AL) { return AL == AL_TABLE_STATE; }
 // Bounds lo = r0 + m (r1 - r0), hi = r1 - m (r1 - r0), each operation rounded once (no contraction): every kernel and the host restatement
 // of the tests then hold the same two doubles
 DEVFN void al_bounds(const double* range, double m, double& lo, double& hi) {
@@ -93,7 +114,7 @@ DEVFN double al_joint_term(const ProblemDev& P, int b, int t, const double* x) {
 #pragma unroll
   for (int i = 0; i < H1_NJ; ++i) {
     double lo, hi;
-    if constexpr (AL == AL_TABLE) { lo = bd[ALB_JLO + i]; hi = bd[ALB_JHI + i]; } else al_bounds(H1_JRANGE[i], P.al_margin, lo, hi);
+    if constexpr (al_table(AL)) { lo = bd[ALB_JLO + i]; hi = bd[ALB_JHI + i]; } else al_bounds(H1_JRANGE[i], P.al_margin, lo, hi);
     const double q = x[7 + i];
     c += al_phi2(q - hi, k[AL_JHI + i], rho);
     c += al_phi2(lo - q, k[AL_JLO + i], rho);
@@ -110,9 +131,25 @@ DEVFN double al_ctrl_term(const ProblemDev& P, int b, int t, const double* u) {
 #pragma unroll
   for (int i = 0; i < H1_NU; ++i) {
     double lo, hi;
-    if constexpr (AL == AL_TABLE) { lo = bd[ALB_ULO + i]; hi = bd[ALB_UHI + i]; } else al_bounds(H1_CTRLRANGE[i], P.al_margin, lo, hi);
+    if constexpr (al_table(AL)) { lo = bd[ALB_ULO + i]; hi = bd[ALB_UHI + i]; } else al_bounds(H1_CTRLRANGE[i], P.al_margin, lo, hi);
     c += al_phi2(u[i] - hi, k[AL_UHI + i], rho);
     c += al_phi2(lo - u[i], k[AL_ULO + i], rho);
+  }
+  return c / (2.0 * rho);
+}
+// the state family's terms of knot t of rollout b, every knot (the terminal one included); added to the knot cost by a kernel of its own
+// (dyn_kernels.hip k_al_state_knot_cost), not by knot_cost_w
+DEVFN double al_state_term(const ProblemDev& P, int b, int t, const double* x) {
+  const double* r = P.als + (long)b * P.als_stride;
+  const double* bd = P.alsb + (long)b * P.alsb_stride;
+  const double rho = r[ALS_RHO];
+  const double* k = r + ALS_HDR + (long)t * ALS_KNOT;
+  double c = 0.0;
+#pragma unroll
+  for (int i = 0; i < ALS_COORDS; ++i) {
+    const double v = x[als_slot(i)];
+    c += al_phi2(v - bd[ALSB_HI + i], k[ALS_HI + i], rho);
+    c += al_phi2(bd[ALSB_LO + i] - v, k[ALS_LO + i], rho);
   }
   return c / (2.0 * rho);
 }

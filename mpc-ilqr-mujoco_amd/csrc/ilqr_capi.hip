@@ -105,6 +105,15 @@ struct ilqr_hip_ctx {
   double* d_alb = nullptr;
   int n_alb = 0;                          // 0: the model's ranges at the installed margin, else the installed table's n_sets
   std::vector<double> h_alb;
+  // state family of the augmented Lagrangian (ilqr_hip_set_al_state_bounds): installed while P.alsb points at d_alsb [B][ALSB_STRIDE]; d_als
+  // [B][als_record_doubles(N)] its multiplier store, d_als_viol [B], d_als_trace [al_trace_cap][B][2] (the last two allocated with their
+  // joint / torque counterparts); h_alsb the installed records as the caller gave them, [n_alsb][56]
+  // d_alb_model [ALB_STRIDE]: the model's bounds at the installed margin as one record, what P.alb points at while a state table is installed
+  // without a bounds table (al_point_bounds) -- the state instantiations take every bound from a record
+  double *d_als = nullptr, *d_alsb = nullptr, *d_als_viol = nullptr, *d_als_trace = nullptr, *d_alb_model = nullptr;
+  int n_alsb = 0;
+  double als_rho0 = 0.0, als_tol = 0.0;
+  std::vector<double> h_alsb;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
@@ -324,6 +333,20 @@ static inline int enter_launching(ilqr_hip_ctx* c) {
   if (c->P.al) if (const char* why = al_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   return ILQR_OK;
 }
+// Where the joint / torque family takes its bounds from: the installed table; without one null (the model's ranges at P.al_margin, formed in
+// the kernels) -- or, while a state table is installed, one record of those same doubles (h1host::al_default_bounds)
+static int al_point_bounds(ilqr_hip_ctx* c) {
+  if (c->n_alb) { c->P.alb = c->d_alb; c->P.alb_stride = c->n_alb == 1 ? 0 : (long)h1::ALB_STRIDE; return ILQR_OK; }
+  c->P.alb = nullptr; c->P.alb_stride = 0;
+  if (!c->P.al || !c->n_alsb) return ILQR_OK;
+  double rec[h1::ALB_STRIDE] = {0};
+  h1host::al_default_bounds(c->P.al_margin, rec);
+  if (!c->d_alb_model) TRY(dalloc(c, &c->d_alb_model, (size_t)h1::ALB_STRIDE));
+  HIPCHK(c, hipMemcpyAsync(c->d_alb_model, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->P.alb = c->d_alb_model;
+  return ILQR_OK;
+}
 static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   ilqr::AlDev A{};
   A.store = c->d_al; A.stride = h1::al_record_doubles(c->N);
@@ -331,6 +354,10 @@ static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   A.rho_joint_max = c->al_rho0[0] * c->al_max_factor; A.rho_ctrl_max = c->al_rho0[1] * c->al_max_factor;
   A.viol = c->d_al_viol; A.done = c->d_al_done; A.trace = c->d_al_trace; A.left = c->d_al_left;
   A.bounds = c->P.alb; A.bounds_stride = c->P.alb_stride;
+  A.sbounds = c->P.alsb; A.sbounds_stride = c->P.alsb_stride;
+  A.sstore = c->d_als; A.sstride = h1::als_record_doubles(c->N);
+  A.rho_state0 = c->als_rho0; A.rho_state_max = c->als_rho0 * c->al_max_factor; A.tol_state = c->als_tol;
+  A.sviol = c->d_als_viol; A.strace = c->d_als_trace;
   return A;
 }
 // the multipliers follow the trajectory: shifted by the knots it is shifted by (shift > N: a cold start, all zero), penalties back to their
@@ -463,6 +490,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   P.x_ref_stride = P.u_ref_stride = P.com_ref_stride = P.stance_stride = P.ee_ref_stride = P.com_vel_ref_stride = 0;
   P.wsets = nullptr; P.wsets_stride = 0;
   P.al = nullptr; P.al_stride = 0; P.al_margin = 0.0; P.alb = nullptr; P.alb_stride = 0;
+  P.als = nullptr; P.als_stride = 0; P.alsb = nullptr; P.alsb_stride = 0;
   // default: stance everywhere (RobotUtils::isStance default, robot_utils.cpp:494-504), lambda = 1e-6 (ilqr.cpp:16)
   std::vector<int> ones((N + 1) * 2, 1);
   hipMemcpyAsync(c->d_stance, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
@@ -486,7 +514,8 @@ int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_alb, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_alb, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left,
+                  c->d_als, c->d_alsb, c->d_als_viol, c->d_als_trace, c->d_alb_model};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->h_al_left) (void)hipHostFree(c->h_al_left);
   if (c->ev_al) hipEventDestroy(c->ev_al);
@@ -571,21 +600,25 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
   if (c->P.wsets) { c->err = "the augmented Lagrangian together with weight sets is not supported: ilqr_hip_clear_weight_sets first"; return ILQR_ERR_UNSUPPORTED; }
   const size_t B = c->B;
   if (!c->d_al) { TRY(dalloc(c, &c->d_al, B * (size_t)h1::al_record_doubles(c->N))); TRY(dalloc(c, &c->d_al_viol, B * 2)); TRY(dalloc(c, &c->d_al_done, B)); }
+  if (!c->d_als_viol) TRY(dalloc(c, &c->d_als_viol, B));
   if (!c->ev_al) HIPCHK_S(c, hipEventCreateWithFlags(&c->ev_al, hipEventDisableTiming));
   if (rounds > c->al_trace_cap) {
     HIPCHK_S(c, hipStreamSynchronize(c->stream));
     if (c->d_al_trace) (void)hipFree(c->d_al_trace);
     if (c->d_al_left) (void)hipFree(c->d_al_left);
     if (c->h_al_left) (void)hipHostFree(c->h_al_left);
-    c->d_al_trace = nullptr; c->d_al_left = nullptr; c->h_al_left = nullptr; c->al_trace_cap = 0;
-    TRY(dalloc(c, &c->d_al_trace, (size_t)rounds * B * 5)); TRY(dalloc(c, &c->d_al_left, (size_t)rounds));
+    if (c->d_als_trace) (void)hipFree(c->d_als_trace);
+    c->d_al_trace = nullptr; c->d_al_left = nullptr; c->h_al_left = nullptr; c->d_als_trace = nullptr; c->al_trace_cap = 0;
+    TRY(dalloc(c, &c->d_al_trace, (size_t)rounds * B * 5)); TRY(dalloc(c, &c->d_al_left, (size_t)rounds)); TRY(dalloc(c, &c->d_als_trace, (size_t)rounds * B * 2));
     HIPCHK_S(c, hipHostMalloc((void**)&c->h_al_left, sizeof(int) * (size_t)rounds, hipHostMallocDefault));
     c->al_trace_cap = rounds;
   }
   c->al_rounds = rounds; c->al_rho0[0] = rho_joint0; c->al_rho0[1] = rho_ctrl0; c->al_growth = growth; c->al_max_factor = rho_max_factor;
   c->al_tol[0] = tol_joint; c->al_tol[1] = tol_ctrl; c->al_rounds_run = 0;
   c->P.al = c->d_al; c->P.al_stride = h1::al_record_doubles(c->N); c->P.al_margin = margin;
+  TRY(al_point_bounds(c));      // (a state table without a bounds table: the model's record at the new margin)
   HIPCHK_S(c, hipMemsetAsync(c->d_al_trace, 0xFF, (size_t)rounds * B * 5 * sizeof(double), c->stream));      // (all bits set: NaN)
+  HIPCHK_S(c, hipMemsetAsync(c->d_als_trace, 0xFF, (size_t)rounds * B * 2 * sizeof(double), c->stream));
   al_follow_initialize(c, c->N + 1);
   HIPCHK_S(c, hipGetLastError());
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
@@ -595,6 +628,7 @@ int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al_rounds = 0; c->al_rounds_run = 0;      // (the buffers stay with the handle for the next call)
   c->P.alb = nullptr; c->P.alb_stride = 0; c->n_alb = 0;      // (the bounds table goes with it: a fresh installation starts on the model's ranges)
+  c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0;      // (and the state family's)
   return ILQR_OK;
 }
 int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al_rounds : 0) : -1; }
@@ -626,15 +660,15 @@ int ilqr_hip_set_al_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) {
   HIPCHK(c, hipMemcpyAsync(c->d_alb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->h_alb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_BOUNDS);
-  c->P.alb = c->d_alb; c->P.alb_stride = n_sets == 1 ? 0 : (long)h1::ALB_STRIDE;
   c->n_alb = n_sets;
-  return ILQR_OK;
+  return al_point_bounds(c);
 }
 int ilqr_hip_clear_al_bounds(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  c->P.alb = nullptr; c->P.alb_stride = 0; c->n_alb = 0;      // (the buffer stays with the handle for the next table)
-  return ILQR_OK;
+  c->n_alb = 0;      // (the buffer stays with the handle for the next table)
+  enter(c);
+  return al_point_bounds(c);
 }
 int ilqr_hip_num_al_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alb : -1; }
 int ilqr_hip_get_al_bounds(ilqr_hip_ctx* c, double* bounds) {
@@ -724,6 +758,126 @@ int ilqr_hip_al_update(ilqr_hip_ctx* c, int round) {
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
+
+// ---- the state family: bounds on the 28 box coordinates (pelvis position, pelvis velocity, joint velocities), one record lo[28], hi[28] per set
+int ilqr_hip_al_state_slot(int k) { return (k >= 0 && k < ILQR_AL_STATE_COORDS) ? h1::als_slot(k) : -1; }
+// every pair: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
+__attribute__((noinline, minsize)) static bool al_state_bounds_ok(const double* v, int n_sets) {
+  for (int s = 0; s < n_sets; ++s)
+    for (int i = 0; i < ILQR_AL_STATE_COORDS; ++i) {
+      const double lo = v[(size_t)s * ILQR_AL_STATE_BOUNDS + i], hi = v[(size_t)s * ILQR_AL_STATE_BOUNDS + ILQR_AL_STATE_COORDS + i];
+      if (!(lo <= hi) || lo == HUGE_VAL || hi == -HUGE_VAL) return false;      // (a NaN fails lo <= hi)
+    }
+  return true;
+}
+#define AL_STATE_INSTALLED(c) do { if (!(c)->P.al) { (c)->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; } } while (0)
+int ilqr_hip_set_al_state_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!bounds || check_sets(c, n_sets) || !(rho_state0 > 0.0) || !std::isfinite(rho_state0) || !(tol_state >= 0.0) || !al_state_bounds_ok(bounds, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  static_assert(h1::ALSB_FIELDS == ILQR_AL_STATE_BOUNDS && h1::ALS_COORDS == ILQR_AL_STATE_COORDS && h1::ALSB_HI == 28, "the interface's record is the device record without its padding");
+  const size_t B = c->B, rec_d = (size_t)h1::als_record_doubles(c->N);
+  if (!c->d_alsb) TRY(dalloc(c, &c->d_alsb, B * h1::ALSB_STRIDE));
+  if (!c->d_als) TRY(dalloc(c, &c->d_als, B * rec_d));
+  std::vector<double> rec((size_t)n_sets * h1::ALSB_STRIDE, 0.0);
+  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * h1::ALSB_STRIDE, bounds + (size_t)s * ILQR_AL_STATE_BOUNDS, sizeof(double) * ILQR_AL_STATE_BOUNDS);
+  HIPCHK(c, hipMemcpyAsync(c->d_alsb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  // the multipliers: zero where no table was installed; a table that replaces one keeps them.  rho_state starts at rho_state0 either way
+  std::vector<double> st(B * rec_d, 0.0);
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  if (c->n_alsb) HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < B; ++b) st[b * rec_d + h1::ALS_RHO] = rho_state0;
+  HIPCHK_S(c, hipMemcpy(c->d_als, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!c->n_alsb) HIPCHK_S(c, hipMemset(c->d_als_viol, 0, B * sizeof(double)));
+  c->h_alsb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_STATE_BOUNDS);
+  c->P.als = c->d_als; c->P.als_stride = (long)rec_d;
+  c->P.alsb = c->d_alsb; c->P.alsb_stride = n_sets == 1 ? 0 : (long)h1::ALSB_STRIDE;
+  c->n_alsb = n_sets; c->als_rho0 = rho_state0; c->als_tol = tol_state;
+  return al_point_bounds(c);
+}
+int ilqr_hip_clear_al_state_bounds(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0;      // (the buffers stay with the handle for the next table)
+  return al_point_bounds(c);
+}
+int ilqr_hip_num_al_state_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alsb : -1; }
+int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* c, double* bounds) {
+  if (!c || !bounds) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  for (int b = 0; b < c->B; ++b)
+    for (int i = 0; i < ILQR_AL_STATE_BOUNDS; ++i)
+      bounds[(size_t)b * ILQR_AL_STATE_BOUNDS + i] = c->n_alsb ? c->h_alsb[(size_t)(c->n_alsb == 1 ? 0 : b) * ILQR_AL_STATE_BOUNDS + i] : (i < ILQR_AL_STATE_COORDS ? -HUGE_VAL : HUGE_VAL);
+  return ILQR_OK;
+}
+// host image of the state store <-> the interface's [B][N+1][28][2] (lower, upper) array and rho [B]; to_store as al_convert (knot 0 stored as zero)
+__attribute__((noinline, minsize)) static void al_state_convert(const ilqr_hip_ctx* c, double* st, double* mu, double* rho, bool to_store) {
+  const size_t N = c->N, rec = (size_t)h1::als_record_doubles(c->N);
+  for (size_t b = 0; b < (size_t)c->B; ++b) {
+    double* r = st + b * rec;
+    if (rho) { if (to_store) r[h1::ALS_RHO] = rho[b]; else rho[b] = r[h1::ALS_RHO]; }
+    if (mu) for (size_t t = 0; t <= N; ++t) {
+      double* k = r + h1::ALS_HDR + t * h1::ALS_KNOT;
+      for (int i = 0; i < h1::ALS_COORDS; ++i) {
+        double* o = mu + ((b * (N + 1) + t) * h1::ALS_COORDS + i) * 2;
+        if (to_store) { k[h1::ALS_LO + i] = t == 0 ? 0.0 : o[0]; k[h1::ALS_HI + i] = t == 0 ? 0.0 : o[1]; }
+        else { o[0] = k[h1::ALS_LO + i]; o[1] = k[h1::ALS_HI + i]; }
+      }
+    }
+  }
+}
+// without a table: zero multipliers, rho_state and violation 0 (nothing is constrained)
+static int al_state_get(ilqr_hip_ctx* c, double* mu, double* rho) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  const size_t B = c->B, N = c->N;
+  if (!c->n_alsb) {
+    if (mu) std::fill(mu, mu + B * (N + 1) * ILQR_AL_STATE_BOUNDS, 0.0);
+    if (rho) std::fill(rho, rho + B, 0.0);
+    return ILQR_OK;
+  }
+  enter(c);
+  std::vector<double> st(B * (size_t)h1::als_record_doubles(c->N));
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  al_state_convert(c, st.data(), mu, rho, false);
+  return ILQR_OK;
+}
+int ilqr_hip_get_al_state_multipliers(ilqr_hip_ctx* c, double* mu) { return mu ? al_state_get(c, mu, nullptr) : ILQR_ERR_ARG; }
+int ilqr_hip_get_al_state_penalties(ilqr_hip_ctx* c, double* rho) { return rho ? al_state_get(c, nullptr, rho) : ILQR_ERR_ARG; }
+int ilqr_hip_set_al_state_multipliers(ilqr_hip_ctx* c, const double* mu, const double* rho) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!c->n_alsb) { c->err = "no state bounds installed"; return ILQR_ERR_STATE; }
+  const size_t B = c->B, N = c->N;
+  if (!al_values_ok(mu, B * (N + 1) * ILQR_AL_STATE_BOUNDS, false) || !al_values_ok(rho, B, true)) return ILQR_ERR_ARG;
+  enter(c);
+  std::vector<double> st(B * (size_t)h1::als_record_doubles(c->N));
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  al_state_convert(c, st.data(), const_cast<double*>(mu), const_cast<double*>(rho), true);
+  HIPCHK_S(c, hipMemcpy(c->d_als, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
+  return ILQR_OK;
+}
+int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* c, double* viol) {
+  if (!c || !viol) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!c->n_alsb) { std::fill(viol, viol + c->B, 0.0); return ILQR_OK; }
+  enter(c);
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(viol, c->d_als_viol, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* c, double* out) {
+  if (!c || !out) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  enter(c);
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(out, c->d_als_trace, (size_t)c->al_rounds * c->B * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+#undef AL_STATE_INSTALLED
 
 int ilqr_hip_set_contact_schedule(ilqr_hip_ctx* c, const int* stance, int n_sets) {
   if (!c || !stance || check_sets(c, n_sets)) return ILQR_ERR_ARG;
@@ -1036,6 +1190,7 @@ static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
   if (P.wsets) T.wsets += b0 * P.wsets_stride;
   if (P.al) T.al += b0 * P.al_stride;
   if (P.alb) T.alb += b0 * P.alb_stride;
+  if (P.alsb) { T.als += b0 * P.als_stride; T.alsb += b0 * P.alsb_stride; }
   return T;
 }
 static int ensure_slices(ilqr_hip_ctx* c, int k) {
@@ -1541,6 +1696,7 @@ __attribute__((noinline)) static int enqueue_al_rounds(ilqr_hip_ctx* c, int k) {
   HIPCHK_S(c, hipMemsetAsync(c->d_al_done, 0, (size_t)c->B * sizeof(int), st));
   HIPCHK_S(c, hipMemsetAsync(c->d_al_left, 0, (size_t)rounds * sizeof(int), st));
   HIPCHK_S(c, hipMemsetAsync(c->d_al_trace, 0xFF, (size_t)rounds * c->B * 5 * sizeof(double), st));      // (all bits set: NaN)
+  HIPCHK_S(c, hipMemsetAsync(c->d_als_trace, 0xFF, (size_t)rounds * c->B * 2 * sizeof(double), st));
   c->al_rounds_run = 0;
   int rc = ILQR_OK;
   for (int round = 0; round < rounds && rc == ILQR_OK; ++round) {
@@ -1927,7 +2083,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
   h1::ProblemDev Ps = c->P;
   std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
   Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
-  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0;
+  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0; Ps.als = nullptr; Ps.als_stride = 0; Ps.alsb = nullptr; Ps.alsb_stride = 0;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and

@@ -154,10 +154,17 @@ struct AlDev {
   double* trace;                   // [rounds][B][5]
   int* left;                       // [rounds] rollouts not done after each round (zeroed ahead of the round's update)
   const double* bounds; long bounds_stride;      // the bounds table (ProblemDev::alb, the same records; stride 0: one record for all); null: the model's ranges at `margin`
+  // the state family (ilqr_hip_set_al_state_bounds); sbounds null: not installed, nothing below is read.  Appended: nothing above moves
+  const double* sbounds; long sbounds_stride;    // its bounds table (ProblemDev::alsb, the same records)
+  double* sstore; long sstride;                  // its multiplier store (ProblemDev::als points at the same records)
+  double rho_state0, rho_state_max, tol_state;
+  double* sviol;                   // [B] state violation of the nominal trajectory at the last update
+  double* strace;                  // [rounds][B][2] violation, rho_state the round ran with
 };
 // masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st);
-// shift > N: every multiplier becomes zero (cold start); the penalties are reset to the given values, done flags and violations cleared
+// shift > N: every multiplier becomes zero (cold start); the penalties are reset to the given values (the state family's to A.rho_state0),
+// done flags and violations cleared
 void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st);
 // launch_solve_begin with active = !done (done: of S's rollouts)
 void launch_solve_begin_al(const DevState& S, const int* done, hipStream_t st);

@@ -656,6 +656,10 @@ DEVFN void quad_hessian_tiles(const double (&av)[4][2], const double (&bv)[4][4]
 // AL_TABLE: the same lanes request their own lo and hi from rollout b's bounds record (ProblemDev::alb) beside their two multipliers --
 // two more per-lane loads in the phase-0 batch, nothing on the path between phase 0 and the lanes' use in phases 1b / 2.  Indexed by b,
 // never by bs, as the weight sets are.
+// AL_TABLE_STATE: the other state lanes of wave 0 (0..2 and 26..50: box coordinate lane < 3 ? lane : lane - 23) carry the state
+// family's two bounds the same way -- their two multipliers from the second store (ProblemDev::als) and their lo / hi from rollout b's record
+// of ProblemDev::alsb in the same phase-0 batch and the same four variables, the rollout's third penalty as a scalar load beside the other two.
+// A lane still owns at most one coordinate.
 template <bool WS, int AL>
 __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S, ProblemDev P, int mode, const int* list, const int* count, int lower,
                                                                      const double* recg, long knot0) {
@@ -676,6 +680,8 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   const bool pk = lower == 2;            // operand layout (every knot, the terminal one included)
   double al_rho_j = 0.0, al_rho_c = 0.0, al_mu_lo = 0.0, al_mu_hi = 0.0, al_lo = 0.0, al_hi = 0.0;
   if constexpr (AL != AL_OFF) { const double* ar = P.al + (long)b * P.al_stride; al_rho_j = ar[AL_RHO_JOINT]; al_rho_c = ar[AL_RHO_CTRL]; }
+  double al_rho_s = 0.0;
+  if constexpr (al_state(AL)) al_rho_s = (P.als + (long)b * P.als_stride)[ALS_RHO];
   __shared__ QuadLds L;
 #ifdef QUAD_STAMP
   long long qlast = clock64();
@@ -710,11 +716,25 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       // wave 0: hinge lane - 7 of knot t; wave 1: actuator lane - 64 of knot tu (indices clamped into the knot's record, masked by the users)
       const double* ak = P.al + (long)b * P.al_stride + AL_HDR + (long)(wv == 0 ? t : tu) * AL_KNOT;
       const int ai = wv == 0 ? AL_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : AL_ULO + iu;
+      if constexpr (!al_state(AL)) {
       al_mu_lo = ak[ai]; al_mu_hi = ak[ai + H1_NJ];
       if constexpr (AL == AL_TABLE) {
         const double* ab = P.alb + (long)b * P.alb_stride;      // (the same clamped coordinate; ALB_JHI = ALB_JLO + 19, ALB_UHI = ALB_ULO + 19)
         const int bi = wv == 0 ? ALB_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : ALB_ULO + iu;
         al_lo = ab[bi]; al_hi = ab[bi + H1_NJ];
+      }
+      } else {
+        // a box lane takes its pair from the state family's records instead: one pair of multipliers and one pair of bounds per lane either way
+        const bool box = wv == 0 && (lane < 3 || (lane >= H1_NQ && lane < H1_NX));
+        const int kb = lane < 3 ? lane : lane - 23;
+        const double* sk = P.als + (long)b * P.als_stride + ALS_HDR + (long)t * ALS_KNOT + ALS_LO;
+        const double* pm = box ? sk + kb : ak + ai;
+        al_mu_lo = pm[0]; al_mu_hi = pm[box ? (int)ALS_COORDS : (int)H1_NJ];
+        const double* sb = P.alsb + (long)b * P.alsb_stride + ALSB_LO;
+        const double* ab = P.alb + (long)b * P.alb_stride;
+        const int bi = wv == 0 ? ALB_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : ALB_ULO + iu;
+        const double* pb = box ? sb + kb : ab + bi;
+        al_lo = pb[0]; al_hi = pb[box ? (int)ALS_COORDS : (int)H1_NJ];
       }
     }
     // the table words of phases 1a and 2b travel with the knot's data as well (each was a dependent round trip to the constant
@@ -808,11 +828,18 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       if constexpr (AL != AL_OFF) {
         if (a >= 7 && a < H1_NQ) {
           double lo, hi;
-          if constexpr (AL == AL_TABLE) { lo = al_lo; hi = al_hi; } else al_bounds(H1_JRANGE[a - 7], P.al_margin, lo, hi);
+          if constexpr (al_table(AL)) { lo = al_lo; hi = al_hi; } else al_bounds(H1_JRANGE[a - 7], P.al_margin, lo, hi);
           const double q = xv;                           // (hinge slots are not permuted)
           const double sh = al_mu_hi + al_rho_j * (q - hi), sl = al_mu_lo + al_rho_j * (lo - q);
           if (sh > 0.0) { g += sh; dgl += al_rho_j; }
           if (sl > 0.0) { g -= sl; dgl += al_rho_j; }
+        }
+        if constexpr (al_state(AL)) {
+          if (a < 3 || a >= H1_NQ) {                     // (nor are the pelvis position and the velocity slots)
+            const double sh = al_mu_hi + al_rho_s * (xv - al_hi), sl = al_mu_lo + al_rho_s * (al_lo - xv);
+            if (sh > 0.0) { g += sh; dgl += al_rho_s; }
+            if (sl > 0.0) { g -= sl; dgl += al_rho_s; }
+          }
         }
       } else
       if (a >= 7 && a < H1_NQ) {
@@ -862,7 +889,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       double g = Rl() * (u - urv), h = Rl();
       if constexpr (AL != AL_OFF) {
         double lo, hi;
-        if constexpr (AL == AL_TABLE) { lo = al_lo; hi = al_hi; } else al_bounds(H1_CTRLRANGE[l1], P.al_margin, lo, hi);
+        if constexpr (al_table(AL)) { lo = al_lo; hi = al_hi; } else al_bounds(H1_CTRLRANGE[l1], P.al_margin, lo, hi);
         const double sh = al_mu_hi + al_rho_c * (u - hi), sl = al_mu_lo + al_rho_c * (lo - u);
         if (sh > 0.0) { g += sh; h += al_rho_c; }
         if (sl > 0.0) { g -= sl; h += al_rho_c; }
@@ -1046,7 +1073,8 @@ void launch_cost_quadratics(const DevState& S, const ProblemDev& P, int mode, hi
   else hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
   // one workgroup per knot; the grid is padded to a multiple of 8 so that every XCD's share (L % 8) has ceil(total / 8) slots
   const long per = (knots + 7) / 8;
-  if (P.al && P.alb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_TABLE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  if (P.al && P.alsb && P.alb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_TABLE_STATE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  else if (P.al && P.alb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_TABLE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
   else if (P.al) hipLaunchKernelGGL((k_cost_quadratics<false, AL_MODEL>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
   else if (P.wsets) hipLaunchKernelGGL((k_cost_quadratics<true, AL_OFF>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
   else hipLaunchKernelGGL((k_cost_quadratics<false, AL_OFF>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);

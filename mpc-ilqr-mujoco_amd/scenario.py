@@ -346,6 +346,62 @@ def stack_al_bounds(records, B, margin=0.0):
     return _check_al_bounds(out)
 
 
+# keys of a state-bounds record: name -> (first box coordinate, length); box coordinates in the order of ilqr_hip_set_al_state_bounds
+_AL_STATE_FIELDS = {"pelvis_pos": (0, 3), "pelvis_lin_vel": (3, 3), "pelvis_ang_vel": (6, 3), "joint_vel": (9, 19)}
+
+
+def stack_al_state_bounds(records, B):
+    """State-bounds table [n, 56] for BatchedILQR.set_al_state_bounds: lo[28], hi[28] over the box coordinates pelvis position (3, world),
+    pelvis linear velocity (3, world), pelvis angular velocity (3, body), joint velocities (19, order of u).  records is one dict (n = 1:
+    every rollout reads it) or a sequence of B dicts (n = B).  Every key is optional and takes a pair (lo, hi), each a scalar or a vector of
+    the key's length: "pelvis_pos", "pelvis_lin_vel", "pelvis_ang_vel", "joint_vel"; and the shorthands "pelvis_z": (lo, hi) of the
+    pelvis height alone, and "joint_speed": v, a scalar or [19], for the symmetric joint_vel bound (-v, +v).  A shorthand is applied after
+    the key it refines.  A key left out gives -inf / +inf: no bound.  Raises ValueError for another key, a wrong shape, a sequence that is
+    not B long, or a record ilqr_hip_set_al_state_bounds refuses (a NaN, lo > hi, lo = +inf, hi = -inf)."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be positive")
+    if isinstance(records, dict):
+        records = [records]
+    else:
+        records = list(records)
+        if len(records) != B:
+            raise ValueError("records must be one dict or B of them")
+    out = np.empty((len(records), 56))
+    out[:, :28] = -np.inf; out[:, 28:] = np.inf
+
+    def pair(name, v, n):
+        try:
+            lo, hi = v
+        except (TypeError, ValueError):
+            raise ValueError("%s takes a pair (lo, hi)" % name)
+        lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+        if lo.shape not in ((), (n,)) or hi.shape not in ((), (n,)):
+            raise ValueError("%s: lo and hi are scalars or [%d]" % (name, n))
+        return lo, hi
+
+    for b, rec in enumerate(records):
+        if not isinstance(rec, dict):
+            raise ValueError("a state-bounds record is a dict")
+        extra = set(rec) - set(_AL_STATE_FIELDS) - {"pelvis_z", "joint_speed"}
+        if extra:
+            raise ValueError("unknown state-bounds field(s) %s: a record has %s, pelvis_z and joint_speed" % (sorted(extra), list(_AL_STATE_FIELDS)))
+        for name, (k0, n) in _AL_STATE_FIELDS.items():
+            if rec.get(name) is not None:
+                out[b, k0:k0 + n], out[b, 28 + k0:28 + k0 + n] = pair(name, rec[name], n)
+        if rec.get("pelvis_z") is not None:
+            out[b, 2], out[b, 28 + 2] = (float(v.reshape(-1)[0]) for v in pair("pelvis_z", rec["pelvis_z"], 1))
+        if rec.get("joint_speed") is not None:
+            v = np.asarray(rec["joint_speed"], dtype=np.float64)
+            if v.shape not in ((), (19,)) or np.isnan(v).any() or (v < 0).any():
+                raise ValueError("joint_speed must be a scalar or [19], >= 0")
+            out[b, 9:28], out[b, 28 + 9:56] = -v, v
+    lo, hi = out[:, :28], out[:, 28:]
+    if np.isnan(out).any() or (lo > hi).any() or (lo == np.inf).any() or (hi == -np.inf).any():
+        raise ValueError("state bounds: no NaN, lo <= hi, lo < +inf, hi > -inf")
+    return out
+
+
 def al_bounds_from_plant_joints(joints, margin=0.0):
     """The bounds table [n, 76] in which the solver knows each rollout's torque range of stack_plant_joints' records `joints` [n, 76]:
     ctrl_lo, ctrl_hi = range_scale_i * the default control bound of actuator i at `margin` (range_scale = 0, a dead motor: lo = hi = 0);

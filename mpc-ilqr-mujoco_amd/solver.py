@@ -29,6 +29,9 @@ EXPORTS = [
     "ilqr_hip_get_al_multipliers", "ilqr_hip_set_al_multipliers", "ilqr_hip_get_al_penalties", "ilqr_hip_get_al_violation", "ilqr_hip_get_al_trace",
     "ilqr_hip_al_update",
     "ilqr_hip_set_al_bounds", "ilqr_hip_clear_al_bounds", "ilqr_hip_num_al_bound_sets", "ilqr_hip_get_al_bounds", "ilqr_hip_al_default_bounds",
+    "ilqr_hip_set_al_state_bounds", "ilqr_hip_clear_al_state_bounds", "ilqr_hip_num_al_state_bound_sets", "ilqr_hip_get_al_state_bounds",
+    "ilqr_hip_get_al_state_multipliers", "ilqr_hip_set_al_state_multipliers", "ilqr_hip_get_al_state_penalties", "ilqr_hip_get_al_state_violation",
+    "ilqr_hip_get_al_state_trace", "ilqr_hip_al_state_slot",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -87,6 +90,10 @@ PLANT_JOINT_FIELDS = (("gain", 1.0), ("range_scale", 1.0), ("damping", 1.0), ("a
 PLANT_JOINTS = 76
 # one record of the bounds table of the augmented-Lagrangian limits (ILQR_AL_BOUNDS): joint_lo[19], joint_hi[19], ctrl_lo[19], ctrl_hi[19]
 AL_BOUNDS = 76
+# one record of the state bounds of the augmented Lagrangian (ILQR_AL_STATE_BOUNDS): lo[28], hi[28] over the box coordinates -- pelvis
+# position (3), pelvis linear velocity (3), pelvis angular velocity (3), joint velocities (19); al_state_slot(k) is coordinate k's state slot
+AL_STATE_COORDS = 28
+AL_STATE_BOUNDS = 56
 # columns of a plant terrain record (include/ilqr_hip.h ILQR_PLANT_TERRAIN)
 PLANT_TERRAIN = ("z_left", "z_right", "edge_x", "first", "end")
 
@@ -212,6 +219,11 @@ def gravity_compensation(x, gravity):
     if rc:
         raise ILQRError(STATUS.get(rc, str(rc)))
     return u
+
+
+def al_state_slot(k):
+    """State slot of box coordinate k of the state bounds (ilqr_hip_al_state_slot; host only); -1 outside 0..27."""
+    return int(load_library().ilqr_hip_al_state_slot(int(k)))
 
 
 def al_default_bounds(margin=0.0):
@@ -430,6 +442,55 @@ class BatchedILQR:
     def al_bounds(self):
         """[B, AL_BOUNDS]: the record each rollout is solved with (without a table: the model's bounds at the installed margin)."""
         return self._get("ilqr_hip_get_al_bounds", (self.B, AL_BOUNDS))
+
+    # ---- augmented-Lagrangian bounds on pelvis position, pelvis velocity and joint velocities (include/ilqr_hip.h ilqr_hip_set_al_state_bounds)
+    def set_al_state_bounds(self, bounds, rho_state0, tol_state=1e-3):
+        """Bounds on the 28 box coordinates, enforced as a third family of the installed augmented Lagrangian: [AL_STATE_BOUNDS] /
+        [1, AL_STATE_BOUNDS] (every rollout) or [B, AL_STATE_BOUNDS] (rollout b reads row b); columns lo[28], hi[28]
+        (scenario.stack_al_state_bounds).  -inf / +inf switch a side off.  rho_state0: the initial penalty of the family; a rollout is done
+        only when its state violation is <= tol_state as well.  Acts on the cost only; stays until clear_al_state_bounds() or
+        clear_augmented_lagrangian()."""
+        b = _c64(bounds)
+        if b.ndim == 1:
+            b = b[None]
+        if b.ndim != 2 or b.shape[1] != AL_STATE_BOUNDS:
+            raise ValueError("bounds must be [%d], [1, %d] or [B, %d]" % (AL_STATE_BOUNDS, AL_STATE_BOUNDS, AL_STATE_BOUNDS))
+        self._chk(self.L.ilqr_hip_set_al_state_bounds(self.h, _p(b), int(b.shape[0]), C.c_double(float(rho_state0)), C.c_double(float(tol_state))))
+
+    def clear_al_state_bounds(self):
+        """No state bounds any more."""
+        self._chk(self.L.ilqr_hip_clear_al_state_bounds(self.h))
+
+    def num_al_state_bound_sets(self):
+        """0: no table; else the number of records of the installed table (1 or B)."""
+        return int(self.L.ilqr_hip_num_al_state_bound_sets(self.h))
+
+    def al_state_bounds(self):
+        """[B, AL_STATE_BOUNDS]: the record each rollout is solved with (without a table: -inf / +inf)."""
+        return self._get("ilqr_hip_get_al_state_bounds", (self.B, AL_STATE_BOUNDS))
+
+    def al_state_multipliers(self):
+        """[B,N+1,28,2]: the multipliers of the (lower, upper) bounds of the box coordinates."""
+        return self._get("ilqr_hip_get_al_state_multipliers", (self.B, self.N + 1, AL_STATE_COORDS, 2))
+
+    def set_al_state_multipliers(self, mu=None, rho=None):
+        """Install state multipliers [B,N+1,28,2] and / or the penalties rho_state [B]; None leaves that part as it is."""
+        mu, rho = (None if a is None else _c64(a) for a in (mu, rho))
+        if (mu is not None and mu.shape != (self.B, self.N + 1, AL_STATE_COORDS, 2)) or (rho is not None and rho.shape != (self.B,)):
+            raise ValueError("state multipliers: mu [B,N+1,28,2], rho [B]")
+        self._chk(self.L.ilqr_hip_set_al_state_multipliers(self.h, _p(mu), _p(rho)))
+
+    def al_state_penalties(self):
+        """rho_state [B] as the store holds it."""
+        return self._get("ilqr_hip_get_al_state_penalties", (self.B,))
+
+    def al_state_violation(self):
+        """viol_state [B] of the last update (the done flags: al_violation)."""
+        return self._get("ilqr_hip_get_al_state_violation", (self.B,))
+
+    def al_state_trace(self):
+        """[rounds, B, 2]: state violation and rho_state of every round of the last solve (NaN: not run)."""
+        return self._get("ilqr_hip_get_al_state_trace", (self.augmented_lagrangian_rounds(), self.B, 2))
 
     def set_references(self, x_ref, u_ref, com_ref):
         x_ref, u_ref, com_ref = _c64(x_ref), _c64(u_ref), _c64(com_ref)

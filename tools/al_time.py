@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian) against the plain penalties on ONE handle,
 on one GPU, the two alternating:
-   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds]
+   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state]
   * ms per call of the two cost stages (stage_cost_quadratics: k_quad_kin + k_cost_quadratics; stage_total_cost: k_traj_knot_cost +
     k_traj_cost_sum) and, per launch inside a solve, of the cost quadratics (ilqr_hip_get_stage_ms, stage 2);
   * ms per call of the update kernel alone (ilqr_hip_al_update: k_al_update, one memset, one synchronisation);
@@ -10,7 +10,10 @@ Each stage sample is the wall time of `calls` back-to-back calls (every call syn
 medians over the rounds are reported and no threshold is applied.  Prints one JSON line; not part of bench.py.
 --bounds adds two modes to the alternation on the same handle: AL under a one-record table of bounds (ilqr_hip_set_al_bounds, n_sets = 1)
 and under a per-rollout table (n_sets = batch).  Both tables hold the bounds the installation has without a table, so the three AL modes
-do the same arithmetic on the same values and differ in where the bounds come from."""
+do the same arithmetic on the same values and differ in where the bounds come from.
+--state (implies --bounds) adds a fifth mode: the per-rollout table plus a per-rollout table of state bounds (ilqr_hip_set_al_state_bounds,
+n_sets = batch; every bound +-1e3, none active) -- the state instantiation of k_cost_quadratics and k_al_state_knot_cost behind
+k_traj_knot_cost against the AL_TABLE instantiations of the mode before it."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py)
@@ -29,7 +32,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4096); ap.add_argument("--horizon", type=int, default=25)
     ap.add_argument("--calls", type=int, default=20); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--bounds", action="store_true", help="also time AL under a one-record and under a per-rollout table of bounds")
+    ap.add_argument("--state", action="store_true", help="also time AL under a per-rollout table of bounds plus a per-rollout table of state bounds")
     a = ap.parse_args()
+    a.bounds = a.bounds or a.state
     pkg = load_package()
     from mpc_ilqr_mujoco_amd import solver as sv
     sc = pkg.scenario
@@ -39,11 +44,12 @@ def main():
     s = sv.BatchedILQR(B, N=N, dt=prob["dt"]); s.set_problem(prob)
     s.set_options(early_exit=False); s.set_max_iterations(a.iters)
     al = dict(rounds=3, rho_joint0=2 * prob["w_joint"], rho_ctrl0=2 * prob["w_ctrl"], growth=10.0, rho_max_factor=1e4, margin=0.1, tol_joint=0.0, tol_ctrl=0.0)
-    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ())
+    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ()) + (("al_bounds_B_state_B",) if a.state else ())
     ms = {m: {"quadratics": [], "total_cost": [], "solve": [], "quadratics_per_launch_in_solve": []} for m in modes}
     for m in modes[1:]:
         ms[m]["update"] = []
     record = sv.al_default_bounds(al["margin"])
+    state_record = np.concatenate([np.full(sv.AL_STATE_COORDS, -1e3), np.full(sv.AL_STATE_COORDS, 1e3)])
 
     def timed(fn, calls):
         fn()
@@ -62,7 +68,12 @@ def main():
                     s.clear_al_bounds()
                 else:
                     s.set_al_bounds(record if m == "al_bounds_1" else np.tile(record, (B, 1)))
-                assert s.num_al_bound_sets() == {"al": 0, "al_bounds_1": 1, "al_bounds_B": B}[m]
+                if m == "al_bounds_B_state_B":
+                    s.set_al_state_bounds(np.tile(state_record, (B, 1)), 2 * prob["w_joint"], 0.0)
+                else:
+                    s.clear_al_state_bounds()
+                assert s.num_al_bound_sets() == {"al": 0, "al_bounds_1": 1, "al_bounds_B": B, "al_bounds_B_state_B": B}[m]
+                assert s.num_al_state_bound_sets() == (B if m == "al_bounds_B_state_B" else 0)
             s.initialize(x0, ui)
             s.enable_profiling(True)
             t0 = time.perf_counter(); s.solve(None); dt = 1e3 * (time.perf_counter() - t0)
