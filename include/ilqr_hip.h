@@ -825,10 +825,33 @@ int ilqr_hip_enable_profiling(ilqr_hip_ctx* ctx, int on);
 /* Restrict the event pairs to the stages whose bit (stage index as above) is set in `mask` (default 0xFF: all).  Every timed
    launch costs two event records on its stream: all eight stages together add 1.3 ms to a 95 ms solve at B = 4096. */
 int ilqr_hip_set_profiled_stages(ilqr_hip_ctx* ctx, unsigned mask);
-/* Diagnostic of the concurrent nominal re-rollout (iterations >= 1 of a solve roll the nominal trajectory beside the
-   linearisation, ilqr.cpp:563 vs :576): number of trajectory elements of the last solve in which the re-rolled trajectory
-   differed bit-wise from the one the linearisation saw.  0 means the launch order is equivalent to the reference's. */
+/* Diagnostic of the concurrent nominal re-rollout (with ilqr_hip_set_reroll_nominal, iterations >= 1 of a solve roll the nominal
+   trajectory beside the linearisation, ilqr.cpp:563 vs :576): number of trajectory elements of the last solve in which the re-rolled
+   trajectory differed bit-wise from the one the linearisation saw.  0 means the launch order is equivalent to the reference's -- and
+   that the default, which does not re-roll, computes what the re-roll computes.  0 as well where nothing was re-rolled. */
 int ilqr_hip_get_adopt_mismatches(ilqr_hip_ctx* ctx, unsigned long long* count);
+/* Nominal re-rollout.  The reference rolls the nominal trajectory out from x0 at the top of every iteration (ilqr.cpp:551,563) and evaluates
+   its cost, the line-search baseline.  From iteration 1 on that trajectory is the previous one or the line-search candidate the iteration
+   before accepted: a rollout from x0 under the same controls by the same step implementation, which the rollout reproduces bit for bit, and
+   whose cost the bookkeeping has stored summed in the same order.  The same holds for iteration 0 of a solve whose trajectory is a cold start
+   (ilqr_hip_initialize*) under the dynamics parameters now set, and of rounds >= 2 of an augmented-Lagrangian solve: the cost-only pass at
+   the top of every solve and round evaluates the baseline under the weights and multipliers now set.  By default none of these launches
+   runs -- the rollout, its knot costs, their sum, the adoption.  A warm-shifted or caller-supplied trajectory, a new x0 (ilqr_hip_solve with
+   x0), changed dynamics parameters: iteration 0 rolls out in front of the linearisation, as the reference does.  Every observable of the
+   solve is unchanged, bit for bit (GPU test).
+   on != 0, or environment ILQR_REUSE_ROLLOUT=0, restores every rollout the reference executes -- the verification mode: beside the
+   linearisation into a shadow buffer (0.01 MB per rollout at N = 25, allocated by the first solve that re-rolls) and adopted with
+   ilqr_hip_get_adopt_mismatches counting, or in front of it with ILQR_OVERLAP_ROLLOUT=0.  ILQR_REUSE_ROLLOUT=1 / 0 overrides the handle's
+   setting (read with the other switches, ilqr_hip_reload_environment).  The cross-check kernel families of the test library whose line
+   search and rollout run different step implementations roll out in every iteration whatever the setting.
+   bench.py's per-iteration flop budget still charges every iteration a nominal step per knot, as it charges a full linearisation with the
+   cache: its rates are algorithmic-equivalent rates.  No reference counterpart: the reference recomputes. */
+int ilqr_hip_set_reroll_nominal(ilqr_hip_ctx* ctx, int on);
+/* Rollouts the nominal-rollout launches of the last solve were enqueued for: launches x the rollouts of the batch (or slice) each covers,
+   all augmented-Lagrangian rounds together; an iteration whose region runs in two groups (ilqr_hip_get_split_iterations) launches once per
+   group, each over the batch under the group's flags.  Host-side count, no synchronisation.  By default 0 behind a cold start and batch x 1 behind a warm
+   start; batch x iterations enqueued (x rounds) in the verification mode.  -1 for a null handle. */
+long long ilqr_hip_get_nominal_rollouts(const ilqr_hip_ctx* ctx);
 int ilqr_hip_get_stage_ms(ilqr_hip_ctx* ctx, double* ms /*[8]*/, double* launches /*[8]*/);
 /* Iterations whose kernels the last solve enqueued: max_iterations, or fewer when the convergence exit (ilqr.cpp:645-655,
    ilqr_hip_set_options early_exit) is on and every rollout of the batch had left the loop -- the host follows the device-side

@@ -35,7 +35,7 @@ struct Knobs {
   int relin;            // ILQR_RELIN (-1: the handle's own setting, ilqr_hip_set_relinearize_unchanged)
   int repass;           // ILQR_REPASS=1: the full first pass in every iteration (as ilqr_hip_set_repeat_first_pass; either one is enough)
   int ls_list_max;      // ILQR_LS_LIST_MAX: a first-pass list of at most this many rollouts takes the one-rollout-per-wave line search (1024: one wave per SIMD)
-  int slices, stagger, overlap_rollout, reuse_rollout, ee_gate /* -1: the handle's own setting */, split /* -1: on with the convergence exit */, spec, spec_dual, spec_max;
+  int slices, stagger, overlap_rollout, reuse_rollout /* -1: the handle's own setting, ilqr_hip_set_reroll_nominal */, ee_gate /* -1: the handle's own setting */, split /* -1: on with the convergence exit */, spec, spec_dual, spec_max;
   int spec_lists;       // ILQR_SPEC_LISTS=0: never the listed side-by-side order (as ilqr_hip_set_listed_spec(ctx, 0); either one is enough)
   int spec_list_max;    // ILQR_SPEC_LIST_MAX: the order is taken while 2 chg_n + kr_n is at most this many one-wave-per-SIMD slots
   int spec_list_from;   // ILQR_SPEC_LIST_FROM: first iteration that enqueues the pair of orders (0: iteration 3 max_iter / 5, a fixed rule -- the empty launches of the order not taken cost time where the lists are long)
@@ -61,7 +61,7 @@ static Knobs read_knobs() {
   k.repass = geti("ILQR_REPASS", 0);
   k.ls_list_max = geti("ILQR_LS_LIST_MAX", 1024);
   k.overlap_rollout = geti("ILQR_OVERLAP_ROLLOUT", 1);
-  { const char* e = getenv("ILQR_REUSE_ROLLOUT"); k.reuse_rollout = (e && e[0] == '1') ? 1 : 0; }
+  k.reuse_rollout = geti("ILQR_REUSE_ROLLOUT", -1);
   k.ee_gate = geti("ILQR_EE_GATE", -1);
   k.split = geti("ILQR_SPLIT", -1);
   k.spec = geti("ILQR_SPEC", 1);
@@ -80,7 +80,11 @@ struct ilqr_hip_ctx {
   hipStream_t stream3 = nullptr;          // nominal re-rollout of iterations >= 1, concurrently with both
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_roll = nullptr;
   hipEvent_t ev_lin = nullptr, ev_adopt = nullptr;   // adoption of the re-rolled trajectory beside the backward pass (enqueue_region, wait_adoption)
-  double* d_shadowx = nullptr;            // [B][N+1][51] target of the concurrent re-rollout
+  double* d_shadowx = nullptr;            // [B][N+1][51] target of the concurrent re-rollout: allocated by the first solve that re-rolls aside (ensure_shadow)
+  // ilqr_hip_set_reroll_nominal: 1 = the verification mode, every nominal rollout the reference runs (solve_order.h nominal_roll); nominal_rollouts:
+  // rollouts the nominal-rollout launches of the last solve were enqueued for, all rounds and slices (ilqr_hip_get_nominal_rollouts)
+  int reroll_nominal = 0;
+  long long nominal_rollouts = 0;
   DevState S{};
   h1::ProblemDev P{};
   // reference sets on the device
@@ -471,7 +475,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
       hipEventCreateWithFlags(&c->evA_roll, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evA_lin, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->evA_adopt, hipEventDisableTiming) != hipSuccess)) { c->err = "stream / event creation failed (early continuation)"; rc = ILQR_ERR_HIP; }
   A(dalloc(c, &c->d_tmpx, B * (N + 1) * n)); A(dalloc(c, &c->d_tmpu, B * N * m));
-  A(dalloc(c, &c->d_prevx, B * (N + 1) * n)); A(dalloc(c, &c->d_prevu, B * N * m)); A(dalloc(c, &c->d_shadowx, B * (N + 1) * n));
+  A(dalloc(c, &c->d_prevx, B * (N + 1) * n)); A(dalloc(c, &c->d_prevu, B * N * m));
   A(dalloc(c, &c->d_u0, B * m)); A(dalloc(c, &c->d_K0, B * m * n)); A(dalloc(c, &c->d_cost_tmp, B)); A(dalloc(c, &c->d_mismatch, 1));
   // shared reference sets sized for per-rollout use
   A(dalloc(c, &c->d_xref, B * (N + 1) * n)); A(dalloc(c, &c->d_uref, B * N * m)); A(dalloc(c, &c->d_comref, B * (N + 1) * 3));
@@ -1233,12 +1237,23 @@ static ilqr::SolveSettings solve_settings(const ilqr_hip_ctx* c, const DevState&
   s.spec = k.spec != 0; s.spec_dual = k.spec_dual != 0; s.spec_max = k.spec_max;
   s.spec_lists = k.spec_lists != 0; s.listed_spec = c->listed_spec != 0; s.spec_list_max = k.spec_list_max; s.spec_list_from = k.spec_list_from;
   s.dedup = effective(k.dedup_retry, c->dedup_retry) != 0; s.relin = effective(k.relin, c->relin) != 0; s.repass = k.repass || c->repass;
-  s.overlap_rollout = k.overlap_rollout != 0; s.reuse_rollout = k.reuse_rollout != 0;
+  s.overlap_rollout = k.overlap_rollout != 0; s.reuse_rollout = effective(k.reuse_rollout, !c->reroll_nominal) != 0;
   s.max_iter = c->max_iter; s.B = S.B; s.slices = c->n_slices; s.analytic_jacobians = c->jac_mode == ILQR_JAC_ANALYTIC; s.first_aside = c->first_aside;
   s.lists = S.order != nullptr; s.chg = S.chg != nullptr; s.chg_f = S.chg_f != nullptr; s.kr = S.kr && S.kr_n;
   s.ls_list = S.ls_list != nullptr; s.ls_kind = S.ls_kind != nullptr; s.lgate = c->d_lgate != nullptr;
   s.grp_a = S.grp_a != nullptr; s.stream_a = c->a1 != nullptr; s.adopt_events = G.lin && G.adopt; s.twin = c->twin;
   return s;
+}
+// The shadow buffer of the re-rollout beside the region, 0.01 MB per rollout at N = 25 (43 MB at B = 4096, 344 MB at B = 32 768): allocated by
+// the first solve any iteration or round of which re-rolls aside (first_aside: rounds >= 2 of an augmented-Lagrangian solve set it), as the
+// twin below.  A handle that never re-rolls never holds it.  Unlike the twin it is what the caller asked for: failing to get it fails the solve.
+static int ensure_shadow(ilqr_hip_ctx* c, const ilqr::LaunchPlan& L) {
+  if (c->d_shadowx) return ILQR_OK;
+  ilqr::SolveSettings s = solve_settings(c, c->S, main_lanes(c));
+  s.first_aside = true;
+  const ilqr::SolveOrder O = ilqr::resolve_solve_order(s, L);
+  if (ilqr::nominal_roll(O, L, 0) != ilqr::ROLL_ASIDE && ilqr::nominal_roll(O, L, 1) != ilqr::ROLL_ASIDE) return ILQR_OK;
+  return dalloc(c, &c->d_shadowx, (size_t)c->B * (c->N + 1) * ILQR_NX);
 }
 static int alloc_twin(ilqr_hip_ctx* c);
 // (the side-by-side order is an optimisation: a handle that cannot get the memory keeps the sequential order instead of failing the solve)
@@ -1301,15 +1316,18 @@ struct SolveCtx {
   int ls_bound;             // with the gate the host has seen how many rollouts were still active at the start of iteration iter - 1: an upper
                             // bound for this iteration's passes -- the active set only shrinks; else -1
   bool adopt_aside;         // the re-rolled trajectory is adopted on G.r, beside the backward pass
+  bool a_adopts;            // ... and group A's on GA.r: the regions of iterations >= 1 re-roll aside (one answer per solve, solve_order.h nominal_roll)
   bool prev_split;          // group A of the iteration at hand is already enqueued
 };
-// One group's share of the concurrent region of an iteration -- linearisation (:576) on G.m, cost quadratics (:588) on G.q, the
-// nominal re-rollout (:551,563) into the shadow buffer and its adoption on G.r (solve_order.h rolls_aside) -- behind an event recorded on
-// fork_src.
+// One group's share of the concurrent region of an iteration -- linearisation (:576) on G.m, cost quadratics (:588) on G.q, and where
+// roll is ROLL_ASIDE the nominal re-rollout (:551,563) into the shadow buffer and its adoption on G.r (solve_order.h nominal_roll) --
+// behind an event recorded on fork_src.  G.lin is recorded behind the linearisation wherever somebody waits for it: the adoption, or the
+// solve's own stream for a group whose linearisation runs on a stream of its own (group A).
 // Sm: the view the mask-selected kernels (rollout, trajectory cost, adoption) get -- S, or S with a group's flags as `active`;
 // wl: the group's compacted list for the per-knot kernels (null: the iteration's own list / mask, as knot_mode and iter_l say).
-static int enqueue_region(const SolveCtx& X, const Lanes& G, hipStream_t fork_src, const DevState& Sm, int knot_mode, int iter_l, const ilqr::WorkList* wl, bool concurrent_roll) {
+static int enqueue_region(const SolveCtx& X, const Lanes& G, hipStream_t fork_src, const DevState& Sm, int knot_mode, int iter_l, const ilqr::WorkList* wl, ilqr::NominalRoll roll) {
   ilqr_hip_ctx* c = X.c;
+  const bool concurrent_roll = roll == ilqr::ROLL_ASIDE;
   HIPCHK(c, hipEventRecord(G.fork, fork_src));
   if (G.m != fork_src) HIPCHK(c, hipStreamWaitEvent(G.m, G.fork, 0));
   HIPCHK(c, hipStreamWaitEvent(G.q, G.fork, 0));
@@ -1317,13 +1335,15 @@ static int enqueue_region(const SolveCtx& X, const Lanes& G, hipStream_t fork_sr
     HIPCHK(c, hipStreamWaitEvent(G.r, G.fork, 0));
     DevState Sr = Sm; Sr.xbar = X.shadow;
     { StageTimer T(c, 0, G.r); ilqr::launch_rollout(X.L, Sr, X.P, ilqr::MASK_ACTIVE, 1, 0, X.S.Jbase, G.r); }
+    c->nominal_rollouts += Sr.B;
     HIPCHK(c, hipEventRecord(G.roll, G.r));
   }
   { StageTimer T(c, 2, G.q); ilqr::launch_cost_quadratics(X.S, X.P, knot_mode, G.q, iter_l, X.L.lxx_layout, wl); }
   HIPCHK(c, hipEventRecord(G.join, G.q));
   { StageTimer T(c, 1, G.m); ilqr::launch_linearize(X.L, X.S, X.P, knot_mode, c->fd_eps, G.m, 3, iter_l, X.L.pack ? 1 : 0, wl, X.stance_dyn); }
-  if (concurrent_roll && G.lin && G.adopt) {
-    HIPCHK(c, hipEventRecord(G.lin, G.m));
+  const bool adopt_aside = concurrent_roll && G.lin && G.adopt;
+  if (G.lin && (adopt_aside || G.m != fork_src)) HIPCHK(c, hipEventRecord(G.lin, G.m));
+  if (adopt_aside) {
     HIPCHK(c, hipStreamWaitEvent(G.r, G.lin, 0)); HIPCHK(c, hipStreamWaitEvent(G.r, G.join, 0));
     ilqr::launch_adopt_rollout(Sm, X.shadow, ilqr::MASK_ACTIVE, c->d_mismatch, G.r);
     HIPCHK(c, hipEventRecord(G.adopt, G.r));
@@ -1333,7 +1353,7 @@ static int enqueue_region(const SolveCtx& X, const Lanes& G, hipStream_t fork_sr
 // t goes on only behind the adoption of the re-rolled trajectory (the line search reads it; the backward pass does not)
 static int wait_adoption(const SolveCtx& X, hipStream_t t) {
   if (X.adopt_aside) HIPCHK(X.c, hipStreamWaitEvent(t, X.G.adopt, 0));
-  if (X.prev_split) HIPCHK(X.c, hipStreamWaitEvent(t, X.GA.adopt, 0));
+  if (X.prev_split && X.a_adopts) HIPCHK(X.c, hipStreamWaitEvent(t, X.GA.adopt, 0));
   return ILQR_OK;
 }
 // a side-by-side pass: the second stream starts behind what G.m holds so far, and G.m goes on behind what the second stream was given
@@ -1443,14 +1463,14 @@ static int enqueue_sequential_iteration(const SolveCtx& X, const ilqr::Iteration
       ilqr::launch_cand_costs(Sf, P, ilqr::MASK_ACTIVE, st, false, gseq);
     } else ilqr::launch_line_search(L, S, P, ilqr::MASK_ACTIVE, st, iter, ls_bound); }
   { StageTimer T(c, 5, st); ilqr::launch_control(S, 0, iter, c->tol, c->early_exit | X.O.dedup_bit, st, L.ls_costs_per_knot, gseq); }      // :619-620,645-655
-  *split_next = X.O.can_split && iter + 1 < c->max_iter && ilqr::rolls_aside(X.O, L, iter + 1);
+  *split_next = ilqr::splits_next(X.O, L, iter, c->max_iter);
   if (*split_next) {
     // group A of iteration iter + 1: the first entries of its list, as many as the first control pass has just put there
     HIPCHK(c, hipMemcpyAsync(S.order_an + iter + 1, S.order_n + 2 * (iter + 1), sizeof(int), hipMemcpyDeviceToDevice, st));
     DevState Sg = S; Sg.active = S.grp_a;
     if (X.O.cache) HIPCHK(c, hipMemcpyAsync(S.chg_an + iter + 1, S.chg_n + iter + 1, sizeof(int), hipMemcpyDeviceToDevice, st));
     const ilqr::WorkList wa = X.O.cache ? ilqr::WorkList{S.chg + (size_t)(iter + 1) * S.B, S.chg_an + iter + 1} : ilqr::WorkList{S.order + (size_t)(2 * (iter + 1)) * S.B, S.order_an + iter + 1};
-    TRY(enqueue_region(X, X.GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, true));
+    TRY(enqueue_region(X, X.GA, st, Sg, ilqr::MASK_ACTIVE, -1, &wa, ilqr::nominal_roll(X.O, L, iter + 1)));
   }
   { StageTimer T(c, 6, st); ilqr::launch_backward(L, S, ilqr::MASK_RETRY, st, X.fold_h, iter); }                                // :637
   { StageTimer T(c, 7, st);                                                                                              // :638
@@ -1470,8 +1490,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
   const ilqr::LaunchPlan L = plan_of(c);
   const ilqr::SolveOrder O = ilqr::resolve_solve_order(solve_settings(c, S, G), L);
   SolveCtx X{c, S, P, L, O, G, group_a_lanes(c, G), lead,
-             c->d_shadowx + (S.xbar - c->S.xbar), c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N,
-             L.folds_h ? P.dyn.h : 0.0, c->twin ? twin_view(c, S) : S, 0, -1, false, false};
+             c->d_shadowx ? c->d_shadowx + (S.xbar - c->S.xbar) : nullptr, c->d_stance_dyn + (S.xbar - c->S.xbar) / ((long)(c->N + 1) * ILQR_NX) * 2L * c->N,
+             L.folds_h ? P.dyn.h : 0.0, c->twin ? twin_view(c, S) : S, 0, -1, false, ilqr::nominal_roll(O, L, 1) == ilqr::ROLL_ASIDE, false};
   { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st);
     // (rounds >= 2 of an augmented-Lagrangian solve with the convergence exit: the rollouts that are done enter inactive)
     if (P.al && c->al_round > 0 && c->early_exit) ilqr::launch_solve_begin_al(S, c->d_al_done + (S.active - c->S.active), st);
@@ -1497,16 +1517,17 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     }
     X.iter = iter;
     X.ls_bound = (O.gate && iter >= 2) ? c->h_active[iter - 1] : -1;
-    const bool concurrent_roll = ilqr::rolls_aside(O, L, iter);
+    const ilqr::NominalRoll roll = ilqr::nominal_roll(O, L, iter);
+    const bool concurrent_roll = roll == ilqr::ROLL_ASIDE;
     if (!X.prev_split) {
-      if ((iter == 0 || !O.reuse_rollout) && !concurrent_roll) { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); }
+      if (roll == ilqr::ROLL_BEFORE) { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ACTIVE, 1, 0, S.Jbase, st); c->nominal_rollouts += S.B; }
       if (iter == 0 && wait_lead) HIPCHK(c, hipStreamWaitEvent(st, wait_lead, 0));
       const ilqr::WorkList wc{S.chg + (size_t)iter * S.B, S.chg_n + iter};
-      TRY(enqueue_region(X, G, st, S, sel_mode, iter, (O.cache && iter > 0) ? &wc : nullptr, concurrent_roll));
+      TRY(enqueue_region(X, G, st, S, sel_mode, iter, (O.cache && iter > 0) ? &wc : nullptr, roll));
     } else {
       DevState Sg = S; Sg.active = S.grp_r;      // (the mask-selected kernels: every rollout of the group, changed or not)
       const ilqr::WorkList wr = O.cache ? ilqr::WorkList{S.chg_r, S.chg_rn + iter} : ilqr::WorkList{S.order_r, S.order_rn + iter};
-      TRY(enqueue_region(X, G, st, Sg, ilqr::MASK_ACTIVE, -1, &wr, true));
+      TRY(enqueue_region(X, G, st, Sg, ilqr::MASK_ACTIVE, -1, &wr, roll));      // (ROLL_ASIDE or ROLL_NONE: solve_order.h splits_next)
       ++c->split_iterations;
     }
     X.adopt_aside = concurrent_roll && G.lin && G.adopt;
@@ -1524,7 +1545,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
     X.prev_split = split_next; prev_seq = ord.kind == ilqr::ORDER_SEQUENTIAL;
   }
   if (X.prev_split) {      // (the convergence exit ended the loop behind a group A that found nothing to do: its streams rejoin)
-    HIPCHK(c, hipStreamWaitEvent(st, X.GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, X.GA.lin, 0)); HIPCHK(c, hipStreamWaitEvent(st, X.GA.adopt, 0));
+    HIPCHK(c, hipStreamWaitEvent(st, X.GA.join, 0)); HIPCHK(c, hipStreamWaitEvent(st, X.GA.lin, 0));
+    if (X.a_adopts) HIPCHK(c, hipStreamWaitEvent(st, X.GA.adopt, 0));
   }
   c->lin_iterations = c->iterations_enqueued;
   return ILQR_OK;
@@ -1532,6 +1554,8 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
 int ilqr_hip_set_relinearize_unchanged(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->relin = on ? 1 : 0; return ILQR_OK; }
 int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->repass = on ? 1 : 0; return ILQR_OK; }
 int ilqr_hip_set_listed_spec(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->listed_spec = on ? 1 : 0; return ILQR_OK; }
+int ilqr_hip_set_reroll_nominal(ilqr_hip_ctx* c, int on) { if (!c) return ILQR_ERR_ARG; c->reroll_nominal = on ? 1 : 0; return ILQR_OK; }
+long long ilqr_hip_get_nominal_rollouts(const ilqr_hip_ctx* c) { return c ? c->nominal_rollouts : -1; }
 // What the lists of the last solve held, iteration by iteration, read ONCE behind the handle's stream for the getters below: act[2 it] /
 // act[2 it + 1] the rollouts active at the start of iteration it / in its lambda retry (DevState::order_n), chg[it] and kr[it] the lengths of
 // its chg and kr lists, took[it] = 1 where it enqueued the listed pair and the device took the side-by-side order (word 4 of its gate
@@ -1728,7 +1752,8 @@ int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->d_mismatch, 0, sizeof(unsigned long long), st));
   const int k = slices_wanted(c, c->B);
   c->n_slices = k;
-  c->spec_iterations = 0; c->split_iterations = 0;
+  c->spec_iterations = 0; c->split_iterations = 0; c->nominal_rollouts = 0;
+  TRY(ensure_shadow(c, L));
   if (!c->twin && ilqr::resolve_solve_order(solve_settings(c, S, main_lanes(c)), L).twin_wanted) TRY(ensure_twin(c));
   if (L.pack && !c->ab_pads_clean) { ilqr::launch_pack_zero_pads(S, st); c->ab_pads_clean = true; }
   c->first_aside = c->xbar_rolled && c->rolled_variant == L.rollout && same_dyn(c->rolled_dyn, P.dyn);

@@ -2,7 +2,8 @@
 // LaunchPlan can do and which of the optional buffers it holds.  Host-only C++17 without a HIP include, like launch_plan.h: the C ABI
 // (ilqr_capi.hip) fills a SolveSettings from the handle (solve_settings), resolves one SolveOrder per enqueue (enqueue_solve) and asks
 // iteration_order once per iteration; neither it nor its getters test a switch themselves.  Nothing is cached: every function here is a
-// few comparisons.  tests/cpp/solve_order_dump.cpp prints them, tests/test_solve_order_cpu.py restates the rules.
+// few comparisons.  tests/cpp/solve_order_dump.cpp prints them, tests/test_solve_order_cpu.py restates the rules (nominal_roll and splits_next:
+// tests/cpp/nominal_roll_dump.cpp, tests/test_nominal_roll_cpu.py).
 #pragma once
 
 #include "launch_plan.h"
@@ -26,7 +27,7 @@ struct SolveSettings {
   bool relin;               // ilqr_hip_set_relinearize_unchanged / ILQR_RELIN
   bool repass;              // ilqr_hip_set_repeat_first_pass / ILQR_REPASS=1 (either one is enough)
   bool overlap_rollout;     // ILQR_OVERLAP_ROLLOUT
-  bool reuse_rollout;       // ILQR_REUSE_ROLLOUT
+  bool reuse_rollout;       // not ilqr_hip_set_reroll_nominal / ILQR_REUSE_ROLLOUT (on unless either asks for the re-roll: nominal_roll)
   int max_iter;
   int B;                    // rollouts of the view that is enqueued (the batch, or one slice of it)
   int slices;               // batch slices of the solve (1: the whole batch on one stream set)
@@ -134,7 +135,7 @@ struct SolveOrder {
   // The twin is allocated by the first solve that can take a side-by-side order: B <= spec_max, or the convergence exit with its gate on
   // (the late passes of any batch shrink below the threshold), or the listed order.  ILQR_SPEC=0 keeps a handle from ever allocating it.
   bool twin_wanted;
-  bool overlap_rollout, reuse_rollout, first_aside;      // rolls_aside
+  bool overlap_rollout, reuse_rollout, first_aside;      // rolls_aside, nominal_roll
 };
 
 inline SolveOrder resolve_solve_order(const SolveSettings& s, const LaunchPlan& L) {
@@ -160,16 +161,43 @@ inline SolveOrder resolve_solve_order(const SolveSettings& s, const LaunchPlan& 
   return o;
 }
 
-// The nominal re-rollout of iteration iter runs beside the linearisation.  From the second iteration on the nominal trajectory already is a
+// The nominal re-rollout of iteration iter runs beside the linearisation -- where it runs at all (nominal_roll below: the verification
+// mode, ILQR_REUSE_ROLLOUT=0 / ilqr_hip_set_reroll_nominal).  From the second iteration on the nominal trajectory already is a
 // rollout from x0 (the accepted line-search candidate, or the unchanged previous nominal), so the re-rollout reproduces it bit for bit
 // (ilqr_hip_get_adopt_mismatches): it runs beside the linearisation and is adopted (with its cost, the line-search baseline) once the
 // linearisation and the cost quadratics have read the old copy; the backward pass reads neither, only the line search waits for the
-// adoption.  ILQR_OVERLAP_ROLLOUT=0 restores the sequential order; ILQR_REUSE_ROLLOUT=1 skips the re-rollout (not the default: SURVEY 8(d)
-// counts it).  (only while the line search and the rollout run the same step implementation; iteration 0 as well when the nominal trajectory
-// is itself a rollout by this very kernel -- the cold start, initializeWithReference ilqr.cpp:113-115; a warm-shifted or caller-supplied
-// trajectory is rolled out BEFORE the linearisation, as the reference does)
+// adoption.  ILQR_OVERLAP_ROLLOUT=0 puts it in front of the region instead.  (only while the line search and the rollout run the same step
+// implementation; iteration 0 as well when the nominal trajectory is itself a rollout by this very kernel -- the cold start,
+// initializeWithReference ilqr.cpp:113-115; a warm-shifted or caller-supplied trajectory is rolled out BEFORE the linearisation, as the
+// reference does)
 inline bool rolls_aside(const SolveOrder& o, const LaunchPlan& L, int iter) {
   return (iter > 0 ? L.reroll_aside : (o.first_aside && L.cold_start_aside)) && !o.reuse_rollout && o.overlap_rollout;
+}
+
+// THE rule for the nominal rollout of iteration iter (ilqr.cpp:551,563), for every launch order and every augmented-Lagrangian round: not
+// at all, in front of the region on the solve's own stream, or beside the region into the shadow buffer with adoption and mismatch count.
+// With o.reuse_rollout (the default; ILQR_REUSE_ROLLOUT=0 or ilqr_hip_set_reroll_nominal(ctx, 1) clear it) a rollout whose result the
+// buffers already hold is not launched:
+//   iterations >= 1, L.reroll_aside -- the nominal trajectory is the previous one or an accepted line-search candidate, both rollouts from
+//     x0 by the step implementation the rollout kernel runs, so S.xbar holds the bits the re-roll would write; k_control, k_control_spec and
+//     k_control_listed have written S.Jbase = Jn on acceptance, summed along the knots in k_traj_cost_sum's order, so S.Jbase does too;
+//   iteration 0, o.first_aside and L.cold_start_aside -- S.xbar is a cold start by this very kernel under the present dynamics parameters
+//     (in rounds >= 2 of an augmented-Lagrangian solve: the trajectory the previous round left), and the cost-only call at the top of
+//     enqueue_solve has just written S.Jbase under the present weights and multipliers.
+// Everywhere else the rollout computes something new and runs BEFORE the region: a warm-shifted or caller-supplied trajectory, a new x0 or
+// schedule in iteration 0; every iteration of the mixed cross-check families of the test library, whose line search and rollout run
+// different step implementations (!L.reroll_aside).  Without o.reuse_rollout: what rolls_aside says, ASIDE or BEFORE, in every iteration.
+enum NominalRoll { ROLL_NONE = 0, ROLL_BEFORE = 1, ROLL_ASIDE = 2 };
+inline NominalRoll nominal_roll(const SolveOrder& o, const LaunchPlan& L, int iter) {
+  if (!o.reuse_rollout) return rolls_aside(o, L, iter) ? ROLL_ASIDE : ROLL_BEFORE;
+  return (iter > 0 ? L.reroll_aside : (o.first_aside && L.cold_start_aside)) ? ROLL_NONE : ROLL_BEFORE;
+}
+// The early-continuation split of iteration iter + 1 (SolveOrder::can_split) needs what the bit-identity rests on, not the re-rollout
+// itself: a group's region may start from S.xbar as the first control pass left it only where a re-roll would reproduce it.  Whether a
+// group's region launches a rollout is nominal_roll(o, L, iter + 1) -- ROLL_ASIDE or ROLL_NONE here, never ROLL_BEFORE (iter + 1 >= 1).
+// (ILQR_OVERLAP_ROLLOUT=0 without reuse: one group, as before)
+inline bool splits_next(const SolveOrder& o, const LaunchPlan& L, int iter, int max_iter) {
+  return o.can_split && iter + 1 < max_iter && L.reroll_aside && nominal_roll(o, L, iter + 1) != ROLL_BEFORE;
 }
 
 // pass_bound: an upper bound of the rollouts in this iteration's passes -- with the gate the count the host has seen at the start of

@@ -51,7 +51,7 @@ EXPORTS = [
     "ilqr_hip_plant_get_alive", "ilqr_hip_plant_state_device",
     "ilqr_hip_plant_follow", "ilqr_hip_initialize_warm_from_plant_shifted", "ilqr_hip_initialize_warm_resident_shifted", "ilqr_hip_compute_control_at",
     "ilqr_hip_set_relinearize_unchanged", "ilqr_hip_get_linearized_rollouts", "ilqr_hip_set_repeat_first_pass", "ilqr_hip_get_first_pass_rollouts",
-    "ilqr_hip_get_retry_pass_rollouts",
+    "ilqr_hip_get_retry_pass_rollouts", "ilqr_hip_set_reroll_nominal", "ilqr_hip_get_nominal_rollouts",
     "ilqr_hip_set_listed_spec", "ilqr_hip_get_listed_spec_iterations", "ilqr_hip_get_iteration_orders", "ilqr_hip_get_iteration_lists",
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
@@ -308,6 +308,21 @@ class BatchedILQR:
         n = int(fn(self.h))
         if n < 0:
             raise ILQRError("ilqr_hip_get_first_pass_rollouts: %s" % self.L.ilqr_hip_last_error(self.h).decode())
+        return n
+
+    def set_reroll_nominal(self, on=True):
+        """Run every nominal rollout the reference executes, beside the linearisation with adoption and mismatch count (verification);
+        off by default: a rollout whose result the buffers already hold -- iterations >= 1, iteration 0 behind a cold start -- is not
+        launched (ilqr_hip_set_reroll_nominal; as ILQR_REUSE_ROLLOUT=0)."""
+        self._chk(self.L.ilqr_hip_set_reroll_nominal(self.h, int(bool(on))))
+
+    def nominal_rollouts(self):
+        """Rollouts the nominal-rollout launches of the last solve were enqueued for (ilqr_hip_get_nominal_rollouts)."""
+        fn = self.L.ilqr_hip_get_nominal_rollouts
+        fn.restype = C.c_longlong
+        n = int(fn(self.h))
+        if n < 0:
+            raise ILQRError("ilqr_hip_get_nominal_rollouts: null handle")
         return n
 
     def reload_environment(self):
