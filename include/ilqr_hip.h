@@ -229,6 +229,63 @@ int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* ctx, double* viol /*[B]*/);
 int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][2]*/);
 /* The state slot of box coordinate k; -1 outside 0..27.  Host only: no GPU, no handle. */
 int ilqr_hip_al_state_slot(int k);
+/* Bounds that change from knot to knot: a WINDOW of bounds per set in place of one record per set.  ilqr_hip_set_al_knot_bounds takes
+   [n_sets][N+1][76], row t in the field order of ilqr_hip_set_al_bounds; ilqr_hip_set_al_state_knot_bounds takes [n_sets][N+1][56], row t in
+   the field order of ilqr_hip_set_al_state_bounds, with that call's rho_state0 and tol_state.  n_sets is 1 (every rollout reads the one
+   window) or the batch (rollout b reads window b).  At knot t of rollout b every constraint of the family takes its lo / hi from row t of
+   rollout b's window: the hinges and the box coordinates at the knots 0..N, the actuators at the knots 0..N-1 (the torque fields of row N are
+   validated like every other row and never read).  Everything else stays word for word what ilqr_hip_set_augmented_lagrangian,
+   ilqr_hip_set_al_bounds and ilqr_hip_set_al_state_bounds describe: the term phi, the update mu <- max(0, mu + rho c), knot 0 carrying the
+   cost term but zero multipliers and left out of the violation, viol_*, the done rule, rho growth, the rounds, the -inf / +inf "side off"
+   rule, and "acts on the COST only" (dynamics, plant, score and the plain penalties are untouched).
+   The later call wins within a family: a window replaces a whole-horizon table of that family (multipliers are kept, as when a table
+   replaces a table; the state family's rho_state = rho_state0 either way, and its multipliers are zeroed only where no state family was
+   installed); ilqr_hip_set_al_bounds / ilqr_hip_set_al_state_bounds replace a window; ilqr_hip_clear_al_bounds /
+   ilqr_hip_clear_al_state_bounds drop whichever is installed.  The two families are independent: either may have a window, a table or
+   (joint / torque) the model's bounds.  While one family has a window the library itself repeats the other family's record over the knots on
+   the device, so that one kernel instantiation serves the mixed cases; the results are those of the record.
+   The window is horizon-local: a warm start shifts the multipliers as it does today and does not move the window -- the caller, or the
+   bounds track below, writes the next one.  It survives the cold and warm initialisers, ilqr_hip_set_al_multipliers and a repeated
+   ilqr_hip_set_augmented_lagrangian; ilqr_hip_clear_augmented_lagrangian drops it.
+   ILQR_ERR_STATE while no augmented Lagrangian is installed.  ILQR_ERR_ARG: a null pointer, n_sets not 1 or the batch, a NaN, lo > hi,
+   lo == +inf or hi == -inf in any row, rho_state0 <= 0 or not finite, tol_state < 0; everything is checked before the handle is touched, a
+   refused call leaves what was installed as it was.  ILQR_ERR_UNSUPPORTED when the kernels that read windows cannot be loaded: they live in
+   libilqr_hip_alknot.so beside the library, opened by the first of these calls.  Allocates the two window buffers on first use ([B][N+1]
+   records of 80 and of 64 doubles).  Uploads and synchronises the handle's stream.  The refusals of ilqr_hip_set_augmented_lagrangian
+   (cross-check families, weight sets) stay as they are. */
+int ilqr_hip_set_al_knot_bounds(ilqr_hip_ctx* ctx, const double* bounds /*[n_sets][N+1][76]*/, int n_sets);
+int ilqr_hip_set_al_state_knot_bounds(ilqr_hip_ctx* ctx, const double* bounds /*[n_sets][N+1][56]*/, int n_sets, double rho_state0, double tol_state);
+/* What each rollout is solved with at each knot, whoever wrote it: a window (of a setter or of ilqr_hip_al_bounds_window_from_track), a
+   whole-horizon record repeated over the knots, or without any table the model's bounds at the installed margin (joint_ctrl) and -inf / +inf
+   (state).  Either pointer may be NULL.  Synchronises the handle's stream.  ILQR_ERR_STATE while no augmented Lagrangian is installed.
+   On a handle with a window of a family, ilqr_hip_get_al_bounds / ilqr_hip_get_al_state_bounds of that family return ILQR_ERR_STATE (one
+   record per rollout cannot describe it; the error text names this call); in every other state they behave as before.
+   ilqr_hip_num_al_bound_sets / ilqr_hip_num_al_state_bound_sets report the installed n_sets, table or window. */
+int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* ctx, double* joint_ctrl /*[B][N+1][76] or NULL*/, double* state /*[B][N+1][56] or NULL*/);
+/* Bit 0: the joint / torque family has a window; bit 1: the state family has one.  0 without an augmented Lagrangian; -1 for a null handle. */
+int ilqr_hip_al_bounds_per_knot(const ilqr_hip_ctx* ctx);
+/* A bounds track, cut on the device as the reference windows are (ilqr_hip_set_reference_track): `rows` >= 1 rows on the loop's timeline,
+   joint_ctrl [rows][76] and / or state [rows][56] in the field orders above (at least one part; a NULL part is not cut and that family
+   stays as installed).  One upload; the handle owns the copy and a new track replaces it (the starts go back to one shared start of 0).
+   A state part needs an installed state family (table or window), else ILQR_ERR_STATE: the track supplies the bounds, the installation
+   rho_state0 and tol_state.  Validation as for the setters, row by row (ILQR_ERR_ARG; ILQR_ERR_STATE without an augmented Lagrangian;
+   ILQR_ERR_UNSUPPORTED without the module).  Synchronises the handle's stream. */
+int ilqr_hip_set_al_bounds_track(ilqr_hip_ctx* ctx, int rows, const double* joint_ctrl /*[rows][76] or NULL*/, const double* state /*[rows][56] or NULL*/);
+/* Frees the track; the windows last written stay installed.  Synchronises the handle's stream. */
+int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* ctx);
+/* Rows of the installed bounds track; 0 without one, -1 for a null handle */
+int ilqr_hip_al_bounds_track_rows(const ilqr_hip_ctx* ctx);
+/* One start row per set, kept on the device: n_sets is 1 (one start for every rollout) or the batch; every start >= 0 (ILQR_ERR_ARG).
+   Default: one shared start of 0.  ILQR_ERR_STATE without a bounds track. */
+int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* ctx, const int* start /*[n_sets]*/, int n_sets);
+/* Enqueues one kernel on the handle's stream (al_bounds_track_kernels.hip), no upload, no synchronisation: for set b and t = 0..N it writes
+   row min(start[b] + step + t, rows - 1) of each part of the track into row t of set b's window of that part -- the end clamp of x_ref.  A
+   pure copy: the windows are bit for bit what the knot setters would upload, and afterwards the handle is in the state those setters
+   leave, with n_sets equal to the number of starts (multipliers and penalties untouched).  Where that state differs from the one before --
+   the first cut, or after other starts -- and the other family has no window, the same call also enqueues the copy that repeats that
+   family's record over the knots.  step >= 0, else ILQR_ERR_ARG.  ILQR_ERR_STATE without an augmented Lagrangian, without a track, or with
+   a state part while no state family is installed. */
+int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* ctx, int step);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N

@@ -143,6 +143,34 @@ class iLQR {
     chk(ilqr_hip_get_al_state_violation(ctx_, out.data()));
     return out;
   }
+  // bounds that change from knot to knot (ilqr_hip_set_al_knot_bounds): windows, row-major [n_sets][N+1][ILQR_AL_BOUNDS] /
+  // [n_sets][N+1][ILQR_AL_STATE_BOUNDS], n_sets = 1 or the batch; getAlKnotBounds: what each rollout is solved with at each knot, whoever
+  // wrote it, (joint_ctrl [batch][N+1][76], state [batch][N+1][56]); alBoundsPerKnot: bit 0 joint / torque window, bit 1 state window
+  void setAlKnotBounds(const std::vector<double>& bounds, int n_sets) {
+    if (n_sets <= 0 || bounds.size() != (size_t)n_sets * (ilqr_hip_horizon(ctx_) + 1) * ILQR_AL_BOUNDS) chk(ILQR_ERR_ARG);
+    chk(ilqr_hip_set_al_knot_bounds(ctx_, bounds.data(), n_sets));
+  }
+  void setAlStateKnotBounds(const std::vector<double>& bounds, int n_sets, double rho_state0, double tol_state) {
+    if (n_sets <= 0 || bounds.size() != (size_t)n_sets * (ilqr_hip_horizon(ctx_) + 1) * ILQR_AL_STATE_BOUNDS) chk(ILQR_ERR_ARG);
+    chk(ilqr_hip_set_al_state_knot_bounds(ctx_, bounds.data(), n_sets, rho_state0, tol_state));
+  }
+  std::pair<std::vector<double>, std::vector<double>> getAlKnotBounds() {
+    const size_t knots = (size_t)ilqr_hip_batch(ctx_) * (ilqr_hip_horizon(ctx_) + 1);
+    std::vector<double> jc(knots * ILQR_AL_BOUNDS), st(knots * ILQR_AL_STATE_BOUNDS);
+    chk(ilqr_hip_get_al_knot_bounds(ctx_, jc.data(), st.data()));
+    return {jc, st};
+  }
+  int alBoundsPerKnot() const { return ilqr_hip_al_bounds_per_knot(ctx_); }
+  // a bounds track cut on the device (ilqr_hip_set_al_bounds_track): joint_ctrl [rows][76] and / or state [rows][56] (an empty vector: that
+  // part is not given), one start row per set, and the kernel that writes the windows of MPC step `step`
+  void setAlBoundsTrack(int rows, const std::vector<double>& joint_ctrl, const std::vector<double>& state) {
+    if (rows <= 0 || (!joint_ctrl.empty() && joint_ctrl.size() != (size_t)rows * ILQR_AL_BOUNDS) || (!state.empty() && state.size() != (size_t)rows * ILQR_AL_STATE_BOUNDS)) chk(ILQR_ERR_ARG);
+    chk(ilqr_hip_set_al_bounds_track(ctx_, rows, joint_ctrl.empty() ? nullptr : joint_ctrl.data(), state.empty() ? nullptr : state.data()));
+  }
+  void clearAlBoundsTrack() { chk(ilqr_hip_clear_al_bounds_track(ctx_)); }
+  int alBoundsTrackRows() const { return ilqr_hip_al_bounds_track_rows(ctx_); }
+  void setAlBoundsTrackStarts(const std::vector<int>& start) { chk(ilqr_hip_set_al_bounds_track_starts(ctx_, start.data(), (int)start.size())); }
+  void alBoundsWindowFromTrack(int step) { chk(ilqr_hip_al_bounds_window_from_track(ctx_, step)); }
   void setGravity(double gx, double gy, double gz) { chk(ilqr_hip_set_gravity(ctx_, gx, gy, gz)); }
   void setContactSchedule(const std::vector<int>& stance /*[N+1][2]*/) { chk(ilqr_hip_set_contact_schedule(ctx_, stance.data(), 1)); }
   // contact row: ILQR_CONTACT_NONE (default) or ILQR_CONTACT_RIGID_STANCE on the scheduled feet

@@ -6,6 +6,8 @@
 //                      (ilqr_hip_set_al_bounds), <false> the model's ranges at the installed margin; <., true>: and the state family
 //                      (ilqr_hip_set_al_state_bounds: the second store, AlDev::sstore) -- a third loop, a third maximum, the done rule over
 //                      all three families, the growth of rho_state and the state trace row
+//                      <., ., true>: the bounds of knot t are row t of the rollout's windows (ilqr_hip_set_al_knot_bounds ...); instantiated
+//                      in libilqr_hip_alknot.so only (al_knot_kernels.hip includes this file with -DAL_KNOT_MODULE: the kernel alone)
 //   k_al_shift         warm-start shift of the multipliers by the knots the trajectory is shifted by (zero tail; shift > N: all zero), penalties reset
 //   k_al_state_shift   the same for the state family's store: every column shifts as a hinge column does (knot 0 stays zero)
 //   k_solve_begin_al   k_solve_begin with active = !done: the prologue of the rounds >= 2 of a solve with the convergence exit
@@ -26,7 +28,8 @@ __device__ __forceinline__ double wave_max(double v) {
 
 // Constraint e of a knot's record, e in [0, 38): side = e / 19 (0 lower, 1 upper bound), coordinate e % 19.  The multiplier sits at
 // base + e for both families (AL_JHI = AL_JLO + 19, AL_UHI = AL_ULO + 19).
-template <bool TABLE, bool STATE>
+// KNOT: the bounds of knot t are row t of the rollout's windows (AlDev::bounds_knot, sbounds_knot); instantiated in the per-knot module only
+template <bool TABLE, bool STATE, bool KNOT = false>
 __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round, int masked) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -43,7 +46,8 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
   for (int e = lane; e < N * 2 * H1_NJ; e += 64) {
     const int t = 1 + e / (2 * H1_NJ), r = e % (2 * H1_NJ), side = r / H1_NJ, j = r % H1_NJ;
     double lo, hi;
-    if constexpr (TABLE) { lo = bd[ALB_JLO + j]; hi = bd[ALB_JHI + j]; } else al_bounds(H1_JRANGE[j], A.margin, lo, hi);
+    if constexpr (KNOT) { const double* bk = bd + (long)t * A.bounds_knot; lo = bk[ALB_JLO + j]; hi = bk[ALB_JHI + j]; }
+    else if constexpr (TABLE) { lo = bd[ALB_JLO + j]; hi = bd[ALB_JHI + j]; } else al_bounds(H1_JRANGE[j], A.margin, lo, hi);
     const double q = xb[t * H1_NX + 7 + j];
     const double c = side ? q - hi : lo - q;
     vj = c > vj ? c : vj;
@@ -57,7 +61,8 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
   for (int e = lane; e < N * 2 * H1_NU; e += 64) {
     const int t = e / (2 * H1_NU), r = e % (2 * H1_NU), side = r / H1_NU, i = r % H1_NU;
     double lo, hi;
-    if constexpr (TABLE) { lo = bd[ALB_ULO + i]; hi = bd[ALB_UHI + i]; } else al_bounds(H1_CTRLRANGE[i], A.margin, lo, hi);
+    if constexpr (KNOT) { const double* bk = bd + (long)t * A.bounds_knot; lo = bk[ALB_ULO + i]; hi = bk[ALB_UHI + i]; }
+    else if constexpr (TABLE) { lo = bd[ALB_ULO + i]; hi = bd[ALB_UHI + i]; } else al_bounds(H1_CTRLRANGE[i], A.margin, lo, hi);
     const double u = ub[t * H1_NU + i];
     const double c = side ? u - hi : lo - u;
     vc = c > vc ? c : vc;
@@ -77,7 +82,8 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
     for (int e = lane; e < N * 2 * ALS_COORDS; e += 64) {
       const int t = 1 + e / (2 * ALS_COORDS), r = e % (2 * ALS_COORDS), side = r / ALS_COORDS, k = r % ALS_COORDS;
       const double v = xb[t * H1_NX + als_slot(k)];
-      const double c = side ? v - sb[ALSB_HI + k] : sb[ALSB_LO + k] - v;
+      const double* sk = KNOT ? sb + (long)t * A.sbounds_knot : sb;
+      const double c = side ? v - sk[ALSB_HI + k] : sk[ALSB_LO + k] - v;
       vs = c > vs ? c : vs;
       if (!was_done) {
         double* mu = srec + ALS_HDR + (long)t * ALS_KNOT + ALS_LO + r;
@@ -104,6 +110,7 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
   atomicAdd(A.left + round, 1);
 }
 
+#ifndef AL_KNOT_MODULE
 // Each lane owns one column of the knot records and walks the knots upwards: it reads knot t + shift after it has written every knot < t, so
 // the shift is in place without a barrier.
 __global__ void __launch_bounds__(128) k_al_shift(AlDev A, int N, int shift, double rho_joint, double rho_ctrl) {
@@ -169,7 +176,8 @@ __global__ void __launch_bounds__(64) k_solve_begin_al(DevState S, const int* do
 }
 
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st) {
-  if (A.sbounds && A.bounds) hipLaunchKernelGGL((k_al_update<true, true>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);      // (a state table brings a bounds record with it)
+  if (A.bounds && A.bounds_knot) g_al_knot.al_update(&S, &A, round, masked, st);      // (windows: the module's instantiations)
+  else if (A.sbounds && A.bounds) hipLaunchKernelGGL((k_al_update<true, true>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);      // (a state table brings a bounds record with it)
   else if (A.bounds) hipLaunchKernelGGL((k_al_update<true, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);
   else hipLaunchKernelGGL((k_al_update<false, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);
 }
@@ -178,5 +186,6 @@ void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, 
   if (A.sbounds) hipLaunchKernelGGL(k_al_state_shift, dim3(B), dim3(64), 0, st, A, N, shift);
 }
 void launch_solve_begin_al(const DevState& S, const int* done, hipStream_t st) { hipLaunchKernelGGL(k_solve_begin_al, dim3(1), dim3(64), 0, st, S, done); }
+#endif      // AL_KNOT_MODULE
 
 }  // namespace ilqr

@@ -26,6 +26,9 @@ __device__ __forceinline__ bool sel(const DevState& S, int b, int mode) {
   return S.active[b] != 0 && S.need_retry[b] != 0;
 }
 
+// -DAL_KNOT_MODULE (csrc/Makefile, libilqr_hip_alknot.so; ilqr_kernels.h AlKnotModule): this file once more as the per-knot instantiations of
+// the two knot-cost kernels and their entry points alone -- none of the library's own kernels and launchers
+#ifndef AL_KNOT_MODULE
 #ifdef ILQR_LEGACY_KERNELS
 __global__ void __launch_bounds__(64) k_rollout_r(DevState S, ProblemDev P, int mode, int do_roll, int count_iter, double* cost_out) {
   extern __shared__ double lds[];
@@ -217,6 +220,7 @@ __global__ void __launch_bounds__(64) k_line_search_r(DevState S, ProblemDev P, 
 #endif
 }
 #endif
+#endif      // AL_KNOT_MODULE
 
 // computeTotalCost (ilqr.cpp:363-518) of the 8 line-search candidates of every rollout, taken off the serial rollout of
 // the two-lanes-per-candidate line search (k_line_search_s, where it cost 78 k of 194 k cycles per step):
@@ -233,7 +237,8 @@ __global__ void __launch_bounds__(64) k_line_search_r(DevState S, ProblemDev P, 
 // of the plain penalties; AL_TABLE with the bounds of the lane's own rollout (ProblemDev::alb: the knots and the eight candidates of a
 // rollout read the same five lines).  The state family (ilqr_hip_set_al_state_bounds) is not an instantiation of this kernel: with its 56 terms
 // inlined the kernel needs 268 + 12 registers and drops to one wave per SIMD (docs/KERNEL_RESOURCES_AL_STATE.md); k_al_state_knot_cost below adds
-// them to the knot costs this kernel has written.
+// them to the knot costs this kernel has written.  AL_KNOT_TABLE (windows of bounds, ProblemDev::alb_knot): the lane reads row t of its rollout's
+// window, five lines of its own; instantiated in libilqr_hip_alknot.so only (the entry points below).
 template <bool WS, int AL>
 __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate) {
   if (gate && *gate == 0) return;
@@ -284,6 +289,8 @@ __global__ void __launch_bounds__(64) k_traj_knot_cost(DevState S, ProblemDev P,
 // k_traj_cost_sum): one lane per (candidate, knot) under the same numbering, selection and gate.  al_state_term is the last term of the knot
 // cost either way -- c + term, one rounding -- so the sum is the one an instantiation of k_traj_knot_cost would have stored.  The lane reads its
 // 28 coordinates from the row itself (224 of its 408 bytes) and the four lines of multipliers and the four of bounds of its rollout and knot.
+// KNOT: the bounds are row t of the rollout's window (ProblemDev::alsb_knot); <false> is the kernel as it was.
+template <bool KNOT>
 __global__ void __launch_bounds__(64) k_al_state_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, int cshift, int oshift, const int* gate) {
   if (gate && *gate == 0) return;
   const int N = S.N;
@@ -294,8 +301,20 @@ __global__ void __launch_bounds__(64) k_al_state_knot_cost(DevState S, ProblemDe
   const long cand = idx / (N + 1);
   const int b = (int)(cand >> cshift);
   if (!sel(S, b, mode)) return;
-  S.cand_knot[((cand << oshift) * (N + 1)) + t] += al_state_term(P, b, t, xsrc + idx * H1_NX);
+  S.cand_knot[((cand << oshift) * (N + 1)) + t] += al_state_term<KNOT>(P, b, t, xsrc + idx * H1_NX);
 }
+#ifdef AL_KNOT_MODULE
+}  // namespace ilqr
+// the module's entry points (ilqr_kernels.h AlKnotModule): the launches launch_cand_costs / launch_nominal_costs make, on the per-knot instantiations
+extern "C" void ilqr_alknot_module_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate, hipStream_t st) {
+  const long total = ((long)S->B << cshift) * (S->N + 1);
+  hipLaunchKernelGGL((ilqr::k_traj_knot_cost<false, AL_KNOT_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, *S, *P, mode, xsrc, usrc, cshift, oshift, gate);
+}
+extern "C" void ilqr_alknot_module_state_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st) {
+  const long total = ((long)S->B << cshift) * (S->N + 1);
+  hipLaunchKernelGGL(ilqr::k_al_state_knot_cost<true>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, *S, *P, mode, xsrc, cshift, oshift, gate);
+}
+#else
 __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int cshift, int oshift, double* cost_out) {
   const int cand = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = cand >> cshift;
@@ -307,21 +326,25 @@ __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int 
 }
 void launch_cand_costs(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, bool with_sum, const int* gate) {
   const long total = (long)S.B * 8 * (S.N + 1);
-  if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
+  if (P.al && P.alb && P.alb_knot) g_al_knot.knot_cost(&S, &P, mode, S.xcand, S.ucand, 3, 0, gate, st);      // (windows of bounds: the module's instantiation)
+  else if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
   else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, 3, 0, gate);
+  if (P.al && P.alsb && P.alsb_knot) g_al_knot.state_knot_cost(&S, &P, mode, S.xcand, 3, 0, gate, st);
+  else if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, 3, 0, gate);
   if (with_sum) hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)(((long)S.B * 8 + 63) / 64)), dim3(64), 0, st, S, mode, 3, 0, S.cand_cost);
 }
 // computeTotalCost of the nominal trajectories (S.xbar, S.ubar) into cost_out[B], same kernels, same summation order
 void launch_nominal_costs(const DevState& S, const ProblemDev& P, int mode, double* cost_out, hipStream_t st) {
   const long total = (long)S.B * (S.N + 1);
-  if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
+  if (P.al && P.alb && P.alb_knot) g_al_knot.knot_cost(&S, &P, mode, S.xbar, S.ubar, 0, 3, nullptr, st);      // (windows of bounds: the module's instantiation)
+  else if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
   else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, 0, 3, (const int*)nullptr);
+  if (P.al && P.alsb && P.alsb_knot) g_al_knot.state_knot_cost(&S, &P, mode, S.xbar, 0, 3, nullptr, st);
+  else if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, 0, 3, (const int*)nullptr);
   hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)((S.B + 63) / 64)), dim3(64), 0, st, S, mode, 0, 3, cost_out);
 }
 
@@ -417,3 +440,4 @@ void launch_lin_primal_r(const DevState&, const ProblemDev&, int, hipStream_t) {
 #endif
 
 }  // namespace ilqr
+#endif      // AL_KNOT_MODULE

@@ -53,6 +53,11 @@ struct ProblemDev {
   // when one record serves every rollout (layouts below).  Read while `al` is installed only.  Appended: nothing above moves
   const double* als;         long als_stride;
   const double* alsb;        long alsb_stride;
+  // bounds that change from knot to knot (ilqr_hip_set_al_knot_bounds, ilqr_hip_set_al_state_knot_bounds, ilqr_hip_al_bounds_window_from_track):
+  // 0 = one record per set as above; else alb / alsb point at windows, [N+1] records per set, knot-major, knot t's record alb_knot / alsb_knot
+  // doubles behind knot 0's (ALB_STRIDE / ALSB_STRIDE) and alb_stride / alsb_stride the doubles of one set's window (0: one window for all).
+  // Both are set or both are 0 while a state family is installed (ilqr_capi.hip al_point_bounds).  Appended: nothing above moves
+  long alb_knot, alsb_knot;
 };
 // The multiplier store, in doubles.  Rollout b's record: one 128-byte line of scalars (AL_RHO_JOINT, AL_RHO_CTRL, the rest padding), then one
 // record of AL_KNOT = 80 doubles (five whole lines) per knot t = 0..N: the hinges' multipliers of the lower bounds, of the upper bounds, two
@@ -84,9 +89,13 @@ constexpr int als_slot(int k) { return k < 3 ? k : 23 + k; }
 // AL_TABLE_STATE: AL_TABLE with the state family (ProblemDev::als, alsb) on top.  There is no AL_MODEL_STATE: while a state table is
 // installed without a joint / torque table, ProblemDev::alb points at one record of the model's bounds at the installed margin, the same
 // doubles al_bounds forms (ilqr_capi.hip al_point_bounds) -- a second state instantiation of k_cost_quadratics costs the library 29 KB.
-enum { AL_OFF = 0, AL_MODEL = 1, AL_TABLE = 2, AL_TABLE_STATE = 3 };
-constexpr bool al_table(int AL) { return AL == AL_TABLE || AL == AL_TABLE_STATE; }
-constexpr bool al_state(int AL) { return AL == AL_TABLE_STATE; }
+// AL_KNOT_TABLE / AL_KNOT_TABLE_STATE: AL_TABLE / AL_TABLE_STATE with the bounds of knot t taken from row t of rollout b's window
+// (ProblemDev::alb_knot, alsb_knot).  Instantiations of their own, so that the four above keep their machine code; there is no mixed one:
+// while one family has a window the library expands the other family's record into a window of equal rows.
+enum { AL_OFF = 0, AL_MODEL = 1, AL_TABLE = 2, AL_TABLE_STATE = 3, AL_KNOT_TABLE = 4, AL_KNOT_TABLE_STATE = 5 };
+constexpr bool al_table(int AL) { return AL == AL_TABLE || AL == AL_TABLE_STATE || AL == AL_KNOT_TABLE || AL == AL_KNOT_TABLE_STATE; }
+constexpr bool al_state(int AL) { return AL == AL_TABLE_STATE || AL == AL_KNOT_TABLE_STATE; }
+constexpr bool al_per_knot(int AL) { return AL == AL_KNOT_TABLE || AL == AL_KNOT_TABLE_STATE; }
 // Bounds lo = r0 + m (r1 - r0), hi = r1 - m (r1 - r0), each operation rounded once (no contraction): every kernel and the host restatement
 // of the tests then hold the same two doubles
 DEVFN void al_bounds(const double* range, double m, double& lo, double& hi) {
@@ -108,6 +117,7 @@ template <int AL>
 DEVFN double al_joint_term(const ProblemDev& P, int b, int t, const double* x) {
   const double* r = P.al + (long)b * P.al_stride;
   const double* bd = P.alb + (long)b * P.alb_stride;      // (AL_TABLE only)
+  if constexpr (al_per_knot(AL)) bd += (long)t * P.alb_knot;
   const double rho = r[AL_RHO_JOINT];
   const double* k = r + AL_HDR + (long)t * AL_KNOT;
   double c = 0.0;
@@ -125,6 +135,7 @@ template <int AL>
 DEVFN double al_ctrl_term(const ProblemDev& P, int b, int t, const double* u) {
   const double* r = P.al + (long)b * P.al_stride;
   const double* bd = P.alb + (long)b * P.alb_stride;      // (AL_TABLE only)
+  if constexpr (al_per_knot(AL)) bd += (long)t * P.alb_knot;
   const double rho = r[AL_RHO_CTRL];
   const double* k = r + AL_HDR + (long)t * AL_KNOT;
   double c = 0.0;
@@ -138,10 +149,12 @@ DEVFN double al_ctrl_term(const ProblemDev& P, int b, int t, const double* u) {
   return c / (2.0 * rho);
 }
 // the state family's terms of knot t of rollout b, every knot (the terminal one included); added to the knot cost by a kernel of its own
-// (dyn_kernels.hip k_al_state_knot_cost), not by knot_cost_w
+// (dyn_kernels.hip k_al_state_knot_cost), not by knot_cost_w.  KNOT: the bounds are row t of rollout b's window
+template <bool KNOT = false>
 DEVFN double al_state_term(const ProblemDev& P, int b, int t, const double* x) {
   const double* r = P.als + (long)b * P.als_stride;
   const double* bd = P.alsb + (long)b * P.alsb_stride;
+  if constexpr (KNOT) bd += (long)t * P.alsb_knot;
   const double rho = r[ALS_RHO];
   const double* k = r + ALS_HDR + (long)t * ALS_KNOT;
   double c = 0.0;

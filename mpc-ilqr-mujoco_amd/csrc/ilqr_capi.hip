@@ -22,6 +22,7 @@
 #include "solve_order.h"
 #include "plant_score_kernels.h"
 #include "reference_track_kernels.h"
+#include "al_bounds_track_kernels.h"
 
 using ilqr::DevState;
 
@@ -118,6 +119,15 @@ struct ilqr_hip_ctx {
   int n_alsb = 0;
   double als_rho0 = 0.0, als_tol = 0.0;
   std::vector<double> h_alsb;
+  // windows of bounds (ilqr_hip_set_al_knot_bounds, ilqr_hip_set_al_state_knot_bounds, ilqr_hip_al_bounds_window_from_track): d_albk [B][N+1][ALB_STRIDE],
+  // d_alsbk [B][N+1][ALSB_STRIDE]; albk / alsbk: that family's installed bounds are a window (n_alb / n_alsb then its n_sets, h_alb / h_alsb stale).
+  // While either is set P.alb / P.alsb point at the windows and the other family's record is expanded into its window (al_point_bounds).
+  // The bounds track (ilqr_hip_set_al_bounds_track): d_abt_jc [rows][ALB_STRIDE], d_abt_st [rows][ALSB_STRIDE], either may be null; its start rows
+  // d_abt_start [B] on the device (allocated with the handle's first track)
+  double *d_albk = nullptr, *d_alsbk = nullptr, *d_abt_jc = nullptr, *d_abt_st = nullptr;
+  int* d_abt_start = nullptr;
+  bool albk = false, alsbk = false;
+  int abt_rows = 0, abt_sets = 1;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
@@ -337,18 +347,76 @@ static inline int enter_launching(ilqr_hip_ctx* c) {
   if (c->P.al) if (const char* why = al_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   return ILQR_OK;
 }
-// Where the joint / torque family takes its bounds from: the installed table; without one null (the model's ranges at P.al_margin, formed in
-// the kernels) -- or, while a state table is installed, one record of those same doubles (h1host::al_default_bounds)
-static int al_point_bounds(ilqr_hip_ctx* c) {
-  if (c->n_alb) { c->P.alb = c->d_alb; c->P.alb_stride = c->n_alb == 1 ? 0 : (long)h1::ALB_STRIDE; return ILQR_OK; }
-  c->P.alb = nullptr; c->P.alb_stride = 0;
-  if (!c->P.al || !c->n_alsb) return ILQR_OK;
-  double rec[h1::ALB_STRIDE] = {0};
-  h1host::al_default_bounds(c->P.al_margin, rec);
-  if (!c->d_alb_model) TRY(dalloc(c, &c->d_alb_model, (size_t)h1::ALB_STRIDE));
-  HIPCHK(c, hipMemcpyAsync(c->d_alb_model, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->P.alb = c->d_alb_model;
+// libilqr_hip_<stem>.so in the directory this library was loaded from
+__attribute__((noinline, minsize)) static std::string module_path(const char* stem) {
+  Dl_info info;
+  std::string dir = ".";
+  if (dladdr((const void*)&ilqr_hip_al_default_bounds, &info) && info.dli_fname) {
+    const std::string self = info.dli_fname;
+    const size_t slash = self.rfind('/');
+    if (slash != std::string::npos) dir = self.substr(0, slash);
+  }
+  return dir + "/libilqr_hip_" + stem + ".so";
+}
+// The per-knot instantiations of the cost kernels and of k_al_update live in libilqr_hip_alknot.so (ilqr_kernels.h AlKnotModule), opened on the
+// first call that installs a window from the directory this library was loaded from.  Missing module or entry point: ILQR_ERR_UNSUPPORTED.
+namespace ilqr { AlKnotModule g_al_knot = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; }
+__attribute__((noinline, minsize)) static int need_al_knot_module(ilqr_hip_ctx* c) {
+  static std::once_flag once;
+  static std::string why;
+  std::call_once(once, [] {
+    const std::string path = module_path("alknot");
+    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    // one exported symbol: the table of the module's entry points (al_knot_kernels.hip)
+    const auto table = lib ? (const ilqr::AlKnotModule* (*)())dlsym(lib, "ilqr_alknot_module") : nullptr;
+    if (!table) { why = "module missing or without its entry point: " + path; return; }
+    ilqr::g_al_knot = *table();
+  });
+  if (!ilqr::g_al_knot.al_update) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  return ILQR_OK;
+}
+// Where the two families take their bounds from.  No window installed: the joint / torque family from the installed table; without one null
+// (the model's ranges at P.al_margin, formed in the kernels) -- or, while a state table is installed, one record of those same doubles
+// (h1host::al_default_bounds); the state family from its table.  A window of either family installed (albk / alsbk; the module is loaded):
+// both families read windows -- a family that has none gets its record (the table's, or the model's) repeated over the knots by
+// k_al_bounds_expand, device to device, so that two per-knot instantiations of k_cost_quadratics serve every combination.
+__attribute__((noinline, minsize)) static int al_point_bounds(ilqr_hip_ctx* c) {
+  c->P.alb_knot = 0; c->P.alsb_knot = 0;
+  const bool knot = c->P.al && (c->albk || c->alsbk);
+  if (c->P.al && c->n_alsb) { c->P.alsb = c->d_alsb; c->P.alsb_stride = c->n_alsb == 1 ? 0 : (long)h1::ALSB_STRIDE; }
+  if (c->n_alb && !c->albk) { c->P.alb = c->d_alb; c->P.alb_stride = c->n_alb == 1 ? 0 : (long)h1::ALB_STRIDE; }
+  else {
+    c->P.alb = nullptr; c->P.alb_stride = 0;
+    if (!c->P.al || (!c->n_alsb && !knot)) return ILQR_OK;
+    if (!c->albk) {
+      double rec[h1::ALB_STRIDE] = {0};
+      h1host::al_default_bounds(c->P.al_margin, rec);
+      if (!c->d_alb_model) TRY(dalloc(c, &c->d_alb_model, (size_t)h1::ALB_STRIDE));
+      HIPCHK(c, hipMemcpyAsync(c->d_alb_model, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      c->P.alb = c->d_alb_model;
+    }
+  }
+  if (!knot) return ILQR_OK;
+  const long n1 = c->N + 1;
+  if (!c->albk) {
+    const int sets = c->n_alb ? c->n_alb : 1;
+    ilqr::g_al_knot.expand(c->P.alb, c->P.alb_stride, c->d_albk, h1::ALB_STRIDE, sets, c->N, c->stream);
+  }
+  c->P.alb = c->d_albk; c->P.alb_stride = c->n_alb > 1 ? n1 * h1::ALB_STRIDE : 0; c->P.alb_knot = h1::ALB_STRIDE;
+  if (c->n_alsb) {
+    if (!c->alsbk) ilqr::g_al_knot.expand(c->P.alsb, c->P.alsb_stride, c->d_alsbk, h1::ALSB_STRIDE, c->n_alsb, c->N, c->stream);
+    c->P.alsb = c->d_alsbk; c->P.alsb_stride = c->n_alsb > 1 ? n1 * h1::ALSB_STRIDE : 0; c->P.alsb_knot = h1::ALSB_STRIDE;
+  }
+  HIPCHK(c, hipGetLastError());
+  return ILQR_OK;
+}
+// the module and the two window buffers: what every call that may install a window needs, before it touches the handle's state
+__attribute__((noinline, minsize)) static int al_knot_ready(ilqr_hip_ctx* c) {
+  TRY(need_al_knot_module(c));
+  const size_t n = (size_t)c->B * (c->N + 1);
+  if (!c->d_albk) TRY(dalloc(c, &c->d_albk, n * h1::ALB_STRIDE));
+  if (!c->d_alsbk) TRY(dalloc(c, &c->d_alsbk, n * h1::ALSB_STRIDE));
   return ILQR_OK;
 }
 static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
@@ -362,6 +430,7 @@ static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   A.sstore = c->d_als; A.sstride = h1::als_record_doubles(c->N);
   A.rho_state0 = c->als_rho0; A.rho_state_max = c->als_rho0 * c->al_max_factor; A.tol_state = c->als_tol;
   A.sviol = c->d_als_viol; A.strace = c->d_als_trace;
+  A.bounds_knot = c->P.alb_knot; A.sbounds_knot = c->P.alsb_knot;
   return A;
 }
 // the multipliers follow the trajectory: shifted by the knots it is shifted by (shift > N: a cold start, all zero), penalties back to their
@@ -398,14 +467,7 @@ PlantModuleLib& plant_module(int which) {
   std::call_once(once[which], [which] {
     PlantModuleLib& m = mods[which];
     const ModuleDesc& d = MODULE_DESC[which];
-    Dl_info info;
-    std::string dir = ".";
-    if (dladdr((const void*)&ilqr_hip_plant_intervals, &info) && info.dli_fname) {
-      const std::string self = info.dli_fname;
-      const size_t slash = self.rfind('/');
-      if (slash != std::string::npos) dir = self.substr(0, slash);
-    }
-    const std::string path = dir + "/libilqr_hip_" + d.stem + ".so";
+    const std::string path = module_path(d.stem);
     void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
     if (!lib) { m.why = std::string("the ") + d.name + " kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
     m.ok = true;
@@ -433,7 +495,9 @@ static int need_module(ilqr_hip_ctx* c, int which) {
 
 extern "C" {
 
-int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt) {
+// (once per handle, as ilqr_hip_destroy; like the getters and setters marked minsize below it is compiled for size, which is what the
+// library-size check of tests/test_gpu_configs.py weighs)
+__attribute__((minsize)) int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, double dt) {
   if (!out || batch <= 0 || horizon <= 0 || !(dt > 0.0)) return ILQR_ERR_ARG;
   *out = nullptr;
   int ndev = 0;
@@ -494,7 +558,7 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   P.x_ref_stride = P.u_ref_stride = P.com_ref_stride = P.stance_stride = P.ee_ref_stride = P.com_vel_ref_stride = 0;
   P.wsets = nullptr; P.wsets_stride = 0;
   P.al = nullptr; P.al_stride = 0; P.al_margin = 0.0; P.alb = nullptr; P.alb_stride = 0;
-  P.als = nullptr; P.als_stride = 0; P.alsb = nullptr; P.alsb_stride = 0;
+  P.als = nullptr; P.als_stride = 0; P.alsb = nullptr; P.alsb_stride = 0; P.alb_knot = 0; P.alsb_knot = 0;
   // default: stance everywhere (RobotUtils::isStance default, robot_utils.cpp:494-504), lambda = 1e-6 (ilqr.cpp:16)
   std::vector<int> ones((N + 1) * 2, 1);
   hipMemcpyAsync(c->d_stance, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
@@ -512,14 +576,14 @@ int ilqr_hip_create(ilqr_hip_ctx** out, int device, int batch, int horizon, doub
   return ILQR_OK;
 }
 
-int ilqr_hip_destroy(ilqr_hip_ctx* c) {
+__attribute__((minsize)) int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
                   c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_alb, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left,
-                  c->d_als, c->d_alsb, c->d_als_viol, c->d_als_trace, c->d_alb_model};
+                  c->d_als, c->d_alsb, c->d_als_viol, c->d_als_trace, c->d_alb_model, c->d_albk, c->d_alsbk, c->d_abt_jc, c->d_abt_st, c->d_abt_start};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->h_al_left) (void)hipHostFree(c->h_al_left);
   if (c->ev_al) hipEventDestroy(c->ev_al);
@@ -633,6 +697,7 @@ int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
   c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al_rounds = 0; c->al_rounds_run = 0;      // (the buffers stay with the handle for the next call)
   c->P.alb = nullptr; c->P.alb_stride = 0; c->n_alb = 0;      // (the bounds table goes with it: a fresh installation starts on the model's ranges)
   c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0;      // (and the state family's)
+  c->albk = false; c->alsbk = false; c->P.alb_knot = 0; c->P.alsb_knot = 0;      // (and the windows; the bounds track stays with the handle)
   return ILQR_OK;
 }
 int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al_rounds : 0) : -1; }
@@ -642,6 +707,8 @@ int ilqr_hip_al_default_bounds(double margin, double* bounds) {
   h1host::al_default_bounds(margin, bounds);
   return ILQR_OK;
 }
+// the old getters' refusal while their family's bounds are a window
+static const char* const AL_WINDOW_ERR = "per-knot bounds: ilqr_hip_get_al_knot_bounds";
 // every pair: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
 __attribute__((noinline, minsize)) static bool al_bounds_ok(const double* v, int n_sets) {
   for (int s = 0; s < n_sets; ++s)
@@ -664,13 +731,13 @@ int ilqr_hip_set_al_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) {
   HIPCHK(c, hipMemcpyAsync(c->d_alb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->h_alb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_BOUNDS);
-  c->n_alb = n_sets;
+  c->n_alb = n_sets; c->albk = false;      // (a table replaces a window)
   return al_point_bounds(c);
 }
 int ilqr_hip_clear_al_bounds(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  c->n_alb = 0;      // (the buffer stays with the handle for the next table)
+  c->n_alb = 0; c->albk = false;      // (table or window; the buffers stay with the handle for the next one)
   enter(c);
   return al_point_bounds(c);
 }
@@ -678,6 +745,7 @@ int ilqr_hip_num_al_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alb : -1
 int ilqr_hip_get_al_bounds(ilqr_hip_ctx* c, double* bounds) {
   if (!c || !bounds) return ILQR_ERR_ARG;
   if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  if (c->albk) { c->err = AL_WINDOW_ERR; return ILQR_ERR_STATE; }
   double def[ILQR_AL_BOUNDS];
   if (!c->n_alb) h1host::al_default_bounds(c->P.al_margin, def);
   for (int b = 0; b < c->B; ++b)
@@ -775,41 +843,47 @@ __attribute__((noinline, minsize)) static bool al_state_bounds_ok(const double* 
   return true;
 }
 #define AL_STATE_INSTALLED(c) do { if (!(c)->P.al) { (c)->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; } } while (0)
-int ilqr_hip_set_al_state_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!bounds || check_sets(c, n_sets) || !(rho_state0 > 0.0) || !std::isfinite(rho_state0) || !(tol_state >= 0.0) || !al_state_bounds_ok(bounds, n_sets)) return ILQR_ERR_ARG;
-  enter(c);
-  static_assert(h1::ALSB_FIELDS == ILQR_AL_STATE_BOUNDS && h1::ALS_COORDS == ILQR_AL_STATE_COORDS && h1::ALSB_HI == 28, "the interface's record is the device record without its padding");
+// the state family's multiplier store, for a table or a window of bounds: zero where none was installed; bounds that replace others keep the
+// multipliers.  rho_state starts at rho_state0 either way
+__attribute__((noinline, minsize)) static int al_state_store_install(ilqr_hip_ctx* c, double rho_state0, double tol_state) {
   const size_t B = c->B, rec_d = (size_t)h1::als_record_doubles(c->N);
-  if (!c->d_alsb) TRY(dalloc(c, &c->d_alsb, B * h1::ALSB_STRIDE));
   if (!c->d_als) TRY(dalloc(c, &c->d_als, B * rec_d));
-  std::vector<double> rec((size_t)n_sets * h1::ALSB_STRIDE, 0.0);
-  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * h1::ALSB_STRIDE, bounds + (size_t)s * ILQR_AL_STATE_BOUNDS, sizeof(double) * ILQR_AL_STATE_BOUNDS);
-  HIPCHK(c, hipMemcpyAsync(c->d_alsb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  // the multipliers: zero where no table was installed; a table that replaces one keeps them.  rho_state starts at rho_state0 either way
   std::vector<double> st(B * rec_d, 0.0);
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
   if (c->n_alsb) HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t b = 0; b < B; ++b) st[b * rec_d + h1::ALS_RHO] = rho_state0;
   HIPCHK_S(c, hipMemcpy(c->d_als, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
   if (!c->n_alsb) HIPCHK_S(c, hipMemset(c->d_als_viol, 0, B * sizeof(double)));
-  c->h_alsb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_STATE_BOUNDS);
   c->P.als = c->d_als; c->P.als_stride = (long)rec_d;
-  c->P.alsb = c->d_alsb; c->P.alsb_stride = n_sets == 1 ? 0 : (long)h1::ALSB_STRIDE;
-  c->n_alsb = n_sets; c->als_rho0 = rho_state0; c->als_tol = tol_state;
+  c->als_rho0 = rho_state0; c->als_tol = tol_state;
+  return ILQR_OK;
+}
+int ilqr_hip_set_al_state_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!bounds || check_sets(c, n_sets) || !(rho_state0 > 0.0) || !std::isfinite(rho_state0) || !(tol_state >= 0.0) || !al_state_bounds_ok(bounds, n_sets)) return ILQR_ERR_ARG;
+  enter(c);
+  static_assert(h1::ALSB_FIELDS == ILQR_AL_STATE_BOUNDS && h1::ALS_COORDS == ILQR_AL_STATE_COORDS && h1::ALSB_HI == 28, "the interface's record is the device record without its padding");
+  if (!c->d_alsb) TRY(dalloc(c, &c->d_alsb, (size_t)c->B * h1::ALSB_STRIDE));
+  std::vector<double> rec((size_t)n_sets * h1::ALSB_STRIDE, 0.0);
+  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * h1::ALSB_STRIDE, bounds + (size_t)s * ILQR_AL_STATE_BOUNDS, sizeof(double) * ILQR_AL_STATE_BOUNDS);
+  HIPCHK(c, hipMemcpyAsync(c->d_alsb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  TRY(al_state_store_install(c, rho_state0, tol_state));
+  c->h_alsb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_STATE_BOUNDS);
+  c->n_alsb = n_sets; c->alsbk = false;      // (a table replaces a window)
   return al_point_bounds(c);
 }
 int ilqr_hip_clear_al_state_bounds(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   AL_STATE_INSTALLED(c);
-  c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0;      // (the buffers stay with the handle for the next table)
+  c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0; c->alsbk = false;      // (table or window; the buffers stay with the handle for the next one)
   return al_point_bounds(c);
 }
 int ilqr_hip_num_al_state_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alsb : -1; }
-int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* c, double* bounds) {
+__attribute__((minsize)) int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* c, double* bounds) {
   if (!c || !bounds) return ILQR_ERR_ARG;
   AL_STATE_INSTALLED(c);
+  if (c->alsbk) { c->err = AL_WINDOW_ERR; return ILQR_ERR_STATE; }
   for (int b = 0; b < c->B; ++b)
     for (int i = 0; i < ILQR_AL_STATE_BOUNDS; ++i)
       bounds[(size_t)b * ILQR_AL_STATE_BOUNDS + i] = c->n_alsb ? c->h_alsb[(size_t)(c->n_alsb == 1 ? 0 : b) * ILQR_AL_STATE_BOUNDS + i] : (i < ILQR_AL_STATE_COORDS ? -HUGE_VAL : HUGE_VAL);
@@ -881,6 +955,132 @@ int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* c, double* out) {
   HIPCHK_S(c, hipMemcpy(out, c->d_als_trace, (size_t)c->al_rounds * c->B * 2 * sizeof(double), hipMemcpyDeviceToHost));
   return ILQR_OK;
 }
+
+// ---- bounds that change from knot to knot: windows [n_sets][N+1][76] / [n_sets][N+1][56] in the whole-horizon setters' field order, and a
+// bounds track they are cut from on the device (al_bounds_track_kernels.hip).  The kernels that read windows: need_al_knot_module
+#define AL_COLD __attribute__((minsize))      // setters, getters and uploads: none is on a solve's path
+// HIPCHK with one text for every call of this section (HIPCHK keeps each call's own source text in the library)
+#define HIPCHK_AL(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed((ctx), "per-knot bounds", e_); } while (0)
+// `padded` rows of `width` doubles from `n` rows of `fields`
+__attribute__((noinline, minsize)) static int al_upload_rows(ilqr_hip_ctx* c, double* dst, const double* src, size_t n, int fields, int width) {
+  std::vector<double> rec(n * width, 0.0);
+  for (size_t r = 0; r < n; ++r) std::memcpy(rec.data() + r * width, src + r * fields, sizeof(double) * fields);
+  HIPCHK_AL(c, hipMemcpyAsync(dst, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
+AL_COLD int ilqr_hip_set_al_knot_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!bounds || check_sets(c, n_sets) || !al_bounds_ok(bounds, n_sets * (c->N + 1))) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(al_knot_ready(c));
+  TRY(al_upload_rows(c, c->d_albk, bounds, (size_t)n_sets * (c->N + 1), ILQR_AL_BOUNDS, h1::ALB_STRIDE));
+  c->n_alb = n_sets; c->albk = true;
+  return al_point_bounds(c);
+}
+AL_COLD int ilqr_hip_set_al_state_knot_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!bounds || check_sets(c, n_sets) || !(rho_state0 > 0.0) || !std::isfinite(rho_state0) || !(tol_state >= 0.0) || !al_state_bounds_ok(bounds, n_sets * (c->N + 1))) return ILQR_ERR_ARG;
+  enter(c);
+  TRY(al_knot_ready(c));
+  TRY(al_upload_rows(c, c->d_alsbk, bounds, (size_t)n_sets * (c->N + 1), ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE));
+  TRY(al_state_store_install(c, rho_state0, tol_state));
+  c->n_alsb = n_sets; c->alsbk = true;
+  return al_point_bounds(c);
+}
+int ilqr_hip_al_bounds_per_knot(const ilqr_hip_ctx* c) { return c ? ((c->P.al && c->albk) ? 1 : 0) | ((c->P.al && c->alsbk) ? 2 : 0) : -1; }
+AL_COLD int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* c, double* joint_ctrl, double* state) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  enter(c);
+  const size_t B = c->B, n1 = (size_t)c->N + 1;
+  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
+  for (int fam = 0; fam < 2; ++fam) {
+    double* out = fam ? state : joint_ctrl;
+    if (!out) continue;
+    const size_t F = fam ? ILQR_AL_STATE_BOUNDS : ILQR_AL_BOUNDS, W = fam ? h1::ALSB_STRIDE : h1::ALB_STRIDE;
+    const long knot = fam ? c->P.alsb_knot : c->P.alb_knot, stride = fam ? c->P.alsb_stride : c->P.alb_stride;
+    const double* dev = fam ? c->P.alsb : c->P.alb;
+    // what the kernels read: the windows (knot != 0), a table's records, or nothing (the model's bounds at the margin; no state family)
+    std::vector<double> img;
+    double def[ILQR_AL_BOUNDS];
+    if (dev) {
+      img.resize((stride ? B : 1) * (knot ? n1 : 1) * W);
+      HIPCHK_AL(c, hipMemcpy(img.data(), dev, img.size() * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (!fam) h1host::al_default_bounds(c->P.al_margin, def);
+    for (size_t b = 0; b < B; ++b)
+      for (size_t t = 0; t < n1; ++t) {
+        double* o = out + (b * n1 + t) * F;
+        if (dev) std::memcpy(o, img.data() + (stride ? b : 0) * (knot ? n1 : 1) * W + (knot ? t : 0) * W, sizeof(double) * F);
+        else if (!fam) std::memcpy(o, def, sizeof(def));
+        else for (size_t i = 0; i < F; ++i) o[i] = i < ILQR_AL_STATE_COORDS ? -HUGE_VAL : HUGE_VAL;
+      }
+  }
+  return ILQR_OK;
+}
+// ---- the bounds track
+static const char* const AL_TRACK_STATE_ERR = "the track's state part needs an installed state family";
+static const char* const AL_NO_TRACK_ERR = "no bounds track installed";
+AL_COLD int ilqr_hip_set_al_bounds_track(ilqr_hip_ctx* c, int rows, const double* joint_ctrl, const double* state) {
+  if (!c) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (rows < 1 || (!joint_ctrl && !state) || (joint_ctrl && !al_bounds_ok(joint_ctrl, rows)) || (state && !al_state_bounds_ok(state, rows))) return ILQR_ERR_ARG;
+  if (state && !c->n_alsb) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
+  enter(c);
+  TRY(al_knot_ready(c));
+  HIPCHK_AL(c, hipStreamSynchronize(c->stream));      // (a window kernel in flight still reads the track this call replaces)
+  if (c->d_abt_jc) hipFree(c->d_abt_jc);
+  if (c->d_abt_st) hipFree(c->d_abt_st);
+  c->d_abt_jc = nullptr; c->d_abt_st = nullptr; c->abt_rows = 0; c->abt_sets = 1;
+  if (!c->d_abt_start) TRY(dalloc(c, &c->d_abt_start, (size_t)c->B));
+  HIPCHK_AL(c, hipMemsetAsync(c->d_abt_start, 0, (size_t)c->B * sizeof(int), c->stream));      // one shared start of 0
+  if (joint_ctrl) { TRY(dalloc(c, &c->d_abt_jc, (size_t)rows * h1::ALB_STRIDE)); TRY(al_upload_rows(c, c->d_abt_jc, joint_ctrl, rows, ILQR_AL_BOUNDS, h1::ALB_STRIDE)); }
+  if (state) { TRY(dalloc(c, &c->d_abt_st, (size_t)rows * h1::ALSB_STRIDE)); TRY(al_upload_rows(c, c->d_abt_st, state, rows, ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE)); }
+  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
+  c->abt_rows = rows;
+  return ILQR_OK;
+}
+AL_COLD int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK_AL(c, hipStreamSynchronize(c->stream));      // (a window kernel in flight still reads it)
+  if (c->d_abt_jc) hipFree(c->d_abt_jc);
+  if (c->d_abt_st) hipFree(c->d_abt_st);
+  c->d_abt_jc = nullptr; c->d_abt_st = nullptr; c->abt_rows = 0; c->abt_sets = 1;
+  return ILQR_OK;
+}
+int ilqr_hip_al_bounds_track_rows(const ilqr_hip_ctx* c) { return c ? c->abt_rows : -1; }
+AL_COLD int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* c, const int* start, int n_sets) {
+  if (!c || !start || check_sets(c, n_sets)) return ILQR_ERR_ARG;
+  for (int b = 0; b < n_sets; ++b) if (start[b] < 0) return ILQR_ERR_ARG;
+  if (!c->abt_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
+  enter(c);
+  HIPCHK_AL(c, hipMemcpyAsync(c->d_abt_start, start, (size_t)n_sets * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
+  c->abt_sets = n_sets;
+  return ILQR_OK;
+}
+AL_COLD int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* c, int step) {
+  if (!c || step < 0) return ILQR_ERR_ARG;
+  AL_STATE_INSTALLED(c);
+  if (!c->abt_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
+  if (c->d_abt_st && !c->n_alsb) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
+  enter(c);
+  const int n_sets = c->abt_sets;
+  const ilqr::AlBoundsTrackDev T{c->d_abt_jc, c->d_abt_st, c->abt_rows};
+  const ilqr::AlBoundsWindowDev W{c->d_albk, c->d_alsbk};
+  ilqr::g_al_knot.window_from_track(&T, &W, c->d_abt_start, n_sets, step, c->N, c->stream);
+  HIPCHK_AL(c, hipGetLastError());
+  // the state the knot setters leave; the pointers move only where that state changes (the first cut, or other starts)
+  const bool jc = c->d_abt_jc != nullptr, st = c->d_abt_st != nullptr;
+  const bool same = (!jc || (c->albk && c->n_alb == n_sets)) && (!st || (c->alsbk && c->n_alsb == n_sets)) && c->P.alb_knot;
+  if (jc) { c->albk = true; c->n_alb = n_sets; }
+  if (st) { c->alsbk = true; c->n_alsb = n_sets; }
+  return same ? ILQR_OK : al_point_bounds(c);      // asynchronous on the handle's stream
+}
+#undef HIPCHK_AL
 #undef AL_STATE_INSTALLED
 
 int ilqr_hip_set_contact_schedule(ilqr_hip_ctx* c, const int* stance, int n_sets) {
@@ -997,7 +1197,7 @@ int ilqr_hip_window_from_track(ilqr_hip_ctx* c, int step, int follow_schedule) {
   c->xbar_rolled = false;      // (contact mode: the schedule is part of the dynamics)
   return ILQR_OK;      // asynchronous on the handle's stream
 }
-int ilqr_hip_get_reference_windows(ilqr_hip_ctx* c, double* x_ref, double* u_ref, double* com_ref, double* ee_ref, double* com_vel_ref, int* stance) {
+__attribute__((minsize)) int ilqr_hip_get_reference_windows(ilqr_hip_ctx* c, double* x_ref, double* u_ref, double* com_ref, double* ee_ref, double* com_vel_ref, int* stance) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2108,7 +2308,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
   h1::ProblemDev Ps = c->P;
   std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
   Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
-  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0; Ps.als = nullptr; Ps.als_stride = 0; Ps.alsb = nullptr; Ps.alsb_stride = 0;
+  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0; Ps.als = nullptr; Ps.als_stride = 0; Ps.alsb = nullptr; Ps.alsb_stride = 0; Ps.alb_knot = 0; Ps.alsb_knot = 0;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and
@@ -2818,7 +3018,7 @@ void ilqr_hip_pelvis_inertial_offset(double r[3]) {
   if (r) h1host::pelvis_inertial_offset(r);      // (host table: the model constants of this translation unit are device constants)
 }
 // ---- closed-loop score of the plant (plant_score_kernels.hip)
-int ilqr_hip_plant_set_score(ilqr_hip_ctx* c, const double* Q_diag, const double* R_diag, double w_upright, double w_balance, double w_joint_limits, double w_control_limits) {
+__attribute__((minsize)) int ilqr_hip_plant_set_score(ilqr_hip_ctx* c, const double* Q_diag, const double* R_diag, double w_upright, double w_balance, double w_joint_limits, double w_control_limits) {
   if (!c || !Q_diag || !R_diag) return ILQR_ERR_ARG;
   const double w[4] = {w_upright, w_balance, w_joint_limits, w_control_limits};
   for (double v : w) if (!(v >= 0.0) || !std::isfinite(v)) return ILQR_ERR_ARG;

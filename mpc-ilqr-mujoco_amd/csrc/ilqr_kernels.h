@@ -160,7 +160,28 @@ struct AlDev {
   double rho_state0, rho_state_max, tol_state;
   double* sviol;                   // [B] state violation of the nominal trajectory at the last update
   double* strace;                  // [rounds][B][2] violation, rho_state the round ran with
+  // windows of bounds (ProblemDev::alb_knot, alsb_knot, the same values): 0 one record per set, else the doubles from knot t's record to knot
+  // t + 1's inside a set's window, and bounds_stride / sbounds_stride the doubles of one set's window.  Appended: nothing above moves
+  long bounds_knot, sbounds_knot;
 };
+// The kernels that read windows of bounds live in a module of their own, libilqr_hip_alknot.so beside the library (csrc/Makefile; opened by
+// ilqr_capi.hip on the first call that installs a window, as the plant kernels' modules are): the per-knot instantiations of
+// k_cost_quadratics, k_traj_knot_cost, k_al_state_knot_cost and k_al_update and the kernels that write the windows, compiled from the same sources with -DAL_KNOT_MODULE, so that
+// the library holds the instantiations it held and nothing more.  Its entry points, C linkage (ilqr_alknot_module_<name>; ilqr_alknot_module() returns this table of them); the library's
+// launchers call them where ProblemDev::alb_knot / alsb_knot / AlDev::bounds_knot is set, which ilqr_capi.hip sets only once the table below is filled.
+struct AlBoundsTrackDev;
+struct AlBoundsWindowDev;      // (al_bounds_track_kernels.h)
+struct AlKnotModule {
+  void (*knot_cost)(const DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate, hipStream_t st);
+  void (*state_knot_cost)(const DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st);
+  void (*cost_quadratics)(const DevState* S, const h1::ProblemDev* P, int mode, const int* list, const int* count, int lower, hipStream_t st);
+  void (*al_update)(const DevState* S, const AlDev* A, int round, int masked, hipStream_t st);
+  // al_bounds_track_kernels.hip: launch_al_bounds_window_from_track, launch_al_bounds_expand (a code object of their own in the library
+  // costs it ~25 KB of headers and metadata for two copy kernels)
+  void (*window_from_track)(const AlBoundsTrackDev* T, const AlBoundsWindowDev* W, const int* start, int n_sets, int step, int N, hipStream_t st);
+  void (*expand)(const double* rec, long rec_stride, double* win, int width, int n_sets, int N, hipStream_t st);
+};
+extern AlKnotModule g_al_knot;      // (ilqr_capi.hip)
 // masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st);
 // shift > N: every multiplier becomes zero (cold start); the penalties are reset to the given values (the state family's to A.rho_state0),

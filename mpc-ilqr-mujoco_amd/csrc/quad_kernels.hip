@@ -660,6 +660,8 @@ DEVFN void quad_hessian_tiles(const double (&av)[4][2], const double (&bv)[4][4]
 // family's two bounds the same way -- their two multipliers from the second store (ProblemDev::als) and their lo / hi from rollout b's record
 // of ProblemDev::alsb in the same phase-0 batch and the same four variables, the rollout's third penalty as a scalar load beside the other two.
 // A lane still owns at most one coordinate.
+// AL_KNOT_TABLE / AL_KNOT_TABLE_STATE (windows of bounds, ProblemDev::alb_knot / alsb_knot): the same requests from row t (actuator lanes: row
+// tu) of rollout b's window -- one 64-bit multiply-add per bounds pointer, nothing else.  Instantiated in libilqr_hip_alknot.so only.
 template <bool WS, int AL>
 __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S, ProblemDev P, int mode, const int* list, const int* count, int lower,
                                                                      const double* recg, long knot0) {
@@ -718,8 +720,9 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       const int ai = wv == 0 ? AL_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : AL_ULO + iu;
       if constexpr (!al_state(AL)) {
       al_mu_lo = ak[ai]; al_mu_hi = ak[ai + H1_NJ];
-      if constexpr (AL == AL_TABLE) {
+      if constexpr (AL == AL_TABLE || AL == AL_KNOT_TABLE) {
         const double* ab = P.alb + (long)b * P.alb_stride;      // (the same clamped coordinate; ALB_JHI = ALB_JLO + 19, ALB_UHI = ALB_ULO + 19)
+        if constexpr (al_per_knot(AL)) ab += (long)(wv == 0 ? t : tu) * P.alb_knot;      // (the row of the knot the lane's multipliers are of)
         const int bi = wv == 0 ? ALB_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : ALB_ULO + iu;
         al_lo = ab[bi]; al_hi = ab[bi + H1_NJ];
       }
@@ -732,6 +735,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
         al_mu_lo = pm[0]; al_mu_hi = pm[box ? (int)ALS_COORDS : (int)H1_NJ];
         const double* sb = P.alsb + (long)b * P.alsb_stride + ALSB_LO;
         const double* ab = P.alb + (long)b * P.alb_stride;
+        if constexpr (al_per_knot(AL)) { sb += (long)t * P.alsb_knot; ab += (long)(wv == 0 ? t : tu) * P.alb_knot; }
         const int bi = wv == 0 ? ALB_JLO + ((lane >= 7 && lane < H1_NQ) ? lane - 7 : 0) : ALB_ULO + iu;
         const double* pb = box ? sb + kb : ab + bi;
         al_lo = pb[0]; al_hi = pb[box ? (int)ALS_COORDS : (int)H1_NJ];
@@ -1064,8 +1068,24 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   QSTAMP(5)
 }
 
+#ifdef AL_KNOT_MODULE
+}  // namespace ilqr
+// -DAL_KNOT_MODULE (csrc/Makefile, libilqr_hip_alknot.so; ilqr_kernels.h AlKnotModule): this file once more for the per-knot instantiations of
+// k_cost_quadratics.  The entry point makes the two launches of launch_cost_quadratics below for an already resolved work list: while a
+// state family is installed both families are windows (ilqr_capi.hip al_point_bounds), so two instantiations serve every case.
+extern "C" void ilqr_alknot_module_cost_quadratics(const ilqr::DevState* Sp, const h1::ProblemDev* Pp, int mode, const int* list, const int* count, int lower, hipStream_t st) {
+  using namespace ilqr;
+  const DevState& S = *Sp; const ProblemDev& P = *Pp;
+  const WorkList w{list, count};
+  const long knots = (long)S.B * (S.N + 1), per = (knots + 7) / 8;
+  hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
+  if (P.alsb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_KNOT_TABLE_STATE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  else hipLaunchKernelGGL((k_cost_quadratics<false, AL_KNOT_TABLE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+}
+#else
 void launch_cost_quadratics(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, int iter, int lower, const WorkList* wl) {
   const WorkList w = wl ? *wl : work_list(S, mode, iter);
+  if (P.al && P.alb && P.alb_knot) { g_al_knot.cost_quadratics(&S, &P, mode, w.list, w.count, lower, st); return; }      // (windows of bounds: both launches from the module)
   const long knots = (long)S.B * (S.N + 1);
   // the per-knot kinematics run for every rollout a masked (stage-API) launch might select; inside a solve for the compacted list
   // (a weight-set table, ProblemDev::wsets, selects the WS instantiations of both kernels)
@@ -1081,3 +1101,4 @@ void launch_cost_quadratics(const DevState& S, const ProblemDev& P, int mode, hi
 }
 
 }  // namespace ilqr
+#endif      // AL_KNOT_MODULE

@@ -44,7 +44,9 @@ weights and gravity of `base_problem` and uploads the whole of `refs` as a track
 rollout (`track_starts` [B]; None or one entry: one shared start, 0 by default), and every group calls
 `window_from_track(t_idx, follow_schedule)` where the host path calls problem_at + set_problem -- one kernel, nothing uploaded, no
 synchronisation; rollout b then tracks the rows from track_starts[b] + t_idx on (ReferenceData.problem_at_starts is the same rule on the
-host).  MPC_extractReference times the enqueue only.  The logged reference rows come from the host's copy of the rule, for the logged
+host).  While the solver handle has a bounds track (BatchedILQR.set_al_bounds_track) every solve of either loop also calls
+`al_bounds_window_from_track` with the step index its reference windows use, and `track_starts` feeds that track's start rows as well; without a
+bounds track there is no new call.  MPC_extractReference times the enqueue only.  The logged reference rows come from the host's copy of the rule, for the logged
 rollouts alone, and `last_stance0` from the host's contact table (rollout 0).
 
 `MPCRunner(..., resident=True, plant_model=(contact_mode, joint_limits), plant_params=P)` runs closed loops in which the plant is not the
@@ -193,6 +195,7 @@ class MPCRunner:
                 raise ValueError("plant_terrain must be [1, 5] or [B, 5] (scenario.stack_plant_terrain)")
         self.plant_terrain = plant_terrain
         self.device_refs, self.track_ready = bool(device_refs), False
+        self.track_starts_given, self.bounds_starts_for = track_starts is not None, None
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
         self.history_rows = None if history_rows is None else int(history_rows)
@@ -232,10 +235,24 @@ class MPCRunner:
                          ("iLQR_lineSearch", ms["iLQR_lineSearch"] + ms["iLQR_lineSearch_retry"])):
             self.prof.setdefault(key, []).append(float(val))
 
+    def _bounds_window(self, step):
+        """While the solver handle has a bounds track (BatchedILQR.set_al_bounds_track), the bounds windows of the solve at loop step `step`,
+        beside its reference windows: one kernel, nothing uploaded.  `track_starts` feeds the bounds track's start rows too, once per track."""
+        track_rows = getattr(self.s, "al_bounds_track_rows", None)      # (a solver stand-in without bounds tracks has none)
+        rows = track_rows() if track_rows else 0
+        if not rows:
+            self.bounds_starts_for = None
+            return
+        if self.bounds_starts_for != rows and self.track_starts_given:
+            self.s.set_al_bounds_track_starts(self.track_starts)
+        self.bounds_starts_for = rows
+        self.s.al_bounds_window_from_track(step)
+
     def step_once(self, x_measured, u_init=None, kick=None):
         t0 = time.perf_counter()
         prob = self.refs.problem_at(self.t_idx, self.s.N, self.base, follow_schedule=self.follow_schedule)   # extractReferenceWindow
         self.s.set_problem(prob)
+        self._bounds_window(self.t_idx)
         t1 = time.perf_counter(); self._add("MPC_extractReference", t0, t1)
         self.last_stance0 = prob["stance"][0, 0]
         if self.has_prev and self.since_solve == 1:
@@ -358,6 +375,7 @@ class MPCRunner:
             else:
                 prob = self.refs.problem_at(t_solve, s.N, self.base, follow_schedule=self.follow_schedule)
                 s.set_problem(prob)
+            self._bounds_window(t_solve)
             t1 = time.perf_counter(); self._add("MPC_extractReference", t0, t1)
             if self.device_refs:
                 r0 = start_of(0) + t_solve if self.follow_schedule else 0

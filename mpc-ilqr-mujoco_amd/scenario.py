@@ -402,6 +402,61 @@ def stack_al_state_bounds(records, B):
     return out
 
 
+def _is_knot_triple(v):
+    return (isinstance(v, (tuple, list)) and len(v) == 3 and all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in v[:2]))
+
+
+def _knot_records(records, B, N):
+    """records of the knot stackers -> per record the N + 1 plain dicts of its knots: a value that is a triple (first_knot, end_knot, value)
+    or a list of triples holds at the knots first_knot <= t < end_knot (a later triple overrides an earlier one) and is left out elsewhere"""
+    B, N = int(B), int(N)
+    if B < 1 or N < 1:
+        raise ValueError("B and N must be positive")
+    if isinstance(records, dict):
+        records = [records]
+    else:
+        records = list(records)
+        if len(records) != B:
+            raise ValueError("records must be one dict or B of them")
+    out = []
+    for rec in records:
+        if not isinstance(rec, dict):
+            raise ValueError("a bounds record is a dict")
+        knots = [dict() for _ in range(N + 1)]
+        for key, v in rec.items():
+            if _is_knot_triple(v):
+                v = [v]
+            if isinstance(v, list) and len(v) > 0 and all(_is_knot_triple(e) for e in v):
+                for first, end, val in v:
+                    if not 0 <= first <= end <= N + 1:
+                        raise ValueError("%s: knots (%r, %r) are not 0 <= first_knot <= end_knot <= N + 1" % (key, first, end))
+                    for t in range(int(first), int(end)):
+                        knots[t][key] = val
+            else:
+                for k in knots:
+                    k[key] = v
+        out.append(knots)
+    return out
+
+
+def stack_al_knot_bounds(records, B, N, margin=0.0):
+    """Bounds windows [n, N+1, 76] for BatchedILQR.set_al_knot_bounds (and, with N + 1 = rows, tracks for set_al_bounds_track): row t holds
+    knot t's joint_lo[19], joint_hi[19], ctrl_lo[19], ctrl_hi[19].  records is one dict (n = 1) or a sequence of B dicts (n = B) with the
+    keys and values of stack_al_bounds; every value may also be a triple (first_knot, end_knot, value) -- the value holds at the knots
+    first_knot <= t < end_knot -- or a list of such triples.  Knots outside every triple get the default: the model's bound at `margin`.
+    Raises ValueError where stack_al_bounds does, and for knots outside 0 <= first_knot <= end_knot <= N + 1."""
+    per = _knot_records(records, B, N)
+    return np.stack([np.concatenate([stack_al_bounds(k, 1, margin) for k in knots]) for knots in per])
+
+
+def stack_al_state_knot_bounds(records, B, N):
+    """State-bounds windows [n, N+1, 56] for BatchedILQR.set_al_state_knot_bounds: row t holds knot t's lo[28], hi[28].  records as for
+    stack_al_state_bounds; every value may also be a triple (first_knot, end_knot, value) or a list of such triples, as in
+    stack_al_knot_bounds.  Knots outside every triple get -inf / +inf: no bound."""
+    per = _knot_records(records, B, N)
+    return np.stack([np.concatenate([stack_al_state_bounds(k, 1) for k in knots]) for knots in per])
+
+
 def al_bounds_from_plant_joints(joints, margin=0.0):
     """The bounds table [n, 76] in which the solver knows each rollout's torque range of stack_plant_joints' records `joints` [n, 76]:
     ctrl_lo, ctrl_hi = range_scale_i * the default control bound of actuator i at `margin` (range_scale = 0, a dead motor: lo = hi = 0);

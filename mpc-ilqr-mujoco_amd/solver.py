@@ -32,6 +32,9 @@ EXPORTS = [
     "ilqr_hip_set_al_state_bounds", "ilqr_hip_clear_al_state_bounds", "ilqr_hip_num_al_state_bound_sets", "ilqr_hip_get_al_state_bounds",
     "ilqr_hip_get_al_state_multipliers", "ilqr_hip_set_al_state_multipliers", "ilqr_hip_get_al_state_penalties", "ilqr_hip_get_al_state_violation",
     "ilqr_hip_get_al_state_trace", "ilqr_hip_al_state_slot",
+    "ilqr_hip_set_al_knot_bounds", "ilqr_hip_set_al_state_knot_bounds", "ilqr_hip_get_al_knot_bounds", "ilqr_hip_al_bounds_per_knot",
+    "ilqr_hip_set_al_bounds_track", "ilqr_hip_clear_al_bounds_track", "ilqr_hip_al_bounds_track_rows", "ilqr_hip_set_al_bounds_track_starts",
+    "ilqr_hip_al_bounds_window_from_track",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -506,6 +509,74 @@ class BatchedILQR:
     def al_state_trace(self):
         """[rounds, B, 2]: state violation and rho_state of every round of the last solve (NaN: not run)."""
         return self._get("ilqr_hip_get_al_state_trace", (self.augmented_lagrangian_rounds(), self.B, 2))
+
+    # ---- bounds that change from knot to knot (include/ilqr_hip.h ilqr_hip_set_al_knot_bounds)
+    def _knot_window(self, bounds, width, what):
+        """a window of bounds as [n_sets, N+1, width] doubles (one window may come two-dimensional)"""
+        b = _c64(bounds)
+        if b.ndim == 2:
+            b = b[None]
+        if b.ndim != 3 or b.shape[1:] != (self.N + 1, width):
+            raise ValueError("%s must be [N+1, %d], [1, N+1, %d] or [B, N+1, %d]" % (what, width, width, width))
+        return b
+
+    def set_al_knot_bounds(self, bounds):
+        """A window of joint / torque bounds per rollout in place of one record: [N+1, AL_BOUNDS] / [1, N+1, AL_BOUNDS] (every rollout) or
+        [B, N+1, AL_BOUNDS]; row t holds knot t's bounds in the columns of set_al_bounds (scenario.stack_al_knot_bounds).  The torque
+        columns of row N are checked and never read.  Replaces a table of set_al_bounds, keeps the multipliers; horizon-local (a warm start
+        does not move it).  Stays until set_al_bounds(), clear_al_bounds() or clear_augmented_lagrangian()."""
+        b = self._knot_window(bounds, AL_BOUNDS, "knot bounds")
+        self._chk(self.L.ilqr_hip_set_al_knot_bounds(self.h, _p(b), int(b.shape[0])))
+
+    def set_al_state_knot_bounds(self, bounds, rho_state0, tol_state=1e-3):
+        """A window of state bounds per rollout: [N+1, AL_STATE_BOUNDS] / [1, N+1, AL_STATE_BOUNDS] or [B, N+1, AL_STATE_BOUNDS]; row t holds
+        knot t's lo[28], hi[28] (scenario.stack_al_state_knot_bounds).  rho_state0 and tol_state as in set_al_state_bounds, which it replaces
+        (and which replaces it)."""
+        b = self._knot_window(bounds, AL_STATE_BOUNDS, "state knot bounds")
+        self._chk(self.L.ilqr_hip_set_al_state_knot_bounds(self.h, _p(b), int(b.shape[0]), C.c_double(float(rho_state0)), C.c_double(float(tol_state))))
+
+    def al_knot_bounds(self):
+        """(joint_ctrl [B, N+1, AL_BOUNDS], state [B, N+1, AL_STATE_BOUNDS]): what each rollout is solved with at each knot, whoever wrote it --
+        a window, a track cut, a table's record repeated over the knots, or the model's bounds at the installed margin and -inf / +inf."""
+        jc, st = np.zeros((self.B, self.N + 1, AL_BOUNDS)), np.zeros((self.B, self.N + 1, AL_STATE_BOUNDS))
+        self._chk(self.L.ilqr_hip_get_al_knot_bounds(self.h, _p(jc), _p(st)))
+        return jc, st
+
+    def al_bounds_per_knot(self):
+        """Bit 0: the joint / torque bounds are a window; bit 1: the state bounds are one."""
+        return int(self.L.ilqr_hip_al_bounds_per_knot(self.h))
+
+    def set_al_bounds_track(self, joint_ctrl=None, state=None):
+        """Upload a bounds track once: joint_ctrl [rows, AL_BOUNDS] and / or state [rows, AL_STATE_BOUNDS] on the loop's timeline (a state part
+        needs installed state bounds, which supply rho_state0 and tol_state).  The start rows become one shared start of 0; a second call
+        replaces the track."""
+        jc, st = (None if a is None else _c64(a) for a in (joint_ctrl, state))
+        if jc is None and st is None:
+            raise ValueError("bounds track: joint_ctrl [rows, %d] and / or state [rows, %d]" % (AL_BOUNDS, AL_STATE_BOUNDS))
+        rows = (jc if jc is not None else st).shape[0]
+        if (jc is not None and jc.shape != (rows, AL_BOUNDS)) or (st is not None and st.shape != (rows, AL_STATE_BOUNDS)):
+            raise ValueError("bounds track: joint_ctrl [rows, %d] and / or state [rows, %d] with one number of rows" % (AL_BOUNDS, AL_STATE_BOUNDS))
+        self._chk(self.L.ilqr_hip_set_al_bounds_track(self.h, int(rows), _p(jc), _p(st)))
+
+    def clear_al_bounds_track(self):
+        """Free the bounds track; the windows last written stay installed."""
+        self._chk(self.L.ilqr_hip_clear_al_bounds_track(self.h))
+
+    def al_bounds_track_rows(self):
+        """0 without a bounds track, else its rows."""
+        return int(self.L.ilqr_hip_al_bounds_track_rows(self.h))
+
+    def set_al_bounds_track_starts(self, starts):
+        """One start row of the bounds track per rollout (B entries) or one shared start (one entry); every start >= 0."""
+        st = np.ascontiguousarray(np.atleast_1d(starts), dtype=np.int32)
+        if st.ndim != 1:
+            raise ValueError("starts must be one-dimensional (one entry, or one per rollout)")
+        self._chk(self.L.ilqr_hip_set_al_bounds_track_starts(self.h, st.ctypes.data_as(_ip), int(st.shape[0])))
+
+    def al_bounds_window_from_track(self, step):
+        """Enqueue the kernel that writes the bounds windows of MPC step `step` (rollout b, knot t: track row min(start[b] + step + t,
+        rows - 1)); uploads nothing and does not synchronise."""
+        self._chk(self.L.ilqr_hip_al_bounds_window_from_track(self.h, int(step)))
 
     def set_references(self, x_ref, u_ref, com_ref):
         x_ref, u_ref, com_ref = _c64(x_ref), _c64(u_ref), _c64(com_ref)

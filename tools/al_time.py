@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian) against the plain penalties on ONE handle,
 on one GPU, the two alternating:
-   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state]
+   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state] [--knot]
   * ms per call of the two cost stages (stage_cost_quadratics: k_quad_kin + k_cost_quadratics; stage_total_cost: k_traj_knot_cost +
     k_traj_cost_sum) and, per launch inside a solve, of the cost quadratics (ilqr_hip_get_stage_ms, stage 2);
   * ms per call of the update kernel alone (ilqr_hip_al_update: k_al_update, one memset, one synchronisation);
@@ -13,7 +13,12 @@ and under a per-rollout table (n_sets = batch).  Both tables hold the bounds the
 do the same arithmetic on the same values and differ in where the bounds come from.
 --state (implies --bounds) adds a fifth mode: the per-rollout table plus a per-rollout table of state bounds (ilqr_hip_set_al_state_bounds,
 n_sets = batch; every bound +-1e3, none active) -- the state instantiation of k_cost_quadratics and k_al_state_knot_cost behind
-k_traj_knot_cost against the AL_TABLE instantiations of the mode before it."""
+k_traj_knot_cost against the AL_TABLE instantiations of the mode before it.
+--knot (implies --state) adds two modes: per-rollout WINDOWS of the same bounds (ilqr_hip_set_al_knot_bounds, n_sets = batch: every knot its own
+five lines) against the per-rollout table, and both families as windows (ilqr_hip_set_al_state_knot_bounds) against the two tables -- the per-knot
+instantiations of libilqr_hip_alknot.so against the table instantiations, the same arithmetic on the same values.  It also times
+ilqr_hip_al_bounds_window_from_track itself (both parts of a track of 2 (N + 1) rows, one start per rollout, `calls` enqueues and one
+synchronisation, per call): "window_from_track" in the output."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py)
@@ -33,7 +38,10 @@ def main():
     ap.add_argument("--calls", type=int, default=20); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--bounds", action="store_true", help="also time AL under a one-record and under a per-rollout table of bounds")
     ap.add_argument("--state", action="store_true", help="also time AL under a per-rollout table of bounds plus a per-rollout table of state bounds")
+    ap.add_argument("--knot", action="store_true", help="also time AL under per-rollout windows of bounds (per knot), and the track cut")
+    ap.add_argument("--cut-only", action="store_true", help="with --knot: time the track cut alone")
     a = ap.parse_args()
+    a.state = a.state or a.knot
     a.bounds = a.bounds or a.state
     pkg = load_package()
     from mpc_ilqr_mujoco_amd import solver as sv
@@ -44,7 +52,7 @@ def main():
     s = sv.BatchedILQR(B, N=N, dt=prob["dt"]); s.set_problem(prob)
     s.set_options(early_exit=False); s.set_max_iterations(a.iters)
     al = dict(rounds=3, rho_joint0=2 * prob["w_joint"], rho_ctrl0=2 * prob["w_ctrl"], growth=10.0, rho_max_factor=1e4, margin=0.1, tol_joint=0.0, tol_ctrl=0.0)
-    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ()) + (("al_bounds_B_state_B",) if a.state else ())
+    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ()) + (("al_bounds_B_state_B",) if a.state else ()) + (("al_knot_B", "al_knot_B_state_knot_B") if a.knot else ())
     ms = {m: {"quadratics": [], "total_cost": [], "solve": [], "quadratics_per_launch_in_solve": []} for m in modes}
     for m in modes[1:]:
         ms[m]["update"] = []
@@ -58,7 +66,7 @@ def main():
             fn()
         return 1e3 * (time.perf_counter() - t0) / calls
 
-    for rnd in range(a.rounds + 1):                      # round 0 warms up
+    for rnd in range(0 if a.cut_only else a.rounds + 1):      # round 0 warms up
         for m in modes:
             if m == "plain":
                 s.clear_augmented_lagrangian()
@@ -66,14 +74,19 @@ def main():
                 s.set_augmented_lagrangian(**al)
                 if m == "al":
                     s.clear_al_bounds()
+                elif m.startswith("al_knot"):
+                    s.set_al_knot_bounds(np.tile(record, (B, N + 1, 1)))
                 else:
                     s.set_al_bounds(record if m == "al_bounds_1" else np.tile(record, (B, 1)))
                 if m == "al_bounds_B_state_B":
                     s.set_al_state_bounds(np.tile(state_record, (B, 1)), 2 * prob["w_joint"], 0.0)
+                elif m == "al_knot_B_state_knot_B":
+                    s.set_al_state_knot_bounds(np.tile(state_record, (B, N + 1, 1)), 2 * prob["w_joint"], 0.0)
                 else:
                     s.clear_al_state_bounds()
-                assert s.num_al_bound_sets() == {"al": 0, "al_bounds_1": 1, "al_bounds_B": B, "al_bounds_B_state_B": B}[m]
-                assert s.num_al_state_bound_sets() == (B if m == "al_bounds_B_state_B" else 0)
+                assert s.num_al_bound_sets() == (0 if m == "al" else 1 if m == "al_bounds_1" else B)
+                assert s.num_al_state_bound_sets() == (B if "state" in m else 0)
+                assert s.al_bounds_per_knot() == {"al_knot_B": 1, "al_knot_B_state_knot_B": 3}.get(m, 0)
             s.initialize(x0, ui)
             s.enable_profiling(True)
             t0 = time.perf_counter(); s.solve(None); dt = 1e3 * (time.perf_counter() - t0)
@@ -86,9 +99,24 @@ def main():
             if rnd:
                 for k, v in row.items():
                     ms[m][k].append(v)
+    cut = None
+    if a.knot:                                           # the track cut alone: enqueues back to back, one synchronisation
+        s.set_augmented_lagrangian(**al)
+        s.set_al_state_bounds(state_record, 2 * prob["w_joint"], 0.0)
+        s.set_al_bounds_track(np.tile(record, (2 * (N + 1), 1)), np.tile(state_record, (2 * (N + 1), 1)))
+        s.set_al_bounds_track_starts(np.arange(B) % (N + 1))
+        samples = []
+        for rnd in range(a.rounds + 1):
+            s.al_bounds_window_from_track(0); s.al_violation()      # (al_violation synchronises the stream and copies [B][2] doubles)
+            t0 = time.perf_counter()
+            for k in range(a.calls):
+                s.al_bounds_window_from_track(k)
+            s.al_violation()
+            samples.append(1e3 * (time.perf_counter() - t0) / a.calls)
+        cut = {"ms_median": float(np.median(samples[1:])), "samples": samples[1:]}
     s.close()
     print(json.dumps({"tool": "al_time", "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "calls": a.calls, "rounds": a.rounds, "iters": a.iters,
-                      "al": al, "ms_median": {m: {k: float(np.median(v)) for k, v in d.items()} for m, d in ms.items()}, "samples": ms}))
+                      "al": al, "window_from_track": cut, "ms_median": {m: {k: float(np.median(v)) if v else None for k, v in d.items()} for m, d in ms.items()}, "samples": ms}))
 
 
 if __name__ == "__main__":
