@@ -176,10 +176,12 @@ __global__ void __launch_bounds__(64) k_solve_begin_al(DevState S, const int* do
 }
 
 void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, hipStream_t st) {
-  if (A.bounds && A.bounds_knot) g_al_knot.al_update(&S, &A, round, masked, st);      // (windows: the module's instantiations)
-  else if (A.sbounds && A.bounds) hipLaunchKernelGGL((k_al_update<true, true>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);      // (a state table brings a bounds record with it)
-  else if (A.bounds) hipLaunchKernelGGL((k_al_update<true, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);
-  else hipLaunchKernelGGL((k_al_update<false, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked);
+  switch (al_variant(true, A.bounds, A.sbounds, A.bounds_knot)) {      // (al_plan.h: the variant of the cost kernels)
+    case AL_KNOT_TABLE: case AL_KNOT_TABLE_STATE: g_al_knot.al_update(&S, &A, round, masked, st); break;      // (windows: the module's instantiations)
+    case AL_TABLE_STATE: hipLaunchKernelGGL((k_al_update<true, true>), dim3(S.B), dim3(64), 0, st, S, A, round, masked); break;
+    case AL_TABLE: hipLaunchKernelGGL((k_al_update<true, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked); break;
+    default: hipLaunchKernelGGL((k_al_update<false, false>), dim3(S.B), dim3(64), 0, st, S, A, round, masked); break;
+  }
 }
 void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st) {
   hipLaunchKernelGGL(k_al_shift, dim3(B), dim3(128), 0, st, A, N, shift, rho_joint, rho_ctrl);

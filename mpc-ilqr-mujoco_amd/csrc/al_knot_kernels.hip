@@ -29,7 +29,7 @@ const ilqr::AlKnotModule* ilqr_alknot_module() {
   return &table;
 }
 }
-// a state family brings a window of the joint / torque bounds with it (ilqr_capi.hip al_point_bounds): both windows or the first alone
+// a state family brings a window of the joint / torque bounds with it (al_plan.h): both windows or the first alone
 extern "C" void ilqr_alknot_module_al_update(const ilqr::DevState* S, const ilqr::AlDev* A, int round, int masked, hipStream_t st) {
   if (A->sbounds) hipLaunchKernelGGL((ilqr::k_al_update<true, true, true>), dim3(S->B), dim3(64), 0, st, *S, *A, round, masked);
   else hipLaunchKernelGGL((ilqr::k_al_update<true, false, true>), dim3(S->B), dim3(64), 0, st, *S, *A, round, masked);

@@ -324,27 +324,29 @@ __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int 
   for (int t = 0; t <= S.N; ++t) c += ck[t];
   cost_out[cand] = c;
 }
+// The knot costs of the trajectories xsrc / usrc into S.cand_knot: the knot-cost kernel of the handle's variant (al_plan.h; a weight-set table
+// selects the WS instantiation, without the augmented Lagrangian only), then the state family's terms where the variant has them.  cshift:
+// log2 of the candidates per rollout in the sources, oshift: of the slots between two of them in S.cand_knot.
+#define KNOT_COST_LAUNCH(WS, AL) hipLaunchKernelGGL((k_traj_knot_cost<WS, AL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, xsrc, usrc, cshift, oshift, gate)
+static void launch_knot_costs(const DevState& S, const ProblemDev& P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate, hipStream_t st) {
+  const long total = ((long)S.B << cshift) * (S.N + 1);
+  const int variant = al_variant(P.al, P.alb, P.alsb, P.alb_knot);
+  switch (variant) {
+    case AL_KNOT_TABLE: case AL_KNOT_TABLE_STATE: g_al_knot.knot_cost(&S, &P, mode, xsrc, usrc, cshift, oshift, gate, st); break;      // (windows of bounds: the module's instantiation)
+    case AL_TABLE: case AL_TABLE_STATE: KNOT_COST_LAUNCH(false, AL_TABLE); break;
+    case AL_MODEL: KNOT_COST_LAUNCH(false, AL_MODEL); break;
+    default: if (P.wsets) KNOT_COST_LAUNCH(true, AL_OFF); else KNOT_COST_LAUNCH(false, AL_OFF); break;
+  }
+  if (variant == AL_KNOT_TABLE_STATE) g_al_knot.state_knot_cost(&S, &P, mode, xsrc, cshift, oshift, gate, st);
+  else if (variant == AL_TABLE_STATE) hipLaunchKernelGGL(k_al_state_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, xsrc, cshift, oshift, gate);
+}
 void launch_cand_costs(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, bool with_sum, const int* gate) {
-  const long total = (long)S.B * 8 * (S.N + 1);
-  if (P.al && P.alb && P.alb_knot) g_al_knot.knot_cost(&S, &P, mode, S.xcand, S.ucand, 3, 0, gate, st);      // (windows of bounds: the module's instantiation)
-  else if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, (const double*)S.ucand, 3, 0, gate);
-  if (P.al && P.alsb && P.alsb_knot) g_al_knot.state_knot_cost(&S, &P, mode, S.xcand, 3, 0, gate, st);
-  else if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xcand, 3, 0, gate);
+  launch_knot_costs(S, P, mode, S.xcand, S.ucand, 3, 0, gate, st);
   if (with_sum) hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)(((long)S.B * 8 + 63) / 64)), dim3(64), 0, st, S, mode, 3, 0, S.cand_cost);
 }
 // computeTotalCost of the nominal trajectories (S.xbar, S.ubar) into cost_out[B], same kernels, same summation order
 void launch_nominal_costs(const DevState& S, const ProblemDev& P, int mode, double* cost_out, hipStream_t st) {
-  const long total = (long)S.B * (S.N + 1);
-  if (P.al && P.alb && P.alb_knot) g_al_knot.knot_cost(&S, &P, mode, S.xbar, S.ubar, 0, 3, nullptr, st);      // (windows of bounds: the module's instantiation)
-  else if (P.al && P.alb) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_TABLE>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  else if (P.al) hipLaunchKernelGGL((k_traj_knot_cost<false, AL_MODEL>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  else if (P.wsets) hipLaunchKernelGGL((k_traj_knot_cost<true, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  else hipLaunchKernelGGL((k_traj_knot_cost<false, AL_OFF>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, (const double*)S.ubar, 0, 3, (const int*)nullptr);
-  if (P.al && P.alsb && P.alsb_knot) g_al_knot.state_knot_cost(&S, &P, mode, S.xbar, 0, 3, nullptr, st);
-  else if (P.al && P.alsb) hipLaunchKernelGGL(k_al_state_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, (const double*)S.xbar, 0, 3, (const int*)nullptr);
+  launch_knot_costs(S, P, mode, S.xbar, S.ubar, 0, 3, nullptr, st);
   hipLaunchKernelGGL(k_traj_cost_sum, dim3((unsigned)((S.B + 63) / 64)), dim3(64), 0, st, S, mode, 0, 3, cost_out);
 }
 

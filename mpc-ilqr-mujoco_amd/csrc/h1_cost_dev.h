@@ -20,6 +20,7 @@
 // Quaternion slots use R = Eigen's toRotationMatrix polynomial on the raw (x,y,z,w) coefficients and
 // the reference's slot conventions (permuted state in, un-permuted slots out).
 #pragma once
+#include "al_plan.h"
 #include "h1_dynamics_dev.h"
 
 namespace h1 {
@@ -56,7 +57,7 @@ struct ProblemDev {
   // bounds that change from knot to knot (ilqr_hip_set_al_knot_bounds, ilqr_hip_set_al_state_knot_bounds, ilqr_hip_al_bounds_window_from_track):
   // 0 = one record per set as above; else alb / alsb point at windows, [N+1] records per set, knot-major, knot t's record alb_knot / alsb_knot
   // doubles behind knot 0's (ALB_STRIDE / ALSB_STRIDE) and alb_stride / alsb_stride the doubles of one set's window (0: one window for all).
-  // Both are set or both are 0 while a state family is installed (ilqr_capi.hip al_point_bounds).  Appended: nothing above moves
+  // Both are set or both are 0 while a state family is installed (al_plan.h).  Appended: nothing above moves
   long alb_knot, alsb_knot;
 };
 // The multiplier store, in doubles.  Rollout b's record: one 128-byte line of scalars (AL_RHO_JOINT, AL_RHO_CTRL, the rest padding), then one
@@ -84,15 +85,8 @@ static_assert(ALS_HI + ALS_COORDS <= ALS_KNOT && ALS_KNOT % 16 == 0 && ALS_HDR %
 static_assert(H1_NX == 51 && H1_NQ == 26, "box coordinates: slots 0..2 and 26..50");
 inline long als_record_doubles(int N) { return ALS_HDR + (long)ALS_KNOT * (N + 1); }
 constexpr int als_slot(int k) { return k < 3 ? k : 23 + k; }
-// Where the limit terms take their bounds from: AL_MODEL the model's ranges at ProblemDev::al_margin, AL_TABLE rollout b's record of
-// ProblemDev::alb.  (AL_OFF: the plain penalties.)  A template axis, so that the paths without a table keep their machine code.
-// AL_TABLE_STATE: AL_TABLE with the state family (ProblemDev::als, alsb) on top.  There is no AL_MODEL_STATE: while a state table is
-// installed without a joint / torque table, ProblemDev::alb points at one record of the model's bounds at the installed margin, the same
-// doubles al_bounds forms (ilqr_capi.hip al_point_bounds) -- a second state instantiation of k_cost_quadratics costs the library 29 KB.
-// AL_KNOT_TABLE / AL_KNOT_TABLE_STATE: AL_TABLE / AL_TABLE_STATE with the bounds of knot t taken from row t of rollout b's window
-// (ProblemDev::alb_knot, alsb_knot).  Instantiations of their own, so that the four above keep their machine code; there is no mixed one:
-// while one family has a window the library expands the other family's record into a window of equal rows.
-enum { AL_OFF = 0, AL_MODEL = 1, AL_TABLE = 2, AL_TABLE_STATE = 3, AL_KNOT_TABLE = 4, AL_KNOT_TABLE_STATE = 5 };
+// The AL template axis (AL_OFF .. AL_KNOT_TABLE_STATE) and which of its values a handle's installation selects: al_plan.h.  A template axis,
+// so that the paths without a table keep their machine code, and instantiations of their own per knot, so that the four others keep theirs.
 constexpr bool al_table(int AL) { return AL == AL_TABLE || AL == AL_TABLE_STATE || AL == AL_KNOT_TABLE || AL == AL_KNOT_TABLE_STATE; }
 constexpr bool al_state(int AL) { return AL == AL_TABLE_STATE || AL == AL_KNOT_TABLE_STATE; }
 constexpr bool al_per_knot(int AL) { return AL == AL_KNOT_TABLE || AL == AL_KNOT_TABLE_STATE; }

@@ -96,38 +96,35 @@ struct ilqr_hip_ctx {
   int n_xref = 0, n_stance = 0, n_ee = 0;
   double* d_wsets = nullptr;              // [B][WS_STRIDE] weight-set table (ilqr_hip_set_weight_sets; allocated by its first call); installed while P.wsets points at it
   int n_wsets = 0;                        // 0: shared weights, else the installed table's n_sets
-  // Augmented Lagrangian (ilqr_hip_set_augmented_lagrangian): installed while P.al points at d_al.  d_al [B][al_record_doubles(N)] the multiplier
-  // store (h1_cost_dev.h), d_al_viol [B][2], d_al_done [B], d_al_trace [al_trace_cap][B][5], d_al_left [al_trace_cap] rollouts not done after each
-  // round and its pinned copy h_al_left (the host's read between two rounds, as the early-exit gate reads its counts); all kept by the handle
-  // once allocated.  al_round: the round enqueue_solve is enqueuing; al_rounds_run: rounds the last solve enqueued
-  int al_rounds = 0, al_trace_cap = 0, al_round = 0, al_rounds_run = 0;
-  double al_rho0[2] = {0, 0}, al_growth = 1.0, al_max_factor = 1.0, al_tol[2] = {0, 0};
-  double *d_al = nullptr, *d_al_viol = nullptr, *d_al_trace = nullptr;
-  int *d_al_done = nullptr, *d_al_left = nullptr, *h_al_left = nullptr;
-  hipEvent_t ev_al = nullptr;
-  // bounds table of the augmented Lagrangian (ilqr_hip_set_al_bounds): installed while P.alb points at d_alb [B][ALB_STRIDE] (allocated by the
-  // first call, kept by the handle); h_alb the installed records as the caller gave them, [n_alb][76]
-  double* d_alb = nullptr;
-  int n_alb = 0;                          // 0: the model's ranges at the installed margin, else the installed table's n_sets
-  std::vector<double> h_alb;
-  // state family of the augmented Lagrangian (ilqr_hip_set_al_state_bounds): installed while P.alsb points at d_alsb [B][ALSB_STRIDE]; d_als
-  // [B][als_record_doubles(N)] its multiplier store, d_als_viol [B], d_als_trace [al_trace_cap][B][2] (the last two allocated with their
-  // joint / torque counterparts); h_alsb the installed records as the caller gave them, [n_alsb][56]
-  // d_alb_model [ALB_STRIDE]: the model's bounds at the installed margin as one record, what P.alb points at while a state table is installed
-  // without a bounds table (al_point_bounds) -- the state instantiations take every bound from a record
-  double *d_als = nullptr, *d_alsb = nullptr, *d_als_viol = nullptr, *d_als_trace = nullptr, *d_alb_model = nullptr;
-  int n_alsb = 0;
-  double als_rho0 = 0.0, als_tol = 0.0;
-  std::vector<double> h_alsb;
-  // windows of bounds (ilqr_hip_set_al_knot_bounds, ilqr_hip_set_al_state_knot_bounds, ilqr_hip_al_bounds_window_from_track): d_albk [B][N+1][ALB_STRIDE],
-  // d_alsbk [B][N+1][ALSB_STRIDE]; albk / alsbk: that family's installed bounds are a window (n_alb / n_alsb then its n_sets, h_alb / h_alsb stale).
-  // While either is set P.alb / P.alsb point at the windows and the other family's record is expanded into its window (al_point_bounds).
-  // The bounds track (ilqr_hip_set_al_bounds_track): d_abt_jc [rows][ALB_STRIDE], d_abt_st [rows][ALSB_STRIDE], either may be null; its start rows
-  // d_abt_start [B] on the device (allocated with the handle's first track)
-  double *d_albk = nullptr, *d_alsbk = nullptr, *d_abt_jc = nullptr, *d_abt_st = nullptr;
-  int* d_abt_start = nullptr;
-  bool albk = false, alsbk = false;
-  int abt_rows = 0, abt_sets = 1;
+  // Augmented Lagrangian (ilqr_hip_set_augmented_lagrangian): installed while P.al points at al.jc.store; every buffer is kept by the handle once
+  // allocated and freed by ilqr_hip_destroy.  Which pointers ProblemDev / AlDev get from all this: al_point_bounds, by the plan of al_plan.h.
+  // One record per family of bounds -- jc the hinges and actuators (ilqr_hip_set_al_bounds ...), st the 28 box coordinates
+  // (ilqr_hip_set_al_state_bounds ...) -- which the bodies behind the two families' entry points take as their parameter:
+  struct AlFamily {
+    int fields, width;        // doubles of a bounds record in the interface (76 / 56) and on the device (ALB_STRIDE / ALSB_STRIDE)
+    int blocks, per;          // a bounds record is `blocks` blocks of lo[per], hi[per] (2 x 19 / 1 x 28); so is a knot's multiplier record:
+    int knot_rec, block_at[2];   // its doubles and the offset of each block in it (h1_cost_dev.h); block 1 (the actuators) has no knot N
+    double* store = nullptr;  // [B][AL_HDR + (N+1) knot_rec] the multiplier store: penalty `g` of the record at [g], allocated with the family
+    double *table = nullptr, *window = nullptr, *track = nullptr;   // bounds [B][width], [B][N+1][width], [rows][width] (null: the track has no such part)
+    int sets = 0;             // 0: nothing installed (jc: the model's ranges at the installed margin), else the n_sets of the table or window
+    bool knot = false;        // the installed bounds are a window (host is then stale)
+    std::vector<double> host; // the installed table as the caller gave it, [sets][fields]
+  };
+  struct Al {
+    int rounds = 0, trace_cap = 0, round = 0, rounds_run = 0;      // round: the one enqueue_solve is enqueuing; rounds_run: rounds the last solve enqueued
+    double rho0[2] = {0, 0}, growth = 1.0, max_factor = 1.0, tol[2] = {0, 0}, srho0 = 0.0, stol = 0.0;
+    // viol [B][2], done [B], trace [trace_cap][B][5], left [trace_cap] rollouts not done after each round and its pinned copy h_left (the host's
+    // read between two rounds, as the early-exit gate reads its counts); sviol [B], strace [trace_cap][B][2] the state family's
+    double *viol = nullptr, *trace = nullptr, *sviol = nullptr, *strace = nullptr;
+    int *done = nullptr, *left = nullptr, *h_left = nullptr;
+    hipEvent_t ev = nullptr;
+    AlFamily jc{ILQR_AL_BOUNDS, h1::ALB_STRIDE, 2, 19, h1::AL_KNOT, {h1::AL_JLO, h1::AL_ULO}};
+    AlFamily st{ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE, 1, ILQR_AL_STATE_COORDS, h1::ALS_KNOT, {h1::ALS_LO, 0}};
+    double* model = nullptr;  // [ALB_STRIDE] the model's bounds at the installed margin as one record (AlPlan::upload_model)
+    // the bounds track (ilqr_hip_set_al_bounds_track; the families' `track`): its start rows [B] on the device, allocated with the first track
+    int* track_start = nullptr;
+    int track_rows = 0, track_sets = 1;
+  } al;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
   double *d_stepx = nullptr, *d_stepu = nullptr, *d_stepn = nullptr;   // ilqr_hip_step* scratch, grown on demand
@@ -358,85 +355,85 @@ __attribute__((noinline, minsize)) static std::string module_path(const char* st
   }
   return dir + "/libilqr_hip_" + stem + ".so";
 }
-// The per-knot instantiations of the cost kernels and of k_al_update live in libilqr_hip_alknot.so (ilqr_kernels.h AlKnotModule), opened on the
-// first call that installs a window from the directory this library was loaded from.  Missing module or entry point: ILQR_ERR_UNSUPPORTED.
-namespace ilqr { AlKnotModule g_al_knot = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; }
-__attribute__((noinline, minsize)) static int need_al_knot_module(ilqr_hip_ctx* c) {
-  static std::once_flag once;
-  static std::string why;
-  std::call_once(once, [] {
-    const std::string path = module_path("alknot");
+// One way to open a module: libilqr_hip_<stem>.so, opened once per process, on first use, from the directory this library was loaded from,
+// and handed to `resolve`, which looks its entry points up and says whether all are there.  `name`: of the kernels, in the messages.
+struct ModuleLib { std::once_flag once; bool ok = false; std::string why; };
+__attribute__((noinline)) static bool open_module(ModuleLib& m, const char* stem, const char* name, bool (*resolve)(void* lib, int which), int which) {
+  std::call_once(m.once, [&] {
+    const std::string path = module_path(stem);
     void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    // one exported symbol: the table of the module's entry points (al_knot_kernels.hip)
-    const auto table = lib ? (const ilqr::AlKnotModule* (*)())dlsym(lib, "ilqr_alknot_module") : nullptr;
-    if (!table) { why = "module missing or without its entry point: " + path; return; }
-    ilqr::g_al_knot = *table();
+    if (!lib) { m.why = std::string("the ") + name + " kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
+    m.ok = resolve(lib, which);
+    if (!m.ok) m.why = std::string("the ") + name + " kernels' module lacks an entry point: " + path;
   });
-  if (!ilqr::g_al_knot.al_update) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
+  return m.ok;
+}
+// n rows of `fields` doubles onto the device as rows of `width` doubles, padded with zeros; returns behind the copy
+__attribute__((noinline, minsize)) static int upload_rows(ilqr_hip_ctx* c, double* dst, const double* src, size_t n, int fields, int width) {
+  std::vector<double> padded;
+  if (width != fields) {
+    padded.assign(n * width, 0.0);
+    for (size_t r = 0; r < n; ++r) std::memcpy(padded.data() + r * width, src + r * fields, sizeof(double) * fields);
+    src = padded.data();
+  }
+  HIPCHK(c, hipMemcpyAsync(dst, src, n * width * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
-// Where the two families take their bounds from.  No window installed: the joint / torque family from the installed table; without one null
-// (the model's ranges at P.al_margin, formed in the kernels) -- or, while a state table is installed, one record of those same doubles
-// (h1host::al_default_bounds); the state family from its table.  A window of either family installed (albk / alsbk; the module is loaded):
-// both families read windows -- a family that has none gets its record (the table's, or the model's) repeated over the knots by
-// k_al_bounds_expand, device to device, so that two per-knot instantiations of k_cost_quadratics serve every combination.
-__attribute__((noinline, minsize)) static int al_point_bounds(ilqr_hip_ctx* c) {
-  c->P.alb_knot = 0; c->P.alsb_knot = 0;
-  const bool knot = c->P.al && (c->albk || c->alsbk);
-  if (c->P.al && c->n_alsb) { c->P.alsb = c->d_alsb; c->P.alsb_stride = c->n_alsb == 1 ? 0 : (long)h1::ALSB_STRIDE; }
-  if (c->n_alb && !c->albk) { c->P.alb = c->d_alb; c->P.alb_stride = c->n_alb == 1 ? 0 : (long)h1::ALB_STRIDE; }
-  else {
-    c->P.alb = nullptr; c->P.alb_stride = 0;
-    if (!c->P.al || (!c->n_alsb && !knot)) return ILQR_OK;
-    if (!c->albk) {
-      double rec[h1::ALB_STRIDE] = {0};
-      h1host::al_default_bounds(c->P.al_margin, rec);
-      if (!c->d_alb_model) TRY(dalloc(c, &c->d_alb_model, (size_t)h1::ALB_STRIDE));
-      HIPCHK(c, hipMemcpyAsync(c->d_alb_model, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      c->P.alb = c->d_alb_model;
-    }
-  }
-  if (!knot) return ILQR_OK;
-  const long n1 = c->N + 1;
-  if (!c->albk) {
-    const int sets = c->n_alb ? c->n_alb : 1;
-    ilqr::g_al_knot.expand(c->P.alb, c->P.alb_stride, c->d_albk, h1::ALB_STRIDE, sets, c->N, c->stream);
-  }
-  c->P.alb = c->d_albk; c->P.alb_stride = c->n_alb > 1 ? n1 * h1::ALB_STRIDE : 0; c->P.alb_knot = h1::ALB_STRIDE;
-  if (c->n_alsb) {
-    if (!c->alsbk) ilqr::g_al_knot.expand(c->P.alsb, c->P.alsb_stride, c->d_alsbk, h1::ALSB_STRIDE, c->n_alsb, c->N, c->stream);
-    c->P.alsb = c->d_alsbk; c->P.alsb_stride = c->n_alsb > 1 ? n1 * h1::ALSB_STRIDE : 0; c->P.alsb_knot = h1::ALSB_STRIDE;
-  }
-  HIPCHK(c, hipGetLastError());
-  return ILQR_OK;
-}
+// The per-knot instantiations of the cost kernels and of k_al_update live in libilqr_hip_alknot.so (ilqr_kernels.h AlKnotModule), opened by the
+// first call that may install a window.  Missing module or entry point: ILQR_ERR_UNSUPPORTED.
+namespace ilqr { AlKnotModule g_al_knot = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; }
+using AlFamily = ilqr_hip_ctx::AlFamily;
 // the module and the two window buffers: what every call that may install a window needs, before it touches the handle's state
 __attribute__((noinline, minsize)) static int al_knot_ready(ilqr_hip_ctx* c) {
-  TRY(need_al_knot_module(c));
-  const size_t n = (size_t)c->B * (c->N + 1);
-  if (!c->d_albk) TRY(dalloc(c, &c->d_albk, n * h1::ALB_STRIDE));
-  if (!c->d_alsbk) TRY(dalloc(c, &c->d_alsbk, n * h1::ALSB_STRIDE));
+  static ModuleLib lib;
+  // one exported symbol: the table of the module's entry points (al_knot_kernels.hip)
+  const auto resolve = [](void* so, int) { const auto table = (const ilqr::AlKnotModule* (*)())dlsym(so, "ilqr_alknot_module"); if (table) ilqr::g_al_knot = *table(); return table != nullptr; };
+  if (!open_module(lib, "alknot", "per-knot bounds", resolve, 0)) { c->err = lib.why; return ILQR_ERR_UNSUPPORTED; }
+  for (AlFamily* f : {&c->al.jc, &c->al.st}) if (!f->window) TRY(dalloc(c, &f->window, (size_t)c->B * (c->N + 1) * f->width));
+  return ILQR_OK;
+}
+// Points ProblemDev at the bounds: resolves the plan of what is installed (al_plan.h states the rules), does the work it names -- the model's
+// record, the expansions (k_al_bounds_expand, device to device; a plan that names one has the module loaded) -- and writes each family's
+// pointer and strides as the plan names them.
+__attribute__((noinline, minsize)) static int al_point_bounds(ilqr_hip_ctx* c) {
+  const ilqr::AlPlan plan = ilqr::resolve_al_plan(c->P.al != nullptr, {c->al.jc.sets, c->al.jc.knot}, {c->al.st.sets, c->al.st.knot});
+  if (plan.upload_model) {
+    double rec[h1::ALB_STRIDE] = {0};
+    h1host::al_default_bounds(c->P.al_margin, rec);
+    if (!c->al.model) TRY(dalloc(c, &c->al.model, (size_t)h1::ALB_STRIDE));
+    TRY(upload_rows(c, c->al.model, rec, 1, h1::ALB_STRIDE, h1::ALB_STRIDE));
+  }
+  const auto point = [&](const AlFamily& f, const ilqr::AlFamilyPlan& fp, bool expand, const double*& ptr, long& stride, long& knot) {
+    const double* rec = (fp.source == ilqr::AL_SRC_MODEL_RECORD || fp.source == ilqr::AL_SRC_MODEL_EXPANDED) ? c->al.model : f.table;
+    if (expand) ilqr::g_al_knot.expand(rec, fp.shared ? 0 : f.width, f.window, f.width, f.sets ? f.sets : 1, c->N, c->stream);
+    ptr = (fp.source == ilqr::AL_SRC_NONE || fp.source == ilqr::AL_SRC_MODEL_RANGES) ? nullptr : fp.per_knot ? f.window : rec;
+    stride = fp.shared ? 0 : fp.per_knot ? (long)(c->N + 1) * f.width : (long)f.width;
+    knot = fp.per_knot ? f.width : 0;
+  };
+  point(c->al.jc, plan.jc, plan.expand_jc, c->P.alb, c->P.alb_stride, c->P.alb_knot);
+  point(c->al.st, plan.st, plan.expand_st, c->P.alsb, c->P.alsb_stride, c->P.alsb_knot);
+  if (plan.module) HIPCHK(c, hipGetLastError());
   return ILQR_OK;
 }
 static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   ilqr::AlDev A{};
-  A.store = c->d_al; A.stride = h1::al_record_doubles(c->N);
-  A.margin = c->P.al_margin; A.growth = c->al_growth; A.tol_joint = c->al_tol[0]; A.tol_ctrl = c->al_tol[1];
-  A.rho_joint_max = c->al_rho0[0] * c->al_max_factor; A.rho_ctrl_max = c->al_rho0[1] * c->al_max_factor;
-  A.viol = c->d_al_viol; A.done = c->d_al_done; A.trace = c->d_al_trace; A.left = c->d_al_left;
+  A.store = c->al.jc.store; A.stride = h1::al_record_doubles(c->N);
+  A.margin = c->P.al_margin; A.growth = c->al.growth; A.tol_joint = c->al.tol[0]; A.tol_ctrl = c->al.tol[1];
+  A.rho_joint_max = c->al.rho0[0] * c->al.max_factor; A.rho_ctrl_max = c->al.rho0[1] * c->al.max_factor;
+  A.viol = c->al.viol; A.done = c->al.done; A.trace = c->al.trace; A.left = c->al.left;
   A.bounds = c->P.alb; A.bounds_stride = c->P.alb_stride;
   A.sbounds = c->P.alsb; A.sbounds_stride = c->P.alsb_stride;
-  A.sstore = c->d_als; A.sstride = h1::als_record_doubles(c->N);
-  A.rho_state0 = c->als_rho0; A.rho_state_max = c->als_rho0 * c->al_max_factor; A.tol_state = c->als_tol;
-  A.sviol = c->d_als_viol; A.strace = c->d_als_trace;
+  A.sstore = c->al.st.store; A.sstride = h1::als_record_doubles(c->N);
+  A.rho_state0 = c->al.srho0; A.rho_state_max = c->al.srho0 * c->al.max_factor; A.tol_state = c->al.stol;
+  A.sviol = c->al.sviol; A.strace = c->al.strace;
   A.bounds_knot = c->P.alb_knot; A.sbounds_knot = c->P.alsb_knot;
   return A;
 }
 // the multipliers follow the trajectory: shifted by the knots it is shifted by (shift > N: a cold start, all zero), penalties back to their
 // initial values -- enqueued on the handle's stream by every initialiser while AL is installed
 static void al_follow_initialize(ilqr_hip_ctx* c, int shift) {
-  if (c->P.al) ilqr::launch_al_shift(al_view(c), c->B, c->N, shift, c->al_rho0[0], c->al_rho0[1], c->stream);
+  if (c->P.al) ilqr::launch_al_shift(al_view(c), c->B, c->N, shift, c->al.rho0[0], c->al.rho0[1], c->stream);
 }
 
 // The wrench, payload, observation, actuator, joints and terrain families of the plant kernels are modules of their own (csrc/Makefile PLANT_MODULE;
@@ -455,29 +452,21 @@ const ModuleDesc MODULE_DESC[ilqr::PLANT_MODULES] = {
   {"joints", "joints", {"set_attr", "follow", "step", nullptr}},
   {"terrain", "terrain", {"set_attr", "follow", "step", nullptr}},
 };
-struct PlantModuleLib {
-  void* fn[MODULE_FNS] = {nullptr};
-  bool ok = false;
-  std::string why;
-};
+struct PlantModuleLib : ModuleLib { void* fn[MODULE_FNS] = {nullptr}; };
+PlantModuleLib g_plant_module[ilqr::PLANT_MODULES];
+bool resolve_plant_module(void* lib, int which) {
+  const ModuleDesc& d = MODULE_DESC[which];
+  bool ok = true;
+  for (int i = 0; i < MODULE_FNS && d.entry[i]; ++i) {
+    g_plant_module[which].fn[i] = dlsym(lib, (std::string("ilqr_") + d.stem + "_module_" + d.entry[i]).c_str());
+    ok = ok && g_plant_module[which].fn[i];
+  }
+  return ok;
+}
 // opened and resolved once per process and module
 PlantModuleLib& plant_module(int which) {
-  static PlantModuleLib mods[ilqr::PLANT_MODULES];
-  static std::once_flag once[ilqr::PLANT_MODULES];
-  std::call_once(once[which], [which] {
-    PlantModuleLib& m = mods[which];
-    const ModuleDesc& d = MODULE_DESC[which];
-    const std::string path = module_path(d.stem);
-    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!lib) { m.why = std::string("the ") + d.name + " kernels' module is missing: " + path + " (csrc/Makefile builds it beside the library)"; return; }
-    m.ok = true;
-    for (int i = 0; i < MODULE_FNS && d.entry[i]; ++i) {
-      m.fn[i] = dlsym(lib, (std::string("ilqr_") + d.stem + "_module_" + d.entry[i]).c_str());
-      m.ok = m.ok && m.fn[i];
-    }
-    if (!m.ok) m.why = std::string("the ") + d.name + " kernels' module lacks an entry point: " + path;
-  });
-  return mods[which];
+  open_module(g_plant_module[which], MODULE_DESC[which].stem, MODULE_DESC[which].name, resolve_plant_module, which);
+  return g_plant_module[which];
 }
 // entry point `slot` of a module that need_module has checked, as its typedef of ilqr_kernels.h
 template <class Fn> Fn module_fn(int which, ModuleFn slot) { return (Fn)plant_module(which).fn[slot]; }
@@ -582,11 +571,11 @@ __attribute__((minsize)) int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->d_al, c->d_alb, c->d_al_viol, c->d_al_trace, c->d_al_done, c->d_al_left,
-                  c->d_als, c->d_alsb, c->d_als_viol, c->d_als_trace, c->d_alb_model, c->d_albk, c->d_alsbk, c->d_abt_jc, c->d_abt_st, c->d_abt_start};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->al.viol, c->al.trace, c->al.done, c->al.left, c->al.sviol, c->al.strace, c->al.model, c->al.track_start};
   for (void* p : ptrs) if (p) hipFree(p);
-  if (c->h_al_left) (void)hipHostFree(c->h_al_left);
-  if (c->ev_al) hipEventDestroy(c->ev_al);
+  for (const AlFamily* f : {&c->al.jc, &c->al.st}) for (void* p : {(void*)f->store, (void*)f->table, (void*)f->window, (void*)f->track}) if (p) hipFree(p);
+  if (c->al.h_left) (void)hipHostFree(c->al.h_left);
+  if (c->al.ev) hipEventDestroy(c->al.ev);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate, S.kr, S.kr_n, S.ls_list, S.ls_kind, c->d_lgate}; for (void* p : gp) if (p) hipFree(p); }
   { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
@@ -667,26 +656,26 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
   if (const char* why = al_refusal(c)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   if (c->P.wsets) { c->err = "the augmented Lagrangian together with weight sets is not supported: ilqr_hip_clear_weight_sets first"; return ILQR_ERR_UNSUPPORTED; }
   const size_t B = c->B;
-  if (!c->d_al) { TRY(dalloc(c, &c->d_al, B * (size_t)h1::al_record_doubles(c->N))); TRY(dalloc(c, &c->d_al_viol, B * 2)); TRY(dalloc(c, &c->d_al_done, B)); }
-  if (!c->d_als_viol) TRY(dalloc(c, &c->d_als_viol, B));
-  if (!c->ev_al) HIPCHK_S(c, hipEventCreateWithFlags(&c->ev_al, hipEventDisableTiming));
-  if (rounds > c->al_trace_cap) {
+  if (!c->al.jc.store) { TRY(dalloc(c, &c->al.jc.store, B * (size_t)h1::al_record_doubles(c->N))); TRY(dalloc(c, &c->al.viol, B * 2)); TRY(dalloc(c, &c->al.done, B)); }
+  if (!c->al.sviol) TRY(dalloc(c, &c->al.sviol, B));
+  if (!c->al.ev) HIPCHK_S(c, hipEventCreateWithFlags(&c->al.ev, hipEventDisableTiming));
+  if (rounds > c->al.trace_cap) {
     HIPCHK_S(c, hipStreamSynchronize(c->stream));
-    if (c->d_al_trace) (void)hipFree(c->d_al_trace);
-    if (c->d_al_left) (void)hipFree(c->d_al_left);
-    if (c->h_al_left) (void)hipHostFree(c->h_al_left);
-    if (c->d_als_trace) (void)hipFree(c->d_als_trace);
-    c->d_al_trace = nullptr; c->d_al_left = nullptr; c->h_al_left = nullptr; c->d_als_trace = nullptr; c->al_trace_cap = 0;
-    TRY(dalloc(c, &c->d_al_trace, (size_t)rounds * B * 5)); TRY(dalloc(c, &c->d_al_left, (size_t)rounds)); TRY(dalloc(c, &c->d_als_trace, (size_t)rounds * B * 2));
-    HIPCHK_S(c, hipHostMalloc((void**)&c->h_al_left, sizeof(int) * (size_t)rounds, hipHostMallocDefault));
-    c->al_trace_cap = rounds;
+    if (c->al.trace) (void)hipFree(c->al.trace);
+    if (c->al.left) (void)hipFree(c->al.left);
+    if (c->al.h_left) (void)hipHostFree(c->al.h_left);
+    if (c->al.strace) (void)hipFree(c->al.strace);
+    c->al.trace = nullptr; c->al.left = nullptr; c->al.h_left = nullptr; c->al.strace = nullptr; c->al.trace_cap = 0;
+    TRY(dalloc(c, &c->al.trace, (size_t)rounds * B * 5)); TRY(dalloc(c, &c->al.left, (size_t)rounds)); TRY(dalloc(c, &c->al.strace, (size_t)rounds * B * 2));
+    HIPCHK_S(c, hipHostMalloc((void**)&c->al.h_left, sizeof(int) * (size_t)rounds, hipHostMallocDefault));
+    c->al.trace_cap = rounds;
   }
-  c->al_rounds = rounds; c->al_rho0[0] = rho_joint0; c->al_rho0[1] = rho_ctrl0; c->al_growth = growth; c->al_max_factor = rho_max_factor;
-  c->al_tol[0] = tol_joint; c->al_tol[1] = tol_ctrl; c->al_rounds_run = 0;
-  c->P.al = c->d_al; c->P.al_stride = h1::al_record_doubles(c->N); c->P.al_margin = margin;
+  c->al.rounds = rounds; c->al.rho0[0] = rho_joint0; c->al.rho0[1] = rho_ctrl0; c->al.growth = growth; c->al.max_factor = rho_max_factor;
+  c->al.tol[0] = tol_joint; c->al.tol[1] = tol_ctrl; c->al.rounds_run = 0;
+  c->P.al = c->al.jc.store; c->P.al_stride = h1::al_record_doubles(c->N); c->P.al_margin = margin;
   TRY(al_point_bounds(c));      // (a state table without a bounds table: the model's record at the new margin)
-  HIPCHK_S(c, hipMemsetAsync(c->d_al_trace, 0xFF, (size_t)rounds * B * 5 * sizeof(double), c->stream));      // (all bits set: NaN)
-  HIPCHK_S(c, hipMemsetAsync(c->d_als_trace, 0xFF, (size_t)rounds * B * 2 * sizeof(double), c->stream));
+  HIPCHK_S(c, hipMemsetAsync(c->al.trace, 0xFF, (size_t)rounds * B * 5 * sizeof(double), c->stream));      // (all bits set: NaN)
+  HIPCHK_S(c, hipMemsetAsync(c->al.strace, 0xFF, (size_t)rounds * B * 2 * sizeof(double), c->stream));
   al_follow_initialize(c, c->N + 1);
   HIPCHK_S(c, hipGetLastError());
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
@@ -694,394 +683,304 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
 }
 int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
-  c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al_rounds = 0; c->al_rounds_run = 0;      // (the buffers stay with the handle for the next call)
-  c->P.alb = nullptr; c->P.alb_stride = 0; c->n_alb = 0;      // (the bounds table goes with it: a fresh installation starts on the model's ranges)
-  c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0;      // (and the state family's)
-  c->albk = false; c->alsbk = false; c->P.alb_knot = 0; c->P.alsb_knot = 0;      // (and the windows; the bounds track stays with the handle)
-  return ILQR_OK;
+  c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al.rounds = 0; c->al.rounds_run = 0;      // (the buffers stay with the handle for the next call)
+  c->P.als = nullptr; c->P.als_stride = 0;
+  // the tables and windows of both families go with it: a fresh installation starts on the model's ranges (the bounds track stays with the handle)
+  for (AlFamily* f : {&c->al.jc, &c->al.st}) { f->sets = 0; f->knot = false; }
+  return al_point_bounds(c);      // (nothing installed: null pointers, no work)
 }
-int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al_rounds : 0) : -1; }
-// ---- the bounds table: one record of ILQR_AL_BOUNDS doubles per set, joint lo, joint hi, ctrl lo, ctrl hi
+int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al.rounds : 0) : -1; }
+// what every entry point below needs first
+__attribute__((noinline)) static int al_installed(ilqr_hip_ctx* c) {
+  if (c->P.al) return ILQR_OK;
+  c->err = "no augmented Lagrangian installed";
+  return ILQR_ERR_STATE;
+}
+// ---- the bounds, one body per operation for both families (ilqr_hip_ctx::AlFamily).  Joint / torque family: one record of ILQR_AL_BOUNDS doubles per
+// set, joint lo, joint hi, ctrl lo, ctrl hi; state family: the 28 box coordinates (pelvis position, pelvis velocity, joint velocities), one
+// record lo[28], hi[28] per set.  Windows [n_sets][N+1][fields] hold one such record per knot; the bounds track they can be cut from on the
+// device: al_bounds_track_kernels.hip.
+static_assert(h1::ALB_FIELDS == ILQR_AL_BOUNDS && h1::ALB_JHI == 19 && h1::ALB_ULO == 38 && h1::ALB_UHI == 57, "the interface's record is the device record without its padding");
+static_assert(h1::ALSB_FIELDS == ILQR_AL_STATE_BOUNDS && h1::ALS_COORDS == ILQR_AL_STATE_COORDS && h1::ALSB_HI == 28, "the interface's record is the device record without its padding");
+static_assert(h1::AL_JHI == h1::AL_JLO + 19 && h1::AL_UHI == h1::AL_ULO + 19 && h1::ALS_HI == h1::ALS_LO + 28 && h1::AL_HDR == h1::ALS_HDR && h1::AL_RHO_JOINT == 0 && h1::AL_RHO_CTRL == 1 && h1::ALS_RHO == 0,
+              "a knot's multiplier record: per block the lower bounds' multipliers, then the upper bounds'; the penalties lead the store's header");
 int ilqr_hip_al_default_bounds(double margin, double* bounds) {
   if (!bounds || !(margin >= 0.0) || !(margin < 0.5)) return ILQR_ERR_ARG;
   h1host::al_default_bounds(margin, bounds);
   return ILQR_OK;
 }
+int ilqr_hip_al_state_slot(int k) { return (k >= 0 && k < ILQR_AL_STATE_COORDS) ? h1::als_slot(k) : -1; }
 // the old getters' refusal while their family's bounds are a window
 static const char* const AL_WINDOW_ERR = "per-knot bounds: ilqr_hip_get_al_knot_bounds";
-// every pair: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
-__attribute__((noinline, minsize)) static bool al_bounds_ok(const double* v, int n_sets) {
-  for (int s = 0; s < n_sets; ++s)
-    for (int f = 0; f < 2; ++f)
-      for (int i = 0; i < 19; ++i) {
-        const double lo = v[(size_t)s * ILQR_AL_BOUNDS + 38 * f + i], hi = v[(size_t)s * ILQR_AL_BOUNDS + 38 * f + 19 + i];
+// the family exists: the joint / torque family with the installation, the state family with its bounds
+static bool al_family_absent(const ilqr_hip_ctx* c, const AlFamily& f) { return &f == &c->al.st && !f.sets; }
+// every pair of n records: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
+__attribute__((noinline, minsize)) static bool al_bounds_ok(const AlFamily& f, const double* v, size_t n) {
+  for (size_t r = 0; r < n; ++r)
+    for (int g = 0; g < f.blocks; ++g)
+      for (int i = 0; i < f.per; ++i) {
+        const double lo = v[r * f.fields + 2 * f.per * g + i], hi = v[r * f.fields + 2 * f.per * g + f.per + i];
         if (!(lo <= hi) || lo == HUGE_VAL || hi == -HUGE_VAL) return false;      // (a NaN fails lo <= hi)
       }
   return true;
 }
-int ilqr_hip_set_al_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) {
-  if (!c) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  if (!bounds || check_sets(c, n_sets) || !al_bounds_ok(bounds, n_sets)) return ILQR_ERR_ARG;
-  enter(c);
-  if (!c->d_alb) TRY(dalloc(c, &c->d_alb, (size_t)c->B * h1::ALB_STRIDE));
-  static_assert(h1::ALB_FIELDS == ILQR_AL_BOUNDS && h1::ALB_JHI == 19 && h1::ALB_ULO == 38 && h1::ALB_UHI == 57, "the interface's record is the device record without its padding");
-  std::vector<double> rec((size_t)n_sets * h1::ALB_STRIDE, 0.0);
-  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * h1::ALB_STRIDE, bounds + (size_t)s * ILQR_AL_BOUNDS, sizeof(double) * ILQR_AL_BOUNDS);
-  HIPCHK(c, hipMemcpyAsync(c->d_alb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->h_alb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_BOUNDS);
-  c->n_alb = n_sets; c->albk = false;      // (a table replaces a window)
-  return al_point_bounds(c);
+// what a family without bounds is solved with: the model's ranges at the installed margin / every side switched off
+__attribute__((noinline)) static void al_no_bounds(const ilqr_hip_ctx* c, const AlFamily& f, double* rec) {
+  if (&f == &c->al.jc) h1host::al_default_bounds(c->P.al_margin, rec);
+  else for (int i = 0; i < f.fields; ++i) rec[i] = i < f.per ? -HUGE_VAL : HUGE_VAL;
 }
-int ilqr_hip_clear_al_bounds(ilqr_hip_ctx* c) {
-  if (!c) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  c->n_alb = 0; c->albk = false;      // (table or window; the buffers stay with the handle for the next one)
-  enter(c);
-  return al_point_bounds(c);
-}
-int ilqr_hip_num_al_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alb : -1; }
-int ilqr_hip_get_al_bounds(ilqr_hip_ctx* c, double* bounds) {
-  if (!c || !bounds) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  if (c->albk) { c->err = AL_WINDOW_ERR; return ILQR_ERR_STATE; }
-  double def[ILQR_AL_BOUNDS];
-  if (!c->n_alb) h1host::al_default_bounds(c->P.al_margin, def);
-  for (int b = 0; b < c->B; ++b)
-    std::memcpy(bounds + (size_t)b * ILQR_AL_BOUNDS, c->n_alb ? c->h_alb.data() + (size_t)(c->n_alb == 1 ? 0 : b) * ILQR_AL_BOUNDS : def, sizeof(double) * ILQR_AL_BOUNDS);
-  return ILQR_OK;
-}
-// host image of the store <-> the interface's [B][N+1][19][2] / [B][N][19][2] (lo, hi) arrays
-static int al_read_store(ilqr_hip_ctx* c, std::vector<double>& st) {
-  st.resize((size_t)c->B * h1::al_record_doubles(c->N));
+static size_t al_store_doubles(const ilqr_hip_ctx* c, const AlFamily& f) { return h1::AL_HDR + (size_t)f.knot_rec * (c->N + 1); }
+// the state family's multiplier store, for a table or a window of bounds: zero where none was installed; bounds that replace others keep the
+// multipliers.  rho_state starts at rho_state0 either way
+__attribute__((noinline, minsize)) static int al_state_store_install(ilqr_hip_ctx* c, double rho_state0, double tol_state) {
+  AlFamily& f = c->al.st;
+  const size_t B = c->B, rec_d = al_store_doubles(c, f);
+  if (!f.store) TRY(dalloc(c, &f.store, B * rec_d));
+  std::vector<double> st(B * rec_d, 0.0);
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(st.data(), c->d_al, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (f.sets) HIPCHK_S(c, hipMemcpy(st.data(), f.store, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < B; ++b) st[b * rec_d + h1::ALS_RHO] = rho_state0;
+  HIPCHK_S(c, hipMemcpy(f.store, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!f.sets) HIPCHK_S(c, hipMemset(c->al.sviol, 0, B * sizeof(double)));
+  c->P.als = f.store; c->P.als_stride = (long)rec_d;
+  c->al.srho0 = rho_state0; c->al.stol = tol_state;
   return ILQR_OK;
 }
-// one pass over the store's image: to_store = false reads it into the interface's arrays, true writes them into it (any pointer may be null;
-// knot 0 of the hinges is stored as zero: x_0 is given, its multipliers stay zero)
-__attribute__((noinline, minsize)) static void al_convert(const ilqr_hip_ctx* c, double* st, double* joint, double* ctrl, double* rho, bool to_store) {
-  const size_t N = c->N, rec = h1::al_record_doubles(c->N);
-  auto mv = [&](double& s, double& o, bool zero) { if (to_store) s = zero ? 0.0 : o; else o = s; };
+// a table (one record per set) or a window (N + 1 records per set) of a family's bounds, behind the caller's argument checks: the later call
+// wins within a family.  state: rho_state0 and tol_state of the state family, whose store comes with its bounds
+__attribute__((noinline, minsize)) static int al_install(ilqr_hip_ctx* c, AlFamily& f, const double* bounds, int n_sets, bool window, const double* state = nullptr) {
+  enter(c);
+  const size_t rows = (size_t)n_sets * (window ? c->N + 1 : 1);
+  if (window) TRY(al_knot_ready(c));
+  else if (!f.table) TRY(dalloc(c, &f.table, (size_t)c->B * f.width));
+  TRY(upload_rows(c, window ? f.window : f.table, bounds, rows, f.fields, f.width));
+  if (state) TRY(al_state_store_install(c, state[0], state[1]));
+  if (!window) f.host.assign(bounds, bounds + rows * f.fields);
+  f.sets = n_sets; f.knot = window;
+  return al_point_bounds(c);
+}
+// both setters' argument checks; rows: records per set
+__attribute__((noinline, minsize)) static int al_set_bounds(ilqr_hip_ctx* c, AlFamily& f, const double* bounds, int n_sets, bool window, const double* state = nullptr) {
+  TRY(al_installed(c));
+  if (!bounds || check_sets(c, n_sets) || (state && (!(state[0] > 0.0) || !std::isfinite(state[0]) || !(state[1] >= 0.0))) || !al_bounds_ok(f, bounds, (size_t)n_sets * (window ? c->N + 1 : 1))) return ILQR_ERR_ARG;
+  return al_install(c, f, bounds, n_sets, window, state);
+}
+// table or window; the buffers stay with the handle for the next one
+__attribute__((noinline)) static int al_clear_bounds(ilqr_hip_ctx* c, AlFamily& f) {
+  TRY(al_installed(c));
+  f.sets = 0; f.knot = false;
+  if (&f == &c->al.st) { c->P.als = nullptr; c->P.als_stride = 0; }
+  enter(c);
+  return al_point_bounds(c);
+}
+// the whole-horizon getter: the record each rollout is solved with
+__attribute__((noinline, minsize)) static int al_get_bounds(ilqr_hip_ctx* c, AlFamily& f, double* bounds) {
+  if (!bounds) return ILQR_ERR_ARG;
+  TRY(al_installed(c));
+  if (f.knot) { c->err = AL_WINDOW_ERR; return ILQR_ERR_STATE; }
+  double none[ILQR_AL_BOUNDS];
+  if (!f.sets) al_no_bounds(c, f, none);
+  for (int b = 0; b < c->B; ++b) std::memcpy(bounds + (size_t)b * f.fields, f.sets ? f.host.data() + (size_t)(f.sets == 1 ? 0 : b) * f.fields : none, sizeof(double) * f.fields);
+  return ILQR_OK;
+}
+int ilqr_hip_set_al_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) { return c ? al_set_bounds(c, c->al.jc, bounds, n_sets, false) : ILQR_ERR_ARG; }
+int ilqr_hip_set_al_knot_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) { return c ? al_set_bounds(c, c->al.jc, bounds, n_sets, true) : ILQR_ERR_ARG; }
+int ilqr_hip_set_al_state_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
+  const double state[2] = {rho_state0, tol_state};
+  return c ? al_set_bounds(c, c->al.st, bounds, n_sets, false, state) : ILQR_ERR_ARG;
+}
+int ilqr_hip_set_al_state_knot_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
+  const double state[2] = {rho_state0, tol_state};
+  return c ? al_set_bounds(c, c->al.st, bounds, n_sets, true, state) : ILQR_ERR_ARG;
+}
+int ilqr_hip_clear_al_bounds(ilqr_hip_ctx* c) { return c ? al_clear_bounds(c, c->al.jc) : ILQR_ERR_ARG; }
+int ilqr_hip_clear_al_state_bounds(ilqr_hip_ctx* c) { return c ? al_clear_bounds(c, c->al.st) : ILQR_ERR_ARG; }
+int ilqr_hip_num_al_bound_sets(const ilqr_hip_ctx* c) { return c ? c->al.jc.sets : -1; }
+int ilqr_hip_num_al_state_bound_sets(const ilqr_hip_ctx* c) { return c ? c->al.st.sets : -1; }
+int ilqr_hip_get_al_bounds(ilqr_hip_ctx* c, double* bounds) { return c ? al_get_bounds(c, c->al.jc, bounds) : ILQR_ERR_ARG; }
+int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* c, double* bounds) { return c ? al_get_bounds(c, c->al.st, bounds) : ILQR_ERR_ARG; }
+int ilqr_hip_al_bounds_per_knot(const ilqr_hip_ctx* c) { return c ? ((c->P.al && c->al.jc.knot) ? 1 : 0) | ((c->P.al && c->al.st.knot) ? 2 : 0) : -1; }
+// what the kernels read at every knot, whoever wrote it: the windows (knot stride set), a table's records, or nothing (al_no_bounds)
+__attribute__((minsize)) int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* c, double* joint_ctrl, double* state) {
+  if (!c) return ILQR_ERR_ARG;
+  TRY(al_installed(c));
+  enter(c);
+  const size_t B = c->B, n1 = (size_t)c->N + 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const struct { const AlFamily& f; double* out; const double* dev; long stride, knot; } fams[2] = {
+    {c->al.jc, joint_ctrl, c->P.alb, c->P.alb_stride, c->P.alb_knot}, {c->al.st, state, c->P.alsb, c->P.alsb_stride, c->P.alsb_knot}};
+  for (const auto& v : fams) {
+    if (!v.out) continue;
+    const size_t F = v.f.fields, W = v.f.width, per_set = (v.knot ? n1 : 1) * W;
+    std::vector<double> img(v.dev ? (v.stride ? B : 1) * per_set : F);
+    if (v.dev) HIPCHK(c, hipMemcpy(img.data(), v.dev, img.size() * sizeof(double), hipMemcpyDeviceToHost));
+    else al_no_bounds(c, v.f, img.data());
+    for (size_t b = 0; b < B; ++b)
+      for (size_t t = 0; t < n1; ++t)
+        std::memcpy(v.out + (b * n1 + t) * F, v.dev ? img.data() + (v.stride ? b : 0) * per_set + (v.knot ? t : 0) * W : img.data(), sizeof(double) * F);
+  }
+  return ILQR_OK;
+}
+
+// ---- the multiplier stores.  Host image of a family's store <-> the interface's arrays, one pass: block g of a knot's record <-> mu[g]
+// [B][N+1][per][2] (lower, upper; block 1, the actuators: [B][N][per][2]), the penalties <-> rho [B][blocks]; to_store = false reads the image
+// into the arrays, true writes them into it (any pointer may be null; knot 0 of block 0 is stored as zero: x_0 is given, its multipliers stay zero)
+__attribute__((noinline, minsize)) static void al_convert(const ilqr_hip_ctx* c, const AlFamily& f, double* st, double* const mu[2], double* rho, bool to_store) {
+  const size_t N = c->N, rec = al_store_doubles(c, f);
   for (size_t b = 0; b < (size_t)c->B; ++b) {
     double* r = st + b * rec;
-    if (rho) { mv(r[h1::AL_RHO_JOINT], rho[2 * b], false); mv(r[h1::AL_RHO_CTRL], rho[2 * b + 1], false); }
-    for (size_t t = 0; t <= N; ++t) {
-      double* k = r + h1::AL_HDR + t * h1::AL_KNOT;
-      for (int i = 0; i < 19; ++i) {
-        if (joint) { double* o = joint + ((b * (N + 1) + t) * 19 + i) * 2; mv(k[h1::AL_JLO + i], o[0], t == 0); mv(k[h1::AL_JHI + i], o[1], t == 0); }
-        if (ctrl && t < N) { double* o = ctrl + ((b * N + t) * 19 + i) * 2; mv(k[h1::AL_ULO + i], o[0], false); mv(k[h1::AL_UHI + i], o[1], false); }
-      }
+    for (int g = 0; g < f.blocks; ++g) {
+      if (rho) { if (to_store) r[g] = rho[f.blocks * b + g]; else rho[f.blocks * b + g] = r[g]; }
+      if (!mu[g]) continue;
+      const size_t T = g ? N : N + 1;
+      for (size_t t = 0; t < T; ++t)
+        for (int i = 0; i < 2 * f.per; ++i) {
+          double& s = r[h1::AL_HDR + t * f.knot_rec + f.block_at[g] + i];
+          double& o = mu[g][((b * T + t) * f.per + i % f.per) * 2 + i / f.per];
+          if (to_store) s = (g == 0 && t == 0) ? 0.0 : o; else o = s;
+        }
     }
   }
 }
-static int al_get(ilqr_hip_ctx* c, double* joint, double* ctrl, double* rho) {
-  if (!c) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+// doubles of mu[g] and of rho
+static size_t al_mu_doubles(const ilqr_hip_ctx* c, const AlFamily& f, int g) { return (size_t)c->B * (g ? c->N : c->N + 1) * f.per * 2; }
+// reads the store (set: installs the caller's arrays in its image and writes it back).  Without a state family its getters give zero
+// multipliers and rho_state 0 (nothing is constrained) and its setter refuses
+__attribute__((noinline)) static int al_store_io(ilqr_hip_ctx* c, AlFamily& f, double* const mu[2], double* rho, bool set) {
+  TRY(al_installed(c));
+  if (al_family_absent(c, f)) {
+    if (set) { c->err = "no state bounds installed"; return ILQR_ERR_STATE; }
+    for (int g = 0; g < f.blocks; ++g) if (mu[g]) std::fill(mu[g], mu[g] + al_mu_doubles(c, f, g), 0.0);
+    if (rho) std::fill(rho, rho + (size_t)c->B * f.blocks, 0.0);
+    return ILQR_OK;
+  }
+  if (set) {
+    auto ok = [](const double* v, size_t n, bool positive) { if (v) for (size_t e = 0; e < n; ++e) if (!std::isfinite(v[e]) || v[e] < 0.0 || (positive && v[e] == 0.0)) return false; return true; };
+    for (int g = 0; g < f.blocks; ++g) if (!ok(mu[g], al_mu_doubles(c, f, g), false)) return ILQR_ERR_ARG;
+    if (!ok(rho, (size_t)c->B * f.blocks, true)) return ILQR_ERR_ARG;
+  }
   enter(c);
-  std::vector<double> st; TRY(al_read_store(c, st));
-  al_convert(c, st.data(), joint, ctrl, rho, false);
+  std::vector<double> st((size_t)c->B * al_store_doubles(c, f));
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(st.data(), f.store, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+  al_convert(c, f, st.data(), mu, rho, set);
+  if (set) HIPCHK_S(c, hipMemcpy(f.store, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
   return ILQR_OK;
 }
-int ilqr_hip_get_al_multipliers(ilqr_hip_ctx* c, double* joint, double* ctrl) { return al_get(c, joint, ctrl, nullptr); }
-int ilqr_hip_get_al_penalties(ilqr_hip_ctx* c, double* rho) { return rho ? al_get(c, nullptr, nullptr, rho) : ILQR_ERR_ARG; }
-__attribute__((noinline, minsize)) static bool al_values_ok(const double* v, size_t n, bool positive) {
-  if (v) for (size_t e = 0; e < n; ++e) if (!std::isfinite(v[e]) || v[e] < 0.0 || (positive && v[e] == 0.0)) return false;
-  return true;
-}
+int ilqr_hip_get_al_multipliers(ilqr_hip_ctx* c, double* joint, double* ctrl) { double* const mu[2] = {joint, ctrl}; return c ? al_store_io(c, c->al.jc, mu, nullptr, false) : ILQR_ERR_ARG; }
+int ilqr_hip_get_al_penalties(ilqr_hip_ctx* c, double* rho) { double* const mu[2] = {nullptr, nullptr}; return c && rho ? al_store_io(c, c->al.jc, mu, rho, false) : ILQR_ERR_ARG; }
 int ilqr_hip_set_al_multipliers(ilqr_hip_ctx* c, const double* joint, const double* ctrl, const double* rho) {
-  if (!c) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  const size_t B = c->B, N = c->N;
-  if (!al_values_ok(joint, B * (N + 1) * 38, false) || !al_values_ok(ctrl, B * N * 38, false) || !al_values_ok(rho, B * 2, true)) return ILQR_ERR_ARG;
-  enter(c);
-  std::vector<double> st; TRY(al_read_store(c, st));
-  al_convert(c, st.data(), const_cast<double*>(joint), const_cast<double*>(ctrl), const_cast<double*>(rho), true);
-  HIPCHK_S(c, hipMemcpy(c->d_al, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-  return ILQR_OK;
+  double* const mu[2] = {const_cast<double*>(joint), const_cast<double*>(ctrl)};
+  return c ? al_store_io(c, c->al.jc, mu, const_cast<double*>(rho), true) : ILQR_ERR_ARG;
 }
+int ilqr_hip_get_al_state_multipliers(ilqr_hip_ctx* c, double* m) { double* const mu[2] = {m, nullptr}; return c && m ? al_store_io(c, c->al.st, mu, nullptr, false) : ILQR_ERR_ARG; }
+int ilqr_hip_get_al_state_penalties(ilqr_hip_ctx* c, double* rho) { double* const mu[2] = {nullptr, nullptr}; return c && rho ? al_store_io(c, c->al.st, mu, rho, false) : ILQR_ERR_ARG; }
+int ilqr_hip_set_al_state_multipliers(ilqr_hip_ctx* c, const double* m, const double* rho) {
+  double* const mu[2] = {const_cast<double*>(m), nullptr};
+  return c ? al_store_io(c, c->al.st, mu, const_cast<double*>(rho), true) : ILQR_ERR_ARG;
+}
+// ---- the observables of the update
 int ilqr_hip_get_al_violation(ilqr_hip_ctx* c, double* viol, int* done) {
   if (!c) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  TRY(al_installed(c));
   enter(c);
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  if (viol) HIPCHK_S(c, hipMemcpy(viol, c->d_al_viol, (size_t)c->B * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (done) HIPCHK_S(c, hipMemcpy(done, c->d_al_done, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost));
+  if (viol) HIPCHK_S(c, hipMemcpy(viol, c->al.viol, (size_t)c->B * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (done) HIPCHK_S(c, hipMemcpy(done, c->al.done, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost));
   return ILQR_OK;
 }
-int ilqr_hip_get_al_trace(ilqr_hip_ctx* c, double* out) {
+int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* c, double* viol) {
+  if (!c || !viol) return ILQR_ERR_ARG;
+  TRY(al_installed(c));
+  if (al_family_absent(c, c->al.st)) { std::fill(viol, viol + c->B, 0.0); return ILQR_OK; }
+  enter(c);
+  HIPCHK_S(c, hipStreamSynchronize(c->stream));
+  HIPCHK_S(c, hipMemcpy(viol, c->al.sviol, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+// the trace of the last solve: `width` doubles per round and rollout
+__attribute__((noinline)) static int al_get_trace(ilqr_hip_ctx* c, const double* trace, int width, double* out) {
   if (!c || !out) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
+  TRY(al_installed(c));
   enter(c);
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(out, c->d_al_trace, (size_t)c->al_rounds * c->B * 5 * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK_S(c, hipMemcpy(out, trace, (size_t)c->al.rounds * c->B * width * sizeof(double), hipMemcpyDeviceToHost));
   return ILQR_OK;
 }
+int ilqr_hip_get_al_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.trace : nullptr, 5, out); }
+int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.strace : nullptr, 2, out); }
 int ilqr_hip_al_update(ilqr_hip_ctx* c, int round) {
   if (!c || round < 0) return ILQR_ERR_ARG;
-  if (!c->P.al) { c->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; }
-  if (round >= c->al_rounds) return ILQR_ERR_ARG;
+  TRY(al_installed(c));
+  if (round >= c->al.rounds) return ILQR_ERR_ARG;
   if (!c->initialized) return ILQR_ERR_STATE;
   enter(c);
-  HIPCHK_S(c, hipMemsetAsync(c->d_al_left + round, 0, sizeof(int), c->stream));
+  HIPCHK_S(c, hipMemsetAsync(c->al.left + round, 0, sizeof(int), c->stream));
   ilqr::launch_al_update(c->S, al_view(c), round, c->early_exit, c->stream);
   HIPCHK_S(c, hipGetLastError());
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
 
-// ---- the state family: bounds on the 28 box coordinates (pelvis position, pelvis velocity, joint velocities), one record lo[28], hi[28] per set
-int ilqr_hip_al_state_slot(int k) { return (k >= 0 && k < ILQR_AL_STATE_COORDS) ? h1::als_slot(k) : -1; }
-// every pair: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
-__attribute__((noinline, minsize)) static bool al_state_bounds_ok(const double* v, int n_sets) {
-  for (int s = 0; s < n_sets; ++s)
-    for (int i = 0; i < ILQR_AL_STATE_COORDS; ++i) {
-      const double lo = v[(size_t)s * ILQR_AL_STATE_BOUNDS + i], hi = v[(size_t)s * ILQR_AL_STATE_BOUNDS + ILQR_AL_STATE_COORDS + i];
-      if (!(lo <= hi) || lo == HUGE_VAL || hi == -HUGE_VAL) return false;      // (a NaN fails lo <= hi)
-    }
-  return true;
-}
-#define AL_STATE_INSTALLED(c) do { if (!(c)->P.al) { (c)->err = "no augmented Lagrangian installed"; return ILQR_ERR_STATE; } } while (0)
-// the state family's multiplier store, for a table or a window of bounds: zero where none was installed; bounds that replace others keep the
-// multipliers.  rho_state starts at rho_state0 either way
-__attribute__((noinline, minsize)) static int al_state_store_install(ilqr_hip_ctx* c, double rho_state0, double tol_state) {
-  const size_t B = c->B, rec_d = (size_t)h1::als_record_doubles(c->N);
-  if (!c->d_als) TRY(dalloc(c, &c->d_als, B * rec_d));
-  std::vector<double> st(B * rec_d, 0.0);
-  HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  if (c->n_alsb) HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t b = 0; b < B; ++b) st[b * rec_d + h1::ALS_RHO] = rho_state0;
-  HIPCHK_S(c, hipMemcpy(c->d_als, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (!c->n_alsb) HIPCHK_S(c, hipMemset(c->d_als_viol, 0, B * sizeof(double)));
-  c->P.als = c->d_als; c->P.als_stride = (long)rec_d;
-  c->als_rho0 = rho_state0; c->als_tol = tol_state;
-  return ILQR_OK;
-}
-int ilqr_hip_set_al_state_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!bounds || check_sets(c, n_sets) || !(rho_state0 > 0.0) || !std::isfinite(rho_state0) || !(tol_state >= 0.0) || !al_state_bounds_ok(bounds, n_sets)) return ILQR_ERR_ARG;
-  enter(c);
-  static_assert(h1::ALSB_FIELDS == ILQR_AL_STATE_BOUNDS && h1::ALS_COORDS == ILQR_AL_STATE_COORDS && h1::ALSB_HI == 28, "the interface's record is the device record without its padding");
-  if (!c->d_alsb) TRY(dalloc(c, &c->d_alsb, (size_t)c->B * h1::ALSB_STRIDE));
-  std::vector<double> rec((size_t)n_sets * h1::ALSB_STRIDE, 0.0);
-  for (int s = 0; s < n_sets; ++s) std::memcpy(rec.data() + (size_t)s * h1::ALSB_STRIDE, bounds + (size_t)s * ILQR_AL_STATE_BOUNDS, sizeof(double) * ILQR_AL_STATE_BOUNDS);
-  HIPCHK(c, hipMemcpyAsync(c->d_alsb, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  TRY(al_state_store_install(c, rho_state0, tol_state));
-  c->h_alsb.assign(bounds, bounds + (size_t)n_sets * ILQR_AL_STATE_BOUNDS);
-  c->n_alsb = n_sets; c->alsbk = false;      // (a table replaces a window)
-  return al_point_bounds(c);
-}
-int ilqr_hip_clear_al_state_bounds(ilqr_hip_ctx* c) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  c->P.als = nullptr; c->P.als_stride = 0; c->P.alsb = nullptr; c->P.alsb_stride = 0; c->n_alsb = 0; c->alsbk = false;      // (table or window; the buffers stay with the handle for the next one)
-  return al_point_bounds(c);
-}
-int ilqr_hip_num_al_state_bound_sets(const ilqr_hip_ctx* c) { return c ? c->n_alsb : -1; }
-__attribute__((minsize)) int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* c, double* bounds) {
-  if (!c || !bounds) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (c->alsbk) { c->err = AL_WINDOW_ERR; return ILQR_ERR_STATE; }
-  for (int b = 0; b < c->B; ++b)
-    for (int i = 0; i < ILQR_AL_STATE_BOUNDS; ++i)
-      bounds[(size_t)b * ILQR_AL_STATE_BOUNDS + i] = c->n_alsb ? c->h_alsb[(size_t)(c->n_alsb == 1 ? 0 : b) * ILQR_AL_STATE_BOUNDS + i] : (i < ILQR_AL_STATE_COORDS ? -HUGE_VAL : HUGE_VAL);
-  return ILQR_OK;
-}
-// host image of the state store <-> the interface's [B][N+1][28][2] (lower, upper) array and rho [B]; to_store as al_convert (knot 0 stored as zero)
-__attribute__((noinline, minsize)) static void al_state_convert(const ilqr_hip_ctx* c, double* st, double* mu, double* rho, bool to_store) {
-  const size_t N = c->N, rec = (size_t)h1::als_record_doubles(c->N);
-  for (size_t b = 0; b < (size_t)c->B; ++b) {
-    double* r = st + b * rec;
-    if (rho) { if (to_store) r[h1::ALS_RHO] = rho[b]; else rho[b] = r[h1::ALS_RHO]; }
-    if (mu) for (size_t t = 0; t <= N; ++t) {
-      double* k = r + h1::ALS_HDR + t * h1::ALS_KNOT;
-      for (int i = 0; i < h1::ALS_COORDS; ++i) {
-        double* o = mu + ((b * (N + 1) + t) * h1::ALS_COORDS + i) * 2;
-        if (to_store) { k[h1::ALS_LO + i] = t == 0 ? 0.0 : o[0]; k[h1::ALS_HI + i] = t == 0 ? 0.0 : o[1]; }
-        else { o[0] = k[h1::ALS_LO + i]; o[1] = k[h1::ALS_HI + i]; }
-      }
-    }
-  }
-}
-// without a table: zero multipliers, rho_state and violation 0 (nothing is constrained)
-static int al_state_get(ilqr_hip_ctx* c, double* mu, double* rho) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  const size_t B = c->B, N = c->N;
-  if (!c->n_alsb) {
-    if (mu) std::fill(mu, mu + B * (N + 1) * ILQR_AL_STATE_BOUNDS, 0.0);
-    if (rho) std::fill(rho, rho + B, 0.0);
-    return ILQR_OK;
-  }
-  enter(c);
-  std::vector<double> st(B * (size_t)h1::als_record_doubles(c->N));
-  HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-  al_state_convert(c, st.data(), mu, rho, false);
-  return ILQR_OK;
-}
-int ilqr_hip_get_al_state_multipliers(ilqr_hip_ctx* c, double* mu) { return mu ? al_state_get(c, mu, nullptr) : ILQR_ERR_ARG; }
-int ilqr_hip_get_al_state_penalties(ilqr_hip_ctx* c, double* rho) { return rho ? al_state_get(c, nullptr, rho) : ILQR_ERR_ARG; }
-int ilqr_hip_set_al_state_multipliers(ilqr_hip_ctx* c, const double* mu, const double* rho) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!c->n_alsb) { c->err = "no state bounds installed"; return ILQR_ERR_STATE; }
-  const size_t B = c->B, N = c->N;
-  if (!al_values_ok(mu, B * (N + 1) * ILQR_AL_STATE_BOUNDS, false) || !al_values_ok(rho, B, true)) return ILQR_ERR_ARG;
-  enter(c);
-  std::vector<double> st(B * (size_t)h1::als_record_doubles(c->N));
-  HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(st.data(), c->d_als, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-  al_state_convert(c, st.data(), const_cast<double*>(mu), const_cast<double*>(rho), true);
-  HIPCHK_S(c, hipMemcpy(c->d_als, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-  return ILQR_OK;
-}
-int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* c, double* viol) {
-  if (!c || !viol) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!c->n_alsb) { std::fill(viol, viol + c->B, 0.0); return ILQR_OK; }
-  enter(c);
-  HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(viol, c->d_als_viol, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost));
-  return ILQR_OK;
-}
-int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* c, double* out) {
-  if (!c || !out) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  enter(c);
-  HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(out, c->d_als_trace, (size_t)c->al_rounds * c->B * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  return ILQR_OK;
-}
-
-// ---- bounds that change from knot to knot: windows [n_sets][N+1][76] / [n_sets][N+1][56] in the whole-horizon setters' field order, and a
-// bounds track they are cut from on the device (al_bounds_track_kernels.hip).  The kernels that read windows: need_al_knot_module
-#define AL_COLD __attribute__((minsize))      // setters, getters and uploads: none is on a solve's path
-// HIPCHK with one text for every call of this section (HIPCHK keeps each call's own source text in the library)
-#define HIPCHK_AL(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed((ctx), "per-knot bounds", e_); } while (0)
-// `padded` rows of `width` doubles from `n` rows of `fields`
-__attribute__((noinline, minsize)) static int al_upload_rows(ilqr_hip_ctx* c, double* dst, const double* src, size_t n, int fields, int width) {
-  std::vector<double> rec(n * width, 0.0);
-  for (size_t r = 0; r < n; ++r) std::memcpy(rec.data() + r * width, src + r * fields, sizeof(double) * fields);
-  HIPCHK_AL(c, hipMemcpyAsync(dst, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
-}
-AL_COLD int ilqr_hip_set_al_knot_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!bounds || check_sets(c, n_sets) || !al_bounds_ok(bounds, n_sets * (c->N + 1))) return ILQR_ERR_ARG;
-  enter(c);
-  TRY(al_knot_ready(c));
-  TRY(al_upload_rows(c, c->d_albk, bounds, (size_t)n_sets * (c->N + 1), ILQR_AL_BOUNDS, h1::ALB_STRIDE));
-  c->n_alb = n_sets; c->albk = true;
-  return al_point_bounds(c);
-}
-AL_COLD int ilqr_hip_set_al_state_knot_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_state0, double tol_state) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!bounds || check_sets(c, n_sets) || !(rho_state0 > 0.0) || !std::isfinite(rho_state0) || !(tol_state >= 0.0) || !al_state_bounds_ok(bounds, n_sets * (c->N + 1))) return ILQR_ERR_ARG;
-  enter(c);
-  TRY(al_knot_ready(c));
-  TRY(al_upload_rows(c, c->d_alsbk, bounds, (size_t)n_sets * (c->N + 1), ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE));
-  TRY(al_state_store_install(c, rho_state0, tol_state));
-  c->n_alsb = n_sets; c->alsbk = true;
-  return al_point_bounds(c);
-}
-int ilqr_hip_al_bounds_per_knot(const ilqr_hip_ctx* c) { return c ? ((c->P.al && c->albk) ? 1 : 0) | ((c->P.al && c->alsbk) ? 2 : 0) : -1; }
-AL_COLD int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* c, double* joint_ctrl, double* state) {
-  if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  enter(c);
-  const size_t B = c->B, n1 = (size_t)c->N + 1;
-  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
-  for (int fam = 0; fam < 2; ++fam) {
-    double* out = fam ? state : joint_ctrl;
-    if (!out) continue;
-    const size_t F = fam ? ILQR_AL_STATE_BOUNDS : ILQR_AL_BOUNDS, W = fam ? h1::ALSB_STRIDE : h1::ALB_STRIDE;
-    const long knot = fam ? c->P.alsb_knot : c->P.alb_knot, stride = fam ? c->P.alsb_stride : c->P.alb_stride;
-    const double* dev = fam ? c->P.alsb : c->P.alb;
-    // what the kernels read: the windows (knot != 0), a table's records, or nothing (the model's bounds at the margin; no state family)
-    std::vector<double> img;
-    double def[ILQR_AL_BOUNDS];
-    if (dev) {
-      img.resize((stride ? B : 1) * (knot ? n1 : 1) * W);
-      HIPCHK_AL(c, hipMemcpy(img.data(), dev, img.size() * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (!fam) h1host::al_default_bounds(c->P.al_margin, def);
-    for (size_t b = 0; b < B; ++b)
-      for (size_t t = 0; t < n1; ++t) {
-        double* o = out + (b * n1 + t) * F;
-        if (dev) std::memcpy(o, img.data() + (stride ? b : 0) * (knot ? n1 : 1) * W + (knot ? t : 0) * W, sizeof(double) * F);
-        else if (!fam) std::memcpy(o, def, sizeof(def));
-        else for (size_t i = 0; i < F; ++i) o[i] = i < ILQR_AL_STATE_COORDS ? -HUGE_VAL : HUGE_VAL;
-      }
-  }
-  return ILQR_OK;
-}
 // ---- the bounds track
 static const char* const AL_TRACK_STATE_ERR = "the track's state part needs an installed state family";
 static const char* const AL_NO_TRACK_ERR = "no bounds track installed";
-AL_COLD int ilqr_hip_set_al_bounds_track(ilqr_hip_ctx* c, int rows, const double* joint_ctrl, const double* state) {
+// (behind a synchronisation: a window kernel in flight still reads the track)
+__attribute__((noinline)) static void al_track_free(ilqr_hip_ctx* c) {
+  for (AlFamily* f : {&c->al.jc, &c->al.st}) { if (f->track) hipFree(f->track); f->track = nullptr; }
+  c->al.track_rows = 0; c->al.track_sets = 1;
+}
+__attribute__((minsize)) int ilqr_hip_set_al_bounds_track(ilqr_hip_ctx* c, int rows, const double* joint_ctrl, const double* state) {
   if (!c) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (rows < 1 || (!joint_ctrl && !state) || (joint_ctrl && !al_bounds_ok(joint_ctrl, rows)) || (state && !al_state_bounds_ok(state, rows))) return ILQR_ERR_ARG;
-  if (state && !c->n_alsb) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
+  TRY(al_installed(c));
+  if (rows < 1 || (!joint_ctrl && !state) || (joint_ctrl && !al_bounds_ok(c->al.jc, joint_ctrl, rows)) || (state && !al_bounds_ok(c->al.st, state, rows))) return ILQR_ERR_ARG;
+  if (state && !c->al.st.sets) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
   enter(c);
   TRY(al_knot_ready(c));
-  HIPCHK_AL(c, hipStreamSynchronize(c->stream));      // (a window kernel in flight still reads the track this call replaces)
-  if (c->d_abt_jc) hipFree(c->d_abt_jc);
-  if (c->d_abt_st) hipFree(c->d_abt_st);
-  c->d_abt_jc = nullptr; c->d_abt_st = nullptr; c->abt_rows = 0; c->abt_sets = 1;
-  if (!c->d_abt_start) TRY(dalloc(c, &c->d_abt_start, (size_t)c->B));
-  HIPCHK_AL(c, hipMemsetAsync(c->d_abt_start, 0, (size_t)c->B * sizeof(int), c->stream));      // one shared start of 0
-  if (joint_ctrl) { TRY(dalloc(c, &c->d_abt_jc, (size_t)rows * h1::ALB_STRIDE)); TRY(al_upload_rows(c, c->d_abt_jc, joint_ctrl, rows, ILQR_AL_BOUNDS, h1::ALB_STRIDE)); }
-  if (state) { TRY(dalloc(c, &c->d_abt_st, (size_t)rows * h1::ALSB_STRIDE)); TRY(al_upload_rows(c, c->d_abt_st, state, rows, ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE)); }
-  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
-  c->abt_rows = rows;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  al_track_free(c);
+  if (!c->al.track_start) TRY(dalloc(c, &c->al.track_start, (size_t)c->B));
+  HIPCHK(c, hipMemsetAsync(c->al.track_start, 0, (size_t)c->B * sizeof(int), c->stream));      // one shared start of 0
+  const struct { AlFamily& f; const double* src; } parts[2] = {{c->al.jc, joint_ctrl}, {c->al.st, state}};
+  for (const auto& v : parts) if (v.src) { TRY(dalloc(c, &v.f.track, (size_t)rows * v.f.width)); TRY(upload_rows(c, v.f.track, v.src, rows, v.f.fields, v.f.width)); }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->al.track_rows = rows;
   return ILQR_OK;
 }
-AL_COLD int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* c) {
+__attribute__((minsize)) int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   enter(c);
-  HIPCHK_AL(c, hipStreamSynchronize(c->stream));      // (a window kernel in flight still reads it)
-  if (c->d_abt_jc) hipFree(c->d_abt_jc);
-  if (c->d_abt_st) hipFree(c->d_abt_st);
-  c->d_abt_jc = nullptr; c->d_abt_st = nullptr; c->abt_rows = 0; c->abt_sets = 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  al_track_free(c);
   return ILQR_OK;
 }
-int ilqr_hip_al_bounds_track_rows(const ilqr_hip_ctx* c) { return c ? c->abt_rows : -1; }
-AL_COLD int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* c, const int* start, int n_sets) {
+int ilqr_hip_al_bounds_track_rows(const ilqr_hip_ctx* c) { return c ? c->al.track_rows : -1; }
+__attribute__((minsize)) int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* c, const int* start, int n_sets) {
   if (!c || !start || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   for (int b = 0; b < n_sets; ++b) if (start[b] < 0) return ILQR_ERR_ARG;
-  if (!c->abt_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
+  if (!c->al.track_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
   enter(c);
-  HIPCHK_AL(c, hipMemcpyAsync(c->d_abt_start, start, (size_t)n_sets * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK_AL(c, hipStreamSynchronize(c->stream));
-  c->abt_sets = n_sets;
+  HIPCHK(c, hipMemcpyAsync(c->al.track_start, start, (size_t)n_sets * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->al.track_sets = n_sets;
   return ILQR_OK;
 }
-AL_COLD int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* c, int step) {
+__attribute__((minsize)) int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* c, int step) {
   if (!c || step < 0) return ILQR_ERR_ARG;
-  AL_STATE_INSTALLED(c);
-  if (!c->abt_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
-  if (c->d_abt_st && !c->n_alsb) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
+  TRY(al_installed(c));
+  if (!c->al.track_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
+  if (c->al.st.track && !c->al.st.sets) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
   enter(c);
-  const int n_sets = c->abt_sets;
-  const ilqr::AlBoundsTrackDev T{c->d_abt_jc, c->d_abt_st, c->abt_rows};
-  const ilqr::AlBoundsWindowDev W{c->d_albk, c->d_alsbk};
-  ilqr::g_al_knot.window_from_track(&T, &W, c->d_abt_start, n_sets, step, c->N, c->stream);
-  HIPCHK_AL(c, hipGetLastError());
+  const int n_sets = c->al.track_sets;
+  const ilqr::AlBoundsTrackDev T{c->al.jc.track, c->al.st.track, c->al.track_rows};
+  const ilqr::AlBoundsWindowDev W{c->al.jc.window, c->al.st.window};
+  ilqr::g_al_knot.window_from_track(&T, &W, c->al.track_start, n_sets, step, c->N, c->stream);
+  HIPCHK(c, hipGetLastError());
   // the state the knot setters leave; the pointers move only where that state changes (the first cut, or other starts)
-  const bool jc = c->d_abt_jc != nullptr, st = c->d_abt_st != nullptr;
-  const bool same = (!jc || (c->albk && c->n_alb == n_sets)) && (!st || (c->alsbk && c->n_alsb == n_sets)) && c->P.alb_knot;
-  if (jc) { c->albk = true; c->n_alb = n_sets; }
-  if (st) { c->alsbk = true; c->n_alsb = n_sets; }
+  bool same = c->P.alb_knot != 0;
+  for (AlFamily* f : {&c->al.jc, &c->al.st}) if (f->track) { same = same && f->knot && f->sets == n_sets; f->knot = true; f->sets = n_sets; }
   return same ? ILQR_OK : al_point_bounds(c);      // asynchronous on the handle's stream
 }
-#undef HIPCHK_AL
-#undef AL_STATE_INSTALLED
 
 int ilqr_hip_set_contact_schedule(ilqr_hip_ctx* c, const int* stance, int n_sets) {
   if (!c || !stance || check_sets(c, n_sets)) return ILQR_ERR_ARG;
@@ -1694,7 +1593,7 @@ static int enqueue_solve(ilqr_hip_ctx* c, const DevState& S, const h1::ProblemDe
              L.folds_h ? P.dyn.h : 0.0, c->twin ? twin_view(c, S) : S, 0, -1, false, ilqr::nominal_roll(O, L, 1) == ilqr::ROLL_ASIDE, false};
   { StageTimer T(c, 0, st); ilqr::launch_rollout(L, S, P, ilqr::MASK_ALL, 0, 0, S.Jbase, st);
     // (rounds >= 2 of an augmented-Lagrangian solve with the convergence exit: the rollouts that are done enter inactive)
-    if (P.al && c->al_round > 0 && c->early_exit) ilqr::launch_solve_begin_al(S, c->d_al_done + (S.active - c->S.active), st);
+    if (P.al && c->al.round > 0 && c->early_exit) ilqr::launch_solve_begin_al(S, c->al.done + (S.active - c->S.active), st);
     else ilqr::launch_solve_begin(S, st); }  // ilqr.cpp:540
   // the operand-layout Riccati kernel (analytic Jacobians, riccati_pack.hip) has its producers write A_t, B_t and lxx~_t in its own
   // layout; the generic one-wave kernel reads only the tiles I >= J of lxx_t (t < N): the cost quadratics then leave the others unwritten
@@ -1915,30 +1814,30 @@ __attribute__((noinline)) static int enqueue_batch(ilqr_hip_ctx* c, int k) {
 // multipliers, and no list survives k_solve_begin: the linearisation cache and the two skips see nothing of the round before.
 __attribute__((noinline)) static int enqueue_al_rounds(ilqr_hip_ctx* c, int k) {
   hipStream_t st = c->stream;
-  const int rounds = c->al_rounds;
+  const int rounds = c->al.rounds;
   const bool al_stop = c->early_exit && early_exit_gate(c);      // the host reads the count of rollouts left between two rounds
-  HIPCHK_S(c, hipMemsetAsync(c->d_al_done, 0, (size_t)c->B * sizeof(int), st));
-  HIPCHK_S(c, hipMemsetAsync(c->d_al_left, 0, (size_t)rounds * sizeof(int), st));
-  HIPCHK_S(c, hipMemsetAsync(c->d_al_trace, 0xFF, (size_t)rounds * c->B * 5 * sizeof(double), st));      // (all bits set: NaN)
-  HIPCHK_S(c, hipMemsetAsync(c->d_als_trace, 0xFF, (size_t)rounds * c->B * 2 * sizeof(double), st));
-  c->al_rounds_run = 0;
+  HIPCHK_S(c, hipMemsetAsync(c->al.done, 0, (size_t)c->B * sizeof(int), st));
+  HIPCHK_S(c, hipMemsetAsync(c->al.left, 0, (size_t)rounds * sizeof(int), st));
+  HIPCHK_S(c, hipMemsetAsync(c->al.trace, 0xFF, (size_t)rounds * c->B * 5 * sizeof(double), st));      // (all bits set: NaN)
+  HIPCHK_S(c, hipMemsetAsync(c->al.strace, 0xFF, (size_t)rounds * c->B * 2 * sizeof(double), st));
+  c->al.rounds_run = 0;
   int rc = ILQR_OK;
   for (int round = 0; round < rounds && rc == ILQR_OK; ++round) {
-    c->al_round = round;
+    c->al.round = round;
     if (round > 0) { c->first_aside = true; c->spec_iterations = 0; c->split_iterations = 0; }
     rc = enqueue_batch(c, k);
     if (rc != ILQR_OK) break;
     ilqr::launch_al_update(c->S, al_view(c), round, c->early_exit, st);
-    c->al_rounds_run = round + 1;
+    c->al.rounds_run = round + 1;
     if (al_stop && round + 1 < rounds) {
-      hipError_t e = hipMemcpyAsync(&c->h_al_left[round], c->d_al_left + round, sizeof(int), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipEventRecord(c->ev_al, st);
-      if (e == hipSuccess) e = hipEventSynchronize(c->ev_al);
+      hipError_t e = hipMemcpyAsync(&c->al.h_left[round], c->al.left + round, sizeof(int), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(c->al.ev, st);
+      if (e == hipSuccess) e = hipEventSynchronize(c->al.ev);
       if (e != hipSuccess) rc = hip_failed(c, "reading the count of rollouts left between two rounds", e);
-      else if (c->h_al_left[round] == 0) break;      // every rollout is done
+      else if (c->al.h_left[round] == 0) break;      // every rollout is done
     }
   }
-  c->al_round = 0;
+  c->al.round = 0;
   return rc;
 }
 int ilqr_hip_solve_async(ilqr_hip_ctx* c) {
@@ -2598,20 +2497,11 @@ int ilqr_hip_plant_set_model(ilqr_hip_ctx* c, int contact_mode, int joint_limits
 using TableBuf = ilqr_hip_ctx::TableBuf;
 // installs n_sets records of `values` doubles, padded with zeros to `rec` doubles on the device
 static int table_install(ilqr_hip_ctx* c, TableBuf* t, const double* v, int n_sets, int values, int rec) {
-  std::vector<double> padded;
-  if (rec != values) {
-    padded.assign((size_t)n_sets * rec, 0.0);
-    for (int s = 0; s < n_sets; ++s) std::memcpy(padded.data() + (size_t)s * rec, v + (size_t)s * values, values * sizeof(double));
-    v = padded.data();
-  }
-  const size_t bytes = (size_t)n_sets * rec * sizeof(double);
   HIPCHK(c, hipStreamSynchronize(c->stream));      // (a plant call in flight may still read the table this one replaces)
   if (t->d && t->sets != n_sets) { hipFree(t->d); t->d = nullptr; t->sets = 0; }
-  if (!t->d) HIPCHK(c, hipMalloc((void**)&t->d, bytes));
+  if (!t->d) HIPCHK(c, hipMalloc((void**)&t->d, (size_t)n_sets * rec * sizeof(double)));
   t->sets = n_sets;
-  HIPCHK(c, hipMemcpyAsync(t->d, v, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ILQR_OK;
+  return upload_rows(c, t->d, v, n_sets, values, rec);
 }
 static int table_clear(ilqr_hip_ctx* c, TableBuf* t) {
   if (t->d) {

@@ -168,7 +168,7 @@ struct AlDev {
 // ilqr_capi.hip on the first call that installs a window, as the plant kernels' modules are): the per-knot instantiations of
 // k_cost_quadratics, k_traj_knot_cost, k_al_state_knot_cost and k_al_update and the kernels that write the windows, compiled from the same sources with -DAL_KNOT_MODULE, so that
 // the library holds the instantiations it held and nothing more.  Its entry points, C linkage (ilqr_alknot_module_<name>; ilqr_alknot_module() returns this table of them); the library's
-// launchers call them where ProblemDev::alb_knot / alsb_knot / AlDev::bounds_knot is set, which ilqr_capi.hip sets only once the table below is filled.
+// launchers call them for the per-knot variants of al_variant (al_plan.h), which a handle's pointers name only once the table below is filled (AlPlan::module).
 struct AlBoundsTrackDev;
 struct AlBoundsWindowDev;      // (al_bounds_track_kernels.h)
 struct AlKnotModule {

@@ -1068,36 +1068,41 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   QSTAMP(5)
 }
 
+// one workgroup per knot; the grid is padded to a multiple of 8 so that every XCD's share (L % 8) has ceil(total / 8) slots
+#define QUAD_LAUNCH(WS, AL) hipLaunchKernelGGL((k_cost_quadratics<WS, AL>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0)
 #ifdef AL_KNOT_MODULE
 }  // namespace ilqr
 // -DAL_KNOT_MODULE (csrc/Makefile, libilqr_hip_alknot.so; ilqr_kernels.h AlKnotModule): this file once more for the per-knot instantiations of
-// k_cost_quadratics.  The entry point makes the two launches of launch_cost_quadratics below for an already resolved work list: while a
-// state family is installed both families are windows (ilqr_capi.hip al_point_bounds), so two instantiations serve every case.
+// k_cost_quadratics.  The entry point makes the two launches of launch_cost_quadratics below for an already resolved work list, for the two
+// per-knot variants of al_variant (al_plan.h).
 extern "C" void ilqr_alknot_module_cost_quadratics(const ilqr::DevState* Sp, const h1::ProblemDev* Pp, int mode, const int* list, const int* count, int lower, hipStream_t st) {
   using namespace ilqr;
   const DevState& S = *Sp; const ProblemDev& P = *Pp;
   const WorkList w{list, count};
   const long knots = (long)S.B * (S.N + 1), per = (knots + 7) / 8;
   hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
-  if (P.alsb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_KNOT_TABLE_STATE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else hipLaunchKernelGGL((k_cost_quadratics<false, AL_KNOT_TABLE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  switch (al_variant(P.al, P.alb, P.alsb, P.alb_knot)) {
+    case AL_KNOT_TABLE_STATE: QUAD_LAUNCH(false, AL_KNOT_TABLE_STATE); break;
+    default: QUAD_LAUNCH(false, AL_KNOT_TABLE); break;
+  }
 }
 #else
 void launch_cost_quadratics(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, int iter, int lower, const WorkList* wl) {
   const WorkList w = wl ? *wl : work_list(S, mode, iter);
-  if (P.al && P.alb && P.alb_knot) { g_al_knot.cost_quadratics(&S, &P, mode, w.list, w.count, lower, st); return; }      // (windows of bounds: both launches from the module)
+  const int variant = al_variant(P.al, P.alb, P.alsb, P.alb_knot);
+  if (al_per_knot(variant)) { g_al_knot.cost_quadratics(&S, &P, mode, w.list, w.count, lower, st); return; }      // (windows of bounds: both launches from the module)
   const long knots = (long)S.B * (S.N + 1);
   // the per-knot kinematics run for every rollout a masked (stage-API) launch might select; inside a solve for the compacted list
   // (a weight-set table, ProblemDev::wsets, selects the WS instantiations of both kernels)
   if (P.wsets) hipLaunchKernelGGL(k_quad_kin<true>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
   else hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
-  // one workgroup per knot; the grid is padded to a multiple of 8 so that every XCD's share (L % 8) has ceil(total / 8) slots
   const long per = (knots + 7) / 8;
-  if (P.al && P.alsb && P.alb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_TABLE_STATE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else if (P.al && P.alb) hipLaunchKernelGGL((k_cost_quadratics<false, AL_TABLE>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else if (P.al) hipLaunchKernelGGL((k_cost_quadratics<false, AL_MODEL>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else if (P.wsets) hipLaunchKernelGGL((k_cost_quadratics<true, AL_OFF>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
-  else hipLaunchKernelGGL((k_cost_quadratics<false, AL_OFF>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0);
+  switch (variant) {
+    case AL_TABLE_STATE: QUAD_LAUNCH(false, AL_TABLE_STATE); break;
+    case AL_TABLE: QUAD_LAUNCH(false, AL_TABLE); break;
+    case AL_MODEL: QUAD_LAUNCH(false, AL_MODEL); break;
+    default: if (P.wsets) QUAD_LAUNCH(true, AL_OFF); else QUAD_LAUNCH(false, AL_OFF); break;
+  }
 }
 
 }  // namespace ilqr

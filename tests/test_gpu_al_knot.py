@@ -692,3 +692,92 @@ def test_life_cycle_and_refusals():
             t.solve(x0)
     assert np.all(np.isfinite(t.solve(x0))) and t.al_bounds_per_knot() == 3
     t.close()
+
+
+# ------------------------------------------------------------------------------------------------------------- 10. walked installations
+def _walk_inputs():
+    """B = 3 rollouts: the hinges, controls, joint / torque windows and multipliers of three rollouts of al_bounds_cases.regimes_table(), the box
+    coordinates, state windows and state multipliers of three rollouts of al_state_cases.regimes() -- one trajectory that excites both
+    families' discriminating windows (al_knot_cases.joint_windows / state_windows).  Tables are row N of the windows."""
+    Xj, Uj, mu_j, mu_c, rho, _, jcases, _ = bc.regimes_table()
+    Xs, _, _, _, mu_s, rho3, _, _, scases, _ = stc.regimes()
+    ji = [next(i for i, c in enumerate(jcases) if c[0] == "joint" and c[4] == 0 and c[3] > 0), next(i for i, c in enumerate(jcases) if c[0] == "ctrl" and c[4] == 1), bc.INF_ROLLOUTS[0]]
+    si = [next(i for i, c in enumerate(scases) if c[2] > 0 and c[3] == 0),next(i for i, c in enumerate(scases) if c[0] >= 3 and c[2] > 0 and c[3] == 1), stc.INF_ROLLOUTS[0]]
+    assert len(set(ji)) == 3 and len(set(si)) == 3
+    X = Xj[ji].copy(); X[:, :, sr.SLOTS] = Xs[si][:, :, sr.SLOTS]
+    return dict(X=X, U=Uj[ji].copy(), mu_j=mu_j[ji], mu_c=mu_c[ji], rho=rho[ji], mu_s=mu_s[si], rho_s=rho3[si, 2].copy(),
+                jwin=kc.joint_windows()[ji].copy(), swin=kc.state_windows()[0][si].copy())
+
+
+def test_walked_installation_states_equal_fresh_handles():
+    """One long-lived handle walked through every source of bounds the library resolves -- the model's ranges, tables of 1 and B, the model's
+    record under a state table, windows, each expansion of the other family's record, a track cut, removal and re-installation -- against a
+    fresh handle that installs each state directly: bounds, stage cost, quadratics and the update, bit for bit.  Where a state family is
+    installed the stage cost differs from the same state without it (an unread table would pass the comparison)."""
+    d = _walk_inputs()
+    B, N = 3, N4
+    jwin, swin = d["jwin"], d["swin"]
+    T, ST = jwin[:, N].copy(), swin[:, N].copy()
+    RHO_S, TOL_S, M0, M1 = 1.0, 1e-3, stc.STAGE_MARGIN, 0.1
+    jtrack, strack = np.concatenate([jwin[0], jwin[1]]), np.concatenate([swin[0], swin[1]])
+    starts, step = [0, 2, 5], 1
+    jcut, scut = kr.cut(jtrack, starts, step, N, B), kr.cut(strack, starts, step, N, B)
+
+    def fresh(margin, joint, state):
+        s = _solver(B, N=N); s.set_problem(stc.stage_problem())
+        s.set_augmented_lagrangian(1, 1.0, 1.0, margin=margin)
+        if joint is not None:
+            (s.set_al_knot_bounds if joint.ndim == 3 else s.set_al_bounds)(joint)
+        if state is not None:
+            (s.set_al_state_knot_bounds if state.ndim == 3 else s.set_al_state_bounds)(state, RHO_S, TOL_S)
+        return s
+
+    def measure(s, state):
+        s.initialize(d["X"][:, 0], d["U"]); s.set_trajectory(d["X"], d["U"])      # (the cold start clears the done flags of the update before)
+        s.set_al_multipliers(d["mu_j"], d["mu_c"], d["rho"])
+        if state:
+            s.set_al_state_multipliers(d["mu_s"], d["rho_s"])
+        out = list(s.al_knot_bounds()) + [np.array(s.al_bounds_per_knot()), np.array(s.num_al_bound_sets()), np.array(s.num_al_state_bound_sets())]
+        out.append(s.stage_total_cost())
+        s.stage_cost_quadratics(); out += list(s.quadratics())
+        s.al_update(0)
+        out += list(s.al_violation()) + list(s.al_multipliers()) + [s.al_penalties(), s.al_state_multipliers(), s.al_state_penalties(), s.al_state_violation()]
+        return out
+
+    w = _solver(B, N=N); w.set_problem(stc.stage_problem())
+
+    def track(s):
+        s.set_al_state_bounds(ST, RHO_S, TOL_S)                           # (the track's state part needs an installed state family)
+        s.set_al_bounds_track(jtrack, strack); s.set_al_bounds_track_starts(starts); s.al_bounds_window_from_track(step)
+
+    # (name, the step of the walk, what a fresh handle installs: margin, joint / torque bounds, state bounds)
+    walk = [
+        ("model bounds", lambda: w.set_augmented_lagrangian(1, 1.0, 1.0, margin=M0), (M0, None, None)),
+        ("table of 1", lambda: w.set_al_bounds(T[0]), (M0, T[0], None)),
+        ("table of B", lambda: w.set_al_bounds(T), (M0, T, None)),
+        ("table of B, state table of 1", lambda: w.set_al_state_bounds(ST[0], RHO_S, TOL_S), (M0, T, ST[0])),
+        ("state table alone: the model record", lambda: w.clear_al_bounds(), (M0, None, ST[0])),
+        ("the model record at the new margin", lambda: w.set_augmented_lagrangian(1, 1.0, 1.0, margin=M1), (M1, None, ST[0])),
+        ("joint window alone", lambda: (w.clear_al_state_bounds(), w.set_al_knot_bounds(jwin)), (M1, jwin, None)),
+        ("joint window, expanded state table", lambda: w.set_al_state_bounds(ST, RHO_S, TOL_S), (M1, jwin, ST)),
+        ("expanded joint table, state window", lambda: (w.set_al_bounds(T), w.set_al_state_knot_bounds(swin, RHO_S, TOL_S)), (M1, T, swin)),
+        ("expanded model record, state window", lambda: w.clear_al_bounds(), (M1, None, swin)),
+        ("both windows", lambda: w.set_al_knot_bounds(jwin), (M1, jwin, swin)),
+        ("joint window after the state family left", lambda: w.clear_al_state_bounds(), (M1, jwin, None)),
+        ("both windows cut from a track", lambda: track(w), (M1, jcut, scut)),
+        ("removal and re-installation", lambda: (w.clear_augmented_lagrangian(), w.set_augmented_lagrangian(1, 1.0, 1.0, margin=M0)), (M0, None, None)),
+    ]
+    assert len(walk) == 14
+    for name, go, (margin, joint, state) in walk:
+        go()
+        got = measure(w, state is not None)
+        f = fresh(margin, joint, state); want = measure(f, state is not None); f.close()
+        assert len(got) == len(want) == 18
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert np.array_equal(a, b), (name, i)
+        assert got[2] == (0 if joint is None or joint.ndim < 3 else 1) | (0 if state is None or state.ndim < 3 else 2), name
+        if state is not None:
+            f = fresh(margin, joint, None); f.initialize(d["X"][:, 0], d["U"]); f.set_trajectory(d["X"], d["U"]); f.set_al_multipliers(d["mu_j"], d["mu_c"], d["rho"])
+            without = f.stage_total_cost(); f.close()
+            assert np.all(got[5] != without), (name, got[5], without)
+    w.close()
