@@ -286,6 +286,66 @@ int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* ctx, const int* start /*[n
    family's record over the knots.  step >= 0, else ILQR_ERR_ARG.  ILQR_ERR_STATE without an augmented Lagrangian, without a track, or with
    a state part while no state family is installed. */
 int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* ctx, int step);
+/* Augmented-Lagrangian bounds on POINTS of the robot, the task family: nine task coordinates k = 0..8 in the world frame -- the whole-body
+   centre of mass x, y, z (k = 0..2), the left ankle origin (k = 3..5) and the right ankle origin (k = 6..8): the points the cost tracks
+   softly (w_com, w_ee_pos).  "Keep the swing foot 3 cm above the floor", "land the foot inside this stone", "keep the centre of mass over
+   the support box".  The ankle origins are those of ilqr_hip_reference_kinematics.  The CoM is the one the w_com term tracks -- the URDF
+   link masses, because the term's gradient and Hessian are that point's -- which lies about 3 mm from the CoM of the MuJoCo model that
+   ilqr_hip_reference_kinematics returns; ilqr_hip_get_al_task_points reports the coordinates the bounds act on.
+   The bounds are always a WINDOW, [n_sets][N+1][ILQR_AL_TASK_BOUNDS = 18], row t = lo[9] then hi[9]; n_sets is 1 (every rollout reads the one
+   window) or the batch (rollout b reads window b).  A fourth family beside the hinges, the actuators and the box coordinates, rule for rule
+   the state family: the constraints p_k - hi and lo - p_k at the knots t = 0..N with the term phi per constraint; knot 0 carries the cost
+   term, keeps zero multipliers and is left out of the violation (x_0 is given), the terminal knot is included; one penalty rho_task per
+   rollout, starting at rho_task0 and capped at rho_max_factor rho_task0; after each inner solve mu <- max(0, mu + rho_task c) and viol_task =
+   the largest max(0, c) over coordinates, sides and knots 1..N, in metres.  A rollout is done only when every installed family is within
+   its tolerance (tol_task here); otherwise all penalties grow.  A done rollout is frozen as described above; ilqr_hip_al_update updates this
+   family too.  Every other AL getter keeps its shape and meaning.
+   STANCE KNOTS: a foot's three rows at a knot where the contact schedule (ilqr_hip_set_contact_schedule) has that foot in stance (flag 1)
+   behave as rows with both sides switched off, whatever the window holds: there the stance constraint or the velocity term holds the foot.
+   A constant "z >= z_min" on a foot therefore means swing clearance.
+   A lower bound may be -inf and an upper bound +inf: that side is switched off as in the other families (c = -inf, term -mu^2 / (2 rho),
+   zero gradient and curvature, multiplier driven to 0, violation 0).  The Hessian of the term is exact, second-order part included, as
+   the tracking terms' is.  The window acts on the COST only: dynamics, plant and score are untouched.  It works with or without the other
+   families' tables and windows; while it is installed the library repeats their records over the knots on the device, as it does when one
+   of them has a window.
+   ILQR_ERR_STATE while no augmented Lagrangian is installed (every handle call below).  ILQR_ERR_ARG: a null pointer, n_sets not 1 or the
+   batch, a NaN, lo > hi, lo == +inf, hi == -inf in any row, rho_task0 <= 0 or not finite, tol_task < 0; everything is checked before the
+   handle is touched, a refused call leaves a previously installed window as it was.  ILQR_ERR_UNSUPPORTED when libilqr_hip_alknot.so beside
+   the library, which holds every kernel of this family, cannot be loaded.  Allocates the third multiplier store on first use ([B] records
+   of 16 + 32 (N + 1) doubles: al_task_dev.h).  Installing where no window was installed zeroes the task multipliers; replacing a window
+   keeps them; rho_task = rho_task0 either way.  Uploads and synchronises the handle's stream.
+   The window is horizon-local: a warm start shifts the multipliers and does not move it.  It survives the cold and warm initialisers,
+   ilqr_hip_set_al_multipliers, the other families coming and going and a repeated ilqr_hip_set_augmented_lagrangian;
+   ilqr_hip_clear_augmented_lagrangian drops it.  The cold initialisers zero the task multipliers and reset rho_task; the warm ones shift
+   them by the knots the trajectory is shifted by (zero tail, knot 0 zero) and reset rho_task.  The refusals of
+   ilqr_hip_set_augmented_lagrangian (cross-check families, weight sets) stay as they are.  The bounds track does not cut this family. */
+#define ILQR_AL_TASK_COORDS 9
+#define ILQR_AL_TASK_BOUNDS 18
+int ilqr_hip_set_al_task_bounds(ilqr_hip_ctx* ctx, const double* bounds /*[n_sets][N+1][18]*/, int n_sets, double rho_task0, double tol_task);
+/* No task family any more (same kernels and kernel arguments as a handle that never had a window). */
+int ilqr_hip_clear_al_task_bounds(ilqr_hip_ctx* ctx);
+/* 0: no window installed, else the n_sets of the installed window (1 or the batch); -1 for a null handle */
+int ilqr_hip_num_al_task_bound_sets(const ilqr_hip_ctx* ctx);
+/* The window each rollout is solved with: a one-set window expanded; without a window lo = -inf, hi = +inf in every row.  (Rows of a foot
+   in stance are returned as installed; the kernels do not read them.)  Synchronises the handle's stream. */
+int ilqr_hip_get_al_task_bounds(ilqr_hip_ctx* ctx, double* bounds /*[B][N+1][18]*/);
+/* The task multipliers, (lower, upper) per task coordinate; zeros without a window. */
+int ilqr_hip_get_al_task_multipliers(ilqr_hip_ctx* ctx, double* mu /*[B][N+1][9][2]*/);
+/* Either pointer may be NULL (that part stays).  Multipliers >= 0, penalties > 0, else ILQR_ERR_ARG; knot-0 entries are stored as zero.
+   ILQR_ERR_STATE without a window. */
+int ilqr_hip_set_al_task_multipliers(ilqr_hip_ctx* ctx, const double* mu /*[B][N+1][9][2]*/, const double* rho /*[B]*/);
+/* rho_task as the store holds it; zeros without a window */
+int ilqr_hip_get_al_task_penalties(ilqr_hip_ctx* ctx, double* rho /*[B]*/);
+/* viol_task of the nominal trajectory at the last update; zeros without a window (the done flags: ilqr_hip_get_al_violation) */
+int ilqr_hip_get_al_task_violation(ilqr_hip_ctx* ctx, double* viol /*[B]*/);
+/* Per round of the last solve and rollout: viol_task and the rho_task the round ran with.  NaN where ilqr_hip_get_al_trace has NaN, and
+   everywhere without a window. */
+int ilqr_hip_get_al_task_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][2]*/);
+/* The nine task coordinates of every knot of the resident nominal trajectory, as the kernels of this family compute them (each coordinate
+   is the same double in the cost, the quadratics and the update): what a user plots against the window.  Needs an installed augmented
+   Lagrangian (ILQR_ERR_STATE) and an initialised trajectory (ILQR_ERR_STATE), not a task window; ILQR_ERR_UNSUPPORTED without the module.
+   Synchronises the handle's stream. */
+int ilqr_hip_get_al_task_points(ilqr_hip_ctx* ctx, double* out /*[B][N+1][9]*/);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N

@@ -8,13 +8,18 @@
 //                      all three families, the growth of rho_state and the state trace row
 //                      <., ., true>: the bounds of knot t are row t of the rollout's windows (ilqr_hip_set_al_knot_bounds ...); instantiated
 //                      in libilqr_hip_alknot.so only (al_knot_kernels.hip includes this file with -DAL_KNOT_MODULE: the kernel alone)
+//                      <., ., true, true>: and the task family (ilqr_hip_set_al_task_bounds: the third store, AlDev::tstore) -- a fourth loop on
+//                      the points of the nominal trajectory (al_task_dev.h), one lane per knot, a fourth maximum, the done rule over all four
+//                      families, the growth of rho_task and the task trace row; per-knot instantiations only, in the module
 //   k_al_shift         warm-start shift of the multipliers by the knots the trajectory is shifted by (zero tail; shift > N: all zero), penalties reset
 //   k_al_state_shift   the same for the state family's store: every column shifts as a hinge column does (knot 0 stays zero)
+//   k_al_task_shift    the same for the task family's store; k_al_task_points: the nine task coordinates of the nominal trajectories (module only)
 //   k_solve_begin_al   k_solve_begin with active = !done: the prologue of the rounds >= 2 of a solve with the convergence exit
 // Every rule is per rollout: nothing here reads another rollout's data, and the one shared word (AlDev::left) is a count.
 // Compiled as the tail of ilqr_kernels.hip, beside k_solve_begin and k_warm_shift (a code object of their own for three small kernels cost
 // each library ~25 KB of headers and metadata).
 #pragma once
+#include "al_task_dev.h"
 #include "h1_cost_dev.h"
 #include "ilqr_kernels.h"
 
@@ -29,7 +34,8 @@ __device__ __forceinline__ double wave_max(double v) {
 // Constraint e of a knot's record, e in [0, 38): side = e / 19 (0 lower, 1 upper bound), coordinate e % 19.  The multiplier sits at
 // base + e for both families (AL_JHI = AL_JLO + 19, AL_UHI = AL_ULO + 19).
 // KNOT: the bounds of knot t are row t of the rollout's windows (AlDev::bounds_knot, sbounds_knot); instantiated in the per-knot module only
-template <bool TABLE, bool STATE, bool KNOT = false>
+// TASK: the task family's window (AlDev::tbounds) on top of the per-knot instantiations
+template <bool TABLE, bool STATE, bool KNOT = false, bool TASK = false>
 __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round, int masked) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -92,25 +98,80 @@ __global__ void __launch_bounds__(64) k_al_update(DevState S, AlDev A, int round
       }
     }
   }
+  // task coordinates (TASK), knots 1..N as the hinges, lane = knot: the nine points of the knot's state once, then its 18 sides; a foot's rows
+  // are off where the schedule has it in stance (c = -inf: the multiplier goes to 0, no violation)
+  double vt = 0.0, rho_t = 0.0;
+  double* trec = nullptr;
+  if constexpr (TASK) {
+    trec = A.tstore + (long)b * A.tstride;
+    rho_t = trec[ALT_RHO];
+    const double* tb = A.tbounds + (long)b * A.tbounds_stride;
+    const int* stn = A.stance + b * A.stance_stride;
+    for (int t = 1 + lane; t <= N; t += 64) {
+      double p[ALT_COORDS]; al_task_points(xb + t * H1_NX, p);
+      const double* tk = tb + (long)t * A.tbounds_knot;
+      const int stf[2] = {stn[2 * t], stn[2 * t + 1]};
+      double* mu = trec + ALT_HDR + (long)t * ALT_KNOT;
+#pragma unroll
+      for (int i = 0; i < ALT_COORDS; ++i) {
+        const bool off = al_task_row_off(i, stf);
+        const double lo = off ? -__builtin_inf() : tk[ALTB_LO + i], hi = off ? __builtin_inf() : tk[ALTB_HI + i];
+        const double ch = p[i] - hi, cl = lo - p[i];
+        vt = ch > vt ? ch : vt; vt = cl > vt ? cl : vt;
+        if (!was_done) {
+          const double sh = al_task_side(ch, mu[ALT_HI + i], rho_t), sl = al_task_side(cl, mu[ALT_LO + i], rho_t);
+          mu[ALT_HI + i] = sh > 0.0 ? sh : 0.0; mu[ALT_LO + i] = sl > 0.0 ? sl : 0.0;
+        }
+      }
+    }
+  }
   vj = wave_max(vj); vc = wave_max(vc);
   if constexpr (STATE) vs = wave_max(vs);
+  if constexpr (TASK) vt = wave_max(vt);
   if (lane != 0) return;
   A.viol[2 * b] = vj; A.viol[2 * b + 1] = vc;
   if constexpr (STATE) A.sviol[b] = vs;
+  if constexpr (TASK) A.tviol[b] = vt;
   if (was_done && masked) return;          // (the round did not run for this rollout: its trace row stays NaN)
   double* tr = A.trace + ((size_t)round * S.B + b) * 5;
   tr[0] = vj; tr[1] = vc; tr[2] = rho_j; tr[3] = rho_c; tr[4] = (double)iters;
   if constexpr (STATE) { double* ts = A.strace + ((size_t)round * S.B + b) * 2; ts[0] = vs; ts[1] = rho_s; }
+  if constexpr (TASK) { double* tt = A.ttrace + ((size_t)round * S.B + b) * 2; tt[0] = vt; tt[1] = rho_t; }
   if (was_done) return;
-  if (vj <= A.tol_joint && vc <= A.tol_ctrl && (!STATE || vs <= A.tol_state)) { A.done[b] = 1; return; }
+  if (vj <= A.tol_joint && vc <= A.tol_ctrl && (!STATE || vs <= A.tol_state) && (!TASK || vt <= A.tol_task)) { A.done[b] = 1; return; }
   const double gj = rho_j * A.growth, gc = rho_c * A.growth;
   rec[AL_RHO_JOINT] = gj < A.rho_joint_max ? gj : A.rho_joint_max;
   rec[AL_RHO_CTRL] = gc < A.rho_ctrl_max ? gc : A.rho_ctrl_max;
   if constexpr (STATE) { const double gs = rho_s * A.growth; srec[ALS_RHO] = gs < A.rho_state_max ? gs : A.rho_state_max; }
+  if constexpr (TASK) { const double gt = rho_t * A.growth; trec[ALT_RHO] = gt < A.rho_task_max ? gt : A.rho_task_max; }
   atomicAdd(A.left + round, 1);
 }
 
-#ifndef AL_KNOT_MODULE
+#ifdef AL_KNOT_MODULE
+// The task family's store under the walk of k_al_state_shift (below, in the library): every column is one side of a task coordinate at the
+// knots 0..N, kept for 1 <= t and t + shift <= N; rho_task back to rho_task0.  The window of bounds is horizon-local and does not move.
+__global__ void __launch_bounds__(64) k_al_task_shift(AlDev A, int N, int shift) {
+  const int b = blockIdx.x, e = threadIdx.x;
+  double* rec = A.tstore + (long)b * A.tstride;
+  if (e == 0) { rec[ALT_RHO] = A.rho_task0; A.tviol[b] = 0.0; }
+  if (e >= 2 * ALT_COORDS) return;
+  double* k = rec + ALT_HDR + ALT_LO;
+  for (int t = 0; t <= N; ++t) {
+    const long ts = (long)t + shift;
+    const bool keep = t >= 1 && ts <= N;
+    const double v = k[(ts <= N ? ts : (long)N) * ALT_KNOT + e];      // (index clamped into the record, masked below)
+    k[(long)t * ALT_KNOT + e] = keep ? v : 0.0;
+  }
+}
+// the nine task coordinates of every knot of the nominal trajectories as the cost kernels and the update form them: one lane per (rollout, knot)
+__global__ void __launch_bounds__(64) k_al_task_points(DevState S, double* out) {
+  const long idx = (long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= (long)S.B * (S.N + 1)) return;
+  double p[ALT_COORDS]; al_task_points(S.xbar + idx * H1_NX, p);
+#pragma unroll
+  for (int i = 0; i < ALT_COORDS; ++i) out[idx * ALT_COORDS + i] = p[i];
+}
+#else
 // Each lane owns one column of the knot records and walks the knots upwards: it reads knot t + shift after it has written every knot < t, so
 // the shift is in place without a barrier.
 __global__ void __launch_bounds__(128) k_al_shift(AlDev A, int N, int shift, double rho_joint, double rho_ctrl) {
@@ -186,6 +247,7 @@ void launch_al_update(const DevState& S, const AlDev& A, int round, int masked, 
 void launch_al_shift(const AlDev& A, int B, int N, int shift, double rho_joint, double rho_ctrl, hipStream_t st) {
   hipLaunchKernelGGL(k_al_shift, dim3(B), dim3(128), 0, st, A, N, shift, rho_joint, rho_ctrl);
   if (A.sbounds) hipLaunchKernelGGL(k_al_state_shift, dim3(B), dim3(64), 0, st, A, N, shift);
+  if (A.tbounds) g_al_knot.task_shift(&A, B, N, shift, st);      // (the task family's kernels: the module's)
 }
 void launch_solve_begin_al(const DevState& S, const int* done, hipStream_t st) { hipLaunchKernelGGL(k_solve_begin_al, dim3(1), dim3(64), 0, st, S, done); }
 #endif      // AL_KNOT_MODULE

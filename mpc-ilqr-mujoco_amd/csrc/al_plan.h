@@ -8,7 +8,8 @@
 // ONE record of those same doubles (h1host::al_default_bounds): the state instantiations take every bound from a record, there is no
 // AL_MODEL_STATE.  The state family reads its table.  A window of either family installed: both families read windows, a family that has none
 // gets its record (the table's, or the model's) repeated over the knots, so that two per-knot instantiations serve every combination; those
-// live in the per-knot module (ilqr_kernels.h AlKnotModule).  One set serves every rollout through a set stride of 0.
+// live in the per-knot module (ilqr_kernels.h AlKnotModule).  One set serves every rollout through a set stride of 0.  A window of the task
+// family (the last function below) counts as a window installed.
 #pragma once
 
 namespace h1 {
@@ -50,11 +51,12 @@ constexpr int al_variant(bool al, bool alb, bool alsb, bool alb_knot) {
   return !al ? h1::AL_OFF : (alb && alb_knot) ? (alsb ? h1::AL_KNOT_TABLE_STATE : h1::AL_KNOT_TABLE) : (alb && alsb) ? h1::AL_TABLE_STATE : alb ? h1::AL_TABLE : h1::AL_MODEL;
 }
 
-inline AlPlan resolve_al_plan(bool on, AlInstalled jc, AlInstalled st) {
+// other_window: a family that is not one of the two has a window installed (the task family, below)
+inline AlPlan resolve_al_plan_beside(bool on, AlInstalled jc, AlInstalled st, bool other_window) {
   AlPlan p{};
   p.jc.shared = p.st.shared = true;      // (a family without a pointer has no stride)
   if (!on) return p;        // (AL_OFF, AL_SRC_NONE and no work are the zeros)
-  const bool state = st.sets > 0, knot = (jc.sets > 0 && jc.window) || (state && st.window);
+  const bool state = st.sets > 0, knot = (jc.sets > 0 && jc.window) || (state && st.window) || other_window;
   p.module = knot;
   p.jc.source = (jc.sets > 0 && jc.window) ? AL_SRC_WINDOW : jc.sets > 0 ? (knot ? AL_SRC_TABLE_EXPANDED : AL_SRC_TABLE)
               : knot ? AL_SRC_MODEL_EXPANDED : state ? AL_SRC_MODEL_RECORD : AL_SRC_MODEL_RANGES;
@@ -65,6 +67,23 @@ inline AlPlan resolve_al_plan(bool on, AlInstalled jc, AlInstalled st) {
   p.expand_jc = p.jc.source == AL_SRC_TABLE_EXPANDED || p.jc.source == AL_SRC_MODEL_EXPANDED;
   p.expand_st = p.st.source == AL_SRC_TABLE_EXPANDED;
   p.variant = al_variant(true, p.jc.source != AL_SRC_MODEL_RANGES, state, knot);
+  return p;
+}
+inline AlPlan resolve_al_plan(bool on, AlInstalled jc, AlInstalled st) { return resolve_al_plan_beside(on, jc, st, false); }
+
+// The task family (ilqr_hip_set_al_task_bounds: bounds on the CoM and the ankle origins, al_task_dev.h) on top.  Its bounds are always a window,
+// so installing it counts as "a window is installed": the other two families then read windows through the expansions above and the per-knot
+// module is called into.  An axis of its own, orthogonal to the variant: `task` selects the task instantiations of the two per-knot variants
+// (the launchers read it off ProblemDev::altb / AlDev::tbounds).  Without a task window the base is resolve_al_plan(on, jc, st) field for field.
+struct AlTaskPlan {
+  AlPlan base;
+  AlFamilyPlan tk;          // source AL_SRC_WINDOW or AL_SRC_NONE
+  bool task;
+};
+inline AlTaskPlan resolve_al_plan(bool on, AlInstalled jc, AlInstalled st, AlInstalled tk) {
+  const bool task = on && tk.sets > 0;
+  AlTaskPlan p{resolve_al_plan_beside(on, jc, st, task), {AL_SRC_NONE, true, false}, task};
+  if (task) p.tk = {AL_SRC_WINDOW, tk.sets == 1, true};
   return p;
 }
 

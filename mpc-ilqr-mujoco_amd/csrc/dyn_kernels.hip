@@ -11,6 +11,9 @@
 #define ABA_FENCE          // scheduling fences between the sweeps of the articulated-body algorithm (h1_aba_reg.h): k_lin_primal_r spills 532 instead of 1152 B
 #include "h1_aba_reg.h"
 #include "ilqr_kernels.h"
+#ifdef AL_KNOT_MODULE
+#include "al_task_dev.h"      // (the task family's knot cost: in the per-knot module only)
+#endif
 
 using namespace h1;
 
@@ -304,6 +307,20 @@ __global__ void __launch_bounds__(64) k_al_state_knot_cost(DevState S, ProblemDe
   S.cand_knot[((cand << oshift) * (N + 1)) + t] += al_state_term<KNOT>(P, b, t, xsrc + idx * H1_NX);
 }
 #ifdef AL_KNOT_MODULE
+// The task family's terms of the same knots (al_task_dev.h al_task_term: the CoM and the two ankle origins of the lane's state against row t of
+// its rollout's window), added the same way behind the state family's: c + term, one rounding.  In the module only.
+__global__ void __launch_bounds__(64) k_al_task_knot_cost(DevState S, ProblemDev P, int mode, const double* xsrc, int cshift, int oshift, const int* gate) {
+  if (gate && *gate == 0) return;
+  const int N = S.N;
+  const long total = ((long)S.B << cshift) * (N + 1);
+  const long idx = (long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= total) return;
+  const int t = (int)(idx % (N + 1));
+  const long cand = idx / (N + 1);
+  const int b = (int)(cand >> cshift);
+  if (!sel(S, b, mode)) return;
+  S.cand_knot[((cand << oshift) * (N + 1)) + t] += al_task_term(P, b, t, xsrc + idx * H1_NX);
+}
 }  // namespace ilqr
 // the module's entry points (ilqr_kernels.h AlKnotModule): the launches launch_cand_costs / launch_nominal_costs make, on the per-knot instantiations
 extern "C" void ilqr_alknot_module_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate, hipStream_t st) {
@@ -313,6 +330,10 @@ extern "C" void ilqr_alknot_module_knot_cost(const ilqr::DevState* S, const h1::
 extern "C" void ilqr_alknot_module_state_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st) {
   const long total = ((long)S->B << cshift) * (S->N + 1);
   hipLaunchKernelGGL(ilqr::k_al_state_knot_cost<true>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, *S, *P, mode, xsrc, cshift, oshift, gate);
+}
+extern "C" void ilqr_alknot_module_task_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st) {
+  const long total = ((long)S->B << cshift) * (S->N + 1);
+  hipLaunchKernelGGL(ilqr::k_al_task_knot_cost, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, *S, *P, mode, xsrc, cshift, oshift, gate);
 }
 #else
 __global__ void __launch_bounds__(64) k_traj_cost_sum(DevState S, int mode, int cshift, int oshift, double* cost_out) {
@@ -339,6 +360,7 @@ static void launch_knot_costs(const DevState& S, const ProblemDev& P, int mode, 
   }
   if (variant == AL_KNOT_TABLE_STATE) g_al_knot.state_knot_cost(&S, &P, mode, xsrc, cshift, oshift, gate, st);
   else if (variant == AL_TABLE_STATE) hipLaunchKernelGGL(k_al_state_knot_cost<false>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, S, P, mode, xsrc, cshift, oshift, gate);
+  if (P.altb) g_al_knot.task_knot_cost(&S, &P, mode, xsrc, cshift, oshift, gate, st);      // (the task family: behind the state term, ahead of the sum)
 }
 void launch_cand_costs(const DevState& S, const ProblemDev& P, int mode, hipStream_t st, bool with_sum, const int* gate) {
   launch_knot_costs(S, P, mode, S.xcand, S.ucand, 3, 0, gate, st);

@@ -59,6 +59,12 @@ struct ProblemDev {
   // doubles behind knot 0's (ALB_STRIDE / ALSB_STRIDE) and alb_stride / alsb_stride the doubles of one set's window (0: one window for all).
   // Both are set or both are 0 while a state family is installed (al_plan.h).  Appended: nothing above moves
   long alb_knot, alsb_knot;
+  // augmented-Lagrangian bounds on the CoM and the two ankle origins, the task family (ilqr_hip_set_al_task_bounds; al_task_dev.h states the
+  // layouts): altb null = none; else alt the third multiplier store, one record of alt_stride doubles per rollout, and altb a window of bounds,
+  // [N+1] rows per set altb_knot doubles apart, altb_stride the doubles of one set's window (0: one window for all).  While it is installed the
+  // other families read windows too (al_plan.h).  Read while `al` is installed only.  Appended: nothing above moves
+  const double* alt;         long alt_stride;
+  const double* altb;        long altb_stride, altb_knot;
 };
 // The multiplier store, in doubles.  Rollout b's record: one 128-byte line of scalars (AL_RHO_JOINT, AL_RHO_CTRL, the rest padding), then one
 // record of AL_KNOT = 80 doubles (five whole lines) per knot t = 0..N: the hinges' multipliers of the lower bounds, of the upper bounds, two

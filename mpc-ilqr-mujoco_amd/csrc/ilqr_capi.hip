@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/ilqr_hip.h"
+#include "al_task_dev.h"
 #include "h1_cost_dev.h"
 #include "h1_host_model.h"
 #include "ilqr_kernels.h"
@@ -99,7 +100,7 @@ struct ilqr_hip_ctx {
   // Augmented Lagrangian (ilqr_hip_set_augmented_lagrangian): installed while P.al points at al.jc.store; every buffer is kept by the handle once
   // allocated and freed by ilqr_hip_destroy.  Which pointers ProblemDev / AlDev get from all this: al_point_bounds, by the plan of al_plan.h.
   // One record per family of bounds -- jc the hinges and actuators (ilqr_hip_set_al_bounds ...), st the 28 box coordinates
-  // (ilqr_hip_set_al_state_bounds ...) -- which the bodies behind the two families' entry points take as their parameter:
+  // (ilqr_hip_set_al_state_bounds ...), tk the nine task coordinates (ilqr_hip_set_al_task_bounds: a window always, no table, no track) -- which the bodies behind the two families' entry points take as their parameter:
   struct AlFamily {
     int fields, width;        // doubles of a bounds record in the interface (76 / 56) and on the device (ALB_STRIDE / ALSB_STRIDE)
     int blocks, per;          // a bounds record is `blocks` blocks of lo[per], hi[per] (2 x 19 / 1 x 28); so is a knot's multiplier record:
@@ -112,14 +113,16 @@ struct ilqr_hip_ctx {
   };
   struct Al {
     int rounds = 0, trace_cap = 0, round = 0, rounds_run = 0;      // round: the one enqueue_solve is enqueuing; rounds_run: rounds the last solve enqueued
-    double rho0[2] = {0, 0}, growth = 1.0, max_factor = 1.0, tol[2] = {0, 0}, srho0 = 0.0, stol = 0.0;
+    double rho0[2] = {0, 0}, growth = 1.0, max_factor = 1.0, tol[2] = {0, 0}, srho0 = 0.0, stol = 0.0, trho0 = 0.0, ttol = 0.0;
     // viol [B][2], done [B], trace [trace_cap][B][5], left [trace_cap] rollouts not done after each round and its pinned copy h_left (the host's
     // read between two rounds, as the early-exit gate reads its counts); sviol [B], strace [trace_cap][B][2] the state family's
-    double *viol = nullptr, *trace = nullptr, *sviol = nullptr, *strace = nullptr;
+    // tviol [B], ttrace [trace_cap][B][2] the task family's; tpoints [B][N+1][9] the getter's buffer (ilqr_hip_get_al_task_points, allocated by its first call)
+    double *viol = nullptr, *trace = nullptr, *sviol = nullptr, *strace = nullptr, *tviol = nullptr, *ttrace = nullptr, *tpoints = nullptr;
     int *done = nullptr, *left = nullptr, *h_left = nullptr;
     hipEvent_t ev = nullptr;
     AlFamily jc{ILQR_AL_BOUNDS, h1::ALB_STRIDE, 2, 19, h1::AL_KNOT, {h1::AL_JLO, h1::AL_ULO}};
     AlFamily st{ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE, 1, ILQR_AL_STATE_COORDS, h1::ALS_KNOT, {h1::ALS_LO, 0}};
+    AlFamily tk{ILQR_AL_TASK_BOUNDS, h1::ALTB_STRIDE, 1, ILQR_AL_TASK_COORDS, h1::ALT_KNOT, {h1::ALT_LO, 0}};
     double* model = nullptr;  // [ALB_STRIDE] the model's bounds at the installed margin as one record (AlPlan::upload_model)
     // the bounds track (ilqr_hip_set_al_bounds_track; the families' `track`): its start rows [B] on the device, allocated with the first track
     int* track_start = nullptr;
@@ -382,7 +385,7 @@ __attribute__((noinline, minsize)) static int upload_rows(ilqr_hip_ctx* c, doubl
 }
 // The per-knot instantiations of the cost kernels and of k_al_update live in libilqr_hip_alknot.so (ilqr_kernels.h AlKnotModule), opened by the
 // first call that may install a window.  Missing module or entry point: ILQR_ERR_UNSUPPORTED.
-namespace ilqr { AlKnotModule g_al_knot = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; }
+namespace ilqr { AlKnotModule g_al_knot = {}; }
 using AlFamily = ilqr_hip_ctx::AlFamily;
 // the module and the two window buffers: what every call that may install a window needs, before it touches the handle's state
 __attribute__((noinline, minsize)) static int al_knot_ready(ilqr_hip_ctx* c) {
@@ -390,14 +393,15 @@ __attribute__((noinline, minsize)) static int al_knot_ready(ilqr_hip_ctx* c) {
   // one exported symbol: the table of the module's entry points (al_knot_kernels.hip)
   const auto resolve = [](void* so, int) { const auto table = (const ilqr::AlKnotModule* (*)())dlsym(so, "ilqr_alknot_module"); if (table) ilqr::g_al_knot = *table(); return table != nullptr; };
   if (!open_module(lib, "alknot", "per-knot bounds", resolve, 0)) { c->err = lib.why; return ILQR_ERR_UNSUPPORTED; }
-  for (AlFamily* f : {&c->al.jc, &c->al.st}) if (!f->window) TRY(dalloc(c, &f->window, (size_t)c->B * (c->N + 1) * f->width));
+  for (AlFamily* f : {&c->al.jc, &c->al.st, &c->al.tk}) if (!f->window) TRY(dalloc(c, &f->window, (size_t)c->B * (c->N + 1) * f->width));
   return ILQR_OK;
 }
 // Points ProblemDev at the bounds: resolves the plan of what is installed (al_plan.h states the rules), does the work it names -- the model's
 // record, the expansions (k_al_bounds_expand, device to device; a plan that names one has the module loaded) -- and writes each family's
 // pointer and strides as the plan names them.
 __attribute__((noinline, minsize)) static int al_point_bounds(ilqr_hip_ctx* c) {
-  const ilqr::AlPlan plan = ilqr::resolve_al_plan(c->P.al != nullptr, {c->al.jc.sets, c->al.jc.knot}, {c->al.st.sets, c->al.st.knot});
+  const ilqr::AlTaskPlan tplan = ilqr::resolve_al_plan(c->P.al != nullptr, {c->al.jc.sets, c->al.jc.knot}, {c->al.st.sets, c->al.st.knot}, {c->al.tk.sets, true});
+  const ilqr::AlPlan& plan = tplan.base;
   if (plan.upload_model) {
     double rec[h1::ALB_STRIDE] = {0};
     h1host::al_default_bounds(c->P.al_margin, rec);
@@ -413,10 +417,11 @@ __attribute__((noinline, minsize)) static int al_point_bounds(ilqr_hip_ctx* c) {
   };
   point(c->al.jc, plan.jc, plan.expand_jc, c->P.alb, c->P.alb_stride, c->P.alb_knot);
   point(c->al.st, plan.st, plan.expand_st, c->P.alsb, c->P.alsb_stride, c->P.alsb_knot);
+  point(c->al.tk, tplan.tk, false, c->P.altb, c->P.altb_stride, c->P.altb_knot);
   if (plan.module) HIPCHK(c, hipGetLastError());
   return ILQR_OK;
 }
-static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
+__attribute__((noinline, minsize)) static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   ilqr::AlDev A{};
   A.store = c->al.jc.store; A.stride = h1::al_record_doubles(c->N);
   A.margin = c->P.al_margin; A.growth = c->al.growth; A.tol_joint = c->al.tol[0]; A.tol_ctrl = c->al.tol[1];
@@ -428,6 +433,11 @@ static ilqr::AlDev al_view(const ilqr_hip_ctx* c) {
   A.rho_state0 = c->al.srho0; A.rho_state_max = c->al.srho0 * c->al.max_factor; A.tol_state = c->al.stol;
   A.sviol = c->al.sviol; A.strace = c->al.strace;
   A.bounds_knot = c->P.alb_knot; A.sbounds_knot = c->P.alsb_knot;
+  A.tbounds = c->P.altb; A.tbounds_stride = c->P.altb_stride; A.tbounds_knot = c->P.altb_knot;
+  A.tstore = c->al.tk.store; A.tstride = h1::alt_record_doubles(c->N);
+  A.rho_task0 = c->al.trho0; A.rho_task_max = c->al.trho0 * c->al.max_factor; A.tol_task = c->al.ttol;
+  A.tviol = c->al.tviol; A.ttrace = c->al.ttrace;
+  A.stance = c->P.stance; A.stance_stride = c->P.stance_stride;
   return A;
 }
 // the multipliers follow the trajectory: shifted by the knots it is shifted by (shift > N: a cold start, all zero), penalties back to their
@@ -548,6 +558,7 @@ __attribute__((minsize)) int ilqr_hip_create(ilqr_hip_ctx** out, int device, int
   P.wsets = nullptr; P.wsets_stride = 0;
   P.al = nullptr; P.al_stride = 0; P.al_margin = 0.0; P.alb = nullptr; P.alb_stride = 0;
   P.als = nullptr; P.als_stride = 0; P.alsb = nullptr; P.alsb_stride = 0; P.alb_knot = 0; P.alsb_knot = 0;
+  P.alt = nullptr; P.alt_stride = 0; P.altb = nullptr; P.altb_stride = 0; P.altb_knot = 0;
   // default: stance everywhere (RobotUtils::isStance default, robot_utils.cpp:494-504), lambda = 1e-6 (ilqr.cpp:16)
   std::vector<int> ones((N + 1) * 2, 1);
   hipMemcpyAsync(c->d_stance, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
@@ -571,9 +582,9 @@ __attribute__((minsize)) int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   DevState& S = c->S;
   void* ptrs[] = {S.cand_knot, S.lin_dump, S.quad_rec, S.x0, S.xbar, S.ubar, S.xcand, S.ucand, S.cand_cost, S.A, S.Bm, S.lx, S.lu, S.lxx, S.luu, S.K, S.kff, S.Vx, S.Vxx, S.J, S.Jbase, S.ls_cost,
                   S.lambda, S.active, S.need_retry, S.iters, S.improved, S.alpha_idx, S.trace_cost, S.trace_alpha, S.trace_lambda, S.order, S.order_n, c->d_tmpx, c->d_tmpu,
-                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->al.viol, c->al.trace, c->al.done, c->al.left, c->al.sviol, c->al.strace, c->al.model, c->al.track_start};
+                  c->d_prevx, c->d_prevu, c->d_shadowx, c->d_u0, c->d_K0, c->d_cost_tmp, c->d_stepx, c->d_stepu, c->d_stepn, c->d_mismatch, c->d_payload, c->d_xref, c->d_uref, c->d_comref, c->d_eeref, c->d_comvelref, c->d_stance, c->d_stance_dyn, c->d_stance_out, c->d_wsets, c->al.viol, c->al.trace, c->al.done, c->al.left, c->al.sviol, c->al.strace, c->al.model, c->al.track_start, c->al.tviol, c->al.ttrace, c->al.tpoints};
   for (void* p : ptrs) if (p) hipFree(p);
-  for (const AlFamily* f : {&c->al.jc, &c->al.st}) for (void* p : {(void*)f->store, (void*)f->table, (void*)f->window, (void*)f->track}) if (p) hipFree(p);
+  for (const AlFamily* f : {&c->al.jc, &c->al.st, &c->al.tk}) for (void* p : {(void*)f->store, (void*)f->table, (void*)f->window, (void*)f->track}) if (p) hipFree(p);
   if (c->al.h_left) (void)hipHostFree(c->al.h_left);
   if (c->al.ev) hipEventDestroy(c->al.ev);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
@@ -648,7 +659,7 @@ int ilqr_hip_clear_weight_sets(ilqr_hip_ctx* c) {
 int ilqr_hip_num_weight_sets(const ilqr_hip_ctx* c) { return c ? c->n_wsets : -1; }
 
 // ---------------------------------------------------------------- augmented-Lagrangian joint and torque limits
-int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_joint0, double rho_ctrl0, double growth, double rho_max_factor, double margin,
+__attribute__((minsize)) int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_joint0, double rho_ctrl0, double growth, double rho_max_factor, double margin,
                                       double tol_joint, double tol_ctrl) {
   if (!c || rounds < 1 || !(rho_joint0 > 0.0) || !(rho_ctrl0 > 0.0) || !(growth >= 1.0) || !(rho_max_factor >= 1.0) || !(margin >= 0.0) || !(margin < 0.5) ||
       !(tol_joint >= 0.0) || !(tol_ctrl >= 0.0) || !std::isfinite(rho_joint0) || !std::isfinite(rho_ctrl0) || !std::isfinite(growth) || !std::isfinite(rho_max_factor)) return ILQR_ERR_ARG;
@@ -658,6 +669,7 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
   const size_t B = c->B;
   if (!c->al.jc.store) { TRY(dalloc(c, &c->al.jc.store, B * (size_t)h1::al_record_doubles(c->N))); TRY(dalloc(c, &c->al.viol, B * 2)); TRY(dalloc(c, &c->al.done, B)); }
   if (!c->al.sviol) TRY(dalloc(c, &c->al.sviol, B));
+  if (!c->al.tviol) TRY(dalloc(c, &c->al.tviol, B));
   if (!c->al.ev) HIPCHK_S(c, hipEventCreateWithFlags(&c->al.ev, hipEventDisableTiming));
   if (rounds > c->al.trace_cap) {
     HIPCHK_S(c, hipStreamSynchronize(c->stream));
@@ -665,8 +677,10 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
     if (c->al.left) (void)hipFree(c->al.left);
     if (c->al.h_left) (void)hipHostFree(c->al.h_left);
     if (c->al.strace) (void)hipFree(c->al.strace);
-    c->al.trace = nullptr; c->al.left = nullptr; c->al.h_left = nullptr; c->al.strace = nullptr; c->al.trace_cap = 0;
+    if (c->al.ttrace) (void)hipFree(c->al.ttrace);
+    c->al.trace = nullptr; c->al.left = nullptr; c->al.h_left = nullptr; c->al.strace = nullptr; c->al.ttrace = nullptr; c->al.trace_cap = 0;
     TRY(dalloc(c, &c->al.trace, (size_t)rounds * B * 5)); TRY(dalloc(c, &c->al.left, (size_t)rounds)); TRY(dalloc(c, &c->al.strace, (size_t)rounds * B * 2));
+    TRY(dalloc(c, &c->al.ttrace, (size_t)rounds * B * 2));
     HIPCHK_S(c, hipHostMalloc((void**)&c->al.h_left, sizeof(int) * (size_t)rounds, hipHostMallocDefault));
     c->al.trace_cap = rounds;
   }
@@ -676,17 +690,18 @@ int ilqr_hip_set_augmented_lagrangian(ilqr_hip_ctx* c, int rounds, double rho_jo
   TRY(al_point_bounds(c));      // (a state table without a bounds table: the model's record at the new margin)
   HIPCHK_S(c, hipMemsetAsync(c->al.trace, 0xFF, (size_t)rounds * B * 5 * sizeof(double), c->stream));      // (all bits set: NaN)
   HIPCHK_S(c, hipMemsetAsync(c->al.strace, 0xFF, (size_t)rounds * B * 2 * sizeof(double), c->stream));
+  HIPCHK_S(c, hipMemsetAsync(c->al.ttrace, 0xFF, (size_t)rounds * B * 2 * sizeof(double), c->stream));
   al_follow_initialize(c, c->N + 1);
   HIPCHK_S(c, hipGetLastError());
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
-int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
+__attribute__((minsize)) int ilqr_hip_clear_augmented_lagrangian(ilqr_hip_ctx* c) {
   if (!c) return ILQR_ERR_ARG;
   c->P.al = nullptr; c->P.al_stride = 0; c->P.al_margin = 0.0; c->al.rounds = 0; c->al.rounds_run = 0;      // (the buffers stay with the handle for the next call)
-  c->P.als = nullptr; c->P.als_stride = 0;
-  // the tables and windows of both families go with it: a fresh installation starts on the model's ranges (the bounds track stays with the handle)
-  for (AlFamily* f : {&c->al.jc, &c->al.st}) { f->sets = 0; f->knot = false; }
+  c->P.als = nullptr; c->P.als_stride = 0; c->P.alt = nullptr; c->P.alt_stride = 0;
+  // the tables and windows of every family go with it: a fresh installation starts on the model's ranges (the bounds track stays with the handle)
+  for (AlFamily* f : {&c->al.jc, &c->al.st, &c->al.tk}) { f->sets = 0; f->knot = false; }
   return al_point_bounds(c);      // (nothing installed: null pointers, no work)
 }
 int ilqr_hip_augmented_lagrangian_rounds(const ilqr_hip_ctx* c) { return c ? (c->P.al ? c->al.rounds : 0) : -1; }
@@ -713,7 +728,7 @@ int ilqr_hip_al_state_slot(int k) { return (k >= 0 && k < ILQR_AL_STATE_COORDS) 
 // the old getters' refusal while their family's bounds are a window
 static const char* const AL_WINDOW_ERR = "per-knot bounds: ilqr_hip_get_al_knot_bounds";
 // the family exists: the joint / torque family with the installation, the state family with its bounds
-static bool al_family_absent(const ilqr_hip_ctx* c, const AlFamily& f) { return &f == &c->al.st && !f.sets; }
+static bool al_family_absent(const ilqr_hip_ctx* c, const AlFamily& f) { return &f != &c->al.jc && !f.sets; }
 // every pair of n records: no NaN, lo <= hi, lo < +inf, hi > -inf (lo = -inf / hi = +inf switch that side off)
 __attribute__((noinline, minsize)) static bool al_bounds_ok(const AlFamily& f, const double* v, size_t n) {
   for (size_t r = 0; r < n; ++r)
@@ -730,10 +745,10 @@ __attribute__((noinline)) static void al_no_bounds(const ilqr_hip_ctx* c, const 
   else for (int i = 0; i < f.fields; ++i) rec[i] = i < f.per ? -HUGE_VAL : HUGE_VAL;
 }
 static size_t al_store_doubles(const ilqr_hip_ctx* c, const AlFamily& f) { return h1::AL_HDR + (size_t)f.knot_rec * (c->N + 1); }
-// the state family's multiplier store, for a table or a window of bounds: zero where none was installed; bounds that replace others keep the
-// multipliers.  rho_state starts at rho_state0 either way
-__attribute__((noinline, minsize)) static int al_state_store_install(ilqr_hip_ctx* c, double rho_state0, double tol_state) {
-  AlFamily& f = c->al.st;
+// the state (or the task) family's multiplier store, for a table or a window of bounds: zero where none was installed; bounds that replace
+// others keep the multipliers.  rho_state (rho_task) starts at rho_state0 (rho_task0) either way
+__attribute__((noinline, minsize)) static int al_state_store_install(ilqr_hip_ctx* c, AlFamily& f, double rho_state0, double tol_state) {
+  const bool task = &f == &c->al.tk;
   const size_t B = c->B, rec_d = al_store_doubles(c, f);
   if (!f.store) TRY(dalloc(c, &f.store, B * rec_d));
   std::vector<double> st(B * rec_d, 0.0);
@@ -741,7 +756,8 @@ __attribute__((noinline, minsize)) static int al_state_store_install(ilqr_hip_ct
   if (f.sets) HIPCHK_S(c, hipMemcpy(st.data(), f.store, st.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t b = 0; b < B; ++b) st[b * rec_d + h1::ALS_RHO] = rho_state0;
   HIPCHK_S(c, hipMemcpy(f.store, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (!f.sets) HIPCHK_S(c, hipMemset(c->al.sviol, 0, B * sizeof(double)));
+  if (!f.sets) HIPCHK_S(c, hipMemset(task ? c->al.tviol : c->al.sviol, 0, B * sizeof(double)));
+  if (task) { c->P.alt = f.store; c->P.alt_stride = (long)rec_d; c->al.trho0 = rho_state0; c->al.ttol = tol_state; return ILQR_OK; }
   c->P.als = f.store; c->P.als_stride = (long)rec_d;
   c->al.srho0 = rho_state0; c->al.stol = tol_state;
   return ILQR_OK;
@@ -754,7 +770,7 @@ __attribute__((noinline, minsize)) static int al_install(ilqr_hip_ctx* c, AlFami
   if (window) TRY(al_knot_ready(c));
   else if (!f.table) TRY(dalloc(c, &f.table, (size_t)c->B * f.width));
   TRY(upload_rows(c, window ? f.window : f.table, bounds, rows, f.fields, f.width));
-  if (state) TRY(al_state_store_install(c, state[0], state[1]));
+  if (state) TRY(al_state_store_install(c, f, state[0], state[1]));
   if (!window) f.host.assign(bounds, bounds + rows * f.fields);
   f.sets = n_sets; f.knot = window;
   return al_point_bounds(c);
@@ -766,10 +782,11 @@ __attribute__((noinline, minsize)) static int al_set_bounds(ilqr_hip_ctx* c, AlF
   return al_install(c, f, bounds, n_sets, window, state);
 }
 // table or window; the buffers stay with the handle for the next one
-__attribute__((noinline)) static int al_clear_bounds(ilqr_hip_ctx* c, AlFamily& f) {
+__attribute__((noinline, minsize)) static int al_clear_bounds(ilqr_hip_ctx* c, AlFamily& f) {
   TRY(al_installed(c));
   f.sets = 0; f.knot = false;
   if (&f == &c->al.st) { c->P.als = nullptr; c->P.als_stride = 0; }
+  if (&f == &c->al.tk) { c->P.alt = nullptr; c->P.alt_stride = 0; }
   enter(c);
   return al_point_bounds(c);
 }
@@ -801,15 +818,17 @@ int ilqr_hip_get_al_bounds(ilqr_hip_ctx* c, double* bounds) { return c ? al_get_
 int ilqr_hip_get_al_state_bounds(ilqr_hip_ctx* c, double* bounds) { return c ? al_get_bounds(c, c->al.st, bounds) : ILQR_ERR_ARG; }
 int ilqr_hip_al_bounds_per_knot(const ilqr_hip_ctx* c) { return c ? ((c->P.al && c->al.jc.knot) ? 1 : 0) | ((c->P.al && c->al.st.knot) ? 2 : 0) : -1; }
 // what the kernels read at every knot, whoever wrote it: the windows (knot stride set), a table's records, or nothing (al_no_bounds)
-__attribute__((minsize)) int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* c, double* joint_ctrl, double* state) {
+__attribute__((noinline, minsize)) static int al_get_knot_bounds(ilqr_hip_ctx* c, double* joint_ctrl, double* state, double* task) {
   if (!c) return ILQR_ERR_ARG;
   TRY(al_installed(c));
   enter(c);
   const size_t B = c->B, n1 = (size_t)c->N + 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const struct { const AlFamily& f; double* out; const double* dev; long stride, knot; } fams[2] = {
-    {c->al.jc, joint_ctrl, c->P.alb, c->P.alb_stride, c->P.alb_knot}, {c->al.st, state, c->P.alsb, c->P.alsb_stride, c->P.alsb_knot}};
-  for (const auto& v : fams) {
+  const struct { const AlFamily& f; double* out; const double* dev; long stride, knot; } fams[3] = {
+    {c->al.jc, joint_ctrl, c->P.alb, c->P.alb_stride, c->P.alb_knot}, {c->al.st, state, c->P.alsb, c->P.alsb_stride, c->P.alsb_knot},
+    {c->al.tk, task, c->P.altb, c->P.altb_stride, c->P.altb_knot}};
+  for (int i = 0; i < 3; ++i) {
+    const auto& v = fams[i];
     if (!v.out) continue;
     const size_t F = v.f.fields, W = v.f.width, per_set = (v.knot ? n1 : 1) * W;
     std::vector<double> img(v.dev ? (v.stride ? B : 1) * per_set : F);
@@ -821,6 +840,17 @@ __attribute__((minsize)) int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* c, double
   }
   return ILQR_OK;
 }
+int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* c, double* joint_ctrl, double* state) { return al_get_knot_bounds(c, joint_ctrl, state, nullptr); }
+// ---- the task family's entry points: the bodies above on the third family record.  Its bounds are a window always
+static_assert(h1::ALTB_FIELDS == ILQR_AL_TASK_BOUNDS && h1::ALT_COORDS == ILQR_AL_TASK_COORDS && h1::ALTB_HI == 9 && h1::ALT_HI == h1::ALT_LO + 9 && h1::ALT_HDR == h1::AL_HDR && h1::ALT_RHO == 0,
+              "the interface's row is the device row without its padding; the store's layout is the one al_convert walks");
+__attribute__((minsize)) int ilqr_hip_set_al_task_bounds(ilqr_hip_ctx* c, const double* bounds, int n_sets, double rho_task0, double tol_task) {
+  const double state[2] = {rho_task0, tol_task};
+  return c ? al_set_bounds(c, c->al.tk, bounds, n_sets, true, state) : ILQR_ERR_ARG;
+}
+int ilqr_hip_clear_al_task_bounds(ilqr_hip_ctx* c) { return c ? al_clear_bounds(c, c->al.tk) : ILQR_ERR_ARG; }
+int ilqr_hip_num_al_task_bound_sets(const ilqr_hip_ctx* c) { return c ? c->al.tk.sets : -1; }
+int ilqr_hip_get_al_task_bounds(ilqr_hip_ctx* c, double* bounds) { return bounds ? al_get_knot_bounds(c, nullptr, nullptr, bounds) : ILQR_ERR_ARG; }
 
 // ---- the multiplier stores.  Host image of a family's store <-> the interface's arrays, one pass: block g of a knot's record <-> mu[g]
 // [B][N+1][per][2] (lower, upper; block 1, the actuators: [B][N][per][2]), the penalties <-> rho [B][blocks]; to_store = false reads the image
@@ -846,10 +876,10 @@ __attribute__((noinline, minsize)) static void al_convert(const ilqr_hip_ctx* c,
 static size_t al_mu_doubles(const ilqr_hip_ctx* c, const AlFamily& f, int g) { return (size_t)c->B * (g ? c->N : c->N + 1) * f.per * 2; }
 // reads the store (set: installs the caller's arrays in its image and writes it back).  Without a state family its getters give zero
 // multipliers and rho_state 0 (nothing is constrained) and its setter refuses
-__attribute__((noinline)) static int al_store_io(ilqr_hip_ctx* c, AlFamily& f, double* const mu[2], double* rho, bool set) {
+__attribute__((noinline, minsize)) static int al_store_io(ilqr_hip_ctx* c, AlFamily& f, double* const mu[2], double* rho, bool set) {
   TRY(al_installed(c));
   if (al_family_absent(c, f)) {
-    if (set) { c->err = "no state bounds installed"; return ILQR_ERR_STATE; }
+    if (set) { c->err = &f == &c->al.tk ? "no task bounds installed" : "no state bounds installed"; return ILQR_ERR_STATE; }
     for (int g = 0; g < f.blocks; ++g) if (mu[g]) std::fill(mu[g], mu[g] + al_mu_doubles(c, f, g), 0.0);
     if (rho) std::fill(rho, rho + (size_t)c->B * f.blocks, 0.0);
     return ILQR_OK;
@@ -879,8 +909,14 @@ int ilqr_hip_set_al_state_multipliers(ilqr_hip_ctx* c, const double* m, const do
   double* const mu[2] = {const_cast<double*>(m), nullptr};
   return c ? al_store_io(c, c->al.st, mu, const_cast<double*>(rho), true) : ILQR_ERR_ARG;
 }
+int ilqr_hip_get_al_task_multipliers(ilqr_hip_ctx* c, double* m) { double* const mu[2] = {m, nullptr}; return c && m ? al_store_io(c, c->al.tk, mu, nullptr, false) : ILQR_ERR_ARG; }
+int ilqr_hip_get_al_task_penalties(ilqr_hip_ctx* c, double* rho) { double* const mu[2] = {nullptr, nullptr}; return c && rho ? al_store_io(c, c->al.tk, mu, rho, false) : ILQR_ERR_ARG; }
+int ilqr_hip_set_al_task_multipliers(ilqr_hip_ctx* c, const double* m, const double* rho) {
+  double* const mu[2] = {const_cast<double*>(m), nullptr};
+  return c ? al_store_io(c, c->al.tk, mu, const_cast<double*>(rho), true) : ILQR_ERR_ARG;
+}
 // ---- the observables of the update
-int ilqr_hip_get_al_violation(ilqr_hip_ctx* c, double* viol, int* done) {
+__attribute__((minsize)) int ilqr_hip_get_al_violation(ilqr_hip_ctx* c, double* viol, int* done) {
   if (!c) return ILQR_ERR_ARG;
   TRY(al_installed(c));
   enter(c);
@@ -889,17 +925,19 @@ int ilqr_hip_get_al_violation(ilqr_hip_ctx* c, double* viol, int* done) {
   if (done) HIPCHK_S(c, hipMemcpy(done, c->al.done, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost));
   return ILQR_OK;
 }
-int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* c, double* viol) {
-  if (!c || !viol) return ILQR_ERR_ARG;
+__attribute__((noinline, minsize)) static int al_get_family_violation(ilqr_hip_ctx* c, const AlFamily& f, const double* dev, double* viol) {
+  if (!viol) return ILQR_ERR_ARG;
   TRY(al_installed(c));
-  if (al_family_absent(c, c->al.st)) { std::fill(viol, viol + c->B, 0.0); return ILQR_OK; }
+  if (al_family_absent(c, f)) { std::fill(viol, viol + c->B, 0.0); return ILQR_OK; }
   enter(c);
   HIPCHK_S(c, hipStreamSynchronize(c->stream));
-  HIPCHK_S(c, hipMemcpy(viol, c->al.sviol, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK_S(c, hipMemcpy(viol, dev, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost));
   return ILQR_OK;
 }
+int ilqr_hip_get_al_state_violation(ilqr_hip_ctx* c, double* viol) { return c ? al_get_family_violation(c, c->al.st, c->al.sviol, viol) : ILQR_ERR_ARG; }
+int ilqr_hip_get_al_task_violation(ilqr_hip_ctx* c, double* viol) { return c ? al_get_family_violation(c, c->al.tk, c->al.tviol, viol) : ILQR_ERR_ARG; }
 // the trace of the last solve: `width` doubles per round and rollout
-__attribute__((noinline)) static int al_get_trace(ilqr_hip_ctx* c, const double* trace, int width, double* out) {
+__attribute__((noinline, minsize)) static int al_get_trace(ilqr_hip_ctx* c, const double* trace, int width, double* out) {
   if (!c || !out) return ILQR_ERR_ARG;
   TRY(al_installed(c));
   enter(c);
@@ -909,6 +947,22 @@ __attribute__((noinline)) static int al_get_trace(ilqr_hip_ctx* c, const double*
 }
 int ilqr_hip_get_al_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.trace : nullptr, 5, out); }
 int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.strace : nullptr, 2, out); }
+int ilqr_hip_get_al_task_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.ttrace : nullptr, 2, out); }
+// the nine task coordinates of the resident nominal trajectory, by the kernel the cost kernels and the update share their arithmetic with
+__attribute__((minsize)) int ilqr_hip_get_al_task_points(ilqr_hip_ctx* c, double* out) {
+  if (!c || !out) return ILQR_ERR_ARG;
+  TRY(al_installed(c));
+  if (!c->initialized) return ILQR_ERR_STATE;
+  enter(c);
+  TRY(al_knot_ready(c));
+  const size_t n = (size_t)c->B * (c->N + 1) * ILQR_AL_TASK_COORDS;
+  if (!c->al.tpoints) TRY(dalloc(c, &c->al.tpoints, n));
+  ilqr::g_al_knot.task_points(&c->S, c->al.tpoints, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->al.tpoints, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
 int ilqr_hip_al_update(ilqr_hip_ctx* c, int round) {
   if (!c || round < 0) return ILQR_ERR_ARG;
   TRY(al_installed(c));
@@ -1294,6 +1348,7 @@ static h1::ProblemDev slice_problem(const h1::ProblemDev& P, long b0) {
   if (P.al) T.al += b0 * P.al_stride;
   if (P.alb) T.alb += b0 * P.alb_stride;
   if (P.alsb) { T.als += b0 * P.als_stride; T.alsb += b0 * P.alsb_stride; }
+  if (P.altb) { T.alt += b0 * P.alt_stride; T.altb += b0 * P.altb_stride; }
   return T;
 }
 static int ensure_slices(ilqr_hip_ctx* c, int k) {
@@ -1820,6 +1875,7 @@ __attribute__((noinline)) static int enqueue_al_rounds(ilqr_hip_ctx* c, int k) {
   HIPCHK_S(c, hipMemsetAsync(c->al.left, 0, (size_t)rounds * sizeof(int), st));
   HIPCHK_S(c, hipMemsetAsync(c->al.trace, 0xFF, (size_t)rounds * c->B * 5 * sizeof(double), st));      // (all bits set: NaN)
   HIPCHK_S(c, hipMemsetAsync(c->al.strace, 0xFF, (size_t)rounds * c->B * 2 * sizeof(double), st));
+  HIPCHK_S(c, hipMemsetAsync(c->al.ttrace, 0xFF, (size_t)rounds * c->B * 2 * sizeof(double), st));
   c->al.rounds_run = 0;
   int rc = ILQR_OK;
   for (int round = 0; round < rounds && rc == ILQR_OK; ++round) {
@@ -2207,7 +2263,7 @@ static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
   h1::ProblemDev Ps = c->P;
   std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
   Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
-  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0; Ps.als = nullptr; Ps.als_stride = 0; Ps.alsb = nullptr; Ps.alsb_stride = 0; Ps.alb_knot = 0; Ps.alsb_knot = 0;
+  Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0; Ps.als = nullptr; Ps.als_stride = 0; Ps.alsb = nullptr; Ps.alsb_stride = 0; Ps.alb_knot = 0; Ps.alsb_knot = 0; Ps.altb = nullptr;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and

@@ -163,6 +163,13 @@ struct AlDev {
   // windows of bounds (ProblemDev::alb_knot, alsb_knot, the same values): 0 one record per set, else the doubles from knot t's record to knot
   // t + 1's inside a set's window, and bounds_stride / sbounds_stride the doubles of one set's window.  Appended: nothing above moves
   long bounds_knot, sbounds_knot;
+  // the task family (ilqr_hip_set_al_task_bounds; al_task_dev.h); tbounds null: not installed, nothing below is read.  Appended: nothing above moves
+  const double* tbounds; long tbounds_stride, tbounds_knot;      // its window of bounds (ProblemDev::altb, the same rows)
+  double* tstore; long tstride;                  // its multiplier store (ProblemDev::alt points at the same records)
+  double rho_task0, rho_task_max, tol_task;
+  double* tviol;                   // [B] task violation of the nominal trajectory at the last update (knots 1..N, swing rows of the feet)
+  double* ttrace;                  // [rounds][B][2] violation, rho_task the round ran with
+  const int* stance; long stance_stride;         // the contact schedule (ProblemDev::stance): a foot's rows are off where it stands
 };
 // The kernels that read windows of bounds live in a module of their own, libilqr_hip_alknot.so beside the library (csrc/Makefile; opened by
 // ilqr_capi.hip on the first call that installs a window, as the plant kernels' modules are): the per-knot instantiations of
@@ -180,6 +187,12 @@ struct AlKnotModule {
   // costs it ~25 KB of headers and metadata for two copy kernels)
   void (*window_from_track)(const AlBoundsTrackDev* T, const AlBoundsWindowDev* W, const int* start, int n_sets, int step, int N, hipStream_t st);
   void (*expand)(const double* rec, long rec_stride, double* win, int width, int n_sets, int N, hipStream_t st);
+  // the task family (al_task_dev.h), whose every kernel lives here: its terms added to the knot costs (behind knot_cost and state_knot_cost,
+  // ahead of the sum), the warm-start shift of its store, and the nine points of the nominal trajectories into out [B][N+1][9].  cost_quadratics
+  // and al_update above launch their task instantiations where ProblemDev::altb / AlDev::tbounds is set.  Appended: nothing above moves
+  void (*task_knot_cost)(const DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st);
+  void (*task_shift)(const AlDev* A, int B, int N, int shift, hipStream_t st);
+  void (*task_points)(const DevState* S, double* out, hipStream_t st);
 };
 extern AlKnotModule g_al_knot;      // (ilqr_capi.hip)
 // masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row

@@ -26,6 +26,7 @@
 //                      Workgroups are numbered so that the knots sharing the lines of a record group run on one XCD (one L2).
 #include <hip/hip_runtime.h>
 
+#include "al_task_dev.h"
 #include "h1_cost_dev.h"
 #include "h1_fast_math.h"
 #include "h1_model_constexpr.h"
@@ -90,7 +91,14 @@ enum {
   // field f of knot k: double (k / QREC_KNOTS) * QREC_LINES * 16 + (f / QREC_RUN) * 16 + (k % QREC_KNOTS) * QREC_RUN + f % QREC_RUN
 };
 static_assert(16 % QREC_RUN == 0 && QREC_RUN % 2 == 0, "record runs: whole lines, 16-byte pieces");
-size_t quad_rec_doubles(size_t knots) { return ((knots + QREC_KNOTS - 1) / QREC_KNOTS) * (size_t)QREC_LINES * 16; }
+// The task instantiations of the two kernels (the task family of the augmented Lagrangian, al_task_dev.h; libilqr_hip_alknot.so only) append
+// QR_GSCALE3 [4][3], a scale per AXIS of the four slots where the record above has one per slot: gscale[c] + rho_task per active side of the
+// axis.  The record's size -- and with it the lines of a group of knots -- is a property of the instantiation; the buffer holds either.
+enum { QR_GSCALE3 = QREC_SIZE, QREC_TASK_SIZE = QREC_SIZE + 12, QREC_TASK_LINES = (QREC_TASK_SIZE + QREC_RUN - 1) / QREC_RUN };
+static_assert(QREC_TASK_SIZE % QREC_RUN == 0 && QREC_TASK_SIZE <= 2 * 256, "task record: whole runs, two 16-byte pieces per lane of the reader");
+constexpr int qrec_size(bool task) { return task ? QREC_TASK_SIZE : QREC_SIZE; }
+constexpr int qrec_lines(bool task) { return task ? QREC_TASK_LINES : QREC_LINES; }
+size_t quad_rec_doubles(size_t knots) { return ((knots + QREC_KNOTS - 1) / QREC_KNOTS) * (size_t)QREC_TASK_LINES * 16; }
 
 // ---- k_quad_kin: compile-time model tables ------------------------------------------------------------------------------------
 struct QMassTab { double mu[H1_NB], msub[H1_NB], mtot; };
@@ -179,9 +187,43 @@ template <int FIRST, int LEN, int FOOT, class Put> struct QChain {
   }
 };
 
+// The task family's part of a knot's functionals (TASK instantiation of k_quad_kin): for axis k of the CoM (slot 0) and of each foot whose slot
+// is the position functional (stance flag != 1; slots 2, 3), with s_hi = max(0, mu_hi + rho (p_k - hi)), s_lo = max(0, mu_lo + rho (lo - p_k)):
+// m_k = s_hi - s_lo joins the slot's gradient vector and its second-order direction -- the term's gradient is J_k^T m_k, the second-order part of
+// its Hessian m_k d2 p_k -- and the axis' scale grows by rho per active side (the first-order part rho J_k^T J_k).  p is al_task_points' double.
+DEVFN void quad_task_terms(const ProblemDev& P, int b, int t, const double* xg, int st0, int st1, double (&vec)[4][3], double (&gsum)[4][3],
+                           const double (&gscale)[4], double (&gs3)[4][3]) {
+#pragma clang fp contract(off)
+  double p[ALT_COORDS]; al_task_points(xg, p);
+  const double* r = P.alt + (long)b * P.alt_stride;
+  const double rho = r[ALT_RHO];
+  const double* mu = r + ALT_HDR + (long)t * ALT_KNOT;
+  const double* bd = P.altb + (long)b * P.altb_stride + (long)t * P.altb_knot;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gs3[c][k] = gscale[c];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    if (s == 1 && st0 == 1) continue;
+    if (s == 2 && st1 == 1) continue;
+    const int c = s == 0 ? 0 : 1 + s;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int i = 3 * s + k;
+      const double sh = al_task_side(p[i] - bd[ALTB_HI + i], mu[ALT_HI + i], rho), sl = al_task_side(bd[ALTB_LO + i] - p[i], mu[ALT_LO + i], rho);
+      const double ph = sh > 0.0 ? sh : 0.0, pl = sl > 0.0 ? sl : 0.0;
+      const double m = ph - pl;
+      gsum[c][k] = gsum[c][k] + m; vec[c][k] = vec[c][k] + m;
+      gs3[c][k] = (gs3[c][k] + (sh > 0.0 ? rho : 0.0)) + (sl > 0.0 ? rho : 0.0);
+    }
+  }
+}
+
 // One lane per knot.  `rec`: the record buffer (quad_rec_doubles); knot0: index of the view's first knot in it (batch slices).
 // WS: the task weights come from the lane's own rollout's weight set (CostWeights, h1_cost_dev.h): the branches on them are per lane
-template <bool WS>
+// TASK: the task family's terms on top (quad_task_terms) and the larger record
+template <bool WS, bool TASK = false>
 __global__ void __launch_bounds__(64) k_quad_kin(DevState S, ProblemDev P, const int* list, const int* count, double* rec, long knot0) {
   const int N1 = S.N + 1;
   const unsigned g = blockIdx.x * 64u + threadIdx.x;                    // (32-bit on purpose: a 64-bit division is ~150 scalar instructions)
@@ -212,7 +254,7 @@ __global__ void __launch_bounds__(64) k_quad_kin(DevState S, ProblemDev P, const
   __syncthreads();
   const double* xg = xs + threadIdx.x * H1_NX;
   const long kn = knot0 + (long)b * N1 + t;
-  double* out = rec + (size_t)(kn / QREC_KNOTS) * ((size_t)QREC_LINES * 16) + (kn % QREC_KNOTS) * QREC_RUN;
+  double* out = rec + (size_t)(kn / QREC_KNOTS) * ((size_t)qrec_lines(TASK) * 16) + (kn % QREC_KNOTS) * QREC_RUN;
   auto put = [&](int f, double v) { out[(f / QREC_RUN) * 16 + f % QREC_RUN] = v; };
   typedef decltype(put) PutT;
 
@@ -375,6 +417,14 @@ __global__ void __launch_bounds__(64) k_quad_kin(DevState S, ProblemDev P, const
 #pragma unroll
     for (int k = 0; k < 3; ++k) { vec[0][k] += Wt.w_balance(P) * mu[k]; vec[1][k] += Wt.w_balance(P) * nu[k]; }
   }
+  if constexpr (TASK) {
+    double gs3[4][3];
+    quad_task_terms(P, b, t, xg, st0, st1, vec, gsum, gscale, gs3);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) put(QR_GSCALE3 + 3 * c + k, gs3[c][k]);
+  }
   put(QR_HASBAL, hasbal);
 #pragma unroll
   for (int k = 0; k < 8; ++k) put(QR_BAL + k, bal[k]);
@@ -416,6 +466,10 @@ struct QuadLds {
 };
 static_assert(sizeof(QuadLds) <= 16384, "QuadLds must fit ten two-wave workgroups per CU");
 static_assert(offsetof(QuadLds, aux) == sizeof(double) * QREC_SIZE, "aux directly behind rec: one base pointer for the column table");
+// the task instantiations keep the record's tail, the per-axis scales, behind everything else: rec and aux stay where the column table expects them
+template <bool TASK> struct QuadLdsT : QuadLds {};
+template <> struct QuadLdsT<true> : QuadLds { double gs3[QREC_TASK_SIZE - QREC_SIZE]; };
+static_assert(sizeof(QuadLdsT<true>) <= 16384 && sizeof(QuadLdsT<false>) == sizeof(QuadLds), "QuadLds must fit ten two-wave workgroups per CU");
 
 // Phase 1a as ONE formula: column c of the Jacobian rows of functional (type, point set) = M(c) u(c), M a 3 x 3 block and u a
 // 3-vector of the record (or of the LDS constants behind it): offsets from the record base, built at compile time.
@@ -662,7 +716,9 @@ DEVFN void quad_hessian_tiles(const double (&av)[4][2], const double (&bv)[4][4]
 // A lane still owns at most one coordinate.
 // AL_KNOT_TABLE / AL_KNOT_TABLE_STATE (windows of bounds, ProblemDev::alb_knot / alsb_knot): the same requests from row t (actuator lanes: row
 // tu) of rollout b's window -- one 64-bit multiply-add per bounds pointer, nothing else.  Instantiated in libilqr_hip_alknot.so only.
-template <bool WS, int AL>
+// TASK (the two per-knot variants only; al_task_dev.h): the record is the task producer's, and in phase 2a the scale of operand row (ks, lk < 3)
+// is the per-axis one (QR_GSCALE3), `used` is "that scale != 0".  Gradient, patch phase and write-out read QR_GSUM, QR_TIL and QR_DV as ever.
+template <bool WS, int AL, bool TASK = false>
 __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S, ProblemDev P, int mode, const int* list, const int* count, int lower,
                                                                      const double* recg, long knot0) {
   const int lane = threadIdx.x, wv = lane >> 6;
@@ -684,7 +740,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   if constexpr (AL != AL_OFF) { const double* ar = P.al + (long)b * P.al_stride; al_rho_j = ar[AL_RHO_JOINT]; al_rho_c = ar[AL_RHO_CTRL]; }
   double al_rho_s = 0.0;
   if constexpr (al_state(AL)) al_rho_s = (P.als + (long)b * P.als_stride)[ALS_RHO];
-  __shared__ QuadLds L;
+  __shared__ QuadLdsT<TASK> L;
 #ifdef QUAD_STAMP
   long long qlast = clock64();
 #endif
@@ -705,11 +761,11 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
   {
     const int f1 = mode == MASK_ALL ? 1 : S.active[b], f2 = mode == MASK_RETRY ? S.need_retry[b] : 1;
     const long kn = knot0 + (long)b * N1 + t;
-    const double* rg = recg + (size_t)(kn / QREC_KNOTS) * ((size_t)QREC_LINES * 16) + (kn % QREC_KNOTS) * QREC_RUN;
+    const double* rg = recg + (size_t)(kn / QREC_KNOTS) * ((size_t)qrec_lines(TASK) * 16) + (kn % QREC_KNOTS) * QREC_RUN;
     typedef double v2d_q __attribute__((ext_vector_type(2)));
     v2d_q rv[2];                                                              // 16-byte pieces lane and lane + 128 of the record's 234
 #pragma unroll
-    for (int k = 0; k < 2; ++k) { int f = 2 * (lane + 128 * k); f = f < QREC_SIZE ? f : QREC_SIZE - 2; rv[k] = *reinterpret_cast<const v2d_q*>(rg + (f / QREC_RUN) * 16 + f % QREC_RUN); }
+    for (int k = 0; k < 2; ++k) { int f = 2 * (lane + 128 * k); f = f < qrec_size(TASK) ? f : qrec_size(TASK) - 2; rv[k] = *reinterpret_cast<const v2d_q*>(rg + (f / QREC_RUN) * 16 + f % QREC_RUN); }
     const int a = lane < H1_NX ? lane : 0;
     xv = xg[a]; xrv = (P.x_ref + b * P.x_ref_stride + t * H1_NX)[a]; qdv = Qd[a];
     const int l1 = lane - 64, iu = (l1 >= 0 && l1 < H1_NU) ? l1 : 0, tu = term ? N - 1 : t;
@@ -760,7 +816,11 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
     const unsigned pkw = QPK.w[lane & 63];
     if (!(f1 && f2)) return;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) { const int f = 2 * (lane + 128 * k); if (f < QREC_SIZE) *reinterpret_cast<v2d_q*>(&L.rec[f]) = rv[k]; }
+    for (int k = 0; k < 2; ++k) {
+      const int f = 2 * (lane + 128 * k);
+      if (f < QREC_SIZE) *reinterpret_cast<v2d_q*>(&L.rec[f]) = rv[k];
+      if constexpr (TASK) if (f >= QREC_SIZE && f < QREC_TASK_SIZE) { L.gs3[f - QREC_SIZE] = rv[k][0]; L.gs3[f - QREC_SIZE + 1] = rv[k][1]; }
+    }
     if (lane < 64) L.pk[lane] = pkw;
     // constants of the uniform column formula (QColTable): identity and zero vector; mfrac_s e_k and e_k x beta_s from the lanes that
     // hold mfrac_s (field 60 + s: lane 60 + s, k = 0) and beta_s[j] (field 64 + 3 s + j: lane 64 + 3 s + j, k = 0)
@@ -925,7 +985,8 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
       const double* rowJ = L.J[3 * ks + (lk < 3 ? lk : 0)];
       const double* rowA = lk < 3 ? rowJ : (ks == 0 ? L.J[QJ_R0] : (ks == 1 ? L.J[QJ_R1] : (ks == 2 ? L.J[QJ_C + 2] : L.J[QJ_M])));
       const double* rowB = lk < 3 ? rowJ : (ks == 0 ? L.J[QJ_R0] : (ks == 1 ? L.J[QJ_R1] : (ks == 2 ? L.J[QJ_M] : L.J[QJ_C + 2])));
-      const double sA = lk < 3 ? rec[QR_GSCALE + ks] : w_balance_b;
+      double sA;
+      if constexpr (TASK) sA = lk < 3 ? L.gs3[3 * ks + lk] : w_balance_b; else sA = lk < 3 ? rec[QR_GSCALE + ks] : w_balance_b;
       const bool used = lk < 3 ? (sA != 0.0) : (has_bal != 0);
 #pragma unroll
       for (int T = 0; T < 4; ++T) {
@@ -1069,6 +1130,7 @@ __global__ void __launch_bounds__(128, QUAD_WAVES) k_cost_quadratics(DevState S,
 }
 
 // one workgroup per knot; the grid is padded to a multiple of 8 so that every XCD's share (L % 8) has ceil(total / 8) slots
+#define QUAD_LAUNCH_TASK(AL) hipLaunchKernelGGL((k_cost_quadratics<false, AL, true>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0)
 #define QUAD_LAUNCH(WS, AL) hipLaunchKernelGGL((k_cost_quadratics<WS, AL>), dim3((unsigned)(per * 8)), dim3(128), 0, st, S, P, mode, w.list, w.count, lower, (const double*)S.quad_rec, S.quad_knot0)
 #ifdef AL_KNOT_MODULE
 }  // namespace ilqr
@@ -1080,6 +1142,11 @@ extern "C" void ilqr_alknot_module_cost_quadratics(const ilqr::DevState* Sp, con
   const DevState& S = *Sp; const ProblemDev& P = *Pp;
   const WorkList w{list, count};
   const long knots = (long)S.B * (S.N + 1), per = (knots + 7) / 8;
+  if (P.altb) {      // the task family on top: the task instantiations of both kernels, the larger record between them
+    hipLaunchKernelGGL((k_quad_kin<false, true>), dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
+    if (P.alsb) QUAD_LAUNCH_TASK(AL_KNOT_TABLE_STATE); else QUAD_LAUNCH_TASK(AL_KNOT_TABLE);
+    return;
+  }
   hipLaunchKernelGGL(k_quad_kin<false>, dim3((unsigned)((knots + 63) / 64)), dim3(64), 0, st, S, P, w.list, w.count, S.quad_rec, S.quad_knot0);
   switch (al_variant(P.al, P.alb, P.alsb, P.alb_knot)) {
     case AL_KNOT_TABLE_STATE: QUAD_LAUNCH(false, AL_KNOT_TABLE_STATE); break;

@@ -457,6 +457,66 @@ def stack_al_state_knot_bounds(records, B, N):
     return np.stack([np.concatenate([stack_al_state_bounds(k, 1) for k in knots]) for knots in per])
 
 
+# keys of a task-bounds record: name -> first task coordinate (three each), in the order of ilqr_hip_set_al_task_bounds
+_AL_TASK_FIELDS = {"com": 0, "left_foot": 3, "right_foot": 6}
+
+
+def stack_al_task_bounds(records, B, N):
+    """Task-bounds windows [n, N+1, 18] for BatchedILQR.set_al_task_bounds: row t holds knot t's lo[9], hi[9] over the task coordinates CoM
+    x, y, z, left ankle origin x, y, z, right ankle origin x, y, z (world frame).  records is one dict (n = 1: every rollout reads the
+    window) or a sequence of B dicts (n = B).  Every key is optional: "com", "left_foot", "right_foot" take a pair (lo, hi), each a scalar,
+    [3] (the whole horizon) or [N+1, 3] (one row per knot); the shorthands "swing_clearance": z_min sets z >= z_min on both feet (the
+    solver ignores a foot's rows at its stance knots, so this bounds the swing phases) and "com_xy": ((x0, y0), (x1, y1)) the box
+    x0 <= x <= x1, y0 <= y <= y1 of the CoM.  A shorthand is applied after the key it refines.  A key left out gives -inf / +inf: no bound.
+    Raises ValueError for another key, a wrong shape, a sequence that is not B long, or a window ilqr_hip_set_al_task_bounds refuses (a NaN,
+    lo > hi, lo = +inf, hi = -inf)."""
+    B, N = int(B), int(N)
+    if B < 1 or N < 1:
+        raise ValueError("B and N must be positive")
+    if isinstance(records, dict):
+        records = [records]
+    else:
+        records = list(records)
+        if len(records) != B:
+            raise ValueError("records must be one dict or B of them")
+    out = np.empty((len(records), N + 1, 18))
+    out[:, :, :9] = -np.inf; out[:, :, 9:] = np.inf
+
+    def rows(name, v):
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape not in ((), (3,), (N + 1, 3)):
+            raise ValueError("%s: lo and hi are scalars, [3] or [N+1, 3]" % name)
+        return np.broadcast_to(v, (N + 1, 3))
+
+    for b, rec in enumerate(records):
+        if not isinstance(rec, dict):
+            raise ValueError("a task-bounds record is a dict")
+        extra = set(rec) - set(_AL_TASK_FIELDS) - {"swing_clearance", "com_xy"}
+        if extra:
+            raise ValueError("unknown task-bounds field(s) %s: a record has %s, swing_clearance and com_xy" % (sorted(extra), list(_AL_TASK_FIELDS)))
+        for name, k0 in _AL_TASK_FIELDS.items():
+            if rec.get(name) is not None:
+                try:
+                    lo, hi = rec[name]
+                except (TypeError, ValueError):
+                    raise ValueError("%s takes a pair (lo, hi)" % name)
+                out[b, :, k0:k0 + 3], out[b, :, 9 + k0:9 + k0 + 3] = rows(name, lo), rows(name, hi)
+        if rec.get("swing_clearance") is not None:
+            z = np.asarray(rec["swing_clearance"], dtype=np.float64)
+            if z.shape != ():
+                raise ValueError("swing_clearance is one height")
+            out[b, :, 5] = out[b, :, 8] = float(z)
+        if rec.get("com_xy") is not None:
+            c = np.asarray(rec["com_xy"], dtype=np.float64)
+            if c.shape != (2, 2):
+                raise ValueError("com_xy is ((x0, y0), (x1, y1))")
+            out[b, :, 0:2], out[b, :, 9:11] = c[0], c[1]
+    lo, hi = out[..., :9], out[..., 9:]
+    if np.isnan(out).any() or (lo > hi).any() or (lo == np.inf).any() or (hi == -np.inf).any():
+        raise ValueError("task bounds: no NaN, lo <= hi, lo < +inf, hi > -inf")
+    return out
+
+
 def al_bounds_from_plant_joints(joints, margin=0.0):
     """The bounds table [n, 76] in which the solver knows each rollout's torque range of stack_plant_joints' records `joints` [n, 76]:
     ctrl_lo, ctrl_hi = range_scale_i * the default control bound of actuator i at `margin` (range_scale = 0, a dead motor: lo = hi = 0);

@@ -35,6 +35,9 @@ EXPORTS = [
     "ilqr_hip_set_al_knot_bounds", "ilqr_hip_set_al_state_knot_bounds", "ilqr_hip_get_al_knot_bounds", "ilqr_hip_al_bounds_per_knot",
     "ilqr_hip_set_al_bounds_track", "ilqr_hip_clear_al_bounds_track", "ilqr_hip_al_bounds_track_rows", "ilqr_hip_set_al_bounds_track_starts",
     "ilqr_hip_al_bounds_window_from_track",
+    "ilqr_hip_set_al_task_bounds", "ilqr_hip_clear_al_task_bounds", "ilqr_hip_num_al_task_bound_sets", "ilqr_hip_get_al_task_bounds",
+    "ilqr_hip_get_al_task_multipliers", "ilqr_hip_set_al_task_multipliers", "ilqr_hip_get_al_task_penalties", "ilqr_hip_get_al_task_violation",
+    "ilqr_hip_get_al_task_trace", "ilqr_hip_get_al_task_points",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -97,6 +100,10 @@ AL_BOUNDS = 76
 # position (3), pelvis linear velocity (3), pelvis angular velocity (3), joint velocities (19); al_state_slot(k) is coordinate k's state slot
 AL_STATE_COORDS = 28
 AL_STATE_BOUNDS = 56
+# one row of a window of task bounds of the augmented Lagrangian (ILQR_AL_TASK_BOUNDS): lo[9], hi[9] over the task coordinates -- CoM x, y, z,
+# left ankle origin x, y, z, right ankle origin x, y, z, world frame
+AL_TASK_COORDS = 9
+AL_TASK_BOUNDS = 18
 # columns of a plant terrain record (include/ilqr_hip.h ILQR_PLANT_TERRAIN)
 PLANT_TERRAIN = ("z_left", "z_right", "edge_x", "first", "end")
 
@@ -509,6 +516,56 @@ class BatchedILQR:
     def al_state_trace(self):
         """[rounds, B, 2]: state violation and rho_state of every round of the last solve (NaN: not run)."""
         return self._get("ilqr_hip_get_al_state_trace", (self.augmented_lagrangian_rounds(), self.B, 2))
+
+    # ---- augmented-Lagrangian bounds on the centre of mass and the two ankle origins (include/ilqr_hip.h ilqr_hip_set_al_task_bounds)
+    def set_al_task_bounds(self, win, rho_task0, tol_task=1e-3):
+        """A window of bounds on the nine task coordinates (CoM, left ankle origin, right ankle origin; world frame), enforced as a fourth
+        family of the installed augmented Lagrangian: [N+1, AL_TASK_BOUNDS] / [1, N+1, AL_TASK_BOUNDS] (every rollout) or
+        [B, N+1, AL_TASK_BOUNDS]; row t holds knot t's lo[9], hi[9] (scenario.stack_al_task_bounds).  -inf / +inf switch a side off; a
+        foot's rows are off at the knots where the contact schedule has it in stance.  rho_task0: the initial penalty of the family; a
+        rollout is done only when its task violation (metres) is <= tol_task as well.  Acts on the cost only; horizon-local (a warm start
+        shifts the multipliers, not the window); stays until clear_al_task_bounds() or clear_augmented_lagrangian()."""
+        b = self._knot_window(win, AL_TASK_BOUNDS, "task bounds")
+        self._chk(self.L.ilqr_hip_set_al_task_bounds(self.h, _p(b), int(b.shape[0]), C.c_double(float(rho_task0)), C.c_double(float(tol_task))))
+
+    def clear_al_task_bounds(self):
+        """No task bounds any more."""
+        self._chk(self.L.ilqr_hip_clear_al_task_bounds(self.h))
+
+    def num_al_task_bound_sets(self):
+        """0: no window; else the number of windows installed (1 or B)."""
+        return int(self.L.ilqr_hip_num_al_task_bound_sets(self.h))
+
+    def al_task_bounds(self):
+        """[B, N+1, AL_TASK_BOUNDS]: the window each rollout is solved with (without one: -inf / +inf)."""
+        return self._get("ilqr_hip_get_al_task_bounds", (self.B, self.N + 1, AL_TASK_BOUNDS))
+
+    def al_task_multipliers(self):
+        """[B,N+1,9,2]: the multipliers of the (lower, upper) bounds of the task coordinates."""
+        return self._get("ilqr_hip_get_al_task_multipliers", (self.B, self.N + 1, AL_TASK_COORDS, 2))
+
+    def set_al_task_multipliers(self, mu=None, rho=None):
+        """Install task multipliers [B,N+1,9,2] and / or the penalties rho_task [B]; None leaves that part as it is."""
+        mu, rho = (None if a is None else _c64(a) for a in (mu, rho))
+        if (mu is not None and mu.shape != (self.B, self.N + 1, AL_TASK_COORDS, 2)) or (rho is not None and rho.shape != (self.B,)):
+            raise ValueError("task multipliers: mu [B,N+1,9,2], rho [B]")
+        self._chk(self.L.ilqr_hip_set_al_task_multipliers(self.h, _p(mu), _p(rho)))
+
+    def al_task_penalties(self):
+        """rho_task [B] as the store holds it."""
+        return self._get("ilqr_hip_get_al_task_penalties", (self.B,))
+
+    def al_task_violation(self):
+        """viol_task [B] of the last update, metres (the done flags: al_violation)."""
+        return self._get("ilqr_hip_get_al_task_violation", (self.B,))
+
+    def al_task_trace(self):
+        """[rounds, B, 2]: task violation and rho_task of every round of the last solve (NaN: not run)."""
+        return self._get("ilqr_hip_get_al_task_trace", (self.augmented_lagrangian_rounds(), self.B, 2))
+
+    def al_task_points(self):
+        """[B, N+1, 9]: the task coordinates of the resident nominal trajectory as the kernels compute them."""
+        return self._get("ilqr_hip_get_al_task_points", (self.B, self.N + 1, AL_TASK_COORDS))
 
     # ---- bounds that change from knot to knot (include/ilqr_hip.h ilqr_hip_set_al_knot_bounds)
     def _knot_window(self, bounds, width, what):

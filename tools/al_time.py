@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian) against the plain penalties on ONE handle,
 on one GPU, the two alternating:
-   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state] [--knot]
+   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state] [--knot] [--task]
   * ms per call of the two cost stages (stage_cost_quadratics: k_quad_kin + k_cost_quadratics; stage_total_cost: k_traj_knot_cost +
     k_traj_cost_sum) and, per launch inside a solve, of the cost quadratics (ilqr_hip_get_stage_ms, stage 2);
   * ms per call of the update kernel alone (ilqr_hip_al_update: k_al_update, one memset, one synchronisation);
@@ -18,7 +18,10 @@ k_traj_knot_cost against the AL_TABLE instantiations of the mode before it.
 five lines) against the per-rollout table, and both families as windows (ilqr_hip_set_al_state_knot_bounds) against the two tables -- the per-knot
 instantiations of libilqr_hip_alknot.so against the table instantiations, the same arithmetic on the same values.  It also times
 ilqr_hip_al_bounds_window_from_track itself (both parts of a track of 2 (N + 1) rows, one start per rollout, `calls` enqueues and one
-synchronisation, per call): "window_from_track" in the output."""
+synchronisation, per call): "window_from_track" in the output.
+--task (implies --knot) adds one mode: the per-rollout windows of joint / torque bounds plus a per-rollout window of task bounds
+(ilqr_hip_set_al_task_bounds, n_sets = batch; every bound +-1e3 m, none active; the stance schedule is the problem's) -- the task
+instantiations of k_quad_kin, k_cost_quadratics and k_al_update and k_al_task_knot_cost against the per-knot instantiations of "al_knot_B"."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py)
@@ -39,8 +42,10 @@ def main():
     ap.add_argument("--bounds", action="store_true", help="also time AL under a one-record and under a per-rollout table of bounds")
     ap.add_argument("--state", action="store_true", help="also time AL under a per-rollout table of bounds plus a per-rollout table of state bounds")
     ap.add_argument("--knot", action="store_true", help="also time AL under per-rollout windows of bounds (per knot), and the track cut")
+    ap.add_argument("--task", action="store_true", help="also time AL under per-rollout windows of bounds plus a per-rollout window of task bounds")
     ap.add_argument("--cut-only", action="store_true", help="with --knot: time the track cut alone")
     a = ap.parse_args()
+    a.knot = a.knot or a.task
     a.state = a.state or a.knot
     a.bounds = a.bounds or a.state
     pkg = load_package()
@@ -52,12 +57,13 @@ def main():
     s = sv.BatchedILQR(B, N=N, dt=prob["dt"]); s.set_problem(prob)
     s.set_options(early_exit=False); s.set_max_iterations(a.iters)
     al = dict(rounds=3, rho_joint0=2 * prob["w_joint"], rho_ctrl0=2 * prob["w_ctrl"], growth=10.0, rho_max_factor=1e4, margin=0.1, tol_joint=0.0, tol_ctrl=0.0)
-    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ()) + (("al_bounds_B_state_B",) if a.state else ()) + (("al_knot_B", "al_knot_B_state_knot_B") if a.knot else ())
+    modes = ("plain", "al") + (("al_bounds_1", "al_bounds_B") if a.bounds else ()) + (("al_bounds_B_state_B",) if a.state else ()) + (("al_knot_B", "al_knot_B_state_knot_B") if a.knot else ()) + (("al_knot_B_task_B",) if a.task else ())
     ms = {m: {"quadratics": [], "total_cost": [], "solve": [], "quadratics_per_launch_in_solve": []} for m in modes}
     for m in modes[1:]:
         ms[m]["update"] = []
     record = sv.al_default_bounds(al["margin"])
     state_record = np.concatenate([np.full(sv.AL_STATE_COORDS, -1e3), np.full(sv.AL_STATE_COORDS, 1e3)])
+    task_row = np.concatenate([np.full(sv.AL_TASK_COORDS, -1e3), np.full(sv.AL_TASK_COORDS, 1e3)])
 
     def timed(fn, calls):
         fn()
@@ -84,9 +90,14 @@ def main():
                     s.set_al_state_knot_bounds(np.tile(state_record, (B, N + 1, 1)), 2 * prob["w_joint"], 0.0)
                 else:
                     s.clear_al_state_bounds()
+                if m == "al_knot_B_task_B":
+                    s.set_al_task_bounds(np.tile(task_row, (B, N + 1, 1)), 2 * prob["w_joint"], 0.0)
+                else:
+                    s.clear_al_task_bounds()
+                assert s.num_al_task_bound_sets() == (B if "task" in m else 0)
                 assert s.num_al_bound_sets() == (0 if m == "al" else 1 if m == "al_bounds_1" else B)
                 assert s.num_al_state_bound_sets() == (B if "state" in m else 0)
-                assert s.al_bounds_per_knot() == {"al_knot_B": 1, "al_knot_B_state_knot_B": 3}.get(m, 0)
+                assert s.al_bounds_per_knot() == {"al_knot_B": 1, "al_knot_B_state_knot_B": 3, "al_knot_B_task_B": 1}.get(m, 0)
             s.initialize(x0, ui)
             s.enable_profiling(True)
             t0 = time.perf_counter(); s.solve(None); dt = 1e3 * (time.perf_counter() - t0)
