@@ -266,7 +266,8 @@ int ilqr_hip_get_al_knot_bounds(ilqr_hip_ctx* ctx, double* joint_ctrl /*[B][N+1]
 int ilqr_hip_al_bounds_per_knot(const ilqr_hip_ctx* ctx);
 /* A bounds track, cut on the device as the reference windows are (ilqr_hip_set_reference_track): `rows` >= 1 rows on the loop's timeline,
    joint_ctrl [rows][76] and / or state [rows][56] in the field orders above (at least one part; a NULL part is not cut and that family
-   stays as installed).  One upload; the handle owns the copy and a new track replaces it (the starts go back to one shared start of 0).
+   stays as installed).  One upload; the handle owns the copy and a new track replaces it.  Installing a track of either kind (this one or
+   ilqr_hip_set_al_task_bounds_track) sets the start rows, which both kinds share, back to one shared start of 0.
    A state part needs an installed state family (table or window), else ILQR_ERR_STATE: the track supplies the bounds, the installation
    rho_state0 and tol_state.  Validation as for the setters, row by row (ILQR_ERR_ARG; ILQR_ERR_STATE without an augmented Lagrangian;
    ILQR_ERR_UNSUPPORTED without the module).  Synchronises the handle's stream. */
@@ -276,15 +277,18 @@ int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* ctx);
 /* Rows of the installed bounds track; 0 without one, -1 for a null handle */
 int ilqr_hip_al_bounds_track_rows(const ilqr_hip_ctx* ctx);
 /* One start row per set, kept on the device: n_sets is 1 (one start for every rollout) or the batch; every start >= 0 (ILQR_ERR_ARG).
-   Default: one shared start of 0.  ILQR_ERR_STATE without a bounds track. */
+   Default: one shared start of 0.  One start buffer on the handle serves the bounds track and the task bounds track: the call is accepted
+   while either is installed, ILQR_ERR_STATE without both. */
 int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* ctx, const int* start /*[n_sets]*/, int n_sets);
 /* Enqueues one kernel on the handle's stream (al_bounds_track_kernels.hip), no upload, no synchronisation: for set b and t = 0..N it writes
    row min(start[b] + step + t, rows - 1) of each part of the track into row t of set b's window of that part -- the end clamp of x_ref.  A
    pure copy: the windows are bit for bit what the knot setters would upload, and afterwards the handle is in the state those setters
    leave, with n_sets equal to the number of starts (multipliers and penalties untouched).  Where that state differs from the one before --
    the first cut, or after other starts -- and the other family has no window, the same call also enqueues the copy that repeats that
-   family's record over the knots.  step >= 0, else ILQR_ERR_ARG.  ILQR_ERR_STATE without an augmented Lagrangian, without a track, or with
-   a state part while no state family is installed. */
+   family's record over the knots.  The same ONE kernel cuts the task bounds track (ilqr_hip_set_al_task_bounds_track) when that is
+   installed: window row t of set b is row min(start[b] + step + t, rows_task - 1) of it.  step >= 0, else ILQR_ERR_ARG.  ILQR_ERR_STATE
+   without an augmented Lagrangian, without a track of either kind, with a state part while no state family is installed, or with a task
+   track while no task family is. */
 int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* ctx, int step);
 /* Augmented-Lagrangian bounds on POINTS of the robot, the task family: nine task coordinates k = 0..8 in the world frame -- the whole-body
    centre of mass x, y, z (k = 0..2), the left ankle origin (k = 3..5) and the right ankle origin (k = 6..8): the points the cost tracks
@@ -318,7 +322,8 @@ int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* ctx, int step);
    ilqr_hip_set_al_multipliers, the other families coming and going and a repeated ilqr_hip_set_augmented_lagrangian;
    ilqr_hip_clear_augmented_lagrangian drops it.  The cold initialisers zero the task multipliers and reset rho_task; the warm ones shift
    them by the knots the trajectory is shifted by (zero tail, knot 0 zero) and reset rho_task.  The refusals of
-   ilqr_hip_set_augmented_lagrangian (cross-check families, weight sets) stay as they are.  The bounds track does not cut this family. */
+   ilqr_hip_set_augmented_lagrangian (cross-check families, weight sets) stay as they are.  ilqr_hip_set_al_bounds_track does not cut this
+   family; a track of its own does (ilqr_hip_set_al_task_bounds_track). */
 #define ILQR_AL_TASK_COORDS 9
 #define ILQR_AL_TASK_BOUNDS 18
 int ilqr_hip_set_al_task_bounds(ilqr_hip_ctx* ctx, const double* bounds /*[n_sets][N+1][18]*/, int n_sets, double rho_task0, double tol_task);
@@ -346,6 +351,21 @@ int ilqr_hip_get_al_task_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][2]*/
    Lagrangian (ILQR_ERR_STATE) and an initialised trajectory (ILQR_ERR_STATE), not a task window; ILQR_ERR_UNSUPPORTED without the module.
    Synchronises the handle's stream. */
 int ilqr_hip_get_al_task_points(ilqr_hip_ctx* ctx, double* out /*[B][N+1][9]*/);
+/* The task family's part of the bounds track: `rows` >= 1 rows lo[9], hi[9] on the loop's timeline over the task coordinates above, with a
+   row count of its own, independent of ilqr_hip_set_al_bounds_track's (on the device a row is padded to 32 doubles, two whole lines).  One
+   upload; the handle owns the copy and a new task track replaces it.  ilqr_hip_al_bounds_window_from_track cuts every installed part in one
+   kernel; afterwards the handle is in the state ilqr_hip_set_al_task_bounds(the same window cut on the host, n_sets = the number of starts)
+   leaves, multipliers and penalties untouched; the stance rule is unchanged (the kernels keep reading the schedule window).  The track
+   supplies bounds only: rho_task0 and tol_task stay the installation's.  The start rows are the ones ilqr_hip_set_al_bounds_track_starts
+   sets, shared with the other track; installing either track sets them back to one shared start of 0.
+   Validation row by row as in the window setter (ILQR_ERR_ARG: a null pointer, rows < 1, a NaN, lo > hi, lo == +inf, hi == -inf).
+   ILQR_ERR_STATE without an augmented Lagrangian or without an installed task family.  ILQR_ERR_UNSUPPORTED without the module.  A refused
+   call leaves what was installed as it was.  Synchronises the handle's stream. */
+int ilqr_hip_set_al_task_bounds_track(ilqr_hip_ctx* ctx, int rows, const double* task /*[rows][18]*/);
+/* Frees the task track; the window last written stays installed.  Synchronises the handle's stream. */
+int ilqr_hip_clear_al_task_bounds_track(ilqr_hip_ctx* ctx);
+/* Rows of the installed task bounds track; 0 without one, -1 for a null handle */
+int ilqr_hip_al_task_bounds_track_rows(const ilqr_hip_ctx* ctx);
 /* RobotUtils::setGravity -- src/common/robot_utils.cpp:782-789 */
 int ilqr_hip_set_gravity(ilqr_hip_ctx* ctx, double gx, double gy, double gz);
 /* RobotUtils::loadContactSchedule / isStance -- src/common/robot_utils.cpp:445-504; horizon-local rows 0..N
@@ -634,6 +654,37 @@ int ilqr_hip_plant_set_score(ilqr_hip_ctx* ctx, const double* Q_diag /*[51]*/, c
 int ilqr_hip_plant_clear_score(ilqr_hip_ctx* ctx);
 int ilqr_hip_plant_get_score(ilqr_hip_ctx* ctx, double* score /*[B][8]*/);
 int ilqr_hip_plant_score_device(ilqr_hip_ctx* ctx, const double** score_device);
+/* ---- task score of the plant: did the TRUE trajectory obey the task bounds (ilqr_hip_set_al_task_bounds) -- did the foot clear the floor,
+   land on the stone, did the centre of mass stay over the box -- under every way the plant can differ from the solver's model.  While it is
+   installed every ilqr_hip_plant_advance / ilqr_hip_plant_follow is followed, on the same stream, by two small kernels (behind the cost
+   score's when both are installed).  For interval j of the call they read the state row the plant appended to the history ring and score
+   it against row k of the task window the handle currently holds, whoever wrote it (a setter or ilqr_hip_al_bounds_window_from_track):
+   k = 0 for ilqr_hip_plant_advance, first_knot + j for ilqr_hip_plant_follow.  The stance flags are those of schedule row k, each rollout
+   its own set where the sets are per rollout.
+   With p the nine points of that state -- the doubles ilqr_hip_get_al_task_points and the solver's kernels form -- the violation of task
+   coordinate i is v_i = max(0, p_i - hi_i, lo_i - p_i), written as compares: an infinite side never counts, and a foot's three rows are off
+   where the schedule has that foot in stance (the solver's rule: a standing foot below a clearance floor scores nothing).  Groups g = CoM,
+   left foot, right foot; V_g = max of v_i over the group.  The record, ILQR_PLANT_TASK_SCORE_TERMS doubles per rollout:
+     0, 1, 2  maximum of V_g over the scored intervals, in metres; 0 before the first interval
+     3, 4, 5  number of intervals with V_g > tol, as doubles
+     6        sum over intervals and coordinates of v_i^2
+     7        number of intervals scored, as a double
+   An interval with a non-finite point adds NaN to slot 6, is counted in slot 7, is left out of slots 0..5 and touches no other rollout.
+   The record is a pure function of ring rows, window rows, schedule rows and tol, accumulated without atomics in interval order:
+   ilqr_hip_plant_follow(0, m) and m calls (j, 1) give the same record bit for bit.
+   Ring requirement: the score kernels read the ring, so with a score installed a plant call whose intervals exceed the ring's rows (no
+   ring at all; count > rows) returns ILQR_ERR_STATE before anything is launched or counted.  So does a plant call while the task score is
+   installed and no task family is.
+   set_task_score: tol >= 0 and finite (ILQR_ERR_ARG); installs and empties the record (again: empties it again); synchronises the handle's
+   stream.  ilqr_hip_plant_reset empties the record too.  clear_task_score: frees it; the plant calls then launch exactly what they launch
+   without it.  get_task_score: score[B][8], synchronises; task_score_device: the record as a device pointer, no synchronisation; both
+   ILQR_ERR_STATE while none is installed.  Independent of ilqr_hip_plant_set_score: either, both or neither.  Physics, the cost score, the
+   solver and the observation path are untouched: the score reads the truth. */
+#define ILQR_PLANT_TASK_SCORE_TERMS 8
+int ilqr_hip_plant_set_task_score(ilqr_hip_ctx* ctx, double tol);
+int ilqr_hip_plant_clear_task_score(ilqr_hip_ctx* ctx);
+int ilqr_hip_plant_get_task_score(ilqr_hip_ctx* ctx, double* score /*[B][8]*/);
+int ilqr_hip_plant_task_score_device(ilqr_hip_ctx* ctx, const double** score_device);
 /* ---- the plant's own model and one parameter set per rollout: closed loops in which the plant is NOT the solver's model.  By default the
    plant steps with the handle's dynamics -- a loop in which the model is perfect; the reference's plant, mj_step, is not its solver's model
    either (main/humanoid_mpc.cpp:99-118 builds the two separately).  Both calls below change what ilqr_hip_plant_advance / _follow step

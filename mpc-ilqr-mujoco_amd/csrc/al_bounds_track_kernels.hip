@@ -4,7 +4,7 @@
 //   k_al_bounds_expand             one workgroup per set: one record repeated over the N + 1 rows of the set's window (what the library does to
 //                                  a whole-horizon record of one family while the other family has a window).
 // Both are pure copies -- no arithmetic on a value -- so the windows are bit for bit what the host setters upload.  Track rows and window
-// rows are whole 128-byte lines (80 or 64 doubles, 128-byte aligned: h1_cost_dev.h ALB_STRIDE, ALSB_STRIDE): the copy runs in 16-byte
+// rows are whole 128-byte lines (80, 64 or 32 doubles, 128-byte aligned: h1_cost_dev.h ALB_STRIDE, ALSB_STRIDE, al_task_dev.h ALTB_STRIDE): the copy runs in 16-byte
 // pieces, consecutive lanes on consecutive pieces, so that eight lanes write one line and a wave eight whole lines per store instruction.
 // A translation unit of its own: no kernel of the solve or of the plant shares a compilation with it.  Linked into libilqr_hip_alknot.so
 // (csrc/Makefile; ilqr_kernels.h AlKnotModule), not into the library: ilqr_capi.hip calls the two entry points at the end of this file.
@@ -40,6 +40,7 @@ __global__ void __launch_bounds__(ABT_THREADS) k_al_bounds_window_from_track(AlB
   const long s = (long)start[b] + step;
   if (T.joint_ctrl && Wd.joint_ctrl) cut_bound_rows<80>(Wd.joint_ctrl + b * n1 * 80, T.joint_ctrl, s, T.rows, N + 1, tid);
   if (T.state && Wd.state) cut_bound_rows<64>(Wd.state + b * n1 * 64, T.state, s, T.rows, N + 1, tid);
+  if (T.task && Wd.task) cut_bound_rows<32>(Wd.task + b * n1 * 32, T.task, s, T.rows_task, N + 1, tid);
 }
 
 // the same copy from a "track" of one row: every window row is the set's record

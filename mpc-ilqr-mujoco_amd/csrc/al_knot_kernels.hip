@@ -25,11 +25,14 @@ void ilqr_alknot_module_expand(const double* rec, long rec_stride, double* win, 
 void ilqr_alknot_module_task_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st);
 void ilqr_alknot_module_task_shift(const ilqr::AlDev* A, int B, int N, int shift, hipStream_t st);
 void ilqr_alknot_module_task_points(const ilqr::DevState* S, double* out, hipStream_t st);
+// plant_task_score_kernels.hip of this module
+void ilqr_alknot_module_plant_task_score(const ilqr::PlantTaskScoreDev* T, int B, const double* hist_x, long hist_row0, long hist_cap, int knot0, int count, double* terms, double* record, hipStream_t st);
 // the one symbol the library resolves: the table of the module's entry points (ilqr_kernels.h AlKnotModule)
 const ilqr::AlKnotModule* ilqr_alknot_module() {
   static const ilqr::AlKnotModule table = {ilqr_alknot_module_knot_cost, ilqr_alknot_module_state_knot_cost, ilqr_alknot_module_cost_quadratics,
                                            ilqr_alknot_module_al_update, ilqr_alknot_module_window_from_track, ilqr_alknot_module_expand,
-                                           ilqr_alknot_module_task_knot_cost, ilqr_alknot_module_task_shift, ilqr_alknot_module_task_points};
+                                           ilqr_alknot_module_task_knot_cost, ilqr_alknot_module_task_shift, ilqr_alknot_module_task_points,
+                                           ilqr_alknot_module_plant_task_score};
   return &table;
 }
 }

@@ -22,6 +22,7 @@
 #include "plant_plan.h"
 #include "solve_order.h"
 #include "plant_score_kernels.h"
+#include "plant_task_score_kernels.h"
 #include "reference_track_kernels.h"
 #include "al_bounds_track_kernels.h"
 
@@ -100,7 +101,7 @@ struct ilqr_hip_ctx {
   // Augmented Lagrangian (ilqr_hip_set_augmented_lagrangian): installed while P.al points at al.jc.store; every buffer is kept by the handle once
   // allocated and freed by ilqr_hip_destroy.  Which pointers ProblemDev / AlDev get from all this: al_point_bounds, by the plan of al_plan.h.
   // One record per family of bounds -- jc the hinges and actuators (ilqr_hip_set_al_bounds ...), st the 28 box coordinates
-  // (ilqr_hip_set_al_state_bounds ...), tk the nine task coordinates (ilqr_hip_set_al_task_bounds: a window always, no table, no track) -- which the bodies behind the two families' entry points take as their parameter:
+  // (ilqr_hip_set_al_state_bounds ...), tk the nine task coordinates (ilqr_hip_set_al_task_bounds: a window always, no table; a track of its own, ilqr_hip_set_al_task_bounds_track) -- which the bodies behind the two families' entry points take as their parameter:
   struct AlFamily {
     int fields, width;        // doubles of a bounds record in the interface (76 / 56) and on the device (ALB_STRIDE / ALSB_STRIDE)
     int blocks, per;          // a bounds record is `blocks` blocks of lo[per], hi[per] (2 x 19 / 1 x 28); so is a knot's multiplier record:
@@ -124,9 +125,10 @@ struct ilqr_hip_ctx {
     AlFamily st{ILQR_AL_STATE_BOUNDS, h1::ALSB_STRIDE, 1, ILQR_AL_STATE_COORDS, h1::ALS_KNOT, {h1::ALS_LO, 0}};
     AlFamily tk{ILQR_AL_TASK_BOUNDS, h1::ALTB_STRIDE, 1, ILQR_AL_TASK_COORDS, h1::ALT_KNOT, {h1::ALT_LO, 0}};
     double* model = nullptr;  // [ALB_STRIDE] the model's bounds at the installed margin as one record (AlPlan::upload_model)
-    // the bounds track (ilqr_hip_set_al_bounds_track; the families' `track`): its start rows [B] on the device, allocated with the first track
+    // the bounds tracks (ilqr_hip_set_al_bounds_track: jc and st `track`, track_rows; ilqr_hip_set_al_task_bounds_track: tk `track`,
+    // task_track_rows): the start rows [B] on the device that both share, allocated with the first track of either kind
     int* track_start = nullptr;
-    int track_rows = 0, track_sets = 1;
+    int track_rows = 0, track_sets = 1, task_track_rows = 0;
   } al;
   // scratch
   double *d_tmpx = nullptr, *d_tmpu = nullptr, *d_prevx = nullptr, *d_prevu = nullptr, *d_u0 = nullptr, *d_K0 = nullptr, *d_cost_tmp = nullptr;
@@ -266,6 +268,9 @@ struct ilqr_hip_ctx {
   // [N][B][8] and the scoring weights (Q, R, upright, balance, joint limits, control limits), all independent of P's and of the weight sets
   double *d_score = nullptr, *d_score_terms = nullptr;
   bool score_on = false;
+  // task score of the plant (ilqr_hip_plant_set_task_score; plant_task_score_kernels.hip in the per-knot module): the record [B][8], the term
+  // rows of one plant call [N][B][8], the tolerance of the counts; installed while d_tscore is set
+  double *d_tscore = nullptr, *d_tscore_terms = nullptr, tscore_tol = 0.0;
   double score_Q[ILQR_NX] = {0}, score_R[ILQR_NU] = {0}, score_w[4] = {0};
   // reference track (ilqr_hip_set_reference_track; reference_track_kernels.hip): ONE allocation [rows][51 | 19 | 3 | 6 | 3] doubles array by
   // array, then [contact_rows][2] ints; the start rows [B] on the device (allocated with the first track) and their maximum here, for the
@@ -589,7 +594,7 @@ __attribute__((minsize)) int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   if (c->al.ev) hipEventDestroy(c->al.ev);
   if (c->twin) { void* tw[] = {c->T.K, c->T.kff, c->T.Vx, c->T.Vxx, c->T.xcand, c->T.ucand, c->T.cand_cost, c->T.cand_knot, c->T.lambda, c->d_spec_gate}; for (void* p : tw) if (p) hipFree(p); }
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate, S.kr, S.kr_n, S.ls_list, S.ls_kind, c->d_lgate}; for (void* p : gp) if (p) hipFree(p); }
-  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
+  { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_tscore, c->d_tscore_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
   for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints, &c->terrain}) if (t->d) hipFree(t->d);
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
@@ -976,43 +981,55 @@ int ilqr_hip_al_update(ilqr_hip_ctx* c, int round) {
   return ILQR_OK;
 }
 
-// ---- the bounds track
+// ---- the bounds tracks: the joint / torque and state parts (one row count) and the task part (a row count of its own); one body per
+// operation, `task` naming the kind.  The start rows are shared
 static const char* const AL_TRACK_STATE_ERR = "the track's state part needs an installed state family";
+static const char* const AL_TRACK_TASK_ERR = "the task track needs an installed task family";
 static const char* const AL_NO_TRACK_ERR = "no bounds track installed";
 // (behind a synchronisation: a window kernel in flight still reads the track)
-__attribute__((noinline)) static void al_track_free(ilqr_hip_ctx* c) {
-  for (AlFamily* f : {&c->al.jc, &c->al.st}) { if (f->track) hipFree(f->track); f->track = nullptr; }
-  c->al.track_rows = 0; c->al.track_sets = 1;
+__attribute__((noinline, minsize)) static int al_track_free(ilqr_hip_ctx* c, bool task) {
+  if (!c) return ILQR_ERR_ARG;
+  enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (AlFamily* f : {&c->al.jc, &c->al.st, &c->al.tk}) if ((f == &c->al.tk) == task) { if (f->track) hipFree(f->track); f->track = nullptr; }
+  (task ? c->al.task_track_rows : c->al.track_rows) = 0;
+  if (!c->al.track_rows && !c->al.task_track_rows) c->al.track_sets = 1;
+  return ILQR_OK;
 }
-__attribute__((minsize)) int ilqr_hip_set_al_bounds_track(ilqr_hip_ctx* c, int rows, const double* joint_ctrl, const double* state) {
+// part[3]: the joint / torque, state and task rows; the parts of the other kind are null
+__attribute__((noinline, minsize)) static int al_track_install(ilqr_hip_ctx* c, int rows, const double* const part[3], bool task) {
   if (!c) return ILQR_ERR_ARG;
   TRY(al_installed(c));
-  if (rows < 1 || (!joint_ctrl && !state) || (joint_ctrl && !al_bounds_ok(c->al.jc, joint_ctrl, rows)) || (state && !al_bounds_ok(c->al.st, state, rows))) return ILQR_ERR_ARG;
-  if (state && !c->al.st.sets) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
+  AlFamily* const fam[3] = {&c->al.jc, &c->al.st, &c->al.tk};
+  if (rows < 1 || (!part[0] && !part[1] && !part[2])) return ILQR_ERR_ARG;
+  for (int i = 0; i < 3; ++i) if (part[i] && !al_bounds_ok(*fam[i], part[i], rows)) return ILQR_ERR_ARG;
+  for (int i = 1; i < 3; ++i) if (part[i] && !fam[i]->sets) { c->err = i == 1 ? AL_TRACK_STATE_ERR : AL_TRACK_TASK_ERR; return ILQR_ERR_STATE; }
   enter(c);
   TRY(al_knot_ready(c));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  al_track_free(c);
+  TRY(al_track_free(c, task));
   if (!c->al.track_start) TRY(dalloc(c, &c->al.track_start, (size_t)c->B));
   HIPCHK(c, hipMemsetAsync(c->al.track_start, 0, (size_t)c->B * sizeof(int), c->stream));      // one shared start of 0
-  const struct { AlFamily& f; const double* src; } parts[2] = {{c->al.jc, joint_ctrl}, {c->al.st, state}};
-  for (const auto& v : parts) if (v.src) { TRY(dalloc(c, &v.f.track, (size_t)rows * v.f.width)); TRY(upload_rows(c, v.f.track, v.src, rows, v.f.fields, v.f.width)); }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->al.track_rows = rows;
+  c->al.track_sets = 1;
+  for (int i = 0; i < 3; ++i) if (part[i]) { TRY(dalloc(c, &fam[i]->track, (size_t)rows * fam[i]->width)); TRY(upload_rows(c, fam[i]->track, part[i], rows, fam[i]->fields, fam[i]->width)); }
+  (task ? c->al.task_track_rows : c->al.track_rows) = rows;
   return ILQR_OK;
 }
-__attribute__((minsize)) int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* c) {
-  if (!c) return ILQR_ERR_ARG;
-  enter(c);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  al_track_free(c);
-  return ILQR_OK;
+int ilqr_hip_set_al_bounds_track(ilqr_hip_ctx* c, int rows, const double* joint_ctrl, const double* state) {
+  const double* const part[3] = {joint_ctrl, state, nullptr};
+  return al_track_install(c, rows, part, false);
 }
+int ilqr_hip_set_al_task_bounds_track(ilqr_hip_ctx* c, int rows, const double* task) {
+  const double* const part[3] = {nullptr, nullptr, task};
+  return al_track_install(c, rows, part, true);
+}
+int ilqr_hip_clear_al_bounds_track(ilqr_hip_ctx* c) { return al_track_free(c, false); }
+int ilqr_hip_clear_al_task_bounds_track(ilqr_hip_ctx* c) { return al_track_free(c, true); }
 int ilqr_hip_al_bounds_track_rows(const ilqr_hip_ctx* c) { return c ? c->al.track_rows : -1; }
+int ilqr_hip_al_task_bounds_track_rows(const ilqr_hip_ctx* c) { return c ? c->al.task_track_rows : -1; }
 __attribute__((minsize)) int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* c, const int* start, int n_sets) {
   if (!c || !start || check_sets(c, n_sets)) return ILQR_ERR_ARG;
   for (int b = 0; b < n_sets; ++b) if (start[b] < 0) return ILQR_ERR_ARG;
-  if (!c->al.track_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
+  if (!c->al.track_rows && !c->al.task_track_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
   enter(c);
   HIPCHK(c, hipMemcpyAsync(c->al.track_start, start, (size_t)n_sets * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1022,17 +1039,18 @@ __attribute__((minsize)) int ilqr_hip_set_al_bounds_track_starts(ilqr_hip_ctx* c
 __attribute__((minsize)) int ilqr_hip_al_bounds_window_from_track(ilqr_hip_ctx* c, int step) {
   if (!c || step < 0) return ILQR_ERR_ARG;
   TRY(al_installed(c));
-  if (!c->al.track_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
+  if (!c->al.track_rows && !c->al.task_track_rows) { c->err = AL_NO_TRACK_ERR; return ILQR_ERR_STATE; }
   if (c->al.st.track && !c->al.st.sets) { c->err = AL_TRACK_STATE_ERR; return ILQR_ERR_STATE; }
+  if (c->al.tk.track && !c->al.tk.sets) { c->err = AL_TRACK_TASK_ERR; return ILQR_ERR_STATE; }
   enter(c);
   const int n_sets = c->al.track_sets;
-  const ilqr::AlBoundsTrackDev T{c->al.jc.track, c->al.st.track, c->al.track_rows};
-  const ilqr::AlBoundsWindowDev W{c->al.jc.window, c->al.st.window};
+  const ilqr::AlBoundsTrackDev T{c->al.jc.track, c->al.st.track, c->al.track_rows, c->al.tk.track, c->al.task_track_rows};
+  const ilqr::AlBoundsWindowDev W{c->al.jc.window, c->al.st.window, c->al.tk.window};
   ilqr::g_al_knot.window_from_track(&T, &W, c->al.track_start, n_sets, step, c->N, c->stream);
   HIPCHK(c, hipGetLastError());
   // the state the knot setters leave; the pointers move only where that state changes (the first cut, or other starts)
   bool same = c->P.alb_knot != 0;
-  for (AlFamily* f : {&c->al.jc, &c->al.st}) if (f->track) { same = same && f->knot && f->sets == n_sets; f->knot = true; f->sets = n_sets; }
+  for (AlFamily* f : {&c->al.jc, &c->al.st, &c->al.tk}) if (f->track) { same = same && f->knot && f->sets == n_sets; f->knot = true; f->sets = n_sets; }
   return same ? ILQR_OK : al_point_bounds(c);      // asynchronous on the handle's stream
 }
 
@@ -2250,6 +2268,12 @@ int ilqr_hip_get_stance(ilqr_hip_ctx* c, int* stance) {
   return ILQR_OK;
 }
 // ---------------------------------------------------------------- device-resident plant (plant_kernels.hip)
+// the task score's record before the first scored interval: zeros (nothing to do while none is installed); returns behind the stream
+__attribute__((noinline, minsize)) static int task_score_empty(ilqr_hip_ctx* c) {
+  if (c->d_tscore) HIPCHK(c, hipMemsetAsync(c->d_tscore, 0, (size_t)c->B * ILQR_PLANT_TASK_SCORE_TERMS * sizeof(double), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ILQR_OK;
+}
 // the record of ilqr_hip_plant_set_score before the first scored interval: sums and count zero, minimum height +inf (empty while no score is installed)
 static std::vector<double> empty_score(const ilqr_hip_ctx* c) {
   std::vector<double> r(c->score_on ? (size_t)c->B * ILQR_PLANT_SCORE_TERMS : 0, 0.0);
@@ -2260,11 +2284,28 @@ static std::vector<double> empty_score(const ilqr_hip_ctx* c) {
 // behind it on the handle's stream: the score kernels see the reference buffers that kernel saw.  Their problem descriptor is the handle's
 // with the scoring weights in the place of the shared ones and no weight-set table.
 static void enqueue_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
+  if (!c->score_on) return;
   h1::ProblemDev Ps = c->P;
   std::memcpy(Ps.Q, c->score_Q, sizeof(Ps.Q)); std::memcpy(Ps.R, c->score_R, sizeof(Ps.R));
   Ps.w_upright = c->score_w[0]; Ps.w_balance = c->score_w[1]; Ps.w_joint = c->score_w[2]; Ps.w_ctrl = c->score_w[3];
   Ps.wsets = nullptr; Ps.wsets_stride = 0; Ps.al = nullptr; Ps.al_stride = 0; Ps.alb = nullptr; Ps.alb_stride = 0; Ps.als = nullptr; Ps.als_stride = 0; Ps.alsb = nullptr; Ps.alsb_stride = 0; Ps.alb_knot = 0; Ps.alsb_knot = 0; Ps.altb = nullptr;
   ilqr::launch_plant_score(Ps, c->B, c->plant.hist_x, c->plant.hist_u, row0, c->hist_cap, knot0, count, c->d_score_terms, c->d_score, c->stream);
+}
+// What a plant call of `count` intervals needs while a score of either kind is installed, checked before anything is launched or counted: the
+// ring rows the score kernels read, and for the task score (ilqr_hip_plant_set_task_score) a task window to score against
+__attribute__((noinline, minsize)) static int plant_scores_ready(ilqr_hip_ctx* c, int count) {
+  if ((c->score_on || c->d_tscore) && count > c->hist_cap) {
+    c->err = "plant call with a score installed: " + std::to_string(count) + " intervals exceed the history ring's " + std::to_string(c->hist_cap) + " rows (ilqr_hip_plant_set_history: the score kernels read the ring's rows)";
+    return ILQR_ERR_STATE;
+  }
+  if (c->d_tscore && !c->P.altb) { c->err = "plant call with a task score installed and no task family"; return ILQR_ERR_STATE; }
+  return ILQR_OK;
+}
+// the same for the task score, behind the cost score's kernels: the rows knot0 + j of the task window and of the schedule the handle holds now
+static void enqueue_task_score(ilqr_hip_ctx* c, long row0, int knot0, int count) {
+  if (!c->d_tscore) return;
+  const ilqr::PlantTaskScoreDev T{c->P.altb, c->P.altb_stride, c->P.altb_knot, c->P.stance, c->P.stance_stride, c->tscore_tol};
+  ilqr::g_al_knot.plant_task_score(&T, c->B, c->plant.hist_x, row0, c->hist_cap, knot0, count, c->d_tscore_terms, c->d_tscore, c->stream);
 }
 // The plant's dynamics parameters: the handle's at the physics step (main/humanoid_mpc.cpp:99,128), under the plant's own contact mode and
 // joint-limit option where ilqr_hip_plant_set_model has given it one.  (With a parameter table the kernels replace g, mu, soft and lim_k per rollout.)
@@ -2398,7 +2439,7 @@ int ilqr_hip_plant_reset(ilqr_hip_ctx* c, const double* x) {
   HIPCHK(c, hipMemsetAsync(c->plant.stance, 0, B * 2 * sizeof(int), c->stream));
   const std::vector<double> empty = empty_score(c);      // (outlives the copy: the synchronisation below)
   if (c->score_on) HIPCHK(c, hipMemcpyAsync(c->d_score, empty.data(), empty.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's buffers are free on return)
+  TRY(task_score_empty(c));      // (synchronises: the caller's buffers are free on return)
   c->plant_set = true; c->plant_kick = false; c->hist_n = 0; c->plant_intervals = 0;
   c->act_substeps = 0;      // (the actuator's state is primed again by the next substep)
   return ILQR_OK;
@@ -2431,13 +2472,14 @@ int ilqr_hip_plant_advance(ilqr_hip_ctx* c) {
   if (geom) {      // (the contact mode or the family may have changed since plant_configure)
     if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
-  if (c->score_on && c->hist_cap < 1) { c->err = "plant_advance with a score installed needs a history ring (ilqr_hip_plant_set_history): the score kernels read the ring's rows"; return ILQR_ERR_STATE; }
+  TRY(plant_scores_ready(c, 1));
   const ilqr::PlantPlan plan = plant_plan_of(c, false);
   TRY(prepare_plant(c, plan));
   const h1::DynParams dyn = plant_dyn(c);
   const long row = c->hist_cap > 0 ? c->hist_n % c->hist_cap : -1L;
   enqueue_plant(c, plan, dyn, geom ? 1 : 0, 0, 1, row);
-  if (c->score_on) enqueue_score(c, row, 0, 1);
+  enqueue_score(c, row, 0, 1);
+  enqueue_task_score(c, row, 0, 1);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
   c->plant_intervals += 1;
@@ -2467,16 +2509,14 @@ int ilqr_hip_plant_follow(ilqr_hip_ctx* c, int first_knot, int count) {
   if (geom) {      // (as ilqr_hip_plant_advance)
     if (const char* why = plant_geometry_refusal(c, c->plant_mode)) { c->err = why; return ILQR_ERR_UNSUPPORTED; }
   }
-  if (c->score_on && count > c->hist_cap) {
-    c->err = "plant_follow with a score installed: " + std::to_string(count) + " intervals exceed the history ring's " + std::to_string(c->hist_cap) + " rows (the score kernels read the ring's rows)";
-    return ILQR_ERR_STATE;
-  }
+  TRY(plant_scores_ready(c, count));
   const ilqr::PlantPlan plan = plant_plan_of(c, true);
   TRY(prepare_plant(c, plan));
   const h1::DynParams dyn = plant_dyn(c);
   const long row0 = c->hist_cap > 0 ? c->hist_n % c->hist_cap : 0L;
   enqueue_plant(c, plan, dyn, geom ? 1 : 0, first_knot, count, row0);
-  if (c->score_on) enqueue_score(c, row0, first_knot, count);
+  enqueue_score(c, row0, first_knot, count);
+  enqueue_task_score(c, row0, first_knot, count);
   HIPCHK(c, hipGetLastError());
   c->plant_kick = false;
   c->plant_intervals += count;
@@ -2982,29 +3022,46 @@ __attribute__((minsize)) int ilqr_hip_plant_set_score(ilqr_hip_ctx* c, const dou
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
-int ilqr_hip_plant_clear_score(ilqr_hip_ctx* c) {
-  if (!c) return ILQR_ERR_ARG;
+// one body per operation for the two records (the cost score's and the task score's: [B][8] each, installed while `rec` is set)
+static_assert(ILQR_PLANT_TASK_SCORE_TERMS == ILQR_PLANT_SCORE_TERMS && PLANT_TASK_SCORE_TERMS == ILQR_PLANT_TASK_SCORE_TERMS, "both records are [B][8]");
+__attribute__((noinline, minsize)) static int score_free(ilqr_hip_ctx* c, double** rec, double** terms) {
   enter(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));      // (score kernels in flight still write the buffers)
-  if (c->d_score) hipFree(c->d_score);
-  if (c->d_score_terms) hipFree(c->d_score_terms);
-  c->d_score = c->d_score_terms = nullptr; c->score_on = false;
+  if (*rec) hipFree(*rec);
+  if (*terms) hipFree(*terms);
+  *rec = *terms = nullptr;
   return ILQR_OK;
 }
-int ilqr_hip_plant_get_score(ilqr_hip_ctx* c, double* score) {
-  if (!c || !score) return ILQR_ERR_ARG;
-  if (!c->score_on) return ILQR_ERR_STATE;
+// out: the record on the host (synchronises), or dev: its device pointer
+__attribute__((noinline, minsize)) static int score_read(ilqr_hip_ctx* c, const double* rec, double* out, const double** dev) {
+  if (!out && !dev) return ILQR_ERR_ARG;
+  if (!rec) return ILQR_ERR_STATE;
+  if (dev) { *dev = rec; return ILQR_OK; }
   enter(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(score, c->d_score, (size_t)c->B * ILQR_PLANT_SCORE_TERMS * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, rec, (size_t)c->B * ILQR_PLANT_SCORE_TERMS * sizeof(double), hipMemcpyDeviceToHost));
   return ILQR_OK;
 }
-int ilqr_hip_plant_score_device(ilqr_hip_ctx* c, const double** score_device) {
-  if (!c || !score_device) return ILQR_ERR_ARG;
-  if (!c->score_on) return ILQR_ERR_STATE;
-  *score_device = c->d_score;
-  return ILQR_OK;
+int ilqr_hip_plant_clear_score(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  c->score_on = false;
+  return score_free(c, &c->d_score, &c->d_score_terms);
 }
+int ilqr_hip_plant_get_score(ilqr_hip_ctx* c, double* score) { return c ? score_read(c, c->score_on ? c->d_score : nullptr, score, nullptr) : ILQR_ERR_ARG; }
+int ilqr_hip_plant_score_device(ilqr_hip_ctx* c, const double** score_device) { return c ? score_read(c, c->score_on ? c->d_score : nullptr, nullptr, score_device) : ILQR_ERR_ARG; }
+// ---- task score of the plant (plant_task_score_kernels.hip, in the per-knot module)
+__attribute__((minsize)) int ilqr_hip_plant_set_task_score(ilqr_hip_ctx* c, double tol) {
+  if (!c || !(tol >= 0.0) || !std::isfinite(tol)) return ILQR_ERR_ARG;
+  enter(c);
+  const size_t rec = (size_t)c->B * ILQR_PLANT_TASK_SCORE_TERMS;
+  if (!c->d_tscore_terms) TRY(dalloc(c, &c->d_tscore_terms, (size_t)c->N * rec));
+  if (!c->d_tscore) TRY(dalloc(c, &c->d_tscore, rec));
+  c->tscore_tol = tol;      // (kernels of a plant call in flight took their tolerance by value)
+  return task_score_empty(c);
+}
+int ilqr_hip_plant_clear_task_score(ilqr_hip_ctx* c) { return c ? score_free(c, &c->d_tscore, &c->d_tscore_terms) : ILQR_ERR_ARG; }
+int ilqr_hip_plant_get_task_score(ilqr_hip_ctx* c, double* score) { return c ? score_read(c, c->d_tscore, score, nullptr) : ILQR_ERR_ARG; }
+int ilqr_hip_plant_task_score_device(ilqr_hip_ctx* c, const double** score_device) { return c ? score_read(c, c->d_tscore, nullptr, score_device) : ILQR_ERR_ARG; }
 int ilqr_hip_get_iterations_enqueued(const ilqr_hip_ctx* c) { return c ? c->iterations_enqueued : -1; }
 int ilqr_hip_get_adopt_mismatches(ilqr_hip_ctx* c, unsigned long long* count) {
   if (!c || !count) return ILQR_ERR_ARG;

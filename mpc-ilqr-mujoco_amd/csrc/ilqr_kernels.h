@@ -178,6 +178,7 @@ struct AlDev {
 // launchers call them for the per-knot variants of al_variant (al_plan.h), which a handle's pointers name only once the table below is filled (AlPlan::module).
 struct AlBoundsTrackDev;
 struct AlBoundsWindowDev;      // (al_bounds_track_kernels.h)
+struct PlantTaskScoreDev;      // (plant_task_score_kernels.h)
 struct AlKnotModule {
   void (*knot_cost)(const DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, const double* usrc, int cshift, int oshift, const int* gate, hipStream_t st);
   void (*state_knot_cost)(const DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st);
@@ -193,6 +194,8 @@ struct AlKnotModule {
   void (*task_knot_cost)(const DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st);
   void (*task_shift)(const AlDev* A, int B, int N, int shift, hipStream_t st);
   void (*task_points)(const DevState* S, double* out, hipStream_t st);
+  // plant_task_score_kernels.hip: launch_plant_task_score (ilqr_hip_plant_set_task_score).  Appended: nothing above moves
+  void (*plant_task_score)(const PlantTaskScoreDev* T, int B, const double* hist_x, long hist_row0, long hist_cap, int knot0, int count, double* terms, double* record, hipStream_t st);
 };
 extern AlKnotModule g_al_knot;      // (ilqr_capi.hip)
 // masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row

@@ -44,9 +44,11 @@ weights and gravity of `base_problem` and uploads the whole of `refs` as a track
 rollout (`track_starts` [B]; None or one entry: one shared start, 0 by default), and every group calls
 `window_from_track(t_idx, follow_schedule)` where the host path calls problem_at + set_problem -- one kernel, nothing uploaded, no
 synchronisation; rollout b then tracks the rows from track_starts[b] + t_idx on (ReferenceData.problem_at_starts is the same rule on the
-host).  While the solver handle has a bounds track (BatchedILQR.set_al_bounds_track) every solve of either loop also calls
-`al_bounds_window_from_track` with the step index its reference windows use, and `track_starts` feeds that track's start rows as well; without a
-bounds track there is no new call.  MPC_extractReference times the enqueue only.  The logged reference rows come from the host's copy of the rule, for the logged
+host).  While the solver handle has a bounds track of either kind (BatchedILQR.set_al_bounds_track, set_al_task_bounds_track) every solve of
+either loop also calls `al_bounds_window_from_track` with the step index its reference windows use, and `track_starts` feeds the tracks' shared
+start rows as well; without a bounds track there is no new call.  `MPCRunner(..., resident=True, task_score=tol)` installs the task score of the
+plant (BatchedILQR.plant_set_task_score) before the plant is reset: every plant call then scores its intervals against the task window the
+handle holds, and `runner.task_score()` returns the record [B, 8] after `run`.  MPC_extractReference times the enqueue only.  The logged reference rows come from the host's copy of the rule, for the logged
 rollouts alone, and `last_stance0` from the host's contact table (rollout 0).
 
 `MPCRunner(..., resident=True, plant_model=(contact_mode, joint_limits), plant_params=P)` runs closed loops in which the plant is not the
@@ -124,7 +126,7 @@ class MPCRunner:
 
     def __init__(self, solver, refs, base_problem, log_dir=None, log_rollouts=(0,), follow_schedule=False, profile_stages=False, plant_contacts="schedule",
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
-                 device_refs=False, track_starts=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None,
+                 device_refs=False, track_starts=None, task_score=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None,
                  plant_observation=None, observation_seed=0, observation_stream0=0, plant_actuator=None, actuator_seed=0, actuator_stream0=0, plant_joints=None,
                  plant_terrain=None):
         if plant_contacts not in ("schedule", "geometry"):
@@ -133,8 +135,8 @@ class MPCRunner:
             raise ValueError("substeps / feedback_mode need the device-resident plant (resident=True)")
         if int(solve_every) < 1 or (int(solve_every) > 1 and int(solve_every) > solver.N - 1):
             raise ValueError("solve_every must be in 1 .. N - 1")
-        if not resident and (score is not None or history_rows is not None):
-            raise ValueError("score / history_rows need the device-resident plant (resident=True)")
+        if not resident and (score is not None or history_rows is not None or task_score is not None):
+            raise ValueError("score / task_score / history_rows need the device-resident plant (resident=True)")
         if history_rows is not None and int(history_rows) < int(solve_every):
             raise ValueError("history_rows must be at least solve_every (the ring holds the intervals of one plant call)")
         if not resident and (device_refs or track_starts is not None):
@@ -198,6 +200,7 @@ class MPCRunner:
         self.track_starts_given, self.bounds_starts_for = track_starts is not None, None
         self.track_starts = np.zeros(1, dtype=np.int64) if track_starts is None else np.atleast_1d(np.asarray(track_starts)).astype(np.int64)
         self.score_args = None if score is None else dict(score)
+        self.task_score_tol = None if task_score is None else float(task_score)
         self.history_rows = None if history_rows is None else int(history_rows)
         self.resident, self.substeps, self.feedback_mode = bool(resident), int(substeps), int(feedback_mode)
         self.solve_every, self.since_solve = int(solve_every), 1      # since_solve: plant intervals applied since the last solve (the next warm start's shift)
@@ -236,11 +239,13 @@ class MPCRunner:
             self.prof.setdefault(key, []).append(float(val))
 
     def _bounds_window(self, step):
-        """While the solver handle has a bounds track (BatchedILQR.set_al_bounds_track), the bounds windows of the solve at loop step `step`,
-        beside its reference windows: one kernel, nothing uploaded.  `track_starts` feeds the bounds track's start rows too, once per track."""
+        """While the solver handle has a bounds track of either kind (BatchedILQR.set_al_bounds_track, set_al_task_bounds_track), the bounds
+        windows of the solve at loop step `step`, beside its reference windows: one kernel, nothing uploaded.  `track_starts` feeds the
+        tracks' shared start rows too, once per pair of tracks."""
         track_rows = getattr(self.s, "al_bounds_track_rows", None)      # (a solver stand-in without bounds tracks has none)
-        rows = track_rows() if track_rows else 0
-        if not rows:
+        task_rows = getattr(self.s, "al_task_bounds_track_rows", None)
+        rows = (track_rows() if track_rows else 0, task_rows() if task_rows else 0)
+        if not any(rows):
             self.bounds_starts_for = None
             return
         if self.bounds_starts_for != rows and self.track_starts_given:
@@ -358,6 +363,8 @@ class MPCRunner:
         s.plant_set_history(steps if self.history_rows is None else self.history_rows)
         if self.score_args is not None:
             s.plant_set_score(**self.score_args)             # (empties the record: it covers this run)
+        if self.task_score_tol is not None:
+            s.plant_set_task_score(self.task_score_tol)      # (the same)
         s.plant_reset(x0)                                    # the only upload of a state (besides the cold start's x0)
         if self.device_refs and not self.track_ready:        # once: weights and gravity, the track, the start rows
             s.set_problem_constants(self.base)
@@ -436,6 +443,12 @@ class MPCRunner:
         if self.score_args is None:
             raise ValueError("no score was asked for (MPCRunner(..., resident=True, score={...}))")
         return self.s.plant_score()
+
+    def task_score(self):
+        """The task score record [B, 8] of the last `run` (columns solver.PLANT_TASK_SCORE_TERMS); needs MPCRunner(..., task_score=tol)."""
+        if self.task_score_tol is None:
+            raise ValueError("no task score was asked for (MPCRunner(..., resident=True, task_score=tol))")
+        return self.s.plant_task_score()
 
     def close(self):
         for lg in self.logs.values():

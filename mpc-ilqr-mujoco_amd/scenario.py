@@ -462,7 +462,8 @@ _AL_TASK_FIELDS = {"com": 0, "left_foot": 3, "right_foot": 6}
 
 
 def stack_al_task_bounds(records, B, N):
-    """Task-bounds windows [n, N+1, 18] for BatchedILQR.set_al_task_bounds: row t holds knot t's lo[9], hi[9] over the task coordinates CoM
+    """Task-bounds windows [n, N+1, 18] for BatchedILQR.set_al_task_bounds (and, with N + 1 = rows and one record, out[0] is a track for
+    set_al_task_bounds_track): row t holds knot t's lo[9], hi[9] over the task coordinates CoM
     x, y, z, left ankle origin x, y, z, right ankle origin x, y, z (world frame).  records is one dict (n = 1: every rollout reads the
     window) or a sequence of B dicts (n = B).  Every key is optional: "com", "left_foot", "right_foot" take a pair (lo, hi), each a scalar,
     [3] (the whole horizon) or [N+1, 3] (one row per knot); the shorthands "swing_clearance": z_min sets z >= z_min on both feet (the
@@ -512,6 +513,70 @@ def stack_al_task_bounds(records, B, N):
                 raise ValueError("com_xy is ((x0, y0), (x1, y1))")
             out[b, :, 0:2], out[b, :, 9:11] = c[0], c[1]
     lo, hi = out[..., :9], out[..., 9:]
+    if np.isnan(out).any() or (lo > hi).any() or (lo == np.inf).any() or (hi == -np.inf).any():
+        raise ValueError("task bounds: no NaN, lo <= hi, lo < +inf, hi > -inf")
+    return out
+
+
+def swing_phases(flags):
+    """The swing phases of one foot of a contact schedule: flags [rows] (1 stance, 0 swing) -> [(first, end)], the maximal runs of rows with
+    flag 0 as half-open ranges, in order; a run reaching the last row counts."""
+    flags = np.asarray(flags)
+    phases, first = [], None
+    for r, f in enumerate(flags):
+        if f == 0 and first is None:
+            first = r
+        if f != 0 and first is not None:
+            phases.append((first, r)); first = None
+    if first is not None:
+        phases.append((first, len(flags)))
+    return phases
+
+
+def al_task_track_from_footsteps(stance, footsteps, half_size, land_rows=2, clearance=None, clearance_margin_rows=2):
+    """A task bounds track [rows, 18] (BatchedILQR.set_al_task_bounds_track) from a footstep plan.  stance [rows, 2] is the contact schedule
+    on the loop's timeline (1 stance, 0 swing; column 0 the left foot); footsteps = {"left": [(x, y), ...], "right": [...]} has one landing
+    centre per swing phase of that foot, in order (a swing phase: a maximal run of rows with flag 0, swing_phases; a run reaching the last
+    row counts).  On the last `land_rows` rows of each phase the foot's x and y are bounded to centre +- half_size ("land inside this
+    stone"); with `clearance`, z >= clearance holds on the rows of a phase at least `clearance_margin_rows` from both of its ends (row r of
+    a phase [first, end): first + margin <= r < end - margin).  Everything else is -inf / +inf.  Raises ValueError when a foot's footstep
+    count differs from its phase count or a shape is wrong."""
+    stance = np.asarray(stance)
+    if stance.ndim != 2 or stance.shape[1] != 2 or stance.shape[0] < 1:
+        raise ValueError("stance is the contact schedule [rows, 2]")
+    if not isinstance(footsteps, dict) or set(footsteps) != {"left", "right"}:
+        raise ValueError('footsteps is {"left": [(x, y), ...], "right": [(x, y), ...]}')
+    half = np.asarray(half_size, dtype=np.float64)
+    if half.shape not in ((), (2,)) or not (half >= 0.0).all():
+        raise ValueError("half_size is one non-negative length or (half_x, half_y)")
+    half = np.broadcast_to(half, (2,))
+    land_rows, margin = int(land_rows), int(clearance_margin_rows)
+    if land_rows < 0 or margin < 0:
+        raise ValueError("land_rows and clearance_margin_rows are non-negative")
+    if clearance is not None and np.asarray(clearance, dtype=np.float64).shape != ():
+        raise ValueError("clearance is one height")
+    rows = stance.shape[0]
+    out = np.empty((rows, 18))
+    out[:, :9] = -np.inf; out[:, 9:] = np.inf
+    for e, name in enumerate(("left", "right")):
+        k0 = _AL_TASK_FIELDS[name + "_foot"]
+        try:
+            steps = np.asarray(footsteps[name], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("footsteps[%r] is a list of (x, y)" % name)
+        if steps.size == 0:
+            steps = np.zeros((0, 2))
+        if steps.ndim != 2 or steps.shape[1] != 2:
+            raise ValueError("footsteps[%r] is a list of (x, y)" % name)
+        phases = swing_phases(stance[:, e])
+        if len(phases) != len(steps):
+            raise ValueError("%s foot: %d footsteps for %d swing phases" % (name, len(steps), len(phases)))
+        for (first, end), centre in zip(phases, steps):
+            land = slice(max(first, end - land_rows), end)
+            out[land, k0:k0 + 2], out[land, 9 + k0:9 + k0 + 2] = centre - half, centre + half
+            if clearance is not None and first + margin < end - margin:
+                out[first + margin:end - margin, k0 + 2] = float(clearance)
+    lo, hi = out[:, :9], out[:, 9:]
     if np.isnan(out).any() or (lo > hi).any() or (lo == np.inf).any() or (hi == -np.inf).any():
         raise ValueError("task bounds: no NaN, lo <= hi, lo < +inf, hi > -inf")
     return out

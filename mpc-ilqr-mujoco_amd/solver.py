@@ -38,6 +38,7 @@ EXPORTS = [
     "ilqr_hip_set_al_task_bounds", "ilqr_hip_clear_al_task_bounds", "ilqr_hip_num_al_task_bound_sets", "ilqr_hip_get_al_task_bounds",
     "ilqr_hip_get_al_task_multipliers", "ilqr_hip_set_al_task_multipliers", "ilqr_hip_get_al_task_penalties", "ilqr_hip_get_al_task_violation",
     "ilqr_hip_get_al_task_trace", "ilqr_hip_get_al_task_points",
+    "ilqr_hip_set_al_task_bounds_track", "ilqr_hip_clear_al_task_bounds_track", "ilqr_hip_al_task_bounds_track_rows",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
     "ilqr_hip_initialize", "ilqr_hip_initialize_warm_resident", "ilqr_hip_initialize_device",
@@ -60,6 +61,7 @@ EXPORTS = [
     "ilqr_hip_get_retry_pass_rollouts", "ilqr_hip_set_reroll_nominal", "ilqr_hip_get_nominal_rollouts",
     "ilqr_hip_set_listed_spec", "ilqr_hip_get_listed_spec_iterations", "ilqr_hip_get_iteration_orders", "ilqr_hip_get_iteration_lists",
     "ilqr_hip_plant_set_score", "ilqr_hip_plant_clear_score", "ilqr_hip_plant_get_score", "ilqr_hip_plant_score_device",
+    "ilqr_hip_plant_set_task_score", "ilqr_hip_plant_clear_task_score", "ilqr_hip_plant_get_task_score", "ilqr_hip_plant_task_score_device",
     "ilqr_hip_set_reference_track", "ilqr_hip_clear_reference_track", "ilqr_hip_reference_track_rows", "ilqr_hip_set_track_starts",
     "ilqr_hip_window_from_track", "ilqr_hip_get_reference_windows",
     "ilqr_hip_plant_set_model", "ilqr_hip_plant_set_params", "ilqr_hip_plant_clear_params", "ilqr_hip_plant_num_param_sets", "ilqr_hip_plant_get_params",
@@ -78,6 +80,9 @@ EXPORTS = [
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
 # slots of the closed-loop score record (include/ilqr_hip.h ILQR_PLANT_SCORE_TERMS)
 PLANT_SCORE_TERMS = ("state", "control", "upright", "balance", "joint_limits", "control_limits", "min_pelvis_height", "intervals")
+# slots of the task score record (include/ilqr_hip.h ILQR_PLANT_TASK_SCORE_TERMS): per group (CoM, left foot, right foot) the largest
+# violation in metres and the number of intervals above the tolerance; the sum of squared violations; the number of intervals scored
+PLANT_TASK_SCORE_TERMS = ("max_com", "max_left", "max_right", "over_com", "over_left", "over_right", "sum_squares", "intervals")
 # columns of a plant parameter set (include/ilqr_hip.h ILQR_PLANT_PARAMS)
 PLANT_PARAMS = ("gravity_x", "gravity_y", "gravity_z", "friction", "softness", "limit_stiffness", "torque_gain")
 # columns of a plant wrench record (include/ilqr_hip.h ILQR_PLANT_WRENCH)
@@ -630,9 +635,27 @@ class BatchedILQR:
             raise ValueError("starts must be one-dimensional (one entry, or one per rollout)")
         self._chk(self.L.ilqr_hip_set_al_bounds_track_starts(self.h, st.ctypes.data_as(_ip), int(st.shape[0])))
 
+    def set_al_task_bounds_track(self, task):
+        """Upload the task family's bounds track once: task [rows, AL_TASK_BOUNDS], rows lo[9], hi[9] on the loop's timeline
+        (scenario.stack_al_task_bounds, scenario.al_task_track_from_footsteps).  Needs installed task bounds (set_al_task_bounds), which
+        supply rho_task0 and tol_task.  Its row count is its own, independent of set_al_bounds_track's; the start rows are shared with that
+        track and become one shared start of 0.  A second call replaces the track."""
+        tk = _c64(task)
+        if tk.ndim != 2 or tk.shape[1] != AL_TASK_BOUNDS:
+            raise ValueError("task bounds track: [rows, %d]" % AL_TASK_BOUNDS)
+        self._chk(self.L.ilqr_hip_set_al_task_bounds_track(self.h, int(tk.shape[0]), _p(tk)))
+
+    def clear_al_task_bounds_track(self):
+        """Free the task bounds track; the window last written stays installed."""
+        self._chk(self.L.ilqr_hip_clear_al_task_bounds_track(self.h))
+
+    def al_task_bounds_track_rows(self):
+        """0 without a task bounds track, else its rows."""
+        return int(self.L.ilqr_hip_al_task_bounds_track_rows(self.h))
+
     def al_bounds_window_from_track(self, step):
-        """Enqueue the kernel that writes the bounds windows of MPC step `step` (rollout b, knot t: track row min(start[b] + step + t,
-        rows - 1)); uploads nothing and does not synchronise."""
+        """Enqueue the ONE kernel that writes the bounds windows of MPC step `step` from every installed track (rollout b, knot t: track row
+        min(start[b] + step + t, rows - 1), each track clamped to its own last row); uploads nothing and does not synchronise."""
         self._chk(self.L.ilqr_hip_al_bounds_window_from_track(self.h, int(step)))
 
     def set_references(self, x_ref, u_ref, com_ref):
@@ -1054,6 +1077,18 @@ class BatchedILQR:
         """Remove the score: the plant calls launch what they launch without it."""
         self._chk(self.L.ilqr_hip_plant_clear_score(self.h))
 
+    def plant_set_task_score(self, tol=0.0):
+        """Install the task score (ilqr_hip_plant_set_task_score): from now on every plant_advance / plant_follow scores the state rows it
+        appends to the history ring against the task window the handle holds then (row 0 for an advance, first_knot + j for interval j of a
+        follow; a foot's rows off where the schedule has it in stance) and folds the result into a record per rollout; `tol` (metres) is the
+        threshold of the counts.  Empties the record.  The history ring must hold at least the intervals of the largest plant call, and a
+        task family must be installed when the plant is called."""
+        self._chk(self.L.ilqr_hip_plant_set_task_score(self.h, C.c_double(float(tol))))
+
+    def plant_clear_task_score(self):
+        """Remove the task score: the plant calls launch what they launch without it."""
+        self._chk(self.L.ilqr_hip_plant_clear_task_score(self.h))
+
     def plant_set_model(self, contact_mode=None, joint_limits=None):
         """The plant's own contact mode (0..4) and joint-limit option (bool), each None to follow the solver's (the default): the plant kernels
         step with that model, the solve keeps the solver's (ilqr_hip_plant_set_model).  Launches nothing."""
@@ -1247,6 +1282,11 @@ class BatchedILQR:
     def plant_score(self):
         """The record [B, 8], columns PLANT_SCORE_TERMS: six summed cost terms, the minimum pelvis height, the number of intervals scored."""
         return self._get("ilqr_hip_plant_get_score", (self.B, len(PLANT_SCORE_TERMS)))
+
+    def plant_task_score(self):
+        """The record [B, 8], columns PLANT_TASK_SCORE_TERMS: per group the largest violation and the intervals above the tolerance, the sum of
+        squared violations (NaN once an interval had a non-finite point), the number of intervals scored."""
+        return self._get("ilqr_hip_plant_get_task_score", (self.B, len(PLANT_TASK_SCORE_TERMS)))
 
     def enable_profiling(self, on=True):
         self._chk(self.L.ilqr_hip_enable_profiling(self.h, int(bool(on))))

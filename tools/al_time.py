@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the augmented-Lagrangian joint and torque limits (ilqr_hip_set_augmented_lagrangian) against the plain penalties on ONE handle,
 on one GPU, the two alternating:
-   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state] [--knot] [--task]
+   python tools/al_time.py [--batch 4096] [--horizon 25] [--calls 20] [--rounds 5] [--iters 10] [--bounds] [--state] [--knot] [--task] [--task-track [--follow M]]
   * ms per call of the two cost stages (stage_cost_quadratics: k_quad_kin + k_cost_quadratics; stage_total_cost: k_traj_knot_cost +
     k_traj_cost_sum) and, per launch inside a solve, of the cost quadratics (ilqr_hip_get_stage_ms, stage 2);
   * ms per call of the update kernel alone (ilqr_hip_al_update: k_al_update, one memset, one synchronisation);
@@ -21,7 +21,11 @@ ilqr_hip_al_bounds_window_from_track itself (both parts of a track of 2 (N + 1) 
 synchronisation, per call): "window_from_track" in the output.
 --task (implies --knot) adds one mode: the per-rollout windows of joint / torque bounds plus a per-rollout window of task bounds
 (ilqr_hip_set_al_task_bounds, n_sets = batch; every bound +-1e3 m, none active; the stance schedule is the problem's) -- the task
-instantiations of k_quad_kin, k_cost_quadratics and k_al_update and k_al_task_knot_cost against the per-knot instantiations of "al_knot_B"."""
+instantiations of k_quad_kin, k_cost_quadratics and k_al_update and k_al_task_knot_cost against the per-knot instantiations of "al_knot_B".
+--task-track (implies --knot; with --cut-only nothing else runs) times the cut once more with a task track of the same rows installed beside the
+other two parts (ilqr_hip_set_al_task_bounds_track): "window_from_track_task", with the bytes each cut writes; and a plant_follow of --follow M
+intervals (default 1) on the same handle without and with the task score (ilqr_hip_plant_set_task_score), `calls` enqueues and one
+synchronisation, alternating: "plant_follow"."""
 import argparse, importlib.util, json, os, sys, time
 import numpy as np
 import torch      # first HIP runtime of the process (as tests/conftest.py)
@@ -44,8 +48,10 @@ def main():
     ap.add_argument("--knot", action="store_true", help="also time AL under per-rollout windows of bounds (per knot), and the track cut")
     ap.add_argument("--task", action="store_true", help="also time AL under per-rollout windows of bounds plus a per-rollout window of task bounds")
     ap.add_argument("--cut-only", action="store_true", help="with --knot: time the track cut alone")
+    ap.add_argument("--task-track", action="store_true", help="also time the cut with a task track, and plant_follow without and with the task score")
+    ap.add_argument("--follow", type=int, default=1, help="with --task-track: intervals of the timed plant_follow")
     a = ap.parse_args()
-    a.knot = a.knot or a.task
+    a.knot = a.knot or a.task or a.task_track
     a.state = a.state or a.knot
     a.bounds = a.bounds or a.state
     pkg = load_package()
@@ -110,12 +116,9 @@ def main():
             if rnd:
                 for k, v in row.items():
                     ms[m][k].append(v)
-    cut = None
-    if a.knot:                                           # the track cut alone: enqueues back to back, one synchronisation
-        s.set_augmented_lagrangian(**al)
-        s.set_al_state_bounds(state_record, 2 * prob["w_joint"], 0.0)
-        s.set_al_bounds_track(np.tile(record, (2 * (N + 1), 1)), np.tile(state_record, (2 * (N + 1), 1)))
-        s.set_al_bounds_track_starts(np.arange(B) % (N + 1))
+    cut = cut_task = follow = None
+
+    def time_cut():
         samples = []
         for rnd in range(a.rounds + 1):
             s.al_bounds_window_from_track(0); s.al_violation()      # (al_violation synchronises the stream and copies [B][2] doubles)
@@ -124,10 +127,50 @@ def main():
                 s.al_bounds_window_from_track(k)
             s.al_violation()
             samples.append(1e3 * (time.perf_counter() - t0) / a.calls)
-        cut = {"ms_median": float(np.median(samples[1:])), "samples": samples[1:]}
+        return samples[1:]
+
+    if a.knot:                                           # the track cut alone: enqueues back to back, one synchronisation
+        s.set_augmented_lagrangian(**al)
+        s.set_al_state_bounds(state_record, 2 * prob["w_joint"], 0.0)
+        s.set_al_bounds_track(np.tile(record, (2 * (N + 1), 1)), np.tile(state_record, (2 * (N + 1), 1)))
+        s.set_al_bounds_track_starts(np.arange(B) % (N + 1))
+        samples = time_cut()
+        # bytes a cut writes: B windows of N + 1 padded rows per part (80 + 64 doubles; the task part adds 32); it reads as many, mostly from cache
+        cut = {"ms_median": float(np.median(samples)), "samples": samples, "bytes_written": 8 * B * (N + 1) * (80 + 64)}
+    if a.task_track:
+        s.set_al_task_bounds(task_row[None, None, :].repeat(N + 1, axis=1), 2 * prob["w_joint"], 0.0)
+        s.set_al_task_bounds_track(np.tile(task_row, (2 * (N + 1), 1)))      # (installing it resets the shared starts)
+        s.set_al_bounds_track_starts(np.arange(B) % (N + 1))
+        samples = time_cut()
+        cut_task = {"ms_median": float(np.median(samples)), "samples": samples, "bytes_written": 8 * B * (N + 1) * (80 + 64 + 32)}
+        assert s.num_al_task_bound_sets() == B and s.al_bounds_per_knot() == 3
+        # plant_follow without and with the task score: the ring row of every interval is read once ([B][51] doubles), with the interval's window
+        # and schedule rows ([B][32] doubles, [B][2] ints); term rows [M][B][8] written and read, the record [B][8] read and written
+        M = a.follow
+        s.clear_al_bounds_track(); s.clear_al_task_bounds_track()
+        s.initialize(x0, ui); s.solve(None)
+        s.plant_configure(1, 0, "schedule"); s.plant_set_history(M); s.plant_reset(x0)
+        rows = {"without": [], "with": []}
+        for rnd in range(a.rounds + 1):
+            for how in ("without", "with"):
+                if how == "with":
+                    s.plant_set_task_score(0.0)
+                else:
+                    s.plant_clear_task_score()
+                s.plant_reset(x0)
+                s.plant_follow(0, M); s.plant_alive()              # (plant_alive synchronises the stream and copies [B] ints)
+                s.plant_reset(x0)
+                t0 = time.perf_counter()
+                for k in range(a.calls):
+                    s.plant_follow(0, M)
+                s.plant_alive()
+                if rnd:
+                    rows[how].append(1e3 * (time.perf_counter() - t0) / a.calls)
+        follow = {"intervals": M, "ms_median": {k: float(np.median(v)) for k, v in rows.items()}, "samples": rows,
+                  "score_bytes": 8 * B * (M * (51 + 32 + 8 + 8) + 16) + 4 * 2 * B * M}
     s.close()
     print(json.dumps({"tool": "al_time", "device": torch.cuda.get_device_name(0), "batch": B, "horizon": N, "calls": a.calls, "rounds": a.rounds, "iters": a.iters,
-                      "al": al, "window_from_track": cut, "ms_median": {m: {k: float(np.median(v)) if v else None for k, v in d.items()} for m, d in ms.items()}, "samples": ms}))
+                      "al": al, "window_from_track": cut, "window_from_track_task": cut_task, "plant_follow": follow, "ms_median": {m: {k: float(np.median(v)) if v else None for k, v in d.items()} for m, d in ms.items()}, "samples": ms}))
 
 
 if __name__ == "__main__":
