@@ -351,6 +351,16 @@ int ilqr_hip_get_al_task_trace(ilqr_hip_ctx* ctx, double* out /*[rounds][B][2]*/
    Lagrangian (ILQR_ERR_STATE) and an initialised trajectory (ILQR_ERR_STATE), not a task window; ILQR_ERR_UNSUPPORTED without the module.
    Synchronises the handle's stream. */
 int ilqr_hip_get_al_task_points(ilqr_hip_ctx* ctx, double* out /*[B][N+1][9]*/);
+/* The VELOCITIES of those nine coordinates at every knot of the resident nominal trajectory, world frame, m/s: the velocity of the
+   whole-body centre of mass (k = 0..2), of the left ankle origin (k = 3..5) and of the right ankle origin (k = 6..8) -- the quantities
+   R(quat) gamma_s(theta, v) the cost penalises softly (w_com_vel, w_ee_vel), in Pinocchio's velocity convention (the base's linear and
+   angular velocity in the body frame), with the rotation polynomial on the raw quaternion and the URDF link masses.  What a user plots
+   against a cap on the stance foot's slip or on the speed of the centre of mass; bounds on these velocities are not built.
+   Needs an installed augmented Lagrangian (ILQR_ERR_STATE) and an initialised trajectory (ILQR_ERR_STATE), not a task window;
+   ILQR_ERR_ARG for a null pointer; ILQR_ERR_UNSUPPORTED without libilqr_hip_alknot.so, which holds the kernel.  Synchronises the handle's
+   stream. */
+#define ILQR_AL_TASK_VEL_COORDS 9
+int ilqr_hip_get_al_task_velocities(ilqr_hip_ctx* ctx, double* out /*[B][N+1][9]*/);
 /* The task family's part of the bounds track: `rows` >= 1 rows lo[9], hi[9] on the loop's timeline over the task coordinates above, with a
    row count of its own, independent of ilqr_hip_set_al_bounds_track's (on the device a row is padded to 32 doubles, two whole lines).  One
    upload; the handle owns the copy and a new task track replaces it.  ilqr_hip_al_bounds_window_from_track cuts every installed part in one

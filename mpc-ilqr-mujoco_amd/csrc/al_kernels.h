@@ -14,6 +14,7 @@
 //   k_al_shift         warm-start shift of the multipliers by the knots the trajectory is shifted by (zero tail; shift > N: all zero), penalties reset
 //   k_al_state_shift   the same for the state family's store: every column shifts as a hinge column does (knot 0 stays zero)
 //   k_al_task_shift    the same for the task family's store; k_al_task_points: the nine task coordinates of the nominal trajectories (module only)
+//   k_al_task_velocities  the velocities of those nine coordinates (al_task_dev.h al_task_velocities; module only)
 //   k_solve_begin_al   k_solve_begin with active = !done: the prologue of the rounds >= 2 of a solve with the convergence exit
 // Every rule is per rollout: nothing here reads another rollout's data, and the one shared word (AlDev::left) is a count.
 // Compiled as the tail of ilqr_kernels.hip, beside k_solve_begin and k_warm_shift (a code object of their own for three small kernels cost
@@ -170,6 +171,14 @@ __global__ void __launch_bounds__(64) k_al_task_points(DevState S, double* out) 
   double p[ALT_COORDS]; al_task_points(S.xbar + idx * H1_NX, p);
 #pragma unroll
   for (int i = 0; i < ALT_COORDS; ++i) out[idx * ALT_COORDS + i] = p[i];
+}
+// the nine velocities of the same points at every knot of the nominal trajectories (al_task_dev.h al_task_velocities): one lane per (rollout, knot)
+__global__ void __launch_bounds__(64) k_al_task_velocities(DevState S, double* out) {
+  const long idx = (long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= (long)S.B * (S.N + 1)) return;
+  double v[ALV_COORDS]; al_task_velocities(S.xbar + idx * H1_NX, v);
+#pragma unroll
+  for (int i = 0; i < ALV_COORDS; ++i) out[idx * ALV_COORDS + i] = v[i];
 }
 #else
 // Each lane owns one column of the knot records and walks the knots upwards: it reads knot t + shift after it has written every knot < t, so

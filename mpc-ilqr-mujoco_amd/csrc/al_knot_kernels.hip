@@ -25,6 +25,7 @@ void ilqr_alknot_module_expand(const double* rec, long rec_stride, double* win, 
 void ilqr_alknot_module_task_knot_cost(const ilqr::DevState* S, const h1::ProblemDev* P, int mode, const double* xsrc, int cshift, int oshift, const int* gate, hipStream_t st);
 void ilqr_alknot_module_task_shift(const ilqr::AlDev* A, int B, int N, int shift, hipStream_t st);
 void ilqr_alknot_module_task_points(const ilqr::DevState* S, double* out, hipStream_t st);
+void ilqr_alknot_module_task_velocities(const ilqr::DevState* S, double* out, hipStream_t st);
 // plant_task_score_kernels.hip of this module
 void ilqr_alknot_module_plant_task_score(const ilqr::PlantTaskScoreDev* T, int B, const double* hist_x, long hist_row0, long hist_cap, int knot0, int count, double* terms, double* record, hipStream_t st);
 // the one symbol the library resolves: the table of the module's entry points (ilqr_kernels.h AlKnotModule)
@@ -32,7 +33,7 @@ const ilqr::AlKnotModule* ilqr_alknot_module() {
   static const ilqr::AlKnotModule table = {ilqr_alknot_module_knot_cost, ilqr_alknot_module_state_knot_cost, ilqr_alknot_module_cost_quadratics,
                                            ilqr_alknot_module_al_update, ilqr_alknot_module_window_from_track, ilqr_alknot_module_expand,
                                            ilqr_alknot_module_task_knot_cost, ilqr_alknot_module_task_shift, ilqr_alknot_module_task_points,
-                                           ilqr_alknot_module_plant_task_score};
+                                           ilqr_alknot_module_plant_task_score, ilqr_alknot_module_task_velocities};
   return &table;
 }
 }
@@ -52,4 +53,8 @@ extern "C" void ilqr_alknot_module_task_shift(const ilqr::AlDev* A, int B, int N
 extern "C" void ilqr_alknot_module_task_points(const ilqr::DevState* S, double* out, hipStream_t st) {
   const long total = (long)S->B * (S->N + 1);
   hipLaunchKernelGGL(ilqr::k_al_task_points, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, *S, out);
+}
+extern "C" void ilqr_alknot_module_task_velocities(const ilqr::DevState* S, double* out, hipStream_t st) {
+  const long total = (long)S->B * (S->N + 1);
+  hipLaunchKernelGGL(ilqr::k_al_task_velocities, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, *S, out);
 }

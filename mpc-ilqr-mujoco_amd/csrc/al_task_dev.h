@@ -129,4 +129,93 @@ DEVFN double al_task_term(const ProblemDev& P, int b, int t, const double* x) {
   return c / (2.0 * rho);
 }
 
+// ---- The VELOCITIES of the same three point sets in the world frame (ilqr_hip_get_al_task_velocities) -- coordinate k in [0, 9): 0..2 the
+// velocity of the whole-body CoM, 3..5 of the left ankle origin, 6..8 of the right ankle origin -- the quantities R(quat) gamma_s(theta, v) the
+// cost penalises softly (w_com_vel, w_ee_vel; Pinocchio's velocity convention: the base's linear and angular velocity in the body frame, the
+// rotation polynomial on the raw quaternion, URDF masses).
+//   al_task_velocities  the nine coordinates of one state under al_task_points' rounding rule (no contraction, every operation rounded once):
+//                       the one function a family of bounds on these velocities would share between its kernels, as the task family shares
+//                       al_task_points.  Today the getter's kernel (k_al_task_velocities) is its only caller.
+enum { ALV_COORDS = 9 };
+
+// body frame in the pelvis frame with its motion: origin velocity vp and angular velocity Om, both with the base's own motion included
+struct AlvBody { double R[9], p[3], vp[3], Om[3]; };
+DEVFN void alv_cross(const double* a, const double* b, double* c) {
+#pragma clang fp contract(off)
+  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+// body I from its parent; hv += mu_I (vp_I + Om_I x R_I com_I), its share of the velocity of the whole-body CoM
+template <int I> DEVFN void alv_step(const AlvBody& P, const double* x, AlvBody& B, double* hv) {
+#pragma clang fp contract(off)
+  constexpr int ax = h1c::C_AXIS[I];
+  double sn, cs; h1f::sincos_fast(x[7 + I - 1], &sn, &cs);
+  const double qd = x[H1_NQ + 6 + I - 1];
+  double Rj[9];
+  alt_rj_row<I, 0>(cs, sn, Rj); alt_rj_row<I, 1>(cs, sn, Rj + 3); alt_rj_row<I, 2>(cs, sn, Rj + 6);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) B.R[3 * r + c] = (P.R[3 * r] * Rj[c] + P.R[3 * r + 1] * Rj[3 + c]) + P.R[3 * r + 2] * Rj[6 + c];
+  constexpr double px = h1c::CU_POS[I][0], py = h1c::CU_POS[I][1], pz = h1c::CU_POS[I][2];
+  constexpr double c0 = h1c::CU_COM[I][0], c1 = h1c::CU_COM[I][1], c2 = h1c::CU_COM[I][2];
+  constexpr double mu = alt_mu(I);
+  double d[3], cm[3], wd[3], wc[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    d[k] = (P.R[3 * k] * px + P.R[3 * k + 1] * py) + P.R[3 * k + 2] * pz;
+    B.p[k] = P.p[k] + d[k];
+    B.Om[k] = P.Om[k] + B.R[3 * k + ax] * qd;
+    cm[k] = (B.R[3 * k] * c0 + B.R[3 * k + 1] * c1) + B.R[3 * k + 2] * c2;
+  }
+  alv_cross(P.Om, d, wd); alv_cross(B.Om, cm, wc);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    B.vp[k] = P.vp[k] + wd[k];
+    hv[k] = hv[k] + mu * (B.vp[k] + wc[k]);
+  }
+}
+template <int FIRST, int LEN> DEVFN void alv_chain(const AlvBody& par, const double* x, AlvBody& last, double* hv) {
+  AlvBody a = par;
+  if constexpr (LEN >= 1) { alv_step<FIRST>(a, x, last, hv); a = last; }
+  if constexpr (LEN >= 2) { alv_step<FIRST + 1>(a, x, last, hv); a = last; }
+  if constexpr (LEN >= 3) { alv_step<FIRST + 2>(a, x, last, hv); a = last; }
+  if constexpr (LEN >= 4) { alv_step<FIRST + 3>(a, x, last, hv); a = last; }
+  if constexpr (LEN >= 5) { alv_step<FIRST + 4>(a, x, last, hv); }
+}
+// x: one state, MuJoCo slot order (quaternion w, x, y, z at 3..6; v_b, omega_b of the base in its own frame at H1_NQ .. H1_NQ + 5);
+// v[9]: the velocities of the CoM, the left ankle origin and the right ankle origin, world frame
+DEVFN void al_task_velocities(const double* x, double* v) {
+#pragma clang fp contract(off)
+  const double qx = x[4], qy = x[5], qz = x[6], qw = x[3];      // (raw coefficients, as al_task_points)
+  double R0[9];
+  {
+    const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
+    const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+    R0[0] = 1 - (tyy + tzz); R0[1] = txy - twz; R0[2] = txz + twy;
+    R0[3] = txy + twz; R0[4] = 1 - (txx + tzz); R0[5] = tyz - twx;
+    R0[6] = txz - twy; R0[7] = tyz + twx; R0[8] = 1 - (txx + tyy);
+  }
+  AlvBody pel;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pel.R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { pel.p[k] = 0.0; pel.vp[k] = x[H1_NQ + k]; pel.Om[k] = x[H1_NQ + 3 + k]; }
+  constexpr double mu0 = alt_mu(0);
+  const double c0[3] = {h1c::CU_COM[0][0], h1c::CU_COM[0][1], h1c::CU_COM[0][2]};
+  double w0[3]; alv_cross(pel.Om, c0, w0);
+  double hv[3] = {mu0 * (pel.vp[0] + w0[0]), mu0 * (pel.vp[1] + w0[1]), mu0 * (pel.vp[2] + w0[2])};
+  AlvBody lf, rf, tor, arm;
+  alv_chain<1, 5>(pel, x, lf, hv);
+  alv_chain<6, 5>(pel, x, rf, hv);
+  alv_chain<11, 1>(pel, x, tor, hv);
+  alv_chain<12, 4>(tor, x, arm, hv);
+  alv_chain<16, 4>(tor, x, arm, hv);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    v[k] = (R0[3 * k] * hv[0] + R0[3 * k + 1] * hv[1]) + R0[3 * k + 2] * hv[2];
+    v[3 + k] = (R0[3 * k] * lf.vp[0] + R0[3 * k + 1] * lf.vp[1]) + R0[3 * k + 2] * lf.vp[2];
+    v[6 + k] = (R0[3 * k] * rf.vp[0] + R0[3 * k + 1] * rf.vp[1]) + R0[3 * k + 2] * rf.vp[2];
+  }
+}
+
 }  // namespace h1

@@ -954,7 +954,8 @@ int ilqr_hip_get_al_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c,
 int ilqr_hip_get_al_state_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.strace : nullptr, 2, out); }
 int ilqr_hip_get_al_task_trace(ilqr_hip_ctx* c, double* out) { return al_get_trace(c, c ? c->al.ttrace : nullptr, 2, out); }
 // the nine task coordinates of the resident nominal trajectory, by the kernel the cost kernels and the update share their arithmetic with
-__attribute__((minsize)) int ilqr_hip_get_al_task_points(ilqr_hip_ctx* c, double* out) {
+// (velocities: the velocities of the same nine coordinates, by their kernel, through the same buffer)
+__attribute__((noinline, minsize)) static int al_get_task_coords(ilqr_hip_ctx* c, double* out, bool velocities) {
   if (!c || !out) return ILQR_ERR_ARG;
   TRY(al_installed(c));
   if (!c->initialized) return ILQR_ERR_STATE;
@@ -962,12 +963,15 @@ __attribute__((minsize)) int ilqr_hip_get_al_task_points(ilqr_hip_ctx* c, double
   TRY(al_knot_ready(c));
   const size_t n = (size_t)c->B * (c->N + 1) * ILQR_AL_TASK_COORDS;
   if (!c->al.tpoints) TRY(dalloc(c, &c->al.tpoints, n));
-  ilqr::g_al_knot.task_points(&c->S, c->al.tpoints, c->stream);
+  (velocities ? ilqr::g_al_knot.task_velocities : ilqr::g_al_knot.task_points)(&c->S, c->al.tpoints, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, c->al.tpoints, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ILQR_OK;
 }
+int ilqr_hip_get_al_task_points(ilqr_hip_ctx* c, double* out) { return al_get_task_coords(c, out, false); }
+int ilqr_hip_get_al_task_velocities(ilqr_hip_ctx* c, double* out) { return al_get_task_coords(c, out, true); }
+static_assert(ILQR_AL_TASK_VEL_COORDS == ILQR_AL_TASK_COORDS && h1::ALV_COORDS == ILQR_AL_TASK_VEL_COORDS, "one buffer for both getters");
 int ilqr_hip_al_update(ilqr_hip_ctx* c, int round) {
   if (!c || round < 0) return ILQR_ERR_ARG;
   TRY(al_installed(c));

@@ -196,6 +196,9 @@ struct AlKnotModule {
   void (*task_points)(const DevState* S, double* out, hipStream_t st);
   // plant_task_score_kernels.hip: launch_plant_task_score (ilqr_hip_plant_set_task_score).  Appended: nothing above moves
   void (*plant_task_score)(const PlantTaskScoreDev* T, int B, const double* hist_x, long hist_row0, long hist_cap, int knot0, int count, double* terms, double* record, hipStream_t st);
+  // the velocities of the task family's nine coordinates at every knot of the nominal trajectories into out [B][N+1][9]
+  // (ilqr_hip_get_al_task_velocities; al_task_dev.h al_task_velocities).  Appended: nothing above moves
+  void (*task_velocities)(const DevState* S, double* out, hipStream_t st);
 };
 extern AlKnotModule g_al_knot;      // (ilqr_capi.hip)
 // masked: the convergence exit is on -- a rollout that was done when the round began did not run and gets no trace row

@@ -37,7 +37,7 @@ EXPORTS = [
     "ilqr_hip_al_bounds_window_from_track",
     "ilqr_hip_set_al_task_bounds", "ilqr_hip_clear_al_task_bounds", "ilqr_hip_num_al_task_bound_sets", "ilqr_hip_get_al_task_bounds",
     "ilqr_hip_get_al_task_multipliers", "ilqr_hip_set_al_task_multipliers", "ilqr_hip_get_al_task_penalties", "ilqr_hip_get_al_task_violation",
-    "ilqr_hip_get_al_task_trace", "ilqr_hip_get_al_task_points",
+    "ilqr_hip_get_al_task_trace", "ilqr_hip_get_al_task_points", "ilqr_hip_get_al_task_velocities",
     "ilqr_hip_set_al_task_bounds_track", "ilqr_hip_clear_al_task_bounds_track", "ilqr_hip_al_task_bounds_track_rows",
     "ilqr_hip_set_contact_schedule", "ilqr_hip_set_ee_references", "ilqr_hip_set_references",
     "ilqr_hip_set_regularization", "ilqr_hip_set_max_iterations", "ilqr_hip_set_tolerance", "ilqr_hip_set_options", "ilqr_hip_set_early_exit_gate",
@@ -109,6 +109,8 @@ AL_STATE_BOUNDS = 56
 # left ankle origin x, y, z, right ankle origin x, y, z, world frame
 AL_TASK_COORDS = 9
 AL_TASK_BOUNDS = 18
+# the velocities of those coordinates (ILQR_AL_TASK_VEL_COORDS): of the CoM, the left ankle origin and the right ankle origin, world frame, m/s
+AL_TASK_VEL_COORDS = 9
 # columns of a plant terrain record (include/ilqr_hip.h ILQR_PLANT_TERRAIN)
 PLANT_TERRAIN = ("z_left", "z_right", "edge_x", "first", "end")
 
@@ -571,6 +573,12 @@ class BatchedILQR:
     def al_task_points(self):
         """[B, N+1, 9]: the task coordinates of the resident nominal trajectory as the kernels compute them."""
         return self._get("ilqr_hip_get_al_task_points", (self.B, self.N + 1, AL_TASK_COORDS))
+
+    def al_task_velocities(self):
+        """[B, N+1, 9]: the velocities (m/s, world frame) of the task coordinates -- CoM, left ankle origin, right ankle origin -- at every knot
+        of the resident nominal trajectory, in the convention of the cost's velocity terms.  Needs an installed augmented Lagrangian and an
+        initialised trajectory."""
+        return self._get("ilqr_hip_get_al_task_velocities", (self.B, self.N + 1, AL_TASK_VEL_COORDS))
 
     # ---- bounds that change from knot to knot (include/ilqr_hip.h ilqr_hip_set_al_knot_bounds)
     def _knot_window(self, bounds, width, what):
