@@ -491,7 +491,7 @@ static int need_module(ilqr_hip_ctx* c, int which) {
   const PlantModuleLib& m = plant_module(which);
   if (!m.ok) { c->err = m.why; return ILQR_ERR_UNSUPPORTED; }
   if (!((c->module_attr_set >> which) & 1u)) {
-    if (module_fn<ilqr::wrench_set_attr_fn>(which, FN_SET_ATTR)() != 0) { c->err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the ") + MODULE_DESC[which].name + " kernels"; return ILQR_ERR_HIP; }
+    if (module_fn<ilqr::plant_set_attr_fn>(which, FN_SET_ATTR)() != 0) { c->err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed on the ") + MODULE_DESC[which].name + " kernels"; return ILQR_ERR_HIP; }
     c->module_attr_set |= 1u << which;
   }
   return ILQR_OK;
@@ -2385,36 +2385,28 @@ static int upload_actuator_blend(ilqr_hip_ctx* c) {
 }
 // The plant kernel of one call: without a table exactly the launch without the feature; with one, the followed kernel of the plan's family
 // with the tables' records -- for an advance over the one interval (0, 1), which is an advance bit for bit -- behind the draws the plan names.
-// Each family takes the tables of the ones before it, any of which may be null but the parameter record: the parameter table's or the
-// handle's own (plant_self_params).  row: the advance's ring row (-1: no ring) or the follow's first ring row.  The caller has loaded
+// Every followed family gets the same call record (ilqr_kernels.h PlantCall) with every table of the handle in it and reads its own and the
+// ones before it, any of which may be null but the parameter record: the parameter table's or the handle's own (plant_self_params).  row: the advance's ring row (-1: no ring) or the follow's first ring row.  The caller has loaded
 // plan.modules.
 static void enqueue_plant(ilqr_hip_ctx* c, const ilqr::PlantPlan& plan, const h1::DynParams& dyn, int geom, int first_knot, int count, long row) {
   const int g = (geom && dyn.contact != 0) ? 1 : 0, kick = c->plant_kick ? 1 : 0;
-  const ilqr::PlantTable T = c->pparams.d ? ilqr::PlantTable{c->pparams.d, c->pparams.sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
-  const auto W = ilqr::WrenchTable{c->wrench.d, c->wrench.sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
-  const auto M = ilqr::PayloadTable{c->payload.d, c->payload.sets == 1 ? 0 : PAYLOAD_REC};
   const bool one = c->act.sets == 1;
-  const auto A = ilqr::ActuatorTable{c->act.d, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
-  const auto J = ilqr::JointTable{c->joints.d, c->joints.sets == 1 ? 0 : JOINT_REC};
-  const auto a = ilqr::WrenchFollowArgs{c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
-  const double* delta = plan.draw_observation ? c->d_obs_delta : nullptr;
+  ilqr::PlantCall call{};
+  call.a = {c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row < 0 ? 0L : row, (long)c->hist_cap};
+  call.T = c->pparams.d ? ilqr::PlantTable{c->pparams.d, c->pparams.sets == 1 ? 0 : ILQR_PLANT_PARAMS + 1} : ilqr::PlantTable{c->d_self_params, 0};
+  call.W = {c->wrench.d, c->wrench.sets == 1 ? 0 : WRENCH_REC, c->plant_intervals};
+  call.M = {c->payload.d, c->payload.sets == 1 ? 0 : PAYLOAD_REC};
+  call.dobs = plan.draw_observation ? c->d_obs_delta : nullptr;
+  call.A = {c->act.d, one ? 0 : ILQR_PLANT_ACTUATOR, c->d_act_beta, one ? 0 : ILQR_NU, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied, c->act_substeps};
+  if (plan.pass_joints) call.J = {c->joints.d, c->joints.sets == 1 ? 0 : JOINT_REC};      // (an all-nominal joint table is no table to any family)
+  call.R = {c->terrain.d, c->terrain.sets == 1 ? 0 : TERRAIN_REC};
   if (plan.draw_observation) enqueue_observation_draw(c, c->plant_intervals, count);
   if (plan.draw_actuator) enqueue_actuator_draw(c, c->plant_intervals, count);
   switch (plan.family) {
-    case ilqr::PLANT_TERRAIN: {      // (an all-nominal joint table is no table to this family either)
-      const auto Jt = c->joints_nominal ? ilqr::JointTable{nullptr, 0} : J;
-      const auto R = ilqr::TerrainTable{c->terrain.d, c->terrain.sets == 1 ? 0 : TERRAIN_REC};
-      module_fn<ilqr::terrain_follow_fn>(ilqr::MOD_TERRAIN, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &Jt, &R, &a, c->stream);
-      break;
-    }
-    case ilqr::PLANT_JOINTS: module_fn<ilqr::joints_follow_fn>(ilqr::MOD_JOINTS, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &J, &a, c->stream); break;
-    case ilqr::PLANT_ACTUATOR: module_fn<ilqr::actuator_follow_fn>(ilqr::MOD_ACTUATOR, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &A, &a, c->stream); break;
-    case ilqr::PLANT_OBSERVE: module_fn<ilqr::observe_follow_fn>(ilqr::MOD_OBSERVE, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, delta, &a, c->stream); break;
-    case ilqr::PLANT_PAYLOAD: module_fn<ilqr::payload_follow_fn>(ilqr::MOD_PAYLOAD, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &M, &a, c->stream); break;
-    case ilqr::PLANT_WRENCH: module_fn<ilqr::wrench_follow_fn>(ilqr::MOD_WRENCH, FN_FOLLOW)(&c->S, &c->plant, &dyn, &T, &W, &a, c->stream); break;
-    case ilqr::PLANT_PARAMS: ilqr::launch_plant_follow_params(c->S, c->plant, dyn, T, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, a.hist_row0, c->hist_cap, c->stream); break;
-    case ilqr::PLANT_FOLLOW: ilqr::launch_plant_follow(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, first_knot, count, row, c->hist_cap, c->stream); break;
     case ilqr::PLANT_ADVANCE: ilqr::launch_plant_advance(c->S, c->plant, dyn, c->d_stance, c->P.stance_stride, g, c->plant_substeps, c->plant_feedback, kick, row, c->stream); break;
+    case ilqr::PLANT_FOLLOW: ilqr::launch_plant_follow(c->S, c->plant, dyn, call, c->stream); break;
+    case ilqr::PLANT_PARAMS: ilqr::launch_plant_follow_params(c->S, c->plant, dyn, call, c->stream); break;
+    default: module_fn<ilqr::plant_follow_fn>(plan.family - ilqr::PLANT_WRENCH, FN_FOLLOW)(&c->S, &c->plant, &dyn, &call, c->stream);      // the family's own module (plant_plan.h: in the order of the families)
   }
   if (plan.draw_actuator) c->act_substeps += (long)count * c->plant_substeps;
 }
@@ -2971,9 +2963,7 @@ static int step_in_module(ilqr_hip_ctx* c, ilqr::PlantModule which, int count, c
   if (payload) HIPCHK(c, hipMemcpyAsync(c->d_stepm, payload, n * ILQR_PLANT_PAYLOAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (joints) HIPCHK(c, hipMemcpyAsync(c->d_stepj, joints, n * ILQR_PLANT_JOINTS * sizeof(double), hipMemcpyHostToDevice, c->stream));
   const double *w = wrench ? c->d_stepw : nullptr, *m = payload ? c->d_stepm : nullptr;
-  if (which == ilqr::MOD_WRENCH) module_fn<ilqr::wrench_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, c->stream);
-  else if (which == ilqr::MOD_PAYLOAD) module_fn<ilqr::payload_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, m, c->stream);
-  else module_fn<ilqr::joints_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, m, c->d_stepj, c->stream);
+  module_fn<ilqr::plant_step_fn>(which, FN_STEP)(count, c->d_stepx, c->d_stepu, &c->P.dyn, c->d_stepn, stance_left, stance_right, w, m, joints ? c->d_stepj : nullptr, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(x_next, c->d_stepn, n * ILQR_NX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -261,80 +261,49 @@ struct PlantDev {
 // from the feet instead; kick != 0: apply Pl.dv first; hist_row >= 0: fill that row of the ring
 void launch_plant_advance(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, long hist_row,
                           hipStream_t st);
-// `count` consecutive intervals in one launch under the policy knots first_knot .. first_knot + count - 1 (schedule rows likewise); the
-// kick before the first interval only; ring rows (hist_row0 + j) % hist_cap, hist_cap = 0: no ring
-void launch_plant_follow(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
-                         long hist_row0, long hist_cap, hipStream_t st);
 int plant_kernels_set_attr();
-// the same with a plant parameter table (ilqr_hip_plant_set_params): rollout b steps with record b * rec_stride of `records` -- g[3], mu,
-// soft, lim_k, torque gain, padding; 8 doubles -- in the place of those fields of dyn, and with gain * u.  rec_stride 8: one record per
-// rollout; 0: one record for all.  dyn still supplies h, the contact mode and the limits switch.  (first_knot, count) = (0, 1) is the
-// advance: with a table there is no kernel of its own for it.
+// ---- the followed plant: `count` consecutive intervals in one launch under the policy knots first_knot .. first_knot + count - 1 (schedule
+// rows likewise); the kick before the first interval only; ring rows (hist_row0 + j) % hist_cap, hist_cap = 0: no ring.  (first_knot, count)
+// = (0, 1) is the advance: with a table there is no kernel of its own for it.
+struct PlantFollowArgs { const int* sched; long sched_stride; int geom, substeps, feedback_mode, kick, first_knot, count; long hist_row0, hist_cap; };
+// The tables of the eight followed kernel families (plant_plan.h PlantFamily), each family the superset of the one before it.  In every
+// table rollout b reads record b * rec_stride of `records`: rec_stride the record's size, or 0: ONE record that every rollout reads.  A
+// table that is not installed has null `records`; a family ignores the tables above its own.
+// plant parameter table (ilqr_hip_plant_set_params): g[3], mu, soft, lim_k, torque gain, padding; 8 doubles -- in the place of those fields
+// of dyn, and gain * u in the place of u.  dyn still supplies h, the contact mode and the limits switch.  Every family from the parameter
+// family on reads T: without a parameter table the caller passes ONE record of the handle's own values with gain 1 (rec_stride 0).
 struct PlantTable {
   const double* records;
   int rec_stride;
 };
-void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const PlantTable& T, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode,
-                                int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st);
-// the same under an external wrench on the pelvis per rollout (ilqr_hip_plant_set_wrench): rollout b reads record b * rec_stride of
-// W.records -- F[3], T[3] (world), r[3] (pelvis frame), first, end, padding; 16 doubles -- and steps under it in the plant intervals
-// first <= W.interval0 + j < end.  rec_stride 16 or 0 as above.  T is always read: without a parameter table the caller passes ONE record
-// of the handle's own values with gain 1 (rec_stride 0).
+// external wrench on the pelvis (ilqr_hip_plant_set_wrench): F[3], T[3] (world), r[3] (pelvis frame), first, end, padding; 16 doubles.  The
+// rollout steps under it in the plant intervals first <= interval0 + j < end.
 struct WrenchTable {
   const double* records;
   int rec_stride;
-  long interval0;      // plant intervals run since ilqr_hip_plant_reset when this launch starts
+  long interval0;      // plant intervals run since ilqr_hip_plant_reset when this launch starts; set whether or not there is a wrench table (the terrain's window counts from it too)
 };
-// The family lives in a module of its own, libilqr_hip_wrench.so (plant_kernels.hip compiled with -DPLANT_WRENCH_MODULE), which the C API
-// opens on first use; these are its three entry points, C linkage:
-//   int  ilqr_wrench_module_set_attr()                                  the LDS attributes of its kernels on the current device
-//   void ilqr_wrench_module_follow(S, Pl, dyn, T, W, args, stream)      the followed plant kernel under the two tables
-//   void ilqr_wrench_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9], stream)
-//                                                                       one two-lane step per item under its wrench (F, T, r): launch_step_s with explicit stance flags
-struct WrenchFollowArgs { const int* sched; long sched_stride; int geom, substeps, feedback_mode, kick, first_knot, count; long hist_row0, hist_cap; };
-typedef int (*wrench_set_attr_fn)();
-typedef void (*wrench_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const WrenchFollowArgs*, hipStream_t);
-typedef void (*wrench_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, hipStream_t);
-// the same with a rigid payload on the pelvis per rollout as well (ilqr_hip_plant_set_payload): rollout b reads record b * rec_stride of
-// M.records -- mass, centre of mass c[3] (pelvis frame), Ixx, Iyy, Izz, Ixy, Ixz, Iyz about c, padding; 16 doubles -- in every substep.
-// rec_stride 16 or 0 as above.  T and W as in the wrench family, except that W.records may be null: no wrench.
+// rigid payload on the pelvis (ilqr_hip_plant_set_payload): mass, centre of mass c[3] (pelvis frame), Ixx, Iyy, Izz, Ixy, Ixz, Iyz about c,
+// padding; 16 doubles -- in every substep
 struct PayloadTable {
   const double* records;
   int rec_stride;
 };
-// The family lives in a module of its own as well, libilqr_hip_payload.so (plant_kernels.hip compiled with -DPLANT_PAYLOAD_MODULE):
-//   int  ilqr_payload_module_set_attr()
-//   void ilqr_payload_module_follow(S, Pl, dyn, T, W, M, args, stream)
-//   void ilqr_payload_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9] or null, payload[count][10], stream)
-typedef int (*payload_set_attr_fn)();
-typedef void (*payload_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const WrenchFollowArgs*, hipStream_t);
-typedef void (*payload_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, hipStream_t);
-// the same under an observation table (ilqr_hip_plant_set_observation): the control law reads x [+] delta, delta the error rows
-// [count][B][51] of the call's intervals as ilqr_observe_module_draw wrote them.  rollout b reads record b * rec_stride of O.records --
-// bias[50], sigma[50] in tangent order; 100 doubles -- rec_stride 100 or 0 as above; its stream of the generator is stream0 + b.
-// T as in the wrench family; W.records and M.records may each be null: no wrench, no payload.
+// observation table (ilqr_hip_plant_set_observation): bias[50], sigma[50] in tangent order; 100 doubles; the rollout's stream of the
+// generator is stream0 + b.  The followed kernel does not read the table itself: its control law reads x [+] delta, delta the error rows
+// PlantCall::dobs [count][B][51] of the call's intervals as ilqr_observe_module_draw wrote them from the table.
 struct ObservationTable {
   const double* records;
   int rec_stride;
   unsigned long long seed, stream0;
 };
-// The family lives in a module of its own as well, libilqr_hip_observe.so (plant_kernels.hip compiled with -DPLANT_OBSERVE_MODULE):
-//   int  ilqr_observe_module_set_attr()
-//   void ilqr_observe_module_follow(S, Pl, dyn, T, W, M, delta, args, stream)
-//   void ilqr_observe_module_draw(B, O, interval0, count, delta[count][B][51], stream)     the errors of intervals interval0 .. + count - 1
-//   void ilqr_observe_module_apply(B, x[B][51], delta[B][51], out[B][51], stream)          out = x [+] delta
-typedef int (*observe_set_attr_fn)();
-typedef void (*observe_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const WrenchFollowArgs*, hipStream_t);
-typedef void (*observe_draw_fn)(int, const ObservationTable*, long, int, double*, hipStream_t);
-typedef void (*observe_apply_fn)(int, const double*, const double*, double*, hipStream_t);
-// the same with an actuator between the control law and the joints (ilqr_hip_plant_set_actuator): per substep the law's output -- the
-// COMMAND, which stays what the plant reports -- goes through a delay line, a first-order lag and additive noise, and the step takes the
-// result.  rollout b reads record b * rec_stride of A.records -- delay, tau[19], sigma[19]; 39 doubles -- and row b * blend_stride of
-// A.blend, beta[19] = -expm1(-h / tau) as the host computed it (rec_stride 39 / blend_stride 19, or both 0: one record for all).
-// A.z: the normals [count][B][19] of the call's intervals as ilqr_actuator_module_draw wrote them.  The actuator's state is the handle's
-// and persists across launches: fifo [B][9][19], y [B][19]; applied [B][19] takes the torque of the launch's last substep.  substep0:
-// substeps run since the state was primed; 0 primes it (every slot and y take the first command).
-// T as in the wrench family; W.records, M.records and the observation rows delta may each be null.
+// an actuator between the control law and the joints (ilqr_hip_plant_set_actuator): per substep the law's output -- the COMMAND, which
+// stays what the plant reports -- goes through a delay line, a first-order lag and additive noise, and the step takes the result.
+// Record: delay, tau[19], sigma[19]; 39 doubles -- and row b * blend_stride of `blend`, beta[19] = -expm1(-h / tau) as the host computed it
+// (rec_stride 39 / blend_stride 19, or both 0: one record for all).  z: the normals [count][B][19] of the call's intervals as
+// ilqr_actuator_module_draw wrote them.  The actuator's state is the handle's and persists across launches: fifo [B][9][19], y [B][19];
+// applied [B][19] takes the torque of the launch's last substep.  substep0: substeps run since the state was primed; 0 primes it (every
+// slot and y take the first command).
 struct ActuatorTable {
   const double* records;
   int rec_stride;
@@ -346,45 +315,52 @@ struct ActuatorTable {
   double* applied;
   long substep0;
 };
-// The family lives in a module of its own as well, libilqr_hip_actuator.so (plant_kernels.hip compiled with -DPLANT_ACTUATOR_MODULE):
-//   int  ilqr_actuator_module_set_attr()
-//   void ilqr_actuator_module_follow(S, Pl, dyn, T, W, M, delta or null, A, args, stream)
-//   void ilqr_actuator_module_draw(B, seed, stream0, interval0, count, z[count][B][19], stream)     the normals of intervals interval0 .. + count - 1
-typedef int (*actuator_set_attr_fn)();
-typedef void (*actuator_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
-                                   const WrenchFollowArgs*, hipStream_t);
-typedef void (*actuator_draw_fn)(int, unsigned long long, unsigned long long, long, int, double*, hipStream_t);
-// the same with the joints of each rollout read from a record (ilqr_hip_plant_set_joints): rollout b reads record b * rec_stride of J.records
-// -- gain[19], range scale[19], damping[19], armature[19], four doubles of padding; 80 doubles -- (rec_stride 80, or 0: one record for all).
-// T as in the wrench family; W.records, M.records, the observation rows delta and A.records may each be null.
+// the joints of each rollout (ilqr_hip_plant_set_joints): gain[19], range scale[19], damping[19], armature[19], four doubles of padding; 80 doubles
 struct JointTable {
   const double* records;
   int rec_stride;
 };
-// The family lives in a module of its own as well, libilqr_hip_joints.so (plant_kernels.hip compiled with -DPLANT_JOINTS_MODULE):
-//   int  ilqr_joints_module_set_attr()
-//   void ilqr_joints_module_follow(S, Pl, dyn, T, W, M, delta or null, A, J, args, stream)
-//   void ilqr_joints_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9] or null, payload[count][10] or null, joints[count][76], stream)
-typedef int (*joints_set_attr_fn)();
-typedef void (*joints_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
-                                 const JointTable*, const WrenchFollowArgs*, hipStream_t);
-typedef void (*joints_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, const double*, hipStream_t);
-// the same on a floor of each rollout's own height (ilqr_hip_plant_set_terrain): rollout b reads record b * rec_stride of R.records -- z_left,
-// z_right, edge_x, first, end, three doubles of padding; 8 doubles -- (rec_stride 8, or 0: one record for all) and decides its stance flags
-// per substep against that floor.  T as in the wrench family; W.records, M.records, the observation rows delta, A.records and J.records may
-// each be null.  The window is counted from W.interval0, which is set whether or not there is a wrench table.
+// a floor of each rollout's own height (ilqr_hip_plant_set_terrain): z_left, z_right, edge_x, first, end, three doubles of padding; 8
+// doubles; the rollout decides its stance flags per substep against that floor.  The window is counted from W.interval0.
 struct TerrainTable {
   const double* records;
   int rec_stride;
 };
-// The family lives in a module of its own as well, libilqr_hip_terrain.so (plant_kernels.hip compiled with -DPLANT_TERRAIN_MODULE):
-//   int  ilqr_terrain_module_set_attr()
-//   void ilqr_terrain_module_follow(S, Pl, dyn, T, W, M, delta or null, A, J, R, args, stream)
-//   void ilqr_terrain_module_step(count, x, u, dyn, xn, terrain[count][3] (z_left, z_right, edge_x), stance_out[count][2], stream)
-typedef int (*terrain_set_attr_fn)();
-typedef void (*terrain_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantTable*, const WrenchTable*, const PayloadTable*, const double*, const ActuatorTable*,
-                                  const JointTable*, const TerrainTable*, const WrenchFollowArgs*, hipStream_t);
+// ONE call record for every followed family, in the library and across the module boundary: everything any family reads.  dobs: the
+// observation's error rows, null without an observation table.
+struct PlantCall {
+  PlantFollowArgs a;
+  PlantTable T;
+  WrenchTable W;
+  PayloadTable M;
+  const double* dobs;
+  ActuatorTable A;
+  JointTable J;
+  TerrainTable R;
+};
+// the library's two families: without a table (reads C.a alone) and with the parameter table (C.a and C.T)
+void launch_plant_follow(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const PlantCall& C, hipStream_t st);
+void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const h1::DynParams& dyn, const PlantCall& C, hipStream_t st);
+// The six families above live in a module each, libilqr_hip_<stem>.so (plant_kernels.hip compiled with -DPLANT_<STEM>_MODULE; stems wrench,
+// payload, observe, actuator, joints, terrain), which the C API opens on first use.  Entry points, C linkage, of every module:
+//   int  ilqr_<stem>_module_set_attr()                          plant_set_attr_fn: the LDS attributes of its kernels on the current device
+//   void ilqr_<stem>_module_follow(S, Pl, dyn, call, stream)    plant_follow_fn: the module's followed plant kernel
+// and beside them
+//   wrench, payload, joints   void ilqr_<stem>_module_step(count, x, u, dyn, xn, stance_l, stance_r, wrench[count][9], payload[count][10], joints[count][76], stream)
+//                             plant_step_fn: one two-lane step per item (launch_step_s with explicit stance flags) under the item's wrench (F, T,
+//                             r), payload and joint record.  A module ignores the arrays its kernel does not take (wrench: payload and joints;
+//                             payload: joints); in the payload module wrench may be null, in the joints module wrench and payload: none.
+//   terrain                   void ilqr_terrain_module_step(count, x, u, dyn, xn, terrain[count][3] (z_left, z_right, edge_x), stance_out[count][2], stream)
+//   observe                   void ilqr_observe_module_draw(B, O, interval0, count, delta[count][B][51], stream)     the errors of intervals interval0 .. + count - 1
+//                             void ilqr_observe_module_apply(B, x[B][51], delta[B][51], out[B][51], stream)          out = x [+] delta
+//   actuator                  void ilqr_actuator_module_draw(B, seed, stream0, interval0, count, z[count][B][19], stream)     the normals of intervals interval0 .. + count - 1
+typedef int (*plant_set_attr_fn)();
+typedef void (*plant_follow_fn)(const DevState*, const PlantDev*, const h1::DynParams*, const PlantCall*, hipStream_t);
+typedef void (*plant_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, int, int, const double*, const double*, const double*, hipStream_t);
 typedef void (*terrain_step_fn)(int, const double*, const double*, const h1::DynParams*, double*, const double*, int*, hipStream_t);
+typedef void (*observe_draw_fn)(int, const ObservationTable*, long, int, double*, hipStream_t);
+typedef void (*observe_apply_fn)(int, const double*, const double*, double*, hipStream_t);
+typedef void (*actuator_draw_fn)(int, unsigned long long, unsigned long long, long, int, double*, hipStream_t);
 // ---- riccati_mfma.hip (four waves per rollout) / riccati_wave.hip (one wave per rollout, standard layout)
 void launch_backward_mfma(const DevState& S, int mode, hipStream_t st);
 int backward_mfma_set_attr();

@@ -12,7 +12,12 @@
 // with parameter, wrench and payload tables (k_plant_follow_m), with those three under an observation table (k_plant_follow_o), and with
 // those four under an actuator table (k_plant_follow_a), and with those five under a joint table (k_plant_follow_j); an eighth time, with
 // those six under a terrain table (k_plant_follow_t), by the terrain module.
+// The host side is written once, at the end of the file: every family is launched from one call record (ilqr_kernels.h PlantCall) by one
+// launcher, its dynamic LDS and the kernel arguments behind the common ones built up family by family (follow_lds, follow_tail), and a
+// module exports the same entry points under its own stem.
 #include <hip/hip_runtime.h>
+
+#include <tuple>
 
 #include "h1_cost_dev.h"
 #define ABA_FENCE          // as dyn_split_kernels.hip: the step is compiled under the same switches there and here
@@ -26,7 +31,7 @@ namespace ilqr {
 
 // This file is compiled eight times (csrc/Makefile): into the library, as everything but the wrench family; and with -DPLANT_WRENCH_MODULE into
 // libilqr_hip_wrench.so, as the wrench family alone (k_plant_follow_w, k_step_w and the wrench-carrying copies of the non-inlined steps),
-// which the C API opens on first use (ilqr_capi.hip wrench_module).  The family is 1.0 MB of code that both the product and the test
+// which the C API opens on first use (ilqr_capi.hip MODULE_DESC). The family is 1.0 MB of code that both the product and the test
 // library would carry; the product library has to stay below 0.8 of the test library (tests/test_gpu_configs.py), which 0.17 MB would
 // have used up.  One module serves both libraries: the plant runs on the two-lane step whatever the handle's family.
 // A third compilation, -DPLANT_PAYLOAD_MODULE into libilqr_hip_payload.so, is the payload family alone (k_plant_follow_m, k_step_m and the
@@ -55,6 +60,50 @@ namespace ilqr {
 #if defined(PLANT_WRENCH_MODULE) || defined(PLANT_PAYLOAD_MODULE) || defined(PLANT_OBSERVE_MODULE) || defined(PLANT_ACTUATOR_MODULE) || defined(PLANT_JOINTS_MODULE) || defined(PLANT_LOWER_FAMILIES)
 #define PLANT_MODULE         // a module: none of the library's own kernels and launchers
 #endif
+// What a module compilation holds, named ONCE for the launchers at the end of this file: the number of its followed family (the
+// PLANT_TABLE of plant_follow_body.h), that kernel, the stem of its exported symbols ilqr_<stem>_module_<entry>, and -- where it has a
+// per-item step kernel under explicit stance flags -- that kernel, its LDS bytes and what it takes of the entry point's (wrench, payload,
+// joints).  The library holds families 0 and 1 and the advance.
+#if defined(PLANT_WRENCH_MODULE)
+#define PLANT_FAMILY 2
+#define PLANT_FOLLOW_KERNEL k_plant_follow_w
+#define PLANT_STEM wrench
+#define PLANT_STEP_KERNEL k_step_w
+#define PLANT_STEP_LDS_BYTES STEP_W_LDS_BYTES
+#define PLANT_STEP_TAIL wrench
+#elif defined(PLANT_PAYLOAD_MODULE)
+#define PLANT_FAMILY 3
+#define PLANT_FOLLOW_KERNEL k_plant_follow_m
+#define PLANT_STEM payload
+#define PLANT_STEP_KERNEL k_step_m
+#define PLANT_STEP_LDS_BYTES STEP_M_LDS_BYTES
+#define PLANT_STEP_TAIL wrench, payload
+#elif defined(PLANT_OBSERVE_MODULE)
+#define PLANT_FAMILY 4
+#define PLANT_FOLLOW_KERNEL k_plant_follow_o
+#define PLANT_STEM observe
+#elif defined(PLANT_ACTUATOR_MODULE)
+#define PLANT_FAMILY 5
+#define PLANT_FOLLOW_KERNEL k_plant_follow_a
+#define PLANT_STEM actuator
+#elif defined(PLANT_JOINTS_MODULE)
+#define PLANT_FAMILY 6
+#define PLANT_FOLLOW_KERNEL k_plant_follow_j
+#define PLANT_STEM joints
+#define PLANT_STEP_KERNEL k_step_j
+#define PLANT_STEP_LDS_BYTES STEP_J_LDS_BYTES
+#define PLANT_STEP_TAIL wrench, payload, joints
+#elif defined(PLANT_TERRAIN_MODULE)
+#define PLANT_FAMILY 7
+#define PLANT_FOLLOW_KERNEL k_plant_follow_t
+#define PLANT_STEM terrain
+#define PLANT_STEP_KERNEL k_step_t      // (decides its own stance flags: an entry point of its own shape, no PLANT_STEP_TAIL)
+#define PLANT_STEP_LDS_BYTES STEP_T_LDS_BYTES
+#endif
+// sizes of the tables' records in doubles, for the kernels that stage them and for follow_lds (h1s::DIST_REC and h1s::JOINT_REC: h1_aba_split.h)
+#define PLANT_REC 8
+#define WRENCH_REC 16
+#define TERRAIN_REC 8
 #include "dyn_step_shared.h"
 
 // LDS of a workgroup, in doubles: the dynamics scratch of the step (LDS_SLOTS x 64, at the base: the non-inlined steps address it there),
@@ -255,7 +304,6 @@ DEVFN void zero_half_u(h1s::HalfU& u) {
 // opaque lane index, right before the step: nothing of the record is live across the control law or from one substep to the next.
 // There is no k_plant_advance_p: with a table an advance is the followed kernel over one interval, which is an advance bit for bit
 // (GPU tests of plant_follow); a second family of twelve kernels would be a further 0.5 MB of code for a path that is not the fast one.
-#define PLANT_REC 8
 template <int RPW>
 DEVFN void stage_plant_records(const DevState& S, double* rows, int b0, const double* ptab, int rec_stride) {
   for (int e = threadIdx.x; e < RPW * PLANT_REC; e += 64) {
@@ -298,7 +346,6 @@ DEVFN void plant_step_table(bool side, h1s::HalfX& h, const h1s::HalfU& u, const
 // an interval outside the window.  A substep hands the step the offset of one of the two rows, so the window costs no second code path
 // and a wrench of zero is the arithmetic of a table whose window is shut.  The kernel always reads a parameter record: without a
 // parameter table the caller passes one record of the handle's own values with gain 1.
-#define WRENCH_REC 16
 template <int RPW>
 DEVFN void stage_wrench_records(const DevState& S, double* rows, int b0, const double* wtab, int wr_stride) {
   for (int e = threadIdx.x; e < (RPW + 1) * WRENCH_REC; e += 64) {
@@ -674,7 +721,6 @@ __global__ void __launch_bounds__(256) k_actuator_draw(int B, unsigned long long
 // z_left, z_right (the floor's height under each foot), edge_x (the height holds for a foot whose ankle-link origin has world x >= edge_x;
 // -inf: everywhere), the window [first, end) in plant intervals, three doubles of padding -- or ONE record that every rollout reads (t_stride = 0).
 // Staged in LDS once per launch behind the joint rows, consecutive lanes on consecutive doubles (2 KB at FB = 0, 256 B at FB = 1).
-#define TERRAIN_REC 8
 template <int RPW>
 DEVFN void stage_terrain_records(const DevState& S, double* rows, int b0, const double* ttab, int t_stride) {
   for (int e = threadIdx.x; e < RPW * TERRAIN_REC; e += 64) {
@@ -740,21 +786,94 @@ __global__ void __launch_bounds__(64) k_step_t(int count, const double* x, const
 }
 #endif
 
-struct FollowArgs { const int* sched; long sched_stride; int geom, substeps, kick, k0, count; long hist_row0, hist_cap; };
+// ---- The host side of the followed kernels, ONE of each piece for the eight families.  FAMILY is the PLANT_TABLE the kernel was included
+// with; a family is the one below it plus its own rows of LDS and its own kernel arguments, and both are written down that way.
+// Dynamic LDS of a workgroup in bytes, term by term as plant_follow_body.h lays the rows out behind FollowLayout.
+template <int FAMILY, int FB> static constexpr size_t follow_lds() {
+  constexpr int RPW = FollowLayout<FB>::RPW;
+  int d = FollowLayout<FB>::DOUBLES;
+  if (FAMILY >= 1) d += RPW * PLANT_REC;                  // the parameter records
+  if (FAMILY == 2) d += (RPW + 1) * WRENCH_REC;           // the wrench records and the zero row
+  if (FAMILY >= 3) d += 2 * RPW * h1s::DIST_REC;          // in their place, two disturbance rows per rollout
+  if (FAMILY >= 4) d += RPW * PLANT_NX;                   // the observed rows XO
+  if (FAMILY >= 5) d += RPW * PLANT_NU;                   // the applied rows UA
+  if (FAMILY >= 6) d += RPW * h1s::JOINT_REC;             // the joint records
+  if (FAMILY >= 7) d += RPW * TERRAIN_REC;                // the terrain records
+  return d * sizeof(double);
+}
+// A slip in the sum above is an access outside the workgroup's LDS and not a failing test, so every family's bytes are pinned, {FB 0, FB 1}.
+template <int FAMILY> static constexpr bool follow_lds_is(size_t fb0, size_t fb1) { return follow_lds<FAMILY, 0>() == fb0 && follow_lds<FAMILY, 1>() == fb1 && fb0 <= 160 * 1024 && fb1 <= 160 * 1024; }
+static_assert(follow_lds_is<0>(76800, 78080) && follow_lds_is<1>(78848, 78336) && follow_lds_is<2>(83072, 78976) && follow_lds_is<3>(91136, 79872), "k_plant_follow .. _m: the workgroup's LDS");
+static_assert(follow_lds_is<4>(104192, 81504) && follow_lds_is<5>(109056, 82112) && follow_lds_is<6>(129536, 84672) && follow_lds_is<7>(131584, 84928), "k_plant_follow_o .. _t: the workgroup's LDS");
+// the kernel: a compilation holds the library's two families or one module's
+template <int FAMILY, int KIND, int FB> static constexpr auto follow_kernel() {
+#ifdef PLANT_MODULE
+  static_assert(FAMILY == PLANT_FAMILY, "a module holds one family");
+  return &PLANT_FOLLOW_KERNEL<KIND, FB>;
+#else
+  static_assert(FAMILY == 0 || FAMILY == 1, "the library holds the table-free and the parameter family");
+  if constexpr (FAMILY == 0) return &k_plant_follow<KIND, FB>;
+  else return &k_plant_follow_p<KIND, FB>;
+#endif
+}
+// the kernel arguments behind hist_cap (PLANT_TABLE_PARAMS of plant_follow_body.h)
+template <int FAMILY> static auto follow_tail(const PlantCall& c) {
+  if constexpr (FAMILY == 0) return std::tuple<>{};
+  else {
+    const auto below = follow_tail<FAMILY - 1>(c);
+    if constexpr (FAMILY == 1) return std::tuple_cat(below, std::make_tuple(c.T.records, c.T.rec_stride));
+    else if constexpr (FAMILY == 2) return std::tuple_cat(below, std::make_tuple(c.W.records, c.W.rec_stride, c.W.interval0));
+    else if constexpr (FAMILY == 3) return std::tuple_cat(below, std::make_tuple(c.M.records, c.M.rec_stride));
+    else if constexpr (FAMILY == 4) return std::tuple_cat(below, std::make_tuple(c.dobs));
+    else if constexpr (FAMILY == 5) return std::tuple_cat(below, std::make_tuple(c.A.records, c.A.rec_stride, c.A.blend, c.A.blend_stride, c.A.z, c.A.fifo, c.A.y, c.A.applied, c.A.substep0));
+    else if constexpr (FAMILY == 6) return std::tuple_cat(below, std::make_tuple(c.J.records, c.J.rec_stride));
+    else return std::tuple_cat(below, std::make_tuple(c.R.records, c.R.rec_stride));
+  }
+}
+template <class... Tail> using follow_kernel_fn = void (*)(DevState, PlantDev, DynParams, const int*, long, int, int, int, int, int, long, long, Tail...);
+template <int FAMILY, int KIND, int FB>
+static void follow_launch(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantCall& c, hipStream_t st) {
+  const dim3 grid((unsigned)((S.B + FollowLayout<FB>::RPW - 1) / FollowLayout<FB>::RPW));
+  const PlantFollowArgs& a = c.a;
+  std::apply([&](auto... tail) {
+    constexpr auto kernel = follow_kernel<FAMILY, KIND, FB>();
+    static_assert(std::is_same_v<decltype(kernel), const follow_kernel_fn<decltype(tail)...>>, "follow_tail: not the kernel's argument list");
+    hipLaunchKernelGGL(kernel, grid, dim3(64), (follow_lds<FAMILY, FB>()), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.first_knot, a.count, a.hist_row0, a.hist_cap, tail...);
+  }, follow_tail<FAMILY>(c));
+}
+template <int FAMILY>
+static void launch_follow(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantCall& c, hipStream_t st) {
+  with_step_kind(dyn, [&](auto K) {
+    if (c.a.feedback_mode) follow_launch<FAMILY, K(), 1>(S, Pl, dyn, c, st);
+    else follow_launch<FAMILY, K(), 0>(S, Pl, dyn, c, st);
+  });
+}
+static int lds_attr(const void* kernel, size_t bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess; }
+template <int FAMILY, int KIND, int FB> static int follow_attr() { return lds_attr((const void*)follow_kernel<FAMILY, KIND, FB>(), follow_lds<FAMILY, FB>()); }
+// the LDS attributes of every kernel of this compilation: per step kind its followed kernels at both feedback modes (the library: behind
+// the advance of that mode), then its step kernel where it has one.  This is the first use of every kernel in the file, so the order here
+// is the order of the kernels in the code object.
 #ifndef PLANT_MODULE
-template <int KIND, int FB> static int plant_attr() {
-  return hipFuncSetAttribute((const void*)k_plant_advance<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PlantLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess ||
-         hipFuncSetAttribute((const void*)k_plant_follow<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FollowLayout<FB>::DOUBLES * sizeof(double))) != hipSuccess;
-}
-template <int FB> static constexpr size_t follow_lds_p() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC) * sizeof(double); }
-template <int KIND, int FB> static int plant_attr_p() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_p<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_p<FB>()) != hipSuccess;
-}
+template <int KIND, int FB> static int advance_attr() { return lds_attr((const void*)k_plant_advance<KIND, FB>, PlantLayout<FB>::DOUBLES * sizeof(double)); }
 int plant_kernels_set_attr() {
+#else
+static int module_kernels_set_attr() {      // (exported with C linkage, below)
+#endif
   int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr<K(), 0>(); rc |= plant_attr<K(), 1>(); rc |= plant_attr_p<K(), 0>(); rc |= plant_attr_p<K(), 1>(); });
+  for_each_step_kind([&](auto K) {
+#ifndef PLANT_MODULE
+    rc |= advance_attr<K(), 0>(); rc |= follow_attr<0, K(), 0>(); rc |= advance_attr<K(), 1>(); rc |= follow_attr<0, K(), 1>();
+    rc |= follow_attr<1, K(), 0>(); rc |= follow_attr<1, K(), 1>();
+#else
+    rc |= follow_attr<PLANT_FAMILY, K(), 0>(); rc |= follow_attr<PLANT_FAMILY, K(), 1>();
+#endif
+#ifdef PLANT_STEP_KERNEL
+    rc |= lds_attr((const void*)PLANT_STEP_KERNEL<K()>, PLANT_STEP_LDS_BYTES);
+#endif
+  });
   return rc;
 }
+#ifndef PLANT_MODULE
 template <int KIND, int FB>
 static void plant_launch(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int kick, long hist_row, hipStream_t st) {
   typedef PlantLayout<FB> Lay;
@@ -768,324 +887,51 @@ void launch_plant_advance(const DevState& S, const PlantDev& Pl, const DynParams
     else plant_launch<K(), 0>(S, Pl, dyn, sched, sched_stride, geom, substeps, kick, hist_row, st);
   });
 }
-
-template <int KIND, int FB>
-static void follow_launch(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow<KIND, FB>), grid, dim3(64), Lay::DOUBLES * sizeof(double), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap);
-}
-void launch_plant_follow(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode, int kick, int first_knot, int count,
-                         long hist_row0, long hist_cap, hipStream_t st) {
-  const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (feedback_mode) follow_launch<K(), 1>(S, Pl, dyn, a, st);
-    else follow_launch<K(), 0>(S, Pl, dyn, a, st);
-  });
-}
-
-template <int KIND, int FB>
-static void follow_launch_p(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_p<KIND, FB>), grid, dim3(64), follow_lds_p<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride);
-}
-void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const int* sched, long sched_stride, int geom, int substeps, int feedback_mode,
-                                int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st) {
-  const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (feedback_mode) follow_launch_p<K(), 1>(S, Pl, dyn, T, a, st);
-    else follow_launch_p<K(), 0>(S, Pl, dyn, T, a, st);
-  });
-}
-#elif defined(PLANT_PAYLOAD_MODULE)      // attributes and launchers of the payload family, exported from its module with C linkage (ilqr_kernels.h)
-template <int FB> static constexpr size_t follow_lds_m() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC) * sizeof(double); }
-template <int KIND, int FB> static int plant_attr_m() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_m<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_m<FB>()) != hipSuccess;
-}
-template <int KIND> static int step_attr_m() {
-  return hipFuncSetAttribute((const void*)k_step_m<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_M_LDS_BYTES) != hipSuccess;
-}
-static int payload_kernels_set_attr() {
-  int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr_m<K(), 0>(); rc |= plant_attr_m<K(), 1>(); rc |= step_attr_m<K()>(); });
-  return rc;
-}
-template <int KIND, int FB>
-static void follow_launch_m(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_m<KIND, FB>), grid, dim3(64), follow_lds_m<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride);
-}
-static void launch_plant_follow_payload(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const WrenchFollowArgs& w, hipStream_t st) {
-  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (w.feedback_mode) follow_launch_m<K(), 1>(S, Pl, dyn, T, W, M, a, st);
-    else follow_launch_m<K(), 0>(S, Pl, dyn, T, W, M, a, st);
-  });
-}
-static void launch_step_payload(int count, const double* x, const double* u, const DynParams& dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload, hipStream_t st) {
-  const dim3 grid((unsigned)((count + 31) / 32));
-  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_m<K()>), grid, dim3(64), STEP_M_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench, payload); });
-}
-#elif defined(PLANT_OBSERVE_MODULE)      // attributes and launchers of the observation family, exported from its module with C linkage (ilqr_kernels.h)
-template <int FB> static constexpr size_t follow_lds_o() {
-  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX) * sizeof(double);
-}
-static_assert(follow_lds_o<0>() <= 160 * 1024 && follow_lds_o<1>() <= 160 * 1024, "k_plant_follow_o: the workgroup's LDS");
-template <int KIND, int FB> static int plant_attr_o() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_o<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_o<FB>()) != hipSuccess;
-}
-static int observe_kernels_set_attr() {
-  int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr_o<K(), 0>(); rc |= plant_attr_o<K(), 1>(); });
-  return rc;
-}
-template <int KIND, int FB>
-static void follow_launch_o(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_o<KIND, FB>), grid, dim3(64), follow_lds_o<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs);
-}
-static void launch_plant_follow_observe(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const WrenchFollowArgs& w,
-                                        hipStream_t st) {
-  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (w.feedback_mode) follow_launch_o<K(), 1>(S, Pl, dyn, T, W, M, dobs, a, st);
-    else follow_launch_o<K(), 0>(S, Pl, dyn, T, W, M, dobs, a, st);
-  });
-}
-static void launch_observation_draw(int B, const ObservationTable& O, long interval0, int count, double* out, hipStream_t st) {
-  const dim3 grid((unsigned)((B + OBS_RPB - 1) / OBS_RPB), (unsigned)count);
-  hipLaunchKernelGGL(k_observation_draw, grid, dim3(256), 0, st, B, O.records, O.rec_stride, O.seed, O.stream0, interval0, out);
-}
-static void launch_observe_apply(int B, const double* x, const double* delta, double* out, hipStream_t st) {
-  const dim3 grid((unsigned)(((long)B * PLANT_NX + 255) / 256));
-  hipLaunchKernelGGL(k_observe_apply, grid, dim3(256), 0, st, B, x, delta, out);
-}
-#elif defined(PLANT_ACTUATOR_MODULE)      // attributes and launchers of the actuator family, exported from its module with C linkage (ilqr_kernels.h)
-template <int FB> static constexpr size_t follow_lds_a() {
-  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX + FollowLayout<FB>::RPW * PLANT_NU) * sizeof(double);
-}
-static_assert(follow_lds_a<0>() <= 160 * 1024 && follow_lds_a<1>() <= 160 * 1024, "k_plant_follow_a: the workgroup's LDS");
-template <int KIND, int FB> static int plant_attr_a() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_a<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_a<FB>()) != hipSuccess;
-}
-static int actuator_kernels_set_attr() {
-  int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr_a<K(), 0>(); rc |= plant_attr_a<K(), 1>(); });
-  return rc;
-}
-template <int KIND, int FB>
-static void follow_launch_a(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const ActuatorTable& A,
-                            const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_a<KIND, FB>), grid, dim3(64), follow_lds_a<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs, A.records, A.rec_stride, A.blend, A.blend_stride, A.z, A.fifo, A.y, A.applied,
-                     A.substep0);
-}
-static void launch_plant_follow_actuator(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs,
-                                         const ActuatorTable& A, const WrenchFollowArgs& w, hipStream_t st) {
-  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (w.feedback_mode) follow_launch_a<K(), 1>(S, Pl, dyn, T, W, M, dobs, A, a, st);
-    else follow_launch_a<K(), 0>(S, Pl, dyn, T, W, M, dobs, A, a, st);
-  });
-}
-static void launch_actuator_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, int count, double* out, hipStream_t st) {
-  const dim3 grid((unsigned)((B + ACT_RPB - 1) / ACT_RPB), (unsigned)count);
-  hipLaunchKernelGGL(k_actuator_draw, grid, dim3(256), 0, st, B, seed, stream0, interval0, out);
-}
-#elif defined(PLANT_JOINTS_MODULE)      // attributes and launchers of the joints family, exported from its module with C linkage (ilqr_kernels.h)
-template <int FB> static constexpr size_t follow_lds_j() {
-  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX + FollowLayout<FB>::RPW * PLANT_NU +
-          FollowLayout<FB>::RPW * h1s::JOINT_REC) * sizeof(double);
-}
-static_assert(follow_lds_j<0>() <= 160 * 1024 && follow_lds_j<1>() <= 160 * 1024, "k_plant_follow_j: the workgroup's LDS");
-template <int KIND, int FB> static int plant_attr_j() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_j<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_j<FB>()) != hipSuccess;
-}
-template <int KIND> static int step_attr_j() {
-  return hipFuncSetAttribute((const void*)k_step_j<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_J_LDS_BYTES) != hipSuccess;
-}
-static int joints_kernels_set_attr() {
-  int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr_j<K(), 0>(); rc |= plant_attr_j<K(), 1>(); rc |= step_attr_j<K()>(); });
-  return rc;
-}
-template <int KIND, int FB>
-static void follow_launch_j(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const ActuatorTable& A,
-                            const JointTable& J, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_j<KIND, FB>), grid, dim3(64), follow_lds_j<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs, A.records, A.rec_stride, A.blend, A.blend_stride, A.z, A.fifo, A.y, A.applied,
-                     A.substep0, J.records, J.rec_stride);
-}
-static void launch_plant_follow_joints(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs,
-                                       const ActuatorTable& A, const JointTable& J, const WrenchFollowArgs& w, hipStream_t st) {
-  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (w.feedback_mode) follow_launch_j<K(), 1>(S, Pl, dyn, T, W, M, dobs, A, J, a, st);
-    else follow_launch_j<K(), 0>(S, Pl, dyn, T, W, M, dobs, A, J, a, st);
-  });
-}
-static void launch_step_joints(int count, const double* x, const double* u, const DynParams& dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload,
-                               const double* joints, hipStream_t st) {
-  const dim3 grid((unsigned)((count + 31) / 32));
-  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_j<K()>), grid, dim3(64), STEP_J_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench, payload, joints); });
-}
-#elif defined(PLANT_TERRAIN_MODULE)      // attributes and launchers of the terrain family, exported from its module with C linkage (ilqr_kernels.h)
-template <int FB> static constexpr size_t follow_lds_t() {
-  return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + 2 * FollowLayout<FB>::RPW * h1s::DIST_REC + FollowLayout<FB>::RPW * PLANT_NX + FollowLayout<FB>::RPW * PLANT_NU +
-          FollowLayout<FB>::RPW * h1s::JOINT_REC + FollowLayout<FB>::RPW * TERRAIN_REC) * sizeof(double);
-}
-static_assert(follow_lds_t<0>() <= 160 * 1024 && follow_lds_t<1>() <= 160 * 1024, "k_plant_follow_t: the workgroup's LDS");
-template <int KIND, int FB> static int plant_attr_t() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_t<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_t<FB>()) != hipSuccess;
-}
-template <int KIND> static int step_attr_t() {
-  return hipFuncSetAttribute((const void*)k_step_t<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_T_LDS_BYTES) != hipSuccess;
-}
-static int terrain_kernels_set_attr() {
-  int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr_t<K(), 0>(); rc |= plant_attr_t<K(), 1>(); rc |= step_attr_t<K()>(); });
-  return rc;
-}
-template <int KIND, int FB>
-static void follow_launch_t(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs, const ActuatorTable& A,
-                            const JointTable& J, const TerrainTable& R, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_t<KIND, FB>), grid, dim3(64), follow_lds_t<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0, M.records, M.rec_stride, dobs, A.records, A.rec_stride, A.blend, A.blend_stride, A.z, A.fifo, A.y, A.applied,
-                     A.substep0, J.records, J.rec_stride, R.records, R.rec_stride);
-}
-static void launch_plant_follow_terrain(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const PayloadTable& M, const double* dobs,
-                                        const ActuatorTable& A, const JointTable& J, const TerrainTable& R, const WrenchFollowArgs& w, hipStream_t st) {
-  const FollowArgs a{w.sched, w.sched_stride, w.geom, w.substeps, w.kick, w.first_knot, w.count, w.hist_row0, w.hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (w.feedback_mode) follow_launch_t<K(), 1>(S, Pl, dyn, T, W, M, dobs, A, J, R, a, st);
-    else follow_launch_t<K(), 0>(S, Pl, dyn, T, W, M, dobs, A, J, R, a, st);
-  });
-}
-static void launch_step_terrain(int count, const double* x, const double* u, const DynParams& dyn, double* xn, const double* terrain, int* stance_out, hipStream_t st) {
-  const dim3 grid((unsigned)((count + 31) / 32));
-  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_t<K()>), grid, dim3(64), STEP_T_LDS_BYTES, st, count, x, u, dyn, xn, terrain, stance_out); });
-}
-#else      // PLANT_WRENCH_MODULE: attributes and launchers of the wrench family, exported from the module with C linkage (ilqr_kernels.h)
-template <int FB> static constexpr size_t follow_lds_w() { return (FollowLayout<FB>::DOUBLES + FollowLayout<FB>::RPW * PLANT_REC + (FollowLayout<FB>::RPW + 1) * WRENCH_REC) * sizeof(double); }
-template <int KIND, int FB> static int plant_attr_w() {
-  return hipFuncSetAttribute((const void*)k_plant_follow_w<KIND, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)follow_lds_w<FB>()) != hipSuccess;
-}
-template <int KIND> static int step_attr_w() {
-  return hipFuncSetAttribute((const void*)k_step_w<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_W_LDS_BYTES) != hipSuccess;
-}
-static int wrench_kernels_set_attr() {
-  int rc = 0;
-  for_each_step_kind([&](auto K) { rc |= plant_attr_w<K(), 0>(); rc |= plant_attr_w<K(), 1>(); rc |= step_attr_w<K()>(); });
-  return rc;
-}
-template <int KIND, int FB>
-static void follow_launch_w(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const FollowArgs& a, hipStream_t st) {
-  typedef FollowLayout<FB> Lay;
-  const dim3 grid((unsigned)((S.B + Lay::RPW - 1) / Lay::RPW));
-  hipLaunchKernelGGL((k_plant_follow_w<KIND, FB>), grid, dim3(64), follow_lds_w<FB>(), st, S, Pl, dyn, a.sched, a.sched_stride, a.geom, a.substeps, a.kick, a.k0, a.count, a.hist_row0, a.hist_cap,
-                     T.records, T.rec_stride, W.records, W.rec_stride, W.interval0);
-}
-static void launch_plant_follow_wrench(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantTable& T, const WrenchTable& W, const int* sched, long sched_stride, int geom, int substeps,
-                                int feedback_mode, int kick, int first_knot, int count, long hist_row0, long hist_cap, hipStream_t st) {
-  const FollowArgs a{sched, sched_stride, geom, substeps, kick, first_knot, count, hist_row0, hist_cap};
-  with_step_kind(dyn, [&](auto K) {
-    if (feedback_mode) follow_launch_w<K(), 1>(S, Pl, dyn, T, W, a, st);
-    else follow_launch_w<K(), 0>(S, Pl, dyn, T, W, a, st);
-  });
-}
-static void launch_step_wrench(int count, const double* x, const double* u, const DynParams& dyn, double* xn, int stance_l, int stance_r, const double* wrench, hipStream_t st) {
-  const dim3 grid((unsigned)((count + 31) / 32));
-  with_step_kind(dyn, [&](auto K) { hipLaunchKernelGGL((k_step_w<K()>), grid, dim3(64), STEP_W_LDS_BYTES, st, count, x, u, dyn, xn, stance_l, stance_r, wrench); });
-}
+void launch_plant_follow(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantCall& C, hipStream_t st) { launch_follow<0>(S, Pl, dyn, C, st); }
+void launch_plant_follow_params(const DevState& S, const PlantDev& Pl, const DynParams& dyn, const PlantCall& C, hipStream_t st) { launch_follow<1>(S, Pl, dyn, C, st); }
 #endif
 
 }  // namespace ilqr
 
-#ifdef PLANT_WRENCH_MODULE
+// ---- the entry points of a module, C linkage (ilqr_kernels.h): ilqr_<stem>_module_<entry>
+#ifdef PLANT_MODULE
+#define PLANT_ENTRY_(stem, entry) ilqr_##stem##_module_##entry
+#define PLANT_ENTRY_OF(stem, entry) PLANT_ENTRY_(stem, entry)
+#define PLANT_ENTRY(entry) PLANT_ENTRY_OF(PLANT_STEM, entry)
 extern "C" {
-int ilqr_wrench_module_set_attr() { return ilqr::wrench_kernels_set_attr(); }
-void ilqr_wrench_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
-  ilqr::launch_plant_follow_wrench(*S, *Pl, *dyn, *T, *W, a->sched, a->sched_stride, a->geom, a->substeps, a->feedback_mode, a->kick, a->first_knot, a->count, a->hist_row0, a->hist_cap, st);
+int PLANT_ENTRY(set_attr)() { return ilqr::module_kernels_set_attr(); }
+void PLANT_ENTRY(follow)(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantCall* call, hipStream_t st) {
+  ilqr::launch_follow<PLANT_FAMILY>(*S, *Pl, *dyn, *call, st);
 }
-void ilqr_wrench_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, hipStream_t st) {
-  ilqr::launch_step_wrench(count, x, u, *dyn, xn, stance_l, stance_r, wrench, st);
-}
+#ifdef PLANT_STEP_TAIL
+// one two-lane step per item under explicit stance flags: of (wrench, payload, joints) the kernel takes PLANT_STEP_TAIL
+void PLANT_ENTRY(step)(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload, const double* joints,
+                       hipStream_t st) {
+  const dim3 grid((unsigned)((count + 31) / 32));
+  ilqr::with_step_kind(*dyn, [&](auto K) { hipLaunchKernelGGL((ilqr::PLANT_STEP_KERNEL<K()>), grid, dim3(64), PLANT_STEP_LDS_BYTES, st, count, x, u, *dyn, xn, stance_l, stance_r, PLANT_STEP_TAIL); });
 }
 #endif
-
-#ifdef PLANT_PAYLOAD_MODULE
-extern "C" {
-int ilqr_payload_module_set_attr() { return ilqr::payload_kernels_set_attr(); }
-void ilqr_payload_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
-                                const ilqr::WrenchFollowArgs* a, hipStream_t st) {
-  ilqr::launch_plant_follow_payload(*S, *Pl, *dyn, *T, *W, *M, *a, st);
-}
-void ilqr_payload_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload, hipStream_t st) {
-  ilqr::launch_step_payload(count, x, u, *dyn, xn, stance_l, stance_r, wrench, payload, st);
-}
-}
-#endif
-
-#ifdef PLANT_OBSERVE_MODULE
-extern "C" {
-int ilqr_observe_module_set_attr() { return ilqr::observe_kernels_set_attr(); }
-void ilqr_observe_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
-                                const double* delta, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
-  ilqr::launch_plant_follow_observe(*S, *Pl, *dyn, *T, *W, *M, delta, *a, st);
-}
-void ilqr_observe_module_draw(int B, const ilqr::ObservationTable* O, long interval0, int count, double* delta, hipStream_t st) { ilqr::launch_observation_draw(B, *O, interval0, count, delta, st); }
-void ilqr_observe_module_apply(int B, const double* x, const double* delta, double* out, hipStream_t st) { ilqr::launch_observe_apply(B, x, delta, out, st); }
-}
-#endif
-
-#ifdef PLANT_ACTUATOR_MODULE
-extern "C" {
-int ilqr_actuator_module_set_attr() { return ilqr::actuator_kernels_set_attr(); }
-void ilqr_actuator_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
-                                 const double* delta, const ilqr::ActuatorTable* A, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
-  ilqr::launch_plant_follow_actuator(*S, *Pl, *dyn, *T, *W, *M, delta, *A, *a, st);
-}
-void ilqr_actuator_module_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, int count, double* z, hipStream_t st) {
-  ilqr::launch_actuator_draw(B, seed, stream0, interval0, count, z, st);
-}
-}
-#endif
-
-#ifdef PLANT_JOINTS_MODULE
-extern "C" {
-int ilqr_joints_module_set_attr() { return ilqr::joints_kernels_set_attr(); }
-void ilqr_joints_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
-                               const double* delta, const ilqr::ActuatorTable* A, const ilqr::JointTable* J, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
-  ilqr::launch_plant_follow_joints(*S, *Pl, *dyn, *T, *W, *M, delta, *A, *J, *a, st);
-}
-void ilqr_joints_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, int stance_l, int stance_r, const double* wrench, const double* payload,
-                             const double* joints, hipStream_t st) {
-  ilqr::launch_step_joints(count, x, u, *dyn, xn, stance_l, stance_r, wrench, payload, joints, st);
-}
-}
-#endif
-
 #ifdef PLANT_TERRAIN_MODULE
-extern "C" {
-int ilqr_terrain_module_set_attr() { return ilqr::terrain_kernels_set_attr(); }
-void ilqr_terrain_module_follow(const ilqr::DevState* S, const ilqr::PlantDev* Pl, const h1::DynParams* dyn, const ilqr::PlantTable* T, const ilqr::WrenchTable* W, const ilqr::PayloadTable* M,
-                                const double* delta, const ilqr::ActuatorTable* A, const ilqr::JointTable* J, const ilqr::TerrainTable* R, const ilqr::WrenchFollowArgs* a, hipStream_t st) {
-  ilqr::launch_plant_follow_terrain(*S, *Pl, *dyn, *T, *W, *M, delta, *A, *J, *R, *a, st);
-}
 void ilqr_terrain_module_step(int count, const double* x, const double* u, const h1::DynParams* dyn, double* xn, const double* terrain, int* stance_out, hipStream_t st) {
-  ilqr::launch_step_terrain(count, x, u, *dyn, xn, terrain, stance_out, st);
+  const dim3 grid((unsigned)((count + 31) / 32));
+  ilqr::with_step_kind(*dyn, [&](auto K) { hipLaunchKernelGGL((ilqr::k_step_t<K()>), grid, dim3(64), PLANT_STEP_LDS_BYTES, st, count, x, u, *dyn, xn, terrain, stance_out); });
 }
+#endif
+#ifdef PLANT_OBSERVE_MODULE
+void ilqr_observe_module_draw(int B, const ilqr::ObservationTable* O, long interval0, int count, double* delta, hipStream_t st) {
+  const dim3 grid((unsigned)((B + OBS_RPB - 1) / OBS_RPB), (unsigned)count);
+  hipLaunchKernelGGL(ilqr::k_observation_draw, grid, dim3(256), 0, st, B, O->records, O->rec_stride, O->seed, O->stream0, interval0, delta);
+}
+void ilqr_observe_module_apply(int B, const double* x, const double* delta, double* out, hipStream_t st) {
+  const dim3 grid((unsigned)(((long)B * PLANT_NX + 255) / 256));
+  hipLaunchKernelGGL(ilqr::k_observe_apply, grid, dim3(256), 0, st, B, x, delta, out);
+}
+#endif
+#ifdef PLANT_ACTUATOR_MODULE
+void ilqr_actuator_module_draw(int B, unsigned long long seed, unsigned long long stream0, long interval0, int count, double* z, hipStream_t st) {
+  const dim3 grid((unsigned)((B + ACT_RPB - 1) / ACT_RPB), (unsigned)count);
+  hipLaunchKernelGGL(ilqr::k_actuator_draw, grid, dim3(256), 0, st, B, seed, stream0, interval0, z);
+}
+#endif
 }
 #endif

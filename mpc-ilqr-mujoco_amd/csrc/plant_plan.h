@@ -31,11 +31,13 @@ struct PlantPlan {
   bool draw_observation;    // the observation module's draw runs in front of the family's kernel
   bool draw_actuator;       // the actuator module's draw does
   bool self_params;         // the kernels read the handle's own parameter record (plant_self_params): a module family without a parameter table
+  bool pass_joints;         // the kernel is handed the joint table: installed and not all-nominal (only the joints family and above read it)
 };
 
 inline PlantPlan resolve_plant_plan(const PlantTables& t, bool follow) {
   PlantPlan p{};
-  p.family = t.terrain ? PLANT_TERRAIN : (t.joints && !t.joints_nominal) ? PLANT_JOINTS : t.actuator ? PLANT_ACTUATOR : t.observation ? PLANT_OBSERVE : t.payload ? PLANT_PAYLOAD
+  p.pass_joints = t.joints && !t.joints_nominal;
+  p.family = t.terrain ? PLANT_TERRAIN : p.pass_joints ? PLANT_JOINTS : t.actuator ? PLANT_ACTUATOR : t.observation ? PLANT_OBSERVE : t.payload ? PLANT_PAYLOAD
            : t.wrench ? PLANT_WRENCH : t.params ? PLANT_PARAMS : follow ? PLANT_FOLLOW : PLANT_ADVANCE;
   p.draw_observation = t.observation && p.family >= PLANT_OBSERVE;
   p.draw_actuator = t.actuator && p.family >= PLANT_ACTUATOR;

@@ -12,7 +12,7 @@ int main() {
     const PlantTables t{params != 0, wrench != 0, payload != 0, obs != 0, act != 0, joints != 0, nominal != 0};
     const PlantPlan p = resolve_plant_plan(t, follow != 0);
     std::printf("params=%d wrench=%d payload=%d observation=%d actuator=%d joints=%d joints_nominal=%d follow=%d", params, wrench, payload, obs, act, joints, nominal, follow);
-    std::printf(" p.family=%d p.modules=%u p.draw_observation=%d p.draw_actuator=%d p.self_params=%d\n", (int)p.family, p.modules, p.draw_observation, p.draw_actuator, p.self_params);
+    std::printf(" p.family=%d p.modules=%u p.draw_observation=%d p.draw_actuator=%d p.self_params=%d p.pass_joints=%d\n", (int)p.family, p.modules, p.draw_observation, p.draw_actuator, p.self_params, p.pass_joints);
   }
   return 0;
 }

@@ -15,7 +15,7 @@ int main() {
     t.terrain = terrain != 0;
     const PlantPlan p = resolve_plant_plan(t, follow != 0);
     std::printf("terrain=%d params=%d wrench=%d payload=%d observation=%d actuator=%d joints=%d joints_nominal=%d follow=%d", terrain, params, wrench, payload, obs, act, joints, nominal, follow);
-    std::printf(" p.family=%d p.modules=%u p.draw_observation=%d p.draw_actuator=%d p.self_params=%d\n", (int)p.family, p.modules, p.draw_observation, p.draw_actuator, p.self_params);
+    std::printf(" p.family=%d p.modules=%u p.draw_observation=%d p.draw_actuator=%d p.self_params=%d p.pass_joints=%d\n", (int)p.family, p.modules, p.draw_observation, p.draw_actuator, p.self_params, p.pass_joints);
   }
   return 0;
 }

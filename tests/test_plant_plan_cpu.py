@@ -62,6 +62,8 @@ def expected(d):
     # the module families read "the parameter table or the handle's own record": uploaded whenever a table of theirs is installed -- an
     # all-nominal joint table too -- and no parameter table is
     e["p.self_params"] = int(any(d[k] for k in ("wrench", "payload", "observation", "actuator", "joints")) and not d["params"])
+    # the kernel is handed the joint table's records only where the table is one: installed, and not all-nominal
+    e["p.pass_joints"] = int(bool(d["joints"]) and not d["joints_nominal"])
     return e
 
 
@@ -78,6 +80,13 @@ def test_a_nominal_joint_table_alone_is_no_table(rows):
     for d in hit:
         assert d["p.family"] == (FOLLOW if d["follow"] else ADVANCE) and d["p.modules"] == 0
         assert not d["p.draw_observation"] and not d["p.draw_actuator"]
+
+
+def test_the_joint_table_is_passed_iff_installed_and_not_nominal(rows):
+    for d in rows:
+        assert d["p.pass_joints"] == int(d["joints"] and not d["joints_nominal"]), d
+        if d["p.family"] == JOINTS:
+            assert d["p.pass_joints"], d      # the joints family never runs on a null joint table
 
 
 def test_every_module_family_names_its_module(rows):

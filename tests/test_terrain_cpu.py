@@ -334,3 +334,4 @@ def test_plan_with_a_terrain_table_is_the_terrain_family_over_the_tables_below(r
         mods = MOD_TERRAIN | (pp.MOD_OBSERVE if d["observation"] else 0) | (pp.MOD_ACTUATOR if d["actuator"] else 0)
         assert d["p.modules"] == mods, d                       # its own module and the draws': never the joints module's
         assert d["p.self_params"] == int(not d["params"]), d   # a module family reads a parameter record: the table's or the handle's own
+        assert d["p.pass_joints"] == int(d["joints"] and not d["joints_nominal"]), d      # an all-nominal joint table is no table to this family either
