@@ -1123,6 +1123,64 @@ int ilqr_hip_set_repeat_first_pass(ilqr_hip_ctx* ctx, int on);
    handle or a failed read. */
 long long ilqr_hip_get_first_pass_rollouts(ilqr_hip_ctx* ctx);
 
+/* ---- solve groups: several starts per problem, the best one adopted on the device.  iLQR is a local method: after a push, a late touchdown
+   or a bound that has just become active the shifted previous solution can be a poor start.  A handle's batch can be cut into M = B / G
+   groups of G consecutive rollouts; a group stands for ONE problem (one robot) solved from G starting trajectories.  The members of a group
+   share x0, references, schedule and plant tables: that is the caller's business (scenario.repeat_for_groups repeats any per-rollout table
+   member-minor), and so are per-rollout weight sets and bound tables inside a group -- nothing is refused for them; a caller whose members
+   differ in their cost passes a key of its own to group_select.  Member 0 of every group is the incumbent: it is never perturbed, so before
+   the selection it is exactly the plain solve, and a group never does worse per solve than the handle without groups.  One step is
+       warm start -> group_perturb -> solve -> group_select -> group_adopt -> plant_advance / plant_follow
+   and the three group calls are enqueued on the handle's stream and never synchronise.  Their kernels (k_group_perturb, k_group_select,
+   k_group_adopt) live in the module libilqr_hip_groups.so, opened from the library's directory by the first set_groups with G > 1 --
+   missing: ILQR_ERR_UNSUPPORTED with the path in ilqr_hip_last_error, the only refusal of this family.  No reference counterpart.
+   set_groups: G >= 1 and G divides the batch, else ILQR_ERR_ARG.  G = 1 switches the feature off and frees its buffers; G > 1 allocates
+   winner[M] and group_rec[M][4].  Launches no kernel; removes an installed perturbation and forgets the last selection.
+   num_groups: M, 0 while the feature is off, -1 for a null handle.
+   group_set_perturbation: sigma[n_sets][19], one standard deviation per actuator, n_sets = 1 (every member g >= 1 reads row 0) or G (member
+   g reads row g; row 0, the incumbent's, must be all zeros), else ILQR_ERR_ARG; ILQR_ERR_ARG also for a null pointer, an entry that is
+   not finite or negative, or hold < 1; ILQR_ERR_STATE while groups are off.  Uploads, synchronises and sets the draw counter to 0.
+   group_clear_perturbation: removes it (the counter returns to 0).
+   group_draws: the draw counter -- group_perturb calls since the perturbation was installed; -1 for a null handle.
+   group_perturb: for every rollout b with g = b mod G >= 1, every knot t and actuator j
+       ubar[b][t][j] += sigma[row(g)][j] * z(b, floor(t / hold), j),
+   z a standard normal of Philox4x32-10 with key (seed lo, seed hi) and counter (s lo, s hi, draw, k), s = stream0 + b, draw the counter
+   in front of the call: block k gives the normals 2k and 2k + 1 of the sequence index i = floor(t / hold) * 19 + j by the Box-Muller
+   construction of the plant's observation model above.  The product is rounded on its own and then added; a sigma of exactly 0 adds
+   nothing, by selection.  The counter then advances by one.  It is a counter of this family's own: the draws are independent of the
+   plant's observation and actuator streams whatever the seeds, and no plant call moves it.  The call then rolls the members
+   g >= 1 out from (x0, ubar), so that the cost the next solve starts from -- what it reports for a rollout that accepts no step, and what
+   group_select reads -- is the cost of the perturbed controls; the incumbents keep every bit.  Iteration 0 of the next solve rolls every
+   rollout out from (x0, ubar) in front of the linearisation again, in every launch order, as behind a warm start.
+   ILQR_ERR_STATE before an initialize, while groups are off or while no perturbation is installed.
+   group_select: the key of rollout b is key_device[b] (a device array [B] of the caller's) or, with NULL, the cost of the last solve --
+   what ilqr_hip_get_cost reports.  Per group the winner is the member with the smallest finite key, among equal keys the lowest member;
+   NaN and +-inf never win; without a finite key the winner is member 0.  Writes winner[m], a global rollout index, and group_rec[m] =
+   {the winner's key, member 0's key, the number of finite keys, the largest finite key (NaN without one)}.  ILQR_ERR_STATE while groups
+   are off, or with NULL before a solve.
+   group_get_winners: synchronises the handle's stream; winner[M], rec[M][4], either may be NULL.  ILQR_ERR_STATE before a select.
+   group_winners_device: the two device arrays, without synchronising (either pointer may be NULL).
+   group_copy_winners_device: enqueues a copy of winner[M] into a device array of the caller's (a row of a per-step log, read once when
+   the run ends); never synchronises.  ILQR_ERR_STATE before a select.
+   group_adopt: every member of a group receives, bit for bit, the winner's solution state -- what a later call reads about a solved
+   rollout: x0, xbar, ubar, K, kff, the cost, lambda and the iteration count as their getters report them and, per installed family of the
+   augmented Lagrangian, its whole row of the multiplier store (the header with the penalties and every knot record) with its violation
+   and done words.  The diagnostic history stays the member's own: the per-iteration traces, the round traces of the augmented
+   Lagrangian, the work lists and the counters.  Linearisation, quadratics, value function and candidates are not copied: iteration 0 of
+   the next solve recomputes them for every rollout.  Afterwards the handle is in the state "after a solve".  A group whose winner is
+   member 0 keeps every bit.  ILQR_ERR_STATE before a select. */
+int ilqr_hip_set_groups(ilqr_hip_ctx* ctx, int G);
+int ilqr_hip_num_groups(const ilqr_hip_ctx* ctx);
+int ilqr_hip_group_set_perturbation(ilqr_hip_ctx* ctx, int n_sets, const double* sigma /*[n_sets][19]*/, int hold, unsigned long long seed, unsigned long long stream0);
+int ilqr_hip_group_clear_perturbation(ilqr_hip_ctx* ctx);
+long ilqr_hip_group_draws(const ilqr_hip_ctx* ctx);
+int ilqr_hip_group_perturb(ilqr_hip_ctx* ctx);
+int ilqr_hip_group_select(ilqr_hip_ctx* ctx, const double* key_device /*[B] or NULL*/);
+int ilqr_hip_group_get_winners(ilqr_hip_ctx* ctx, int* winner /*[M]*/, double* rec /*[M][4]*/);
+int ilqr_hip_group_winners_device(ilqr_hip_ctx* ctx, const int** winner_device, const double** rec_device);
+int ilqr_hip_group_copy_winners_device(ilqr_hip_ctx* ctx, int* winner_out_device /*[M]*/);
+int ilqr_hip_group_adopt(ilqr_hip_ctx* ctx);
+
 /* ---- host-side model helpers (no GPU needed) ---- */
 /* reference construction as RobotUtils::loadReferences does it (src/common/robot_utils.cpp:369-403):
    whole-body CoM (MuJoCo masses) and world positions of the two ankle bodies */

@@ -20,6 +20,7 @@
 #include "h1_host_model.h"
 #include "ilqr_kernels.h"
 #include "plant_plan.h"
+#include "group_kernels.h"
 #include "solve_order.h"
 #include "plant_score_kernels.h"
 #include "plant_task_score_kernels.h"
@@ -278,6 +279,18 @@ struct ilqr_hip_ctx {
   double* d_track = nullptr;
   int* d_track_start = nullptr;
   int track_rows = 0, track_contact_rows = 0, track_sets = 1, track_max_start = 0;
+  // solve groups (ilqr_hip_set_groups; group_kernels.hip in the module libilqr_hip_groups.so): G consecutive rollouts solve one problem from G
+  // starts.  G = 1: off, no buffer.  winner [M] the global rollout index of each group's winner and rec [M][4] its record (k_group_select;
+  // selected: one has run since the groups were set); sigma [sets][19] on the device while a perturbation is installed (sets 1 or G), with the
+  // hold, seed, first stream and draw counter of k_group_perturb.  All of it is the handle's own: nothing here enters ProblemDev or DevState.
+  struct Groups {
+    int G = 1, sets = 0, hold = 1;
+    int *winner = nullptr, *mask = nullptr;      // mask [B]: 1 for the members g >= 1 (the rollouts group_perturb re-rolls), 0 for the incumbents
+    double *rec = nullptr, *sigma = nullptr;
+    unsigned long long seed = 0, stream0 = 0;
+    long draws = 0;
+    bool selected = false;
+  } grp;
 };
 
 // A failed HIP call: "<the call>: <HIP's message>" into the handle, ILQR_ERR_HIP to the caller.  The message is built out of line: built
@@ -596,6 +609,7 @@ __attribute__((minsize)) int ilqr_hip_destroy(ilqr_hip_ctx* c) {
   { void* gp[] = {S.grp_a, S.grp_r, S.order_r, S.order_rn, S.order_an, S.chg, S.chg_n, S.chg_r, S.chg_rn, S.chg_an, S.chg_f, c->d_fp_gate, S.kr, S.kr_n, S.ls_list, S.ls_kind, c->d_lgate}; for (void* p : gp) if (p) hipFree(p); }
   { void* pl[] = {c->plant.x, c->plant.u, c->plant.dv, c->plant.stance, c->plant.alive, c->plant.hist_x, c->plant.hist_u, c->d_score, c->d_score_terms, c->d_tscore, c->d_tscore_terms, c->d_track, c->d_track_start, c->d_self_params, c->d_stepw, c->d_stepm, c->d_stepj, c->d_stept, c->d_obs_delta, c->d_obs_x, c->d_act_beta, c->d_act_z, c->d_act_fifo, c->d_act_y, c->d_act_applied}; for (void* p : pl) if (p) hipFree(p); }
   for (ilqr_hip_ctx::TableBuf* t : {&c->pparams, &c->wrench, &c->payload, &c->obs, &c->act, &c->joints, &c->terrain}) if (t->d) hipFree(t->d);
+  for (void* p : {(void*)c->grp.winner, (void*)c->grp.rec, (void*)c->grp.sigma, (void*)c->grp.mask}) if (p) hipFree(p);
   for (hipEvent_t e : {c->evA_fork, c->evA_join, c->evA_roll, c->evA_lin, c->evA_adopt}) if (e) hipEventDestroy(e);
   if (c->a1) hipStreamDestroy(c->a1);
   if (c->ev_spec_fork) hipEventDestroy(c->ev_spec_fork);
@@ -3202,6 +3216,131 @@ int ilqr_hip_foot_clearance(const double* qpos, double* clearance) {
 int ilqr_hip_gravity_compensation(const double* x, const double* gravity, double* u) {
   if (!x || !gravity || !u) return ILQR_ERR_ARG;
   h1host::gravity_compensation(x, gravity, u);
+  return ILQR_OK;
+}
+
+// ---------------------------------------------------------------- solve groups (group_kernels.hip, libilqr_hip_groups.so)
+// The module, opened by the first call that switches groups on.  Missing module or entry point: ILQR_ERR_UNSUPPORTED.
+static ilqr::GroupModule g_groups = {};
+__attribute__((noinline, minsize)) static int groups_ready(ilqr_hip_ctx* c) {
+  static ModuleLib lib;
+  const auto resolve = [](void* so, int) { const auto table = (const ilqr::GroupModule* (*)())dlsym(so, "ilqr_groups_module"); if (table) g_groups = *table(); return table != nullptr; };
+  if (!open_module(lib, "groups", "solve groups'", resolve, 0)) { c->err = lib.why; return ILQR_ERR_UNSUPPORTED; }
+  return ILQR_OK;
+}
+// what every group call needs first: groups on (and, where asked, a selection)
+__attribute__((noinline, minsize)) static int groups_on(ilqr_hip_ctx* c, bool selected) {
+  if (c->grp.G < 2) { c->err = "solve groups are off (ilqr_hip_set_groups)"; return ILQR_ERR_STATE; }
+  if (selected && !c->grp.selected) { c->err = "no ilqr_hip_group_select since the groups were set"; return ILQR_ERR_STATE; }
+  enter(c);
+  return ILQR_OK;
+}
+__attribute__((noinline, minsize)) static int groups_drop_perturbation(ilqr_hip_ctx* c) {
+  if (c->grp.sigma) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->grp.sigma); }
+  c->grp.sigma = nullptr; c->grp.sets = 0; c->grp.hold = 1; c->grp.seed = c->grp.stream0 = 0; c->grp.draws = 0;
+  return ILQR_OK;
+}
+__attribute__((minsize)) int ilqr_hip_set_groups(ilqr_hip_ctx* c, int G) {
+  if (!c || G < 1 || c->B % G) return ILQR_ERR_ARG;
+  enter(c);
+  if (G > 1) TRY(groups_ready(c));
+  TRY(groups_drop_perturbation(c));      // (its rows are the old group's members)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (void* p : {(void*)c->grp.winner, (void*)c->grp.rec, (void*)c->grp.mask}) if (p) (void)hipFree(p);
+  c->grp.winner = nullptr; c->grp.rec = nullptr; c->grp.mask = nullptr; c->grp.G = 1; c->grp.selected = false;
+  if (G == 1) return ILQR_OK;
+  TRY(dalloc(c, &c->grp.winner, (size_t)(c->B / G))); TRY(dalloc(c, &c->grp.rec, (size_t)(c->B / G) * 4)); TRY(dalloc(c, &c->grp.mask, (size_t)c->B));
+  std::vector<int> mask((size_t)c->B);
+  for (int b = 0; b < c->B; ++b) mask[b] = (b % G) != 0;
+  HIPCHK(c, hipMemcpyAsync(c->grp.mask, mask.data(), mask.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->grp.G = G;
+  return ILQR_OK;
+}
+int ilqr_hip_num_groups(const ilqr_hip_ctx* c) { return c ? (c->grp.G > 1 ? c->B / c->grp.G : 0) : -1; }
+__attribute__((minsize)) int ilqr_hip_group_set_perturbation(ilqr_hip_ctx* c, int n_sets, const double* sigma, int hold, unsigned long long seed, unsigned long long stream0) {
+  if (!c || !sigma || hold < 1) return ILQR_ERR_ARG;
+  TRY(groups_on(c, false));
+  if (n_sets != 1 && n_sets != c->grp.G) return ILQR_ERR_ARG;
+  for (int i = 0; i < n_sets * ILQR_NU; ++i) if (!std::isfinite(sigma[i]) || sigma[i] < 0.0 || (n_sets > 1 && i < ILQR_NU && sigma[i] != 0.0)) return ILQR_ERR_ARG;
+  if (!c->grp.sigma) HIPCHK(c, hipMalloc((void**)&c->grp.sigma, (size_t)c->grp.G * ILQR_NU * sizeof(double)));
+  TRY(upload_rows(c, c->grp.sigma, sigma, (size_t)n_sets, ILQR_NU, ILQR_NU));
+  c->grp.sets = n_sets; c->grp.hold = hold; c->grp.seed = seed; c->grp.stream0 = stream0; c->grp.draws = 0;
+  return ILQR_OK;
+}
+int ilqr_hip_group_clear_perturbation(ilqr_hip_ctx* c) { if (!c) return ILQR_ERR_ARG; enter(c); return groups_drop_perturbation(c); }
+long ilqr_hip_group_draws(const ilqr_hip_ctx* c) { return c ? c->grp.draws : -1L; }
+__attribute__((minsize)) int ilqr_hip_group_perturb(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  if (!c->initialized) { c->err = "group_perturb before initialize"; return ILQR_ERR_STATE; }
+  TRY(groups_on(c, false));
+  if (!c->grp.sigma) { c->err = "group_perturb without a perturbation (ilqr_hip_group_set_perturbation)"; return ILQR_ERR_STATE; }
+  TRY(enter_launching(c));
+  const ilqr::GroupPerturbDev Pd{c->grp.sigma, c->grp.sets, c->grp.hold, c->grp.seed, c->grp.stream0, (unsigned long long)c->grp.draws};
+  g_groups.perturb(c->S.ubar, &Pd, c->B, c->N, c->grp.G, c->stream);
+  // The members g >= 1 are rolled out from their new controls here (the incumbents keep every bit: the mask): iteration 0 of the next solve
+  // rolls every rollout out in front of the linearisation anyway (xbar_rolled = false: solve_order.h nominal_roll, ROLL_BEFORE in every launch
+  // order), but the cost a solve starts from -- what it reports for a rollout that accepts no step -- is taken from the trajectory as the
+  // solve finds it (k_solve_begin, ilqr.cpp:540), and that must be the trajectory of the perturbed controls: group_select reads it.
+  DevState Sg = c->S; Sg.active = c->grp.mask;
+  ilqr::launch_rollout(plan_of(c), Sg, c->P, ilqr::MASK_ACTIVE, 1, 0, Sg.Jbase, c->stream);
+  HIPCHK(c, hipGetLastError());
+  ++c->grp.draws;
+  c->xbar_rolled = false;
+  return ILQR_OK;
+}
+__attribute__((minsize)) int ilqr_hip_group_select(ilqr_hip_ctx* c, const double* key_device) {
+  if (!c) return ILQR_ERR_ARG;
+  TRY(groups_on(c, false));
+  if (!key_device && !c->solved) { c->err = "group_select on the solve's cost before a solve"; return ILQR_ERR_STATE; }
+  g_groups.select(key_device ? key_device : c->S.J, c->B, c->grp.G, c->grp.winner, c->grp.rec, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->grp.selected = true;
+  return ILQR_OK;
+}
+__attribute__((minsize)) int ilqr_hip_group_get_winners(ilqr_hip_ctx* c, int* winner, double* rec) {
+  if (!c) return ILQR_ERR_ARG;
+  TRY(groups_on(c, true));
+  const size_t M = (size_t)(c->B / c->grp.G);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (winner) HIPCHK(c, hipMemcpy(winner, c->grp.winner, M * sizeof(int), hipMemcpyDeviceToHost));
+  if (rec) HIPCHK(c, hipMemcpy(rec, c->grp.rec, M * 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return ILQR_OK;
+}
+int ilqr_hip_group_winners_device(ilqr_hip_ctx* c, const int** winner_device, const double** rec_device) {
+  if (!c) return ILQR_ERR_ARG;
+  TRY(groups_on(c, false));
+  if (winner_device) *winner_device = c->grp.winner;
+  if (rec_device) *rec_device = c->grp.rec;
+  return ILQR_OK;
+}
+int ilqr_hip_group_copy_winners_device(ilqr_hip_ctx* c, int* winner_out_device) {
+  if (!c || !winner_out_device) return ILQR_ERR_ARG;
+  TRY(groups_on(c, true));
+  HIPCHK(c, hipMemcpyAsync(winner_out_device, c->grp.winner, (size_t)(c->B / c->grp.G) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  return ILQR_OK;
+}
+// The slabs of a rollout's solution state: what a later call reads about a solved rollout.  Not here: linearisation, quadratics, value function,
+// candidates, lin_dump (iteration 0 of the next solve recomputes them for every rollout) and the diagnostic history (traces, lists, counters).
+__attribute__((minsize)) int ilqr_hip_group_adopt(ilqr_hip_ctx* c) {
+  if (!c) return ILQR_ERR_ARG;
+  TRY(groups_on(c, true));
+  const size_t N = c->N, D = sizeof(double);
+  const DevState& S = c->S;
+  ilqr::GroupSlabs T{};
+  bool ok = true;
+  const auto add = [&](void* p, size_t bytes) { ok = ilqr::group_slabs_add(T, p, bytes) && ok; };
+  add(S.x0, ILQR_NX * D); add(S.xbar, (N + 1) * ILQR_NX * D); add(S.ubar, N * ILQR_NU * D); add(S.K, N * ILQR_NU * ILQR_NX * D); add(S.kff, N * ILQR_NU * D);
+  add(S.J, D); add(S.lambda, D); add(S.iters, sizeof(int));
+  if (c->P.al) {
+    add(c->al.jc.store, al_store_doubles(c, c->al.jc) * D); add(c->al.viol, 2 * D); add(c->al.done, sizeof(int));
+    if (c->P.als) { add(c->al.st.store, al_store_doubles(c, c->al.st) * D); add(c->al.sviol, D); }
+    if (c->P.alt) { add(c->al.tk.store, al_store_doubles(c, c->al.tk) * D); add(c->al.tviol, D); }
+  }
+  if (!ok) { c->err = "group_adopt: the slab table is full"; return ILQR_ERR_HIP; }
+  g_groups.adopt(&T, c->grp.winner, c->B, c->grp.G, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->xbar_rolled = false;      // (as after a solve: every other host-side fact describes buffers this call does not write)
   return ILQR_OK;
 }
 

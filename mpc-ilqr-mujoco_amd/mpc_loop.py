@@ -82,6 +82,16 @@ joint and rollout (BatchedILQR.plant_set_actuator).  The log and the score keep 
 or [B, 5] (scenario.stack_plant_terrain) is a height under the left and the right foot, an edge in x behind which the height holds and the
 window of plant intervals it holds in, counted from the reset of the run (BatchedILQR.plant_set_terrain), installed behind the joints, in
 front of the reset.  The plant's feet land and lift against that floor; the solve and the score's schedule know nothing of it.
+
+`MPCRunner(..., resident=True, starts=G, start_sigma=S, start_hold=1, start_seed=0)` spends the batch on B / G robots: the batch is cut into
+solve groups of G consecutive rollouts (BatchedILQR.set_groups) that share x0, references and plant tables -- the caller repeats them with
+scenario.repeat_for_groups -- and every solve runs  warm start -> group_perturb -> solve -> group_select -> group_adopt -> plant call:  the
+members g >= 1 start from the shifted previous solution plus S o z (S a scalar, [19] or [G, 19], scenario.stack_group_sigma; one draw per
+`start_hold` knots), member 0 from the shifted solution itself, and the member with the lowest solve cost drives all G plants of its group,
+which therefore stay bit-identical.  The cold start is perturbed too, behind `initialize`.  Nothing synchronises but the solve; the winners of
+every solve are logged on the device and `runner.winners` [solves, B / G] (global rollout indices) is downloaded once when the run ends.
+starts > 1 is refused on the host-plant path and together with plant_observation / plant_actuator, whose streams are per rollout: the members of
+a group would measure different states.  starts = 1: exactly the calls of a runner without it.
 """
 import os
 import time
@@ -128,7 +138,25 @@ class MPCRunner:
                  resident=False, substeps=1, feedback_mode=0, solve_every=1, score=None, history_rows=None,
                  device_refs=False, track_starts=None, task_score=None, plant_params=None, plant_model=None, plant_wrench=None, plant_payload=None,
                  plant_observation=None, observation_seed=0, observation_stream0=0, plant_actuator=None, actuator_seed=0, actuator_stream0=0, plant_joints=None,
-                 plant_terrain=None):
+                 plant_terrain=None, starts=1, start_sigma=None, start_hold=1, start_seed=0):
+        self.starts = int(starts)
+        if self.starts < 1:
+            raise ValueError("starts must be >= 1 and divide the batch")
+        if self.starts > 1:
+            if solver.B % self.starts:
+                raise ValueError("starts must be >= 1 and divide the batch")
+            if not resident:
+                raise ValueError("starts > 1 needs the device-resident plant (resident=True)")
+            if plant_observation is not None or plant_actuator is not None:
+                raise ValueError("starts > 1 together with plant_observation / plant_actuator is not supported: their streams are per rollout, the members of a group would measure different states")
+            if start_sigma is None:
+                raise ValueError("starts > 1 needs start_sigma (a scalar, [19] or [starts, 19]: scenario.stack_group_sigma)")
+            start_sigma = np.asarray(start_sigma, dtype=np.float64)
+            start_sigma = np.broadcast_to(start_sigma, (1, NU)).copy() if start_sigma.ndim < 2 else start_sigma
+            if start_sigma.shape not in ((1, NU), (self.starts, NU)) or int(start_hold) < 1:
+                raise ValueError("start_sigma must be a scalar, [19], [1, 19] or [starts, 19], start_hold >= 1")
+        self.start_sigma, self.start_hold, self.start_seed = start_sigma, int(start_hold), int(start_seed)
+        self.winners = None
         if plant_contacts not in ("schedule", "geometry"):
             raise ValueError("plant_contacts must be 'schedule' or 'geometry'")
         if not resident and (int(substeps) != 1 or int(feedback_mode) != 0):
@@ -373,6 +401,13 @@ class MPCRunner:
             self.track_ready = True
         start_of = lambda b: int(self.track_starts[b if len(self.track_starts) > 1 else 0])
         rows = []                                            # per plant interval: (cost, ms, x_ref_j, u_ref_j, x_opt_j, u_opt_j)
+        win_log = None
+        if self.starts > 1:                                  # solve groups: the perturbation, and one row of winners per solve on the device
+            import torch
+            s.set_groups(self.starts)
+            s.group_set_perturbation(self.start_sigma, hold=self.start_hold, seed=self.start_seed)
+            win_log = torch.zeros(((steps + m - 1) // m, s.num_groups()), dtype=torch.int32, device="cuda:%d" % getattr(s, "device", 0))
+            torch.cuda.synchronize()                         # (torch's stream is not the handle's: the zeros are there before the first copy)
         for k in range(0, steps, m):
             cnt = min(m, steps - k)                          # plant intervals of this group
             t0 = time.perf_counter()
@@ -394,13 +429,21 @@ class MPCRunner:
                     s.initialize_warm_from_plant()           # ilqr.cpp:68-80, x0 from the plant on the device
                 else:
                     s.initialize_warm_from_plant(shift=self.since_solve)
+                if win_log is not None:
+                    s.group_perturb()
                 t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
                 self.last_cost = s.solve(None)
             else:                                            # the gravity-compensation guess is computed on the host from x0
                 xm = x0 if self.plant_observation is None else s.plant_get_observed()      # (the measurement of interval 0: the plant was reset to x0)
                 s.initialize(xm, u_init)
+                if win_log is not None:
+                    s.group_perturb()
                 t2 = time.perf_counter(); self._add("MPC_warmStart", t1, t2)
                 self.last_cost = s.solve(xm)
+            if win_log is not None:                          # enqueued behind the solve: the winner's solution drives every plant of its group
+                s.group_select()
+                s.group_adopt()
+                s.group_copy_winners_device(win_log[k // m].data_ptr())
             t3 = time.perf_counter(); self._add("MPC_iLQR_solve", t2, t3)
             if self.profile_stages:
                 self._add_stage_ms()
@@ -428,6 +471,8 @@ class MPCRunner:
                     rows.append((self.last_cost.copy(), ms, xr, ur, xb[:, j].copy(), ub[:, j].copy()))
             self._add("MPC_stepOnce", t0, time.perf_counter())
         hx, hu = s.plant_history()                           # ONE download for the whole run
+        if win_log is not None:
+            self.winners = win_log.cpu().numpy()             # (behind plant_history's synchronisation of the handle's stream)
         xs = np.concatenate([hx, s.plant_state()[None]], axis=0)
         t_first = self.t_idx - steps
         gone = steps - len(hx)                               # intervals a ring of history_rows < steps has overwritten: not logged

@@ -648,6 +648,36 @@ def stack_plant_terrain(records, B):
     return out
 
 
+def repeat_for_groups(table, G):
+    """A per-problem table or stacked window [M, ...] repeated for solve groups of G members, member-minor: [M G, ...] whose rows m G .. m G + G - 1
+    are row m (BatchedILQR.set_groups: the members of a group share x0, references, schedule and plant tables)."""
+    G = int(G)
+    if G < 1:
+        raise ValueError("G must be >= 1")
+    table = np.asarray(table)
+    if table.ndim < 1:
+        raise ValueError("a table has a leading axis of problems")
+    return np.ascontiguousarray(np.repeat(table, G, axis=0))
+
+
+def stack_group_sigma(G, base, ladder=None):
+    """The perturbation table [G, 19] of BatchedILQR.group_set_perturbation: row 0 zeros (the incumbent), row g = base * ladder[g - 1].
+    base: a scalar or [19] standard deviations per actuator (Nm); ladder [G - 1] factors, by default geometric, 2 ** (g - 1): each member
+    searches twice as far from the incumbent as the one before it."""
+    G = int(G)
+    if G < 1:
+        raise ValueError("G must be >= 1")
+    base = np.broadcast_to(np.asarray(base, dtype=np.float64), (19,))
+    ladder = 2.0 ** np.arange(G - 1) if ladder is None else np.asarray(ladder, dtype=np.float64)
+    if ladder.shape != (G - 1,):
+        raise ValueError("ladder must have G - 1 entries")
+    out = np.zeros((G, 19))
+    out[1:] = ladder[:, None] * base[None, :]
+    if not np.all(np.isfinite(out)) or np.any(out < 0.0):
+        raise ValueError("sigmas must be finite and >= 0")
+    return out
+
+
 def _axis_angle_quat(w):
     ang = np.linalg.norm(w, axis=-1, keepdims=True)
     half = 0.5 * ang

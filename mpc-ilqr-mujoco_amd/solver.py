@@ -75,7 +75,11 @@ EXPORTS = [
     "ilqr_hip_plant_set_joints", "ilqr_hip_plant_get_joints", "ilqr_hip_step_joints",
     "ilqr_hip_plant_set_terrain", "ilqr_hip_plant_clear_terrain", "ilqr_hip_plant_num_terrain_sets", "ilqr_hip_plant_get_terrain", "ilqr_hip_step_terrain",
     "ilqr_hip_terrain_stance",
+    "ilqr_hip_set_groups", "ilqr_hip_num_groups", "ilqr_hip_group_set_perturbation", "ilqr_hip_group_clear_perturbation", "ilqr_hip_group_draws",
+    "ilqr_hip_group_perturb", "ilqr_hip_group_select", "ilqr_hip_group_get_winners", "ilqr_hip_group_winners_device", "ilqr_hip_group_copy_winners_device", "ilqr_hip_group_adopt",
 ]
+# slots of a group record (include/ilqr_hip.h ilqr_hip_group_select)
+GROUP_RECORD = ("winner_key", "incumbent_key", "finite_keys", "largest_finite_key")
 # the items of a problem dict that are reference windows (one set, or one per rollout)
 REFERENCE_KEYS = ("x_ref", "u_ref", "com_ref", "stance", "ee_ref", "com_vel_ref")
 # slots of the closed-loop score record (include/ilqr_hip.h ILQR_PLANT_SCORE_TERMS)
@@ -274,7 +278,7 @@ class BatchedILQR:
 
     def __init__(self, batch, N=25, dt=0.02, device=0, lib_path=None):
         self.L = load_library(lib_path)
-        self.B, self.N, self.dt = int(batch), int(N), float(dt)
+        self.B, self.N, self.dt, self.device = int(batch), int(N), float(dt), int(device)
         self.max_iter = 10
         h = C.c_void_p()
         rc = self.L.ilqr_hip_create(C.byref(h), int(device), self.B, self.N, C.c_double(self.dt))
@@ -1364,6 +1368,72 @@ class BatchedILQR:
         keys = ["iLQR_computeCost+forwardRollout", "iLQR_linearization", "iLQR_costQuadratics", "iLQR_backwardPass", "iLQR_lineSearch", "iLQR_control",
                 "iLQR_backwardPass_retry", "iLQR_lineSearch_retry"]
         return dict(zip(keys, ms)), dict(zip(keys, n))
+
+    # ---- solve groups: several starts per problem, the best one adopted on the device (include/ilqr_hip.h "solve groups")
+    def set_groups(self, G):
+        """Cut the batch into B / G groups of G consecutive rollouts that solve one problem from G starts; G = 1 switches groups off
+        (ilqr_hip_set_groups).  Removes an installed perturbation."""
+        G = int(G)
+        if G < 1 or self.B % G:
+            raise ValueError("G must be >= 1 and divide the batch")
+        self._chk(self.L.ilqr_hip_set_groups(self.h, G))
+        self.G = G
+
+    def num_groups(self):
+        """Groups of the handle, 0 while the feature is off."""
+        return int(self.L.ilqr_hip_num_groups(self.h))
+
+    def group_set_perturbation(self, sigma, hold=1, seed=0, stream0=0):
+        """sigma [19] or [1, 19] (every member g >= 1) or [G, 19] (row g for member g, row 0 zeros; scenario.stack_group_sigma): the standard
+        deviation per actuator of what group_perturb adds to the controls of the members g >= 1, one draw per `hold` knots
+        (ilqr_hip_group_set_perturbation).  Sets the draw counter to 0."""
+        sigma = np.atleast_2d(_c64(sigma))
+        if sigma.ndim != 2 or sigma.shape[1] != NU:
+            raise ValueError("sigma must be [19], [1, 19] or [G, 19]")
+        self._chk(self.L.ilqr_hip_group_set_perturbation(self.h, int(sigma.shape[0]), _p(sigma), int(hold), C.c_ulonglong(int(seed)), C.c_ulonglong(int(stream0))))
+
+    def group_clear_perturbation(self):
+        self._chk(self.L.ilqr_hip_group_clear_perturbation(self.h))
+
+    def group_draws(self):
+        """group_perturb calls since the perturbation was installed: the draw the next call uses."""
+        fn = self.L.ilqr_hip_group_draws
+        fn.restype = C.c_long
+        return int(fn(self.h))
+
+    def group_perturb(self):
+        """Enqueue the perturbation of the starts: ubar of every member g >= 1 gets sigma o z, member 0 keeps every bit (ilqr_hip_group_perturb)."""
+        self._chk(self.L.ilqr_hip_group_perturb(self.h))
+
+    def group_select(self, key=None):
+        """Enqueue the selection: per group the member with the smallest finite key, ties to the lowest member.  key: None (the cost of the
+        last solve), a torch tensor [B] of doubles on the handle's device, or a device pointer to such an array (ilqr_hip_group_select)."""
+        if key is not None and hasattr(key, "data_ptr"):
+            if str(key.dtype) != "torch.float64" or key.numel() != self.B or not key.is_contiguous() or not key.is_cuda:
+                raise ValueError("key must be a contiguous float64 device tensor of B entries")
+            key = key.data_ptr()
+        self._chk(self.L.ilqr_hip_group_select(self.h, C.c_void_p(key)))
+
+    def group_winners(self):
+        """(winner [M] global rollout indices, rec [M, 4] columns GROUP_RECORD) of the last group_select; synchronises."""
+        M = self.num_groups()
+        winner, rec = np.zeros(M, dtype=np.int32), np.zeros((M, 4))
+        self._chk(self.L.ilqr_hip_group_get_winners(self.h, winner.ctypes.data_as(_ip), _p(rec)))
+        return winner, rec
+
+    def group_winners_device(self):
+        """Device pointers (winner [M] ints, rec [M][4] doubles), without synchronising."""
+        w, r = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.ilqr_hip_group_winners_device(self.h, C.byref(w), C.byref(r)))
+        return w.value, r.value
+
+    def group_copy_winners_device(self, out_ptr):
+        """Enqueue a copy of winner [M] into a caller-owned device array of M ints (a row of a per-step log); no synchronisation."""
+        self._chk(self.L.ilqr_hip_group_copy_winners_device(self.h, C.c_void_p(out_ptr)))
+
+    def group_adopt(self):
+        """Enqueue the adoption: every member of a group receives the solution state of its group's winner, bit for bit (ilqr_hip_group_adopt)."""
+        self._chk(self.L.ilqr_hip_group_adopt(self.h))
 
     @property
     def stream(self):
